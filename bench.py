@@ -7,9 +7,14 @@ CNN -> species head, raw logits out) over one batch of synthetic 3 s / 48 kHz cl
 256 clips of BASELINE.json configs[1] ("BirdNET v2.4 fp32, batch 256x3s@48kHz synthetic sine+noise"), at
 N > 1 the 1024 clips per GPU of configs[2] ("batch 8192 clips sharded 8xMI355X"; a `weak_256` leg keeps
 the 256-per-GPU figure comparable with the N = 1 line, `host_pointer_per_rank` measures the PCIe- and
-host-staging-inclusive rate with every rank ingesting at once).  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0 with `roofline` (dominant
-kernel, measured with HIP events on the launch stream inside the timed region) and `cpu_baseline`
-(the numpy/BLAS oracle restatement timed on this box's host cores; N=1 only).
+host-staging-inclusive rate with every rank ingesting at once).  Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).
+`--full` adds everything else to the line: `roofline` (dominant kernel, measured with HIP events on the launch stream inside the
+timed region), the finite / small-batch / oracle checks, `step_distribution`, `fp32_mfma_only`, `host_pointer`, `cpu_baseline`
+(the numpy/BLAS oracle restatement timed on this box's host cores; N=1 only), the `secondary` bat / Perch legs and, at N > 1,
+`weak_256` and `host_pointer_per_rank`.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy; the
+inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -50,11 +55,38 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true", help="skip the bat / Perch legs attached to the headline line as `secondary`")
     ap.add_argument("--no-distribution", action="store_true", help="skip the per-step distribution run (>= 40 extra steps)")
     ap.add_argument("--no-host-pointer", action="store_true", help="skip the host_pointer leg (rates through the blocking host-pointer entries)")
-    ap.add_argument("--detail", action="store_true", help="print a per-launch table to stderr")
+    ap.add_argument("--detail", action="store_true", help="print a per-launch table to stderr (needs --full: per-kernel timing)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: per-kernel timing and roofline, "
+                    "finite / small-batch / oracle checks, step distribution, fp32-MFMA run, host-pointer rates, CPU baseline, "
+                    "bat / Perch legs (N > 1: weak_256, host_pointer_per_rank); each can still be turned off by its --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32 / float64; rows sampled with a fixed seed if the arrays exceed 64 MB)")
     ap.add_argument("--depth", type=int, default=2, help="engine pipeline depth: successive batches run on alternating "
                     "contexts (own stream + activation arena) so one batch's tail overlaps the next one's head; 1 = off "
                     "(then each batch is split over two concurrent lanes instead)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: `arrays` = {name: host array of the last timed step, rows = clips}, written as <dirname>/<name>.npy in float32
+    (float64 stays float64).  Over `limit` bytes in all, the same rows of every array are kept: a sorted sample drawn with a fixed
+    seed, so two runs with the same arguments write the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    rows = {a.shape[0] for a in arrays.values()}
+    total = sum(a.nbytes for a in arrays.values())
+    limit -= 1024 * len(arrays)                                  # (room for the .npy headers)
+    if total > limit:
+        assert len(rows) == 1, rows
+        n = rows.pop()
+        keep = max(1, int(n * limit // total))
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
 
 
 def lib_digest():
@@ -419,22 +451,36 @@ def main_bat(args):
     for _ in range(max(args.warmup, 1)):
         step()
     torch.cuda.synchronize(dev)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    ev[0].record(stream)
-    lib.bnhip_us_frame_cv_device(0, pcm.data_ptr(), 1, B, cfg.n_samples, 256000, 8192, 4096, 20000, scratch.data_ptr(), cv.data_ptr(),
-                                 stream.cuda_stream)
-    ev[1].record(stream)
-    backbone.predict_device(x.data_ptr(), B, logits.data_ptr(), emb.data_ptr())
-    ev[2].record(stream)
-    head.predict_device(emb.data_ptr(), B, scores.data_ptr())
-    ev[3].record(stream)
-    torch.cuda.synchronize(dev)
-    stage_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
+    if args.full:
+        # per-stage times: one more (untimed) step bracketed stage by stage
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record(stream)
+        lib.bnhip_us_frame_cv_device(0, pcm.data_ptr(), 1, B, cfg.n_samples, 256000, 8192, 4096, 20000, scratch.data_ptr(), cv.data_ptr(),
+                                     stream.cuda_stream)
+        ev[1].record(stream)
+        backbone.predict_device(x.data_ptr(), B, logits.data_ptr(), emb.data_ptr())
+        ev[2].record(stream)
+        head.predict_device(emb.data_ptr(), B, scores.data_ptr())
+        ev[3].record(stream)
+        torch.cuda.synchronize(dev)
+        stage_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frame_cv": cv.cpu().numpy(), "logits": logits.cpu().numpy(), "embeddings": emb.cpu().numpy(),
+                                         "scores": scores.cpu().numpy()})
+    out = {"metric": "0.5625s-256kHz bat clips/sec (1 GPU): frame-CV gate + backbone embedding + regional head", "value": B * args.steps / dt,
+           "unit": "clips/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 (gate: f64)", "data": "synthetic FM chirps "
+           "(SURVEY 8d cfg 4), random-init weights",
+           "config": {"workload": "BASELINE configs[3]: BattyBirdNET, 256 kHz input, batch %d x 144000 samples, int16 + float32 resident in HBM" % B,
+                      "batch_per_gpu": B, "head_classes": n_cls, "head_container": "onnx"}}
+    if not args.full:
+        backbone.close(); head.close()
+        return out
     # parity of the timed configuration's own output against the CPU restatements (two clips, outside the timed region)
     from oracle import gofuncs as G, onnx_interp
     from oracle.interp import Interpreter
@@ -448,16 +494,10 @@ def main_bat(args):
     sc_err = float(np.abs(sg(scores[rows].cpu().numpy()) - sg(sc_ref)).max())
     # algorithmic work of the gate: frames x 5 N log2 N flops on complex128, 2 bytes in per sample
     fft_flops = B * frames * 5.0 * 8192 * 13
-    out = {"metric": "0.5625s-256kHz bat clips/sec (1 GPU): frame-CV gate + backbone embedding + regional head", "value": B * args.steps / dt,
-           "unit": "clips/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 (gate: f64)", "data": "synthetic FM chirps "
-           "(SURVEY 8d cfg 4), random-init weights",
-           "config": {"workload": "BASELINE configs[3]: BattyBirdNET, 256 kHz input, batch %d x 144000 samples, int16 + float32 resident in HBM" % B,
-                      "batch_per_gpu": B, "head_classes": n_cls, "head_container": "onnx"},
-           "stages_ms": {"us_frame_cv": stage_ms[0], "backbone": stage_ms[1], "head": stage_ms[2]},
-           "us_frame_cv": {"frames_per_clip": frames, "gflops_f64": fft_flops / 1e9,
-                           "tflops_f64": fft_flops / (stage_ms[0] * 1e-3) / 1e12, "input_gbs": B * cfg.n_samples * 2 / (stage_ms[0] * 1e-3) / 1e9},
-           "max_rel_cv_diff_vs_go_restatement": cv_err, "max_abs_score_diff_vs_oracle": sc_err}
+    out.update({"stages_ms": {"us_frame_cv": stage_ms[0], "backbone": stage_ms[1], "head": stage_ms[2]},
+                "us_frame_cv": {"frames_per_clip": frames, "gflops_f64": fft_flops / 1e9,
+                                "tflops_f64": fft_flops / (stage_ms[0] * 1e-3) / 1e12, "input_gbs": B * cfg.n_samples * 2 / (stage_ms[0] * 1e-3) / 1e9},
+                "max_rel_cv_diff_vs_go_restatement": cv_err, "max_abs_score_diff_vs_oracle": sc_err})
     backbone.close(); head.close()
     return out
 
@@ -693,20 +733,21 @@ def run_model(args):
         step_no[0] += 1
         clf.predict_device(xs[k].data_ptr(), B, outs[k].data_ptr())
 
-    # warm-up: W untimed steps.  The last one is bracketed launch-by-launch to find the dominant kernel class and
+    # warm-up: W untimed steps.  With --full the last one is bracketed launch-by-launch to find the dominant kernel class and
     # the per-class breakdown; the TIMED region then brackets only that class (bracketing every launch costs ~7 %
-    # of a step because each event is a kernel boundary; one class costs ~1 %).
+    # of a step because each event is a kernel boundary; one class costs ~1 %).  A plain run brackets nothing.
+    profile = args.full and not args.no_profile
     for _ in range(max(args.warmup - 1, 0)):
         step()
     torch.cuda.synchronize(dev)
     warm_prof, prof_steps = [], []
-    if not args.no_profile:
+    if profile:
         clf.profile_filter(None)
         clf.profile_enable(True)
     if args.warmup > 0:
         step()
     torch.cuda.synchronize(dev)
-    if not args.no_profile:
+    if profile:
         warm_prof, prof_steps = clf.profile_read(per_step=True)
         if warm_prof:
             clf.profile_filter(max(warm_prof, key=lambda r: r["ms"])["kernel"])
@@ -720,20 +761,25 @@ def run_model(args):
     if use_dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    prof = clf.profile_read() if not args.no_profile else []
+    if args.dump_outputs and args.steps > 0:
+        # the logits of the last timed step: this rank's clips (N > 1: one file per rank, the 64 MB shared out among them)
+        last = outs[(step_no[0] - 1) % NSETS].cpu().numpy()
+        dump_outputs(args.dump_outputs, {"logits" if world == 1 else f"logits_rank{rank}": last}, DUMP_LIMIT_BYTES // world)
+    prof = clf.profile_read() if profile else []
     if args.detail and rank == 0:
         for r in prof_steps:
             ms = r["ms"] / r["launches"]
             print(f"{r['step']:3d} {r['kernel']:12s} {r['name']:28s} {ms * 1e3:8.1f} us  "
                   f"{r['flops'] / r['launches'] / (ms * 1e-3) / 1e12:6.1f} TF  {r['bytes'] / r['launches'] / (ms * 1e-3) / 1e9:7.0f} GB/s",
                   file=sys.stderr)
-    clf.profile_enable(False)
+    if profile:
+        clf.profile_enable(False)
     # per-step distribution (>= 30 batches, median + p95, like cmd/perch-benchmark/main.go:31-32,354-391): a second,
     # untimed-by-contract run of >= 40 steps with ONE event pair per step on the stream the step runs on.  With two contexts
     # in flight the steps overlap, so two figures: the interval between consecutive completions (what throughput is made of)
     # and each step's own start-to-end latency.
     dist_stats = None
-    if rank == 0 and not args.no_distribution:
+    if rank == 0 and args.full and not args.no_distribution:
         nd = max(40, args.steps)
         clf.profile_steps(True)
         for _ in range(nd):
@@ -757,10 +803,43 @@ def run_model(args):
     dt, rank_rates, rccl_ranks = dist_timing(dt, B, args.steps, use_dist, dev)
     # N > 1 (every rank takes part; rank 0 reports): the 256-per-GPU figure of the N = 1 line, and the ingest legs
     weak_256 = ingest = None
-    if world > 1 and not perch and default_batch and B != 256:
+    if world > 1 and args.full and not perch and default_batch and B != 256:
         weak_256 = weak_leg(blob, gpu, depth, args, xs, 256, use_dist, dev, stream)
-    if world > 1 and not perch and not args.no_host_pointer:
+    if world > 1 and args.full and not perch and not args.no_host_pointer:
         ingest = ranks_host_pointer(blob, gpu, args, x_host[:256], use_dist, dev)
+
+    headline = None
+    if rank == 0:
+        headline = {
+            "metric": ("5s-32kHz clips/sec (whole node) + max-abs softmax diff vs the fp32 oracle, Perch-v2-dimension stand-in" if perch else
+                       "3s-48kHz clips/sec (whole node) + max-abs prob diff vs TFLite, BirdNET v2.4"), "value": B * world * args.steps / dt, "unit": "clips/s",
+            "n_gpus": world, "rccl_ranks": rccl_ranks, "per_rank_clips_per_s": rank_rates, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "bf16 MFMA operands, f32 accumulate and storage" if args.precision == "bf16" else "f32",
+            "data": ("synthetic sine+noise clips at 32 kHz; random-init weights of a Perch-v2-DIMENSION stand-in (synth_model.perch_config: "
+                     "the real artefact is ONNX, absent from the snapshot, and its graph is unknown here)") if perch else
+                    "synthetic sine+noise clips (SURVEY 8d cfg 2); random-init BirdNET-v2.4-topology weights "
+                    "(real .tflite absent from the reference snapshot)",
+            "config": {"workload": ("BASELINE configs[4]: Google Perch v2 dimensions (14,795-class head), batch 512 x 5 s @ 32 kHz per GPU "
+                                    "(4096 over 8), log-mel front-end + EfficientNet-B3-shaped CNN + head on device, raw logits out")
+                                   if perch else
+                                   (f"BASELINE configs[2]: BirdNET v2.4 fp32, batch {B * world} clips sharded over {world} x MI355X ({B} per GPU), "
+                                    "weights broadcast once over RCCL, mel front-end + CNN + head on device, raw logits out"
+                                    if world > 1 and B == 1024 else
+                                    f"BASELINE configs[1]: BirdNET v2.4 fp32, batch {B} x 3 s @ 48 kHz per GPU, "
+                                    "mel front-end + CNN + head on device, raw logits out"),
+                       "inputs": "device-resident (device-only): the clips are in HBM when the timed region starts; rates through the "
+                                 "blocking host-pointer entries (PCIe-inclusive) are in `host_pointer`",
+                       "batch_per_gpu": B, "n_samples": cfg.n_samples, "n_classes": clf.num_species(),
+                       "sharding": f"clips index-contiguous over {world} rank(s); weights broadcast once",
+                       "pipeline_depth": depth, "input_sets": NSETS},
+        }
+    if not args.full:
+        # a plain run: the headline and nothing else (the checks, per-kernel figures and other legs are --full's)
+        clf.close()
+        if use_dist:
+            dist.destroy_process_group()
+        return headline
 
     ok = all(bool(torch.isfinite(o).all().item()) for o in outs[:min(NSETS, args.steps + args.warmup)])
     # set 0 was last computed inside (or, for short runs, before) the timed region by the same engine: checks below use it
@@ -795,35 +874,13 @@ def run_model(args):
         if not (prob_diff <= (2e-2 if args.precision == "bf16" else 1e-4) and top1_same):
             print(f"[bench] PARITY CHECK FAILED: max-abs prob diff vs oracle {prob_diff}, top-1 identical {top1_same}", file=sys.stderr)
     if rank == 0:
-        total_clips = B * world * args.steps
-        out = {
-            "metric": ("5s-32kHz clips/sec (whole node) + max-abs softmax diff vs the fp32 oracle, Perch-v2-dimension stand-in" if perch else
-                       "3s-48kHz clips/sec (whole node) + max-abs prob diff vs TFLite, BirdNET v2.4"), "value": total_clips / dt, "unit": "clips/s",
+        out = dict(headline)
+        out.update({
             "max_abs_prob_diff_vs_oracle": prob_diff, "top1_identical_vs_oracle": top1_same,
             "prob_diff_reference": f"oracle restatement of the TFLite float op semantics on rows {oracle_rows} of the timed batch "
                                    "(tolerance 1e-4; no TFLite runtime or real weights exist in this environment)",
-            "n_gpus": world, "rccl_ranks": rccl_ranks, "per_rank_clips_per_s": rank_rates, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16 MFMA operands, f32 accumulate and storage" if args.precision == "bf16" else "f32",
-            "data": ("synthetic sine+noise clips at 32 kHz; random-init weights of a Perch-v2-DIMENSION stand-in (synth_model.perch_config: "
-                     "the real artefact is ONNX, absent from the snapshot, and its graph is unknown here)") if perch else
-                    "synthetic sine+noise clips (SURVEY 8d cfg 2); random-init BirdNET-v2.4-topology weights "
-                    "(real .tflite absent from the reference snapshot)",
-            "config": {"workload": ("BASELINE configs[4]: Google Perch v2 dimensions (14,795-class head), batch 512 x 5 s @ 32 kHz per GPU "
-                                    "(4096 over 8), log-mel front-end + EfficientNet-B3-shaped CNN + head on device, raw logits out")
-                                   if perch else
-                                   (f"BASELINE configs[2]: BirdNET v2.4 fp32, batch {B * world} clips sharded over {world} x MI355X ({B} per GPU), "
-                                    "weights broadcast once over RCCL, mel front-end + CNN + head on device, raw logits out"
-                                    if world > 1 and B == 1024 else
-                                    f"BASELINE configs[1]: BirdNET v2.4 fp32, batch {B} x 3 s @ 48 kHz per GPU, "
-                                    "mel front-end + CNN + head on device, raw logits out"),
-                       "inputs": "device-resident (device-only): the clips are in HBM when the timed region starts; rates through the "
-                                 "blocking host-pointer entries (PCIe-inclusive) are in `host_pointer`",
-                       "batch_per_gpu": B, "n_samples": cfg.n_samples, "n_classes": clf.num_species(),
-                       "sharding": f"clips index-contiguous over {world} rank(s); weights broadcast once",
-                       "pipeline_depth": depth, "input_sets": NSETS},
             "finite_outputs": ok, "max_abs_logit_diff_vs_small_batch": consist, "consistent": bool(consist <= 1e-3),
-        }
+        })
         if dist_stats:
             out["step_distribution"] = dist_stats
         if weak_256:
@@ -967,7 +1024,7 @@ def run_model(args):
                          ("perch_bf16", {"workload": "perch", "steps": 8, "warmup": 2, "precision": "bf16"})):
             a2 = copy.copy(args)
             a2.batch = 0; a2.no_cpu_baseline = True; a2.no_fp32_run = True; a2.no_host_pointer = True; a2.no_secondary = True
-            a2.no_distribution = True; a2.detail = False
+            a2.no_distribution = True; a2.detail = False; a2.dump_outputs = None
             for k, v in kw.items():
                 setattr(a2, k, v)
             try:

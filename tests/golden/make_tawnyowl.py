@@ -26,3 +26,7 @@ back = np.cumsum(np.load(DST)["delta"].astype(np.int64)).astype(np.int64)
 back = ((back + 2**31) % 2**32 - 2**31).astype(np.int32)
 assert np.array_equal(back, pcm)
 print(DST, os.path.getsize(DST), "bytes")
+# the header bytes (RIFF, extensible fmt, fact and data chunk heads): header + PCM words rebuild the file byte for byte
+HDR = os.path.join(os.path.dirname(DST), "tawnyowl_header.bin")
+open(HDR, "wb").write(raw[:i + 8])
+print(HDR, i + 8, "bytes; whole file sha256", hashlib.sha256(raw).hexdigest())

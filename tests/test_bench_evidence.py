@@ -61,3 +61,26 @@ def test_baseline_batch_per_gpu():
     import bench
     assert [bench.baseline_batch("birdnet", n) for n in (1, 2, 4, 8)] == [256, 1024, 1024, 1024]
     assert [bench.baseline_batch("perch", n) for n in (1, 8)] == [512, 512]
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_rows_over_the_limit(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 kept) .npy per array; over the byte limit, the same seeded rows of every array,
+    the same on every call, and the files stay within the limit."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(5)
+    logits, cv = rng.normal(size=(300, 50)).astype(np.float16), rng.normal(size=300)
+    b.dump_outputs(str(tmp_path / "small"), {"logits": logits, "frame_cv": cv})
+    got = np.load(tmp_path / "small" / "logits.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, logits.astype(np.float32))
+    assert np.load(tmp_path / "small" / "frame_cv.npy").dtype == np.float64
+    limit = 40 * 1024
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"logits": logits, "frame_cv": cv}, limit=limit)
+    files = [tmp_path / d / f for d in ("a", "b") for f in ("logits.npy", "frame_cv.npy")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= limit
+    sl, sc = np.load(files[0]), np.load(files[1])
+    assert 0 < sl.shape[0] < 300 and sl.shape[0] == sc.shape[0]
+    assert np.array_equal(sl, np.load(files[2])) and np.array_equal(sc, np.load(files[3]))
+    rows = [int(np.flatnonzero((cv == v))[0]) for v in sc]                 # the sample keeps rows whole and in order
+    assert rows == sorted(rows) and np.array_equal(sl, logits[rows].astype(np.float32))

@@ -30,15 +30,16 @@ def tawnyowl_pcm32():
 
 def test_tawnyowl_fixture_is_intact():
     """CPU: the committed fixture decodes to the 720 000 PCM words of the reference's tawnyowl.wav (sha256 recorded when
-    tests/golden/make_tawnyowl.py ran against /root/reference), and frames into five 3 s clips."""
+    tests/golden/make_tawnyowl.py ran against the reference's file), the file rebuilt from the fixtures reads back through
+    wav.read_wav as the Go-restated conversion of those words, and it frames into five 3 s clips."""
     import hashlib
     from birdnet_go_amd import wav
+    from test_wav import tawnyowl_wav_bytes
     pcm = tawnyowl_pcm32()
     z = np.load(os.path.join(GOLD, "tawnyowl_pcm32.npz"))
     assert pcm.size == 720000 and hashlib.sha256(pcm.tobytes()).digest() == z["sha256"].tobytes()
-    if os.path.exists("/root/reference/tawnyowl.wav"):
-        s, rate, bits = wav.read_wav("/root/reference/tawnyowl.wav")
-        assert (rate, bits) == (48000, 32) and np.array_equal(s, G.pcm_to_f32(pcm.tobytes(), 32))
+    s, rate, bits = wav.read_wav(tawnyowl_wav_bytes())
+    assert (rate, bits) == (48000, 32) and np.array_equal(s, G.pcm_to_f32(pcm.tobytes(), 32))
     clips, starts = wav.frame_clips(G.pcm_to_f32(pcm.tobytes(), 32), 48000)
     assert clips.shape == (5, 144000) and list(starts) == [0.0, 3.0, 6.0, 9.0, 12.0]
 

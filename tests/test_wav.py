@@ -1,5 +1,5 @@
 """WAV ingest + framing (section 8f row 1), CPU only; conversion checked against the oracle's restatement
-of convert/pcm.go and, when the reference checkout is present (this container), against tawnyowl.wav."""
+of convert/pcm.go and against tawnyowl.wav, rebuilt byte for byte from the committed fixtures under tests/golden/."""
 import os
 import struct
 
@@ -64,9 +64,26 @@ def test_framing_overlap_and_tail():
         wav.frame_clips(x, 48000, 3.0, 3.0)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/tawnyowl.wav"), reason="reference checkout absent")
-def test_tawnyowl_is_five_clips():
-    s, rate, bits = wav.read_wav("/root/reference/tawnyowl.wav")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+TAWNY_SHA256 = "b3f272d2f4cf5e71f48b4696a82d05eec5995c779ac53345d29b1d74de2c390a"     # the reference's tawnyowl.wav, 2 880 080 bytes
+
+
+def tawnyowl_wav_bytes():
+    """The reference's tawnyowl.wav (WAVE_FORMAT_EXTENSIBLE, fmt + fact + data chunks), rebuilt from its 80 header bytes
+    (golden/tawnyowl_header.bin) and its PCM words (golden/tawnyowl_pcm32.npz, delta-coded); checked against the file's sha256."""
+    import hashlib
+    z = np.load(os.path.join(GOLD, "tawnyowl_pcm32.npz"))
+    acc = np.cumsum(z["delta"].astype(np.int64))
+    pcm = ((acc + 2**31) % 2**32 - 2**31).astype("<i4")
+    raw = open(os.path.join(GOLD, "tawnyowl_header.bin"), "rb").read() + pcm.tobytes()
+    assert hashlib.sha256(raw).hexdigest() == TAWNY_SHA256
+    return raw
+
+
+def test_tawnyowl_is_five_clips(tmp_path):
+    path = tmp_path / "tawnyowl.wav"
+    path.write_bytes(tawnyowl_wav_bytes())
+    s, rate, bits = wav.read_wav(str(path))
     assert (rate, bits, s.size) == (48000, 32, 720000)                # SURVEY 8c
     c, t = wav.frame_clips(s, rate)
     assert c.shape == (5, 144000) and np.abs(s).max() <= 1.0

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B in the pipelined bench: k_pw_ws as a tuner candidate (default) vs taken away (BNHIP_PW_WS=0), alternating, plus the serial engine
 cd $GRAFT_REPO_ROOT
-B="python bench.py --no-cpu-baseline --no-secondary --no-host-pointer --no-distribution --no-fp32-run --no-oracle-check --steps 40 --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-secondary --no-host-pointer --no-distribution --no-fp32-run --no-oracle-check --steps 40 --warmup 5"
 for i in 1 2; do
   timeout 200 $B > gpurun_out/ab_ws_on_$i.json 2> /dev/null
   BNHIP_PW_WS=0 timeout 200 $B > gpurun_out/ab_ws_off_$i.json 2> /dev/null

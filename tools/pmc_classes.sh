@@ -7,7 +7,7 @@ TAG=${1:-r06}
 PAT=${2:-k_expand_dw}
 OUT=$PWD/gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-PB="python bench.py --depth 1 --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-run --no-oracle-check --no-profile --no-host-pointer --no-secondary --no-distribution"
+PB="python bench.py --full --depth 1 --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-run --no-oracle-check --no-profile --no-host-pointer --no-secondary --no-distribution"
 DBS=""
 i=0
 for c in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU" "SQ_WAVES SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32" "SQ_WAVES SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64" "SQ_WAVES SQ_INSTS_VALU_CVT SQ_INSTS_LDS SQ_INSTS_VMEM" "SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES"; do

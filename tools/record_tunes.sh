@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out
 best=0; bestdir=
 for t in $(seq $TRIES); do
   D=/tmp/tune_try$t; rm -rf $D; mkdir -p $D
-  BNHIP_TUNE_DIR=$D BNHIP_TUNE_RECORD=1 python bench.py --no-cpu-baseline --no-distribution > /dev/null 2>&1
+  BNHIP_TUNE_DIR=$D BNHIP_TUNE_RECORD=1 python bench.py --full --no-cpu-baseline --no-distribution > /dev/null 2>&1
   BNHIP_TUNE_DIR=$D BNHIP_TUNE_RECORD=1 python bench.py --batch 1024 --steps 6 --no-cpu-baseline --no-secondary --no-host-pointer --no-fp32-run --no-distribution --no-oracle-check > /dev/null 2>&1
   v=0
   for r in 1 2; do
