@@ -1,4 +1,4 @@
-// Graph planner + executor: TFLite op graph -> fused gfx950 kernel plan.
+// Graph planner (planner.cpp) + executor (engine.cpp): TFLite op graph -> fused gfx950 kernel plan.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,6 +81,12 @@ struct FrontSpec {
 };
 
 struct ProfEntry { hipEvent_t a, b; int step; int n; };
+
+struct WeightPlan {                  // host half of the weight arena, made by the planner (planner.cpp), uploaded by Engine::bind_device
+    std::vector<float> img;          // the arena image (256-byte aligned pieces)
+    std::vector<size_t> step_w[4];   // per step: offsets of w0..w3 in img (SIZE_MAX = none)
+    std::vector<size_t> step_bx;     // per step: offset of the split-bf16 weight image (S_PW / S_EXPAND_DW of a bf16x3 engine)
+};
 
 class Engine {
   public:
@@ -223,6 +229,7 @@ class Engine {
     int lane_cap = 0;                   // clips one lane can hold (ceil(max_batch / n_lanes))
     size_t lane_bytes = 0;              // size of one lane's arena region
     hipEvent_t get_event();
+    bool bind_device(const WeightPlan& wp, std::string* err, int* code);   // device half of build(): arenas, upload, pointers
 };
 
 }  // namespace bnhip
