@@ -9,7 +9,10 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
 #include <condition_variable>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -24,6 +27,7 @@
 #include "hostpipe.h"
 #include "numa.h"
 #include "model_onnx.h"
+#include "resample_bank.h"
 #include "tflite_model.h"
 #include "windows.h"
 
@@ -1230,6 +1234,325 @@ int bnhip_resampler_flush_f32(bnhip_resampler* r, float* out, int out_cap, int* 
 void bnhip_resampler_destroy(bnhip_resampler* r) {
     try { resampler_free(r); } catch (...) {}
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ resampler bank
+// The rate fan-out of BufferConsumer.Write (internal/analysis/buffer_consumer.go:105-210: one stateful Resampler per
+// (source, non-native rate)) for every source of one (rate_in, rate_out) pair at once: one H2D copy (descriptors + packed
+// PCM16), one k_resample_bank launch, one D2H copy and one synchronise per call, on ONE HIP stream per bank.  Each stream's
+// filter history is a fixed pair of device slabs of H = T - 1 floats (keep_from = n0(i_end) - (T - 1) with n0(i_end) >=
+// n_total bounds it): the launch reads one slab and writes the new tail into the other, the host flips the parity on commit.
+struct bnhip_resampler_bank {
+    struct Stream {
+        bool live = false;
+        int parity = 0;                 // slab read by the next call
+        long long n_total = 0, i_next = 0, n_base = 0;
+        int n_hist = 0;
+    };
+    std::mutex mu;                      // calls on one bank are serialised
+    int device = 0, rate_in = 0, rate_out = 0, L = 1, M = 1, T = 0, half = 0, H = 1;
+    std::vector<Stream> st;
+    float* d_table = nullptr;
+    float* d_hist = nullptr;            // [max_streams][2][H]
+    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // descriptors | packed PCM16 (bytes)
+    int16_t* h_out = nullptr; int16_t* d_out = nullptr; size_t out_cap = 0;      // packed outputs (samples)
+    hipStream_t stream = nullptr;
+};
+
+namespace {
+
+void bank_free(bnhip_resampler_bank* b) {
+    if (!b) return;
+    hipSetDevice(b->device);
+    if (b->stream) { hipStreamSynchronize(b->stream); hipStreamDestroy(b->stream); }
+    for (void* p : {(void*)b->d_table, (void*)b->d_hist, b->d_stage, (void*)b->d_out}) if (p) hipFree(p);
+    for (void* p : {(void*)b->h_stage, (void*)b->h_out}) if (p) hipHostFree(p);
+    (void)hipGetLastError();
+    delete b;
+}
+
+long long bank_ready(const bnhip_resampler_bank* b, long long n_total) {      // = resampler_ready
+    long long num = n_total * b->L - b->half;
+    if (num <= 0) return 0;
+    return (num + b->M - 1) / b->M;
+}
+
+long long bank_estimate(const bnhip_resampler_bank* b, long long n_in) {     // = bnhip_resampler_estimate
+    return n_in <= 0 ? 0 : (n_in * b->L + b->M - 1) / b->M + 1;
+}
+
+// a page-locked host buffer and its device twin of at least `need` bytes; the old pair is freed only once the new one exists
+bool bank_grow(void** h, void** d, size_t* cap, size_t need) {
+    if (need <= *cap) return true;
+    const size_t c = std::max<size_t>(need + need / 2, 1 << 16);
+    void *nh = nullptr, *nd = nullptr;
+    if (hipHostMalloc(&nh, c, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipMalloc(&nd, c) != hipSuccess) { (void)hipGetLastError(); hipHostFree(nh); return false; }
+    if (*h) hipHostFree(*h);
+    if (*d) hipFree(*d);
+    *h = nh; *d = nd; *cap = c;
+    return true;
+}
+
+bool bank_stream_ok(const bnhip_resampler_bank* b, int s) { return s >= 0 && (size_t)s < b->st.size() && b->st[s].live; }
+
+// One call: frames f = 0..n_frames-1 of streams[f] (a stream may appear several times; its frames are consumed in call order),
+// or with flush != 0 the end of each listed stream.  Checks everything, stages everything, runs, synchronises, commits, then
+// hands frame f's outputs (in call order) to deliver(f, samples, count).  Until the commit nothing of any stream changes.
+template <class Deliver>
+int bank_run(bnhip_resampler_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, bool flush,
+             long long out_cap, Deliver deliver) {
+    if (n_frames < 0 || (n_frames > 0 && !streams)) return set_err(BNHIP_E_INVALID, "bad resampler bank arguments");
+    if (!flush && n_frames > 0 && !n_in) return set_err(BNHIP_E_INVALID, "n_in is NULL");
+    struct Group { int stream; long long n_in = 0, n_after = 0, i_end = 0, keep_from = 0; int in_off = 0, cnt = 0, out_off = 0, keep = 0; };
+    std::vector<Group> groups;
+    std::vector<int> group_of(b->st.size(), -1), frame_group(n_frames);
+    std::vector<long long> frame_cnt(n_frames);
+    long long need = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const int s = streams[f];
+        if (!bank_stream_ok(b, s)) return set_err(BNHIP_E_INVALID, "no such resampler bank stream: " + std::to_string(s));
+        const long long n = flush ? 0 : n_in[f];
+        if (n < 0) return set_err(BNHIP_E_INVALID, "negative frame length");
+        if (n > 0 && (!frames || !frames[f])) return set_err(BNHIP_E_INVALID, "frame pointer is NULL");
+        if (group_of[s] < 0) {
+            group_of[s] = (int)groups.size();
+            Group g; g.stream = s;
+            groups.push_back(g);
+        } else if (flush) {
+            return set_err(BNHIP_E_INVALID, "stream listed twice in one flush");
+        }
+        frame_group[f] = group_of[s];
+        groups[group_of[s]].n_in += n;
+        need += bank_estimate(b, n);
+    }
+    // per-frame split: what resampler_ready gives on the running n_total, frame after frame
+    long long in_total = 0;
+    for (Group& g : groups) { const auto& S = b->st[g.stream]; g.n_after = S.n_total; g.i_end = S.i_next; }
+    for (int f = 0; f < n_frames; f++) {
+        Group& g = groups[frame_group[f]];
+        const auto& S = b->st[g.stream];
+        long long i_end;
+        if (flush) i_end = (S.n_total * b->L + b->M - 1) / b->M;
+        else { g.n_after += n_in[f]; i_end = bank_ready(b, g.n_after); }
+        frame_cnt[f] = i_end - g.i_end;
+        g.i_end = i_end;
+    }
+    long long out_total = 0, blocks = 0;
+    for (Group& g : groups) {
+        const auto& S = b->st[g.stream];
+        g.cnt = (int)(g.i_end - S.i_next);
+        if (flush) { g.keep_from = 0; g.keep = 0; }
+        else {
+            long long kf = (g.i_end * b->M + b->half) / b->L - (b->T - 1);
+            if (kf < S.n_base) kf = S.n_base;
+            if (kf > g.n_after) kf = g.n_after;
+            g.keep_from = kf;
+            g.keep = (int)(g.n_after - kf);
+            if (g.keep > b->H) return set_err(BNHIP_E_RUNTIME, "internal error: resampler bank history exceeds its slab");
+        }
+        g.in_off = (int)in_total;
+        g.out_off = (int)out_total;
+        in_total += g.n_in;
+        out_total += g.cnt;
+        blocks += (g.cnt + 255) / 256 + 1;
+    }
+    if (!flush && need > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");      // resample.go:137-144
+    if (out_total > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");
+    if (in_total > INT32_MAX / 2 || out_total > INT32_MAX / 2 || blocks > INT32_MAX / 2)
+        return set_err(BNHIP_E_INVALID, "resampler bank call too large");
+    // streams with nothing to do (every frame empty) stay out of the launch
+    std::vector<ResampleBankDesc> desc;
+    desc.reserve(groups.size());
+    int block0 = 0;
+    for (const Group& g : groups) {
+        if (!flush && g.n_in == 0) continue;
+        const auto& S = b->st[g.stream];
+        ResampleBankDesc d{};
+        d.n_base = S.n_base; d.i_next = S.i_next; d.keep_from = g.keep_from;
+        d.in_off = g.in_off; d.n_in = (int)g.n_in; d.n_hist = S.n_hist;
+        d.hist_rd = (g.stream * 2 + S.parity) * b->H; d.hist_wr = (g.stream * 2 + (S.parity ^ 1)) * b->H;
+        d.keep = g.keep; d.cnt = g.cnt; d.out_off = g.out_off; d.block0 = block0;
+        block0 += (g.cnt + 255) / 256 + 1;
+        desc.push_back(d);
+    }
+    if (!desc.empty()) {
+        hipSetDevice(b->device);
+        const size_t desc_bytes = desc.size() * sizeof(ResampleBankDesc);
+        const size_t stage_bytes = desc_bytes + (size_t)in_total * 2;
+        if (!bank_grow((void**)&b->h_stage, &b->d_stage, &b->stage_cap, stage_bytes))
+            return set_err(BNHIP_E_NOMEM, "allocation failed (resampler bank staging)");
+        size_t oc = b->out_cap * 2;
+        if (!bank_grow((void**)&b->h_out, (void**)&b->d_out, &oc, std::max<size_t>((size_t)out_total * 2, 2)))
+            return set_err(BNHIP_E_NOMEM, "allocation failed (resampler bank output)");
+        b->out_cap = oc / 2;
+        memcpy(b->h_stage, desc.data(), desc_bytes);
+        int16_t* pk = reinterpret_cast<int16_t*>(b->h_stage + desc_bytes);
+        std::vector<long long> fill(groups.size(), 0);
+        for (int f = 0; f < n_frames && !flush; f++) {
+            if (n_in[f] <= 0) continue;
+            const Group& g = groups[frame_group[f]];
+            memcpy(pk + g.in_off + fill[frame_group[f]], frames[f], (size_t)n_in[f] * 2);
+            fill[frame_group[f]] += n_in[f];
+        }
+        const auto* d_desc = static_cast<const ResampleBankDesc*>(b->d_stage);
+        const auto* d_pcm = reinterpret_cast<const int16_t*>(static_cast<const uint8_t*>(b->d_stage) + desc_bytes);
+        hipError_t he = hipMemcpyAsync(b->d_stage, b->h_stage, stage_bytes, hipMemcpyHostToDevice, b->stream);
+        if (he == hipSuccess) {
+            if (launch_resample_bank(d_desc, (int)desc.size(), block0, d_pcm, b->d_hist, b->d_out, b->d_table, b->L, b->M, b->T,
+                                     b->half, b->stream)) {
+                hipStreamSynchronize(b->stream);
+                return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+            }
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess && out_total > 0)
+            he = hipMemcpyAsync(b->h_out, b->d_out, (size_t)out_total * 2, hipMemcpyDeviceToHost, b->stream);
+        const hipError_t hs = hipStreamSynchronize(b->stream);
+        if (he == hipSuccess) he = hs;
+        if (he != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_RUNTIME, std::string("resampler bank: ") + hipGetErrorString(he)); }
+    }
+    // ---- commit: everything above succeeded
+    for (const Group& g : groups) {
+        auto& S = b->st[g.stream];
+        if (flush) { S.n_total = 0; S.i_next = 0; S.n_base = 0; S.n_hist = 0; continue; }   // a new stream starts
+        if (g.n_in == 0) continue;
+        S.n_total = g.n_after; S.i_next = g.i_end;
+        S.n_hist = g.keep; S.n_base = g.keep_from; S.parity ^= 1;
+    }
+    std::vector<long long> taken(groups.size(), 0);
+    for (int f = 0; f < n_frames; f++) {
+        const int gi = frame_group[f];
+        deliver(f, b->h_out + groups[gi].out_off + taken[gi], (int)frame_cnt[f]);
+        taken[gi] += frame_cnt[f];
+    }
+    return BNHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bnhip_resampler_bank_create(int device, int rate_in, int rate_out, int max_streams, bnhip_resampler_bank** out) {
+    if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (rate_in <= 0 || rate_out <= 0) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
+    if (max_streams < 1 || max_streams > (1 << 20)) return set_err(BNHIP_E_INVALID, "max_streams must be in [1, 1048576]");
+    if (rate_in == rate_out) return BNHIP_OK;            // NewResampler returns nil, nil: no resampling required (resample.go:58-60)
+    bnhip_resampler_bank* b = nullptr;
+    BN_GUARD_BEGIN
+    int rc = bnhip_init(nullptr);
+    if (rc) return rc;
+    if (device < 0 || device >= g_devices) return set_err(BNHIP_E_INVALID, "device ordinal out of range");
+    hipSetDevice(device);
+    b = new bnhip_resampler_bank();
+    b->device = device; b->rate_in = rate_in; b->rate_out = rate_out;
+    const int g = igcd(rate_in, rate_out);
+    b->L = rate_out / g; b->M = rate_in / g;
+    std::vector<float> table;
+    resample_design(b->L, b->M, 5.0, 10, &table, &b->T, &b->half);
+    b->H = std::max(b->T - 1, 1);
+    if (resample_bank_lds(b->L, b->M, b->T) > 150 * 1024) {
+        delete b; b = nullptr;
+        return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+    }
+    b->st.resize(max_streams);
+    hipError_t he = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (he == hipSuccess) he = hipMalloc((void**)&b->d_table, table.size() * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&b->d_hist, (size_t)max_streams * 2 * b->H * 4);
+    if (he == hipSuccess) he = hipMemcpy(b->d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        bank_free(b); b = nullptr;
+        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string("resampler bank create: ") + hipGetErrorString(he));
+    }
+    *out = b;
+    return BNHIP_OK;
+    BN_GUARD_END(bank_free(b))
+}
+
+int bnhip_resampler_bank_add_stream(bnhip_resampler_bank* b, int* out_stream) {
+    if (!b || !out_stream) return set_err(BNHIP_E_INVALID, "NULL argument");
+    *out_stream = -1;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    for (size_t s = 0; s < b->st.size(); s++) {
+        if (b->st[s].live) continue;
+        b->st[s] = bnhip_resampler_bank::Stream();       // fresh state: a reused slot starts a new stream
+        b->st[s].live = true;
+        *out_stream = (int)s;
+        return BNHIP_OK;
+    }
+    return set_err(BNHIP_E_INVALID, "resampler bank is full (max_streams)");
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_resampler_bank_remove_stream(bnhip_resampler_bank* b, int stream) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (!bank_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such resampler bank stream: " + std::to_string(stream));
+    b->st[stream].live = false;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_resampler_bank_estimate(const bnhip_resampler_bank* b, int n_in) {
+    if (!b || n_in <= 0) return 0;
+    return (int)bank_estimate(b, n_in);
+}
+
+int bnhip_resampler_bank_process_pcm16(bnhip_resampler_bank* b, int n_frames, const int* streams, const int16_t* const* frames,
+                                       const int* n_in, int16_t* out, size_t out_cap, int* out_count) {
+    if (!b || (n_frames > 0 && (!out || !out_count))) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    long long pos = 0;
+    return bank_run(b, n_frames, streams, frames, n_in, false, (long long)std::min<size_t>(out_cap, INT64_MAX),
+                    [&](int f, const int16_t* p, int n) {
+                        if (n > 0) memcpy(out + pos, p, (size_t)n * 2);
+                        out_count[f] = n;
+                        pos += n;
+                    });
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_resampler_bank_flush_pcm16(bnhip_resampler_bank* b, int n, const int* streams, int16_t* out, size_t out_cap, int* out_count) {
+    if (!b || (n > 0 && (!out || !out_count))) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    long long pos = 0;
+    return bank_run(b, n, streams, nullptr, nullptr, true, (long long)std::min<size_t>(out_cap, INT64_MAX),
+                    [&](int f, const int16_t* p, int c) {
+                        if (c > 0) memcpy(out + pos, p, (size_t)c * 2);
+                        out_count[f] = c;
+                        pos += c;
+                    });
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_windows_write_resampled(bnhip_windows* w, bnhip_resampler_bank* b, int n_frames, const int* streams, const int* sources,
+                                  const int16_t* const* frames, const int* n_in) {
+    if (!w || !b || (n_frames > 0 && !sources)) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    for (int f = 0; f < n_frames; f++)
+        if (!w->a->stats(sources[f], nullptr, nullptr, nullptr)) return set_err(BNHIP_E_INVALID, "no such source: " + std::to_string(sources[f]));
+    std::lock_guard<std::mutex> lk(b->mu);
+    // one ring write per input frame, as BufferConsumer.Write's AnalysisBuffer.Write per frame (an empty result is a write too);
+    // a source removed since the check above loses its frame as a missing buffer does in the reference (buffer_consumer.go:196-206)
+    return bank_run(b, n_frames, streams, frames, n_in, false, INT64_MAX,
+                    [&](int f, const int16_t* p, int n) { (void)w->a->write(sources[f], p, (size_t)n * 2); });
+    BN_GUARD_END((void)0)
+}
+
+void bnhip_resampler_bank_destroy(bnhip_resampler_bank* b) {
+    try { bank_free(b); } catch (...) {}
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // ------------------------------------------------------------------------------------------------ diagnostics
 int bnhip_profile_enable(bnhip_model* m, int on) {

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "resample_bank.h"
 
 namespace bnhip {
 
@@ -123,6 +124,81 @@ int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_
     else if (!in_pcm16 && !out_pcm16) BN_RS(false, false);
     else return -1;
 #undef BN_RS
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ bank form
+// Every stream of a bank (api.cpp bnhip_resampler_bank_*) in one launch.  A stream's input is the virtual array
+//   x(n) = slab[n - n_base]                     for n_base <= n < n_base + n_hist     (history, already float32)
+//        = float32(pcm16) / 32768               for the next n_in samples             (this call's frames, back to back)
+//        = 0                                    otherwise (before the stream start, or beyond what was supplied)
+// which is exactly what k_resample reads from the single-stream resampler's [history | chunk] work buffer, and every output is
+// the same fmaf chain over the same taps in the same order, so the bits are k_resample's.  Blocks are flattened over
+// (stream, 256-output tile) plus one tail block per stream that writes the stream's new history into its other slab.
+__device__ __forceinline__ float bank_x(const ResampleBankDesc& d, const int16_t* __restrict__ pcm, const float* __restrict__ hist,
+                                        long long n) {
+    long long k = n - d.n_base;
+    if (n < 0 || k < 0) return 0.0f;
+    if (k < d.n_hist) return hist[d.hist_rd + k];
+    k -= d.n_hist;
+    if (k < d.n_in) return (float)pcm[d.in_off + k] / 32768.0f;
+    return 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_resample_bank(const ResampleBankDesc* __restrict__ desc, int n_desc,
+                                                       const int16_t* __restrict__ pcm, float* __restrict__ hist,
+                                                       int16_t* __restrict__ out, const float* __restrict__ table, int L, int M,
+                                                       int T, int half) {
+    extern __shared__ float sm[];
+    // the stream of this block: the last descriptor whose block0 <= blockIdx.x (block0 ascends; descriptor 0 starts at 0)
+    const int b = blockIdx.x;
+    int lo_d = 0, hi_d = n_desc - 1;
+    while (lo_d < hi_d) {
+        const int mid = (lo_d + hi_d + 1) >> 1;
+        if (desc[mid].block0 <= b) lo_d = mid;
+        else hi_d = mid - 1;
+    }
+    const ResampleBankDesc d = desc[lo_d];
+    const int tile = b - d.block0;
+    const int n_tiles = (d.cnt + 255) >> 8;
+    if (tile >= n_tiles) {                        // tail block: the inputs from keep_from on, for the next call
+        for (int j = threadIdx.x; j < d.keep; j += 256) hist[d.hist_wr + j] = bank_x(d, pcm, hist, d.keep_from + j);
+        return;
+    }
+    float* tab = sm;                              // [L*T]
+    float* xs = sm + L * T;                       // input span of this block
+    const int i0 = tile * 256;
+    const int i1 = min(d.cnt, i0 + 256);
+    for (int k = threadIdx.x; k < L * T; k += 256) tab[k] = table[k];
+    const long long lo = ((d.i_next + i0) * M + half) / L - (T - 1);
+    const long long hi = ((d.i_next + i1 - 1) * M + half) / L;
+    const int span = (int)(hi - lo + 1);
+    for (int k = threadIdx.x; k < span; k += 256) xs[k] = bank_x(d, pcm, hist, lo + k);
+    __syncthreads();
+    const int i = i0 + threadIdx.x;
+    if (i >= i1) return;
+    const long long pos = (d.i_next + i) * M + half;
+    const int p = (int)(pos % L);
+    const int n0 = (int)(pos / L - lo);
+    const float* tp = tab + p * T;
+    float acc = 0.0f;
+    for (int t = 0; t < T; t++) acc = fmaf(xs[n0 - t], tp[t], acc);
+    float f = fminf(fmaxf(acc, -1.0f), 1.0f);
+    out[(size_t)d.out_off + i] = (int16_t)(f * 32767.0f);     // truncation toward zero
+}
+
+size_t resample_bank_lds(int L, int M, int T) {
+    const long long span = ((long long)255 * M) / L + T + 2;
+    return ((size_t)L * T + (size_t)span) * sizeof(float);
+}
+
+int launch_resample_bank(const ResampleBankDesc* d_desc, int n_desc, int n_blocks, const int16_t* d_pcm, float* d_hist,
+                         int16_t* d_out, const float* d_table, int L, int M, int T, int half, hipStream_t s) {
+    const size_t lds = resample_bank_lds(L, M, T);
+    if (lds > 150 * 1024) return -1;
+    if (n_desc <= 0 || n_blocks <= 0) return 0;
+    lds_limit_once<&k_resample_bank>(160 * 1024);
+    hipLaunchKernelGGL(k_resample_bank, dim3(n_blocks), dim3(256), lds, s, d_desc, n_desc, d_pcm, d_hist, d_out, d_table, L, M, T, half);
     return 0;
 }
 

@@ -55,6 +55,15 @@ typedef int  (*fn_win_stats)(const bnhip_windows*, int, uint64_t*, uint64_t*, si
 typedef int  (*fn_win_reset)(bnhip_windows*, int);
 typedef void (*fn_win_destroy)(bnhip_windows*);
 typedef int  (*fn_win_predict_topk)(bnhip_windows*, bnhip_model*, int, int, double, int, int*, int*, float*, int32_t*, const void**);
+typedef struct bnhip_resampler_bank bnhip_resampler_bank;
+typedef int  (*fn_rb_create)(int, int, int, int, bnhip_resampler_bank**);
+typedef int  (*fn_rb_add_stream)(bnhip_resampler_bank*, int*);
+typedef int  (*fn_rb_remove_stream)(bnhip_resampler_bank*, int);
+typedef int  (*fn_rb_estimate)(const bnhip_resampler_bank*, int);
+typedef int  (*fn_rb_process_pcm16)(bnhip_resampler_bank*, int, const int*, const int16_t* const*, const int*, int16_t*, size_t, int*);
+typedef int  (*fn_rb_flush_pcm16)(bnhip_resampler_bank*, int, const int*, int16_t*, size_t, int*);
+typedef int  (*fn_win_write_resampled)(bnhip_windows*, bnhip_resampler_bank*, int, const int*, const int*, const int16_t* const*, const int*);
+typedef void (*fn_rb_destroy)(bnhip_resampler_bank*);
 
 typedef struct {
     void* handle;
@@ -67,6 +76,9 @@ typedef struct {
     fn_win_create win_create; fn_win_info win_info; fn_win_add_source win_add_source; fn_win_remove_source win_remove_source;
     fn_win_write win_write; fn_win_collect win_collect; fn_win_stats win_stats; fn_win_reset win_reset; fn_win_destroy win_destroy;
     fn_predict_pcm_topk predict_pcm_topk; fn_win_predict_topk win_predict_topk;
+    fn_rb_create rb_create; fn_rb_add_stream rb_add_stream; fn_rb_remove_stream rb_remove_stream; fn_rb_estimate rb_estimate;
+    fn_rb_process_pcm16 rb_process_pcm16; fn_rb_flush_pcm16 rb_flush_pcm16; fn_win_write_resampled win_write_resampled;
+    fn_rb_destroy rb_destroy;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -101,6 +113,10 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(win_stats, "bnhip_windows_stats"); BN_RESOLVE(win_reset, "bnhip_windows_reset");
     BN_RESOLVE(win_destroy, "bnhip_windows_destroy");
     BN_RESOLVE(predict_pcm_topk, "bnhip_predict_pcm_topk"); BN_RESOLVE(win_predict_topk, "bnhip_windows_predict_topk");
+    BN_RESOLVE(rb_create, "bnhip_resampler_bank_create"); BN_RESOLVE(rb_add_stream, "bnhip_resampler_bank_add_stream");
+    BN_RESOLVE(rb_remove_stream, "bnhip_resampler_bank_remove_stream"); BN_RESOLVE(rb_estimate, "bnhip_resampler_bank_estimate");
+    BN_RESOLVE(rb_process_pcm16, "bnhip_resampler_bank_process_pcm16"); BN_RESOLVE(rb_flush_pcm16, "bnhip_resampler_bank_flush_pcm16");
+    BN_RESOLVE(win_write_resampled, "bnhip_windows_write_resampled"); BN_RESOLVE(rb_destroy, "bnhip_resampler_bank_destroy");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -146,6 +162,30 @@ static int bnbind_win_reset(bnhip_windows* w, int s) { return BN.win_reset(w, s)
 static void bnbind_win_destroy(bnhip_windows* w) { if (BN.win_destroy) BN.win_destroy(w); }
 static int bnbind_predict_pcm_topk(bnhip_model* m, const void* pcm, int bits, int n, int act, double sens, int k, float* c, int32_t* i) {
     return BN.predict_pcm_topk(m, pcm, bits, n, act, sens, k, c, i);
+}
+// resampler bank (static inline: the C test driver does not call these, and -Wunused-function spares inline ones)
+static inline int bnbind_rb_create(int dev, int from, int to, int max_streams, bnhip_resampler_bank** b) {
+    return BN.rb_create(dev, from, to, max_streams, b);
+}
+static inline int bnbind_rb_add_stream(bnhip_resampler_bank* b, int* s) { return BN.rb_add_stream(b, s); }
+static inline int bnbind_rb_remove_stream(bnhip_resampler_bank* b, int s) { return BN.rb_remove_stream(b, s); }
+static inline int bnbind_rb_estimate(const bnhip_resampler_bank* b, int n) { return BN.rb_estimate(b, n); }
+static inline int bnbind_rb_process_pcm16(bnhip_resampler_bank* b, int n, const int* st, const int16_t* const* f, const int* n_in,
+                                          int16_t* out, size_t cap, int* cnt) {
+    return BN.rb_process_pcm16(b, n, st, f, n_in, out, cap, cnt);
+}
+static inline int bnbind_rb_flush_pcm16(bnhip_resampler_bank* b, int n, const int* st, int16_t* out, size_t cap, int* cnt) {
+    return BN.rb_flush_pcm16(b, n, st, out, cap, cnt);
+}
+static inline int bnbind_win_write_resampled(bnhip_windows* w, bnhip_resampler_bank* b, int n, const int* st, const int* src,
+                                             const int16_t* const* f, const int* n_in) {
+    return BN.win_write_resampled(w, b, n, st, src, f, n_in);
+}
+static inline void bnbind_rb_destroy(bnhip_resampler_bank* b) { if (BN.rb_destroy) BN.rb_destroy(b); }
+// frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
+// the pointer table points at byte offset off[k] of the staging block
+static inline void bnbind_rb_point(const int16_t** ptrs, const char* stage, const int* off, int n) {
+    for (int k = 0; k < n; k++) ptrs[k] = (const int16_t*)(const void*)(stage + off[k]);
 }
 */
 import "C"
@@ -971,4 +1011,238 @@ func ResampleBytes(pcm []byte, fromRate, toRate int, device int) ([]byte, error)
 	result := make([]byte, len(out))
 	copy(result, out)
 	return result, nil
+}
+
+// ResamplerBank is BufferConsumer.Write's rate fan-out (internal/analysis/buffer_consumer.go:105-210: one Resampler per
+// (source, non-native rate)) for every source of ONE (fromRate, toRate) pair: a stream per source, and each call resamples
+// all the frames it is given in one device call (bnhip_resampler_bank_*).  Every stream's bytes are those its own Resampler
+// would return for the same frames.  Calls are serialised on the bank.
+type ResamplerBank struct {
+	mu               sync.Mutex
+	h                *C.bnhip_resampler_bank
+	fromRate, toRate int
+	stage            unsafe.Pointer // C memory: this call's frames back to back
+	stageCap         int
+	ptrs             unsafe.Pointer // C memory: one const int16_t* per frame
+	ptrsCap          int
+}
+
+// NewResamplerBank: nil, nil for equal rates, as NewResampler.
+func NewResamplerBank(fromRate, toRate, maxStreams, device int) (*ResamplerBank, error) {
+	if fromRate == toRate {
+		return nil, nil //nolint:nilnil // as the reference's NewResampler: nil means "no resampling needed"
+	}
+	var h *C.bnhip_resampler_bank
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_rb_create(C.int(device), C.int(fromRate), C.int(toRate), C.int(maxStreams), &h); rc != 0 || h == nil {
+		return nil, fmt.Errorf("failed to create resampler bank from %d Hz to %d Hz: %s", fromRate, toRate, lastError())
+	}
+	return &ResamplerBank{h: h, fromRate: fromRate, toRate: toRate}, nil
+}
+
+// AddStream starts a stream (one source's Resampler); slots of removed streams are reused with fresh state.
+func (b *ResamplerBank) AddStream() (int, error) {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return -1, errors.New("hip: resampler bank is closed")
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var s C.int
+	if rc := C.bnbind_rb_add_stream(b.h, &s); rc != 0 {
+		return -1, fmt.Errorf("hip: resampler_bank_add_stream failed (%d): %s", int(rc), lastError())
+	}
+	return int(s), nil
+}
+
+func (b *ResamplerBank) RemoveStream(stream int) error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return nil
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_rb_remove_stream(b.h, C.int(stream)); rc != 0 {
+		return fmt.Errorf("hip: resampler_bank_remove_stream failed (%d): %s", int(rc), lastError())
+	}
+	return nil
+}
+
+// EstimateOutputBytes = Resampler.EstimateOutputBytes for one frame (resample.go:83-88).
+func (b *ResamplerBank) EstimateOutputBytes(inputBytes int) int {
+	if inputBytes <= 0 || b.h == nil {
+		return 0
+	}
+	return int(C.bnbind_rb_estimate(b.h, C.int(inputBytes/bytesPerSample))) * bytesPerSample
+}
+
+// stageLocked copies the frames into the bank's C staging; -> the pointer table, the per-frame sample counts.
+func (b *ResamplerBank) stageLocked(frames [][]byte) (**C.int16_t, []C.int, error) {
+	total := 0
+	for _, f := range frames {
+		if len(f)%bytesPerSample != 0 {
+			return nil, nil, fmt.Errorf("input length %d is not a multiple of %d", len(f), bytesPerSample)
+		}
+		total += len(f)
+	}
+	if total > b.stageCap || b.stage == nil {
+		C.free(b.stage)
+		b.stage, b.stageCap = C.malloc(C.size_t(total+1)), total+1
+	}
+	if len(frames) > b.ptrsCap || b.ptrs == nil {
+		C.free(b.ptrs)
+		b.ptrs, b.ptrsCap = C.malloc(C.size_t((len(frames)+1)*int(unsafe.Sizeof(uintptr(0))))), len(frames)+1
+	}
+	if b.stage == nil || b.ptrs == nil {
+		C.free(b.stage)
+		C.free(b.ptrs)
+		b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
+		return nil, nil, errors.New("hip: out of host memory (resampler bank staging)")
+	}
+	lens := make([]C.int, len(frames)+1)
+	offs := make([]C.int, len(frames)+1)
+	stage := unsafe.Slice((*byte)(b.stage), b.stageCap)
+	pos := 0
+	for k, f := range frames {
+		copy(stage[pos:], f)
+		offs[k], lens[k] = C.int(pos), C.int(len(f)/bytesPerSample)
+		pos += len(f)
+	}
+	C.bnbind_rb_point((**C.int16_t)(b.ptrs), (*C.char)(b.stage), &offs[0], C.int(len(frames)))
+	return (**C.int16_t)(b.ptrs), lens, nil
+}
+
+// Process resamples frames[k] of streams[k] for every k in one device call -> one slice per frame, each what that stream's
+// Resampler.ResampleInto returns for it in sequence (a stream may appear several times; its frames go in slice order).  An
+// unknown stream or an odd byte count fails the whole call before any stream advances.
+func (b *ResamplerBank) Process(streams []int, frames [][]byte) ([][]byte, error) {
+	if len(streams) != len(frames) {
+		return nil, fmt.Errorf("hip: %d streams for %d frames", len(streams), len(frames))
+	}
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return nil, errors.New("hip: resampler bank is closed")
+	}
+	if len(frames) == 0 {
+		return nil, nil
+	}
+	ptrs, lens, err := b.stageLocked(frames)
+	if err != nil {
+		return nil, err
+	}
+	st := make([]C.int, len(streams))
+	capSamples := 0
+	for k, s := range streams {
+		st[k] = C.int(s)
+		capSamples += int(C.bnbind_rb_estimate(b.h, lens[k]))
+	}
+	out := make([]int16, capSamples+1)
+	counts := make([]C.int, len(frames))
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_rb_process_pcm16(b.h, C.int(len(frames)), &st[0], ptrs, &lens[0], (*C.int16_t)(unsafe.Pointer(&out[0])),
+		C.size_t(capSamples), &counts[0]); rc != 0 {
+		return nil, fmt.Errorf("hip: resampler bank failed (%d): %s", int(rc), lastError())
+	}
+	res := make([][]byte, len(frames))
+	raw := unsafe.Slice((*byte)(unsafe.Pointer(&out[0])), len(out)*bytesPerSample)
+	pos := 0
+	for k, c := range counts {
+		n := int(c) * bytesPerSample
+		res[k] = raw[pos : pos+n : pos+n]
+		pos += n
+	}
+	return res, nil
+}
+
+// Flush ends each listed stream (each at most once): its tail, then the stream starts anew (Resampler.Flush).
+func (b *ResamplerBank) Flush(streams []int) ([][]byte, error) {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return nil, errors.New("hip: resampler bank is closed")
+	}
+	if len(streams) == 0 {
+		return nil, nil
+	}
+	st := make([]C.int, len(streams))
+	for k, s := range streams {
+		st[k] = C.int(s)
+	}
+	const tailCap = 1 << 16
+	out := make([]int16, tailCap*len(streams))
+	counts := make([]C.int, len(streams))
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_rb_flush_pcm16(b.h, C.int(len(streams)), &st[0], (*C.int16_t)(unsafe.Pointer(&out[0])), C.size_t(len(out)),
+		&counts[0]); rc != 0 {
+		return nil, fmt.Errorf("hip: resampler bank flush failed (%d): %s", int(rc), lastError())
+	}
+	res := make([][]byte, len(streams))
+	raw := unsafe.Slice((*byte)(unsafe.Pointer(&out[0])), len(out)*bytesPerSample)
+	pos := 0
+	for k, c := range counts {
+		n := int(c) * bytesPerSample
+		res[k] = raw[pos : pos+n : pos+n]
+		pos += n
+	}
+	return res, nil
+}
+
+func (b *ResamplerBank) FromRate() int { return b.fromRate }
+func (b *ResamplerBank) ToRate() int   { return b.toRate }
+
+func (b *ResamplerBank) Close() error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h != nil {
+		C.bnbind_rb_destroy(b.h)
+		b.h = nil
+	}
+	C.free(b.stage)
+	C.free(b.ptrs)
+	b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
+	return nil
+}
+
+// WriteResampled is BufferConsumer.Write's non-native rate group for every source of a tick at once: frames[k] (captured at
+// the bank's fromRate) is resampled on streams[k] of bank and written into sources[k] of this assembler, one ring write per
+// input frame (AnalysisBuffer.Write per frame, analysis.go:152-175), in one device call.  Every source and stream is checked
+// before anything runs: an error leaves every stream and every ring as it was.
+func (w *WindowAssembler) WriteResampled(bank *ResamplerBank, streams, sources []int, frames [][]byte) error {
+	if len(streams) != len(frames) || len(sources) != len(frames) {
+		return fmt.Errorf("hip: %d streams and %d sources for %d frames", len(streams), len(sources), len(frames))
+	}
+	w.life.RLock()
+	defer w.life.RUnlock()
+	if w.h == nil {
+		return errors.New("hip: window assembler is closed")
+	}
+	bank.mu.Lock()
+	defer bank.mu.Unlock()
+	if bank.h == nil {
+		return errors.New("hip: resampler bank is closed")
+	}
+	if len(frames) == 0 {
+		return nil
+	}
+	ptrs, lens, err := bank.stageLocked(frames)
+	if err != nil {
+		return err
+	}
+	st := make([]C.int, len(frames))
+	src := make([]C.int, len(frames))
+	for k := range frames {
+		st[k], src[k] = C.int(streams[k]), C.int(sources[k])
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_win_write_resampled(w.h, bank.h, C.int(len(frames)), &st[0], &src[0], ptrs, &lens[0]); rc != 0 {
+		return fmt.Errorf("hip: windows_write_resampled failed (%d): %s", int(rc), lastError())
+	}
+	return nil
 }

@@ -94,3 +94,16 @@ func (*Resampler) FromRate() int                             { return 0 }
 func (*Resampler) ToRate() int                               { return 0 }
 func (*Resampler) Close() error                              { return nil }
 func (*Resampler) String() string                            { return "Resampler(hip: unavailable)" }
+
+type ResamplerBank struct{}
+
+func NewResamplerBank(int, int, int, int) (*ResamplerBank, error)            { return nil, ErrHIPUnavailable }
+func (*ResamplerBank) AddStream() (int, error)                               { return -1, ErrHIPUnavailable }
+func (*ResamplerBank) RemoveStream(int) error                                { return nil }
+func (*ResamplerBank) EstimateOutputBytes(int) int                           { return 0 }
+func (*ResamplerBank) Process([]int, [][]byte) ([][]byte, error)             { return nil, ErrHIPUnavailable }
+func (*ResamplerBank) Flush([]int) ([][]byte, error)                         { return nil, ErrHIPUnavailable }
+func (*ResamplerBank) FromRate() int                                         { return 0 }
+func (*ResamplerBank) ToRate() int                                           { return 0 }
+func (*ResamplerBank) Close() error                                          { return nil }
+func (*WindowAssembler) WriteResampled(*ResamplerBank, []int, []int, [][]byte) error { return ErrHIPUnavailable }

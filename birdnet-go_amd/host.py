@@ -36,7 +36,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_host_alloc", "bnhip_host_free", "bnhip_windows_create", "bnhip_windows_info", "bnhip_windows_add_source",
            "bnhip_windows_remove_source", "bnhip_windows_write", "bnhip_windows_collect", "bnhip_windows_ready",
            "bnhip_windows_stats", "bnhip_windows_reset", "bnhip_windows_destroy", "bnhip_predict_pcm_topk",
-           "bnhip_windows_predict_topk"]
+           "bnhip_windows_predict_topk", "bnhip_resampler_bank_create", "bnhip_resampler_bank_add_stream",
+           "bnhip_resampler_bank_remove_stream", "bnhip_resampler_bank_estimate", "bnhip_resampler_bank_process_pcm16",
+           "bnhip_resampler_bank_flush_pcm16", "bnhip_windows_write_resampled", "bnhip_resampler_bank_destroy"]
 
 
 class HipError(RuntimeError):
@@ -570,6 +572,119 @@ class StreamResampler:
     def _alive(self):
         if not self._h:
             raise HipError(E_INVALID, "resampler is closed")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pcm16_frames(frames):
+    """-> (int16 arrays kept alive, C array of their addresses, C array of their lengths) for the bank entries."""
+    arrs = []
+    for f in frames:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            if len(f) % 2:
+                raise HipError(E_INVALID, f"input length {len(f)} is not a multiple of 2 (16-bit PCM requires even byte count)")
+            arrs.append(np.frombuffer(f, "<i2"))
+        else:
+            arrs.append(np.ascontiguousarray(f, np.int16).reshape(-1))
+    n = len(arrs)
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    lens = (C.c_int * max(n, 1))(*[a.size for a in arrs])
+    return arrs, ptrs, lens
+
+
+class ResamplerBank:
+    """`bnhip_resampler_bank` (include/bnhip.h): one StreamResampler per stream for many streams of one (from, to) rate pair,
+    every call one device call.  `process([(stream, pcm16), ...])` -> one bytes object per frame, each what that stream's own
+    StreamResampler returns for the frame in sequence (a stream may appear several times; its frames go in list order);
+    `write_windows(win, [(stream, source, pcm16), ...])` writes each frame's result into `source` of a stream.NativeWindows,
+    one ring write per frame, without the samples leaving the library.  Errors leave every stream untouched."""
+
+    def __init__(self, from_rate, to_rate, max_streams=256, device=0):
+        self._lib = L = load_library()
+        vp, ci = C.c_void_p, C.c_int
+        L.bnhip_resampler_bank_create.argtypes = [ci, ci, ci, ci, C.POINTER(vp)]
+        L.bnhip_resampler_bank_add_stream.argtypes = [vp, C.POINTER(ci)]
+        L.bnhip_resampler_bank_remove_stream.argtypes = [vp, ci]
+        L.bnhip_resampler_bank_estimate.argtypes = [vp, ci]
+        L.bnhip_resampler_bank_process_pcm16.argtypes = [vp, ci, vp, vp, vp, vp, C.c_size_t, vp]
+        L.bnhip_resampler_bank_flush_pcm16.argtypes = [vp, ci, vp, vp, C.c_size_t, vp]
+        L.bnhip_windows_write_resampled.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        L.bnhip_resampler_bank_destroy.argtypes = [vp]
+        L.bnhip_resampler_bank_destroy.restype = None
+        self.from_rate, self.to_rate, self.max_streams = int(from_rate), int(to_rate), int(max_streams)
+        self._h = C.c_void_p()
+        _check(L, L.bnhip_resampler_bank_create(device, self.from_rate, self.to_rate, self.max_streams, C.byref(self._h)))
+        if not self._h:
+            raise HipError(E_INVALID, "equal rates need no resampler bank (ResamplerBank.new returns None)")
+
+    @classmethod
+    def new(cls, from_rate, to_rate, max_streams=256, device=0):
+        """None when no resampling is required, as NewResampler (resample.go:58-60)."""
+        return None if from_rate == to_rate else cls(from_rate, to_rate, max_streams, device)
+
+    def add_stream(self):
+        s = C.c_int(-1)
+        _check(self._lib, self._lib.bnhip_resampler_bank_add_stream(self._alive(), C.byref(s)))
+        return s.value
+
+    def remove_stream(self, stream):
+        _check(self._lib, self._lib.bnhip_resampler_bank_remove_stream(self._alive(), int(stream)))
+
+    def estimate_output_bytes(self, input_bytes):
+        return int(self._lib.bnhip_resampler_bank_estimate(self._alive(), int(input_bytes) // 2)) * 2
+
+    def process(self, items, out_cap=None):
+        """[(stream, pcm16 bytes | int16 array), ...] -> [bytes, ...] per frame.  out_cap (samples) defaults to the sum of the
+        frames' estimates; a smaller one is the library's E_INVALID (for tests of that path)."""
+        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _ in items])
+        arrs, ptrs, lens = _pcm16_frames([f for _, f in items])
+        if out_cap is None:
+            out_cap = sum(int(self._lib.bnhip_resampler_bank_estimate(self._alive(), a.size)) for a in arrs)
+        out = np.empty(max(out_cap, 1), np.int16)
+        counts = np.zeros(max(len(items), 1), np.int32)
+        _check(self._lib, self._lib.bnhip_resampler_bank_process_pcm16(self._alive(), len(items), streams, ptrs, lens, out.ctypes.data,
+                                                                        out_cap, counts.ctypes.data))
+        res, pos = [], 0
+        for c in counts[:len(items)]:
+            res.append(out[pos:pos + c].tobytes())
+            pos += int(c)
+        return res
+
+    def flush(self, streams, cap=1 << 16):
+        """End of each listed stream: the tail per stream; each then starts anew."""
+        streams = list(streams)
+        arr = (C.c_int * max(len(streams), 1))(*[int(s) for s in streams])
+        out = np.empty(cap, np.int16)
+        counts = np.zeros(max(len(streams), 1), np.int32)
+        _check(self._lib, self._lib.bnhip_resampler_bank_flush_pcm16(self._alive(), len(streams), arr, out.ctypes.data, cap,
+                                                                      counts.ctypes.data))
+        res, pos = [], 0
+        for c in counts[:len(streams)]:
+            res.append(out[pos:pos + c].tobytes())
+            pos += int(c)
+        return res
+
+    def write_windows(self, win, items):
+        """[(stream, source, pcm16), ...] -> each frame resampled and written into source `source` of win (stream.NativeWindows),
+        one ring write per frame (bnhip_windows_write_resampled)."""
+        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _, _ in items])
+        sources = (C.c_int * max(len(items), 1))(*[int(src) for _, src, _ in items])
+        arrs, ptrs, lens = _pcm16_frames([f for _, _, f in items])
+        win._check(self._lib.bnhip_windows_write_resampled(win._alive(), self._alive(), len(items), streams, sources, ptrs, lens))
+
+    def close(self):
+        if self._h:
+            self._lib.bnhip_resampler_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def _alive(self):
+        if not self._h:
+            raise HipError(E_INVALID, "resampler bank is closed")
+        return self._h
 
     def __del__(self):
         try:

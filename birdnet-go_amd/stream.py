@@ -587,7 +587,17 @@ def process_data(orch, data, start_time, captured_at, source, model_id, queue, o
 class WindowBatcher:
     """All (source, model) monitors of buffer_manager.go:388-496 in one object.  `tick()` is one poll: every buffer with a
     window ready is read, windows of the same model form one batch (at most `max_batch` per device call), inactive models
-    are read and discarded exactly as the reference does (:478-480: the audio is consumed, not analysed)."""
+    are read and discarded exactly as the reference does (:478-480: the audio is consumed, not analysed).
+
+    A buffer allocated with a `source_rate` other than its model's effective rate is fed resampled audio, BufferConsumer.Write's
+    rate groups (buffer_consumer.go:105-210): a source's buffers are grouped by (source rate, model rate) and each group's
+    audio is resampled once per frame, whatever the number of models in it.  Python rings: one host.StreamResampler per
+    (source, rate pair), then one buffer write per frame, as the reference.  Native rings: the frames are queued per rate pair
+    and the next `tick()` resamples every source's queued frames in ONE device call per rate pair (host.ResamplerBank, one
+    ring write per frame) before it collects - such a buffer's audio therefore reaches its ring up to one tick later than
+    audio at the model's own rate."""
+
+    BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
 
     def __init__(self, orch: Orchestrator, queue: _results.ResultsQueue = None, overruns: OverrunTrackers = None,
                  max_batch=256, pre_capture_s=0.0, bit_depth=16, clock=time.time, on_error=None, native=True):
@@ -600,11 +610,33 @@ class WindowBatcher:
         self.assemblers = {}                 # native: model_id -> NativeWindows
         self.mu = threading.Lock()
         self.on_error, self.errors = on_error, 0   # a failed device call costs its own windows only (the reference logs and polls on)
+        self.rates = {}                      # (source, model_id) -> (source rate, model rate) of a resampled buffer
+        self.resamplers = {}                 # python: (source, source rate, model rate) -> host.StreamResampler
+        self.banks = {}                      # native: (source rate, model rate) -> host.ResamplerBank
+        self.bank_streams = {}               # native: (source, source rate, model rate) -> stream of that pair's bank
+        self.pending = {}                    # native: (source rate, model rate) -> [(source, stream, pcm bytes, buffers)] until the next tick
 
-    def allocate(self, source, model_id, capacity=None):
+    def allocate(self, source, model_id, capacity=None, source_rate=None):
+        """The buffer of (source, model_id).  source_rate: the rate the source captures at; None or the model's effective rate
+        = the bytes are written as they are, any other rate = resampled to the model's (see the class docstring)."""
         spec = self.orch.model_spec_for(model_id)
         if spec is None:
             raise OrchestratorError(f"unknown model: {model_id}")
+        if source_rate is not None and source_rate <= 0:
+            raise StreamError(f"invalid source sample rate: {source_rate}")
+        model_rate = spec.effective_sample_rate()
+        key = None if source_rate is None or source_rate == model_rate else (int(source_rate), int(model_rate))
+        ab = self._allocate_buffer(source, model_id, spec, capacity)
+        with self.mu:
+            old = self.rates.pop((source, model_id), None)
+            if old is not None:                                   # a re-allocated buffer starts a fresh resampler stream
+                self._release_rate(source, old)
+            if key is not None:
+                self.rates[(source, model_id)] = key
+                self._acquire_rate(source, key)
+        return ab
+
+    def _allocate_buffer(self, source, model_id, spec, capacity):
         clip, overlap, read = spec.buffer_dimensions()
         capacity = capacity if capacity is not None else 2 * clip
         if not self.native:
@@ -618,6 +650,9 @@ class WindowBatcher:
                 if win is not None:                       # the model was re-registered with another geometry
                     for k in [k for k in self.buffers if k[1] == model_id]:
                         del self.buffers[k]
+                        key = self.rates.pop(k, None)
+                        if key is not None:
+                            self._release_rate(k[0], key)
                     win.close()
                 win = self.assemblers[model_id] = NativeWindows(overlap, read, self.max_batch)
             old = self.buffers.pop((source, model_id), None)
@@ -632,14 +667,88 @@ class WindowBatcher:
                 ab = self.buffers.pop(k)
                 if isinstance(ab, _NativeSource):
                     ab.win.remove_source(ab.index)
+                key = self.rates.pop(k, None)
+                if key is not None:
+                    self._release_rate(source, key)
         self.overruns.remove_source(source)
 
+    # (under self.mu) one resampler stream per (source, rate pair) while a buffer of the source uses the pair
+    def _acquire_rate(self, source, key):
+        sk = (source,) + key
+        if not self.native:
+            if sk not in self.resamplers:
+                self.resamplers[sk] = _host.StreamResampler(key[0], key[1])
+            return
+        if sk in self.bank_streams:
+            return
+        bank = self.banks.get(key)
+        if bank is None:
+            bank = self.banks[key] = _host.ResamplerBank(key[0], key[1], self.BANK_STREAMS)
+        self.bank_streams[sk] = bank.add_stream()
+
+    def _release_rate(self, source, key):
+        if any(s == source and k == key for (s, _), k in self.rates.items()):
+            return                                                # another model of the source still reads this pair
+        sk = (source,) + key
+        r = self.resamplers.pop(sk, None)
+        if r is not None:
+            r.close()
+        st = self.bank_streams.pop(sk, None)
+        if st is not None:
+            self.banks[key].remove_stream(st)
+            if key in self.pending:
+                self.pending[key] = [it for it in self.pending[key] if it[1] != st]
+
     def write(self, source, data):
-        """Capture side: the same bytes go to every model's buffer of that source."""
+        """Capture side: the same bytes go to every model's buffer of that source; a buffer of another rate gets them resampled
+        (once per rate pair: buffer_consumer.go:184-210)."""
         with self.mu:
-            abs_ = [ab for (s, _), ab in self.buffers.items() if s == source]
+            groups = {}
+            for (s, m), ab in self.buffers.items():
+                if s == source:
+                    groups.setdefault(self.rates.get((s, m)), []).append(ab)
+            abs_ = groups.pop(None, [])
+            resampled = []
+            if groups:
+                raw = _as_bytes(data).tobytes()
+                for key, targets in groups.items():
+                    if self.native:
+                        self.pending.setdefault(key, []).append((source, self.bank_streams[(source,) + key], raw, targets))
+                    else:
+                        resampled.append((self.resamplers[(source,) + key], targets))
         for ab in abs_:
             ab.write(data)
+        for r, targets in resampled:
+            out = r.resample_into(raw)
+            for ab in targets:
+                ab.write(out)
+
+    def _drain_resampled(self):
+        """Native: every rate pair's queued frames through one device call (host.ResamplerBank), one ring write per frame.  When
+        each frame has one buffer and all of them are in one assembler the results go straight into its rings
+        (bnhip_windows_write_resampled); otherwise they come back and are written to every buffer of the frame's group."""
+        failed = []
+        with self.mu:
+            pending, self.pending = self.pending, {}
+            live = {id(ab) for ab in self.buffers.values()}
+            for key, items in pending.items():
+                items = [(src, st, raw, [ab for ab in targets if id(ab) in live]) for src, st, raw, targets in items]
+                bank = self.banks[key]
+                try:
+                    wins = {id(ab.win) for *_, targets in items for ab in targets}
+                    if len(wins) == 1 and all(len(targets) == 1 for *_, targets in items):
+                        bank.write_windows(items[0][3][0].win, [(st, targets[0].index, raw) for _, st, raw, targets in items])
+                    else:
+                        outs = bank.process([(st, raw) for _, st, raw, _ in items])
+                        for (*_, targets), out in zip(items, outs):
+                            for ab in targets:
+                                ab.write(out)
+                except Exception as e:                        # the reference logs a failed resample and goes on (buffer_consumer.go:193-201)
+                    self.errors += len(items)
+                    failed.append((sorted({src for src, *_ in items}), e))
+        for sources, e in failed:
+            if self.on_error:
+                self.on_error(None, sources, e)
 
     def _tick_native(self):
         with self.mu:
@@ -697,9 +806,18 @@ class WindowBatcher:
                 win.close()
             self.assemblers.clear()
             self.buffers.clear()
+            for r in list(self.resamplers.values()) + list(self.banks.values()):
+                r.close()
+            self.resamplers.clear()
+            self.banks.clear()
+            self.bank_streams.clear()
+            self.pending.clear()
+            self.rates.clear()
 
     def tick(self):
         if self.native:
+            if self.pending:
+                self._drain_resampled()
             return self._tick_native()
         with self.mu:
             items = list(self.buffers.items())

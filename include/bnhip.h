@@ -237,6 +237,37 @@ int bnhip_resampler_flush_pcm16(bnhip_resampler* r, int16_t* out, int out_cap, i
 int bnhip_resampler_flush_f32(bnhip_resampler* r, float* out, int out_cap, int* n_out);
 void bnhip_resampler_destroy(bnhip_resampler* r);
 
+/* Resampler bank: the rate fan-out of BufferConsumer.Write (internal/analysis/buffer_consumer.go:105-210, one stateful
+ * Resampler per (source, non-native rate)) for many streams that share (rate_in, rate_out), one device call per call: the
+ * frames of every stream are packed into one page-locked staging buffer with a descriptor table, resampled by one kernel
+ * launch and copied back once, on one HIP stream per bank.  PCM16 in and out only (resample.go).  Each stream's output is bit
+ * for bit what a bnhip_resampler of its own returns for the same frames in the same order.
+ *   create:        equal rates -> *out = NULL and BNHIP_OK (as bnhip_resampler_create); max_streams fixes the slot table.
+ *   add_stream:    a fresh stream; slots of removed streams are reused (with fresh state).  A full bank is BNHIP_E_INVALID.
+ *   estimate:      = bnhip_resampler_estimate (upper bound for one frame of n_in samples).
+ *   process:       frames f = 0..n_frames-1 (frames[f], n_in[f] samples) of streams[f]; a stream may appear several times,
+ *                  its frames are consumed in call order.  out receives every frame's samples packed in call order,
+ *                  out_count[f] their number (what bnhip_resampler_process_pcm16 returns for that frame).  out_cap (samples)
+ *                  below the sum of estimate(n_in[f]), an unknown or removed stream, a negative length: BNHIP_E_INVALID and
+ *                  no stream advances.  An empty frame emits nothing.  A device error leaves every stream as it was.
+ *   flush:         end of each listed stream (each at most once): the tail, then the stream starts anew (bnhip_resampler_flush_*).
+ *   windows_write_resampled: process + one bnhip_windows_write per input frame of frame f's samples into source sources[f]
+ *                  of w (an empty result is a write, as AnalysisBuffer.Write of an empty slice); every source is checked
+ *                  before anything runs.  Nothing leaves the library's staging.
+ * Calls on one bank are serialised internally; writers of other assemblers may run at the same time. */
+typedef struct bnhip_resampler_bank bnhip_resampler_bank;
+int bnhip_resampler_bank_create(int device, int rate_in, int rate_out, int max_streams, bnhip_resampler_bank** out);
+int bnhip_resampler_bank_add_stream(bnhip_resampler_bank* b, int* out_stream);
+int bnhip_resampler_bank_remove_stream(bnhip_resampler_bank* b, int stream);
+int bnhip_resampler_bank_estimate(const bnhip_resampler_bank* b, int n_in);
+int bnhip_resampler_bank_process_pcm16(bnhip_resampler_bank* b, int n_frames, const int* streams, const int16_t* const* frames,
+                                       const int* n_in, int16_t* out, size_t out_cap, int* out_count);
+int bnhip_resampler_bank_flush_pcm16(bnhip_resampler_bank* b, int n, const int* streams, int16_t* out, size_t out_cap,
+                                     int* out_count);
+int bnhip_windows_write_resampled(bnhip_windows* w, bnhip_resampler_bank* b, int n_frames, const int* streams, const int* sources,
+                                  const int16_t* const* frames, const int* n_in);
+void bnhip_resampler_bank_destroy(bnhip_resampler_bank* b);
+
 /* Stream plumbing for hosts that own a HIP stream (bench harness: torch's current stream). */
 int bnhip_set_stream(bnhip_model* m, void* hip_stream);
 int bnhip_synchronize(bnhip_model* m);

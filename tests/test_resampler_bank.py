@@ -1,0 +1,199 @@
+"""Resampler bank (bnhip_resampler_bank_*): BufferConsumer.Write's rate fan-out (internal/analysis/buffer_consumer.go:105-210)
+for many sources of one rate pair in one device call.  Contract: every stream's bytes are exactly those of a stream resampler
+of its own fed the same frames (so, concatenated + flush, exactly the one-shot call over the whole stream, which
+tests/test_resample.py ties to the filter spec), per frame; bad arguments fail before any stream advances."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from birdnet_go_amd import host
+from birdnet_go_amd import stream as S
+
+BANK_SYMBOLS = ["bnhip_resampler_bank_create", "bnhip_resampler_bank_add_stream", "bnhip_resampler_bank_remove_stream",
+                "bnhip_resampler_bank_estimate", "bnhip_resampler_bank_process_pcm16", "bnhip_resampler_bank_flush_pcm16",
+                "bnhip_windows_write_resampled", "bnhip_resampler_bank_destroy"]
+
+
+def _lib():
+    lib = host.load_library()
+    vp, ci = C.c_void_p, C.c_int
+    lib.bnhip_resampler_bank_create.argtypes = [ci, ci, ci, ci, C.POINTER(vp)]
+    lib.bnhip_resampler_bank_add_stream.argtypes = [vp, C.POINTER(ci)]
+    lib.bnhip_resampler_bank_remove_stream.argtypes = [vp, ci]
+    lib.bnhip_resampler_bank_estimate.argtypes = [vp, ci]
+    lib.bnhip_resampler_bank_process_pcm16.argtypes = [vp, ci, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.bnhip_resampler_bank_flush_pcm16.argtypes = [vp, ci, vp, vp, C.c_size_t, vp]
+    lib.bnhip_windows_write_resampled.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    lib.bnhip_resampler_bank_destroy.argtypes = [vp]
+    lib.bnhip_resampler_bank_destroy.restype = None
+    return lib
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_bank_symbols_exported(built_lib):
+    lib = C.CDLL(built_lib)
+    for s in BANK_SYMBOLS:
+        assert hasattr(lib, s), s
+        assert s in host.SYMBOLS, s
+
+
+def test_bank_null_and_invalid_arguments(built_lib):
+    lib = _lib()
+    h = C.c_void_p(123)
+    one = (C.c_int * 1)(0)
+    assert lib.bnhip_resampler_bank_create(0, 48000, 32000, 4, None) == host.E_INVALID
+    assert lib.bnhip_resampler_bank_create(0, 0, 32000, 4, C.byref(h)) == host.E_INVALID and not h.value
+    assert lib.bnhip_resampler_bank_create(0, 48000, -1, 4, C.byref(h)) == host.E_INVALID
+    assert lib.bnhip_resampler_bank_create(0, 48000, 32000, 0, C.byref(h)) == host.E_INVALID
+    assert lib.bnhip_resampler_bank_add_stream(None, C.byref(C.c_int())) == host.E_INVALID
+    assert lib.bnhip_resampler_bank_remove_stream(None, 0) == host.E_INVALID
+    assert lib.bnhip_resampler_bank_estimate(None, 100) == 0
+    assert lib.bnhip_resampler_bank_process_pcm16(None, 1, one, None, one, None, 0, None) == host.E_INVALID
+    assert lib.bnhip_resampler_bank_flush_pcm16(None, 1, one, None, 0, None) == host.E_INVALID
+    w = S.NativeWindows(4, 8, max_batch=2)
+    assert lib.bnhip_windows_write_resampled(w._h, None, 1, one, one, None, one) == host.E_INVALID
+    assert lib.bnhip_windows_write_resampled(None, None, 1, one, one, None, one) == host.E_INVALID
+    w.close()
+    lib.bnhip_resampler_bank_destroy(None)                          # NULL-safe like Close()
+
+
+def test_bank_equal_rates_is_null(built_lib):
+    lib = _lib()
+    h = C.c_void_p(123)
+    assert lib.bnhip_resampler_bank_create(0, 32000, 32000, 8, C.byref(h)) == host.BNHIP_OK and not h.value
+    assert host.ResamplerBank.new(48000, 48000) is None
+
+
+@pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="GPU present")
+def test_bank_without_device_is_a_loud_error(built_lib):
+    lib = _lib()
+    h = C.c_void_p()
+    assert lib.bnhip_resampler_bank_create(0, 48000, 32000, 8, C.byref(h)) == host.E_NO_DEVICE and not h.value
+    with pytest.raises(host.ErrHIPUnavailable):
+        host.ResamplerBank(48000, 32000)
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+def _pcm(n, rate, seed):
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / rate
+    x = 0.45 * np.sin(2 * np.pi * 997.0 * t) + 0.3 * np.sin(2 * np.pi * 6151.0 * t) + 0.1 * rng.standard_normal(n)
+    return np.clip(x * 32767 * 1.2, -32768, 32767).astype("<i2")      # includes clipped peaks
+
+
+def _ragged(rng, rate):
+    r = rng.random()
+    if r < 0.06:
+        return 0
+    if r < 0.12:
+        return 1
+    if r < 0.2:
+        return int(rng.integers(2, 40)) * 2 + 1                      # odd
+    return int(rng.integers(rate // 20, rate // 6))
+
+
+@pytest.mark.gpu
+def test_bank_bit_exact_against_one_shot_and_stream_resampler(gpu):
+    """256 streams over five rate pairs (64 at 256k -> 48k), random ragged frames per tick (0, 1 and odd sizes included), some
+    streams skipping ticks and some appearing twice in one call: per stream, concatenated outputs + flush == the one-shot
+    resample of the whole stream byte for byte, and per-frame byte counts == a StreamResampler fed the same frames."""
+    pairs = [(48000, 32000, 64), (44100, 48000, 48), (16000, 48000, 40), (22050, 48000, 40), (256000, 48000, 64)]
+    assert sum(p[2] for p in pairs) == 256
+    rng = np.random.default_rng(2024)
+    ticks = 10
+    for fr, to, n_streams in pairs:
+        bank = host.ResamplerBank(fr, to, max_streams=n_streams)
+        ids = [bank.add_stream() for _ in range(n_streams)]
+        assert sorted(ids) == list(range(n_streams))
+        src = {s: _pcm(fr * 2, fr, 1000 * fr + s) for s in ids}
+        pos = {s: 0 for s in ids}
+        got = {s: [] for s in ids}
+        frames = {s: [] for s in ids}
+        for _ in range(ticks):
+            items, later = [], []
+            for s in ids:
+                if rng.random() < 0.15:                              # skips this tick
+                    continue
+                for rep in range(2 if rng.random() < 0.1 else 1):    # sometimes twice in one call, apart
+                    n = min(_ragged(rng, fr), len(src[s]) - pos[s])
+                    (later if rep else items).append((s, src[s][pos[s]:pos[s] + n].tobytes()))
+                    pos[s] += n
+            items += later
+            outs = bank.process(items)
+            assert len(outs) == len(items)
+            for (s, b), o in zip(items, outs):
+                got[s].append(o)
+                frames[s].append(b)
+        tails = bank.flush(ids, cap=1 << 20)
+        for s, tail in zip(ids, tails):
+            whole = src[s][:pos[s]]
+            assert b"".join(got[s]) + tail == host.Resampler(fr, to).resample_to(whole.tobytes()), (fr, to, s)
+        for s in ids[:16]:                                           # per-frame split == the single-stream entry's
+            rs = host.StreamResampler(fr, to)
+            assert [len(rs.resample_into(b)) for b in frames[s]] == [len(o) for o in got[s]], (fr, to, s)
+            rs.close()
+        bank.close()
+
+
+@pytest.mark.gpu
+def test_bank_stream_lifetime(gpu):
+    """A removed and reused slot starts a fresh stream; removing one stream changes no other stream's bytes."""
+    fr, to = 48000, 32000
+    a, b = _pcm(20000, fr, 1), _pcm(20000, fr, 2)
+    bank = host.ResamplerBank(fr, to, max_streams=4)
+    s0, s1 = bank.add_stream(), bank.add_stream()
+    o1 = bank.process([(s0, a[:4800].tobytes()), (s1, b[:4800].tobytes())])
+    bank.remove_stream(s0)
+    with pytest.raises(host.HipError):
+        bank.process([(s0, a[4800:9600].tobytes())])                 # removed: E_INVALID
+    s2 = bank.add_stream()
+    assert s2 == s0                                                  # slot reused ...
+    o2 = bank.process([(s2, b[:4800].tobytes()), (s1, b[4800:20000].tobytes())])
+    t = bank.flush([s2, s1], cap=1 << 16)
+    fresh = host.StreamResampler(fr, to)
+    assert o2[0] == fresh.resample_into(b[:4800].tobytes())         # ... with fresh state
+    one = host.Resampler(fr, to).resample_to(b.tobytes())
+    assert o1[1] + o2[1] + t[1] == one                               # s1 untouched by s0's removal
+    bank.close()
+
+
+@pytest.mark.gpu
+def test_bank_error_paths_leave_state_untouched(gpu):
+    fr, to = 44100, 48000
+    x = _pcm(30000, fr, 9)
+    lib = _lib()
+    bank = host.ResamplerBank(fr, to, max_streams=3)
+    s0, s1 = bank.add_stream(), bank.add_stream()
+    first = bank.process([(s0, x[:4410].tobytes()), (s1, x[:1000].tobytes())])
+    need = bank.estimate_output_bytes(4410 * 2) // 2 + bank.estimate_output_bytes(3000 * 2) // 2
+    with pytest.raises(host.HipError) as e:                          # destination too small: nothing advances
+        bank.process([(s0, x[4410:8820].tobytes()), (s1, x[1000:4000].tobytes())], out_cap=need - 1)
+    assert e.value.code == host.E_INVALID
+    with pytest.raises(host.HipError) as e:                          # unknown stream among valid ones
+        bank.process([(s0, x[4410:8820].tobytes()), (2, x[1000:4000].tobytes())])
+    assert e.value.code == host.E_INVALID
+    # a negative length
+    streams, lens = (C.c_int * 1)(s0), (C.c_int * 1)(-2)
+    ptrs, out, cnt = (C.c_void_p * 1)(x.ctypes.data), np.zeros(64, np.int16), np.zeros(1, np.int32)
+    assert lib.bnhip_resampler_bank_process_pcm16(bank._h, 1, streams, ptrs, lens, out.ctypes.data, 64, cnt.ctypes.data) == host.E_INVALID
+    second = bank.process([(s0, x[4410:8820].tobytes()), (s1, x[1000:4000].tobytes())])
+    rs0, rs1 = host.StreamResampler(fr, to), host.StreamResampler(fr, to)
+    assert first == [rs0.resample_into(x[:4410].tobytes()), rs1.resample_into(x[:1000].tobytes())]
+    assert second == [rs0.resample_into(x[4410:8820].tobytes()), rs1.resample_into(x[1000:4000].tobytes())]
+    # windows: a removed source (or stream) fails the whole call, no stream advanced and no ring written
+    w = S.NativeWindows(64, 64, max_batch=4)
+    a, b = w.add_source("a", 4096), w.add_source("b", 4096)
+    w.remove_source(b)
+    with pytest.raises(S.StreamError):
+        bank.write_windows(w, [(s0, a, x[8820:9000].tobytes()), (s1, b, x[4000:4100].tobytes())])
+    bank.remove_stream(s1)
+    with pytest.raises(S.StreamError):
+        bank.write_windows(w, [(s0, a, x[8820:9000].tobytes()), (s1, a, x[4000:4100].tobytes())])
+    assert w.stats(a) == (0, 0, 0)
+    bank.write_windows(w, [(s0, a, x[8820:9000].tobytes()), (s0, a, b"")])
+    want = rs0.resample_into(x[8820:9000].tobytes())
+    assert w.stats(a) == (2, 0, len(want))                           # one ring write per input frame, the empty one included
+    w.close()
+    bank.close()
