@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdlib>
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "eq_bank.h"
 #include "hostpipe.h"
 #include "numa.h"
 #include "model_onnx.h"
@@ -1548,6 +1550,348 @@ int bnhip_windows_write_resampled(bnhip_windows* w, bnhip_resampler_bank* b, int
 
 void bnhip_resampler_bank_destroy(bnhip_resampler_bank* b) {
     try { bank_free(b); } catch (...) {}
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ equalizer bank
+// The analysis route's EQ + gain (AudioRouter.applyProcessing, internal/audiocore/router.go:1006-1080, the route the analysis
+// BufferConsumer gets from AddRoute with the source's chain and gain, internal/analysis/audio_pipeline_service.go:1005-1006)
+// for every source of a bank at once: one H2D copy (descriptors + coefficients + packed PCM16), one k_eq_bank launch, one D2H
+// copy and one synchronise per call, on ONE HIP stream per bank.  The chains live on the host and travel with each call, so
+// set_chain and reset touch no device memory; each stream's filter state is a fixed pair of device slabs of
+// EQ_MAX_STAGES x {in1, in2, out1, out2} doubles, read from one and written to the other, the parity flipped on commit.
+struct bnhip_eq_bank {
+    struct Stream {
+        bool live = false;
+        bool fresh = true;              // the next call starts from zero state (new stream, new chain, reset)
+        int parity = 0;                 // slab read by the next call
+        int n_stages = 0;
+        double gain = 1.0;
+        double coef[EQ_MAX_STAGES][5] = {};   // {b0, b1, b2, a1, a2} / a0 per stage: filter f, pass p, in chain order
+        bool passthrough() const { return n_stages == 0 && gain == 1.0; }
+    };
+    std::mutex mu;                      // calls on one bank are serialised
+    int device = 0;
+    std::vector<Stream> st;
+    double* d_state = nullptr;          // [max_streams][2][EQ_MAX_STAGES][4]
+    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // descriptors | coefficients | PCM16 (bytes)
+    int16_t* h_out = nullptr; void* d_out = nullptr; size_t out_cap = 0;         // packed outputs (bytes)
+    hipStream_t stream = nullptr;
+};
+
+namespace {
+
+constexpr int EQ_SLAB = EQ_MAX_STAGES * 4;     // doubles of one state slab
+
+void eq_free(bnhip_eq_bank* b) {
+    if (!b) return;
+    hipSetDevice(b->device);
+    if (b->stream) { hipStreamSynchronize(b->stream); hipStreamDestroy(b->stream); }
+    for (void* p : {(void*)b->d_state, b->d_stage, b->d_out}) if (p) hipFree(p);
+    for (void* p : {(void*)b->h_stage, (void*)b->h_out}) if (p) hipHostFree(p);
+    (void)hipGetLastError();
+    delete b;
+}
+
+bool eq_stream_ok(const bnhip_eq_bank* b, int s) { return s >= 0 && (size_t)s < b->st.size() && b->st[s].live; }
+
+// One call: frames f = 0..n_frames-1 of streams[f] (a stream may appear several times; its frames are consumed in call order).
+// Checks everything, stages everything, runs, synchronises, commits, then hands frame f's output (as many samples as its input)
+// to deliver(f, samples, count).  A pass-through stream (no stages, gain 1) is not converted: its frames are delivered as they
+// are, as the reference skips the route's processing (router.go:848).  Until the commit nothing of any stream changes.
+template <class Deliver>
+int eq_run(bnhip_eq_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, long long out_cap,
+           Deliver deliver) {
+    if (n_frames < 0 || (n_frames > 0 && (!streams || !n_in))) return set_err(BNHIP_E_INVALID, "bad equalizer bank arguments");
+    struct Group { int stream; long long n = 0; int in_off = 0; };
+    std::vector<Group> groups;
+    std::vector<int> group_of(b->st.size(), -1), frame_group(n_frames);
+    long long total = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const int s = streams[f];
+        if (!eq_stream_ok(b, s)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(s));
+        if (n_in[f] < 0) return set_err(BNHIP_E_INVALID, "negative frame length");
+        if (n_in[f] > 0 && (!frames || !frames[f])) return set_err(BNHIP_E_INVALID, "frame pointer is NULL");
+        if (group_of[s] < 0) {
+            group_of[s] = (int)groups.size();
+            Group g; g.stream = s;
+            groups.push_back(g);
+        }
+        frame_group[f] = group_of[s];
+        groups[group_of[s]].n += n_in[f];
+        total += n_in[f];
+    }
+    if (total > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");      // convert/pcm.go:142-145
+    // processed streams with samples, packed back to back; a wave runs 4 of them, every row of it as many steps as its longest
+    std::vector<int> run;
+    long long in_total = 0;
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        Group& g = groups[gi];
+        if (g.n == 0 || b->st[g.stream].passthrough()) continue;
+        g.in_off = (int)in_total;
+        in_total += g.n;
+        run.push_back((int)gi);
+    }
+    if (in_total > INT32_MAX / 4) return set_err(BNHIP_E_INVALID, "equalizer bank call too large");
+    if (!run.empty()) {
+        std::vector<EqBankDesc> desc(run.size());
+        std::vector<double> coef;
+        for (size_t k = 0; k < run.size(); k++) {
+            const Group& g = groups[run[k]];
+            const auto& S = b->st[g.stream];
+            EqBankDesc& d = desc[k];
+            d.gain = S.gain; d.in_off = g.in_off; d.n = (int)g.n; d.n_stages = S.n_stages;
+            d.coef_off = (int)coef.size();
+            for (int s = 0; s < S.n_stages; s++) coef.insert(coef.end(), S.coef[s], S.coef[s] + 5);
+            d.st_rd = S.fresh ? -1 : (g.stream * 2 + S.parity) * EQ_SLAB;
+            d.st_wr = (g.stream * 2 + (S.parity ^ 1)) * EQ_SLAB;
+        }
+        for (size_t k0 = 0; k0 < desc.size(); k0 += 4) {
+            long long steps = 0;
+            for (size_t k = k0; k < std::min(desc.size(), k0 + 4); k++)
+                steps = std::max<long long>(steps, desc[k].n + std::max(desc[k].n_stages, 1) - 1);
+            desc[k0].blk_steps = (int)((steps + 15) / 16 * 16);
+        }
+        hipSetDevice(b->device);
+        const size_t desc_bytes = desc.size() * sizeof(EqBankDesc), coef_bytes = coef.size() * sizeof(double);
+        const size_t stage_bytes = desc_bytes + coef_bytes + (size_t)in_total * 2;
+        if (!bank_grow((void**)&b->h_stage, &b->d_stage, &b->stage_cap, stage_bytes))
+            return set_err(BNHIP_E_NOMEM, "allocation failed (equalizer bank staging)");
+        if (!bank_grow((void**)&b->h_out, &b->d_out, &b->out_cap, (size_t)in_total * 2))
+            return set_err(BNHIP_E_NOMEM, "allocation failed (equalizer bank output)");
+        memcpy(b->h_stage, desc.data(), desc_bytes);
+        if (coef_bytes) memcpy(b->h_stage + desc_bytes, coef.data(), coef_bytes);
+        int16_t* pk = reinterpret_cast<int16_t*>(b->h_stage + desc_bytes + coef_bytes);
+        std::vector<long long> fill(groups.size(), 0);
+        for (int f = 0; f < n_frames; f++) {
+            const Group& g = groups[frame_group[f]];
+            if (n_in[f] <= 0 || b->st[g.stream].passthrough()) continue;
+            memcpy(pk + g.in_off + fill[frame_group[f]], frames[f], (size_t)n_in[f] * 2);
+            fill[frame_group[f]] += n_in[f];
+        }
+        const uint8_t* ds = static_cast<const uint8_t*>(b->d_stage);
+        hipError_t he = hipMemcpyAsync(b->d_stage, b->h_stage, stage_bytes, hipMemcpyHostToDevice, b->stream);
+        if (he == hipSuccess) {
+            launch_eq_bank(reinterpret_cast<const EqBankDesc*>(ds), (int)desc.size(), reinterpret_cast<const double*>(ds + desc_bytes),
+                           reinterpret_cast<const int16_t*>(ds + desc_bytes + coef_bytes), b->d_state, static_cast<int16_t*>(b->d_out),
+                           b->stream);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess)
+            he = hipMemcpyAsync(b->h_out, b->d_out, (size_t)in_total * 2, hipMemcpyDeviceToHost, b->stream);
+        const hipError_t hs = hipStreamSynchronize(b->stream);
+        if (he == hipSuccess) he = hs;
+        if (he != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_RUNTIME, std::string("equalizer bank: ") + hipGetErrorString(he)); }
+    }
+    // ---- commit: everything above succeeded
+    for (int gi : run) {
+        auto& S = b->st[groups[gi].stream];
+        S.parity ^= 1;
+        S.fresh = false;
+    }
+    std::vector<long long> taken(groups.size(), 0);
+    for (int f = 0; f < n_frames; f++) {
+        const int gi = frame_group[f];
+        const Group& g = groups[gi];
+        if (b->st[g.stream].passthrough()) deliver(f, frames ? frames[f] : nullptr, n_in[f]);
+        else deliver(f, b->h_out + g.in_off + taken[gi], n_in[f]);
+        taken[gi] += n_in[f];
+    }
+    return BNHIP_OK;
+}
+
+// RBJ audio-EQ-cookbook biquads (R. Bristow-Johnson, "Cookbook formulae for audio EQ biquad filter coefficients"), raw
+// {b0, b1, b2, a0, a1, a2}.  w0 = 2 pi f / Fs; alpha = sin(w0) / (2 Q), or for a bandwidth in octaves
+// alpha = sin(w0) sinh(ln(2) / 2 * BW * w0 / sin(w0)); A = 10^(dBgain / 40).
+double eq_hz_to_octaves(double f, double width) {         // equalizer.go hzToOctaves: the band's lower edge stays above 1 Hz
+    double half = width / 2.0;
+    if (half >= f - 1.0) half = f - 1.0;
+    if (half <= 0) half = 0.01;
+    double lower = f - half;
+    if (lower <= 0) lower = 0.01;
+    return std::log2((f + half) / lower);
+}
+
+int eq_design(int type, double fs, double f, double q, double width, double gain_db, int passes, double* o) {
+    if (passes < 1) return set_err(BNHIP_E_INVALID, "passes must be 1 or greater");
+    const bool by_width = type == BNHIP_EQ_BANDPASS || type == BNHIP_EQ_BANDREJECT || type == BNHIP_EQ_PEAKING;
+    if (by_width && f <= 0) return set_err(BNHIP_E_INVALID, "frequency must be greater than 0");
+    if (by_width && width <= 0) return set_err(BNHIP_E_INVALID, "width must be greater than 0");
+    const double w0 = 2.0 * M_PI * f / fs, cw = std::cos(w0), sw = std::sin(w0);
+    const double alpha = by_width ? sw * std::sinh(std::log(2.0) / 2.0 * eq_hz_to_octaves(f, width) * w0 / sw) : sw / (2.0 * q);
+    const double A = std::pow(10.0, gain_db / 40.0);
+    double b0, b1, b2, a0, a1, a2;
+    switch (type) {
+    case BNHIP_EQ_LOWPASS:
+        b0 = (1.0 - cw) / 2.0; b1 = 1.0 - cw; b2 = b0; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
+    case BNHIP_EQ_HIGHPASS:
+        b0 = (1.0 + cw) / 2.0; b1 = -(1.0 + cw); b2 = b0; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
+    case BNHIP_EQ_ALLPASS:
+        b0 = 1.0 - alpha; b1 = -2.0 * cw; b2 = 1.0 + alpha; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
+    case BNHIP_EQ_BANDPASS:        // constant 0 dB peak gain
+        b0 = alpha; b1 = 0.0; b2 = -alpha; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
+    case BNHIP_EQ_BANDREJECT:
+        b0 = 1.0; b1 = -2.0 * cw; b2 = 1.0; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
+    case BNHIP_EQ_LOWSHELF: {
+        const double bs = std::sqrt(A) / q * sw;     // 2 sqrt(A) alpha with the shelf's Q
+        b0 = A * ((A + 1.0) - (A - 1.0) * cw + bs); b1 = 2.0 * A * ((A - 1.0) - (A + 1.0) * cw); b2 = A * ((A + 1.0) - (A - 1.0) * cw - bs);
+        a0 = (A + 1.0) + (A - 1.0) * cw + bs; a1 = -2.0 * ((A - 1.0) + (A + 1.0) * cw); a2 = (A + 1.0) + (A - 1.0) * cw - bs;
+        break;
+    }
+    case BNHIP_EQ_HIGHSHELF: {
+        const double bs = std::sqrt(A) / q * sw;
+        b0 = A * ((A + 1.0) + (A - 1.0) * cw + bs); b1 = -2.0 * A * ((A - 1.0) + (A + 1.0) * cw); b2 = A * ((A + 1.0) + (A - 1.0) * cw - bs);
+        a0 = (A + 1.0) - (A - 1.0) * cw + bs; a1 = 2.0 * ((A - 1.0) - (A + 1.0) * cw); a2 = (A + 1.0) - (A - 1.0) * cw - bs;
+        break;
+    }
+    case BNHIP_EQ_PEAKING:
+        b0 = 1.0 + alpha * A; b1 = -2.0 * cw; b2 = 1.0 - alpha * A; a0 = 1.0 + alpha / A; a1 = -2.0 * cw; a2 = 1.0 - alpha / A; break;
+    default:
+        return set_err(BNHIP_E_INVALID, "unknown filter type " + std::to_string(type));
+    }
+    const double r[6] = {b0, b1, b2, a0, a1, a2};
+    for (double v : r)
+        if (!std::isfinite(v)) return set_err(BNHIP_E_INVALID, "filter parameters give non-finite coefficients");
+    if (a0 == 0.0) return set_err(BNHIP_E_INVALID, "filter parameters give a0 == 0");
+    memcpy(o, r, sizeof r);
+    return BNHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bnhip_eq_bank_create(int device, int max_streams, bnhip_eq_bank** out) {
+    if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (max_streams < 1 || max_streams > (1 << 20)) return set_err(BNHIP_E_INVALID, "max_streams must be in [1, 1048576]");
+    bnhip_eq_bank* b = nullptr;
+    BN_GUARD_BEGIN
+    int rc = bnhip_init(nullptr);
+    if (rc) return rc;
+    if (device < 0 || device >= g_devices) return set_err(BNHIP_E_INVALID, "device ordinal out of range");
+    hipSetDevice(device);
+    b = new bnhip_eq_bank();
+    b->device = device;
+    b->st.resize(max_streams);
+    hipError_t he = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (he == hipSuccess) he = hipMalloc((void**)&b->d_state, (size_t)max_streams * 2 * EQ_SLAB * sizeof(double));
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        eq_free(b); b = nullptr;
+        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string("equalizer bank create: ") + hipGetErrorString(he));
+    }
+    *out = b;
+    return BNHIP_OK;
+    BN_GUARD_END(eq_free(b))
+}
+
+int bnhip_eq_bank_add_stream(bnhip_eq_bank* b, int* out_stream) {
+    if (!b || !out_stream) return set_err(BNHIP_E_INVALID, "NULL argument");
+    *out_stream = -1;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    for (size_t s = 0; s < b->st.size(); s++) {
+        if (b->st[s].live) continue;
+        b->st[s] = bnhip_eq_bank::Stream();              // no chain, gain 1, zero state
+        b->st[s].live = true;
+        *out_stream = (int)s;
+        return BNHIP_OK;
+    }
+    return set_err(BNHIP_E_INVALID, "equalizer bank is full (max_streams)");
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_eq_bank_remove_stream(bnhip_eq_bank* b, int stream) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (!eq_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(stream));
+    b->st[stream].live = false;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_eq_bank_set_chain(bnhip_eq_bank* b, int stream, const double* sections, int n_sections, const int* passes, double gain_linear) {
+    if (!b || n_sections < 0 || (n_sections > 0 && (!sections || !passes))) return set_err(BNHIP_E_INVALID, "bad equalizer chain arguments");
+    if (!std::isfinite(gain_linear)) return set_err(BNHIP_E_INVALID, "gain is not finite");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (!eq_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(stream));
+    bnhip_eq_bank::Stream ns;
+    long long stages = 0;
+    for (int k = 0; k < n_sections; k++) {
+        const double* c = sections + 6 * k;           // {b0, b1, b2, a0, a1, a2}
+        for (int j = 0; j < 6; j++)
+            if (!std::isfinite(c[j])) return set_err(BNHIP_E_INVALID, "section " + std::to_string(k) + " has a non-finite coefficient");
+        if (c[3] == 0.0) return set_err(BNHIP_E_INVALID, "section " + std::to_string(k) + " has a0 == 0");
+        if (passes[k] < 1) return set_err(BNHIP_E_INVALID, "passes must be 1 or greater");
+        stages += passes[k];
+        if (stages > EQ_MAX_STAGES)
+            return set_err(BNHIP_E_UNSUPPORTED, "equalizer chain has more than " + std::to_string(EQ_MAX_STAGES) + " stages (filters x passes)");
+        // NewFilter's precomputed coefficients (equalizer.go:112-136): each divided by a0
+        const double n5[5] = {c[0] / c[3], c[1] / c[3], c[2] / c[3], c[4] / c[3], c[5] / c[3]};
+        for (int p = 0; p < passes[k]; p++) memcpy(ns.coef[ns.n_stages++], n5, sizeof n5);
+    }
+    ns.gain = gain_linear;
+    ns.live = true;
+    b->st[stream] = ns;                                   // a fresh chain: zero state (UpdateFilterChain installs new filters)
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_eq_bank_reset(bnhip_eq_bank* b, int stream) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (!eq_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(stream));
+    b->st[stream].fresh = true;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_eq_bank_process_pcm16(bnhip_eq_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in,
+                                int16_t* out, size_t out_cap, int* out_count) {
+    if (!b || (n_frames > 0 && (!out || !out_count))) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    long long pos = 0;
+    return eq_run(b, n_frames, streams, frames, n_in, (long long)std::min<size_t>(out_cap, INT64_MAX),
+                  [&](int f, const int16_t* p, int n) {
+                      if (n > 0) memcpy(out + pos, p, (size_t)n * 2);
+                      out_count[f] = n;
+                      pos += n;
+                  });
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_windows_write_equalized(bnhip_windows* w, bnhip_eq_bank* b, int n_frames, const int* streams, const int* sources,
+                                  const int16_t* const* frames, const int* n_in) {
+    if (!w || !b || (n_frames > 0 && !sources)) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    for (int f = 0; f < n_frames; f++)
+        if (!w->a->stats(sources[f], nullptr, nullptr, nullptr)) return set_err(BNHIP_E_INVALID, "no such source: " + std::to_string(sources[f]));
+    std::lock_guard<std::mutex> lk(b->mu);
+    // one ring write per frame, as BufferConsumer.Write gets one processed frame per capture frame
+    return eq_run(b, n_frames, streams, frames, n_in, INT64_MAX,
+                  [&](int f, const int16_t* p, int n) { (void)w->a->write(sources[f], p, (size_t)n * 2); });
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_eq_design(int type, double sample_rate, double frequency, double q, double width_hz, double gain_db, int passes,
+                    double* section6) {
+    if (!section6) return set_err(BNHIP_E_INVALID, "section6 is NULL");
+    if (!std::isfinite(sample_rate) || !std::isfinite(frequency) || !std::isfinite(q) || !std::isfinite(width_hz) ||
+        !std::isfinite(gain_db) || sample_rate <= 0)
+        return set_err(BNHIP_E_INVALID, "filter parameters must be finite and the sample rate positive");
+    BN_GUARD_BEGIN
+    return eq_design(type, sample_rate, frequency, q, width_hz, gain_db, passes, section6);
+    BN_GUARD_END((void)0)
+}
+
+void bnhip_eq_bank_destroy(bnhip_eq_bank* b) {
+    try { eq_free(b); } catch (...) {}
 }
 
 }  // extern "C"

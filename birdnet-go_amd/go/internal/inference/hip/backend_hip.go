@@ -64,6 +64,15 @@ typedef int  (*fn_rb_process_pcm16)(bnhip_resampler_bank*, int, const int*, cons
 typedef int  (*fn_rb_flush_pcm16)(bnhip_resampler_bank*, int, const int*, int16_t*, size_t, int*);
 typedef int  (*fn_win_write_resampled)(bnhip_windows*, bnhip_resampler_bank*, int, const int*, const int*, const int16_t* const*, const int*);
 typedef void (*fn_rb_destroy)(bnhip_resampler_bank*);
+typedef struct bnhip_eq_bank bnhip_eq_bank;
+typedef int  (*fn_eq_create)(int, int, bnhip_eq_bank**);
+typedef int  (*fn_eq_add_stream)(bnhip_eq_bank*, int*);
+typedef int  (*fn_eq_remove_stream)(bnhip_eq_bank*, int);
+typedef int  (*fn_eq_set_chain)(bnhip_eq_bank*, int, const double*, int, const int*, double);
+typedef int  (*fn_eq_reset)(bnhip_eq_bank*, int);
+typedef int  (*fn_eq_process_pcm16)(bnhip_eq_bank*, int, const int*, const int16_t* const*, const int*, int16_t*, size_t, int*);
+typedef int  (*fn_win_write_equalized)(bnhip_windows*, bnhip_eq_bank*, int, const int*, const int*, const int16_t* const*, const int*);
+typedef void (*fn_eq_destroy)(bnhip_eq_bank*);
 
 typedef struct {
     void* handle;
@@ -79,6 +88,8 @@ typedef struct {
     fn_rb_create rb_create; fn_rb_add_stream rb_add_stream; fn_rb_remove_stream rb_remove_stream; fn_rb_estimate rb_estimate;
     fn_rb_process_pcm16 rb_process_pcm16; fn_rb_flush_pcm16 rb_flush_pcm16; fn_win_write_resampled win_write_resampled;
     fn_rb_destroy rb_destroy;
+    fn_eq_create eq_create; fn_eq_add_stream eq_add_stream; fn_eq_remove_stream eq_remove_stream; fn_eq_set_chain eq_set_chain;
+    fn_eq_reset eq_reset; fn_eq_process_pcm16 eq_process_pcm16; fn_win_write_equalized win_write_equalized; fn_eq_destroy eq_destroy;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -117,6 +128,10 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(rb_remove_stream, "bnhip_resampler_bank_remove_stream"); BN_RESOLVE(rb_estimate, "bnhip_resampler_bank_estimate");
     BN_RESOLVE(rb_process_pcm16, "bnhip_resampler_bank_process_pcm16"); BN_RESOLVE(rb_flush_pcm16, "bnhip_resampler_bank_flush_pcm16");
     BN_RESOLVE(win_write_resampled, "bnhip_windows_write_resampled"); BN_RESOLVE(rb_destroy, "bnhip_resampler_bank_destroy");
+    BN_RESOLVE(eq_create, "bnhip_eq_bank_create"); BN_RESOLVE(eq_add_stream, "bnhip_eq_bank_add_stream");
+    BN_RESOLVE(eq_remove_stream, "bnhip_eq_bank_remove_stream"); BN_RESOLVE(eq_set_chain, "bnhip_eq_bank_set_chain");
+    BN_RESOLVE(eq_reset, "bnhip_eq_bank_reset"); BN_RESOLVE(eq_process_pcm16, "bnhip_eq_bank_process_pcm16");
+    BN_RESOLVE(win_write_equalized, "bnhip_windows_write_equalized"); BN_RESOLVE(eq_destroy, "bnhip_eq_bank_destroy");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -182,6 +197,23 @@ static inline int bnbind_win_write_resampled(bnhip_windows* w, bnhip_resampler_b
     return BN.win_write_resampled(w, b, n, st, src, f, n_in);
 }
 static inline void bnbind_rb_destroy(bnhip_resampler_bank* b) { if (BN.rb_destroy) BN.rb_destroy(b); }
+// equalizer bank (static inline, as the resampler bank's)
+static inline int bnbind_eq_create(int dev, int max_streams, bnhip_eq_bank** b) { return BN.eq_create(dev, max_streams, b); }
+static inline int bnbind_eq_add_stream(bnhip_eq_bank* b, int* s) { return BN.eq_add_stream(b, s); }
+static inline int bnbind_eq_remove_stream(bnhip_eq_bank* b, int s) { return BN.eq_remove_stream(b, s); }
+static inline int bnbind_eq_set_chain(bnhip_eq_bank* b, int s, const double* sec, int n, const int* passes, double gain) {
+    return BN.eq_set_chain(b, s, sec, n, passes, gain);
+}
+static inline int bnbind_eq_reset(bnhip_eq_bank* b, int s) { return BN.eq_reset(b, s); }
+static inline int bnbind_eq_process_pcm16(bnhip_eq_bank* b, int n, const int* st, const int16_t* const* f, const int* n_in,
+                                          int16_t* out, size_t cap, int* cnt) {
+    return BN.eq_process_pcm16(b, n, st, f, n_in, out, cap, cnt);
+}
+static inline int bnbind_win_write_equalized(bnhip_windows* w, bnhip_eq_bank* b, int n, const int* st, const int* src,
+                                             const int16_t* const* f, const int* n_in) {
+    return BN.win_write_equalized(w, b, n, st, src, f, n_in);
+}
+static inline void bnbind_eq_destroy(bnhip_eq_bank* b) { if (BN.eq_destroy) BN.eq_destroy(b); }
 // frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
 // the pointer table points at byte offset off[k] of the staging block
 static inline void bnbind_rb_point(const int16_t** ptrs, const char* stage, const int* off, int n) {
@@ -1243,6 +1275,228 @@ func (w *WindowAssembler) WriteResampled(bank *ResamplerBank, streams, sources [
 	defer runtime.UnlockOSThread()
 	if rc := C.bnbind_win_write_resampled(w.h, bank.h, C.int(len(frames)), &st[0], &src[0], ptrs, &lens[0]); rc != 0 {
 		return fmt.Errorf("hip: windows_write_resampled failed (%d): %s", int(rc), lastError())
+	}
+	return nil
+}
+
+// EqualizerBank is the analysis route's processing, AudioRouter.applyProcessing (internal/audiocore/router.go:1006-1080), for
+// many sources: a stream per source holds its FilterChain and gainLinear, and each call converts, filters, scales and
+// truncates all the frames it is given in one device call (bnhip_eq_bank_*).  Every stream's bytes are those of the
+// reference's float64 arithmetic for the same sections.  Calls are serialised on the bank.
+type EqualizerBank struct {
+	mu       sync.Mutex
+	h        *C.bnhip_eq_bank
+	stage    unsafe.Pointer // C memory: this call's frames back to back
+	stageCap int
+	ptrs     unsafe.Pointer // C memory: one const int16_t* per frame
+	ptrsCap  int
+}
+
+func NewEqualizerBank(maxStreams, device int) (*EqualizerBank, error) {
+	var h *C.bnhip_eq_bank
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_eq_create(C.int(device), C.int(maxStreams), &h); rc != 0 || h == nil {
+		return nil, fmt.Errorf("failed to create equalizer bank: %s", lastError())
+	}
+	return &EqualizerBank{h: h}, nil
+}
+
+// AddStream starts a stream with no chain and gain 1 (pass-through); slots of removed streams are reused with fresh state.
+func (b *EqualizerBank) AddStream() (int, error) {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return -1, errors.New("hip: equalizer bank is closed")
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var s C.int
+	if rc := C.bnbind_eq_add_stream(b.h, &s); rc != 0 {
+		return -1, fmt.Errorf("hip: eq_bank_add_stream failed (%d): %s", int(rc), lastError())
+	}
+	return int(s), nil
+}
+
+func (b *EqualizerBank) RemoveStream(stream int) error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return nil
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_eq_remove_stream(b.h, C.int(stream)); rc != 0 {
+		return fmt.Errorf("hip: eq_bank_remove_stream failed (%d): %s", int(rc), lastError())
+	}
+	return nil
+}
+
+// SetChain installs a route's chain and gain (AddRoute / UpdateFilterChain) with zero state.  More than 16 stages (the sum
+// of passes) is refused; a refused call leaves the old chain and its state.
+func (b *EqualizerBank) SetChain(stream int, sections []EqualizerSection, gainLinear float64) error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return errors.New("hip: equalizer bank is closed")
+	}
+	coef := make([]C.double, 6*len(sections)+1)
+	passes := make([]C.int, len(sections)+1)
+	for k, s := range sections {
+		for j, v := range s.Coef {
+			coef[6*k+j] = C.double(v)
+		}
+		passes[k] = C.int(s.Passes)
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_eq_set_chain(b.h, C.int(stream), &coef[0], C.int(len(sections)), &passes[0], C.double(gainLinear)); rc != 0 {
+		return fmt.Errorf("hip: eq_bank_set_chain failed (%d): %s", int(rc), lastError())
+	}
+	return nil
+}
+
+// Reset is FilterChain.Reset: zero state, same chain.
+func (b *EqualizerBank) Reset(stream int) error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return errors.New("hip: equalizer bank is closed")
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_eq_reset(b.h, C.int(stream)); rc != 0 {
+		return fmt.Errorf("hip: eq_bank_reset failed (%d): %s", int(rc), lastError())
+	}
+	return nil
+}
+
+// stageLocked copies the frames into the bank's C staging (as ResamplerBank.stageLocked).
+func (b *EqualizerBank) stageLocked(frames [][]byte) (**C.int16_t, []C.int, error) {
+	total := 0
+	for _, f := range frames {
+		if len(f)%bytesPerSample != 0 {
+			return nil, nil, fmt.Errorf("input length %d is not a multiple of %d", len(f), bytesPerSample)
+		}
+		total += len(f)
+	}
+	if total > b.stageCap || b.stage == nil {
+		C.free(b.stage)
+		b.stage, b.stageCap = C.malloc(C.size_t(total+1)), total+1
+	}
+	if len(frames) > b.ptrsCap || b.ptrs == nil {
+		C.free(b.ptrs)
+		b.ptrs, b.ptrsCap = C.malloc(C.size_t((len(frames)+1)*int(unsafe.Sizeof(uintptr(0))))), len(frames)+1
+	}
+	if b.stage == nil || b.ptrs == nil {
+		C.free(b.stage)
+		C.free(b.ptrs)
+		b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
+		return nil, nil, errors.New("hip: out of host memory (equalizer bank staging)")
+	}
+	lens := make([]C.int, len(frames)+1)
+	offs := make([]C.int, len(frames)+1)
+	stage := unsafe.Slice((*byte)(b.stage), b.stageCap)
+	pos := 0
+	for k, f := range frames {
+		copy(stage[pos:], f)
+		offs[k], lens[k] = C.int(pos), C.int(len(f)/bytesPerSample)
+		pos += len(f)
+	}
+	C.bnbind_rb_point((**C.int16_t)(b.ptrs), (*C.char)(b.stage), &offs[0], C.int(len(frames)))
+	return (**C.int16_t)(b.ptrs), lens, nil
+}
+
+// Process runs frames[k] of streams[k] for every k in one device call -> one slice per frame, as long as its input (a stream
+// may appear several times; its frames go in slice order).  An unknown stream or an odd byte count fails the whole call
+// before any stream advances.
+func (b *EqualizerBank) Process(streams []int, frames [][]byte) ([][]byte, error) {
+	if len(streams) != len(frames) {
+		return nil, fmt.Errorf("hip: %d streams for %d frames", len(streams), len(frames))
+	}
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return nil, errors.New("hip: equalizer bank is closed")
+	}
+	if len(frames) == 0 {
+		return nil, nil
+	}
+	ptrs, lens, err := b.stageLocked(frames)
+	if err != nil {
+		return nil, err
+	}
+	st := make([]C.int, len(streams))
+	total := 0
+	for k, s := range streams {
+		st[k] = C.int(s)
+		total += int(lens[k])
+	}
+	out := make([]int16, total+1)
+	counts := make([]C.int, len(frames))
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_eq_process_pcm16(b.h, C.int(len(frames)), &st[0], ptrs, &lens[0], (*C.int16_t)(unsafe.Pointer(&out[0])),
+		C.size_t(total), &counts[0]); rc != 0 {
+		return nil, fmt.Errorf("hip: equalizer bank failed (%d): %s", int(rc), lastError())
+	}
+	res := make([][]byte, len(frames))
+	raw := unsafe.Slice((*byte)(unsafe.Pointer(&out[0])), len(out)*bytesPerSample)
+	pos := 0
+	for k, c := range counts {
+		n := int(c) * bytesPerSample
+		res[k] = raw[pos : pos+n : pos+n]
+		pos += n
+	}
+	return res, nil
+}
+
+func (b *EqualizerBank) Close() error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h != nil {
+		C.bnbind_eq_destroy(b.h)
+		b.h = nil
+	}
+	C.free(b.stage)
+	C.free(b.ptrs)
+	b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
+	return nil
+}
+
+// WriteEqualized processes frames[k] on streams[k] of bank and writes the result into sources[k] of this assembler, one ring
+// write per frame, in one device call.  Every source and stream is checked before anything runs: an error leaves every
+// stream and every ring as it was.
+func (w *WindowAssembler) WriteEqualized(bank *EqualizerBank, streams, sources []int, frames [][]byte) error {
+	if len(streams) != len(frames) || len(sources) != len(frames) {
+		return fmt.Errorf("hip: %d streams and %d sources for %d frames", len(streams), len(sources), len(frames))
+	}
+	w.life.RLock()
+	defer w.life.RUnlock()
+	if w.h == nil {
+		return errors.New("hip: window assembler is closed")
+	}
+	bank.mu.Lock()
+	defer bank.mu.Unlock()
+	if bank.h == nil {
+		return errors.New("hip: equalizer bank is closed")
+	}
+	if len(frames) == 0 {
+		return nil
+	}
+	ptrs, lens, err := bank.stageLocked(frames)
+	if err != nil {
+		return err
+	}
+	st := make([]C.int, len(frames))
+	src := make([]C.int, len(frames))
+	for k := range frames {
+		st[k], src[k] = C.int(streams[k]), C.int(sources[k])
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_win_write_equalized(w.h, bank.h, C.int(len(frames)), &st[0], &src[0], ptrs, &lens[0]); rc != 0 {
+		return fmt.Errorf("hip: windows_write_equalized failed (%d): %s", int(rc), lastError())
 	}
 	return nil
 }

@@ -107,3 +107,14 @@ func (*ResamplerBank) FromRate() int                                         { r
 func (*ResamplerBank) ToRate() int                                           { return 0 }
 func (*ResamplerBank) Close() error                                          { return nil }
 func (*WindowAssembler) WriteResampled(*ResamplerBank, []int, []int, [][]byte) error { return ErrHIPUnavailable }
+
+type EqualizerBank struct{}
+
+func NewEqualizerBank(int, int) (*EqualizerBank, error)                   { return nil, ErrHIPUnavailable }
+func (*EqualizerBank) AddStream() (int, error)                            { return -1, ErrHIPUnavailable }
+func (*EqualizerBank) RemoveStream(int) error                             { return nil }
+func (*EqualizerBank) SetChain(int, []EqualizerSection, float64) error    { return ErrHIPUnavailable }
+func (*EqualizerBank) Reset(int) error                                    { return ErrHIPUnavailable }
+func (*EqualizerBank) Process([]int, [][]byte) ([][]byte, error)          { return nil, ErrHIPUnavailable }
+func (*EqualizerBank) Close() error                                       { return nil }
+func (*WindowAssembler) WriteEqualized(*EqualizerBank, []int, []int, [][]byte) error { return ErrHIPUnavailable }

@@ -38,7 +38,10 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_windows_stats", "bnhip_windows_reset", "bnhip_windows_destroy", "bnhip_predict_pcm_topk",
            "bnhip_windows_predict_topk", "bnhip_resampler_bank_create", "bnhip_resampler_bank_add_stream",
            "bnhip_resampler_bank_remove_stream", "bnhip_resampler_bank_estimate", "bnhip_resampler_bank_process_pcm16",
-           "bnhip_resampler_bank_flush_pcm16", "bnhip_windows_write_resampled", "bnhip_resampler_bank_destroy"]
+           "bnhip_resampler_bank_flush_pcm16", "bnhip_windows_write_resampled", "bnhip_resampler_bank_destroy",
+           "bnhip_eq_bank_create", "bnhip_eq_bank_add_stream", "bnhip_eq_bank_remove_stream", "bnhip_eq_bank_set_chain",
+           "bnhip_eq_bank_reset", "bnhip_eq_bank_process_pcm16", "bnhip_windows_write_equalized", "bnhip_eq_design",
+           "bnhip_eq_bank_destroy"]
 
 
 class HipError(RuntimeError):
@@ -684,6 +687,141 @@ class ResamplerBank:
     def _alive(self):
         if not self._h:
             raise HipError(E_INVALID, "resampler bank is closed")
+        return self._h
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# equalizer.go's filter names -> bnhip.h BNHIP_EQ_*
+EQ_TYPES = {"LowPass": 0, "HighPass": 1, "AllPass": 2, "BandPass": 3, "BandReject": 4, "LowShelf": 5, "HighShelf": 6, "Peaking": 7}
+
+
+def _eq_design_fn(lib):
+    lib.bnhip_eq_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]
+    return lib.bnhip_eq_design
+
+
+def design_filter(type, rate, frequency, q=0.0, width=0.0, gain=0.0, passes=1):
+    """One RBJ biquad as equalizer.go's New<type> constructor builds it -> raw section (b0, b1, b2, a0, a1, a2) as a tuple of
+    floats (bnhip_eq_design).  An unknown type or parameters the constructor refuses (or that give non-finite coefficients)
+    raise HipError(E_INVALID)."""
+    if type not in EQ_TYPES:
+        raise HipError(E_INVALID, f"unknown filter type {type!r}")
+    lib = load_library()
+    out = np.zeros(6, np.float64)
+    _check(lib, _eq_design_fn(lib)(EQ_TYPES[type], float(rate), float(frequency), float(q), float(width), float(gain), int(passes),
+                                   out.ctypes.data))
+    return tuple(float(v) for v in out)
+
+
+def build_filter_chain(settings, rate):
+    """equalizer.BuildFilterChain (equalizer/builder.go): settings is conf.EqualizerSettings as a dict ({"enabled": bool,
+    "filters": [{"type", "frequency", "q", "width", "gain", "passes"}, ...]}) -> [(section6, passes), ...], or None when the
+    equalizer is disabled, has no filters, or none of them could be built.  passes < 1 becomes 1; unknown types and filters
+    that fail validation are skipped."""
+    if not settings or not settings.get("enabled") or not settings.get("filters"):
+        return None
+    chain = []
+    for f in settings["filters"]:
+        passes = max(int(f.get("passes", 0)), 1)
+        if f.get("type") not in EQ_TYPES:
+            continue
+        try:
+            sec = design_filter(f["type"], rate, f.get("frequency", 0.0), q=f.get("q", 0.0), width=f.get("width", 0.0),
+                                gain=f.get("gain", 0.0), passes=passes)
+        except HipError as e:
+            if e.code != E_INVALID:
+                raise
+            continue
+        chain.append((sec, passes))
+    return chain or None
+
+
+def gain_linear(gain_db):
+    """The route's gainLinear: math.Pow(10, gainDB/20) (audio_pipeline_service.go:1005)."""
+    return 10.0 ** (float(gain_db) / 20.0)
+
+
+class EqualizerBank:
+    """`bnhip_eq_bank` (include/bnhip.h): the analysis route's EQ chain + gain (AudioRouter.applyProcessing) for many streams,
+    every call one device call.  `set_chain(stream, chain, gain_linear)` installs [(section6, passes), ...] (None or [] = no
+    filters) with zero state; `process([(stream, pcm16), ...])` -> one bytes object per frame, as many samples as its input (a
+    stream may appear several times; its frames go in list order); `write_windows(win, [(stream, source, pcm16), ...])` writes
+    each frame's result into `source` of a stream.NativeWindows, one ring write per frame.  Errors leave every stream untouched."""
+
+    MAX_STAGES = 16
+
+    def __init__(self, max_streams=256, device=0):
+        self._lib = L = load_library()
+        vp, ci = C.c_void_p, C.c_int
+        L.bnhip_eq_bank_create.argtypes = [ci, ci, C.POINTER(vp)]
+        L.bnhip_eq_bank_add_stream.argtypes = [vp, C.POINTER(ci)]
+        L.bnhip_eq_bank_remove_stream.argtypes = [vp, ci]
+        L.bnhip_eq_bank_set_chain.argtypes = [vp, ci, vp, ci, vp, C.c_double]
+        L.bnhip_eq_bank_reset.argtypes = [vp, ci]
+        L.bnhip_eq_bank_process_pcm16.argtypes = [vp, ci, vp, vp, vp, vp, C.c_size_t, vp]
+        L.bnhip_windows_write_equalized.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        L.bnhip_eq_bank_destroy.argtypes = [vp]
+        L.bnhip_eq_bank_destroy.restype = None
+        self.max_streams = int(max_streams)
+        self._h = C.c_void_p()
+        _check(L, L.bnhip_eq_bank_create(device, self.max_streams, C.byref(self._h)))
+
+    def add_stream(self):
+        s = C.c_int(-1)
+        _check(self._lib, self._lib.bnhip_eq_bank_add_stream(self._alive(), C.byref(s)))
+        return s.value
+
+    def remove_stream(self, stream):
+        _check(self._lib, self._lib.bnhip_eq_bank_remove_stream(self._alive(), int(stream)))
+
+    def set_chain(self, stream, chain, gain_linear=1.0):
+        chain = list(chain or [])
+        secs = np.array([list(sec) for sec, _ in chain], np.float64).reshape(-1)
+        passes = np.array([int(p) for _, p in chain], np.int32)
+        _check(self._lib, self._lib.bnhip_eq_bank_set_chain(self._alive(), int(stream), secs.ctypes.data if chain else None, len(chain),
+                                                            passes.ctypes.data if chain else None, float(gain_linear)))
+
+    def reset(self, stream):
+        _check(self._lib, self._lib.bnhip_eq_bank_reset(self._alive(), int(stream)))
+
+    def process(self, items, out_cap=None):
+        """[(stream, pcm16 bytes | int16 array), ...] -> [bytes, ...] per frame.  out_cap (samples) defaults to the total input;
+        a smaller one is the library's E_INVALID (for tests of that path)."""
+        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _ in items])
+        arrs, ptrs, lens = _pcm16_frames([f for _, f in items])
+        if out_cap is None:
+            out_cap = sum(a.size for a in arrs)
+        out = np.empty(max(out_cap, 1), np.int16)
+        counts = np.zeros(max(len(items), 1), np.int32)
+        _check(self._lib, self._lib.bnhip_eq_bank_process_pcm16(self._alive(), len(items), streams, ptrs, lens, out.ctypes.data, out_cap,
+                                                                counts.ctypes.data))
+        res, pos = [], 0
+        for c in counts[:len(items)]:
+            res.append(out[pos:pos + c].tobytes())
+            pos += int(c)
+        return res
+
+    def write_windows(self, win, items):
+        """[(stream, source, pcm16), ...] -> each frame processed and written into source `source` of win (stream.NativeWindows),
+        one ring write per frame (bnhip_windows_write_equalized)."""
+        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _, _ in items])
+        sources = (C.c_int * max(len(items), 1))(*[int(src) for _, src, _ in items])
+        arrs, ptrs, lens = _pcm16_frames([f for _, _, f in items])
+        win._check(self._lib.bnhip_windows_write_equalized(win._alive(), self._alive(), len(items), streams, sources, ptrs, lens))
+
+    def close(self):
+        if self._h:
+            self._lib.bnhip_eq_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def _alive(self):
+        if not self._h:
+            raise HipError(E_INVALID, "equalizer bank is closed")
         return self._h
 
     def __del__(self):

@@ -595,7 +595,18 @@ class WindowBatcher:
     (source, rate pair), then one buffer write per frame, as the reference.  Native rings: the frames are queued per rate pair
     and the next `tick()` resamples every source's queued frames in ONE device call per rate pair (host.ResamplerBank, one
     ring write per frame) before it collects - such a buffer's audio therefore reaches its ring up to one tick later than
-    audio at the model's own rate."""
+    audio at the model's own rate.
+
+    `set_processing(source, source_rate, filters, gain_db)` gives a source the analysis route's EQ chain and input gain
+    (AudioRouter.applyProcessing, internal/audiocore/router.go:1006-1080): every frame of the source is converted to float64,
+    filtered, scaled, clamped and truncated back to PCM16 once, at the source rate, before the rate grouping above, so every
+    buffer of the source, resampled or not, sees the processed bytes.  A source without filters and with 0 dB gain is not
+    processed at all (router.go:848).  Python rings: one host.EqualizerBank call per write.  Native rings: a processed
+    source's frames are queued in order and the next `tick()` processes every source's queued frames in ONE device call,
+    then writes them to the source's rings (straight from the library when each frame has one ring at the model's rate and all
+    of them are in one assembler) and into the same tick's resampler queue, before it collects - a processed source's audio
+    therefore reaches its rings up to one tick late, as resampled audio does.  A failed call costs its own frames only
+    (on_error), as the reference drops a frame whose processing failed."""
 
     BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
 
@@ -615,6 +626,9 @@ class WindowBatcher:
         self.banks = {}                      # native: (source rate, model rate) -> host.ResamplerBank
         self.bank_streams = {}               # native: (source, source rate, model rate) -> stream of that pair's bank
         self.pending = {}                    # native: (source rate, model rate) -> [(source, stream, pcm bytes, buffers)] until the next tick
+        self.eq_bank = None                  # host.EqualizerBank of the processed sources (created on first use)
+        self.eq_streams = {}                 # source -> its stream of eq_bank
+        self.eq_pending = []                 # native: [(source, stream, pcm bytes)] of processed sources until the next tick
 
     def allocate(self, source, model_id, capacity=None, source_rate=None):
         """The buffer of (source, model_id).  source_rate: the rate the source captures at; None or the model's effective rate
@@ -699,9 +713,61 @@ class WindowBatcher:
             if key in self.pending:
                 self.pending[key] = [it for it in self.pending[key] if it[1] != st]
 
+    def set_processing(self, source, source_rate, filters=None, gain_db=0.0):
+        """The source's EQ chain and input gain, as AddRoute gives them to the analysis consumer (audio_pipeline_service.go:
+        1005-1006).  filters: conf.EqualizerSettings as a dict ({"enabled", "filters": [...]}) or a list of filter dicts
+        (enabled), built for source_rate by host.build_filter_chain; gain_db: the source's gain (10^(dB/20)).  A new setting
+        starts from zero filter state, as a freshly built chain does (see the class docstring)."""
+        if source_rate is None or source_rate <= 0:
+            raise StreamError(f"invalid source sample rate: {source_rate}")
+        settings = {"enabled": True, "filters": list(filters)} if isinstance(filters, (list, tuple)) else filters
+        chain = _host.build_filter_chain(settings, int(source_rate))
+        gain = _host.gain_linear(gain_db)
+        if chain is None and gain == 1.0:                         # the route's processing is skipped (router.go:848)
+            self.clear_processing(source)
+            return
+        if self.eq_pending:                                       # frames captured under the old setting keep it
+            self._drain_equalized()
+        with self.mu:
+            if self.eq_bank is None:
+                self.eq_bank = _host.EqualizerBank(self.BANK_STREAMS)
+            st = self.eq_streams.get(source)
+            if st is None:
+                st = self.eq_streams[source] = self.eq_bank.add_stream()
+            self.eq_bank.set_chain(st, chain, gain)
+
+    def clear_processing(self, source):
+        """The source's frames go to its buffers as they are again."""
+        if self.eq_pending:
+            self._drain_equalized()
+        with self.mu:
+            st = self.eq_streams.pop(source, None)
+            if st is not None:
+                self.eq_bank.remove_stream(st)
+
     def write(self, source, data):
         """Capture side: the same bytes go to every model's buffer of that source; a buffer of another rate gets them resampled
-        (once per rate pair: buffer_consumer.go:184-210)."""
+        (once per rate pair: buffer_consumer.go:184-210).  A processed source's bytes are processed first (set_processing)."""
+        with self.mu:
+            st = self.eq_streams.get(source)
+        if st is not None:
+            raw = _as_bytes(data).tobytes()
+            try:
+                if len(raw) % BYTES_PER_SAMPLE:
+                    raise StreamError(f"frame of {len(raw)} bytes is not whole 16-bit samples")
+                if self.native:
+                    with self.mu:
+                        self.eq_pending.append((source, st, raw))
+                    return
+                data = self.eq_bank.process([(st, raw)])[0]
+            except Exception as e:                                # router.go:1064-1073: the frame is dropped, the route goes on
+                self.errors += 1
+                if self.on_error:
+                    self.on_error(None, [source], e)
+                return
+        self._fan_out(source, data)
+
+    def _fan_out(self, source, data):
         with self.mu:
             groups = {}
             for (s, m), ab in self.buffers.items():
@@ -722,6 +788,35 @@ class WindowBatcher:
             out = r.resample_into(raw)
             for ab in targets:
                 ab.write(out)
+
+    def _drain_equalized(self):
+        """Native: every processed source's queued frames through one device call (host.EqualizerBank), then on to the source's
+        buffers.  When each frame's source has one buffer, at its model's rate, and all of them are in one assembler the results
+        go straight into its rings (bnhip_windows_write_equalized); otherwise they come back and take write()'s path."""
+        outs = None
+        with self.mu:
+            pending, self.eq_pending = self.eq_pending, []
+            if not pending:
+                return
+            bufs = {}
+            for (s, m), ab in self.buffers.items():
+                bufs.setdefault(s, []).append((m, ab))
+            direct = [bufs.get(src, []) for src, _, _ in pending]
+            wins = {id(b[0][1].win) for b in direct if len(b) == 1}
+            try:
+                if len(wins) == 1 and all(len(b) == 1 and (src, b[0][0]) not in self.rates for (src, _, _), b in zip(pending, direct)):
+                    self.eq_bank.write_windows(direct[0][0][1].win, [(st, b[0][1].index, raw) for (_, st, raw), b in zip(pending, direct)])
+                else:
+                    outs = self.eq_bank.process([(st, raw) for _, st, raw in pending])
+            except Exception as e:                                # the frames of this call are lost, as a failed applyProcessing
+                self.errors += len(pending)
+                failed = (sorted({src for src, _, _ in pending}), e)
+            else:
+                failed = None
+        if failed and self.on_error:
+            self.on_error(None, *failed)
+        for (src, _, _), out in zip(pending, outs or []):
+            self._fan_out(src, out)
 
     def _drain_resampled(self):
         """Native: every rate pair's queued frames through one device call (host.ResamplerBank), one ring write per frame.  When
@@ -813,9 +908,16 @@ class WindowBatcher:
             self.bank_streams.clear()
             self.pending.clear()
             self.rates.clear()
+            if self.eq_bank is not None:
+                self.eq_bank.close()
+            self.eq_bank = None
+            self.eq_streams.clear()
+            self.eq_pending.clear()
 
     def tick(self):
         if self.native:
+            if self.eq_pending:
+                self._drain_equalized()
             if self.pending:
                 self._drain_resampled()
             return self._tick_native()

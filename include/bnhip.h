@@ -268,6 +268,52 @@ int bnhip_windows_write_resampled(bnhip_windows* w, bnhip_resampler_bank* b, int
                                   const int16_t* const* frames, const int* n_in);
 void bnhip_resampler_bank_destroy(bnhip_resampler_bank* b);
 
+/* Equalizer bank: the analysis route's processing, AudioRouter.applyProcessing (internal/audiocore/router.go:1006-1080), for
+ * many sources, one device call per call.  AddRoute gives the analysis BufferConsumer the source's gain (10^(dB/20)) and EQ
+ * chain (internal/analysis/audio_pipeline_service.go:1005-1006); every PCM16 frame is then converted to float64
+ * (x / 32768), run through every biquad of the chain `passes` times (equalizer.FilterChain.ApplyBatch), scaled by the gain,
+ * clamped to [-1, 1] and truncated to int16(x * 32767) (convert.Float64ToBytesPCM16), at the source rate, before
+ * BufferConsumer.Write's rate fan-out.  Output bytes equal that float64 arithmetic byte for byte (given the same sections).
+ *   create:        max_streams fixes the slot table; one HIP stream per bank.  destroy: NULL-safe.
+ *   add_stream:    a fresh stream (no chain, gain 1: pass-through); slots of removed streams are reused with fresh state.
+ *   set_chain:     FilterChain + gainLinear of a route (router.go AddRoute / UpdateFilterChain): n_sections raw biquads
+ *                  {b0, b1, b2, a0, a1, a2} (each divided by a0 as NewFilter, equalizer.go:112-136), section k run passes[k]
+ *                  times.  Replaces the chain and zeroes its state.  Non-finite values, a0 == 0, passes < 1:
+ *                  BNHIP_E_INVALID; more than 16 stages (sum of passes): BNHIP_E_UNSUPPORTED (a divergence: the reference has
+ *                  no limit; its default chain is 2 stages).  A refused call leaves the old chain and its state.
+ *   reset:         FilterChain.Reset: zero state, same chain.
+ *   process:       frames f = 0..n_frames-1 (frames[f], n_in[f] samples) of streams[f]; a stream may appear several times,
+ *                  its frames are consumed in call order.  out receives every frame's samples (as many as its input) packed
+ *                  in call order, out_count[f] their number.  A stream with no sections and gain 1 is passed through byte for
+ *                  byte without conversion (router.go:848 skips the route's processing).  out_cap (samples) below the total,
+ *                  an unknown or removed stream, a negative length: BNHIP_E_INVALID and no stream advances.  A device error
+ *                  leaves every stream as it was.
+ *   windows_write_equalized: process + one bnhip_windows_write per frame into source sources[f] of w; every source is checked
+ *                  before anything runs.
+ *   design:        the RBJ biquad of equalizer.go's New* constructors (type BNHIP_EQ_*): raw section6 = {b0, b1, b2, a0, a1, a2}.
+ *                  BandPass, BandReject and Peaking take width_hz (converted to octaves as hzToOctaves); the shelves and
+ *                  Peaking take gain_db; q is the Q of the others.  Validation as the constructors (passes >= 1; for the
+ *                  width types frequency > 0 and width_hz > 0), and non-finite results (e.g. q == 0) are BNHIP_E_INVALID.
+ *                  Computed with the C library's sin / cos / pow, so a coefficient may differ from Go's in the last ulp.
+ * Calls on one bank are serialised internally. */
+typedef struct bnhip_eq_bank bnhip_eq_bank;
+enum {
+    BNHIP_EQ_LOWPASS = 0, BNHIP_EQ_HIGHPASS = 1, BNHIP_EQ_ALLPASS = 2, BNHIP_EQ_BANDPASS = 3, BNHIP_EQ_BANDREJECT = 4,
+    BNHIP_EQ_LOWSHELF = 5, BNHIP_EQ_HIGHSHELF = 6, BNHIP_EQ_PEAKING = 7
+};
+int bnhip_eq_bank_create(int device, int max_streams, bnhip_eq_bank** out);
+int bnhip_eq_bank_add_stream(bnhip_eq_bank* b, int* out_stream);
+int bnhip_eq_bank_remove_stream(bnhip_eq_bank* b, int stream);
+int bnhip_eq_bank_set_chain(bnhip_eq_bank* b, int stream, const double* sections, int n_sections, const int* passes, double gain_linear);
+int bnhip_eq_bank_reset(bnhip_eq_bank* b, int stream);
+int bnhip_eq_bank_process_pcm16(bnhip_eq_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in,
+                                int16_t* out, size_t out_cap, int* out_count);
+int bnhip_windows_write_equalized(bnhip_windows* w, bnhip_eq_bank* b, int n_frames, const int* streams, const int* sources,
+                                  const int16_t* const* frames, const int* n_in);
+int bnhip_eq_design(int type, double sample_rate, double frequency, double q, double width_hz, double gain_db, int passes,
+                    double* section6);
+void bnhip_eq_bank_destroy(bnhip_eq_bank* b);
+
 /* Stream plumbing for hosts that own a HIP stream (bench harness: torch's current stream). */
 int bnhip_set_stream(bnhip_model* m, void* hip_stream);
 int bnhip_synchronize(bnhip_model* m);
