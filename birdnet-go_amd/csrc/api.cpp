@@ -19,6 +19,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <utility>
@@ -29,7 +30,7 @@
 #include "hostpipe.h"
 #include "numa.h"
 #include "model_onnx.h"
-#include "resample_bank.h"
+#include "resample.h"
 #include "tflite_model.h"
 #include "windows.h"
 
@@ -166,12 +167,6 @@ struct bnhip_model {
     Engine& eng() { return *engs[0]; }
     const Engine& eng() const { return *engs[0]; }
 };
-
-namespace bnhip {
-void resample_design(int L, int M, double beta, int half_factor, std::vector<float>* table, int* T_out, int* half_out);
-int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_pcm16, int out_pcm16, int n_clips, int n_in,
-                    int n_out, int L, int M, int T, int half, long long i_base, long long n_base, hipStream_t s);
-}
 
 namespace {
 
@@ -357,7 +352,44 @@ int post_topk_one(Engine& e, const float* logits, int n_clips, int activation, d
     return BNHIP_OK;
 }
 
-int igcd(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
+// The polyphase geometry of one rate pair (resample.hip): L / M = rate_out / rate_in in lowest terms, T taps per phase and the
+// filter half-length.  Output i's newest input is n0(i) = floor((i*M + half) / L); indices count from the stream start.
+struct ResamplePlan {
+    int L = 1, M = 1, T = 0, half = 0;
+    // outputs computable once n_total inputs are known: every i whose newest tap n0(i) < n_total
+    long long ready(long long n_total) const {
+        const long long num = n_total * L - half;
+        return num <= 0 ? 0 : (num + M - 1) / M;
+    }
+    // EstimateOutput analogue (resample.go:83-88): an upper bound for any call, whatever the state
+    long long estimate(long long n_in) const { return n_in <= 0 ? 0 : (n_in * L + M - 1) / M + 1; }
+    // outputs of n inputs followed by zeros: the one-shot length, and where a flush ends
+    long long end(long long n) const { return (n * L + M - 1) / M; }
+    // the first input the next call still needs once the outputs before i_end are out: n0(i_end) - (T-1), within [n_base, n_after]
+    long long keep_from(long long i_end, long long n_base, long long n_after) const {
+        return std::min(std::max((i_end * M + half) / L - (T - 1), n_base), n_after);
+    }
+    bool fits_lds() const { return resample_lds(L, M, T) <= RESAMPLE_LDS_MAX; }
+};
+
+// rate_in, rate_out > 0.  With a table the filter is designed too (T, half and the [L][T] phase table); without, only L / M are set.
+ResamplePlan resample_plan(int rate_in, int rate_out, std::vector<float>* table) {
+    const int g = std::gcd(rate_in, rate_out);
+    ResamplePlan p;
+    p.L = rate_out / g;
+    p.M = rate_in / g;
+    if (table) resample_design(p.L, p.M, 5.0, 10, table, &p.T, &p.half);
+    return p;
+}
+
+// bnhip_init, then the ordinal checked and made current
+int use_device(int device) {
+    int rc = bnhip_init(nullptr);
+    if (rc) return rc;
+    if (device < 0 || device >= g_devices) return set_err(BNHIP_E_INVALID, "device ordinal out of range");
+    hipSetDevice(device);
+    return BNHIP_OK;
+}
 
 int copy_out(const std::string& s, char* buf, size_t cap) {
     if (buf && cap) {
@@ -374,7 +406,8 @@ int copy_out(const std::string& s, char* buf, size_t cap) {
 // history lives on the device between calls so that any chunking of a stream produces the samples of one call over the
 // whole stream, bit for bit.
 struct bnhip_resampler {
-    int device = 0, rate_in = 0, rate_out = 0, L = 1, M = 1, T = 0, half = 0;
+    int device = 0;
+    ResamplePlan p;
     float* d_table = nullptr;
     float* d_work = nullptr;      // [hist | new chunk] as float32
     size_t work_cap = 0;          // floats
@@ -1017,9 +1050,7 @@ int bnhip_debug_fetch(bnhip_model* m, int tensor_index, int n_clips, float* out,
 // ------------------------------------------------------------------------------------------------ resampler
 int bnhip_resample_length(int n_in, int rate_in, int rate_out) {
     if (n_in <= 0 || rate_in <= 0 || rate_out <= 0) return 0;
-    int g = igcd(rate_in, rate_out);
-    long long L = rate_out / g, M = rate_in / g;
-    return (int)(((long long)n_in * L + M - 1) / M);
+    return (int)resample_plan(rate_in, rate_out, nullptr).end(n_in);
 }
 
 static int resample_impl(int device, const void* in, bool pcm16, int n_clips, int n_in, int rate_in, int rate_out, void* out,
@@ -1034,13 +1065,10 @@ static int resample_impl(int device, const void* in, bool pcm16, int n_clips, in
         memcpy(out, in, (size_t)n_clips * n_in * esz);
         return BNHIP_OK;
     }
-    int rc = bnhip_init(nullptr);
+    int rc = use_device(device);
     if (rc) return rc;
-    if (device < 0 || device >= g_devices) return set_err(BNHIP_E_INVALID, "device ordinal out of range");
-    hipSetDevice(device);
-    int g = igcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g, T = 0, half = 0;
     std::vector<float> table;
-    resample_design(L, M, 5.0, 10, &table, &T, &half);
+    const ResamplePlan p = resample_plan(rate_in, rate_out, &table);
     void *d_in = nullptr, *d_out = nullptr; float* d_tab = nullptr;
     hipError_t he = hipMalloc(&d_in, (size_t)n_clips * n_in * esz);
     if (he == hipSuccess) he = hipMalloc(&d_out, (size_t)n_clips * no * esz);
@@ -1049,7 +1077,7 @@ static int resample_impl(int device, const void* in, bool pcm16, int n_clips, in
     if (he == hipSuccess) he = hipMemcpy(d_tab, table.data(), table.size() * 4, hipMemcpyHostToDevice);
     int lrc = 0;
     if (he == hipSuccess) {
-        lrc = launch_resample(d_in, d_out, d_tab, pcm16, pcm16, n_clips, n_in, no, L, M, T, half, 0, 0, nullptr);
+        lrc = launch_resample(d_in, d_out, d_tab, pcm16, pcm16, n_clips, n_in, no, p.L, p.M, p.T, p.half, 0, 0, nullptr);
         if (lrc == 0) he = hipMemcpy(out, d_out, (size_t)n_clips * no * esz, hipMemcpyDeviceToHost);
     }
     if (d_in) hipFree(d_in);
@@ -1090,21 +1118,14 @@ int bnhip_resampler_create(int device, int rate_in, int rate_out, bnhip_resample
     if (rate_in == rate_out) return BNHIP_OK;            // NewResampler returns nil, nil: no resampling required (resample.go:58-60)
     bnhip_resampler* r = nullptr;
     BN_GUARD_BEGIN
-    int rc = bnhip_init(nullptr);
+    int rc = use_device(device);
     if (rc) return rc;
-    if (device < 0 || device >= g_devices) return set_err(BNHIP_E_INVALID, "device ordinal out of range");
-    hipSetDevice(device);
-    r = new bnhip_resampler();
-    r->device = device; r->rate_in = rate_in; r->rate_out = rate_out;
-    int g = igcd(rate_in, rate_out);
-    r->L = rate_out / g; r->M = rate_in / g;
     std::vector<float> table;
-    resample_design(r->L, r->M, 5.0, 10, &table, &r->T, &r->half);
-    // same LDS bound as the kernel launch (phase table + worst-case span of 256 outputs)
-    if (((size_t)r->L * r->T + (size_t)(255LL * r->M / r->L + r->T + 2)) * 4 > 150 * 1024) {
-        delete r; r = nullptr;
-        return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
-    }
+    const ResamplePlan p = resample_plan(rate_in, rate_out, &table);
+    if (!p.fits_lds()) return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+    r = new bnhip_resampler();
+    r->device = device;
+    r->p = p;
     hipError_t he = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     if (he == hipSuccess) he = hipMalloc((void**)&r->d_table, table.size() * 4);
     if (he == hipSuccess) he = hipMemcpy(r->d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice);
@@ -1114,17 +1135,9 @@ int bnhip_resampler_create(int device, int rate_in, int rate_out, bnhip_resample
     BN_GUARD_END(resampler_free(r))
 }
 
-// outputs computable once n_total inputs are known: every i whose newest tap n0(i) = floor((i*M + half)/L) < n_total
-static long long resampler_ready(const bnhip_resampler* r, long long n_total) {
-    long long num = n_total * r->L - r->half;
-    if (num <= 0) return 0;
-    return (num + r->M - 1) / r->M;
-}
-
 int bnhip_resampler_estimate(const bnhip_resampler* r, int n_in) {
     if (!r || n_in <= 0) return 0;
-    // EstimateOutput analogue (resample.go:83-88): an upper bound for any call, whatever the state
-    return (int)(((long long)n_in * r->L + r->M - 1) / r->M) + 1;
+    return (int)r->p.estimate(n_in);
 }
 
 // flush: 0 = emit what the inputs so far determine; 1 = end of stream (future inputs are zeros), then reset
@@ -1134,7 +1147,7 @@ static int resampler_run(bnhip_resampler* r, const void* in, bool pcm16, int n_i
     if (n_in < 0 || (n_in > 0 && !in) || !out) return set_err(BNHIP_E_INVALID, "bad resampler arguments");
     if (n_in == 0 && !flush) return BNHIP_OK;            // empty input: nothing written (resample.go:100-102)
     const long long n_after = r->n_total + n_in;
-    const long long i_end = flush ? (n_after * r->L + r->M - 1) / r->M : resampler_ready(r, n_after);
+    const long long i_end = flush ? r->p.end(n_after) : r->p.ready(n_after);
     const long long cnt = i_end - r->i_next;
     // a too-small destination fails before the state advances (resample.go:137-144)
     if (cnt > out_cap || (!flush && bnhip_resampler_estimate(r, n_in) > out_cap))
@@ -1146,9 +1159,7 @@ static int resampler_run(bnhip_resampler* r, const void* in, bool pcm16, int n_i
     // what the next call still needs: the inputs from n0(i_end) - (T-1) on.  Computed up front so that every allocation
     // (including the staging the history compaction moves through) happens BEFORE any work is queued: a failure below
     // leaves n_total / i_next / n_hist / n_base exactly as they were ("fails before the state advances", resample.go:137-144).
-    long long keep_from = (i_end * r->M + r->half) / r->L - (r->T - 1);
-    if (keep_from < r->n_base) keep_from = r->n_base;
-    if (keep_from > n_after) keep_from = n_after;
+    const long long keep_from = r->p.keep_from(i_end, r->n_base, n_after);
     const int drop = flush ? 0 : (int)(keep_from - r->n_base), keep = flush ? 0 : n_work - drop;
     if (need > r->work_cap) {
         size_t cap = std::max<size_t>(need * 2, 4096);
@@ -1188,7 +1199,7 @@ static int resampler_run(bnhip_resampler* r, const void* in, bool pcm16, int n_i
         }
     }
     if (he == hipSuccess && cnt > 0) {
-        int lrc = launch_resample(r->d_work, r->d_out, r->d_table, 0, pcm16 ? 1 : 0, 1, n_work, (int)cnt, r->L, r->M, r->T, r->half,
+        int lrc = launch_resample(r->d_work, r->d_out, r->d_table, 0, pcm16 ? 1 : 0, 1, n_work, (int)cnt, r->p.L, r->p.M, r->p.T, r->p.half,
                                   r->i_next, r->n_base, r->stream);
         if (lrc) { hipStreamSynchronize(r->stream); return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS"); }
         he = hipMemcpyAsync(out, r->d_out, (size_t)cnt * esz, hipMemcpyDeviceToHost, r->stream);
@@ -1239,49 +1250,40 @@ void bnhip_resampler_destroy(bnhip_resampler* r) {
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------------ resampler bank
-// The rate fan-out of BufferConsumer.Write (internal/analysis/buffer_consumer.go:105-210: one stateful Resampler per
-// (source, non-native rate)) for every source of one (rate_in, rate_out) pair at once: one H2D copy (descriptors + packed
-// PCM16), one k_resample_bank launch, one D2H copy and one synchronise per call, on ONE HIP stream per bank.  Each stream's
-// filter history is a fixed pair of device slabs of H = T - 1 floats (keep_from = n0(i_end) - (T - 1) with n0(i_end) >=
-// n_total bounds it): the launch reads one slab and writes the new tail into the other, the host flips the parity on commit.
-struct bnhip_resampler_bank {
-    struct Stream {
+// ------------------------------------------------------------------------------------------------ stream banks
+// What the resampler and equalizer banks share.  Calls on a bank are serialised on its mutex and each one is one transaction on
+// the bank's HIP stream: one H2D copy (the bank's headers, then the packed PCM16 of the streams that run), one launch, one D2H
+// copy of the packed outputs and one synchronise.  Each stream's device state is a pair of slabs: a launch reads slab `parity`
+// and writes the other, and the host flips the parity in the commit, which runs only once everything succeeded - so a failed
+// call changes no stream.
+template <class State>
+struct StreamBank {
+    struct Stream : State {
         bool live = false;
         int parity = 0;                 // slab read by the next call
-        long long n_total = 0, i_next = 0, n_base = 0;
-        int n_hist = 0;
     };
     std::mutex mu;                      // calls on one bank are serialised
-    int device = 0, rate_in = 0, rate_out = 0, L = 1, M = 1, T = 0, half = 0, H = 1;
+    int device = 0;
     std::vector<Stream> st;
-    float* d_table = nullptr;
-    float* d_hist = nullptr;            // [max_streams][2][H]
-    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // descriptors | packed PCM16 (bytes)
-    int16_t* h_out = nullptr; int16_t* d_out = nullptr; size_t out_cap = 0;      // packed outputs (samples)
     hipStream_t stream = nullptr;
+    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // headers | packed PCM16 (bytes)
+    int16_t* h_out = nullptr; void* d_out = nullptr; size_t out_cap = 0;         // packed outputs (bytes)
+    ~StreamBank() {                     // (bank_free has drained the stream)
+        if (stream) hipStreamDestroy(stream);
+        for (void* p : {d_stage, d_out}) if (p) hipFree(p);
+        for (void* p : {(void*)h_stage, (void*)h_out}) if (p) hipHostFree(p);
+    }
 };
 
 namespace {
 
-void bank_free(bnhip_resampler_bank* b) {
+template <class B>
+void bank_free(B* b) {
     if (!b) return;
     hipSetDevice(b->device);
-    if (b->stream) { hipStreamSynchronize(b->stream); hipStreamDestroy(b->stream); }
-    for (void* p : {(void*)b->d_table, (void*)b->d_hist, b->d_stage, (void*)b->d_out}) if (p) hipFree(p);
-    for (void* p : {(void*)b->h_stage, (void*)b->h_out}) if (p) hipHostFree(p);
+    if (b->stream) hipStreamSynchronize(b->stream);
+    delete b;                           // the destructors free the bank's buffers and its stream
     (void)hipGetLastError();
-    delete b;
-}
-
-long long bank_ready(const bnhip_resampler_bank* b, long long n_total) {      // = resampler_ready
-    long long num = n_total * b->L - b->half;
-    if (num <= 0) return 0;
-    return (num + b->M - 1) / b->M;
-}
-
-long long bank_estimate(const bnhip_resampler_bank* b, long long n_in) {     // = bnhip_resampler_estimate
-    return n_in <= 0 ? 0 : (n_in * b->L + b->M - 1) / b->M + 1;
 }
 
 // a page-locked host buffer and its device twin of at least `need` bytes; the old pair is freed only once the new one exists
@@ -1297,115 +1299,148 @@ bool bank_grow(void** h, void** d, size_t* cap, size_t need) {
     return true;
 }
 
-bool bank_stream_ok(const bnhip_resampler_bank* b, int s) { return s >= 0 && (size_t)s < b->st.size() && b->st[s].live; }
+template <class B>
+int bank_stream_check(const B* b, int s) {
+    if (s >= 0 && (size_t)s < b->st.size() && b->st[s].live) return BNHIP_OK;
+    return set_err(BNHIP_E_INVALID, std::string("no such ") + B::what + " stream: " + std::to_string(s));
+}
 
-// One call: frames f = 0..n_frames-1 of streams[f] (a stream may appear several times; its frames are consumed in call order),
-// or with flush != 0 the end of each listed stream.  Checks everything, stages everything, runs, synchronises, commits, then
-// hands frame f's outputs (in call order) to deliver(f, samples, count).  Until the commit nothing of any stream changes.
-template <class Deliver>
-int bank_run(bnhip_resampler_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, bool flush,
-             long long out_cap, Deliver deliver) {
-    if (n_frames < 0 || (n_frames > 0 && !streams)) return set_err(BNHIP_E_INVALID, "bad resampler bank arguments");
-    if (!flush && n_frames > 0 && !n_in) return set_err(BNHIP_E_INVALID, "n_in is NULL");
-    struct Group { int stream; long long n_in = 0, n_after = 0, i_end = 0, keep_from = 0; int in_off = 0, cnt = 0, out_off = 0, keep = 0; };
-    std::vector<Group> groups;
+// The rest of both creates, on the current device: the stream slots, the HIP stream, then alloc(bank) for the bank's own device
+// buffers.  A failure frees the bank; *out is set only on success.
+template <class B, class Alloc>
+int bank_create(int device, int max_streams, B** out, Alloc alloc) {
+    B* b = nullptr;
+    BN_GUARD_BEGIN
+    b = new B();
+    b->device = device;
+    b->st.resize(max_streams);
+    hipError_t he = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (he == hipSuccess) he = alloc(*b);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        bank_free(b); b = nullptr;
+        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(B::what) + " create: " + hipGetErrorString(he));
+    }
+    *out = b;
+    return BNHIP_OK;
+    BN_GUARD_END(bank_free(b))
+}
+
+template <class B>
+int bank_add_stream(B* b, int* out_stream) {
+    if (!b || !out_stream) return set_err(BNHIP_E_INVALID, "NULL argument");
+    *out_stream = -1;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    for (size_t s = 0; s < b->st.size(); s++) {
+        if (b->st[s].live) continue;
+        b->st[s] = typename B::Stream();               // fresh state: a reused slot starts a new stream
+        b->st[s].live = true;
+        *out_stream = (int)s;
+        return BNHIP_OK;
+    }
+    return set_err(BNHIP_E_INVALID, std::string(B::what) + " is full (max_streams)");
+    BN_GUARD_END((void)0)
+}
+
+template <class B>
+int bank_remove_stream(B* b, int stream) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (int rc = bank_stream_check(b, stream)) return rc;
+    b->st[stream].live = false;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+// One stream's frames of a call.  The bank's plan decides whether the group runs on the device and whether its frames are
+// handed back as they are; a group that runs has its inputs at in_off of the packed PCM16 and its outputs at out_off of the
+// packed output.
+struct BankGroup {
+    int stream;
+    long long n_in = 0, n_out = 0;      // samples of its frames, of their outputs
+    bool run = false, pass = false;
+    int in_off = 0, out_off = 0;
+};
+
+struct BankBlob { const void* p = nullptr; size_t bytes = 0; };
+
+// One call on either bank: frames f = 0..n_frames-1 of streams[f] (a stream may appear several times; its frames are consumed
+// in call order), or with flush the end of each listed stream (at most once each; no frames).  Checks everything, stages
+// everything, runs, synchronises, commits, then hands frame f's outputs (in call order) to deliver(f, samples, count).  Until
+// the commit nothing of any stream changes.  The bank supplies
+//   plan(groups, frame_group, cnt)          which groups run or pass, cnt[f] = frame f's output count (preset to its input
+//                                           count), and its own checks; -> BNHIP_OK or an error
+//   describe(groups, in_total, out_total, hdr)   with the offsets placed: its descriptors etc., staged as hdr[0] | hdr[1]
+//                                           in front of the packed PCM16; -> BNHIP_OK or an error
+//   launch(d_hdr, d_pcm, d_out)             -> BNHIP_OK or an error (nothing was launched)
+//   commit(group, k)                        the new state of the k-th group that ran
+template <class B, class Plan, class Describe, class Launch, class Commit, class Deliver>
+int bank_call(B* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, bool flush, long long out_cap,
+              Plan plan, Describe describe, Launch launch, Commit commit, Deliver deliver) {
+    if (n_frames < 0 || (n_frames > 0 && (!streams || (!flush && !n_in)))) return set_err(BNHIP_E_INVALID, std::string("bad ") + B::what + " arguments");
+    std::vector<BankGroup> groups;
     std::vector<int> group_of(b->st.size(), -1), frame_group(n_frames);
-    std::vector<long long> frame_cnt(n_frames);
-    long long need = 0;
+    std::vector<long long> cnt(n_frames);
     for (int f = 0; f < n_frames; f++) {
         const int s = streams[f];
-        if (!bank_stream_ok(b, s)) return set_err(BNHIP_E_INVALID, "no such resampler bank stream: " + std::to_string(s));
+        if (int rc = bank_stream_check(b, s)) return rc;
         const long long n = flush ? 0 : n_in[f];
         if (n < 0) return set_err(BNHIP_E_INVALID, "negative frame length");
         if (n > 0 && (!frames || !frames[f])) return set_err(BNHIP_E_INVALID, "frame pointer is NULL");
         if (group_of[s] < 0) {
             group_of[s] = (int)groups.size();
-            Group g; g.stream = s;
-            groups.push_back(g);
+            groups.push_back(BankGroup{s});
         } else if (flush) {
             return set_err(BNHIP_E_INVALID, "stream listed twice in one flush");
         }
         frame_group[f] = group_of[s];
         groups[group_of[s]].n_in += n;
-        need += bank_estimate(b, n);
+        cnt[f] = n;
     }
-    // per-frame split: what resampler_ready gives on the running n_total, frame after frame
-    long long in_total = 0;
-    for (Group& g : groups) { const auto& S = b->st[g.stream]; g.n_after = S.n_total; g.i_end = S.i_next; }
+    if (int rc = plan(groups, frame_group, cnt)) return rc;
+    long long total = 0;
     for (int f = 0; f < n_frames; f++) {
-        Group& g = groups[frame_group[f]];
-        const auto& S = b->st[g.stream];
-        long long i_end;
-        if (flush) i_end = (S.n_total * b->L + b->M - 1) / b->M;
-        else { g.n_after += n_in[f]; i_end = bank_ready(b, g.n_after); }
-        frame_cnt[f] = i_end - g.i_end;
-        g.i_end = i_end;
+        groups[frame_group[f]].n_out += cnt[f];
+        total += cnt[f];
     }
-    long long out_total = 0, blocks = 0;
-    for (Group& g : groups) {
-        const auto& S = b->st[g.stream];
-        g.cnt = (int)(g.i_end - S.i_next);
-        if (flush) { g.keep_from = 0; g.keep = 0; }
-        else {
-            long long kf = (g.i_end * b->M + b->half) / b->L - (b->T - 1);
-            if (kf < S.n_base) kf = S.n_base;
-            if (kf > g.n_after) kf = g.n_after;
-            g.keep_from = kf;
-            g.keep = (int)(g.n_after - kf);
-            if (g.keep > b->H) return set_err(BNHIP_E_RUNTIME, "internal error: resampler bank history exceeds its slab");
-        }
+    if (total > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");      // resample.go:137-144, convert/pcm.go:142-145
+    long long in_total = 0, out_total = 0;
+    int n_run = 0;
+    for (BankGroup& g : groups) {
+        if (!g.run) continue;
         g.in_off = (int)in_total;
         g.out_off = (int)out_total;
         in_total += g.n_in;
-        out_total += g.cnt;
-        blocks += (g.cnt + 255) / 256 + 1;
+        out_total += g.n_out;
+        n_run++;
     }
-    if (!flush && need > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");      // resample.go:137-144
-    if (out_total > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");
-    if (in_total > INT32_MAX / 2 || out_total > INT32_MAX / 2 || blocks > INT32_MAX / 2)
-        return set_err(BNHIP_E_INVALID, "resampler bank call too large");
-    // streams with nothing to do (every frame empty) stay out of the launch
-    std::vector<ResampleBankDesc> desc;
-    desc.reserve(groups.size());
-    int block0 = 0;
-    for (const Group& g : groups) {
-        if (!flush && g.n_in == 0) continue;
-        const auto& S = b->st[g.stream];
-        ResampleBankDesc d{};
-        d.n_base = S.n_base; d.i_next = S.i_next; d.keep_from = g.keep_from;
-        d.in_off = g.in_off; d.n_in = (int)g.n_in; d.n_hist = S.n_hist;
-        d.hist_rd = (g.stream * 2 + S.parity) * b->H; d.hist_wr = (g.stream * 2 + (S.parity ^ 1)) * b->H;
-        d.keep = g.keep; d.cnt = g.cnt; d.out_off = g.out_off; d.block0 = block0;
-        block0 += (g.cnt + 255) / 256 + 1;
-        desc.push_back(d);
-    }
-    if (!desc.empty()) {
+    BankBlob hdr[2];
+    if (int rc = describe(groups, in_total, out_total, hdr)) return rc;
+    if (n_run > 0) {
         hipSetDevice(b->device);
-        const size_t desc_bytes = desc.size() * sizeof(ResampleBankDesc);
-        const size_t stage_bytes = desc_bytes + (size_t)in_total * 2;
+        const size_t hdr_bytes = hdr[0].bytes + hdr[1].bytes, stage_bytes = hdr_bytes + (size_t)in_total * 2;
         if (!bank_grow((void**)&b->h_stage, &b->d_stage, &b->stage_cap, stage_bytes))
-            return set_err(BNHIP_E_NOMEM, "allocation failed (resampler bank staging)");
-        size_t oc = b->out_cap * 2;
-        if (!bank_grow((void**)&b->h_out, (void**)&b->d_out, &oc, std::max<size_t>((size_t)out_total * 2, 2)))
-            return set_err(BNHIP_E_NOMEM, "allocation failed (resampler bank output)");
-        b->out_cap = oc / 2;
-        memcpy(b->h_stage, desc.data(), desc_bytes);
-        int16_t* pk = reinterpret_cast<int16_t*>(b->h_stage + desc_bytes);
+            return set_err(BNHIP_E_NOMEM, std::string("allocation failed (") + B::what + " staging)");
+        if (!bank_grow((void**)&b->h_out, &b->d_out, &b->out_cap, std::max<size_t>((size_t)out_total * 2, 2)))
+            return set_err(BNHIP_E_NOMEM, std::string("allocation failed (") + B::what + " output)");
+        memcpy(b->h_stage, hdr[0].p, hdr[0].bytes);
+        if (hdr[1].bytes) memcpy(b->h_stage + hdr[0].bytes, hdr[1].p, hdr[1].bytes);
+        int16_t* pk = reinterpret_cast<int16_t*>(b->h_stage + hdr_bytes);
         std::vector<long long> fill(groups.size(), 0);
         for (int f = 0; f < n_frames && !flush; f++) {
-            if (n_in[f] <= 0) continue;
-            const Group& g = groups[frame_group[f]];
-            memcpy(pk + g.in_off + fill[frame_group[f]], frames[f], (size_t)n_in[f] * 2);
-            fill[frame_group[f]] += n_in[f];
+            const int gi = frame_group[f];
+            if (n_in[f] <= 0 || !groups[gi].run) continue;
+            memcpy(pk + groups[gi].in_off + fill[gi], frames[f], (size_t)n_in[f] * 2);
+            fill[gi] += n_in[f];
         }
-        const auto* d_desc = static_cast<const ResampleBankDesc*>(b->d_stage);
-        const auto* d_pcm = reinterpret_cast<const int16_t*>(static_cast<const uint8_t*>(b->d_stage) + desc_bytes);
+        const uint8_t* ds = static_cast<const uint8_t*>(b->d_stage);
         hipError_t he = hipMemcpyAsync(b->d_stage, b->h_stage, stage_bytes, hipMemcpyHostToDevice, b->stream);
         if (he == hipSuccess) {
-            if (launch_resample_bank(d_desc, (int)desc.size(), block0, d_pcm, b->d_hist, b->d_out, b->d_table, b->L, b->M, b->T,
-                                     b->half, b->stream)) {
+            if (int rc = launch(ds, reinterpret_cast<const int16_t*>(ds + hdr_bytes), static_cast<int16_t*>(b->d_out))) {
                 hipStreamSynchronize(b->stream);
-                return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+                return rc;
             }
             he = hipGetLastError();
         }
@@ -1413,292 +1448,184 @@ int bank_run(bnhip_resampler_bank* b, int n_frames, const int* streams, const in
             he = hipMemcpyAsync(b->h_out, b->d_out, (size_t)out_total * 2, hipMemcpyDeviceToHost, b->stream);
         const hipError_t hs = hipStreamSynchronize(b->stream);
         if (he == hipSuccess) he = hs;
-        if (he != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_RUNTIME, std::string("resampler bank: ") + hipGetErrorString(he)); }
+        if (he != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_RUNTIME, std::string(B::what) + ": " + hipGetErrorString(he)); }
     }
     // ---- commit: everything above succeeded
-    for (const Group& g : groups) {
-        auto& S = b->st[g.stream];
-        if (flush) { S.n_total = 0; S.i_next = 0; S.n_base = 0; S.n_hist = 0; continue; }   // a new stream starts
-        if (g.n_in == 0) continue;
-        S.n_total = g.n_after; S.i_next = g.i_end;
-        S.n_hist = g.keep; S.n_base = g.keep_from; S.parity ^= 1;
-    }
+    for (size_t gi = 0, k = 0; gi < groups.size(); gi++)
+        if (groups[gi].run) commit(groups[gi], k++);
     std::vector<long long> taken(groups.size(), 0);
     for (int f = 0; f < n_frames; f++) {
         const int gi = frame_group[f];
-        deliver(f, b->h_out + groups[gi].out_off + taken[gi], (int)frame_cnt[f]);
-        taken[gi] += frame_cnt[f];
+        const BankGroup& g = groups[gi];
+        deliver(f, g.pass ? (frames ? frames[f] : nullptr) : b->h_out + g.out_off + taken[gi], (int)cnt[f]);
+        taken[gi] += cnt[f];
     }
     return BNHIP_OK;
 }
 
 }  // namespace
 
-extern "C" {
+// ------------------------------------------------------------------------------------------------ resampler bank
+// The rate fan-out of BufferConsumer.Write (internal/analysis/buffer_consumer.go:105-210: one stateful Resampler per
+// (source, non-native rate)) for every source of one (rate_in, rate_out) pair at once, one k_resample_bank launch per call.
+// Each stream's filter history is a fixed pair of device slabs of H = T - 1 floats (keep_from = n0(i_end) - (T - 1) with
+// n0(i_end) >= n_total bounds it): the launch reads one slab and writes the new tail into the other.
+struct ResamplerStream {
+    long long n_total = 0, i_next = 0, n_base = 0;
+    int n_hist = 0;
+};
 
-int bnhip_resampler_bank_create(int device, int rate_in, int rate_out, int max_streams, bnhip_resampler_bank** out) {
-    if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (rate_in <= 0 || rate_out <= 0) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
-    if (max_streams < 1 || max_streams > (1 << 20)) return set_err(BNHIP_E_INVALID, "max_streams must be in [1, 1048576]");
-    if (rate_in == rate_out) return BNHIP_OK;            // NewResampler returns nil, nil: no resampling required (resample.go:58-60)
-    bnhip_resampler_bank* b = nullptr;
-    BN_GUARD_BEGIN
-    int rc = bnhip_init(nullptr);
-    if (rc) return rc;
-    if (device < 0 || device >= g_devices) return set_err(BNHIP_E_INVALID, "device ordinal out of range");
-    hipSetDevice(device);
-    b = new bnhip_resampler_bank();
-    b->device = device; b->rate_in = rate_in; b->rate_out = rate_out;
-    const int g = igcd(rate_in, rate_out);
-    b->L = rate_out / g; b->M = rate_in / g;
-    std::vector<float> table;
-    resample_design(b->L, b->M, 5.0, 10, &table, &b->T, &b->half);
-    b->H = std::max(b->T - 1, 1);
-    if (resample_bank_lds(b->L, b->M, b->T) > 150 * 1024) {
-        delete b; b = nullptr;
-        return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
-    }
-    b->st.resize(max_streams);
-    hipError_t he = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipMalloc((void**)&b->d_table, table.size() * 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&b->d_hist, (size_t)max_streams * 2 * b->H * 4);
-    if (he == hipSuccess) he = hipMemcpy(b->d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        bank_free(b); b = nullptr;
-        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string("resampler bank create: ") + hipGetErrorString(he));
-    }
-    *out = b;
-    return BNHIP_OK;
-    BN_GUARD_END(bank_free(b))
-}
+struct bnhip_resampler_bank : StreamBank<ResamplerStream> {
+    static constexpr const char* what = "resampler bank";
+    ResamplePlan p;
+    int H = 1;
+    float* d_table = nullptr;
+    float* d_hist = nullptr;            // [max_streams][2][H]
+    ~bnhip_resampler_bank() { for (void* q : {(void*)d_table, (void*)d_hist}) if (q) hipFree(q); }
+};
 
-int bnhip_resampler_bank_add_stream(bnhip_resampler_bank* b, int* out_stream) {
-    if (!b || !out_stream) return set_err(BNHIP_E_INVALID, "NULL argument");
-    *out_stream = -1;
-    BN_GUARD_BEGIN
-    std::lock_guard<std::mutex> lk(b->mu);
-    for (size_t s = 0; s < b->st.size(); s++) {
-        if (b->st[s].live) continue;
-        b->st[s] = bnhip_resampler_bank::Stream();       // fresh state: a reused slot starts a new stream
-        b->st[s].live = true;
-        *out_stream = (int)s;
+namespace {
+
+template <class Deliver>
+int bank_run(bnhip_resampler_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, bool flush,
+             long long out_cap, Deliver deliver) {
+    const ResamplePlan& p = b->p;
+    std::vector<ResampleBankDesc> desc;
+    int n_blocks = 0;
+    auto plan = [&](std::vector<BankGroup>& groups, const std::vector<int>& frame_group, std::vector<long long>& cnt) -> int {
+        // per-frame split: what ready() gives on the running n_total, frame after frame
+        std::vector<long long> n_after(groups.size()), i_end(groups.size());
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+            const auto& S = b->st[groups[gi].stream];
+            n_after[gi] = S.n_total;
+            i_end[gi] = S.i_next;
+            groups[gi].run = flush || groups[gi].n_in > 0;      // streams with nothing to do (every frame empty) stay out of the launch
+        }
+        long long need = 0;
+        for (int f = 0; f < n_frames; f++) {
+            const int gi = frame_group[f];
+            const long long e = flush ? p.end(n_after[gi]) : p.ready(n_after[gi] += n_in[f]);
+            cnt[f] = e - i_end[gi];
+            i_end[gi] = e;
+            if (!flush) need += p.estimate(n_in[f]);
+        }
+        if (need > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");      // resample.go:137-144
         return BNHIP_OK;
-    }
-    return set_err(BNHIP_E_INVALID, "resampler bank is full (max_streams)");
-    BN_GUARD_END((void)0)
+    };
+    auto describe = [&](const std::vector<BankGroup>& groups, long long in_total, long long out_total, BankBlob* hdr) -> int {
+        long long blocks = 0;
+        for (const BankGroup& g : groups) blocks += (g.n_out + 255) / 256 + 1;
+        if (in_total > INT32_MAX / 2 || out_total > INT32_MAX / 2 || blocks > INT32_MAX / 2)
+            return set_err(BNHIP_E_INVALID, "resampler bank call too large");
+        desc.reserve(groups.size());
+        for (const BankGroup& g : groups) {
+            if (!g.run) continue;
+            const auto& S = b->st[g.stream];
+            ResampleBankDesc d{};
+            d.n_base = S.n_base; d.i_next = S.i_next;
+            if (!flush) {
+                d.keep_from = p.keep_from(S.i_next + g.n_out, S.n_base, S.n_total + g.n_in);
+                d.keep = (int)(S.n_total + g.n_in - d.keep_from);
+                if (d.keep > b->H) return set_err(BNHIP_E_RUNTIME, "internal error: resampler bank history exceeds its slab");
+            }
+            d.in_off = g.in_off; d.n_in = (int)g.n_in; d.n_hist = S.n_hist;
+            d.hist_rd = (g.stream * 2 + S.parity) * b->H; d.hist_wr = (g.stream * 2 + (S.parity ^ 1)) * b->H;
+            d.cnt = (int)g.n_out; d.out_off = g.out_off; d.block0 = n_blocks;
+            n_blocks += (d.cnt + 255) / 256 + 1;
+            desc.push_back(d);
+        }
+        hdr[0] = {desc.data(), desc.size() * sizeof(ResampleBankDesc)};
+        return BNHIP_OK;
+    };
+    auto launch = [&](const uint8_t* d_hdr, const int16_t* d_pcm, int16_t* d_out) -> int {
+        if (launch_resample_bank(reinterpret_cast<const ResampleBankDesc*>(d_hdr), (int)desc.size(), n_blocks, d_pcm, b->d_hist, d_out,
+                                 b->d_table, p.L, p.M, p.T, p.half, b->stream))
+            return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+        return BNHIP_OK;
+    };
+    auto commit = [&](const BankGroup& g, size_t k) {
+        auto& S = b->st[g.stream];
+        if (flush) { S.n_total = 0; S.i_next = 0; S.n_base = 0; S.n_hist = 0; return; }     // a new stream starts
+        S.n_total += g.n_in; S.i_next += g.n_out;
+        S.n_hist = desc[k].keep; S.n_base = desc[k].keep_from; S.parity ^= 1;
+    };
+    return bank_call(b, n_frames, streams, frames, n_in, flush, out_cap, plan, describe, launch, commit, deliver);
 }
 
-int bnhip_resampler_bank_remove_stream(bnhip_resampler_bank* b, int stream) {
-    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
-    BN_GUARD_BEGIN
-    std::lock_guard<std::mutex> lk(b->mu);
-    if (!bank_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such resampler bank stream: " + std::to_string(stream));
-    b->st[stream].live = false;
-    return BNHIP_OK;
-    BN_GUARD_END((void)0)
-}
-
-int bnhip_resampler_bank_estimate(const bnhip_resampler_bank* b, int n_in) {
-    if (!b || n_in <= 0) return 0;
-    return (int)bank_estimate(b, n_in);
-}
-
-int bnhip_resampler_bank_process_pcm16(bnhip_resampler_bank* b, int n_frames, const int* streams, const int16_t* const* frames,
-                                       const int* n_in, int16_t* out, size_t out_cap, int* out_count) {
-    if (!b || (n_frames > 0 && (!out || !out_count))) return set_err(BNHIP_E_INVALID, "NULL argument");
-    BN_GUARD_BEGIN
-    std::lock_guard<std::mutex> lk(b->mu);
-    long long pos = 0;
-    return bank_run(b, n_frames, streams, frames, n_in, false, (long long)std::min<size_t>(out_cap, INT64_MAX),
-                    [&](int f, const int16_t* p, int n) {
-                        if (n > 0) memcpy(out + pos, p, (size_t)n * 2);
-                        out_count[f] = n;
-                        pos += n;
-                    });
-    BN_GUARD_END((void)0)
-}
-
-int bnhip_resampler_bank_flush_pcm16(bnhip_resampler_bank* b, int n, const int* streams, int16_t* out, size_t out_cap, int* out_count) {
-    if (!b || (n > 0 && (!out || !out_count))) return set_err(BNHIP_E_INVALID, "NULL argument");
-    BN_GUARD_BEGIN
-    std::lock_guard<std::mutex> lk(b->mu);
-    long long pos = 0;
-    return bank_run(b, n, streams, nullptr, nullptr, true, (long long)std::min<size_t>(out_cap, INT64_MAX),
-                    [&](int f, const int16_t* p, int c) {
-                        if (c > 0) memcpy(out + pos, p, (size_t)c * 2);
-                        out_count[f] = c;
-                        pos += c;
-                    });
-    BN_GUARD_END((void)0)
-}
-
-int bnhip_windows_write_resampled(bnhip_windows* w, bnhip_resampler_bank* b, int n_frames, const int* streams, const int* sources,
-                                  const int16_t* const* frames, const int* n_in) {
-    if (!w || !b || (n_frames > 0 && !sources)) return set_err(BNHIP_E_INVALID, "NULL argument");
-    BN_GUARD_BEGIN
-    for (int f = 0; f < n_frames; f++)
-        if (!w->a->stats(sources[f], nullptr, nullptr, nullptr)) return set_err(BNHIP_E_INVALID, "no such source: " + std::to_string(sources[f]));
-    std::lock_guard<std::mutex> lk(b->mu);
-    // one ring write per input frame, as BufferConsumer.Write's AnalysisBuffer.Write per frame (an empty result is a write too);
-    // a source removed since the check above loses its frame as a missing buffer does in the reference (buffer_consumer.go:196-206)
-    return bank_run(b, n_frames, streams, frames, n_in, false, INT64_MAX,
-                    [&](int f, const int16_t* p, int n) { (void)w->a->write(sources[f], p, (size_t)n * 2); });
-    BN_GUARD_END((void)0)
-}
-
-void bnhip_resampler_bank_destroy(bnhip_resampler_bank* b) {
-    try { bank_free(b); } catch (...) {}
-}
-
-}  // extern "C"
+}  // namespace
 
 // ------------------------------------------------------------------------------------------------ equalizer bank
 // The analysis route's EQ + gain (AudioRouter.applyProcessing, internal/audiocore/router.go:1006-1080, the route the analysis
 // BufferConsumer gets from AddRoute with the source's chain and gain, internal/analysis/audio_pipeline_service.go:1005-1006)
-// for every source of a bank at once: one H2D copy (descriptors + coefficients + packed PCM16), one k_eq_bank launch, one D2H
-// copy and one synchronise per call, on ONE HIP stream per bank.  The chains live on the host and travel with each call, so
-// set_chain and reset touch no device memory; each stream's filter state is a fixed pair of device slabs of
-// EQ_MAX_STAGES x {in1, in2, out1, out2} doubles, read from one and written to the other, the parity flipped on commit.
-struct bnhip_eq_bank {
-    struct Stream {
-        bool live = false;
-        bool fresh = true;              // the next call starts from zero state (new stream, new chain, reset)
-        int parity = 0;                 // slab read by the next call
-        int n_stages = 0;
-        double gain = 1.0;
-        double coef[EQ_MAX_STAGES][5] = {};   // {b0, b1, b2, a1, a2} / a0 per stage: filter f, pass p, in chain order
-        bool passthrough() const { return n_stages == 0 && gain == 1.0; }
-    };
-    std::mutex mu;                      // calls on one bank are serialised
-    int device = 0;
-    std::vector<Stream> st;
+// for every source of a bank at once, one k_eq_bank launch per call.  The chains live on the host and travel with each call
+// (descriptors | coefficients | PCM16), so set_chain and reset touch no device memory; each stream's filter state is a fixed
+// pair of device slabs of EQ_MAX_STAGES x {in1, in2, out1, out2} doubles.
+struct EqStream {
+    bool fresh = true;                  // the next call starts from zero state (new stream, new chain, reset)
+    int n_stages = 0;
+    double gain = 1.0;
+    double coef[EQ_MAX_STAGES][5] = {};   // {b0, b1, b2, a1, a2} / a0 per stage: filter f, pass p, in chain order
+    bool passthrough() const { return n_stages == 0 && gain == 1.0; }
+};
+
+struct bnhip_eq_bank : StreamBank<EqStream> {
+    static constexpr const char* what = "equalizer bank";
     double* d_state = nullptr;          // [max_streams][2][EQ_MAX_STAGES][4]
-    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // descriptors | coefficients | PCM16 (bytes)
-    int16_t* h_out = nullptr; void* d_out = nullptr; size_t out_cap = 0;         // packed outputs (bytes)
-    hipStream_t stream = nullptr;
+    ~bnhip_eq_bank() { if (d_state) hipFree(d_state); }
 };
 
 namespace {
 
 constexpr int EQ_SLAB = EQ_MAX_STAGES * 4;     // doubles of one state slab
 
-void eq_free(bnhip_eq_bank* b) {
-    if (!b) return;
-    hipSetDevice(b->device);
-    if (b->stream) { hipStreamSynchronize(b->stream); hipStreamDestroy(b->stream); }
-    for (void* p : {(void*)b->d_state, b->d_stage, b->d_out}) if (p) hipFree(p);
-    for (void* p : {(void*)b->h_stage, (void*)b->h_out}) if (p) hipHostFree(p);
-    (void)hipGetLastError();
-    delete b;
-}
-
-bool eq_stream_ok(const bnhip_eq_bank* b, int s) { return s >= 0 && (size_t)s < b->st.size() && b->st[s].live; }
-
-// One call: frames f = 0..n_frames-1 of streams[f] (a stream may appear several times; its frames are consumed in call order).
-// Checks everything, stages everything, runs, synchronises, commits, then hands frame f's output (as many samples as its input)
-// to deliver(f, samples, count).  A pass-through stream (no stages, gain 1) is not converted: its frames are delivered as they
-// are, as the reference skips the route's processing (router.go:848).  Until the commit nothing of any stream changes.
+// Every frame's output has as many samples as its input.  A pass-through stream (no stages, gain 1) is not converted: its frames
+// are delivered as they are, as the reference skips the route's processing (router.go:848).  (flush is always false here.)
 template <class Deliver>
-int eq_run(bnhip_eq_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, long long out_cap,
-           Deliver deliver) {
-    if (n_frames < 0 || (n_frames > 0 && (!streams || !n_in))) return set_err(BNHIP_E_INVALID, "bad equalizer bank arguments");
-    struct Group { int stream; long long n = 0; int in_off = 0; };
-    std::vector<Group> groups;
-    std::vector<int> group_of(b->st.size(), -1), frame_group(n_frames);
-    long long total = 0;
-    for (int f = 0; f < n_frames; f++) {
-        const int s = streams[f];
-        if (!eq_stream_ok(b, s)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(s));
-        if (n_in[f] < 0) return set_err(BNHIP_E_INVALID, "negative frame length");
-        if (n_in[f] > 0 && (!frames || !frames[f])) return set_err(BNHIP_E_INVALID, "frame pointer is NULL");
-        if (group_of[s] < 0) {
-            group_of[s] = (int)groups.size();
-            Group g; g.stream = s;
-            groups.push_back(g);
+int bank_run(bnhip_eq_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, bool flush,
+             long long out_cap, Deliver deliver) {
+    std::vector<EqBankDesc> desc;
+    std::vector<double> coef;
+    auto plan = [&](std::vector<BankGroup>& groups, const std::vector<int>&, std::vector<long long>&) -> int {
+        for (BankGroup& g : groups) {
+            g.pass = b->st[g.stream].passthrough();
+            g.run = g.n_in > 0 && !g.pass;
         }
-        frame_group[f] = group_of[s];
-        groups[group_of[s]].n += n_in[f];
-        total += n_in[f];
-    }
-    if (total > out_cap) return set_err(BNHIP_E_INVALID, "destination buffer too small");      // convert/pcm.go:142-145
-    // processed streams with samples, packed back to back; a wave runs 4 of them, every row of it as many steps as its longest
-    std::vector<int> run;
-    long long in_total = 0;
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        Group& g = groups[gi];
-        if (g.n == 0 || b->st[g.stream].passthrough()) continue;
-        g.in_off = (int)in_total;
-        in_total += g.n;
-        run.push_back((int)gi);
-    }
-    if (in_total > INT32_MAX / 4) return set_err(BNHIP_E_INVALID, "equalizer bank call too large");
-    if (!run.empty()) {
-        std::vector<EqBankDesc> desc(run.size());
-        std::vector<double> coef;
-        for (size_t k = 0; k < run.size(); k++) {
-            const Group& g = groups[run[k]];
+        return BNHIP_OK;
+    };
+    auto describe = [&](const std::vector<BankGroup>& groups, long long in_total, long long, BankBlob* hdr) -> int {
+        if (in_total > INT32_MAX / 4) return set_err(BNHIP_E_INVALID, "equalizer bank call too large");
+        for (const BankGroup& g : groups) {
+            if (!g.run) continue;
             const auto& S = b->st[g.stream];
-            EqBankDesc& d = desc[k];
-            d.gain = S.gain; d.in_off = g.in_off; d.n = (int)g.n; d.n_stages = S.n_stages;
+            EqBankDesc d{};
+            d.gain = S.gain; d.in_off = g.in_off; d.n = (int)g.n_in; d.n_stages = S.n_stages;
             d.coef_off = (int)coef.size();
             for (int s = 0; s < S.n_stages; s++) coef.insert(coef.end(), S.coef[s], S.coef[s] + 5);
             d.st_rd = S.fresh ? -1 : (g.stream * 2 + S.parity) * EQ_SLAB;
             d.st_wr = (g.stream * 2 + (S.parity ^ 1)) * EQ_SLAB;
+            desc.push_back(d);
         }
+        // a wave runs 4 streams, every row of it as many steps as its longest
         for (size_t k0 = 0; k0 < desc.size(); k0 += 4) {
             long long steps = 0;
             for (size_t k = k0; k < std::min(desc.size(), k0 + 4); k++)
                 steps = std::max<long long>(steps, desc[k].n + std::max(desc[k].n_stages, 1) - 1);
             desc[k0].blk_steps = (int)((steps + 15) / 16 * 16);
         }
-        hipSetDevice(b->device);
-        const size_t desc_bytes = desc.size() * sizeof(EqBankDesc), coef_bytes = coef.size() * sizeof(double);
-        const size_t stage_bytes = desc_bytes + coef_bytes + (size_t)in_total * 2;
-        if (!bank_grow((void**)&b->h_stage, &b->d_stage, &b->stage_cap, stage_bytes))
-            return set_err(BNHIP_E_NOMEM, "allocation failed (equalizer bank staging)");
-        if (!bank_grow((void**)&b->h_out, &b->d_out, &b->out_cap, (size_t)in_total * 2))
-            return set_err(BNHIP_E_NOMEM, "allocation failed (equalizer bank output)");
-        memcpy(b->h_stage, desc.data(), desc_bytes);
-        if (coef_bytes) memcpy(b->h_stage + desc_bytes, coef.data(), coef_bytes);
-        int16_t* pk = reinterpret_cast<int16_t*>(b->h_stage + desc_bytes + coef_bytes);
-        std::vector<long long> fill(groups.size(), 0);
-        for (int f = 0; f < n_frames; f++) {
-            const Group& g = groups[frame_group[f]];
-            if (n_in[f] <= 0 || b->st[g.stream].passthrough()) continue;
-            memcpy(pk + g.in_off + fill[frame_group[f]], frames[f], (size_t)n_in[f] * 2);
-            fill[frame_group[f]] += n_in[f];
-        }
-        const uint8_t* ds = static_cast<const uint8_t*>(b->d_stage);
-        hipError_t he = hipMemcpyAsync(b->d_stage, b->h_stage, stage_bytes, hipMemcpyHostToDevice, b->stream);
-        if (he == hipSuccess) {
-            launch_eq_bank(reinterpret_cast<const EqBankDesc*>(ds), (int)desc.size(), reinterpret_cast<const double*>(ds + desc_bytes),
-                           reinterpret_cast<const int16_t*>(ds + desc_bytes + coef_bytes), b->d_state, static_cast<int16_t*>(b->d_out),
-                           b->stream);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess)
-            he = hipMemcpyAsync(b->h_out, b->d_out, (size_t)in_total * 2, hipMemcpyDeviceToHost, b->stream);
-        const hipError_t hs = hipStreamSynchronize(b->stream);
-        if (he == hipSuccess) he = hs;
-        if (he != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_RUNTIME, std::string("equalizer bank: ") + hipGetErrorString(he)); }
-    }
-    // ---- commit: everything above succeeded
-    for (int gi : run) {
-        auto& S = b->st[groups[gi].stream];
+        hdr[0] = {desc.data(), desc.size() * sizeof(EqBankDesc)};
+        hdr[1] = {coef.data(), coef.size() * sizeof(double)};
+        return BNHIP_OK;
+    };
+    auto launch = [&](const uint8_t* d_hdr, const int16_t* d_pcm, int16_t* d_out) -> int {
+        return launch_eq_bank(reinterpret_cast<const EqBankDesc*>(d_hdr), (int)desc.size(),
+                              reinterpret_cast<const double*>(d_hdr + desc.size() * sizeof(EqBankDesc)), d_pcm, b->d_state, d_out, b->stream);
+    };
+    auto commit = [&](const BankGroup& g, size_t) {
+        auto& S = b->st[g.stream];
         S.parity ^= 1;
         S.fresh = false;
-    }
-    std::vector<long long> taken(groups.size(), 0);
-    for (int f = 0; f < n_frames; f++) {
-        const int gi = frame_group[f];
-        const Group& g = groups[gi];
-        if (b->st[g.stream].passthrough()) deliver(f, frames ? frames[f] : nullptr, n_in[f]);
-        else deliver(f, b->h_out + g.in_off + taken[gi], n_in[f]);
-        taken[gi] += n_in[f];
-    }
-    return BNHIP_OK;
+    };
+    return bank_call(b, n_frames, streams, frames, n_in, flush, out_cap, plan, describe, launch, commit, deliver);
 }
 
 // RBJ audio-EQ-cookbook biquads (R. Bristow-Johnson, "Cookbook formulae for audio EQ biquad filter coefficients"), raw
@@ -1758,67 +1685,114 @@ int eq_design(int type, double fs, double f, double q, double width, double gain
     return BNHIP_OK;
 }
 
+// The *_process_pcm16 / *_flush_pcm16 entries: frame f's outputs packed into out in call order, their count in out_count[f]
+template <class B>
+int bank_to_buffer(B* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in, bool flush, int16_t* out,
+                   size_t out_cap, int* out_count) {
+    if (!b || (n_frames > 0 && (!out || !out_count))) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    long long pos = 0;
+    return bank_run(b, n_frames, streams, frames, n_in, flush, (long long)std::min<size_t>(out_cap, INT64_MAX),
+                    [&](int f, const int16_t* p, int n) {
+                        if (n > 0) memcpy(out + pos, p, (size_t)n * 2);
+                        out_count[f] = n;
+                        pos += n;
+                    });
+    BN_GUARD_END((void)0)
+}
+
+// The bnhip_windows_write_* entries: one ring write per frame, as BufferConsumer.Write's AnalysisBuffer.Write per frame (an
+// empty result is a write too).  Every source is checked before the bank is locked; a source removed since then loses its frame
+// as a missing buffer does in the reference (buffer_consumer.go:196-206).
+template <class B>
+int bank_to_rings(bnhip_windows* w, B* b, int n_frames, const int* streams, const int* sources, const int16_t* const* frames,
+                  const int* n_in) {
+    if (!w || !b || (n_frames > 0 && !sources)) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    for (int f = 0; f < n_frames; f++)
+        if (!w->a->stats(sources[f], nullptr, nullptr, nullptr)) return set_err(BNHIP_E_INVALID, "no such source: " + std::to_string(sources[f]));
+    std::lock_guard<std::mutex> lk(b->mu);
+    return bank_run(b, n_frames, streams, frames, n_in, false, INT64_MAX,
+                    [&](int f, const int16_t* p, int n) { (void)w->a->write(sources[f], p, (size_t)n * 2); });
+    BN_GUARD_END((void)0)
+}
+
 }  // namespace
 
 extern "C" {
+
+int bnhip_resampler_bank_create(int device, int rate_in, int rate_out, int max_streams, bnhip_resampler_bank** out) {
+    if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (rate_in <= 0 || rate_out <= 0) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
+    if (max_streams < 1 || max_streams > (1 << 20)) return set_err(BNHIP_E_INVALID, "max_streams must be in [1, 1048576]");
+    if (rate_in == rate_out) return BNHIP_OK;            // NewResampler returns nil, nil: no resampling required (resample.go:58-60)
+    BN_GUARD_BEGIN
+    int rc = use_device(device);
+    if (rc) return rc;
+    std::vector<float> table;
+    const ResamplePlan p = resample_plan(rate_in, rate_out, &table);
+    if (!p.fits_lds()) return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+    return bank_create(device, max_streams, out, [&](bnhip_resampler_bank& b) {
+        b.p = p;
+        b.H = std::max(p.T - 1, 1);
+        hipError_t he = hipMalloc((void**)&b.d_table, table.size() * 4);
+        if (he == hipSuccess) he = hipMalloc((void**)&b.d_hist, (size_t)max_streams * 2 * b.H * 4);
+        if (he == hipSuccess) he = hipMemcpy(b.d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice);
+        return he;
+    });
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_resampler_bank_add_stream(bnhip_resampler_bank* b, int* out_stream) { return bank_add_stream(b, out_stream); }
+int bnhip_resampler_bank_remove_stream(bnhip_resampler_bank* b, int stream) { return bank_remove_stream(b, stream); }
+
+int bnhip_resampler_bank_estimate(const bnhip_resampler_bank* b, int n_in) {
+    if (!b || n_in <= 0) return 0;
+    return (int)b->p.estimate(n_in);
+}
+
+int bnhip_resampler_bank_process_pcm16(bnhip_resampler_bank* b, int n_frames, const int* streams, const int16_t* const* frames,
+                                       const int* n_in, int16_t* out, size_t out_cap, int* out_count) {
+    return bank_to_buffer(b, n_frames, streams, frames, n_in, false, out, out_cap, out_count);
+}
+
+int bnhip_resampler_bank_flush_pcm16(bnhip_resampler_bank* b, int n, const int* streams, int16_t* out, size_t out_cap, int* out_count) {
+    return bank_to_buffer(b, n, streams, nullptr, nullptr, true, out, out_cap, out_count);
+}
+
+int bnhip_windows_write_resampled(bnhip_windows* w, bnhip_resampler_bank* b, int n_frames, const int* streams, const int* sources,
+                                  const int16_t* const* frames, const int* n_in) {
+    return bank_to_rings(w, b, n_frames, streams, sources, frames, n_in);
+}
+
+void bnhip_resampler_bank_destroy(bnhip_resampler_bank* b) {
+    try { bank_free(b); } catch (...) {}
+}
 
 int bnhip_eq_bank_create(int device, int max_streams, bnhip_eq_bank** out) {
     if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
     *out = nullptr;
     if (max_streams < 1 || max_streams > (1 << 20)) return set_err(BNHIP_E_INVALID, "max_streams must be in [1, 1048576]");
-    bnhip_eq_bank* b = nullptr;
     BN_GUARD_BEGIN
-    int rc = bnhip_init(nullptr);
+    int rc = use_device(device);
     if (rc) return rc;
-    if (device < 0 || device >= g_devices) return set_err(BNHIP_E_INVALID, "device ordinal out of range");
-    hipSetDevice(device);
-    b = new bnhip_eq_bank();
-    b->device = device;
-    b->st.resize(max_streams);
-    hipError_t he = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (he == hipSuccess) he = hipMalloc((void**)&b->d_state, (size_t)max_streams * 2 * EQ_SLAB * sizeof(double));
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        eq_free(b); b = nullptr;
-        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string("equalizer bank create: ") + hipGetErrorString(he));
-    }
-    *out = b;
-    return BNHIP_OK;
-    BN_GUARD_END(eq_free(b))
-}
-
-int bnhip_eq_bank_add_stream(bnhip_eq_bank* b, int* out_stream) {
-    if (!b || !out_stream) return set_err(BNHIP_E_INVALID, "NULL argument");
-    *out_stream = -1;
-    BN_GUARD_BEGIN
-    std::lock_guard<std::mutex> lk(b->mu);
-    for (size_t s = 0; s < b->st.size(); s++) {
-        if (b->st[s].live) continue;
-        b->st[s] = bnhip_eq_bank::Stream();              // no chain, gain 1, zero state
-        b->st[s].live = true;
-        *out_stream = (int)s;
-        return BNHIP_OK;
-    }
-    return set_err(BNHIP_E_INVALID, "equalizer bank is full (max_streams)");
+    return bank_create(device, max_streams, out, [&](bnhip_eq_bank& b) {
+        return hipMalloc((void**)&b.d_state, (size_t)max_streams * 2 * EQ_SLAB * sizeof(double));
+    });
     BN_GUARD_END((void)0)
 }
 
-int bnhip_eq_bank_remove_stream(bnhip_eq_bank* b, int stream) {
-    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
-    BN_GUARD_BEGIN
-    std::lock_guard<std::mutex> lk(b->mu);
-    if (!eq_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(stream));
-    b->st[stream].live = false;
-    return BNHIP_OK;
-    BN_GUARD_END((void)0)
-}
+int bnhip_eq_bank_add_stream(bnhip_eq_bank* b, int* out_stream) { return bank_add_stream(b, out_stream); }
+int bnhip_eq_bank_remove_stream(bnhip_eq_bank* b, int stream) { return bank_remove_stream(b, stream); }
 
 int bnhip_eq_bank_set_chain(bnhip_eq_bank* b, int stream, const double* sections, int n_sections, const int* passes, double gain_linear) {
     if (!b || n_sections < 0 || (n_sections > 0 && (!sections || !passes))) return set_err(BNHIP_E_INVALID, "bad equalizer chain arguments");
     if (!std::isfinite(gain_linear)) return set_err(BNHIP_E_INVALID, "gain is not finite");
     BN_GUARD_BEGIN
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!eq_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(stream));
+    if (int rc = bank_stream_check(b, stream)) return rc;
     bnhip_eq_bank::Stream ns;
     long long stages = 0;
     for (int k = 0; k < n_sections; k++) {
@@ -1845,7 +1819,7 @@ int bnhip_eq_bank_reset(bnhip_eq_bank* b, int stream) {
     if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
     BN_GUARD_BEGIN
     std::lock_guard<std::mutex> lk(b->mu);
-    if (!eq_stream_ok(b, stream)) return set_err(BNHIP_E_INVALID, "no such equalizer bank stream: " + std::to_string(stream));
+    if (int rc = bank_stream_check(b, stream)) return rc;
     b->st[stream].fresh = true;
     return BNHIP_OK;
     BN_GUARD_END((void)0)
@@ -1853,30 +1827,12 @@ int bnhip_eq_bank_reset(bnhip_eq_bank* b, int stream) {
 
 int bnhip_eq_bank_process_pcm16(bnhip_eq_bank* b, int n_frames, const int* streams, const int16_t* const* frames, const int* n_in,
                                 int16_t* out, size_t out_cap, int* out_count) {
-    if (!b || (n_frames > 0 && (!out || !out_count))) return set_err(BNHIP_E_INVALID, "NULL argument");
-    BN_GUARD_BEGIN
-    std::lock_guard<std::mutex> lk(b->mu);
-    long long pos = 0;
-    return eq_run(b, n_frames, streams, frames, n_in, (long long)std::min<size_t>(out_cap, INT64_MAX),
-                  [&](int f, const int16_t* p, int n) {
-                      if (n > 0) memcpy(out + pos, p, (size_t)n * 2);
-                      out_count[f] = n;
-                      pos += n;
-                  });
-    BN_GUARD_END((void)0)
+    return bank_to_buffer(b, n_frames, streams, frames, n_in, false, out, out_cap, out_count);
 }
 
 int bnhip_windows_write_equalized(bnhip_windows* w, bnhip_eq_bank* b, int n_frames, const int* streams, const int* sources,
                                   const int16_t* const* frames, const int* n_in) {
-    if (!w || !b || (n_frames > 0 && !sources)) return set_err(BNHIP_E_INVALID, "NULL argument");
-    BN_GUARD_BEGIN
-    for (int f = 0; f < n_frames; f++)
-        if (!w->a->stats(sources[f], nullptr, nullptr, nullptr)) return set_err(BNHIP_E_INVALID, "no such source: " + std::to_string(sources[f]));
-    std::lock_guard<std::mutex> lk(b->mu);
-    // one ring write per frame, as BufferConsumer.Write gets one processed frame per capture frame
-    return eq_run(b, n_frames, streams, frames, n_in, INT64_MAX,
-                  [&](int f, const int16_t* p, int n) { (void)w->a->write(sources[f], p, (size_t)n * 2); });
-    BN_GUARD_END((void)0)
+    return bank_to_rings(w, b, n_frames, streams, sources, frames, n_in);
 }
 
 int bnhip_eq_design(int type, double sample_rate, double frequency, double q, double width_hz, double gain_db, int passes,
@@ -1891,7 +1847,7 @@ int bnhip_eq_design(int type, double sample_rate, double frequency, double q, do
 }
 
 void bnhip_eq_bank_destroy(bnhip_eq_bank* b) {
-    try { eq_free(b); } catch (...) {}
+    try { bank_free(b); } catch (...) {}
 }
 
 }  // extern "C"

@@ -1,11 +1,25 @@
-// Batched streaming resampler (api.cpp bnhip_resampler_bank_*): one launch resamples one call's frames of every stream of a
-// bank that shares (rate_in, rate_out).  The descriptor table travels in front of the packed PCM16 in one staging buffer.
+// Polyphase resampler (resample.hip): the filter design, the one-shot / streaming launch and the bank launch (api.cpp
+// bnhip_resampler_bank_*), which resamples one call's frames of every stream of a bank that shares (rate_in, rate_out).  The
+// bank's descriptor table travels in front of the packed PCM16 in one staging buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace bnhip {
+
+// the [L][T] phase table of rate ratio L/M (filter half-length half_factor * max(L, M) taps)
+void resample_design(int L, int M, double beta, int half_factor, std::vector<float>* table, int* T_out, int* half_out);
+
+// LDS a launch of this geometry needs (phase table + worst-case input span of 256 outputs); more than RESAMPLE_LDS_MAX does not run
+size_t resample_lds(int L, int M, int T);
+constexpr size_t RESAMPLE_LDS_MAX = 150 * 1024;
+
+// returns 0 on success, -1 if the geometry does not fit LDS
+int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_pcm16, int out_pcm16, int n_clips, int n_in,
+                    int n_out, int L, int M, int T, int half, long long i_base, long long n_base, hipStream_t s);
 
 // One stream of one call.  Stream indices (n_base, i_next, keep_from) are positions since the stream started.
 struct ResampleBankDesc {
@@ -25,8 +39,6 @@ struct ResampleBankDesc {
 };
 static_assert(sizeof(ResampleBankDesc) == 64, "descriptor layout");
 
-// LDS a launch of this geometry needs (phase table + worst-case input span of 256 outputs), as launch_resample
-size_t resample_bank_lds(int L, int M, int T);
 // returns 0 on success, -1 if the geometry does not fit LDS
 int launch_resample_bank(const ResampleBankDesc* d_desc, int n_desc, int n_blocks, const int16_t* d_pcm, float* d_hist,
                          int16_t* d_out, const float* d_table, int L, int M, int T, int half, hipStream_t s);

@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "kernels.h"
-#include "resample_bank.h"
+#include "resample.h"
 
 namespace bnhip {
 
@@ -109,10 +109,8 @@ __global__ __launch_bounds__(256) void k_resample(const void* __restrict__ in_, 
 // returns 0 on success, -1 if the geometry does not fit LDS
 int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_pcm16, int out_pcm16, int n_clips, int n_in,
                     int n_out, int L, int M, int T, int half, long long i_base, long long n_base, hipStream_t s) {
-    // worst-case input span of 256 outputs
-    long long span = ((long long)255 * M) / L + T + 2;
-    size_t lds = ((size_t)L * T + (size_t)span) * sizeof(float);
-    if (lds > 150 * 1024) return -1;
+    const size_t lds = resample_lds(L, M, T);
+    if (lds > RESAMPLE_LDS_MAX) return -1;
     dim3 grid((n_out + 255) / 256, n_clips);
 #define BN_RS(IP, OP)                                                                                                        \
     do {                                                                                                                     \
@@ -187,15 +185,15 @@ __global__ __launch_bounds__(256) void k_resample_bank(const ResampleBankDesc* _
     out[(size_t)d.out_off + i] = (int16_t)(f * 32767.0f);     // truncation toward zero
 }
 
-size_t resample_bank_lds(int L, int M, int T) {
+size_t resample_lds(int L, int M, int T) {
     const long long span = ((long long)255 * M) / L + T + 2;
     return ((size_t)L * T + (size_t)span) * sizeof(float);
 }
 
 int launch_resample_bank(const ResampleBankDesc* d_desc, int n_desc, int n_blocks, const int16_t* d_pcm, float* d_hist,
                          int16_t* d_out, const float* d_table, int L, int M, int T, int half, hipStream_t s) {
-    const size_t lds = resample_bank_lds(L, M, T);
-    if (lds > 150 * 1024) return -1;
+    const size_t lds = resample_lds(L, M, T);
+    if (lds > RESAMPLE_LDS_MAX) return -1;
     if (n_desc <= 0 || n_blocks <= 0) return 0;
     lds_limit_once<&k_resample_bank>(160 * 1024);
     hipLaunchKernelGGL(k_resample_bank, dim3(n_blocks), dim3(256), lds, s, d_desc, n_desc, d_pcm, d_hist, d_out, d_table, L, M, T, half);

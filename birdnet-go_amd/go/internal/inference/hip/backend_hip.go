@@ -1050,13 +1050,9 @@ func ResampleBytes(pcm []byte, fromRate, toRate int, device int) ([]byte, error)
 // all the frames it is given in one device call (bnhip_resampler_bank_*).  Every stream's bytes are those its own Resampler
 // would return for the same frames.  Calls are serialised on the bank.
 type ResamplerBank struct {
-	mu               sync.Mutex
+	bankStage
 	h                *C.bnhip_resampler_bank
 	fromRate, toRate int
-	stage            unsafe.Pointer // C memory: this call's frames back to back
-	stageCap         int
-	ptrs             unsafe.Pointer // C memory: one const int16_t* per frame
-	ptrsCap          int
 }
 
 // NewResamplerBank: nil, nil for equal rates, as NewResampler.
@@ -1070,7 +1066,7 @@ func NewResamplerBank(fromRate, toRate, maxStreams, device int) (*ResamplerBank,
 	if rc := C.bnbind_rb_create(C.int(device), C.int(fromRate), C.int(toRate), C.int(maxStreams), &h); rc != 0 || h == nil {
 		return nil, fmt.Errorf("failed to create resampler bank from %d Hz to %d Hz: %s", fromRate, toRate, lastError())
 	}
-	return &ResamplerBank{h: h, fromRate: fromRate, toRate: toRate}, nil
+	return &ResamplerBank{bankStage: bankStage{what: "resampler bank"}, h: h, fromRate: fromRate, toRate: toRate}, nil
 }
 
 // AddStream starts a stream (one source's Resampler); slots of removed streams are reused with fresh state.
@@ -1111,42 +1107,6 @@ func (b *ResamplerBank) EstimateOutputBytes(inputBytes int) int {
 	return int(C.bnbind_rb_estimate(b.h, C.int(inputBytes/bytesPerSample))) * bytesPerSample
 }
 
-// stageLocked copies the frames into the bank's C staging; -> the pointer table, the per-frame sample counts.
-func (b *ResamplerBank) stageLocked(frames [][]byte) (**C.int16_t, []C.int, error) {
-	total := 0
-	for _, f := range frames {
-		if len(f)%bytesPerSample != 0 {
-			return nil, nil, fmt.Errorf("input length %d is not a multiple of %d", len(f), bytesPerSample)
-		}
-		total += len(f)
-	}
-	if total > b.stageCap || b.stage == nil {
-		C.free(b.stage)
-		b.stage, b.stageCap = C.malloc(C.size_t(total+1)), total+1
-	}
-	if len(frames) > b.ptrsCap || b.ptrs == nil {
-		C.free(b.ptrs)
-		b.ptrs, b.ptrsCap = C.malloc(C.size_t((len(frames)+1)*int(unsafe.Sizeof(uintptr(0))))), len(frames)+1
-	}
-	if b.stage == nil || b.ptrs == nil {
-		C.free(b.stage)
-		C.free(b.ptrs)
-		b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
-		return nil, nil, errors.New("hip: out of host memory (resampler bank staging)")
-	}
-	lens := make([]C.int, len(frames)+1)
-	offs := make([]C.int, len(frames)+1)
-	stage := unsafe.Slice((*byte)(b.stage), b.stageCap)
-	pos := 0
-	for k, f := range frames {
-		copy(stage[pos:], f)
-		offs[k], lens[k] = C.int(pos), C.int(len(f)/bytesPerSample)
-		pos += len(f)
-	}
-	C.bnbind_rb_point((**C.int16_t)(b.ptrs), (*C.char)(b.stage), &offs[0], C.int(len(frames)))
-	return (**C.int16_t)(b.ptrs), lens, nil
-}
-
 // Process resamples frames[k] of streams[k] for every k in one device call -> one slice per frame, each what that stream's
 // Resampler.ResampleInto returns for it in sequence (a stream may appear several times; its frames go in slice order).  An
 // unknown stream or an odd byte count fails the whole call before any stream advances.
@@ -1162,7 +1122,7 @@ func (b *ResamplerBank) Process(streams []int, frames [][]byte) ([][]byte, error
 	if len(frames) == 0 {
 		return nil, nil
 	}
-	ptrs, lens, err := b.stageLocked(frames)
+	ptrs, lens, err := b.stage(frames)
 	if err != nil {
 		return nil, err
 	}
@@ -1180,15 +1140,7 @@ func (b *ResamplerBank) Process(streams []int, frames [][]byte) ([][]byte, error
 		C.size_t(capSamples), &counts[0]); rc != 0 {
 		return nil, fmt.Errorf("hip: resampler bank failed (%d): %s", int(rc), lastError())
 	}
-	res := make([][]byte, len(frames))
-	raw := unsafe.Slice((*byte)(unsafe.Pointer(&out[0])), len(out)*bytesPerSample)
-	pos := 0
-	for k, c := range counts {
-		n := int(c) * bytesPerSample
-		res[k] = raw[pos : pos+n : pos+n]
-		pos += n
-	}
-	return res, nil
+	return splitPacked(out, counts), nil
 }
 
 // Flush ends each listed stream (each at most once): its tail, then the stream starts anew (Resampler.Flush).
@@ -1214,15 +1166,7 @@ func (b *ResamplerBank) Flush(streams []int) ([][]byte, error) {
 		&counts[0]); rc != 0 {
 		return nil, fmt.Errorf("hip: resampler bank flush failed (%d): %s", int(rc), lastError())
 	}
-	res := make([][]byte, len(streams))
-	raw := unsafe.Slice((*byte)(unsafe.Pointer(&out[0])), len(out)*bytesPerSample)
-	pos := 0
-	for k, c := range counts {
-		n := int(c) * bytesPerSample
-		res[k] = raw[pos : pos+n : pos+n]
-		pos += n
-	}
-	return res, nil
+	return splitPacked(out, counts), nil
 }
 
 func (b *ResamplerBank) FromRate() int { return b.fromRate }
@@ -1235,9 +1179,7 @@ func (b *ResamplerBank) Close() error {
 		C.bnbind_rb_destroy(b.h)
 		b.h = nil
 	}
-	C.free(b.stage)
-	C.free(b.ptrs)
-	b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
+	b.release()
 	return nil
 }
 
@@ -1246,37 +1188,10 @@ func (b *ResamplerBank) Close() error {
 // input frame (AnalysisBuffer.Write per frame, analysis.go:152-175), in one device call.  Every source and stream is checked
 // before anything runs: an error leaves every stream and every ring as it was.
 func (w *WindowAssembler) WriteResampled(bank *ResamplerBank, streams, sources []int, frames [][]byte) error {
-	if len(streams) != len(frames) || len(sources) != len(frames) {
-		return fmt.Errorf("hip: %d streams and %d sources for %d frames", len(streams), len(sources), len(frames))
-	}
-	w.life.RLock()
-	defer w.life.RUnlock()
-	if w.h == nil {
-		return errors.New("hip: window assembler is closed")
-	}
-	bank.mu.Lock()
-	defer bank.mu.Unlock()
-	if bank.h == nil {
-		return errors.New("hip: resampler bank is closed")
-	}
-	if len(frames) == 0 {
-		return nil
-	}
-	ptrs, lens, err := bank.stageLocked(frames)
-	if err != nil {
-		return err
-	}
-	st := make([]C.int, len(frames))
-	src := make([]C.int, len(frames))
-	for k := range frames {
-		st[k], src[k] = C.int(streams[k]), C.int(sources[k])
-	}
-	runtime.LockOSThread()
-	defer runtime.UnlockOSThread()
-	if rc := C.bnbind_win_write_resampled(w.h, bank.h, C.int(len(frames)), &st[0], &src[0], ptrs, &lens[0]); rc != 0 {
-		return fmt.Errorf("hip: windows_write_resampled failed (%d): %s", int(rc), lastError())
-	}
-	return nil
+	return w.writeFrames(&bank.bankStage, func() bool { return bank.h != nil }, streams, sources, frames,
+		func(n C.int, st, src *C.int, ptrs **C.int16_t, lens *C.int) C.int {
+			return C.bnbind_win_write_resampled(w.h, bank.h, n, st, src, ptrs, lens)
+		})
 }
 
 // EqualizerBank is the analysis route's processing, AudioRouter.applyProcessing (internal/audiocore/router.go:1006-1080), for
@@ -1284,12 +1199,8 @@ func (w *WindowAssembler) WriteResampled(bank *ResamplerBank, streams, sources [
 // truncates all the frames it is given in one device call (bnhip_eq_bank_*).  Every stream's bytes are those of the
 // reference's float64 arithmetic for the same sections.  Calls are serialised on the bank.
 type EqualizerBank struct {
-	mu       sync.Mutex
-	h        *C.bnhip_eq_bank
-	stage    unsafe.Pointer // C memory: this call's frames back to back
-	stageCap int
-	ptrs     unsafe.Pointer // C memory: one const int16_t* per frame
-	ptrsCap  int
+	bankStage
+	h *C.bnhip_eq_bank
 }
 
 func NewEqualizerBank(maxStreams, device int) (*EqualizerBank, error) {
@@ -1299,7 +1210,7 @@ func NewEqualizerBank(maxStreams, device int) (*EqualizerBank, error) {
 	if rc := C.bnbind_eq_create(C.int(device), C.int(maxStreams), &h); rc != 0 || h == nil {
 		return nil, fmt.Errorf("failed to create equalizer bank: %s", lastError())
 	}
-	return &EqualizerBank{h: h}, nil
+	return &EqualizerBank{bankStage: bankStage{what: "equalizer bank"}, h: h}, nil
 }
 
 // AddStream starts a stream with no chain and gain 1 (pass-through); slots of removed streams are reused with fresh state.
@@ -1371,42 +1282,6 @@ func (b *EqualizerBank) Reset(stream int) error {
 	return nil
 }
 
-// stageLocked copies the frames into the bank's C staging (as ResamplerBank.stageLocked).
-func (b *EqualizerBank) stageLocked(frames [][]byte) (**C.int16_t, []C.int, error) {
-	total := 0
-	for _, f := range frames {
-		if len(f)%bytesPerSample != 0 {
-			return nil, nil, fmt.Errorf("input length %d is not a multiple of %d", len(f), bytesPerSample)
-		}
-		total += len(f)
-	}
-	if total > b.stageCap || b.stage == nil {
-		C.free(b.stage)
-		b.stage, b.stageCap = C.malloc(C.size_t(total+1)), total+1
-	}
-	if len(frames) > b.ptrsCap || b.ptrs == nil {
-		C.free(b.ptrs)
-		b.ptrs, b.ptrsCap = C.malloc(C.size_t((len(frames)+1)*int(unsafe.Sizeof(uintptr(0))))), len(frames)+1
-	}
-	if b.stage == nil || b.ptrs == nil {
-		C.free(b.stage)
-		C.free(b.ptrs)
-		b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
-		return nil, nil, errors.New("hip: out of host memory (equalizer bank staging)")
-	}
-	lens := make([]C.int, len(frames)+1)
-	offs := make([]C.int, len(frames)+1)
-	stage := unsafe.Slice((*byte)(b.stage), b.stageCap)
-	pos := 0
-	for k, f := range frames {
-		copy(stage[pos:], f)
-		offs[k], lens[k] = C.int(pos), C.int(len(f)/bytesPerSample)
-		pos += len(f)
-	}
-	C.bnbind_rb_point((**C.int16_t)(b.ptrs), (*C.char)(b.stage), &offs[0], C.int(len(frames)))
-	return (**C.int16_t)(b.ptrs), lens, nil
-}
-
 // Process runs frames[k] of streams[k] for every k in one device call -> one slice per frame, as long as its input (a stream
 // may appear several times; its frames go in slice order).  An unknown stream or an odd byte count fails the whole call
 // before any stream advances.
@@ -1422,7 +1297,7 @@ func (b *EqualizerBank) Process(streams []int, frames [][]byte) ([][]byte, error
 	if len(frames) == 0 {
 		return nil, nil
 	}
-	ptrs, lens, err := b.stageLocked(frames)
+	ptrs, lens, err := b.stage(frames)
 	if err != nil {
 		return nil, err
 	}
@@ -1440,15 +1315,7 @@ func (b *EqualizerBank) Process(streams []int, frames [][]byte) ([][]byte, error
 		C.size_t(total), &counts[0]); rc != 0 {
 		return nil, fmt.Errorf("hip: equalizer bank failed (%d): %s", int(rc), lastError())
 	}
-	res := make([][]byte, len(frames))
-	raw := unsafe.Slice((*byte)(unsafe.Pointer(&out[0])), len(out)*bytesPerSample)
-	pos := 0
-	for k, c := range counts {
-		n := int(c) * bytesPerSample
-		res[k] = raw[pos : pos+n : pos+n]
-		pos += n
-	}
-	return res, nil
+	return splitPacked(out, counts), nil
 }
 
 func (b *EqualizerBank) Close() error {
@@ -1458,9 +1325,7 @@ func (b *EqualizerBank) Close() error {
 		C.bnbind_eq_destroy(b.h)
 		b.h = nil
 	}
-	C.free(b.stage)
-	C.free(b.ptrs)
-	b.stage, b.stageCap, b.ptrs, b.ptrsCap = nil, 0, nil, 0
+	b.release()
 	return nil
 }
 
@@ -1468,6 +1333,81 @@ func (b *EqualizerBank) Close() error {
 // write per frame, in one device call.  Every source and stream is checked before anything runs: an error leaves every
 // stream and every ring as it was.
 func (w *WindowAssembler) WriteEqualized(bank *EqualizerBank, streams, sources []int, frames [][]byte) error {
+	return w.writeFrames(&bank.bankStage, func() bool { return bank.h != nil }, streams, sources, frames,
+		func(n C.int, st, src *C.int, ptrs **C.int16_t, lens *C.int) C.int {
+			return C.bnbind_win_write_equalized(w.h, bank.h, n, st, src, ptrs, lens)
+		})
+}
+
+// bankStage is what both banks share: the mutex that serialises calls on the bank, its name in errors, and the C memory a call
+// stages its frames in (cgo: C may not keep or receive Go pointers into Go memory).
+type bankStage struct {
+	mu      sync.Mutex
+	what    string         // "resampler bank" | "equalizer bank"
+	buf     unsafe.Pointer // C memory: this call's frames back to back
+	bufCap  int
+	ptrs    unsafe.Pointer // C memory: one const int16_t* per frame
+	ptrsCap int
+}
+
+// stage copies the frames into the C staging (the caller holds mu); -> the pointer table, the per-frame sample counts.
+func (s *bankStage) stage(frames [][]byte) (**C.int16_t, []C.int, error) {
+	total := 0
+	for _, f := range frames {
+		if len(f)%bytesPerSample != 0 {
+			return nil, nil, fmt.Errorf("input length %d is not a multiple of %d", len(f), bytesPerSample)
+		}
+		total += len(f)
+	}
+	if total > s.bufCap || s.buf == nil {
+		C.free(s.buf)
+		s.buf, s.bufCap = C.malloc(C.size_t(total+1)), total+1
+	}
+	if len(frames) > s.ptrsCap || s.ptrs == nil {
+		C.free(s.ptrs)
+		s.ptrs, s.ptrsCap = C.malloc(C.size_t((len(frames)+1)*int(unsafe.Sizeof(uintptr(0))))), len(frames)+1
+	}
+	if s.buf == nil || s.ptrs == nil {
+		s.release()
+		return nil, nil, fmt.Errorf("hip: out of host memory (%s staging)", s.what)
+	}
+	lens := make([]C.int, len(frames)+1)
+	offs := make([]C.int, len(frames)+1)
+	buf := unsafe.Slice((*byte)(s.buf), s.bufCap)
+	pos := 0
+	for k, f := range frames {
+		copy(buf[pos:], f)
+		offs[k], lens[k] = C.int(pos), C.int(len(f)/bytesPerSample)
+		pos += len(f)
+	}
+	C.bnbind_rb_point((**C.int16_t)(s.ptrs), (*C.char)(s.buf), &offs[0], C.int(len(frames)))
+	return (**C.int16_t)(s.ptrs), lens, nil
+}
+
+// release frees the staging (the caller holds mu); the next stage allocates anew.
+func (s *bankStage) release() {
+	C.free(s.buf)
+	C.free(s.ptrs)
+	s.buf, s.bufCap, s.ptrs, s.ptrsCap = nil, 0, nil, 0
+}
+
+// splitPacked cuts a bank call's packed outputs into one slice per frame, counts[k] samples each (views of out).
+func splitPacked(out []int16, counts []C.int) [][]byte {
+	res := make([][]byte, len(counts))
+	raw := unsafe.Slice((*byte)(unsafe.Pointer(&out[0])), len(out)*bytesPerSample)
+	pos := 0
+	for k, c := range counts {
+		n := int(c) * bytesPerSample
+		res[k] = raw[pos : pos+n : pos+n]
+		pos += n
+	}
+	return res
+}
+
+// writeFrames is the body of WriteResampled and WriteEqualized: with the assembler and the bank locked and open, the frames staged
+// in the bank's C memory and write(n, streams, sources, frame pointers, lengths) = that bank's bnhip_windows_write_* call.
+func (w *WindowAssembler) writeFrames(bank *bankStage, open func() bool, streams, sources []int, frames [][]byte,
+	write func(n C.int, st, src *C.int, ptrs **C.int16_t, lens *C.int) C.int) error {
 	if len(streams) != len(frames) || len(sources) != len(frames) {
 		return fmt.Errorf("hip: %d streams and %d sources for %d frames", len(streams), len(sources), len(frames))
 	}
@@ -1478,13 +1418,13 @@ func (w *WindowAssembler) WriteEqualized(bank *EqualizerBank, streams, sources [
 	}
 	bank.mu.Lock()
 	defer bank.mu.Unlock()
-	if bank.h == nil {
-		return errors.New("hip: equalizer bank is closed")
+	if !open() {
+		return fmt.Errorf("hip: %s is closed", bank.what)
 	}
 	if len(frames) == 0 {
 		return nil
 	}
-	ptrs, lens, err := bank.stageLocked(frames)
+	ptrs, lens, err := bank.stage(frames)
 	if err != nil {
 		return err
 	}
@@ -1495,8 +1435,8 @@ func (w *WindowAssembler) WriteEqualized(bank *EqualizerBank, streams, sources [
 	}
 	runtime.LockOSThread()
 	defer runtime.UnlockOSThread()
-	if rc := C.bnbind_win_write_equalized(w.h, bank.h, C.int(len(frames)), &st[0], &src[0], ptrs, &lens[0]); rc != 0 {
-		return fmt.Errorf("hip: windows_write_equalized failed (%d): %s", int(rc), lastError())
+	if rc := write(C.int(len(frames)), &st[0], &src[0], ptrs, &lens[0]); rc != 0 {
+		return fmt.Errorf("hip: writing %s frames to the windows failed (%d): %s", bank.what, int(rc), lastError())
 	}
 	return nil
 }

@@ -599,27 +599,102 @@ def _pcm16_frames(frames):
     return arrs, ptrs, lens
 
 
-class ResamplerBank:
+def _c_ints(values):
+    v = [int(x) for x in values]
+    return (C.c_int * max(len(v), 1))(*v)
+
+
+def _split_frames(out, counts):
+    """Packed int16 outputs and the per-frame sample counts -> one bytes object per frame."""
+    res, pos = [], 0
+    for c in counts:
+        res.append(out[pos:pos + c].tobytes())
+        pos += int(c)
+    return res
+
+
+class _StreamBank:
+    """What ResamplerBank and EqualizerBank share: the handle `_h` of bnhip_<_prefix>_*, its stream slots, `process` (one bytes
+    object per frame), `write_windows` (one ring write per frame, through _write) and the lifetime.  A subclass binds its own
+    entries with _bind and bounds process's default out_cap with _out_bound."""
+
+    _prefix = _what = _write = None
+
+    def _bind(self, **argtypes):
+        """Loads the library and declares the shared entries plus the subclass's own (entry suffix -> argtypes)."""
+        self._lib = L = load_library()
+        vp, ci = C.c_void_p, C.c_int
+        argtypes.update(add_stream=[vp, C.POINTER(ci)], remove_stream=[vp, ci], process_pcm16=[vp, ci, vp, vp, vp, vp, C.c_size_t, vp],
+                        destroy=[vp])
+        for name, types in argtypes.items():
+            getattr(L, f"bnhip_{self._prefix}_{name}").argtypes = types
+        getattr(L, f"bnhip_{self._prefix}_destroy").restype = None
+        getattr(L, self._write).argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        self._h = C.c_void_p()
+        return L
+
+    def _fn(self, name):
+        return getattr(self._lib, f"bnhip_{self._prefix}_{name}")
+
+    def add_stream(self):
+        s = C.c_int(-1)
+        _check(self._lib, self._fn("add_stream")(self._alive(), C.byref(s)))
+        return s.value
+
+    def remove_stream(self, stream):
+        _check(self._lib, self._fn("remove_stream")(self._alive(), int(stream)))
+
+    def process(self, items, out_cap=None):
+        """[(stream, pcm16 bytes | int16 array), ...] -> [bytes, ...] per frame.  out_cap (samples) defaults to the most the frames
+        can give; a smaller one is the library's E_INVALID (for tests of that path)."""
+        streams = _c_ints(s for s, _ in items)
+        arrs, ptrs, lens = _pcm16_frames([f for _, f in items])
+        if out_cap is None:
+            out_cap = self._out_bound(arrs)
+        out = np.empty(max(out_cap, 1), np.int16)
+        counts = np.zeros(max(len(items), 1), np.int32)
+        _check(self._lib, self._fn("process_pcm16")(self._alive(), len(items), streams, ptrs, lens, out.ctypes.data, out_cap,
+                                                    counts.ctypes.data))
+        return _split_frames(out, counts[:len(items)])
+
+    def write_windows(self, win, items):
+        """[(stream, source, pcm16), ...] -> each frame's result written into source `source` of win (stream.NativeWindows), one
+        ring write per frame, without the samples leaving the library."""
+        streams = _c_ints(s for s, _, _ in items)
+        sources = _c_ints(src for _, src, _ in items)
+        arrs, ptrs, lens = _pcm16_frames([f for _, _, f in items])
+        win._check(getattr(self._lib, self._write)(win._alive(), self._alive(), len(items), streams, sources, ptrs, lens))
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def _alive(self):
+        if not self._h:
+            raise HipError(E_INVALID, f"{self._what} is closed")
+        return self._h
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ResamplerBank(_StreamBank):
     """`bnhip_resampler_bank` (include/bnhip.h): one StreamResampler per stream for many streams of one (from, to) rate pair,
     every call one device call.  `process([(stream, pcm16), ...])` -> one bytes object per frame, each what that stream's own
     StreamResampler returns for the frame in sequence (a stream may appear several times; its frames go in list order);
     `write_windows(win, [(stream, source, pcm16), ...])` writes each frame's result into `source` of a stream.NativeWindows,
-    one ring write per frame, without the samples leaving the library.  Errors leave every stream untouched."""
+    one ring write per frame (bnhip_windows_write_resampled).  Errors leave every stream untouched."""
+
+    _prefix, _what, _write = "resampler_bank", "resampler bank", "bnhip_windows_write_resampled"
 
     def __init__(self, from_rate, to_rate, max_streams=256, device=0):
-        self._lib = L = load_library()
         vp, ci = C.c_void_p, C.c_int
-        L.bnhip_resampler_bank_create.argtypes = [ci, ci, ci, ci, C.POINTER(vp)]
-        L.bnhip_resampler_bank_add_stream.argtypes = [vp, C.POINTER(ci)]
-        L.bnhip_resampler_bank_remove_stream.argtypes = [vp, ci]
-        L.bnhip_resampler_bank_estimate.argtypes = [vp, ci]
-        L.bnhip_resampler_bank_process_pcm16.argtypes = [vp, ci, vp, vp, vp, vp, C.c_size_t, vp]
-        L.bnhip_resampler_bank_flush_pcm16.argtypes = [vp, ci, vp, vp, C.c_size_t, vp]
-        L.bnhip_windows_write_resampled.argtypes = [vp, vp, ci, vp, vp, vp, vp]
-        L.bnhip_resampler_bank_destroy.argtypes = [vp]
-        L.bnhip_resampler_bank_destroy.restype = None
+        L = self._bind(create=[ci, ci, ci, ci, C.POINTER(vp)], estimate=[vp, ci], flush_pcm16=[vp, ci, vp, vp, C.c_size_t, vp])
         self.from_rate, self.to_rate, self.max_streams = int(from_rate), int(to_rate), int(max_streams)
-        self._h = C.c_void_p()
         _check(L, L.bnhip_resampler_bank_create(device, self.from_rate, self.to_rate, self.max_streams, C.byref(self._h)))
         if not self._h:
             raise HipError(E_INVALID, "equal rates need no resampler bank (ResamplerBank.new returns None)")
@@ -629,71 +704,20 @@ class ResamplerBank:
         """None when no resampling is required, as NewResampler (resample.go:58-60)."""
         return None if from_rate == to_rate else cls(from_rate, to_rate, max_streams, device)
 
-    def add_stream(self):
-        s = C.c_int(-1)
-        _check(self._lib, self._lib.bnhip_resampler_bank_add_stream(self._alive(), C.byref(s)))
-        return s.value
-
-    def remove_stream(self, stream):
-        _check(self._lib, self._lib.bnhip_resampler_bank_remove_stream(self._alive(), int(stream)))
-
     def estimate_output_bytes(self, input_bytes):
         return int(self._lib.bnhip_resampler_bank_estimate(self._alive(), int(input_bytes) // 2)) * 2
 
-    def process(self, items, out_cap=None):
-        """[(stream, pcm16 bytes | int16 array), ...] -> [bytes, ...] per frame.  out_cap (samples) defaults to the sum of the
-        frames' estimates; a smaller one is the library's E_INVALID (for tests of that path)."""
-        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _ in items])
-        arrs, ptrs, lens = _pcm16_frames([f for _, f in items])
-        if out_cap is None:
-            out_cap = sum(int(self._lib.bnhip_resampler_bank_estimate(self._alive(), a.size)) for a in arrs)
-        out = np.empty(max(out_cap, 1), np.int16)
-        counts = np.zeros(max(len(items), 1), np.int32)
-        _check(self._lib, self._lib.bnhip_resampler_bank_process_pcm16(self._alive(), len(items), streams, ptrs, lens, out.ctypes.data,
-                                                                        out_cap, counts.ctypes.data))
-        res, pos = [], 0
-        for c in counts[:len(items)]:
-            res.append(out[pos:pos + c].tobytes())
-            pos += int(c)
-        return res
+    def _out_bound(self, arrs):                     # the sum of the frames' estimates
+        return sum(int(self._lib.bnhip_resampler_bank_estimate(self._alive(), a.size)) for a in arrs)
 
     def flush(self, streams, cap=1 << 16):
         """End of each listed stream: the tail per stream; each then starts anew."""
         streams = list(streams)
-        arr = (C.c_int * max(len(streams), 1))(*[int(s) for s in streams])
         out = np.empty(cap, np.int16)
         counts = np.zeros(max(len(streams), 1), np.int32)
-        _check(self._lib, self._lib.bnhip_resampler_bank_flush_pcm16(self._alive(), len(streams), arr, out.ctypes.data, cap,
+        _check(self._lib, self._lib.bnhip_resampler_bank_flush_pcm16(self._alive(), len(streams), _c_ints(streams), out.ctypes.data, cap,
                                                                       counts.ctypes.data))
-        res, pos = [], 0
-        for c in counts[:len(streams)]:
-            res.append(out[pos:pos + c].tobytes())
-            pos += int(c)
-        return res
-
-    def write_windows(self, win, items):
-        """[(stream, source, pcm16), ...] -> each frame resampled and written into source `source` of win (stream.NativeWindows),
-        one ring write per frame (bnhip_windows_write_resampled)."""
-        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _, _ in items])
-        sources = (C.c_int * max(len(items), 1))(*[int(src) for _, src, _ in items])
-        arrs, ptrs, lens = _pcm16_frames([f for _, _, f in items])
-        win._check(self._lib.bnhip_windows_write_resampled(win._alive(), self._alive(), len(items), streams, sources, ptrs, lens))
-
-    def close(self):
-        if self._h:
-            self._lib.bnhip_resampler_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def _alive(self):
-        if not self._h:
-            raise HipError(E_INVALID, "resampler bank is closed")
-        return self._h
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _split_frames(out, counts[:len(streams)])
 
 
 # equalizer.go's filter names -> bnhip.h BNHIP_EQ_*
@@ -746,7 +770,7 @@ def gain_linear(gain_db):
     return 10.0 ** (float(gain_db) / 20.0)
 
 
-class EqualizerBank:
+class EqualizerBank(_StreamBank):
     """`bnhip_eq_bank` (include/bnhip.h): the analysis route's EQ chain + gain (AudioRouter.applyProcessing) for many streams,
     every call one device call.  `set_chain(stream, chain, gain_linear)` installs [(section6, passes), ...] (None or [] = no
     filters) with zero state; `process([(stream, pcm16), ...])` -> one bytes object per frame, as many samples as its input (a
@@ -754,30 +778,13 @@ class EqualizerBank:
     each frame's result into `source` of a stream.NativeWindows, one ring write per frame.  Errors leave every stream untouched."""
 
     MAX_STAGES = 16
+    _prefix, _what, _write = "eq_bank", "equalizer bank", "bnhip_windows_write_equalized"
 
     def __init__(self, max_streams=256, device=0):
-        self._lib = L = load_library()
         vp, ci = C.c_void_p, C.c_int
-        L.bnhip_eq_bank_create.argtypes = [ci, ci, C.POINTER(vp)]
-        L.bnhip_eq_bank_add_stream.argtypes = [vp, C.POINTER(ci)]
-        L.bnhip_eq_bank_remove_stream.argtypes = [vp, ci]
-        L.bnhip_eq_bank_set_chain.argtypes = [vp, ci, vp, ci, vp, C.c_double]
-        L.bnhip_eq_bank_reset.argtypes = [vp, ci]
-        L.bnhip_eq_bank_process_pcm16.argtypes = [vp, ci, vp, vp, vp, vp, C.c_size_t, vp]
-        L.bnhip_windows_write_equalized.argtypes = [vp, vp, ci, vp, vp, vp, vp]
-        L.bnhip_eq_bank_destroy.argtypes = [vp]
-        L.bnhip_eq_bank_destroy.restype = None
+        L = self._bind(create=[ci, ci, C.POINTER(vp)], set_chain=[vp, ci, vp, ci, vp, C.c_double], reset=[vp, ci])
         self.max_streams = int(max_streams)
-        self._h = C.c_void_p()
         _check(L, L.bnhip_eq_bank_create(device, self.max_streams, C.byref(self._h)))
-
-    def add_stream(self):
-        s = C.c_int(-1)
-        _check(self._lib, self._lib.bnhip_eq_bank_add_stream(self._alive(), C.byref(s)))
-        return s.value
-
-    def remove_stream(self, stream):
-        _check(self._lib, self._lib.bnhip_eq_bank_remove_stream(self._alive(), int(stream)))
 
     def set_chain(self, stream, chain, gain_linear=1.0):
         chain = list(chain or [])
@@ -789,46 +796,8 @@ class EqualizerBank:
     def reset(self, stream):
         _check(self._lib, self._lib.bnhip_eq_bank_reset(self._alive(), int(stream)))
 
-    def process(self, items, out_cap=None):
-        """[(stream, pcm16 bytes | int16 array), ...] -> [bytes, ...] per frame.  out_cap (samples) defaults to the total input;
-        a smaller one is the library's E_INVALID (for tests of that path)."""
-        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _ in items])
-        arrs, ptrs, lens = _pcm16_frames([f for _, f in items])
-        if out_cap is None:
-            out_cap = sum(a.size for a in arrs)
-        out = np.empty(max(out_cap, 1), np.int16)
-        counts = np.zeros(max(len(items), 1), np.int32)
-        _check(self._lib, self._lib.bnhip_eq_bank_process_pcm16(self._alive(), len(items), streams, ptrs, lens, out.ctypes.data, out_cap,
-                                                                counts.ctypes.data))
-        res, pos = [], 0
-        for c in counts[:len(items)]:
-            res.append(out[pos:pos + c].tobytes())
-            pos += int(c)
-        return res
-
-    def write_windows(self, win, items):
-        """[(stream, source, pcm16), ...] -> each frame processed and written into source `source` of win (stream.NativeWindows),
-        one ring write per frame (bnhip_windows_write_equalized)."""
-        streams = (C.c_int * max(len(items), 1))(*[int(s) for s, _, _ in items])
-        sources = (C.c_int * max(len(items), 1))(*[int(src) for _, src, _ in items])
-        arrs, ptrs, lens = _pcm16_frames([f for _, _, f in items])
-        win._check(self._lib.bnhip_windows_write_equalized(win._alive(), self._alive(), len(items), streams, sources, ptrs, lens))
-
-    def close(self):
-        if self._h:
-            self._lib.bnhip_eq_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def _alive(self):
-        if not self._h:
-            raise HipError(E_INVALID, "equalizer bank is closed")
-        return self._h
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _out_bound(self, arrs):                     # the total input
+        return sum(a.size for a in arrs)
 
 
 class Perch:

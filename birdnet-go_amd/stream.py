@@ -789,58 +789,57 @@ class WindowBatcher:
             for ab in targets:
                 ab.write(out)
 
+    def _bank_call(self, bank, items, failed):
+        """(under self.mu) One call of `bank` (host.EqualizerBank / host.ResamplerBank) for the queued [(source, stream, pcm bytes,
+        buffers), ...], `buffers` being the rings an item may be written to directly.  When every item has exactly one and all of
+        them are in one assembler the results go straight into its rings (bank.write_windows) -> None; otherwise they come back,
+        one bytes object per item.  A failed call loses the frames of its items (on_error, as the reference logs a failed
+        applyProcessing or resample and goes on): they count in self.errors, (sources, error) goes to `failed` -> None."""
+        try:
+            wins = {id(ab.win) for *_, bufs in items for ab in bufs}
+            if len(wins) == 1 and all(len(bufs) == 1 for *_, bufs in items):
+                bank.write_windows(items[0][3][0].win, [(st, bufs[0].index, raw) for _, st, raw, bufs in items])
+                return None
+            return bank.process([(st, raw) for _, st, raw, _ in items])
+        except Exception as e:
+            self.errors += len(items)
+            failed.append((sorted({src for src, *_ in items}), e))
+            return None
+
     def _drain_equalized(self):
         """Native: every processed source's queued frames through one device call (host.EqualizerBank), then on to the source's
-        buffers.  When each frame's source has one buffer, at its model's rate, and all of them are in one assembler the results
-        go straight into its rings (bnhip_windows_write_equalized); otherwise they come back and take write()'s path."""
-        outs = None
+        buffers: straight into the rings when each frame's source has one buffer, at its model's rate, and all of them are in one
+        assembler; otherwise the results come back and take write()'s path, so they also reach this tick's resampler queue."""
+        failed = []
         with self.mu:
             pending, self.eq_pending = self.eq_pending, []
             if not pending:
                 return
-            bufs = {}
-            for (s, m), ab in self.buffers.items():
-                bufs.setdefault(s, []).append((m, ab))
-            direct = [bufs.get(src, []) for src, _, _ in pending]
-            wins = {id(b[0][1].win) for b in direct if len(b) == 1}
-            try:
-                if len(wins) == 1 and all(len(b) == 1 and (src, b[0][0]) not in self.rates for (src, _, _), b in zip(pending, direct)):
-                    self.eq_bank.write_windows(direct[0][0][1].win, [(st, b[0][1].index, raw) for (_, st, raw), b in zip(pending, direct)])
-                else:
-                    outs = self.eq_bank.process([(st, raw) for _, st, raw in pending])
-            except Exception as e:                                # the frames of this call are lost, as a failed applyProcessing
-                self.errors += len(pending)
-                failed = (sorted({src for src, _, _ in pending}), e)
-            else:
-                failed = None
-        if failed and self.on_error:
-            self.on_error(None, *failed)
-        for (src, _, _), out in zip(pending, outs or []):
+            bufs, resampled = {}, {s for s, _ in self.rates}
+            for (s, _), ab in self.buffers.items():
+                bufs.setdefault(s, []).append(ab)
+            items = [(src, st, raw, [] if src in resampled else bufs.get(src, [])) for src, st, raw in pending]
+            outs = self._bank_call(self.eq_bank, items, failed)
+        for sources, e in failed:
+            if self.on_error:
+                self.on_error(None, sources, e)
+        for (src, *_), out in zip(items, outs or []):
             self._fan_out(src, out)
 
     def _drain_resampled(self):
-        """Native: every rate pair's queued frames through one device call (host.ResamplerBank), one ring write per frame.  When
-        each frame has one buffer and all of them are in one assembler the results go straight into its rings
-        (bnhip_windows_write_resampled); otherwise they come back and are written to every buffer of the frame's group."""
+        """Native: every rate pair's queued frames through one device call (host.ResamplerBank), one ring write per frame: straight
+        into the rings when each frame has one buffer and all of them are in one assembler; otherwise the results come back and
+        are written to every buffer of the frame's group."""
         failed = []
         with self.mu:
             pending, self.pending = self.pending, {}
             live = {id(ab) for ab in self.buffers.values()}
             for key, items in pending.items():
                 items = [(src, st, raw, [ab for ab in targets if id(ab) in live]) for src, st, raw, targets in items]
-                bank = self.banks[key]
-                try:
-                    wins = {id(ab.win) for *_, targets in items for ab in targets}
-                    if len(wins) == 1 and all(len(targets) == 1 for *_, targets in items):
-                        bank.write_windows(items[0][3][0].win, [(st, targets[0].index, raw) for _, st, raw, targets in items])
-                    else:
-                        outs = bank.process([(st, raw) for _, st, raw, _ in items])
-                        for (*_, targets), out in zip(items, outs):
-                            for ab in targets:
-                                ab.write(out)
-                except Exception as e:                        # the reference logs a failed resample and goes on (buffer_consumer.go:193-201)
-                    self.errors += len(items)
-                    failed.append((sorted({src for src, *_ in items}), e))
+                outs = self._bank_call(self.banks[key], items, failed)
+                for (*_, targets), out in zip(items, outs or []):
+                    for ab in targets:
+                        ab.write(out)
         for sources, e in failed:
             if self.on_error:
                 self.on_error(None, sources, e)

@@ -274,6 +274,15 @@ def test_errors_change_nothing(gpu):
         assert e.value.code == host.E_INVALID
     with pytest.raises(host.HipError):
         bank.set_chain(st[2], chain, float("inf"))
+    # windows: a removed stream among valid frames fails the whole call, no stream advanced and no ring written
+    w = S.NativeWindows(64, 64, max_batch=4)
+    srcs = [w.add_source(f"src{k}", 4096) for k in range(3)]
+    w.write(srcs[1], b"\x00\x01" * 50)
+    before = [w.stats(x) for x in srcs]
+    with pytest.raises(S.StreamError):
+        bank.write_windows(w, [(s, x, a) for (s, a), x in zip(items, srcs)] + [(gone, srcs[0], items[0][1])])
+    assert [w.stats(x) for x in srcs] == before
+    w.close()
     _check_bytes(bank.process(items), eqref.process(ref, items))    # exactly the bytes the call would have given
     bank.close()
 

@@ -178,6 +178,9 @@ def test_bank_error_paths_leave_state_untouched(gpu):
     streams, lens = (C.c_int * 1)(s0), (C.c_int * 1)(-2)
     ptrs, out, cnt = (C.c_void_p * 1)(x.ctypes.data), np.zeros(64, np.int16), np.zeros(1, np.int32)
     assert lib.bnhip_resampler_bank_process_pcm16(bank._h, 1, streams, ptrs, lens, out.ctypes.data, 64, cnt.ctypes.data) == host.E_INVALID
+    with pytest.raises(host.HipError) as e:                          # a stream listed twice in one flush: no stream ends
+        bank.flush([s0, s1, s0])
+    assert e.value.code == host.E_INVALID
     second = bank.process([(s0, x[4410:8820].tobytes()), (s1, x[1000:4000].tobytes())])
     rs0, rs1 = host.StreamResampler(fr, to), host.StreamResampler(fr, to)
     assert first == [rs0.resample_into(x[:4410].tobytes()), rs1.resample_into(x[:1000].tobytes())]
