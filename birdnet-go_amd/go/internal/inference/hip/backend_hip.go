@@ -73,6 +73,21 @@ typedef int  (*fn_eq_reset)(bnhip_eq_bank*, int);
 typedef int  (*fn_eq_process_pcm16)(bnhip_eq_bank*, int, const int*, const int16_t* const*, const int*, int16_t*, size_t, int*);
 typedef int  (*fn_win_write_equalized)(bnhip_windows*, bnhip_eq_bank*, int, const int*, const int*, const int16_t* const*, const int*);
 typedef void (*fn_eq_destroy)(bnhip_eq_bank*);
+typedef struct bnhip_soundlevel_bank bnhip_soundlevel_bank;
+// bnhip.h's bnhip_sound_level, restated field for field (tests/test_soundlevel_bank.py compares sizeof and every offsetof)
+typedef struct bnhip_sound_level {
+    int stream, frame;
+    int duration_s, n_bands;
+    double center_hz[32], min_db[32], max_db[32], mean_db[32];
+    int sample_count[32];
+} bnhip_sound_level;
+typedef int  (*fn_sl_bands)(int, double*, int, int*);
+typedef int  (*fn_sl_create)(int, int, int, const double*, int, bnhip_soundlevel_bank**);
+typedef int  (*fn_sl_add_stream)(bnhip_soundlevel_bank*, int, int*);
+typedef int  (*fn_sl_remove_stream)(bnhip_soundlevel_bank*, int);
+typedef int  (*fn_sl_reset)(bnhip_soundlevel_bank*, int);
+typedef int  (*fn_sl_process_pcm16)(bnhip_soundlevel_bank*, int, const int*, const int16_t* const*, const int*, bnhip_sound_level*, int, int*);
+typedef void (*fn_sl_destroy)(bnhip_soundlevel_bank*);
 
 typedef struct {
     void* handle;
@@ -90,6 +105,8 @@ typedef struct {
     fn_rb_destroy rb_destroy;
     fn_eq_create eq_create; fn_eq_add_stream eq_add_stream; fn_eq_remove_stream eq_remove_stream; fn_eq_set_chain eq_set_chain;
     fn_eq_reset eq_reset; fn_eq_process_pcm16 eq_process_pcm16; fn_win_write_equalized win_write_equalized; fn_eq_destroy eq_destroy;
+    fn_sl_bands sl_bands; fn_sl_create sl_create; fn_sl_add_stream sl_add_stream; fn_sl_remove_stream sl_remove_stream;
+    fn_sl_reset sl_reset; fn_sl_process_pcm16 sl_process_pcm16; fn_sl_destroy sl_destroy;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -132,6 +149,10 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(eq_remove_stream, "bnhip_eq_bank_remove_stream"); BN_RESOLVE(eq_set_chain, "bnhip_eq_bank_set_chain");
     BN_RESOLVE(eq_reset, "bnhip_eq_bank_reset"); BN_RESOLVE(eq_process_pcm16, "bnhip_eq_bank_process_pcm16");
     BN_RESOLVE(win_write_equalized, "bnhip_windows_write_equalized"); BN_RESOLVE(eq_destroy, "bnhip_eq_bank_destroy");
+    BN_RESOLVE(sl_bands, "bnhip_soundlevel_bands"); BN_RESOLVE(sl_create, "bnhip_soundlevel_bank_create");
+    BN_RESOLVE(sl_add_stream, "bnhip_soundlevel_bank_add_stream"); BN_RESOLVE(sl_remove_stream, "bnhip_soundlevel_bank_remove_stream");
+    BN_RESOLVE(sl_reset, "bnhip_soundlevel_bank_reset"); BN_RESOLVE(sl_process_pcm16, "bnhip_soundlevel_bank_process_pcm16");
+    BN_RESOLVE(sl_destroy, "bnhip_soundlevel_bank_destroy");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -214,6 +235,19 @@ static inline int bnbind_win_write_equalized(bnhip_windows* w, bnhip_eq_bank* b,
     return BN.win_write_equalized(w, b, n, st, src, f, n_in);
 }
 static inline void bnbind_eq_destroy(bnhip_eq_bank* b) { if (BN.eq_destroy) BN.eq_destroy(b); }
+// sound level bank (static inline, as the other banks')
+static inline int bnbind_sl_bands(int rate, double* bands6, int cap, int* n) { return BN.sl_bands(rate, bands6, cap, n); }
+static inline int bnbind_sl_create(int dev, int rate, int max_streams, const double* bands6, int n, bnhip_soundlevel_bank** b) {
+    return BN.sl_create(dev, rate, max_streams, bands6, n, b);
+}
+static inline int bnbind_sl_add_stream(bnhip_soundlevel_bank* b, int interval, int* s) { return BN.sl_add_stream(b, interval, s); }
+static inline int bnbind_sl_remove_stream(bnhip_soundlevel_bank* b, int s) { return BN.sl_remove_stream(b, s); }
+static inline int bnbind_sl_reset(bnhip_soundlevel_bank* b, int s) { return BN.sl_reset(b, s); }
+static inline int bnbind_sl_process_pcm16(bnhip_soundlevel_bank* b, int n, const int* st, const int16_t* const* f, const int* n_in,
+                                          bnhip_sound_level* reps, int max_reps, int* n_reps) {
+    return BN.sl_process_pcm16(b, n, st, f, n_in, reps, max_reps, n_reps);
+}
+static inline void bnbind_sl_destroy(bnhip_soundlevel_bank* b) { if (BN.sl_destroy) BN.sl_destroy(b); }
 // frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
 // the pointer table points at byte offset off[k] of the staging block
 static inline void bnbind_rb_point(const int16_t** ptrs, const char* stage, const int* off, int n) {
@@ -1339,11 +1373,149 @@ func (w *WindowAssembler) WriteEqualized(bank *EqualizerBank, streams, sources [
 		})
 }
 
-// bankStage is what both banks share: the mutex that serialises calls on the bank, its name in errors, and the C memory a call
+// SoundLevelBank is the 1/3-octave sound level monitor, soundlevel.Processor behind one SoundLevelConsumer route per source
+// (internal/analysis/audio_pipeline_service.go:685-740), for many sources of ONE sample rate: a stream per source, and each
+// call runs every frame it is given as one ProcessSamples call, in one device call (bnhip_soundlevel_bank_*).  Calls are
+// serialised on the bank.
+type SoundLevelBank struct {
+	bankStage
+	h *C.bnhip_soundlevel_bank
+}
+
+// NewSoundLevelBank: bands from BuildSoundLevelBands (bit-equal to the reference's); nil = the library's own table, whose
+// coefficients come from the C library's math and may differ from Go's in the last ulp.
+func NewSoundLevelBank(sampleRate, maxStreams, device int, bands []SoundLevelBand) (*SoundLevelBank, error) {
+	tbl := make([]C.double, 6*len(bands)+1)
+	for j, b := range bands {
+		for i, v := range [6]float64{b.CenterFreq, b.B0, b.B1, b.B2, b.A1, b.A2} {
+			tbl[6*j+i] = C.double(v)
+		}
+	}
+	var ptr *C.double
+	if len(bands) > 0 {
+		ptr = &tbl[0]
+	}
+	var h *C.bnhip_soundlevel_bank
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_sl_create(C.int(device), C.int(sampleRate), C.int(maxStreams), ptr, C.int(len(bands)), &h); rc != 0 || h == nil {
+		return nil, fmt.Errorf("failed to create sound level bank at %d Hz: %s", sampleRate, lastError())
+	}
+	return &SoundLevelBank{bankStage: bankStage{what: "sound level bank"}, h: h}, nil
+}
+
+// AddStream starts a fresh Processor reporting every intervalSeconds (below 1: 1); slots of removed streams are reused.
+func (b *SoundLevelBank) AddStream(intervalSeconds int) (int, error) {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return -1, errors.New("hip: sound level bank is closed")
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var s C.int
+	if rc := C.bnbind_sl_add_stream(b.h, C.int(intervalSeconds), &s); rc != 0 {
+		return -1, fmt.Errorf("hip: soundlevel_bank_add_stream failed (%d): %s", int(rc), lastError())
+	}
+	return int(s), nil
+}
+
+func (b *SoundLevelBank) RemoveStream(stream int) error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return nil
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_sl_remove_stream(b.h, C.int(stream)); rc != 0 {
+		return fmt.Errorf("hip: soundlevel_bank_remove_stream failed (%d): %s", int(rc), lastError())
+	}
+	return nil
+}
+
+// Reset is Processor.Reset: zero filter state, the partial second, the unmeasured blocks and the interval dropped.
+func (b *SoundLevelBank) Reset(stream int) error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return errors.New("hip: sound level bank is closed")
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_sl_reset(b.h, C.int(stream)); rc != 0 {
+		return fmt.Errorf("hip: soundlevel_bank_reset failed (%d): %s", int(rc), lastError())
+	}
+	return nil
+}
+
+// Process runs frames[k] of streams[k] for every k as one ProcessSamples call each, in one device call -> the finished
+// reports in frame order (an empty frame is not a call).  An unknown stream or an odd byte count fails the whole call before
+// any stream advances.
+func (b *SoundLevelBank) Process(streams []int, frames [][]byte) ([]SoundLevelReport, error) {
+	if len(streams) != len(frames) {
+		return nil, fmt.Errorf("hip: %d streams for %d frames", len(streams), len(frames))
+	}
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h == nil {
+		return nil, errors.New("hip: sound level bank is closed")
+	}
+	if len(frames) == 0 {
+		return nil, nil
+	}
+	ptrs, lens, err := b.stage(frames)
+	if err != nil {
+		return nil, err
+	}
+	st := make([]C.int, len(streams))
+	maxReports := 0
+	for k, s := range streams {
+		st[k] = C.int(s)
+		if lens[k] > 0 {
+			maxReports++ // at most one report per ProcessSamples call
+		}
+	}
+	reps := (*C.bnhip_sound_level)(C.malloc(C.size_t(maxReports+1) * C.size_t(unsafe.Sizeof(C.bnhip_sound_level{}))))
+	if reps == nil {
+		return nil, errors.New("hip: out of host memory (sound level reports)")
+	}
+	defer C.free(unsafe.Pointer(reps))
+	var n C.int
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_sl_process_pcm16(b.h, C.int(len(frames)), &st[0], ptrs, &lens[0], reps, C.int(maxReports), &n); rc != 0 {
+		return nil, fmt.Errorf("hip: sound level bank failed (%d): %s", int(rc), lastError())
+	}
+	out := make([]SoundLevelReport, int(n))
+	for i, r := range unsafe.Slice(reps, int(n)) {
+		rep := SoundLevelReport{Stream: int(r.stream), Frame: int(r.frame), Duration: int(r.duration_s),
+			OctaveBands: make(map[string]SoundLevelBandData, int(r.n_bands))}
+		for j := 0; j < int(r.n_bands); j++ {
+			rep.OctaveBands[SoundLevelBandKey(float64(r.center_hz[j]))] = SoundLevelBandData{CenterFreq: float64(r.center_hz[j]),
+				Min: float64(r.min_db[j]), Max: float64(r.max_db[j]), Mean: float64(r.mean_db[j]), SampleCount: int(r.sample_count[j])}
+		}
+		out[i] = rep
+	}
+	return out, nil
+}
+
+func (b *SoundLevelBank) Close() error {
+	b.mu.Lock()
+	defer b.mu.Unlock()
+	if b.h != nil {
+		C.bnbind_sl_destroy(b.h)
+		b.h = nil
+	}
+	b.release()
+	return nil
+}
+
+// bankStage is what every bank shares: the mutex that serialises calls on the bank, its name in errors, and the C memory a call
 // stages its frames in (cgo: C may not keep or receive Go pointers into Go memory).
 type bankStage struct {
 	mu      sync.Mutex
-	what    string         // "resampler bank" | "equalizer bank"
+	what    string         // "resampler bank" | "equalizer bank" | "sound level bank"
 	buf     unsafe.Pointer // C memory: this call's frames back to back
 	bufCap  int
 	ptrs    unsafe.Pointer // C memory: one const int16_t* per frame

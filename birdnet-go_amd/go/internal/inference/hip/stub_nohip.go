@@ -118,3 +118,12 @@ func (*EqualizerBank) Reset(int) error                                    { retu
 func (*EqualizerBank) Process([]int, [][]byte) ([][]byte, error)          { return nil, ErrHIPUnavailable }
 func (*EqualizerBank) Close() error                                       { return nil }
 func (*WindowAssembler) WriteEqualized(*EqualizerBank, []int, []int, [][]byte) error { return ErrHIPUnavailable }
+
+type SoundLevelBank struct{}
+
+func NewSoundLevelBank(int, int, int, []SoundLevelBand) (*SoundLevelBank, error) { return nil, ErrHIPUnavailable }
+func (*SoundLevelBank) AddStream(int) (int, error)                              { return -1, ErrHIPUnavailable }
+func (*SoundLevelBank) RemoveStream(int) error                                  { return nil }
+func (*SoundLevelBank) Reset(int) error                                         { return ErrHIPUnavailable }
+func (*SoundLevelBank) Process([]int, [][]byte) ([]SoundLevelReport, error)     { return nil, ErrHIPUnavailable }
+func (*SoundLevelBank) Close() error                                            { return nil }

@@ -41,7 +41,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_resampler_bank_flush_pcm16", "bnhip_windows_write_resampled", "bnhip_resampler_bank_destroy",
            "bnhip_eq_bank_create", "bnhip_eq_bank_add_stream", "bnhip_eq_bank_remove_stream", "bnhip_eq_bank_set_chain",
            "bnhip_eq_bank_reset", "bnhip_eq_bank_process_pcm16", "bnhip_windows_write_equalized", "bnhip_eq_design",
-           "bnhip_eq_bank_destroy"]
+           "bnhip_eq_bank_destroy", "bnhip_soundlevel_bands", "bnhip_soundlevel_bank_create", "bnhip_soundlevel_bank_add_stream",
+           "bnhip_soundlevel_bank_remove_stream", "bnhip_soundlevel_bank_reset", "bnhip_soundlevel_bank_process_pcm16",
+           "bnhip_soundlevel_bank_destroy"]
 
 
 class HipError(RuntimeError):
@@ -614,22 +616,20 @@ def _split_frames(out, counts):
 
 
 class _StreamBank:
-    """What ResamplerBank and EqualizerBank share: the handle `_h` of bnhip_<_prefix>_*, its stream slots, `process` (one bytes
-    object per frame), `write_windows` (one ring write per frame, through _write) and the lifetime.  A subclass binds its own
-    entries with _bind and bounds process's default out_cap with _out_bound."""
+    """What every bank shares: the handle `_h` of bnhip_<_prefix>_*, its stream slots and the lifetime.  A subclass binds its own
+    entries with _bind (they override the shared ones' argtypes)."""
 
-    _prefix = _what = _write = None
+    _prefix = _what = None
 
     def _bind(self, **argtypes):
         """Loads the library and declares the shared entries plus the subclass's own (entry suffix -> argtypes)."""
         self._lib = L = load_library()
         vp, ci = C.c_void_p, C.c_int
-        argtypes.update(add_stream=[vp, C.POINTER(ci)], remove_stream=[vp, ci], process_pcm16=[vp, ci, vp, vp, vp, vp, C.c_size_t, vp],
-                        destroy=[vp])
-        for name, types in argtypes.items():
-            getattr(L, f"bnhip_{self._prefix}_{name}").argtypes = types
+        types = dict(add_stream=[vp, C.POINTER(ci)], remove_stream=[vp, ci], destroy=[vp])
+        types.update(argtypes)
+        for name, t in types.items():
+            getattr(L, f"bnhip_{self._prefix}_{name}").argtypes = t
         getattr(L, f"bnhip_{self._prefix}_destroy").restype = None
-        getattr(L, self._write).argtypes = [vp, vp, ci, vp, vp, vp, vp]
         self._h = C.c_void_p()
         return L
 
@@ -643,6 +643,35 @@ class _StreamBank:
 
     def remove_stream(self, stream):
         _check(self._lib, self._fn("remove_stream")(self._alive(), int(stream)))
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def _alive(self):
+        if not self._h:
+            raise HipError(E_INVALID, f"{self._what} is closed")
+        return self._h
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _PcmBank(_StreamBank):
+    """What ResamplerBank and EqualizerBank share beyond that: `process` (one bytes object per frame) and `write_windows` (one
+    ring write per frame, through _write).  A subclass bounds process's default out_cap with _out_bound."""
+
+    _write = None
+
+    def _bind(self, **argtypes):
+        vp, ci = C.c_void_p, C.c_int
+        L = super()._bind(**dict(dict(process_pcm16=[vp, ci, vp, vp, vp, vp, C.c_size_t, vp]), **argtypes))
+        getattr(L, self._write).argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        return L
 
     def process(self, items, out_cap=None):
         """[(stream, pcm16 bytes | int16 array), ...] -> [bytes, ...] per frame.  out_cap (samples) defaults to the most the frames
@@ -665,24 +694,8 @@ class _StreamBank:
         arrs, ptrs, lens = _pcm16_frames([f for _, _, f in items])
         win._check(getattr(self._lib, self._write)(win._alive(), self._alive(), len(items), streams, sources, ptrs, lens))
 
-    def close(self):
-        if self._h:
-            self._fn("destroy")(self._h)
-            self._h = C.c_void_p()
 
-    def _alive(self):
-        if not self._h:
-            raise HipError(E_INVALID, f"{self._what} is closed")
-        return self._h
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ResamplerBank(_StreamBank):
+class ResamplerBank(_PcmBank):
     """`bnhip_resampler_bank` (include/bnhip.h): one StreamResampler per stream for many streams of one (from, to) rate pair,
     every call one device call.  `process([(stream, pcm16), ...])` -> one bytes object per frame, each what that stream's own
     StreamResampler returns for the frame in sequence (a stream may appear several times; its frames go in list order);
@@ -770,7 +783,7 @@ def gain_linear(gain_db):
     return 10.0 ** (float(gain_db) / 20.0)
 
 
-class EqualizerBank(_StreamBank):
+class EqualizerBank(_PcmBank):
     """`bnhip_eq_bank` (include/bnhip.h): the analysis route's EQ chain + gain (AudioRouter.applyProcessing) for many streams,
     every call one device call.  `set_chain(stream, chain, gain_linear)` installs [(section6, passes), ...] (None or [] = no
     filters) with zero state; `process([(stream, pcm16), ...])` -> one bytes object per frame, as many samples as its input (a
@@ -798,6 +811,81 @@ class EqualizerBank(_StreamBank):
 
     def _out_bound(self, arrs):                     # the total input
         return sum(a.size for a in arrs)
+
+
+SOUNDLEVEL_MAX_BANDS = 32
+
+
+class _SoundLevel(C.Structure):
+    """bnhip_sound_level (include/bnhip.h): one SoundLevelData."""
+    _fields_ = [("stream", C.c_int), ("frame", C.c_int), ("duration_s", C.c_int), ("n_bands", C.c_int),
+                ("center_hz", C.c_double * 32), ("min_db", C.c_double * 32), ("max_db", C.c_double * 32),
+                ("mean_db", C.c_double * 32), ("sample_count", C.c_int * 32)]
+
+
+def sound_level_band_key(hz):
+    """formatBandKey (soundlevel/processor.go:440-445): "%.1f_Hz" below 1 kHz, else "%.1f_kHz" of hz / 1000."""
+    hz = float(hz)
+    return "%.1f_Hz" % hz if hz < 1000 else "%.1f_kHz" % (hz / 1000)
+
+
+def sound_level_bands(rate):
+    """NewProcessor's 1/3-octave bands at `rate` (bnhip_soundlevel_bands) -> [(centre Hz, b0, b1, b2, a1, a2), ...] (normalised
+    by a0).  rate <= 0 raises HipError(E_INVALID)."""
+    lib = load_library()
+    lib.bnhip_soundlevel_bands.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    out = np.zeros((SOUNDLEVEL_MAX_BANDS, 6), np.float64)
+    n = C.c_int(0)
+    _check(lib, lib.bnhip_soundlevel_bands(int(rate), out.ctypes.data, SOUNDLEVEL_MAX_BANDS, C.byref(n)))
+    return [tuple(float(v) for v in row) for row in out[:n.value]]
+
+
+class SoundLevelBank(_StreamBank):
+    """`bnhip_soundlevel_bank` (include/bnhip.h): one soundlevel.Processor per stream for many streams of one sample rate, every
+    call one device call.  `add_stream(interval_s)` starts a fresh Processor; `process([(stream, pcm16), ...])` runs each frame
+    as one ProcessSamples call (a stream may appear several times; its frames go in list order; an empty frame is not a call)
+    and returns the finished reports in frame order, each {"stream", "frame", "duration_seconds", "octave_bands": {key:
+    {"center_frequency_hz", "min_db", "max_db", "mean_db", "sample_count"}}}.  bands: None = NewProcessor's table for the rate,
+    or [(centre, b0, b1, b2, a1, a2), ...] (as a Go host passes its own).  Errors leave every stream untouched."""
+
+    _prefix, _what = "soundlevel_bank", "sound level bank"
+
+    def __init__(self, sample_rate, max_streams=256, device=0, bands=None):
+        vp, ci = C.c_void_p, C.c_int
+        L = self._bind(create=[ci, ci, ci, vp, ci, C.POINTER(vp)], add_stream=[vp, ci, C.POINTER(ci)], reset=[vp, ci],
+                       process_pcm16=[vp, ci, vp, vp, vp, vp, ci, C.POINTER(ci)])
+        self.sample_rate, self.max_streams = int(sample_rate), int(max_streams)
+        tbl = None if bands is None else np.ascontiguousarray(np.asarray(bands, np.float64).reshape(-1, 6))
+        _check(L, L.bnhip_soundlevel_bank_create(device, self.sample_rate, self.max_streams, None if tbl is None else tbl.ctypes.data,
+                                                 0 if tbl is None else len(tbl), C.byref(self._h)))
+
+    def add_stream(self, interval_s=10):
+        s = C.c_int(-1)
+        _check(self._lib, self._lib.bnhip_soundlevel_bank_add_stream(self._alive(), int(interval_s), C.byref(s)))
+        return s.value
+
+    def reset(self, stream):
+        _check(self._lib, self._lib.bnhip_soundlevel_bank_reset(self._alive(), int(stream)))
+
+    def process(self, items, max_reports=None):
+        """max_reports defaults to the non-empty frames (at most one report each); a smaller one can be the library's E_INVALID."""
+        streams = _c_ints(s for s, _ in items)
+        arrs, ptrs, lens = _pcm16_frames([f for _, f in items])
+        if max_reports is None:
+            max_reports = sum(1 for a in arrs if a.size)
+        reps = (_SoundLevel * max(max_reports, 1))()
+        n = C.c_int(0)
+        _check(self._lib, self._lib.bnhip_soundlevel_bank_process_pcm16(self._alive(), len(items), streams, ptrs, lens, reps,
+                                                                        int(max_reports), C.byref(n)))
+        out = []
+        for r in reps[:n.value]:
+            bands = {}
+            for j in range(r.n_bands):
+                bands[sound_level_band_key(r.center_hz[j])] = {
+                    "center_frequency_hz": r.center_hz[j], "min_db": r.min_db[j], "max_db": r.max_db[j], "mean_db": r.mean_db[j],
+                    "sample_count": r.sample_count[j]}
+            out.append({"stream": r.stream, "frame": r.frame, "duration_seconds": r.duration_s, "octave_bands": bands})
+        return out
 
 
 class Perch:

@@ -606,7 +606,14 @@ class WindowBatcher:
     then writes them to the source's rings (straight from the library when each frame has one ring at the model's rate and all
     of them are in one assembler) and into the same tick's resampler queue, before it collects - a processed source's audio
     therefore reaches its rings up to one tick late, as resampled audio does.  A failed call costs its own frames only
-    (on_error), as the reference drops a frame whose processing failed."""
+    (on_error), as the reference drops a frame whose processing failed.
+
+    `set_sound_level(source, source_rate, interval_s)` gives a source the 1/3-octave sound level monitor (soundlevel.Processor
+    behind a SoundLevelConsumer route, internal/analysis/audio_pipeline_service.go:685-740): every frame of the source, at the
+    source rate and after set_processing's EQ and gain, is one ProcessSamples call, and `take_sound_levels()` returns the
+    finished SoundLevelData-shaped reports.  One host.SoundLevelBank per source rate.  Python rings: one bank call per write.
+    Native rings: the frames are queued and the next `tick()` runs one bank call per rate, after the EQ drain and before the
+    resampler drain.  A failed call costs its own frames only (on_error), as the consumer logs the error and goes on."""
 
     BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
 
@@ -629,6 +636,10 @@ class WindowBatcher:
         self.eq_bank = None                  # host.EqualizerBank of the processed sources (created on first use)
         self.eq_streams = {}                 # source -> its stream of eq_bank
         self.eq_pending = []                 # native: [(source, stream, pcm bytes)] of processed sources until the next tick
+        self.sl_banks = {}                   # source rate -> host.SoundLevelBank (created on first use)
+        self.sl_streams = {}                 # source -> (source rate, stream of that rate's bank, name)
+        self.sl_pending = {}                 # native: source rate -> [(source, stream, pcm bytes)] until the next tick
+        self.sl_reports = []                 # finished reports until take_sound_levels()
 
     def allocate(self, source, model_id, capacity=None, source_rate=None):
         """The buffer of (source, model_id).  source_rate: the rate the source captures at; None or the model's effective rate
@@ -745,6 +756,70 @@ class WindowBatcher:
             if st is not None:
                 self.eq_bank.remove_stream(st)
 
+    def set_sound_level(self, source, source_rate, interval_s=10, name=None):
+        """The source's sound level monitor: a fresh Processor (NewProcessor(sid, sid, rate, interval)) reporting every interval_s
+        seconds (below 1: 1); name defaults to the source.  Calling it again starts a fresh stream, as the reference builds a new
+        Processor; frames queued before keep the old one."""
+        if source_rate is None or source_rate <= 0:
+            raise StreamError(f"invalid source sample rate: {source_rate}")
+        rate = int(source_rate)
+        self._drain_sound_levels_queued()
+        with self.mu:
+            old = self.sl_streams.pop(source, None)
+            if old is not None:
+                self.sl_banks[old[0]].remove_stream(old[1])
+            bank = self.sl_banks.get(rate)
+            if bank is None:
+                bank = self.sl_banks[rate] = _host.SoundLevelBank(rate, self.BANK_STREAMS)
+            self.sl_streams[source] = (rate, bank.add_stream(interval_s), source if name is None else name)
+
+    def clear_sound_level(self, source):
+        """The source's monitor stops; frames queued before still count."""
+        self._drain_sound_levels_queued()
+        with self.mu:
+            old = self.sl_streams.pop(source, None)
+            if old is not None:
+                self.sl_banks[old[0]].remove_stream(old[1])
+
+    def take_sound_levels(self):
+        """-> the finished reports since the last call, oldest first: {"timestamp" (the batcher's clock when the report was
+        made), "source", "name", "duration_seconds", "octave_bands": {key: {"center_frequency_hz", "min_db", "max_db", "mean_db",
+        "sample_count"}}}."""
+        with self.mu:
+            out, self.sl_reports = self.sl_reports, []
+        return out
+
+    def _drain_sound_levels_queued(self):
+        if self.eq_pending:                                       # a monitored source's processed frames are queued behind them
+            self._drain_equalized()
+        if self.sl_pending:
+            self._drain_sound_levels()
+
+    def _sound_level_reports(self, items, reports):
+        """(under self.mu) bank reports of the call over items [(source, stream, pcm bytes), ...] -> self.sl_reports."""
+        for r in reports:
+            src = items[r["frame"]][0]
+            name = self.sl_streams.get(src, (None, None, src))[2]
+            self.sl_reports.append({"timestamp": self.clock(), "source": src, "name": name, "duration_seconds": r["duration_seconds"],
+                                    "octave_bands": r["octave_bands"]})
+
+    def _drain_sound_levels(self):
+        """Native: every monitored source's queued frames through one device call per source rate (host.SoundLevelBank)."""
+        failed = []
+        with self.mu:
+            pending, self.sl_pending = self.sl_pending, {}
+            for rate, items in pending.items():
+                try:
+                    reports = self.sl_banks[rate].process([(st, raw) for _, st, raw in items])
+                except Exception as e:
+                    self.errors += len(items)
+                    failed.append((sorted({src for src, *_ in items}), e))
+                    continue
+                self._sound_level_reports(items, reports)
+        for sources, e in failed:
+            if self.on_error:
+                self.on_error(None, sources, e)
+
     def write(self, source, data):
         """Capture side: the same bytes go to every model's buffer of that source; a buffer of another rate gets them resampled
         (once per rate pair: buffer_consumer.go:184-210).  A processed source's bytes are processed first (set_processing)."""
@@ -768,7 +843,18 @@ class WindowBatcher:
         self._fan_out(source, data)
 
     def _fan_out(self, source, data):
+        sl = None
         with self.mu:
+            mon = self.sl_streams.get(source)
+            raw_sl = _as_bytes(data).tobytes() if mon is not None else b""
+            raw_sl = raw_sl[:len(raw_sl) & ~1]                    # whole samples (sound_level_consumer.go:109-111)
+            if raw_sl:                                            # an empty frame is not a call (:117)
+                sl = (source, mon[1], raw_sl)
+                if self.native:
+                    self.sl_pending.setdefault(mon[0], []).append(sl)
+                    sl = None
+                else:
+                    bank = self.sl_banks[mon[0]]
             groups = {}
             for (s, m), ab in self.buffers.items():
                 if s == source:
@@ -788,6 +874,17 @@ class WindowBatcher:
             out = r.resample_into(raw)
             for ab in targets:
                 ab.write(out)
+        if sl is not None:                                        # python: one monitor call per write
+            with self.mu:
+                try:
+                    self._sound_level_reports([sl], bank.process([sl[1:]]))
+                except Exception as e:
+                    self.errors += 1
+                    err = e
+                else:
+                    err = None
+            if err is not None and self.on_error:
+                self.on_error(None, [source], err)
 
     def _bank_call(self, bank, items, failed):
         """(under self.mu) One call of `bank` (host.EqualizerBank / host.ResamplerBank) for the queued [(source, stream, pcm bytes,
@@ -818,7 +915,8 @@ class WindowBatcher:
             bufs, resampled = {}, {s for s, _ in self.rates}
             for (s, _), ab in self.buffers.items():
                 bufs.setdefault(s, []).append(ab)
-            items = [(src, st, raw, [] if src in resampled else bufs.get(src, [])) for src, st, raw in pending]
+            # a monitored source's processed frames come back (its monitor is queued from them in _fan_out)
+            items = [(src, st, raw, [] if src in resampled or src in self.sl_streams else bufs.get(src, [])) for src, st, raw in pending]
             outs = self._bank_call(self.eq_bank, items, failed)
         for sources, e in failed:
             if self.on_error:
@@ -912,11 +1010,18 @@ class WindowBatcher:
             self.eq_bank = None
             self.eq_streams.clear()
             self.eq_pending.clear()
+            for bank in self.sl_banks.values():
+                bank.close()
+            self.sl_banks.clear()
+            self.sl_streams.clear()
+            self.sl_pending.clear()
 
     def tick(self):
         if self.native:
             if self.eq_pending:
                 self._drain_equalized()
+            if self.sl_pending:
+                self._drain_sound_levels()
             if self.pending:
                 self._drain_resampled()
             return self._tick_native()

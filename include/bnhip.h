@@ -314,6 +314,55 @@ int bnhip_eq_design(int type, double sample_rate, double frequency, double q, do
                     double* section6);
 void bnhip_eq_bank_destroy(bnhip_eq_bank* b);
 
+/* Sound level bank: the 1/3-octave sound level monitor, soundlevel.Processor (internal/audiocore/soundlevel/processor.go) behind
+ * one SoundLevelConsumer route per source (internal/analysis/sound_level_consumer.go:103-150, registered by
+ * internal/analysis/audio_pipeline_service.go:685-740), for many sources of ONE sample rate, one device call per call.  Per
+ * source, in float64: every PCM16 sample x / 32768 runs through the ISO 266 band-pass biquads (processAudioSample :231-250,
+ * state reset when the output is NaN, +-Inf or above 100 in magnitude); every consecutive 1-second block's sum of squares gives
+ * rms = sqrt(sum / fs), clamped to [1e-10, 10], and 20 * Log10(rms) dB; each call that ends with at least one unmeasured block
+ * takes exactly ONE measurement (ProcessSamples :258-327: a 2.5 s frame gives one, the next frames the rest, one each); every
+ * `interval` measurements give one report of per-band min / max / mean dB (generateSoundLevelData :349-412).
+ *   bands:         NewProcessor's bands at sample_rate (:120-158, newOctaveBandFilter :161-225): the centres whose upper edge
+ *                  c * 2^(1/6) lies below 0.95 x Nyquist (30 at 48 kHz, 29 at 44.1 kHz, 25 at 16 kHz), each
+ *                  {c, b0, b1, b2, a1, a2} / a0 of the RBJ constant-0-dB band-pass with Q = max(c / (high - low), 0.5).  *n_bands
+ *                  gets the count; bands6 NULL: the count only; cap (bands) below it: BNHIP_E_INVALID.  sample_rate <= 0 and
+ *                  an out-of-range or unstable band are BNHIP_E_INVALID, as NewProcessor's errors.  Computed with the C
+ *                  library's sin / cos / pow, so a coefficient may differ from Go's in the last ulp: a Go host passes its own.
+ *   create:        one bank per sample rate; bands6 NULL: the table of `bands`, else n_bands (1..32) caller bands
+ *                  {c, b0, b1, b2, a1, a2}, each finite with c > 0 and stable (|a2| < 1 and |a1| < 1 + a2, :212-214), else
+ *                  BNHIP_E_INVALID.  max_streams fixes the slot table; one HIP stream per bank.  destroy: NULL-safe.
+ *   add_stream:    a fresh Processor (zero filter state: the 100-sample silence warm-up leaves it at zero) reporting every
+ *                  interval_s seconds (below 1: 1, :93-95); slots of removed streams are reused with fresh state.
+ *   reset:         Processor.Reset (:331-346): zero filter state, the partial second and any unmeasured blocks dropped, the
+ *                  interval cleared.
+ *   process:       frames f = 0..n_frames-1 (frames[f], n_in[f] samples) of streams[f]; a stream may appear several times, its
+ *                  frames are consumed in call order, each one ProcessSamples call; an empty frame is not a call (the
+ *                  consumer returns first, sound_level_consumer.go:117).  The reports the frames complete go to reports[] in
+ *                  frame order, their number to *n_reports; `frame` is the index f after which ProcessSamples returned it.
+ *                  More reports than max_reports, an unknown or removed stream, a negative length: BNHIP_E_INVALID and nothing
+ *                  changes.  A device error leaves every stream, its unmeasured blocks and its interval as they were.
+ * Divergences: dB uses the C library's log, which may differ from Go's math.Log in the last ulp; max_streams is fixed at
+ * create.  The filter outputs, block sums, measurement schedule and report count are the reference's exactly.
+ * Calls on one bank are serialised internally. */
+#define BNHIP_SOUNDLEVEL_MAX_BANDS 32
+typedef struct bnhip_soundlevel_bank bnhip_soundlevel_bank;
+typedef struct bnhip_sound_level {         /* one SoundLevelData (processor.go / soundlevel/types.go) */
+    int stream, frame;                     /* frame: index in the call after which ProcessSamples returned it */
+    int duration_s, n_bands;               /* Duration (the interval), bands in use */
+    double center_hz[BNHIP_SOUNDLEVEL_MAX_BANDS], min_db[BNHIP_SOUNDLEVEL_MAX_BANDS], max_db[BNHIP_SOUNDLEVEL_MAX_BANDS],
+        mean_db[BNHIP_SOUNDLEVEL_MAX_BANDS];
+    int sample_count[BNHIP_SOUNDLEVEL_MAX_BANDS];
+} bnhip_sound_level;
+int bnhip_soundlevel_bands(int sample_rate, double* bands6, int cap, int* n_bands);
+int bnhip_soundlevel_bank_create(int device, int sample_rate, int max_streams, const double* bands6, int n_bands,
+                                 bnhip_soundlevel_bank** out);
+int bnhip_soundlevel_bank_add_stream(bnhip_soundlevel_bank* b, int interval_s, int* out_stream);
+int bnhip_soundlevel_bank_remove_stream(bnhip_soundlevel_bank* b, int stream);
+int bnhip_soundlevel_bank_reset(bnhip_soundlevel_bank* b, int stream);
+int bnhip_soundlevel_bank_process_pcm16(bnhip_soundlevel_bank* b, int n_frames, const int* streams, const int16_t* const* frames,
+                                        const int* n_in, bnhip_sound_level* reports, int max_reports, int* n_reports);
+void bnhip_soundlevel_bank_destroy(bnhip_soundlevel_bank* b);
+
 /* Stream plumbing for hosts that own a HIP stream (bench harness: torch's current stream). */
 int bnhip_set_stream(bnhip_model* m, void* hip_stream);
 int bnhip_synchronize(bnhip_model* m);
