@@ -28,6 +28,7 @@
 
 #include "engine.h"
 #include "eq_bank.h"
+#include "heatmap.h"
 #include "hostpipe.h"
 #include "numa.h"
 #include "model_onnx.h"
@@ -895,6 +896,66 @@ int bnhip_predict_pcm_topk(bnhip_model* m, const void* pcm, int bits_per_sample,
     if (bits_per_sample != 16 && bits_per_sample != 24 && bits_per_sample != 32)
         return set_err(BNHIP_E_INVALID, "unsupported bit depth: " + std::to_string(bits_per_sample) + " (supported: 16, 24, 32)");
     return predict_topk_host(m, pcm, bits_per_sample, n_clips, activation, sensitivity, k, out_conf, out_idx);
+    BN_GUARD_END((void)0)
+}
+
+// Heat-map grid of one species (HeatmapInferenceService.ComputeGridWithBinding, internal/classifier/heatmap_service.go:143-420).
+// Row g = wi * n_cells + c is [coords[2c], coords[2c+1], 1 + wi * stride]; the rows run in chunks of max_batch, every chunk
+// enqueued on the engine's stream behind the previous one: the centres go up once, the [weeks][n_cells] result comes down once.
+// Pruned tail (Engine::heatmap_pruned_step): the plan runs without its final dense step and k_heatmap_column computes the one
+// column; any other plan runs whole and k_heatmap_gather takes the column from the logits.
+int bnhip_range_heatmap(bnhip_model* m, const float* coords, int n_cells, int species, int stride, int total_weeks, float* result) {
+    if (!m || !coords || !result) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (n_cells <= 0 || stride <= 0 || total_weeks <= 0) return set_err(BNHIP_E_INVALID, "n_cells, stride and total_weeks must be positive");
+    BN_GUARD_BEGIN
+    Engine& e = m->eng();
+    if (species < 0 || species >= e.n_classes)
+        return set_err(BNHIP_E_INVALID, "species index " + std::to_string(species) + " out of range [0, " + std::to_string(e.n_classes) + ")");
+    if (e.n_samples != 3)
+        return set_err(BNHIP_E_INVALID, "range filter model must take 3 inputs (lat, lon, week), takes " + std::to_string(e.n_samples));
+    if (m->engs.size() > 1) return set_err(BNHIP_E_INVALID, "bnhip_range_heatmap: a grid runs on one device; use a single-device handle");
+    const int weeks = (total_weeks - 1) / stride + 1;                 // ceil(total_weeks / stride)
+    if ((long long)weeks * n_cells > INT_MAX) return set_err(BNHIP_E_INVALID, "weeks * n_cells overflows");
+    if (e.device < 0) return set_err(BNHIP_E_INVALID, "plan-only model cannot run");
+    if (hipSetDevice(e.device) != hipSuccess) return set_err(BNHIP_E_RUNTIME, "hipSetDevice failed");
+    const int total = weeks * n_cells;
+    // whatever an earlier asynchronous call still has queued on the engine's streams finishes first (as host_run does)
+    e.sync_contexts();
+    if (e.stream) hipStreamSynchronize(e.stream);
+    const size_t coord_floats = ((size_t)n_cells * 2 + 63) / 64 * 64;
+    float* d_coords = nullptr;
+    if (hipMalloc((void**)&d_coords, (coord_floats + (size_t)total) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(BNHIP_E_NOMEM, "device allocation failed (heat-map grid)");
+    }
+    float* d_res = d_coords + coord_floats;
+    std::string err;
+    hipError_t he = hipMemcpyAsync(d_coords, coords, (size_t)n_cells * 2 * 4, hipMemcpyHostToDevice, e.stream);
+    bool ok = he == hipSuccess;
+    if (!ok) err = std::string("H2D copy: ") + hipGetErrorString(he);
+    const int pruned = e.heatmap_pruned_step();
+    for (int g0 = 0; ok && g0 < total; g0 += e.max_batch) {
+        const int n = std::min(e.max_batch, total - g0);
+        launch_heatmap_rows(d_coords, n_cells, stride, g0, n, e.d_stage_in, e.stream);
+        if (pruned >= 0) {
+            const Step& s = e.steps[pruned];
+            ok = e.run_head(pruned, e.d_stage_in, n, &err);
+            const float* a = s.in0 == e.v_input ? e.d_stage_in : e.value_ptr(s.in0);
+            if (ok) launch_heatmap_column(a, s.C, s.w0 + (size_t)species * s.C, s.w1 ? s.w1 + species : nullptr, s.act, n, d_res + g0, e.stream);
+        } else {
+            ok = e.run(e.d_stage_in, n, e.d_stage_logits, nullptr, &err);
+            if (ok) launch_heatmap_gather(e.d_stage_logits, e.n_classes, species, n, d_res + g0, e.stream);
+        }
+    }
+    if (ok && (he = hipGetLastError()) != hipSuccess) { ok = false; err = std::string("kernel launch: ") + hipGetErrorString(he); }
+    if (ok && (he = hipMemcpyAsync(result, d_res, (size_t)total * 4, hipMemcpyDeviceToHost, e.stream)) != hipSuccess) {
+        ok = false; err = std::string("D2H copy: ") + hipGetErrorString(he);
+    }
+    he = hipStreamSynchronize(e.stream);
+    if (ok && he != hipSuccess) { ok = false; err = std::string("heat-map grid: ") + hipGetErrorString(he); }
+    hipFree(d_coords);
+    if (!ok) { e.mm_dirty = true; return set_err(BNHIP_E_RUNTIME, err); }
+    return weeks;
     BN_GUARD_END((void)0)
 }
 

@@ -716,6 +716,23 @@ bool Engine::run_part(int c, hipStream_t st, int s0, int s1, const float* d_in, 
     cur_stream = nullptr;
     return ok;
 }
+int Engine::heatmap_pruned_step() const {
+    if (steps.empty() || precision != 0) return -1;
+    const Step& s = steps.back();
+    if (s.kind != S_PW || s.out != v_logits || s.in1 >= 0 || s.in2 >= 0 || s.H * s.W != 1 || s.Co != n_classes) return -1;
+    if (s.in0 < 0 || vals[s.in0].half || vals[s.in0].elems != (size_t)s.C) return -1;
+    return (int)steps.size() - 1;
+}
+bool Engine::run_head(int s1, const float* d_in, int n, std::string* err) {
+    if (n <= 0 || n > max_batch) { *err = "batch size out of range"; return false; }
+    if (s1 < 0 || s1 > (int)steps.size()) { *err = "not a cut of this plan"; return false; }
+    cur_stream = stream;                         // (a call with its own main stream runs on one lane)
+    part_s1 = s1;
+    bool ok = run_eager(d_in, n, nullptr, nullptr, err);
+    part_s1 = -1;
+    cur_stream = nullptr;
+    return ok;
+}
 bool Engine::ensure_hand(std::string* err) {
     if (d_hand || v_hand < 0) return v_hand >= 0;
     if (hipMalloc((void**)&d_hand, std::max<size_t>((size_t)max_batch * hand_clip_bytes(), 256)) != hipSuccess) {
@@ -1073,7 +1090,7 @@ std::string Engine::describe() const {
     std::ostringstream os;
     os << "{\"tune_source\":\"";
     jesc(os, tune_source);
-    os << "\",\"tune_key\":\"" << (device >= 0 ? tune_key() : std::string()) << "\",\"split_step\":" << split_step << ",\"n_samples\":" << n_samples << ",\"n_classes\":" << n_classes << ",\"emb_dim\":" << emb_dim
+    os << "\",\"tune_key\":\"" << (device >= 0 ? tune_key() : std::string()) << "\",\"split_step\":" << split_step << ",\"heatmap_tail\":\"" << (heatmap_pruned_step() >= 0 ? "pruned" : "gather") << "\",\"n_samples\":" << n_samples << ",\"n_classes\":" << n_classes << ",\"emb_dim\":" << emb_dim
        << ",\"max_batch\":" << max_batch << ",\"logits_output\":" << logits_output << ",\"embedding_output\":" << embedding_output << ",\"precision\":\"" << (precision ? "bf16" : "f32") << "\",\"lanes\":" << n_lanes << ",\"lane_min_batch\":" << dual_lane_min << ",\"act_arena_bytes\":" << act_bytes << ",\"weight_bytes\":" << w_bytes
        << ",\"specs\":[";
     for (size_t i = 0; i < specs.size(); i++) {

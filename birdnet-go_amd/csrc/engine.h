@@ -150,6 +150,12 @@ class Engine {
     bool ensure_hand(std::string* err);
     // steps [s0, s1) of the plan for n clips in context c's arena on stream st; `hand` = the hand-off value's rows for these clips
     bool run_part(int c, hipStream_t st, int s0, int s1, const float* d_in, int n, float* hand, float* d_logits, float* d_emb, std::string* err);
+    // Heat-map grids (bnhip_range_heatmap).  The pruned tail: when the plan's last step is an fp32 dense GEMM that writes the logits
+    // (its folded activation included, nothing after it), the call runs the plan without it and computes one column of it
+    // (k_heatmap_column).  Returns that step's index, or -1: the full plan runs and the column is gathered from the logits.
+    int heatmap_pruned_step() const;
+    // steps [0, s1) for n rows in the engine's own arena on the main stream, on one lane (the unsplit layout value_ptr addresses)
+    bool run_head(int s1, const float* d_in, int n, std::string* err);
     struct HostPipe* hostpipe = nullptr;
     static constexpr int kMaxLanes = 4;
     int n_lanes = 2;                    // batches of >= dual_lane_min clips are split over this many streams (see run_eager)

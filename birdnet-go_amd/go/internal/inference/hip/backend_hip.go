@@ -88,6 +88,7 @@ typedef int  (*fn_sl_remove_stream)(bnhip_soundlevel_bank*, int);
 typedef int  (*fn_sl_reset)(bnhip_soundlevel_bank*, int);
 typedef int  (*fn_sl_process_pcm16)(bnhip_soundlevel_bank*, int, const int*, const int16_t* const*, const int*, bnhip_sound_level*, int, int*);
 typedef void (*fn_sl_destroy)(bnhip_soundlevel_bank*);
+typedef int  (*fn_range_heatmap)(bnhip_model*, const float*, int, int, int, int, float*);
 
 typedef struct {
     void* handle;
@@ -107,6 +108,7 @@ typedef struct {
     fn_eq_reset eq_reset; fn_eq_process_pcm16 eq_process_pcm16; fn_win_write_equalized win_write_equalized; fn_eq_destroy eq_destroy;
     fn_sl_bands sl_bands; fn_sl_create sl_create; fn_sl_add_stream sl_add_stream; fn_sl_remove_stream sl_remove_stream;
     fn_sl_reset sl_reset; fn_sl_process_pcm16 sl_process_pcm16; fn_sl_destroy sl_destroy;
+    fn_range_heatmap range_heatmap;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -153,6 +155,7 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(sl_add_stream, "bnhip_soundlevel_bank_add_stream"); BN_RESOLVE(sl_remove_stream, "bnhip_soundlevel_bank_remove_stream");
     BN_RESOLVE(sl_reset, "bnhip_soundlevel_bank_reset"); BN_RESOLVE(sl_process_pcm16, "bnhip_soundlevel_bank_process_pcm16");
     BN_RESOLVE(sl_destroy, "bnhip_soundlevel_bank_destroy");
+    BN_RESOLVE(range_heatmap, "bnhip_range_heatmap");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -248,6 +251,10 @@ static inline int bnbind_sl_process_pcm16(bnhip_soundlevel_bank* b, int n, const
     return BN.sl_process_pcm16(b, n, st, f, n_in, reps, max_reps, n_reps);
 }
 static inline void bnbind_sl_destroy(bnhip_soundlevel_bank* b) { if (BN.sl_destroy) BN.sl_destroy(b); }
+static inline int bnbind_range_heatmap(bnhip_model* m, const float* coords, int n_cells, int species, int stride, int total_weeks,
+                                       float* result) {
+    return BN.range_heatmap(m, coords, n_cells, species, stride, total_weeks, result);
+}
 // frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
 // the pointer table points at byte offset off[k] of the staging block
 static inline void bnbind_rb_point(const int16_t** ptrs, const char* stage, const int* off, int n) {
@@ -919,6 +926,40 @@ func (r *RangeFilter) PredictBatch(inputs []float32, batchSize int) ([]float32, 
 		return nil, fmt.Errorf("input size mismatch: expected %d values, got %d", batchSize*3, len(inputs))
 	}
 	return r.c.PredictBatch(inputs, batchSize)
+}
+
+// ComputeGrid is HeatmapInferenceService.ComputeGridWithBinding (internal/classifier/heatmap_service.go:143-420) on the device:
+// coords holds totalCells [lat, lon] pairs; result[wi*totalCells+c] receives output speciesIdx for [lat_c, lon_c, 1+wi*stride],
+// wi < ceil(totalWeeks/stride).  One native call: the rows run in chunks of the handle's max batch on the GPU and only the one
+// species' column comes back.  The label -> index lookup stays with the caller (GeomodelSpeciesInfo).  A range filter
+// created over several devices refuses the call (a grid runs on one device).
+func (r *RangeFilter) ComputeGrid(coords []float32, totalCells, speciesIdx, stride, totalWeeks int, result []float32) error {
+	if r.c == nil {
+		return errors.New("hip: range filter is closed")
+	}
+	if totalCells <= 0 || len(coords) != totalCells*2 {
+		return fmt.Errorf("hip: coords length %d does not match totalCells %d * 2", len(coords), totalCells)
+	}
+	if stride <= 0 || totalWeeks <= 0 {
+		return errors.New("hip: stride and totalWeeks must be > 0")
+	}
+	weeks := (totalWeeks + stride - 1) / stride
+	if weeks*totalCells > math.MaxInt32 {
+		return fmt.Errorf("hip: %d weeks x %d cells exceeds one call", weeks, totalCells)
+	}
+	if len(result) < weeks*totalCells {
+		return fmt.Errorf("hip: result length %d < expected %d", len(result), weeks*totalCells)
+	}
+	if speciesIdx < 0 || speciesIdx >= r.c.nClasses {
+		return fmt.Errorf("hip: species index %d out of range [0, %d)", speciesIdx, r.c.nClasses)
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.bnbind_range_heatmap(r.c.h, (*C.float)(unsafe.Pointer(&coords[0])), C.int(totalCells), C.int(speciesIdx),
+		C.int(stride), C.int(totalWeeks), (*C.float)(unsafe.Pointer(&result[0]))); rc < 0 {
+		return fmt.Errorf("hip: range_heatmap failed (%d): %s", int(rc), lastError())
+	}
+	return nil
 }
 
 func (r *RangeFilter) NumSpecies() int { return r.c.nClasses }

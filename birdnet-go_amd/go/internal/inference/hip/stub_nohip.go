@@ -74,6 +74,7 @@ func NewRangeFilter([]byte, ...int) (*RangeFilter, error)                { retur
 func (*RangeFilter) Predict(float32, float32, float32) ([]float32, error) { return nil, ErrHIPUnavailable }
 func (*RangeFilter) PredictBatch([]float32, int) ([]float32, error)      { return nil, ErrHIPUnavailable }
 func (*RangeFilter) NumSpecies() int                                     { return 0 }
+func (*RangeFilter) ComputeGrid([]float32, int, int, int, int, []float32) error { return ErrHIPUnavailable }
 func (*RangeFilter) Close()                                              {}
 
 type USFilterConfig struct{ FFTSize, HopSize, FrequencySplitHz int }

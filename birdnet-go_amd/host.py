@@ -14,6 +14,7 @@ binding is the cgo file under go/ (see INTEGRATION.md).
 """
 import ctypes as C
 import json
+import math
 import os
 
 import numpy as np
@@ -43,7 +44,7 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_eq_bank_reset", "bnhip_eq_bank_process_pcm16", "bnhip_windows_write_equalized", "bnhip_eq_design",
            "bnhip_eq_bank_destroy", "bnhip_soundlevel_bands", "bnhip_soundlevel_bank_create", "bnhip_soundlevel_bank_add_stream",
            "bnhip_soundlevel_bank_remove_stream", "bnhip_soundlevel_bank_reset", "bnhip_soundlevel_bank_process_pcm16",
-           "bnhip_soundlevel_bank_destroy"]
+           "bnhip_soundlevel_bank_destroy", "bnhip_range_heatmap"]
 
 
 class HipError(RuntimeError):
@@ -435,11 +436,45 @@ class RangeFilter:
             raise HipError(E_INVALID, f"input size mismatch: expected {batch_size * 3} values, got {x.size}")
         return self._clf.predict_batch(x, batch_size).reshape(-1)
 
+    def heatmap(self, coords, species, stride=1, total_weeks=48):
+        """One species' occurrence over a grid (HeatmapInferenceService.ComputeGridWithBinding, heatmap_service.go:143-420):
+        coords [n_cells, 2] lat / lon -> float32 [ceil(total_weeks / stride), n_cells], row wi for week 1 + wi * stride."""
+        self._clf._alive()
+        c = np.ascontiguousarray(coords, np.float32).reshape(-1)
+        if c.size % 2:
+            raise HipError(E_INVALID, f"coords must hold lat / lon pairs, got {c.size} values")
+        n_cells = c.size // 2
+        weeks = (total_weeks + stride - 1) // stride if stride > 0 and total_weeks > 0 else 0
+        out = np.empty((max(weeks, 0), n_cells), np.float32)
+        lib = self._clf._lib
+        lib.bnhip_range_heatmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        rc = lib.bnhip_range_heatmap(self._clf._h, c.ctypes.data, n_cells, int(species), int(stride), int(total_weeks),
+                                     out.ctypes.data)
+        if rc < 0:
+            _check(lib, rc)
+        assert rc == weeks, (rc, weeks)
+        return out
+
     def num_species(self):
         return self._clf.num_species()
 
     def close(self):
         self._clf.close()
+
+
+def heatmap_grid(south, north, west, east, resolution):
+    """heatmapGridDimensions and the cell centres of computeHeatmapGrid (internal/api/v2/analytics/heatmap.go:212-219,
+    315-330): rows = max(1, ceil((north - south) / resolution)), the same for cols; cell (row, col) is
+    float32(south + (row + 0.5) * resolution), float32(west + (col + 0.5) * resolution), computed in float64.
+    -> (rows, cols, coords float32 [rows * cols, 2] in row-major cell order)."""
+    rows = max(1, int(math.ceil((north - south) / resolution)))
+    cols = max(1, int(math.ceil((east - west) / resolution)))
+    lat = (south + (np.arange(rows, dtype=np.float64) + 0.5) * resolution).astype(np.float32)
+    lon = (west + (np.arange(cols, dtype=np.float64) + 0.5) * resolution).astype(np.float32)
+    coords = np.empty((rows * cols, 2), np.float32)
+    coords[:, 0] = np.repeat(lat, cols)
+    coords[:, 1] = np.tile(lon, rows)
+    return rows, cols, coords
 
 
 class Bat:

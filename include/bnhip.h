@@ -192,6 +192,23 @@ int bnhip_predict_topk(bnhip_model* m, const float* samples, int n_clips, int ac
 int bnhip_predict_pcm_topk(bnhip_model* m, const void* pcm, int bits_per_sample, int n_clips, int activation,
                            double sensitivity, int k, float* out_conf, int32_t* out_idx);
 
+/* Species occurrence heat-map grid on a range-filter meta-model ([lat, lon, week] -> per-species occurrence): the work of
+ * HeatmapInferenceService.ComputeGridWithBinding (internal/classifier/heatmap_service.go:143-420), which the API's heatmap
+ * handler runs over up to 50 000 cells x 48 weeks (internal/api/v2/analytics/heatmap.go:30-36; its fallback
+ * computeHeatmapGrid, :315-368, keeps one column of Orchestrator.BatchRangeFilterInference, orchestrator.go:1846-1883).
+ * coords: host [n_cells][2] lat / lon pairs (cell centres, used exactly as given); result: host [weeks][n_cells] with
+ * weeks = ceil(total_weeks / stride).  Row (wi, c) is [coords[2c], coords[2c+1], (float)(1 + wi * stride)] and
+ * result[wi * n_cells + c] is its output `species`.  The rows run in chunks of max_batch on the device with no host round trip
+ * per chunk.  When the plan ends in an fp32 dense layer that writes the outputs (its folded activation included), that layer
+ * computes only column `species` ("heatmap_tail":"pruned" in bnhip_model_describe; within 1e-6 of bnhip_predict's column on
+ * sigmoid outputs - a different summation order); otherwise every chunk runs the whole plan and the column is gathered
+ * ("gather": bit-identical to bnhip_predict for the same chunk of rows).
+ * BNHIP_E_INVALID (nothing written): NULL pointers, n_cells / stride / total_weeks <= 0, species outside [0, n_classes), a model
+ * whose input width is not 3, a multi-device or plan-only handle, weeks * n_cells beyond INT_MAX.  A failed call leaves the
+ * handle usable.  returns weeks computed (= ceil(total_weeks / stride)) or a negative BNHIP_E_* */
+int bnhip_range_heatmap(bnhip_model* m, const float* coords, int n_cells, int species,
+                        int stride, int total_weeks, float* result);
+
 /* Ultrasonic frame-CV filter (internal/audiocore/ultrasonic/filter.go:20-66), float64 throughout.
  * samples: host float64 [n_clips * n] (int16/32768 as float64, convert/pcm.go:108-113).
  * cv/ok: [n_clips]. device: HIP device ordinal. */
