@@ -234,7 +234,7 @@ void Engine::tune_or_load() {
             }
         }
         if (!done) {
-            autotune_pw(); autotune_expdw(); autotune_dw();
+            autotune_pw(); autotune_expdw(); autotune_dw(); autotune_tail();
             adopted("self-tuned");
             if (!experiment && !tune_dir.empty() && getenv("BNHIP_TUNE_RECORD")) {
                 const std::string path = tune_dir + "/" + key + ".tune";
@@ -312,7 +312,13 @@ bool Engine::apply_tuning_text(const std::string& text) {
         size_t idx = 0; Row& r = rows[i]; char name[512] = {0};
         ok = fscanf(f, "%zu %d %d %d %d %d %d %d %d %d %511[^\n]", &idx, &r.kind, &r.nt, &r.wm, &r.ntf, &r.wmf, &r.shape, &r.dwl, &r.bx, &r.S, name) == 11 &&
              idx == i && r.kind == (int)steps[i].kind && steps[i].name == name;
-        if (ok && steps[i].kind == S_PW) ok = r.nt >= 0 && r.nt <= 8 && r.ntf >= 0 && r.ntf <= 8 && r.wm >= 0 && r.wm <= 12 && r.wmf >= 0 && r.wmf <= 12 &&
+        if (ok && steps[i].kind == S_PW) {                    // the fused tails (wm 13 .. 15) only where the plan marked the step and the tile holds whole clips
+            auto tail_row = [&](int nt, int wm) {
+                return wm < 13 || (steps[i].tail && (nt == 4 || nt == 6 || nt == 8) && pw_tail_rows(wm) % (steps[i].H * steps[i].W) == 0);
+            };
+            ok = tail_row(r.nt, r.wm) && tail_row(r.ntf, r.wmf);
+        }
+        if (ok && steps[i].kind == S_PW) ok = r.nt >= 0 && r.nt <= 8 && r.ntf >= 0 && r.ntf <= 8 && r.wm >= 0 && r.wm <= 15 && r.wmf >= 0 && r.wmf <= 15 &&
                                               (((r.wm >= 5) == (steps[i].wm >= 5) && (r.wmf >= 5) == (steps[i].wm_full >= 5)) || !steps[i].wbx);       // (never switches the arithmetic family: bf16 storage was decided from it)
         if (ok && steps[i].kind == S_DW) {                    // the staged form only where its tuner would have timed it
             const Step& t = steps[i];
@@ -331,6 +337,9 @@ bool Engine::apply_tuning_text(const std::string& text) {
         }
     }
     fclose(f);
+    // (a fused depthwise tail writes the register-tiled kernel's sums: its depthwise step keeps that form for the calls that run unfused)
+    for (size_t i = 0; ok && i + 1 < n; i++)
+        if (steps[i].kind == S_PW && steps[i].tail == 2 && (rows[i].wm >= 13 || rows[i].wmf >= 13)) ok = rows[i + 1].dwl == 0;
     if (!ok) return false;
     // A row changes what the tuners decide and nothing else; what follows from a decision (the tile count the consumers of the
     // per-tile sums index by) is recomputed from the plan, not read: a stale or edited file can pick a slower kernel, not a wrong one.
@@ -635,6 +644,105 @@ void Engine::autotune_pw() {
     (void)hipGetLastError();
 }
 
+// ---- fused tails (Step::tail, k_pw_b16's clip-aligned row tiles with the consumer in the epilogue)
+PwParams Engine::tail_params(const Step& s, int n, bool lane_tuning) const {
+    PwParams p{nullptr, s.w0, s.w1, nullptr, nullptr, nullptr, n * s.H * s.W, s.Co, s.C, s.H * s.W, s.act, lane_tuning ? s.nt : s.nt_full,
+               lane_tuning ? s.wm : s.wm_full};
+    p.prec = precision; p.sw = pw_sw;
+    p.a_bf16 = vals[s.in0].half ? 1 : 0; p.out_bf16 = vals[s.out].half ? 1 : 0;
+    return p;
+}
+static PwTail tail_of(const Step& s, const Step& c) {
+    PwTail t;
+    t.kind = s.tail; t.H = s.H; t.W = s.W;
+    if (s.tail == 2) { t.k = c.kh; t.pt = c.pt; t.pl = c.pl; t.act = c.act; t.w = c.w0; t.bias = c.w1; }
+    return t;
+}
+// A call takes the fused form of step si when the tuning chose it, the launches it replaces lie in the same part of the plan (a
+// two-phase host call never cuts a pair in two forms) and the clip-aligned tiles put a block on every CU; smaller calls run the
+// pair - same bits.  BNHIP_PW_TAIL=2 takes it for every call.
+bool Engine::tail_taken(int si, int n, bool lane_tuning) const {
+    const Step& s = steps[si];
+    if (s.kind != S_PW || !s.tail || !s.wbx) return false;
+    const int wm = lane_tuning ? s.wm : s.wm_full, nt = lane_tuning ? s.nt : s.nt_full;
+    if (wm < 13) return false;
+    const int last = si + (s.tail == 1 ? 2 : 1), s_end = part_s1 < 0 ? (int)steps.size() : part_s1;
+    if (si < part_s0 || last >= s_end) return false;
+    if (s.tail == 2 && steps[si + 1].dwl) return false;
+    const PwParams p = tail_params(s, n, lane_tuning);
+    if (!pw_tail_ok(p, tail_of(s, steps[si + 1]), nt, wm)) return false;
+    return (pw_sw & PW_SW_TAIL_FORCE) || pw_tail_fills(p, nt, wm);
+}
+// Per marked layer and per tuning (a lane's batch, max_batch): every fused candidate - row tiles of 48 / 96 / 192 rows, column
+// tiles of 64 / 96 / 128 - against the SUM of the GEMM's tuned tile and the depthwise (or the two mean) launches it would replace.
+void Engine::autotune_tail() {
+    hipEvent_t a, b;
+    hipEventCreate(&a); hipEventCreate(&b);
+    const int n_lane = (max_batch + n_lanes - 1) / n_lanes;
+    const bool forced = (pw_sw & PW_SW_TAIL_FORCE) != 0;
+    for (int pass = 0; pass < 2; pass++) {
+        const int n = pass == 0 ? n_lane : max_batch;
+        const bool same = pass == 1 && n == n_lane;
+        for (size_t si = 0; si < steps.size(); si++) {
+            Step& s = steps[si];
+            if (s.kind != S_PW || !s.tail || !s.wbx) continue;
+            if (same) { s.nt_full = s.nt; s.wm_full = s.wm; continue; }
+            Step& c = steps[si + 1];
+            PwParams p = tail_params(s, n, pass == 0);
+            if (p.wm >= 13) { p.wm = 6; p.nt = 0; }                     // (forced at plan time, no tuned tile: the default)
+            p.A = vptr(s.in0, d_stage_in, d_stage_logits, nullptr);
+            p.out = vptr(s.out, d_stage_in, d_stage_logits, nullptr);
+            PwTail t = tail_of(s, c);
+            float* mean_out = nullptr;
+            DwParams dp{p.out, c.w0, c.w1, nullptr, n, c.H, c.W, c.C, c.Ho, c.Wo, c.kh, c.kw, c.sh, c.sw, c.pt, c.pl, c.act};
+            if (s.tail == 2) {
+                t.out = dp.out = vptr(c.out, d_stage_in, d_stage_logits, nullptr);
+                t.partial = vptr(c.out2, d_stage_in, d_stage_logits, nullptr);
+            } else mean_out = vptr(steps[si + 2].out, d_stage_in, d_stage_logits, nullptr);
+            auto timeit = [&](auto&& go) {
+                go();
+                hipEventRecord(a, stream);
+                for (int r = 0; r < 3; r++) go();
+                hipEventRecord(b, stream);
+                hipEventSynchronize(b);
+                float ms = 0; hipEventElapsedTime(&ms, a, b);
+                return ms / 3;
+            };
+            const float pair = timeit([&]() {
+                launch_pw_bx3(p, s.wbx, stream);
+                if (s.tail == 2) { if (c.dwl) launch_dwconv_lds(dp, t.partial, c.shape, stream); else launch_dwconv(dp, t.partial, stream); }
+                else { launch_mean_partial(p.out, vptr(c.out, d_stage_in, d_stage_logits, nullptr), n, c.H * c.W, c.C, c.S, stream);
+                       launch_mean_finish(vptr(c.out, d_stage_in, d_stage_logits, nullptr), mean_out, n, c.H * c.W, c.C, c.S, stream); }
+            });
+            if (getenv("BNHIP_DEBUG")) fprintf(stderr, "[bnhip] tune %-16s n=%d unfused pair (nt=%d wm=%d): %.1f us\n", s.name.c_str(), n, p.nt, p.wm, pair * 1e3);
+            float best = forced ? 1e30f : pair * 0.98f; int best_nt = 0, best_wm = 0;
+            PwParams pf = p;
+            if (s.tail == 1) pf.out = mean_out;
+            for (int wm = 13; wm <= 15; wm++)
+                for (int nt = 4; nt <= 8; nt += 2) {
+                    if (!pw_tail_ok(pf, t, nt, wm) || (!forced && !pw_tail_fills(pf, nt, wm))) continue;
+                    const long cols = (long)((s.Co + nt * 16 - 1) / (nt * 16)) * nt * 16;
+                    if (cols * 100 > (long)((s.Co + 15) / 16 * 16) * 130 && !(forced && nt == 4)) continue;      // skip absurd padding
+                    const float ms = timeit([&]() { launch_pw_tail(pf, t, s.wbx, nt, wm, stream); });
+                    if (getenv("BNHIP_DEBUG")) fprintf(stderr, "[bnhip] tune %-16s n=%d fused tail nt=%d wm=%d: %.1f us\n", s.name.c_str(), n, nt, wm, ms * 1e3);
+                    if (ms < best) { best = ms; best_nt = nt; best_wm = wm; }
+                }
+            if (!best_wm) continue;
+            if (pass == 0) { s.nt = best_nt; s.wm = best_wm; } else { s.nt_full = best_nt; s.wm_full = best_wm; }
+            if (s.tail == 2 && c.dwl) {
+                // the fused form writes k_dwconv_t's sums: the calls that run this layer unfused take that kernel too
+                c.dwl = 0; c.shape = -1;
+                dp.in = nullptr; dp.out = nullptr; dp.B = 1;
+                c.S = dwconv_sum_slabs(dp);
+                for (auto& u : steps) if (&u != &c && u.in0 == c.out2) u.S = c.S;
+            }
+        }
+    }
+    hipStreamSynchronize(stream);
+    hipEventDestroy(a); hipEventDestroy(b);
+    (void)hipGetLastError();
+}
+
 // ================================================================================================ run
 float* Engine::vptr(int v, const float* d_in, float* d_logits, float* d_emb, int lane) const {
     if (v < 0) return nullptr;
@@ -877,6 +985,10 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
         float* in2 = vptr(s.in2, d_in, d_logits, d_emb, clip0);
         float* out = vptr(s.out, d_in, d_logits, d_emb, clip0);
         float* out2 = vptr(s.out2, d_in, d_logits, d_emb, clip0);
+        // a step whose work ran in the epilogue of the GEMM in front of it (fused tail)
+        if (s.kind == S_DW && si > 0 && steps[si - 1].tail == 2 && tail_taken(si - 1, n, nl > 1)) continue;
+        if (s.kind == S_MEAN_PARTIAL && si > 0 && steps[si - 1].tail == 1 && tail_taken(si - 1, n, nl > 1)) continue;
+        if (s.kind == S_MEAN_FINISH && si > 1 && steps[si - 2].tail == 1 && tail_taken(si - 2, n, nl > 1)) continue;
         ProfEntry pe{};
         // diagnostics (tools/debug): a host-side synchronize before / after every launch of one kernel class
         static const char* dbg_sync_before = getenv("BNHIP_DEBUG_SYNC_BEFORE");
@@ -963,6 +1075,15 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
                 p.a_bf16 = vals[s.in0].half ? 1 : 0; p.out_bf16 = vals[s.out].half ? 1 : 0;
                 p.res_bf16 = (s.in2 >= 0 && vals[s.in2].half) ? 1 : 0;
                 p.sw = pw_sw;
+                if (tail_taken(si, n, nl > 1)) {
+                    const Step& c = steps[si + 1];
+                    PwTail t = tail_of(s, c);
+                    if (s.tail == 2) { t.out = vptr(c.out, d_in, d_logits, d_emb, clip0); t.partial = vptr(c.out2, d_in, d_logits, d_emb, clip0); }
+                    else p.out = vptr(steps[si + 2].out, d_in, d_logits, d_emb, clip0);
+                    launch_pw_tail(p, t, s.wbx, p.nt, p.wm, stream);
+                    break;
+                }
+                if (p.wm >= 13) p.wm = 10;        // a call too small for the fused form: the same column tile on 64-row tiles, then its consumer
                 if (p.wm >= 5 && s.wbx) launch_pw_bx3(p, s.wbx, stream);
                 else launch_pw_gemm(p, stream);
                 break;
@@ -1086,6 +1207,26 @@ static void jesc(std::ostringstream& os, const std::string& s) {
     for (char c : s) { if (c == '"' || c == '\\') os << '\\'; os << c; }
 }
 
+// How a step reads in describe() and the profile when the full-batch tuning fuses a tail: the GEMM carries the work of both halves
+// under a name that shows it ("b13/expand+dw", "top+mean") and the bytes it really moves - its own output stays in LDS -, the steps
+// it absorbed carry none.
+struct StepView { std::string name; double flops, bytes; bool absorbed; };
+static StepView step_view(const Engine& e, size_t i) {
+    const Step& s = e.steps[i];
+    StepView v{s.name, s.flops, s.bytes, false};
+    auto fused = [&](size_t k) { return e.steps[k].kind == S_PW && e.steps[k].tail && e.steps[k].wm_full >= 13; };
+    if (fused(i)) {
+        const double mine = 4.0 * s.H * s.W * s.Co;
+        if (s.tail == 2) { v.name += "+dw"; v.flops += e.steps[i + 1].flops; }
+        else { v.name += "+mean"; v.flops += e.steps[i + 1].flops + e.steps[i + 2].flops; v.bytes += 4.0 * s.Co - mine; }
+    } else if ((s.kind == S_DW && i > 0 && e.steps[i - 1].tail == 2 && fused(i - 1)) ||
+               (s.kind == S_MEAN_PARTIAL && i > 0 && e.steps[i - 1].tail == 1 && fused(i - 1)) ||
+               (s.kind == S_MEAN_FINISH && i > 1 && e.steps[i - 2].tail == 1 && fused(i - 2))) {
+        v.flops = 0; v.bytes = 0; v.absorbed = true;
+    }
+    return v;
+}
+
 std::string Engine::describe() const {
     std::ostringstream os;
     os << "{\"tune_source\":\"";
@@ -1102,12 +1243,14 @@ std::string Engine::describe() const {
     os << "],\"steps\":[";
     for (size_t i = 0; i < steps.size(); i++) {
         const Step& s = steps[i];
+        const StepView sv = step_view(*this, i);
+        const bool absorbed = sv.absorbed;
         os << (i ? "," : "") << "{\"i\":" << i << ",\"kernel\":\"" << s.kclass << "\",\"name\":\"";
-        jesc(os, s.name);
+        jesc(os, sv.name);
         os << "\",\"H\":" << s.H << ",\"W\":" << s.W << ",\"C\":" << s.C << ",\"Co\":" << s.Co << ",\"k\":" << s.kh
            << ",\"stride\":" << s.sh << ",\"act\":" << s.act << ",\"fused_scale\":" << (s.kind == S_PW && s.in1 >= 0 ? 1 : 0)
-           << ",\"shape\":" << s.shape << ",\"dw_lds\":" << s.dwl << ",\"bx\":" << s.bx << ",\"nt\":" << s.nt << ",\"wm\":" << s.wm << ",\"nt_full\":" << s.nt_full << ",\"wm_full\":" << s.wm_full << ",\"fused_res\":" << (s.kind == S_PW && s.in2 >= 0 ? 1 : 0) << ",\"fused_sum\":" << (s.out2 >= 0 ? 1 : 0) << ",\"flops\":" << s.flops << ",\"bytes\":" << s.bytes << ",\"wbytes\":" << s.wbytes
-           << ",\"out_v\":" << s.out << ",\"out2_v\":" << s.out2
+           << ",\"shape\":" << s.shape << ",\"dw_lds\":" << s.dwl << ",\"bx\":" << s.bx << ",\"nt\":" << s.nt << ",\"wm\":" << s.wm << ",\"nt_full\":" << s.nt_full << ",\"wm_full\":" << s.wm_full << ",\"fused_res\":" << (s.kind == S_PW && s.in2 >= 0 ? 1 : 0) << ",\"fused_sum\":" << (s.out2 >= 0 ? 1 : 0) << ",\"flops\":" << sv.flops << ",\"bytes\":" << sv.bytes << ",\"wbytes\":" << s.wbytes
+           << ",\"tail\":" << s.tail << ",\"absorbed\":" << (absorbed ? 1 : 0) << ",\"out_v\":" << s.out << ",\"out2_v\":" << s.out2
            << ",\"in_bf16\":" << ((s.in0 >= 0 && vals[s.in0].half) ? 1 : 0) << ",\"out_bf16\":" << ((s.out >= 0 && vals[s.out].half) ? 1 : 0) << "}";
     }
     os << "]}";
@@ -1124,11 +1267,12 @@ std::string Engine::profile_read() {
         float ms = 0;
         hipEventElapsedTime(&ms, e.a, e.b);
         const Step& s = steps[e.step];
+        const StepView sv = step_view(*this, e.step);
         if (!agg.count(s.kclass)) order.push_back(s.kclass);
         Agg& a = agg[s.kclass];
-        a.ms += ms; a.launches++; a.flops += s.flops * e.n; a.bytes += s.bytes * e.n + s.wbytes;
+        a.ms += ms; a.launches++; a.flops += sv.flops * e.n; a.bytes += sv.bytes * e.n + s.wbytes;
         Agg& ps = per_step[e.step];
-        ps.ms += ms; ps.launches++; ps.flops += s.flops * e.n; ps.bytes += s.bytes * e.n + s.wbytes;
+        ps.ms += ms; ps.launches++; ps.flops += sv.flops * e.n; ps.bytes += sv.bytes * e.n + s.wbytes;
         ev_pool.push_back(e.a); ev_pool.push_back(e.b);
     }
     prof.clear();
@@ -1143,7 +1287,7 @@ std::string Engine::profile_read() {
         const Agg& a = per_step[i];
         if (!a.launches) continue;
         os << ",{\"step\":" << i << ",\"kernel\":\"" << steps[i].kclass << "\",\"name\":\"";
-        jesc(os, steps[i].name);
+        jesc(os, step_view(*this, i).name);
         os << "\",\"launches\":" << a.launches << ",\"ms\":" << a.ms << ",\"flops\":" << a.flops << ",\"bytes\":" << a.bytes << "}";
     }
     os << "]";

@@ -42,6 +42,8 @@ struct Step {
     int H = 0, W = 0, C = 0, Ho = 0, Wo = 0, Co = 0, kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0;
     int act = 0, act2 = 0, op = 0, mode = 0, S = 1, Cr = 0;
     int nt = 0, wm = 0;      // pw_gemm tile shape chosen by the create-time autotuner (0 = heuristic), for a lane's batch
+    int tail = 0;            // S_PW, decided at plan time (mark_tails): the consumer of this step's output can run in the GEMM's epilogue
+                             // (wm 13 .. 15, PwTail) - 1: the spatial mean of the next two steps, 2: the depthwise convolution of the next
     int H2 = 0, W2 = 0, pt2 = 0, pl2 = 0;   // fused stem + depthwise (mode == 1 on an S_EXPAND_DW step): raw image size, stem padding
     int shape = -1;          // expand_dw tile shape (index into the kernel's table) chosen by the autotuner; -1 = cost model
     int nt_full = 0, wm_full = 0;   // same, tuned at max_batch (calls that run unsplit: pipelined contexts, profiling)
@@ -163,6 +165,10 @@ class Engine {
     hipStream_t lane_stream[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
     void autotune_pw();
+    void autotune_tail();               // S_PW with Step::tail: the fused form against the launches it replaces, per layer
+    void mark_tails();                  // plan time: which S_PW steps may absorb their consumer (BNHIP_PW_TAIL=0: none, =2: all of them do)
+    bool tail_taken(int si, int n, bool lane_tuning) const;   // step si runs fused for a call of n clips (its consumer steps are then skipped)
+    PwParams tail_params(const Step& s, int n, bool lane_tuning) const;
     void tune_or_load();                            // the three create-time tuners, or their recorded result (BNHIP_TUNE_FILE)
     bool save_tuning(const char* path) const;      // BNHIP_TUNE_FILE: the create-time tuners' decisions, one line per step
     bool load_tuning(const char* path);             // false (and nothing changed) unless the file describes exactly this plan

@@ -152,8 +152,9 @@ struct PwParams {         // pointwise conv / fully-connected as GEMM: out[M,N] 
     int sw = 0;           // PW_SW_* bits: experiment / test switches of the split-bf16 kernel family, read from the environment ONCE per
                           // engine (Engine::build) and carried here - no getenv on the launch path
 };
-enum { PW_SW_B16_OFF = 1, PW_SW_B16_FORCE = 2, PW_SW_B16S_OFF = 4, PW_SW_B16S_FORCE = 8, PW_SW_WS_OFF = 16, PW_SW_WS_FORCE = 32, PW_SW_LAT_OFF = 64 };
-int pw_switches_from_env();       // BNHIP_PW_B16 / _B16S / _WS / _LAT (0 only): "0" = never, "2" = wherever the kernel accepts the layer (parity tests)
+enum { PW_SW_B16_OFF = 1, PW_SW_B16_FORCE = 2, PW_SW_B16S_OFF = 4, PW_SW_B16S_FORCE = 8, PW_SW_WS_OFF = 16, PW_SW_WS_FORCE = 32, PW_SW_LAT_OFF = 64,
+       PW_SW_TAIL_OFF = 128, PW_SW_TAIL_FORCE = 256 };
+int pw_switches_from_env();       // BNHIP_PW_B16 / _B16S / _WS / _TAIL / _LAT (0 only): "0" = never, "2" = wherever the kernel accepts the layer (parity tests)
 void launch_pw_gemm(const PwParams& p, hipStream_t s);
 bool pw_pipe_ok(int nt, int wm, int K);   // PwParams::wm = 2 + wm selects the software-pipelined kernel (k_pw_pipe)
 int pw_default_nt(int M, int N);
@@ -169,6 +170,23 @@ void launch_pw_bx3(const PwParams& p, const uint16_t* Wimg, hipStream_t s);
 // tiles; one product per operand pair for "precision":"bf16" engines - 128-row tiles only - or the six-product fp32-equivalent
 // form): called by launch_pw_bx3, which has resolved the tile (nt = 16-column units) and the grid.
 bool pw_b16_ok(int prec, int K, int sw);
+// k_pw_b16 with a row tile that is a whole number of clips (PwParams::wm = 13 / 14 / 15: 48, 96, 192 rows; six-product form, fp32
+// activations, no scale, no residual) and the consumer of its output folded into the epilogue: the k x k stride-1 SAME depthwise
+// convolution of the next step with its squeeze-excite sums (what k_dwconv_t computes, in its operation order), or the spatial mean
+// (k_mean_partial + k_mean_finish, in theirs).  The GEMM's own output never reaches memory.
+struct PwTail {
+    int kind = 0;                 // 1 = spatial mean into PwParams::out [B][N]; 2 = depthwise
+    int H = 0, W = 0;             // the clip's image (H W = PwParams::HW)
+    int k = 0, pt = 0, pl = 0, act = 0;                 // depthwise: taps k x k, SAME padding, activation
+    const float* w = nullptr; const float* bias = nullptr;   // [k][k][N], [N] (nullable)
+    float* out = nullptr;         // depthwise output [B][HW][N]
+    float* partial = nullptr;     // [B][tchunks][N] squeeze-excite sums in k_dwconv_t's layout (nullable)
+    int PY = 0, tiles_w = 0, tiles = 0, tchunks = 0;    // set by the launcher: k_dwconv_t's / k_mean_partial's reduction geometry
+};
+int pw_tail_rows(int wm);                                 // row tile of a fused form (0: wm is not one)
+bool pw_tail_ok(const PwParams& p, const PwTail& t, int nt, int wm);   // the layer fits the form wm with 16 nt-column tiles
+bool pw_tail_fills(const PwParams& p, int nt, int wm);    // the call puts a block on every CU (pw_fill_grid's rule); smaller calls take the pair
+void launch_pw_tail(const PwParams& p, const PwTail& t, const uint16_t* Wimg, int nt, int wm, hipStream_t s);
 bool pw_b16s_ok(const PwParams& p);   // weights-stationary form for skinny layers (N <= 32, K <= 192) of one-product engines: PwParams::wm = 11
 void launch_pw_b16s(const PwParams& p, const uint16_t* Wimg, int Npad, hipStream_t s);
 void launch_pw_b16(const PwParams& p, const uint16_t* Wimg, int nt, int wm /*1 | 2*/, int Npad, int nblk_n, unsigned nblk, hipStream_t s);
@@ -194,6 +212,8 @@ struct DwParams {
 // partial (nullable): [B, dwconv_sum_slabs(p), C] per-slab channel sums of the OUTPUT (fused squeeze-excite mean);
 // dwconv_sum_slabs returns 0 when the shape has no tiled kernel (then no fused sums are available).
 int dwconv_sum_slabs(const DwParams& p);
+// the reduction geometry of the register-tiled kernel (k_dwconv_t): tiles of 2 x 4 outputs, PY tiles per chunk; false: no tiled kernel
+bool dwconv_tile_geometry(const DwParams& p, int* PY, int* tiles_w, int* tiles, int* tchunks);
 void launch_dwconv(const DwParams& p, float* partial, hipStream_t s);
 
 // fused MBConv front half: y = act_d(dwconv(act_e(x We^T + be)) + bd); partial (nullable) [B, slabs, Cmid]
@@ -233,6 +253,7 @@ std::vector<uint16_t> expdw_bx_image(const float* We /*[Cmid][Cin]*/, int Cmid, 
 
 // mean over H*W: in [B,HW,C] -> partial [B,S,C] (sums), S = number of pixel splits
 int mean_splits(int HW);
+int mean_partial_py(int C);       // pixel rows (blockDim.y) of k_mean_partial for C channels
 void launch_mean_partial(const float* in, float* partial, int B, int HW, int C, int S, hipStream_t s);
 // finish: out[b][c] = sum_s partial[b][s][c] / HW
 void launch_mean_finish(const float* partial, float* out, int B, int HW, int C, int S, hipStream_t s);

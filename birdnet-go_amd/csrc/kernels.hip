@@ -1768,6 +1768,12 @@ int dwconv_sum_slabs(const DwParams& p) {
     dw_geometry(p, TH, TW, &CX, &PY, &tw, &t, &tch, &cch);
     return tch;
 }
+bool dwconv_tile_geometry(const DwParams& p, int* PY, int* tiles_w, int* tiles, int* tchunks) {
+    int TH, TW, CX, cch;
+    if (!dw_tiled_shape(p, &TH, &TW) || TH != 2 || TW != 4) return false;
+    dw_geometry(p, TH, TW, &CX, PY, tiles_w, tiles, tchunks, &cch);
+    return true;
+}
 void launch_dwconv(const DwParams& p, float* partial, hipStream_t s) {
     int TH, TW;
     if (dw_tiled_shape(p, &TH, &TW)) {
@@ -1819,9 +1825,14 @@ __global__ __launch_bounds__(256) void k_mean_partial(const float* __restrict__ 
         partial[((size_t)b * S + sp) * C + c] = sum;
     }
 }
-void launch_mean_partial(const float* in, float* partial, int B, int HW, int C, int S, hipStream_t s) {
+int mean_partial_py(int C) {
     int CW = C < 64 ? C : 64;
     int PY = 256 / CW; if (PY < 1) PY = 1;
+    return PY;
+}
+void launch_mean_partial(const float* in, float* partial, int B, int HW, int C, int S, hipStream_t s) {
+    int CW = C < 64 ? C : 64;
+    int PY = mean_partial_py(C);
     dim3 grid((C + CW - 1) / CW, S, B);
     hipLaunchKernelGGL(k_mean_partial, grid, dim3(CW, PY), 0, s, in, partial, HW, C, S);
 }

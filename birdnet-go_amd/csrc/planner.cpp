@@ -1551,7 +1551,45 @@ int pw_switches_from_env() {
         return !e ? 0 : e[0] == '0' ? off : e[0] == '2' ? force : 0;
     };
     return sw("BNHIP_PW_B16", PW_SW_B16_OFF, PW_SW_B16_FORCE) | sw("BNHIP_PW_B16S", PW_SW_B16S_OFF, PW_SW_B16S_FORCE) |
-           sw("BNHIP_PW_WS", PW_SW_WS_OFF, PW_SW_WS_FORCE) | sw("BNHIP_PW_LAT", PW_SW_LAT_OFF, 0);
+           sw("BNHIP_PW_WS", PW_SW_WS_OFF, PW_SW_WS_FORCE) | sw("BNHIP_PW_LAT", PW_SW_LAT_OFF, 0) |
+           sw("BNHIP_PW_TAIL", PW_SW_TAIL_OFF, PW_SW_TAIL_FORCE);
+}
+
+// Which pointwise steps may run their consumer in the GEMM's epilogue (k_pw_b16's clip-aligned row tiles, PwTail): an fp32 engine's
+// split-bf16 GEMM without scale or residual whose output is read by nothing but the next step's stride-1 SAME 3 x 3 / 5 x 5 depthwise
+// convolution, or by the global spatial mean, with a clip's H W pixels a multiple of 16 that divides an offered row tile.  Whether
+// the fused form is then used is the tuner's decision per layer (autotune_tail) and the call's size (tail_taken).
+void Engine::mark_tails() {
+    for (auto& s : steps) s.tail = 0;
+    if (precision != 0 || (pw_sw & PW_SW_TAIL_OFF)) return;
+    const int ns = (int)steps.size();
+    for (int si = 0; si + 1 < ns; si++) {
+        Step& s = steps[si];
+        if (s.kind != S_PW || !s.bx || s.in1 >= 0 || s.in2 >= 0 || s.out < 0 || s.out == v_logits || s.out == v_emb || vals[s.out].external) continue;
+        int readers = 0;
+        for (int k = 0; k < ns; k++)
+            for (int v : {steps[k].in0, steps[k].in1, steps[k].in2}) readers += v == s.out;
+        if (readers != 1 || steps[si + 1].in0 != s.out) continue;
+        const Step& c = steps[si + 1];
+        PwTail t;
+        t.H = s.H; t.W = s.W;
+        if (c.kind == S_DW && c.sh == 1 && c.sw == 1 && c.kh == c.kw && (c.kh == 3 || c.kh == 5) && c.Ho == c.H && c.Wo == c.W && c.H == s.H && c.W == s.W &&
+            c.C == s.Co && c.Co == s.Co && c.pt == (c.kh - 1) / 2 && c.pl == (c.kw - 1) / 2) {
+            t.kind = 2; t.k = c.kh; t.pt = c.pt; t.pl = c.pl; t.act = c.act;
+        } else if (c.kind == S_MEAN_PARTIAL && si + 2 < ns && steps[si + 2].kind == S_MEAN_FINISH && steps[si + 2].in0 == c.out && c.C == s.Co) {
+            t.kind = 1;
+        } else continue;
+        PwParams p{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s.H * s.W, s.Co, s.C, s.H * s.W, s.act};
+        p.prec = precision; p.sw = pw_sw;
+        // (tests: BNHIP_PW_TAIL_FORM=<wm>,<nt> names the form a forced engine plans with - it stands where the tuners do not run)
+        int want_wm = 0, want_nt = 6;
+        if (const char* e = getenv("BNHIP_PW_TAIL_FORM")) { if (sscanf(e, "%d,%d", &want_wm, &want_nt) != 2) { want_wm = 0; want_nt = 6; } }
+        int fit = 0, forced_fit = 0;
+        for (int wm : {14, 13, 15}) if (pw_tail_ok(p, t, 6, wm)) { if (!fit) fit = wm; if (wm == want_wm && pw_tail_ok(p, t, want_nt, wm)) forced_fit = wm; }
+        if (!fit) continue;
+        s.tail = t.kind;
+        if (pw_sw & PW_SW_TAIL_FORCE) { s.wm = s.wm_full = forced_fit ? forced_fit : fit; s.nt = s.nt_full = forced_fit ? want_nt : 6; }
+    }
 }
 
 // ================================================================================================ build
@@ -1575,6 +1613,7 @@ bool Engine::build(TflModel m, int dev, int maxb, bool plan_only, std::string* e
         return false;
     }
     tensor_value = L.tv;
+    mark_tails();
 
     mark_liveness(vals, steps);
     if (v_emb >= 0) vals[v_emb].last = (int)steps.size();      // keep until copy-out

@@ -33,8 +33,199 @@ __device__ long long* g_b16_trace = nullptr;      // [64 blocks][4 waves][B16_TR
 #define B16_T(i) do { } while (0)
 #endif
 
-template <bool ABF, bool SCR> struct ASet { ARaw<ABF> a[2]; };
-template <bool ABF> struct ASet<ABF, true> { ARaw<ABF> a[2]; float4 slo[2], shi[2]; };
+// ---- fused tails (EPI != 0): the consumer of the GEMM's output runs on the tile while it is in LDS
+// Columns of a group share the staging area: the largest divisor G of NT with BM rows x (16 G + 4) floats of staged tile plus
+// BM x 4 G floats of per-tile sums (depthwise: at most HW / 4 tiles per clip, pw_tail_ok) inside the two operand buffers.
+constexpr int pw_tail_group(int NT, int BM, int budget) {
+    int g = 1;
+    for (int c = 1; c <= NT; c++)
+        if (NT % c == 0 && BM * (20 * c + 4) <= budget) g = c;
+    return g;
+}
+// D[i = n 4 kq + r][j = m li]: a lane holds 4 consecutive channels of row 16 (WM wave + mt) + li of the block's tile.  Bias and
+// activation exactly as pw_epilogue applies them; then, per column group: stage [BM rows][16 G columns] (row stride 16 G + 4),
+// barrier, consume.
+//   mean (EPI 1): thread = (clip, channel); k_mean_partial's order - PY strided partial sums over the clip's pixels, added for
+//     y = 0 .. PY - 1 - and k_mean_finish's division.
+//   depthwise (EPI = k): thread = (clip, 2 x 4 output tile, channel quad), k_dwconv_t<k, 1, 2, 4>'s loop nest with the input rows read
+//     from LDS; stores are channel-fastest across lanes; the per-tile sums go through LDS and are added PY tiles per chunk in tile
+//     order, one value per (clip, chunk, channel), as k_dwconv_t's block does.
+template <int NT, int WM, int NW, int EPI, int LDSF>
+__device__ __forceinline__ void pw_tail_epilogue(const PwParams& p, const PwTail& te, f32x4 (&acc)[NT][WM], float* lds, int m0, int n0) {
+    constexpr int NTHR = 64 * NW, BM = 16 * WM * NW;
+    constexpr int G = pw_tail_group(NT, BM, LDSF), NG = NT / G, GC = 16 * G, RS = GC + 4, Q = 4 * G;
+    static_assert(BM * (20 * G + 4) <= LDSF, "staged tile and sums inside the operand buffers");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    const bool vec_ok = (p.N & 3) == 0;
+    if (p.bias) {
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            int n = n0 + 16 * t + 4 * kq;
+            f32x4 bq = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (vec_ok && n + 3 < p.N) { float4 t4 = *reinterpret_cast<const float4*>(p.bias + n); bq = (f32x4){t4.x, t4.y, t4.z, t4.w}; }
+            else {
+#pragma unroll
+                for (int r = 0; r < 4; r++) if (n + r < p.N) bq[r] = p.bias[n + r];
+            }
+#pragma unroll
+            for (int mt = 0; mt < WM; mt++) acc[t][mt] += bq;
+        }
+    }
+    if (p.act == ACT_SWISH) {
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int mt = 0; mt < WM; mt++) acc[t][mt] = swish4(acc[t][mt]);
+    } else {
+        with_act(p.act, [&](auto f) {
+#pragma unroll
+            for (int t = 0; t < NT; t++)
+#pragma unroll
+                for (int mt = 0; mt < WM; mt++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) acc[t][mt][r] = f(acc[t][mt][r]);
+        });
+    }
+    const int HW = p.HW, B = p.M / HW;
+    const int b0 = m0 / HW;                         // BM % HW == 0: the block's first clip
+    const int clips = min(BM / HW, B - b0);         // clips of this block that exist (> 0: the grid covers M)
+    float* red = lds + BM * RS;
+    for (int g = 0; g < NG; g++) {
+        // (every wave is past the K loop's last barrier / the previous group's consumers: the staging area is free)
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            if (t / G != g) continue;
+#pragma unroll
+            for (int mt = 0; mt < WM; mt++)
+                *reinterpret_cast<f32x4*>(&lds[(16 * (WM * wave + mt) + li) * RS + 16 * (t - g * G) + 4 * kq]) = acc[t][mt];
+        }
+        __syncthreads();
+        const int ng0 = n0 + GC * g;                // first channel of the group
+        if constexpr (EPI == 1) {
+            const int PY = te.PY;
+            for (int it = tid; it < clips * GC; it += NTHR) {
+                const int cl = it / GC, ch = it - cl * GC, c = ng0 + ch;
+                if (c >= p.N) continue;
+                const float* x = lds + (size_t)cl * HW * RS + ch;
+                float sum = 0.f;
+                for (int y = 0; y < PY; y++) {
+                    float a = 0.f;
+                    for (int px = y; px < HW; px += PY) a += x[px * RS];
+                    sum += a;
+                }
+                float tot = 0.f;
+                tot += sum;                         // (k_mean_finish over its one slab)
+                p.out[(size_t)(b0 + cl) * p.N + c] = tot / (float)HW;
+            }
+            __syncthreads();
+        } else {
+            constexpr int K = EPI, TH = 2, TW = 4, RW = TW - 1 + K, RH = TH - 1 + K;
+            const int H = te.H, W = te.W, C4 = p.N >> 2, tiles = te.tiles;
+            for (int it = tid; it < clips * tiles * Q; it += NTHR) {
+                const int q = it % Q, rest = it / Q, tile = rest % tiles, cl = rest / tiles;
+                const int c4 = (ng0 >> 2) + q;
+                float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c4 < C4) {
+                    const int b = b0 + cl;
+                    const int th0 = (tile / te.tiles_w) * TH, tw0 = (tile % te.tiles_w) * TW;
+                    const int hi0 = th0 - te.pt, wi0 = tw0 - te.pl;
+                    const float* in = lds + (size_t)cl * HW * RS + 4 * q;
+                    const float4* w4 = reinterpret_cast<const float4*>(te.w) + c4;
+                    float4 a4[TH][TW];
+#pragma unroll
+                    for (int a = 0; a < TH; a++)
+#pragma unroll
+                        for (int c = 0; c < TW; c++) a4[a][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int r = 0; r < RH; r++) {
+                        const int hi = hi0 + r;
+                        if (hi < 0 || hi >= H) continue;
+                        float4 x[RW];
+#pragma unroll
+                        for (int c = 0; c < RW; c++) {
+                            const int wi = wi0 + c;
+                            if (!(wi >= 0 && wi < W)) x[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                            else x[c] = *reinterpret_cast<const float4*>(in + (hi * W + wi) * RS);
+                        }
+#pragma unroll
+                        for (int a = 0; a < TH; a++) {
+                            const int i = r - a;        // kernel row feeding output row a from input row r
+                            if (i < 0 || i >= K) continue;
+#pragma unroll
+                            for (int j = 0; j < K; j++) {
+                                const float4 w = w4[(size_t)(i * K + j) * C4];
+#pragma unroll
+                                for (int c = 0; c < TW; c++) {
+                                    const float4 xv = x[c + j];
+                                    a4[a][c].x = fmaf(xv.x, w.x, a4[a][c].x); a4[a][c].y = fmaf(xv.y, w.y, a4[a][c].y);
+                                    a4[a][c].z = fmaf(xv.z, w.z, a4[a][c].z); a4[a][c].w = fmaf(xv.w, w.w, a4[a][c].w);
+                                }
+                            }
+                        }
+                    }
+                    const float4 bv = te.bias ? reinterpret_cast<const float4*>(te.bias)[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (te.act == ACT_SWISH) {
+#pragma unroll
+                        for (int a = 0; a < TH; a++)
+#pragma unroll
+                            for (int c = 0; c < TW; c++) {
+                                float4& v = a4[a][c];
+                                const f32x4 r = swish4((f32x4){v.x + bv.x, v.y + bv.y, v.z + bv.z, v.w + bv.w});
+                                v = make_float4(r[0], r[1], r[2], r[3]);
+                            }
+                    } else {
+                        with_act(te.act, [&](auto f) {
+#pragma unroll
+                            for (int a = 0; a < TH; a++)
+#pragma unroll
+                                for (int c = 0; c < TW; c++) {
+                                    float4& v = a4[a][c];
+                                    v.x = f(v.x + bv.x); v.y = f(v.y + bv.y); v.z = f(v.z + bv.z); v.w = f(v.w + bv.w);
+                                }
+                        });
+                    }
+                    float4* out4 = reinterpret_cast<float4*>(te.out) + (size_t)b * HW * C4 + c4;
+#pragma unroll
+                    for (int a = 0; a < TH; a++) {
+                        const int ho = th0 + a;
+                        if (ho >= H) continue;
+#pragma unroll
+                        for (int c = 0; c < TW; c++) {
+                            const int wo = tw0 + c;
+                            if (wo >= W) continue;
+                            const float4 v = a4[a][c];
+                            out4[(size_t)(ho * W + wo) * C4] = v;
+                            sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
+                        }
+                    }
+                }
+                reinterpret_cast<float4*>(red)[it] = sum;
+            }
+            __syncthreads();
+            if (te.partial) {
+                const int PY = te.PY, tchunks = te.tchunks;
+                for (int it = tid; it < clips * tchunks * Q; it += NTHR) {
+                    const int q = it % Q, rest = it / Q, tc = rest % tchunks, cl = rest / tchunks;
+                    const int c4 = (ng0 >> 2) + q;
+                    if (c4 >= C4) continue;
+                    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+                    for (int y = 0; y < PY; y++) {
+                        const int tile = tc * PY + y;
+                        if (tile >= tiles) break;       // (k_dwconv_t adds the zero of a thread without a tile: the same value)
+                        const float4 v = reinterpret_cast<const float4*>(red)[(cl * tiles + tile) * Q + q];
+                        t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+                    }
+                    reinterpret_cast<float4*>(te.partial)[((size_t)(b0 + cl) * tchunks + tc) * C4 + c4] = t;
+                }
+            }
+            // (the next group's staging does not touch `red`, and its barrier orders these reads before the next sums)
+        }
+    }
+}
+
+template <bool ABF, bool SCR, int WM = 2> struct ASet { ARaw<ABF> a[WM < 2 ? 2 : WM]; };
+template <bool ABF, int WM> struct ASet<ABF, true, WM> { ARaw<ABF> a[WM < 2 ? 2 : WM]; float4 slo[WM < 2 ? 2 : WM], shi[WM < 2 ? 2 : WM]; };
 
 // SCL: the squeeze-excite scale of a slab goes through LDS once per block ([clips of the row tile][32] floats) instead of being
 // loaded per row - possible when a 16-row MFMA tile never straddles two clips (HW % 16 == 0); otherwise each lane loads its own.
@@ -44,21 +235,26 @@ template <bool ABF> struct ASet<ABF, true> { ARaw<ABF> a[2]; float4 slo[2], shi[
 // SIX: the fp32-equivalent form (PwParams::prec == 0, fp32 engines): A split into three bf16 pieces in registers, all three
 // weight planes of the slab in LDS, six products per operand pair in k_pw_bx3's order.  WM: 16-row tiles per wave (rows per
 // block = 64 WM).
-template <int NT, bool SC, bool ABF, bool SCL = false, int WM = 2, bool SIX = false>
-__global__ __launch_bounds__(256) void k_pw_b16(PwParams p, const uint16_t* __restrict__ Wimg, int Npad, int nblk_n, unsigned nblk,
-                                                 FDiv dn, FDiv dhw) {
+// NW: waves per block (rows per block = 16 WM NW).  EPI: what happens to the tile after the K loop - 0: pw_epilogue (bias, activation,
+// residual, store); 1 / 3 / 5: the fused tails (PwTail: spatial mean | 3 x 3 | 5 x 5 depthwise), for row tiles that are a whole
+// number of clips.  The K loop is the same code for every NW and EPI: the pre-activation values do not depend on them.
+template <int NT, bool SC, bool ABF, bool SCL = false, int WM = 2, bool SIX = false, int NW = 4, int EPI = 0>
+__global__ __launch_bounds__(64 * NW) void k_pw_b16(PwParams p, const uint16_t* __restrict__ Wimg, int Npad, int nblk_n, unsigned nblk,
+                                                     FDiv dn, FDiv dhw, PwTail tail) {
     static_assert(!SCL || SC, "SCL is a form of SC");
     static_assert(!SIX || !ABF, "fp32 engines keep fp32 activations");
+    static_assert(EPI == 0 || (SIX && !SC), "the fused tails: six-product form without a scale");
     constexpr bool SCR = SC && !SCL;                           // scale in registers, per lane
-    constexpr int BM = 64 * WM, BN = 16 * NT;
+    constexpr int NTHR = 64 * NW;
+    constexpr int BM = 16 * WM * NW, BN = 16 * NT;
     constexpr int NP = SIX ? 3 : 1;                            // weight planes used (hi | hi, mid, lo)
     constexpr int WSLOTS = NP * 4 * BN;                        // 16-byte slots of a slab's weight tile: [plane NP][kq 4][row BN]
-    constexpr int WQ = (WSLOTS + 255) / 256;
+    constexpr int WQ = (WSLOTS + NTHR - 1) / NTHR;
     constexpr int SCLIPS = BM / 16 + 1;                        // clips a 128-row tile can touch when HW >= 16
     constexpr int SBUF = SCL ? SCLIPS * 32 : 0;                // floats of one scale buffer
     constexpr int OBUF = WSLOTS * 4 + SBUF;                    // floats of one operand buffer
     constexpr int STG = 4 * 16 * (BN + 4);                     // pw_epilogue's staging area (floats)
-    constexpr int LDSN = 2 * OBUF > STG ? 2 * OBUF : STG;
+    constexpr int LDSN = (EPI != 0 || 2 * OBUF > STG) ? 2 * OBUF : STG;       // (the fused tails stage through the operand buffers alone)
     __shared__ __attribute__((aligned(16))) float lds[LDSN];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
@@ -85,7 +281,7 @@ __global__ __launch_bounds__(256) void k_pw_b16(PwParams p, const uint16_t* __re
     unsigned woff[WQ];
 #pragma unroll
     for (int q = 0; q < WQ; q++) {
-        const int slot = min(tid + 256 * q, WSLOTS - 1);
+        const int slot = min(tid + NTHR * q, WSLOTS - 1);
         const int kqs = slot / BN, r = slot - kqs * BN;                                   // kqs = plane * 4 + kq
         woff[q] = (unsigned)kqs * (unsigned)Npad + (unsigned)min(n0 + r, Npad - 1);       // 16-byte units inside a slab of the image
     }
@@ -95,7 +291,7 @@ __global__ __launch_bounds__(256) void k_pw_b16(PwParams p, const uint16_t* __re
     const int sclip = tid >> 3, sk4 = tid & 7;
     const int nclips_blk = SCL ? (int)fdiv((unsigned)(min(m0 + BM, p.M) - 1), dhw) - b_first + 1 : 0;
 
-    ASet<ABF, SCR> set0, set1;
+    ASet<ABF, SCR, WM> set0, set1;
     u32v4 wreg[WQ];
     float4 sreg;
     auto aload = [&](int sl, auto& st) {
@@ -129,14 +325,14 @@ __global__ __launch_bounds__(256) void k_pw_b16(PwParams p, const uint16_t* __re
         const u32v4* Ws = W16 + (size_t)sl * 12 * Npad;                       // 3 planes x 4 kq x Npad slots per slab; plane 0 = hi
 #pragma unroll
         for (int q = 0; q < WQ; q++)
-            if (tid + 256 * q < WSLOTS) wreg[q] = Ws[woff[q]];
+            if (tid + NTHR * q < WSLOTS) wreg[q] = Ws[woff[q]];
     };
     auto wstore = [&](int buf) {
         float* base = lds + buf * OBUF;
         u32v4* Wl = reinterpret_cast<u32v4*>(base);
 #pragma unroll
         for (int q = 0; q < WQ; q++)
-            if (tid + 256 * q < WSLOTS) Wl[tid + 256 * q] = wreg[q];
+            if (tid + NTHR * q < WSLOTS) Wl[tid + NTHR * q] = wreg[q];
         if constexpr (SCL) {
             if (sclip < SCLIPS) *reinterpret_cast<float4*>(base + WSLOTS * 4 + sclip * 32 + 4 * sk4) = sreg;
         }
@@ -237,7 +433,8 @@ __global__ __launch_bounds__(256) void k_pw_b16(PwParams p, const uint16_t* __re
         if (sl + 1 < nslab) slab(sl + 1, set1);
     }
     B16_T(3);
-    pw_epilogue<NT, WM>(p, acc, lds, m0, n0);
+    if constexpr (EPI == 0) pw_epilogue<NT, WM>(p, acc, lds, m0, n0);
+    else pw_tail_epilogue<NT, WM, NW, EPI, 2 * OBUF>(p, tail, acc, lds, m0, n0);
     B16_T(4);
 }
 
@@ -400,7 +597,7 @@ void launch_pw_b16(const PwParams& p, const uint16_t* Wimg, int nt, int wm, int 
     const bool sc = p.ascale != nullptr, abf = p.a_bf16 != 0, six = p.prec == 0;
     const bool scl = sc && p.HW >= 16 && (p.HW & 15) == 0;      // a 16-row tile never straddles two clips: scale through LDS
     dim3 grid(nblk);
-#define B16_LAUNCH(NT_, SC_, ABF_, SCL_, WM_, SIX_) hipLaunchKernelGGL((k_pw_b16<NT_, SC_, ABF_, SCL_, WM_, SIX_>), grid, dim3(256), 0, s, p, Wimg, Npad, nblk_n, nblk, dn, dhw)
+#define B16_LAUNCH(NT_, SC_, ABF_, SCL_, WM_, SIX_) hipLaunchKernelGGL((k_pw_b16<NT_, SC_, ABF_, SCL_, WM_, SIX_>), grid, dim3(256), 0, s, p, Wimg, Npad, nblk_n, nblk, dn, dhw, PwTail{})
 #define B16_FLAV(NT_, WM_, SIX_, ABF_) do { if (scl) B16_LAUNCH(NT_, true, ABF_, true, WM_, SIX_); else if (sc) B16_LAUNCH(NT_, true, ABF_, false, WM_, SIX_); \
                                             else B16_LAUNCH(NT_, false, ABF_, false, WM_, SIX_); } while (0)
 #define B16_CASE(NT_) case NT_: \
@@ -414,6 +611,47 @@ void launch_pw_b16(const PwParams& p, const uint16_t* Wimg, int nt, int wm, int 
 #undef B16_CASE
 }
 
+// ---- fused tails: PwParams::wm 13 / 14 / 15 = 3 waves x 16 rows, 6 waves x 16 rows, 4 waves x 48 rows
+static std::atomic<long> g_pw_tail_launches{0};     // diagnostics (tests assert that the fused kernel ran)
+int pw_tail_rows(int wm) { return wm == 13 ? 48 : wm == 14 ? 96 : wm == 15 ? 192 : 0; }
+static bool pw_tail_geometry(const PwParams& p, PwTail* t) {
+    if (t->kind == 1) { t->PY = mean_partial_py(p.N); return mean_splits(p.HW) == 1; }
+    DwParams d{nullptr, nullptr, nullptr, nullptr, 1, t->H, t->W, p.N, t->H, t->W, t->k, t->k, 1, 1, t->pt, t->pl, t->act};
+    return dwconv_tile_geometry(d, &t->PY, &t->tiles_w, &t->tiles, &t->tchunks) && 4 * t->tiles <= p.HW;
+}
+bool pw_tail_ok(const PwParams& p, const PwTail& t, int nt, int wm) {
+    const int bm = pw_tail_rows(wm);
+    if (!bm || (p.sw & PW_SW_TAIL_OFF) || p.prec != 0 || p.a_bf16 || p.out_bf16 || p.ascale || p.res) return false;
+    if (nt != 4 && nt != 6 && nt != 8) return false;
+    if ((p.K & 3) || p.K < 16 || (p.N & 3) || p.HW < 16 || (p.HW & 15) || bm % p.HW || p.M % p.HW || t.H * t.W != p.HW) return false;
+    if (t.kind == 2 && t.k != 3 && t.k != 5) return false;
+    if (t.kind != 1 && t.kind != 2) return false;
+    PwTail g = t;
+    return pw_tail_geometry(p, &g);
+}
+bool pw_tail_fills(const PwParams& p, int nt, int wm) {
+    const int bm = pw_tail_rows(wm);
+    return bm && (long)((p.M + bm - 1) / bm) * ((p.N + 16 * nt - 1) / (16 * nt)) >= device_cus();
+}
+void launch_pw_tail(const PwParams& p, const PwTail& t_, const uint16_t* Wimg, int nt, int wm, hipStream_t s) {
+    g_pw_tail_launches.fetch_add(1, std::memory_order_relaxed);
+    PwTail t = t_;
+    pw_tail_geometry(p, &t);
+    const int bm = pw_tail_rows(wm), Npad = pw_bx3_npad(p.N);
+    const int nblk_n = (p.N + 16 * nt - 1) / (16 * nt);
+    const unsigned nblk = (unsigned)((p.M + bm - 1) / bm) * (unsigned)nblk_n;
+    const FDiv dn = make_fdiv((unsigned)nblk_n), dhw = make_fdiv((unsigned)std::max(p.HW, 1));
+    const int epi = t.kind == 1 ? 1 : t.k;
+#define TAIL_LAUNCH(NT_, WM_, NW_, EPI_) hipLaunchKernelGGL((k_pw_b16<NT_, false, false, false, WM_, true, NW_, EPI_>), dim3(nblk), dim3(64 * NW_), 0, s, p, Wimg, Npad, nblk_n, nblk, dn, dhw, t)
+#define TAIL_EPI(NT_, WM_, NW_) do { if (epi == 1) TAIL_LAUNCH(NT_, WM_, NW_, 1); else if (epi == 3) TAIL_LAUNCH(NT_, WM_, NW_, 3); else TAIL_LAUNCH(NT_, WM_, NW_, 5); } while (0)
+#define TAIL_TILE(NT_) do { if (wm == 13) TAIL_EPI(NT_, 1, 3); else if (wm == 14) TAIL_EPI(NT_, 1, 6); else TAIL_EPI(NT_, 3, 4); } while (0)
+    if (nt == 4) TAIL_TILE(4); else if (nt == 6) TAIL_TILE(6); else TAIL_TILE(8);
+#undef TAIL_LAUNCH
+#undef TAIL_EPI
+#undef TAIL_TILE
+}
+
 }  // namespace bnhip
 
+extern "C" long bnhip_debug_pw_tail_launches(void) { return bnhip::g_pw_tail_launches.load(std::memory_order_relaxed); }
 extern "C" long bnhip_debug_pw_b16_launches(void) { return bnhip::g_pw_b16_launches.load(std::memory_order_relaxed); }
