@@ -1,4 +1,4 @@
-// Graph planner (planner.cpp) + executor (engine.cpp): TFLite op graph -> fused gfx950 kernel plan.
+// Graph planner (planner.cpp) + create-time tuning (tune.cpp) + executor (engine.cpp): TFLite op graph -> fused gfx950 kernel plan.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -90,6 +90,12 @@ struct WeightPlan {                  // host half of the weight arena, made by t
     std::vector<size_t> step_bx;     // per step: offset of the split-bf16 weight image (S_PW / S_EXPAND_DW of a bf16x3 engine)
 };
 
+// step s as a depthwise convolution of n clips; with the defaults, the geometry the dwconv_* helpers are asked about
+inline DwParams dw_params(const Step& s, const float* in = nullptr, float* out = nullptr, int n = 1) {
+    return DwParams{in, s.w0, s.w1, out, n, s.H, s.W, s.C, s.Ho, s.Wo, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.act};
+}
+PwTail tail_of(const Step& s, const Step& c);   // the fused tail of GEMM step s (Step::tail) with its consumer c (output pointers left null)
+
 class Engine {
   public:
     ~Engine();
@@ -116,9 +122,6 @@ class Engine {
     int pw_sw = 0;                      // PW_SW_* switch bits of the split-bf16 GEMM family: the environment read ONCE in build(), carried in every PwParams
     bool use_graphs = false;            // opt-in: replay the plan as a hipGraph once a (pointers, n) combination repeats (measured: no gain on ROCm 7.2)
     void drop_graphs();
-    void autotune_expdw();
-    void mark_bf16_storage();           // "precision":"bf16": which activation values are kept as bf16 in HBM
-    void autotune_dw();                 // S_DW: register-tiled k_dwconv_t vs the LDS-staged form, per layer
     // Pipelining across calls ("depth" option, bnhip_predict_device only): call i runs on context i % depth (own stream,
     // own activation arena), so the tail of one batch overlaps the head of the next.  Completion is then signalled by
     // synchronize(), not by the caller's stream.
@@ -164,12 +167,17 @@ class Engine {
     int dual_lane_min = 32;
     hipStream_t lane_stream[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
-    void autotune_pw();
-    void autotune_tail();               // S_PW with Step::tail: the fused form against the launches it replaces, per layer
     void mark_tails();                  // plan time: which S_PW steps may absorb their consumer (BNHIP_PW_TAIL=0: none, =2: all of them do)
     bool tail_taken(int si, int n, bool lane_tuning) const;   // step si runs fused for a call of n clips (its consumer steps are then skipped)
-    PwParams tail_params(const Step& s, int n, bool lane_tuning) const;
-    void tune_or_load();                            // the three create-time tuners, or their recorded result (BNHIP_TUNE_FILE)
+    PwParams pw_params(const Step& s, int n, bool lane_tuning) const;   // step s as a GEMM of n clips on its lane / full-batch tuning (operand pointers left null)
+    // Create-time tuning (tune.cpp), once the weights are on the device: the bf16 storage decision, then the plan's tuning - adopted
+    // from a file, the process cache or a directory of recorded tunings, or timed by the four tuners.
+    void mark_bf16_storage();           // "precision":"bf16": which activation values are kept as bf16 in HBM
+    void tune_or_load();                // the four create-time tuners, or their recorded result
+    void autotune_pw();                 // S_PW: tile shape and kernel form per layer, at a lane's batch and at max_batch
+    void autotune_expdw();              // S_EXPAND_DW: tile shape of the fused kernel, per layer
+    void autotune_dw();                 // S_DW: register-tiled k_dwconv_t vs the LDS-staged form, per layer
+    void autotune_tail();               // S_PW with Step::tail: the fused form against the launches it replaces, per layer
     bool save_tuning(const char* path) const;      // BNHIP_TUNE_FILE: the create-time tuners' decisions, one line per step
     bool load_tuning(const char* path);             // false (and nothing changed) unless the file describes exactly this plan
     std::string tuning_text() const;                // the same decisions as text (what the file holds)
@@ -177,6 +185,9 @@ class Engine {
     std::string tune_key() const;                   // plan hash + batch / depth / precision / switches: cache key and file name of a recorded tuning
     std::string tune_dir;                           // "tune_dir" option / BNHIP_TUNE_DIR: directory of recorded tunings (<tune_key>.tune)
     std::string tune_source;                        // where this engine's tuning came from: file:… | process-cache | dir:… | self-tuned | (empty: autotune off)
+    bool expdw_pipe16(const Step& s) const;         // an S_EXPAND_DW step whose phase 1 runs on the bf16 pipe (expdw_sk_pipe16)
+    ExpDwGeo expdw_geo(const Step& s) const;        // the ExpDwGeo launch_expand_dw / launch_dwconv_lds derive for step s: what the shape helpers are asked about
+    void set_sum_slabs(Step& s, int S);             // s.S, and the S of the steps that read its per-tile sums (out2)
     std::map<int, int> tensor_value;    // tflite tensor index -> value id (diagnostics)
     const float* value_ptr(int v) const { return reinterpret_cast<const float*>(act_arena + vals[v].offset); }
     int n_samples = 0, n_classes = 0, emb_dim = 0, C_spec = 0;

@@ -1,6 +1,6 @@
 // Plan time: the TFLite op graph -> Engine::steps / vals / specs, the activation arena layouts and the host image of the
 // weight arena.  Pure CPU work (plan_only engines stop here); the device half of Engine::build - allocation, weight upload,
-// pointer patching - is Engine::bind_device in engine.cpp.
+// pointer patching - is Engine::bind_device in engine.cpp; the bf16 storage decision and the create-time tuning that follow it are tune.cpp.
 #include "engine.h"
 
 #include <algorithm>
@@ -1020,12 +1020,13 @@ struct Lowering {
         int slabs = 0, cap = 0;
         if (!steps.empty() && steps.back().kind == S_EXPAND_DW && steps.back().out == vin) {
             const Step& d = steps.back();
+            // (not Engine::expdw_geo: no skw, because wbx is not bound yet; the eight-wave shapes it offers tile as their four-wave twins, so neither count depends on it)
             const ExpDwGeo dg{d.kh, d.sh, d.H, d.W, d.Ho, d.Wo, d.pt, d.pl, d.mode == 1};
             slabs = expdw_sum_slabs(dg);
             cap = expdw_max_slabs(dg);
         } else if (!steps.empty() && steps.back().kind == S_DW && steps.back().out == vin) {
             const Step& d = steps.back();
-            DwParams dp{nullptr, nullptr, nullptr, nullptr, 1, d.H, d.W, d.C, d.Ho, d.Wo, d.kh, d.kw, d.sh, d.sw, d.pt, d.pl, d.act};
+            const DwParams dp = dw_params(d);
             slabs = cap = dwconv_sum_slabs(dp);
             if (dwconv_lds_supported(dp)) cap = std::max(cap, expdw_max_slabs(ExpDwGeo{d.kh, d.sh, d.H, d.W, d.Ho, d.Wo, d.pt, d.pl}));
         }

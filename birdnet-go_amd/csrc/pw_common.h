@@ -65,7 +65,7 @@ __device__ __forceinline__ f32x4 swish4(f32x4 v) {
 #endif
 }
 
-// bf16 activation storage ("precision":"bf16" engines, engine.cpp mark_bf16_storage): a value whose producer and consumers all
+// bf16 activation storage ("precision":"bf16" engines, tune.cpp mark_bf16_storage): a value whose producer and consumers all
 // understand it is kept as bf16 in HBM - the 6x-expanded tensors between expand, depthwise and projection, which are what the
 // HBM-bound layers move.  Round to nearest even on the way out (v_cvt_pk_bf16_f32), a 16-bit shift on the way in; arithmetic
 // and accumulation stay fp32.  Four channels = one 8-byte access instead of a 16-byte one.

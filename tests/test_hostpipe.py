@@ -146,7 +146,7 @@ def test_two_contexts_with_different_data_equal_the_serial_results(gpu, full_blo
 
 @pytest.mark.gpu
 def test_bf16_storage_engine_through_the_pipeline_equals_its_serial_path(gpu, full_blob):
-    """A "precision":"bf16" engine keeps the expanded tensors as bf16 in HBM (engine.cpp mark_bf16_storage); every context of
+    """A "precision":"bf16" engine keeps the expanded tensors as bf16 in HBM (tune.cpp mark_bf16_storage); every context of
     the host pipeline has its own activation arena with the same value layout, so 512 distinct clips through two contexts
     must equal the same engine's serial path (host_depth 1) bit for bit, and a repeat of the call must equal itself."""
     x256 = sm.synth_clips(256, 144000, 48000)

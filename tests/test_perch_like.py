@@ -169,7 +169,7 @@ def test_bf16_precision_drift_is_bounded(gpu):
 
 @pytest.mark.gpu
 def test_bf16_activation_storage_plan_and_drift(gpu, monkeypatch):
-    """"precision":"bf16" also keeps the 6x-expanded tensors as bf16 in HBM (engine.cpp mark_bf16_storage: outputs of the
+    """"precision":"bf16" also keeps the 6x-expanded tensors as bf16 in HBM (tune.cpp mark_bf16_storage: outputs of the
     split-bf16 expand GEMMs, of the depthwise kernels and of the fused expand + depthwise kernel, consumed by depthwise /
     projection).  The plan must mark exactly those, an f32 engine none; against the same engine with fp32 storage
     (BNHIP_BF16_ACT=0) the only new rounding is the depthwise input, so logits move little; and the oracle bounds of the
@@ -461,7 +461,7 @@ def test_tuning_file_reproduces_the_plan_and_is_ignored_by_other_plans(gpu, tmp_
 @pytest.mark.gpu
 def test_bf16_residual_stream_plan_and_drift(gpu, monkeypatch):
     """"precision":"bf16" keeps the residual stream - projection outputs, read by the next expand, the next residual add and the
-    ratio-1 blocks' depthwise kernels - as bf16 where every reader can widen it (engine.cpp mark_bf16_storage; BNHIP_BF16_RESID=0
+    ratio-1 blocks' depthwise kernels - as bf16 where every reader can widen it (tune.cpp mark_bf16_storage; BNHIP_BF16_RESID=0
     keeps block outputs fp32).  The plan shows it (projections write bf16, fused expand + depthwise steps read bf16), the softmax
     moves by less than the option's own drift against the oracle, top-1 stays."""
     cfg = sm.perch_config()
