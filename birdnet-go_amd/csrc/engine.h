@@ -107,7 +107,7 @@ class Engine {
     bool no_reuse = false;              // diagnostics: every activation keeps its own buffer
     bool autotune = true;               // time pw_gemm tile widths per layer at create time (a few ms)
     // multi-device handles: every engine plans the same weight image; only the first uploads it from the host, the others
-    // allocate their weight arena and receive the bytes device-to-device (RCCL broadcast / peer copy, see api.cpp) before
+    // allocate their weight arena and receive the bytes device-to-device (RCCL broadcast / peer copy, see api_model.cpp) before
     // finish_deferred() runs the create-time autotune
     bool defer_weights = false;
     void finish_deferred();

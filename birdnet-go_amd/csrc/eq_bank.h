@@ -1,4 +1,4 @@
-// Batched per-source equalizer (api.cpp bnhip_eq_bank_*): one launch runs one call's PCM16 frames of every processed stream
+// Batched per-source equalizer (api_eq.cpp bnhip_eq_bank_*): one launch runs one call's PCM16 frames of every processed stream
 // of a bank through its biquad stages, gain, clamp and truncation.  The descriptor table, the normalised coefficients and the
 // packed PCM16 travel in one staging buffer.
 #pragma once

@@ -1,4 +1,4 @@
-// Species occurrence heat-map grids of the range-filter meta-model (api.cpp bnhip_range_heatmap): the kernels that turn a grid of
+// Species occurrence heat-map grids of the range-filter meta-model (api_predict.cpp bnhip_range_heatmap): the kernels that turn a grid of
 // cell centres into model rows and keep one output column of every row.
 #pragma once
 #include <hip/hip_runtime.h>

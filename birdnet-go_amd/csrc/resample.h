@@ -1,4 +1,4 @@
-// Polyphase resampler (resample.hip): the filter design, the one-shot / streaming launch and the bank launch (api.cpp
+// Polyphase resampler (resample.hip): the filter design, the one-shot / streaming launch and the bank launch (api_resample.cpp
 // bnhip_resampler_bank_*), which resamples one call's frames of every stream of a bank that shares (rate_in, rate_out).  The
 // bank's descriptor table travels in front of the packed PCM16 in one staging buffer.
 #pragma once

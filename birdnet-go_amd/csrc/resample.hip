@@ -64,7 +64,7 @@ void resample_design(int L, int M, double beta, int half_factor, std::vector<flo
     *half_out = half;
 }
 
-// i_base / n_base (streaming form, api.cpp bnhip_resampler_*): stream index of this launch's first output and of in[0]; the
+// i_base / n_base (streaming form, api_resample.cpp bnhip_resampler_*): stream index of this launch's first output and of in[0]; the
 // one-shot entries pass 0 / 0.  Inputs before the stream start and beyond the supplied span read as zero.
 template <bool IN_PCM16, bool OUT_PCM16>
 __global__ __launch_bounds__(256) void k_resample(const void* __restrict__ in_, void* __restrict__ out_, const float* __restrict__ table,
@@ -126,7 +126,7 @@ int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_
 }
 
 // ------------------------------------------------------------------------------------------------ bank form
-// Every stream of a bank (api.cpp bnhip_resampler_bank_*) in one launch.  A stream's input is the virtual array
+// Every stream of a bank (api_resample.cpp bnhip_resampler_bank_*) in one launch.  A stream's input is the virtual array
 //   x(n) = slab[n - n_base]                     for n_base <= n < n_base + n_hist     (history, already float32)
 //        = float32(pcm16) / 32768               for the next n_in samples             (this call's frames, back to back)
 //        = 0                                    otherwise (before the stream start, or beyond what was supplied)

@@ -6,7 +6,7 @@
 //     NaN, +-Inf or |y| > 100: state zeroed, y = x * 0.1
 //     x2 = x1; x1 = x; y2 = y1; y1 = y
 //   sum += y*y from 0.0 over every consecutive fs-sample block of the stream  (calculateRMS :427-437, before its sqrt)
-// The host takes the block sums from here (sqrt, clamp, dB and the interval statistics run in api.cpp).
+// The host takes the block sums from here (sqrt, clamp, dB and the interval statistics run in api_soundlevel.cpp).
 //
 // Mapping: one lane per (stream, band), 32 lanes per stream, so one wave holds two streams.  The bands are independent: no
 // cross-lane move sits on the recurrence.  Every lane of a stream needs the same input sample at each step: lane j of a stream

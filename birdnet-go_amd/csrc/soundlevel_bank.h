@@ -1,4 +1,4 @@
-// Batched 1/3-octave sound level monitor (api.cpp bnhip_soundlevel_bank_*): one launch runs one call's PCM16 frames of every
+// Batched 1/3-octave sound level monitor (api_soundlevel.cpp bnhip_soundlevel_bank_*): one launch runs one call's PCM16 frames of every
 // stream of a bank through the bank's band-pass biquads and returns, per band, the sum of squares of every 1-second block the
 // call completes.  The descriptor table, the band table and the packed PCM16 travel in one staging buffer.
 #pragma once

@@ -39,7 +39,7 @@ class WindowAssembler {
     // Every source with at least read_bytes buffered, starting behind the last source served (a tick that hits `cap` does not
     // starve the sources at the end of the table): window k goes to batch + k * window_bytes(), its source index to sources[k].
     int collect(uint8_t* batch, int cap, int* sources);
-    // The same in steps, for a consumer that overlaps the copies with something else (api.cpp bnhip_windows_predict_topk: the
+    // The same in steps, for a consumer that overlaps the copies with something else (api_predict.cpp bnhip_windows_predict_topk: the
     // host pipeline fills chunk c + 1's rows while chunk c is on the device).  begin: who is ready (row r <- sources[r]); holds
     // the COLLECT lock until end, which the same thread must call - the table lock is released before begin returns (the ready
     // sources are pinned by reference for the duration), so add_source / remove_source / write never wait for a device call

@@ -115,6 +115,68 @@ def test_us_guards_need_no_gpu(built_lib):
     assert not ok.any()
 
 
+def test_refusal_order_of_the_topk_and_frame_cv_entries(built_lib, tiny_blob):
+    """Which refusal wins when several arguments are bad at once, per entry, with the full text: every top-k entry on a plan-only
+    handle with k = 0, activation = 7 and (where it takes one) bit depth 12, then with the winning argument mended, one at a
+    time; the frame-CV entries with each geometry the filter's guards reject.  Nothing here touches a device."""
+    from birdnet_go_amd import stream as S
+    lib = host.load_library()
+    vp, ci = C.c_void_p, C.c_int
+    m = host.HipClassifier(tiny_blob, plan_only=True)
+    n_samples, n_classes = ci(), ci()
+    assert lib.bnhip_model_info(m._h, C.byref(n_samples), C.byref(n_classes), None) == host.BNHIP_OK
+    x = np.zeros((1, n_samples.value), np.float32)
+    lg = np.zeros((1, n_classes.value), np.float32)
+    conf, idx = (C.c_float * 64)(), (C.c_int32 * 64)()
+    w = S.NativeWindows(4, 8, max_batch=2)                  # (sets the prototypes)
+    n, src = ci(7), (ci * 4)()
+    K, ACT, DEPTH, PLAN = (b"n_clips and k must be positive", b"unknown activation",
+                           b"unsupported bit depth: 12 (supported: 16, 24, 32)", b"plan-only model cannot run")
+    post = lambda act, k, nc=n_classes.value: lib.bnhip_postprocess_topk(m._h, lg.ctypes.data, 1, nc, act, 1.0, k, conf, idx)
+    topk = lambda act, k: lib.bnhip_predict_topk(m._h, x.ctypes.data, 1, act, 1.0, k, conf, idx)
+    pcm = lambda bits, act, k: lib.bnhip_predict_pcm_topk(m._h, x.ctypes.data, bits, 1, act, 1.0, k, conf, idx)
+    tick = lambda bits, act, k: lib.bnhip_windows_predict_topk(w._h, m._h, bits, act, 1.0, k, src, C.byref(n), conf, idx, None)
+    table = [
+        # bnhip_postprocess_topk: n_clips / k, plan-only, n_classes, activation
+        (lambda: post(7, 0, n_classes.value + 1), K), (lambda: post(7, 5, n_classes.value + 1), PLAN), (lambda: post(7, 5), PLAN),
+        # bnhip_predict_topk: n_clips / k, activation, plan-only
+        (lambda: topk(7, 0), K), (lambda: topk(7, 5), ACT), (lambda: topk(0, 5), PLAN),
+        # bnhip_predict_pcm_topk: bit depth, then as bnhip_predict_topk
+        (lambda: pcm(12, 7, 0), DEPTH), (lambda: pcm(16, 7, 0), K), (lambda: pcm(16, 7, 5), ACT), (lambda: pcm(16, 0, 5), PLAN),
+        # bnhip_windows_predict_topk: bit depth, k, activation, plan-only
+        (lambda: tick(12, 7, 0), DEPTH), (lambda: tick(16, 7, 0), K), (lambda: tick(16, 7, 5), ACT), (lambda: tick(16, 0, 5), PLAN),
+        # (bnhip_predict_pcm words its bit depth refusal without the value)
+        (lambda: lib.bnhip_predict_pcm(m._h, x.ctypes.data, 12, 0, None, None), b"unsupported bit depth (supported: 16, 24, 32)"),
+    ]
+    for row, (call, text) in enumerate(table):
+        assert (call(), lib.bnhip_last_error()) == (host.E_INVALID, text), f"row {row}"
+    assert n.value == 0
+    w.close()
+    m.close()
+
+    # frame-CV: (n, sample_rate, fft_size, hop, split_hz) the guards of filter.go:21-37 reject - the host entry answers (0, false)
+    # per clip, the device entry refuses; both before bnhip_init, so also on a box without a device
+    GEOM = b"geometry rejected by the filter's guards (filter.go:21-37): use the host entry for the (0, false) answer"
+    buf = np.ones(4, np.float64)
+    for geom in [(20000, 256000, 6000, 1024, 20000),         # FFT size not a power of two
+                 (20000, 48000, 2048, 1024, 24000),          # split_hz at Nyquist
+                 (2048 + 1023, 256000, 2048, 1024, 20000),   # one frame
+                 (100, 256000, 2048, 1024, 20000)]:          # clip shorter than the FFT
+        cv, ok = np.full(3, 7.0), np.full(3, 7, np.int32)
+        g = [ci(v) for v in geom]
+        assert lib.bnhip_us_frame_cv(99, buf.ctypes.data, 3, *g, cv.ctypes.data, ok.ctypes.data) == host.BNHIP_OK, geom
+        assert (cv == 0).all() and (ok == 0).all(), geom
+        rc = lib.bnhip_us_frame_cv_device(ci(99), vp(buf.ctypes.data), ci(0), ci(3), *g, vp(buf.ctypes.data), vp(buf.ctypes.data), vp())
+        assert (rc, lib.bnhip_last_error()) == (host.E_INVALID, GEOM), geom
+    # a power-of-two FFT too large to stay in LDS is refused by both, still before any device
+    g = [ci(v) for v in (1 << 16, 256000, 1 << 14, 1024, 20000)]
+    LDS = b"FFT size exceeds the LDS-resident limit (8192)"
+    assert lib.bnhip_us_frame_cv(99, buf.ctypes.data, 3, *g, buf.ctypes.data, buf.ctypes.data) == host.E_UNSUPPORTED
+    assert lib.bnhip_last_error() == LDS
+    rc = lib.bnhip_us_frame_cv_device(ci(99), vp(buf.ctypes.data), ci(0), ci(3), *g, vp(buf.ctypes.data), vp(buf.ctypes.data), vp())
+    assert (rc, lib.bnhip_last_error()) == (host.E_UNSUPPORTED, LDS)
+
+
 # ------------------------------------------------------------------------------------------------ the cgo preamble, compiled
 GO_SHIM = os.path.join(ROOT, "birdnet-go_amd", "go", "internal", "inference", "hip", "backend_hip.go")
 
