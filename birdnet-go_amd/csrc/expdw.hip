@@ -1,6 +1,6 @@
 // gfx950 fused MBConv front half (expand 1x1 + depthwise k x k + squeeze-excite sums) and the LDS-staged plain depthwise form:
-// k_expand_dw, k_expand_dw_sk and their launchers, tile-shape tables and plan-time images.  Split out of kernels.hip (the
-// heaviest templates of the library: their own translation unit compiles in parallel with the rest).
+// k_expand_dw, k_expand_dw_sk and their launchers, tile-shape tables and plan-time images.  (The heaviest templates of
+// the library: their own translation unit compiles in parallel with the rest.)
 #include "kernels.h"
 #include "pw_common.h"
 
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void
                     if (wave + 4 * a < jtv) {
                         const float* xq = p.x + (size_t)xoff[a] + kx;
                         const float4 t0 = *reinterpret_cast<const float4*>(xq), t1 = *reinterpret_cast<const float4*>(xq + 4);
-                        const bf16x8 xh = bx1_cvt8((f32x4){t0.x, t0.y, t0.z, t0.w}, (f32x4){t1.x, t1.y, t1.z, t1.w});
+                        const bf16x8 xh = bx1_cvt8(t0, t1);
                         acc[a][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, xh, acc[a][0], 0, 0, 0);
                         acc[a][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, xh, acc[a][1], 0, 0, 0);
                     }
@@ -387,19 +387,11 @@ __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void
                     const float* xq = p.x + (size_t)xoff[a] + kx;
                     const float4 t0 = *reinterpret_cast<const float4*>(xq), t1 = *reinterpret_cast<const float4*>(xq + 4);
                     bf16x8 xh, xm, xl;
-                    bx3_split8((f32x4){t0.x, t0.y, t0.z, t0.w}, (f32x4){t1.x, t1.y, t1.z, t1.w}, &xh, &xm, &xl);
+                    bx3_split8(t0, t1, &xh, &xm, &xl);
 #pragma unroll
                     for (int t = 0; t < 2; t++) {
-                        const bf16x8 wh = __builtin_bit_cast(bf16x8, wq[t][0]), wm = __builtin_bit_cast(bf16x8, wq[t][1]),
-                                     wl = __builtin_bit_cast(bf16x8, wq[t][2]);
-                        f32x4 c = acc[a][t];
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, xm, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, xh, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xm, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh, c, 0, 0, 0);
-                        acc[a][t] = c;
+                        acc[a][t] = bx3_mfma6(acc[a][t], __builtin_bit_cast(bf16x8, wq[t][0]), __builtin_bit_cast(bf16x8, wq[t][1]),
+                                              __builtin_bit_cast(bf16x8, wq[t][2]), xh, xm, xl);
                     }
                 }
             }
@@ -596,7 +588,7 @@ __global__ __launch_bounds__(64 * NW, expdw_sk_waves(K, S, TOH, TOW, TRH, PH == 
                 for (int ns = 0; ns < NS; ns++) {
                     const float* xq = xp + (32 * ns + 8 * kq < Cin ? 32 * ns + 8 * kq : 0);
                     const float4 t0 = *reinterpret_cast<const float4*>(xq), t1 = *reinterpret_cast<const float4*>(xq + 4);
-                    xb[a][ns] = bx1_cvt8((f32x4){t0.x, t0.y, t0.z, t0.w}, (f32x4){t1.x, t1.y, t1.z, t1.w});
+                    xb[a][ns] = bx1_cvt8(t0, t1);
                 }
             } else {
                 const float* xp = xbase + (size_t)((b * p.H * p.W + ihc * p.xsh + iwc * p.xsw) * Cin);
@@ -897,18 +889,11 @@ int expdw_kp(int Cin) { return (Cin + 31) / 32 * 32; }
 std::vector<uint16_t> expdw_bx_image(const float* We /*[Cmid][Cin]*/, int Cmid, int Cin) {
     const int Cp = expdw_cp(Cmid), Kp = expdw_kp(Cin);
     std::vector<uint16_t> img((size_t)Cp * 3 * Kp, 0);
-    auto rne = [](float f) -> uint16_t {
-        unsigned u; memcpy(&u, &f, 4);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-        return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    };
-    auto widen = [](uint16_t h) { unsigned u = (unsigned)h << 16; float f; memcpy(&f, &u, 4); return f; };
     for (int n = 0; n < Cmid; n++)
         for (int k = 0; k < Cin; k++) {
-            const float x = We[(size_t)n * Cin + k];
-            const uint16_t h = rne(x); const float r = x - widen(h);
-            const uint16_t m = rne(r); const float q = r - widen(m);
-            img[((size_t)n * 3 + 0) * Kp + k] = h; img[((size_t)n * 3 + 1) * Kp + k] = m; img[((size_t)n * 3 + 2) * Kp + k] = rne(q);
+            uint16_t piece[3];
+            bx3_split_host(We[(size_t)n * Cin + k], piece);
+            for (int pl = 0; pl < 3; pl++) img[((size_t)n * 3 + pl) * Kp + k] = piece[pl];
         }
     return img;
 }

@@ -1,6 +1,6 @@
 // 8-point DFT on complex doubles in registers (decimation in frequency, three radix-2 stages with the W8 constants folded
 // in).  Outputs land in bit-reversed slots: slot s holds y[kFftR8Slot[s]].  Shared by the ultrasonic power kernel
-// (kernels.hip) and the block-cooperative STFT (stft.hip).
+// (post.hip) and the block-cooperative STFT (stft.hip).
 #pragma once
 
 namespace bnhip {

@@ -1,8 +1,8 @@
 // Generic fallback kernels: every float op of a TFLite graph that the fused BirdNET plan does not absorb still has to
 // execute (the reference call being replaced accepts any float graph: internal/inference/tflite/classifier.go:38-92).
 // These are plain bandwidth-bound gfx950 kernels - one thread per output element, coalesced along the innermost
-// (channel) dimension, 64-bit-safe indexing - with libm-accurate math: they exist for coverage, the fused kernels in
-// kernels.hip are the fast path.  Activations are [clip][per-clip elements]; views are per-clip 4-D (dims + strides in
+// (channel) dimension, 64-bit-safe indexing - with libm-accurate math: they exist for coverage, the fused kernels of
+// the other units are the fast path.  Activations are [clip][per-clip elements]; views are per-clip 4-D (dims + strides in
 // elements) plus a clip stride (0 for constants).
 #include "kernels.h"
 

@@ -1,4 +1,10 @@
-// Launch wrappers for the gfx950 kernels in kernels.hip.  All tensors are fp32, activations NHWC.
+// Launch wrappers for the gfx950 kernels of the BirdNET inference hot path, one unit per kernel family: frontend.hip, stft.hip,
+// conv.hip, pw_gemm.hip, pw_bx3.hip, pw_b16.hip, pw_ws.hip, expdw.hip, dwconv.hip, post.hip.  fp32 throughout (the reference
+// documents f16 as fatal for v2.4: internal/classifier/model_openvino.go:99-103); contractions run on the f32-input MFMA
+// (v_mfma_f32_16x16x4_f32), whose result is bit-for-bit a k-ordered fmaf chain, so numerics are those of a plain fp32 CPU kernel.
+//
+// Layouts: activations NHWC fp32; pointwise/FC weights [N][K] (TFLite OHWI with 1x1 == [Cout][Cin]),
+// depthwise weights [kh][kw][C], stem weights re-laid to [kh][kw][Cin][Cout] at plan time.
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -26,6 +32,15 @@ inline int device_cus() {
     cus[dev].store(pr.multiProcessorCount, std::memory_order_relaxed);
     return pr.multiProcessorCount;
 }
+
+// Grid of a tiled pointwise kernel: 64 wm rows x 16 nt columns per block.  pw_fill_grid (pw_gemm.hip) shrinks the tile of a small
+// call until *g, which comes in as pw_grid of the tile, has a block per CU; true: the tile changed.
+struct PwGrid { int nblk_n; unsigned nblk; };
+inline PwGrid pw_grid(int M, int N, int nt, int wm) {
+    const int nblk_n = (N + nt * 16 - 1) / (nt * 16);
+    return PwGrid{nblk_n, (unsigned)((M + 64 * wm - 1) / (64 * wm)) * (unsigned)nblk_n};
+}
+bool pw_fill_grid(int M, int N, int* nt, int* wm, PwGrid* g);
 
 template <auto Kern>
 inline void lds_limit_once(int bytes) {
@@ -238,7 +253,7 @@ int expdw_cp(int Cmid);
 void launch_expand_dw(const float* x, const float* we, const float* be, const float* wd, const float* bd, float* y,
                       float* partial, int B, int H, int W, int Cin, int Cmid, int Ho, int Wo, int k, int s, int pt,
                       int pl, int act_e, int act_d, int shape /* index into the shape table; -1 = cost model */,
-                      const StemGeom* stem /* non-null: x is the raw image and the expand is the 3x3/2 stem (see kernels.hip) */,
+                      const StemGeom* stem /* non-null: x is the raw image and the expand is the 3x3/2 stem (see expdw.hip) */,
                       hipStream_t st, const uint16_t* wep = nullptr /* non-null: phase 1 on the split-bf16 MFMA (expdw_bx_image) */,
                       int prec = 0 /* with wep: 1 = plain bf16 operands (one product) */,
                       int out_bf16 = 0 /* y is written as bf16 (bf16 activation storage; Cmid % 4 == 0) */,

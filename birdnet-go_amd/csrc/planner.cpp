@@ -952,7 +952,7 @@ struct Lowering {
     }
     // Appends k_expand_dw step f (expand half set by the caller), claiming the matched depthwise conv d and a trailing activation.
     // we: Co rows of `ld` floats, the first K used; be: expand bias or nullptr.  Every load in k_expand_dw is unconditional
-    // (see kernels.hip): the parameters go in as padded copies [Cp][Kw], [Cp], [k*k][Cp], [Cp].
+    // (see expdw.hip): the parameters go in as padded copies [Cp][Kw], [Cp], [k*k][Cp], [Cp].
     void emit_expand_dw(Step f, const DwMatch& d, const float* we, int ld, int K, int Kw, const float* be) {
         const TflOp& dw = m.ops[d.di];
         int dout = dw.outputs[0], act_d = d.act;

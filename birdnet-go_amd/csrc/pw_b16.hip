@@ -16,7 +16,7 @@
 // Block = 128 rows x 16 NT columns, 4 waves, accumulators [NT][2] x f32x4.
 // Also in this file: the six-product (fp32-equivalent) form of the same kernel for the fp32 engines, 64- or 128-row tiles
 // (template parameters SIX, WM), and k_pw_b16s - skinny projections with the whole weight matrix in registers.
-#include "pw_split.h"
+#include "pw_common.h"
 
 #include <algorithm>
 #include <atomic>
@@ -43,7 +43,7 @@ constexpr int pw_tail_group(int NT, int BM, int budget) {
     return g;
 }
 // D[i = n 4 kq + r][j = m li]: a lane holds 4 consecutive channels of row 16 (WM wave + mt) + li of the block's tile.  Bias and
-// activation exactly as pw_epilogue applies them; then, per column group: stage [BM rows][16 G columns] (row stride 16 G + 4),
+// activation are pw_epilogue's (pw_bias_act); then, per column group: stage [BM rows][16 G columns] (row stride 16 G + 4),
 // barrier, consume.
 //   mean (EPI 1): thread = (clip, channel); k_mean_partial's order - PY strided partial sums over the clip's pixels, added for
 //     y = 0 .. PY - 1 - and k_mean_finish's division.
@@ -58,35 +58,7 @@ __device__ __forceinline__ void pw_tail_epilogue(const PwParams& p, const PwTail
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
     const bool vec_ok = (p.N & 3) == 0;
-    if (p.bias) {
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-            int n = n0 + 16 * t + 4 * kq;
-            f32x4 bq = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (vec_ok && n + 3 < p.N) { float4 t4 = *reinterpret_cast<const float4*>(p.bias + n); bq = (f32x4){t4.x, t4.y, t4.z, t4.w}; }
-            else {
-#pragma unroll
-                for (int r = 0; r < 4; r++) if (n + r < p.N) bq[r] = p.bias[n + r];
-            }
-#pragma unroll
-            for (int mt = 0; mt < WM; mt++) acc[t][mt] += bq;
-        }
-    }
-    if (p.act == ACT_SWISH) {
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int mt = 0; mt < WM; mt++) acc[t][mt] = swish4(acc[t][mt]);
-    } else {
-        with_act(p.act, [&](auto f) {
-#pragma unroll
-            for (int t = 0; t < NT; t++)
-#pragma unroll
-                for (int mt = 0; mt < WM; mt++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) acc[t][mt][r] = f(acc[t][mt][r]);
-        });
-    }
+    pw_bias_act<NT, WM>(p, acc, n0, kq, vec_ok);
     const int HW = p.HW, B = p.M / HW;
     const int b0 = m0 / HW;                         // BM % HW == 0: the block's first clip
     const int clips = min(BM / HW, B - b0);         // clips of this block that exist (> 0: the grid covers M)
@@ -285,14 +257,14 @@ __global__ __launch_bounds__(64 * NW) void k_pw_b16(PwParams p, const uint16_t* 
         const int kqs = slot / BN, r = slot - kqs * BN;                                   // kqs = plane * 4 + kq
         woff[q] = (unsigned)kqs * (unsigned)Npad + (unsigned)min(n0 + r, Npad - 1);       // 16-byte units inside a slab of the image
     }
-    const u32v4* W16 = reinterpret_cast<const u32v4*>(Wimg);
+    const u32x4* W16 = reinterpret_cast<const u32x4*>(Wimg);
     const uint16_t* A16 = reinterpret_cast<const uint16_t*>(p.A);
     // scale tile loader: thread t -> clip t / 8, k quad t % 8
     const int sclip = tid >> 3, sk4 = tid & 7;
     const int nclips_blk = SCL ? (int)fdiv((unsigned)(min(m0 + BM, p.M) - 1), dhw) - b_first + 1 : 0;
 
     ASet<ABF, SCR, WM> set0, set1;
-    u32v4 wreg[WQ];
+    u32x4 wreg[WQ];
     float4 sreg;
     auto aload = [&](int sl, auto& st) {
         const int k0 = sl * 32;
@@ -301,8 +273,8 @@ __global__ __launch_bounds__(64 * NW) void k_pw_b16(PwParams p, const uint16_t* 
         for (int mt = 0; mt < WM; mt++) {
             if constexpr (ABF) {
                 const uint16_t* ap = A16 + aoff[mt] + k0;
-                st.a[mt].lo = inlo ? *reinterpret_cast<const u32v2*>(ap) : (u32v2){0u, 0u};
-                st.a[mt].hi = inhi ? *reinterpret_cast<const u32v2*>(ap + 16) : (u32v2){0u, 0u};
+                st.a[mt].lo = inlo ? *reinterpret_cast<const u32x2*>(ap) : (u32x2){0u, 0u};
+                st.a[mt].hi = inhi ? *reinterpret_cast<const u32x2*>(ap + 16) : (u32x2){0u, 0u};
             } else {
                 const float* ap = p.A + aoff[mt] + k0;
                 st.a[mt].lo = inlo ? *reinterpret_cast<const float4*>(ap) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -322,14 +294,14 @@ __global__ __launch_bounds__(64 * NW) void k_pw_b16(PwParams p, const uint16_t* 
                        ? *reinterpret_cast<const float4*>(p.ascale + (size_t)(b_first + sclip) * K + k0 + 4 * sk4)
                        : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        const u32v4* Ws = W16 + (size_t)sl * 12 * Npad;                       // 3 planes x 4 kq x Npad slots per slab; plane 0 = hi
+        const u32x4* Ws = W16 + (size_t)sl * 12 * Npad;                       // 3 planes x 4 kq x Npad slots per slab; plane 0 = hi
 #pragma unroll
         for (int q = 0; q < WQ; q++)
             if (tid + NTHR * q < WSLOTS) wreg[q] = Ws[woff[q]];
     };
     auto wstore = [&](int buf) {
         float* base = lds + buf * OBUF;
-        u32v4* Wl = reinterpret_cast<u32v4*>(base);
+        u32x4* Wl = reinterpret_cast<u32x4*>(base);
 #pragma unroll
         for (int q = 0; q < WQ; q++)
             if (tid + NTHR * q < WSLOTS) Wl[tid + NTHR * q] = wreg[q];
@@ -366,23 +338,23 @@ __global__ __launch_bounds__(64 * NW) void k_pw_b16(PwParams p, const uint16_t* 
         B16_T(9 + 4 * sl);                                 // next weight tile in LDS (its global loads had landed)
         if (sl + 2 < nslab) wload(sl + 2);
         const float* obuf = lds + (sl & 1) * OBUF;
-        b16x8 ah[WM], am[SIX ? WM : 1], al[SIX ? WM : 1];
+        bf16x8 ah[WM], am[SIX ? WM : 1], al[SIX ? WM : 1];
 #pragma unroll
         for (int mt = 0; mt < WM; mt++) {
             if constexpr (ABF && !SC) {
-                ah[mt] = __builtin_bit_cast(b16x8, (u32v4){st.a[mt].lo[0], st.a[mt].lo[1], st.a[mt].hi[0], st.a[mt].hi[1]});
+                ah[mt] = __builtin_bit_cast(bf16x8, (u32x4){st.a[mt].lo[0], st.a[mt].lo[1], st.a[mt].hi[0], st.a[mt].hi[1]});
             } else {
                 float4 v0, v1;
                 avals(mt, st, obuf + WSLOTS * 4, v0, v1);
-                if constexpr (SIX) b16_split8(v0, v1, &ah[mt], &am[SIX ? mt : 0], &al[SIX ? mt : 0]);
-                else ah[mt] = b16_cvt8(v0, v1);
+                if constexpr (SIX) bx3_split8(v0, v1, &ah[mt], &am[SIX ? mt : 0], &al[SIX ? mt : 0]);
+                else ah[mt] = bx1_cvt8(v0, v1);
             }
         }
         if (sl + 2 < nslab) aload(sl + 2, st);
-        const u32v4* Wl = reinterpret_cast<const u32v4*>(obuf);
+        const u32x4* Wl = reinterpret_cast<const u32x4*>(obuf);
         if constexpr (SIX) {
             // weight fragments of tile t + 1 are requested before the MFMAs of tile t
-            u32v4 wfr[2][3];
+            u32x4 wfr[2][3];
 #pragma unroll
             for (int pl3 = 0; pl3 < 3; pl3++) wfr[0][pl3] = Wl[(pl3 * 4 + kq) * BN + li];
 #pragma unroll
@@ -391,25 +363,16 @@ __global__ __launch_bounds__(64 * NW) void k_pw_b16(PwParams p, const uint16_t* 
 #pragma unroll
                     for (int pl3 = 0; pl3 < 3; pl3++) wfr[(t + 1) & 1][pl3] = Wl[(pl3 * 4 + kq) * BN + 16 * (t + 1) + li];
                 }
-                const b16x8 wh = __builtin_bit_cast(b16x8, wfr[t & 1][0]);
-                const b16x8 wm = __builtin_bit_cast(b16x8, wfr[t & 1][1]);
-                const b16x8 wl = __builtin_bit_cast(b16x8, wfr[t & 1][2]);
+                const bf16x8 wh = __builtin_bit_cast(bf16x8, wfr[t & 1][0]);
+                const bf16x8 wm = __builtin_bit_cast(bf16x8, wfr[t & 1][1]);
+                const bf16x8 wl = __builtin_bit_cast(bf16x8, wfr[t & 1][2]);
 #pragma unroll
-                for (int mt = 0; mt < WM; mt++) {
-                    f32x4 c = acc[t][mt];                        // smallest terms first (k_pw_bx3's order)
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, ah[mt], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, al[SIX ? mt : 0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, am[SIX ? mt : 0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, ah[mt], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, am[SIX ? mt : 0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, ah[mt], c, 0, 0, 0);
-                    acc[t][mt] = c;
-                }
+                for (int mt = 0; mt < WM; mt++) acc[t][mt] = bx3_mfma6(acc[t][mt], wh, wm, wl, ah[mt], am[SIX ? mt : 0], al[SIX ? mt : 0]);
             }
         } else {
-            b16x8 wf[NT];
+            bf16x8 wf[NT];
 #pragma unroll
-            for (int t = 0; t < NT; t++) wf[t] = __builtin_bit_cast(b16x8, Wl[kq * BN + 16 * t + li]);
+            for (int t = 0; t < NT; t++) wf[t] = __builtin_bit_cast(bf16x8, Wl[kq * BN + 16 * t + li]);
 #pragma unroll
             for (int t = 0; t < NT; t++)
 #pragma unroll
@@ -458,12 +421,12 @@ __global__ __launch_bounds__(256) void k_pw_b16s(PwParams p, const uint16_t* __r
     const int t0 = wave_g * tiles_per_wave, t1 = min(t0 + tiles_per_wave, ntiles);
     if (t0 >= t1) return;
     // weights: plane 0 of the image, slot (slab, kq, row 16 t + li)
-    const u32v4* W16 = reinterpret_cast<const u32v4*>(Wimg);
-    b16x8 wf[NS][NT];
+    const u32x4* W16 = reinterpret_cast<const u32x4*>(Wimg);
+    bf16x8 wf[NS][NT];
 #pragma unroll
     for (int ns = 0; ns < NS; ns++)
 #pragma unroll
-        for (int t = 0; t < NT; t++) wf[ns][t] = __builtin_bit_cast(b16x8, W16[((size_t)ns * 12 + kq) * Npad + min(16 * t + li, Npad - 1)]);
+        for (int t = 0; t < NT; t++) wf[ns][t] = __builtin_bit_cast(bf16x8, W16[((size_t)ns * 12 + kq) * Npad + min(16 * t + li, Npad - 1)]);
     f32x4 bias[NT];
 #pragma unroll
     for (int t = 0; t < NT; t++) {
@@ -482,8 +445,8 @@ __global__ __launch_bounds__(256) void k_pw_b16s(PwParams p, const uint16_t* __r
 #pragma unroll
         for (int ns = 0; ns < NS; ns++) {
             if constexpr (ABF) {
-                dst[ns].lo = inlo[ns] ? *reinterpret_cast<const u32v2*>(A16 + off + 32 * ns) : (u32v2){0u, 0u};
-                dst[ns].hi = inhi[ns] ? *reinterpret_cast<const u32v2*>(A16 + off + 32 * ns + 16) : (u32v2){0u, 0u};
+                dst[ns].lo = inlo[ns] ? *reinterpret_cast<const u32x2*>(A16 + off + 32 * ns) : (u32x2){0u, 0u};
+                dst[ns].hi = inhi[ns] ? *reinterpret_cast<const u32x2*>(A16 + off + 32 * ns + 16) : (u32x2){0u, 0u};
             } else {
                 dst[ns].lo = inlo[ns] ? *reinterpret_cast<const float4*>(p.A + off + 32 * ns) : make_float4(0.f, 0.f, 0.f, 0.f);
                 dst[ns].hi = inhi[ns] ? *reinterpret_cast<const float4*>(p.A + off + 32 * ns + 16) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -512,9 +475,9 @@ __global__ __launch_bounds__(256) void k_pw_b16s(PwParams p, const uint16_t* __r
         for (int t = 0; t < NT; t++) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ns = 0; ns < NS; ns++) {
-            b16x8 af;
+            bf16x8 af;
             if constexpr (ABF && !SC) {
-                af = __builtin_bit_cast(b16x8, (u32v4){cur[ns].lo[0], cur[ns].lo[1], cur[ns].hi[0], cur[ns].hi[1]});
+                af = __builtin_bit_cast(bf16x8, (u32x4){cur[ns].lo[0], cur[ns].lo[1], cur[ns].hi[0], cur[ns].hi[1]});
             } else {
                 float4 v0, v1;
                 if constexpr (ABF) { v0 = b16_unpack4(cur[ns].lo); v1 = b16_unpack4(cur[ns].hi); }
@@ -524,7 +487,7 @@ __global__ __launch_bounds__(256) void k_pw_b16s(PwParams p, const uint16_t* __r
                     v0.x *= s0.x; v0.y *= s0.y; v0.z *= s0.z; v0.w *= s0.w;
                     v1.x *= s1.x; v1.y *= s1.y; v1.z *= s1.z; v1.w *= s1.w;
                 }
-                af = b16_cvt8(v0, v1);
+                af = bx1_cvt8(v0, v1);
             }
 #pragma unroll
             for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ns][t], af, acc[t], 0, 0, 0);

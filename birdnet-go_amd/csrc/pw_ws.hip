@@ -20,51 +20,41 @@
 // block, the slab's weight tile double-buffered in LDS, A through a four-slab register ring, the block's squeeze-excite rows
 // resident in LDS - was built for the long-K projections in the same round, bit-identical, and measured 10-25 % SLOWER than the
 // best tiled candidate on every projection and on the dense head: profiles/r05_pw_lab_all_candidates.txt; removed)
-#include "pw_split.h"
+#include "pw_common.h"
 
 #include <algorithm>
 #include <atomic>
 
 namespace bnhip {
 
-// exact split of a pair of fp32 values into three packed bf16 pairs (k_pw_bx3's decomposition: hi = RNE(x), mid = RNE(x - hi),
-// lo = RNE(x - hi - mid); the subtractions are exact)
-__device__ __forceinline__ void ws_split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    const f32x2 v = {x0, x1};
-    const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v, b16x2));
-    const f32x2 r = {b16_sub(v[0], __uint_as_float(hb << 16)), b16_sub(v[1], __uint_as_float(hb & 0xffff0000u))};
-    const unsigned mb = __builtin_bit_cast(unsigned, __builtin_convertvector(r, b16x2));
-    const f32x2 t = {b16_sub(r[0], __uint_as_float(mb << 16)), b16_sub(r[1], __uint_as_float(mb & 0xffff0000u))};
-    h = hb; m = mb; l = __builtin_bit_cast(unsigned, __builtin_convertvector(t, b16x2));
-}
 // pair q (0..3) of a lane's eight values of a slab: (lo.x lo.y) (lo.z lo.w) (hi.x hi.y) (hi.z hi.w)
 __device__ __forceinline__ void ws_pair(const float4& lo, const float4& hi, int q, float& x0, float& x1) {
     x0 = q == 0 ? lo.x : q == 1 ? lo.z : q == 2 ? hi.x : hi.z;
     x1 = q == 0 ? lo.y : q == 1 ? lo.w : q == 2 ? hi.y : hi.w;
 }
 
-struct WsFrag { u32v4 h, m, l; };      // a 16 x 32 operand fragment as three bf16 planes (one-product kernels use h only)
+struct WsFrag { u32x4 h, m, l; };      // a 16 x 32 operand fragment as three bf16 planes (one-product kernels use h only)
 
-// the six products of a (column tile, slab) on the WM accumulators of a tile pair, k_pw_bx3's order per accumulator
-// (smallest terms first), the chains interleaved so that an MFMA never reads the result of the one issued just before it
+// the six products of a (column tile, slab) on the WM accumulators of a tile pair: bx3_mfma6's order (pw_common.h) per accumulator,
+// the chains interleaved so that an MFMA never reads the result of the one issued just before it
 template <int WM, bool SIX>
-__device__ __forceinline__ void ws_mfma(f32x4 (&c)[WM], const u32v4 (&w)[SIX ? 3 : 1], const WsFrag (&f)[2]) {
-    const b16x8 wh = __builtin_bit_cast(b16x8, w[0]);
+__device__ __forceinline__ void ws_mfma(f32x4 (&c)[WM], const u32x4 (&w)[SIX ? 3 : 1], const WsFrag (&f)[2]) {
+    const bf16x8 wh = __builtin_bit_cast(bf16x8, w[0]);
     if constexpr (SIX) {
-        const b16x8 wm = __builtin_bit_cast(b16x8, w[1]), wl = __builtin_bit_cast(b16x8, w[2]);
+        const bf16x8 wm = __builtin_bit_cast(bf16x8, w[1]), wl = __builtin_bit_cast(bf16x8, w[2]);
 #pragma unroll
-        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, __builtin_bit_cast(b16x8, f[mt].h), c[mt], 0, 0, 0);
+        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, __builtin_bit_cast(bf16x8, f[mt].h), c[mt], 0, 0, 0);
 #pragma unroll
-        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, __builtin_bit_cast(b16x8, f[mt].l), c[mt], 0, 0, 0);
+        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, __builtin_bit_cast(bf16x8, f[mt].l), c[mt], 0, 0, 0);
 #pragma unroll
-        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, __builtin_bit_cast(b16x8, f[mt].m), c[mt], 0, 0, 0);
+        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, __builtin_bit_cast(bf16x8, f[mt].m), c[mt], 0, 0, 0);
 #pragma unroll
-        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, __builtin_bit_cast(b16x8, f[mt].h), c[mt], 0, 0, 0);
+        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, __builtin_bit_cast(bf16x8, f[mt].h), c[mt], 0, 0, 0);
 #pragma unroll
-        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, __builtin_bit_cast(b16x8, f[mt].m), c[mt], 0, 0, 0);
+        for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, __builtin_bit_cast(bf16x8, f[mt].m), c[mt], 0, 0, 0);
     }
 #pragma unroll
-    for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, __builtin_bit_cast(b16x8, f[mt].h), c[mt], 0, 0, 0);
+    for (int mt = 0; mt < WM; mt++) c[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, __builtin_bit_cast(bf16x8, f[mt].h), c[mt], 0, 0, 0);
 }
 
 // bias + activation + residual + store of one accumulator quad: row m, channels n .. n + 3 (bias: nullable), pw_epilogue's
@@ -108,7 +98,7 @@ __global__ __launch_bounds__(64 * NW) void k_pw_ws(PwParams p, const uint16_t* _
     constexpr int BN = 16 * NT, NP = SIX ? 3 : 1;
     constexpr int WSLOTS = NS * NP * 4 * BN;                 // 16-byte slots: [slab][plane][kq][column]
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
-    u32v4* Wl = reinterpret_cast<u32v4*>(ws_lds);
+    u32x4* Wl = reinterpret_cast<u32x4*>(ws_lds);
     float* Bl = reinterpret_cast<float*>(ws_lds + (size_t)WSLOTS * 16);       // the block's bias columns
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);         // (uniform: the tile bookkeeping below stays on the scalar unit)
@@ -128,11 +118,11 @@ __global__ __launch_bounds__(64 * NW) void k_pw_ws(PwParams p, const uint16_t* _
 #define WS_T() do { } while (0)
 #endif
     WS_T();
-    const u32v4* W16 = reinterpret_cast<const u32v4*>(Wimg);
+    const u32x4* W16 = reinterpret_cast<const u32x4*>(Wimg);
     {   // the block's weight columns: every load of a thread requested before the first store (a load - store loop paid a memory
         // latency per trip: 11 k of a wave's 66 k cycles in the first timing of this kernel)
         constexpr int WQ = (WSLOTS + 64 * NW - 1) / (64 * NW);
-        u32v4 wv[WQ];
+        u32x4 wv[WQ];
 #pragma unroll
         for (int i = 0; i < WQ; i++) {
             const int slot = min(tid + 64 * NW * i, WSLOTS - 1);
@@ -169,9 +159,9 @@ __global__ __launch_bounds__(64 * NW) void k_pw_ws(PwParams p, const uint16_t* _
         for (int mt = 0; mt < 2; mt++) {
             if constexpr (ABF) {
                 const uint16_t* ap = A16 + off[mt];
-                const u32v2 lo = *reinterpret_cast<const u32v2*>(ap + klo), hi = *reinterpret_cast<const u32v2*>(ap + khi);
-                dst[mt].lo = inlo ? lo : (u32v2){0u, 0u};
-                dst[mt].hi = inhi ? hi : (u32v2){0u, 0u};
+                const u32x2 lo = *reinterpret_cast<const u32x2*>(ap + klo), hi = *reinterpret_cast<const u32x2*>(ap + khi);
+                dst[mt].lo = inlo ? lo : (u32x2){0u, 0u};
+                dst[mt].hi = inhi ? hi : (u32x2){0u, 0u};
             } else {
                 const float* ap = p.A + off[mt];
                 const float4 lo = *reinterpret_cast<const float4*>(ap + klo), hi = *reinterpret_cast<const float4*>(ap + khi);
@@ -187,14 +177,14 @@ __global__ __launch_bounds__(64 * NW) void k_pw_ws(PwParams p, const uint16_t* _
             float x0, x1;
             ws_pair(a.lo, a.hi, q, x0, x1);
             unsigned h, m, l;
-            ws_split2(x0, x1, h, m, l);
+            bx3_split2(x0, x1, h, m, l);
             f.h[q] = h; f.m[q] = m; f.l[q] = l;
         } else if (q == 0) {
-            if constexpr (ABF) f.h = (u32v4){a.lo[0], a.lo[1], a.hi[0], a.hi[1]};
-            else f.h = __builtin_bit_cast(u32v4, b16_cvt8(a.lo, a.hi));
+            if constexpr (ABF) f.h = (u32x4){a.lo[0], a.lo[1], a.hi[0], a.hi[1]};
+            else f.h = __builtin_bit_cast(u32x4, bx1_cvt8(a.lo, a.hi));
         }
     };
-    auto wfrag = [&](int idx, u32v4 (&dst)[NP]) {            // step idx = slab * NT + column tile
+    auto wfrag = [&](int idx, u32x4 (&dst)[NP]) {            // step idx = slab * NT + column tile
         const int ns = idx / NT, t = idx - ns * NT;
 #pragma unroll
         for (int pl = 0; pl < NP; pl++) dst[pl] = Wl[((ns * NP + pl) * 4 + kq) * BN + 16 * t + li];
@@ -225,7 +215,7 @@ __global__ __launch_bounds__(64 * NW) void k_pw_ws(PwParams p, const uint16_t* _
         for (int t = 0; t < NT; t++)
 #pragma unroll
             for (int mt = 0; mt < WM; mt++) acc[t][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        u32v4 wfr[2][NP];
+        u32x4 wfr[2][NP];
         wfrag(0, wfr[0]);
 #pragma unroll
         for (int ns = 0; ns < NS; ns++) {
@@ -366,7 +356,7 @@ void launch_pw_ws(const PwParams& p, const uint16_t* Wimg, int Npad, hipStream_t
 // do not depend on the call's size.
 template <int NT, bool SC, int DW>
 __global__ __launch_bounds__(256) void k_pw_lat(PwParams p, const uint16_t* __restrict__ Wimg, int Npad, int ngroups, FDiv dhw) {
-    __shared__ __attribute__((aligned(16))) u32v4 frl[2][4][3][64];       // [group parity][slab of the group][plane][lane]
+    __shared__ __attribute__((aligned(16))) u32x4 frl[2][4][3][64];       // [group parity][slab of the group][plane][lane]
     const int lane = threadIdx.x & 63, li = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int gblocks = (ngroups + 3) >> 2;                  // blocks per row tile
@@ -377,7 +367,7 @@ __global__ __launch_bounds__(256) void k_pw_lat(PwParams p, const uint16_t* __re
     const int m = min(16 * rt + li, p.M - 1), n0 = 16 * NT * cg;
     const float* arow = p.A + (size_t)m * K + 4 * kq;
     const float* srow = SC ? p.ascale + (size_t)fdiv((unsigned)m, dhw) * K + 4 * kq : nullptr;
-    const u32v4* W16 = reinterpret_cast<const u32v4*>(Wimg);
+    const u32x4* W16 = reinterpret_cast<const u32x4*>(Wimg);
     unsigned wcol[NT];
 #pragma unroll
     for (int t = 0; t < NT; t++) wcol[t] = (unsigned)kq * (unsigned)Npad + (unsigned)min(n0 + 16 * t + li, Npad - 1);
@@ -396,9 +386,9 @@ __global__ __launch_bounds__(256) void k_pw_lat(PwParams p, const uint16_t* __re
             s_.shi = *reinterpret_cast<const float4*>(srow + khi);
         }
     };
-    u32v4 wst[DW][NT][3];
-    auto wload = [&](int sl, u32v4 (&dst)[NT][3]) {
-        const u32v4* Ws = W16 + (size_t)sl * 12 * Npad;
+    u32x4 wst[DW][NT][3];
+    auto wload = [&](int sl, u32x4 (&dst)[NT][3]) {
+        const u32x4* Ws = W16 + (size_t)sl * 12 * Npad;
 #pragma unroll
         for (int t = 0; t < NT; t++)
 #pragma unroll
@@ -416,7 +406,7 @@ __global__ __launch_bounds__(256) void k_pw_lat(PwParams p, const uint16_t* __re
             float x0, x1;
             ws_pair(v0, v1, q, x0, x1);
             unsigned h, mm, l;
-            ws_split2(x0, x1, h, mm, l);
+            bx3_split2(x0, x1, h, mm, l);
             f.h[q] = h; f.m[q] = mm; f.l[q] = l;
         }
         frl[par][wave][0][lane] = f.h; frl[par][wave][1][lane] = f.m; frl[par][wave][2][lane] = f.l;

@@ -2,7 +2,7 @@
 // boundaries of every K slab, first 64 logical blocks) and runs it on the late-layer shapes at batch 256.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form -DPW_TRACE -I birdnet-go_amd/csrc \
 //         -o tools/ubench/pw_trace.bin tools/ubench/pw_trace.hip
-#include "../../birdnet-go_amd/csrc/kernels.hip"
+#include "../../birdnet-go_amd/csrc/pw_gemm.hip"
 
 #include <vector>
 using namespace bnhip;
