@@ -37,7 +37,7 @@ ResamplePlan resample_plan(int rate_in, int rate_out, std::vector<float>* table)
     ResamplePlan p;
     p.L = rate_out / g;
     p.M = rate_in / g;
-    if (table) resample_design(p.L, p.M, 5.0, 10, table, &p.T, &p.half);
+    if (table) resample_design(p.L, p.M, RESAMPLE_BETA, RESAMPLE_HALF_FACTOR, table, &p.T, &p.half);
     return p;
 }
 

@@ -1,9 +1,53 @@
-// 8-point DFT on complex doubles in registers (decimation in frequency, three radix-2 stages with the W8 constants folded
+// Register FFT building blocks.
+// fft_regs<P>: radix-2 DIT on P = 2 / 4 / 8 / 16 complex values, outputs in natural order (the four-step STFT of stft.hip, the closing
+// radix-2 / radix-4 pass of spectrogram.hip).
+// fft_r8_dft8: 8-point DFT on complex doubles in registers (decimation in frequency, three radix-2 stages with the W8 constants folded
 // in).  Outputs land in bit-reversed slots: slot s holds y[kFftR8Slot[s]].  Shared by the ultrasonic power kernel
-// (post.hip) and the block-cooperative STFT (stft.hip).
+// (post.hip) and the spectrogram image kernel (spectrogram.hip).
 #pragma once
 
 namespace bnhip {
+
+// In-place radix-2 DIT on P complex doubles held in registers; every index is a compile-time constant after unrolling.
+template <int P, typename R>
+__device__ __forceinline__ void fft_regs(R (&re)[P], R (&im)[P]) {
+    // cos / sin of 2 pi t / 16, t = 0..7 (P <= 16 uses a stride into this table)
+    constexpr double C16[8] = {1.0, 0.92387953251128673848, 0.70710678118654752440, 0.38268343236508977173,
+                               0.0, -0.38268343236508977173, -0.70710678118654752440, -0.92387953251128673848};
+    constexpr double S16[8] = {0.0, 0.38268343236508977173, 0.70710678118654752440, 0.92387953251128673848,
+                               1.0, 0.92387953251128673848, 0.70710678118654752440, 0.38268343236508977173};
+    constexpr int LOG = P == 16 ? 4 : (P == 8 ? 3 : (P == 4 ? 2 : 1));
+#pragma unroll
+    for (int i = 0; i < P; i++) {
+        int j = 0;
+#pragma unroll
+        for (int bit = 0; bit < LOG; bit++) j |= ((i >> bit) & 1) << (LOG - 1 - bit);
+        if (i < j) { R t = re[i]; re[i] = re[j]; re[j] = t; t = im[i]; im[i] = im[j]; im[j] = t; }
+    }
+#pragma unroll
+    for (int len = 2; len <= P; len <<= 1) {
+        const int half = len >> 1, step = 16 / len;
+#pragma unroll
+        for (int i = 0; i < P; i += len) {
+#pragma unroll
+            for (int k = 0; k < half; k++) {
+                const R wr = (R)C16[k * step], wi = (R)-S16[k * step];      // e^{-2 pi i k / len}
+                const R xr = re[i + k + half], xi = im[i + k + half];
+                const R ur = re[i + k], ui = im[i + k];
+                if (k == 0) {                                               // w = 1
+                    re[i + k] = ur + xr; im[i + k] = ui + xi; re[i + k + half] = ur - xr; im[i + k + half] = ui - xi;
+                } else if (2 * k == half) {                                 // w = -i
+                    re[i + k] = ur + xi; im[i + k] = ui - xr; re[i + k + half] = ur - xi; im[i + k + half] = ui + xr;
+                } else {                                                    // explicit FMAs (contraction is off file-wide)
+                    re[i + k] = fma(xr, wr, fma(-xi, wi, ur));
+                    im[i + k] = fma(xr, wi, fma(xi, wr, ui));
+                    re[i + k + half] = fma(-xr, wr, fma(xi, wi, ur));
+                    im[i + k + half] = fma(-xr, wi, fma(-xi, wr, ui));
+                }
+            }
+        }
+    }
+}
 
 __device__ __forceinline__ void fft_r8_dft8(double (&re)[8], double (&im)[8]) {
     constexpr double R = 0.70710678118654752440;

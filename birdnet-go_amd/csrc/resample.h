@@ -12,6 +12,9 @@ namespace bnhip {
 
 // the [L][T] phase table of rate ratio L/M (filter half-length half_factor * max(L, M) taps)
 void resample_design(int L, int M, double beta, int half_factor, std::vector<float>* table, int* T_out, int* half_out);
+// the design every entry point uses
+constexpr double RESAMPLE_BETA = 5.0;
+constexpr int RESAMPLE_HALF_FACTOR = 10;
 
 // LDS a launch of this geometry needs (phase table + worst-case input span of 256 outputs); more than RESAMPLE_LDS_MAX does not run
 size_t resample_lds(int L, int M, int T);

@@ -120,7 +120,7 @@ int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_
     if (in_pcm16 && out_pcm16) BN_RS(true, true);
     else if (!in_pcm16 && out_pcm16) BN_RS(false, true);
     else if (!in_pcm16 && !out_pcm16) BN_RS(false, false);
-    else return -1;
+    else BN_RS(true, false);                                        // (the spectrogram entry: PCM in, the float samples it renders out)
 #undef BN_RS
     return 0;
 }

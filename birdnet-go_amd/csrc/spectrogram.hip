@@ -1,0 +1,255 @@
+// Detection-clip spectrogram images for gfx950: PCM -> framed, windowed real FFT (fp64) -> mean power of a column's K frames ->
+// dB -> level index 0..255 -> uint8 [n_clips][H][W], Nyquist in row 0.  The rendering spec (frame centres, normalisation, level
+// rule) is DESIGN.md §9; tests/specref.py restates it in numpy float64.
+//
+// Reference path being replaced: the `sox ... rate 24k spectrogram -x W -y H -z R -r` child process per clip of
+// internal/spectrogram/generator.go:425-530.  sox is not in the reference tree: pixel values are this project's spec, not sox's.
+//
+// Mapping.  A block of 256 threads owns T consecutive columns of one clip (T = 32 / 16 / 8 for N <= 1024 / 2048 / 4096) and
+// walks their T * K frames in rounds of up to F consecutive frames (F from the LDS budget, spectrogram_plan):
+//   1. the round's sample span [centre of its first frame - N/2, centre of its last + N/2) comes from HBM once, as int16 or
+//      float32, and goes to LDS as doubles (frames overlap: at "lg" with a 15 s clip the hop is 351 against N = 1024);
+//   2. each frame is windowed (the caller's table; the kernel computes no window) and packed into N/2 complex points
+//      z[i] = x[2i] w[2i] + i x[2i+1] w[2i+1];
+//   3. the F packed frames are transformed together, in place, by radix-8 decimation-in-frequency passes (fft_r8_dft8, one
+//      butterfly per thread and step, the block's threads spread over all frames of the round) closed by one radix-2 / radix-4 pass
+//      (fft_regs) when N/2 is not a power of 8 - the pass structure of k_us_frame_power8 with the length a parameter.  Z[k] ends
+//      up at the mixed-radix digit-reversed index;
+//   4. thread b recovers X[b] = E[b] + W_N^b O[b] from Z[b] and conj(Z[N/2 - b]), adds the K frame powers of a column in frame
+//      order (a column whose K frames span several rounds carries its sum in LDS) and writes the level index into the block's
+//      H x T byte tile;
+//   5. the tile leaves as runs of T contiguous bytes per image row.
+// A round never splits a column unless K > F, and then it holds frames of that one column only, so the sum order is k = 0..K-1.
+#include "spectrogram.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <type_traits>
+
+#include "fft_r8.h"
+#include "kernels.h"
+
+namespace bnhip {
+
+#define SPEC_PHYS(i) ((i) + ((i) >> 3))      // one pad per 8 doubles, as US8_PHYS: the last radix-8 pass walks with stride 8
+constexpr int SPEC_THREADS = 256;
+constexpr int SPEC_FMAX = 64;                // frames per round at most (the per-frame offset table's size)
+
+struct SpecParams {
+    const void* samples;
+    const double2* tw;         // [N/2] (cos, -sin)(2 pi j / N)
+    const double* window;      // [N]
+    uint8_t* image;
+    int n, W, H, N, K, T, F, span_cap;
+    int log2n2, npass, lg[4];  // N/2 = 2^log2n2 = product of the passes' radices 2^lg[i]
+    double pscale, top_db, range_db;
+};
+
+// where Z[k] lies after the passes: digit i of k (radix 2^lg[i], least significant first) becomes the digit of weight N/2 / (r_0 .. r_i)
+__device__ __forceinline__ int spec_pos(const SpecParams& p, int k) {
+    int pos = 0, rem = p.log2n2;
+    for (int i = 0; i < p.npass; i++) {
+        rem -= p.lg[i];
+        pos |= (k & ((1 << p.lg[i]) - 1)) << rem;
+        k >>= p.lg[i];
+    }
+    return pos;
+}
+
+// closing pass (span 1: no twiddles): R consecutive points, natural-order outputs
+template <int R>
+__device__ __forceinline__ void spec_pass_small(double* zr, double* zi, int base) {
+    double re[R], im[R];
+#pragma unroll
+    for (int m = 0; m < R; m++) { const int i = SPEC_PHYS(base + m); re[m] = zr[i]; im[m] = zi[i]; }
+    fft_regs<R, double>(re, im);
+#pragma unroll
+    for (int m = 0; m < R; m++) { const int i = SPEC_PHYS(base + m); zr[i] = re[m]; zi[i] = im[m]; }
+}
+
+template <typename S>
+__global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char spec_sm[];
+    const int N = p.N, N2 = N >> 1, H = p.H, FS = SPEC_PHYS(N2);
+    double* work = reinterpret_cast<double*>(spec_sm);           // [F][re | im][FS]
+    double* span = work + (size_t)p.F * 2 * FS;                  // [span_cap]
+    double* acc = span + p.span_cap;                             // [H] power sums of a column that spans rounds
+    int* foff = reinterpret_cast<int*>(acc + H);                 // [SPEC_FMAX] first sample of each frame of the round, in span
+    uint8_t* img = reinterpret_cast<uint8_t*>(foff + SPEC_FMAX); // [H][T]
+    const int tid = threadIdx.x, clip = blockIdx.y;
+    const int c0 = blockIdx.x * p.T, ncol = min(p.T, p.W - c0);
+    const S* x = static_cast<const S*>(p.samples) + (size_t)clip * p.n;
+    const long long den = 2LL * p.K * p.W;
+    const double2* win2 = reinterpret_cast<const double2*>(p.window);
+
+    int c = 0, k0 = 0;
+    while (c < ncol) {
+        int Cr, Kr;
+        if (p.K <= p.F) { Cr = min(p.F / p.K, ncol - c); Kr = p.K; }
+        else { Cr = 1; Kr = min(p.F, p.K - k0); }
+        const int nf = Cr * Kr;
+        // ---- 1. the round's span: frame g = column * K + k is centred at floor((2 g + 1) n / (2 K W))
+        const long long g0 = (long long)(c0 + c) * p.K + k0;
+        const long long s_lo = ((2 * g0 + 1) * p.n) / den - N2;
+        const long long s_hi = ((2 * (g0 + nf - 1) + 1) * p.n) / den + N2;
+        const int len = (int)min(s_hi - s_lo, (long long)p.span_cap);
+        if (tid < nf) foff[tid] = (int)(((2 * (g0 + tid) + 1) * p.n) / den - N2 - s_lo);
+        for (int i = tid; i < len; i += SPEC_THREADS) {
+            const long long s = s_lo + i;
+            double v = 0.0;
+            if (s >= 0 && s < p.n) v = std::is_same<S, int16_t>::value ? (double)x[s] / 32768.0 : (double)x[s];
+            span[i] = v;
+        }
+        __syncthreads();
+        // ---- 2. window and pack
+        for (int idx = tid; idx < (nf << p.log2n2); idx += SPEC_THREADS) {
+            const int f = idx >> p.log2n2, i = idx & (N2 - 1), o = foff[f] + 2 * i;
+            const double2 w = win2[i];
+            double* zr = work + (size_t)f * 2 * FS;
+            zr[SPEC_PHYS(i)] = (o < len ? span[o] : 0.0) * w.x;
+            zr[FS + SPEC_PHYS(i)] = (o + 1 < len ? span[o + 1] : 0.0) * w.y;
+        }
+        __syncthreads();
+        // ---- 3. in-place DIF passes over all frames of the round
+        int lgL = p.log2n2;                                          // the pass splits blocks of 2^lgL points
+        for (int ps = 0; ps < p.npass; ps++) {
+            const int lr = p.lg[ps], sp = 1 << (lgL - lr);           // radix 2^lr, butterfly stride sp
+            const int per = p.log2n2 - lr;                           // log2 butterflies per frame
+            for (int u = tid; u < (nf << per); u += SPEC_THREADS) {
+                const int f = u >> per, t = u & ((1 << per) - 1);
+                const int j = t & (sp - 1), base = ((t - j) << lr) + j;
+                double* zr = work + (size_t)f * 2 * FS;
+                double* zi = zr + FS;
+                if (lr == 3) {
+                    double re[8], im[8];
+#pragma unroll
+                    for (int m = 0; m < 8; m++) { const int i = SPEC_PHYS(base + m * sp); re[m] = zr[i]; im[m] = zi[i]; }
+                    fft_r8_dft8(re, im);
+                    const int tstep = j << (p.log2n2 + 1 - lgL);     // W_L^(j q) = W_N^(q * tstep)
+#pragma unroll
+                    for (int sl = 0; sl < 8; sl++) {
+                        const int q = kFftR8Slot[sl];
+                        double yr = re[sl], yi = im[sl];
+                        if (q != 0 && sp > 1) {
+                            const int e = q * tstep;                 // < 7 N / 8
+                            double2 w = p.tw[e & (N2 - 1)];
+                            if (e >= N2) { w.x = -w.x; w.y = -w.y; }
+                            const double tr = yr * w.x - yi * w.y, ti = yr * w.y + yi * w.x;
+                            yr = tr; yi = ti;
+                        }
+                        const int i = SPEC_PHYS(base + q * sp);
+                        zr[i] = yr; zi[i] = yi;
+                    }
+                } else if (lr == 2) spec_pass_small<4>(zr, zi, base);
+                else spec_pass_small<2>(zr, zi, base);
+            }
+            __syncthreads();
+            lgL -= lr;
+        }
+        // ---- 4. spectrum of the real frames, power sums, level indices
+        const bool first = k0 == 0, last = k0 + Kr == p.K;
+        for (int lc = 0; lc < Cr; lc++)
+            for (int b = tid; b < H; b += SPEC_THREADS) {
+                double sum = first ? 0.0 : acc[b];
+                const int ia = SPEC_PHYS(spec_pos(p, b & (N2 - 1))), ib = SPEC_PHYS(spec_pos(p, (N2 - b) & (N2 - 1)));
+                const double2 w = p.tw[b & (N2 - 1)];                 // W_N^b (unused at b = N/2)
+                for (int kk = 0; kk < Kr; kk++) {
+                    const double* zr = work + (size_t)(lc * Kr + kk) * 2 * FS;
+                    const double* zi = zr + FS;
+                    double xr, xi;
+                    if (b == N2) { xr = zr[0] - zi[0]; xi = 0.0; }
+                    else {
+                        const double ar = zr[ia], ai = zi[ia], br = zr[ib], bi = -zi[ib];     // Z[b], conj(Z[N/2 - b])
+                        const double er = 0.5 * (ar + br), ei = 0.5 * (ai + bi);
+                        const double dr = ar - br, di = ai - bi;
+                        const double orr = 0.5 * di, oi = -0.5 * dr;                            // O = -i/2 (Z[b] - conj(Z[N/2 - b]))
+                        xr = er + (orr * w.x - oi * w.y); xi = ei + (orr * w.y + oi * w.x);
+                    }
+                    sum += (xr * xr + xi * xi) * p.pscale;
+                }
+                if (!last) { acc[b] = sum; continue; }
+                const double P = sum / (double)p.K;
+                int level = 0;
+                if (P > 0.0) {
+                    const double db = 10.0 * log10(P);
+                    const double v = (db - p.top_db + p.range_db) / p.range_db * 255.0;
+                    if (v >= 255.0) level = 255;
+                    else if (v > 0.0) level = (int)floor(v + 0.5);
+                }
+                img[(H - 1 - b) * p.T + c + lc] = (uint8_t)level;
+            }
+        __syncthreads();
+        if (p.K <= p.F) c += Cr;
+        else { k0 += Kr; if (k0 == p.K) { k0 = 0; c++; } }
+    }
+    // ---- 5. rows of ncol contiguous bytes
+    uint8_t* out = p.image + (size_t)clip * H * p.W + c0;
+    for (int idx = tid; idx < H * p.T; idx += SPEC_THREADS) {
+        const int r = idx / p.T, j = idx - r * p.T;
+        if (j < ncol) out[(size_t)r * p.W + j] = img[idx];
+    }
+}
+
+static size_t spec_lds_bytes(int N, int H, int T, int F, int hop) {
+    const int N2 = N / 2;
+    return (size_t)F * 2 * SPEC_PHYS(N2) * 8 + ((size_t)(F - 1) * hop + N + 2) * 8 + (size_t)H * 8 + SPEC_FMAX * 4 + (size_t)H * T;
+}
+
+SpecPlan spectrogram_plan(int n, int W, int H) {
+    SpecPlan q;
+    q.N = 2 * (H - 1);
+    const long long wn = (long long)W * q.N;
+    q.K = (int)std::max<long long>(1, (n + wn - 1) / wn);
+    const long long kw = (long long)q.K * W;
+    const int hop = (int)((n + kw - 1) / kw);                        // <= N: centres of consecutive frames are at most this far apart
+    q.T = q.N <= 1024 ? 32 : (q.N <= 2048 ? 16 : 8);
+    // F: as many frames per round as leave room for two blocks per CU; one block per CU where not even two frames fit that
+    const long long fcap = std::min<long long>(SPEC_FMAX, (long long)q.T * q.K);
+    auto fit = [&](size_t budget) {
+        int F = 1;
+        while (F < fcap && spec_lds_bytes(q.N, H, q.T, F + 1, hop) <= budget) F++;
+        return F;
+    };
+    q.F = fit(78 * 1024);
+    if (q.F < 2) q.F = fit(160 * 1024 - 256);
+    q.span_cap = (q.F - 1) * hop + q.N + 2;
+    q.lds = spec_lds_bytes(q.N, H, q.T, q.F, hop);
+    return q;
+}
+
+std::vector<double> spectrogram_table(int N, const double* window) {
+    std::vector<double> t((size_t)2 * N);
+    for (int j = 0; j < N / 2; j++) {
+        const double a = 6.283185307179586476925286766559 * (double)j / (double)N;
+        t[2 * j] = std::cos(a); t[2 * j + 1] = -std::sin(a);
+    }
+    for (int i = 0; i < N; i++) t[(size_t)N + i] = window[i];
+    return t;
+}
+
+void launch_spectrogram(const void* samples, int f32, int n_clips, int n, int W, int H, const double* d_table, double wsum,
+                        double top_db, double range_db, uint8_t* image, hipStream_t s) {
+    const SpecPlan q = spectrogram_plan(n, W, H);
+    SpecParams p{};
+    p.samples = samples;
+    p.tw = reinterpret_cast<const double2*>(d_table);
+    p.window = d_table + q.N;
+    p.image = image;
+    p.n = n; p.W = W; p.H = H; p.N = q.N; p.K = q.K; p.T = q.T; p.F = q.F; p.span_cap = q.span_cap;
+    while ((2 << p.log2n2) < q.N) p.log2n2++;
+    for (int rem = p.log2n2; rem > 0;) { const int lr = rem >= 3 ? 3 : rem; p.lg[p.npass++] = lr; rem -= lr; }
+    p.pscale = (2.0 / wsum) * (2.0 / wsum);
+    p.top_db = top_db; p.range_db = range_db;
+    const dim3 grid((W + q.T - 1) / q.T, n_clips);
+    if (f32) {
+        lds_limit_once<&k_spectrogram<float>>(160 * 1024);
+        hipLaunchKernelGGL(k_spectrogram<float>, grid, dim3(SPEC_THREADS), q.lds, s, p);
+    } else {
+        lds_limit_once<&k_spectrogram<int16_t>>(160 * 1024);
+        hipLaunchKernelGGL(k_spectrogram<int16_t>, grid, dim3(SPEC_THREADS), q.lds, s, p);
+    }
+}
+
+}  // namespace bnhip

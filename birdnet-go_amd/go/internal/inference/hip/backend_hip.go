@@ -89,6 +89,8 @@ typedef int  (*fn_sl_reset)(bnhip_soundlevel_bank*, int);
 typedef int  (*fn_sl_process_pcm16)(bnhip_soundlevel_bank*, int, const int*, const int16_t* const*, const int*, bnhip_sound_level*, int, int*);
 typedef void (*fn_sl_destroy)(bnhip_soundlevel_bank*);
 typedef int  (*fn_range_heatmap)(bnhip_model*, const float*, int, int, int, int, float*);
+typedef int  (*fn_spec_size)(int, int*, int*);
+typedef int  (*fn_spec_pcm16)(int, const int16_t*, int, int, int, int, int, int, const double*, double, double, uint8_t*);
 
 typedef struct {
     void* handle;
@@ -109,6 +111,7 @@ typedef struct {
     fn_sl_bands sl_bands; fn_sl_create sl_create; fn_sl_add_stream sl_add_stream; fn_sl_remove_stream sl_remove_stream;
     fn_sl_reset sl_reset; fn_sl_process_pcm16 sl_process_pcm16; fn_sl_destroy sl_destroy;
     fn_range_heatmap range_heatmap;
+    fn_spec_size spec_size; fn_spec_pcm16 spec_pcm16;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -156,6 +159,7 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(sl_reset, "bnhip_soundlevel_bank_reset"); BN_RESOLVE(sl_process_pcm16, "bnhip_soundlevel_bank_process_pcm16");
     BN_RESOLVE(sl_destroy, "bnhip_soundlevel_bank_destroy");
     BN_RESOLVE(range_heatmap, "bnhip_range_heatmap");
+    BN_RESOLVE(spec_size, "bnhip_spectrogram_size"); BN_RESOLVE(spec_pcm16, "bnhip_spectrogram_pcm16");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -254,6 +258,11 @@ static inline void bnbind_sl_destroy(bnhip_soundlevel_bank* b) { if (BN.sl_destr
 static inline int bnbind_range_heatmap(bnhip_model* m, const float* coords, int n_cells, int species, int stride, int total_weeks,
                                        float* result) {
     return BN.range_heatmap(m, coords, n_cells, species, stride, total_weeks, result);
+}
+static inline int bnbind_spec_size(int width, int* height, int* fft_size) { return BN.spec_size(width, height, fft_size); }
+static inline int bnbind_spec_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate_in, int rate_out, int width, int height,
+                                    const double* window, double top_db, double range_db, uint8_t* image) {
+    return BN.spec_pcm16(device, pcm, n_clips, n, rate_in, rate_out, width, height, window, top_db, range_db, image);
 }
 // frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
 // the pointer table points at byte offset off[k] of the staging block
@@ -993,6 +1002,56 @@ func ComputeUSFrameCV(samples []float64, sampleRate int, cfg USFilterConfig, dev
 		return 0, false, fmt.Errorf("hip: us_frame_cv failed (%d): %s", int(rc), lastError())
 	}
 	return float64(cv), ok != 0, nil
+}
+
+// SpectrogramOptions are the knobs of one render: the profile's target rate (24 000 bird / 256 000 bat, frequency_profile.go:13-16;
+// 0 keeps the source rate), a window table of 2 * (height - 1) coefficients (nil = periodic Hann; the "scientific" styles pass a
+// Dolph table), and the level scale (RangeDB 80 / 100 / 120, conf/config.go:262-264; 0 means 100).
+type SpectrogramOptions struct {
+	ResampleRate int
+	Window       []float64
+	TopDB        float64
+	RangeDB      float64
+}
+
+// Spectrogram is the device's answer to one GenerateFromPCM (internal/spectrogram/generator.go:425): the raw image (sox's -r:
+// no axes, no legend) of one mono PCM16 clip as level indices [height][width], Nyquist in row 0.  The host maps the indices
+// through its style's palette and encodes the PNG.  Pixel values follow this engine's own rendering spec; they are not pinned
+// against sox.
+func Spectrogram(pcm []int16, sampleRate, width int, opts SpectrogramOptions, device int) (img []uint8, height int, err error) {
+	return RenderSpectrograms(pcm, 1, sampleRate, width, opts, device)
+}
+
+// RenderSpectrograms renders nClips clips of one length (pcm = the clips back to back) in ONE device call: a burst of detections
+// costs one H2D copy, the kernels and one D2H copy instead of a sox child per image.  img is [nClips][height][width].
+func RenderSpectrograms(pcm []int16, nClips, sampleRate, width int, opts SpectrogramOptions, device int) (img []uint8, height int, err error) {
+	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var h, fft C.int
+	if rc := C.bnbind_spec_size(C.int(width), &h, &fft); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram_size failed (%d): %s", int(rc), lastError())
+	}
+	var win *C.double
+	if opts.Window != nil {
+		if len(opts.Window) != int(fft) {
+			return nil, 0, fmt.Errorf("hip: spectrogram window must hold %d coefficients, got %d", int(fft), len(opts.Window))
+		}
+		win = (*C.double)(unsafe.Pointer(&opts.Window[0]))
+	}
+	rangeDB := opts.RangeDB
+	if rangeDB == 0 {
+		rangeDB = 100
+	}
+	img = make([]uint8, nClips*int(h)*width)
+	if rc := C.bnbind_spec_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(len(pcm)/nClips),
+		C.int(sampleRate), C.int(opts.ResampleRate), C.int(width), h, win, C.double(opts.TopDB), C.double(rangeDB),
+		(*C.uint8_t)(unsafe.Pointer(&img[0]))); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram failed (%d): %s", int(rc), lastError())
+	}
+	return img, int(h), nil
 }
 
 // Resampler mirrors internal/audiocore/resample.Resampler (resample.go:44-224) method for method: a stateful PCM16 resampler

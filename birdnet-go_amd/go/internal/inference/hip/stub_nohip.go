@@ -83,6 +83,21 @@ func ComputeUSFrameCV([]float64, int, USFilterConfig, int) (float64, bool, error
 	return 0, false, ErrHIPUnavailable
 }
 
+type SpectrogramOptions struct {
+	ResampleRate int
+	Window       []float64
+	TopDB        float64
+	RangeDB      float64
+}
+
+func Spectrogram([]int16, int, int, SpectrogramOptions, int) ([]uint8, int, error) {
+	return nil, 0, ErrHIPUnavailable
+}
+
+func RenderSpectrograms([]int16, int, int, int, SpectrogramOptions, int) ([]uint8, int, error) {
+	return nil, 0, ErrHIPUnavailable
+}
+
 type Resampler struct{}
 
 func NewResampler(int, int, int) (*Resampler, error)         { return nil, ErrHIPUnavailable }

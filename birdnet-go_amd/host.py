@@ -44,7 +44,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_eq_bank_reset", "bnhip_eq_bank_process_pcm16", "bnhip_windows_write_equalized", "bnhip_eq_design",
            "bnhip_eq_bank_destroy", "bnhip_soundlevel_bands", "bnhip_soundlevel_bank_create", "bnhip_soundlevel_bank_add_stream",
            "bnhip_soundlevel_bank_remove_stream", "bnhip_soundlevel_bank_reset", "bnhip_soundlevel_bank_process_pcm16",
-           "bnhip_soundlevel_bank_destroy", "bnhip_range_heatmap"]
+           "bnhip_soundlevel_bank_destroy", "bnhip_range_heatmap", "bnhip_spectrogram_size", "bnhip_spectrogram_pcm16",
+           "bnhip_spectrogram_device"]
 
 
 class HipError(RuntimeError):
@@ -378,6 +379,59 @@ def us_frame_cv(samples, sample_rate, fft_size=8192, hop=4096, split_hz=20000, d
     _check(lib, lib.bnhip_us_frame_cv(device, s.ctypes.data, s.shape[0], s.shape[1], sample_rate, fft_size, hop,
                                       split_hz, cv.ctypes.data, ok.ctypes.data))
     return cv, ok.astype(bool)
+
+
+def spectrogram_size(width):
+    """-> (height, fft_size) of a `width`-pixel image: fftFriendlyHeight (spectrogram/generator.go:115-123) and N = 2 (height - 1)."""
+    lib = load_library()
+    lib.bnhip_spectrogram_size.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    h, n = C.c_int(0), C.c_int(0)
+    _check(lib, lib.bnhip_spectrogram_size(int(width), C.byref(h), C.byref(n)))
+    return h.value, n.value
+
+
+def _spectrogram_window(window, fft_size):
+    """(keep-alive array, pointer) of a caller's window table; None -> NULL (periodic Hann on the host side of the C ABI)."""
+    if window is None:
+        return None, None
+    w = np.ascontiguousarray(window, np.float64)
+    if w.shape != (fft_size,):
+        raise HipError(E_INVALID, f"window must hold {fft_size} coefficients, got shape {w.shape}")
+    return w, w.ctypes.data
+
+
+def spectrogram(clips_pcm16, rate, width, rate_out=0, window=None, top_db=0.0, range_db=100.0, device=0):
+    """Raw spectrogram images of a batch of equally long clips in one device call (what GenerateFromPCM, spectrogram/generator.go:425,
+    asks sox for clip by clip): int16 [B, n] (or [n]) at `rate` Hz -> uint8 [B, H, W] level indices, Nyquist in row 0.
+    rate_out: resample first (24 000 bird profile, 256 000 bat profile); 0 renders at the source rate.  Spec: DESIGN.md §9."""
+    lib = load_library()
+    x = np.ascontiguousarray(clips_pcm16, np.int16)
+    if x.ndim == 1:
+        x = x[None, :]
+    if x.ndim != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise HipError(E_INVALID, "clips must be a non-empty int16 [B, n] array")
+    height, fft_size = spectrogram_size(width)
+    keep, wp = _spectrogram_window(window, fft_size)
+    img = np.empty((x.shape[0], height, int(width)), np.uint8)
+    lib.bnhip_spectrogram_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_double, C.c_double, C.c_void_p]
+    _check(lib, lib.bnhip_spectrogram_pcm16(device, x.ctypes.data, x.shape[0], x.shape[1], int(rate), int(rate_out), int(width), height,
+                                            wp, float(top_db), float(range_db), img.ctypes.data))
+    del keep
+    return img
+
+
+def spectrogram_device(d_samples_ptr, f32, n_clips, n, width, height, d_image_ptr, window=None, top_db=0.0, range_db=100.0, device=0,
+                       hip_stream_ptr=None):
+    """Device-resident form: samples (int16, or float32 with f32) and the uint8 [n_clips, height, width] image are device pointers;
+    enqueued on the stream, not synchronised."""
+    lib = load_library()
+    keep, wp = _spectrogram_window(window, 2 * (int(height) - 1))
+    lib.bnhip_spectrogram_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                             C.c_double, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_spectrogram_device(device, d_samples_ptr, 1 if f32 else 0, int(n_clips), int(n), int(width), int(height), wp,
+                                             float(top_db), float(range_db), d_image_ptr, hip_stream_ptr))
+    del keep
 
 
 def _sigmoid_f32div(x):

@@ -223,6 +223,33 @@ int bnhip_us_frame_cv(int device, const double* samples, int n_clips, int n, int
 int bnhip_us_frame_cv_device(int device, const void* d_samples, int pcm16, int n_clips, int n, int sample_rate, int fft_size,
                              int hop, int split_hz, double* d_scratch, double* d_cv, void* hip_stream);
 
+/* Detection-clip spectrogram images: what GenerateFromPCM (internal/spectrogram/generator.go:425-530) gets from a
+ * `sox ... rate 24k spectrogram -x W -y H -z R -r` child process per clip, for a batch of clips of one length in one call.
+ * sox is not in the reference's tree: the pixel values follow this project's own rendering spec (restated in
+ * float64 by tests/specref.py) and are NOT pinned against sox.  Raw images only (no axes, no legend), mono.
+ *   N = 2 (height - 1) is the transform length; K = max(1, ceil(n / (width N))) frames are averaged per column; frame (c, k) is
+ *   centred at sample floor((2 (c K + k) + 1) n / (2 K width)), zero outside the clip; x = pcm / 32768 (or the float sample);
+ *   P[b] = mean over k of |sum_i w[i] x[i] e^(-2 pi i b i / N)|^2 (2 / sum w)^2 (a full-scale sine peaks at 0 dB);
+ *   v = (10 log10 P - top_db + range_db) / range_db * 255; the index is 0 for v <= 0 or P = 0, 255 for v >= 255, else floor(v + 0.5).
+ *   image: uint8 [n_clips][height][width], row r = bin height - 1 - r (Nyquist on top).  All arithmetic is float64.
+ * window: host table of N doubles, NULL = periodic Hann 0.5 - 0.5 cos(2 pi i / N); uploaded tables are cached per (device, N, contents).
+ * size:   height = fftFriendlyHeight(width) (generator.go:115-123) and fft_size = N for a width in 1..4096.
+ * pcm16:  host PCM in, host image out: one H2D copy, the kernels, one D2H copy, one synchronise.  rate_out == 0 or == rate_in renders
+ *         at the source rate; otherwise the clips first pass through the one-shot resampler on the device (int16 in, float32 out,
+ *         the bnhip_resample_length(n, ...) samples bnhip_resample_f32 gives) - 24 000 Hz for the bird profile, 256 000 Hz for the bat
+ *         profile (frequency_profile.go:13-16) - and nothing returns to the host in between.
+ * device: d_samples (int16, or float32 with f32 != 0) and d_image are device memory; enqueued on hip_stream (NULL = default
+ *         stream), not synchronised.
+ * BNHIP_E_INVALID: NULL / empty arguments, n < 1, n_clips > 65535, width outside 1..4096, a height that is not 2^k + 1, a non-finite
+ * top_db or range_db, range_db <= 0, non-finite window coefficients or a window that sums to zero.  BNHIP_E_UNSUPPORTED: N outside
+ * 64..4096, a rate pair whose resampler geometry does not fit LDS.  Argument errors are answered before any device is touched. */
+int bnhip_spectrogram_size(int width, int* height, int* fft_size);
+int bnhip_spectrogram_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate_in, int rate_out,
+                            int width, int height, const double* window, double top_db, double range_db,
+                            uint8_t* image);
+int bnhip_spectrogram_device(int device, const void* d_samples, int f32, int n_clips, int n, int width, int height,
+                             const double* window, double top_db, double range_db, uint8_t* d_image, void* hip_stream);
+
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
  * pass through (NewResampler returns nil, :58-60); a too-small destination is an error before any work (:137-144).
