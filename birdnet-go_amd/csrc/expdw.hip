@@ -218,12 +218,22 @@ __device__ __forceinline__ void ed_sums_out(const ExpDwParams& p, const float4* 
     }
 }
 
-template <int K, int S, int TOH, int TOW, int TRH, bool H8 = false, bool BX = false, bool COPY = false>
+// VW > 0, the full-width form: where one tile column spans the whole image width (the 6 x 32 layers: TOW x S = 32 under a
+// footprint of 34-36 columns) the columns outside the image - 1 of 13 or 2 of 14 MFMA tiles per block - were computed from a
+// clamped address, put through the activation and replaced by zero.  Here the GEMM's rows are the image's own pixels
+// (192 = 12 tiles, three per wave); E keeps its layout, so phase 2 is untouched, and the same operations in the same order
+// form every element that is kept.  BNHIP_EXPDW_FULLW=0 restores the footprint mapping (A/B runs, tests).
+constexpr int expdw_fullw_vw(int K, int S, int TOW) { return TOW * S == 32 && (TOW - 1) * S + K >= 32 ? 32 : 0; }
+template <int K, int S, int TOH, int TOW, int TRH, bool H8 = false, bool BX = false, bool COPY = false, int VW = 0>
 __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void k_expand_dw(ExpDwParams p, unsigned nblk) {
     constexpr int TIH = (TOH - 1) * S + K, TIW = (TOW - 1) * S + K;
     static_assert(TRH <= TIH, "TRH is a cap on the footprint rows");
-    constexpr int NPIX = TRH * TIW, NPIXP = (NPIX + 15) / 16 * 16;
-    constexpr int JT = NPIXP / 16, JTW = (JT + 3) / 4;
+    constexpr bool FULLW = VW > 0;
+    static_assert(!FULLW || (!COPY && VW % 16 == 0 && VW <= TIW && VW == expdw_fullw_vw(K, S, TOW)), "full-width form: see expdw_fullw_vw");
+    static_assert(!FULLW || (TIW - VW) * TRH * 8 <= 256, "full-width form: the padding columns are one float4 store of some threads");
+    constexpr int NPIX = TRH * TIW;                           // pixels of E (LDS layout: the same in both mappings)
+    constexpr int GW = FULLW ? VW : TIW;                      // columns the GEMM computes per footprint row
+    constexpr int JT = (TRH * GW + 15) / 16, JTW = (JT + 3) / 4;
     constexpr int SW = TOW / 8;                               // output columns per thread in phase 2 (thread-tiles are 4 x 8)
     __shared__ __attribute__((aligned(16))) float lds[NPIX * ED_ES + 256 + K * K * 32];
     float* E = lds;                                                      // [<=TRH rows][TIW][36] expanded footprint
@@ -245,8 +255,10 @@ __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void
     // footprint rows are compacted to the in-image range [vr0, vr1) (host guarantees vr1 - vr0 <= TRH); columns keep
     // the compile-time width TIW (out-of-image columns are masked): GEMM row j <-> footprint pixel
     // (vr0 + j / TIW, j % TIW), stored at E[j]
+    // FULLW (one tile column whose footprint covers the whole image width VW): GEMM row j <-> image pixel (vr0 + j / VW, j % VW),
+    // stored at E[(j / VW) * TIW + j % VW + pl]; the padding columns left and right are never computed
     const int vr0 = max(ih0, 0) - ih0, vr1 = min(ih0 + TIH, p.H) - ih0;
-    const int nvalid = (vr1 - vr0) * TIW;
+    const int nvalid = (vr1 - vr0) * GW;
     const int jtv = (nvalid + 15) >> 4;
     const int Cin = p.Cin, Kw = p.Kw;
     const int n_base = cc * 32;
@@ -290,15 +302,26 @@ __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void
 
     // this lane's pixel per owned tile (a): clamped global offset + validity
     int xoff[JTW];
-    bool xin[JTW];
+    bool xin[FULLW ? 1 : JTW];
 #pragma unroll
     for (int a = 0; a < JTW; a++) {
         int j = 16 * (wave + 4 * a) + li;
-        int r = j / TIW, c = j - r * TIW;
-        int iw = iw0 + c;
-        xin[a] = j < nvalid && iw >= 0 && iw < p.W;
-        int ihc = min(ih0 + vr0 + r, p.H - 1), iwc = min(max(iw, 0), p.W - 1);
+        int r = j / GW, c = j - r * GW;
+        int ihc = min(ih0 + vr0 + r, p.H - 1), iwc = c;     // (rows past the valid ones: any in-image row, never stored)
+        if constexpr (!FULLW) {
+            int iw = iw0 + c;
+            xin[a] = j < nvalid && iw >= 0 && iw < p.W;
+            iwc = min(max(iw, 0), p.W - 1);
+        }
         xoff[a] = (b * p.H * p.W + ihc * p.xsh + iwc * p.xsw) * Cin + (BX ? 8 : 4) * kq;
+    }
+    if constexpr (FULLW) {
+        // the footprint's padding columns [0, pl) and [pl + VW, TIW) of the valid rows are zeros of the expanded tensor: plain
+        // stores, (TIW - VW) x rows x 8 quads - less than one per thread - long before the barrier that publishes E
+        constexpr int PC = TIW - VW;
+        const int pr = (tid >> 3) / PC, pc = (tid >> 3) - pr * PC;
+        if (PC > 0 && pr < vr1 - vr0)
+            *reinterpret_cast<float4*>(&E[(pr * TIW + (pc < p.pl ? pc : pc + VW)) * ED_ES + 4 * (tid & 7)]) = zero4;
     }
     const float* wrow0 = p.we + (size_t)(n_base + li) * Kw + 4 * kq;
     const float* wrow1 = wrow0 + (size_t)16 * Kw;
@@ -416,7 +439,7 @@ __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void
 
     // ---- E <- act_e(acc) at compacted footprint coordinates (masked columns are zero).  Only a tile on the left / right
     // image border has columns to mask (block-uniform test): interior tiles store without the eight selects per 16 pixels
-    const bool border = iw0 < 0 || iw0 + TIW > p.W;
+    const bool border = !FULLW && (iw0 < 0 || iw0 + TIW > p.W);
 #pragma unroll
     for (int a = 0; a < JTW; a++) {
         if (wave + 4 * a < jtv) {                         // wave-uniform: tiles beyond the valid rows cost nothing
@@ -432,7 +455,11 @@ __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void
                 });
             }
             int j = 16 * (wave + 4 * a) + li;
-            if (j < nvalid) {
+            if constexpr (FULLW) {                        // (VW is a multiple of 16: a tile below jtv holds valid pixels only)
+                int e = ((j / VW) * TIW + j % VW + p.pl) * ED_ES + 4 * kq;
+                *reinterpret_cast<f32x4*>(&E[e]) = acc[a][0];
+                *reinterpret_cast<f32x4*>(&E[e + 16]) = acc[a][1];
+            } else if (j < nvalid) {
                 int e = j * ED_ES + 4 * kq;
                 if (border) {
                     const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -812,8 +839,14 @@ static const ExpDwShape kExpDwShapes[] = {
     {3, 1, 8, 16, 10, 8}, {3, 1, 8, 32, 6, 8}, {3, 1, 8, 32, 10, 8}, {5, 1, 8, 16, 12, 8}, {5, 1, 8, 32, 6, 8},
     {3, 2, 8, 8, 12, 8}, {3, 2, 8, 8, 17, 8}, {5, 2, 8, 8, 19, 8},
 };
-static long expdw_cost(const ExpDwShape& sh, int H, int Ho, int Wo, int pt, bool* fits) {
-    const int tih = (sh.toh - 1) * sh.s + sh.k, tiw = (sh.tow - 1) * sh.s + sh.k;
+// the full-width form of k_expand_dw applies (oriented geometry): one tile column, the image as wide as the instantiated VW,
+// the footprint covering all of it
+static bool expdw_fullw_geo(const ExpDwShape& sh, int W, int Wo, int pl) {
+    const int vw = expdw_fullw_vw(sh.k, sh.s, sh.tow), tiw = (sh.tow - 1) * sh.s + sh.k;
+    return sh.nw == 4 && vw > 0 && W == vw && Wo <= sh.tow && pl >= 0 && pl + vw <= tiw;
+}
+static long expdw_cost(const ExpDwShape& sh, int H, int W, int Ho, int Wo, int pt, int pl, bool* fits) {
+    const int tih = (sh.toh - 1) * sh.s + sh.k, tiw = expdw_fullw_geo(sh, W, Wo, pl) ? W : (sh.tow - 1) * sh.s + sh.k;
     const int th = (Ho + sh.toh - 1) / sh.toh, tw = (Wo + sh.tow - 1) / sh.tow;
     long rows = 0;
     *fits = true;
@@ -849,8 +882,15 @@ bool expdw_shape_fits(int idx, const ExpDwGeo& g0, bool planning) {
     }
     const ExpDwGeo g = expdw_oriented(idx, g0);
     bool fits;
-    (void)expdw_cost(sh, g.H, g.Ho, g.Wo, g.pt, &fits);
+    (void)expdw_cost(sh, g.H, g.W, g.Ho, g.Wo, g.pt, g.pl, &fits);
     return fits;
+}
+bool expdw_fullwidth(int idx, const ExpDwGeo& g0) {
+    static const bool off = getenv("BNHIP_EXPDW_FULLW") && atoi(getenv("BNHIP_EXPDW_FULLW")) == 0;
+    if (off || idx < 0 || idx >= 2 * kNumExpDwShapes || g0.stem || g0.skw != 0) return false;
+    const ExpDwShape& sh = kExpDwShapes[idx % kNumExpDwShapes];
+    const ExpDwGeo g = expdw_oriented(idx, g0);
+    return sh.k == g0.k && sh.s == g0.s && expdw_fullw_geo(sh, g.W, g.Wo, g.pl);
 }
 int expdw_shape_slabs(int idx, const ExpDwGeo& g0) {
     const ExpDwShape& sh = kExpDwShapes[idx % kNumExpDwShapes];
@@ -866,7 +906,7 @@ int expdw_default_shape(const ExpDwGeo& g0) {
         const ExpDwGeo g = expdw_oriented(i, g0);
         const ExpDwShape& sh = kExpDwShapes[i % kNumExpDwShapes];
         bool fits;
-        long c = expdw_cost(sh, g.H, g.Ho, g.Wo, g.pt, &fits);
+        long c = expdw_cost(sh, g.H, g.W, g.Ho, g.Wo, g.pt, g.pl, &fits);
         const long lds = (long)sh.trh * ((sh.tow - 1) * sh.s + sh.k) * ED_ES * 4;
         if (lds > 51 * 1024) c += c / 3;                // fewer than three blocks per CU: measured to outweigh a smaller halo
         if (best < 0 || c < best_cost) { best = i; best_cost = c; }
@@ -917,6 +957,18 @@ bool expdw_supported(int k, int s, int Cin, int Cmid, int act_e, int prec) {
     // (k_expand_dw_sk<PH = 1, NS = 5 | 8>: 160 / 256 padded input channels, 2 NS MFMAs of 16 cycles per tile and chunk)
     return prec == 1 && expdw_sk_pipe16(Cin, act_e, false, prec, true);
 }
+// k_expand_dw of one tile shape: the full-width form where the shape has one and the launch qualifies
+template <int K, int S, int TH, int TW, int TR, bool H8, bool BX>
+static void ed_launch(const ExpDwParams& p, unsigned nblk, hipStream_t st, bool fullw) {
+    constexpr int VW = expdw_fullw_vw(K, S, TW);
+    if constexpr (VW > 0) {
+        if (fullw) {
+            hipLaunchKernelGGL((k_expand_dw<K, S, TH, TW, TR, H8, BX, false, VW>), dim3(nblk), dim3(256), 0, st, p, nblk);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_expand_dw<K, S, TH, TW, TR, H8, BX>), dim3(nblk), dim3(256), 0, st, p, nblk);
+}
 void launch_expand_dw(const float* x, const float* we, const float* be, const float* wd, const float* bd, float* y,
                       float* partial, int B, int H, int W, int Cin, int Cmid, int Ho, int Wo, int k, int s, int pt,
                       int pl, int act_e, int act_d, int shape, const StemGeom* stem, hipStream_t st, const uint16_t* wep, int prec, int out_bf16,
@@ -949,6 +1001,7 @@ void launch_expand_dw(const float* x, const float* we, const float* be, const fl
     // ... except where phase 1 runs on the bf16 pipe (expdw_sk_pipe16: "precision":"bf16" engines, one product per pair - 2 MFMAs
     // instead of 12-16 per tile, chunk and slab)
     const bool b16 = pipe16;
+    const bool fullw = !sk && expdw_fullwidth(shape, g0);
     if (pipe16) { p.wep = wep; p.Kp = expdw_kp(Cin); p.prec = prec; p.in_bf16 = in_bf16; }     // (the planner marks x bf16 for this form only)
     if (sk && !stem) {
         // small-K form: a block owns (clip, tile) and walks the channel chunks itself
@@ -996,7 +1049,7 @@ void launch_expand_dw(const float* x, const float* we, const float* be, const fl
 #undef ED_CASE8
 #define ED_CASE(K_, S_, TH_, TW_, TR_)                                                                        \
     if (sh->k == K_ && sh->s == S_ && sh->toh == TH_ && sh->tow == TW_ && sh->trh == TR_) {                   \
-        if (bx) hipLaunchKernelGGL((k_expand_dw<K_, S_, TH_, TW_, TR_, false, true>), dim3(nblk), dim3(256), 0, st, p, nblk); \
+        if (bx) ed_launch<K_, S_, TH_, TW_, TR_, false, true>(p, nblk, st, fullw);                                \
         else if (b16 && p.Kp == 64) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 32, true, 4, 1, 2>), dim3(nblk), dim3(256), 0, st, p, nblk); \
         else if (b16 && p.Kp == 96) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 32, true, 4, 1, 3>), dim3(nblk), dim3(256), 0, st, p, nblk); \
         else if (b16 && p.Kp == 160) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 32, true, 4, 1, 5>), dim3(nblk), dim3(256), 0, st, p, nblk); \
@@ -1005,8 +1058,8 @@ void launch_expand_dw(const float* x, const float* we, const float* be, const fl
         else if (sk && p.Kw == 16) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 16>), dim3(nblk), dim3(256), 0, st, p, nblk); \
         else if (sk && p.Kw == 24) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 24>), dim3(nblk), dim3(256), 0, st, p, nblk); \
         else if (sk && p.Kw == 32) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 32>), dim3(nblk), dim3(256), 0, st, p, nblk); \
-        else if (p.Kw & 8) hipLaunchKernelGGL((k_expand_dw<K_, S_, TH_, TW_, TR_, true>), dim3(nblk), dim3(256), 0, st, p, nblk); \
-        else hipLaunchKernelGGL((k_expand_dw<K_, S_, TH_, TW_, TR_>), dim3(nblk), dim3(256), 0, st, p, nblk);  \
+        else if (p.Kw & 8) ed_launch<K_, S_, TH_, TW_, TR_, true, false>(p, nblk, st, fullw);                     \
+        else ed_launch<K_, S_, TH_, TW_, TR_, false, false>(p, nblk, st, fullw);                                  \
         return;                                                                                               \
     }
     ED_CASE(3, 1, 8, 16, 10) ED_CASE(3, 1, 4, 16, 6) ED_CASE(3, 1, 8, 32, 6) ED_CASE(3, 1, 8, 32, 10)

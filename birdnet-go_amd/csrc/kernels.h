@@ -244,6 +244,7 @@ int expdw_sum_slabs(const ExpDwGeo& g);   // slabs of the cost-model shape; 0 = 
 int expdw_num_shapes();                   // 2n
 bool expdw_shape_fits(int idx, const ExpDwGeo& g, bool planning = true);   // planning: also honour BNHIP_EXPDW_ORIENT (the launchers pass false: no getenv per launch)
 int expdw_shape_slabs(int idx, const ExpDwGeo& g);
+bool expdw_fullwidth(int idx, const ExpDwGeo& g);   // k_expand_dw takes its full-width form (in-image columns only) for this shape index; g.skw != 0 / stem: never
 int expdw_default_shape(const ExpDwGeo& g);
 int expdw_max_slabs(const ExpDwGeo& g);
 struct StemGeom { int Hin, Win, pt, pl; };   // raw image size and the stem conv's top/left padding
