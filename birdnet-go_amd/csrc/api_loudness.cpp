@@ -1,0 +1,158 @@
+// C ABI of the clip loudness entries (bnhip_loudness_measure_pcm16, bnhip_loudness_normalize_pcm16, bnhip_loudness_workspace_size,
+// bnhip_loudness_normalize_device).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+#include "api_common.h"
+#include "loudness.h"
+
+using namespace bnhip;
+
+namespace {
+
+// the coefficient table of one (device, rate, segment length), uploaded on first use and kept; the oldest of kTableCap entries leaves.  A caller
+// holds g_mu from the lookup until its kernels are enqueued: hipFree waits for the device, so a table is never freed between a
+// lookup and the launch that reads it, nor under a queued kernel.
+struct LoudTable { int device, rate, seg_len; double* d; };
+constexpr size_t kTableCap = 32;
+std::mutex g_mu;
+std::vector<LoudTable> g_tables;
+
+// (g_mu held)  -> NULL on an allocation / copy failure
+const LoudTable* loud_table(int device, int rate, int seg_len) {
+    for (auto& e : g_tables) if (e.device == device && e.rate == rate && e.seg_len == seg_len) return &e;
+    if (g_tables.size() >= kTableCap) { hipFree(g_tables.front().d); g_tables.erase(g_tables.begin()); }
+    const std::vector<double> t = loudness_table(rate, seg_len);
+    double* d = nullptr;
+    if (hipMalloc((void**)&d, t.size() * 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (hipMemcpy(d, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); hipFree(d); return nullptr; }
+    g_tables.push_back({device, rate, seg_len, d});
+    return &g_tables.back();
+}
+
+// what every entry checks before any device is touched (validateDims, audionorm.go:266-276); -> 0 or a negative BNHIP_E_*
+int dims_check(int n_clips, int n, int rate) {
+    if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
+    if (n < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
+    if (rate < LOUD_MIN_RATE) return set_err(BNHIP_E_INVALID, "sample rate too low; minimum is 8000 Hz (K-weighting is undefined below it)");
+    return 0;
+}
+
+// Options.validate (audionorm.go:278-293) and the clamp's magnitude
+int plan_check(double target, double ceiling, double max_gain) {
+    if (!std::isfinite(target)) return set_err(BNHIP_E_INVALID, "target loudness must be finite");
+    if (target >= 0.0 || target <= -70.0) return set_err(BNHIP_E_INVALID, "target loudness out of range (-70, 0)");
+    if (!std::isfinite(ceiling)) return set_err(BNHIP_E_INVALID, "true-peak ceiling must be finite");
+    if (ceiling > 0.0) return set_err(BNHIP_E_INVALID, "true-peak ceiling must be <= 0");
+    if (std::isnan(max_gain)) return set_err(BNHIP_E_INVALID, "max_gain_db must not be NaN");
+    return 0;
+}
+
+LoudPlan make_plan(double target, double ceiling, double max_gain, int gate_fallback, int measure) {
+    LoudPlan p;
+    p.target = target; p.ceiling = ceiling; p.max_gain = std::fabs(max_gain);
+    p.gate_abs = (double)(float)std::pow(10.0, (-70.0 - -0.691) / 10.0);          // absGateEnergy (meter.go:27-34)
+    p.gate_rel = (double)(float)std::pow(10.0, -10.0 / 10.0);                       // relGateEnergyFactor
+    p.gate_fallback = gate_fallback != 0; p.measure = measure;
+    return p;
+}
+
+// the host-pointer form of both entries: one H2D copy, the kernels, the D2H copies, one synchronise
+int run_pcm16(const char* what, int device, const int16_t* pcm, int n_clips, int n, int rate, const LoudPlan& plan, int16_t* out_pcm,
+              bnhip_loudness* out, double* sub_energy) {
+    int rc = use_device(device);
+    if (rc) return rc;
+    const int S = loudness_sub_block(rate);
+    const size_t pcm_bytes = (size_t)n_clips * n * 2, ws_bytes = loudness_workspace_bytes(n_clips, n, S);
+    std::unique_lock<std::mutex> lk(g_mu);
+    const LoudTable* tab = loud_table(device, rate, S / loudness_split(n_clips, n, S));
+    if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (loudness table)");
+    int16_t *d_pcm = nullptr, *d_out_pcm = nullptr; bnhip_loudness* d_out = nullptr; void* d_ws = nullptr;
+    hipError_t he = hipMalloc((void**)&d_pcm, pcm_bytes);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_out, (size_t)n_clips * sizeof(bnhip_loudness));
+    if (he == hipSuccess) he = hipMalloc(&d_ws, ws_bytes);
+    if (he == hipSuccess && out_pcm) he = hipMalloc((void**)&d_out_pcm, pcm_bytes);
+    const bool nomem = he == hipErrorOutOfMemory;
+    if (he == hipSuccess) he = hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice);
+    if (he == hipSuccess) {
+        const LoudWork w = loudness_work(n_clips, n, S, d_ws);
+        launch_loudness(d_pcm, w, tab->d, plan, d_out, d_out_pcm, nullptr);
+        he = hipGetLastError();
+        lk.unlock();
+        // (the null stream orders the copies after the kernels; the first one is the call's synchronise)
+        if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n_clips * sizeof(bnhip_loudness), hipMemcpyDeviceToHost);
+        if (he == hipSuccess && out_pcm) he = hipMemcpy(out_pcm, d_out_pcm, pcm_bytes, hipMemcpyDeviceToHost);
+        if (he == hipSuccess && sub_energy && w.Ns > 0) he = hipMemcpy(sub_energy, w.E1, (size_t)n_clips * w.Ns * 8, hipMemcpyDeviceToHost);
+    }
+    if (d_pcm) hipFree(d_pcm);
+    if (d_out) hipFree(d_out);
+    if (d_ws) hipFree(d_ws);
+    if (d_out_pcm) hipFree(d_out_pcm);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(nomem ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(what) + ": " + hipGetErrorString(he));
+    }
+    return BNHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bnhip_loudness_measure_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, bnhip_loudness* out, double* sub_energy) {
+    if (!pcm || !out) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    const int rc = dims_check(n_clips, n, rate);
+    if (rc) return rc;
+    return run_pcm16("loudness_measure_pcm16", device, pcm, n_clips, n, rate, make_plan(-23.0, -1.0, 0.0, 0, 1), nullptr, out, sub_energy);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_loudness_normalize_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs,
+                                   double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* out_pcm, bnhip_loudness* out) {
+    if (!pcm || !out) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = dims_check(n_clips, n, rate);
+    if (!rc) rc = plan_check(target_lufs, true_peak_dbtp, max_gain_db);
+    if (rc) return rc;
+    return run_pcm16("loudness_normalize_pcm16", device, pcm, n_clips, n, rate,
+                     make_plan(target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, 0), out_pcm, out, nullptr);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_loudness_workspace_size(int n_clips, int n, int rate, size_t* bytes) {
+    if (!bytes) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    const int rc = dims_check(n_clips, n, rate);
+    if (rc) return rc;
+    *bytes = loudness_workspace_bytes(n_clips, n, loudness_sub_block(rate));
+    return BNHIP_OK;
+}
+
+int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clips, int n, int rate, double target_lufs,
+                                    double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* d_out_pcm,
+                                    bnhip_loudness* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!d_pcm || !d_out || !d_workspace) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = dims_check(n_clips, n, rate);
+    if (!rc) rc = plan_check(target_lufs, true_peak_dbtp, max_gain_db);
+    if (rc) return rc;
+    const int S = loudness_sub_block(rate);
+    if (workspace_bytes < loudness_workspace_bytes(n_clips, n, S)) return set_err(BNHIP_E_INVALID, "workspace smaller than bnhip_loudness_workspace_size");
+    if (((uintptr_t)d_workspace & 255) != 0) return set_err(BNHIP_E_INVALID, "workspace must be 256-byte aligned");
+    rc = use_device(device);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    const LoudTable* tab = loud_table(device, rate, S / loudness_split(n_clips, n, S));
+    if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (loudness table)");
+    launch_loudness(d_pcm, loudness_work(n_clips, n, S, d_workspace), tab->d, make_plan(target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, 0),
+                    d_out, d_out_pcm, reinterpret_cast<hipStream_t>(hip_stream));
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("loudness_normalize_device: ") + hipGetErrorString(he));
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+}  // extern "C"

@@ -91,6 +91,14 @@ typedef void (*fn_sl_destroy)(bnhip_soundlevel_bank*);
 typedef int  (*fn_range_heatmap)(bnhip_model*, const float*, int, int, int, int, float*);
 typedef int  (*fn_spec_size)(int, int*, int*);
 typedef int  (*fn_spec_pcm16)(int, const int16_t*, int, int, int, int, int, int, const double*, double, double, uint8_t*);
+// bnhip.h's bnhip_loudness, restated field for field (tests/test_loudness_ref.py compares the two declarations)
+typedef struct bnhip_loudness {
+    double integrated_lufs, true_peak_dbtp, true_peak;
+    double target_gain_db, lift_db, planned_gain_db, gain_db, factor, output_lufs;
+    int flags, reserved;
+} bnhip_loudness;
+typedef int  (*fn_loud_measure)(int, const int16_t*, int, int, int, bnhip_loudness*, double*);
+typedef int  (*fn_loud_normalize)(int, const int16_t*, int, int, int, double, double, double, int, int16_t*, bnhip_loudness*);
 
 typedef struct {
     void* handle;
@@ -112,6 +120,7 @@ typedef struct {
     fn_sl_reset sl_reset; fn_sl_process_pcm16 sl_process_pcm16; fn_sl_destroy sl_destroy;
     fn_range_heatmap range_heatmap;
     fn_spec_size spec_size; fn_spec_pcm16 spec_pcm16;
+    fn_loud_measure loud_measure; fn_loud_normalize loud_normalize;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -160,6 +169,7 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(sl_destroy, "bnhip_soundlevel_bank_destroy");
     BN_RESOLVE(range_heatmap, "bnhip_range_heatmap");
     BN_RESOLVE(spec_size, "bnhip_spectrogram_size"); BN_RESOLVE(spec_pcm16, "bnhip_spectrogram_pcm16");
+    BN_RESOLVE(loud_measure, "bnhip_loudness_measure_pcm16"); BN_RESOLVE(loud_normalize, "bnhip_loudness_normalize_pcm16");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -263,6 +273,13 @@ static inline int bnbind_spec_size(int width, int* height, int* fft_size) { retu
 static inline int bnbind_spec_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate_in, int rate_out, int width, int height,
                                     const double* window, double top_db, double range_db, uint8_t* image) {
     return BN.spec_pcm16(device, pcm, n_clips, n, rate_in, rate_out, width, height, window, top_db, range_db, image);
+}
+static inline int bnbind_loud_measure(int device, const int16_t* pcm, int n_clips, int n, int rate, bnhip_loudness* out, double* sub_energy) {
+    return BN.loud_measure(device, pcm, n_clips, n, rate, out, sub_energy);
+}
+static inline int bnbind_loud_normalize(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs, double true_peak_dbtp,
+                                        double max_gain_db, int gate_fallback, int16_t* out_pcm, bnhip_loudness* out) {
+    return BN.loud_normalize(device, pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, out_pcm, out);
 }
 // frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
 // the pointer table points at byte offset off[k] of the staging block
@@ -1052,6 +1069,105 @@ func RenderSpectrograms(pcm []int16, nClips, sampleRate, width int, opts Spectro
 		return nil, 0, fmt.Errorf("hip: spectrogram failed (%d): %s", int(rc), lastError())
 	}
 	return img, int(h), nil
+}
+
+// Loudness is one clip's EBU R 128 measurement and gain plan (bnhip.h bnhip_loudness): what audionorm.Measurement, audionorm.Result
+// and the export path's gate fallback (analysis/processor/actions_database.go:1392-1438) report, in one record.  The measurement
+// follows the engine's float64 spec; the reference's meter is float32 (within 1e-3 LU / 1e-3 dBTP of it).
+type Loudness struct {
+	IntegratedLUFS float64 // -Inf: shorter than one 400 ms block, or under the absolute gate
+	TruePeakDBTP   float64 // -Inf: digital silence
+	TruePeak       float64
+	TargetGainDB   float64
+	LiftDB         float64 // the gate fallback's lift (GateLifted)
+	PlannedGainDB  float64 // before the clamp
+	GainDB         float64 // what is applied
+	Factor         float64 // pcmgain.FactorFromDB(GainDB): exactly 1 at 0 dB
+	OutputLUFS     float64
+	PeakLimited    bool
+	GateLifted     bool
+	Clamped        bool
+}
+
+// LoudnessOptions are the knobs of one plan.  The reference's callers: the clip export passes MaxGainDB 60 with GateFallback
+// (nativeExportMaxGainDB), the BirdWeather upload MaxGainDB 30 without (audionorm.DefaultMaxGainDB).  Zero TargetLUFS / MaxGainDB
+// mean audionorm.DefaultOptions' -23 LUFS and 30 dB; a zero TruePeakDBTP is a valid ceiling, so set it (-1 by default there).
+type LoudnessOptions struct {
+	TargetLUFS   float64
+	TruePeakDBTP float64
+	MaxGainDB    float64
+	GateFallback bool
+	PlanOnly     bool // measure and plan, return no samples
+}
+
+const (
+	loudnessPeakLimited = 1
+	loudnessGateLifted  = 2
+	loudnessClamped     = 4
+)
+
+func loudnessFromC(in []C.bnhip_loudness) []Loudness {
+	out := make([]Loudness, len(in))
+	for i := range in {
+		c := &in[i]
+		out[i] = Loudness{
+			IntegratedLUFS: float64(c.integrated_lufs), TruePeakDBTP: float64(c.true_peak_dbtp), TruePeak: float64(c.true_peak),
+			TargetGainDB: float64(c.target_gain_db), LiftDB: float64(c.lift_db), PlannedGainDB: float64(c.planned_gain_db),
+			GainDB: float64(c.gain_db), Factor: float64(c.factor), OutputLUFS: float64(c.output_lufs),
+			PeakLimited: int(c.flags)&loudnessPeakLimited != 0, GateLifted: int(c.flags)&loudnessGateLifted != 0,
+			Clamped: int(c.flags)&loudnessClamped != 0,
+		}
+	}
+	return out
+}
+
+// MeasureLoudness measures nClips mono PCM16 clips of one length (pcm = the clips back to back) in ONE device call
+// (audionorm.MeasureInt16 per clip in the reference).
+func MeasureLoudness(pcm []int16, nClips, sampleRate, device int) ([]Loudness, error) {
+	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
+		return nil, fmt.Errorf("hip: loudness needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	res := make([]C.bnhip_loudness, nClips)
+	if rc := C.bnbind_loud_measure(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(len(pcm)/nClips),
+		C.int(sampleRate), &res[0], nil); rc != 0 {
+		return nil, fmt.Errorf("hip: loudness_measure failed (%d): %s", int(rc), lastError())
+	}
+	return loudnessFromC(res), nil
+}
+
+// NormalizeClips measures, plans and gains a burst of nClips mono PCM16 clips of one length in ONE device call: what
+// planNativeNormalizationGain + pcmgain.Applied do clip by clip for an export, PlanClampedGainInt16Bytes for an upload.  pcm is
+// not modified; out holds the gained clips back to back (nil with PlanOnly).
+func NormalizeClips(pcm []int16, nClips, sampleRate int, opts LoudnessOptions, device int) (out []int16, res []Loudness, err error) {
+	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
+		return nil, nil, fmt.Errorf("hip: loudness needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
+	}
+	target, maxGain := opts.TargetLUFS, opts.MaxGainDB
+	if target == 0 {
+		target = -23
+	}
+	if maxGain == 0 {
+		maxGain = 30
+	}
+	fallback := 0
+	if opts.GateFallback {
+		fallback = 1
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	cres := make([]C.bnhip_loudness, nClips)
+	var outPtr *C.int16_t
+	if !opts.PlanOnly {
+		out = make([]int16, len(pcm))
+		outPtr = (*C.int16_t)(unsafe.Pointer(&out[0]))
+	}
+	if rc := C.bnbind_loud_normalize(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(len(pcm)/nClips),
+		C.int(sampleRate), C.double(target), C.double(opts.TruePeakDBTP), C.double(maxGain), C.int(fallback), outPtr, &cres[0]); rc != 0 {
+		return nil, nil, fmt.Errorf("hip: loudness_normalize failed (%d): %s", int(rc), lastError())
+	}
+	return out, loudnessFromC(cres), nil
 }
 
 // Resampler mirrors internal/audiocore/resample.Resampler (resample.go:44-224) method for method: a stateful PCM16 resampler

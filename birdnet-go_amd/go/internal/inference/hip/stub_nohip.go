@@ -98,6 +98,35 @@ func RenderSpectrograms([]int16, int, int, int, SpectrogramOptions, int) ([]uint
 	return nil, 0, ErrHIPUnavailable
 }
 
+type Loudness struct {
+	IntegratedLUFS float64
+	TruePeakDBTP   float64
+	TruePeak       float64
+	TargetGainDB   float64
+	LiftDB         float64
+	PlannedGainDB  float64
+	GainDB         float64
+	Factor         float64
+	OutputLUFS     float64
+	PeakLimited    bool
+	GateLifted     bool
+	Clamped        bool
+}
+
+type LoudnessOptions struct {
+	TargetLUFS   float64
+	TruePeakDBTP float64
+	MaxGainDB    float64
+	GateFallback bool
+	PlanOnly     bool
+}
+
+func MeasureLoudness([]int16, int, int, int) ([]Loudness, error) { return nil, ErrHIPUnavailable }
+
+func NormalizeClips([]int16, int, int, LoudnessOptions, int) ([]int16, []Loudness, error) {
+	return nil, nil, ErrHIPUnavailable
+}
+
 type Resampler struct{}
 
 func NewResampler(int, int, int) (*Resampler, error)         { return nil, ErrHIPUnavailable }

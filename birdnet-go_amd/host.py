@@ -45,7 +45,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_eq_bank_destroy", "bnhip_soundlevel_bands", "bnhip_soundlevel_bank_create", "bnhip_soundlevel_bank_add_stream",
            "bnhip_soundlevel_bank_remove_stream", "bnhip_soundlevel_bank_reset", "bnhip_soundlevel_bank_process_pcm16",
            "bnhip_soundlevel_bank_destroy", "bnhip_range_heatmap", "bnhip_spectrogram_size", "bnhip_spectrogram_pcm16",
-           "bnhip_spectrogram_device"]
+           "bnhip_spectrogram_device", "bnhip_loudness_measure_pcm16", "bnhip_loudness_normalize_pcm16",
+           "bnhip_loudness_workspace_size", "bnhip_loudness_normalize_device"]
 
 
 class HipError(RuntimeError):
@@ -432,6 +433,99 @@ def spectrogram_device(d_samples_ptr, f32, n_clips, n, width, height, d_image_pt
     _check(lib, lib.bnhip_spectrogram_device(device, d_samples_ptr, 1 if f32 else 0, int(n_clips), int(n), int(width), int(height), wp,
                                              float(top_db), float(range_db), d_image_ptr, hip_stream_ptr))
     del keep
+
+
+LOUDNESS_PEAK_LIMITED, LOUDNESS_GATE_LIFTED, LOUDNESS_CLAMPED = 1, 2, 4
+
+
+class Loudness(C.Structure):
+    """bnhip_loudness: one clip's measurement, plan and flags (bnhip.h)."""
+    _fields_ = [("integrated_lufs", C.c_double), ("true_peak_dbtp", C.c_double), ("true_peak", C.c_double),
+                ("target_gain_db", C.c_double), ("lift_db", C.c_double), ("planned_gain_db", C.c_double), ("gain_db", C.c_double),
+                ("factor", C.c_double), ("output_lufs", C.c_double), ("flags", C.c_int), ("reserved", C.c_int)]
+
+    @property
+    def peak_limited(self):
+        return bool(self.flags & LOUDNESS_PEAK_LIMITED)
+
+    @property
+    def gate_lifted(self):
+        return bool(self.flags & LOUDNESS_GATE_LIFTED)
+
+    @property
+    def clamped(self):
+        return bool(self.flags & LOUDNESS_CLAMPED)
+
+
+def _loudness_clips(clips_pcm16, channels):
+    """int16 [B, n] of a batch (or one clip [n]); anything but mono is BNHIP_E_UNSUPPORTED (conf.NumChannels is 1)."""
+    if int(channels) != 1:
+        raise HipError(E_UNSUPPORTED, f"loudness entries are mono, got {channels} channels")
+    x = np.ascontiguousarray(clips_pcm16)
+    if x.dtype != np.int16:
+        raise HipError(E_UNSUPPORTED, f"loudness entries take int16 PCM, got {x.dtype}")
+    if x.ndim == 1:
+        x = x[None, :]
+    if x.ndim != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise HipError(E_INVALID, "clips must be a non-empty int16 [B, n] array")
+    return x
+
+
+def loudness_sub_block(rate):
+    """Samples of a 100 ms sub-block: Go's math.Round(0.1 rate) (audionorm/meter.go:91-93), not Python's round."""
+    return int(math.floor(0.1 * float(rate) + 0.5))
+
+
+def loudness_measure(clips_pcm16, rate, sub_energy=False, channels=1, device=0):
+    """EBU R 128 integrated loudness and true peak of a batch of equally long mono clips in one device call (audionorm.MeasureInt16):
+    int16 [B, n] (or [n]) at `rate` Hz -> list of B Loudness; with sub_energy also the float64 [B, n // S] K-weighted sub-block
+    energies.  Spec: DESIGN.md §9."""
+    lib = load_library()
+    x = _loudness_clips(clips_pcm16, channels)
+    out = (Loudness * x.shape[0])()
+    sub = np.zeros((x.shape[0], x.shape[1] // max(1, loudness_sub_block(rate))), np.float64) if sub_energy else None
+    lib.bnhip_loudness_measure_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_loudness_measure_pcm16(device, x.ctypes.data, x.shape[0], x.shape[1], int(rate), C.addressof(out),
+                                                 sub.ctypes.data if sub is not None and sub.size else None))
+    return (list(out), sub) if sub_energy else list(out)
+
+
+def loudness_normalize(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, apply=True,
+                       channels=1, device=0):
+    """Measure, plan and (apply) gain a batch of equally long mono clips in one device call: int16 [B, n] -> (list of B Loudness, int16
+    [B, n] output or None for apply=False).  (max_gain_db 60, gate_fallback) is the export plan (actions_database.go:1392-1438),
+    (30, no fallback) the BirdWeather upload's (encode_native.go:25-66)."""
+    lib = load_library()
+    x = _loudness_clips(clips_pcm16, channels)
+    out = (Loudness * x.shape[0])()
+    y = np.empty_like(x) if apply else None
+    lib.bnhip_loudness_normalize_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                   C.c_int, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_loudness_normalize_pcm16(device, x.ctypes.data, x.shape[0], x.shape[1], int(rate), float(target_lufs),
+                                                   float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0,
+                                                   y.ctypes.data if apply else None, C.addressof(out)))
+    return list(out), y
+
+
+def loudness_workspace_size(n_clips, n, rate):
+    """Bytes of device scratch loudness_normalize_device needs."""
+    lib = load_library()
+    lib.bnhip_loudness_workspace_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    b = C.c_size_t(0)
+    _check(lib, lib.bnhip_loudness_workspace_size(int(n_clips), int(n), int(rate), C.byref(b)))
+    return b.value
+
+
+def loudness_normalize_device(d_pcm_ptr, n_clips, n, rate, d_out_ptr, d_workspace_ptr, workspace_bytes, d_out_pcm_ptr=None,
+                              target_lufs=-23.0, true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, device=0, hip_stream_ptr=None):
+    """Device-resident form: int16 clips, the Loudness results ([n_clips] of 80 bytes), the output clips and the workspace are device
+    pointers; enqueued on the stream, not synchronised."""
+    lib = load_library()
+    lib.bnhip_loudness_normalize_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_loudness_normalize_device(device, d_pcm_ptr, int(n_clips), int(n), int(rate), float(target_lufs),
+                                                    float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0, d_out_pcm_ptr,
+                                                    d_out_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
 
 
 def _sigmoid_f32div(x):

@@ -250,6 +250,53 @@ int bnhip_spectrogram_pcm16(int device, const int16_t* pcm, int n_clips, int n, 
 int bnhip_spectrogram_device(int device, const void* d_samples, int f32, int n_clips, int n, int width, int height,
                              const double* window, double top_db, double range_db, uint8_t* d_image, void* hip_stream);
 
+/* Clip loudness: the EBU R 128 normalisation every exported clip and every BirdWeather upload gets (internal/audiocore/audionorm,
+ * internal/audiocore/pcmgain; the export plan with its gate fallback, analysis/processor/actions_database.go:1285-1438; the upload
+ * plan, birdweather/encode_native.go:25-66), for a batch of mono int16 clips of one length in one call.  The numbers follow the
+ * spec of DESIGN.md §9 (restated in float64 by tests/loudref.py): the reference's float32 coefficients, its recurrence, gates,
+ * true-peak taps, plan and saturating gain, evaluated in float64 with every operation rounded.
+ *   x = pcm / 32768;  S = floor(0.1 rate + 0.5) samples per sub-block;  E[k] = sum of y^2 over sub-block k of the K-weighted
+ *   signal y (the trailing n - floor(n / S) S samples add nothing);  z[j] = (E[j] + .. + E[j+3]) / (4 S);  absolute gate
+ *   z > (float)10^(-6.9309), relative gate z > 0.1f * the absolute-gated mean;  integrated_lufs = -0.691 + 10 log10(mean of the
+ *   gated z), -inf with no gated block;  true_peak = max(|x|, |4 x 32-tap polyphase interpolation of x|) over n + 16 positions;
+ *   true_peak_dbtp = 20 log10(true_peak), -inf for 0.
+ *   plan: target_gain_db = target_lufs - integrated_lufs, limited to true_peak_dbtp's headroom under the ceiling (PEAK_LIMITED);
+ *   nothing for -inf.  With gate_fallback != 0 a clip of -inf loudness and a non-zero peak is lifted by lift_db =
+ *   min(ceiling - true_peak_dbtp, target + 70) (GATE_LIFTED), the lifted int16 clip is measured on the device and planned again:
+ *   planned_gain_db = lift_db + that plan's gain (target_gain_db and PEAK_LIMITED are then that plan's), or lift_db when it is
+ *   still under the gate.  gain_db = planned_gain_db clamped to +-|max_gain_db| (CLAMPED; +inf = no clamp); factor = 1 exactly
+ *   at 0 dB, else pow(10, gain_db / 20); output = (double)pcm * factor rounded half away from zero, saturated to int16.
+ *   output_lufs = the loudness the plan used (the lifted clip's for a lifted clip) + gain_db - lift_db, -inf when that is -inf.
+ *   integrated_lufs, true_peak_dbtp and true_peak always describe the clip as given.
+ * The reference's callers pass (60, gate_fallback 1) for an export and (30, 0) for an upload.
+ * measure:   measurements only (the plan fields are 0, factor 1, output_lufs = integrated_lufs); sub_energy (nullable) receives
+ *            E as [n_clips][n / S] doubles.
+ * normalize: out_pcm NULL = plan only.  pcm16: host memory in and out: one H2D copy, the kernels, one D2H copy of the results and
+ *            of the output, one synchronise.
+ * device:    d_pcm, d_out_pcm (nullable), d_out and d_workspace are device memory, d_workspace at least
+ *            bnhip_loudness_workspace_size bytes and 256-byte aligned; enqueued on hip_stream (NULL = default stream), not
+ *            synchronised; the workspace is in use until the enqueued work has run.
+ * BNHIP_E_INVALID: NULL / empty arguments, rate < 8000, n < 1, n_clips outside 1..65535, a target that is not finite or outside
+ * (-70, 0), a ceiling that is not finite or > 0, a NaN max_gain_db, a workspace that is too small.  There is no multi-channel or
+ * float entry (conf.NumChannels is 1, nativeNormalizationBitDepth 16): the bindings answer BNHIP_E_UNSUPPORTED for them.  Argument errors are answered before
+ * any device is touched.  Divergences: float64 where the reference's meter is float32 (distance measured in DESIGN.md §9); the
+ * reference's two SIMD sums have no pinned order; libm's tan / pow / sin / log10 may differ from Go's in the last ulp. */
+enum { BNHIP_LOUDNESS_PEAK_LIMITED = 1, BNHIP_LOUDNESS_GATE_LIFTED = 2, BNHIP_LOUDNESS_CLAMPED = 4 };
+typedef struct bnhip_loudness {
+    double integrated_lufs, true_peak_dbtp, true_peak;
+    double target_gain_db, lift_db, planned_gain_db, gain_db, factor, output_lufs;
+    int flags, reserved;
+} bnhip_loudness;
+int bnhip_loudness_measure_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, bnhip_loudness* out,
+                                 double* sub_energy);
+int bnhip_loudness_normalize_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs,
+                                   double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* out_pcm,
+                                   bnhip_loudness* out);
+int bnhip_loudness_workspace_size(int n_clips, int n, int rate, size_t* bytes);
+int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clips, int n, int rate, double target_lufs,
+                                    double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* d_out_pcm,
+                                    bnhip_loudness* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
  * pass through (NewResampler returns nil, :58-60); a too-small destination is an error before any work (:137-144).

@@ -10,6 +10,7 @@ import sys
 
 
 def short(name):
+    name = name.replace("(anonymous namespace)::", "")
     name = re.sub(r"\(.*\)$", "", name)
     name = name.replace("void ", "").replace("bnhip::", "")
     return name[:70]
