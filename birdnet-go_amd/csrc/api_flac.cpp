@@ -1,0 +1,159 @@
+// C ABI of the FLAC entries (bnhip_flac_max_bytes, bnhip_flac_workspace_size, bnhip_flac_encode_device, bnhip_flac_encode_pcm16,
+// bnhip_loudness_flac_pcm16).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#include "api_common.h"
+#include "flac.h"
+#include "loudness.h"
+
+using namespace bnhip;
+
+namespace {
+
+// what every entry checks before any device is touched; -> 0 or a negative BNHIP_E_*
+int dims_check(int n_clips, int n, int rate, int seek_interval) {
+    if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
+    if (n < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
+    if (rate < 1 || rate > FLAC_MAX_RATE) return set_err(BNHIP_E_INVALID, "sample rate must be in [1, 1048575]");
+    if (seek_interval < 0) return set_err(BNHIP_E_INVALID, "seek_interval must not be negative");
+    return 0;
+}
+
+int cap_check(int n_clips, int n, int seek_interval, size_t out_cap) {
+    if (out_cap < flac_max_bytes(n_clips, n, seek_interval)) return set_err(BNHIP_E_INVALID, "out_cap smaller than bnhip_flac_max_bytes");
+    return 0;
+}
+
+struct DevBlocks {
+    std::vector<void*> p;
+    hipError_t he = hipSuccess;
+    bool nomem = false;
+    void* get(size_t bytes) {
+        void* d = nullptr;
+        if (he == hipSuccess) he = hipMalloc(&d, bytes ? bytes : 1);
+        if (he == hipErrorOutOfMemory) nomem = true;
+        if (he == hipSuccess) p.push_back(d);
+        return d;
+    }
+    ~DevBlocks() { for (void* d : p) hipFree(d); }
+};
+
+int hip_fail(const char* what, const DevBlocks& b) {
+    (void)hipGetLastError();
+    return set_err(b.nomem ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(what) + ": " + hipGetErrorString(b.he));
+}
+
+// offsets first (that copy is the call's synchronise), then exactly offsets[n_clips] bytes
+hipError_t fetch(const unsigned long long* d_offsets, const uint8_t* d_bytes, int n_clips, uint64_t* offsets, uint8_t* out) {
+    hipError_t he = hipMemcpy(offsets, d_offsets, ((size_t)n_clips + 1) * 8, hipMemcpyDeviceToHost);
+    if (he == hipSuccess && offsets[n_clips] > 0) he = hipMemcpy(out, d_bytes, (size_t)offsets[n_clips], hipMemcpyDeviceToHost);
+    return he;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bnhip_flac_max_bytes(int n_clips, int n, int seek_interval, size_t* bytes) {
+    if (!bytes) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    const int rc = dims_check(n_clips, n, 1, seek_interval);
+    if (rc) return rc;
+    *bytes = flac_max_bytes(n_clips, n, seek_interval);
+    return BNHIP_OK;
+}
+
+int bnhip_flac_workspace_size(int n_clips, int n, size_t* bytes) {
+    if (!bytes) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    const int rc = dims_check(n_clips, n, 1, 0);
+    if (rc) return rc;
+    *bytes = flac_workspace_bytes(n_clips, n);
+    return BNHIP_OK;
+}
+
+int bnhip_flac_encode_device(int device, const int16_t* d_pcm, int n_clips, int n, int rate, const double* d_factor, int seek_interval,
+                             uint8_t* d_out, size_t out_cap, uint64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!d_pcm || !d_out || !d_offsets || !d_workspace) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = dims_check(n_clips, n, rate, seek_interval);
+    if (!rc) rc = cap_check(n_clips, n, seek_interval, out_cap);
+    if (rc) return rc;
+    if (workspace_bytes < flac_workspace_bytes(n_clips, n)) return set_err(BNHIP_E_INVALID, "workspace smaller than bnhip_flac_workspace_size");
+    if (((uintptr_t)d_workspace & 255) != 0) return set_err(BNHIP_E_INVALID, "workspace must be 256-byte aligned");
+    rc = use_device(device);
+    if (rc) return rc;
+    launch_flac(d_pcm, d_factor, flac_work(n_clips, n, rate, seek_interval, d_workspace), d_out, out_cap, (unsigned long long*)d_offsets,
+                reinterpret_cast<hipStream_t>(hip_stream));
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("flac_encode_device: ") + hipGetErrorString(he));
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_flac_encode_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, const double* factor, int seek_interval,
+                            uint8_t* out, size_t out_cap, uint64_t* offsets) {
+    if (!pcm || !out || !offsets) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = dims_check(n_clips, n, rate, seek_interval);
+    if (rc) return rc;
+    if (factor)
+        for (int i = 0; i < n_clips; i++)
+            if (!std::isfinite(factor[i]) || factor[i] < 0.0) return set_err(BNHIP_E_INVALID, "factor must be finite and not negative");
+    rc = cap_check(n_clips, n, seek_interval, out_cap);
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    const size_t pcm_bytes = (size_t)n_clips * n * 2, cap = flac_max_bytes(n_clips, n, seek_interval);
+    DevBlocks b;
+    int16_t* d_pcm = (int16_t*)b.get(pcm_bytes);
+    double* d_factor = factor ? (double*)b.get((size_t)n_clips * 8) : nullptr;
+    uint8_t* d_bytes = (uint8_t*)b.get(cap);
+    unsigned long long* d_offsets = (unsigned long long*)b.get(((size_t)n_clips + 1) * 8);
+    void* d_ws = b.get(flac_workspace_bytes(n_clips, n));
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess && factor) b.he = hipMemcpy(d_factor, factor, (size_t)n_clips * 8, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
+        launch_flac(d_pcm, d_factor, flac_work(n_clips, n, rate, seek_interval, d_ws), d_bytes, cap, d_offsets, nullptr);
+        b.he = hipGetLastError();
+    }
+    if (b.he == hipSuccess) b.he = fetch(d_offsets, d_bytes, n_clips, offsets, out);
+    if (b.he != hipSuccess) return hip_fail("flac_encode_pcm16", b);
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_loudness_flac_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs, double true_peak_dbtp,
+                              double max_gain_db, int gate_fallback, int seek_interval, bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap,
+                              uint64_t* offsets) {
+    if (!pcm || !out || !out_bytes || !offsets) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = loudness_args_check(n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db);
+    if (!rc) rc = dims_check(n_clips, n, rate, seek_interval);
+    if (!rc) rc = cap_check(n_clips, n, seek_interval, out_cap);
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    const size_t pcm_bytes = (size_t)n_clips * n * 2, cap = flac_max_bytes(n_clips, n, seek_interval);
+    DevBlocks b;
+    int16_t* d_pcm = (int16_t*)b.get(pcm_bytes);
+    int16_t* d_gained = (int16_t*)b.get(pcm_bytes);                 // the normalised clips never leave the device
+    bnhip_loudness* d_res = (bnhip_loudness*)b.get((size_t)n_clips * sizeof(bnhip_loudness));
+    void* d_lws = b.get(loudness_workspace_bytes(n_clips, n, loudness_sub_block(rate)));
+    uint8_t* d_bytes = (uint8_t*)b.get(cap);
+    unsigned long long* d_offsets = (unsigned long long*)b.get(((size_t)n_clips + 1) * 8);
+    void* d_fws = b.get(flac_workspace_bytes(n_clips, n));
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice);
+    if (b.he != hipSuccess) return hip_fail("loudness_flac_pcm16", b);
+    rc = loudness_enqueue("loudness_flac_pcm16", device, d_pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, d_res,
+                          d_gained, d_lws, nullptr);
+    if (rc) { hipDeviceSynchronize(); return rc; }
+    launch_flac(d_gained, nullptr, flac_work(n_clips, n, rate, seek_interval, d_fws), d_bytes, cap, d_offsets, nullptr);
+    b.he = hipGetLastError();
+    if (b.he == hipSuccess) b.he = hipMemcpy(out, d_res, (size_t)n_clips * sizeof(bnhip_loudness), hipMemcpyDeviceToHost);
+    if (b.he == hipSuccess) b.he = fetch(d_offsets, d_bytes, n_clips, offsets, out_bytes);
+    if (b.he != hipSuccess) return hip_fail("loudness_flac_pcm16", b);
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+}  // extern "C"

@@ -100,6 +100,28 @@ int run_pcm16(const char* what, int device, const int16_t* pcm, int n_clips, int
 
 }  // namespace
 
+namespace bnhip {
+
+int loudness_args_check(int n_clips, int n, int rate, double target, double ceiling, double max_gain) {
+    const int rc = dims_check(n_clips, n, rate);
+    return rc ? rc : plan_check(target, ceiling, max_gain);
+}
+
+int loudness_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, int n, int rate, double target, double ceiling,
+                     double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace, hipStream_t s) {
+    const int S = loudness_sub_block(rate);
+    std::lock_guard<std::mutex> lk(g_mu);
+    const LoudTable* tab = loud_table(device, rate, S / loudness_split(n_clips, n, S));
+    if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (loudness table)");
+    launch_loudness(d_pcm, loudness_work(n_clips, n, S, d_workspace), tab->d, make_plan(target, ceiling, max_gain, gate_fallback, 0), d_out,
+                    d_out_pcm, s);
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string(what) + ": " + hipGetErrorString(he));
+    return BNHIP_OK;
+}
+
+}  // namespace bnhip
+
 extern "C" {
 
 int bnhip_loudness_measure_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, bnhip_loudness* out, double* sub_energy) {
@@ -139,19 +161,12 @@ int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clip
     int rc = dims_check(n_clips, n, rate);
     if (!rc) rc = plan_check(target_lufs, true_peak_dbtp, max_gain_db);
     if (rc) return rc;
-    const int S = loudness_sub_block(rate);
-    if (workspace_bytes < loudness_workspace_bytes(n_clips, n, S)) return set_err(BNHIP_E_INVALID, "workspace smaller than bnhip_loudness_workspace_size");
+    if (workspace_bytes < loudness_workspace_bytes(n_clips, n, loudness_sub_block(rate))) return set_err(BNHIP_E_INVALID, "workspace smaller than bnhip_loudness_workspace_size");
     if (((uintptr_t)d_workspace & 255) != 0) return set_err(BNHIP_E_INVALID, "workspace must be 256-byte aligned");
     rc = use_device(device);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    const LoudTable* tab = loud_table(device, rate, S / loudness_split(n_clips, n, S));
-    if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (loudness table)");
-    launch_loudness(d_pcm, loudness_work(n_clips, n, S, d_workspace), tab->d, make_plan(target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, 0),
-                    d_out, d_out_pcm, reinterpret_cast<hipStream_t>(hip_stream));
-    const hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("loudness_normalize_device: ") + hipGetErrorString(he));
-    return BNHIP_OK;
+    return loudness_enqueue("loudness_normalize_device", device, d_pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback,
+                            d_out, d_out_pcm, d_workspace, reinterpret_cast<hipStream_t>(hip_stream));
     BN_GUARD_END((void)0)
 }
 

@@ -58,4 +58,12 @@ LoudWork loudness_work(int n_clips, int n, int S, void* d_block);
 void launch_loudness(const int16_t* pcm, const LoudWork& w, const double* d_table, const LoudPlan& plan, bnhip_loudness* out,
                      int16_t* out_pcm, hipStream_t s);
 
+
+// What an entry of another unit needs of api_loudness.cpp (the fused loudness + FLAC entry of api_flac.cpp):
+// the argument checks of the normalise entries, answered before any device is touched; -> 0 or a negative BNHIP_E_*
+int loudness_args_check(int n_clips, int n, int rate, double target, double ceiling, double max_gain);
+// the device (already made current) has its table looked up or uploaded, and the normalise kernels are enqueued on s
+int loudness_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, int n, int rate, double target, double ceiling,
+                     double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace, hipStream_t s);
+
 }  // namespace bnhip

@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "loudness.h"
+#include "pcmgain.h"
 
 #pragma clang fp contract(off)
 
@@ -28,16 +29,8 @@ constexpr int KW_ROW = KW_CHUNK + 2;       // int16 row stride in LDS: 33 dwords
 constexpr int TP_THREADS = 256, TP_R = LOUD_TP_TILE / TP_THREADS;      // positions per thread
 constexpr int TP_SPAN = LOUD_TP_TILE + LOUD_TP_TAPS - 1;
 
-// one sample of the measured signal: s / 32768, or pcmgain's saturated round-half-away s * f first (pcmgain.go:52-60)
-__device__ __forceinline__ double loud_gained(int16_t s, double f) {
-#pragma clang fp contract(off)
-    if (f == 1.0) return (double)s;
-    double v = round((double)s * f);
-    v = v > 32767.0 ? 32767.0 : v;
-    v = v < -32768.0 ? -32768.0 : v;
-    return v;
-}
-__device__ __forceinline__ double loud_sample(int16_t s, double f) { return loud_gained(s, f) * (1.0 / 32768.0); }
+// one sample of the measured signal: s / 32768, or the saturated gain of pcmgain.h first
+__device__ __forceinline__ double loud_sample(int16_t s, double f) { return pcm_gained(s, f) * (1.0 / 32768.0); }
 
 struct KwState { double x1, x2, u1, u2, y1, y2; };
 
@@ -301,7 +294,7 @@ __global__ __launch_bounds__(256) void k_loud_gain(const int16_t* __restrict__ p
     const double f = res[clip].factor;
     const long long i0 = (long long)clip * n;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        out[i0 + i] = (int16_t)loud_gained(pcm[i0 + i], f);
+        out[i0 + i] = (int16_t)pcm_gained(pcm[i0 + i], f);
 }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }

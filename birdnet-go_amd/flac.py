@@ -1,0 +1,58 @@
+"""FLAC clip encoding: the surface of the reference's internal/audiocore/flac package that the BirdWeather upload and the detection
+save see, over bnhip_flac_encode_pcm16 and bnhip_loudness_flac_pcm16.
+
+  EncodePCMToBuffer                  flac/encode.go:320-369         -> encode_clips(.., seek_interval=0)
+  EncodePCM (file, seek table)       flac/encode.go:79-175          -> encode_clips(.., seek_interval=sample_rate)
+  encodeFLACNative                   birdweather/encode_native.go:28-98 -> normalize_and_encode(.., max_gain_db=DEFAULT_MAX_GAIN_DB)
+
+Mono int16 only.  The bytes follow the project's own encoder spec: valid RFC 9639 streams, not go-flac's bytes.
+"""
+import numpy as np
+
+from . import host as _host
+from .loudness import DEFAULT_MAX_GAIN_DB, default_options, factor_from_db
+
+
+def _burst(clips):
+    """The clips as contiguous arrays and their indices grouped by length (one device call per length)."""
+    clips = [np.ascontiguousarray(c) for c in clips]
+    for c in clips:
+        if c.dtype != np.int16 or c.ndim != 1 or c.size == 0:
+            raise _host.HipError(_host.E_UNSUPPORTED if c.ndim != 1 or c.dtype != np.int16 else _host.E_INVALID,
+                                 "clips must be non-empty mono int16 arrays")
+    groups = {}
+    for i, c in enumerate(clips):
+        groups.setdefault(c.size, []).append(i)
+    return clips, groups
+
+
+def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0):
+    """A burst of detections: a list of int16 mono clips of any lengths -> list of FLAC streams (bytes) in the input's order.
+    gain_db: None, one gain for all, or one per clip; applied on the device (FactorFromDB, then the saturating int16 gain)."""
+    clips, groups = _burst(clips)
+    if gain_db is None:
+        factor = None
+    else:
+        g = np.broadcast_to(np.asarray(gain_db, np.float64), (len(clips),))
+        factor = np.array([factor_from_db(float(v)) for v in g], np.float64)
+    streams = [None] * len(clips)
+    for idx in groups.values():
+        out = _host.flac_encode(np.stack([clips[i] for i in idx]), sample_rate, None if factor is None else factor[idx], seek_interval,
+                                device=device)
+        for j, i in enumerate(idx):
+            streams[i] = out[j]
+    return streams
+
+
+def normalize_and_encode(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, seek_interval=0, device=0):
+    """Loudness-normalise and encode a burst in one device call per length: -> (list of host.Loudness, list of FLAC streams), both
+    in the input's order.  The normalised PCM never reaches the host."""
+    opts = opts or default_options()
+    clips, groups = _burst(clips)
+    results, streams = [None] * len(clips), [None] * len(clips)
+    for idx in groups.values():
+        res, out = _host.loudness_flac(np.stack([clips[i] for i in idx]), sample_rate, opts.target_lufs, opts.true_peak_dbtp, max_gain_db,
+                                       gate_fallback, seek_interval, device=device)
+        for j, i in enumerate(idx):
+            results[i], streams[i] = res[j], out[j]
+    return results, streams

@@ -99,6 +99,9 @@ typedef struct bnhip_loudness {
 } bnhip_loudness;
 typedef int  (*fn_loud_measure)(int, const int16_t*, int, int, int, bnhip_loudness*, double*);
 typedef int  (*fn_loud_normalize)(int, const int16_t*, int, int, int, double, double, double, int, int16_t*, bnhip_loudness*);
+typedef int  (*fn_flac_max_bytes)(int, int, int, size_t*);
+typedef int  (*fn_flac_encode_pcm16)(int, const int16_t*, int, int, int, const double*, int, uint8_t*, size_t, uint64_t*);
+typedef int  (*fn_loud_flac_pcm16)(int, const int16_t*, int, int, int, double, double, double, int, int, bnhip_loudness*, uint8_t*, size_t, uint64_t*);
 
 typedef struct {
     void* handle;
@@ -121,6 +124,7 @@ typedef struct {
     fn_range_heatmap range_heatmap;
     fn_spec_size spec_size; fn_spec_pcm16 spec_pcm16;
     fn_loud_measure loud_measure; fn_loud_normalize loud_normalize;
+    fn_flac_max_bytes flac_max_bytes; fn_flac_encode_pcm16 flac_encode_pcm16; fn_loud_flac_pcm16 loud_flac_pcm16;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -170,6 +174,8 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(range_heatmap, "bnhip_range_heatmap");
     BN_RESOLVE(spec_size, "bnhip_spectrogram_size"); BN_RESOLVE(spec_pcm16, "bnhip_spectrogram_pcm16");
     BN_RESOLVE(loud_measure, "bnhip_loudness_measure_pcm16"); BN_RESOLVE(loud_normalize, "bnhip_loudness_normalize_pcm16");
+    BN_RESOLVE(flac_max_bytes, "bnhip_flac_max_bytes"); BN_RESOLVE(flac_encode_pcm16, "bnhip_flac_encode_pcm16");
+    BN_RESOLVE(loud_flac_pcm16, "bnhip_loudness_flac_pcm16");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -280,6 +286,19 @@ static inline int bnbind_loud_measure(int device, const int16_t* pcm, int n_clip
 static inline int bnbind_loud_normalize(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs, double true_peak_dbtp,
                                         double max_gain_db, int gate_fallback, int16_t* out_pcm, bnhip_loudness* out) {
     return BN.loud_normalize(device, pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, out_pcm, out);
+}
+static inline int bnbind_flac_max_bytes(int n_clips, int n, int seek_interval, size_t* bytes) {
+    return BN.flac_max_bytes(n_clips, n, seek_interval, bytes);
+}
+static inline int bnbind_flac_encode_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, const double* factor, int seek_interval,
+                                           uint8_t* out, size_t out_cap, uint64_t* offsets) {
+    return BN.flac_encode_pcm16(device, pcm, n_clips, n, rate, factor, seek_interval, out, out_cap, offsets);
+}
+static inline int bnbind_loud_flac_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs, double true_peak_dbtp,
+                                         double max_gain_db, int gate_fallback, int seek_interval, bnhip_loudness* out, uint8_t* out_bytes,
+                                         size_t out_cap, uint64_t* offsets) {
+    return BN.loud_flac_pcm16(device, pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, seek_interval, out,
+                              out_bytes, out_cap, offsets);
 }
 // frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
 // the pointer table points at byte offset off[k] of the staging block
@@ -1168,6 +1187,89 @@ func NormalizeClips(pcm []int16, nClips, sampleRate int, opts LoudnessOptions, d
 		return nil, nil, fmt.Errorf("hip: loudness_normalize failed (%d): %s", int(rc), lastError())
 	}
 	return out, loudnessFromC(cres), nil
+}
+
+// splitStreams cuts the streams an encode entry wrote back to back at their offsets; each stream is its own copy.
+func splitStreams(buf []byte, offsets []C.uint64_t) [][]byte {
+	out := make([][]byte, len(offsets)-1)
+	for i := range out {
+		out[i] = append([]byte(nil), buf[int(offsets[i]):int(offsets[i+1])]...)
+	}
+	return out
+}
+
+// EncodeFLAC encodes nClips mono PCM16 clips of one length (pcm = the clips back to back) to FLAC in ONE device call: what
+// flac.EncodePCMToBuffer does clip by clip (seekInterval 0), or flac.EncodePCM with its seek table (seekInterval = the sample
+// rate).  gainDB: nil, or one gain per clip, applied on the device first (pcmgain.FactorFromDB, then the saturating int16 gain).
+// The bytes follow the project's own encoder spec (DESIGN.md section 9): valid RFC 9639 streams, not go-flac's bytes.
+func EncodeFLAC(pcm []int16, nClips, sampleRate int, gainDB []float64, seekInterval, device int) ([][]byte, error) {
+	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
+		return nil, fmt.Errorf("hip: flac needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
+	}
+	if gainDB != nil && len(gainDB) != nClips {
+		return nil, fmt.Errorf("hip: flac needs one gain per clip, got %d for %d clips", len(gainDB), nClips)
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	n := len(pcm) / nClips
+	var capBytes C.size_t
+	if rc := C.bnbind_flac_max_bytes(C.int(nClips), C.int(n), C.int(seekInterval), &capBytes); rc != 0 {
+		return nil, fmt.Errorf("hip: flac_max_bytes failed (%d): %s", int(rc), lastError())
+	}
+	var facPtr *C.double
+	if gainDB != nil {
+		factor := make([]C.double, nClips)
+		for i, g := range gainDB {
+			factor[i] = 1
+			if g != 0 {
+				factor[i] = C.double(math.Pow(10, g/20))
+			}
+		}
+		facPtr = &factor[0]
+	}
+	buf := make([]byte, int(capBytes))
+	offsets := make([]C.uint64_t, nClips+1)
+	if rc := C.bnbind_flac_encode_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(n), C.int(sampleRate),
+		facPtr, C.int(seekInterval), (*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
+		return nil, fmt.Errorf("hip: flac_encode failed (%d): %s", int(rc), lastError())
+	}
+	return splitStreams(buf, offsets), nil
+}
+
+// NormalizeAndEncodeFLAC is NormalizeClips followed by EncodeFLAC in ONE device call (encodeFLACNative, birdweather/
+// encode_native.go:28-98, for a burst; with GateFallback, MaxGainDB 60 and seekInterval = the sample rate the detection save): the
+// normalised PCM never leaves the device - the loudness records and the compressed streams return.  opts.PlanOnly is ignored.
+func NormalizeAndEncodeFLAC(pcm []int16, nClips, sampleRate int, opts LoudnessOptions, seekInterval, device int) (streams [][]byte, res []Loudness, err error) {
+	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
+		return nil, nil, fmt.Errorf("hip: flac needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
+	}
+	target, maxGain := opts.TargetLUFS, opts.MaxGainDB
+	if target == 0 {
+		target = -23
+	}
+	if maxGain == 0 {
+		maxGain = 30
+	}
+	fallback := 0
+	if opts.GateFallback {
+		fallback = 1
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	n := len(pcm) / nClips
+	var capBytes C.size_t
+	if rc := C.bnbind_flac_max_bytes(C.int(nClips), C.int(n), C.int(seekInterval), &capBytes); rc != 0 {
+		return nil, nil, fmt.Errorf("hip: flac_max_bytes failed (%d): %s", int(rc), lastError())
+	}
+	cres := make([]C.bnhip_loudness, nClips)
+	buf := make([]byte, int(capBytes))
+	offsets := make([]C.uint64_t, nClips+1)
+	if rc := C.bnbind_loud_flac_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(n), C.int(sampleRate),
+		C.double(target), C.double(opts.TruePeakDBTP), C.double(maxGain), C.int(fallback), C.int(seekInterval), &cres[0],
+		(*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
+		return nil, nil, fmt.Errorf("hip: loudness_flac failed (%d): %s", int(rc), lastError())
+	}
+	return splitStreams(buf, offsets), loudnessFromC(cres), nil
 }
 
 // Resampler mirrors internal/audiocore/resample.Resampler (resample.go:44-224) method for method: a stateful PCM16 resampler

@@ -127,6 +127,12 @@ func NormalizeClips([]int16, int, int, LoudnessOptions, int) ([]int16, []Loudnes
 	return nil, nil, ErrHIPUnavailable
 }
 
+func EncodeFLAC([]int16, int, int, []float64, int, int) ([][]byte, error) { return nil, ErrHIPUnavailable }
+
+func NormalizeAndEncodeFLAC([]int16, int, int, LoudnessOptions, int, int) ([][]byte, []Loudness, error) {
+	return nil, nil, ErrHIPUnavailable
+}
+
 type Resampler struct{}
 
 func NewResampler(int, int, int) (*Resampler, error)         { return nil, ErrHIPUnavailable }

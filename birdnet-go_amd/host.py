@@ -46,7 +46,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_soundlevel_bank_remove_stream", "bnhip_soundlevel_bank_reset", "bnhip_soundlevel_bank_process_pcm16",
            "bnhip_soundlevel_bank_destroy", "bnhip_range_heatmap", "bnhip_spectrogram_size", "bnhip_spectrogram_pcm16",
            "bnhip_spectrogram_device", "bnhip_loudness_measure_pcm16", "bnhip_loudness_normalize_pcm16",
-           "bnhip_loudness_workspace_size", "bnhip_loudness_normalize_device"]
+           "bnhip_loudness_workspace_size", "bnhip_loudness_normalize_device", "bnhip_flac_max_bytes", "bnhip_flac_workspace_size",
+           "bnhip_flac_encode_device", "bnhip_flac_encode_pcm16", "bnhip_loudness_flac_pcm16"]
 
 
 class HipError(RuntimeError):
@@ -526,6 +527,93 @@ def loudness_normalize_device(d_pcm_ptr, n_clips, n, rate, d_out_ptr, d_workspac
     _check(lib, lib.bnhip_loudness_normalize_device(device, d_pcm_ptr, int(n_clips), int(n), int(rate), float(target_lufs),
                                                     float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0, d_out_pcm_ptr,
                                                     d_out_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def flac_max_bytes(n_clips, n, seek_interval=0):
+    """The worst-case bytes of n_clips streams of n samples (every frame VERBATIM): the out_cap the encode entries ask for."""
+    lib = load_library()
+    lib.bnhip_flac_max_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    b = C.c_size_t(0)
+    _check(lib, lib.bnhip_flac_max_bytes(int(n_clips), int(n), int(seek_interval), C.byref(b)))
+    return b.value
+
+
+def flac_workspace_size(n_clips, n):
+    """Bytes of device scratch flac_encode_device needs."""
+    lib = load_library()
+    lib.bnhip_flac_workspace_size.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    b = C.c_size_t(0)
+    _check(lib, lib.bnhip_flac_workspace_size(int(n_clips), int(n), C.byref(b)))
+    return b.value
+
+
+def _flac_clips(clips_pcm16, channels):
+    """As _loudness_clips: mono int16 [B, n] or BNHIP_E_UNSUPPORTED."""
+    if int(channels) != 1:
+        raise HipError(E_UNSUPPORTED, f"FLAC entries are mono, got {channels} channels")
+    x = np.ascontiguousarray(clips_pcm16)
+    if x.dtype != np.int16:
+        raise HipError(E_UNSUPPORTED, f"FLAC entries take int16 PCM, got {x.dtype}")
+    if x.ndim == 1:
+        x = x[None, :]
+    if x.ndim != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise HipError(E_INVALID, "clips must be a non-empty int16 [B, n] array")
+    return x
+
+
+def _flac_streams(buf, offsets):
+    return [buf[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(offsets) - 1)]
+
+
+def flac_encode(clips_pcm16, rate, factor=None, seek_interval=0, channels=1, device=0, raw=False):
+    """FLAC streams of a batch of equally long mono clips in one device call (flac.EncodePCMToBuffer; with seek_interval = rate what
+    flac.EncodePCM writes to a file): int16 [B, n] (or [n]) -> list of B bytes objects.  factor: per-clip gain applied on the device
+    first (None = none).  raw: (the uint8 buffer as written, offsets uint64 [B + 1]) instead.  Spec: DESIGN.md §9."""
+    lib = load_library()
+    x = _flac_clips(clips_pcm16, channels)
+    B, n = x.shape
+    fac = None if factor is None else np.ascontiguousarray(factor, np.float64).reshape(-1)
+    if fac is not None and fac.size != B:
+        raise HipError(E_INVALID, f"factor must hold one value per clip, got {fac.size} for {B}")
+    cap = flac_max_bytes(B, n, seek_interval)
+    out = np.empty(cap, np.uint8)
+    offsets = np.zeros(B + 1, np.uint64)
+    lib.bnhip_flac_encode_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]
+    _check(lib, lib.bnhip_flac_encode_pcm16(device, x.ctypes.data, B, n, int(rate), fac.ctypes.data if fac is not None else None,
+                                            int(seek_interval), out.ctypes.data, cap, offsets.ctypes.data))
+    return (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
+
+
+def flac_encode_device(d_pcm_ptr, n_clips, n, rate, d_out_ptr, out_cap, d_offsets_ptr, d_workspace_ptr, workspace_bytes, d_factor_ptr=None,
+                       seek_interval=0, device=0, hip_stream_ptr=None):
+    """Device-resident form: the clips, the factors (nullable), the output, the uint64 [n_clips + 1] offsets and the workspace are
+    device pointers; enqueued on the stream, not synchronised."""
+    lib = load_library()
+    lib.bnhip_flac_encode_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_flac_encode_device(device, d_pcm_ptr, int(n_clips), int(n), int(rate), d_factor_ptr, int(seek_interval), d_out_ptr,
+                                             int(out_cap), d_offsets_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def loudness_flac(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, seek_interval=0,
+                  channels=1, device=0):
+    """loudness_normalize and flac_encode in one device call - the normalised clips never reach the host: int16 [B, n] -> (list of B
+    Loudness, list of B bytes objects).  The BirdWeather upload is (30, no fallback, no seek table), a saved detection (60,
+    fallback, seek_interval = rate)."""
+    lib = load_library()
+    x = _flac_clips(clips_pcm16, channels)
+    B, n = x.shape
+    res = (Loudness * B)()
+    cap = flac_max_bytes(B, n, seek_interval)
+    out = np.empty(cap, np.uint8)
+    offsets = np.zeros(B + 1, np.uint64)
+    lib.bnhip_loudness_flac_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_loudness_flac_pcm16(device, x.ctypes.data, B, n, int(rate), float(target_lufs), float(true_peak_dbtp),
+                                              float(max_gain_db), 1 if gate_fallback else 0, int(seek_interval), C.addressof(res),
+                                              out.ctypes.data, cap, offsets.ctypes.data))
+    return list(res), _flac_streams(out, offsets)
 
 
 def _sigmoid_f32div(x):

@@ -297,6 +297,38 @@ int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clip
                                     double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* d_out_pcm,
                                     bnhip_loudness* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* FLAC: the encoder behind every BirdWeather upload and every saved detection clip (flac.EncodePCMToBuffer / EncodePCM,
+ * internal/audiocore/flac/encode.go:79-175, 320-369; birdweather/encode_native.go:28-98), for a batch of mono int16 clips of one
+ * length in one call.  The bytes follow this project's own deterministic encoder spec (DESIGN.md §9 "FLAC", restated by
+ * tests/flacref.py): a valid RFC 9639 stream per clip - "fLaC", STREAMINFO (MD5 zero = unknown), a SEEKTABLE when
+ * seek_interval > 0 (a point for every seek_interval samples, as the reference's file path passes the sample rate), frames of 4096
+ * samples with CONSTANT, FIXED (orders 0..4, partition orders 0..5, Rice parameters 0..14, the exact minimum) or VERBATIM
+ * subframes.  All integer arithmetic: every byte is pinned.  LPC predictors, stereo, wasted bits and the MD5 are out of scope.
+ *   gain: factor (nullable, [n_clips]) is applied as the samples are read: exactly 1 is the identity, otherwise (double)pcm *
+ *   factor rounded half away from zero and saturated, the rule of bnhip_loudness_*.
+ *   output: the streams back to back; offsets[c] .. offsets[c + 1] is clip c's, offsets[n_clips] the bytes written.
+ * max_bytes:      the worst-case output size (every frame VERBATIM); out_cap must be at least that.
+ * encode_pcm16:   host memory in and out: one H2D copy, the kernels, a D2H copy of offsets, then of exactly offsets[n_clips] bytes.
+ * encode_device:  d_pcm, d_factor (nullable), d_out, d_offsets and d_workspace are device memory, d_workspace at least
+ *                 bnhip_flac_workspace_size bytes and 256-byte aligned; enqueued on hip_stream (NULL = default stream), not
+ *                 synchronised, nothing allocated; d_factor's values are the caller's business.
+ * bnhip_loudness_flac_pcm16: bnhip_loudness_normalize_pcm16 and bnhip_flac_encode_pcm16 in one call - the normalised clips stay on
+ *                 the device; the loudness records, the offsets and the compressed bytes return.
+ * BNHIP_E_INVALID: NULL / empty arguments, n < 1, n_clips outside 1..65535, rate outside 1..1048575, a negative seek_interval, a
+ * factor that is not finite or negative, out_cap below bnhip_flac_max_bytes, a workspace that is too small or misaligned, and for
+ * the fused entry what bnhip_loudness_normalize_pcm16 rejects.  Mono int16 only: the bindings answer BNHIP_E_UNSUPPORTED for
+ * anything else.  Argument errors are answered before any device is touched. */
+int bnhip_flac_max_bytes(int n_clips, int n, int seek_interval, size_t* bytes);
+int bnhip_flac_workspace_size(int n_clips, int n, size_t* bytes);
+int bnhip_flac_encode_device(int device, const int16_t* d_pcm, int n_clips, int n, int rate, const double* d_factor,
+                             int seek_interval, uint8_t* d_out, size_t out_cap, uint64_t* d_offsets, void* d_workspace,
+                             size_t workspace_bytes, void* hip_stream);
+int bnhip_flac_encode_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, const double* factor,
+                            int seek_interval, uint8_t* out, size_t out_cap, uint64_t* offsets);
+int bnhip_loudness_flac_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs,
+                              double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval,
+                              bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap, uint64_t* offsets);
+
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
  * pass through (NewResampler returns nil, :58-60); a too-small destination is an error before any work (:137-144).
