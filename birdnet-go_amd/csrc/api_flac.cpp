@@ -3,9 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <vector>
 
-#include "api_common.h"
+#include "api_oneshot.h"
 #include "flac.h"
 #include "loudness.h"
 
@@ -15,8 +14,7 @@ namespace {
 
 // what every entry checks before any device is touched; -> 0 or a negative BNHIP_E_*
 int dims_check(int n_clips, int n, int rate, int seek_interval) {
-    if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
-    if (n < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
+    if (const int rc = clip_dims_check(n_clips, n)) return rc;
     if (rate < 1 || rate > FLAC_MAX_RATE) return set_err(BNHIP_E_INVALID, "sample rate must be in [1, 1048575]");
     if (seek_interval < 0) return set_err(BNHIP_E_INVALID, "seek_interval must not be negative");
     return 0;
@@ -25,25 +23,6 @@ int dims_check(int n_clips, int n, int rate, int seek_interval) {
 int cap_check(int n_clips, int n, int seek_interval, size_t out_cap) {
     if (out_cap < flac_max_bytes(n_clips, n, seek_interval)) return set_err(BNHIP_E_INVALID, "out_cap smaller than bnhip_flac_max_bytes");
     return 0;
-}
-
-struct DevBlocks {
-    std::vector<void*> p;
-    hipError_t he = hipSuccess;
-    bool nomem = false;
-    void* get(size_t bytes) {
-        void* d = nullptr;
-        if (he == hipSuccess) he = hipMalloc(&d, bytes ? bytes : 1);
-        if (he == hipErrorOutOfMemory) nomem = true;
-        if (he == hipSuccess) p.push_back(d);
-        return d;
-    }
-    ~DevBlocks() { for (void* d : p) hipFree(d); }
-};
-
-int hip_fail(const char* what, const DevBlocks& b) {
-    (void)hipGetLastError();
-    return set_err(b.nomem ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(what) + ": " + hipGetErrorString(b.he));
 }
 
 // offsets first (that copy is the call's synchronise), then exactly offsets[n_clips] bytes
@@ -79,16 +58,12 @@ int bnhip_flac_encode_device(int device, const int16_t* d_pcm, int n_clips, int 
     BN_GUARD_BEGIN
     int rc = dims_check(n_clips, n, rate, seek_interval);
     if (!rc) rc = cap_check(n_clips, n, seek_interval, out_cap);
-    if (rc) return rc;
-    if (workspace_bytes < flac_workspace_bytes(n_clips, n)) return set_err(BNHIP_E_INVALID, "workspace smaller than bnhip_flac_workspace_size");
-    if (((uintptr_t)d_workspace & 255) != 0) return set_err(BNHIP_E_INVALID, "workspace must be 256-byte aligned");
-    rc = use_device(device);
+    if (!rc) rc = workspace_check(d_workspace, workspace_bytes, flac_workspace_bytes(n_clips, n), "bnhip_flac_workspace_size");
+    if (!rc) rc = use_device(device);
     if (rc) return rc;
     launch_flac(d_pcm, d_factor, flac_work(n_clips, n, rate, seek_interval, d_workspace), d_out, out_cap, (unsigned long long*)d_offsets,
                 reinterpret_cast<hipStream_t>(hip_stream));
-    const hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("flac_encode_device: ") + hipGetErrorString(he));
-    return BNHIP_OK;
+    return launch_status("flac_encode_device");
     BN_GUARD_END((void)0)
 }
 
@@ -118,8 +93,7 @@ int bnhip_flac_encode_pcm16(int device, const int16_t* pcm, int n_clips, int n, 
         b.he = hipGetLastError();
     }
     if (b.he == hipSuccess) b.he = fetch(d_offsets, d_bytes, n_clips, offsets, out);
-    if (b.he != hipSuccess) return hip_fail("flac_encode_pcm16", b);
-    return BNHIP_OK;
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("flac_encode_pcm16", b);
     BN_GUARD_END((void)0)
 }
 
@@ -151,8 +125,7 @@ int bnhip_loudness_flac_pcm16(int device, const int16_t* pcm, int n_clips, int n
     b.he = hipGetLastError();
     if (b.he == hipSuccess) b.he = hipMemcpy(out, d_res, (size_t)n_clips * sizeof(bnhip_loudness), hipMemcpyDeviceToHost);
     if (b.he == hipSuccess) b.he = fetch(d_offsets, d_bytes, n_clips, offsets, out_bytes);
-    if (b.he != hipSuccess) return hip_fail("loudness_flac_pcm16", b);
-    return BNHIP_OK;
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("loudness_flac_pcm16", b);
     BN_GUARD_END((void)0)
 }
 

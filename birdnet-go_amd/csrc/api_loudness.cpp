@@ -3,40 +3,25 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <mutex>
-#include <vector>
 
-#include "api_common.h"
+#include "api_oneshot.h"
 #include "loudness.h"
 
 using namespace bnhip;
 
 namespace {
 
-// the coefficient table of one (device, rate, segment length), uploaded on first use and kept; the oldest of kTableCap entries leaves.  A caller
-// holds g_mu from the lookup until its kernels are enqueued: hipFree waits for the device, so a table is never freed between a
-// lookup and the launch that reads it, nor under a queued kernel.
+// the coefficient table of one (device, rate, segment length); -> NULL on an allocation / copy failure
 struct LoudTable { int device, rate, seg_len; double* d; };
-constexpr size_t kTableCap = 32;
-std::mutex g_mu;
-std::vector<LoudTable> g_tables;
-
-// (g_mu held)  -> NULL on an allocation / copy failure
-const LoudTable* loud_table(int device, int rate, int seg_len) {
-    for (auto& e : g_tables) if (e.device == device && e.rate == rate && e.seg_len == seg_len) return &e;
-    if (g_tables.size() >= kTableCap) { hipFree(g_tables.front().d); g_tables.erase(g_tables.begin()); }
-    const std::vector<double> t = loudness_table(rate, seg_len);
-    double* d = nullptr;
-    if (hipMalloc((void**)&d, t.size() * 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (hipMemcpy(d, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); hipFree(d); return nullptr; }
-    g_tables.push_back({device, rate, seg_len, d});
-    return &g_tables.back();
+TableCache<LoudTable> g_tables;
+const LoudTable* loud_table(const TableLock& lk, int device, int rate, int seg_len) {
+    return g_tables.find(lk, [&](const LoudTable& e) { return e.device == device && e.rate == rate && e.seg_len == seg_len; },
+                         [&](LoudTable& e) { e = {device, rate, seg_len, upload_table(loudness_table(rate, seg_len))}; return e.d != nullptr; });
 }
 
 // what every entry checks before any device is touched (validateDims, audionorm.go:266-276); -> 0 or a negative BNHIP_E_*
 int dims_check(int n_clips, int n, int rate) {
-    if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
-    if (n < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
+    if (const int rc = clip_dims_check(n_clips, n)) return rc;
     if (rate < LOUD_MIN_RATE) return set_err(BNHIP_E_INVALID, "sample rate too low; minimum is 8000 Hz (K-weighting is undefined below it)");
     return 0;
 }
@@ -67,35 +52,26 @@ int run_pcm16(const char* what, int device, const int16_t* pcm, int n_clips, int
     if (rc) return rc;
     const int S = loudness_sub_block(rate);
     const size_t pcm_bytes = (size_t)n_clips * n * 2, ws_bytes = loudness_workspace_bytes(n_clips, n, S);
-    std::unique_lock<std::mutex> lk(g_mu);
-    const LoudTable* tab = loud_table(device, rate, S / loudness_split(n_clips, n, S));
+    TableLock lk(g_tables.mu);
+    const LoudTable* tab = loud_table(lk, device, rate, S / loudness_split(n_clips, n, S));
     if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (loudness table)");
-    int16_t *d_pcm = nullptr, *d_out_pcm = nullptr; bnhip_loudness* d_out = nullptr; void* d_ws = nullptr;
-    hipError_t he = hipMalloc((void**)&d_pcm, pcm_bytes);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_out, (size_t)n_clips * sizeof(bnhip_loudness));
-    if (he == hipSuccess) he = hipMalloc(&d_ws, ws_bytes);
-    if (he == hipSuccess && out_pcm) he = hipMalloc((void**)&d_out_pcm, pcm_bytes);
-    const bool nomem = he == hipErrorOutOfMemory;
-    if (he == hipSuccess) he = hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
+    DevBlocks b;
+    int16_t* d_pcm = (int16_t*)b.get(pcm_bytes);
+    bnhip_loudness* d_out = (bnhip_loudness*)b.get((size_t)n_clips * sizeof(bnhip_loudness));
+    void* d_ws = b.get(ws_bytes);
+    int16_t* d_out_pcm = out_pcm ? (int16_t*)b.get(pcm_bytes) : nullptr;
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
         const LoudWork w = loudness_work(n_clips, n, S, d_ws);
         launch_loudness(d_pcm, w, tab->d, plan, d_out, d_out_pcm, nullptr);
-        he = hipGetLastError();
+        b.he = hipGetLastError();
         lk.unlock();
         // (the null stream orders the copies after the kernels; the first one is the call's synchronise)
-        if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n_clips * sizeof(bnhip_loudness), hipMemcpyDeviceToHost);
-        if (he == hipSuccess && out_pcm) he = hipMemcpy(out_pcm, d_out_pcm, pcm_bytes, hipMemcpyDeviceToHost);
-        if (he == hipSuccess && sub_energy && w.Ns > 0) he = hipMemcpy(sub_energy, w.E1, (size_t)n_clips * w.Ns * 8, hipMemcpyDeviceToHost);
+        if (b.he == hipSuccess) b.he = hipMemcpy(out, d_out, (size_t)n_clips * sizeof(bnhip_loudness), hipMemcpyDeviceToHost);
+        if (b.he == hipSuccess && out_pcm) b.he = hipMemcpy(out_pcm, d_out_pcm, pcm_bytes, hipMemcpyDeviceToHost);
+        if (b.he == hipSuccess && sub_energy && w.Ns > 0) b.he = hipMemcpy(sub_energy, w.E1, (size_t)n_clips * w.Ns * 8, hipMemcpyDeviceToHost);
     }
-    if (d_pcm) hipFree(d_pcm);
-    if (d_out) hipFree(d_out);
-    if (d_ws) hipFree(d_ws);
-    if (d_out_pcm) hipFree(d_out_pcm);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(nomem ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(what) + ": " + hipGetErrorString(he));
-    }
-    return BNHIP_OK;
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail(what, b);
 }
 
 }  // namespace
@@ -110,14 +86,12 @@ int loudness_args_check(int n_clips, int n, int rate, double target, double ceil
 int loudness_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, int n, int rate, double target, double ceiling,
                      double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace, hipStream_t s) {
     const int S = loudness_sub_block(rate);
-    std::lock_guard<std::mutex> lk(g_mu);
-    const LoudTable* tab = loud_table(device, rate, S / loudness_split(n_clips, n, S));
+    TableLock lk(g_tables.mu);
+    const LoudTable* tab = loud_table(lk, device, rate, S / loudness_split(n_clips, n, S));
     if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (loudness table)");
     launch_loudness(d_pcm, loudness_work(n_clips, n, S, d_workspace), tab->d, make_plan(target, ceiling, max_gain, gate_fallback, 0), d_out,
                     d_out_pcm, s);
-    const hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string(what) + ": " + hipGetErrorString(he));
-    return BNHIP_OK;
+    return launch_status(what);
 }
 
 }  // namespace bnhip
@@ -137,8 +111,7 @@ int bnhip_loudness_normalize_pcm16(int device, const int16_t* pcm, int n_clips, 
                                    double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* out_pcm, bnhip_loudness* out) {
     if (!pcm || !out) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
     BN_GUARD_BEGIN
-    int rc = dims_check(n_clips, n, rate);
-    if (!rc) rc = plan_check(target_lufs, true_peak_dbtp, max_gain_db);
+    int rc = loudness_args_check(n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db);
     if (rc) return rc;
     return run_pcm16("loudness_normalize_pcm16", device, pcm, n_clips, n, rate,
                      make_plan(target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, 0), out_pcm, out, nullptr);
@@ -158,12 +131,10 @@ int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clip
                                     bnhip_loudness* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
     if (!d_pcm || !d_out || !d_workspace) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
     BN_GUARD_BEGIN
-    int rc = dims_check(n_clips, n, rate);
-    if (!rc) rc = plan_check(target_lufs, true_peak_dbtp, max_gain_db);
-    if (rc) return rc;
-    if (workspace_bytes < loudness_workspace_bytes(n_clips, n, loudness_sub_block(rate))) return set_err(BNHIP_E_INVALID, "workspace smaller than bnhip_loudness_workspace_size");
-    if (((uintptr_t)d_workspace & 255) != 0) return set_err(BNHIP_E_INVALID, "workspace must be 256-byte aligned");
-    rc = use_device(device);
+    int rc = loudness_args_check(n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db);
+    if (!rc) rc = workspace_check(d_workspace, workspace_bytes, loudness_workspace_bytes(n_clips, n, loudness_sub_block(rate)),
+                                  "bnhip_loudness_workspace_size");
+    if (!rc) rc = use_device(device);
     if (rc) return rc;
     return loudness_enqueue("loudness_normalize_device", device, d_pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback,
                             d_out, d_out_pcm, d_workspace, reinterpret_cast<hipStream_t>(hip_stream));

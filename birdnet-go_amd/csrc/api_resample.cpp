@@ -3,6 +3,7 @@
 
 #include <numeric>
 
+#include "api_oneshot.h"
 #include "kernels.h"
 #include "resample.h"
 #include "stream_bank.h"
@@ -85,23 +86,18 @@ static int resample_impl(int device, const void* in, bool pcm16, int n_clips, in
     if (rc) return rc;
     std::vector<float> table;
     const ResamplePlan p = resample_plan(rate_in, rate_out, &table);
-    void *d_in = nullptr, *d_out = nullptr; float* d_tab = nullptr;
-    hipError_t he = hipMalloc(&d_in, (size_t)n_clips * n_in * esz);
-    if (he == hipSuccess) he = hipMalloc(&d_out, (size_t)n_clips * no * esz);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_tab, table.size() * 4);
-    if (he == hipSuccess) he = hipMemcpy(d_in, in, (size_t)n_clips * n_in * esz, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(d_tab, table.data(), table.size() * 4, hipMemcpyHostToDevice);
-    int lrc = 0;
-    if (he == hipSuccess) {
-        lrc = launch_resample(d_in, d_out, d_tab, pcm16, pcm16, n_clips, n_in, no, p.L, p.M, p.T, p.half, 0, 0, nullptr);
-        if (lrc == 0) he = hipMemcpy(out, d_out, (size_t)n_clips * no * esz, hipMemcpyDeviceToHost);
+    DevBlocks b;
+    void* d_in = b.get((size_t)n_clips * n_in * esz);
+    void* d_out = b.get((size_t)n_clips * no * esz);
+    float* d_tab = (float*)b.get(table.size() * 4);
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_in, in, (size_t)n_clips * n_in * esz, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_tab, table.data(), table.size() * 4, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
+        if (launch_resample(d_in, d_out, d_tab, pcm16, pcm16, n_clips, n_in, no, p.L, p.M, p.T, p.half, 0, 0, nullptr))
+            return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+        b.he = hipMemcpy(out, d_out, (size_t)n_clips * no * esz, hipMemcpyDeviceToHost);
     }
-    if (d_in) hipFree(d_in);
-    if (d_out) hipFree(d_out);
-    if (d_tab) hipFree(d_tab);
-    if (lrc) return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
-    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("resample: ") + hipGetErrorString(he));
-    return BNHIP_OK;
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("resample", b);
 }
 
 int bnhip_resample_f32(int device, const float* in, int n_clips, int n_in, int rate_in, int rate_out, float* out, int n_out_cap,

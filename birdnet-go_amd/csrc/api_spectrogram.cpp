@@ -3,11 +3,9 @@
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <numeric>
-#include <vector>
 
-#include "api_common.h"
+#include "api_oneshot.h"
 #include "kernels.h"
 #include "resample.h"
 #include "spectrogram.h"
@@ -24,54 +22,42 @@ int fft_friendly_height(int width) {
     return n + 1;
 }
 
-// twiddles + window of one (device, N, window contents), uploaded on first use and kept; the oldest of kTableCap entries leaves.
-// A caller holds g_mu from the lookup until its kernels are enqueued: hipFree waits for the device, so a table is never freed
-// between a lookup and the launch that reads it, nor under a queued kernel.
+// twiddles + window of one (device, N, window contents); window == NULL: periodic Hann, 0.5 - 0.5 cos(2 pi i / N).
+// -> NULL on an allocation / copy failure
 struct SpecTable { int device, N; std::vector<double> window; double wsum; double* d; };
-constexpr size_t kTableCap = 32;
-std::mutex g_mu;
-std::vector<SpecTable> g_tables;
-
-// (g_mu held)  window == NULL: periodic Hann, 0.5 - 0.5 cos(2 pi i / N).  -> NULL on an allocation / copy failure
-const SpecTable* spec_table(int device, int N, const double* window) {
+TableCache<SpecTable> g_tables;
+const SpecTable* spec_table(const TableLock& lk, int device, int N, const double* window) {
     std::vector<double> w((size_t)N);
     for (int i = 0; i < N; i++)
         w[i] = window ? window[i] : 0.5 - 0.5 * std::cos(6.283185307179586476925286766559 * (double)i / (double)N);
-    for (auto& e : g_tables) if (e.device == device && e.N == N && e.window == w) return &e;
-    if (g_tables.size() >= kTableCap) { hipFree(g_tables.front().d); g_tables.erase(g_tables.begin()); }
-    double wsum = 0.0;
-    for (int i = 0; i < N; i++) wsum += w[i];
-    const std::vector<double> t = spectrogram_table(N, w.data());
-    double* d = nullptr;
-    if (hipMalloc((void**)&d, t.size() * 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (hipMemcpy(d, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); hipFree(d); return nullptr; }
-    g_tables.push_back({device, N, std::move(w), wsum, d});
-    return &g_tables.back();
+    return g_tables.find(lk, [&](const SpecTable& e) { return e.device == device && e.N == N && e.window == w; }, [&](SpecTable& e) {
+        double wsum = 0.0;
+        for (int i = 0; i < N; i++) wsum += w[i];
+        double* d = upload_table(spectrogram_table(N, w.data()));
+        e = {device, N, std::move(w), wsum, d};
+        return d != nullptr;
+    });
 }
 
-// (g_mu held)  the one-shot resampler's phase table of one (device, rate pair), kept like the window tables
+// the one-shot resampler's phase table of one (device, rate pair), under g_tables.mu like the window tables
 struct RateTable { int device, rate_in, rate_out, L, M, T, half; float* d; };
-std::vector<RateTable> g_rates;
-const RateTable* rate_table(int device, int rate_in, int rate_out) {
-    for (auto& e : g_rates) if (e.device == device && e.rate_in == rate_in && e.rate_out == rate_out) return &e;
-    if (g_rates.size() >= kTableCap) { if (g_rates.front().d) hipFree(g_rates.front().d); g_rates.erase(g_rates.begin()); }
-    const int g = std::gcd(rate_in, rate_out);
-    RateTable r{device, rate_in, rate_out, rate_out / g, rate_in / g, 0, 0, nullptr};
-    std::vector<float> table;
-    resample_design(r.L, r.M, RESAMPLE_BETA, RESAMPLE_HALF_FACTOR, &table, &r.T, &r.half);
-    if (resample_lds(r.L, r.M, r.T) <= RESAMPLE_LDS_MAX) {            // (d stays NULL for a geometry that cannot run)
-        if (hipMalloc((void**)&r.d, table.size() * 4) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        if (hipMemcpy(r.d, table.data(), table.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); hipFree(r.d); return nullptr; }
-    }
-    g_rates.push_back(r);
-    return &g_rates.back();
+TableCache<RateTable> g_rates;
+const RateTable* rate_table(const TableLock& lk, int device, int rate_in, int rate_out) {
+    return g_rates.find(lk, [&](const RateTable& e) { return e.device == device && e.rate_in == rate_in && e.rate_out == rate_out; },
+                        [&](RateTable& r) {
+        const int g = std::gcd(rate_in, rate_out);
+        r = {device, rate_in, rate_out, rate_out / g, rate_in / g, 0, 0, nullptr};
+        std::vector<float> table;
+        resample_design(r.L, r.M, RESAMPLE_BETA, RESAMPLE_HALF_FACTOR, &table, &r.T, &r.half);
+        if (resample_lds(r.L, r.M, r.T) > RESAMPLE_LDS_MAX) return true;          // (d stays NULL for a geometry that cannot run)
+        return (r.d = upload_table(table)) != nullptr;
+    });
 }
 
 // what both render entries check before any device is touched; -> the transform length, or a negative BNHIP_E_*
 int spec_check(int n_clips, int n, int width, int height, const double* window, double top_db, double range_db) {
     if (n_clips <= 0) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
-    if (n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
-    if (n < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
+    if (const int rc = clip_dims_check(n_clips, n)) return rc;
     if (width < 1 || width > 4096) return set_err(BNHIP_E_INVALID, "width must be in [1, 4096]");
     if (height < 2 || ((height - 1) & (height - 2)) != 0) return set_err(BNHIP_E_INVALID, "height must be 2^k + 1");
     if (!std::isfinite(range_db) || range_db <= 0.0) return set_err(BNHIP_E_INVALID, "range_db must be finite and positive");
@@ -112,37 +98,33 @@ int bnhip_spectrogram_pcm16(int device, const int16_t* pcm, int n_clips, int n, 
     if (resample && (rate_in <= 0 || rate_out < 0)) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
     int rc = use_device(device);
     if (rc) return rc;
-    std::unique_lock<std::mutex> lk(g_mu);
+    TableLock lk(g_tables.mu);
     const RateTable* rt = nullptr;
     int n_render = n;
     if (resample) {
-        rt = rate_table(device, rate_in, rate_out);
+        rt = rate_table(lk, device, rate_in, rate_out);
         if (!rt) return set_err(BNHIP_E_NOMEM, "device allocation failed (resampler phase table)");
         if (!rt->d) return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
         n_render = bnhip_resample_length(n, rate_in, rate_out);
         if (n_render < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
     }
-    const SpecTable* tab = spec_table(device, N, window);
+    const SpecTable* tab = spec_table(lk, device, N, window);
     if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (spectrogram table)");
     const size_t img_bytes = (size_t)n_clips * height * width;
-    int16_t* d_pcm = nullptr; float* d_f32 = nullptr; uint8_t* d_img = nullptr;
-    hipError_t he = hipMalloc((void**)&d_pcm, (size_t)n_clips * n * 2);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_img, img_bytes);
-    if (he == hipSuccess && resample) he = hipMalloc((void**)&d_f32, (size_t)n_clips * n_render * 4);
-    if (he == hipSuccess) he = hipMemcpy(d_pcm, pcm, (size_t)n_clips * n * 2, hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
+    DevBlocks b;
+    int16_t* d_pcm = (int16_t*)b.get((size_t)n_clips * n * 2);
+    uint8_t* d_img = (uint8_t*)b.get(img_bytes);
+    float* d_f32 = resample ? (float*)b.get((size_t)n_clips * n_render * 4) : nullptr;
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_pcm, pcm, (size_t)n_clips * n * 2, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
         if (resample) launch_resample(d_pcm, d_f32, rt->d, 1, 0, n_clips, n, n_render, rt->L, rt->M, rt->T, rt->half, 0, 0, nullptr);
         launch_spectrogram(resample ? (const void*)d_f32 : (const void*)d_pcm, resample ? 1 : 0, n_clips, n_render, width, height, tab->d,
                            tab->wsum, top_db, range_db, d_img, nullptr);
-        he = hipGetLastError();
+        b.he = hipGetLastError();
         lk.unlock();
-        if (he == hipSuccess) he = hipMemcpy(image, d_img, img_bytes, hipMemcpyDeviceToHost);      // (the call's one synchronise)
+        if (b.he == hipSuccess) b.he = hipMemcpy(image, d_img, img_bytes, hipMemcpyDeviceToHost);  // (the call's one synchronise)
     }
-    if (d_pcm) hipFree(d_pcm);
-    if (d_f32) hipFree(d_f32);
-    if (d_img) hipFree(d_img);
-    if (he != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_RUNTIME, std::string("spectrogram_pcm16: ") + hipGetErrorString(he)); }
-    return BNHIP_OK;
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("spectrogram_pcm16", b);
     BN_GUARD_END((void)0)
 }
 
@@ -154,14 +136,12 @@ int bnhip_spectrogram_device(int device, const void* d_samples, int f32, int n_c
     if (N < 0) return N;
     int rc = use_device(device);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    const SpecTable* tab = spec_table(device, N, window);
+    TableLock lk(g_tables.mu);
+    const SpecTable* tab = spec_table(lk, device, N, window);
     if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (spectrogram table)");
     launch_spectrogram(d_samples, f32 != 0, n_clips, n, width, height, tab->d, tab->wsum, top_db, range_db, d_image,
                        reinterpret_cast<hipStream_t>(hip_stream));
-    const hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("spectrogram_device: ") + hipGetErrorString(he));
-    return BNHIP_OK;
+    return launch_status("spectrogram_device");
     BN_GUARD_END((void)0)
 }
 

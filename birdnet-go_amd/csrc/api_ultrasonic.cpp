@@ -1,29 +1,19 @@
 // C ABI of the ultrasonic filter's frame-power coefficient of variation (bnhip_us_frame_cv, bnhip_us_frame_cv_device).
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <utility>
-#include <vector>
-
-#include "api_common.h"
+#include "api_oneshot.h"
 #include "kernels.h"
 
 using namespace bnhip;
 
 namespace {
 
-// twiddle tables of the ultrasonic FFT, one per (device, fft size), uploaded on first use and kept for the process
-std::mutex g_tw_mu;
-std::vector<std::pair<std::pair<int, int>, double*>> g_tw;
-const double* us_twiddles(int device, int fft_size) {
-    std::lock_guard<std::mutex> lk(g_tw_mu);
-    for (auto& e : g_tw) if (e.first.first == device && e.first.second == fft_size) return e.second;
-    std::vector<double> t = us_twiddle_table(fft_size);
-    double* d = nullptr;
-    if (hipMalloc((void**)&d, t.size() * 8) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return nullptr; }
-    g_tw.push_back({{device, fft_size}, d});
-    return d;
+// the twiddle table of the ultrasonic FFT of one (device, fft size); -> NULL on an allocation / copy failure
+struct TwiddleTable { int device, fft_size; double* d; };
+TableCache<TwiddleTable> g_tw;
+const TwiddleTable* us_twiddles(const TableLock& lk, int device, int fft_size) {
+    return g_tw.find(lk, [&](const TwiddleTable& e) { return e.device == device && e.fft_size == fft_size; },
+                     [&](TwiddleTable& e) { e = {device, fft_size, upload_table(us_twiddle_table(fft_size))}; return e.d != nullptr; });
 }
 
 // The geometry of a call, before any device is touched.  -> the frame count (>= 2) with *split_bin set; 0 when the filter's
@@ -56,25 +46,22 @@ int bnhip_us_frame_cv(int device, const double* samples, int n_clips, int n, int
     }
     int rc = use_device(device);
     if (rc) return rc;
-    double *d_s = nullptr, *d_p = nullptr, *d_cv = nullptr;
-    hipError_t he = hipMalloc((void**)&d_s, (size_t)n_clips * n * 8);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_p, (size_t)n_clips * frames * 8);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_cv, (size_t)n_clips * 8);
-    if (he == hipSuccess) he = hipMemcpy(d_s, samples, (size_t)n_clips * n * 8, hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-        const double* d_tw = us_twiddles(device, fft_size);
-        if (!d_tw) he = hipErrorOutOfMemory;
-        else {
-            launch_us_frame_power(d_s, 0, n_clips, n, fft_size, hop, frames, split_bin, d_tw, d_p, nullptr);
-            launch_us_cv(d_p, n_clips, frames, d_cv, nullptr);
-            he = hipGetLastError();
-            if (he == hipSuccess) he = hipMemcpy(cv, d_cv, (size_t)n_clips * 8, hipMemcpyDeviceToHost);
-        }
+    TableLock lk(g_tw.mu);
+    const TwiddleTable* tw = us_twiddles(lk, device, fft_size);
+    if (!tw) return set_err(BNHIP_E_NOMEM, "device allocation failed (FFT twiddle table)");
+    DevBlocks b;
+    double* d_s = (double*)b.get((size_t)n_clips * n * 8);
+    double* d_p = (double*)b.get((size_t)n_clips * frames * 8);
+    double* d_cv = (double*)b.get((size_t)n_clips * 8);
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_s, samples, (size_t)n_clips * n * 8, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
+        launch_us_frame_power(d_s, 0, n_clips, n, fft_size, hop, frames, split_bin, tw->d, d_p, nullptr);
+        launch_us_cv(d_p, n_clips, frames, d_cv, nullptr);
+        b.he = hipGetLastError();
+        lk.unlock();
+        if (b.he == hipSuccess) b.he = hipMemcpy(cv, d_cv, (size_t)n_clips * 8, hipMemcpyDeviceToHost);
     }
-    if (d_s) hipFree(d_s);
-    if (d_p) hipFree(d_p);
-    if (d_cv) hipFree(d_cv);
-    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("us_frame_cv: ") + hipGetErrorString(he));
+    if (b.he != hipSuccess) return hip_fail("us_frame_cv", b);
     for (int i = 0; i < n_clips; i++) ok[i] = 1;
     return BNHIP_OK;
     BN_GUARD_END((void)0)
@@ -93,13 +80,13 @@ int bnhip_us_frame_cv_device(int device, const void* d_samples, int pcm16, int n
     int rc = use_device(device);
     if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const double* d_tw = us_twiddles(device, fft_size);
-    if (!d_tw) return set_err(BNHIP_E_NOMEM, "device allocation failed (FFT twiddle table)");
-    launch_us_frame_power(d_samples, pcm16 != 0, n_clips, n, fft_size, hop, frames, split_bin, d_tw, d_scratch, st);
+    TableLock lk(g_tw.mu);
+    const TwiddleTable* tw = us_twiddles(lk, device, fft_size);
+    if (!tw) return set_err(BNHIP_E_NOMEM, "device allocation failed (FFT twiddle table)");
+    launch_us_frame_power(d_samples, pcm16 != 0, n_clips, n, fft_size, hop, frames, split_bin, tw->d, d_scratch, st);
     launch_us_cv(d_scratch, n_clips, frames, d_cv, st);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return set_err(BNHIP_E_RUNTIME, std::string("us_frame_cv_device: ") + hipGetErrorString(he));
-    return frames;
+    rc = launch_status("us_frame_cv_device");
+    return rc ? rc : frames;
     BN_GUARD_END((void)0)
 }
 

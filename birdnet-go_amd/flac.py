@@ -10,20 +10,7 @@ Mono int16 only.  The bytes follow the project's own encoder spec (DESIGN.md §9
 import numpy as np
 
 from . import host as _host
-from .loudness import DEFAULT_MAX_GAIN_DB, default_options, factor_from_db
-
-
-def _burst(clips):
-    """The clips as contiguous arrays and their indices grouped by length (one device call per length)."""
-    clips = [np.ascontiguousarray(c) for c in clips]
-    for c in clips:
-        if c.dtype != np.int16 or c.ndim != 1 or c.size == 0:
-            raise _host.HipError(_host.E_UNSUPPORTED if c.ndim != 1 or c.dtype != np.int16 else _host.E_INVALID,
-                                 "clips must be non-empty mono int16 arrays")
-    groups = {}
-    for i, c in enumerate(clips):
-        groups.setdefault(c.size, []).append(i)
-    return clips, groups
+from .loudness import DEFAULT_MAX_GAIN_DB, _burst, default_options, factor_from_db
 
 
 def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0):

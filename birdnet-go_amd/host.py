@@ -458,18 +458,29 @@ class Loudness(C.Structure):
         return bool(self.flags & LOUDNESS_CLAMPED)
 
 
-def _loudness_clips(clips_pcm16, channels):
-    """int16 [B, n] of a batch (or one clip [n]); anything but mono is BNHIP_E_UNSUPPORTED (conf.NumChannels is 1)."""
+def _mono_pcm16_clips(what, clips_pcm16, channels):
+    """int16 [B, n] of a batch (or one clip [n]) for the `what` entries ("loudness", "FLAC"); anything but mono int16 is
+    BNHIP_E_UNSUPPORTED (conf.NumChannels is 1)."""
     if int(channels) != 1:
-        raise HipError(E_UNSUPPORTED, f"loudness entries are mono, got {channels} channels")
+        raise HipError(E_UNSUPPORTED, f"{what} entries are mono, got {channels} channels")
     x = np.ascontiguousarray(clips_pcm16)
     if x.dtype != np.int16:
-        raise HipError(E_UNSUPPORTED, f"loudness entries take int16 PCM, got {x.dtype}")
+        raise HipError(E_UNSUPPORTED, f"{what} entries take int16 PCM, got {x.dtype}")
     if x.ndim == 1:
         x = x[None, :]
     if x.ndim != 2 or x.shape[0] == 0 or x.shape[1] == 0:
         raise HipError(E_INVALID, "clips must be a non-empty int16 [B, n] array")
     return x
+
+
+def _size_query(entry, *ints):
+    """A size entry of the C ABI (ints in, one size_t out) -> the bytes it answers."""
+    lib = load_library()
+    fn = getattr(lib, entry)
+    fn.argtypes = [C.c_int] * len(ints) + [C.POINTER(C.c_size_t)]
+    b = C.c_size_t(0)
+    _check(lib, fn(*(int(v) for v in ints), C.byref(b)))
+    return b.value
 
 
 def loudness_sub_block(rate):
@@ -482,7 +493,7 @@ def loudness_measure(clips_pcm16, rate, sub_energy=False, channels=1, device=0):
     int16 [B, n] (or [n]) at `rate` Hz -> list of B Loudness; with sub_energy also the float64 [B, n // S] K-weighted sub-block
     energies.  Spec: DESIGN.md §9."""
     lib = load_library()
-    x = _loudness_clips(clips_pcm16, channels)
+    x = _mono_pcm16_clips("loudness", clips_pcm16, channels)
     out = (Loudness * x.shape[0])()
     sub = np.zeros((x.shape[0], x.shape[1] // max(1, loudness_sub_block(rate))), np.float64) if sub_energy else None
     lib.bnhip_loudness_measure_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -497,7 +508,7 @@ def loudness_normalize(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0
     [B, n] output or None for apply=False).  (max_gain_db 60, gate_fallback) is the export plan (actions_database.go:1392-1438),
     (30, no fallback) the BirdWeather upload's (encode_native.go:25-66)."""
     lib = load_library()
-    x = _loudness_clips(clips_pcm16, channels)
+    x = _mono_pcm16_clips("loudness", clips_pcm16, channels)
     out = (Loudness * x.shape[0])()
     y = np.empty_like(x) if apply else None
     lib.bnhip_loudness_normalize_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
@@ -510,11 +521,7 @@ def loudness_normalize(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0
 
 def loudness_workspace_size(n_clips, n, rate):
     """Bytes of device scratch loudness_normalize_device needs."""
-    lib = load_library()
-    lib.bnhip_loudness_workspace_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-    b = C.c_size_t(0)
-    _check(lib, lib.bnhip_loudness_workspace_size(int(n_clips), int(n), int(rate), C.byref(b)))
-    return b.value
+    return _size_query("bnhip_loudness_workspace_size", n_clips, n, rate)
 
 
 def loudness_normalize_device(d_pcm_ptr, n_clips, n, rate, d_out_ptr, d_workspace_ptr, workspace_bytes, d_out_pcm_ptr=None,
@@ -531,34 +538,12 @@ def loudness_normalize_device(d_pcm_ptr, n_clips, n, rate, d_out_ptr, d_workspac
 
 def flac_max_bytes(n_clips, n, seek_interval=0):
     """The worst-case bytes of n_clips streams of n samples (every frame VERBATIM): the out_cap the encode entries ask for."""
-    lib = load_library()
-    lib.bnhip_flac_max_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-    b = C.c_size_t(0)
-    _check(lib, lib.bnhip_flac_max_bytes(int(n_clips), int(n), int(seek_interval), C.byref(b)))
-    return b.value
+    return _size_query("bnhip_flac_max_bytes", n_clips, n, seek_interval)
 
 
 def flac_workspace_size(n_clips, n):
     """Bytes of device scratch flac_encode_device needs."""
-    lib = load_library()
-    lib.bnhip_flac_workspace_size.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-    b = C.c_size_t(0)
-    _check(lib, lib.bnhip_flac_workspace_size(int(n_clips), int(n), C.byref(b)))
-    return b.value
-
-
-def _flac_clips(clips_pcm16, channels):
-    """As _loudness_clips: mono int16 [B, n] or BNHIP_E_UNSUPPORTED."""
-    if int(channels) != 1:
-        raise HipError(E_UNSUPPORTED, f"FLAC entries are mono, got {channels} channels")
-    x = np.ascontiguousarray(clips_pcm16)
-    if x.dtype != np.int16:
-        raise HipError(E_UNSUPPORTED, f"FLAC entries take int16 PCM, got {x.dtype}")
-    if x.ndim == 1:
-        x = x[None, :]
-    if x.ndim != 2 or x.shape[0] == 0 or x.shape[1] == 0:
-        raise HipError(E_INVALID, "clips must be a non-empty int16 [B, n] array")
-    return x
+    return _size_query("bnhip_flac_workspace_size", n_clips, n)
 
 
 def _flac_streams(buf, offsets):
@@ -570,7 +555,7 @@ def flac_encode(clips_pcm16, rate, factor=None, seek_interval=0, channels=1, dev
     flac.EncodePCM writes to a file): int16 [B, n] (or [n]) -> list of B bytes objects.  factor: per-clip gain applied on the device
     first (None = none).  raw: (the uint8 buffer as written, offsets uint64 [B + 1]) instead.  Spec: DESIGN.md §9."""
     lib = load_library()
-    x = _flac_clips(clips_pcm16, channels)
+    x = _mono_pcm16_clips("FLAC", clips_pcm16, channels)
     B, n = x.shape
     fac = None if factor is None else np.ascontiguousarray(factor, np.float64).reshape(-1)
     if fac is not None and fac.size != B:
@@ -602,7 +587,7 @@ def loudness_flac(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max
     Loudness, list of B bytes objects).  The BirdWeather upload is (30, no fallback, no seek table), a saved detection (60,
     fallback, seek_interval = rate)."""
     lib = load_library()
-    x = _flac_clips(clips_pcm16, channels)
+    x = _mono_pcm16_clips("FLAC", clips_pcm16, channels)
     B, n = x.shape
     res = (Loudness * B)()
     cap = flac_max_bytes(B, n, seek_interval)

@@ -69,10 +69,8 @@ def factor_from_db(gain_db):
     return 1.0 if gain_db == 0 else math.pow(10.0, gain_db / 20.0)
 
 
-def normalize_clips(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, apply=True, device=0):
-    """A burst of detections: a list of int16 mono clips of any lengths -> (list of host.Loudness, list of int16 outputs or None),
-    both in the input's order.  Clips are grouped by length, one device call per length."""
-    opts = opts or default_options()
+def _burst(clips):
+    """The clips as contiguous arrays and their indices grouped by length (one device call per length)."""
     clips = [np.ascontiguousarray(c) for c in clips]
     for c in clips:
         if c.dtype != np.int16 or c.ndim != 1 or c.size == 0:
@@ -81,6 +79,14 @@ def normalize_clips(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_
     groups = {}
     for i, c in enumerate(clips):
         groups.setdefault(c.size, []).append(i)
+    return clips, groups
+
+
+def normalize_clips(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, apply=True, device=0):
+    """A burst of detections: a list of int16 mono clips of any lengths -> (list of host.Loudness, list of int16 outputs or None),
+    both in the input's order.  Clips are grouped by length, one device call per length."""
+    opts = opts or default_options()
+    clips, groups = _burst(clips)
     results, outputs = [None] * len(clips), [None] * len(clips)
     for idx in groups.values():
         res, out = _host.loudness_normalize(np.stack([clips[i] for i in idx]), sample_rate, opts.target_lufs, opts.true_peak_dbtp,

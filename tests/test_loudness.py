@@ -253,3 +253,16 @@ def test_normalize_clips_groups_a_burst_by_length(gpu):
         assert np.array_equal(got, want)
     res, out = loudness.normalize_clips(burst, rate, apply=False)
     assert out is None and len(res) == 5 and not any(g.flags & R.GATE_LIFTED for g in res)
+
+
+def test_coefficient_table_evicted_and_rebuilt(gpu):
+    """The table cache holds 32 entries and the oldest leaves: 40 rates evict and rebuild the first one."""
+    rng = np.random.default_rng(40)
+    clip = noise(rng, 3300, 0.1)[None, :]                         # about four sub-blocks at 8 kHz
+    first = bytes(host.loudness_measure(clip, 8000)[0])
+    for i in range(1, 40):
+        last = host.loudness_measure(clip, 8000 + i, sub_energy=True)
+    assert bytes(host.loudness_measure(clip, 8000)[0]) == first
+    (g,), sub = last
+    check_measurement("evict", 0, g, R.measure(clip[0], 8039), sub[0])
+    assert (g.gain_db, g.factor, g.flags) == (0.0, 1.0, 0)

@@ -188,3 +188,50 @@ def test_generate_batch_writes_the_wrapper_s_indices(gpu, tmp_path):
     sg.generate_from_pcm(clips[2].astype("<i2").tobytes(), str(one), 258, 48000)
     idx, _ = decode_png(one)
     assert np.array_equal(idx, host.spectrogram(clips[2], 48000, 258, rate_out=24000)[0])
+
+
+# ---- the table caches hold 32 entries and the oldest leaves: 40 distinct keys evict and rebuild the first one
+EVICT = dict(width=20, height=33, n=3000, keys=40)                # N = 64, the smallest legal transform
+
+
+def evict_window(i):
+    """Key i of 40: periodic Hann plus a small ramp of its own."""
+    return specref.hann(64) + 1e-3 * (i + 1) * np.arange(64) / 64.0
+
+
+def test_window_table_evicted_and_rebuilt(gpu):
+    clip, W, H = signal("noise_33", EVICT["n"]), EVICT["width"], EVICT["height"]
+    imgs = [render(clip, W, H, window=evict_window(i)) for i in range(EVICT["keys"])]
+    assert not np.array_equal(imgs[0], imgs[39])
+    assert np.array_equal(render(clip, W, H, window=evict_window(0)), imgs[0])
+    check(imgs[39], [clip], W, H, window=evict_window(39))
+
+
+def test_window_table_evicted_and_rebuilt_device_entry(gpu):
+    clip, W, H, n = signal("noise_33", EVICT["n"]), EVICT["width"], EVICT["height"], EVICT["n"]
+    d_in, d_img = _DevBuf(clip.nbytes), _DevBuf(H * W)
+    try:
+        d_in.upload(np.ascontiguousarray(clip))
+        def go(i):
+            host.spectrogram_device(d_in.ptr, False, 1, n, W, H, d_img.ptr, window=evict_window(i))
+            return d_img.download((1, H, W), np.uint8)
+        imgs = [go(i) for i in range(EVICT["keys"])]
+        again = go(0)
+    finally:
+        d_in.free(); d_img.free()
+    assert not np.array_equal(imgs[0], imgs[39])
+    assert np.array_equal(again, imgs[0])
+    check(imgs[39], [clip], W, H, window=evict_window(39))
+
+
+def test_rate_table_evicted_and_rebuilt(gpu):
+    """rate_in = 48000 + 100 i to 24000: L / M = 240 / (480 + i) in lowest terms; the largest phase table and span of the 40 (i = 37,
+    L = 240, M = 517, T = 44) need 44 620 bytes of LDS, far below the limit, so every pair runs."""
+    clip, W, H = signal("noise_33", EVICT["n"]), EVICT["width"], EVICT["height"]
+    rates = [48000 + 100 * i for i in range(EVICT["keys"])]
+    imgs = [render(clip, W, H, rate_in=r, rate_out=24000) for r in rates]
+    assert not np.array_equal(imgs[0], imgs[39])
+    assert np.array_equal(render(clip, W, H, rate_in=rates[0], rate_out=24000), imgs[0])
+    f32 = host.Resampler(rates[39], 24000).resample_f32(clip.astype(np.float32)[None, :] / np.float32(32768.0))
+    assert np.array_equal(imgs[39], device_render(f32, True, 1, f32.shape[1], W, H))
+    specref.compare(imgs[39][0], f32[0].astype(np.float64), W, H)
