@@ -1,8 +1,10 @@
-// FLAC encoding of a batch of clips (DESIGN.md §9 "FLAC"): all integer arithmetic, every frame independent.
+// FLAC encoding of a batch of clips (DESIGN.md §9 "FLAC"): integer arithmetic but for the LPC coefficients' fp64 recursion, every
+// frame independent.
 //
 //   analyse   one block per frame: the gained samples in LDS, the residuals of FIXED orders 0..4 (one wave per order), the sums
 //             S[o][p][k] = sum of (u >> k) over the frame's finest partitions; coarser partitions are exact sums of those.  Then
-//             the exact choice over (o, P, k) and one record per frame.
+//             the exact choice over (o, P, k) and one record per frame.  With lpc_order > 0 eight more waves own LPC orders 1..8:
+//             windowed autocorrelation (int64), Levinson-Durbin by one thread, a thread per order quantises, then the same sums.
 //   layout    a scan of frame bytes per clip, then of clip bytes across the batch -> offsets[n_clips + 1]
 //   headers   "fLaC", STREAMINFO and the seek points of every clip
 //   emit      one block per frame: the chosen residual again, a block scan of the code lengths, the codes ORed into a zeroed LDS
@@ -24,6 +26,7 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int AN_THREADS = 64 * (FLAC_MAX_ORDER + 1);    // analyse: wave o owns order o
+constexpr int AN_THREADS_LPC = AN_THREADS + 64 * FLAC_MAX_LPC_ORDER;      // and with LPC wave 4 + m owns LPC order m
 constexpr int EM_THREADS = 256;
 constexpr int NK = FLAC_MAX_K + 1;
 constexpr int NPART = 1 << FLAC_MAX_PORDER;              // finest partitions
@@ -71,93 +74,237 @@ __device__ __forceinline__ void stage_frame(const int16_t* __restrict__ pcm, con
     for (int i = tid; i < bs; i += threads) xs[i] = (int)pcm_gained(x[i], fac);
 }
 
+// the residual of LPC order m at sample i >= m: q[j] multiplies x[i - 1 - j]; |sum| <= 8 * 2048 * 32768 = 2^29
+__device__ __forceinline__ int lpc_residual(const int* __restrict__ x, int i, int m, const int* __restrict__ q, int shift) {
+    int s = 0;
+#pragma unroll
+    for (int j = 0; j < FLAC_MAX_LPC_ORDER; j++)
+        if (j < m) s += q[j] * x[i - 1 - j];
+    return x[i] - (s >> shift);
+}
+
 // One candidate of a frame's list.
 struct Candidate { int kind, order, porder; u64 bits; };
 
-// Grid (frames, n_clips).
-__global__ __launch_bounds__(AN_THREADS) void k_flac_analyse(const int16_t* __restrict__ pcm, const double* __restrict__ factor, int n, int frames,
-                                                             FlacRecord* __restrict__ rec) {
+// What the LPC part of the analysis keeps in LDS.
+struct LpcShared {
+    u64 R[FLAC_MAX_LPC_ORDER + 1];
+    double rd[FLAC_MAX_LPC_ORDER + 1];
+    double A[FLAC_MAX_LPC_ORDER][FLAC_MAX_LPC_ORDER];       // A[m - 1][j - 1] = a_j of order m
+    int qs[FLAC_MAX_LPC_ORDER][FLAC_MAX_LPC_ORDER];
+    int qshift[FLAC_MAX_LPC_ORDER];
+    int offered[FLAC_MAX_LPC_ORDER];
+    int over[FLAC_MAX_LPC_ORDER];                           // a residual of the order broke the fold bound
+    int reached;                                            // the recursion's last order
+};
+// The LPC candidates' coefficients (DESIGN.md §9 "FLAC", LPC candidates): xs holds the frame; xw is bs words of scratch.  On return
+// qs[m - 1] / qshift[m - 1] hold order m's quantised coefficients and shift where offered[m - 1] is set.  Called by the whole
+// block; it ends synchronised.
+__device__ __forceinline__ void lpc_coefficients(const int* __restrict__ xs, int* __restrict__ xw, int bs, int mmax, LpcShared& S, int tid,
+                                                 int threads) {
+    // the window: a Welch window scaled to 2^14, non-zero at both ends; |xw| <= 2^23
+    const u64 den = (u64)(bs + 1) * (u64)(bs + 1);
+    for (int i = tid; i < bs; i += threads) {
+        const int w = (int)((((u64)4 * (u64)(i + 1) * (u64)(bs - i)) << 14) / den);
+        xw[i] = (xs[i] * w) >> 6;
+    }
+    if (tid <= FLAC_MAX_LPC_ORDER) S.R[tid] = 0ull;
+    if (tid < FLAC_MAX_LPC_ORDER) { S.offered[tid] = 0; S.over[tid] = 0; }
+    __syncthreads();
+    // the lags: |R| <= 4096 * 2^46, exact in int64 in any order
+    long long acc[FLAC_MAX_LPC_ORDER + 1];
+#pragma unroll
+    for (int l = 0; l <= FLAC_MAX_LPC_ORDER; l++) acc[l] = 0;
+    for (int i = tid; i < bs; i += threads) {
+        const long long a = xw[i];
+#pragma unroll
+        for (int l = 0; l <= FLAC_MAX_LPC_ORDER; l++)
+            if (i >= l) acc[l] += a * (long long)xw[i - l];
+    }
+#pragma unroll
+    for (int l = 0; l <= FLAC_MAX_LPC_ORDER; l++) {
+        for (int d = 32; d >= 1; d >>= 1) acc[l] += __shfl_xor(acc[l], d);
+        if ((tid & 63) == 0) atomicAdd(&S.R[l], (u64)acc[l]);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // Levinson-Durbin in fp64: one rounding per operation, in this order (the build forbids contraction)
+        int stop = 0;
+        if (S.R[0] != 0ull) {
+            for (int l = 0; l <= FLAC_MAX_LPC_ORDER; l++) S.rd[l] = (double)(long long)S.R[l];
+            double err = S.rd[0];
+            for (int m = 1; m <= mmax; m++) {
+                double a = S.rd[m];
+                for (int j = 1; j < m; j++) a = a - S.A[m - 2][j - 1] * S.rd[m - j];
+                const double k = a / err;
+                for (int j = 1; j < m; j++) S.A[m - 1][j - 1] = S.A[m - 2][j - 1] - k * S.A[m - 2][m - j - 1];
+                S.A[m - 1][m - 1] = k;
+                err = err * (1.0 - k * k);
+                stop = m;
+                if (!(err > 0.0)) break;
+            }
+        }
+        S.reached = stop;
+    }
+    __syncthreads();
+    if (tid < FLAC_MAX_LPC_ORDER && tid + 1 <= S.reached) {
+        // thread m - 1 quantises order m: precision 12, error feedback
+        const int m = tid + 1;
+        double cmax = 0.0;
+        bool finite = true;
+        for (int j = 0; j < m; j++) {
+            const double v = fabs(S.A[m - 1][j]);
+            finite = finite && isfinite(v);
+            if (v > cmax) cmax = v;
+        }
+        if (finite && cmax > 0.0) {
+            int e;
+            (void)frexp(cmax, &e);
+            int shift = FLAC_LPC_PRECISION - 1 - e;
+            if (shift > FLAC_LPC_MAX_SHIFT) shift = FLAC_LPC_MAX_SHIFT;
+            if (shift >= 0) {
+                const double scale = (double)(1 << shift);
+                double ef = 0.0;
+                for (int j = 0; j < m; j++) {
+                    ef = ef + S.A[m - 1][j] * scale;
+                    double t = rint(ef);
+                    t = t < -2048.0 ? -2048.0 : t > 2047.0 ? 2047.0 : t;
+                    S.qs[m - 1][j] = (int)t;
+                    ef = ef - t;
+                }
+                S.qshift[m - 1] = shift;
+                S.offered[m - 1] = 1;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// Grid (frames, n_clips).  LPC: whether LPC orders 1..lpc_order are candidates; without, the block is five waves and the code that of
+// the FIXED-only encoder.  A slot s is a predictor: FIXED order s for s <= 4, LPC order s - 4 above; wave s owns slot s.
+template <bool LPC>
+__global__ __launch_bounds__(LPC ? AN_THREADS_LPC : AN_THREADS) void k_flac_analyse(const int16_t* __restrict__ pcm, const double* __restrict__ factor,
+                                                                                   int n, int frames, int lpc_order, FlacRecord* __restrict__ rec,
+                                                                                   FlacLpc* __restrict__ lpc) {
+    constexpr int NS = FLAC_MAX_ORDER + 1 + (LPC ? FLAC_MAX_LPC_ORDER : 0);
+    constexpr int THREADS = 64 * NS;
     __shared__ int xs[FLAC_BLOCK];
     // uint32 holds a finest partition's sum: u <= FLAC_MAX_FOLD = 1048560; a block of 4096 has 32 partitions of 128, and the longest
     // single partition is an odd block's 4095 samples: 4095 * 1048560 < 2^32 (by 0.03 %).
-    // A predictor family with larger residuals must widen these sums (the static_assert below is the condition).
+    // An LPC order with a folded residual above FLAC_MAX_FOLD is not a candidate, so the condition below covers both families.
     static_assert((unsigned long long)(FLAC_BLOCK - 1) * FLAC_MAX_FOLD <= 0xffffffffull, "finest partition sums overflow uint32");
-    __shared__ uint32_t fine[FLAC_MAX_ORDER + 1][NPART][NK];
-    __shared__ u64 pbits[FLAC_MAX_ORDER + 1][NLEVEL];
-    __shared__ uint8_t pk[FLAC_MAX_ORDER + 1][NLEVEL];
-    __shared__ u64 cost[FLAC_MAX_ORDER + 1][FLAC_MAX_PORDER + 1];
+    __shared__ uint32_t fine[NS][NPART][NK];
+    static_assert(!LPC || sizeof(fine) >= sizeof(int) * FLAC_BLOCK, "the windowed samples borrow the sums' space");
+    __shared__ u64 pbits[NS][NLEVEL];
+    __shared__ uint8_t pk[NS][NLEVEL];
+    __shared__ u64 cost[NS][FLAC_MAX_PORDER + 1];
     __shared__ Candidate chosen;
+    __shared__ LpcShared S;                                         // (LPC only)
     const int f = blockIdx.x, clip = blockIdx.y, tid = threadIdx.x;
     const int bs = frame_block(n, f);
-    stage_frame(pcm, factor, n, clip, f, bs, xs, tid, AN_THREADS);
-    for (int i = tid; i < (FLAC_MAX_ORDER + 1) * NPART * NK; i += AN_THREADS) (&fine[0][0][0])[i] = 0u;
+    stage_frame(pcm, factor, n, clip, f, bs, xs, tid, THREADS);
+    if (!LPC)
+        for (int i = tid; i < NS * NPART * NK; i += THREADS) (&fine[0][0][0])[i] = 0u;
     __syncthreads();
     int diff = 0;
-    for (int i = tid; i < bs; i += AN_THREADS) diff |= xs[i] != xs[0];
+    for (int i = tid; i < bs; i += THREADS) diff |= xs[i] != xs[0];
     const int differs = __syncthreads_or(diff);
 
     const int tz = __ffs(bs) - 1;
     const int pmax = tz < FLAC_MAX_PORDER ? tz : FLAC_MAX_PORDER;
     const int omax = bs - 1 < FLAC_MAX_ORDER ? bs - 1 : FLAC_MAX_ORDER;
+    const int mmax = LPC ? (bs - 1 < lpc_order ? bs - 1 : lpc_order) : 0;
     const int np = 1 << pmax, L = bs >> pmax;                       // finest partitions and their length
-    {   // wave o, lane -> (partition, chunk of it); a lane starts `lane` samples into its chunk, so that the lanes of a wave read
+    if constexpr (LPC) {
+        lpc_coefficients(xs, reinterpret_cast<int*>(&fine[0][0][0]), bs, mmax, S, tid, THREADS);
+        for (int i = tid; i < NS * NPART * NK; i += THREADS) (&fine[0][0][0])[i] = 0u;
+        __syncthreads();
+    }
+    // a slot's predictor order, and whether it is a candidate at all
+    auto order_of = [](int s) { return s <= FLAC_MAX_ORDER ? s : s - FLAC_MAX_ORDER; };
+    auto live = [&](int s) {
+        if (s <= FLAC_MAX_ORDER) return s <= omax;
+        if constexpr (LPC) {
+            const int m = s - FLAC_MAX_ORDER;
+            return m <= mmax && S.offered[m - 1] && !S.over[m - 1];
+        }
+        return false;
+    };
+    {   // wave s, lane -> (partition, chunk of it); a lane starts `lane` samples into its chunk, so that the lanes of a wave read
         // different LDS banks when the chunk length is a multiple of 64
-        const int o = tid >> 6, lane = tid & 63;
+        const int s = tid >> 6, lane = tid & 63, o = order_of(s);
         const int cn = 64 >> pmax, lc = (L + cn - 1) / cn;
         const int part = lane / cn, c = lane % cn;
         const int start = part * L + c * lc;
         const int end = min(start + lc, (part + 1) * L);
-        if (o <= omax && start < end) {
+        if (live(s) && start < end) {
+            int q[FLAC_MAX_LPC_ORDER], shift = 0;
+            if constexpr (LPC) {
+                if (s > FLAC_MAX_ORDER) {
+#pragma unroll
+                    for (int j = 0; j < FLAC_MAX_LPC_ORDER; j++) q[j] = j < o ? S.qs[o - 1][j] : 0;
+                    shift = S.qshift[o - 1];
+                }
+            }
             uint32_t acc[NK];
 #pragma unroll
             for (int k = 0; k < NK; k++) acc[k] = 0u;
+            bool over = false;
             int jj = lane % lc;
             for (int j = 0; j < lc; j++) {
                 const int i = start + jj;
                 if (i < end && i >= o) {
-                    const uint32_t u = rice_fold(fixed_residual(xs, i, o));
+                    const uint32_t u = rice_fold(LPC && s > FLAC_MAX_ORDER ? lpc_residual(xs, i, o, q, shift) : fixed_residual(xs, i, s));
+                    if (LPC && u > (uint32_t)FLAC_MAX_FOLD) over = true;
+                    else {
 #pragma unroll
-                    for (int k = 0; k < NK; k++) acc[k] += u >> k;
+                        for (int k = 0; k < NK; k++) acc[k] += u >> k;
+                    }
                 }
                 jj = jj + 1 == lc ? 0 : jj + 1;
             }
 #pragma unroll
-            for (int k = 0; k < NK; k++) atomicAdd(&fine[o][part][k], acc[k]);
+            for (int k = 0; k < NK; k++) atomicAdd(&fine[s][part][k], acc[k]);
+            if constexpr (LPC) {
+                if (over) S.over[o - 1] = 1;
+            }
         }
     }
     __syncthreads();
-    // every partition of every order: its sums from the finest ones, its k (ties to the lowest) and its bits
-    if (tid < (FLAC_MAX_ORDER + 1) * NLEVEL) {
-        const int o = tid / NLEVEL, q = tid % NLEVEL;
+    // every partition of every slot: its sums from the finest ones, its k (ties to the lowest) and its bits
+    if (tid < NS * NLEVEL) {
+        const int s = tid / NLEVEL, q = tid % NLEVEL, o = order_of(s);
         const int P = 31 - __clz(q + 1), p = q + 1 - (1 << P);
-        if (o <= omax && P <= pmax && (bs >> P) > o) {
+        if (live(s) && P <= pmax && (bs >> P) > o) {
             const int span = 1 << (pmax - P), first = p * span;
             const u64 cnt = (u64)((bs >> P) - (p == 0 ? o : 0));
             u64 best = ~0ull; int kb = 0;
 #pragma unroll 1
             for (int k = 0; k < NK; k++) {
-                u64 s = 0;
-                for (int j = 0; j < span; j++) s += fine[o][first + j][k];
-                const u64 b = (u64)(1 + k) * cnt + s;
+                u64 sum = 0;
+                for (int j = 0; j < span; j++) sum += fine[s][first + j][k];
+                const u64 b = (u64)(1 + k) * cnt + sum;
                 if (b < best) { best = b; kb = k; }
             }
-            pbits[o][q] = best; pk[o][q] = (uint8_t)kb;
+            pbits[s][q] = best; pk[s][q] = (uint8_t)kb;
         }
     }
     __syncthreads();
-    if (tid < (FLAC_MAX_ORDER + 1) * (FLAC_MAX_PORDER + 1)) {
-        const int o = tid / (FLAC_MAX_PORDER + 1), P = tid % (FLAC_MAX_PORDER + 1);
+    if (tid < NS * (FLAC_MAX_PORDER + 1)) {
+        const int s = tid / (FLAC_MAX_PORDER + 1), P = tid % (FLAC_MAX_PORDER + 1), o = order_of(s);
         u64 c = ~0ull;
-        if (o <= omax && P <= pmax && (bs >> P) > o) {
-            c = 8 + 16 * o + 6;
-            for (int p = 0; p < (1 << P); p++) c += 4 + pbits[o][(1 << P) - 1 + p];
+        if (live(s) && P <= pmax && (bs >> P) > o) {
+            // FIXED: type byte, warm-up, method and partition order; LPC: also 4 bits of precision, 5 of shift, 12 per coefficient
+            c = s <= FLAC_MAX_ORDER ? 8 + 16 * o + 6 : 8 + 16 * o + 4 + 5 + FLAC_LPC_PRECISION * o + 6;
+            for (int p = 0; p < (1 << P); p++) c += 4 + pbits[s][(1 << P) - 1 + p];
         }
-        cost[o][P] = c;
+        cost[s][P] = c;
     }
     __syncthreads();
     if (tid == 0) {
-        // the candidate list, in rank order: CONSTANT (when it applies), the FIXED candidates by (P, o), VERBATIM.  A candidate
-        // replaces the choice only by strictly fewer bits; CONSTANT, where it applies, is taken outright.
+        // the candidate list, in rank order: CONSTANT (when it applies), the FIXED candidates by (P, o), the LPC candidates by
+        // (P, m), VERBATIM.  A predictor replaces the choice only by strictly fewer bits, and the best predictor is taken only if it
+        // has strictly fewer bits than VERBATIM; CONSTANT, where it applies, is taken outright.
         Candidate best{FLAC_VERBATIM, 0, 0, (u64)(8 + 16 * bs)};
         if (!differs) best = Candidate{FLAC_CONSTANT, 0, 0, 8 + 16};
         else {
@@ -165,19 +312,31 @@ __global__ __launch_bounds__(AN_THREADS) void k_flac_analyse(const int16_t* __re
             for (int P = 0; P <= pmax; P++)
                 for (int o = 0; o <= omax; o++)
                     if (cost[o][P] < fx.bits) fx = Candidate{FLAC_FIXED, o, P, cost[o][P]};
+            if (LPC)
+                for (int P = 0; P <= pmax; P++)
+                    for (int m = 1; m <= mmax; m++)
+                        if (cost[FLAC_MAX_ORDER + m][P] < fx.bits) fx = Candidate{FLAC_LPC, m, P, cost[FLAC_MAX_ORDER + m][P]};
             if (fx.bits < best.bits) best = fx;
         }
         chosen = best;
     }
     __syncthreads();
     const Candidate ch = chosen;
+    const bool coded = ch.kind == FLAC_FIXED || ch.kind == FLAC_LPC;
+    const int slot = ch.kind == FLAC_LPC ? FLAC_MAX_ORDER + ch.order : ch.order;
     FlacRecord* r = rec + (long long)clip * frames + f;
-    if (tid < NPART) r->k[tid] = (ch.kind == FLAC_FIXED && tid < (1 << ch.porder)) ? pk[ch.order][(1 << ch.porder) - 1 + tid] : (uint8_t)0;
+    if (tid < NPART) r->k[tid] = (coded && tid < (1 << ch.porder)) ? pk[slot][(1 << ch.porder) - 1 + tid] : (uint8_t)0;
     if (tid == 0) {
         r->kind = (uint8_t)ch.kind; r->order = (uint8_t)ch.order; r->porder = (uint8_t)ch.porder; r->reserved = 0;
         r->bits = (uint32_t)ch.bits;                                   // <= 8 + 16 * 4096
         r->bytes = (uint32_t)(frame_head_bytes((u64)f, bs) + (int)((ch.bits + 7) / 8) + 2);
         r->reserved2 = 0;
+    }
+    if constexpr (LPC) {
+        FlacLpc* l = lpc + (long long)clip * frames + f;
+        const bool won = ch.kind == FLAC_LPC;
+        if (tid < FLAC_MAX_LPC_ORDER) l->q[tid] = (won && tid < ch.order) ? (int16_t)S.qs[ch.order - 1][tid] : (int16_t)0;
+        if (tid == 0) l->shift = won ? S.qshift[ch.order - 1] : 0;
     }
 }
 
@@ -292,16 +451,19 @@ __device__ __forceinline__ uint32_t crc16_mul(uint32_t a, uint32_t b) {
     return r;
 }
 
-// Grid (frames, n_clips).
+// Grid (frames, n_clips).  LPC: whether a record may name an LPC subframe (then `lpc` holds its coefficients).
+template <bool LPC>
 __global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restrict__ pcm, const double* __restrict__ factor, int n, int rate, int frames,
-                                                          u64 head_bytes, const FlacRecord* __restrict__ rec, const u64* __restrict__ rel,
-                                                          const u64* __restrict__ offsets, uint8_t* __restrict__ out, u64 out_cap) {
+                                                          u64 head_bytes, const FlacRecord* __restrict__ rec, const FlacLpc* __restrict__ lpc,
+                                                          const u64* __restrict__ rel, const u64* __restrict__ offsets, uint8_t* __restrict__ out,
+                                                          u64 out_cap) {
     __shared__ int xs[FLAC_BLOCK];
     __shared__ uint32_t W[W_WORDS];
     __shared__ uint32_t sc[EM_THREADS];
     __shared__ uint32_t T[256];                                  // CRC-16 of one byte
     __shared__ uint32_t cv[EM_THREADS];
     __shared__ uint8_t ks[NPART];
+    __shared__ int lq[FLAC_MAX_LPC_ORDER + 1];                  // (LPC only) the coefficients, then the shift
     const int f = blockIdx.x, clip = blockIdx.y, tid = threadIdx.x;
     const int bs = frame_block(n, f);
     const FlacRecord* r = rec + (long long)clip * frames + f;
@@ -310,6 +472,16 @@ __global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restr
     const u64 off = offsets[clip] + head_bytes + rel[(long long)clip * frames + f];
     if (bytes > FRAME_MAX_BYTES || bytes < hb + 2 || off + (u64)bytes > out_cap) return;       // (block-uniform)
     if (kind == FLAC_FIXED && (o > FLAC_MAX_ORDER || P > FLAC_MAX_PORDER || (bs >> P) <= o)) return;
+    if (kind > FLAC_FIXED && (!LPC || kind != FLAC_LPC || o < 1 || o > FLAC_MAX_LPC_ORDER || P > FLAC_MAX_PORDER || (bs >> P) <= o)) return;
+    if constexpr (LPC) {
+        const FlacLpc* l = lpc + (long long)clip * frames + f;
+        if (kind == FLAC_LPC && (l->shift < 0 || l->shift > FLAC_LPC_MAX_SHIFT)) return;
+        if (tid < FLAC_MAX_LPC_ORDER) lq[tid] = l->q[tid];
+        if (tid == FLAC_MAX_LPC_ORDER) lq[tid] = l->shift;
+    }
+    const bool is_lpc = LPC && kind == FLAC_LPC;
+    // the subframe's bits before the residual's method: the type byte, the warm-up, and for LPC precision, shift and coefficients
+    const int pre = is_lpc ? 8 + 16 * o + 4 + 5 + FLAC_LPC_PRECISION * o : 8 + 16 * o;
     stage_frame(pcm, factor, n, clip, f, bs, xs, tid, EM_THREADS);
     for (int i = tid; i < W_WORDS; i += EM_THREADS) W[i] = 0u;
     if (tid < NPART) ks[tid] = r->k[tid];
@@ -346,13 +518,28 @@ __global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restr
         h[m++] = (uint8_t)c8;
         for (int j = 0; j < m; j++) put_bits(W, 8u * j, 8, h[j]);
         // the subframe header: a zero bit, six bits of type, no wasted bits
-        put_bits(W, sub, 8, kind == FLAC_CONSTANT ? 0x00u : kind == FLAC_VERBATIM ? 0x02u : (uint32_t)((8 | o) << 1));
+        put_bits(W, sub, 8, kind == FLAC_CONSTANT ? 0x00u : kind == FLAC_VERBATIM ? 0x02u : is_lpc ? (uint32_t)((32 | (o - 1)) << 1)
+                                                                                                   : (uint32_t)((8 | o) << 1));
         if (kind == FLAC_CONSTANT) put_bits(W, sub + 8, 16, (uint32_t)xs[0] & 0xffffu);
-        if (kind == FLAC_FIXED) put_bits(W, sub + 8 + 16 * o, 6, (uint32_t)P);       // method 00, partition order
+        if constexpr (LPC) {
+            if (is_lpc) {
+                put_bits(W, sub + 8 + 16 * o, 4, (uint32_t)(FLAC_LPC_PRECISION - 1));
+                put_bits(W, sub + 8 + 16 * o + 4, 5, (uint32_t)lq[FLAC_MAX_LPC_ORDER]);
+                for (int j = 0; j < o; j++) put_bits(W, sub + 8 + 16 * o + 9 + FLAC_LPC_PRECISION * j, FLAC_LPC_PRECISION, (uint32_t)lq[j] & 0xfffu);
+            }
+        }
+        if (kind == FLAC_FIXED || is_lpc) put_bits(W, sub + pre, 6, (uint32_t)P);    // method 00, partition order
     }
     if (kind == FLAC_VERBATIM) {
         for (int i = tid; i < bs; i += EM_THREADS) put_bits(W, sub + 8 + 16 * i, 16, (uint32_t)xs[i] & 0xffffu);
-    } else if (kind == FLAC_FIXED) {
+    } else if (kind == FLAC_FIXED || is_lpc) {
+        int q[FLAC_MAX_LPC_ORDER], shift = 0;
+        if constexpr (LPC) {
+#pragma unroll
+            for (int j = 0; j < FLAC_MAX_LPC_ORDER; j++) q[j] = lq[j];
+            shift = lq[FLAC_MAX_LPC_ORDER];
+        }
+        auto residual = [&](int i) { return is_lpc ? lpc_residual(xs, i, o, q, shift) : fixed_residual(xs, i, o); };
         if (tid < o) put_bits(W, sub + 8 + 16 * tid, 16, (uint32_t)xs[tid] & 0xffffu);
         // a thread's samples are contiguous; a code is q zeros, a one, k bits; a partition's first code follows its 4-bit k
         const int ch = (bs + EM_THREADS - 1) / EM_THREADS;
@@ -363,14 +550,14 @@ __global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restr
         uint32_t total = 0;
         for (int i = i0, part = part0, rem = rem0; i < i1; i++) {
             const int k = ks[part];
-            total += (rice_fold(fixed_residual(xs, i, o)) >> k) + 1u + (uint32_t)k + ((i == o || rem == 0) ? 4u : 0u);
+            total += (rice_fold(residual(i)) >> k) + 1u + (uint32_t)k + ((i == o || rem == 0) ? 4u : 0u);
             if (++rem == lp) { rem = 0; part++; }
         }
         const uint32_t incl = block_scan<uint32_t>(total, sc, tid);
-        uint32_t pos = sub + 8 + 16 * o + 6 + (incl - total);
+        uint32_t pos = sub + pre + 6 + (incl - total);
         for (int i = i0, part = part0, rem = rem0; i < i1; i++) {
             const int k = ks[part];
-            const uint32_t u = rice_fold(fixed_residual(xs, i, o));
+            const uint32_t u = rice_fold(residual(i));
             if (i == o || rem == 0) { put_bits(W, pos, 4, (uint32_t)k); pos += 4; }
             const uint32_t q = u >> k;
             put_bits(W, pos + q, k + 1, (1u << k) | (u & ((1u << k) - 1u)));
@@ -444,14 +631,15 @@ size_t flac_max_bytes(int n_clips, int n, int seek_interval) {
     return b * (size_t)n_clips;
 }
 
-size_t flac_workspace_bytes(int n_clips, int n) {
+size_t flac_workspace_bytes(int n_clips, int n, int lpc_order) {
     const size_t F = (size_t)n_clips * (size_t)flac_frames(n);
-    return align256(F * sizeof(FlacRecord)) + align256(F * 8) + align256((size_t)n_clips * 8) + 2 * align256((size_t)n_clips * 4);
+    return align256(F * sizeof(FlacRecord)) + align256(F * 8) + align256((size_t)n_clips * 8) + 2 * align256((size_t)n_clips * 4) +
+           (lpc_order > 0 ? align256(F * sizeof(FlacLpc)) : 0);
 }
 
-FlacWork flac_work(int n_clips, int n, int rate, int seek_interval, void* d_block) {
+FlacWork flac_work(int n_clips, int n, int rate, int seek_interval, void* d_block, int lpc_order) {
     FlacWork w;
-    w.n_clips = n_clips; w.n = n; w.rate = rate; w.seek_interval = seek_interval;
+    w.n_clips = n_clips; w.n = n; w.rate = rate; w.seek_interval = seek_interval; w.lpc_order = lpc_order;
     w.frames = flac_frames(n);
     w.seek_points = flac_seek_points(n, seek_interval);
     w.head_bytes = (size_t)FLAC_STREAM_HEAD + (w.seek_points > 0 ? 4 + (size_t)FLAC_SEEK_POINT * (size_t)w.seek_points : 0);
@@ -461,21 +649,29 @@ FlacWork flac_work(int n_clips, int n, int rate, int seek_interval, void* d_bloc
     w.rel = (u64*)p; p += align256(F * 8);
     w.clip_bytes = (u64*)p; p += align256((size_t)n_clips * 8);
     w.fmin = (uint32_t*)p; p += align256((size_t)n_clips * 4);
-    w.fmax = (uint32_t*)p;
+    w.fmax = (uint32_t*)p; p += align256((size_t)n_clips * 4);
+    if (lpc_order > 0) w.lpc = (FlacLpc*)p;
     return w;
 }
 
 void launch_flac(const int16_t* pcm, const double* factor, const FlacWork& w, uint8_t* out, size_t out_cap, unsigned long long* offsets,
                  hipStream_t s) {
     const dim3 grid((unsigned)w.frames, (unsigned)w.n_clips);
-    hipLaunchKernelGGL(k_flac_analyse, grid, dim3(AN_THREADS), 0, s, pcm, factor, w.n, w.frames, w.rec);
+    if (w.lpc_order > 0)
+        hipLaunchKernelGGL(k_flac_analyse<true>, grid, dim3(AN_THREADS_LPC), 0, s, pcm, factor, w.n, w.frames, w.lpc_order, w.rec, w.lpc);
+    else
+        hipLaunchKernelGGL(k_flac_analyse<false>, grid, dim3(AN_THREADS), 0, s, pcm, factor, w.n, w.frames, 0, w.rec, (FlacLpc*)nullptr);
     hipLaunchKernelGGL(k_flac_layout_clip, dim3(w.n_clips), dim3(256), 0, s, w.frames, (u64)w.head_bytes, (const FlacRecord*)w.rec, w.rel,
                        w.clip_bytes, w.fmin, w.fmax);
     hipLaunchKernelGGL(k_flac_layout_batch, dim3(1), dim3(256), 0, s, w.n_clips, (const u64*)w.clip_bytes, offsets);
     hipLaunchKernelGGL(k_flac_headers, dim3(w.n_clips), dim3(256), 0, s, w.n, w.rate, w.seek_interval, w.frames, w.seek_points,
                        (const u64*)offsets, (const u64*)w.rel, (const uint32_t*)w.fmin, (const uint32_t*)w.fmax, out, (u64)out_cap);
-    hipLaunchKernelGGL(k_flac_emit, grid, dim3(EM_THREADS), 0, s, pcm, factor, w.n, w.rate, w.frames, (u64)w.head_bytes,
-                       (const FlacRecord*)w.rec, (const u64*)w.rel, (const u64*)offsets, out, (u64)out_cap);
+    if (w.lpc_order > 0)
+        hipLaunchKernelGGL(k_flac_emit<true>, grid, dim3(EM_THREADS), 0, s, pcm, factor, w.n, w.rate, w.frames, (u64)w.head_bytes,
+                           (const FlacRecord*)w.rec, (const FlacLpc*)w.lpc, (const u64*)w.rel, (const u64*)offsets, out, (u64)out_cap);
+    else
+        hipLaunchKernelGGL(k_flac_emit<false>, grid, dim3(EM_THREADS), 0, s, pcm, factor, w.n, w.rate, w.frames, (u64)w.head_bytes,
+                           (const FlacRecord*)w.rec, (const FlacLpc*)nullptr, (const u64*)w.rel, (const u64*)offsets, out, (u64)out_cap);
 }
 
 }  // namespace bnhip

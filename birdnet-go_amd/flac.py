@@ -6,14 +6,19 @@ save see, over bnhip_flac_encode_pcm16 and bnhip_loudness_flac_pcm16.
   encodeFLACNative                   birdweather/encode_native.go:28-98 -> normalize_and_encode(.., max_gain_db=DEFAULT_MAX_GAIN_DB)
 
 Mono int16 only.  The bytes follow the project's own encoder spec: valid RFC 9639 streams, not go-flac's bytes.
+lpc_order: 0 (the default) tries CONSTANT / FIXED / VERBATIM subframes only; M in 1..8 tries LPC orders 1..M as well.
 """
 import numpy as np
 
 from . import host as _host
 from .loudness import DEFAULT_MAX_GAIN_DB, _burst, default_options, factor_from_db
 
+# The reference encodes at go-flac's CompressionLevel 5 (flac/encode.go:25,136-145,350-358), an LPC level; this encoder's LPC search
+# gains nothing above order 8 on the reference's own recording (DESIGN.md §9).
+LEVEL5_LPC_ORDER = 8
 
-def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0):
+
+def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0, lpc_order=0):
     """A burst of detections: a list of int16 mono clips of any lengths -> list of FLAC streams (bytes) in the input's order.
     gain_db: None, one gain for all, or one per clip; applied on the device (FactorFromDB, then the saturating int16 gain)."""
     clips, groups = _burst(clips)
@@ -25,13 +30,14 @@ def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0):
     streams = [None] * len(clips)
     for idx in groups.values():
         out = _host.flac_encode(np.stack([clips[i] for i in idx]), sample_rate, None if factor is None else factor[idx], seek_interval,
-                                device=device)
+                                device=device, lpc_order=lpc_order)
         for j, i in enumerate(idx):
             streams[i] = out[j]
     return streams
 
 
-def normalize_and_encode(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, seek_interval=0, device=0):
+def normalize_and_encode(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, seek_interval=0, device=0,
+                         lpc_order=0):
     """Loudness-normalise and encode a burst in one device call per length: -> (list of host.Loudness, list of FLAC streams), both
     in the input's order.  The normalised PCM never reaches the host."""
     opts = opts or default_options()
@@ -39,7 +45,7 @@ def normalize_and_encode(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_
     results, streams = [None] * len(clips), [None] * len(clips)
     for idx in groups.values():
         res, out = _host.loudness_flac(np.stack([clips[i] for i in idx]), sample_rate, opts.target_lufs, opts.true_peak_dbtp, max_gain_db,
-                                       gate_fallback, seek_interval, device=device)
+                                       gate_fallback, seek_interval, device=device, lpc_order=lpc_order)
         for j, i in enumerate(idx):
             results[i], streams[i] = res[j], out[j]
     return results, streams

@@ -102,6 +102,8 @@ typedef int  (*fn_loud_normalize)(int, const int16_t*, int, int, int, double, do
 typedef int  (*fn_flac_max_bytes)(int, int, int, size_t*);
 typedef int  (*fn_flac_encode_pcm16)(int, const int16_t*, int, int, int, const double*, int, uint8_t*, size_t, uint64_t*);
 typedef int  (*fn_loud_flac_pcm16)(int, const int16_t*, int, int, int, double, double, double, int, int, bnhip_loudness*, uint8_t*, size_t, uint64_t*);
+typedef int  (*fn_flac_lpc_encode_pcm16)(int, const int16_t*, int, int, int, const double*, int, uint8_t*, size_t, uint64_t*, int);
+typedef int  (*fn_loud_flac_lpc_pcm16)(int, const int16_t*, int, int, int, double, double, double, int, int, bnhip_loudness*, uint8_t*, size_t, uint64_t*, int);
 
 typedef struct {
     void* handle;
@@ -125,6 +127,7 @@ typedef struct {
     fn_spec_size spec_size; fn_spec_pcm16 spec_pcm16;
     fn_loud_measure loud_measure; fn_loud_normalize loud_normalize;
     fn_flac_max_bytes flac_max_bytes; fn_flac_encode_pcm16 flac_encode_pcm16; fn_loud_flac_pcm16 loud_flac_pcm16;
+    fn_flac_lpc_encode_pcm16 flac_lpc_encode_pcm16; fn_loud_flac_lpc_pcm16 loud_flac_lpc_pcm16;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -176,6 +179,7 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(loud_measure, "bnhip_loudness_measure_pcm16"); BN_RESOLVE(loud_normalize, "bnhip_loudness_normalize_pcm16");
     BN_RESOLVE(flac_max_bytes, "bnhip_flac_max_bytes"); BN_RESOLVE(flac_encode_pcm16, "bnhip_flac_encode_pcm16");
     BN_RESOLVE(loud_flac_pcm16, "bnhip_loudness_flac_pcm16");
+    BN_RESOLVE(flac_lpc_encode_pcm16, "bnhip_flac_lpc_encode_pcm16"); BN_RESOLVE(loud_flac_lpc_pcm16, "bnhip_loudness_flac_lpc_pcm16");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -299,6 +303,16 @@ static inline int bnbind_loud_flac_pcm16(int device, const int16_t* pcm, int n_c
                                          size_t out_cap, uint64_t* offsets) {
     return BN.loud_flac_pcm16(device, pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, seek_interval, out,
                               out_bytes, out_cap, offsets);
+}
+static inline int bnbind_flac_lpc_encode_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, const double* factor,
+                                               int seek_interval, uint8_t* out, size_t out_cap, uint64_t* offsets, int lpc_order) {
+    return BN.flac_lpc_encode_pcm16(device, pcm, n_clips, n, rate, factor, seek_interval, out, out_cap, offsets, lpc_order);
+}
+static inline int bnbind_loud_flac_lpc_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs,
+                                             double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval, bnhip_loudness* out,
+                                             uint8_t* out_bytes, size_t out_cap, uint64_t* offsets, int lpc_order) {
+    return BN.loud_flac_lpc_pcm16(device, pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, seek_interval, out,
+                                  out_bytes, out_cap, offsets, lpc_order);
 }
 // frames handed to the bank are staged in C memory (cgo: C may not keep or receive Go pointers inside Go memory): slot k of
 // the pointer table points at byte offset off[k] of the staging block
@@ -1117,7 +1131,11 @@ type LoudnessOptions struct {
 	MaxGainDB    float64
 	GateFallback bool
 	PlanOnly     bool // measure and plan, return no samples
+	LPCOrder     int  // NormalizeAndEncodeFLAC only: 0, or 1..8 to try LPC subframes of that many orders (Level5LPCOrder)
 }
+
+// Level5LPCOrder is the lpcOrder that stands for the reference's CompressionLevel 5 (flac/encode.go:25,136-145,350-358).
+const Level5LPCOrder = 8
 
 const (
 	loudnessPeakLimited = 1
@@ -1203,18 +1221,51 @@ func splitStreams(buf []byte, offsets []C.uint64_t) [][]byte {
 // rate).  gainDB: nil, or one gain per clip, applied on the device first (pcmgain.FactorFromDB, then the saturating int16 gain).
 // The bytes follow the project's own encoder spec (DESIGN.md section 9): valid RFC 9639 streams, not go-flac's bytes.
 func EncodeFLAC(pcm []int16, nClips, sampleRate int, gainDB []float64, seekInterval, device int) ([][]byte, error) {
-	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
-		return nil, fmt.Errorf("hip: flac needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
-	}
-	if gainDB != nil && len(gainDB) != nClips {
-		return nil, fmt.Errorf("hip: flac needs one gain per clip, got %d for %d clips", len(gainDB), nClips)
+	if err := flacArgs(len(pcm), nClips, gainDB); err != nil {
+		return nil, err
 	}
 	runtime.LockOSThread()
 	defer runtime.UnlockOSThread()
+	streams, what, rc := encodeFLACLocked(pcm, nClips, sampleRate, gainDB, seekInterval, 0, device)
+	if rc != 0 {
+		return nil, fmt.Errorf("hip: %s (%d): %s", what, rc, lastError())
+	}
+	return streams, nil
+}
+
+// EncodeFLACLPC is EncodeFLAC with LPC subframes of orders 1..lpcOrder among a frame's candidates (lpcOrder in 0..8; 0 is
+// EncodeFLAC byte for byte, Level5LPCOrder the reference's level).  The spec is DESIGN.md section 9.
+func EncodeFLACLPC(pcm []int16, nClips, sampleRate int, gainDB []float64, seekInterval, lpcOrder, device int) ([][]byte, error) {
+	if err := flacArgs(len(pcm), nClips, gainDB); err != nil {
+		return nil, err
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	streams, what, rc := encodeFLACLocked(pcm, nClips, sampleRate, gainDB, seekInterval, lpcOrder, device)
+	if rc != 0 {
+		return nil, fmt.Errorf("hip: %s (%d): %s", what, rc, lastError())
+	}
+	return streams, nil
+}
+
+// flacArgs is what EncodeFLAC and EncodeFLACLPC check before the library is called.
+func flacArgs(samples, nClips int, gainDB []float64) error {
+	if nClips <= 0 || samples == 0 || samples%nClips != 0 {
+		return fmt.Errorf("hip: flac needs nClips > 0 clips of one length, got %d samples for %d clips", samples, nClips)
+	}
+	if gainDB != nil && len(gainDB) != nClips {
+		return fmt.Errorf("hip: flac needs one gain per clip, got %d for %d clips", len(gainDB), nClips)
+	}
+	return nil
+}
+
+// encodeFLACLocked is the body of EncodeFLAC and EncodeFLACLPC after flacArgs.  The caller holds the OS thread (the library's last
+// error is per thread) and turns a non-zero code into an error: -> (streams, what failed, the BNHIP_E_* code).
+func encodeFLACLocked(pcm []int16, nClips, sampleRate int, gainDB []float64, seekInterval, lpcOrder, device int) ([][]byte, string, int) {
 	n := len(pcm) / nClips
 	var capBytes C.size_t
 	if rc := C.bnbind_flac_max_bytes(C.int(nClips), C.int(n), C.int(seekInterval), &capBytes); rc != 0 {
-		return nil, fmt.Errorf("hip: flac_max_bytes failed (%d): %s", int(rc), lastError())
+		return nil, "flac_max_bytes failed", int(rc)
 	}
 	var facPtr *C.double
 	if gainDB != nil {
@@ -1229,16 +1280,17 @@ func EncodeFLAC(pcm []int16, nClips, sampleRate int, gainDB []float64, seekInter
 	}
 	buf := make([]byte, int(capBytes))
 	offsets := make([]C.uint64_t, nClips+1)
-	if rc := C.bnbind_flac_encode_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(n), C.int(sampleRate),
-		facPtr, C.int(seekInterval), (*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
-		return nil, fmt.Errorf("hip: flac_encode failed (%d): %s", int(rc), lastError())
+	if rc := C.bnbind_flac_lpc_encode_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(n), C.int(sampleRate),
+		facPtr, C.int(seekInterval), (*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0], C.int(lpcOrder)); rc != 0 {
+		return nil, "flac_encode failed", int(rc)
 	}
-	return splitStreams(buf, offsets), nil
+	return splitStreams(buf, offsets), "", 0
 }
 
 // NormalizeAndEncodeFLAC is NormalizeClips followed by EncodeFLAC in ONE device call (encodeFLACNative, birdweather/
 // encode_native.go:28-98, for a burst; with GateFallback, MaxGainDB 60 and seekInterval = the sample rate the detection save): the
-// normalised PCM never leaves the device - the loudness records and the compressed streams return.  opts.PlanOnly is ignored.
+// normalised PCM never leaves the device - the loudness records and the compressed streams return.  opts.PlanOnly is ignored;
+// opts.LPCOrder is EncodeFLACLPC's lpcOrder.
 func NormalizeAndEncodeFLAC(pcm []int16, nClips, sampleRate int, opts LoudnessOptions, seekInterval, device int) (streams [][]byte, res []Loudness, err error) {
 	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
 		return nil, nil, fmt.Errorf("hip: flac needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
@@ -1264,9 +1316,9 @@ func NormalizeAndEncodeFLAC(pcm []int16, nClips, sampleRate int, opts LoudnessOp
 	cres := make([]C.bnhip_loudness, nClips)
 	buf := make([]byte, int(capBytes))
 	offsets := make([]C.uint64_t, nClips+1)
-	if rc := C.bnbind_loud_flac_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(n), C.int(sampleRate),
+	if rc := C.bnbind_loud_flac_lpc_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(n), C.int(sampleRate),
 		C.double(target), C.double(opts.TruePeakDBTP), C.double(maxGain), C.int(fallback), C.int(seekInterval), &cres[0],
-		(*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
+		(*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0], C.int(opts.LPCOrder)); rc != 0 {
 		return nil, nil, fmt.Errorf("hip: loudness_flac failed (%d): %s", int(rc), lastError())
 	}
 	return splitStreams(buf, offsets), loudnessFromC(cres), nil

@@ -119,7 +119,10 @@ type LoudnessOptions struct {
 	MaxGainDB    float64
 	GateFallback bool
 	PlanOnly     bool
+	LPCOrder     int
 }
+
+const Level5LPCOrder = 8
 
 func MeasureLoudness([]int16, int, int, int) ([]Loudness, error) { return nil, ErrHIPUnavailable }
 
@@ -128,6 +131,8 @@ func NormalizeClips([]int16, int, int, LoudnessOptions, int) ([]int16, []Loudnes
 }
 
 func EncodeFLAC([]int16, int, int, []float64, int, int) ([][]byte, error) { return nil, ErrHIPUnavailable }
+
+func EncodeFLACLPC([]int16, int, int, []float64, int, int, int) ([][]byte, error) { return nil, ErrHIPUnavailable }
 
 func NormalizeAndEncodeFLAC([]int16, int, int, LoudnessOptions, int, int) ([][]byte, []Loudness, error) {
 	return nil, nil, ErrHIPUnavailable

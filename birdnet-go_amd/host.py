@@ -47,7 +47,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_soundlevel_bank_destroy", "bnhip_range_heatmap", "bnhip_spectrogram_size", "bnhip_spectrogram_pcm16",
            "bnhip_spectrogram_device", "bnhip_loudness_measure_pcm16", "bnhip_loudness_normalize_pcm16",
            "bnhip_loudness_workspace_size", "bnhip_loudness_normalize_device", "bnhip_flac_max_bytes", "bnhip_flac_workspace_size",
-           "bnhip_flac_encode_device", "bnhip_flac_encode_pcm16", "bnhip_loudness_flac_pcm16"]
+           "bnhip_flac_encode_device", "bnhip_flac_encode_pcm16", "bnhip_loudness_flac_pcm16", "bnhip_flac_lpc_workspace_size",
+           "bnhip_flac_lpc_encode_device", "bnhip_flac_lpc_encode_pcm16", "bnhip_loudness_flac_lpc_pcm16"]
 
 
 class HipError(RuntimeError):
@@ -546,14 +547,20 @@ def flac_workspace_size(n_clips, n):
     return _size_query("bnhip_flac_workspace_size", n_clips, n)
 
 
+def flac_lpc_workspace_size(n_clips, n, lpc_order):
+    """Bytes of device scratch flac_encode_device needs with that lpc_order (0: flac_workspace_size)."""
+    return _size_query("bnhip_flac_lpc_workspace_size", n_clips, n, lpc_order)
+
+
 def _flac_streams(buf, offsets):
     return [buf[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(offsets) - 1)]
 
 
-def flac_encode(clips_pcm16, rate, factor=None, seek_interval=0, channels=1, device=0, raw=False):
+def flac_encode(clips_pcm16, rate, factor=None, seek_interval=0, channels=1, device=0, raw=False, lpc_order=0):
     """FLAC streams of a batch of equally long mono clips in one device call (flac.EncodePCMToBuffer; with seek_interval = rate what
     flac.EncodePCM writes to a file): int16 [B, n] (or [n]) -> list of B bytes objects.  factor: per-clip gain applied on the device
-    first (None = none).  raw: (the uint8 buffer as written, offsets uint64 [B + 1]) instead.  Spec: DESIGN.md §9."""
+    first (None = none).  raw: (the uint8 buffer as written, offsets uint64 [B + 1]) instead.  lpc_order: 0, or M in 1..8 to try
+    LPC subframes of orders 1..M as well (flac.LEVEL5_LPC_ORDER for the reference's level).  Spec: DESIGN.md §9."""
     lib = load_library()
     x = _mono_pcm16_clips("FLAC", clips_pcm16, channels)
     B, n = x.shape
@@ -563,29 +570,30 @@ def flac_encode(clips_pcm16, rate, factor=None, seek_interval=0, channels=1, dev
     cap = flac_max_bytes(B, n, seek_interval)
     out = np.empty(cap, np.uint8)
     offsets = np.zeros(B + 1, np.uint64)
-    lib.bnhip_flac_encode_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
-                                            C.c_void_p]
-    _check(lib, lib.bnhip_flac_encode_pcm16(device, x.ctypes.data, B, n, int(rate), fac.ctypes.data if fac is not None else None,
-                                            int(seek_interval), out.ctypes.data, cap, offsets.ctypes.data))
+    lib.bnhip_flac_lpc_encode_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_int]
+    _check(lib, lib.bnhip_flac_lpc_encode_pcm16(device, x.ctypes.data, B, n, int(rate), fac.ctypes.data if fac is not None else None,
+                                                int(seek_interval), out.ctypes.data, cap, offsets.ctypes.data, int(lpc_order)))
     return (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
 
 
 def flac_encode_device(d_pcm_ptr, n_clips, n, rate, d_out_ptr, out_cap, d_offsets_ptr, d_workspace_ptr, workspace_bytes, d_factor_ptr=None,
-                       seek_interval=0, device=0, hip_stream_ptr=None):
-    """Device-resident form: the clips, the factors (nullable), the output, the uint64 [n_clips + 1] offsets and the workspace are
-    device pointers; enqueued on the stream, not synchronised."""
+                       seek_interval=0, device=0, hip_stream_ptr=None, lpc_order=0):
+    """Device-resident form: the clips, the factors (nullable), the output, the uint64 [n_clips + 1] offsets and the workspace
+    (flac_lpc_workspace_size of the same lpc_order) are device pointers; enqueued on the stream, not synchronised."""
     lib = load_library()
-    lib.bnhip_flac_encode_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
-                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    _check(lib, lib.bnhip_flac_encode_device(device, d_pcm_ptr, int(n_clips), int(n), int(rate), d_factor_ptr, int(seek_interval), d_out_ptr,
-                                             int(out_cap), d_offsets_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+    lib.bnhip_flac_lpc_encode_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+    _check(lib, lib.bnhip_flac_lpc_encode_device(device, d_pcm_ptr, int(n_clips), int(n), int(rate), d_factor_ptr, int(seek_interval),
+                                                 d_out_ptr, int(out_cap), d_offsets_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr,
+                                                 int(lpc_order)))
 
 
 def loudness_flac(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, seek_interval=0,
-                  channels=1, device=0):
+                  channels=1, device=0, lpc_order=0):
     """loudness_normalize and flac_encode in one device call - the normalised clips never reach the host: int16 [B, n] -> (list of B
     Loudness, list of B bytes objects).  The BirdWeather upload is (30, no fallback, no seek table), a saved detection (60,
-    fallback, seek_interval = rate)."""
+    fallback, seek_interval = rate).  lpc_order as flac_encode's."""
     lib = load_library()
     x = _mono_pcm16_clips("FLAC", clips_pcm16, channels)
     B, n = x.shape
@@ -593,11 +601,11 @@ def loudness_flac(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max
     cap = flac_max_bytes(B, n, seek_interval)
     out = np.empty(cap, np.uint8)
     offsets = np.zeros(B + 1, np.uint64)
-    lib.bnhip_loudness_flac_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
-                                              C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    _check(lib, lib.bnhip_loudness_flac_pcm16(device, x.ctypes.data, B, n, int(rate), float(target_lufs), float(true_peak_dbtp),
-                                              float(max_gain_db), 1 if gate_fallback else 0, int(seek_interval), C.addressof(res),
-                                              out.ctypes.data, cap, offsets.ctypes.data))
+    lib.bnhip_loudness_flac_lpc_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+    _check(lib, lib.bnhip_loudness_flac_lpc_pcm16(device, x.ctypes.data, B, n, int(rate), float(target_lufs), float(true_peak_dbtp),
+                                                  float(max_gain_db), 1 if gate_fallback else 0, int(seek_interval), C.addressof(res),
+                                                  out.ctypes.data, cap, offsets.ctypes.data, int(lpc_order)))
     return list(res), _flac_streams(out, offsets)
 
 

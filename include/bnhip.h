@@ -303,7 +303,14 @@ int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clip
  * tests/flacref.py): a valid RFC 9639 stream per clip - "fLaC", STREAMINFO (MD5 zero = unknown), a SEEKTABLE when
  * seek_interval > 0 (a point for every seek_interval samples, as the reference's file path passes the sample rate), frames of 4096
  * samples with CONSTANT, FIXED (orders 0..4, partition orders 0..5, Rice parameters 0..14, the exact minimum) or VERBATIM
- * subframes.  All integer arithmetic: every byte is pinned.  LPC predictors, stereo, wasted bits and the MD5 are out of scope.
+ * subframes.  All integer arithmetic: every byte is pinned.  Stereo, wasted bits and the MD5 are out of scope.
+ *   LPC: the bnhip_*_lpc_* entries take lpc_order M in 0..8 as their last argument.  M = 0 is the encoder above, byte for byte (the
+ *   entries without the argument are these called with 0).  With M > 0 LPC subframes of orders 1..min(M, bs - 1) join a frame's
+ *   candidates (the reference encodes at compression level 5, an LPC level: flac/encode.go:25,136-145,350-358): a Welch-windowed
+ *   integer autocorrelation, Levinson-Durbin in fp64 with a stated operation order and no contraction, 12-bit coefficients with error
+ *   feedback, a shift of at most 15, the FIXED candidates' residual coding; an LPC candidate wins only by strictly fewer bits than
+ *   every FIXED one, so bnhip_flac_max_bytes stands.  The spec is DESIGN.md §9 "FLAC", restated by tests/flaclpcref.py; the bytes
+ *   are pinned to it, not to go-flac's.  bnhip_flac_lpc_workspace_size answers the workspace of bnhip_flac_lpc_encode_device.
  *   gain: factor (nullable, [n_clips]) is applied as the samples are read: exactly 1 is the identity, otherwise (double)pcm *
  *   factor rounded half away from zero and saturated, the rule of bnhip_loudness_*.
  *   output: the streams back to back; offsets[c] .. offsets[c + 1] is clip c's, offsets[n_clips] the bytes written.
@@ -315,7 +322,7 @@ int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clip
  * bnhip_loudness_flac_pcm16: bnhip_loudness_normalize_pcm16 and bnhip_flac_encode_pcm16 in one call - the normalised clips stay on
  *                 the device; the loudness records, the offsets and the compressed bytes return.
  * BNHIP_E_INVALID: NULL / empty arguments, n < 1, n_clips outside 1..65535, rate outside 1..1048575, a negative seek_interval, a
- * factor that is not finite or negative, out_cap below bnhip_flac_max_bytes, a workspace that is too small or misaligned, and for
+ * factor that is not finite or negative, lpc_order outside 0..8, out_cap below bnhip_flac_max_bytes, a workspace that is too small or misaligned, and for
  * the fused entry what bnhip_loudness_normalize_pcm16 rejects.  Mono int16 only: the bindings answer BNHIP_E_UNSUPPORTED for
  * anything else.  Argument errors are answered before any device is touched. */
 int bnhip_flac_max_bytes(int n_clips, int n, int seek_interval, size_t* bytes);
@@ -328,6 +335,15 @@ int bnhip_flac_encode_pcm16(int device, const int16_t* pcm, int n_clips, int n, 
 int bnhip_loudness_flac_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs,
                               double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval,
                               bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap, uint64_t* offsets);
+int bnhip_flac_lpc_workspace_size(int n_clips, int n, int lpc_order, size_t* bytes);
+int bnhip_flac_lpc_encode_device(int device, const int16_t* d_pcm, int n_clips, int n, int rate, const double* d_factor,
+                                 int seek_interval, uint8_t* d_out, size_t out_cap, uint64_t* d_offsets, void* d_workspace,
+                                 size_t workspace_bytes, void* hip_stream, int lpc_order);
+int bnhip_flac_lpc_encode_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, const double* factor,
+                                int seek_interval, uint8_t* out, size_t out_cap, uint64_t* offsets, int lpc_order);
+int bnhip_loudness_flac_lpc_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs,
+                                  double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval,
+                                  bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap, uint64_t* offsets, int lpc_order);
 
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates

@@ -6,12 +6,16 @@ tools/loudness_rate.py's generator, the export plan (-23 LUFS, -1 dBTP, +-60 dB,
   (d) bnhip_flac_encode_device on gained clips, output and workspace already on the device, synchronised: launch_flac's kernels
       alone (their per-kernel split comes from a kernel trace of this leg run on its own:
       rocprofv3 --kernel-trace --stats -- python tools/flac_rate.py --legs d, summarised by tools/prof_summary.py);
-  (e) the bytes copied device-to-host in (a) and in (b), counted from the entries' contracts and checked against the offsets.
+  (e) the bytes copied device-to-host in (a) and in (b), counted from the entries' contracts and checked against the offsets;
+  (f) (b) with LPC predictors, lpc_order = --lpc-order (8: the reference's level), and (g) (d) likewise: the same burst, beside
+      (b) and (d) in the same alternation; their compression and (e) of (f) are reported beside (b)'s.
 Host clock around calls that end in a synchronise; --warmup warm-up and --reps timed repetitions per leg, the legs alternated
 twice (half the repetitions per pass).  (b) is checked against (a) followed by bnhip_flac_encode_pcm16, (c) and (d) against (b),
-byte for byte; clip 0 of (b) is decoded by tests/flacdec.py.  Prints one JSON line and writes it to --out.
+byte for byte; clip 0 of (b) is decoded by tests/flacdec.py; (f) against (a) followed by the encode at that lpc_order, (g) against
+(f), clip 0 of (f) decoded by tests/flaclpcdec.py.  Prints one JSON line and writes it to --out.
 
-    python tools/flac_rate.py [--clips 64] [--seconds 15] [--reps 20] [--warmup 3] [--legs abcd] [--out profiles/r14_flac_rate.json]
+    python tools/flac_rate.py [--clips 64] [--seconds 15] [--reps 20] [--warmup 3] [--legs abcdfg] [--lpc-order 8]
+                              [--out profiles/r15_flac_lpc_rate.json]
 """
 import argparse
 import ctypes as C
@@ -37,8 +41,9 @@ def main():
     ap.add_argument("--seconds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--legs", default="abcd")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14_flac_rate.json"))
+    ap.add_argument("--legs", default="abcdfg")
+    ap.add_argument("--lpc-order", type=int, default=8)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_flac_lpc_rate.json"))
     a = ap.parse_args()
     host.init()                                                      # no device: a loud error, not a fallback
     rate = 48000
@@ -46,16 +51,19 @@ def main():
     B, n = pcm.shape
     plan = (PLAN["target_lufs"], PLAN["true_peak_dbtp"], PLAN["max_gain_db"], PLAN["gate_fallback"])
     res = {"tool": "flac_rate", "clips": B, "seconds": a.seconds, "rate": rate, "plan": PLAN, "seek_interval": 0, "reps": a.reps,
-           "warmup": a.warmup, "frames_per_clip": (n + 4095) // 4096, "pcm_bytes": int(pcm.nbytes)}
+           "warmup": a.warmup, "frames_per_clip": (n + 4095) // 4096, "pcm_bytes": int(pcm.nbytes), "lpc_order": a.lpc_order}
+    M = a.lpc_order
 
     legs = {"a": lambda: host.loudness_normalize(pcm, rate, *plan),
             "b": lambda: host.loudness_flac(pcm, rate, *plan),
-            "c": lambda: [host.loudness_flac(c, rate, *plan) for c in pcm]}
+            "c": lambda: [host.loudness_flac(c, rate, *plan) for c in pcm],
+            "f": lambda: host.loudness_flac(pcm, rate, *plan, lpc_order=M)}
     # the reference answers, once: (a), then the host-pointer encoder on its output
     want_res, gained = legs["a"]()
     want_streams = host.flac_encode(gained, rate)
     total = sum(len(s) for s in want_streams)
-    if "d" in a.legs:
+    want_lpc = host.flac_encode(gained, rate, lpc_order=M) if ("f" in a.legs or "g" in a.legs) else None
+    if "d" in a.legs or "g" in a.legs:
         # device memory through the HIP runtime the library itself uses (torch bundles a second one, which finds no GPU after libbnhip's)
         hip = C.CDLL("libamdhip64.so")
         hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -76,7 +84,15 @@ def main():
             host.flac_encode_device(d_in, B, n, rate, d_out, cap, d_off, d_ws, ws)
             assert hip.hipDeviceSynchronize() == 0
         legs["d"] = leg_d
-    run = [l for l in "abcd" if l in a.legs]
+        if "g" in a.legs:
+            ws_lpc = host.flac_lpc_workspace_size(B, n, M)
+            d_out_lpc, d_off_lpc, d_ws_lpc = dev(cap), dev(8 * (B + 1)), dev(ws_lpc)
+
+            def leg_g():
+                host.flac_encode_device(d_in, B, n, rate, d_out_lpc, cap, d_off_lpc, d_ws_lpc, ws_lpc, lpc_order=M)
+                assert hip.hipDeviceSynchronize() == 0
+            legs["g"] = leg_g
+    run = [l for l in "abcdfg" if l in a.legs]
     ts, got = {l: [] for l in run}, {}
     for l in run:
         for _ in range(a.warmup):
@@ -87,7 +103,8 @@ def main():
                 t0 = time.perf_counter()
                 got[l] = legs[l]()
                 ts[l].append((time.perf_counter() - t0) * 1e3)
-    names = {"a": "a_normalize_pcm_back", "b": "b_normalize_flac", "c": "c_normalize_flac_per_clip", "d": "d_flac_device_resident"}
+    names = {"a": "a_normalize_pcm_back", "b": "b_normalize_flac", "c": "c_normalize_flac_per_clip", "d": "d_flac_device_resident",
+             "f": "f_normalize_flac_lpc", "g": "g_flac_lpc_device_resident"}
     for l in run:
         v = np.array(ts[l])
         res[names[l] + "_ms"] = round(float(np.median(v)), 3)
@@ -130,6 +147,33 @@ def main():
         res["d_equals_b"] = bool(out.tobytes() == b"".join(want_streams))
         ok = ok and res["d_equals_b"]
         res["d_GB_per_s_of_pcm"] = round(pcm.nbytes / (res["d_flac_device_resident_ms"] / 1e3) / 1e9, 1)
+    if want_lpc is not None:
+        total_lpc = sum(len(s) for s in want_lpc)
+        res["lpc_compressed_bytes"] = total_lpc
+        res["lpc_compression_ratio"] = round(total_lpc / pcm.nbytes, 4)
+        ratios = [len(s) / (2.0 * n) for s in want_lpc]
+        res["lpc_compression_ratio_per_clip_min_median_max"] = [round(float(f(ratios)), 4) for f in (np.min, np.median, np.max)]
+        res["e_d2h_bytes_f"] = rec + 8 * (B + 1) + total_lpc
+        res["e_d2h_f_over_a"] = round(res["e_d2h_bytes_f"] / res["e_d2h_bytes_a"], 4)
+    if "f" in run:
+        r, streams = got["f"]
+        import flaclpcdec
+        res["f_equals_a_then_encode"] = bool(fields(r) == fields(want_res) and streams == want_lpc)
+        res["f_clip0_decodes_to_a"] = bool(np.array_equal(flaclpcdec.decode(streams[0])[0], gained[0]))
+        ok = ok and res["f_equals_a_then_encode"] and res["f_clip0_decodes_to_a"]
+        if "b" in run:
+            res["f_over_b"] = round(res["f_normalize_flac_lpc_ms"] / res["b_normalize_flac_ms"], 3)
+    if "g" in run:
+        off = np.zeros(B + 1, np.uint64)
+        assert hip.hipMemcpy(off.ctypes.data, d_off_lpc, off.nbytes, 2) == 0
+        out = np.empty(int(off[B]), np.uint8)
+        assert hip.hipMemcpy(out.ctypes.data, d_out_lpc, out.nbytes, 2) == 0
+        res["g_equals_f"] = bool(out.tobytes() == b"".join(want_lpc))
+        ok = ok and res["g_equals_f"]
+        res["g_GB_per_s_of_pcm"] = round(pcm.nbytes / (res["g_flac_lpc_device_resident_ms"] / 1e3) / 1e9, 1)
+        if "d" in run:
+            res["g_over_d"] = round(res["g_flac_lpc_device_resident_ms"] / res["d_flac_device_resident_ms"], 3)
+    if "d" in a.legs or "g" in a.legs:
         for p in blocks:
             hip.hipFree(p)
     line = json.dumps(res)
