@@ -210,6 +210,33 @@ bool Engine::tail_taken(int si, int n, bool lane_tuning) const {
     return (pw_sw & PW_SW_TAIL_FORCE) || pw_tail_fills(p, nt, wm);
 }
 
+// ---- min/max + normalise as one launch
+// The plan keeps its two steps; a lane runs them as k_clip_norm_resident when the plan has the pair (norm_pair, find_norm_pair), the
+// lane has more than 16 clips (smaller ones keep k_clip_minmax_parts, which exists for their latency), the clip fits on chip and the
+// pointers are aligned to whole quads - otherwise the pair runs, same bits.  BNHIP_NORM_RESIDENT=0, read once in build(), keeps the
+// pair everywhere.
+void Engine::find_norm_pair() {
+    norm_pair = -1; pcm_direct = false;
+    if (!norm_resident || specs.empty()) return;
+    for (int si = 0; si + 1 < (int)steps.size(); si++) {
+        const Step& a = steps[si]; const Step& b = steps[si + 1];
+        if (a.kind == S_MINMAX && b.kind == S_NORMALIZE && a.in0 == v_input && b.in0 == v_input && b.in1 == a.out) { norm_pair = si; break; }
+    }
+    if (norm_pair < 0 || !clip_norm_resident_fits(n_samples)) { norm_pair = -1; return; }
+    // PCM straight into the launch: only when nothing else in the plan reads the float waveform
+    pcm_direct = true;
+    for (int si = 0; si < (int)steps.size(); si++) {
+        if (si == norm_pair || si == norm_pair + 1) continue;
+        const Step& s = steps[si];
+        if (s.in0 == v_input || s.in1 == v_input || s.in2 == v_input) pcm_direct = false;
+    }
+}
+bool Engine::norm_resident_taken(int n, const void* x, int bits, const float* xn) const {
+    if (norm_pair < 0 || n <= 16) return false;
+    const uintptr_t in_align = bits == 16 ? 8 : bits == 24 ? 4 : 16;
+    return !(reinterpret_cast<uintptr_t>(x) & (in_align - 1)) && !(reinterpret_cast<uintptr_t>(xn) & 15);
+}
+
 // ================================================================================================ run
 float* Engine::vptr(int v, const float* d_in, float* d_logits, float* d_emb, int lane) const {
     if (v < 0) return nullptr;
@@ -258,14 +285,14 @@ bool Engine::run_pipelined(const float* d_in, int n, float* d_logits, float* d_e
 }
 // One chunk of a host-pointer call in context c's arena on stream st (hostpipe.cpp orders st behind the chunk's copy and
 // records its completion): the whole plan, unsplit.
-bool Engine::run_on_context(int c, hipStream_t st, const float* d_in, int n, float* d_logits, float* d_emb, std::string* err) {
+bool Engine::run_on_context(int c, hipStream_t st, const float* d_in, int n, float* d_logits, float* d_emb, std::string* err, PcmSource pcm) {
     if (n <= 0 || n > max_batch) { *err = "batch size out of range"; return false; }
     if (c < 0 || c >= kMaxDepth || !st || !ctx_arena[c]) { *err = "context does not exist"; return false; }
     call_idx++;                                  // a later unsplit run() orders itself behind the contexts
     cur_arena = ctx_arena[c];
     cur_stream = st;
     cur_ctx = c;                                 // (the context's own min/max scratch)
-    bool ok = run_eager(d_in, n, d_logits, d_emb, err);
+    bool ok = run_eager(d_in, n, d_logits, d_emb, err, pcm);
     cur_ctx = -1;
     cur_arena = nullptr;
     cur_stream = nullptr;
@@ -273,18 +300,19 @@ bool Engine::run_on_context(int c, hipStream_t st, const float* d_in, int n, flo
 }
 // Steps [s0, s1) for n clips in context c's arena on stream st (hostpipe.cpp's two-phase calls); the one value that crosses the cut
 // is read / written at `hand` instead of its arena slot.
-bool Engine::run_part(int c, hipStream_t st, int s0, int s1, const float* d_in, int n, float* hand, float* d_logits, float* d_emb, std::string* err) {
+bool Engine::run_part(int c, hipStream_t st, int s0, int s1, const float* d_in, int n, float* hand, float* d_logits, float* d_emb, std::string* err, PcmSource pcm) {
     if (n <= 0 || n > max_batch) { *err = "batch size out of range"; return false; }
     if (c < 0 || c >= kMaxDepth || !st || !ctx_arena[c]) { *err = "context does not exist"; return false; }
     if (v_hand < 0 || !hand || s0 < 0 || s1 > (int)steps.size() || s0 >= s1 || (s0 != 0 && s0 != split_step) || (s1 != (int)steps.size() && s1 != split_step)) {
         *err = "not a cut of this plan"; return false;
     }
+    if (pcm.samples && s0 != 0) { *err = "a PCM source belongs to the part that starts the plan"; return false; }
     call_idx++;
     cur_arena = ctx_arena[c];
     cur_stream = st;
     cur_ctx = c;
     part_s0 = s0; part_s1 = s1; part_hand = hand;
-    bool ok = run_eager(d_in, n, d_logits, d_emb, err);
+    bool ok = run_eager(d_in, n, d_logits, d_emb, err, pcm);
     part_s0 = 0; part_s1 = -1; part_hand = nullptr;
     cur_ctx = -1;
     cur_arena = nullptr;
@@ -360,7 +388,7 @@ void Engine::sync_contexts() {
     for (int i = 0; i < kMaxKStreams; i++) if (kstream[i]) hipStreamSynchronize(kstream[i]);
 }
 
-bool Engine::run(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err) {
+bool Engine::run(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err, PcmSource pcm) {
     if (n <= 0 || n > max_batch) { *err = "batch size out of range"; return false; }
     if (call_idx) {
         // an unsplit call after pipelined ones: order it (on the GPU) behind whatever the contexts still have queued -
@@ -369,10 +397,10 @@ bool Engine::run(const float* d_in, int n, float* d_logits, float* d_emb, std::s
             if (ctx_stream[c] && ctx_stream[c] != stream) { hipEventRecord(ev_ctx_done[c], ctx_stream[c]); hipStreamWaitEvent(stream, ev_ctx_done[c], 0); }
         if (kstream[0] && kstream[0] != stream) hipStreamSynchronize(kstream[0]);      // (caller-owned main stream: the engine's own may still hold a chunk)
     }
-    if (!use_graphs || profiling) return run_eager(d_in, n, d_logits, d_emb, err);
+    if (!use_graphs || profiling) return run_eager(d_in, n, d_logits, d_emb, err, pcm);
     GraphEntry* ge = nullptr;
     for (auto& g : graphs)
-        if (g.in == d_in && g.logits == d_logits && g.emb == d_emb && g.n == n) { ge = &g; break; }
+        if (g.in == d_in && g.logits == d_logits && g.emb == d_emb && g.n == n && g.pcm == pcm.samples && g.pcm_bits == pcm.bits) { ge = &g; break; }
     if (ge && ge->exec) {
         hipError_t e = hipGraphLaunch(ge->exec, stream);
         if (e != hipSuccess) { *err = std::string("hipGraphLaunch: ") + hipGetErrorString(e); return false; }
@@ -380,25 +408,25 @@ bool Engine::run(const float* d_in, int n, float* d_logits, float* d_emb, std::s
     }
     if (!ge) {                                   // first sighting: run eagerly (also primes one-time function attributes)
         if (graphs.size() >= 8) { if (graphs.front().exec) hipGraphExecDestroy(graphs.front().exec); graphs.erase(graphs.begin()); }
-        graphs.push_back(GraphEntry{d_in, d_logits, d_emb, n, 1, nullptr});
-        return run_eager(d_in, n, d_logits, d_emb, err);
+        graphs.push_back(GraphEntry{d_in, d_logits, d_emb, n, 1, nullptr, pcm.samples, pcm.bits});
+        return run_eager(d_in, n, d_logits, d_emb, err, pcm);
     }
     // second sighting: capture, instantiate, replay
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed);
-    if (e != hipSuccess) { (void)hipGetLastError(); use_graphs = false; return run_eager(d_in, n, d_logits, d_emb, err); }
-    bool ok = run_eager(d_in, n, d_logits, d_emb, err);
+    if (e != hipSuccess) { (void)hipGetLastError(); use_graphs = false; return run_eager(d_in, n, d_logits, d_emb, err, pcm); }
+    bool ok = run_eager(d_in, n, d_logits, d_emb, err, pcm);
     e = hipStreamEndCapture(stream, &graph);
     if (!ok || e != hipSuccess || !graph) {
         if (graph) hipGraphDestroy(graph);
         (void)hipGetLastError();
         use_graphs = false;                      // capture is not available on this stream: stay eager
-        return run_eager(d_in, n, d_logits, d_emb, err);
+        return run_eager(d_in, n, d_logits, d_emb, err, pcm);
     }
     hipGraphExec_t exec = nullptr;
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
-    if (e != hipSuccess || !exec) { (void)hipGetLastError(); use_graphs = false; return run_eager(d_in, n, d_logits, d_emb, err); }
+    if (e != hipSuccess || !exec) { (void)hipGetLastError(); use_graphs = false; return run_eager(d_in, n, d_logits, d_emb, err, pcm); }
     ge->exec = exec;
     e = hipGraphLaunch(exec, stream);
     if (e != hipSuccess) { *err = std::string("hipGraphLaunch: ") + hipGetErrorString(e); return false; }
@@ -410,7 +438,7 @@ bool Engine::run(const float* d_in, int n, float* d_logits, float* d_emb, std::s
 // buffers.  The lanes fill each other's gaps: the short latency-bound launches (squeeze-excite, late layers with few
 // workgroups) and every kernel's tail wave overlap the other lane's work.  Launches are interleaved step by step so
 // neither lane waits for the other's enqueue.
-bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, float* d_emb_all, std::string* err) {
+bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, float* d_emb_all, std::string* err, PcmSource pcm) {
     struct Lane { const float* d_in; int n; float* d_logits; float* d_emb; hipStream_t st; int clip0; };
     Lane lanes[kMaxLanes];
     int nl = 1;
@@ -441,6 +469,20 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
         for (int li = 1; li < nl; li++) hipStreamWaitEvent(lanes[li].st, ev_fork, 0);
     }
     const int s_end = part_s1 < 0 ? (int)steps.size() : part_s1;
+    // min/max + normalise as one launch (k_clip_norm_resident): decided ONCE per lane, here - what the launch reads (the lane's float
+    // clips, or its PCM samples where nothing else in the plan reads the waveform) or nullptr for the pair.  A lane of a PCM call that
+    // does not convert in that launch gets its float copy first.
+    const void* res_x[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
+    int res_bits[kMaxLanes] = {0, 0, 0, 0};
+    for (int li = 0; li < nl; li++) {
+        const Lane& L = lanes[li];
+        const bool pair_here = norm_pair >= part_s0 && norm_pair + 1 < s_end;
+        const float* xn = pair_here ? vptr(steps[norm_pair + 1].out, L.d_in, L.d_logits, L.d_emb, nl > 1 ? li : -1) : nullptr;
+        const char* src = pcm.samples ? static_cast<const char*>(pcm.samples) + (size_t)L.clip0 * n_samples * (pcm.bits / 8) : nullptr;
+        if (src && pair_here && pcm_direct && norm_resident_taken(L.n, src, pcm.bits, xn)) { res_x[li] = src; res_bits[li] = pcm.bits; continue; }
+        if (src) launch_pcm_to_f32(src, pcm.bits, const_cast<float*>(L.d_in), (size_t)L.n * n_samples, L.st);
+        if (pair_here && norm_resident_taken(L.n, L.d_in, 0, xn)) res_x[li] = L.d_in;
+    }
     for (int si = part_s0; si < s_end; si++) {
       for (int li = 0; li < nl; li++) {
         const Step& s = steps[si];
@@ -456,6 +498,7 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
         if (s.kind == S_DW && si > 0 && steps[si - 1].tail == 2 && tail_taken(si - 1, n, nl > 1)) continue;
         if (s.kind == S_MEAN_PARTIAL && si > 0 && steps[si - 1].tail == 1 && tail_taken(si - 1, n, nl > 1)) continue;
         if (s.kind == S_MEAN_FINISH && si > 1 && steps[si - 2].tail == 1 && tail_taken(si - 2, n, nl > 1)) continue;
+        if (s.kind == S_NORMALIZE && si == norm_pair + 1 && res_x[li]) continue;      // ran inside the clip_minmax step's launch
         ProfEntry pe{};
         // diagnostics (tools/debug): a host-side synchronize before / after every launch of one kernel class
         static const char* dbg_sync_before = getenv("BNHIP_DEBUG_SYNC_BEFORE");
@@ -470,6 +513,16 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
         if (prof_this) { pe.a = get_event(); pe.b = get_event(); pe.step = si; pe.n = n; hipEventRecord(pe.a, stream); }
         switch (s.kind) {
             case S_MINMAX:
+                if (si == norm_pair && res_x[li]) {
+                    // (launch_clip_norm_resident refuses exactly what norm_resident_taken refuses: a refusal here is a bug, not a fallback)
+                    if (!launch_clip_norm_resident(res_x[li], res_bits[li], n, n_samples, specs[0].eps, specs[0].norm_sub, specs[0].norm_mul,
+                                                   reinterpret_cast<float2*>(out), vptr(steps[si + 1].out, d_in, d_logits, d_emb, clip0), stream)) {
+                        *err = "k_clip_norm_resident refused a call its predicate accepted"; mm_dirty = true; return false;
+                    }
+                    // (profile: the launch reads x once, as float or as PCM, and writes xn - the normalize step's bytes, not the sum)
+                    pe.more_bytes = steps[si + 1].bytes - s.bytes - (res_bits[li] ? (double)n_samples * (4 - res_bits[li] / 8) : 0.0);
+                    break;
+                }
                 // (scratch of the small-call form: a buffer of its own per context and lane - the arena's full and lane layouts
                 // share memory, a counter kept there would be overwritten by the other layout's activations between calls)
                 launch_clip_minmax(in0, n, n_samples, specs[0].eps, reinterpret_cast<float2*>(out),
@@ -733,9 +786,9 @@ std::string Engine::profile_read() {
         const StepView sv = step_view(*this, e.step);
         if (!agg.count(s.kclass)) order.push_back(s.kclass);
         Agg& a = agg[s.kclass];
-        a.ms += ms; a.launches++; a.flops += sv.flops * e.n; a.bytes += sv.bytes * e.n + s.wbytes;
+        a.ms += ms; a.launches++; a.flops += sv.flops * e.n; a.bytes += (sv.bytes + e.more_bytes) * e.n + s.wbytes;
         Agg& ps = per_step[e.step];
-        ps.ms += ms; ps.launches++; ps.flops += sv.flops * e.n; ps.bytes += sv.bytes * e.n + s.wbytes;
+        ps.ms += ms; ps.launches++; ps.flops += sv.flops * e.n; ps.bytes += (sv.bytes + e.more_bytes) * e.n + s.wbytes;
         ev_pool.push_back(e.a); ev_pool.push_back(e.b);
     }
     prof.clear();

@@ -82,7 +82,12 @@ struct FrontSpec {
     float log_floor = 0.f, log_scale = 1.f;
 };
 
-struct ProfEntry { hipEvent_t a, b; int step; int n; };
+// `pcm` of Engine::run / run_on_context / run_part (from step 0): the call's input still is PCM samples, clip-major like d_in, and d_in
+// is the writable float staging for it.  Lanes that run min/max + normalise as the one resident launch convert in its load; every
+// other lane (and every plan without that pair) gets its float copy in d_in first, on the lane's stream.
+struct PcmSource { const void* samples = nullptr; int bits = 0; /* 16 / 24 / 32 */ };
+
+struct ProfEntry { hipEvent_t a, b; int step; int n; double more_bytes = 0; };   // more_bytes: per clip, of a step that ran inside this launch
 
 struct WeightPlan {                  // host half of the weight arena, made by the planner (planner.cpp), uploaded by Engine::bind_device
     std::vector<float> img;          // the arena image (256-byte aligned pieces)
@@ -101,7 +106,7 @@ class Engine {
     ~Engine();
     // returns false and sets err (+ code: BNHIP_E_*) on failure
     bool build(TflModel m, int device, int max_batch, bool plan_only, std::string* err, int* code);
-    bool run(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err);
+    bool run(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err, PcmSource pcm = {});
 
     int device = 0, max_batch = 256;
     bool no_reuse = false;              // diagnostics: every activation keeps its own buffer
@@ -132,6 +137,12 @@ class Engine {
     static constexpr int kMinMaxScratch = 16 * (2 * kMinMaxParts + 2);   // floats: 16 clips x (parts + counter) of k_clip_minmax_parts
     float* mm_scratch = nullptr;        // [context][lane][kMinMaxScratch]: outside the arenas (their layouts overlap), zeroed once
     bool mm_dirty = false;              // a call failed: the arrival counters in mm_scratch may be non-zero - re-zeroed before the next call
+    // min/max + normalise as ONE launch that keeps each clip on chip between the two passes (k_clip_norm_resident, frontend.hip)
+    bool norm_resident = true;          // BNHIP_NORM_RESIDENT=0: always the two launches; the environment read ONCE in build()
+    int norm_pair = -1;                 // index of the S_MINMAX step whose successor is its S_NORMALIZE, when the clip fits on chip; else -1
+    bool pcm_direct = false;            // nothing but that pair reads the input: a PCM call needs no float copy of the batch
+    void find_norm_pair();              // plan time
+    bool norm_resident_taken(int n, const void* x, int bits, const float* xn) const;   // a lane of n clips runs the pair as the one launch, reading x (float32: bits 0, or PCM)
     hipEvent_t ev_ctx_fork = nullptr, ev_ctx_done[kMaxDepth] = {nullptr, nullptr, nullptr};
     unsigned call_idx = 0;
     bool run_pipelined(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err);
@@ -142,7 +153,7 @@ class Engine {
     // created on first use (ensure_contexts) when the engine was built with depth 1.
     int host_depth = 2;
     bool ensure_contexts(int d, std::string* err, bool with_streams = true);   // host pipeline: arenas only (it runs on kstream[0..1])
-    bool run_on_context(int c, hipStream_t st, const float* d_in, int n, float* d_logits, float* d_emb, std::string* err);
+    bool run_on_context(int c, hipStream_t st, const float* d_in, int n, float* d_logits, float* d_emb, std::string* err, PcmSource pcm = {});
     // Two-phase host calls (hostpipe.cpp, calls that fit one batch): the plan is cut at `split_step`, a launch boundary that exactly
     // one activation crosses (`v_hand`).  Steps [0, split_step) run per chunk as the chunks arrive and leave that value in hand-off
     // memory at the chunk's clip offset; steps [split_step, end) run over groups of chunks, where the late layers have the rows to
@@ -154,7 +165,7 @@ class Engine {
     size_t hand_clip_bytes() const { return v_hand < 0 ? 0 : vals[v_hand].elems * (vals[v_hand].half ? 2 : 4); }
     bool ensure_hand(std::string* err);
     // steps [s0, s1) of the plan for n clips in context c's arena on stream st; `hand` = the hand-off value's rows for these clips
-    bool run_part(int c, hipStream_t st, int s0, int s1, const float* d_in, int n, float* hand, float* d_logits, float* d_emb, std::string* err);
+    bool run_part(int c, hipStream_t st, int s0, int s1, const float* d_in, int n, float* hand, float* d_logits, float* d_emb, std::string* err, PcmSource pcm = {});
     // Heat-map grids (bnhip_range_heatmap).  The pruned tail: when the plan's last step is an fp32 dense GEMM that writes the logits
     // (its folded activation included, nothing after it), the call runs the plan without it and computes one column of it
     // (k_heatmap_column).  Returns that step's index, or -1: the full plan runs and the column is gathered from the logits.
@@ -234,9 +245,9 @@ class Engine {
     int steps_read(double* start_ms, double* end_ms, int cap);     // relative to the first call's start; clears
 
   private:
-    struct GraphEntry { const float* in; float* logits; float* emb; int n; int seen; hipGraphExec_t exec; };
+    struct GraphEntry { const float* in; float* logits; float* emb; int n; int seen; hipGraphExec_t exec; const void* pcm; int pcm_bits; };
     std::vector<GraphEntry> graphs;     // tiny cache: the host path always presents the same staging pointers
-    bool run_eager(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err);
+    bool run_eager(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err, PcmSource pcm = {});
     char* act_arena = nullptr;
     char* cur_arena = nullptr;          // arena the launches of the current call address (act_arena or a context's)
     hipStream_t cur_stream = nullptr;   // main stream of the current call (stream or a context's)

@@ -2,7 +2,9 @@
 // real-DFT * mel -> power law -> NHWC store in one kernel).  The FFT-based front end is stft.hip.
 #include "kernels.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 
 namespace bnhip {
@@ -129,6 +131,158 @@ void launch_clip_minmax(const float* x, int n_clips, int n_samples, float eps, f
         return;
     }
     hipLaunchKernelGGL(k_clip_minmax, dim3(n_clips), dim3(1024), 0, s, x, n_samples, eps, mm);
+}
+
+// ------------------------------------------------------------------------------------------ resident min/max + normalise
+// k_clip_minmax followed by k_normalize (stft.hip) reads the clip from HBM twice: the second kernel cannot start before the first
+// has seen the clip's last sample.  A v2.4 clip is 576 KB and one CU has 512 KB of vector registers and 160 KB of LDS, so one
+// 1024-thread block (16 waves at 128 VGPRs) keeps the whole clip on chip between the two passes: thread t holds quads
+// t + 1024 r, r < kNormR, in registers, the quads from 1024 kNormR on sit in dynamic LDS (each thread reads back only what it wrote
+// itself, so the data needs no barrier).  One read of x, one write of xn, one launch.  The arithmetic is the pair's: min / max are
+// exact whatever the grouping (v_min_f32 / v_max_f32 order -0 below +0), so every thread folds the 16 wave partials for itself, and the four normalise operations are k_normalize's in its order under the same -ffp-contract=off, IEEE division
+// included - xn and mm are the pair's bit for bit.  PCM input (int16, packed 24-bit, int32) is converted in the load exactly as
+// k_pcm*_to_f32 convert it.  No block waits for another one.
+// Addressing: every round of 1024 quads reads and writes through a buffer descriptor of its own that starts at the round's first quad
+// and ends with the clip, built with scalar arithmetic; the thread's one byte offset serves all of them, and the hardware range
+// check stands in for the end-of-clip test: a quad past the end loads as zeros (and is kept out of min / max) and is not stored.
+// With a selected index per load the 28 offsets of the register part were live at once and the kernel spilled.
+struct Pcm24 {};                                  // sample-type tag: 3 bytes little-endian, two's complement
+constexpr int kNormR = 28;                        // quads per thread in registers (112 of the 128 VGPRs)
+constexpr int kNormRegQuads = 1024 * kNormR;
+constexpr int kNormLdsBytes = 160 * 1024 - 256;   // dynamic part; the static part is the 2 x 16 wave partials
+constexpr int kNormLdsQuads = kNormLdsBytes / 16;
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __amdgpu_buffer_rsrc_t ClipBuf;
+// bytes [off, bytes) of a clip as a raw buffer (stride 0): a thread offset at or past the end is out of range.  The range check
+// covers the VGPR offset only, never the instruction's scalar offset - so a block-uniform displacement goes into the descriptor
+// (scalar arithmetic), not into the access.
+__device__ __forceinline__ ClipBuf clip_buf(const void* base, int bytes, int off) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(base)) + off, 0, max(bytes - off, 0), 0x00020000);
+}
+// quad q of the buffer as four floats
+template <typename T> struct ClipIn;
+template <> struct ClipIn<float> {
+    static constexpr int kBytes = 4;
+    static __device__ __forceinline__ float4 quad(ClipBuf b, int q) {
+        const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(b, q * 16, 0, 0);
+        return make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
+    }
+};
+template <> struct ClipIn<int16_t> {
+    static constexpr int kBytes = 2;
+    static __device__ __forceinline__ float s16(uint32_t v) { return (float)(int16_t)v / 32768.0f; }
+    static __device__ __forceinline__ float4 quad(ClipBuf b, int q) {
+        const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(b, q * 8, 0, 0);
+        return make_float4(s16(w.x), s16(w.x >> 16), s16(w.y), s16(w.y >> 16));
+    }
+};
+template <> struct ClipIn<Pcm24> {
+    static constexpr int kBytes = 3;
+    static __device__ __forceinline__ float s24(uint32_t v) { return (float)((int32_t)(v << 8) >> 8) / 8388608.0f; }
+    static __device__ __forceinline__ float4 quad(ClipBuf b, int q) {       // four samples = three aligned words
+        const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(b, q * 12, 0, 0);
+        return make_float4(s24(w.x), s24((w.x >> 24) | (w.y << 8)), s24((w.y >> 16) | (w.z << 16)), s24(w.z >> 8));
+    }
+};
+template <> struct ClipIn<int32_t> {
+    static constexpr int kBytes = 4;
+    static __device__ __forceinline__ float4 quad(ClipBuf b, int q) {
+        const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(b, q * 16, 0, 0);
+        return make_float4((float)(int32_t)w.x / 2147483648.0f, (float)(int32_t)w.y / 2147483648.0f, (float)(int32_t)w.z / 2147483648.0f,
+                           (float)(int32_t)w.w / 2147483648.0f);
+    }
+};
+__device__ __forceinline__ void quad_minmax(const float4& v, bool in_clip, float& mn, float& mx) {
+    const float a = fminf(fminf(mn, v.x), fminf(v.y, fminf(v.z, v.w)));
+    const float b = fmaxf(fmaxf(mx, v.x), fmaxf(v.y, fmaxf(v.z, v.w)));
+    mn = in_clip ? a : mn;
+    mx = in_clip ? b : mx;
+}
+__device__ __forceinline__ float norm1(float x, float mn, float d, float sub, float mul) {      // k_normalize, operation for operation
+    float t = x - mn;
+    t = t / d;
+    t = t - sub;
+    return t * mul;
+}
+__device__ __forceinline__ void store_norm4(ClipBuf o, int q, const float4& v, float mn, float d, float sub, float mul) {
+    u32x4 w;
+    w.x = __float_as_uint(norm1(v.x, mn, d, sub, mul)); w.y = __float_as_uint(norm1(v.y, mn, d, sub, mul));
+    w.z = __float_as_uint(norm1(v.z, mn, d, sub, mul)); w.w = __float_as_uint(norm1(v.w, mn, d, sub, mul));
+    __builtin_amdgcn_raw_buffer_store_b128(w, o, q * 16, 0, 0);
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void k_clip_norm_resident(const void* __restrict__ x, int n_samples, float eps, float norm_sub, float norm_mul,
+                                                             float2* __restrict__ mm, float* __restrict__ out) {
+    extern __shared__ float4 lq[];                // quads kNormRegQuads .. n4 - 1 of the clip
+    __shared__ float smn[16], smx[16];
+    constexpr int kIn = ClipIn<T>::kBytes * 4;     // bytes of an input quad
+    const char* xc = static_cast<const char*>(x) + (size_t)blockIdx.x * n_samples * ClipIn<T>::kBytes;
+    const float* oc = out + (size_t)blockIdx.x * n_samples;
+    const int n4 = n_samples / 4, nl = max(n4 - kNormRegQuads, 0), tid = threadIdx.x;
+    float mn = INFINITY, mx = -INFINITY;
+    // the LDS part first, while the registers are free: 8 independent loads per thread and round
+    for (int j0 = 0; j0 < nl; j0 += 8 * 1024) {
+        float4 t[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) t[u] = ClipIn<T>::quad(clip_buf(xc, n4 * kIn, (kNormRegQuads + j0 + u * 1024) * kIn), tid);
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int j = j0 + u * 1024 + tid;
+            quad_minmax(t[u], j < nl, mn, mx);
+            if (j < nl) lq[j] = t[u];
+        }
+    }
+    // the register part: kNormR independent loads per thread
+    float4 v[kNormR];
+#pragma unroll
+    for (int r = 0; r < kNormR; r++) v[r] = ClipIn<T>::quad(clip_buf(xc, n4 * kIn, 1024 * r * kIn), tid);
+#pragma unroll
+    for (int r = 0; r < kNormR; r++) {            // (in source order: the scheduler's interleaving of the rounds costs registers, which spill)
+        quad_minmax(v[r], tid + 1024 * r < n4, mn, mx);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_down(mn, o, 64)); mx = fmaxf(mx, __shfl_down(mx, o, 64)); }
+    if ((tid & 63) == 0) { smn[tid >> 6] = mn; smx[tid >> 6] = mx; }
+    __syncthreads();
+    // every thread needs the clip's pair: lane l takes partial l % 16 and a butterfly over 16 lanes folds them (two registers; 16
+    // partials read by every thread at once cost 20 and spilled the resident quads)
+    mn = smn[tid & 15]; mx = smx[tid & 15];
+    for (int o = 8; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 16)); mx = fmaxf(mx, __shfl_xor(mx, o, 16)); }
+    const float d = (mx - mn) + eps;
+    if (tid == 0) mm[blockIdx.x] = make_float2(mn, d);
+#pragma unroll
+    for (int r = 0; r < kNormR; r++) {
+        store_norm4(clip_buf(oc, n4 * 16, 1024 * r * 16), tid, v[r], mn, d, norm_sub, norm_mul);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const ClipBuf ol = clip_buf(oc, n4 * 16, kNormRegQuads * 16);
+    for (int j = tid; j < nl; j += 1024) store_norm4(ol, j, lq[j], mn, d, norm_sub, norm_mul);
+}
+bool clip_norm_resident_fits(int n_samples) {
+    return n_samples > 0 && (n_samples & 3) == 0 && n_samples / 4 <= kNormRegQuads + kNormLdsQuads;
+}
+template <typename T>
+static void launch_cnr(const void* x, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out, hipStream_t s) {
+    lds_limit_once<&k_clip_norm_resident<T>>(kNormLdsBytes);
+    const int nl = std::max(n_samples / 4 - kNormRegQuads, 0);
+    hipLaunchKernelGGL(k_clip_norm_resident<T>, dim3(n_clips), dim3(1024), (size_t)nl * 16, s, x, n_samples, eps, norm_sub, norm_mul, mm, out);
+}
+bool launch_clip_norm_resident(const void* x, int bits, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out,
+                               hipStream_t s) {
+    // whole quads, loaded and stored at their natural alignment (a clip is a whole number of quads, so every clip's base is aligned
+    // when the first one is: 16 bytes for float32 / int32, 8 for int16, 4 for the three words of a 24-bit quad)
+    const uintptr_t in_align = bits == 16 ? 8 : bits == 24 ? 4 : 16;
+    if (n_clips <= 0 || !clip_norm_resident_fits(n_samples) || (reinterpret_cast<uintptr_t>(x) & (in_align - 1)) || (reinterpret_cast<uintptr_t>(out) & 15))
+        return false;
+    if (bits == 0) launch_cnr<float>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
+    else if (bits == 16) launch_cnr<int16_t>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
+    else if (bits == 24) launch_cnr<Pcm24>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
+    else if (bits == 32) launch_cnr<int32_t>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
+    else return false;
+    return true;
 }
 
 // Fused normalise -> frame -> window -> (real-DFT * mel) -> x^p1 -> x^p2 -> NHWC store.

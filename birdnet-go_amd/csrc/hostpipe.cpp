@@ -348,11 +348,12 @@ int small_run(Engine& e, const HostJob& j, std::string& err) {
         if (j.prepare) j.prepare(off, n);
         if (j.pcm_bits) {
             HP_TRY(hipMemcpyAsync(e.d_stage_pcm, src, cnt * bps, hipMemcpyHostToDevice, e.stream), "H2D copy");
-            launch_pcm_to_f32(e.d_stage_pcm, j.pcm_bits, e.d_stage_in, cnt, e.stream);
         } else {
             HP_TRY(hipMemcpyAsync(e.d_stage_in, src, cnt * 4, hipMemcpyHostToDevice, e.stream), "H2D copy");
         }
-        if (!e.run(e.d_stage_in, n, e.d_stage_logits, j.emb ? e.d_stage_emb : nullptr, &err)) { hipStreamSynchronize(e.stream); return BNHIP_E_RUNTIME; }
+        // (PCM is converted inside the plan: in the min/max + normalise launch where that runs as one)
+        const PcmSource pcm{j.pcm_bits ? e.d_stage_pcm : nullptr, j.pcm_bits};
+        if (!e.run(e.d_stage_in, n, e.d_stage_logits, j.emb ? e.d_stage_emb : nullptr, &err, pcm)) { hipStreamSynchronize(e.stream); return BNHIP_E_RUNTIME; }
         if (kk) {
             launch_activation(e.d_stage_logits, e.d_post_conf, n, e.n_classes, j.activation, j.sensitivity, e.stream);
             launch_topk(e.d_post_conf, n, e.n_classes, kk, e.d_topk_conf, e.d_topk_idx, e.stream);
@@ -532,8 +533,8 @@ int host_run_split(Engine& e, const HostJob& j, const std::vector<int>& csize, s
             if (trace) hipEventRecord(tev[1 + 3 * c], hp.xfer);
             HP_PIPE(hipStreamWaitEvent(st, s.ev_h2d, 0), "stream wait");
             if (trace) hipEventRecord(tev[2 + 3 * c], st);
-            if (j.pcm_bits) launch_pcm_to_f32(s.d_raw, j.pcm_bits, s.d_in, cnt, st);
-            if (!e.run_part(op.st, st, 0, e.split_step, s.d_in, n, reinterpret_cast<float*>(hand + (size_t)cfirst[c] * hcb), s.d_logits, nullptr, &err)) { abort_all(); return BNHIP_E_RUNTIME; }
+            const PcmSource pcm{j.pcm_bits ? s.d_raw : nullptr, j.pcm_bits};
+            if (!e.run_part(op.st, st, 0, e.split_step, s.d_in, n, reinterpret_cast<float*>(hand + (size_t)cfirst[c] * hcb), s.d_logits, nullptr, &err, pcm)) { abort_all(); return BNHIP_E_RUNTIME; }
             HP_PIPE(hipEventRecord(s.ev_comp, st), "event record");      // (front of chunk c done)
             if (trace) hipEventRecord(tev[3 + 3 * c], st);
             c++;
@@ -753,8 +754,8 @@ int host_run(Engine& e, const HostJob& j, std::string& err) {
         if (c >= LAG) HP_PIPE(issue_d2h(c - LAG), "D2H copy");
         HP_PIPE(hipStreamWaitEvent(cs, s.ev_h2d, 0), "stream wait");
         if (trace) hipEventRecord(tev[2 + 3 * c], cs);
-        if (j.pcm_bits) launch_pcm_to_f32(s.d_raw, j.pcm_bits, s.d_in, cnt, cs);      // a1: PCM -> float32 on the device
-        if (!e.run_on_context(ctx, cs, s.d_in, n, s.d_logits, j.emb ? s.d_emb : nullptr, &err)) { abort_all(); return BNHIP_E_RUNTIME; }
+        const PcmSource pcm{j.pcm_bits ? s.d_raw : nullptr, j.pcm_bits};      // a1: PCM -> float32 on the device, inside the plan's first launch where it can be
+        if (!e.run_on_context(ctx, cs, s.d_in, n, s.d_logits, j.emb ? s.d_emb : nullptr, &err, pcm)) { abort_all(); return BNHIP_E_RUNTIME; }
         if (kk) {
             launch_activation(s.d_logits, s.d_conf, n, e.n_classes, j.activation, j.sensitivity, cs);
             launch_topk(s.d_conf, n, e.n_classes, kk, s.d_tkc, s.d_tki, cs);

@@ -64,6 +64,13 @@ void launch_pcm_to_f32(const void* pcm, int bits /*16, 24, 32*/, float* out, siz
 // per-clip (min, max(x-min)+eps) as TFLite's REDUCE_MIN/SUB/REDUCE_MAX/ADD chain produces them
 constexpr int kMinMaxParts = 16;      // blocks per clip of the small-call form; scratch = [clip][2 * kMinMaxParts + 2] floats, zero before first use
 void launch_clip_minmax(const float* x, int n_clips, int n_samples, float eps, float2* mm, float* scratch /*nullable*/, hipStream_t s);
+// k_clip_norm_resident: launch_clip_minmax + launch_normalize (stft.hip) as ONE launch that keeps each clip in a CU's registers and
+// LDS between the two passes - mm and out are the pair's bit for bit.  x holds float32 (bits 0) or PCM samples (bits 16 / 24 / 32,
+// converted in the load as launch_pcm_to_f32 converts them).  false, and nothing launched: the clip does not fit on chip
+// (clip_norm_resident_fits) or a pointer is not aligned to whole quads - the caller then runs the pair.
+bool clip_norm_resident_fits(int n_samples);
+bool launch_clip_norm_resident(const void* x, int bits, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out,
+                               hipStream_t s);
 
 struct FrontendParams {
     const float* x;        // [B, n_samples] raw clip

@@ -1598,6 +1598,7 @@ bool Engine::build(TflModel m, int dev, int maxb, bool plan_only, std::string* e
     device = dev;
     max_batch = maxb;
     pw_sw = pw_switches_from_env();      // (tests flip these between engines of one process; nothing reads them after this line)
+    if (const char* e = getenv("BNHIP_NORM_RESIDENT")) norm_resident = atoi(e) != 0;
     const PlanSwitches sw;
     *code = BNHIP_E_UNSUPPORTED;
     // graph rewrites first (float16 constants behind DEQUANTIZE, unfolded batch norm, PAD + VALID convolutions): the
@@ -1615,6 +1616,7 @@ bool Engine::build(TflModel m, int dev, int maxb, bool plan_only, std::string* e
     }
     tensor_value = L.tv;
     mark_tails();
+    find_norm_pair();
 
     mark_liveness(vals, steps);
     if (v_emb >= 0) vals[v_emb].last = (int)steps.size();      // keep until copy-out
