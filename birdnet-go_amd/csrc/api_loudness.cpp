@@ -1,5 +1,6 @@
 // C ABI of the clip loudness entries (bnhip_loudness_measure_pcm16, bnhip_loudness_normalize_pcm16, bnhip_loudness_workspace_size,
-// bnhip_loudness_normalize_device).
+// bnhip_loudness_normalize_device) and of their forms for a ragged burst (bnhip_loudness_ragged_workspace_size,
+// bnhip_loudness_ragged_normalize_pcm16, bnhip_loudness_ragged_normalize_device).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,6 +25,11 @@ int dims_check(int n_clips, int n, int rate) {
     if (const int rc = clip_dims_check(n_clips, n)) return rc;
     if (rate < LOUD_MIN_RATE) return set_err(BNHIP_E_INVALID, "sample rate too low; minimum is 8000 Hz (K-weighting is undefined below it)");
     return 0;
+}
+
+int ragged_dims_check(int n_clips, const int* lens, int rate) {
+    if (const int rc = ragged_lens_check(n_clips, lens)) return rc;
+    return dims_check(1, 1, rate);
 }
 
 // Options.validate (audionorm.go:278-293) and the clamp's magnitude
@@ -94,6 +100,23 @@ int loudness_enqueue(const char* what, int device, const int16_t* d_pcm, int n_c
     return launch_status(what);
 }
 
+int loudness_ragged_args_check(int n_clips, const int* lens, int rate, double target, double ceiling, double max_gain) {
+    const int rc = ragged_dims_check(n_clips, lens, rate);
+    return rc ? rc : plan_check(target, ceiling, max_gain);
+}
+
+int loudness_ragged_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, const int* lens, int rate, double target,
+                            double ceiling, double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace,
+                            hipStream_t s) {
+    const int S = loudness_sub_block(rate);
+    TableLock lk(g_tables.mu);
+    const LoudTable* tab = loud_table(lk, device, rate, S / loudness_ragged_split(n_clips, lens, S));
+    if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (loudness table)");
+    launch_loudness(d_pcm, loudness_ragged_work(n_clips, lens, S, d_workspace), tab->d, make_plan(target, ceiling, max_gain, gate_fallback, 0),
+                    d_out, d_out_pcm, s);
+    return launch_status(what);
+}
+
 }  // namespace bnhip
 
 extern "C" {
@@ -138,6 +161,57 @@ int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clip
     if (rc) return rc;
     return loudness_enqueue("loudness_normalize_device", device, d_pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback,
                             d_out, d_out_pcm, d_workspace, reinterpret_cast<hipStream_t>(hip_stream));
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_loudness_ragged_workspace_size(int n_clips, const int* lens, int rate, size_t* bytes) {
+    if (!bytes) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    const int rc = ragged_dims_check(n_clips, lens, rate);
+    if (rc) return rc;
+    *bytes = loudness_ragged_workspace_bytes(n_clips, lens, loudness_sub_block(rate));
+    return BNHIP_OK;
+}
+
+int bnhip_loudness_ragged_normalize_device(int device, const int16_t* d_pcm, int n_clips, const int* lens, int rate, double target_lufs,
+                                           double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* d_out_pcm,
+                                           bnhip_loudness* d_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!d_pcm || !d_out || !d_workspace) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = loudness_ragged_args_check(n_clips, lens, rate, target_lufs, true_peak_dbtp, max_gain_db);
+    if (!rc) rc = workspace_check(d_workspace, workspace_bytes, loudness_ragged_workspace_bytes(n_clips, lens, loudness_sub_block(rate)),
+                                  "bnhip_loudness_ragged_workspace_size");
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    return loudness_ragged_enqueue("loudness_ragged_normalize_device", device, d_pcm, n_clips, lens, rate, target_lufs, true_peak_dbtp,
+                                   max_gain_db, gate_fallback, d_out, d_out_pcm, d_workspace, reinterpret_cast<hipStream_t>(hip_stream));
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_loudness_ragged_normalize_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate, double target_lufs,
+                                          double true_peak_dbtp, double max_gain_db, int gate_fallback, int16_t* out_pcm, bnhip_loudness* out) {
+    if (!pcm || !out) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = loudness_ragged_args_check(n_clips, lens, rate, target_lufs, true_peak_dbtp, max_gain_db);
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    // one device block: the clips, the gained clips, the records, the workspace
+    const size_t pcm_bytes = ragged_total(n_clips, lens) * 2, res_bytes = (size_t)n_clips * sizeof(bnhip_loudness);
+    DevCarve cv;
+    const size_t o_pcm = cv.add(pcm_bytes), o_out = out_pcm ? cv.add(pcm_bytes) : 0, o_res = cv.add(res_bytes);
+    const size_t o_ws = cv.add(loudness_ragged_workspace_bytes(n_clips, lens, loudness_sub_block(rate)));
+    DevBlocks b;
+    cv.base = (char*)b.get(cv.bytes());
+    int16_t* d_pcm = cv.at<int16_t>(o_pcm);
+    int16_t* d_out_pcm = out_pcm ? cv.at<int16_t>(o_out) : nullptr;
+    bnhip_loudness* d_res = cv.at<bnhip_loudness>(o_res);
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice);
+    if (b.he != hipSuccess) return hip_fail("loudness_ragged_normalize_pcm16", b);
+    rc = loudness_ragged_enqueue("loudness_ragged_normalize_pcm16", device, d_pcm, n_clips, lens, rate, target_lufs, true_peak_dbtp, max_gain_db,
+                                 gate_fallback, d_res, d_out_pcm, cv.at<void>(o_ws), nullptr);
+    if (rc) { hipDeviceSynchronize(); return rc; }
+    b.he = hipMemcpy(out, d_res, res_bytes, hipMemcpyDeviceToHost);
+    if (b.he == hipSuccess && out_pcm) b.he = hipMemcpy(out_pcm, d_out_pcm, pcm_bytes, hipMemcpyDeviceToHost);
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("loudness_ragged_normalize_pcm16", b);
     BN_GUARD_END((void)0)
 }
 

@@ -57,6 +57,16 @@ struct DevBlocks {
     ~DevBlocks() { for (void* d : p) hipFree(d); }
 };
 
+// The parts of a call that takes all its device memory as one block: add() every part first (-> its offset, 256-byte aligned, what
+// the device entries ask of a workspace), allocate bytes() once, then at() each offset.
+struct DevCarve {
+    size_t total = 0;
+    char* base = nullptr;
+    size_t add(size_t bytes) { const size_t off = total; total += ((bytes ? bytes : 1) + 255) & ~(size_t)255; return off; }
+    size_t bytes() const { return total; }
+    template <class T> T* at(size_t off) const { return base ? (T*)(base + off) : nullptr; }
+};
+
 // b.he != hipSuccess: BNHIP_E_NOMEM for a failed allocation, else BNHIP_E_RUNTIME; the HIP error is cleared for the thread's next call
 inline int hip_fail(const char* what, const DevBlocks& b) {
     (void)hipGetLastError();
@@ -75,6 +85,27 @@ inline int clip_dims_check(int n_clips, int n) {
     if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
     if (n < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
     return 0;
+}
+
+// A ragged burst's lengths (host array lens[n_clips], each >= 1) before any device is touched.  The clips are packed back to back at
+// 64-bit offsets; the total is held to STREAMINFO's 36 bits, which keeps every flat count of the kernels (frames, segments, true-peak
+// tiles) inside a 31-bit grid.
+constexpr long long RAGGED_MAX_SAMPLES = (1ll << 36) - 1;
+inline int ragged_lens_check(int n_clips, const int* lens) {
+    if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
+    if (!lens) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    long long total = 0;
+    for (int c = 0; c < n_clips; c++) {
+        if (lens[c] < 1) return set_err(BNHIP_E_INVALID, "every clip length must be at least 1");
+        total += lens[c];
+    }
+    if (total > RAGGED_MAX_SAMPLES) return set_err(BNHIP_E_INVALID, "the clips' total length must be below 2^36 samples");
+    return 0;
+}
+inline size_t ragged_total(int n_clips, const int* lens) {
+    size_t total = 0;
+    for (int c = 0; c < n_clips; c++) total += (size_t)lens[c];
+    return total;
 }
 
 // a device entry's caller-owned workspace against what `size_entry` (the bnhip_*_workspace_size to name) answers

@@ -1,11 +1,14 @@
-// FLAC encoding of a batch of equally long mono int16 clips on the device (flac.hip, api_flac.cpp bnhip_flac_*): the project's own
-// deterministic encoder of DESIGN.md §9 "FLAC", a valid RFC 9639 stream per clip.  Every byte is pinned: integer arithmetic, and for
-// the LPC candidates (lpc_order > 0) an fp64 recursion of stated operation order, each operation rounded once (-ffp-contract=off).
+// FLAC encoding of a batch of equally long mono int16 clips, or of a ragged burst of clips of any lengths, on the device (flac.hip,
+// api_flac.cpp bnhip_flac_*): the project's own deterministic encoder of DESIGN.md §9 "FLAC", a valid RFC 9639 stream per clip.
+// Every byte is pinned: integer arithmetic, and for the LPC candidates (lpc_order > 0) an fp64 recursion of stated operation order,
+// each operation rounded once (-ffp-contract=off).  A clip's stream depends on its own samples, gain, rate, seek_interval and
+// lpc_order alone: the ragged form (ragged.h) gives the bytes of the uniform form called per clip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/bnhip.h"
 
@@ -44,14 +47,17 @@ static_assert(sizeof(FlacLpc) == 20, "FlacLpc layout");
 struct FlacWork {
     int n_clips = 0, n = 0, rate = 0, seek_interval = 0;
     int lpc_order = 0;                       // 0: CONSTANT / FIXED / VERBATIM only; M in 1..8: LPC orders 1..M are candidates too
-    int frames = 0;                          // per clip
-    int seek_points = 0;                     // per clip
-    size_t head_bytes = 0;                   // per clip: everything before the first frame
-    FlacRecord* rec = nullptr;               // [n_clips][frames]
-    unsigned long long* rel = nullptr;       // [n_clips][frames] byte offset of the frame's header from the first frame's header
+    int frames = 0;                          // per clip (uniform)
+    long long total_frames = 0;              // of all clips
+    // ragged only: the host's prefix tables start[n_clips + 1] | frame0[n_clips + 1], which launch_flac copies to the head of the
+    // block, where `start` and `frame0` point; NULL for a uniform batch
+    std::vector<long long> tables;
+    const long long *start = nullptr, *frame0 = nullptr;
+    FlacRecord* rec = nullptr;               // [total_frames], clip after clip
+    unsigned long long* rel = nullptr;       // [total_frames] byte offset of the frame's header from its clip's first frame's header
     unsigned long long* clip_bytes = nullptr;  // [n_clips]
     uint32_t *fmin = nullptr, *fmax = nullptr;  // [n_clips] smallest / largest frame
-    FlacLpc* lpc = nullptr;                  // [n_clips][frames], only with lpc_order > 0
+    FlacLpc* lpc = nullptr;                  // [total_frames], only with lpc_order > 0
 };
 int flac_frames(int n);
 int flac_seek_points(int n, int seek_interval);
@@ -59,9 +65,13 @@ int flac_seek_points(int n, int seek_interval);
 size_t flac_max_bytes(int n_clips, int n, int seek_interval);
 size_t flac_workspace_bytes(int n_clips, int n, int lpc_order = 0);      // (lpc_order 0: no side array, the size of before)
 FlacWork flac_work(int n_clips, int n, int rate, int seek_interval, void* d_block, int lpc_order = 0);
+// The same of a ragged burst: lens[n_clips] >= 1 on the host, the clips packed back to back.  The sum of flac_max_bytes(1, lens[c]).
+size_t flac_ragged_max_bytes(int n_clips, const int* lens, int seek_interval);
+size_t flac_ragged_workspace_bytes(int n_clips, const int* lens, int lpc_order);
+FlacWork flac_ragged_work(int n_clips, const int* lens, int rate, int seek_interval, void* d_block, int lpc_order);
 
-// pcm int16 [n_clips][n]; factor [n_clips] nullable (the gain of pcmgain.h, applied as the samples are staged); out: the streams
-// back to back, offsets uint64 [n_clips + 1].  Enqueues analyse, the two layout scans, the stream headers and emit; w.lpc_order picks
+// pcm int16 [n_clips][n], or the packed clips of a ragged work; factor [n_clips] nullable (the gain of pcmgain.h, applied as the samples are staged); out: the streams
+// back to back, offsets uint64 [n_clips + 1].  Enqueues a ragged work's table copy, analyse, the two layout scans, the stream headers and emit; w.lpc_order picks
 // the kernels' LPC forms (0: the forms without).  Nothing is synchronised; no kernel writes at or past out + out_cap.
 void launch_flac(const int16_t* pcm, const double* factor, const FlacWork& w, uint8_t* out, size_t out_cap,
                  unsigned long long* offsets, hipStream_t s);

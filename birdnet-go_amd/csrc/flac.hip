@@ -11,6 +11,10 @@
 //             bit buffer (the zeros of the unary parts cost nothing), CRC-8 and CRC-16, then the frame copied to its byte offset.
 // A frame's absolute offset is offsets[clip] + head_bytes + rel[frame]: emit and headers add the three, which saves a pass that
 // would only store the sums.  Vector stores only.
+// Geometry (ragged.h): a uniform batch runs analyse and emit on a (frames, n_clips) grid and indexes by arithmetic; a ragged burst
+// runs them on the flat list of all clips' frames, and a block finds (clip, frame in clip) by a search over frame0[n_clips + 1].
+// Everything a clip's stream depends on - its length, frame count, seek points, head size - is derived from the clip's own length
+// in both forms, so a clip's bytes do not depend on its neighbours.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +22,7 @@
 
 #include "flac.h"
 #include "pcmgain.h"
+#include "ragged.h"
 
 namespace bnhip {
 
@@ -46,6 +51,15 @@ __host__ __device__ inline int frame_block(int n, int f) {
     const long long left = (long long)n - (long long)f * FLAC_BLOCK;
     return left < FLAC_BLOCK ? (int)left : FLAC_BLOCK;
 }
+__host__ __device__ inline int seek_points_of(int n, int seek_interval) {
+    if (seek_interval <= 0 || n < 1) return 0;
+    const long long last = ((long long)(n - 1) / seek_interval) * seek_interval;       // the last multiple below n
+    return seek_interval >= FLAC_BLOCK ? (int)(last / seek_interval) + 1 : (int)(last / FLAC_BLOCK) + 1;
+}
+// everything of a stream before its first frame
+__host__ __device__ inline u64 stream_head_bytes(int seek_points) {
+    return (u64)FLAC_STREAM_HEAD + (seek_points > 0 ? 4ull + (u64)FLAC_SEEK_POINT * (u64)seek_points : 0ull);
+}
 __host__ __device__ inline int rate_code(int rate) {
     switch (rate) {
         case 88200: return 1; case 176400: return 2; case 192000: return 3; case 8000: return 4; case 16000: return 5;
@@ -67,10 +81,34 @@ __device__ __forceinline__ int fixed_residual(const int* __restrict__ x, int i, 
 // u = 2 r for r >= 0, -2 r - 1 otherwise
 __device__ __forceinline__ uint32_t rice_fold(int r) { return ((uint32_t)r << 1) ^ (uint32_t)(r >> 31); }
 
-__device__ __forceinline__ void stage_frame(const int16_t* __restrict__ pcm, const double* __restrict__ factor, int n, int clip, int f, int bs,
-                                            int* __restrict__ xs, int tid, int threads) {
+// A call's frames: frame0 NULL for a uniform batch of `frames` frames per clip, else the prefix table [n_clips + 1] of a ragged burst.
+struct FlacGeom {
+    ClipGeom c;
+    int frames = 0;
+    const long long* frame0 = nullptr;
+};
+// One clip of the call: its samples, its first sample in pcm, its frames, its first frame's index in rec / rel / lpc.
+struct FlacClip { int n; long long x0; int frames; long long f0; };
+__device__ __forceinline__ FlacClip flac_clip(const FlacGeom& g, int clip) {
+    FlacClip k;
+    k.n = clip_len(g.c, clip); k.x0 = clip_start(g.c, clip);
+    k.frames = g.frame0 ? (int)(g.frame0[clip + 1] - g.frame0[clip]) : g.frames;
+    k.f0 = g.frame0 ? g.frame0[clip] : (long long)clip * g.frames;
+    return k;
+}
+// The frame of a block of analyse / emit: grid (frames, n_clips) of a uniform batch, (all frames) of a ragged burst.
+__device__ __forceinline__ FlacClip block_frame(const FlacGeom& g, int* clip, int* f) {
+    if (g.frame0) {
+        *clip = ragged_clip(g.frame0, g.c.n_clips, (long long)blockIdx.x);
+        *f = (int)((long long)blockIdx.x - g.frame0[*clip]);
+    } else { *clip = blockIdx.y; *f = blockIdx.x; }
+    return flac_clip(g, *clip);
+}
+
+__device__ __forceinline__ void stage_frame(const int16_t* __restrict__ pcm, const double* __restrict__ factor, const FlacClip& k, int clip, int f,
+                                            int bs, int* __restrict__ xs, int tid, int threads) {
     const double fac = factor ? factor[clip] : 1.0;
-    const int16_t* x = pcm + (long long)clip * n + (long long)f * FLAC_BLOCK;          // f * 4096 + i < n
+    const int16_t* x = pcm + k.x0 + (long long)f * FLAC_BLOCK;                         // f * 4096 + i < n
     for (int i = tid; i < bs; i += threads) xs[i] = (int)pcm_gained(x[i], fac);
 }
 
@@ -180,11 +218,11 @@ __device__ __forceinline__ void lpc_coefficients(const int* __restrict__ xs, int
     __syncthreads();
 }
 
-// Grid (frames, n_clips).  LPC: whether LPC orders 1..lpc_order are candidates; without, the block is five waves and the code that of
+// Grid: block_frame's.  LPC: whether LPC orders 1..lpc_order are candidates; without, the block is five waves and the code that of
 // the FIXED-only encoder.  A slot s is a predictor: FIXED order s for s <= 4, LPC order s - 4 above; wave s owns slot s.
 template <bool LPC>
 __global__ __launch_bounds__(LPC ? AN_THREADS_LPC : AN_THREADS) void k_flac_analyse(const int16_t* __restrict__ pcm, const double* __restrict__ factor,
-                                                                                   int n, int frames, int lpc_order, FlacRecord* __restrict__ rec,
+                                                                                   FlacGeom g, int lpc_order, FlacRecord* __restrict__ rec,
                                                                                    FlacLpc* __restrict__ lpc) {
     constexpr int NS = FLAC_MAX_ORDER + 1 + (LPC ? FLAC_MAX_LPC_ORDER : 0);
     constexpr int THREADS = 64 * NS;
@@ -200,9 +238,11 @@ __global__ __launch_bounds__(LPC ? AN_THREADS_LPC : AN_THREADS) void k_flac_anal
     __shared__ u64 cost[NS][FLAC_MAX_PORDER + 1];
     __shared__ Candidate chosen;
     __shared__ LpcShared S;                                         // (LPC only)
-    const int f = blockIdx.x, clip = blockIdx.y, tid = threadIdx.x;
-    const int bs = frame_block(n, f);
-    stage_frame(pcm, factor, n, clip, f, bs, xs, tid, THREADS);
+    const int tid = threadIdx.x;
+    int clip, f;
+    const FlacClip kc = block_frame(g, &clip, &f);
+    const int bs = frame_block(kc.n, f);
+    stage_frame(pcm, factor, kc, clip, f, bs, xs, tid, THREADS);
     if (!LPC)
         for (int i = tid; i < NS * NPART * NK; i += THREADS) (&fine[0][0][0])[i] = 0u;
     __syncthreads();
@@ -324,7 +364,7 @@ __global__ __launch_bounds__(LPC ? AN_THREADS_LPC : AN_THREADS) void k_flac_anal
     const Candidate ch = chosen;
     const bool coded = ch.kind == FLAC_FIXED || ch.kind == FLAC_LPC;
     const int slot = ch.kind == FLAC_LPC ? FLAC_MAX_ORDER + ch.order : ch.order;
-    FlacRecord* r = rec + (long long)clip * frames + f;
+    FlacRecord* r = rec + kc.f0 + f;
     if (tid < NPART) r->k[tid] = (coded && tid < (1 << ch.porder)) ? pk[slot][(1 << ch.porder) - 1 + tid] : (uint8_t)0;
     if (tid == 0) {
         r->kind = (uint8_t)ch.kind; r->order = (uint8_t)ch.order; r->porder = (uint8_t)ch.porder; r->reserved = 0;
@@ -333,7 +373,7 @@ __global__ __launch_bounds__(LPC ? AN_THREADS_LPC : AN_THREADS) void k_flac_anal
         r->reserved2 = 0;
     }
     if constexpr (LPC) {
-        FlacLpc* l = lpc + (long long)clip * frames + f;
+        FlacLpc* l = lpc + kc.f0 + f;
         const bool won = ch.kind == FLAC_LPC;
         if (tid < FLAC_MAX_LPC_ORDER) l->q[tid] = (won && tid < ch.order) ? (int16_t)S.qs[ch.order - 1][tid] : (int16_t)0;
         if (tid == 0) l->shift = won ? S.qshift[ch.order - 1] : 0;
@@ -355,14 +395,17 @@ __device__ __forceinline__ T block_scan(T v, T* __restrict__ sh, int tid) {
 }
 
 // One block per clip: rel[f], the clip's bytes, its smallest and largest frame.
-__global__ __launch_bounds__(256) void k_flac_layout_clip(int frames, u64 head_bytes, const FlacRecord* __restrict__ rec, u64* __restrict__ rel,
+__global__ __launch_bounds__(256) void k_flac_layout_clip(FlacGeom g, int seek_interval, const FlacRecord* __restrict__ rec, u64* __restrict__ rel,
                                                           u64* __restrict__ clip_bytes, uint32_t* __restrict__ fmin, uint32_t* __restrict__ fmax) {
     __shared__ u64 sh[256];
     __shared__ uint32_t lo, hi;
     const int clip = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) { lo = 0xffffffffu; hi = 0u; }
     __syncthreads();
-    const long long base = (long long)clip * frames;
+    const FlacClip kc = flac_clip(g, clip);
+    const int frames = kc.frames;
+    const long long base = kc.f0;
+    const u64 head_bytes = stream_head_bytes(seek_points_of(kc.n, seek_interval));
     u64 carry = 0;
     uint32_t mn = 0xffffffffu, mx = 0u;
     for (int f0 = 0; f0 < frames; f0 += 256) {
@@ -400,12 +443,14 @@ __device__ __forceinline__ void store_be(uint8_t* __restrict__ p, u64 v, int byt
 }
 
 // One block per clip: the stream marker, STREAMINFO, and with seek points the SEEKTABLE.
-__global__ __launch_bounds__(256) void k_flac_headers(int n, int rate, int seek_interval, int frames, int seek_points, const u64* __restrict__ offsets,
+__global__ __launch_bounds__(256) void k_flac_headers(FlacGeom g, int rate, int seek_interval, const u64* __restrict__ offsets,
                                                       const u64* __restrict__ rel, const uint32_t* __restrict__ fmin, const uint32_t* __restrict__ fmax,
                                                       uint8_t* __restrict__ out, u64 out_cap) {
     const int clip = blockIdx.x, tid = threadIdx.x;
+    const FlacClip kc = flac_clip(g, clip);
+    const int n = kc.n, seek_points = seek_points_of(n, seek_interval);
     const u64 base = offsets[clip];
-    const u64 head = (u64)FLAC_STREAM_HEAD + (seek_points > 0 ? 4ull + (u64)FLAC_SEEK_POINT * (u64)seek_points : 0ull);
+    const u64 head = stream_head_bytes(seek_points);
     if (base + head > out_cap) return;
     uint8_t* o = out + base;
     if (tid == 0) {
@@ -425,7 +470,7 @@ __global__ __launch_bounds__(256) void k_flac_headers(int n, int rate, int seek_
         const int f = seek_interval >= FLAC_BLOCK ? (int)(((long long)q * seek_interval) / FLAC_BLOCK) : q;
         uint8_t* p = o + FLAC_STREAM_HEAD + 4 + (u64)FLAC_SEEK_POINT * (u64)q;
         store_be(p, (u64)f * FLAC_BLOCK, 8);
-        store_be(p + 8, rel[(long long)clip * frames + f], 8);
+        store_be(p + 8, rel[kc.f0 + f], 8);
         store_be(p + 16, (u64)frame_block(n, f), 2);
     }
 }
@@ -451,10 +496,10 @@ __device__ __forceinline__ uint32_t crc16_mul(uint32_t a, uint32_t b) {
     return r;
 }
 
-// Grid (frames, n_clips).  LPC: whether a record may name an LPC subframe (then `lpc` holds its coefficients).
+// Grid: block_frame's.  LPC: whether a record may name an LPC subframe (then `lpc` holds its coefficients).
 template <bool LPC>
-__global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restrict__ pcm, const double* __restrict__ factor, int n, int rate, int frames,
-                                                          u64 head_bytes, const FlacRecord* __restrict__ rec, const FlacLpc* __restrict__ lpc,
+__global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restrict__ pcm, const double* __restrict__ factor, FlacGeom g, int rate,
+                                                          int seek_interval, const FlacRecord* __restrict__ rec, const FlacLpc* __restrict__ lpc,
                                                           const u64* __restrict__ rel, const u64* __restrict__ offsets, uint8_t* __restrict__ out,
                                                           u64 out_cap) {
     __shared__ int xs[FLAC_BLOCK];
@@ -464,17 +509,19 @@ __global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restr
     __shared__ uint32_t cv[EM_THREADS];
     __shared__ uint8_t ks[NPART];
     __shared__ int lq[FLAC_MAX_LPC_ORDER + 1];                  // (LPC only) the coefficients, then the shift
-    const int f = blockIdx.x, clip = blockIdx.y, tid = threadIdx.x;
-    const int bs = frame_block(n, f);
-    const FlacRecord* r = rec + (long long)clip * frames + f;
+    const int tid = threadIdx.x;
+    int clip, f;
+    const FlacClip kc = block_frame(g, &clip, &f);
+    const int bs = frame_block(kc.n, f);
+    const FlacRecord* r = rec + kc.f0 + f;
     const int kind = r->kind, o = r->order, P = r->porder;
     const int bytes = (int)r->bytes, hb = frame_head_bytes((u64)f, bs);
-    const u64 off = offsets[clip] + head_bytes + rel[(long long)clip * frames + f];
+    const u64 off = offsets[clip] + stream_head_bytes(seek_points_of(kc.n, seek_interval)) + rel[kc.f0 + f];
     if (bytes > FRAME_MAX_BYTES || bytes < hb + 2 || off + (u64)bytes > out_cap) return;       // (block-uniform)
     if (kind == FLAC_FIXED && (o > FLAC_MAX_ORDER || P > FLAC_MAX_PORDER || (bs >> P) <= o)) return;
     if (kind > FLAC_FIXED && (!LPC || kind != FLAC_LPC || o < 1 || o > FLAC_MAX_LPC_ORDER || P > FLAC_MAX_PORDER || (bs >> P) <= o)) return;
     if constexpr (LPC) {
-        const FlacLpc* l = lpc + (long long)clip * frames + f;
+        const FlacLpc* l = lpc + kc.f0 + f;
         if (kind == FLAC_LPC && (l->shift < 0 || l->shift > FLAC_LPC_MAX_SHIFT)) return;
         if (tid < FLAC_MAX_LPC_ORDER) lq[tid] = l->q[tid];
         if (tid == FLAC_MAX_LPC_ORDER) lq[tid] = l->shift;
@@ -482,7 +529,7 @@ __global__ __launch_bounds__(EM_THREADS) void k_flac_emit(const int16_t* __restr
     const bool is_lpc = LPC && kind == FLAC_LPC;
     // the subframe's bits before the residual's method: the type byte, the warm-up, and for LPC precision, shift and coefficients
     const int pre = is_lpc ? 8 + 16 * o + 4 + 5 + FLAC_LPC_PRECISION * o : 8 + 16 * o;
-    stage_frame(pcm, factor, n, clip, f, bs, xs, tid, EM_THREADS);
+    stage_frame(pcm, factor, kc, clip, f, bs, xs, tid, EM_THREADS);
     for (int i = tid; i < W_WORDS; i += EM_THREADS) W[i] = 0u;
     if (tid < NPART) ks[tid] = r->k[tid];
     {
@@ -607,15 +654,10 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int flac_frames(int n) { return (int)(((long long)n + FLAC_BLOCK - 1) / FLAC_BLOCK); }
 
-int flac_seek_points(int n, int seek_interval) {
-    if (seek_interval <= 0 || n < 1) return 0;
-    const long long last = ((long long)(n - 1) / seek_interval) * seek_interval;       // the last multiple below n
-    return seek_interval >= FLAC_BLOCK ? (int)(last / seek_interval) + 1 : (int)(last / FLAC_BLOCK) + 1;
-}
+int flac_seek_points(int n, int seek_interval) { return seek_points_of(n, seek_interval); }
 
 size_t flac_max_bytes(int n_clips, int n, int seek_interval) {
-    const int pts = flac_seek_points(n, seek_interval);
-    size_t b = (size_t)FLAC_STREAM_HEAD + (pts > 0 ? 4 + (size_t)FLAC_SEEK_POINT * (size_t)pts : 0);
+    size_t b = (size_t)stream_head_bytes(flac_seek_points(n, seek_interval));
     const long long full = n / FLAC_BLOCK;
     const int rem = n % FLAC_BLOCK;
     // full frames: 5 header bytes beside the frame number, the subframe byte, the samples, the CRC-16
@@ -631,47 +673,92 @@ size_t flac_max_bytes(int n_clips, int n, int seek_interval) {
     return b * (size_t)n_clips;
 }
 
-size_t flac_workspace_bytes(int n_clips, int n, int lpc_order) {
-    const size_t F = (size_t)n_clips * (size_t)flac_frames(n);
-    return align256(F * sizeof(FlacRecord)) + align256(F * 8) + align256((size_t)n_clips * 8) + 2 * align256((size_t)n_clips * 4) +
+size_t flac_ragged_max_bytes(int n_clips, const int* lens, int seek_interval) {
+    size_t b = 0;
+    for (int c = 0; c < n_clips; c++) b += flac_max_bytes(1, lens[c], seek_interval);
+    return b;
+}
+
+namespace {
+
+// the arrays of F frames of n_clips clips, after `tables` bytes of prefix tables
+size_t work_bytes(size_t tables, size_t n_clips, size_t F, int lpc_order) {
+    return tables + align256(F * sizeof(FlacRecord)) + align256(F * 8) + align256(n_clips * 8) + 2 * align256(n_clips * 4) +
            (lpc_order > 0 ? align256(F * sizeof(FlacLpc)) : 0);
+}
+void carve(FlacWork& w, char* p, size_t F) {
+    const size_t n_clips = (size_t)w.n_clips;
+    w.rec = (FlacRecord*)p; p += align256(F * sizeof(FlacRecord));
+    w.rel = (u64*)p; p += align256(F * 8);
+    w.clip_bytes = (u64*)p; p += align256(n_clips * 8);
+    w.fmin = (uint32_t*)p; p += align256(n_clips * 4);
+    w.fmax = (uint32_t*)p; p += align256(n_clips * 4);
+    if (w.lpc_order > 0) w.lpc = (FlacLpc*)p;
+}
+size_t ragged_tables_bytes(int n_clips) { return align256(2 * ((size_t)n_clips + 1) * 8); }
+long long ragged_frames(int n_clips, const int* lens) {
+    long long F = 0;
+    for (int c = 0; c < n_clips; c++) F += flac_frames(lens[c]);
+    return F;
+}
+
+}  // namespace
+
+size_t flac_workspace_bytes(int n_clips, int n, int lpc_order) {
+    return work_bytes(0, (size_t)n_clips, (size_t)n_clips * (size_t)flac_frames(n), lpc_order);
+}
+
+size_t flac_ragged_workspace_bytes(int n_clips, const int* lens, int lpc_order) {
+    return work_bytes(ragged_tables_bytes(n_clips), (size_t)n_clips, (size_t)ragged_frames(n_clips, lens), lpc_order);
 }
 
 FlacWork flac_work(int n_clips, int n, int rate, int seek_interval, void* d_block, int lpc_order) {
     FlacWork w;
     w.n_clips = n_clips; w.n = n; w.rate = rate; w.seek_interval = seek_interval; w.lpc_order = lpc_order;
     w.frames = flac_frames(n);
-    w.seek_points = flac_seek_points(n, seek_interval);
-    w.head_bytes = (size_t)FLAC_STREAM_HEAD + (w.seek_points > 0 ? 4 + (size_t)FLAC_SEEK_POINT * (size_t)w.seek_points : 0);
-    const size_t F = (size_t)n_clips * (size_t)w.frames;
-    char* p = (char*)d_block;
-    w.rec = (FlacRecord*)p; p += align256(F * sizeof(FlacRecord));
-    w.rel = (u64*)p; p += align256(F * 8);
-    w.clip_bytes = (u64*)p; p += align256((size_t)n_clips * 8);
-    w.fmin = (uint32_t*)p; p += align256((size_t)n_clips * 4);
-    w.fmax = (uint32_t*)p; p += align256((size_t)n_clips * 4);
-    if (lpc_order > 0) w.lpc = (FlacLpc*)p;
+    w.total_frames = (long long)n_clips * w.frames;
+    carve(w, (char*)d_block, (size_t)w.total_frames);
+    return w;
+}
+
+FlacWork flac_ragged_work(int n_clips, const int* lens, int rate, int seek_interval, void* d_block, int lpc_order) {
+    FlacWork w;
+    w.n_clips = n_clips; w.rate = rate; w.seek_interval = seek_interval; w.lpc_order = lpc_order;
+    // start[n_clips + 1], then frame0[n_clips + 1]
+    w.tables.resize(2 * ((size_t)n_clips + 1));
+    long long* start = w.tables.data(), *frame0 = start + n_clips + 1;
+    start[0] = frame0[0] = 0;
+    for (int c = 0; c < n_clips; c++) { start[c + 1] = start[c] + lens[c]; frame0[c + 1] = frame0[c] + flac_frames(lens[c]); }
+    w.total_frames = frame0[n_clips];
+    w.start = (const long long*)d_block;
+    w.frame0 = w.start + n_clips + 1;
+    carve(w, (char*)d_block + ragged_tables_bytes(n_clips), (size_t)w.total_frames);
     return w;
 }
 
 void launch_flac(const int16_t* pcm, const double* factor, const FlacWork& w, uint8_t* out, size_t out_cap, unsigned long long* offsets,
                  hipStream_t s) {
-    const dim3 grid((unsigned)w.frames, (unsigned)w.n_clips);
+    // (a pageable source is staged before hipMemcpyAsync returns, so the host tables need not outlive the call)
+    if (!w.tables.empty()) (void)hipMemcpyAsync((void*)w.start, w.tables.data(), w.tables.size() * 8, hipMemcpyHostToDevice, s);
+    FlacGeom g;
+    g.c.n_clips = w.n_clips; g.c.n = w.n; g.c.start = w.start;
+    g.frames = w.frames; g.frame0 = w.frame0;
+    const dim3 grid = w.frame0 ? dim3((unsigned)w.total_frames) : dim3((unsigned)w.frames, (unsigned)w.n_clips);
     if (w.lpc_order > 0)
-        hipLaunchKernelGGL(k_flac_analyse<true>, grid, dim3(AN_THREADS_LPC), 0, s, pcm, factor, w.n, w.frames, w.lpc_order, w.rec, w.lpc);
+        hipLaunchKernelGGL(k_flac_analyse<true>, grid, dim3(AN_THREADS_LPC), 0, s, pcm, factor, g, w.lpc_order, w.rec, w.lpc);
     else
-        hipLaunchKernelGGL(k_flac_analyse<false>, grid, dim3(AN_THREADS), 0, s, pcm, factor, w.n, w.frames, 0, w.rec, (FlacLpc*)nullptr);
-    hipLaunchKernelGGL(k_flac_layout_clip, dim3(w.n_clips), dim3(256), 0, s, w.frames, (u64)w.head_bytes, (const FlacRecord*)w.rec, w.rel,
-                       w.clip_bytes, w.fmin, w.fmax);
+        hipLaunchKernelGGL(k_flac_analyse<false>, grid, dim3(AN_THREADS), 0, s, pcm, factor, g, 0, w.rec, (FlacLpc*)nullptr);
+    hipLaunchKernelGGL(k_flac_layout_clip, dim3(w.n_clips), dim3(256), 0, s, g, w.seek_interval, (const FlacRecord*)w.rec, w.rel, w.clip_bytes,
+                       w.fmin, w.fmax);
     hipLaunchKernelGGL(k_flac_layout_batch, dim3(1), dim3(256), 0, s, w.n_clips, (const u64*)w.clip_bytes, offsets);
-    hipLaunchKernelGGL(k_flac_headers, dim3(w.n_clips), dim3(256), 0, s, w.n, w.rate, w.seek_interval, w.frames, w.seek_points,
-                       (const u64*)offsets, (const u64*)w.rel, (const uint32_t*)w.fmin, (const uint32_t*)w.fmax, out, (u64)out_cap);
+    hipLaunchKernelGGL(k_flac_headers, dim3(w.n_clips), dim3(256), 0, s, g, w.rate, w.seek_interval, (const u64*)offsets, (const u64*)w.rel,
+                       (const uint32_t*)w.fmin, (const uint32_t*)w.fmax, out, (u64)out_cap);
     if (w.lpc_order > 0)
-        hipLaunchKernelGGL(k_flac_emit<true>, grid, dim3(EM_THREADS), 0, s, pcm, factor, w.n, w.rate, w.frames, (u64)w.head_bytes,
-                           (const FlacRecord*)w.rec, (const FlacLpc*)w.lpc, (const u64*)w.rel, (const u64*)offsets, out, (u64)out_cap);
+        hipLaunchKernelGGL(k_flac_emit<true>, grid, dim3(EM_THREADS), 0, s, pcm, factor, g, w.rate, w.seek_interval, (const FlacRecord*)w.rec,
+                           (const FlacLpc*)w.lpc, (const u64*)w.rel, (const u64*)offsets, out, (u64)out_cap);
     else
-        hipLaunchKernelGGL(k_flac_emit<false>, grid, dim3(EM_THREADS), 0, s, pcm, factor, w.n, w.rate, w.frames, (u64)w.head_bytes,
-                           (const FlacRecord*)w.rec, (const FlacLpc*)nullptr, (const u64*)w.rel, (const u64*)offsets, out, (u64)out_cap);
+        hipLaunchKernelGGL(k_flac_emit<false>, grid, dim3(EM_THREADS), 0, s, pcm, factor, g, w.rate, w.seek_interval, (const FlacRecord*)w.rec,
+                           (const FlacLpc*)nullptr, (const u64*)w.rel, (const u64*)offsets, out, (u64)out_cap);
 }
 
 }  // namespace bnhip

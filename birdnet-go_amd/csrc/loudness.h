@@ -1,5 +1,11 @@
 // EBU R 128 clip loudness (loudness.hip, api_loudness.cpp bnhip_loudness_*): K-weighted gated integrated loudness, 4x oversampled
-// true peak, the gain plan and the saturating int16 gain of a batch of equally long mono clips, the spec of DESIGN.md §9 in fp64.
+// true peak, the gain plan and the saturating int16 gain of a batch of equally long mono clips, or of a ragged burst of clips of any
+// lengths (ragged.h), the spec of DESIGN.md §9 in fp64.
+//
+// The order in which a sub-block's squares are added depends on the split q (q partial sums, each left to right, added in
+// order), and on nothing else of the call.  So two calls give a clip the same bits exactly when they use the same q: a ragged
+// call and the uniform calls of its clips one by one agree bit for bit when both splits are equal (always, while both calls stay
+// under LOUD_MAX_LANES / 8 sub-blocks and 8 divides S), and to rounding otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +32,10 @@ int loudness_sub_block(int rate);
 // the call under LOUD_MAX_LANES lanes.
 constexpr long long LOUD_MAX_LANES = 1 << 18;
 int loudness_split(int n_clips, int n, int S);
+// the same rule on a call's total: q * sub_blocks <= LOUD_MAX_LANES.  A ragged burst's split is that of the sum of its clips'
+// lens[c] / S sub-blocks, which for equal lengths is loudness_split(n_clips, n, S).
+int loudness_split_total(long long sub_blocks, int S);
+int loudness_ragged_split(int n_clips, const int* lens, int S);
 // the table above for segments of seg_len samples, computed on the host (libm tan / pow / sin; float32-rounded coefficients
 // widened to double)
 std::vector<double> loudness_table(int rate, int seg_len);
@@ -39,21 +49,29 @@ struct LoudPlan {
 
 // The geometry of one call and its scratch; every array lives in one caller-supplied device block.
 struct LoudWork {
-    int n_clips = 0, n = 0, S = 0, Ns = 0, tp_blocks = 0;
-    int q = 1, Sq = 0, Nq = 0;              // segments per sub-block, samples per segment, segments per clip
-    long long G = 0;                        // n_clips * Nq segments
+    int n_clips = 0, n = 0, S = 0, Ns = 0, tp_blocks = 0;       // (n, Ns, tp_blocks: per clip, uniform only)
+    int max_n = 0;                          // the longest clip
+    int q = 1, Sq = 0;                      // segments per sub-block, samples per segment
+    long long G = 0, tiles = 0;             // segments (q per sub-block) and true-peak tiles of all clips
+    // ragged only: the host's prefix tables start | sub0 | tile0, [n_clips + 1] each, which launch_loudness copies to the head of
+    // the block, where the three pointers point; NULL for a uniform batch
+    std::vector<long long> tables;
+    const long long *start = nullptr, *sub0 = nullptr, *tile0 = nullptr;
     double *zs = nullptr, *st = nullptr;    // [G][4] zero-state end states, true start states
     double* Ep = nullptr;                   // [G] per-segment sums of y^2 of the running measurement
-    double *E1 = nullptr, *E2 = nullptr;    // [n_clips][Ns] sub-block energies of the clip, of the lifted clip
-    double* tp = nullptr;                   // [n_clips][tp_blocks] per-block max |.|
+    double *E1 = nullptr, *E2 = nullptr;    // [G / q] sub-block energies of the clips, of the lifted clips; clip after clip
+    double* tp = nullptr;                   // [tiles] per-tile max |.|, clip after clip
     double* pre = nullptr;                  // [n_clips] pre-gain factor of the running measurement
     int* act = nullptr;                     // [n_clips] clip takes part in the running measurement
 };
 size_t loudness_workspace_bytes(int n_clips, int n, int S);
 LoudWork loudness_work(int n_clips, int n, int S, void* d_block);
+// The same of a ragged burst: lens[n_clips] >= 1 on the host, the clips packed back to back.  A clip shorter than S has no sub-block.
+size_t loudness_ragged_workspace_bytes(int n_clips, const int* lens, int S);
+LoudWork loudness_ragged_work(int n_clips, const int* lens, int S, void* d_block);
 
-// pcm int16 [n_clips][n]; d_table: loudness_table on the device; out: bnhip_loudness [n_clips] on the device; out_pcm nullable.
-// Enqueues: init, the measurement (pass A, scan, pass B, true peak), the tail, with plan.gate_fallback the measurement of the
+// pcm int16 [n_clips][n], or the packed clips of a ragged work; d_table: loudness_table on the device; out: bnhip_loudness [n_clips] on the device; out_pcm nullable.
+// Enqueues: a ragged work's table copy, init, the measurement (pass A, scan, pass B, true peak), the tail, with plan.gate_fallback the measurement of the
 // lifted clips and their tail, and with out_pcm the gain.  Nothing is synchronised.
 void launch_loudness(const int16_t* pcm, const LoudWork& w, const double* d_table, const LoudPlan& plan, bnhip_loudness* out,
                      int16_t* out_pcm, hipStream_t s);
@@ -62,8 +80,13 @@ void launch_loudness(const int16_t* pcm, const LoudWork& w, const double* d_tabl
 // What an entry of another unit needs of api_loudness.cpp (the fused loudness + FLAC entry of api_flac.cpp):
 // the argument checks of the normalise entries, answered before any device is touched; -> 0 or a negative BNHIP_E_*
 int loudness_args_check(int n_clips, int n, int rate, double target, double ceiling, double max_gain);
+// the same of a ragged burst, what ragged_lens_check (api_oneshot.h) rejects included
+int loudness_ragged_args_check(int n_clips, const int* lens, int rate, double target, double ceiling, double max_gain);
 // the device (already made current) has its table looked up or uploaded, and the normalise kernels are enqueued on s
 int loudness_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, int n, int rate, double target, double ceiling,
                      double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace, hipStream_t s);
+int loudness_ragged_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, const int* lens, int rate, double target,
+                            double ceiling, double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace,
+                            hipStream_t s);
 
 }  // namespace bnhip

@@ -8,6 +8,9 @@
 // The true peak has no recurrence: every position is 4 x 32 products over a span staged in LDS.  One wave per clip then
 // gates, plans and flags.  A clip under the absolute gate is measured a second time with its lift applied on the fly.
 // All arithmetic is fp64, every operation rounded (no fused multiply-add), vector stores only.
+// Geometry (ragged.h): the segments, sub-blocks and true-peak tiles of all clips are flat lists, clip after clip.  A uniform batch
+// indexes them by arithmetic; a ragged burst finds a unit's clip by a search over the prefix tables sub0 / tile0 [n_clips + 1], and
+// every per-clip count (sub-blocks, tiles, samples) comes from the tables.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +19,7 @@
 
 #include "loudness.h"
 #include "pcmgain.h"
+#include "ragged.h"
 
 #pragma clang fp contract(off)
 
@@ -45,16 +49,29 @@ __host__ __device__ __forceinline__ double kw_step(const double* __restrict__ c,
     return y;
 }
 
+// A call's units: sub0 / tile0 NULL for a uniform batch of Ns sub-blocks and tp_blocks tiles per clip, else the prefix tables.
+struct LoudGeom {
+    ClipGeom c;
+    int Ns = 0, tp_blocks = 0;
+    const long long *sub0 = nullptr, *tile0 = nullptr;
+};
+// a clip's sub-blocks and the first of them in E / (times q) in zs, st, Ep; its tiles and the first of them in partial
+__device__ __forceinline__ int clip_subs(const LoudGeom& g, int clip) { return g.sub0 ? (int)(g.sub0[clip + 1] - g.sub0[clip]) : g.Ns; }
+__device__ __forceinline__ long long clip_sub0(const LoudGeom& g, int clip) { return g.sub0 ? g.sub0[clip] : (long long)clip * g.Ns; }
+__device__ __forceinline__ int clip_tiles(const LoudGeom& g, int clip) { return g.tile0 ? (int)(g.tile0[clip + 1] - g.tile0[clip]) : g.tp_blocks; }
+__device__ __forceinline__ long long clip_tile0(const LoudGeom& g, int clip) { return g.tile0 ? g.tile0[clip] : (long long)clip * g.tp_blocks; }
+
 __global__ __launch_bounds__(256) void k_loud_init(int n_clips, double* __restrict__ pre, int* __restrict__ act) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n_clips) { pre[i] = 1.0; act[i] = 1; }
 }
 
-// PASS_B == 0: out = zs [G][4]; PASS_B == 1: start = [G][4], out = Ep [G].  (S, Ns here: samples per segment, segments per
-// clip.)  Lane l of block b owns segment g = 64 b + l, clip g / Ns, segment g % Ns of it.  Rounds of KW_CHUNK samples: the wave copies row r (segment r's next samples) with one coalesced
-// load per row into a padded LDS tile, then every lane walks its own row.
+// PASS_B == 0: out = zs [G][4]; PASS_B == 1: start = [G][4], out = Ep [G].  (S here: samples per segment; a clip has q segments
+// per sub-block.)  Lane l of block b owns segment g = 64 b + l: of a uniform batch clip g / (q Ns), segment g % (q Ns) of it; of a
+// ragged burst the clip that owns sub-block g / q, and segment g - q sub0[clip] of it.  Rounds of KW_CHUNK samples: the wave
+// copies row r (segment r's next samples) with one coalesced load per row into a padded LDS tile, then every lane walks its own row.
 template <int PASS_B>
-__global__ __launch_bounds__(KW_LANES) void k_loud_kweight(const int16_t* __restrict__ pcm, int n, int S, int Ns, long long G,
+__global__ __launch_bounds__(KW_LANES) void k_loud_kweight(const int16_t* __restrict__ pcm, LoudGeom geo, int S, int q, long long G,
                                                            const double* __restrict__ tab, const double* __restrict__ pre,
                                                            const int* __restrict__ act, const double* __restrict__ start,
                                                            double* __restrict__ out) {
@@ -63,11 +80,14 @@ __global__ __launch_bounds__(KW_LANES) void k_loud_kweight(const int16_t* __rest
     __shared__ long long base[KW_LANES];
     const int lane = threadIdx.x;
     const long long g = (long long)blockIdx.x * KW_LANES + lane;
-    const long long clip = g < G ? g / Ns : 0;
-    const int k = g < G ? (int)(g % Ns) : 0;
+    int clip = 0, k = 0;
+    if (g < G) {
+        if (geo.sub0) { clip = ragged_clip(geo.sub0, geo.c.n_clips, g / q); k = (int)(g - geo.sub0[clip] * q); }
+        else { const int Nq = geo.Ns * q; clip = (int)(g / Nq); k = (int)(g % Nq); }
+    }
     const bool on = g < G && act[clip] != 0;
     if (!__syncthreads_or(on ? 1 : 0)) return;                 // (a block of lifted-run segments with no lifted clip)
-    const long long off = clip * n + (long long)k * S;
+    const long long off = clip_start(geo.c, clip) + (long long)k * S;
     base[lane] = on ? off : -1;
     const double f = on ? pre[clip] : 1.0;
     double c[10];
@@ -83,7 +103,7 @@ __global__ __launch_bounds__(KW_LANES) void k_loud_kweight(const int16_t* __rest
 #pragma unroll 8
         for (int r = 0; r < KW_LANES; r++) {
             const long long b = base[r];
-            tile[r * KW_ROW + lane] = (b >= 0 && col) ? pcm[b + c0 + lane] : (int16_t)0;       // b + c0 + lane < clip n + (k + 1) S <= (clip + 1) n
+            tile[r * KW_ROW + lane] = (b >= 0 && col) ? pcm[b + c0 + lane] : (int16_t)0;       // b + c0 + lane < the clip's start + (k + 1) S <= its end
         }
         __syncthreads();
         const int m = S - c0 < KW_CHUNK ? S - c0 : KW_CHUNK;
@@ -98,17 +118,18 @@ __global__ __launch_bounds__(KW_LANES) void k_loud_kweight(const int16_t* __rest
 }
 
 // start[clip][0] = 0; start[k + 1] = zs[k] + M start[k], the row sums left to right.  One lane per clip.
-__global__ __launch_bounds__(64) void k_loud_scan(int n_clips, int Ns, const double* __restrict__ tab, const int* __restrict__ act,
+__global__ __launch_bounds__(64) void k_loud_scan(LoudGeom geo, int q, const double* __restrict__ tab, const int* __restrict__ act,
                                                   const double* __restrict__ zs, double* __restrict__ st) {
 #pragma clang fp contract(off)
     const int clip = blockIdx.x * 64 + threadIdx.x;
-    if (clip >= n_clips || !act[clip]) return;
+    if (clip >= geo.c.n_clips || !act[clip]) return;
     double M[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) M[i] = tab[LOUD_TAB_M + i];
     double v[4] = {0.0, 0.0, 0.0, 0.0};
-    const long long g0 = (long long)clip * Ns;
-    for (int k = 0; k < Ns; k++) {
+    const long long g0 = clip_sub0(geo, clip) * q;
+    const int Nq = clip_subs(geo, clip) * q;
+    for (int k = 0; k < Nq; k++) {
         double* o = st + (g0 + k) * 4;
         o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
         const double* z = zs + (g0 + k) * 4;
@@ -120,20 +141,25 @@ __global__ __launch_bounds__(64) void k_loud_scan(int n_clips, int Ns, const dou
     }
 }
 
-// Block (bx, clip): positions k = 1024 bx .. +1023 of P = max(|x[k]|, |sum_t c[p][t] x[k - t]|), k < n + 16, each sum from 0.0 with
-// the oldest sample first (t = 31 .. 0).  A thread keeps its 4 positions' 16 sums in registers.
-__global__ __launch_bounds__(TP_THREADS) void k_loud_truepeak(const int16_t* __restrict__ pcm, int n, int tp_blocks,
+// Block (bx, clip) of a uniform batch, the clip's tile bx = blockIdx.x - tile0[clip] of a ragged burst: positions
+// k = 1024 bx .. +1023 of P = max(|x[k]|, |sum_t c[p][t] x[k - t]|), k < n + 16, each sum from 0.0 with the oldest sample first
+// (t = 31 .. 0).  A thread keeps its 4 positions' 16 sums in registers.
+__global__ __launch_bounds__(TP_THREADS) void k_loud_truepeak(const int16_t* __restrict__ pcm, LoudGeom geo,
                                                               const double* __restrict__ tab, const double* __restrict__ pre,
                                                               const int* __restrict__ act, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     __shared__ double xs[TP_SPAN];
     __shared__ double cs[LOUD_TP_PHASES * LOUD_TP_TAPS];
     __shared__ double red[TP_THREADS / 64];
-    const int clip = blockIdx.y, tid = threadIdx.x;
+    const int tid = threadIdx.x;
+    const int clip = geo.tile0 ? ragged_clip(geo.tile0, geo.c.n_clips, (long long)blockIdx.x) : (int)blockIdx.y;
     if (!act[clip]) return;
     const double f = pre[clip];
-    const long long k_base = (long long)blockIdx.x * LOUD_TP_TILE;
-    const int16_t* x = pcm + (long long)clip * n;
+    const long long t0 = clip_tile0(geo, clip);
+    const int bx = geo.tile0 ? (int)((long long)blockIdx.x - t0) : (int)blockIdx.x;
+    const int n = clip_len(geo.c, clip);
+    const long long k_base = (long long)bx * LOUD_TP_TILE;
+    const int16_t* x = pcm + clip_start(geo.c, clip);
     for (int i = tid; i < TP_SPAN; i += TP_THREADS) {
         const long long idx = k_base - (LOUD_TP_TAPS - 1) + i;
         xs[i] = (idx >= 0 && idx < n) ? loud_sample(x[idx], f) : 0.0;
@@ -183,7 +209,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_loud_truepeak(const int16_t* __r
     if (tid == 0) {
 #pragma unroll
         for (int i = 1; i < TP_THREADS / 64; i++) m = fmax(m, red[i]);
-        partial[(long long)clip * tp_blocks + blockIdx.x] = m;
+        partial[t0 + bx] = m;
     }
 }
 
@@ -206,20 +232,22 @@ __device__ double loud_factor(double gain_db) { return gain_db == 0.0 ? 1.0 : po
 
 // One wave per clip.  run 1: the clip's measurement, then the plan - or, for a clip the gate fallback lifts, its lift, pre-gain
 // and active flag, and the plan waits for run 2.  run 2 (lifted clips only): the lifted clip's measurement refines the lift.
-__global__ __launch_bounds__(64) void k_loud_tail(int run, int S, int Ns, int q, int tp_blocks, const double* __restrict__ Ep,
+__global__ __launch_bounds__(64) void k_loud_tail(int run, int S, LoudGeom geo, int q, const double* __restrict__ Ep,
                                                   double* __restrict__ E, const double* __restrict__ partial, LoudPlan pl, double* __restrict__ pre,
                                                   int* __restrict__ act, bnhip_loudness* __restrict__ out) {
 #pragma clang fp contract(off)
     const int clip = blockIdx.x, lane = threadIdx.x;
     if (run == 2 && !act[clip]) return;
+    const int Ns = clip_subs(geo, clip), tp_blocks = clip_tiles(geo, clip);
+    const long long s0 = clip_sub0(geo, clip), t0 = clip_tile0(geo, clip);
     double P = 0.0;
-    for (int i = lane; i < tp_blocks; i += 64) P = fmax(P, partial[(long long)clip * tp_blocks + i]);
+    for (int i = lane; i < tp_blocks; i += 64) P = fmax(P, partial[t0 + i]);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) P = fmax(P, __shfl_xor(P, d));
     // E[k]: the sub-block's q segment sums, added in order
-    double* e = E + (long long)clip * Ns;
+    double* e = E + s0;
     for (int k = lane; k < Ns; k += 64) {
-        const double* p = Ep + ((long long)clip * Ns + k) * q;
+        const double* p = Ep + (s0 + k) * q;
         double a = p[0];
         for (int i = 1; i < q; i++) a = a + p[i];
         e[k] = a;
@@ -288,11 +316,12 @@ __global__ __launch_bounds__(64) void k_loud_tail(int run, int S, int Ns, int q,
 }
 
 // ApplyInt16 (pcmgain.go:52-63) with the clip's reported factor; factor 1 copies
-__global__ __launch_bounds__(256) void k_loud_gain(const int16_t* __restrict__ pcm, int n, const bnhip_loudness* __restrict__ res,
+__global__ __launch_bounds__(256) void k_loud_gain(const int16_t* __restrict__ pcm, ClipGeom geo, const bnhip_loudness* __restrict__ res,
                                                    int16_t* __restrict__ out) {
     const int clip = blockIdx.y;
     const double f = res[clip].factor;
-    const long long i0 = (long long)clip * n;
+    const long long i0 = clip_start(geo, clip);
+    const int n = clip_len(geo, clip);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
         out[i0 + i] = (int16_t)pcm_gained(pcm[i0 + i], f);
 }
@@ -303,11 +332,18 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int loudness_sub_block(int rate) { return (int)std::floor(0.1 * (double)rate + 0.5); }
 
-int loudness_split(int n_clips, int n, int S) {
-    const long long G = (long long)n_clips * (n / S);
+int loudness_split_total(long long sub_blocks, int S) {
     for (int q = 8; q > 1; q >>= 1)
-        if (S % q == 0 && G * q <= LOUD_MAX_LANES) return q;
+        if (S % q == 0 && sub_blocks * q <= LOUD_MAX_LANES) return q;
     return 1;
+}
+
+int loudness_split(int n_clips, int n, int S) { return loudness_split_total((long long)n_clips * (n / S), S); }
+
+int loudness_ragged_split(int n_clips, const int* lens, int S) {
+    long long Gs = 0;
+    for (int c = 0; c < n_clips; c++) Gs += lens[c] / S;
+    return loudness_split_total(Gs, S);
 }
 
 std::vector<double> loudness_table(int rate, int seg_len) {
@@ -370,53 +406,96 @@ std::vector<double> loudness_table(int rate, int seg_len) {
     return t;
 }
 
-size_t loudness_workspace_bytes(int n_clips, int n, int S) {
-    const size_t Gs = (size_t)n_clips * (size_t)(n / S), G = Gs * (size_t)loudness_split(n_clips, n, S);
-    const size_t tpb = (size_t)(((long long)n + LOUD_TP_DRAIN + LOUD_TP_TILE - 1) / LOUD_TP_TILE);
-    return 2 * align256(G * 32) + align256(G * 8) + 2 * align256(Gs * 8) + align256((size_t)n_clips * tpb * 8) + align256((size_t)n_clips * 8) +
-           align256((size_t)n_clips * 4);
-}
+namespace {
 
-LoudWork loudness_work(int n_clips, int n, int S, void* d_block) {
-    LoudWork w;
-    w.n_clips = n_clips; w.n = n; w.S = S; w.Ns = n / S;
-    w.q = loudness_split(n_clips, n, S); w.Sq = S / w.q; w.Nq = w.Ns * w.q;
-    w.tp_blocks = (int)(((long long)n + LOUD_TP_DRAIN + LOUD_TP_TILE - 1) / LOUD_TP_TILE);
-    w.G = (long long)n_clips * w.Nq;
-    const size_t Gs = (size_t)n_clips * (size_t)w.Ns;
-    char* p = (char*)d_block;
+long long tp_tiles(int n) { return ((long long)n + LOUD_TP_DRAIN + LOUD_TP_TILE - 1) / LOUD_TP_TILE; }
+
+// the arrays of Gs sub-blocks cut q ways and T tiles of n_clips clips, after `tables` bytes of prefix tables
+size_t work_bytes(size_t tables, size_t n_clips, size_t Gs, int q, size_t T) {
+    const size_t G = Gs * (size_t)q;
+    return tables + 2 * align256(G * 32) + align256(G * 8) + 2 * align256(Gs * 8) + align256(T * 8) + align256(n_clips * 8) + align256(n_clips * 4);
+}
+void carve(LoudWork& w, char* p, size_t Gs, size_t T) {
     w.zs = (double*)p; p += align256((size_t)w.G * 32);
     w.st = (double*)p; p += align256((size_t)w.G * 32);
     w.Ep = (double*)p; p += align256((size_t)w.G * 8);
     w.E1 = (double*)p; p += align256(Gs * 8);
     w.E2 = (double*)p; p += align256(Gs * 8);
-    w.tp = (double*)p; p += align256((size_t)n_clips * w.tp_blocks * 8);
-    w.pre = (double*)p; p += align256((size_t)n_clips * 8);
+    w.tp = (double*)p; p += align256(T * 8);
+    w.pre = (double*)p; p += align256((size_t)w.n_clips * 8);
     w.act = (int*)p;
+}
+size_t ragged_tables_bytes(int n_clips) { return align256(3 * ((size_t)n_clips + 1) * 8); }
+
+}  // namespace
+
+size_t loudness_workspace_bytes(int n_clips, int n, int S) {
+    return work_bytes(0, (size_t)n_clips, (size_t)n_clips * (size_t)(n / S), loudness_split(n_clips, n, S), (size_t)n_clips * (size_t)tp_tiles(n));
+}
+
+size_t loudness_ragged_workspace_bytes(int n_clips, const int* lens, int S) {
+    size_t Gs = 0, T = 0;
+    for (int c = 0; c < n_clips; c++) { Gs += (size_t)(lens[c] / S); T += (size_t)tp_tiles(lens[c]); }
+    return work_bytes(ragged_tables_bytes(n_clips), (size_t)n_clips, Gs, loudness_split_total((long long)Gs, S), T);
+}
+
+LoudWork loudness_work(int n_clips, int n, int S, void* d_block) {
+    LoudWork w;
+    w.n_clips = n_clips; w.n = n; w.max_n = n; w.S = S; w.Ns = n / S;
+    w.q = loudness_split(n_clips, n, S); w.Sq = S / w.q;
+    w.tp_blocks = (int)tp_tiles(n);
+    w.tiles = (long long)n_clips * w.tp_blocks;
+    w.G = (long long)n_clips * w.Ns * w.q;
+    carve(w, (char*)d_block, (size_t)n_clips * (size_t)w.Ns, (size_t)w.tiles);
+    return w;
+}
+
+LoudWork loudness_ragged_work(int n_clips, const int* lens, int S, void* d_block) {
+    LoudWork w;
+    w.n_clips = n_clips; w.S = S;
+    // start[n_clips + 1], then sub0[n_clips + 1], then tile0[n_clips + 1]
+    w.tables.resize(3 * ((size_t)n_clips + 1));
+    long long* start = w.tables.data(), *sub0 = start + n_clips + 1, *tile0 = sub0 + n_clips + 1;
+    start[0] = sub0[0] = tile0[0] = 0;
+    for (int c = 0; c < n_clips; c++) {
+        start[c + 1] = start[c] + lens[c]; sub0[c + 1] = sub0[c] + lens[c] / S; tile0[c + 1] = tile0[c] + tp_tiles(lens[c]);
+        w.max_n = std::max(w.max_n, lens[c]);
+    }
+    w.q = loudness_split_total(sub0[n_clips], S); w.Sq = S / w.q;
+    w.tiles = tile0[n_clips];
+    w.G = sub0[n_clips] * w.q;
+    w.start = (const long long*)d_block;
+    w.sub0 = w.start + n_clips + 1; w.tile0 = w.sub0 + n_clips + 1;
+    carve(w, (char*)d_block + ragged_tables_bytes(n_clips), (size_t)sub0[n_clips], (size_t)w.tiles);
     return w;
 }
 
 void launch_loudness(const int16_t* pcm, const LoudWork& w, const double* d_table, const LoudPlan& plan, bnhip_loudness* out,
                      int16_t* out_pcm, hipStream_t s) {
+    // (a pageable source is staged before hipMemcpyAsync returns, so the host tables need not outlive the call)
+    if (!w.tables.empty()) (void)hipMemcpyAsync((void*)w.start, w.tables.data(), w.tables.size() * 8, hipMemcpyHostToDevice, s);
+    LoudGeom g;
+    g.c.n_clips = w.n_clips; g.c.n = w.n; g.c.start = w.start;
+    g.Ns = w.Ns; g.tp_blocks = w.tp_blocks; g.sub0 = w.sub0; g.tile0 = w.tile0;
     hipLaunchKernelGGL(k_loud_init, dim3((w.n_clips + 255) / 256), dim3(256), 0, s, w.n_clips, w.pre, w.act);
     const unsigned kw_blocks = (unsigned)((w.G + KW_LANES - 1) / KW_LANES);
+    const dim3 tp_grid = w.tile0 ? dim3((unsigned)w.tiles) : dim3((unsigned)w.tp_blocks, (unsigned)w.n_clips);
     const int runs = !plan.measure && plan.gate_fallback ? 2 : 1;
     for (int run = 1; run <= runs; run++) {
         double* E = run == 1 ? w.E1 : w.E2;
         if (w.G > 0) {
-            hipLaunchKernelGGL(k_loud_kweight<0>, dim3(kw_blocks), dim3(KW_LANES), 0, s, pcm, w.n, w.Sq, w.Nq, w.G, d_table, w.pre, w.act,
+            hipLaunchKernelGGL(k_loud_kweight<0>, dim3(kw_blocks), dim3(KW_LANES), 0, s, pcm, g, w.Sq, w.q, w.G, d_table, w.pre, w.act,
                                (const double*)nullptr, w.zs);
-            hipLaunchKernelGGL(k_loud_scan, dim3((w.n_clips + 63) / 64), dim3(64), 0, s, w.n_clips, w.Nq, d_table, w.act, w.zs, w.st);
-            hipLaunchKernelGGL(k_loud_kweight<1>, dim3(kw_blocks), dim3(KW_LANES), 0, s, pcm, w.n, w.Sq, w.Nq, w.G, d_table, w.pre, w.act,
+            hipLaunchKernelGGL(k_loud_scan, dim3((w.n_clips + 63) / 64), dim3(64), 0, s, g, w.q, d_table, w.act, w.zs, w.st);
+            hipLaunchKernelGGL(k_loud_kweight<1>, dim3(kw_blocks), dim3(KW_LANES), 0, s, pcm, g, w.Sq, w.q, w.G, d_table, w.pre, w.act,
                                (const double*)w.st, w.Ep);
         }
-        hipLaunchKernelGGL(k_loud_truepeak, dim3(w.tp_blocks, w.n_clips), dim3(TP_THREADS), 0, s, pcm, w.n, w.tp_blocks, d_table, w.pre,
-                           w.act, w.tp);
-        hipLaunchKernelGGL(k_loud_tail, dim3(w.n_clips), dim3(64), 0, s, run, w.S, w.Ns, w.q, w.tp_blocks, w.Ep, E, w.tp, plan, w.pre, w.act, out);
+        hipLaunchKernelGGL(k_loud_truepeak, tp_grid, dim3(TP_THREADS), 0, s, pcm, g, d_table, w.pre, w.act, w.tp);
+        hipLaunchKernelGGL(k_loud_tail, dim3(w.n_clips), dim3(64), 0, s, run, w.S, g, w.q, w.Ep, E, w.tp, plan, w.pre, w.act, out);
     }
     if (out_pcm) {
-        const unsigned gx = (unsigned)std::min<long long>(((long long)w.n + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_loud_gain, dim3(gx, w.n_clips), dim3(256), 0, s, pcm, w.n, out, out_pcm);
+        const unsigned gx = (unsigned)std::min<long long>(((long long)w.max_n + 255) / 256, 1024);
+        hipLaunchKernelGGL(k_loud_gain, dim3(gx, w.n_clips), dim3(256), 0, s, pcm, g.c, out, out_pcm);
     }
 }
 

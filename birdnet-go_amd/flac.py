@@ -18,15 +18,19 @@ from .loudness import DEFAULT_MAX_GAIN_DB, _burst, default_options, factor_from_
 LEVEL5_LPC_ORDER = 8
 
 
-def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0, lpc_order=0):
+def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0, lpc_order=0, ragged=False):
     """A burst of detections: a list of int16 mono clips of any lengths -> list of FLAC streams (bytes) in the input's order.
-    gain_db: None, one gain for all, or one per clip; applied on the device (FactorFromDB, then the saturating int16 gain)."""
+    gain_db: None, one gain for all, or one per clip; applied on the device (FactorFromDB, then the saturating int16 gain).
+    ragged: the whole burst in one device call (bnhip_flac_ragged_encode_pcm16) instead of one call per distinct length; the same
+    bytes."""
     clips, groups = _burst(clips)
     if gain_db is None:
         factor = None
     else:
         g = np.broadcast_to(np.asarray(gain_db, np.float64), (len(clips),))
         factor = np.array([factor_from_db(float(v)) for v in g], np.float64)
+    if ragged:
+        return _host.flac_encode_ragged(clips, sample_rate, factor, seek_interval, device=device, lpc_order=lpc_order)
     streams = [None] * len(clips)
     for idx in groups.values():
         out = _host.flac_encode(np.stack([clips[i] for i in idx]), sample_rate, None if factor is None else factor[idx], seek_interval,
@@ -37,11 +41,15 @@ def encode_clips(clips, sample_rate, gain_db=None, seek_interval=0, device=0, lp
 
 
 def normalize_and_encode(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, seek_interval=0, device=0,
-                         lpc_order=0):
+                         lpc_order=0, ragged=False):
     """Loudness-normalise and encode a burst in one device call per length: -> (list of host.Loudness, list of FLAC streams), both
-    in the input's order.  The normalised PCM never reaches the host."""
+    in the input's order.  The normalised PCM never reaches the host.  ragged: the whole burst in one device call
+    (bnhip_loudness_flac_ragged_pcm16), whatever its lengths."""
     opts = opts or default_options()
     clips, groups = _burst(clips)
+    if ragged:
+        return _host.loudness_flac_ragged(clips, sample_rate, opts.target_lufs, opts.true_peak_dbtp, max_gain_db, gate_fallback, seek_interval,
+                                          device=device, lpc_order=lpc_order)
     results, streams = [None] * len(clips), [None] * len(clips)
     for idx in groups.values():
         res, out = _host.loudness_flac(np.stack([clips[i] for i in idx]), sample_rate, opts.target_lufs, opts.true_peak_dbtp, max_gain_db,

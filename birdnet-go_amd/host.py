@@ -48,7 +48,10 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_spectrogram_device", "bnhip_loudness_measure_pcm16", "bnhip_loudness_normalize_pcm16",
            "bnhip_loudness_workspace_size", "bnhip_loudness_normalize_device", "bnhip_flac_max_bytes", "bnhip_flac_workspace_size",
            "bnhip_flac_encode_device", "bnhip_flac_encode_pcm16", "bnhip_loudness_flac_pcm16", "bnhip_flac_lpc_workspace_size",
-           "bnhip_flac_lpc_encode_device", "bnhip_flac_lpc_encode_pcm16", "bnhip_loudness_flac_lpc_pcm16"]
+           "bnhip_flac_lpc_encode_device", "bnhip_flac_lpc_encode_pcm16", "bnhip_loudness_flac_lpc_pcm16",
+           "bnhip_loudness_ragged_workspace_size", "bnhip_loudness_ragged_normalize_pcm16", "bnhip_loudness_ragged_normalize_device",
+           "bnhip_flac_ragged_max_bytes", "bnhip_flac_ragged_workspace_size", "bnhip_flac_ragged_encode_device",
+           "bnhip_flac_ragged_encode_pcm16", "bnhip_loudness_flac_ragged_pcm16"]
 
 
 class HipError(RuntimeError):
@@ -606,6 +609,145 @@ def loudness_flac(clips_pcm16, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max
     _check(lib, lib.bnhip_loudness_flac_lpc_pcm16(device, x.ctypes.data, B, n, int(rate), float(target_lufs), float(true_peak_dbtp),
                                                   float(max_gain_db), 1 if gate_fallback else 0, int(seek_interval), C.addressof(res),
                                                   out.ctypes.data, cap, offsets.ctypes.data, int(lpc_order)))
+    return list(res), _flac_streams(out, offsets)
+
+
+def ragged_pack(clips):
+    """A ragged burst as the bnhip_*_ragged_* entries take it: a list of 1-D int16 clips of any lengths >= 1 -> (the samples packed back
+    to back, int16 [sum of lengths]; the lengths, int32 [n_clips]).  Anything but mono int16 is BNHIP_E_UNSUPPORTED, an empty burst or
+    an empty clip BNHIP_E_INVALID."""
+    clips = [np.ascontiguousarray(c) for c in clips]
+    for c in clips:
+        if c.dtype != np.int16 or c.ndim != 1:
+            raise HipError(E_UNSUPPORTED, "ragged entries take mono int16 clips")
+    if not clips or any(c.size == 0 for c in clips):
+        raise HipError(E_INVALID, "a ragged burst is a non-empty list of non-empty clips")
+    return np.concatenate(clips), np.array([c.size for c in clips], np.int32)
+
+
+def ragged_unpack(packed, lens):
+    """The clips of a packed buffer, in order (copies)."""
+    ends = np.cumsum(np.asarray(lens, np.int64))
+    return [packed[int(e - n):int(e)].copy() for e, n in zip(ends, lens)]
+
+
+def _ragged_lens(lens):
+    x = np.ascontiguousarray(lens, np.int32).reshape(-1)
+    if x.size == 0:
+        raise HipError(E_INVALID, "a ragged burst holds at least one clip")
+    return x
+
+
+def _ragged_size_query(entry, lens, *ints):
+    """A ragged size entry of the C ABI (n_clips, lens, ints in, one size_t out) -> the bytes it answers."""
+    lib = load_library()
+    x = _ragged_lens(lens)
+    fn = getattr(lib, entry)
+    fn.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * len(ints) + [C.POINTER(C.c_size_t)]
+    b = C.c_size_t(0)
+    _check(lib, fn(x.size, x.ctypes.data, *(int(v) for v in ints), C.byref(b)))
+    return b.value
+
+
+def loudness_ragged_workspace_size(lens, rate):
+    """Bytes of device scratch loudness_normalize_ragged_device needs for clips of these lengths."""
+    return _ragged_size_query("bnhip_loudness_ragged_workspace_size", lens, rate)
+
+
+def flac_ragged_max_bytes(lens, seek_interval=0):
+    """The worst-case bytes of the streams of clips of these lengths: the sum of flac_max_bytes(1, n, seek_interval)."""
+    return _ragged_size_query("bnhip_flac_ragged_max_bytes", lens, seek_interval)
+
+
+def flac_ragged_workspace_size(lens, lpc_order=0):
+    """Bytes of device scratch flac_encode_ragged_device needs for clips of these lengths."""
+    return _ragged_size_query("bnhip_flac_ragged_workspace_size", lens, lpc_order)
+
+
+def loudness_normalize_ragged(clips, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, apply=True,
+                              device=0):
+    """loudness_normalize of a ragged burst in one device call: a list of 1-D int16 clips of any lengths -> (list of Loudness, list of
+    int16 outputs or None for apply=False), both in the input's order.  apply=False is also the measurement."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    out = (Loudness * lens.size)()
+    y = np.empty_like(x) if apply else None
+    lib.bnhip_loudness_ragged_normalize_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                          C.c_int, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_loudness_ragged_normalize_pcm16(device, x.ctypes.data, lens.size, lens.ctypes.data, int(rate), float(target_lufs),
+                                                          float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0,
+                                                          y.ctypes.data if apply else None, C.addressof(out)))
+    return list(out), (ragged_unpack(y, lens) if apply else None)
+
+
+def loudness_normalize_ragged_device(d_pcm_ptr, lens, rate, d_out_ptr, d_workspace_ptr, workspace_bytes, d_out_pcm_ptr=None, target_lufs=-23.0,
+                                     true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, device=0, hip_stream_ptr=None):
+    """Device-resident form: the packed clips, the Loudness results, the packed output clips and the workspace are device pointers,
+    lens a host array; enqueued on the stream, not synchronised."""
+    lib = load_library()
+    x = _ragged_lens(lens)
+    lib.bnhip_loudness_ragged_normalize_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_loudness_ragged_normalize_device(device, d_pcm_ptr, x.size, x.ctypes.data, int(rate), float(target_lufs),
+                                                           float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0, d_out_pcm_ptr,
+                                                           d_out_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def _ragged_factor(factor, n_clips):
+    fac = None if factor is None else np.ascontiguousarray(factor, np.float64).reshape(-1)
+    if fac is not None and fac.size != n_clips:
+        raise HipError(E_INVALID, f"factor must hold one value per clip, got {fac.size} for {n_clips}")
+    return fac
+
+
+def flac_encode_ragged(clips, rate, factor=None, seek_interval=0, device=0, raw=False, lpc_order=0):
+    """flac_encode of a ragged burst in one device call: a list of 1-D int16 clips of any lengths -> list of bytes objects in the
+    input's order (raw: the uint8 buffer as written and offsets uint64 [n_clips + 1])."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    B = int(lens.size)
+    fac = _ragged_factor(factor, B)
+    cap = flac_ragged_max_bytes(lens, seek_interval)
+    out = np.empty(cap, np.uint8)
+    offsets = np.zeros(B + 1, np.uint64)
+    lib.bnhip_flac_ragged_encode_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p, C.c_int]
+    _check(lib, lib.bnhip_flac_ragged_encode_pcm16(device, x.ctypes.data, B, lens.ctypes.data, int(rate),
+                                                   fac.ctypes.data if fac is not None else None, int(seek_interval), out.ctypes.data, cap,
+                                                   offsets.ctypes.data, int(lpc_order)))
+    return (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
+
+
+def flac_encode_ragged_device(d_pcm_ptr, lens, rate, d_out_ptr, out_cap, d_offsets_ptr, d_workspace_ptr, workspace_bytes, d_factor_ptr=None,
+                              seek_interval=0, device=0, hip_stream_ptr=None, lpc_order=0):
+    """Device-resident form: the packed clips, the factors (nullable), the output, the uint64 [n_clips + 1] offsets and the workspace
+    (flac_ragged_workspace_size of the same lengths and lpc_order) are device pointers, lens a host array; enqueued on the stream,
+    not synchronised."""
+    lib = load_library()
+    x = _ragged_lens(lens)
+    lib.bnhip_flac_ragged_encode_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+    _check(lib, lib.bnhip_flac_ragged_encode_device(device, d_pcm_ptr, x.size, x.ctypes.data, int(rate), d_factor_ptr, int(seek_interval),
+                                                    d_out_ptr, int(out_cap), d_offsets_ptr, d_workspace_ptr, int(workspace_bytes),
+                                                    hip_stream_ptr, int(lpc_order)))
+
+
+def loudness_flac_ragged(clips, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, seek_interval=0,
+                         device=0, lpc_order=0):
+    """loudness_flac of a ragged burst in one device call and one device allocation: a list of 1-D int16 clips of any lengths ->
+    (list of Loudness, list of bytes objects), both in the input's order."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    B = int(lens.size)
+    res = (Loudness * B)()
+    cap = flac_ragged_max_bytes(lens, seek_interval)
+    out = np.empty(cap, np.uint8)
+    offsets = np.zeros(B + 1, np.uint64)
+    lib.bnhip_loudness_flac_ragged_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
+    _check(lib, lib.bnhip_loudness_flac_ragged_pcm16(device, x.ctypes.data, B, lens.ctypes.data, int(rate), float(target_lufs),
+                                                     float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0, int(seek_interval),
+                                                     C.addressof(res), out.ctypes.data, cap, offsets.ctypes.data, int(lpc_order)))
     return list(res), _flac_streams(out, offsets)
 
 

@@ -82,11 +82,15 @@ def _burst(clips):
     return clips, groups
 
 
-def normalize_clips(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, apply=True, device=0):
+def normalize_clips(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_GAIN_DB, gate_fallback=False, apply=True, device=0, ragged=False):
     """A burst of detections: a list of int16 mono clips of any lengths -> (list of host.Loudness, list of int16 outputs or None),
-    both in the input's order.  Clips are grouped by length, one device call per length."""
+    both in the input's order.  Clips are grouped by length, one device call per length; ragged: the whole burst in one device call
+    (bnhip_loudness_ragged_normalize_pcm16) instead."""
     opts = opts or default_options()
     clips, groups = _burst(clips)
+    if ragged:
+        return _host.loudness_normalize_ragged(clips, sample_rate, opts.target_lufs, opts.true_peak_dbtp, max_gain_db, gate_fallback, apply,
+                                               device=device)
     results, outputs = [None] * len(clips), [None] * len(clips)
     for idx in groups.values():
         res, out = _host.loudness_normalize(np.stack([clips[i] for i in idx]), sample_rate, opts.target_lufs, opts.true_peak_dbtp,

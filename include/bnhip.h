@@ -345,6 +345,50 @@ int bnhip_loudness_flac_lpc_pcm16(int device, const int16_t* pcm, int n_clips, i
                                   double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval,
                                   bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap, uint64_t* offsets, int lpc_order);
 
+/* Ragged bursts: the loudness and FLAC entries above for clips of unequal lengths in one call (a detection under
+ * conf.ExtendedCaptureSettings is as long as the bird kept calling, so a burst of detections has as many lengths as clips).  A
+ * ragged burst is n_clips mono int16 clips of lens[c] >= 1 samples packed back to back in one buffer: clip c starts at sample
+ * lens[0] + .. + lens[c - 1] (64-bit), with no padding or alignment between clips; one rate, one seek_interval, one plan per call.
+ * lens is a host array of n_clips ints in every entry, the device ones included, and need only stay valid until the call returns.
+ * One set of kernel launches covers the burst; their number does not depend on the lengths.
+ *   results: what the uniform entries give each clip on its own.  FLAC: clip c's stream is byte for byte bnhip_flac_lpc_encode_*
+ *   of that clip alone (a stream depends only on its own samples, gain, rate, seek_interval and lpc_order).  Loudness: a clip with
+ *   lens[c] < S has no sub-block, measures -inf and is planned as the uniform entry plans it.  The order in which a sub-block's
+ *   squares are added depends on the call's split q - the largest of 8, 4, 2, 1 that divides S with q * sum(lens[c] / S) <= 2^18,
+ *   for equal lengths exactly the uniform entries' q - so a ragged call and a uniform call give a clip the same bits exactly when
+ *   their q are equal, and agree to rounding otherwise.
+ *   output: as the uniform entries': the streams back to back with offsets[n_clips + 1], the records [n_clips], and out_pcm packed
+ *   like pcm.  bnhip_flac_ragged_max_bytes is the sum over c of bnhip_flac_max_bytes(1, lens[c], seek_interval).
+ *   pcm16 entries: host memory in and out; all device memory of a call is one allocation (input, gained clips, output, offsets,
+ *   records and workspaces carved from it at 256-byte alignment).  normalize: out_pcm NULL = plan only, which is also how to
+ *   measure (there is no ragged measure entry).
+ *   device entries: as the uniform ones; the length tables (prefix sums computed on the host) are copied into the workspace with
+ *   a copy enqueued on hip_stream; nothing is allocated or synchronised.
+ * BNHIP_E_INVALID: what the uniform entries reject, lens == NULL, a lens[c] < 1, and a total length above 2^36 - 1 samples (the 36
+ * bits of STREAMINFO's sample count, which also keeps every flat frame / segment / tile count inside a 31-bit grid); answered
+ * before any device is touched.
+ * Not offered for ragged bursts: the sub_energy output of the measure entry, mixed sample rates in one call, and spectrogram
+ * images (bnhip_spectrogram_* take equally long clips). */
+int bnhip_loudness_ragged_workspace_size(int n_clips, const int* lens, int rate, size_t* bytes);
+int bnhip_loudness_ragged_normalize_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate,
+                                          double target_lufs, double true_peak_dbtp, double max_gain_db, int gate_fallback,
+                                          int16_t* out_pcm, bnhip_loudness* out);
+int bnhip_loudness_ragged_normalize_device(int device, const int16_t* d_pcm, int n_clips, const int* lens, int rate,
+                                           double target_lufs, double true_peak_dbtp, double max_gain_db, int gate_fallback,
+                                           int16_t* d_out_pcm, bnhip_loudness* d_out, void* d_workspace, size_t workspace_bytes,
+                                           void* hip_stream);
+int bnhip_flac_ragged_max_bytes(int n_clips, const int* lens, int seek_interval, size_t* bytes);
+int bnhip_flac_ragged_workspace_size(int n_clips, const int* lens, int lpc_order, size_t* bytes);
+int bnhip_flac_ragged_encode_device(int device, const int16_t* d_pcm, int n_clips, const int* lens, int rate,
+                                    const double* d_factor, int seek_interval, uint8_t* d_out, size_t out_cap,
+                                    uint64_t* d_offsets, void* d_workspace, size_t workspace_bytes, void* hip_stream,
+                                    int lpc_order);
+int bnhip_flac_ragged_encode_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate, const double* factor,
+                                   int seek_interval, uint8_t* out, size_t out_cap, uint64_t* offsets, int lpc_order);
+int bnhip_loudness_flac_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate, double target_lufs,
+                                     double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval,
+                                     bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap, uint64_t* offsets, int lpc_order);
+
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
  * pass through (NewResampler returns nil, :58-60); a too-small destination is an error before any work (:137-144).
