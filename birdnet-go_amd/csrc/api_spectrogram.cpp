@@ -1,4 +1,5 @@
-// C ABI of the detection-clip spectrogram images (bnhip_spectrogram_size, bnhip_spectrogram_pcm16, bnhip_spectrogram_device).
+// C ABI of the detection-clip spectrogram images (bnhip_spectrogram_size, bnhip_spectrogram_pcm16, bnhip_spectrogram_device), and of
+// the render fused with the PNG encoder of api_png.cpp (bnhip_spectrogram_png_pcm16), which needs this file's window and rate tables.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -7,6 +8,7 @@
 
 #include "api_oneshot.h"
 #include "kernels.h"
+#include "png.h"
 #include "resample.h"
 #include "spectrogram.h"
 
@@ -75,6 +77,31 @@ int spec_check(int n_clips, int n, int width, int height, const double* window, 
     return (int)N;
 }
 
+// What a host-pointer render holds under the table lock: the window table and, with a rate change, the phase table and the
+// rendered length.
+struct RenderTables { const SpecTable* tab = nullptr; const RateTable* rt = nullptr; int n_render = 0; };
+int render_tables(const TableLock& lk, int device, int N, const double* window, bool resample, int n, int rate_in, int rate_out, RenderTables* t) {
+    t->n_render = n;
+    if (resample) {
+        t->rt = rate_table(lk, device, rate_in, rate_out);
+        if (!t->rt) return set_err(BNHIP_E_NOMEM, "device allocation failed (resampler phase table)");
+        if (!t->rt->d) return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
+        t->n_render = bnhip_resample_length(n, rate_in, rate_out);
+        if (t->n_render < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
+    }
+    t->tab = spec_table(lk, device, N, window);
+    if (!t->tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (spectrogram table)");
+    return 0;
+}
+// d_pcm int16 [n_clips][n] -> d_img on the null stream; d_f32 [n_clips][n_render] is the resampler's output where there is a rate change
+void render_enqueue(const RenderTables& t, const int16_t* d_pcm, float* d_f32, int n_clips, int n, int width, int height, double top_db,
+                    double range_db, uint8_t* d_img) {
+    const RateTable* rt = t.rt;
+    if (rt) launch_resample(d_pcm, d_f32, rt->d, 1, 0, n_clips, n, t.n_render, rt->L, rt->M, rt->T, rt->half, 0, 0, nullptr);
+    launch_spectrogram(rt ? (const void*)d_f32 : (const void*)d_pcm, rt ? 1 : 0, n_clips, t.n_render, width, height, t.tab->d, t.tab->wsum, top_db,
+                       range_db, d_img, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -99,32 +126,63 @@ int bnhip_spectrogram_pcm16(int device, const int16_t* pcm, int n_clips, int n, 
     int rc = use_device(device);
     if (rc) return rc;
     TableLock lk(g_tables.mu);
-    const RateTable* rt = nullptr;
-    int n_render = n;
-    if (resample) {
-        rt = rate_table(lk, device, rate_in, rate_out);
-        if (!rt) return set_err(BNHIP_E_NOMEM, "device allocation failed (resampler phase table)");
-        if (!rt->d) return set_err(BNHIP_E_UNSUPPORTED, "resample ratio needs a phase table larger than LDS");
-        n_render = bnhip_resample_length(n, rate_in, rate_out);
-        if (n_render < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
-    }
-    const SpecTable* tab = spec_table(lk, device, N, window);
-    if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (spectrogram table)");
+    RenderTables t;
+    rc = render_tables(lk, device, N, window, resample, n, rate_in, rate_out, &t);
+    if (rc) return rc;
     const size_t img_bytes = (size_t)n_clips * height * width;
     DevBlocks b;
     int16_t* d_pcm = (int16_t*)b.get((size_t)n_clips * n * 2);
     uint8_t* d_img = (uint8_t*)b.get(img_bytes);
-    float* d_f32 = resample ? (float*)b.get((size_t)n_clips * n_render * 4) : nullptr;
+    float* d_f32 = resample ? (float*)b.get((size_t)n_clips * t.n_render * 4) : nullptr;
     if (b.he == hipSuccess) b.he = hipMemcpy(d_pcm, pcm, (size_t)n_clips * n * 2, hipMemcpyHostToDevice);
     if (b.he == hipSuccess) {
-        if (resample) launch_resample(d_pcm, d_f32, rt->d, 1, 0, n_clips, n, n_render, rt->L, rt->M, rt->T, rt->half, 0, 0, nullptr);
-        launch_spectrogram(resample ? (const void*)d_f32 : (const void*)d_pcm, resample ? 1 : 0, n_clips, n_render, width, height, tab->d,
-                           tab->wsum, top_db, range_db, d_img, nullptr);
+        render_enqueue(t, d_pcm, d_f32, n_clips, n, width, height, top_db, range_db, d_img);
         b.he = hipGetLastError();
         lk.unlock();
         if (b.he == hipSuccess) b.he = hipMemcpy(image, d_img, img_bytes, hipMemcpyDeviceToHost);  // (the call's one synchronise)
     }
     return b.he == hipSuccess ? BNHIP_OK : hip_fail("spectrogram_pcm16", b);
+    BN_GUARD_END((void)0)
+}
+
+// bnhip_spectrogram_pcm16 with the PNG encoder (png.h) behind the render: the indices never leave the device.  One device block.
+int bnhip_spectrogram_png_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate_in, int rate_out, int width, int height,
+                                const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap,
+                                uint64_t* offsets) {
+    if (!pcm || !palette || !out || !offsets) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    int rc = png_args_check(n_clips, width, height);
+    if (rc) return rc;
+    const int N = spec_check(n_clips, n, width, height, window, top_db, range_db);
+    if (N < 0) return N;
+    const bool resample = rate_out != 0 && rate_out != rate_in;
+    if (resample && (rate_in <= 0 || rate_out < 0)) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
+    rc = png_cap_check(n_clips, width, height, out_cap);
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    TableLock lk(g_tables.mu);
+    RenderTables t;
+    rc = render_tables(lk, device, N, window, resample, n, rate_in, rate_out, &t);
+    if (rc) return rc;
+    const size_t pcm_bytes = (size_t)n_clips * n * 2, cap = png_max_bytes(n_clips, width, height);
+    DevCarve cv;
+    const size_t o_pcm = cv.add(pcm_bytes), o_img = cv.add((size_t)n_clips * height * width);
+    const size_t o_f32 = cv.add(resample ? (size_t)n_clips * t.n_render * 4 : 0), o_bytes = cv.add(cap), o_off = cv.add(((size_t)n_clips + 1) * 8);
+    const size_t o_ws = cv.add(png_workspace_bytes(n_clips, width, height));
+    DevBlocks b;
+    cv.base = (char*)b.get(cv.bytes());
+    int16_t* d_pcm = cv.at<int16_t>(o_pcm);
+    uint8_t *d_img = cv.at<uint8_t>(o_img), *d_bytes = cv.at<uint8_t>(o_bytes);
+    unsigned long long* d_offsets = cv.at<unsigned long long>(o_off);
+    if (b.he == hipSuccess) b.he = hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
+        render_enqueue(t, d_pcm, resample ? cv.at<float>(o_f32) : nullptr, n_clips, n, width, height, top_db, range_db, d_img);
+        launch_png(d_img, png_work(n_clips, width, height, palette, cv.at<void>(o_ws)), d_bytes, cap, d_offsets, nullptr);
+        b.he = hipGetLastError();
+        lk.unlock();
+        if (b.he == hipSuccess) b.he = png_fetch(d_offsets, d_bytes, n_clips, offsets, out);
+    }
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("spectrogram_png_pcm16", b);
     BN_GUARD_END((void)0)
 }
 

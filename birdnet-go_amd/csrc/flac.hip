@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "block_scan.h"
 #include "flac.h"
 #include "pcmgain.h"
 #include "ragged.h"
@@ -378,20 +379,6 @@ __global__ __launch_bounds__(LPC ? AN_THREADS_LPC : AN_THREADS) void k_flac_anal
         if (tid < FLAC_MAX_LPC_ORDER) l->q[tid] = (won && tid < ch.order) ? (int16_t)S.qs[ch.order - 1][tid] : (int16_t)0;
         if (tid == 0) l->shift = won ? S.qshift[ch.order - 1] : 0;
     }
-}
-
-// inclusive scan over a block of 256; sh is in use until the caller's next __syncthreads
-template <typename T>
-__device__ __forceinline__ T block_scan(T v, T* __restrict__ sh, int tid) {
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const T a = tid >= d ? sh[tid - d] : (T)0;
-        __syncthreads();
-        sh[tid] += a;
-        __syncthreads();
-    }
-    return sh[tid];
 }
 
 // One block per clip: rel[f], the clip's bytes, its smallest and largest frame.

@@ -101,6 +101,10 @@ typedef int  (*fn_loud_measure)(int, const int16_t*, int, int, int, bnhip_loudne
 typedef int  (*fn_loud_normalize)(int, const int16_t*, int, int, int, double, double, double, int, int16_t*, bnhip_loudness*);
 typedef int  (*fn_flac_max_bytes)(int, int, int, size_t*);
 typedef int  (*fn_flac_encode_pcm16)(int, const int16_t*, int, int, int, const double*, int, uint8_t*, size_t, uint64_t*);
+typedef int  (*fn_png_max_bytes)(int, int, int, size_t*);
+typedef int  (*fn_png_encode_u8)(int, const uint8_t*, int, int, int, const uint8_t*, uint8_t*, size_t, uint64_t*);
+typedef int  (*fn_spec_png_pcm16)(int, const int16_t*, int, int, int, int, int, int, const double*, double, double, const uint8_t*, uint8_t*, size_t,
+                                  uint64_t*);
 typedef int  (*fn_loud_flac_pcm16)(int, const int16_t*, int, int, int, double, double, double, int, int, bnhip_loudness*, uint8_t*, size_t, uint64_t*);
 typedef int  (*fn_flac_lpc_encode_pcm16)(int, const int16_t*, int, int, int, const double*, int, uint8_t*, size_t, uint64_t*, int);
 typedef int  (*fn_loud_flac_lpc_pcm16)(int, const int16_t*, int, int, int, double, double, double, int, int, bnhip_loudness*, uint8_t*, size_t, uint64_t*, int);
@@ -128,6 +132,7 @@ typedef struct {
     fn_loud_measure loud_measure; fn_loud_normalize loud_normalize;
     fn_flac_max_bytes flac_max_bytes; fn_flac_encode_pcm16 flac_encode_pcm16; fn_loud_flac_pcm16 loud_flac_pcm16;
     fn_flac_lpc_encode_pcm16 flac_lpc_encode_pcm16; fn_loud_flac_lpc_pcm16 loud_flac_lpc_pcm16;
+    fn_png_max_bytes png_max_bytes; fn_png_encode_u8 png_encode_u8; fn_spec_png_pcm16 spec_png_pcm16;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -180,6 +185,8 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(flac_max_bytes, "bnhip_flac_max_bytes"); BN_RESOLVE(flac_encode_pcm16, "bnhip_flac_encode_pcm16");
     BN_RESOLVE(loud_flac_pcm16, "bnhip_loudness_flac_pcm16");
     BN_RESOLVE(flac_lpc_encode_pcm16, "bnhip_flac_lpc_encode_pcm16"); BN_RESOLVE(loud_flac_lpc_pcm16, "bnhip_loudness_flac_lpc_pcm16");
+    BN_RESOLVE(png_max_bytes, "bnhip_png_max_bytes"); BN_RESOLVE(png_encode_u8, "bnhip_png_encode_u8");
+    BN_RESOLVE(spec_png_pcm16, "bnhip_spectrogram_png_pcm16");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -290,6 +297,16 @@ static inline int bnbind_loud_measure(int device, const int16_t* pcm, int n_clip
 static inline int bnbind_loud_normalize(int device, const int16_t* pcm, int n_clips, int n, int rate, double target_lufs, double true_peak_dbtp,
                                         double max_gain_db, int gate_fallback, int16_t* out_pcm, bnhip_loudness* out) {
     return BN.loud_normalize(device, pcm, n_clips, n, rate, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback, out_pcm, out);
+}
+static inline int bnbind_png_max_bytes(int n_images, int width, int height, size_t* bytes) { return BN.png_max_bytes(n_images, width, height, bytes); }
+static inline int bnbind_png_encode_u8(int device, const uint8_t* images, int n_images, int width, int height, const uint8_t* palette, uint8_t* out,
+                                       size_t out_cap, uint64_t* offsets) {
+    return BN.png_encode_u8(device, images, n_images, width, height, palette, out, out_cap, offsets);
+}
+static inline int bnbind_spec_png_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate_in, int rate_out, int width, int height,
+                                        const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap,
+                                        uint64_t* offsets) {
+    return BN.spec_png_pcm16(device, pcm, n_clips, n, rate_in, rate_out, width, height, window, top_db, range_db, palette, out, out_cap, offsets);
 }
 static inline int bnbind_flac_max_bytes(int n_clips, int n, int seek_interval, size_t* bytes) {
     return BN.flac_max_bytes(n_clips, n, seek_interval, bytes);
@@ -1066,7 +1083,7 @@ type SpectrogramOptions struct {
 
 // Spectrogram is the device's answer to one GenerateFromPCM (internal/spectrogram/generator.go:425): the raw image (sox's -r:
 // no axes, no legend) of one mono PCM16 clip as level indices [height][width], Nyquist in row 0.  The host maps the indices
-// through its style's palette and encodes the PNG.  Pixel values follow this engine's own rendering spec; they are not pinned
+// through its style's palette (RenderSpectrogramPNGs returns the finished files instead).  Pixel values follow this engine's own rendering spec; they are not pinned
 // against sox.
 func Spectrogram(pcm []int16, sampleRate, width int, opts SpectrogramOptions, device int) (img []uint8, height int, err error) {
 	return RenderSpectrograms(pcm, 1, sampleRate, width, opts, device)
@@ -1102,6 +1119,71 @@ func RenderSpectrograms(pcm []int16, nClips, sampleRate, width int, opts Spectro
 		return nil, 0, fmt.Errorf("hip: spectrogram failed (%d): %s", int(rc), lastError())
 	}
 	return img, int(h), nil
+}
+
+// EncodePNG encodes nImages index images of one size (images = [nImages][height][width], back to back) as 8-bit indexed PNG streams
+// in ONE device call: the file GenerateFromPCM (internal/spectrogram/generator.go:425-530) finds at its output path.  palette is
+// 256 (r, g, b) entries.  The streams are the engine's own deterministic encoder (DESIGN.md section 9, "PNG"), not image/png's bytes.
+func EncodePNG(images []uint8, nImages, width, height int, palette []uint8, device int) ([][]byte, error) {
+	if nImages <= 0 || width <= 0 || height <= 0 || len(images) != nImages*width*height {
+		return nil, fmt.Errorf("hip: png needs nImages > 0 images of width x height, got %d bytes for %d of %d x %d", len(images), nImages, width, height)
+	}
+	if len(palette) != 768 {
+		return nil, fmt.Errorf("hip: png palette must hold 256 x 3 bytes, got %d", len(palette))
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var capBytes C.size_t
+	if rc := C.bnbind_png_max_bytes(C.int(nImages), C.int(width), C.int(height), &capBytes); rc != 0 {
+		return nil, fmt.Errorf("hip: png_max_bytes failed (%d): %s", int(rc), lastError())
+	}
+	buf := make([]byte, int(capBytes))
+	offsets := make([]C.uint64_t, nImages+1)
+	if rc := C.bnbind_png_encode_u8(C.int(device), (*C.uint8_t)(unsafe.Pointer(&images[0])), C.int(nImages), C.int(width), C.int(height),
+		(*C.uint8_t)(unsafe.Pointer(&palette[0])), (*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
+		return nil, fmt.Errorf("hip: png_encode failed (%d): %s", int(rc), lastError())
+	}
+	return splitStreams(buf, offsets), nil
+}
+
+// RenderSpectrogramPNGs is RenderSpectrograms followed by EncodePNG in ONE device call: the level indices never leave the device,
+// and the finished PNG files of a burst of detections return.  Each stream decodes to the image RenderSpectrograms gives.
+func RenderSpectrogramPNGs(pcm []int16, nClips, sampleRate, width int, opts SpectrogramOptions, palette []uint8, device int) (files [][]byte, height int, err error) {
+	if nClips <= 0 || len(pcm) == 0 || len(pcm)%nClips != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram needs nClips > 0 clips of one length, got %d samples for %d clips", len(pcm), nClips)
+	}
+	if len(palette) != 768 {
+		return nil, 0, fmt.Errorf("hip: png palette must hold 256 x 3 bytes, got %d", len(palette))
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var h, fft C.int
+	if rc := C.bnbind_spec_size(C.int(width), &h, &fft); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram_size failed (%d): %s", int(rc), lastError())
+	}
+	var win *C.double
+	if opts.Window != nil {
+		if len(opts.Window) != int(fft) {
+			return nil, 0, fmt.Errorf("hip: spectrogram window must hold %d coefficients, got %d", int(fft), len(opts.Window))
+		}
+		win = (*C.double)(unsafe.Pointer(&opts.Window[0]))
+	}
+	rangeDB := opts.RangeDB
+	if rangeDB == 0 {
+		rangeDB = 100
+	}
+	var capBytes C.size_t
+	if rc := C.bnbind_png_max_bytes(C.int(nClips), C.int(width), h, &capBytes); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: png_max_bytes failed (%d): %s", int(rc), lastError())
+	}
+	buf := make([]byte, int(capBytes))
+	offsets := make([]C.uint64_t, nClips+1)
+	if rc := C.bnbind_spec_png_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(nClips), C.int(len(pcm)/nClips),
+		C.int(sampleRate), C.int(opts.ResampleRate), C.int(width), h, win, C.double(opts.TopDB), C.double(rangeDB),
+		(*C.uint8_t)(unsafe.Pointer(&palette[0])), (*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram_png failed (%d): %s", int(rc), lastError())
+	}
+	return splitStreams(buf, offsets), int(h), nil
 }
 
 // Loudness is one clip's EBU R 128 measurement and gain plan (bnhip.h bnhip_loudness): what audionorm.Measurement, audionorm.Result

@@ -98,6 +98,12 @@ func RenderSpectrograms([]int16, int, int, int, SpectrogramOptions, int) ([]uint
 	return nil, 0, ErrHIPUnavailable
 }
 
+func EncodePNG([]uint8, int, int, int, []uint8, int) ([][]byte, error) { return nil, ErrHIPUnavailable }
+
+func RenderSpectrogramPNGs([]int16, int, int, int, SpectrogramOptions, []uint8, int) ([][]byte, int, error) {
+	return nil, 0, ErrHIPUnavailable
+}
+
 type Loudness struct {
 	IntegratedLUFS float64
 	TruePeakDBTP   float64

@@ -51,7 +51,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_flac_lpc_encode_device", "bnhip_flac_lpc_encode_pcm16", "bnhip_loudness_flac_lpc_pcm16",
            "bnhip_loudness_ragged_workspace_size", "bnhip_loudness_ragged_normalize_pcm16", "bnhip_loudness_ragged_normalize_device",
            "bnhip_flac_ragged_max_bytes", "bnhip_flac_ragged_workspace_size", "bnhip_flac_ragged_encode_device",
-           "bnhip_flac_ragged_encode_pcm16", "bnhip_loudness_flac_ragged_pcm16"]
+           "bnhip_flac_ragged_encode_pcm16", "bnhip_loudness_flac_ragged_pcm16", "bnhip_png_max_bytes", "bnhip_png_workspace_size",
+           "bnhip_png_encode_device", "bnhip_png_encode_u8", "bnhip_spectrogram_png_pcm16"]
 
 
 class HipError(RuntimeError):
@@ -749,6 +750,77 @@ def loudness_flac_ragged(clips, rate, target_lufs=-23.0, true_peak_dbtp=-1.0, ma
                                                      float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0, int(seek_interval),
                                                      C.addressof(res), out.ctypes.data, cap, offsets.ctypes.data, int(lpc_order)))
     return list(res), _flac_streams(out, offsets)
+
+
+def png_max_bytes(n_images, width, height):
+    """The worst-case bytes of n_images PNG streams of width x height index images (every band stored): what out_cap must be at least."""
+    return _size_query("bnhip_png_max_bytes", n_images, width, height)
+
+
+def png_workspace_size(n_images, width, height):
+    """Bytes of device scratch png_encode_device needs."""
+    return _size_query("bnhip_png_workspace_size", n_images, width, height)
+
+
+def _png_palette(palette):
+    pal = np.ascontiguousarray(palette, np.uint8).reshape(-1)
+    if pal.size != 768:
+        raise HipError(E_INVALID, "palette must be a 256 x 3 uint8 table")
+    return pal
+
+
+def png_encode(images, palette, device=0, raw=False):
+    """PNG streams of a batch of equally sized 8-bit index images in one device call (the file GenerateFromPCM,
+    spectrogram/generator.go:425, gets from its sox child): uint8 [B, H, W] (or [H, W]) and a 256 x 3 palette -> list of B bytes
+    objects, or with raw=True (the streams back to back as uint8, offsets uint64 [B + 1]).  Spec: DESIGN.md §9 "PNG"."""
+    lib = load_library()
+    x = np.ascontiguousarray(images, np.uint8)
+    if x.ndim == 2:
+        x = x[None]
+    if x.ndim != 3 or x.size == 0:
+        raise HipError(E_INVALID, "images must be a non-empty uint8 [B, H, W] array")
+    pal = _png_palette(palette)
+    B, h, w = x.shape
+    cap = png_max_bytes(B, w, h)
+    out, offsets = np.empty(cap, np.uint8), np.zeros(B + 1, np.uint64)
+    lib.bnhip_png_encode_u8.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_png_encode_u8(device, x.ctypes.data, B, w, h, pal.ctypes.data, out.ctypes.data, cap, offsets.ctypes.data))
+    return (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
+
+
+def png_encode_device(d_images_ptr, n_images, width, height, palette, d_out_ptr, out_cap, d_offsets_ptr, d_workspace_ptr, workspace_bytes,
+                      device=0, hip_stream_ptr=None):
+    """Device-resident form: images, streams, offsets (uint64 [n_images + 1]) and workspace (png_workspace_size) are device pointers,
+    the palette a host table; enqueued on the stream, not synchronised."""
+    lib = load_library()
+    pal = _png_palette(palette)
+    lib.bnhip_png_encode_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_png_encode_device(device, d_images_ptr, int(n_images), int(width), int(height), pal.ctypes.data, d_out_ptr,
+                                            int(out_cap), d_offsets_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def spectrogram_png(clips_pcm16, rate, width, palette, rate_out=0, window=None, top_db=0.0, range_db=100.0, device=0, raw=False):
+    """spectrogram and png_encode in one device call - the indices never reach the host: int16 [B, n] (or [n]) -> list of B PNG streams
+    (raw=True: as png_encode), each decoding to the image `spectrogram` returns for the same arguments."""
+    lib = load_library()
+    x = np.ascontiguousarray(clips_pcm16, np.int16)
+    if x.ndim == 1:
+        x = x[None, :]
+    if x.ndim != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise HipError(E_INVALID, "clips must be a non-empty int16 [B, n] array")
+    pal = _png_palette(palette)
+    height, fft_size = spectrogram_size(width)
+    keep, wp = _spectrogram_window(window, fft_size)
+    B = x.shape[0]
+    cap = png_max_bytes(B, width, height)
+    out, offsets = np.empty(cap, np.uint8), np.zeros(B + 1, np.uint64)
+    lib.bnhip_spectrogram_png_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_spectrogram_png_pcm16(device, x.ctypes.data, B, x.shape[1], int(rate), int(rate_out), int(width), height, wp,
+                                                float(top_db), float(range_db), pal.ctypes.data, out.ctypes.data, cap, offsets.ctypes.data))
+    del keep
+    return (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
 
 
 def _sigmoid_f32div(x):

@@ -148,7 +148,7 @@ def write_png(path, image, pal):
         fh.write(data)
 
 
-def _render(clips, sample_rate, width, profile, style, dynamic_range, device):
+def _render_args(sample_rate, width, profile, style, dynamic_range):
     if str(dynamic_range) not in DYNAMIC_RANGES:
         raise ValueError(f'invalid dynamic range "{dynamic_range}" (valid: 80, 100, 120)')
     if width <= 0:
@@ -157,32 +157,73 @@ def _render(clips, sample_rate, width, profile, style, dynamic_range, device):
         raise ValueError("sample rate must be positive")
     profile = profile or bird_profile()
     range_db = float(dynamic_range)
-    height, fft_size = _host.spectrogram_size(width)
-    img = _host.spectrogram(clips, sample_rate, width, rate_out=profile.resample_rate, window=style_window(style, fft_size, range_db),
-                            top_db=0.0, range_db=range_db, device=device)
-    return img, palette(style)
+    _, fft_size = _host.spectrogram_size(width)
+    return dict(rate_out=profile.resample_rate, window=style_window(style, fft_size, range_db), top_db=0.0, range_db=range_db)
 
 
-def generate_from_pcm(pcm_bytes, output_path, width, sample_rate, profile=None, style="default", dynamic_range="100", device=0):
-    """GenerateFromPCM (generator.go:425): 16-bit little-endian mono PCM -> a raw spectrogram PNG at output_path (absolute)."""
+def _render(clips, sample_rate, width, profile, style, dynamic_range, device):
+    kw = _render_args(sample_rate, width, profile, style, dynamic_range)
+    return _host.spectrogram(clips, sample_rate, width, device=device, **kw), palette(style)
+
+
+def read_png_indices(data):
+    """The uint8 [H, W] indices of one of the device encoder's streams (8-bit indexed, filter type 0 on every row; DESIGN.md §9 "PNG")."""
+    pos, idat, shape = 8, [], None
+    while pos < len(data):
+        n, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if kind == b"IHDR":
+            shape = struct.unpack(">II", body[:8])
+        elif kind == b"IDAT":
+            idat.append(body)
+        pos += 12 + n
+    w, h = shape
+    rows = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(h, w + 1)
+    if rows[:, 0].any():
+        raise ValueError("a row's filter type is not 0")
+    return rows[:, 1:].copy()
+
+
+def _render_png(clips, output_paths, sample_rate, width, profile, style, dynamic_range, device):
+    """Render and encode in one device call; the files are the device's streams, the indices come back out of them."""
+    kw = _render_args(sample_rate, width, profile, style, dynamic_range)
+    streams = _host.spectrogram_png(clips, sample_rate, width, palette(style), device=device, **kw)
+    for p, s in zip(output_paths, streams):
+        with open(p, "wb") as fh:
+            fh.write(s)
+    return np.stack([read_png_indices(s) for s in streams])
+
+
+def generate_from_pcm(pcm_bytes, output_path, width, sample_rate, profile=None, style="default", dynamic_range="100", device=0,
+                      device_png=False):
+    """GenerateFromPCM (generator.go:425): 16-bit little-endian mono PCM -> a raw spectrogram PNG at output_path (absolute).
+    device_png: the file is the device encoder's stream (bnhip_spectrogram_png_pcm16) instead of the host's zlib one."""
     if not output_path:
         raise ValueError("output path is empty")
     if not os.path.isabs(output_path):
         raise ValueError("output path must be absolute")
     if len(pcm_bytes) < 2 or len(pcm_bytes) % 2:
         raise ValueError("PCM data must be a non-empty whole number of 16-bit samples")
-    img, pal = _render(np.frombuffer(pcm_bytes, "<i2"), sample_rate, width, profile, style, dynamic_range, device)
+    clip = np.frombuffer(pcm_bytes, "<i2")
+    if device_png:
+        _render_png(clip, [output_path], sample_rate, width, profile, style, dynamic_range, device)
+        return
+    img, pal = _render(clip, sample_rate, width, profile, style, dynamic_range, device)
     write_png(output_path, img[0], pal)
 
 
-def generate_batch(clips_pcm16, output_paths, width, sample_rate, profile=None, style="default", dynamic_range="100", device=0):
-    """Many clips of one length in one device call: int16 [B, n] -> one PNG per clip at output_paths[i].  -> the uint8 [B, H, W] indices."""
+def generate_batch(clips_pcm16, output_paths, width, sample_rate, profile=None, style="default", dynamic_range="100", device=0,
+                   device_png=False):
+    """Many clips of one length in one device call: int16 [B, n] -> one PNG per clip at output_paths[i].  -> the uint8 [B, H, W] indices.
+    device_png: the files are the device encoder's streams, and the returned indices are decoded from them."""
     clips = np.ascontiguousarray(clips_pcm16, np.int16)
     if clips.ndim != 2 or clips.shape[0] != len(output_paths):
         raise ValueError("clips must be int16 [B, n] with one output path per clip")
     for p in output_paths:
         if not p or not os.path.isabs(p):
             raise ValueError("output path must be absolute")
+    if device_png:
+        return _render_png(clips, output_paths, sample_rate, width, profile, style, dynamic_range, device)
     img, pal = _render(clips, sample_rate, width, profile, style, dynamic_range, device)
     for i, p in enumerate(output_paths):
         write_png(p, img[i], pal)

@@ -250,6 +250,36 @@ int bnhip_spectrogram_pcm16(int device, const int16_t* pcm, int n_clips, int n, 
 int bnhip_spectrogram_device(int device, const void* d_samples, int f32, int n_clips, int n, int width, int height,
                              const double* window, double top_db, double range_db, uint8_t* d_image, void* hip_stream);
 
+/* Spectrogram PNG files: the 8-bit indexed PNG that GenerateFromPCM (internal/spectrogram/generator.go:425-530) finds at its output path
+ * after the `sox ... spectrogram -r -o <path>` child, for a batch of width x height index images of one size in one call.  The
+ * streams are this project's own deterministic encoder (DESIGN.md §9 "PNG", restated by tests/pngref.py): valid PNG (ISO/IEC 15948)
+ * around one zlib (RFC 1950) DEFLATE (RFC 1951) stream per image, integer arithmetic throughout, so every byte is pinned; libpng's or
+ * sox's bytes are not a goal.  Per image: signature, IHDR (bit depth 8, colour type 3, no interlace), PLTE (256 entries), one IDAT
+ * chunk per band of ceil(16384 / (width + 1)) rows (filter type 0 on every row), IEND.  A band is, of an all-zero band's fixed-Huffman
+ * block, a literals-only dynamic-Huffman block and a stored block, the first that applies and is strictly smaller than stored.
+ *   images:  uint8 [n_images][height][width]; palette: HOST table uint8 [768] = 256 x (r, g, b) in every entry, the device one included.
+ *   out:     the streams back to back; offsets: uint64 [n_images + 1], image i is out[offsets[i] .. offsets[i + 1]).
+ *   max_bytes: the all-stored bound of n_images streams - what out_cap must be at least; workspace_size: the device scratch of
+ *            encode_device (256-byte aligned).
+ * encode_device: d_images, d_out, d_offsets and d_workspace are device memory; enqueued on hip_stream (NULL = default stream), not
+ *            synchronised, nothing allocated.
+ * encode_u8: host images in, host streams out: one H2D copy, the kernels, a D2H copy of the offsets and then of exactly
+ *            offsets[n_images] bytes; one device allocation.
+ * bnhip_spectrogram_png_pcm16: bnhip_spectrogram_pcm16 and bnhip_png_encode_u8 in one call - the indices never leave the device, and
+ *            each stream decodes to exactly the image bnhip_spectrogram_pcm16 returns; its arguments and limits are that entry's.
+ * width and height 1..4096, n_images 1..65535.  BNHIP_E_INVALID: NULL arguments, sizes outside those ranges, out_cap below
+ * bnhip_png_max_bytes, a workspace that is too small or not 256-byte aligned.  Argument errors are answered before any device is touched. */
+int bnhip_png_max_bytes(int n_images, int width, int height, size_t* bytes);
+int bnhip_png_workspace_size(int n_images, int width, int height, size_t* bytes);
+int bnhip_png_encode_device(int device, const uint8_t* d_images, int n_images, int width, int height, const uint8_t* palette,
+                            uint8_t* d_out, size_t out_cap, uint64_t* d_offsets, void* d_workspace, size_t workspace_bytes,
+                            void* hip_stream);
+int bnhip_png_encode_u8(int device, const uint8_t* images, int n_images, int width, int height, const uint8_t* palette,
+                        uint8_t* out, size_t out_cap, uint64_t* offsets);
+int bnhip_spectrogram_png_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate_in, int rate_out, int width, int height,
+                                const double* window, double top_db, double range_db, const uint8_t* palette,
+                                uint8_t* out, size_t out_cap, uint64_t* offsets);
+
 /* Clip loudness: the EBU R 128 normalisation every exported clip and every BirdWeather upload gets (internal/audiocore/audionorm,
  * internal/audiocore/pcmgain; the export plan with its gate fallback, analysis/processor/actions_database.go:1285-1438; the upload
  * plan, birdweather/encode_native.go:25-66), for a batch of mono int16 clips of one length in one call.  The numbers follow the
