@@ -1,5 +1,7 @@
-// C ABI of the detection-clip spectrogram images (bnhip_spectrogram_size, bnhip_spectrogram_pcm16, bnhip_spectrogram_device), and of
-// the render fused with the PNG encoder of api_png.cpp (bnhip_spectrogram_png_pcm16), which needs this file's window and rate tables.
+// C ABI of the detection-clip spectrogram images (bnhip_spectrogram_size, bnhip_spectrogram_pcm16, bnhip_spectrogram_device), of
+// the render fused with the PNG encoder of api_png.cpp (bnhip_spectrogram_png_pcm16), which needs this file's window and rate tables,
+// and of their forms for a ragged burst (bnhip_spectrogram_ragged_workspace_size, bnhip_spectrogram_ragged_pcm16,
+// bnhip_spectrogram_png_ragged_pcm16, bnhip_spectrogram_ragged_device).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -56,10 +58,9 @@ const RateTable* rate_table(const TableLock& lk, int device, int rate_in, int ra
     });
 }
 
-// what both render entries check before any device is touched; -> the transform length, or a negative BNHIP_E_*
-int spec_check(int n_clips, int n, int width, int height, const double* window, double top_db, double range_db) {
-    if (n_clips <= 0) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
-    if (const int rc = clip_dims_check(n_clips, n)) return rc;
+// what every render entry checks of the image and the level rule before any device is touched; -> the transform length, or a
+// negative BNHIP_E_*
+int spec_image_check(int width, int height, const double* window, double top_db, double range_db) {
     if (width < 1 || width > 4096) return set_err(BNHIP_E_INVALID, "width must be in [1, 4096]");
     if (height < 2 || ((height - 1) & (height - 2)) != 0) return set_err(BNHIP_E_INVALID, "height must be 2^k + 1");
     if (!std::isfinite(range_db) || range_db <= 0.0) return set_err(BNHIP_E_INVALID, "range_db must be finite and positive");
@@ -75,6 +76,15 @@ int spec_check(int n_clips, int n, int width, int height, const double* window, 
         if (!(s != 0.0)) return set_err(BNHIP_E_INVALID, "window coefficients sum to zero");
     }
     return (int)N;
+}
+int spec_check(int n_clips, int n, int width, int height, const double* window, double top_db, double range_db) {
+    if (n_clips <= 0) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    if (const int rc = clip_dims_check(n_clips, n)) return rc;
+    return spec_image_check(width, height, window, top_db, range_db);
+}
+int spec_ragged_check(int n_clips, const int* lens, int width, int height, const double* window, double top_db, double range_db) {
+    if (const int rc = ragged_lens_check(n_clips, lens)) return rc;
+    return spec_image_check(width, height, window, top_db, range_db);
 }
 
 // What a host-pointer render holds under the table lock: the window table and, with a rate change, the phase table and the
@@ -100,6 +110,40 @@ void render_enqueue(const RenderTables& t, const int16_t* d_pcm, float* d_f32, i
     if (rt) launch_resample(d_pcm, d_f32, rt->d, 1, 0, n_clips, n, t.n_render, rt->L, rt->M, rt->T, rt->half, 0, 0, nullptr);
     launch_spectrogram(rt ? (const void*)d_f32 : (const void*)d_pcm, rt ? 1 : 0, n_clips, t.n_render, width, height, t.tab->d, t.tab->wsum, top_db,
                        range_db, d_img, nullptr);
+}
+
+
+// The lengths a ragged burst is rendered at: lens itself, or with a rate change every clip's bnhip_resample_length (held to what
+// ragged_lens_check asks of the input, so that the packed floats and their tiles stay inside the same limits).  -> 0 or a BNHIP_E_*
+int ragged_render_lens(int n_clips, const int* lens, bool resample, int rate_in, int rate_out, std::vector<int>* lens_out) {
+    if (!resample) return 0;
+    if (rate_in <= 0 || rate_out < 0) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
+    lens_out->resize((size_t)n_clips);
+    for (int c = 0; c < n_clips; c++) (*lens_out)[c] = bnhip_resample_length(lens[c], rate_in, rate_out);
+    return ragged_lens_check(n_clips, lens_out->data());
+}
+// the device parts of a ragged host-pointer render, carved from the call's one block: packed PCM, images, the resampler's packed
+// floats and the two kernels' tables
+struct RaggedParts { size_t pcm_bytes, img_bytes, o_pcm, o_img, o_f32, o_rows, o_rtab; };
+RaggedParts ragged_parts(DevCarve& cv, int n_clips, const int* lens, const std::vector<int>& lens_out, int width, int height) {
+    RaggedParts r;
+    r.pcm_bytes = ragged_total(n_clips, lens) * 2;
+    r.img_bytes = (size_t)n_clips * height * width;
+    r.o_pcm = cv.add(r.pcm_bytes); r.o_img = cv.add(r.img_bytes);
+    r.o_f32 = cv.add(lens_out.empty() ? 0 : ragged_total(n_clips, lens_out.data()) * 4);
+    r.o_rows = cv.add(spectrogram_ragged_table_bytes(n_clips));
+    r.o_rtab = cv.add(lens_out.empty() ? 0 : resample_ragged_table_bytes(n_clips));
+    return r;
+}
+// packed d_pcm -> d_img on the null stream, through the ragged resampler where there is a rate change (lens_out not empty)
+void ragged_render_enqueue(const RenderTables& t, const DevCarve& cv, const RaggedParts& r, int n_clips, const int* lens,
+                           const std::vector<int>& lens_out, int width, int height, double top_db, double range_db) {
+    const RateTable* rt = t.rt;
+    const int16_t* d_pcm = cv.at<int16_t>(r.o_pcm);
+    float* d_f32 = cv.at<float>(r.o_f32);
+    if (rt) launch_resample_ragged(d_pcm, d_f32, rt->d, n_clips, lens, lens_out.data(), rt->L, rt->M, rt->T, rt->half, cv.at<void>(r.o_rtab), nullptr);
+    launch_spectrogram_ragged(rt ? (const void*)d_f32 : (const void*)d_pcm, rt ? 1 : 0, n_clips, rt ? lens_out.data() : lens, width, height,
+                              t.tab->d, t.tab->wsum, top_db, range_db, cv.at<uint8_t>(r.o_img), cv.at<void>(r.o_rows), nullptr);
 }
 
 }  // namespace
@@ -200,6 +244,103 @@ int bnhip_spectrogram_device(int device, const void* d_samples, int f32, int n_c
     launch_spectrogram(d_samples, f32 != 0, n_clips, n, width, height, tab->d, tab->wsum, top_db, range_db, d_image,
                        reinterpret_cast<hipStream_t>(hip_stream));
     return launch_status("spectrogram_device");
+    BN_GUARD_END((void)0)
+}
+
+// ---- ragged bursts: n_clips clips of lens[c] samples packed back to back (bnhip.h "Ragged bursts")
+
+int bnhip_spectrogram_ragged_workspace_size(int n_clips, const int* lens, int width, int height, size_t* bytes) {
+    if (!bytes) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    const int N = spec_ragged_check(n_clips, lens, width, height, nullptr, 0.0, 1.0);
+    if (N < 0) return N;
+    *bytes = spectrogram_ragged_table_bytes(n_clips);
+    return BNHIP_OK;
+}
+
+int bnhip_spectrogram_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate_in, int rate_out, int width,
+                                   int height, const double* window, double top_db, double range_db, uint8_t* image) {
+    if (!pcm || !image) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    const int N = spec_ragged_check(n_clips, lens, width, height, window, top_db, range_db);
+    if (N < 0) return N;
+    const bool resample = rate_out != 0 && rate_out != rate_in;
+    std::vector<int> lens_out;
+    int rc = ragged_render_lens(n_clips, lens, resample, rate_in, rate_out, &lens_out);
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    TableLock lk(g_tables.mu);
+    RenderTables t;
+    rc = render_tables(lk, device, N, window, resample, lens[0], rate_in, rate_out, &t);       // (its n_render is not used here)
+    if (rc) return rc;
+    DevCarve cv;
+    const RaggedParts r = ragged_parts(cv, n_clips, lens, lens_out, width, height);
+    DevBlocks b;
+    cv.base = (char*)b.get(cv.bytes());
+    if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(r.o_pcm), pcm, r.pcm_bytes, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
+        ragged_render_enqueue(t, cv, r, n_clips, lens, lens_out, width, height, top_db, range_db);
+        b.he = hipGetLastError();
+        lk.unlock();
+        if (b.he == hipSuccess) b.he = hipMemcpy(image, cv.at<void>(r.o_img), r.img_bytes, hipMemcpyDeviceToHost);  // (the call's one synchronise)
+    }
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("spectrogram_ragged_pcm16", b);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_spectrogram_png_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate_in, int rate_out, int width,
+                                       int height, const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out,
+                                       size_t out_cap, uint64_t* offsets) {
+    if (!pcm || !palette || !out || !offsets) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    const int N = spec_ragged_check(n_clips, lens, width, height, window, top_db, range_db);
+    if (N < 0) return N;
+    const bool resample = rate_out != 0 && rate_out != rate_in;
+    std::vector<int> lens_out;
+    int rc = png_args_check(n_clips, width, height);
+    if (!rc) rc = ragged_render_lens(n_clips, lens, resample, rate_in, rate_out, &lens_out);
+    if (!rc) rc = png_cap_check(n_clips, width, height, out_cap);
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    TableLock lk(g_tables.mu);
+    RenderTables t;
+    rc = render_tables(lk, device, N, window, resample, lens[0], rate_in, rate_out, &t);       // (its n_render is not used here)
+    if (rc) return rc;
+    const size_t cap = png_max_bytes(n_clips, width, height);
+    DevCarve cv;
+    const RaggedParts r = ragged_parts(cv, n_clips, lens, lens_out, width, height);
+    const size_t o_bytes = cv.add(cap), o_off = cv.add(((size_t)n_clips + 1) * 8), o_ws = cv.add(png_workspace_bytes(n_clips, width, height));
+    DevBlocks b;
+    cv.base = (char*)b.get(cv.bytes());
+    uint8_t* d_bytes = cv.at<uint8_t>(o_bytes);
+    unsigned long long* d_offsets = cv.at<unsigned long long>(o_off);
+    if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(r.o_pcm), pcm, r.pcm_bytes, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) {
+        ragged_render_enqueue(t, cv, r, n_clips, lens, lens_out, width, height, top_db, range_db);
+        launch_png(cv.at<uint8_t>(r.o_img), png_work(n_clips, width, height, palette, cv.at<void>(o_ws)), d_bytes, cap, d_offsets, nullptr);
+        b.he = hipGetLastError();
+        lk.unlock();
+        if (b.he == hipSuccess) b.he = png_fetch(d_offsets, d_bytes, n_clips, offsets, out);
+    }
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail("spectrogram_png_ragged_pcm16", b);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_spectrogram_ragged_device(int device, const void* d_samples, int f32, int n_clips, const int* lens, int width, int height,
+                                    const double* window, double top_db, double range_db, uint8_t* d_image, void* d_workspace,
+                                    size_t workspace_bytes, void* hip_stream) {
+    if (!d_samples || !d_image || !d_workspace) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    const int N = spec_ragged_check(n_clips, lens, width, height, window, top_db, range_db);
+    if (N < 0) return N;
+    int rc = workspace_check(d_workspace, workspace_bytes, spectrogram_ragged_table_bytes(n_clips), "bnhip_spectrogram_ragged_workspace_size");
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    TableLock lk(g_tables.mu);
+    const SpecTable* tab = spec_table(lk, device, N, window);
+    if (!tab) return set_err(BNHIP_E_NOMEM, "device allocation failed (spectrogram table)");
+    launch_spectrogram_ragged(d_samples, f32 != 0, n_clips, lens, width, height, tab->d, tab->wsum, top_db, range_db, d_image, d_workspace,
+                              reinterpret_cast<hipStream_t>(hip_stream));
+    return launch_status("spectrogram_ragged_device");
     BN_GUARD_END((void)0)
 }
 

@@ -24,6 +24,14 @@ constexpr size_t RESAMPLE_LDS_MAX = 150 * 1024;
 int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_pcm16, int out_pcm16, int n_clips, int n_in,
                     int n_out, int L, int M, int T, int half, long long i_base, long long n_base, hipStream_t s);
 
+// The one-shot PCM16 -> float32 form for a ragged burst: clip c of lens_in[c] samples packed back to back gives lens_out[c] =
+// bnhip_resample_length(lens_in[c], ..) >= 1 floats, packed the same way (host arrays).  d_tables: device memory of
+// resample_ragged_table_bytes(n_clips) bytes, filled by a copy enqueued on s ahead of the kernel.  One launch whatever the lengths;
+// the sum of ceil(lens_out[c] / 256) must fit a 31-bit grid.  returns 0 on success, -1 if the geometry does not fit LDS
+size_t resample_ragged_table_bytes(int n_clips);
+int launch_resample_ragged(const int16_t* d_in, float* d_out, const float* d_table, int n_clips, const int* lens_in, const int* lens_out,
+                           int L, int M, int T, int half, void* d_tables, hipStream_t s);
+
 // One stream of one call.  Stream indices (n_base, i_next, keep_from) are positions since the stream started.
 struct ResampleBankDesc {
     long long n_base;      // stream index of the first history sample

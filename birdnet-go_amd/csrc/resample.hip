@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "ragged.h"
 #include "resample.h"
 
 namespace bnhip {
@@ -64,16 +65,16 @@ void resample_design(int L, int M, double beta, int half_factor, std::vector<flo
     *half_out = half;
 }
 
+// One tile of 256 outputs [i0, i0 + 256) of one clip, whose first input / output sample is element in0 / out0 of in_ / out_.
 // i_base / n_base (streaming form, api_resample.cpp bnhip_resampler_*): stream index of this launch's first output and of in[0]; the
 // one-shot entries pass 0 / 0.  Inputs before the stream start and beyond the supplied span read as zero.
 template <bool IN_PCM16, bool OUT_PCM16>
-__global__ __launch_bounds__(256) void k_resample(const void* __restrict__ in_, void* __restrict__ out_, const float* __restrict__ table,
-                                                  int n_in, int n_out, int L, int M, int T, int half, long long i_base, long long n_base) {
+__device__ __forceinline__ void resample_tile(const void* __restrict__ in_, void* __restrict__ out_, const float* __restrict__ table,
+                                              size_t in0, size_t out0, int i0, int n_in, int n_out, int L, int M, int T, int half,
+                                              long long i_base, long long n_base) {
     extern __shared__ float sm[];
     float* tab = sm;                       // [L*T]
     float* xs = sm + L * T;                // input span of this block
-    const int clip = blockIdx.y;
-    const int i0 = blockIdx.x * 256;
     const int i1 = min(n_out, i0 + 256);
     for (int k = threadIdx.x; k < L * T; k += 256) tab[k] = table[k];
     // inputs touched by outputs [i0, i1): n from (i0*M+half)/L - (T-1) to ((i1-1)*M+half)/L   (stream indices)
@@ -84,8 +85,8 @@ __global__ __launch_bounds__(256) void k_resample(const void* __restrict__ in_, 
         long long n = lo + k - n_base;     // index into this launch's input
         float v = 0.0f;
         if (lo + k >= 0 && n >= 0 && n < n_in) {
-            if (IN_PCM16) v = (float)reinterpret_cast<const int16_t*>(in_)[(size_t)clip * n_in + n] / 32768.0f;
-            else v = reinterpret_cast<const float*>(in_)[(size_t)clip * n_in + n];
+            if (IN_PCM16) v = (float)reinterpret_cast<const int16_t*>(in_)[in0 + n] / 32768.0f;
+            else v = reinterpret_cast<const float*>(in_)[in0 + n];
         }
         xs[k] = v;
     }
@@ -100,10 +101,34 @@ __global__ __launch_bounds__(256) void k_resample(const void* __restrict__ in_, 
     for (int t = 0; t < T; t++) acc = fmaf(xs[n0 - t], tp[t], acc);
     if (OUT_PCM16) {
         float f = fminf(fmaxf(acc, -1.0f), 1.0f);
-        reinterpret_cast<int16_t*>(out_)[(size_t)clip * n_out + i] = (int16_t)(f * 32767.0f);     // truncation toward zero
+        reinterpret_cast<int16_t*>(out_)[out0 + i] = (int16_t)(f * 32767.0f);     // truncation toward zero
     } else {
-        reinterpret_cast<float*>(out_)[(size_t)clip * n_out + i] = acc;
+        reinterpret_cast<float*>(out_)[out0 + i] = acc;
     }
+}
+
+// n_clips clips of n_in samples each: block (tile, clip)
+template <bool IN_PCM16, bool OUT_PCM16>
+__global__ __launch_bounds__(256) void k_resample(const void* __restrict__ in_, void* __restrict__ out_, const float* __restrict__ table,
+                                                  int n_in, int n_out, int L, int M, int T, int half, long long i_base, long long n_base) {
+    const int clip = blockIdx.y;
+    resample_tile<IN_PCM16, OUT_PCM16>(in_, out_, table, (size_t)clip * n_in, (size_t)clip * n_out, blockIdx.x * 256, n_in, n_out, L, M, T,
+                                       half, i_base, n_base);
+}
+
+// A ragged burst, PCM16 in and float32 out (what the spectrogram render reads): clip c has start_in[c + 1] - start_in[c] samples at
+// start_in[c] of the packed input and its outputs at start_out[c] of the packed output; the tiles of all clips are one flat list,
+// clip c's from tile0[c] on (prefix tables [n_clips + 1], ragged.h).  An output is the uniform launch's fmaf chain over the same
+// staged taps, so its bits are k_resample's on that clip alone.
+__global__ __launch_bounds__(256) void k_resample_ragged(const int16_t* __restrict__ in, float* __restrict__ out,
+                                                         const float* __restrict__ table, const long long* __restrict__ start_in,
+                                                         const long long* __restrict__ start_out, const long long* __restrict__ tile0,
+                                                         int n_clips, int L, int M, int T, int half) {
+    const int clip = ragged_clip(tile0, n_clips, (long long)blockIdx.x);
+    const long long si = start_in[clip], so = start_out[clip];
+    const int tile = (int)((long long)blockIdx.x - tile0[clip]);
+    resample_tile<true, false>(in, out, table, (size_t)si, (size_t)so, tile * 256, (int)(start_in[clip + 1] - si),
+                               (int)(start_out[clip + 1] - so), L, M, T, half, 0, 0);
 }
 
 // returns 0 on success, -1 if the geometry does not fit LDS
@@ -122,6 +147,29 @@ int launch_resample(const void* d_in, void* d_out, const float* d_table, int in_
     else if (!in_pcm16 && !out_pcm16) BN_RS(false, false);
     else BN_RS(true, false);                                        // (the spectrogram entry: PCM in, the float samples it renders out)
 #undef BN_RS
+    return 0;
+}
+
+size_t resample_ragged_table_bytes(int n_clips) { return (3 * ((size_t)n_clips + 1) * 8 + 255) & ~(size_t)255; }
+
+int launch_resample_ragged(const int16_t* d_in, float* d_out, const float* d_table, int n_clips, const int* lens_in, const int* lens_out,
+                           int L, int M, int T, int half, void* d_tables, hipStream_t s) {
+    const size_t lds = resample_lds(L, M, T);
+    if (lds > RESAMPLE_LDS_MAX) return -1;
+    // start_in[n_clips + 1], then start_out[n_clips + 1], then tile0[n_clips + 1]
+    std::vector<long long> t(3 * ((size_t)n_clips + 1));
+    long long* start_in = t.data(), *start_out = start_in + n_clips + 1, *tile0 = start_out + n_clips + 1;
+    start_in[0] = start_out[0] = tile0[0] = 0;
+    for (int c = 0; c < n_clips; c++) {
+        start_in[c + 1] = start_in[c] + lens_in[c]; start_out[c + 1] = start_out[c] + lens_out[c];
+        tile0[c + 1] = tile0[c] + (lens_out[c] + 255) / 256;
+    }
+    // (a pageable source is staged before hipMemcpyAsync returns, so the host tables need not outlive the call)
+    (void)hipMemcpyAsync(d_tables, t.data(), t.size() * 8, hipMemcpyHostToDevice, s);
+    const long long* d = static_cast<const long long*>(d_tables);
+    lds_limit_once<&k_resample_ragged>(160 * 1024);
+    hipLaunchKernelGGL(k_resample_ragged, dim3((unsigned)tile0[n_clips]), dim3(256), lds, s, d_in, d_out, d_table, d, d + n_clips + 1,
+                       d + 2 * ((size_t)n_clips + 1), n_clips, L, M, T, half);
     return 0;
 }
 

@@ -22,6 +22,13 @@ struct SpecPlan {
 };
 SpecPlan spectrogram_plan(int n, int W, int H);
 
+// One clip of a ragged burst as the kernel reads it: its first sample in the packed buffer and its own plan.
+struct SpecClip {
+    long long start;       // the sum of the lengths before it
+    int n, K, F, span_cap;
+};
+static_assert(sizeof(SpecClip) == 24, "row layout");
+
 // [N/2] (cos, -sin)(2 pi j / N) pairs, then the N window coefficients: the table the kernel reads, uploaded once per
 // (device, N, window contents)
 std::vector<double> spectrogram_table(int N, const double* window);
@@ -30,5 +37,11 @@ std::vector<double> spectrogram_table(int N, const double* window);
 // image: uint8 [n_clips][H][W].  The geometry has been validated by the caller (H = 2^k + 1, N within SPEC_N_MIN..SPEC_N_MAX).
 void launch_spectrogram(const void* samples, int f32, int n_clips, int n, int W, int H, const double* d_table, double wsum,
                         double top_db, double range_db, uint8_t* image, hipStream_t s);
+
+// The same for a ragged burst: samples packed back to back, clip c of lens[c] >= 1 samples (host array).  d_rows: device memory of
+// spectrogram_ragged_table_bytes(n_clips) bytes, filled by a copy enqueued on s ahead of the kernel.
+size_t spectrogram_ragged_table_bytes(int n_clips);
+void launch_spectrogram_ragged(const void* samples, int f32, int n_clips, const int* lens, int W, int H, const double* d_table,
+                               double wsum, double top_db, double range_db, uint8_t* image, void* d_rows, hipStream_t s);
 
 }  // namespace bnhip

@@ -20,6 +20,11 @@
 //      H x T byte tile;
 //   5. the tile leaves as runs of T contiguous bytes per image row.
 // A round never splits a column unless K > F, and then it holds frames of that one column only, so the sum order is k = 0..K-1.
+//
+// Ragged bursts (k_spectrogram<S, true>): every image of a burst is W x H, so the grid stays column tiles x clips; what a clip's
+// length decides - its first sample in the packed buffer, n, K, F and span_cap - comes from row blockIdx.y of a table (SpecClip)
+// instead of the launch's scalars, and the LDS carve-up follows that row.  F only groups frames into rounds and the acc carry keeps
+// the sum order, so a clip's image is what the uniform launch gives that clip alone.
 #include "spectrogram.h"
 
 #include <hip/hip_runtime.h>
@@ -45,6 +50,7 @@ struct SpecParams {
     int n, W, H, N, K, T, F, span_cap;
     int log2n2, npass, lg[4];  // N/2 = 2^log2n2 = product of the passes' radices 2^lg[i]
     double pscale, top_db, range_db;
+    const SpecClip* clips;     // ragged: one row per clip, in place of n, K, F and span_cap above; NULL: the uniform arithmetic
 };
 
 // where Z[k] lies after the passes: digit i of k (radix 2^lg[i], least significant first) becomes the digit of weight N/2 / (r_0 .. r_i)
@@ -69,37 +75,43 @@ __device__ __forceinline__ void spec_pass_small(double* zr, double* zi, int base
     for (int m = 0; m < R; m++) { const int i = SPEC_PHYS(base + m); zr[i] = re[m]; zi[i] = im[m]; }
 }
 
-template <typename S>
+template <typename S, bool RAGGED>
 __global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char spec_sm[];
     const int N = p.N, N2 = N >> 1, H = p.H, FS = SPEC_PHYS(N2);
+    // the clip's own geometry: its row of the table, or the launch's scalars
+    SpecClip g{};
+    if (RAGGED) g = p.clips[blockIdx.y];
+    const int F = RAGGED ? g.F : p.F, span_cap = RAGGED ? g.span_cap : p.span_cap;
     double* work = reinterpret_cast<double*>(spec_sm);           // [F][re | im][FS]
-    double* span = work + (size_t)p.F * 2 * FS;                  // [span_cap]
-    double* acc = span + p.span_cap;                             // [H] power sums of a column that spans rounds
+    double* span = work + (size_t)F * 2 * FS;                    // [span_cap]
+    double* acc = span + span_cap;                               // [H] power sums of a column that spans rounds
     int* foff = reinterpret_cast<int*>(acc + H);                 // [SPEC_FMAX] first sample of each frame of the round, in span
     uint8_t* img = reinterpret_cast<uint8_t*>(foff + SPEC_FMAX); // [H][T]
     const int tid = threadIdx.x, clip = blockIdx.y;
     const int c0 = blockIdx.x * p.T, ncol = min(p.T, p.W - c0);
-    const S* x = static_cast<const S*>(p.samples) + (size_t)clip * p.n;
-    const long long den = 2LL * p.K * p.W;
+    const int n = RAGGED ? g.n : p.n, K = RAGGED ? g.K : p.K;
+    // (a packed clip starts at any sample: element loads only)
+    const S* x = static_cast<const S*>(p.samples) + (RAGGED ? (size_t)g.start : (size_t)clip * n);
+    const long long den = 2LL * K * p.W;
     const double2* win2 = reinterpret_cast<const double2*>(p.window);
 
     int c = 0, k0 = 0;
     while (c < ncol) {
         int Cr, Kr;
-        if (p.K <= p.F) { Cr = min(p.F / p.K, ncol - c); Kr = p.K; }
-        else { Cr = 1; Kr = min(p.F, p.K - k0); }
+        if (K <= F) { Cr = min(F / K, ncol - c); Kr = K; }
+        else { Cr = 1; Kr = min(F, K - k0); }
         const int nf = Cr * Kr;
         // ---- 1. the round's span: frame g = column * K + k is centred at floor((2 g + 1) n / (2 K W))
-        const long long g0 = (long long)(c0 + c) * p.K + k0;
-        const long long s_lo = ((2 * g0 + 1) * p.n) / den - N2;
-        const long long s_hi = ((2 * (g0 + nf - 1) + 1) * p.n) / den + N2;
-        const int len = (int)min(s_hi - s_lo, (long long)p.span_cap);
-        if (tid < nf) foff[tid] = (int)(((2 * (g0 + tid) + 1) * p.n) / den - N2 - s_lo);
+        const long long g0 = (long long)(c0 + c) * K + k0;
+        const long long s_lo = ((2 * g0 + 1) * n) / den - N2;
+        const long long s_hi = ((2 * (g0 + nf - 1) + 1) * n) / den + N2;
+        const int len = (int)min(s_hi - s_lo, (long long)span_cap);
+        if (tid < nf) foff[tid] = (int)(((2 * (g0 + tid) + 1) * n) / den - N2 - s_lo);
         for (int i = tid; i < len; i += SPEC_THREADS) {
             const long long s = s_lo + i;
             double v = 0.0;
-            if (s >= 0 && s < p.n) v = std::is_same<S, int16_t>::value ? (double)x[s] / 32768.0 : (double)x[s];
+            if (s >= 0 && s < n) v = std::is_same<S, int16_t>::value ? (double)x[s] / 32768.0 : (double)x[s];
             span[i] = v;
         }
         __syncthreads();
@@ -149,7 +161,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
             lgL -= lr;
         }
         // ---- 4. spectrum of the real frames, power sums, level indices
-        const bool first = k0 == 0, last = k0 + Kr == p.K;
+        const bool first = k0 == 0, last = k0 + Kr == K;
         for (int lc = 0; lc < Cr; lc++)
             for (int b = tid; b < H; b += SPEC_THREADS) {
                 double sum = first ? 0.0 : acc[b];
@@ -170,7 +182,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
                     sum += (xr * xr + xi * xi) * p.pscale;
                 }
                 if (!last) { acc[b] = sum; continue; }
-                const double P = sum / (double)p.K;
+                const double P = sum / (double)K;
                 int level = 0;
                 if (P > 0.0) {
                     const double db = 10.0 * log10(P);
@@ -181,8 +193,8 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
                 img[(H - 1 - b) * p.T + c + lc] = (uint8_t)level;
             }
         __syncthreads();
-        if (p.K <= p.F) c += Cr;
-        else { k0 += Kr; if (k0 == p.K) { k0 = 0; c++; } }
+        if (K <= F) c += Cr;
+        else { k0 += Kr; if (k0 == K) { k0 = 0; c++; } }
     }
     // ---- 5. rows of ncol contiguous bytes
     uint8_t* out = p.image + (size_t)clip * H * p.W + c0;
@@ -229,27 +241,63 @@ std::vector<double> spectrogram_table(int N, const double* window) {
     return t;
 }
 
-void launch_spectrogram(const void* samples, int f32, int n_clips, int n, int W, int H, const double* d_table, double wsum,
-                        double top_db, double range_db, uint8_t* image, hipStream_t s) {
-    const SpecPlan q = spectrogram_plan(n, W, H);
+// what a launch holds besides the clips' geometry
+static SpecParams spec_params(const void* samples, int W, int H, const double* d_table, double wsum, double top_db, double range_db,
+                              uint8_t* image) {
     SpecParams p{};
     p.samples = samples;
+    p.N = 2 * (H - 1);
     p.tw = reinterpret_cast<const double2*>(d_table);
-    p.window = d_table + q.N;
+    p.window = d_table + p.N;
     p.image = image;
-    p.n = n; p.W = W; p.H = H; p.N = q.N; p.K = q.K; p.T = q.T; p.F = q.F; p.span_cap = q.span_cap;
-    while ((2 << p.log2n2) < q.N) p.log2n2++;
+    p.W = W; p.H = H;
+    while ((2 << p.log2n2) < p.N) p.log2n2++;
     for (int rem = p.log2n2; rem > 0;) { const int lr = rem >= 3 ? 3 : rem; p.lg[p.npass++] = lr; rem -= lr; }
     p.pscale = (2.0 / wsum) * (2.0 / wsum);
     p.top_db = top_db; p.range_db = range_db;
-    const dim3 grid((W + q.T - 1) / q.T, n_clips);
+    return p;
+}
+
+template <bool RAGGED>
+static void spec_launch(const SpecParams& p, int f32, int n_clips, size_t lds, hipStream_t s) {
+    const dim3 grid((p.W + p.T - 1) / p.T, n_clips);
     if (f32) {
-        lds_limit_once<&k_spectrogram<float>>(160 * 1024);
-        hipLaunchKernelGGL(k_spectrogram<float>, grid, dim3(SPEC_THREADS), q.lds, s, p);
+        lds_limit_once<&k_spectrogram<float, RAGGED>>(160 * 1024);
+        hipLaunchKernelGGL((k_spectrogram<float, RAGGED>), grid, dim3(SPEC_THREADS), lds, s, p);
     } else {
-        lds_limit_once<&k_spectrogram<int16_t>>(160 * 1024);
-        hipLaunchKernelGGL(k_spectrogram<int16_t>, grid, dim3(SPEC_THREADS), q.lds, s, p);
+        lds_limit_once<&k_spectrogram<int16_t, RAGGED>>(160 * 1024);
+        hipLaunchKernelGGL((k_spectrogram<int16_t, RAGGED>), grid, dim3(SPEC_THREADS), lds, s, p);
     }
+}
+
+void launch_spectrogram(const void* samples, int f32, int n_clips, int n, int W, int H, const double* d_table, double wsum,
+                        double top_db, double range_db, uint8_t* image, hipStream_t s) {
+    const SpecPlan q = spectrogram_plan(n, W, H);
+    SpecParams p = spec_params(samples, W, H, d_table, wsum, top_db, range_db, image);
+    p.n = n; p.K = q.K; p.T = q.T; p.F = q.F; p.span_cap = q.span_cap;
+    spec_launch<false>(p, f32, n_clips, q.lds, s);
+}
+
+size_t spectrogram_ragged_table_bytes(int n_clips) { return ((size_t)n_clips * sizeof(SpecClip) + 255) & ~(size_t)255; }
+
+void launch_spectrogram_ragged(const void* samples, int f32, int n_clips, const int* lens, int W, int H, const double* d_table,
+                               double wsum, double top_db, double range_db, uint8_t* image, void* d_rows, hipStream_t s) {
+    // the plan of every clip on the host; the launch's LDS is the largest any of them needs (T depends on N only)
+    std::vector<SpecClip> rows((size_t)n_clips);
+    SpecParams p = spec_params(samples, W, H, d_table, wsum, top_db, range_db, image);
+    size_t lds = 0;
+    long long start = 0;
+    for (int c = 0; c < n_clips; c++) {
+        const SpecPlan q = spectrogram_plan(lens[c], W, H);
+        rows[c] = {start, lens[c], q.K, q.F, q.span_cap};
+        start += lens[c];
+        lds = std::max(lds, q.lds);
+        p.T = q.T;
+    }
+    // (a pageable source is staged before hipMemcpyAsync returns, so the host rows need not outlive the call)
+    (void)hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(SpecClip), hipMemcpyHostToDevice, s);
+    p.clips = static_cast<const SpecClip*>(d_rows);
+    spec_launch<true>(p, f32, n_clips, lds, s);
 }
 
 }  // namespace bnhip

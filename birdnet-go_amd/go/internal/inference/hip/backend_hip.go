@@ -105,6 +105,9 @@ typedef int  (*fn_png_max_bytes)(int, int, int, size_t*);
 typedef int  (*fn_png_encode_u8)(int, const uint8_t*, int, int, int, const uint8_t*, uint8_t*, size_t, uint64_t*);
 typedef int  (*fn_spec_png_pcm16)(int, const int16_t*, int, int, int, int, int, int, const double*, double, double, const uint8_t*, uint8_t*, size_t,
                                   uint64_t*);
+typedef int  (*fn_spec_ragged_pcm16)(int, const int16_t*, int, const int*, int, int, int, int, const double*, double, double, uint8_t*);
+typedef int  (*fn_spec_png_ragged_pcm16)(int, const int16_t*, int, const int*, int, int, int, int, const double*, double, double, const uint8_t*,
+                                         uint8_t*, size_t, uint64_t*);
 typedef int  (*fn_loud_flac_pcm16)(int, const int16_t*, int, int, int, double, double, double, int, int, bnhip_loudness*, uint8_t*, size_t, uint64_t*);
 typedef int  (*fn_flac_lpc_encode_pcm16)(int, const int16_t*, int, int, int, const double*, int, uint8_t*, size_t, uint64_t*, int);
 typedef int  (*fn_loud_flac_lpc_pcm16)(int, const int16_t*, int, int, int, double, double, double, int, int, bnhip_loudness*, uint8_t*, size_t, uint64_t*, int);
@@ -133,6 +136,7 @@ typedef struct {
     fn_flac_max_bytes flac_max_bytes; fn_flac_encode_pcm16 flac_encode_pcm16; fn_loud_flac_pcm16 loud_flac_pcm16;
     fn_flac_lpc_encode_pcm16 flac_lpc_encode_pcm16; fn_loud_flac_lpc_pcm16 loud_flac_lpc_pcm16;
     fn_png_max_bytes png_max_bytes; fn_png_encode_u8 png_encode_u8; fn_spec_png_pcm16 spec_png_pcm16;
+    fn_spec_ragged_pcm16 spec_ragged_pcm16; fn_spec_png_ragged_pcm16 spec_png_ragged_pcm16;
 } bnbind_t;
 static bnbind_t BN;
 static char bnbind_errbuf[256];
@@ -187,6 +191,7 @@ static const char* bnbind_load(const char* path) {
     BN_RESOLVE(flac_lpc_encode_pcm16, "bnhip_flac_lpc_encode_pcm16"); BN_RESOLVE(loud_flac_lpc_pcm16, "bnhip_loudness_flac_lpc_pcm16");
     BN_RESOLVE(png_max_bytes, "bnhip_png_max_bytes"); BN_RESOLVE(png_encode_u8, "bnhip_png_encode_u8");
     BN_RESOLVE(spec_png_pcm16, "bnhip_spectrogram_png_pcm16");
+    BN_RESOLVE(spec_ragged_pcm16, "bnhip_spectrogram_ragged_pcm16"); BN_RESOLVE(spec_png_ragged_pcm16, "bnhip_spectrogram_png_ragged_pcm16");
     return NULL;
 }
 static void bnbind_unload(void) {
@@ -307,6 +312,16 @@ static inline int bnbind_spec_png_pcm16(int device, const int16_t* pcm, int n_cl
                                         const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap,
                                         uint64_t* offsets) {
     return BN.spec_png_pcm16(device, pcm, n_clips, n, rate_in, rate_out, width, height, window, top_db, range_db, palette, out, out_cap, offsets);
+}
+static inline int bnbind_spec_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate_in, int rate_out, int width,
+                                           int height, const double* window, double top_db, double range_db, uint8_t* image) {
+    return BN.spec_ragged_pcm16(device, pcm, n_clips, lens, rate_in, rate_out, width, height, window, top_db, range_db, image);
+}
+static inline int bnbind_spec_png_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate_in, int rate_out, int width,
+                                               int height, const double* window, double top_db, double range_db, const uint8_t* palette,
+                                               uint8_t* out, size_t out_cap, uint64_t* offsets) {
+    return BN.spec_png_ragged_pcm16(device, pcm, n_clips, lens, rate_in, rate_out, width, height, window, top_db, range_db, palette, out, out_cap,
+                                    offsets);
 }
 static inline int bnbind_flac_max_bytes(int n_clips, int n, int seek_interval, size_t* bytes) {
     return BN.flac_max_bytes(n_clips, n, seek_interval, bytes);
@@ -1182,6 +1197,97 @@ func RenderSpectrogramPNGs(pcm []int16, nClips, sampleRate, width int, opts Spec
 		C.int(sampleRate), C.int(opts.ResampleRate), C.int(width), h, win, C.double(opts.TopDB), C.double(rangeDB),
 		(*C.uint8_t)(unsafe.Pointer(&palette[0])), (*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
 		return nil, 0, fmt.Errorf("hip: spectrogram_png failed (%d): %s", int(rc), lastError())
+	}
+	return splitStreams(buf, offsets), int(h), nil
+}
+
+// raggedPack lays a burst of clips of any lengths out as the bnhip_*_ragged_* entries take it: the samples back to back and the lengths.
+func raggedPack(clips [][]int16) (pcm []int16, lens []C.int, err error) {
+	if len(clips) == 0 {
+		return nil, nil, fmt.Errorf("hip: a ragged burst holds at least one clip")
+	}
+	total := 0
+	for _, c := range clips {
+		if len(c) == 0 {
+			return nil, nil, fmt.Errorf("hip: a ragged burst holds no empty clip")
+		}
+		total += len(c)
+	}
+	pcm = make([]int16, 0, total)
+	lens = make([]C.int, len(clips))
+	for i, c := range clips {
+		pcm = append(pcm, c...)
+		lens[i] = C.int(len(c))
+	}
+	return pcm, lens, nil
+}
+
+// specRaggedArgs resolves what both ragged renders need of the width and the options: the height, the window pointer, the range.
+func specRaggedArgs(width int, opts SpectrogramOptions) (h C.int, win *C.double, rangeDB float64, err error) {
+	var fft C.int
+	if rc := C.bnbind_spec_size(C.int(width), &h, &fft); rc != 0 {
+		return 0, nil, 0, fmt.Errorf("hip: spectrogram_size failed (%d): %s", int(rc), lastError())
+	}
+	if opts.Window != nil {
+		if len(opts.Window) != int(fft) {
+			return 0, nil, 0, fmt.Errorf("hip: spectrogram window must hold %d coefficients, got %d", int(fft), len(opts.Window))
+		}
+		win = (*C.double)(unsafe.Pointer(&opts.Window[0]))
+	}
+	rangeDB = opts.RangeDB
+	if rangeDB == 0 {
+		rangeDB = 100
+	}
+	return h, win, rangeDB, nil
+}
+
+// RenderSpectrogramsRagged is RenderSpectrograms for clips of unequal lengths (detections under extended capture) in ONE device call:
+// img is [len(clips)][height][width], image i what RenderSpectrograms gives clips[i] alone.
+func RenderSpectrogramsRagged(clips [][]int16, sampleRate, width int, opts SpectrogramOptions, device int) (img []uint8, height int, err error) {
+	pcm, lens, err := raggedPack(clips)
+	if err != nil {
+		return nil, 0, err
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	h, win, rangeDB, err := specRaggedArgs(width, opts)
+	if err != nil {
+		return nil, 0, err
+	}
+	img = make([]uint8, len(clips)*int(h)*width)
+	if rc := C.bnbind_spec_ragged_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(len(clips)), &lens[0], C.int(sampleRate),
+		C.int(opts.ResampleRate), C.int(width), h, win, C.double(opts.TopDB), C.double(rangeDB), (*C.uint8_t)(unsafe.Pointer(&img[0]))); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram_ragged failed (%d): %s", int(rc), lastError())
+	}
+	return img, int(h), nil
+}
+
+// RenderSpectrogramPNGsRagged is RenderSpectrogramPNGs for clips of unequal lengths in ONE device call: file i decodes to image i of
+// RenderSpectrogramsRagged.
+func RenderSpectrogramPNGsRagged(clips [][]int16, sampleRate, width int, opts SpectrogramOptions, palette []uint8, device int) (files [][]byte, height int, err error) {
+	if len(palette) != 768 {
+		return nil, 0, fmt.Errorf("hip: png palette must hold 256 x 3 bytes, got %d", len(palette))
+	}
+	pcm, lens, err := raggedPack(clips)
+	if err != nil {
+		return nil, 0, err
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	h, win, rangeDB, err := specRaggedArgs(width, opts)
+	if err != nil {
+		return nil, 0, err
+	}
+	var capBytes C.size_t
+	if rc := C.bnbind_png_max_bytes(C.int(len(clips)), C.int(width), h, &capBytes); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: png_max_bytes failed (%d): %s", int(rc), lastError())
+	}
+	buf := make([]byte, int(capBytes))
+	offsets := make([]C.uint64_t, len(clips)+1)
+	if rc := C.bnbind_spec_png_ragged_pcm16(C.int(device), (*C.int16_t)(unsafe.Pointer(&pcm[0])), C.int(len(clips)), &lens[0], C.int(sampleRate),
+		C.int(opts.ResampleRate), C.int(width), h, win, C.double(opts.TopDB), C.double(rangeDB), (*C.uint8_t)(unsafe.Pointer(&palette[0])),
+		(*C.uint8_t)(unsafe.Pointer(&buf[0])), capBytes, &offsets[0]); rc != 0 {
+		return nil, 0, fmt.Errorf("hip: spectrogram_png_ragged failed (%d): %s", int(rc), lastError())
 	}
 	return splitStreams(buf, offsets), int(h), nil
 }

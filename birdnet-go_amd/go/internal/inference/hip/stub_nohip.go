@@ -104,6 +104,14 @@ func RenderSpectrogramPNGs([]int16, int, int, int, SpectrogramOptions, []uint8, 
 	return nil, 0, ErrHIPUnavailable
 }
 
+func RenderSpectrogramsRagged([][]int16, int, int, SpectrogramOptions, int) ([]uint8, int, error) {
+	return nil, 0, ErrHIPUnavailable
+}
+
+func RenderSpectrogramPNGsRagged([][]int16, int, int, SpectrogramOptions, []uint8, int) ([][]byte, int, error) {
+	return nil, 0, ErrHIPUnavailable
+}
+
 type Loudness struct {
 	IntegratedLUFS float64
 	TruePeakDBTP   float64

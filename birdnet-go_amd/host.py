@@ -52,7 +52,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_loudness_ragged_workspace_size", "bnhip_loudness_ragged_normalize_pcm16", "bnhip_loudness_ragged_normalize_device",
            "bnhip_flac_ragged_max_bytes", "bnhip_flac_ragged_workspace_size", "bnhip_flac_ragged_encode_device",
            "bnhip_flac_ragged_encode_pcm16", "bnhip_loudness_flac_ragged_pcm16", "bnhip_png_max_bytes", "bnhip_png_workspace_size",
-           "bnhip_png_encode_device", "bnhip_png_encode_u8", "bnhip_spectrogram_png_pcm16"]
+           "bnhip_png_encode_device", "bnhip_png_encode_u8", "bnhip_spectrogram_png_pcm16", "bnhip_spectrogram_ragged_workspace_size",
+           "bnhip_spectrogram_ragged_pcm16", "bnhip_spectrogram_png_ragged_pcm16", "bnhip_spectrogram_ragged_device"]
 
 
 class HipError(RuntimeError):
@@ -821,6 +822,63 @@ def spectrogram_png(clips_pcm16, rate, width, palette, rate_out=0, window=None, 
                                                 float(top_db), float(range_db), pal.ctypes.data, out.ctypes.data, cap, offsets.ctypes.data))
     del keep
     return (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
+
+
+def spectrogram_ragged_workspace_size(lens, width):
+    """Bytes of device scratch spectrogram_ragged_device needs for clips of these lengths at this width (one table row per clip)."""
+    return _ragged_size_query("bnhip_spectrogram_ragged_workspace_size", lens, width, spectrogram_size(width)[0])
+
+
+def spectrogram_ragged(clips, rate, width, rate_out=0, window=None, top_db=0.0, range_db=100.0, device=0):
+    """spectrogram of a ragged burst in one device call: a list of 1-D int16 clips of any lengths -> uint8 [B, H, W], image i what
+    `spectrogram` gives clip i alone."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    height, fft_size = spectrogram_size(width)
+    keep, wp = _spectrogram_window(window, fft_size)
+    img = np.empty((lens.size, height, int(width)), np.uint8)
+    lib.bnhip_spectrogram_ragged_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_double, C.c_double, C.c_void_p]
+    _check(lib, lib.bnhip_spectrogram_ragged_pcm16(device, x.ctypes.data, lens.size, lens.ctypes.data, int(rate), int(rate_out), int(width),
+                                                   height, wp, float(top_db), float(range_db), img.ctypes.data))
+    del keep
+    return img
+
+
+def spectrogram_png_ragged(clips, rate, width, palette, rate_out=0, window=None, top_db=0.0, range_db=100.0, device=0, raw=False):
+    """spectrogram_png of a ragged burst in one device call: a list of 1-D int16 clips of any lengths -> list of B PNG streams (raw=True:
+    as png_encode), stream i decoding to image i of spectrogram_ragged."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    pal = _png_palette(palette)
+    height, fft_size = spectrogram_size(width)
+    keep, wp = _spectrogram_window(window, fft_size)
+    B = lens.size
+    cap = png_max_bytes(B, width, height)
+    out, offsets = np.empty(cap, np.uint8), np.zeros(B + 1, np.uint64)
+    lib.bnhip_spectrogram_png_ragged_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_spectrogram_png_ragged_pcm16(device, x.ctypes.data, B, lens.ctypes.data, int(rate), int(rate_out), int(width),
+                                                       height, wp, float(top_db), float(range_db), pal.ctypes.data, out.ctypes.data, cap,
+                                                       offsets.ctypes.data))
+    del keep
+    return (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
+
+
+def spectrogram_ragged_device(d_samples_ptr, f32, lens, width, height, d_image_ptr, d_workspace_ptr, workspace_bytes, window=None, top_db=0.0,
+                              range_db=100.0, device=0, hip_stream_ptr=None):
+    """Device-resident form: the packed samples (int16, or float32 with f32, at the render rate), the uint8 [n_clips, height, width]
+    image and the workspace (spectrogram_ragged_workspace_size) are device pointers, lens a host array; enqueued on the stream, not
+    synchronised."""
+    lib = load_library()
+    x = _ragged_lens(lens)
+    keep, wp = _spectrogram_window(window, 2 * (int(height) - 1))
+    lib.bnhip_spectrogram_ragged_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                                    C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_spectrogram_ragged_device(device, d_samples_ptr, 1 if f32 else 0, x.size, x.ctypes.data, int(width), int(height), wp,
+                                                    float(top_db), float(range_db), d_image_ptr, d_workspace_ptr, int(workspace_bytes),
+                                                    hip_stream_ptr))
+    del keep
 
 
 def _sigmoid_f32div(x):

@@ -6,7 +6,8 @@ GenerateFromPCM (generator.go:425-530) sees, over bnhip_spectrogram_pcm16.
   BirdProfile / BatProfile           frequency_profile.go      -> bird_profile / bat_profile
   style presets                      conf/config.go:252-255    -> palette(style), style_window(style, n)
   dynamic range presets              conf/config.go:262-264    -> DYNAMIC_RANGES
-  GenerateFromPCM                    generator.go:425          -> generate_from_pcm, generate_batch (many clips, one device call)
+  GenerateFromPCM                    generator.go:425          -> generate_from_pcm, generate_batch (many clips, one device call),
+                                                                  generate_burst (clips of any lengths)
 
 Only raw images are produced (sox's -r: no axes, no legend), mono, as 8-bit indexed PNG.  The pixel values follow the project's own
 rendering spec; they are not pinned against sox, which is not in the reference's tree.
@@ -225,6 +226,51 @@ def generate_batch(clips_pcm16, output_paths, width, sample_rate, profile=None, 
     if device_png:
         return _render_png(clips, output_paths, sample_rate, width, profile, style, dynamic_range, device)
     img, pal = _render(clips, sample_rate, width, profile, style, dynamic_range, device)
+    for i, p in enumerate(output_paths):
+        write_png(p, img[i], pal)
+    return img
+
+
+def _burst(clips):
+    """The clips as contiguous mono int16 arrays and their indices grouped by length, in the order the lengths first appear."""
+    clips = [np.ascontiguousarray(c) for c in clips]
+    for c in clips:
+        if c.dtype != np.int16 or c.ndim != 1 or c.size == 0:
+            raise ValueError("clips must be non-empty 1-D int16 arrays")
+    groups = {}
+    for i, c in enumerate(clips):
+        groups.setdefault(c.size, []).append(i)
+    return clips, groups
+
+
+def generate_burst(clips, output_paths, width, sample_rate, profile=None, style="default", dynamic_range="100", device=0,
+                   device_png=False, ragged=False):
+    """A burst of detections: a sequence of 1-D int16 clips of any lengths -> one PNG per clip at output_paths[i].  -> the uint8
+    [B, H, W] indices, in the input's order.  Clips are grouped by length, one generate_batch call per length; ragged: the whole burst
+    in one device call (bnhip_spectrogram_ragged_pcm16, or with device_png bnhip_spectrogram_png_ragged_pcm16) instead."""
+    clips, groups = _burst(clips)
+    if not clips or len(clips) != len(output_paths):
+        raise ValueError("a burst is a non-empty sequence of clips with one output path per clip")
+    for p in output_paths:
+        if not p or not os.path.isabs(p):
+            raise ValueError("output path must be absolute")
+    if not ragged:
+        img = None
+        for idx in groups.values():
+            part = generate_batch(np.stack([clips[i] for i in idx]), [output_paths[i] for i in idx], width, sample_rate, profile, style,
+                                  dynamic_range, device, device_png)
+            if img is None:
+                img = np.empty((len(clips),) + part.shape[1:], np.uint8)
+            img[idx] = part
+        return img
+    kw = _render_args(sample_rate, width, profile, style, dynamic_range)
+    if device_png:
+        streams = _host.spectrogram_png_ragged(clips, sample_rate, width, palette(style), device=device, **kw)
+        for p, s in zip(output_paths, streams):
+            with open(p, "wb") as fh:
+                fh.write(s)
+        return np.stack([read_png_indices(s) for s in streams])
+    img, pal = _host.spectrogram_ragged(clips, sample_rate, width, device=device, **kw), palette(style)
     for i, p in enumerate(output_paths):
         write_png(p, img[i], pal)
     return img

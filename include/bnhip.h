@@ -375,7 +375,7 @@ int bnhip_loudness_flac_lpc_pcm16(int device, const int16_t* pcm, int n_clips, i
                                   double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval,
                                   bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap, uint64_t* offsets, int lpc_order);
 
-/* Ragged bursts: the loudness and FLAC entries above for clips of unequal lengths in one call (a detection under
+/* Ragged bursts: the loudness, FLAC and spectrogram entries above for clips of unequal lengths in one call (a detection under
  * conf.ExtendedCaptureSettings is as long as the bird kept calling, so a burst of detections has as many lengths as clips).  A
  * ragged burst is n_clips mono int16 clips of lens[c] >= 1 samples packed back to back in one buffer: clip c starts at sample
  * lens[0] + .. + lens[c - 1] (64-bit), with no padding or alignment between clips; one rate, one seek_interval, one plan per call.
@@ -394,11 +394,19 @@ int bnhip_loudness_flac_lpc_pcm16(int device, const int16_t* pcm, int n_clips, i
  *   measure (there is no ragged measure entry).
  *   device entries: as the uniform ones; the length tables (prefix sums computed on the host) are copied into the workspace with
  *   a copy enqueued on hip_stream; nothing is allocated or synchronised.
+ *   spectrogram images: bnhip_spectrogram_ragged_pcm16, bnhip_spectrogram_png_ragged_pcm16 and bnhip_spectrogram_ragged_device are
+ *   bnhip_spectrogram_pcm16, bnhip_spectrogram_png_pcm16 and bnhip_spectrogram_device with lens in place of n: one width, height,
+ *   window, rate pair, top_db and range_db per call, image uint8 [n_clips][height][width].  Clip c's image is byte for byte what the
+ *   uniform entry gives that clip alone (its K = max(1, ceil(lens[c] / (width N))) and frame centres follow its own length; with a
+ *   rate change it is rendered from its own bnhip_resample_length(lens[c], ..) floats, which the device packs like the input), and
+ *   so is its PNG stream.  The PNG bound is bnhip_png_max_bytes(n_clips, width, height).  The device entry takes packed int16 or
+ *   float32 at the render rate; bnhip_spectrogram_ragged_workspace_size is one 24-byte row per clip, rounded up to 256 bytes:
+ *   (24 n_clips + 255) & ~255.
  * BNHIP_E_INVALID: what the uniform entries reject, lens == NULL, a lens[c] < 1, and a total length above 2^36 - 1 samples (the 36
- * bits of STREAMINFO's sample count, which also keeps every flat frame / segment / tile count inside a 31-bit grid); answered
- * before any device is touched.
- * Not offered for ragged bursts: the sub_energy output of the measure entry, mixed sample rates in one call, and spectrogram
- * images (bnhip_spectrogram_* take equally long clips). */
+ * bits of STREAMINFO's sample count, which also keeps every flat frame / segment / tile count inside a 31-bit grid; the spectrogram
+ * entries hold the resampled lengths to the same limit), a workspace that is too small or not 256-byte aligned; answered before any
+ * device is touched.
+ * Not offered for ragged bursts: the sub_energy output of the measure entry, and mixed sample rates, widths or windows in one call. */
 int bnhip_loudness_ragged_workspace_size(int n_clips, const int* lens, int rate, size_t* bytes);
 int bnhip_loudness_ragged_normalize_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate,
                                           double target_lufs, double true_peak_dbtp, double max_gain_db, int gate_fallback,
@@ -418,6 +426,15 @@ int bnhip_flac_ragged_encode_pcm16(int device, const int16_t* pcm, int n_clips, 
 int bnhip_loudness_flac_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate, double target_lufs,
                                      double true_peak_dbtp, double max_gain_db, int gate_fallback, int seek_interval,
                                      bnhip_loudness* out, uint8_t* out_bytes, size_t out_cap, uint64_t* offsets, int lpc_order);
+int bnhip_spectrogram_ragged_workspace_size(int n_clips, const int* lens, int width, int height, size_t* bytes);
+int bnhip_spectrogram_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate_in, int rate_out,
+                                   int width, int height, const double* window, double top_db, double range_db, uint8_t* image);
+int bnhip_spectrogram_png_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate_in, int rate_out,
+                                       int width, int height, const double* window, double top_db, double range_db,
+                                       const uint8_t* palette, uint8_t* out, size_t out_cap, uint64_t* offsets);
+int bnhip_spectrogram_ragged_device(int device, const void* d_samples, int f32, int n_clips, const int* lens, int width,
+                                    int height, const double* window, double top_db, double range_db, uint8_t* d_image,
+                                    void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
