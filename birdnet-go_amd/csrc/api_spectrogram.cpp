@@ -1,7 +1,8 @@
 // C ABI of the detection-clip spectrogram images (bnhip_spectrogram_size, bnhip_spectrogram_pcm16, bnhip_spectrogram_device), of
 // the render fused with the PNG encoder of api_png.cpp (bnhip_spectrogram_png_pcm16), which needs this file's window and rate tables,
 // and of their forms for a ragged burst (bnhip_spectrogram_ragged_workspace_size, bnhip_spectrogram_ragged_pcm16,
-// bnhip_spectrogram_png_ragged_pcm16, bnhip_spectrogram_ragged_device).
+// bnhip_spectrogram_png_ragged_pcm16, bnhip_spectrogram_ragged_device), the last also fed by the device FLAC decoder of flac_decode.h
+// in place of the host's PCM (bnhip_flac_spectrogram_png).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,10 +10,17 @@
 #include <numeric>
 
 #include "api_oneshot.h"
+#include "flac_decode.h"
 #include "kernels.h"
 #include "png.h"
 #include "resample.h"
 #include "spectrogram.h"
+
+namespace bnhip {
+// (api_flac_decode.cpp)
+int flacdec_read_infos(const uint8_t* streams, int n_streams, const uint64_t* offsets, std::vector<bnhip_flac_info>* infos);
+int flacdec_burst_check(int n_streams, const bnhip_flac_info* infos, const uint64_t* offsets, size_t* pcm_samples);
+}  // namespace bnhip
 
 using namespace bnhip;
 
@@ -144,6 +152,88 @@ void ragged_render_enqueue(const RenderTables& t, const DevCarve& cv, const Ragg
     if (rt) launch_resample_ragged(d_pcm, d_f32, rt->d, n_clips, lens, lens_out.data(), rt->L, rt->M, rt->T, rt->half, cv.at<void>(r.o_rtab), nullptr);
     launch_spectrogram_ragged(rt ? (const void*)d_f32 : (const void*)d_pcm, rt ? 1 : 0, n_clips, rt ? lens_out.data() : lens, width, height,
                               t.tab->d, t.tab->wsum, top_db, range_db, cv.at<uint8_t>(r.o_img), cv.at<void>(r.o_rows), nullptr);
+}
+
+// Where the packed int16 clips of a ragged render come from: the host's PCM, or a decode on the device.  reserve() adds the source's
+// own parts to the call's one block, fill() enqueues on the null stream what puts the clips at d_pcm, finish() runs after the
+// call's synchronise.
+struct RaggedSource {
+    virtual void reserve(DevCarve&) {}
+    virtual hipError_t fill(const DevCarve& cv, int16_t* d_pcm, size_t pcm_bytes) = 0;
+    virtual hipError_t finish(const DevCarve&) { return hipSuccess; }
+    virtual ~RaggedSource() {}
+};
+struct PcmSource : RaggedSource {
+    const int16_t* pcm;
+    explicit PcmSource(const int16_t* p) : pcm(p) {}
+    hipError_t fill(const DevCarve&, int16_t* d_pcm, size_t pcm_bytes) override { return hipMemcpy(d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice); }
+};
+// FLAC streams in host memory: the compressed bytes are what crosses to the device, the clips are decoded where the render reads them
+struct FlacSource : RaggedSource {
+    const uint8_t* streams;
+    int n_streams;
+    const uint64_t* offsets;
+    bnhip_flac_decode_result* result;
+    std::vector<bnhip_flac_info> infos;
+    size_t o_in = 0, o_res = 0, o_ws = 0;
+    FlacSource(const uint8_t* s, int n, const uint64_t* o, bnhip_flac_decode_result* r) : streams(s), n_streams(n), offsets(o), result(r) {}
+    void reserve(DevCarve& cv) override {
+        o_in = cv.add(offsets[n_streams]);
+        o_res = cv.add((size_t)n_streams * sizeof(bnhip_flac_decode_result));
+        o_ws = cv.add(flacdec_workspace_bytes(n_streams, infos.data(), offsets));
+    }
+    hipError_t fill(const DevCarve& cv, int16_t* d_pcm, size_t pcm_bytes) override {
+        uint8_t* d_in = cv.at<uint8_t>(o_in);
+        const size_t in_bytes = (size_t)(offsets[n_streams] - offsets[0]);
+        if (in_bytes) {
+            const hipError_t he = hipMemcpy(d_in + offsets[0], streams + offsets[0], in_bytes, hipMemcpyHostToDevice);
+            if (he != hipSuccess) return he;
+        }
+        launch_flacdec(d_in, flacdec_work(n_streams, infos.data(), offsets, cv.at<void>(o_ws)), d_pcm, pcm_bytes / 2,
+                       cv.at<bnhip_flac_decode_result>(o_res), nullptr);
+        return hipGetLastError();
+    }
+    hipError_t finish(const DevCarve& cv) override {
+        return hipMemcpy(result, cv.at<void>(o_res), (size_t)n_streams * sizeof(bnhip_flac_decode_result), hipMemcpyDeviceToHost);
+    }
+};
+
+// The ragged render fused with the PNG encode, for either source: the body of bnhip_spectrogram_png_ragged_pcm16 and
+// bnhip_flac_spectrogram_png after their own argument checks.
+int png_ragged_run(const char* what, int device, RaggedSource& src, int n_clips, const int* lens, int rate_in, int rate_out, int width, int height,
+                   const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap, uint64_t* offsets) {
+    const int N = spec_ragged_check(n_clips, lens, width, height, window, top_db, range_db);
+    if (N < 0) return N;
+    const bool resample = rate_out != 0 && rate_out != rate_in;
+    std::vector<int> lens_out;
+    int rc = png_args_check(n_clips, width, height);
+    if (!rc) rc = ragged_render_lens(n_clips, lens, resample, rate_in, rate_out, &lens_out);
+    if (!rc) rc = png_cap_check(n_clips, width, height, out_cap);
+    if (!rc) rc = use_device(device);
+    if (rc) return rc;
+    TableLock lk(g_tables.mu);
+    RenderTables t;
+    rc = render_tables(lk, device, N, window, resample, lens[0], rate_in, rate_out, &t);       // (its n_render is not used here)
+    if (rc) return rc;
+    const size_t cap = png_max_bytes(n_clips, width, height);
+    DevCarve cv;
+    const RaggedParts r = ragged_parts(cv, n_clips, lens, lens_out, width, height);
+    const size_t o_bytes = cv.add(cap), o_off = cv.add(((size_t)n_clips + 1) * 8), o_ws = cv.add(png_workspace_bytes(n_clips, width, height));
+    src.reserve(cv);
+    DevBlocks b;
+    cv.base = (char*)b.get(cv.bytes());
+    uint8_t* d_bytes = cv.at<uint8_t>(o_bytes);
+    unsigned long long* d_offsets = cv.at<unsigned long long>(o_off);
+    if (b.he == hipSuccess) b.he = src.fill(cv, cv.at<int16_t>(r.o_pcm), r.pcm_bytes);
+    if (b.he == hipSuccess) {
+        ragged_render_enqueue(t, cv, r, n_clips, lens, lens_out, width, height, top_db, range_db);
+        launch_png(cv.at<uint8_t>(r.o_img), png_work(n_clips, width, height, palette, cv.at<void>(o_ws)), d_bytes, cap, d_offsets, nullptr);
+        b.he = hipGetLastError();
+        lk.unlock();
+        if (b.he == hipSuccess) b.he = png_fetch(d_offsets, d_bytes, n_clips, offsets, out);
+        if (b.he == hipSuccess) b.he = src.finish(cv);
+    }
+    return b.he == hipSuccess ? BNHIP_OK : hip_fail(what, b);
 }
 
 }  // namespace
@@ -292,36 +382,31 @@ int bnhip_spectrogram_png_ragged_pcm16(int device, const int16_t* pcm, int n_cli
                                        size_t out_cap, uint64_t* offsets) {
     if (!pcm || !palette || !out || !offsets) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
     BN_GUARD_BEGIN
-    const int N = spec_ragged_check(n_clips, lens, width, height, window, top_db, range_db);
-    if (N < 0) return N;
-    const bool resample = rate_out != 0 && rate_out != rate_in;
-    std::vector<int> lens_out;
-    int rc = png_args_check(n_clips, width, height);
-    if (!rc) rc = ragged_render_lens(n_clips, lens, resample, rate_in, rate_out, &lens_out);
-    if (!rc) rc = png_cap_check(n_clips, width, height, out_cap);
-    if (!rc) rc = use_device(device);
+    PcmSource src(pcm);
+    return png_ragged_run("spectrogram_png_ragged_pcm16", device, src, n_clips, lens, rate_in, rate_out, width, height, window, top_db, range_db,
+                          palette, out, out_cap, offsets);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_flac_spectrogram_png(int device, const uint8_t* streams, int n_streams, const uint64_t* offsets, int rate_out, int width, int height,
+                               const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap,
+                               uint64_t* png_offsets, bnhip_flac_decode_result* result) {
+    if (!streams || !offsets || !palette || !out || !png_offsets || !result) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    FlacSource src(streams, n_streams, offsets, result);
+    int rc = flacdec_read_infos(streams, n_streams, offsets, &src.infos);
+    if (!rc) rc = flacdec_burst_check(n_streams, src.infos.data(), offsets, nullptr);
     if (rc) return rc;
-    TableLock lk(g_tables.mu);
-    RenderTables t;
-    rc = render_tables(lk, device, N, window, resample, lens[0], rate_in, rate_out, &t);       // (its n_render is not used here)
-    if (rc) return rc;
-    const size_t cap = png_max_bytes(n_clips, width, height);
-    DevCarve cv;
-    const RaggedParts r = ragged_parts(cv, n_clips, lens, lens_out, width, height);
-    const size_t o_bytes = cv.add(cap), o_off = cv.add(((size_t)n_clips + 1) * 8), o_ws = cv.add(png_workspace_bytes(n_clips, width, height));
-    DevBlocks b;
-    cv.base = (char*)b.get(cv.bytes());
-    uint8_t* d_bytes = cv.at<uint8_t>(o_bytes);
-    unsigned long long* d_offsets = cv.at<unsigned long long>(o_off);
-    if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(r.o_pcm), pcm, r.pcm_bytes, hipMemcpyHostToDevice);
-    if (b.he == hipSuccess) {
-        ragged_render_enqueue(t, cv, r, n_clips, lens, lens_out, width, height, top_db, range_db);
-        launch_png(cv.at<uint8_t>(r.o_img), png_work(n_clips, width, height, palette, cv.at<void>(o_ws)), d_bytes, cap, d_offsets, nullptr);
-        b.he = hipGetLastError();
-        lk.unlock();
-        if (b.he == hipSuccess) b.he = png_fetch(d_offsets, d_bytes, n_clips, offsets, out);
+    std::vector<int> lens((size_t)n_streams);
+    for (int c = 0; c < n_streams; c++) {
+        const bnhip_flac_info& in = src.infos[(size_t)c];
+        if (in.status != BNHIP_FLAC_OK) return set_err(BNHIP_E_INVALID, "every stream's metadata must be accepted (bnhip_flac_stream_info)");
+        if (in.rate != src.infos[0].rate) return set_err(BNHIP_E_INVALID, "every stream must have the same sample rate");
+        lens[(size_t)c] = (int)in.total_samples;
     }
-    return b.he == hipSuccess ? BNHIP_OK : hip_fail("spectrogram_png_ragged_pcm16", b);
+    if (src.infos[0].rate > 0x7FFFFFFFu) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
+    return png_ragged_run("flac_spectrogram_png", device, src, n_streams, lens.data(), (int)src.infos[0].rate, rate_out, width, height, window,
+                          top_db, range_db, palette, out, out_cap, png_offsets);
     BN_GUARD_END((void)0)
 }
 

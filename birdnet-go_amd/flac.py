@@ -5,6 +5,8 @@ save see, over bnhip_flac_encode_pcm16 and bnhip_loudness_flac_pcm16.
   EncodePCM (file, seek table)       flac/encode.go:79-175          -> encode_clips(.., seek_interval=sample_rate)
   encodeFLACNative                   birdweather/encode_native.go:28-98 -> normalize_and_encode(.., max_gain_db=DEFAULT_MAX_GAIN_DB)
 
+  (reading a saved clip back)         spectrogram/generator.go:276-424 -> stream_info, decode_clips; spectrogram.generate_from_flac
+
 Mono int16 only.  The bytes follow the project's own encoder spec: valid RFC 9639 streams, not go-flac's bytes.
 lpc_order: 0 (the default) tries CONSTANT / FIXED / VERBATIM subframes only; M in 1..8 tries LPC orders 1..M as well.
 """
@@ -57,3 +59,18 @@ def normalize_and_encode(clips, sample_rate, opts=None, max_gain_db=DEFAULT_MAX_
         for j, i in enumerate(idx):
             results[i], streams[i] = res[j], out[j]
     return results, streams
+
+
+def stream_info(stream):
+    """The metadata of one FLAC stream, read on the host: -> host.FlacInfo (rate, bits, channels, total_samples, block and frame bounds,
+    audio_offset, seek_points, and status: host.FLAC_OK, FLAC_BAD_METADATA or FLAC_UNSUPPORTED)."""
+    return _host.flac_stream_info(stream)
+
+
+def decode_clips(streams, device=0):
+    """Saved clips read back: a list of FLAC streams (mono, 16 bits, fixed block size; what encode_clips writes and what a general
+    encoder may write for mono int16) -> (clips, results) in the input's order, in one device call.  clips[i] is an int16 array, or
+    None where results[i].status is not host.FLAC_OK; results[i] is a host.FlacDecodeResult (status, frames, fail_offset).  The
+    STREAMINFO MD5 is not verified."""
+    clips, results = _host.flac_decode(streams, device=device)
+    return [c if r.status == _host.FLAC_OK else None for c, r in zip(clips, results)], results

@@ -53,7 +53,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_flac_ragged_max_bytes", "bnhip_flac_ragged_workspace_size", "bnhip_flac_ragged_encode_device",
            "bnhip_flac_ragged_encode_pcm16", "bnhip_loudness_flac_ragged_pcm16", "bnhip_png_max_bytes", "bnhip_png_workspace_size",
            "bnhip_png_encode_device", "bnhip_png_encode_u8", "bnhip_spectrogram_png_pcm16", "bnhip_spectrogram_ragged_workspace_size",
-           "bnhip_spectrogram_ragged_pcm16", "bnhip_spectrogram_png_ragged_pcm16", "bnhip_spectrogram_ragged_device"]
+           "bnhip_spectrogram_ragged_pcm16", "bnhip_spectrogram_png_ragged_pcm16", "bnhip_spectrogram_ragged_device",
+           "bnhip_flac_stream_info", "bnhip_flac_decode_workspace_size", "bnhip_flac_decode_device", "bnhip_flac_decode_pcm16",
+           "bnhip_flac_spectrogram_png"]
 
 
 class HipError(RuntimeError):
@@ -879,6 +881,104 @@ def spectrogram_ragged_device(d_samples_ptr, f32, lens, width, height, d_image_p
                                                     float(top_db), float(range_db), d_image_ptr, d_workspace_ptr, int(workspace_bytes),
                                                     hip_stream_ptr))
     del keep
+
+
+FLAC_OK, FLAC_BAD_METADATA, FLAC_UNSUPPORTED, FLAC_CORRUPT = 0, 1, 2, 3
+
+
+class FlacInfo(C.Structure):
+    """bnhip_flac_info: one stream's STREAMINFO as bnhip_flac_stream_info reads it, and its verdict (status, a FLAC_* value)."""
+    _fields_ = [("total_samples", C.c_uint64), ("audio_offset", C.c_uint64), ("rate", C.c_uint32), ("bits", C.c_uint32),
+                ("channels", C.c_uint32), ("min_block", C.c_uint32), ("max_block", C.c_uint32), ("min_frame", C.c_uint32),
+                ("max_frame", C.c_uint32), ("seek_points", C.c_uint32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FlacDecodeResult(C.Structure):
+    """bnhip_flac_decode_result: status (FLAC_*), the frames decoded, and where the chain of frames broke (0 on success)."""
+    _fields_ = [("status", C.c_int32), ("frames", C.c_int32), ("fail_offset", C.c_uint64)]
+
+
+def _flac_burst(streams):
+    """A list of bytes-like FLAC streams -> (uint8 buffer of them back to back, offsets uint64 [n + 1])."""
+    parts = [np.frombuffer(bytes(s), np.uint8) for s in streams]
+    if not parts:
+        raise HipError(E_INVALID, "a burst holds at least one stream")
+    offsets = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
+    buf = np.concatenate(parts) if int(offsets[-1]) else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(np.concatenate([buf, np.zeros(1, np.uint8)])), offsets      # (a spare byte: never an empty buffer)
+
+
+def flac_stream_info(stream):
+    """The marker and metadata blocks of one FLAC stream, read on the host (no device) -> FlacInfo."""
+    lib = load_library()
+    buf = np.frombuffer(bytes(stream) + b"\0", np.uint8)
+    info = FlacInfo()
+    lib.bnhip_flac_stream_info.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_flac_stream_info(buf.ctypes.data, buf.size - 1, C.addressof(info)))
+    return info
+
+
+def flac_decode_workspace_size(infos, offsets):
+    """Bytes of device scratch flac_decode_device needs for streams with these infos (a sequence of FlacInfo) and offsets."""
+    lib = load_library()
+    arr = (FlacInfo * len(infos))(*infos)
+    off = np.ascontiguousarray(offsets, np.uint64)
+    out = C.c_size_t(0)
+    lib.bnhip_flac_decode_workspace_size.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    _check(lib, lib.bnhip_flac_decode_workspace_size(len(infos), C.addressof(arr), off.ctypes.data, C.byref(out)))
+    return int(out.value)
+
+
+def flac_decode_device(d_streams_ptr, offsets, infos, d_pcm_ptr, pcm_cap_samples, d_result_ptr, d_workspace_ptr, workspace_bytes, device=0,
+                       hip_stream_ptr=None):
+    """Device-resident form: the streams, the int16 clips, the FlacDecodeResult [n] records and the workspace
+    (flac_decode_workspace_size) are device pointers, offsets and infos host arrays; enqueued on the stream, not synchronised."""
+    lib = load_library()
+    arr = (FlacInfo * len(infos))(*infos)
+    off = np.ascontiguousarray(offsets, np.uint64)
+    lib.bnhip_flac_decode_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_flac_decode_device(device, d_streams_ptr, len(infos), off.ctypes.data, C.addressof(arr), d_pcm_ptr,
+                                             int(pcm_cap_samples), d_result_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def flac_decode(streams, device=0):
+    """A burst of FLAC streams (mono, 16 bits, fixed block size) decoded in one device call: a list of bytes objects -> (list of int16
+    arrays, the clip of a stream whose metadata is not accepted being empty; list of FlacDecodeResult).  The samples of a stream whose
+    status is not FLAC_OK are unspecified."""
+    lib = load_library()
+    buf, offsets = _flac_burst(streams)
+    n = len(streams)
+    infos = [flac_stream_info(s) for s in streams]
+    total = sum(int(i.total_samples) for i in infos if i.status == FLAC_OK and i.total_samples <= 0x7FFFFFFF)
+    pcm = np.empty(max(total, 1), np.int16)
+    lens = np.zeros(n, np.int32)
+    res = (FlacDecodeResult * n)()
+    lib.bnhip_flac_decode_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_flac_decode_pcm16(device, buf.ctypes.data, n, offsets.ctypes.data, pcm.ctypes.data, total, lens.ctypes.data,
+                                            C.addressof(res)))
+    return ragged_unpack(pcm, lens), list(res)
+
+
+def flac_spectrogram_png(streams, width, palette, rate_out=0, window=None, top_db=0.0, range_db=100.0, device=0):
+    """flac_decode and spectrogram_png_ragged in one device call - the PCM never reaches the host: a list of FLAC streams of one sample
+    rate, every one with accepted metadata -> (list of PNG streams, list of FlacDecodeResult)."""
+    lib = load_library()
+    buf, offsets = _flac_burst(streams)
+    n = len(streams)
+    pal = _png_palette(palette)
+    height, fft_size = spectrogram_size(width)
+    keep, wp = _spectrogram_window(window, fft_size)
+    cap = png_max_bytes(n, width, height)
+    out, png_offsets = np.empty(cap, np.uint8), np.zeros(n + 1, np.uint64)
+    res = (FlacDecodeResult * n)()
+    lib.bnhip_flac_spectrogram_png.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                               C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_flac_spectrogram_png(device, buf.ctypes.data, n, offsets.ctypes.data, int(rate_out), int(width), height, wp,
+                                               float(top_db), float(range_db), pal.ctypes.data, out.ctypes.data, cap, png_offsets.ctypes.data,
+                                               C.addressof(res)))
+    del keep
+    return _flac_streams(out, png_offsets), list(res)
 
 
 def _sigmoid_f32div(x):

@@ -274,3 +274,32 @@ def generate_burst(clips, output_paths, width, sample_rate, profile=None, style=
     for i, p in enumerate(output_paths):
         write_png(p, img[i], pal)
     return img
+
+
+def generate_from_flac(streams, output_paths, width, profile=None, style="default", dynamic_range="100", device=0):
+    """GenerateFromFile (generator.go:276-424) for clips saved as FLAC: a sequence of FLAC streams -> one PNG per stream at
+    output_paths[i], the counterpart of generate_burst(.., device_png=True, ragged=True) that starts from the saved file.  The streams
+    are grouped by sample rate, one device call per rate (bnhip_flac_spectrogram_png: decode, render and PNG-encode, the PCM never
+    reaches the host); the files are the device's PNG streams.  -> the streams' statuses (host.FLAC_*), in the input's order; nothing is
+    written for a stream whose status is not host.FLAC_OK."""
+    streams = [bytes(s) for s in streams]
+    if not streams or len(streams) != len(output_paths):
+        raise ValueError("a burst is a non-empty sequence of streams with one output path per stream")
+    for p in output_paths:
+        if not p or not os.path.isabs(p):
+            raise ValueError("output path must be absolute")
+    infos = [_host.flac_stream_info(s) for s in streams]
+    status = [int(i.status) for i in infos]
+    groups = {}
+    for i, info in enumerate(infos):
+        if info.status == _host.FLAC_OK:
+            groups.setdefault(int(info.rate), []).append(i)
+    for rate, idx in groups.items():
+        kw = _render_args(rate, width, profile, style, dynamic_range)
+        pngs, results = _host.flac_spectrogram_png([streams[i] for i in idx], width, palette(style), device=device, **kw)
+        for i, png, res in zip(idx, pngs, results):
+            status[i] = int(res.status)
+            if res.status == _host.FLAC_OK:
+                with open(output_paths[i], "wb") as fh:
+                    fh.write(png)
+    return status

@@ -436,6 +436,62 @@ int bnhip_spectrogram_ragged_device(int device, const void* d_samples, int f32, 
                                     int height, const double* window, double top_db, double range_db, uint8_t* d_image,
                                     void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
+/* FLAC decode: the read side of a saved detection clip - what the reference's pre-renderer and on-demand spectrogram requests start
+ * from (GenerateFromFile, internal/spectrogram/generator.go:276-424, on a clip saved under clipenc.NativeFLAC) - for a burst of
+ * streams in one call.  A burst is n_streams RFC 9639 streams back to back with host offsets[n_streams + 1], the shape
+ * bnhip_flac_*_encode_* writes.  Decoded: mono, 16 bits, fixed block size 16..16384; CONSTANT, VERBATIM, FIXED 0..4 and LPC 1..32
+ * subframes (precision 1..15, shift 0..15), wasted bits, both residual coding methods, escaped partitions, partition orders 0..15,
+ * every block-size and sample-rate code, coded frame numbers of up to seven bytes.  Reported per stream as BNHIP_FLAC_UNSUPPORTED,
+ * never guessed: more than one channel, a depth other than 16 bits, a variable-block-size stream, a STREAMINFO sample count of 0
+ * (unknown) or above 2^31 - 1, min_block != max_block with more than one frame, a block size above 16384, a sample rate of 0, and a
+ * stream with more than F + 64 false frame headers (F its frame count; only an adversarial stream has them).  The STREAMINFO MD5 is
+ * ignored: it is NOT verified.  SEEKTABLE and every other metadata block are skipped and not trusted; a frame is accepted by its
+ * CRC-8 and CRC-16, its number and its place: frame j starts exactly where frame j - 1 ended, frame 0 at audio_offset, and the last
+ * frame ends at the stream's end.  A frame longer than the VERBATIM bound of its block size (2 bs + 32 bytes) is not a frame.
+ *   status: BNHIP_FLAC_OK; BNHIP_FLAC_BAD_METADATA (no marker, STREAMINFO not first, repeated or not 34 bytes, a truncated block,
+ *   block type 127, block bounds below 16 or inverted); BNHIP_FLAC_UNSUPPORTED (the list above); BNHIP_FLAC_CORRUPT (set by the
+ *   device only: the chain of frames broke, or a sample does not fit 16 bits).
+ *   stream_info:  the marker and the metadata blocks of one stream, on the host, every read bounded by n_bytes.  The return value is
+ *                 an argument error only (BNHIP_E_INVALID for NULL); the stream's verdict is out->status.  audio_offset is where the
+ *                 first frame header must be; seek_points the SEEKTABLE's point count.
+ *   output:       the ragged packing of "Ragged bursts": int16 clips back to back, lens[c] = total_samples for a stream whose
+ *                 status is OK and 0 otherwise (such a stream occupies nothing and no kernel touches it).  result[c] = {status,
+ *                 frames decoded, fail_offset}: fail_offset is the byte offset from the stream's start of the first position where
+ *                 the chain could not continue (for a sample outside 16 bits: that frame's start), 0 on success.  The samples of a
+ *                 stream that is not OK are unspecified.
+ *   decode_device: d_streams, d_pcm, d_result and d_workspace are device memory, d_workspace at least
+ *                 bnhip_flac_decode_workspace_size bytes and 256-byte aligned; infos and offsets are host arrays (infos as
+ *                 bnhip_flac_stream_info filled them), copied into the workspace with a copy enqueued on hip_stream; nothing is
+ *                 allocated or synchronised.
+ *   decode_pcm16: host memory in and out: it reads the metadata itself and fills lens; one device allocation, one H2D copy of the
+ *                 streams, the kernels, a D2H copy of the results and of exactly sum(lens) samples.
+ *   bnhip_flac_spectrogram_png: decode, then bnhip_spectrogram_png_ragged_pcm16 (with its resampler) in one call: the PCM never
+ *                 reaches the host, rate_in is the streams' rate.  Every stream's metadata must be OK and all rates equal, else
+ *                 BNHIP_E_INVALID; a stream that comes back CORRUPT still has a well-formed PNG of unspecified content.
+ * BNHIP_E_INVALID: NULL / empty arguments, n_streams outside 1..65535, offsets that do not ascend, a burst above 2^40 bytes or 2^31 - 1
+ * candidate slots (the sum of 2 F + 64), infos marked OK that stream_info would not accept, pcm_cap_samples or out_cap too small, a
+ * workspace that is too small or misaligned, and what the render entries reject; answered before any device is touched. */
+enum { BNHIP_FLAC_OK = 0, BNHIP_FLAC_BAD_METADATA = 1, BNHIP_FLAC_UNSUPPORTED = 2, BNHIP_FLAC_CORRUPT = 3 };
+typedef struct bnhip_flac_info {
+    uint64_t total_samples, audio_offset;
+    uint32_t rate, bits, channels, min_block, max_block, min_frame, max_frame, seek_points;
+    int32_t status, reserved;
+} bnhip_flac_info;
+typedef struct bnhip_flac_decode_result {
+    int32_t status, frames;
+    uint64_t fail_offset;
+} bnhip_flac_decode_result;
+int bnhip_flac_stream_info(const uint8_t* stream, size_t n_bytes, bnhip_flac_info* out);
+int bnhip_flac_decode_workspace_size(int n_streams, const bnhip_flac_info* infos, const uint64_t* offsets, size_t* bytes);
+int bnhip_flac_decode_device(int device, const uint8_t* d_streams, int n_streams, const uint64_t* offsets, const bnhip_flac_info* infos,
+                             int16_t* d_pcm, size_t pcm_cap_samples, bnhip_flac_decode_result* d_result, void* d_workspace,
+                             size_t workspace_bytes, void* hip_stream);
+int bnhip_flac_decode_pcm16(int device, const uint8_t* streams, int n_streams, const uint64_t* offsets, int16_t* pcm,
+                            size_t pcm_cap_samples, int* lens, bnhip_flac_decode_result* result);
+int bnhip_flac_spectrogram_png(int device, const uint8_t* streams, int n_streams, const uint64_t* offsets, int rate_out, int width,
+                               int height, const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out,
+                               size_t out_cap, uint64_t* png_offsets, bnhip_flac_decode_result* result);
+
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
  * pass through (NewResampler returns nil, :58-60); a too-small destination is an error before any work (:137-144).
