@@ -1,9 +1,9 @@
 // Register FFT building blocks.
 // fft_regs<P>: radix-2 DIT on P = 2 / 4 / 8 / 16 complex values, outputs in natural order (the four-step STFT of stft.hip, the closing
-// radix-2 / radix-4 pass of spectrogram.hip).
+// radix-2 / radix-4 pass of fft_passes.h).
 // fft_r8_dft8: 8-point DFT on complex doubles in registers (decimation in frequency, three radix-2 stages with the W8 constants folded
 // in).  Outputs land in bit-reversed slots: slot s holds y[kFftR8Slot[s]].  Shared by the ultrasonic power kernel
-// (post.hip) and the spectrogram image kernel (spectrogram.hip).
+// (post.hip) and the in-LDS passes of the spectrogram and denoise kernels (fft_passes.h).
 #pragma once
 
 namespace bnhip {

@@ -11,9 +11,7 @@
 //      float32, and goes to LDS as doubles (frames overlap: at "lg" with a 15 s clip the hop is 351 against N = 1024);
 //   2. each frame is windowed (the caller's table; the kernel computes no window) and packed into N/2 complex points
 //      z[i] = x[2i] w[2i] + i x[2i+1] w[2i+1];
-//   3. the F packed frames are transformed together, in place, by radix-8 decimation-in-frequency passes (fft_r8_dft8, one
-//      butterfly per thread and step, the block's threads spread over all frames of the round) closed by one radix-2 / radix-4 pass
-//      (fft_regs) when N/2 is not a power of 8 - the pass structure of k_us_frame_power8 with the length a parameter.  Z[k] ends
+//   3. the F packed frames are transformed together, in place, by the passes of fft_passes.h (shared with denoise.hip).  Z[k] ends
 //      up at the mixed-radix digit-reversed index;
 //   4. thread b recovers X[b] = E[b] + W_N^b O[b] from Z[b] and conj(Z[N/2 - b]), adds the K frame powers of a column in frame
 //      order (a column whose K frames span several rounds carries its sum in LDS) and writes the level index into the block's
@@ -33,12 +31,11 @@
 #include <cmath>
 #include <type_traits>
 
-#include "fft_r8.h"
+#include "fft_passes.h"
 #include "kernels.h"
 
 namespace bnhip {
 
-#define SPEC_PHYS(i) ((i) + ((i) >> 3))      // one pad per 8 doubles, as US8_PHYS: the last radix-8 pass walks with stride 8
 constexpr int SPEC_THREADS = 256;
 constexpr int SPEC_FMAX = 64;                // frames per round at most (the per-frame offset table's size)
 
@@ -48,32 +45,10 @@ struct SpecParams {
     const double* window;      // [N]
     uint8_t* image;
     int n, W, H, N, K, T, F, span_cap;
-    int log2n2, npass, lg[4];  // N/2 = 2^log2n2 = product of the passes' radices 2^lg[i]
+    FftPasses fp;              // the passes of N/2 complex points
     double pscale, top_db, range_db;
     const SpecClip* clips;     // ragged: one row per clip, in place of n, K, F and span_cap above; NULL: the uniform arithmetic
 };
-
-// where Z[k] lies after the passes: digit i of k (radix 2^lg[i], least significant first) becomes the digit of weight N/2 / (r_0 .. r_i)
-__device__ __forceinline__ int spec_pos(const SpecParams& p, int k) {
-    int pos = 0, rem = p.log2n2;
-    for (int i = 0; i < p.npass; i++) {
-        rem -= p.lg[i];
-        pos |= (k & ((1 << p.lg[i]) - 1)) << rem;
-        k >>= p.lg[i];
-    }
-    return pos;
-}
-
-// closing pass (span 1: no twiddles): R consecutive points, natural-order outputs
-template <int R>
-__device__ __forceinline__ void spec_pass_small(double* zr, double* zi, int base) {
-    double re[R], im[R];
-#pragma unroll
-    for (int m = 0; m < R; m++) { const int i = SPEC_PHYS(base + m); re[m] = zr[i]; im[m] = zi[i]; }
-    fft_regs<R, double>(re, im);
-#pragma unroll
-    for (int m = 0; m < R; m++) { const int i = SPEC_PHYS(base + m); zr[i] = re[m]; zi[i] = im[m]; }
-}
 
 template <typename S, bool RAGGED>
 __global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
@@ -116,8 +91,8 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
         }
         __syncthreads();
         // ---- 2. window and pack
-        for (int idx = tid; idx < (nf << p.log2n2); idx += SPEC_THREADS) {
-            const int f = idx >> p.log2n2, i = idx & (N2 - 1), o = foff[f] + 2 * i;
+        for (int idx = tid; idx < (nf << p.fp.log2n2); idx += SPEC_THREADS) {
+            const int f = idx >> p.fp.log2n2, i = idx & (N2 - 1), o = foff[f] + 2 * i;
             const double2 w = win2[i];
             double* zr = work + (size_t)f * 2 * FS;
             zr[SPEC_PHYS(i)] = (o < len ? span[o] : 0.0) * w.x;
@@ -125,47 +100,13 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrogram(SpecParams p) {
         }
         __syncthreads();
         // ---- 3. in-place DIF passes over all frames of the round
-        int lgL = p.log2n2;                                          // the pass splits blocks of 2^lgL points
-        for (int ps = 0; ps < p.npass; ps++) {
-            const int lr = p.lg[ps], sp = 1 << (lgL - lr);           // radix 2^lr, butterfly stride sp
-            const int per = p.log2n2 - lr;                           // log2 butterflies per frame
-            for (int u = tid; u < (nf << per); u += SPEC_THREADS) {
-                const int f = u >> per, t = u & ((1 << per) - 1);
-                const int j = t & (sp - 1), base = ((t - j) << lr) + j;
-                double* zr = work + (size_t)f * 2 * FS;
-                double* zi = zr + FS;
-                if (lr == 3) {
-                    double re[8], im[8];
-#pragma unroll
-                    for (int m = 0; m < 8; m++) { const int i = SPEC_PHYS(base + m * sp); re[m] = zr[i]; im[m] = zi[i]; }
-                    fft_r8_dft8(re, im);
-                    const int tstep = j << (p.log2n2 + 1 - lgL);     // W_L^(j q) = W_N^(q * tstep)
-#pragma unroll
-                    for (int sl = 0; sl < 8; sl++) {
-                        const int q = kFftR8Slot[sl];
-                        double yr = re[sl], yi = im[sl];
-                        if (q != 0 && sp > 1) {
-                            const int e = q * tstep;                 // < 7 N / 8
-                            double2 w = p.tw[e & (N2 - 1)];
-                            if (e >= N2) { w.x = -w.x; w.y = -w.y; }
-                            const double tr = yr * w.x - yi * w.y, ti = yr * w.y + yi * w.x;
-                            yr = tr; yi = ti;
-                        }
-                        const int i = SPEC_PHYS(base + q * sp);
-                        zr[i] = yr; zi[i] = yi;
-                    }
-                } else if (lr == 2) spec_pass_small<4>(zr, zi, base);
-                else spec_pass_small<2>(zr, zi, base);
-            }
-            __syncthreads();
-            lgL -= lr;
-        }
+        fft_passes_run<SPEC_THREADS>(p.fp, p.tw, work, nf, tid);
         // ---- 4. spectrum of the real frames, power sums, level indices
         const bool first = k0 == 0, last = k0 + Kr == K;
         for (int lc = 0; lc < Cr; lc++)
             for (int b = tid; b < H; b += SPEC_THREADS) {
                 double sum = first ? 0.0 : acc[b];
-                const int ia = SPEC_PHYS(spec_pos(p, b & (N2 - 1))), ib = SPEC_PHYS(spec_pos(p, (N2 - b) & (N2 - 1)));
+                const int ia = SPEC_PHYS(fft_pos(p.fp, b & (N2 - 1))), ib = SPEC_PHYS(fft_pos(p.fp, (N2 - b) & (N2 - 1)));
                 const double2 w = p.tw[b & (N2 - 1)];                 // W_N^b (unused at b = N/2)
                 for (int kk = 0; kk < Kr; kk++) {
                     const double* zr = work + (size_t)(lc * Kr + kk) * 2 * FS;
@@ -251,8 +192,7 @@ static SpecParams spec_params(const void* samples, int W, int H, const double* d
     p.window = d_table + p.N;
     p.image = image;
     p.W = W; p.H = H;
-    while ((2 << p.log2n2) < p.N) p.log2n2++;
-    for (int rem = p.log2n2; rem > 0;) { const int lr = rem >= 3 ? 3 : rem; p.lg[p.npass++] = lr; rem -= lr; }
+    p.fp = fft_passes_plan(p.N);
     p.pscale = (2.0 / wsum) * (2.0 / wsum);
     p.top_db = top_db; p.range_db = range_db;
     return p;

@@ -55,7 +55,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_png_encode_device", "bnhip_png_encode_u8", "bnhip_spectrogram_png_pcm16", "bnhip_spectrogram_ragged_workspace_size",
            "bnhip_spectrogram_ragged_pcm16", "bnhip_spectrogram_png_ragged_pcm16", "bnhip_spectrogram_ragged_device",
            "bnhip_flac_stream_info", "bnhip_flac_decode_workspace_size", "bnhip_flac_decode_device", "bnhip_flac_decode_pcm16",
-           "bnhip_flac_spectrogram_png"]
+           "bnhip_flac_spectrogram_png", "bnhip_denoise_workspace_size", "bnhip_denoise_device", "bnhip_denoise_pcm16",
+           "bnhip_process_pcm16"]
 
 
 class HipError(RuntimeError):
@@ -542,6 +543,50 @@ def loudness_normalize_device(d_pcm_ptr, n_clips, n, rate, d_out_ptr, d_workspac
     _check(lib, lib.bnhip_loudness_normalize_device(device, d_pcm_ptr, int(n_clips), int(n), int(rate), float(target_lufs),
                                                     float(true_peak_dbtp), float(max_gain_db), 1 if gate_fallback else 0, d_out_pcm_ptr,
                                                     d_out_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def denoise(clips_pcm16, frame, nr_db, nf_db, channels=1, device=0):
+    """Spectral noise reduction of a batch of equally long mono clips in one device call (the afftdn stage of
+    ffmpeg/process.go:212-251): int16 [B, n] (or [n]) -> int16 [B, n].  frame: a power of two in 64..4096; nr_db in [0, 97];
+    nf_db in [-80, -20].  Spec: DESIGN.md §9 "Denoise"."""
+    lib = load_library()
+    x = _mono_pcm16_clips("denoise", clips_pcm16, channels)
+    y = np.empty_like(x)
+    lib.bnhip_denoise_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
+    _check(lib, lib.bnhip_denoise_pcm16(device, x.ctypes.data, x.shape[0], x.shape[1], int(frame), float(nr_db), float(nf_db), y.ctypes.data))
+    return y
+
+
+def denoise_workspace_size(n_clips, n, frame):
+    """Bytes of device scratch denoise_device asks for."""
+    return _size_query("bnhip_denoise_workspace_size", n_clips, n, frame)
+
+
+def denoise_device(d_pcm_ptr, n_clips, n, frame, nr_db, nf_db, d_out_pcm_ptr, d_workspace_ptr, workspace_bytes, device=0, hip_stream_ptr=None):
+    """Device-resident form: the clips, the output clips (distinct) and the workspace are device pointers; enqueued on the stream,
+    not synchronised."""
+    lib = load_library()
+    lib.bnhip_denoise_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_denoise_device(device, d_pcm_ptr, int(n_clips), int(n), int(frame), float(nr_db), float(nf_db), d_out_pcm_ptr,
+                                         d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def process(clips_pcm16, rate, frame=0, nr_db=0.0, nf_db=-40.0, normalize=False, target_lufs=-23.0, true_peak_dbtp=-2.0, gain_db=0.0,
+            channels=1, device=0):
+    """The processed-audio chain denoise -> normalise -> gain (BuildProcessingFilterChain, ffmpeg/process.go:212-251) in one call,
+    the clips staying on the device between the stages: int16 [B, n] -> (int16 [B, n], list of B Loudness or None without
+    normalize).  frame 0: no denoise."""
+    lib = load_library()
+    x = _mono_pcm16_clips("process", clips_pcm16, channels)
+    y = np.empty_like(x)
+    res = (Loudness * x.shape[0])() if normalize else None
+    lib.bnhip_process_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_process_pcm16(device, x.ctypes.data, x.shape[0], x.shape[1], int(rate), int(frame), float(nr_db), float(nf_db),
+                                        1 if normalize else 0, float(target_lufs), float(true_peak_dbtp), float(gain_db), y.ctypes.data,
+                                        C.addressof(res) if normalize else None))
+    return y, (list(res) if normalize else None)
 
 
 def flac_max_bytes(n_clips, n, seek_interval=0):

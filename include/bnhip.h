@@ -492,6 +492,46 @@ int bnhip_flac_spectrogram_png(int device, const uint8_t* streams, int n_streams
                                int height, const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out,
                                size_t out_cap, uint64_t* png_offsets, bnhip_flac_decode_result* result);
 
+/* Processed audio: the review UI's "re-listen with noise reduction / normalisation / gain" (ProcessAudioByID and
+ * ProcessedSpectrogramByID, internal/api/v2/media/media.go:1200-1447), whose filter chain
+ * internal/audiocore/ffmpeg/process.go:164-251 builds for an FFmpeg child process per clip in the fixed order
+ * denoise (afftdn=nr=..:nf=..) -> normalise (loudnorm I=-23 TP=-2) -> gain (volume=..dB), for a batch of mono int16 clips of one
+ * length in one call.  FFmpeg is not in the reference tree, so afftdn's arithmetic cannot be restated: the denoiser's samples
+ * follow this project's own spec (DESIGN.md §9 "Denoise", restated by tests/dnref.py); the reference's two parameters, their
+ * ranges, the presets light (6, -30) / medium (12, -40) / heavy (20, -50), the chain order and the validation rules are kept.
+ *   denoise: frames of `frame` samples (a power of two in 64..4096) at hop frame / 4, frame m starting at (m - 3) frame / 4,
+ *     zeros outside the clip; periodic Hann window w; X = real FFT of w x / 32768; P = |X|^2, smoothed within the frame as
+ *     ((P[k-1] + P[k+1]) + 2 P[k]) / 4 with mirrored edges; white noise at nf_db re full scale, Nz = 10^(nf_db / 10) 3 frame / 8;
+ *     g[k] = max(10^(-nr_db / 20), 1 - Nz / P[k]) (the floor alone where P = 0); y = inverse FFT of g X; output = 32768 * 2/3 * the
+ *     sum of w y over the four frames that cover a sample, in frame order, rounded half away from zero and saturated to int16.
+ *     All in fp64; no frame depends on another, and a clip's bytes do not depend on the batch it is in.
+ *   workspace_size / device: d_pcm, d_out_pcm and d_workspace are device memory, d_workspace at least
+ *     bnhip_denoise_workspace_size bytes and 256-byte aligned (the kernel keeps its frames on chip: the size is a token
+ *     256 bytes, kept so that the entry has the form of the other device entries); d_out_pcm must not be d_pcm; enqueued on
+ *     hip_stream (NULL = default stream), not synchronised.
+ *   pcm16: host memory in and out: one H2D copy, the kernel, one D2H copy.
+ *   bnhip_process_pcm16: the chain with the clips staying on the device - one H2D copy, the active stages, one D2H copy of the
+ *     clips (and of the records when normalising).  frame 0 = no denoise; normalize 0 = no normalisation; gain_db 0 = no gain; a
+ *     call with no stage active is BNHIP_E_INVALID (the reference hands such a request to the unprocessed endpoint instead,
+ *     media.go:1338-1341: there is nothing to process).  The stages are
+ *     bnhip_denoise_pcm16, then bnhip_loudness_normalize_pcm16(target_lufs, true_peak_dbtp, max_gain_db +inf, gate_fallback 0),
+ *     then the saturating int16 gain at pow(10, gain_db / 20); the output is byte for byte what those give called one after
+ *     another.  out (nullable when normalize is 0) receives the normalisation's records.  Divergence: each stage hands int16 to
+ *     the next, where FFmpeg's chain stays in float until its output.
+ * BNHIP_E_INVALID: NULL arguments, n < 1, n_clips outside 1..65535, a frame that is not a power of two in 64..4096, nr_db not
+ * finite or outside [0, 97], nf_db not finite or outside [-80, -20], d_out_pcm == d_pcm, a gain_db that is not finite or outside
+ * +-60 (IsValidGainDB, process.go:198-203), a workspace that is too small or misaligned, and what
+ * bnhip_loudness_normalize_pcm16 rejects when normalising.  Mono int16 only: the bindings answer BNHIP_E_UNSUPPORTED for anything
+ * else.  Argument errors are answered before any device is touched. */
+int bnhip_denoise_workspace_size(int n_clips, int n, int frame, size_t* bytes);
+int bnhip_denoise_device(int device, const int16_t* d_pcm, int n_clips, int n, int frame, double nr_db, double nf_db,
+                         int16_t* d_out_pcm, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+int bnhip_denoise_pcm16(int device, const int16_t* pcm, int n_clips, int n, int frame, double nr_db, double nf_db,
+                        int16_t* out_pcm);
+int bnhip_process_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, int frame, double nr_db, double nf_db,
+                        int normalize, double target_lufs, double true_peak_dbtp, double gain_db, int16_t* out_pcm,
+                        bnhip_loudness* out);
+
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
  * pass through (NewResampler returns nil, :58-60); a too-small destination is an error before any work (:137-144).
