@@ -2,7 +2,8 @@
 // the render fused with the PNG encoder of api_png.cpp (bnhip_spectrogram_png_pcm16), which needs this file's window and rate tables,
 // and of their forms for a ragged burst (bnhip_spectrogram_ragged_workspace_size, bnhip_spectrogram_ragged_pcm16,
 // bnhip_spectrogram_png_ragged_pcm16, bnhip_spectrogram_ragged_device), the last also fed by the device FLAC decoder of flac_decode.h
-// in place of the host's PCM (bnhip_flac_spectrogram_png).
+// in place of the host's PCM (bnhip_flac_spectrogram_png), or by the processed-audio chain of process_chain.h behind it
+// (bnhip_process_spectrogram_png_ragged_pcm16).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,6 +14,7 @@
 #include "flac_decode.h"
 #include "kernels.h"
 #include "png.h"
+#include "process_chain.h"
 #include "resample.h"
 #include "spectrogram.h"
 
@@ -198,7 +200,39 @@ struct FlacSource : RaggedSource {
     }
 };
 
-// The ragged render fused with the PNG encode, for either source: the body of bnhip_spectrogram_png_ragged_pcm16 and
+// The host's PCM through the chain denoise -> normalise -> gain: the unprocessed clips are what crosses to the device, the
+// processed ones are written where the render reads them and reach the host only if the caller asks for them
+struct ProcessSource : RaggedSource {
+    const int16_t* pcm;
+    int device;
+    ChainClips clips;
+    ChainArgs args;
+    bnhip_loudness* loud;
+    int16_t* out_pcm;
+    ChainParts parts;
+    const int16_t* d_final = nullptr;
+    int rc = 0;                              // the chain's own refusal, with its text: what the entry answers instead of a HIP error
+    std::string err;
+    ProcessSource(const int16_t* p, int dev, const ChainClips& c, const ChainArgs& a, bnhip_loudness* l, int16_t* o)
+        : pcm(p), device(dev), clips(c), args(a), loud(l), out_pcm(o) {}
+    void reserve(DevCarve& cv) override { parts = chain_reserve(cv, clips, args); }
+    hipError_t fill(const DevCarve& cv, int16_t* d_pcm, size_t pcm_bytes) override {
+        const hipError_t he = hipMemcpy(chain_input(cv, parts, args, d_pcm), pcm, pcm_bytes, hipMemcpyHostToDevice);
+        if (he != hipSuccess) return he;
+        d_final = d_pcm;
+        rc = chain_enqueue("process_spectrogram_png_ragged_pcm16", device, cv, parts, clips, args, d_pcm);
+        if (rc) { err = bnhip_last_error(); hipDeviceSynchronize(); return hipErrorUnknown; }
+        return hipSuccess;
+    }
+    hipError_t finish(const DevCarve& cv) override {
+        hipError_t he = hipSuccess;
+        if (args.normalize) he = hipMemcpy(loud, cv.at<void>(parts.o_res), parts.res_bytes, hipMemcpyDeviceToHost);
+        if (he == hipSuccess && out_pcm) he = hipMemcpy(out_pcm, d_final, parts.pcm_bytes, hipMemcpyDeviceToHost);
+        return he;
+    }
+};
+
+// The ragged render fused with the PNG encode, for any source: the body of bnhip_spectrogram_png_ragged_pcm16 and
 // bnhip_flac_spectrogram_png after their own argument checks.
 int png_ragged_run(const char* what, int device, RaggedSource& src, int n_clips, const int* lens, int rate_in, int rate_out, int width, int height,
                    const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap, uint64_t* offsets) {
@@ -407,6 +441,28 @@ int bnhip_flac_spectrogram_png(int device, const uint8_t* streams, int n_streams
     if (src.infos[0].rate > 0x7FFFFFFFu) return set_err(BNHIP_E_INVALID, "sample rates must be positive");
     return png_ragged_run("flac_spectrogram_png", device, src, n_streams, lens.data(), (int)src.infos[0].rate, rate_out, width, height, window,
                           top_db, range_db, palette, out, out_cap, png_offsets);
+    BN_GUARD_END((void)0)
+}
+
+// bnhip_process_ragged_pcm16, then bnhip_spectrogram_png_ragged_pcm16 (with its resampler) in one call: the counterpart of
+// ProcessedSpectrogramByID (internal/api/v2/media/media.go:1321), whose FFmpeg child (ffmpeg/process.go:212-251) feeds the
+// spectrogram generator.  One device block, one synchronising fetch.
+int bnhip_process_spectrogram_png_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate, int frame, double nr_db,
+                                               double nf_db, int normalize, double target_lufs, double true_peak_dbtp, double gain_db,
+                                               int rate_out, int width, int height, const double* window, double top_db, double range_db,
+                                               const uint8_t* palette, uint8_t* out, size_t out_cap, uint64_t* png_offsets,
+                                               bnhip_loudness* loud, int16_t* out_pcm) {
+    if (!pcm || !lens || !palette || !out || !png_offsets || (normalize && !loud)) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    BN_GUARD_BEGIN
+    ChainClips c;
+    c.n_clips = n_clips; c.lens = lens;
+    const ChainArgs a{rate, frame, nr_db, nf_db, normalize, target_lufs, true_peak_dbtp, gain_db};
+    int rc = chain_check(c, a);
+    if (rc) return rc;
+    ProcessSource src(pcm, device, c, a, loud, out_pcm);
+    rc = png_ragged_run("process_spectrogram_png_ragged_pcm16", device, src, n_clips, lens, rate, rate_out, width, height, window, top_db,
+                        range_db, palette, out, out_cap, png_offsets);
+    return src.rc ? set_err(src.rc, src.err) : rc;
     BN_GUARD_END((void)0)
 }
 

@@ -23,6 +23,17 @@
 //      rounds race and there are no atomics.  The sum of a sample is ((f_u + f_u+1) + f_u+2) + f_u+3 whatever T and F are, so a
 //      clip's bytes depend neither on the batch it is in nor on the plan.
 // Hops outside the tile (other blocks own them) are not summed; no load leaves [0, n) of the block's clip.
+//
+// Bursts (ragged.h).  The kernel is stated once: a NULL tile table means the uniform arithmetic.  A uniform batch is a
+// dim3(tiles, n_clips) grid: block (x, y) owns tile x of clip y, which starts at y n.  A ragged burst packs clips of lengths
+// len[c] >= 1 back to back and is a flat grid of tile0[n_clips] blocks, tile0 the prefix table of the clips' tile counts
+// ceil(hops_c / T), hops_c = (len_c - 1) / h + 1 >= 1: block b finds its clip by ragged_clip(tile0, n_clips, b) (a search over a
+// table that stays in L2, no LDS), owns tile b - tile0[clip] of it, and reads and writes [start[clip], start[clip] + len[clip])
+// only - step 1 zero-fills what lies outside the clip, step 7 writes gi < n.  Nothing else of the seven steps knows which form it
+// runs in, so a clip's bytes are those of the uniform call on that clip alone.  A clip may start at an odd offset: every int16
+// access to HBM is a scalar one.
+// The flat grid stays inside 31 bits: h >= 16 and T >= 8, so a clip has at most len_c / 128 + 2 tiles, and with the limits of
+// ragged_lens_check (at most 65535 clips, a total below 2^36) a burst has at most 2^36 / 128 + 2 * 65535 < 2^29 + 2^17 tiles.
 #include "denoise.h"
 
 #include <hip/hip_runtime.h>
@@ -33,6 +44,7 @@
 #include "fft_passes.h"
 #include "kernels.h"
 #include "pcmgain.h"
+#include "ragged.h"
 #include "spectrogram.h"
 
 namespace bnhip {
@@ -46,7 +58,9 @@ struct DnParams {
     int16_t* out;
     const double2* tw;         // [N/2] (cos, -sin)(2 pi j / N)
     const double* window;      // [N]
-    int n, N, T, F;
+    ClipGeom g;                // the samples: n_clips clips of g.n, or start[n_clips + 1]
+    const long long* tile0;    // [n_clips + 1] prefix of the clips' tile counts on a flat grid; NULL: block (tile, clip)
+    int N, T, F;
     FftPasses fp;
     double nz, gmin;           // 10^(nf_db / 10) 3N/8, 10^(-nr_db / 20)
 };
@@ -70,11 +84,14 @@ __global__ __launch_bounds__(DN_THREADS) void k_denoise(DnParams p) {
     double* xs = work + (size_t)F * 2 * FS;                      // [F][re | im][XS]
     double* carry = xs + (size_t)F * 2 * XS;                     // [3][h] partial sums of the hops a round leaves open
     int16_t* span = reinterpret_cast<int16_t*>(carry + 3 * h);   // [(F + 3) h]
-    const int tid = threadIdx.x, clip = blockIdx.y, n = p.n;
+    const int tid = threadIdx.x;
+    const int clip = p.tile0 ? ragged_clip(p.tile0, p.g.n_clips, blockIdx.x) : (int)blockIdx.y;
+    const int tile = p.tile0 ? (int)(blockIdx.x - p.tile0[clip]) : (int)blockIdx.x;
+    const int n = clip_len(p.g, clip);
     const int hops = (n - 1) / h + 1;
-    const int j0 = blockIdx.x * p.T, Tt = min(p.T, hops - j0), NF = Tt + 3;
-    const int16_t* x = p.pcm + (size_t)clip * n;
-    int16_t* y = p.out + (size_t)clip * n;
+    const int j0 = tile * p.T, Tt = min(p.T, hops - j0), NF = Tt + 3;
+    const int16_t* x = p.pcm + clip_start(p.g, clip);
+    int16_t* y = p.out + clip_start(p.g, clip);
     const double2* win2 = reinterpret_cast<const double2*>(p.window);
     const int per = (N >> 2) + 1;                                // bin pairs (b, N/2 - b), b = 0..N/4
     // sample j = q h + off of a frame is half (j & 1) of packed point q (h / 2) + (off >> 1): disjoint bits, and fft_pos permutes bits
@@ -187,12 +204,13 @@ static size_t dn_lds_bytes(int N, int F) {
     return (size_t)F * 2 * SPEC_PHYS(N2) * 8 + (size_t)F * 2 * DN_XS(N2) * 8 + (size_t)3 * h * 8 + (size_t)(F + 3) * h * 2;
 }
 
-DenoisePlan denoise_plan(int n_clips, int n, int N) {
+// `tiles(T)`: the blocks of the call at T hops per block
+template <class Tiles>
+static DenoisePlan dn_plan(int N, Tiles tiles) {
     DenoisePlan q;
-    const int h = N / 4, hops = (n - 1) / h + 1;
     // T: as many hops per block as leave the device a few blocks per CU
     q.T = DN_TMAX;
-    while (q.T > 8 && (long long)n_clips * ((hops + q.T - 1) / q.T) < 1024) q.T >>= 1;
+    while (q.T > 8 && tiles(q.T) < 1024) q.T >>= 1;
     // F: as many frames per round as leave room for two blocks per CU; one block per CU where not even two frames fit that
     const int fcap = std::min(DN_FMAX, q.T + 3);
     auto fit = [&](size_t budget) {
@@ -206,26 +224,72 @@ DenoisePlan denoise_plan(int n_clips, int n, int N) {
     return q;
 }
 
+DenoisePlan denoise_plan(int n_clips, int n, int N) {
+    const int h = N / 4, hops = (n - 1) / h + 1;
+    return dn_plan(N, [&](int T) { return (long long)n_clips * ((hops + T - 1) / T); });
+}
+
+static long long dn_ragged_tiles(int n_clips, const int* lens, int N, int T) {
+    const int h = N / 4;
+    long long tiles = 0;
+    for (int c = 0; c < n_clips; c++) tiles += ((lens[c] - 1) / h + 1 + T - 1) / T;
+    return tiles;
+}
+
+DenoisePlan denoise_ragged_plan(int n_clips, const int* lens, int N) {
+    return dn_plan(N, [&](int T) { return dn_ragged_tiles(n_clips, lens, N, T); });
+}
+
+size_t denoise_ragged_table_bytes(int n_clips) { return (2 * ((size_t)n_clips + 1) * 8 + 255) & ~(size_t)255; }
+
 std::vector<double> denoise_table(int N) {
     std::vector<double> w((size_t)N);
     for (int j = 0; j < N; j++) w[j] = 0.5 - 0.5 * std::cos(6.283185307179586476925286766559 * (double)j / (double)N);
     return spectrogram_table(N, w.data());
 }
 
-void launch_denoise(const int16_t* pcm, int n_clips, int n, int N, double nr_db, double nf_db, const double* d_table, int16_t* out,
-                    hipStream_t s) {
-    const DenoisePlan q = denoise_plan(n_clips, n, N);
+static DnParams dn_params(const int16_t* pcm, int N, double nr_db, double nf_db, const double* d_table, int16_t* out, const DenoisePlan& q) {
     DnParams p{};
     p.pcm = pcm; p.out = out;
     p.tw = reinterpret_cast<const double2*>(d_table);
     p.window = d_table + N;
-    p.n = n; p.N = N; p.T = q.T; p.F = q.F;
+    p.N = N; p.T = q.T; p.F = q.F;
     p.fp = fft_passes_plan(N);
     p.nz = std::pow(10.0, nf_db / 10.0) * (3.0 * (double)N / 8.0);
     p.gmin = std::pow(10.0, -nr_db / 20.0);
+    return p;
+}
+
+void launch_denoise(const int16_t* pcm, int n_clips, int n, int N, double nr_db, double nf_db, const double* d_table, int16_t* out,
+                    hipStream_t s) {
+    const DenoisePlan q = denoise_plan(n_clips, n, N);
+    DnParams p = dn_params(pcm, N, nr_db, nf_db, d_table, out, q);
+    p.g.n_clips = n_clips; p.g.n = n;
     const int h = N / 4, hops = (n - 1) / h + 1;
     lds_limit_once<&k_denoise>(160 * 1024);
     hipLaunchKernelGGL(k_denoise, dim3((hops + q.T - 1) / q.T, n_clips), dim3(DN_THREADS), q.lds, s, p);
+}
+
+void launch_denoise_ragged(const int16_t* pcm, int n_clips, const int* lens, int N, double nr_db, double nf_db, const double* d_table,
+                           int16_t* out, void* d_tables, hipStream_t s) {
+    const DenoisePlan q = denoise_ragged_plan(n_clips, lens, N);
+    DnParams p = dn_params(pcm, N, nr_db, nf_db, d_table, out, q);
+    // start | tile0, [n_clips + 1] each
+    const int h = N / 4;
+    std::vector<long long> t(2 * ((size_t)n_clips + 1));
+    long long *start = t.data(), *tile0 = start + n_clips + 1;
+    start[0] = tile0[0] = 0;
+    for (int c = 0; c < n_clips; c++) {
+        start[c + 1] = start[c] + lens[c];
+        tile0[c + 1] = tile0[c] + ((lens[c] - 1) / h + 1 + q.T - 1) / q.T;
+    }
+    // (a pageable source is staged before hipMemcpyAsync returns, so the host tables need not outlive the call)
+    (void)hipMemcpyAsync(d_tables, t.data(), t.size() * 8, hipMemcpyHostToDevice, s);
+    p.g.n_clips = n_clips;
+    p.g.start = static_cast<const long long*>(d_tables);
+    p.tile0 = p.g.start + n_clips + 1;
+    lds_limit_once<&k_denoise>(160 * 1024);
+    hipLaunchKernelGGL(k_denoise, dim3((unsigned)tile0[n_clips]), dim3(DN_THREADS), q.lds, s, p);
 }
 
 void launch_pcm_gain(const int16_t* pcm, size_t total, double factor, int16_t* out, hipStream_t s) {

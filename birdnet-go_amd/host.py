@@ -56,7 +56,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_spectrogram_ragged_pcm16", "bnhip_spectrogram_png_ragged_pcm16", "bnhip_spectrogram_ragged_device",
            "bnhip_flac_stream_info", "bnhip_flac_decode_workspace_size", "bnhip_flac_decode_device", "bnhip_flac_decode_pcm16",
            "bnhip_flac_spectrogram_png", "bnhip_denoise_workspace_size", "bnhip_denoise_device", "bnhip_denoise_pcm16",
-           "bnhip_process_pcm16"]
+           "bnhip_process_pcm16", "bnhip_denoise_ragged_workspace_size", "bnhip_denoise_ragged_device", "bnhip_denoise_ragged_pcm16",
+           "bnhip_process_ragged_pcm16", "bnhip_process_spectrogram_png_ragged_pcm16"]
 
 
 class HipError(RuntimeError):
@@ -926,6 +927,81 @@ def spectrogram_ragged_device(d_samples_ptr, f32, lens, width, height, d_image_p
                                                     float(top_db), float(range_db), d_image_ptr, d_workspace_ptr, int(workspace_bytes),
                                                     hip_stream_ptr))
     del keep
+
+
+def denoise_ragged(clips, frame, nr_db, nf_db, device=0):
+    """denoise of a ragged burst in one device call: a list of 1-D int16 clips of any lengths -> list of int16 outputs, clip i what
+    `denoise` gives clip i alone, byte for byte."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    y = np.empty_like(x)
+    lib.bnhip_denoise_ragged_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p]
+    _check(lib, lib.bnhip_denoise_ragged_pcm16(device, x.ctypes.data, lens.size, lens.ctypes.data, int(frame), float(nr_db), float(nf_db),
+                                               y.ctypes.data))
+    return ragged_unpack(y, lens)
+
+
+def denoise_ragged_workspace_size(lens, frame):
+    """Bytes of device scratch denoise_ragged_device needs for clips of these lengths: two prefix tables of len(lens) + 1 64-bit
+    entries, rounded up to 256."""
+    return _ragged_size_query("bnhip_denoise_ragged_workspace_size", lens, frame)
+
+
+def denoise_ragged_device(d_pcm_ptr, lens, frame, nr_db, nf_db, d_out_pcm_ptr, d_workspace_ptr, workspace_bytes, device=0, hip_stream_ptr=None):
+    """Device-resident form: the packed clips, the packed output clips (distinct) and the workspace are device pointers, lens a host
+    array; enqueued on the stream, not synchronised."""
+    lib = load_library()
+    x = _ragged_lens(lens)
+    lib.bnhip_denoise_ragged_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_denoise_ragged_device(device, d_pcm_ptr, x.size, x.ctypes.data, int(frame), float(nr_db), float(nf_db), d_out_pcm_ptr,
+                                                d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
+
+
+def process_ragged(clips, rate, frame=0, nr_db=0.0, nf_db=-40.0, normalize=False, target_lufs=-23.0, true_peak_dbtp=-2.0, gain_db=0.0,
+                   device=0):
+    """`process` of a ragged burst in one device call: a list of 1-D int16 clips of any lengths -> (list of int16 outputs, list of
+    Loudness or None without normalize), both in the input's order."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    y = np.empty_like(x)
+    res = (Loudness * lens.size)() if normalize else None
+    lib.bnhip_process_ragged_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                               C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_process_ragged_pcm16(device, x.ctypes.data, lens.size, lens.ctypes.data, int(rate), int(frame), float(nr_db),
+                                               float(nf_db), 1 if normalize else 0, float(target_lufs), float(true_peak_dbtp), float(gain_db),
+                                               y.ctypes.data, C.addressof(res) if normalize else None))
+    return ragged_unpack(y, lens), (list(res) if normalize else None)
+
+
+def process_spectrogram_png_ragged(clips, rate, width, palette, frame=0, nr_db=0.0, nf_db=-40.0, normalize=False, target_lufs=-23.0,
+                                   true_peak_dbtp=-2.0, gain_db=0.0, rate_out=0, window=None, top_db=0.0, range_db=100.0, want_pcm=False,
+                                   device=0, raw=False):
+    """process_ragged and spectrogram_png_ragged in one device call, the processed PCM staying on the device (ProcessedSpectrogramByID,
+    media.go:1321): a list of 1-D int16 clips of any lengths -> (list of B PNG streams (raw=True: as png_encode), list of Loudness or
+    None without normalize, list of the processed int16 clips or None without want_pcm)."""
+    lib = load_library()
+    x, lens = ragged_pack(clips)
+    pal = _png_palette(palette)
+    height, fft_size = spectrogram_size(width)
+    keep, wp = _spectrogram_window(window, fft_size)
+    B = lens.size
+    cap = png_max_bytes(B, width, height)
+    out, offsets = np.empty(cap, np.uint8), np.zeros(B + 1, np.uint64)
+    res = (Loudness * B)() if normalize else None
+    y = np.empty_like(x) if want_pcm else None
+    lib.bnhip_process_spectrogram_png_ragged_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                               C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                               C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_process_spectrogram_png_ragged_pcm16(device, x.ctypes.data, B, lens.ctypes.data, int(rate), int(frame), float(nr_db),
+                                                               float(nf_db), 1 if normalize else 0, float(target_lufs), float(true_peak_dbtp),
+                                                               float(gain_db), int(rate_out), int(width), height, wp, float(top_db),
+                                                               float(range_db), pal.ctypes.data, out.ctypes.data, cap, offsets.ctypes.data,
+                                                               C.addressof(res) if normalize else None, y.ctypes.data if want_pcm else None))
+    del keep
+    png = (out[:int(offsets[B])], offsets) if raw else _flac_streams(out, offsets)
+    return png, (list(res) if normalize else None), (ragged_unpack(y, lens) if want_pcm else None)
 
 
 FLAC_OK, FLAC_BAD_METADATA, FLAC_UNSUPPORTED, FLAC_CORRUPT = 0, 1, 2, 3

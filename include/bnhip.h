@@ -522,7 +522,28 @@ int bnhip_flac_spectrogram_png(int device, const uint8_t* streams, int n_streams
  * finite or outside [0, 97], nf_db not finite or outside [-80, -20], d_out_pcm == d_pcm, a gain_db that is not finite or outside
  * +-60 (IsValidGainDB, process.go:198-203), a workspace that is too small or misaligned, and what
  * bnhip_loudness_normalize_pcm16 rejects when normalising.  Mono int16 only: the bindings answer BNHIP_E_UNSUPPORTED for anything
- * else.  Argument errors are answered before any device is touched. */
+ * else.  Argument errors are answered before any device is touched.
+ *
+ * Ragged forms ("Ragged bursts": n_clips clips of lens[c] >= 1 samples packed back to back, lens a host array; 1..65535 clips,
+ * a total below 2^36 samples).  A review page of N detections of the extended capture holds about N lengths: one call instead of
+ * N.  The sample values remain this project's spec, pinned to tests/dnref.py, not afftdn's; clip c's bytes are those of the
+ * uniform entry called on clip c alone, whatever else the burst holds (a sample's four contributions are added in frame order
+ * whatever the grouping of frames into blocks).
+ *   denoise_ragged_workspace_size / _device: the workspace holds the launch's two prefix tables, the clips' starts and their
+ *     tile counts: bytes = 2 * (n_clips + 1) * 8 rounded up to a multiple of 256.  The tables are copied there by a copy
+ *     enqueued on hip_stream; d_out_pcm must not overlap d_pcm over the packed total; nothing is allocated or synchronised.
+ *   denoise_ragged_pcm16: host memory in and out, one device allocation.
+ *   bnhip_process_ragged_pcm16: bnhip_process_pcm16 of a ragged burst: the stages are bnhip_denoise_ragged_pcm16, then
+ *     bnhip_loudness_ragged_normalize_pcm16(target_lufs, true_peak_dbtp, max_gain_db +inf, gate_fallback 0), then the gain; byte
+ *     for byte what those give called one after another.  One device allocation.
+ *   bnhip_process_spectrogram_png_ragged_pcm16: the counterpart of ProcessedSpectrogramByID (media.go:1321) -
+ *     bnhip_process_ragged_pcm16, then bnhip_spectrogram_png_ragged_pcm16 at rate_in = rate (with its resampler when rate_out
+ *     is neither 0 nor rate) in one call: the processed PCM never crosses to the host unless out_pcm (nullable, the packed
+ *     total) asks for it.  loud (required iff normalize) receives the records; out / out_cap / png_offsets as in
+ *     bnhip_spectrogram_png_ragged_pcm16.  One device allocation, one synchronising fetch.  A uniform batch is a ragged burst
+ *     of equal lengths: there is no separate uniform form.
+ * BNHIP_E_INVALID: what the uniform entries reject, a NULL lens, n_clips outside 1..65535, a length below 1, a total above
+ * 2^36 - 1, and for the fused entry what bnhip_spectrogram_png_ragged_pcm16 rejects; answered before any device is touched. */
 int bnhip_denoise_workspace_size(int n_clips, int n, int frame, size_t* bytes);
 int bnhip_denoise_device(int device, const int16_t* d_pcm, int n_clips, int n, int frame, double nr_db, double nf_db,
                          int16_t* d_out_pcm, void* d_workspace, size_t workspace_bytes, void* hip_stream);
@@ -531,6 +552,20 @@ int bnhip_denoise_pcm16(int device, const int16_t* pcm, int n_clips, int n, int 
 int bnhip_process_pcm16(int device, const int16_t* pcm, int n_clips, int n, int rate, int frame, double nr_db, double nf_db,
                         int normalize, double target_lufs, double true_peak_dbtp, double gain_db, int16_t* out_pcm,
                         bnhip_loudness* out);
+int bnhip_denoise_ragged_workspace_size(int n_clips, const int* lens, int frame, size_t* bytes);
+int bnhip_denoise_ragged_device(int device, const int16_t* d_pcm, int n_clips, const int* lens, int frame, double nr_db, double nf_db,
+                                int16_t* d_out_pcm, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+int bnhip_denoise_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int frame, double nr_db, double nf_db,
+                               int16_t* out_pcm);
+int bnhip_process_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate, int frame, double nr_db,
+                               double nf_db, int normalize, double target_lufs, double true_peak_dbtp, double gain_db,
+                               int16_t* out_pcm, bnhip_loudness* out);
+int bnhip_process_spectrogram_png_ragged_pcm16(int device, const int16_t* pcm, int n_clips, const int* lens, int rate, int frame,
+                                               double nr_db, double nf_db, int normalize, double target_lufs, double true_peak_dbtp,
+                                               double gain_db, int rate_out, int width, int height, const double* window,
+                                               double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap,
+                                               uint64_t* png_offsets, bnhip_loudness* loud /* required iff normalize */,
+                                               int16_t* out_pcm /* nullable */);
 
 /* Polyphase resampler for the step upstream of the classifier (Resampler.ResampleTo, internal/audiocore/resample/
  * resample.go:99-172).  Stateless per clip; n_out = ceil(n_in * rate_out / rate_in) (bnhip_resample_length); equal rates
