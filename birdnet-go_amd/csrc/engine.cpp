@@ -397,7 +397,8 @@ bool Engine::run(const float* d_in, int n, float* d_logits, float* d_emb, std::s
             if (ctx_stream[c] && ctx_stream[c] != stream) { hipEventRecord(ev_ctx_done[c], ctx_stream[c]); hipStreamWaitEvent(stream, ev_ctx_done[c], 0); }
         if (kstream[0] && kstream[0] != stream) hipStreamSynchronize(kstream[0]);      // (caller-owned main stream: the engine's own may still hold a chunk)
     }
-    if (!use_graphs || profiling) return run_eager(d_in, n, d_logits, d_emb, err, pcm);
+    // (a window table moves from chunk to chunk of its call: nothing to replay)
+    if (!use_graphs || profiling || pcm.win.first) return run_eager(d_in, n, d_logits, d_emb, err, pcm);
     GraphEntry* ge = nullptr;
     for (auto& g : graphs)
         if (g.in == d_in && g.logits == d_logits && g.emb == d_emb && g.n == n && g.pcm == pcm.samples && g.pcm_bits == pcm.bits) { ge = &g; break; }
@@ -472,12 +473,24 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
     // min/max + normalise as one launch (k_clip_norm_resident): decided ONCE per lane, here - what the launch reads (the lane's float
     // clips, or its PCM samples where nothing else in the plan reads the waveform) or nullptr for the pair.  A lane of a PCM call that
     // does not convert in that launch gets its float copy first.
+    // A call with a window table (file analysis): the lane's windows are read out of the recordings by that launch (its framed form:
+    // nothing but the pair may read the waveform, float32 input included, and the hop must keep the quads aligned), or framed into the
+    // lane's float input first.
     const void* res_x[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
     int res_bits[kMaxLanes] = {0, 0, 0, 0};
+    bool res_framed[kMaxLanes] = {false, false, false, false};
     for (int li = 0; li < nl; li++) {
         const Lane& L = lanes[li];
         const bool pair_here = norm_pair >= part_s0 && norm_pair + 1 < s_end;
         const float* xn = pair_here ? vptr(steps[norm_pair + 1].out, L.d_in, L.d_logits, L.d_emb, nl > 1 ? li : -1) : nullptr;
+        if (pcm.win.first) {
+            if (pair_here && pcm_direct && clip_norm_framed_ok(pcm.samples, pcm.win) && norm_resident_taken(L.n, pcm.samples, pcm.bits, xn)) {
+                res_x[li] = pcm.samples; res_bits[li] = pcm.bits; res_framed[li] = true; continue;
+            }
+            launch_frame_windows(pcm.samples, pcm.bits, win_at(pcm.win, L.clip0), L.n, n_samples, const_cast<float*>(L.d_in), L.st);
+            if (pair_here && norm_resident_taken(L.n, L.d_in, 0, xn)) res_x[li] = L.d_in;
+            continue;
+        }
         const char* src = pcm.samples ? static_cast<const char*>(pcm.samples) + (size_t)L.clip0 * n_samples * (pcm.bits / 8) : nullptr;
         if (src && pair_here && pcm_direct && norm_resident_taken(L.n, src, pcm.bits, xn)) { res_x[li] = src; res_bits[li] = pcm.bits; continue; }
         if (src) launch_pcm_to_f32(src, pcm.bits, const_cast<float*>(L.d_in), (size_t)L.n * n_samples, L.st);
@@ -515,8 +528,10 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
             case S_MINMAX:
                 if (si == norm_pair && res_x[li]) {
                     // (launch_clip_norm_resident refuses exactly what norm_resident_taken refuses: a refusal here is a bug, not a fallback)
+                    const WinView lane_win = win_at(pcm.win, lanes[li].clip0);
                     if (!launch_clip_norm_resident(res_x[li], res_bits[li], n, n_samples, specs[0].eps, specs[0].norm_sub, specs[0].norm_mul,
-                                                   reinterpret_cast<float2*>(out), vptr(steps[si + 1].out, d_in, d_logits, d_emb, clip0), stream)) {
+                                                   reinterpret_cast<float2*>(out), vptr(steps[si + 1].out, d_in, d_logits, d_emb, clip0), stream,
+                                                   res_framed[li] ? &lane_win : nullptr)) {
                         *err = "k_clip_norm_resident refused a call its predicate accepted"; mm_dirty = true; return false;
                     }
                     // (profile: the launch reads x once, as float or as PCM, and writes xn - the normalize step's bytes, not the sum)

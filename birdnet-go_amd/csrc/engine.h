@@ -85,7 +85,10 @@ struct FrontSpec {
 // `pcm` of Engine::run / run_on_context / run_part (from step 0): the call's input still is PCM samples, clip-major like d_in, and d_in
 // is the writable float staging for it.  Lanes that run min/max + normalise as the one resident launch convert in its load; every
 // other lane (and every plan without that pair) gets its float copy in d_in first, on the lane's stream.
-struct PcmSource { const void* samples = nullptr; int bits = 0; /* 16 / 24 / 32 */ };
+// With a window table (`win.first` set; file analysis, analyze.h) `samples` is the device block of recordings instead - float32 (bits 0)
+// or PCM - and clip i of the call is window win.w0 + i of the burst.  A lane then reads its windows where they lie, inside the
+// resident launch (its framed form), when the hop allows it; every other lane gets them framed into d_in first (k_frame_windows).
+struct PcmSource { const void* samples = nullptr; int bits = 0; /* 16 / 24 / 32 */ WinView win = {}; };
 
 struct ProfEntry { hipEvent_t a, b; int step; int n; double more_bytes = 0; };   // more_bytes: per clip, of a step that ran inside this launch
 

@@ -1,6 +1,7 @@
 // gfx950 ingest and the fp64-MFMA mel front end: PCM -> fp32, per-clip min / range, k_frontend (normalise -> frame -> window ->
 // real-DFT * mel -> power law -> NHWC store in one kernel).  The FFT-based front end is stft.hip.
 #include "kernels.h"
+#include "ragged.h"
 
 #include <algorithm>
 #include <cmath>
@@ -213,21 +214,39 @@ __device__ __forceinline__ void store_norm4(ClipBuf o, int q, const float4& v, f
     w.z = __float_as_uint(norm1(v.z, mn, d, sub, mul)); w.w = __float_as_uint(norm1(v.w, mn, d, sub, mul));
     __builtin_amdgcn_raw_buffer_store_b128(w, o, q * 16, 0, 0);
 }
-template <typename T>
+// The framed form (FRAMED, file analysis: analyze.h): x is the block of recordings and block b takes window wv.w0 + b of the burst
+// instead of clip b of a batch.  It finds its recording in the window prefix table (ragged_clip), and its input descriptors start
+// at the window's first sample and end with the window's valid samples, rounded up to a whole quad - the slot's zero fill; hop is
+// a multiple of 4, so every quad is aligned and wholly inside or wholly outside that extent.  The quads behind it load as zeros and,
+// unlike quads behind the clip, take part in min / max: they are the zero padding wav.frame_clips gives a recording's last window.
+// All of it is block-uniform scalar arithmetic in front of the first load; the other form never reads wv.
+template <typename T, bool FRAMED>
 __global__ __launch_bounds__(1024) void k_clip_norm_resident(const void* __restrict__ x, int n_samples, float eps, float norm_sub, float norm_mul,
-                                                             float2* __restrict__ mm, float* __restrict__ out) {
+                                                             float2* __restrict__ mm, float* __restrict__ out, WinView wv) {
     extern __shared__ float4 lq[];                // quads kNormRegQuads .. n4 - 1 of the clip
     __shared__ float smn[16], smx[16];
     constexpr int kIn = ClipIn<T>::kBytes * 4;     // bytes of an input quad
-    const char* xc = static_cast<const char*>(x) + (size_t)blockIdx.x * n_samples * ClipIn<T>::kBytes;
     const float* oc = out + (size_t)blockIdx.x * n_samples;
     const int n4 = n_samples / 4, nl = max(n4 - kNormRegQuads, 0), tid = threadIdx.x;
+    const char* xc;
+    int xbytes;                                   // where the input ends, from xc
+    if constexpr (FRAMED) {
+        const long long w = (long long)wv.w0 + blockIdx.x;
+        const int rec = ragged_clip(wv.first, wv.n_rec, w);
+        const long long s0 = (w - wv.first[rec]) * wv.hop;
+        const int valid = (int)min((long long)n_samples, wv.slot[2 * rec + 1] - s0);
+        xc = static_cast<const char*>(x) + wv.slot[2 * rec] + s0 * ClipIn<T>::kBytes;
+        xbytes = ((valid + 3) >> 2) * kIn;
+    } else {
+        xc = static_cast<const char*>(x) + (size_t)blockIdx.x * n_samples * ClipIn<T>::kBytes;
+        xbytes = n4 * kIn;
+    }
     float mn = INFINITY, mx = -INFINITY;
     // the LDS part first, while the registers are free: 8 independent loads per thread and round
     for (int j0 = 0; j0 < nl; j0 += 8 * 1024) {
         float4 t[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) t[u] = ClipIn<T>::quad(clip_buf(xc, n4 * kIn, (kNormRegQuads + j0 + u * 1024) * kIn), tid);
+        for (int u = 0; u < 8; u++) t[u] = ClipIn<T>::quad(clip_buf(xc, xbytes, (kNormRegQuads + j0 + u * 1024) * kIn), tid);
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const int j = j0 + u * 1024 + tid;
@@ -238,7 +257,7 @@ __global__ __launch_bounds__(1024) void k_clip_norm_resident(const void* __restr
     // the register part: kNormR independent loads per thread
     float4 v[kNormR];
 #pragma unroll
-    for (int r = 0; r < kNormR; r++) v[r] = ClipIn<T>::quad(clip_buf(xc, n4 * kIn, 1024 * r * kIn), tid);
+    for (int r = 0; r < kNormR; r++) v[r] = ClipIn<T>::quad(clip_buf(xc, xbytes, 1024 * r * kIn), tid);
 #pragma unroll
     for (int r = 0; r < kNormR; r++) {            // (in source order: the scheduler's interleaving of the rounds costs registers, which spill)
         quad_minmax(v[r], tid + 1024 * r < n4, mn, mx);
@@ -264,23 +283,35 @@ __global__ __launch_bounds__(1024) void k_clip_norm_resident(const void* __restr
 bool clip_norm_resident_fits(int n_samples) {
     return n_samples > 0 && (n_samples & 3) == 0 && n_samples / 4 <= kNormRegQuads + kNormLdsQuads;
 }
-template <typename T>
-static void launch_cnr(const void* x, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out, hipStream_t s) {
-    lds_limit_once<&k_clip_norm_resident<T>>(kNormLdsBytes);
+template <typename T, bool FRAMED>
+static void launch_cnr_form(const void* x, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out, hipStream_t s,
+                            const WinView& wv) {
+    lds_limit_once<&k_clip_norm_resident<T, FRAMED>>(kNormLdsBytes);
     const int nl = std::max(n_samples / 4 - kNormRegQuads, 0);
-    hipLaunchKernelGGL(k_clip_norm_resident<T>, dim3(n_clips), dim3(1024), (size_t)nl * 16, s, x, n_samples, eps, norm_sub, norm_mul, mm, out);
+    hipLaunchKernelGGL((k_clip_norm_resident<T, FRAMED>), dim3(n_clips), dim3(1024), (size_t)nl * 16, s, x, n_samples, eps, norm_sub, norm_mul, mm, out, wv);
+}
+template <typename T>
+static void launch_cnr(const void* x, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out, hipStream_t s,
+                       const WinView* win) {
+    if (win) launch_cnr_form<T, true>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s, *win);
+    else launch_cnr_form<T, false>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s, WinView{});
+}
+bool clip_norm_framed_ok(const void* block, const WinView& v) {
+    return v.first && v.slot && v.n_rec > 0 && v.hop > 0 && (v.hop & 3) == 0 && !(reinterpret_cast<uintptr_t>(block) & 15);
 }
 bool launch_clip_norm_resident(const void* x, int bits, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out,
-                               hipStream_t s) {
+                               hipStream_t s, const WinView* win) {
     // whole quads, loaded and stored at their natural alignment (a clip is a whole number of quads, so every clip's base is aligned
-    // when the first one is: 16 bytes for float32 / int32, 8 for int16, 4 for the three words of a 24-bit quad)
+    // when the first one is: 16 bytes for float32 / int32, 8 for int16, 4 for the three words of a 24-bit quad; a window of the
+    // framed form starts a multiple of 4 samples into a 16-byte aligned slot)
     const uintptr_t in_align = bits == 16 ? 8 : bits == 24 ? 4 : 16;
     if (n_clips <= 0 || !clip_norm_resident_fits(n_samples) || (reinterpret_cast<uintptr_t>(x) & (in_align - 1)) || (reinterpret_cast<uintptr_t>(out) & 15))
         return false;
-    if (bits == 0) launch_cnr<float>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
-    else if (bits == 16) launch_cnr<int16_t>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
-    else if (bits == 24) launch_cnr<Pcm24>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
-    else if (bits == 32) launch_cnr<int32_t>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s);
+    if (win && !clip_norm_framed_ok(x, *win)) return false;
+    if (bits == 0) launch_cnr<float>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s, win);
+    else if (bits == 16) launch_cnr<int16_t>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s, win);
+    else if (bits == 24) launch_cnr<Pcm24>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s, win);
+    else if (bits == 32) launch_cnr<int32_t>(x, n_clips, n_samples, eps, norm_sub, norm_mul, mm, out, s, win);
     else return false;
     return true;
 }

@@ -12,6 +12,8 @@
 #include <vector>
 #include <cstdint>
 
+#include "analyze.h"
+
 namespace bnhip {
 
 // The dynamic-LDS limit of a kernel is an attribute of the function ON THE CURRENT DEVICE (round 5: process-wide once-flags left every
@@ -68,9 +70,13 @@ void launch_clip_minmax(const float* x, int n_clips, int n_samples, float eps, f
 // LDS between the two passes - mm and out are the pair's bit for bit.  x holds float32 (bits 0) or PCM samples (bits 16 / 24 / 32,
 // converted in the load as launch_pcm_to_f32 converts them).  false, and nothing launched: the clip does not fit on chip
 // (clip_norm_resident_fits) or a pointer is not aligned to whole quads - the caller then runs the pair.
+// win (file analysis, analyze.h): x is the block of recordings and clip b of the launch is window win->w0 + b of the burst, read where
+// it lies; also false when the table's hop is no multiple of 4 or the block is not 16-byte aligned (clip_norm_framed_ok) - the
+// caller then frames the windows first (launch_frame_windows).
 bool clip_norm_resident_fits(int n_samples);
+bool clip_norm_framed_ok(const void* block, const WinView& v);
 bool launch_clip_norm_resident(const void* x, int bits, int n_clips, int n_samples, float eps, float norm_sub, float norm_mul, float2* mm, float* out,
-                               hipStream_t s);
+                               hipStream_t s, const WinView* win = nullptr);
 
 struct FrontendParams {
     const float* x;        // [B, n_samples] raw clip

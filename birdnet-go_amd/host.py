@@ -57,7 +57,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_flac_stream_info", "bnhip_flac_decode_workspace_size", "bnhip_flac_decode_device", "bnhip_flac_decode_pcm16",
            "bnhip_flac_spectrogram_png", "bnhip_denoise_workspace_size", "bnhip_denoise_device", "bnhip_denoise_pcm16",
            "bnhip_process_pcm16", "bnhip_denoise_ragged_workspace_size", "bnhip_denoise_ragged_device", "bnhip_denoise_ragged_pcm16",
-           "bnhip_process_ragged_pcm16", "bnhip_process_spectrogram_png_ragged_pcm16"]
+           "bnhip_process_ragged_pcm16", "bnhip_process_spectrogram_png_ragged_pcm16", "bnhip_analyze_windows",
+           "bnhip_analyze_pcm_topk", "bnhip_analyze_pcm"]
 
 
 class HipError(RuntimeError):
@@ -115,6 +116,34 @@ def _check(lib, rc):
     if rc != BNHIP_OK:
         msg = (lib.bnhip_last_error() or b"").decode("utf-8", "replace")
         raise (ErrHIPUnavailable if rc == E_NO_DEVICE else HipError)(rc, msg)
+
+
+def _analyze_protos(lib):
+    """ctypes prototypes of the file-analysis entries (set at use, as for the other later entries: load_library must go on
+    loading a library that predates them)."""
+    lib.bnhip_analyze_windows.restype = C.c_longlong
+    lib.bnhip_analyze_windows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p]
+    lib.bnhip_analyze_pcm_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double,
+                                           C.c_int, C.c_void_p, C.c_void_p]
+    lib.bnhip_analyze_pcm.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double,
+                                      C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    return lib
+
+
+# one row of bnhip_analyze_pcm (bnhip_detection)
+DETECTION = np.dtype([("recording", "<i4"), ("window", "<i4"), ("class_index", "<i4"), ("confidence", "<f4")])
+
+
+def analyze_windows(lengths, n_samples, hop, min_tail=0):
+    """bnhip_analyze_windows (host only): the window prefix table [n_recordings + 1] of recordings of `lengths` samples framed into
+    windows of n_samples advanced by hop; the last entry is the number of windows."""
+    lib = _analyze_protos(load_library())
+    ln = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+    first = np.zeros(ln.size + 1, np.int64)
+    w = lib.bnhip_analyze_windows(ln.ctypes.data if ln.size else None, ln.size, int(n_samples), int(hop), int(min_tail), first.ctypes.data)
+    if w < 0:
+        _check(lib, int(w))
+    return first
 
 
 def init():
@@ -314,6 +343,44 @@ class HipClassifier:
         _check(self._lib, self._lib.bnhip_predict_pcm_topk(self._h, x.ctypes.data, bit_depth, batch_size, activation, sensitivity, k,
                                                            conf.ctypes.data, idx.ctypes.data))
         return conf, idx
+
+    def _analyze_args(self, raw, bit_depth, lengths):
+        self._alive()
+        _analyze_protos(self._lib)
+        if bit_depth not in (0, 16, 24, 32):
+            raise HipError(E_INVALID, f"unsupported bit depth: {bit_depth} (supported: 0 = float32, 16, 24, 32)")
+        x = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
+        ln = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        bps = bit_depth // 8 if bit_depth else 4
+        if x.size != int(ln.sum()) * bps:
+            raise HipError(E_INVALID, f"input size mismatch: expected {int(ln.sum())} samples of {bps} bytes, got {x.size} bytes")
+        return x, ln
+
+    def analyze_pcm_topk(self, raw, bit_depth, lengths, hop, min_tail=0, k=10, activation=0, sensitivity=1.0):
+        """bnhip_analyze_pcm_topk: recordings (packed back to back, `lengths` samples each; bit_depth 0 = float32) in, the top-k of
+        every overlapping window out - the windows are framed on the device.  -> (conf [W, k], idx [W, k], first_window)."""
+        x, ln = self._analyze_args(raw, bit_depth, lengths)
+        first = analyze_windows(ln, self.n_samples, hop, min_tail)
+        kk, w = min(k, self._n_classes), int(first[-1])
+        conf = np.empty((w, kk), np.float32)
+        idx = np.empty((w, kk), np.int32)
+        _check(self._lib, self._lib.bnhip_analyze_pcm_topk(self._h, x.ctypes.data, bit_depth, ln.ctypes.data, ln.size, int(hop), int(min_tail),
+                                                           activation, sensitivity, k, conf.ctypes.data, idx.ctypes.data))
+        return conf, idx, first
+
+    def analyze_pcm(self, raw, bit_depth, lengths, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
+        """bnhip_analyze_pcm: the same call, answered as detection rows (DETECTION: recording, window inside the recording,
+        class_index, confidence) with confidence >= threshold, ordered by window, then rank.  -> (rows, total); cap limits the rows
+        written (default: room for every row), total is their number whatever the cap."""
+        x, ln = self._analyze_args(raw, bit_depth, lengths)
+        if cap is None:
+            cap = int(analyze_windows(ln, self.n_samples, hop, min_tail)[-1]) * min(k, self._n_classes)
+        rows = np.zeros(int(cap), DETECTION)
+        n = C.c_size_t(0)
+        _check(self._lib, self._lib.bnhip_analyze_pcm(self._h, x.ctypes.data, bit_depth, ln.ctypes.data, ln.size, int(hop), int(min_tail),
+                                                      activation, sensitivity, k, float(threshold), rows.ctypes.data if cap else None,
+                                                      int(cap), C.byref(n)))
+        return rows[:min(int(cap), n.value)], n.value
 
     # ---- plumbing
     def set_stream(self, hip_stream_ptr):

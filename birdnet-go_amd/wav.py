@@ -17,8 +17,8 @@ class WavError(ValueError):
     pass
 
 
-def read_wav(path_or_bytes):
-    """-> (samples float32 [n] (first channel), sample_rate, bit_depth)."""
+def _first_channel(path_or_bytes):
+    """-> (first channel's sample bytes uint8 [n, bits / 8], sample_rate, bit_depth)."""
     raw = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
     if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
         raise WavError("not a RIFF/WAVE file")
@@ -45,7 +45,20 @@ def read_wav(path_or_bytes):
         raise WavError(f"unsupported audio bit depth: {bits}")
     bps = bits // 8
     n = len(data) // (bps * channels)
-    b = np.frombuffer(data, np.uint8, n * bps * channels).reshape(n, channels, bps)[:, 0, :]
+    return np.frombuffer(data, np.uint8, n * bps * channels).reshape(n, channels, bps)[:, 0, :], int(rate), int(bits)
+
+
+def read_wav_pcm(path_or_bytes):
+    """-> (the first channel's PCM bytes as they are in the file (little-endian, bit_depth / 8 each), sample_rate, bit_depth): what
+    the device-framed analysis sends (`HipClassifier.analyze_pcm`), converted on the device exactly as read_wav converts."""
+    b, rate, bits = _first_channel(path_or_bytes)
+    return np.ascontiguousarray(b).tobytes(), rate, bits
+
+
+def read_wav(path_or_bytes):
+    """-> (samples float32 [n] (first channel), sample_rate, bit_depth)."""
+    b, rate, bits = _first_channel(path_or_bytes)
+    n = b.shape[0]
     if bits == 16:
         s = b.copy().view("<i2").reshape(n).astype(np.float32) / np.float32(32768.0)
     elif bits == 24:
@@ -54,21 +67,35 @@ def read_wav(path_or_bytes):
         s = v.astype(np.float32) / np.float32(8388608.0)
     else:
         s = b.copy().view("<i4").reshape(n).astype(np.float32) / np.float32(2147483648.0)
-    return s, int(rate), int(bits)
+    return s, rate, bits
 
 
-def frame_clips(samples, sample_rate, clip_seconds=3.0, overlap_seconds=0.0, min_tail_seconds=1.0):
-    """-> (clips float32 [n_clips, clip_len], start_times_seconds [n_clips])."""
+def _framing(sample_rate, clip_seconds, overlap_seconds, min_tail_seconds):
     clip_len = int(round(clip_seconds * sample_rate))
     hop = clip_len - int(round(overlap_seconds * sample_rate))
     if clip_len <= 0 or hop <= 0:
         raise ValueError("overlap must be smaller than the clip length")
+    return clip_len, hop, int(min_tail_seconds * sample_rate)
+
+
+def window_table(lengths, sample_rate, clip_seconds=3.0, overlap_seconds=0.0, min_tail_seconds=1.0):
+    """frame_clips' rule for recordings of `lengths` samples, without the samples (bnhip_analyze_windows; needs no device):
+    -> (first_window int64 [n + 1], clip_len, hop, min_tail).  Recording r owns windows first_window[r] .. first_window[r + 1] - 1
+    of the burst; its window j starts at sample j * hop."""
+    from . import host
+    clip_len, hop, min_tail = _framing(sample_rate, clip_seconds, overlap_seconds, min_tail_seconds)
+    return host.analyze_windows(lengths, clip_len, hop, min_tail), clip_len, hop, min_tail
+
+
+def frame_clips(samples, sample_rate, clip_seconds=3.0, overlap_seconds=0.0, min_tail_seconds=1.0):
+    """-> (clips float32 [n_clips, clip_len], start_times_seconds [n_clips])."""
+    clip_len, hop, min_tail = _framing(sample_rate, clip_seconds, overlap_seconds, min_tail_seconds)
     x = np.asarray(samples, np.float32).reshape(-1)
     starts = []
     p = 0
     while p < x.size:
         remain = x.size - p
-        if remain >= clip_len or remain >= int(min_tail_seconds * sample_rate) or not starts:
+        if remain >= clip_len or remain >= min_tail or not starts:
             starts.append(p)
         if remain <= clip_len:
             break
@@ -81,14 +108,19 @@ def frame_clips(samples, sample_rate, clip_seconds=3.0, overlap_seconds=0.0, min
 
 
 def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0,
-                 model_rate=48000, device=0):
+                 model_rate=48000, device=0, device_framing=False):
     """File analysis = read -> (resample to the model's rate) -> frame -> batched predict_topk.
     Returns rows (start_s, end_s, label|index, confidence).
 
     `model_rate` is the sample rate the classifier's clip length is expressed in (48 kHz for BirdNET v2.4,
     `internal/classifier/model_registry.go:138-153`).  A file at another rate is resampled on the GPU first, as the
     reference resamples file input to the model rate (`internal/audiocore/resample/resample.go`, call sites
-    `analysis/buffer_consumer.go:118,192`); window times are in seconds of audio, whatever the file's rate."""
+    `analysis/buffer_consumer.go:118,192`); window times are in seconds of audio, whatever the file's rate.
+
+    device_framing=True: the same rows from one `bnhip_analyze_pcm` call - the file's PCM bytes go to the device as they are
+    and the windows are framed there (a resampled file goes as float32)."""
+    if device_framing:
+        return analyze_files([path], classifier, labels, sensitivity, overlap_seconds, top_k, threshold, model_rate, device)[0]
     s, rate, _ = read_wav(path)
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
@@ -106,3 +138,44 @@ def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds
             if c >= threshold:
                 rows.append((float(starts[i]), float(starts[i] + clip_seconds), labels[j] if labels else int(j), float(c)))
     return rows
+
+
+def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
+                  device=0):
+    """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
+    path, each what analyze_file returns for that file.  The files' PCM bytes are sent as they are when all of them are at the
+    model's rate and share one bit depth; otherwise every file goes as float32 (converted, and resampled where its rate differs,
+    exactly as analyze_file does)."""
+    if model_rate <= 0:
+        raise WavError(f"invalid model sample rate {model_rate}")
+    pcm = [read_wav_pcm(p) for p in paths]
+    depths = {bits for _, _, bits in pcm}
+    if len(depths) == 1 and all(rate == model_rate for _, rate, _ in pcm):
+        bits, bufs = depths.pop(), [raw for raw, _, _ in pcm]
+        lengths = [len(raw) // (bits // 8) for raw in bufs]
+    else:
+        bits, bufs = 0, []
+        for p in paths:
+            s, rate, _ = read_wav(p)
+            if rate != model_rate:
+                from . import host
+                s = host.Resampler(rate, model_rate, device=device).resample_f32(s)
+            bufs.append(np.ascontiguousarray(s, np.float32).tobytes())
+        lengths = [len(raw) // 4 for raw in bufs]
+    if not bufs or min(lengths) < 1:
+        raise WavError("a recording without samples")
+    clip_seconds = classifier.n_samples / float(model_rate)
+    clip_len, hop, min_tail = _framing(model_rate, clip_seconds, overlap_seconds, 1.0)
+    if clip_len != classifier.n_samples:
+        raise WavError(f"framed clip length {clip_len} != model input {classifier.n_samples}")
+    # the rows' test is `float32 confidence >= threshold`: on the device the threshold is a float32, so it is rounded UP - no float32
+    # lies between the two, and the test keeps exactly the rows the float64 comparison keeps
+    t32 = np.float32(threshold)
+    if float(t32) < threshold:
+        t32 = np.nextafter(t32, np.float32(np.inf))
+    det, _ = classifier.analyze_pcm(b"".join(bufs), bits, lengths, hop, min_tail, k=top_k, sensitivity=sensitivity, threshold=float(t32))
+    out = [[] for _ in paths]
+    for r, w, j, c in zip(det["recording"], det["window"], det["class_index"], det["confidence"]):
+        start = np.float64(int(w) * hop) / model_rate
+        out[int(r)].append((float(start), float(start + clip_seconds), labels[j] if labels else int(j), float(c)))
+    return out

@@ -209,6 +209,38 @@ int bnhip_predict_pcm_topk(bnhip_model* m, const void* pcm, int bits_per_sample,
 int bnhip_range_heatmap(bnhip_model* m, const float* coords, int n_cells, int species,
                         int stride, int total_weeks, float* result);
 
+/* File analysis: whole recordings in, the result of every overlapping analysis window out, in one call - the reference's `file`
+ * and `directory` commands (doc/wiki/file-analysis.md; the windowing is internal/audiocore/buffer/analysis.go:187-251; SURVEY.md
+ * section 8 row f1, BASELINE config 1).  The windows are never materialised on the host: every recording goes to the device once,
+ * as it is, and the plan's first launch reads each window where it lies.
+ *   windows  Host only, needs no device: the framing rule in integers.  A window is n_samples long and window j of a recording
+ *            starts at sample j * hop; with remain = length - j * hop it is kept when it is the recording's first, or remain >=
+ *            n_samples, or remain >= min_tail, and framing stops when remain <= n_samples (a kept last window is zero-padded).
+ *            first_window: [n_recordings + 1], first_window[r] = windows in front of recording r.  returns the total W (>= 1) or
+ *            a negative BNHIP_E_*.
+ *   pcm_topk pcm: the recordings packed back to back on the host, lengths[r] samples each; bits_per_sample 0 = float32, or 16 /
+ *            24 / 32 as in bnhip_predict_pcm.  n_samples is the model's clip.  Window w of the burst (recording r, j = w -
+ *            first_window[r]) gives row w of out_conf / out_idx: [W][min(k, n_classes)], what bnhip_predict_pcm_topk answers for the
+ *            host-framed window, bit for bit.  One H2D copy per recording, the windows in chunks of max_batch with no host round
+ *            trip per chunk, the rows down once.
+ *   pcm      The same, then the detection rows: every (window, rank) with confidence >= threshold (a NaN is dropped), ordered by
+ *            window, then rank.  *n_out = their total; min(cap, *n_out) rows are written (out may be NULL when cap is 0).
+ *            `window` counts inside its recording: it starts at sample window * hop.
+ * BNHIP_E_INVALID (nothing written, the handle stays usable): NULL pointers, an unknown bit depth, n_recordings outside 1..65535,
+ * a recording without samples, a burst of 2^36 samples or more, hop outside [1, n_samples], a negative min_tail, k <= 0, an
+ * unknown activation, a multi-device or plan-only handle, more than INT_MAX windows. */
+typedef struct bnhip_detection {
+    int32_t recording, window, class_index;
+    float confidence;
+} bnhip_detection;
+long long bnhip_analyze_windows(const int64_t* lengths, int n_recordings, int n_samples, int hop, int64_t min_tail,
+                                int64_t* first_window);
+int bnhip_analyze_pcm_topk(bnhip_model* m, const void* pcm, int bits_per_sample, const int64_t* lengths, int n_recordings, int hop,
+                           int64_t min_tail, int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx);
+int bnhip_analyze_pcm(bnhip_model* m, const void* pcm, int bits_per_sample, const int64_t* lengths, int n_recordings, int hop,
+                      int64_t min_tail, int activation, double sensitivity, int k, float threshold, bnhip_detection* out,
+                      size_t cap, size_t* n_out);
+
 /* Ultrasonic frame-CV filter (internal/audiocore/ultrasonic/filter.go:20-66), float64 throughout.
  * samples: host float64 [n_clips * n] (int16/32768 as float64, convert/pcm.go:108-113).
  * cv/ok: [n_clips]. device: HIP device ordinal. */
