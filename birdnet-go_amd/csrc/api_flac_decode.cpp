@@ -11,7 +11,6 @@
 
 namespace bnhip {
 
-// The metadata of a burst in host memory, read as bnhip_flac_stream_info reads one stream; -> 0 or a negative BNHIP_E_*
 int flacdec_read_infos(const uint8_t* streams, int n_streams, const uint64_t* offsets, std::vector<bnhip_flac_info>* infos) {
     if (n_streams < 1 || n_streams > 65535) return set_err(BNHIP_E_INVALID, "n_streams must be in [1, 65535]");
     infos->resize((size_t)n_streams);
@@ -79,13 +78,13 @@ int bnhip_flac_decode_pcm16(int device, const uint8_t* streams, int n_streams, c
     if (!rc) rc = use_device(device);
     if (rc) return rc;
     for (int c = 0; c < n_streams; c++) lens[c] = infos[(size_t)c].status == BNHIP_FLAC_OK ? (int)infos[(size_t)c].total_samples : 0;
-    // one device block: the streams, the clips, the results, the workspace
+    // one DevCarve: the streams, the clips, the results, the workspace
     const size_t in_bytes = (size_t)(offsets[n_streams] - offsets[0]), res_bytes = (size_t)n_streams * sizeof(bnhip_flac_decode_result);
     DevCarve cv;
     const size_t o_in = cv.add(offsets[n_streams]), o_pcm = cv.add(need * 2), o_res = cv.add(res_bytes);
     const size_t o_ws = cv.add(flacdec_workspace_bytes(n_streams, infos.data(), offsets));
     DevBlocks b;
-    cv.base = (char*)b.get(cv.bytes());
+    cv.alloc(b);
     uint8_t* d_in = cv.at<uint8_t>(o_in);
     if (b.he == hipSuccess && in_bytes) b.he = hipMemcpy(d_in + offsets[0], streams + offsets[0], in_bytes, hipMemcpyHostToDevice);
     if (b.he == hipSuccess) {

@@ -1,5 +1,6 @@
 // The device plumbing of the one-shot clip entries (api_loudness.cpp, api_flac.cpp, api_spectrogram.cpp, api_ultrasonic.cpp and the
-// one-shot half of api_resample.cpp): a cache of uploaded tables, a call's device blocks, and the argument checks they share.
+// one-shot half of api_resample.cpp): a cache of uploaded tables, a call's device blocks, the argument checks they share and the
+// copies that bring byte streams back.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "api_common.h"
+#include "ragged.h"
 
 namespace bnhip {
 
@@ -57,14 +59,29 @@ struct DevBlocks {
     ~DevBlocks() { for (void* d : p) hipFree(d); }
 };
 
-// The parts of a call that takes all its device memory as one block: add() every part first (-> its offset, 256-byte aligned, what
-// the device entries ask of a workspace), allocate bytes() once, then at() each offset.
+// The device parts of a host-pointer call: add() every part first (-> its handle), alloc() once, then at() each handle.  The parts
+// of DEV_OWN_BLOCK bytes and more are carved from one block at 256-byte alignment (what the device entries ask of a workspace), so a
+// call makes one driver allocation however many large parts it has.  A smaller part is an allocation of its own: those the HIP
+// runtime serves from blocks it keeps, with no driver call (1.4 us against 130 us and more from 2 MiB on, and a call on one 15 s
+// clip is 0.26 ms slower with its 1.4 MB parts in one 3 MB block than with each on its own: DESIGN.md section 9, "One body per
+// entry"), so a call whose parts are all small pays for none.
+constexpr size_t DEV_OWN_BLOCK = (size_t)2 << 20;
 struct DevCarve {
-    size_t total = 0;
-    char* base = nullptr;
-    size_t add(size_t bytes) { const size_t off = total; total += ((bytes ? bytes : 1) + 255) & ~(size_t)255; return off; }
-    size_t bytes() const { return total; }
-    template <class T> T* at(size_t off) const { return base ? (T*)(base + off) : nullptr; }
+    std::vector<size_t> sizes;
+    std::vector<char*> parts;
+    size_t add(size_t bytes) { sizes.push_back(bytes ? bytes : 1); return sizes.size() - 1; }
+    void alloc(DevBlocks& b) {
+        auto al = [](size_t s) { return (s + 255) & ~(size_t)255; };
+        size_t shared = 0;
+        for (size_t s : sizes) if (s >= DEV_OWN_BLOCK) shared += al(s);
+        char* next = shared ? (char*)b.get(shared) : nullptr;
+        for (size_t s : sizes) {
+            if (s < DEV_OWN_BLOCK) { parts.push_back((char*)b.get(s)); continue; }
+            parts.push_back(next);
+            if (next) next += al(s);
+        }
+    }
+    template <class T> T* at(size_t part) const { return part < parts.size() ? (T*)parts[part] : nullptr; }
 };
 
 // b.he != hipSuccess: BNHIP_E_NOMEM for a failed allocation, else BNHIP_E_RUNTIME; the HIP error is cleared for the thread's next call
@@ -80,32 +97,33 @@ inline int launch_status(const char* what) {
     return BNHIP_OK;
 }
 
-// what every clip entry checks before any device is touched; -> 0 or a negative BNHIP_E_*
-inline int clip_dims_check(int n_clips, int n) {
-    if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
-    if (n < 1) return set_err(BNHIP_E_INVALID, "n must be at least 1");
-    return 0;
-}
-
-// A ragged burst's lengths (host array lens[n_clips], each >= 1) before any device is touched.  The clips are packed back to back at
-// 64-bit offsets; the total is held to STREAMINFO's 36 bits, which keeps every flat count of the kernels (frames, segments, true-peak
-// tiles) inside a 31-bit grid.
+// What every clip entry checks of its clips before any device is touched; -> 0 or a negative BNHIP_E_*.  A ragged burst's lengths
+// are a host array, each >= 1; its clips are packed back to back at 64-bit offsets, and their total is held to STREAMINFO's 36 bits,
+// which keeps every flat count of the kernels (frames, segments, true-peak tiles) inside a 31-bit grid.
 constexpr long long RAGGED_MAX_SAMPLES = (1ll << 36) - 1;
-inline int ragged_lens_check(int n_clips, const int* lens) {
-    if (n_clips < 1 || n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
-    if (!lens) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+inline int clips_check(const Clips& c) {
+    if (c.n_clips < 1 || c.n_clips > 65535) return set_err(BNHIP_E_INVALID, "n_clips must be in [1, 65535]");
+    if (!c.lens) return c.n < 1 ? set_err(BNHIP_E_INVALID, "n must be at least 1") : 0;
     long long total = 0;
-    for (int c = 0; c < n_clips; c++) {
-        if (lens[c] < 1) return set_err(BNHIP_E_INVALID, "every clip length must be at least 1");
-        total += lens[c];
+    for (int i = 0; i < c.n_clips; i++) {
+        if (c.lens[i] < 1) return set_err(BNHIP_E_INVALID, "every clip length must be at least 1");
+        total += c.lens[i];
     }
     if (total > RAGGED_MAX_SAMPLES) return set_err(BNHIP_E_INVALID, "the clips' total length must be below 2^36 samples");
     return 0;
 }
-inline size_t ragged_total(int n_clips, const int* lens) {
-    size_t total = 0;
-    for (int c = 0; c < n_clips; c++) total += (size_t)lens[c];
-    return total;
+// a ragged entry's lens before they become a Clips, where NULL would say "uniform"; n_clips out of range is clips_check's to answer
+inline int lens_check(int n_clips, const int* lens) {
+    if (!lens && n_clips >= 1 && n_clips <= 65535) return set_err(BNHIP_E_INVALID, "NULL/empty argument");
+    return 0;
+}
+
+// what an entry that returns byte streams copies back: the offsets first (that copy is the call's synchronise), then exactly
+// offsets[n] bytes
+inline hipError_t fetch_streams(const unsigned long long* d_offsets, const uint8_t* d_bytes, int n, uint64_t* offsets, uint8_t* out) {
+    hipError_t he = hipMemcpy(offsets, d_offsets, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost);
+    if (he == hipSuccess && offsets[n] > 0) he = hipMemcpy(out, d_bytes, (size_t)offsets[n], hipMemcpyDeviceToHost);
+    return he;
 }
 
 // a device entry's caller-owned workspace against what `size_entry` (the bnhip_*_workspace_size to name) answers

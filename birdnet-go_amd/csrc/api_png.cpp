@@ -19,12 +19,6 @@ int png_cap_check(int n_images, int width, int height, size_t out_cap) {
     return 0;
 }
 
-hipError_t png_fetch(const unsigned long long* d_offsets, const uint8_t* d_bytes, int n_images, uint64_t* offsets, uint8_t* out) {
-    hipError_t he = hipMemcpy(offsets, d_offsets, ((size_t)n_images + 1) * 8, hipMemcpyDeviceToHost);
-    if (he == hipSuccess && offsets[n_images] > 0) he = hipMemcpy(out, d_bytes, (size_t)offsets[n_images], hipMemcpyDeviceToHost);
-    return he;
-}
-
 }  // namespace bnhip
 
 using namespace bnhip;
@@ -70,13 +64,13 @@ int bnhip_png_encode_u8(int device, const uint8_t* images, int n_images, int wid
     if (!rc) rc = png_cap_check(n_images, width, height, out_cap);
     if (!rc) rc = use_device(device);
     if (rc) return rc;
-    // one device block: the images, the streams, the offsets, the workspace
+    // one DevCarve: the images, the streams, the offsets, the workspace
     const size_t img_bytes = (size_t)n_images * height * width, cap = png_max_bytes(n_images, width, height);
     DevCarve cv;
     const size_t o_img = cv.add(img_bytes), o_bytes = cv.add(cap), o_off = cv.add(((size_t)n_images + 1) * 8);
     const size_t o_ws = cv.add(png_workspace_bytes(n_images, width, height));
     DevBlocks b;
-    cv.base = (char*)b.get(cv.bytes());
+    cv.alloc(b);
     uint8_t *d_img = cv.at<uint8_t>(o_img), *d_bytes = cv.at<uint8_t>(o_bytes);
     unsigned long long* d_offsets = cv.at<unsigned long long>(o_off);
     if (b.he == hipSuccess) b.he = hipMemcpy(d_img, images, img_bytes, hipMemcpyHostToDevice);
@@ -84,7 +78,7 @@ int bnhip_png_encode_u8(int device, const uint8_t* images, int n_images, int wid
         launch_png(d_img, png_work(n_images, width, height, palette, cv.at<void>(o_ws)), d_bytes, cap, d_offsets, nullptr);
         b.he = hipGetLastError();
     }
-    if (b.he == hipSuccess) b.he = png_fetch(d_offsets, d_bytes, n_images, offsets, out);
+    if (b.he == hipSuccess) b.he = fetch_streams(d_offsets, d_bytes, n_images, offsets, out);
     return b.he == hipSuccess ? BNHIP_OK : hip_fail("png_encode_u8", b);
     BN_GUARD_END((void)0)
 }

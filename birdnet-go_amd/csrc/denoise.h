@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "ragged.h"
+
 namespace bnhip {
 
 constexpr int DN_N_MIN = 64, DN_N_MAX = 4096;            // supported frame lengths, powers of two
@@ -21,25 +23,21 @@ struct DenoisePlan {
     int T = 0, F = 0;
     size_t lds = 0;
 };
-DenoisePlan denoise_plan(int n_clips, int n, int N);
-// The same of a ragged burst (ragged.h): lens[n_clips] >= 1 on the host.  T by the uniform rule with the burst's total tile count,
-// the sum of ceil(hops_c / T) over the clips, in place of the product; F and the LDS from N and T as above.
-DenoisePlan denoise_ragged_plan(int n_clips, const int* lens, int N);
-// the ragged launch's device tables start | tile0, (n_clips + 1) 64-bit entries each, rounded up to 256 bytes
-size_t denoise_ragged_table_bytes(int n_clips);
+// T by the call's total tile count, the sum of ceil(hops_c / T) over the clips (a uniform batch's: the product); F and the LDS
+// from N and T.
+DenoisePlan denoise_plan(const Clips& clips, int N);
+// the device tables of a ragged launch: start | tile0, (n_clips + 1) 64-bit entries each, rounded up to 256 bytes; a uniform batch
+// has none (0)
+size_t denoise_table_bytes(const Clips& clips);
 
 // [N/2] (cos, -sin)(2 pi j / N) pairs, then the N periodic Hann coefficients (spectrogram_table of that window)
 std::vector<double> denoise_table(int N);
 
-// pcm, out: int16 [n_clips][n], distinct; d_table: denoise_table on the device.  Arguments validated by the caller.
-void launch_denoise(const int16_t* pcm, int n_clips, int n, int N, double nr_db, double nf_db, const double* d_table, int16_t* out,
-                    hipStream_t s);
-
-// The same of a ragged burst: pcm, out the clips packed back to back (distinct), lens on the host, d_tables
-// denoise_ragged_table_bytes of device memory, 8-byte aligned, which a copy enqueued on s fills before the kernel.  The bytes of
-// clip c are those of launch_denoise on that clip alone.
-void launch_denoise_ragged(const int16_t* pcm, int n_clips, const int* lens, int N, double nr_db, double nf_db, const double* d_table,
-                           int16_t* out, void* d_tables, hipStream_t s);
+// pcm, out: int16 [n_clips][n], or the clips of a ragged burst packed back to back; distinct.  d_table: denoise_table on the device.
+// d_tables: denoise_table_bytes of device memory, 8-byte aligned, which a copy enqueued on s fills before the kernel (not read for a
+// uniform batch).  Arguments validated by the caller.  The bytes of clip c are those of a launch on that clip alone.
+void launch_denoise(const int16_t* pcm, const Clips& clips, int N, double nr_db, double nf_db, const double* d_table, int16_t* out,
+                    void* d_tables, hipStream_t s);
 
 // out[i] = the pcmgain.h gain of pcm[i] at `factor` (in place allowed)
 void launch_pcm_gain(const int16_t* pcm, size_t total, double factor, int16_t* out, hipStream_t s);

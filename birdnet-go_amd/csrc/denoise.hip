@@ -33,7 +33,7 @@
 // runs in, so a clip's bytes are those of the uniform call on that clip alone.  A clip may start at an odd offset: every int16
 // access to HBM is a scalar one.
 // The flat grid stays inside 31 bits: h >= 16 and T >= 8, so a clip has at most len_c / 128 + 2 tiles, and with the limits of
-// ragged_lens_check (at most 65535 clips, a total below 2^36) a burst has at most 2^36 / 128 + 2 * 65535 < 2^29 + 2^17 tiles.
+// clips_check (at most 65535 clips, a total below 2^36) a burst has at most 2^36 / 128 + 2 * 65535 < 2^29 + 2^17 tiles.
 #include "denoise.h"
 
 #include <hip/hip_runtime.h>
@@ -204,13 +204,14 @@ static size_t dn_lds_bytes(int N, int F) {
     return (size_t)F * 2 * SPEC_PHYS(N2) * 8 + (size_t)F * 2 * DN_XS(N2) * 8 + (size_t)3 * h * 8 + (size_t)(F + 3) * h * 2;
 }
 
-// `tiles(T)`: the blocks of the call at T hops per block
-template <class Tiles>
-static DenoisePlan dn_plan(int N, Tiles tiles) {
+// the blocks of one clip of n samples at T hops of N / 4 samples per block
+static int dn_tiles(int n, int N, int T) { return ((n - 1) / (N / 4) + 1 + T - 1) / T; }
+
+DenoisePlan denoise_plan(const Clips& clips, int N) {
     DenoisePlan q;
     // T: as many hops per block as leave the device a few blocks per CU
     q.T = DN_TMAX;
-    while (q.T > 8 && tiles(q.T) < 1024) q.T >>= 1;
+    while (q.T > 8 && clips.sum([&](int n) { return dn_tiles(n, N, q.T); }) < 1024) q.T >>= 1;
     // F: as many frames per round as leave room for two blocks per CU; one block per CU where not even two frames fit that
     const int fcap = std::min(DN_FMAX, q.T + 3);
     auto fit = [&](size_t budget) {
@@ -224,23 +225,7 @@ static DenoisePlan dn_plan(int N, Tiles tiles) {
     return q;
 }
 
-DenoisePlan denoise_plan(int n_clips, int n, int N) {
-    const int h = N / 4, hops = (n - 1) / h + 1;
-    return dn_plan(N, [&](int T) { return (long long)n_clips * ((hops + T - 1) / T); });
-}
-
-static long long dn_ragged_tiles(int n_clips, const int* lens, int N, int T) {
-    const int h = N / 4;
-    long long tiles = 0;
-    for (int c = 0; c < n_clips; c++) tiles += ((lens[c] - 1) / h + 1 + T - 1) / T;
-    return tiles;
-}
-
-DenoisePlan denoise_ragged_plan(int n_clips, const int* lens, int N) {
-    return dn_plan(N, [&](int T) { return dn_ragged_tiles(n_clips, lens, N, T); });
-}
-
-size_t denoise_ragged_table_bytes(int n_clips) { return (2 * ((size_t)n_clips + 1) * 8 + 255) & ~(size_t)255; }
+size_t denoise_table_bytes(const Clips& clips) { return clips.lens ? (2 * ((size_t)clips.n_clips + 1) * 8 + 255) & ~(size_t)255 : 0; }
 
 std::vector<double> denoise_table(int N) {
     std::vector<double> w((size_t)N);
@@ -248,7 +233,10 @@ std::vector<double> denoise_table(int N) {
     return spectrogram_table(N, w.data());
 }
 
-static DnParams dn_params(const int16_t* pcm, int N, double nr_db, double nf_db, const double* d_table, int16_t* out, const DenoisePlan& q) {
+void launch_denoise(const int16_t* pcm, const Clips& clips, int N, double nr_db, double nf_db, const double* d_table, int16_t* out,
+                    void* d_tables, hipStream_t s) {
+    const int n_clips = clips.n_clips;
+    const DenoisePlan q = denoise_plan(clips, N);
     DnParams p{};
     p.pcm = pcm; p.out = out;
     p.tw = reinterpret_cast<const double2*>(d_table);
@@ -257,39 +245,27 @@ static DnParams dn_params(const int16_t* pcm, int N, double nr_db, double nf_db,
     p.fp = fft_passes_plan(N);
     p.nz = std::pow(10.0, nf_db / 10.0) * (3.0 * (double)N / 8.0);
     p.gmin = std::pow(10.0, -nr_db / 20.0);
-    return p;
-}
-
-void launch_denoise(const int16_t* pcm, int n_clips, int n, int N, double nr_db, double nf_db, const double* d_table, int16_t* out,
-                    hipStream_t s) {
-    const DenoisePlan q = denoise_plan(n_clips, n, N);
-    DnParams p = dn_params(pcm, N, nr_db, nf_db, d_table, out, q);
-    p.g.n_clips = n_clips; p.g.n = n;
-    const int h = N / 4, hops = (n - 1) / h + 1;
-    lds_limit_once<&k_denoise>(160 * 1024);
-    hipLaunchKernelGGL(k_denoise, dim3((hops + q.T - 1) / q.T, n_clips), dim3(DN_THREADS), q.lds, s, p);
-}
-
-void launch_denoise_ragged(const int16_t* pcm, int n_clips, const int* lens, int N, double nr_db, double nf_db, const double* d_table,
-                           int16_t* out, void* d_tables, hipStream_t s) {
-    const DenoisePlan q = denoise_ragged_plan(n_clips, lens, N);
-    DnParams p = dn_params(pcm, N, nr_db, nf_db, d_table, out, q);
-    // start | tile0, [n_clips + 1] each
-    const int h = N / 4;
-    std::vector<long long> t(2 * ((size_t)n_clips + 1));
-    long long *start = t.data(), *tile0 = start + n_clips + 1;
-    start[0] = tile0[0] = 0;
-    for (int c = 0; c < n_clips; c++) {
-        start[c + 1] = start[c] + lens[c];
-        tile0[c + 1] = tile0[c] + ((lens[c] - 1) / h + 1 + q.T - 1) / q.T;
+    p.g.n_clips = n_clips; p.g.n = clips.n;
+    dim3 grid;
+    if (!clips.lens) {
+        grid = dim3(dn_tiles(clips.n, N, q.T), n_clips);
+    } else {
+        // start | tile0, [n_clips + 1] each
+        std::vector<long long> t(2 * ((size_t)n_clips + 1));
+        long long *start = t.data(), *tile0 = start + n_clips + 1;
+        start[0] = tile0[0] = 0;
+        for (int c = 0; c < n_clips; c++) {
+            start[c + 1] = start[c] + clips.lens[c];
+            tile0[c + 1] = tile0[c] + dn_tiles(clips.lens[c], N, q.T);
+        }
+        // (a pageable source is staged before hipMemcpyAsync returns, so the host tables need not outlive the call)
+        (void)hipMemcpyAsync(d_tables, t.data(), t.size() * 8, hipMemcpyHostToDevice, s);
+        p.g.start = static_cast<const long long*>(d_tables);
+        p.tile0 = p.g.start + n_clips + 1;
+        grid = dim3((unsigned)tile0[n_clips]);
     }
-    // (a pageable source is staged before hipMemcpyAsync returns, so the host tables need not outlive the call)
-    (void)hipMemcpyAsync(d_tables, t.data(), t.size() * 8, hipMemcpyHostToDevice, s);
-    p.g.n_clips = n_clips;
-    p.g.start = static_cast<const long long*>(d_tables);
-    p.tile0 = p.g.start + n_clips + 1;
     lds_limit_once<&k_denoise>(160 * 1024);
-    hipLaunchKernelGGL(k_denoise, dim3((unsigned)tile0[n_clips]), dim3(DN_THREADS), q.lds, s, p);
+    hipLaunchKernelGGL(k_denoise, grid, dim3(DN_THREADS), q.lds, s, p);
 }
 
 void launch_pcm_gain(const int16_t* pcm, size_t total, double factor, int16_t* out, hipStream_t s) {

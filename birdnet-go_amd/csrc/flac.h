@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/bnhip.h"
+#include "ragged.h"
 
 namespace bnhip {
 
@@ -61,14 +62,12 @@ struct FlacWork {
 };
 int flac_frames(int n);
 int flac_seek_points(int n, int seek_interval);
-// the VERBATIM bound: no stream of n samples is longer (per clip: flac_max_bytes(1, ...))
+// the VERBATIM bound: no stream of n samples is longer (n_clips such streams); of a call's clips, the sum of its clips' bounds
 size_t flac_max_bytes(int n_clips, int n, int seek_interval);
-size_t flac_workspace_bytes(int n_clips, int n, int lpc_order = 0);      // (lpc_order 0: no side array, the size of before)
-FlacWork flac_work(int n_clips, int n, int rate, int seek_interval, void* d_block, int lpc_order = 0);
-// The same of a ragged burst: lens[n_clips] >= 1 on the host, the clips packed back to back.  The sum of flac_max_bytes(1, lens[c]).
-size_t flac_ragged_max_bytes(int n_clips, const int* lens, int seek_interval);
-size_t flac_ragged_workspace_bytes(int n_clips, const int* lens, int lpc_order);
-FlacWork flac_ragged_work(int n_clips, const int* lens, int rate, int seek_interval, void* d_block, int lpc_order);
+size_t flac_max_bytes(const Clips& clips, int seek_interval);
+// A ragged burst's block begins with its prefix tables; a uniform batch's has none, and with lpc_order 0 no side array either.
+size_t flac_workspace_bytes(const Clips& clips, int lpc_order);
+FlacWork flac_work(const Clips& clips, int rate, int seek_interval, void* d_block, int lpc_order);
 
 // pcm int16 [n_clips][n], or the packed clips of a ragged work; factor [n_clips] nullable (the gain of pcmgain.h, applied as the samples are staged); out: the streams
 // back to back, offsets uint64 [n_clips + 1].  Enqueues a ragged work's table copy, analyse, the two layout scans, the stream headers and emit; w.lpc_order picks

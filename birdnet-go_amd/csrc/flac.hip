@@ -660,10 +660,8 @@ size_t flac_max_bytes(int n_clips, int n, int seek_interval) {
     return b * (size_t)n_clips;
 }
 
-size_t flac_ragged_max_bytes(int n_clips, const int* lens, int seek_interval) {
-    size_t b = 0;
-    for (int c = 0; c < n_clips; c++) b += flac_max_bytes(1, lens[c], seek_interval);
-    return b;
+size_t flac_max_bytes(const Clips& clips, int seek_interval) {
+    return clips.sum([&](int n) { return flac_max_bytes(1, n, seek_interval); });
 }
 
 namespace {
@@ -682,44 +680,32 @@ void carve(FlacWork& w, char* p, size_t F) {
     w.fmax = (uint32_t*)p; p += align256(n_clips * 4);
     if (w.lpc_order > 0) w.lpc = (FlacLpc*)p;
 }
-size_t ragged_tables_bytes(int n_clips) { return align256(2 * ((size_t)n_clips + 1) * 8); }
-long long ragged_frames(int n_clips, const int* lens) {
-    long long F = 0;
-    for (int c = 0; c < n_clips; c++) F += flac_frames(lens[c]);
-    return F;
-}
+size_t tables_bytes(const Clips& clips) { return clips.lens ? align256(2 * ((size_t)clips.n_clips + 1) * 8) : 0; }
 
 }  // namespace
 
-size_t flac_workspace_bytes(int n_clips, int n, int lpc_order) {
-    return work_bytes(0, (size_t)n_clips, (size_t)n_clips * (size_t)flac_frames(n), lpc_order);
+size_t flac_workspace_bytes(const Clips& clips, int lpc_order) {
+    return work_bytes(tables_bytes(clips), (size_t)clips.n_clips, clips.sum(flac_frames), lpc_order);
 }
 
-size_t flac_ragged_workspace_bytes(int n_clips, const int* lens, int lpc_order) {
-    return work_bytes(ragged_tables_bytes(n_clips), (size_t)n_clips, (size_t)ragged_frames(n_clips, lens), lpc_order);
-}
-
-FlacWork flac_work(int n_clips, int n, int rate, int seek_interval, void* d_block, int lpc_order) {
+FlacWork flac_work(const Clips& clips, int rate, int seek_interval, void* d_block, int lpc_order) {
+    const int n_clips = clips.n_clips;
     FlacWork w;
-    w.n_clips = n_clips; w.n = n; w.rate = rate; w.seek_interval = seek_interval; w.lpc_order = lpc_order;
-    w.frames = flac_frames(n);
-    w.total_frames = (long long)n_clips * w.frames;
-    carve(w, (char*)d_block, (size_t)w.total_frames);
-    return w;
-}
-
-FlacWork flac_ragged_work(int n_clips, const int* lens, int rate, int seek_interval, void* d_block, int lpc_order) {
-    FlacWork w;
-    w.n_clips = n_clips; w.rate = rate; w.seek_interval = seek_interval; w.lpc_order = lpc_order;
-    // start[n_clips + 1], then frame0[n_clips + 1]
-    w.tables.resize(2 * ((size_t)n_clips + 1));
-    long long* start = w.tables.data(), *frame0 = start + n_clips + 1;
-    start[0] = frame0[0] = 0;
-    for (int c = 0; c < n_clips; c++) { start[c + 1] = start[c] + lens[c]; frame0[c + 1] = frame0[c] + flac_frames(lens[c]); }
-    w.total_frames = frame0[n_clips];
-    w.start = (const long long*)d_block;
-    w.frame0 = w.start + n_clips + 1;
-    carve(w, (char*)d_block + ragged_tables_bytes(n_clips), (size_t)w.total_frames);
+    w.n_clips = n_clips; w.n = clips.n; w.rate = rate; w.seek_interval = seek_interval; w.lpc_order = lpc_order;
+    if (!clips.lens) {
+        w.frames = flac_frames(clips.n);
+        w.total_frames = (long long)n_clips * w.frames;
+    } else {
+        // start[n_clips + 1], then frame0[n_clips + 1]
+        w.tables.resize(2 * ((size_t)n_clips + 1));
+        long long* start = w.tables.data(), *frame0 = start + n_clips + 1;
+        start[0] = frame0[0] = 0;
+        for (int c = 0; c < n_clips; c++) { start[c + 1] = start[c] + clips.lens[c]; frame0[c + 1] = frame0[c] + flac_frames(clips.lens[c]); }
+        w.total_frames = frame0[n_clips];
+        w.start = (const long long*)d_block;
+        w.frame0 = w.start + n_clips + 1;
+    }
+    carve(w, (char*)d_block + tables_bytes(clips), (size_t)w.total_frames);
     return w;
 }
 

@@ -66,4 +66,11 @@ FlacDecWork flacdec_work(int n_streams, const bnhip_flac_info* infos, const uint
 void launch_flacdec(const uint8_t* d_streams, const FlacDecWork& w, int16_t* d_pcm, size_t pcm_cap, bnhip_flac_decode_result* d_result,
                     hipStream_t s);
 
+// What an entry of another unit needs of api_flac_decode.cpp (bnhip_flac_spectrogram_png of api_spectrogram.cpp), both -> 0 or a
+// negative BNHIP_E_* with the error text set:
+// the metadata of a burst in host memory, read as bnhip_flac_stream_info reads one stream
+int flacdec_read_infos(const uint8_t* streams, int n_streams, const uint64_t* offsets, std::vector<bnhip_flac_info>* infos);
+// flacdec_check as an entry answers it
+int flacdec_burst_check(int n_streams, const bnhip_flac_info* infos, const uint64_t* offsets, size_t* pcm_samples);
+
 }  // namespace bnhip

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/bnhip.h"
+#include "ragged.h"
 
 namespace bnhip {
 
@@ -31,11 +32,9 @@ int loudness_sub_block(int rate);
 // (the recurrence is latency bound: a lane's time is its segment's length).  The largest of 8, 4, 2, 1 that divides S and keeps
 // the call under LOUD_MAX_LANES lanes.
 constexpr long long LOUD_MAX_LANES = 1 << 18;
-int loudness_split(int n_clips, int n, int S);
-// the same rule on a call's total: q * sub_blocks <= LOUD_MAX_LANES.  A ragged burst's split is that of the sum of its clips'
-// lens[c] / S sub-blocks, which for equal lengths is loudness_split(n_clips, n, S).
-int loudness_split_total(long long sub_blocks, int S);
-int loudness_ragged_split(int n_clips, const int* lens, int S);
+// The rule works on a call's total, the sum of its clips' len / S sub-blocks: q * sub_blocks <= LOUD_MAX_LANES.  So a ragged burst of
+// equal lengths has the uniform batch's split.
+int loudness_split(const Clips& clips, int S);
 // the table above for segments of seg_len samples, computed on the host (libm tan / pow / sin; float32-rounded coefficients
 // widened to double)
 std::vector<double> loudness_table(int rate, int seg_len);
@@ -64,11 +63,9 @@ struct LoudWork {
     double* pre = nullptr;                  // [n_clips] pre-gain factor of the running measurement
     int* act = nullptr;                     // [n_clips] clip takes part in the running measurement
 };
-size_t loudness_workspace_bytes(int n_clips, int n, int S);
-LoudWork loudness_work(int n_clips, int n, int S, void* d_block);
-// The same of a ragged burst: lens[n_clips] >= 1 on the host, the clips packed back to back.  A clip shorter than S has no sub-block.
-size_t loudness_ragged_workspace_bytes(int n_clips, const int* lens, int S);
-LoudWork loudness_ragged_work(int n_clips, const int* lens, int S, void* d_block);
+// A ragged burst's block begins with its prefix tables; a clip shorter than S has no sub-block.
+size_t loudness_workspace_bytes(const Clips& clips, int S);
+LoudWork loudness_work(const Clips& clips, int S, void* d_block);
 
 // pcm int16 [n_clips][n], or the packed clips of a ragged work; d_table: loudness_table on the device; out: bnhip_loudness [n_clips] on the device; out_pcm nullable.
 // Enqueues: a ragged work's table copy, init, the measurement (pass A, scan, pass B, true peak), the tail, with plan.gate_fallback the measurement of the
@@ -77,16 +74,13 @@ void launch_loudness(const int16_t* pcm, const LoudWork& w, const double* d_tabl
                      int16_t* out_pcm, hipStream_t s);
 
 
-// What an entry of another unit needs of api_loudness.cpp (the fused loudness + FLAC entry of api_flac.cpp):
-// the argument checks of the normalise entries, answered before any device is touched; -> 0 or a negative BNHIP_E_*
-int loudness_args_check(int n_clips, int n, int rate, double target, double ceiling, double max_gain);
-// the same of a ragged burst, what ragged_lens_check (api_oneshot.h) rejects included
-int loudness_ragged_args_check(int n_clips, const int* lens, int rate, double target, double ceiling, double max_gain);
+// What an entry of another unit needs of api_loudness.cpp (the fused loudness + FLAC entries of api_flac.cpp, the chain of
+// api_denoise.cpp):
+// the argument checks of the normalise entries, clips_check (api_oneshot.h) included, answered before any device is touched; -> 0
+// or a negative BNHIP_E_*
+int loudness_args_check(const Clips& clips, int rate, double target, double ceiling, double max_gain);
 // the device (already made current) has its table looked up or uploaded, and the normalise kernels are enqueued on s
-int loudness_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, int n, int rate, double target, double ceiling,
+int loudness_enqueue(const char* what, int device, const int16_t* d_pcm, const Clips& clips, int rate, double target, double ceiling,
                      double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace, hipStream_t s);
-int loudness_ragged_enqueue(const char* what, int device, const int16_t* d_pcm, int n_clips, const int* lens, int rate, double target,
-                            double ceiling, double max_gain, int gate_fallback, bnhip_loudness* d_out, int16_t* d_out_pcm, void* d_workspace,
-                            hipStream_t s);
 
 }  // namespace bnhip

@@ -332,18 +332,11 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int loudness_sub_block(int rate) { return (int)std::floor(0.1 * (double)rate + 0.5); }
 
-int loudness_split_total(long long sub_blocks, int S) {
+int loudness_split(const Clips& clips, int S) {
+    const long long sub_blocks = (long long)clips.sum([&](int n) { return n / S; });
     for (int q = 8; q > 1; q >>= 1)
         if (S % q == 0 && sub_blocks * q <= LOUD_MAX_LANES) return q;
     return 1;
-}
-
-int loudness_split(int n_clips, int n, int S) { return loudness_split_total((long long)n_clips * (n / S), S); }
-
-int loudness_ragged_split(int n_clips, const int* lens, int S) {
-    long long Gs = 0;
-    for (int c = 0; c < n_clips; c++) Gs += lens[c] / S;
-    return loudness_split_total(Gs, S);
 }
 
 std::vector<double> loudness_table(int rate, int seg_len) {
@@ -425,48 +418,43 @@ void carve(LoudWork& w, char* p, size_t Gs, size_t T) {
     w.pre = (double*)p; p += align256((size_t)w.n_clips * 8);
     w.act = (int*)p;
 }
-size_t ragged_tables_bytes(int n_clips) { return align256(3 * ((size_t)n_clips + 1) * 8); }
+size_t tables_bytes(const Clips& clips) { return clips.lens ? align256(3 * ((size_t)clips.n_clips + 1) * 8) : 0; }
 
 }  // namespace
 
-size_t loudness_workspace_bytes(int n_clips, int n, int S) {
-    return work_bytes(0, (size_t)n_clips, (size_t)n_clips * (size_t)(n / S), loudness_split(n_clips, n, S), (size_t)n_clips * (size_t)tp_tiles(n));
+size_t loudness_workspace_bytes(const Clips& clips, int S) {
+    return work_bytes(tables_bytes(clips), (size_t)clips.n_clips, clips.sum([&](int n) { return n / S; }), loudness_split(clips, S),
+                      clips.sum(tp_tiles));
 }
 
-size_t loudness_ragged_workspace_bytes(int n_clips, const int* lens, int S) {
-    size_t Gs = 0, T = 0;
-    for (int c = 0; c < n_clips; c++) { Gs += (size_t)(lens[c] / S); T += (size_t)tp_tiles(lens[c]); }
-    return work_bytes(ragged_tables_bytes(n_clips), (size_t)n_clips, Gs, loudness_split_total((long long)Gs, S), T);
-}
-
-LoudWork loudness_work(int n_clips, int n, int S, void* d_block) {
+LoudWork loudness_work(const Clips& clips, int S, void* d_block) {
+    const int n_clips = clips.n_clips;
     LoudWork w;
-    w.n_clips = n_clips; w.n = n; w.max_n = n; w.S = S; w.Ns = n / S;
-    w.q = loudness_split(n_clips, n, S); w.Sq = S / w.q;
-    w.tp_blocks = (int)tp_tiles(n);
-    w.tiles = (long long)n_clips * w.tp_blocks;
-    w.G = (long long)n_clips * w.Ns * w.q;
-    carve(w, (char*)d_block, (size_t)n_clips * (size_t)w.Ns, (size_t)w.tiles);
-    return w;
-}
-
-LoudWork loudness_ragged_work(int n_clips, const int* lens, int S, void* d_block) {
-    LoudWork w;
-    w.n_clips = n_clips; w.S = S;
-    // start[n_clips + 1], then sub0[n_clips + 1], then tile0[n_clips + 1]
-    w.tables.resize(3 * ((size_t)n_clips + 1));
-    long long* start = w.tables.data(), *sub0 = start + n_clips + 1, *tile0 = sub0 + n_clips + 1;
-    start[0] = sub0[0] = tile0[0] = 0;
-    for (int c = 0; c < n_clips; c++) {
-        start[c + 1] = start[c] + lens[c]; sub0[c + 1] = sub0[c] + lens[c] / S; tile0[c + 1] = tile0[c] + tp_tiles(lens[c]);
-        w.max_n = std::max(w.max_n, lens[c]);
+    w.n_clips = n_clips; w.n = clips.n; w.S = S;
+    w.q = loudness_split(clips, S); w.Sq = S / w.q;
+    long long sub_blocks;
+    if (!clips.lens) {
+        w.max_n = clips.n; w.Ns = clips.n / S;
+        w.tp_blocks = (int)tp_tiles(clips.n);
+        w.tiles = (long long)n_clips * w.tp_blocks;
+        sub_blocks = (long long)n_clips * w.Ns;
+    } else {
+        // start[n_clips + 1], then sub0[n_clips + 1], then tile0[n_clips + 1]
+        w.tables.resize(3 * ((size_t)n_clips + 1));
+        long long* start = w.tables.data(), *sub0 = start + n_clips + 1, *tile0 = sub0 + n_clips + 1;
+        start[0] = sub0[0] = tile0[0] = 0;
+        for (int c = 0; c < n_clips; c++) {
+            const int len = clips.lens[c];
+            start[c + 1] = start[c] + len; sub0[c + 1] = sub0[c] + len / S; tile0[c + 1] = tile0[c] + tp_tiles(len);
+            w.max_n = std::max(w.max_n, len);
+        }
+        w.tiles = tile0[n_clips];
+        sub_blocks = sub0[n_clips];
+        w.start = (const long long*)d_block;
+        w.sub0 = w.start + n_clips + 1; w.tile0 = w.sub0 + n_clips + 1;
     }
-    w.q = loudness_split_total(sub0[n_clips], S); w.Sq = S / w.q;
-    w.tiles = tile0[n_clips];
-    w.G = sub0[n_clips] * w.q;
-    w.start = (const long long*)d_block;
-    w.sub0 = w.start + n_clips + 1; w.tile0 = w.sub0 + n_clips + 1;
-    carve(w, (char*)d_block + ragged_tables_bytes(n_clips), (size_t)sub0[n_clips], (size_t)w.tiles);
+    w.G = sub_blocks * w.q;
+    carve(w, (char*)d_block + tables_bytes(clips), (size_t)sub_blocks, (size_t)w.tiles);
     return w;
 }
 

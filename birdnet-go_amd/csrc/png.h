@@ -59,10 +59,8 @@ void launch_png(const uint8_t* images, const PngWork& w, uint8_t* out, size_t ou
 
 
 // api_png.cpp, for the entries that put another stage in front of the encoder: what every entry checks before any device is touched
-// (-> 0 or a negative BNHIP_E_*), and the copies that end a host-pointer call - the offsets first (that copy is the call's
-// synchronise), then exactly offsets[n_images] bytes.
+// (-> 0 or a negative BNHIP_E_*).
 int png_args_check(int n_images, int width, int height);
 int png_cap_check(int n_images, int width, int height, size_t out_cap);
-hipError_t png_fetch(const unsigned long long* d_offsets, const uint8_t* d_bytes, int n_images, uint64_t* offsets, uint8_t* out);
 
 }  // namespace bnhip

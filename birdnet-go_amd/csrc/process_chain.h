@@ -11,12 +11,6 @@
 
 namespace bnhip {
 
-// The clips of a call: lens NULL for a uniform batch of n_clips clips of n samples, else the host lengths of a ragged burst.
-struct ChainClips {
-    int n_clips = 0, n = 0;
-    const int* lens = nullptr;
-    size_t total() const { return lens ? ragged_total(n_clips, lens) : (size_t)n_clips * (size_t)n; }
-};
 // frame 0 = no denoise; normalize 0 = no normalisation; gain_db 0 = no gain
 struct ChainArgs {
     int rate = 0, frame = 0;
@@ -27,18 +21,18 @@ struct ChainArgs {
 
 // what every chain entry checks before any device is touched: the clips' dimensions, the active stages' own arguments, the gain's
 // range (IsValidGainDB, process.go:198-203), "no filter active"; -> 0 or a negative BNHIP_E_*
-int chain_check(const ChainClips& c, const ChainArgs& a);
+int chain_check(const Clips& c, const ChainArgs& a);
 
-// the chain's parts of the call's one device block, besides d_final: the second clip buffer, the records, the stages' workspaces
+// the chain's parts of the call's DevCarve, besides d_final: the second clip buffer, the records, the stages' workspaces
 struct ChainParts { size_t pcm_bytes = 0, res_bytes = 0, o_other = 0, o_res = 0, o_lws = 0, o_dws = 0; };
-ChainParts chain_reserve(DevCarve& cv, const ChainClips& c, const ChainArgs& a);
+ChainParts chain_reserve(DevCarve& cv, const Clips& c, const ChainArgs& a);
 
 // where the caller puts the unprocessed clips (d_final or the part at o_other) so that the processed ones end at d_final
 int16_t* chain_input(const DevCarve& cv, const ChainParts& p, const ChainArgs& a, int16_t* d_final);
 
 // The device (already made current) has the stages' tables looked up or uploaded and the active stages enqueued on the null
 // stream: chain_input -> ... -> d_final, the records at o_res.  int16 between the stages, no gain clamp, no gate fallback.
-int chain_enqueue(const char* what, int device, const DevCarve& cv, const ChainParts& p, const ChainClips& c, const ChainArgs& a,
+int chain_enqueue(const char* what, int device, const DevCarve& cv, const ChainParts& p, const Clips& c, const ChainArgs& a,
                   int16_t* d_final);
 
 }  // namespace bnhip

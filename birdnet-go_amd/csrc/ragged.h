@@ -8,10 +8,33 @@
 // that stays in L2, against a unit's work of at least a hundred recurrence steps or a 4096-sample frame.  The search needs no LDS
 // (k_flac_analyse<true> has none to spare), no per-unit array to size, upload and keep in step with the lengths, and it skips
 // clips that own no unit (a clip shorter than a sub-block) by construction.
+//
+// The host states the same burst as a Clips, and every host function of the clip entries (sizes, workspaces, launches, checks) takes
+// one: the uniform / ragged decision is made once per kernel family, where the launch's geometry is worked out.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 namespace bnhip {
+
+// The clips of one call on the host: lens NULL for a uniform batch of n_clips clips of n samples, else the host lengths of a ragged
+// burst (n is 0 then).
+struct Clips {
+    int n_clips = 0, n = 0;
+    const int* lens = nullptr;
+    static Clips uniform(int n_clips, int n) { return {n_clips, n, nullptr}; }
+    static Clips ragged(int n_clips, const int* lens) { return {n_clips, 0, lens}; }
+    // the sum over the clips of per_clip(length); a uniform batch's is the product, with no walk over the clips
+    template <class F>
+    size_t sum(F per_clip) const {
+        if (!lens) return (size_t)n_clips * (size_t)per_clip(n);
+        size_t s = 0;
+        for (int c = 0; c < n_clips; c++) s += (size_t)per_clip(lens[c]);
+        return s;
+    }
+    size_t total() const { return sum([](int len) { return len; }); }
+};
 
 // The samples of a burst: start NULL for a uniform batch of n-sample clips, else the prefix table [n_clips + 1].
 struct ClipGeom {

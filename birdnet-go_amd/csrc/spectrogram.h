@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "ragged.h"
+
 namespace bnhip {
 
 constexpr int SPEC_N_MIN = 64, SPEC_N_MAX = 4096;       // supported transform lengths N = 2 (H - 1), powers of two
@@ -33,15 +35,12 @@ static_assert(sizeof(SpecClip) == 24, "row layout");
 // (device, N, window contents)
 std::vector<double> spectrogram_table(int N, const double* window);
 
-// samples: int16 PCM or (f32) float32 [n_clips][n]; d_table: spectrogram_table on the device; wsum = the window's sum;
-// image: uint8 [n_clips][H][W].  The geometry has been validated by the caller (H = 2^k + 1, N within SPEC_N_MIN..SPEC_N_MAX).
-void launch_spectrogram(const void* samples, int f32, int n_clips, int n, int W, int H, const double* d_table, double wsum,
-                        double top_db, double range_db, uint8_t* image, hipStream_t s);
-
-// The same for a ragged burst: samples packed back to back, clip c of lens[c] >= 1 samples (host array).  d_rows: device memory of
-// spectrogram_ragged_table_bytes(n_clips) bytes, filled by a copy enqueued on s ahead of the kernel.
-size_t spectrogram_ragged_table_bytes(int n_clips);
-void launch_spectrogram_ragged(const void* samples, int f32, int n_clips, const int* lens, int W, int H, const double* d_table,
-                               double wsum, double top_db, double range_db, uint8_t* image, void* d_rows, hipStream_t s);
+// samples: int16 PCM or (f32) float32 [n_clips][n], or the clips of a ragged burst packed back to back; d_table: spectrogram_table on
+// the device; wsum = the window's sum; image: uint8 [n_clips][H][W].  d_rows: spectrogram_table_bytes of device memory for a ragged
+// burst's SpecClip rows, filled by a copy enqueued on s ahead of the kernel (a uniform batch has none: 0 bytes, not read).  The
+// geometry has been validated by the caller (H = 2^k + 1, N within SPEC_N_MIN..SPEC_N_MAX).
+size_t spectrogram_table_bytes(const Clips& clips);
+void launch_spectrogram(const void* samples, int f32, const Clips& clips, int W, int H, const double* d_table, double wsum, double top_db,
+                        double range_db, uint8_t* image, void* d_rows, hipStream_t s);
 
 }  // namespace bnhip

@@ -182,22 +182,6 @@ std::vector<double> spectrogram_table(int N, const double* window) {
     return t;
 }
 
-// what a launch holds besides the clips' geometry
-static SpecParams spec_params(const void* samples, int W, int H, const double* d_table, double wsum, double top_db, double range_db,
-                              uint8_t* image) {
-    SpecParams p{};
-    p.samples = samples;
-    p.N = 2 * (H - 1);
-    p.tw = reinterpret_cast<const double2*>(d_table);
-    p.window = d_table + p.N;
-    p.image = image;
-    p.W = W; p.H = H;
-    p.fp = fft_passes_plan(p.N);
-    p.pscale = (2.0 / wsum) * (2.0 / wsum);
-    p.top_db = top_db; p.range_db = range_db;
-    return p;
-}
-
 template <bool RAGGED>
 static void spec_launch(const SpecParams& p, int f32, int n_clips, size_t lds, hipStream_t s) {
     const dim3 grid((p.W + p.T - 1) / p.T, n_clips);
@@ -210,34 +194,41 @@ static void spec_launch(const SpecParams& p, int f32, int n_clips, size_t lds, h
     }
 }
 
-void launch_spectrogram(const void* samples, int f32, int n_clips, int n, int W, int H, const double* d_table, double wsum,
-                        double top_db, double range_db, uint8_t* image, hipStream_t s) {
-    const SpecPlan q = spectrogram_plan(n, W, H);
-    SpecParams p = spec_params(samples, W, H, d_table, wsum, top_db, range_db, image);
-    p.n = n; p.K = q.K; p.T = q.T; p.F = q.F; p.span_cap = q.span_cap;
-    spec_launch<false>(p, f32, n_clips, q.lds, s);
-}
+size_t spectrogram_table_bytes(const Clips& clips) { return clips.lens ? ((size_t)clips.n_clips * sizeof(SpecClip) + 255) & ~(size_t)255 : 0; }
 
-size_t spectrogram_ragged_table_bytes(int n_clips) { return ((size_t)n_clips * sizeof(SpecClip) + 255) & ~(size_t)255; }
-
-void launch_spectrogram_ragged(const void* samples, int f32, int n_clips, const int* lens, int W, int H, const double* d_table,
-                               double wsum, double top_db, double range_db, uint8_t* image, void* d_rows, hipStream_t s) {
+void launch_spectrogram(const void* samples, int f32, const Clips& clips, int W, int H, const double* d_table, double wsum, double top_db,
+                        double range_db, uint8_t* image, void* d_rows, hipStream_t s) {
+    SpecParams p{};
+    p.samples = samples;
+    p.N = 2 * (H - 1);
+    p.tw = reinterpret_cast<const double2*>(d_table);
+    p.window = d_table + p.N;
+    p.image = image;
+    p.W = W; p.H = H;
+    p.fp = fft_passes_plan(p.N);
+    p.pscale = (2.0 / wsum) * (2.0 / wsum);
+    p.top_db = top_db; p.range_db = range_db;
+    if (!clips.lens) {
+        const SpecPlan q = spectrogram_plan(clips.n, W, H);
+        p.n = clips.n; p.K = q.K; p.T = q.T; p.F = q.F; p.span_cap = q.span_cap;
+        spec_launch<false>(p, f32, clips.n_clips, q.lds, s);
+        return;
+    }
     // the plan of every clip on the host; the launch's LDS is the largest any of them needs (T depends on N only)
-    std::vector<SpecClip> rows((size_t)n_clips);
-    SpecParams p = spec_params(samples, W, H, d_table, wsum, top_db, range_db, image);
+    std::vector<SpecClip> rows((size_t)clips.n_clips);
     size_t lds = 0;
     long long start = 0;
-    for (int c = 0; c < n_clips; c++) {
-        const SpecPlan q = spectrogram_plan(lens[c], W, H);
-        rows[c] = {start, lens[c], q.K, q.F, q.span_cap};
-        start += lens[c];
+    for (int c = 0; c < clips.n_clips; c++) {
+        const SpecPlan q = spectrogram_plan(clips.lens[c], W, H);
+        rows[c] = {start, clips.lens[c], q.K, q.F, q.span_cap};
+        start += clips.lens[c];
         lds = std::max(lds, q.lds);
         p.T = q.T;
     }
     // (a pageable source is staged before hipMemcpyAsync returns, so the host rows need not outlive the call)
     (void)hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(SpecClip), hipMemcpyHostToDevice, s);
     p.clips = static_cast<const SpecClip*>(d_rows);
-    spec_launch<true>(p, f32, n_clips, lds, s);
+    spec_launch<true>(p, f32, clips.n_clips, lds, s);
 }
 
 }  // namespace bnhip

@@ -18,6 +18,10 @@
  * the Go binding in birdnet-go_amd/go does so.
  * No entry point lets a C++ exception escape: allocation failure is BNHIP_E_NOMEM, anything else BNHIP_E_RUNTIME
  * ("never panic; any failure => fall back", internal/classifier/model_openvino.go:227-230).
+ *
+ * Where a host-pointer clip entry below says "one device allocation": the parts of a call of 2 MiB and more (clips, streams,
+ * images, workspaces) are carved from one allocation; each smaller part is a hipMalloc of its own, which the HIP runtime
+ * serves from blocks it keeps, with no driver call.
  */
 #ifndef BNHIP_H
 #define BNHIP_H
@@ -266,8 +270,8 @@ int bnhip_us_frame_cv_device(int device, const void* d_samples, int pcm16, int n
  *   image: uint8 [n_clips][height][width], row r = bin height - 1 - r (Nyquist on top).  All arithmetic is float64.
  * window: host table of N doubles, NULL = periodic Hann 0.5 - 0.5 cos(2 pi i / N); uploaded tables are cached per (device, N, contents).
  * size:   height = fftFriendlyHeight(width) (generator.go:115-123) and fft_size = N for a width in 1..4096.
- * pcm16:  host PCM in, host image out: one H2D copy, the kernels, one D2H copy, one synchronise.  rate_out == 0 or == rate_in renders
- *         at the source rate; otherwise the clips first pass through the one-shot resampler on the device (int16 in, float32 out,
+ * pcm16:  host PCM in, host image out: one device allocation, one H2D copy, the kernels, one D2H copy, one synchronise.  rate_out == 0
+ *         or == rate_in renders at the source rate; otherwise the clips first pass through the one-shot resampler on the device (int16 in, float32 out,
  *         the bnhip_resample_length(n, ...) samples bnhip_resample_f32 gives) - 24 000 Hz for the bird profile, 256 000 Hz for the bat
  *         profile (frequency_profile.go:13-16) - and nothing returns to the host in between.
  * device: d_samples (int16, or float32 with f32 != 0) and d_image are device memory; enqueued on hip_stream (NULL = default
@@ -333,8 +337,8 @@ int bnhip_spectrogram_png_pcm16(int device, const int16_t* pcm, int n_clips, int
  * The reference's callers pass (60, gate_fallback 1) for an export and (30, 0) for an upload.
  * measure:   measurements only (the plan fields are 0, factor 1, output_lufs = integrated_lufs); sub_energy (nullable) receives
  *            E as [n_clips][n / S] doubles.
- * normalize: out_pcm NULL = plan only.  pcm16: host memory in and out: one H2D copy, the kernels, one D2H copy of the results and
- *            of the output, one synchronise.
+ * normalize: out_pcm NULL = plan only.  pcm16: host memory in and out: one device allocation, one H2D copy, the kernels, one D2H
+ *            copy of the results and of the output, one synchronise.
  * device:    d_pcm, d_out_pcm (nullable), d_out and d_workspace are device memory, d_workspace at least
  *            bnhip_loudness_workspace_size bytes and 256-byte aligned; enqueued on hip_stream (NULL = default stream), not
  *            synchronised; the workspace is in use until the enqueued work has run.
@@ -377,7 +381,8 @@ int bnhip_loudness_normalize_device(int device, const int16_t* d_pcm, int n_clip
  *   factor rounded half away from zero and saturated, the rule of bnhip_loudness_*.
  *   output: the streams back to back; offsets[c] .. offsets[c + 1] is clip c's, offsets[n_clips] the bytes written.
  * max_bytes:      the worst-case output size (every frame VERBATIM); out_cap must be at least that.
- * encode_pcm16:   host memory in and out: one H2D copy, the kernels, a D2H copy of offsets, then of exactly offsets[n_clips] bytes.
+ * encode_pcm16:   host memory in and out: one device allocation, one H2D copy, the kernels, a D2H copy of offsets, then of exactly
+ *                 offsets[n_clips] bytes.  The fused bnhip_loudness_flac_pcm16 takes one allocation as well.
  * encode_device:  d_pcm, d_factor (nullable), d_out, d_offsets and d_workspace are device memory, d_workspace at least
  *                 bnhip_flac_workspace_size bytes and 256-byte aligned; enqueued on hip_stream (NULL = default stream), not
  *                 synchronised, nothing allocated; d_factor's values are the caller's business.
@@ -421,7 +426,7 @@ int bnhip_loudness_flac_lpc_pcm16(int device, const int16_t* pcm, int n_clips, i
  *   their q are equal, and agree to rounding otherwise.
  *   output: as the uniform entries': the streams back to back with offsets[n_clips + 1], the records [n_clips], and out_pcm packed
  *   like pcm.  bnhip_flac_ragged_max_bytes is the sum over c of bnhip_flac_max_bytes(1, lens[c], seek_interval).
- *   pcm16 entries: host memory in and out; all device memory of a call is one allocation (input, gained clips, output, offsets,
+ *   pcm16 entries: host memory in and out; the device memory of a call is one device allocation (input, gained clips, output, offsets,
  *   records and workspaces carved from it at 256-byte alignment).  normalize: out_pcm NULL = plan only, which is also how to
  *   measure (there is no ragged measure entry).
  *   device entries: as the uniform ones; the length tables (prefix sums computed on the host) are copied into the workspace with

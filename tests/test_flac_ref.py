@@ -266,6 +266,7 @@ def test_flac_argument_errors_before_any_device(built_lib):
         assert fn(n=0) == host.E_INVALID and b"n must be" in lib.bnhip_last_error()
         assert fn(seek=-1) == host.E_INVALID and b"seek_interval" in lib.bnhip_last_error()
         assert fn(out_cap=cap - 1) == host.E_INVALID and b"out_cap" in lib.bnhip_last_error()
+        assert lib.bnhip_last_error() == b"out_cap smaller than bnhip_flac_max_bytes"                        # (the ragged form names its own)
         assert fn(seek=100, out_cap=cap) == host.E_INVALID and b"out_cap" in lib.bnhip_last_error()       # the seek table counts
         assert fn() != host.BNHIP_OK and b"out_cap" not in lib.bnhip_last_error()                            # valid arguments reach the device check
     for fn in (pcm16, device):

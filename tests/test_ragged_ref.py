@@ -80,6 +80,7 @@ def test_errors_before_any_device(built_lib):
         assert run(w, lens=np.array([5, 0, 7], np.int32)) == host.E_INVALID and b"at least 1" in lib.bnhip_last_error(), w
         assert run(w, lens=np.array([5, -3], np.int32)) == host.E_INVALID and b"at least 1" in lib.bnhip_last_error(), w
         assert run(w, n_clips=0) == host.E_INVALID and b"n_clips" in lib.bnhip_last_error(), w
+        assert run(w, n_clips=65536) == host.E_INVALID and b"n_clips" in lib.bnhip_last_error(), w
         assert run(w, lens=huge) == host.E_INVALID and b"2^36" in lib.bnhip_last_error(), w
     # what the uniform entries reject
     for w in ("loud_ws", "loud_pcm16", "loud_device", "fused"):
@@ -91,12 +92,15 @@ def test_errors_before_any_device(built_lib):
         assert run(w, seek=-1) == host.E_INVALID and b"seek_interval" in lib.bnhip_last_error(), w
         assert run(w, lpc=9) == host.E_INVALID and b"lpc_order" in lib.bnhip_last_error(), w
         assert run(w, cap=sz(cap.value - 1)) == host.E_INVALID and b"out_cap" in lib.bnhip_last_error(), w
+        assert lib.bnhip_last_error() == b"out_cap smaller than bnhip_flac_ragged_max_bytes", w      # (each form names its own size entry)
         assert run(w, pcm=vp()) == host.E_INVALID and lib.bnhip_last_error() == b"NULL/empty argument", w
     assert run("flac_ws", lpc=-1) == host.E_INVALID and run("flac_max", seek=-1) == host.E_INVALID
     need = host.flac_ragged_workspace_size(good, 8)
     assert run("flac_device", lpc=8, ws=sz(need - 1)) == host.E_INVALID and b"workspace" in lib.bnhip_last_error()
+    assert lib.bnhip_last_error() == b"workspace smaller than bnhip_flac_ragged_workspace_size"
     need = host.loudness_ragged_workspace_size(good, 8000)
     assert run("loud_device", ws=sz(need - 1)) == host.E_INVALID and b"workspace" in lib.bnhip_last_error()
+    assert lib.bnhip_last_error() == b"workspace smaller than bnhip_loudness_ragged_workspace_size"
     bad = np.array([1.0, np.nan])
     assert lib.bnhip_flac_ragged_encode_pcm16(dev, p, ci(2), vp(good.ctypes.data), ci(8000), vp(bad.ctypes.data), ci(0), o, cap, f,
                                               ci(0)) == host.E_INVALID and b"factor" in lib.bnhip_last_error()
