@@ -5,24 +5,13 @@
 #include <algorithm>
 
 #include "block_scan.h"
+#include "pcm_sample.h"
 #include "ragged.h"
 
 namespace bnhip {
 
 // ------------------------------------------------------------------------------------------ k_frame_windows
-// One sample of the block as float32: internal/analysis/process.go:491-495 and internal/audiocore/convert/pcm.go:242-268, as
-// k_pcm16_to_f32 / k_pcm24_to_f32 / k_pcm32_to_f32 (frontend.hip) state them.
-template <int BITS> __device__ __forceinline__ float frame_sample(const char* p, long long i);
-template <> __device__ __forceinline__ float frame_sample<0>(const char* p, long long i) { return reinterpret_cast<const float*>(p)[i]; }
-template <> __device__ __forceinline__ float frame_sample<16>(const char* p, long long i) { return (float)reinterpret_cast<const int16_t*>(p)[i] / 32768.0f; }
-template <> __device__ __forceinline__ float frame_sample<24>(const char* p, long long i) {
-    const uint8_t* b = reinterpret_cast<const uint8_t*>(p) + 3 * i;
-    int32_t v = (int32_t)b[0] | ((int32_t)b[1] << 8) | ((int32_t)b[2] << 16);
-    if (v & 0x00800000) v |= ~0x00FFFFFF;
-    return (float)v / 8388608.0f;
-}
-template <> __device__ __forceinline__ float frame_sample<32>(const char* p, long long i) { return (float)reinterpret_cast<const int32_t*>(p)[i] / 2147483648.0f; }
-
+// (one sample of the block as float32: frame_sample, pcm_sample.h)
 // blockIdx.y = window of the launch, blockIdx.x strides over its samples
 template <int BITS>
 __global__ __launch_bounds__(256) void k_frame_windows(const char* __restrict__ block, WinView v, int n_samples, float* __restrict__ out) {

@@ -8,10 +8,13 @@
 
 #include "analyze.h"
 #include "api_model.h"
+#include "api_oneshot.h"
+#include "resample.h"
 
 using namespace bnhip;
 
 static_assert(sizeof(bnhip_detection) == 16 && sizeof(DetRow) == 16, "a detection row is 16 bytes");
+static_assert(sizeof(bnhip_recording) == 16, "a recording's description is 16 bytes");
 
 namespace bnhip {
 
@@ -55,16 +58,121 @@ int check_table(const int64_t* lengths, int n_recordings, int n_samples, int hop
     return BNHIP_OK;
 }
 
+// ---- recordings at their own rates and depths (the bnhip_analyze_mixed_* entries)
+// What the mixed entries add to a call: the recordings as they are in their files (the raw block), resampled and converted on the
+// device into the float32 slots that the chunk loop frames - `lengths` of analyze() are then the n_out, at the model's rate.
+struct RatePlan { int rate; int rec; ResamplePlan p; size_t tab_off; };     // rec: the first recording at that rate (for error texts)
+struct Mixed {
+    const bnhip_recording* recs = nullptr;
+    int model_rate = 0;
+    std::vector<int64_t> n_out;                   // [n_rec] samples at the model's rate
+    std::vector<RatePlan> plans;                  // the distinct rates that differ from the model's, ascending
+    std::vector<int> plan_of;                     // [n_rec] index into plans, -1: at the model's rate
+    long long n_tiles = 0;
+    bool plain = false;                           // every recording at the model's rate, one depth: the existing body as it is
+};
+
+// The phase tables of one set of rates, concatenated in one device buffer and kept (api_oneshot.h): a second call with the same
+// rates designs and uploads nothing.
+struct RateSetTable {
+    int device, model_rate;
+    std::vector<int> rates;                       // ascending; their [L][T] tables follow one another in d
+    float* d;
+};
+TableCache<RateSetTable> g_rate_tables;
+
+constexpr long long MIXED_MAX_LEN = (1ll << 31) - 1;
+
+// the recordings of a mixed call: every refusal that needs neither the handle nor a device; fills mx
+int mixed_check(const bnhip_recording* recs, int n_recordings, int model_rate, Mixed* mx) {
+    if (!recs) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (n_recordings < 1 || n_recordings > 65535) return set_err(BNHIP_E_INVALID, "n_recordings must be in [1, 65535]");
+    if (model_rate <= 0) return set_err(BNHIP_E_INVALID, "model_rate must be positive");
+    mx->recs = recs; mx->model_rate = model_rate;
+    mx->n_out.resize(n_recordings); mx->plan_of.assign(n_recordings, -1);
+    long long total_in = 0, total_out = 0;
+    bool plain = true;
+    for (int r = 0; r < n_recordings; r++) {
+        const bnhip_recording& q = recs[r];
+        const std::string who = "recording " + std::to_string(r) + ": ";
+        if (q.bits_per_sample != 0 && q.bits_per_sample != 16 && q.bits_per_sample != 24 && q.bits_per_sample != 32)
+            return set_err(BNHIP_E_INVALID, who + "unsupported bit depth: " + std::to_string(q.bits_per_sample) + " (supported: 0 = float32, 16, 24, 32)");
+        if (q.rate <= 0) return set_err(BNHIP_E_INVALID, who + "the sample rate must be positive");
+        if (q.length < 1) return set_err(BNHIP_E_INVALID, "every recording needs at least one sample");
+        if (q.length > MIXED_MAX_LEN) return set_err(BNHIP_E_INVALID, who + "2^31 samples or more");
+        // ceil(length * L / M) in 64 bits (bnhip_resample_length): length < 2^31 and L < 2^31
+        const long long no = q.rate == model_rate ? (long long)q.length : resample_plan(q.rate, model_rate, nullptr).end(q.length);
+        if (no > MIXED_MAX_LEN) return set_err(BNHIP_E_INVALID, who + "2^31 samples or more at the model's rate");
+        if (q.length > ANALYZE_MAX_SAMPLES - total_in || no > ANALYZE_MAX_SAMPLES - total_out)
+            return set_err(BNHIP_E_INVALID, "burst of 2^36 samples or more");
+        total_in += q.length; total_out += no;
+        mx->n_out[r] = no;
+        mx->n_tiles += resample_slot_tiles(no);
+        plain = plain && q.rate == model_rate && q.bits_per_sample == recs[0].bits_per_sample;
+    }
+    if (mx->n_tiles > INT_MAX) return set_err(BNHIP_E_INVALID, "more resample tiles than a 31-bit grid");
+    mx->plain = plain;
+    if (plain) return BNHIP_OK;
+    std::vector<int> rates;
+    for (int r = 0; r < n_recordings; r++) if (recs[r].rate != model_rate) rates.push_back(recs[r].rate);
+    std::sort(rates.begin(), rates.end());
+    rates.erase(std::unique(rates.begin(), rates.end()), rates.end());
+    for (int rate : rates) mx->plans.push_back(RatePlan{rate, -1, ResamplePlan{}, 0});
+    for (int r = 0; r < n_recordings; r++) {
+        if (recs[r].rate == model_rate) continue;
+        const int pi = (int)(std::lower_bound(rates.begin(), rates.end(), recs[r].rate) - rates.begin());
+        mx->plan_of[r] = pi;
+        if (mx->plans[pi].rec < 0) mx->plans[pi].rec = r;
+    }
+    return BNHIP_OK;
+}
+
+// the geometry of every rate of the call; a phase table that does not fit LDS is refused here, before any allocation
+int mixed_plans(Mixed* mx) {
+    size_t off = 0;
+    for (RatePlan& rp : mx->plans) {
+        rp.p = resample_plan(rp.rate, mx->model_rate, nullptr);
+        if (!rp.p.fits_lds())
+            return set_err(BNHIP_E_UNSUPPORTED, "recording " + std::to_string(rp.rec) + ": resampling " + std::to_string(rp.rate) + " Hz to " +
+                                                    std::to_string(mx->model_rate) + " Hz needs a phase table larger than LDS");
+        rp.tab_off = off;
+        off += (size_t)rp.p.L * rp.p.T;
+    }
+    // (a descriptor states a table's offset in an int: tens of thousands of distinct rates with tables near the LDS limit)
+    if (off > (size_t)INT_MAX) return set_err(BNHIP_E_UNSUPPORTED, "the call's phase tables exceed 2^31 floats");
+    return BNHIP_OK;
+}
+
+// the call's concatenated phase tables on the current device, from the cache or designed now; -> NULL: the upload failed
+const float* mixed_tables(const Mixed& mx, int device, const TableLock& lock) {
+    std::vector<int> rates;
+    for (const RatePlan& rp : mx.plans) rates.push_back(rp.rate);
+    const RateSetTable* t = g_rate_tables.find(
+        lock, [&](const RateSetTable& e) { return e.device == device && e.model_rate == mx.model_rate && e.rates == rates; },
+        [&](RateSetTable& e) {
+            std::vector<float> all, one;
+            for (const RatePlan& rp : mx.plans) {
+                (void)resample_plan(rp.rate, mx.model_rate, &one);
+                all.insert(all.end(), one.begin(), one.end());
+            }
+            e.device = device; e.model_rate = mx.model_rate; e.rates = rates;
+            e.d = upload_table(all);
+            return e.d != nullptr;
+        });
+    return t ? t->d : nullptr;
+}
+
 #define AN_HIP(call, what)                                                                          \
     do {                                                                                            \
         hipError_t e_ = (call);                                                                     \
         if (ok && e_ != hipSuccess) { ok = false; err = std::string(what) + ": " + hipGetErrorString(e_); } \
     } while (0)
 
-// bnhip_analyze_pcm_topk, and with `det` the detection rows behind it
+// bnhip_analyze_pcm_topk, and with `det` the detection rows behind it.  mx (the mixed entries): pcm holds the recordings as mx
+// describes them, and bits / lengths state the float32 slots they are resampled into - what the chunk loop frames.
 int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, int n_recordings, int hop, int64_t min_tail, int activation,
             double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold, bnhip_detection* out_rows, size_t cap,
-            size_t* n_out) {
+            size_t* n_out, Mixed* mx = nullptr) {
     if (!m || !pcm || !lengths) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (det ? (!n_out || (cap && !out_rows)) : (!out_conf || !out_idx)) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (bits != 0 && bits != 16 && bits != 24 && bits != 32)
@@ -76,6 +184,7 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     if (m->engs.size() > 1) return set_err(BNHIP_E_INVALID, "file analysis runs on one device; use a single-device handle");
     if (e.device < 0) return set_err(BNHIP_E_INVALID, "plan-only model cannot run");
     if ((size_t)e.n_classes * 4 > TOPK_LDS_MAX) return set_err(BNHIP_E_UNSUPPORTED, "too many classes for the LDS top-k");
+    if (mx) if (int rc = mixed_plans(mx)) return rc;
     std::vector<long long> table((size_t)n_recordings * 3 + 1);       // first[n + 1], then slot[n][2]
     long long* first = table.data();
     long long* slot = first + n_recordings + 1;
@@ -88,17 +197,40 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
         slot[2 * r] = (long long)block_bytes; slot[2 * r + 1] = lengths[r];
         block_bytes += analyze_slot_bytes(lengths[r], bits);
     }
+    // mixed: the raw block (every recording as it is in its file, from a 16-byte line on), a descriptor per recording and the tile prefix
+    std::vector<ResampleSlotDesc> desc;
+    std::vector<long long> tile0;
+    size_t raw_bytes = 0, rs_lds = 0;
+    if (mx) {
+        desc.resize(n_recordings); tile0.assign((size_t)n_recordings + 1, 0);
+        for (int r = 0; r < n_recordings; r++) {
+            const bnhip_recording& q = mx->recs[r];
+            ResampleSlotDesc& ds = desc[r];
+            ds.in_off = (long long)raw_bytes; ds.out_off = slot[2 * r];
+            ds.n_in = (int)q.length; ds.n_out = (int)lengths[r]; ds.bits = q.bits_per_sample;
+            ds.L = ds.M = ds.T = ds.half = ds.tab_off = 0;
+            if (mx->plan_of[r] >= 0) {
+                const RatePlan& rp = mx->plans[mx->plan_of[r]];
+                ds.L = rp.p.L; ds.M = rp.p.M; ds.T = rp.p.T; ds.half = rp.p.half; ds.tab_off = (int)rp.tab_off;
+                rs_lds = std::max(rs_lds, resample_lds(rp.p.L, rp.p.M, rp.p.T));
+            }
+            raw_bytes += ((size_t)q.length * analyze_sample_bytes(q.bits_per_sample) + 15) / 16 * 16;
+            tile0[r + 1] = tile0[r] + resample_slot_tiles(lengths[r]);
+        }
+    }
     if (hipSetDevice(e.device) != hipSuccess) return set_err(BNHIP_E_RUNTIME, "hipSetDevice failed");
     // whatever an earlier asynchronous call still has queued on the engine's streams finishes first (as host_run does)
     e.sync_contexts();
     if (e.stream) hipStreamSynchronize(e.stream);
     // one allocation: recordings | tables | top-k confidences | top-k indices | detection scratch | row count | rows
+    // (mixed: | raw block | descriptors, tile prefix)
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t table_bytes = table.size() * 8, tk_bytes = (size_t)W * kk * 4;
     const size_t rows_cap = det ? std::min(cap, (size_t)W * kk) : 0;
     const size_t o_table = up(block_bytes), o_conf = o_table + up(table_bytes), o_idx = o_conf + up(tk_bytes), o_scr = o_idx + up(tk_bytes);
     const size_t o_total = o_scr + (det ? up(detections_scratch_bytes(W)) : 0), o_rows = o_total + (det ? 256 : 0);
-    const size_t all_bytes = o_rows + up(rows_cap * sizeof(DetRow));
+    const size_t o_raw = o_rows + up(rows_cap * sizeof(DetRow)), o_desc = o_raw + up(raw_bytes);
+    const size_t desc_bytes = desc.size() * sizeof(ResampleSlotDesc), all_bytes = o_desc + (mx ? up(desc_bytes) + up(tile0.size() * 8) : 0);
     char* d = nullptr;
     if (hipMalloc((void**)&d, all_bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -106,15 +238,27 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     }
     bool ok = true;
     std::string err;
-    const size_t sb = analyze_sample_bytes(bits);
-    // the slots' zero fill, then one copy per recording into its slot
-    AN_HIP(hipMemsetAsync(d, 0, o_table, e.stream), "memset");
+    // the slots' zero fill, then one copy per recording into its slot (mixed: into the raw block; k_resample_slots writes every
+    // slot whole, its zeros included)
+    if (!mx) AN_HIP(hipMemsetAsync(d, 0, o_table, e.stream), "memset");
     const char* src = static_cast<const char*>(pcm);
     for (int r = 0; ok && r < n_recordings; r++) {
-        AN_HIP(hipMemcpyAsync(d + slot[2 * r], src, (size_t)lengths[r] * sb, hipMemcpyHostToDevice, e.stream), "H2D copy");
-        src += (size_t)lengths[r] * sb;
+        const size_t bytes = mx ? (size_t)mx->recs[r].length * analyze_sample_bytes(mx->recs[r].bits_per_sample) : (size_t)lengths[r] * analyze_sample_bytes(bits);
+        AN_HIP(hipMemcpyAsync(mx ? d + o_raw + desc[r].in_off : d + slot[2 * r], src, bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
+        src += bytes;
     }
     AN_HIP(hipMemcpyAsync(d + o_table, table.data(), table_bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
+    if (mx) {
+        // (the lock is held from the tables' lookup until the launch that reads them is enqueued, api_oneshot.h)
+        TableLock lock(g_rate_tables.mu);
+        const float* d_tables = mx->plans.empty() ? nullptr : mixed_tables(*mx, e.device, lock);
+        if (ok && !mx->plans.empty() && !d_tables) { ok = false; err = "phase table upload failed"; }
+        char* d_tile0 = d + o_desc + up(desc_bytes);
+        AN_HIP(hipMemcpyAsync(d + o_desc, desc.data(), desc_bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
+        AN_HIP(hipMemcpyAsync(d_tile0, tile0.data(), tile0.size() * 8, hipMemcpyHostToDevice, e.stream), "H2D copy");
+        if (ok) launch_resample_slots(d + o_raw, d, d_tables, reinterpret_cast<const ResampleSlotDesc*>(d + o_desc),
+                                      reinterpret_cast<const long long*>(d_tile0), n_recordings, tile0[n_recordings], rs_lds, e.stream);
+    }
     WinView view;
     view.first = reinterpret_cast<const long long*>(d + o_table);
     view.slot = view.first + n_recordings + 1;
@@ -185,6 +329,49 @@ int bnhip_analyze_pcm(bnhip_model* m, const void* pcm, int bits_per_sample, cons
     BN_GUARD_BEGIN
     return analyze(m, pcm, bits_per_sample, lengths, n_recordings, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, threshold,
                    out, cap, n_out);
+    BN_GUARD_END((void)0)
+}
+
+// ---- recordings at their own rates and depths
+long long bnhip_analyze_mixed_windows(const bnhip_recording* recs, int n_recordings, int model_rate, int n_samples, int hop, int64_t min_tail,
+                                      int64_t* first_window, int64_t* resampled_length) {
+    BN_GUARD_BEGIN
+    if (!first_window) return set_err(BNHIP_E_INVALID, "NULL argument");
+    Mixed mx;
+    if (int rc = mixed_check(recs, n_recordings, model_rate, &mx)) return rc;
+    if (int rc = check_table(mx.n_out.data(), n_recordings, n_samples, hop, min_tail)) return rc;
+    std::vector<long long> len64(mx.n_out.begin(), mx.n_out.end()), first((size_t)n_recordings + 1);
+    const long long W = analyze_windows(len64.data(), n_recordings, n_samples, hop, min_tail, first.data());
+    std::copy(first.begin(), first.end(), first_window);
+    if (resampled_length) std::copy(mx.n_out.begin(), mx.n_out.end(), resampled_length);
+    return W;
+    BN_GUARD_END((void)0)
+}
+
+// the two device entries: a burst that the existing entries take as it is goes to them
+static int analyze_mixed(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate, int hop, int64_t min_tail,
+                         int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold,
+                         bnhip_detection* out_rows, size_t cap, size_t* n_out) {
+    Mixed mx;
+    if (int rc = mixed_check(recs, n_recordings, model_rate, &mx)) return rc;
+    return analyze(m, pcm, mx.plain ? recs[0].bits_per_sample : 0, mx.n_out.data(), n_recordings, hop, min_tail, activation, sensitivity, k, out_conf,
+                   out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx);
+}
+
+int bnhip_analyze_mixed_pcm_topk(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate, int hop,
+                                 int64_t min_tail, int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx) {
+    BN_GUARD_BEGIN
+    return analyze_mixed(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, out_conf, out_idx, false, 0.f, nullptr, 0,
+                         nullptr);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_analyze_mixed_pcm(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate, int hop,
+                            int64_t min_tail, int activation, double sensitivity, int k, float threshold, bnhip_detection* out, size_t cap,
+                            size_t* n_out) {
+    BN_GUARD_BEGIN
+    return analyze_mixed(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, threshold, out, cap,
+                         n_out);
     BN_GUARD_END((void)0)
 }
 

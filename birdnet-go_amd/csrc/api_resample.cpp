@@ -10,40 +10,6 @@
 
 using namespace bnhip;
 
-namespace {
-
-// The polyphase geometry of one rate pair (resample.hip): L / M = rate_out / rate_in in lowest terms, T taps per phase and the
-// filter half-length.  Output i's newest input is n0(i) = floor((i*M + half) / L); indices count from the stream start.
-struct ResamplePlan {
-    int L = 1, M = 1, T = 0, half = 0;
-    // outputs computable once n_total inputs are known: every i whose newest tap n0(i) < n_total
-    long long ready(long long n_total) const {
-        const long long num = n_total * L - half;
-        return num <= 0 ? 0 : (num + M - 1) / M;
-    }
-    // EstimateOutput analogue (resample.go:83-88): an upper bound for any call, whatever the state
-    long long estimate(long long n_in) const { return n_in <= 0 ? 0 : (n_in * L + M - 1) / M + 1; }
-    // outputs of n inputs followed by zeros: the one-shot length, and where a flush ends
-    long long end(long long n) const { return (n * L + M - 1) / M; }
-    // the first input the next call still needs once the outputs before i_end are out: n0(i_end) - (T-1), within [n_base, n_after]
-    long long keep_from(long long i_end, long long n_base, long long n_after) const {
-        return std::min(std::max((i_end * M + half) / L - (T - 1), n_base), n_after);
-    }
-    bool fits_lds() const { return resample_lds(L, M, T) <= RESAMPLE_LDS_MAX; }
-};
-
-// rate_in, rate_out > 0.  With a table the filter is designed too (T, half and the [L][T] phase table); without, only L / M are set.
-ResamplePlan resample_plan(int rate_in, int rate_out, std::vector<float>* table) {
-    const int g = std::gcd(rate_in, rate_out);
-    ResamplePlan p;
-    p.L = rate_out / g;
-    p.M = rate_in / g;
-    if (table) resample_design(p.L, p.M, RESAMPLE_BETA, RESAMPLE_HALF_FACTOR, table, &p.T, &p.half);
-    return p;
-}
-
-}  // namespace
-
 // Streaming resampler state (Resampler, internal/audiocore/resample/resample.go:44-52): the polyphase filter's input
 // history lives on the device between calls so that any chunking of a stream produces the samples of one call over the
 // whole stream, bit for bit.

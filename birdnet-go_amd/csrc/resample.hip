@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "pcm_sample.h"
 #include "ragged.h"
 #include "resample.h"
 
@@ -171,6 +172,79 @@ int launch_resample_ragged(const int16_t* d_in, float* d_out, const float* d_tab
     hipLaunchKernelGGL(k_resample_ragged, dim3((unsigned)tile0[n_clips]), dim3(256), lds, s, d_in, d_out, d_table, d, d + n_clips + 1,
                        d + 2 * ((size_t)n_clips + 1), n_clips, L, M, T, half);
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ slot form
+// Recordings at their own rates and depths -> float32 slots at the model's rate (ResampleSlotDesc, resample.h), one launch for the
+// burst: a block takes one tile of RESAMPLE_SLOT_TILE outputs of one recording, found in the flat tile list as k_resample_ragged
+// finds its clip.  The recording's phase table is staged once per block and serves the tile's 256-output sub-tiles one after the
+// other; a sub-tile stages its input span - converted in the load, zeros outside the recording - and computes as resample_tile does:
+// the same p, the same newest input and the fmaf chain over the same taps in the same order, so the bits are k_resample<false, false>'s
+// on the converted recording.  The slot's tail up to a whole quad is written as zeros here (the framed min/max launch loads quads).
+template <int BITS>
+__device__ __forceinline__ void resample_slot_tile(const char* __restrict__ in, float* __restrict__ out, const float* __restrict__ table,
+                                                   const ResampleSlotDesc& d, long long i0) {
+    const long long n_pad = ((long long)d.n_out + 3) & ~3ll;
+    const long long i_end = min(n_pad, i0 + RESAMPLE_SLOT_TILE);
+    if (d.L == 0) {                               // at the model's rate: converted only
+        for (long long i = i0 + threadIdx.x; i < i_end; i += 256) out[i] = i < d.n_out ? frame_sample<BITS>(in, i) : 0.0f;
+        return;
+    }
+    extern __shared__ float sm[];
+    const int L = d.L, M = d.M, T = d.T;
+    float* tab = sm;                              // [L*T]
+    float* xs = sm + L * T;                       // input span of one sub-tile
+    for (int k = threadIdx.x; k < L * T; k += 256) tab[k] = table[k];
+    // (a sub-tile always holds an output: n_pad is the first multiple of 4 from n_out on, and s0 is one)
+    for (long long s0 = i0; s0 < i_end; s0 += 256) {
+        const long long s1 = min((long long)d.n_out, s0 + 256);
+        const long long pos0 = s0 * M + d.half;
+        const long long q0 = pos0 / L;
+        const unsigned r0 = (unsigned)(pos0 % L);
+        const long long lo = q0 - (T - 1);
+        const int span = (int)(((s1 - 1) * M + d.half) / L - lo + 1);
+        __syncthreads();                          // the sub-tile in front has read its span
+        for (int k = threadIdx.x; k < span; k += 256) {
+            const long long n = lo + k;
+            xs[k] = n >= 0 && n < d.n_in ? frame_sample<BITS>(in, n) : 0.0f;
+        }
+        __syncthreads();
+        const long long i = s0 + threadIdx.x;
+        if (i < s1) {
+            // pos = pos0 + threadIdx.x * M = q0 * L + rem; a plan that fits LDS has L <= 38 400 and 255 * M / L < 38 400, so rem < 2^31
+            const unsigned rem = r0 + threadIdx.x * (unsigned)M;
+            const int n0 = T - 1 + (int)(rem / (unsigned)L);      // index of the newest input in xs
+            const float* tp = tab + (rem % (unsigned)L) * T;
+            float acc = 0.0f;
+            for (int t = 0; t < T; t++) acc = fmaf(xs[n0 - t], tp[t], acc);
+            out[i] = acc;
+        } else if (i < i_end) {
+            out[i] = 0.0f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_resample_slots(const char* __restrict__ raw, char* __restrict__ slots, const float* __restrict__ tables,
+                                                        const ResampleSlotDesc* __restrict__ desc, const long long* __restrict__ tile0,
+                                                        int n_rec) {
+    const int r = ragged_clip(tile0, n_rec, (long long)blockIdx.x);
+    const ResampleSlotDesc d = desc[r];
+    const long long i0 = ((long long)blockIdx.x - tile0[r]) * RESAMPLE_SLOT_TILE;
+    const char* in = raw + d.in_off;
+    float* out = reinterpret_cast<float*>(slots + d.out_off);
+    const float* table = tables + d.tab_off;
+    if (d.bits == 16) resample_slot_tile<16>(in, out, table, d, i0);
+    else if (d.bits == 24) resample_slot_tile<24>(in, out, table, d, i0);
+    else if (d.bits == 32) resample_slot_tile<32>(in, out, table, d, i0);
+    else resample_slot_tile<0>(in, out, table, d, i0);
+}
+
+void launch_resample_slots(const void* d_raw, void* d_slots, const float* d_tables, const ResampleSlotDesc* d_desc, const long long* d_tile0,
+                           int n_rec, long long n_tiles, size_t lds, hipStream_t s) {
+    if (n_rec <= 0 || n_tiles <= 0) return;
+    lds_limit_once<&k_resample_slots>(160 * 1024);
+    hipLaunchKernelGGL(k_resample_slots, dim3((unsigned)n_tiles), dim3(256), lds, s, static_cast<const char*>(d_raw), static_cast<char*>(d_slots),
+                       d_tables, d_desc, d_tile0, n_rec);
 }
 
 // ------------------------------------------------------------------------------------------------ bank form

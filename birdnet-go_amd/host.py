@@ -58,7 +58,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_flac_spectrogram_png", "bnhip_denoise_workspace_size", "bnhip_denoise_device", "bnhip_denoise_pcm16",
            "bnhip_process_pcm16", "bnhip_denoise_ragged_workspace_size", "bnhip_denoise_ragged_device", "bnhip_denoise_ragged_pcm16",
            "bnhip_process_ragged_pcm16", "bnhip_process_spectrogram_png_ragged_pcm16", "bnhip_analyze_windows",
-           "bnhip_analyze_pcm_topk", "bnhip_analyze_pcm"]
+           "bnhip_analyze_pcm_topk", "bnhip_analyze_pcm", "bnhip_analyze_mixed_windows", "bnhip_analyze_mixed_pcm_topk",
+           "bnhip_analyze_mixed_pcm"]
 
 
 class HipError(RuntimeError):
@@ -130,8 +131,44 @@ def _analyze_protos(lib):
     return lib
 
 
+def _analyze_mixed_protos(lib):
+    """... and of the entries for recordings at their own rates and depths (apart, so that the entries above go on working on a
+    library that predates these)."""
+    _analyze_protos(lib)
+    lib.bnhip_analyze_mixed_windows.restype = C.c_longlong
+    lib.bnhip_analyze_mixed_windows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.bnhip_analyze_mixed_pcm_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double,
+                                                 C.c_int, C.c_void_p, C.c_void_p]
+    lib.bnhip_analyze_mixed_pcm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double,
+                                            C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    return lib
+
+
 # one row of bnhip_analyze_pcm (bnhip_detection)
 DETECTION = np.dtype([("recording", "<i4"), ("window", "<i4"), ("class_index", "<i4"), ("confidence", "<f4")])
+# one recording of the mixed entries (bnhip_recording): samples at its own rate, the rate, the depth (0 = float32)
+RECORDING = np.dtype([("length", "<i8"), ("rate", "<i4"), ("bits_per_sample", "<i4")])
+
+
+def recordings(lengths, rates, depths):
+    """-> the RECORDING table of recordings of `lengths` samples at `rates` Hz and `depths` bits (scalars are broadcast)."""
+    ln = np.asarray(lengths, np.int64).reshape(-1)
+    recs = np.zeros(ln.size, RECORDING)
+    recs["length"], recs["rate"], recs["bits_per_sample"] = ln, rates, depths
+    return recs
+
+
+def analyze_mixed_windows(recs, model_rate, n_samples, hop, min_tail=0):
+    """bnhip_analyze_mixed_windows (host only): recordings (a RECORDING table) at their own rates, framed at model_rate.
+    -> (first_window int64 [n + 1], resampled_length int64 [n]: each recording's samples at model_rate)."""
+    lib = _analyze_mixed_protos(load_library())
+    recs = np.ascontiguousarray(recs, RECORDING).reshape(-1)
+    first, n_out = np.zeros(recs.size + 1, np.int64), np.zeros(recs.size, np.int64)
+    w = lib.bnhip_analyze_mixed_windows(recs.ctypes.data if recs.size else None, recs.size, int(model_rate), int(n_samples), int(hop),
+                                        int(min_tail), first.ctypes.data, n_out.ctypes.data)
+    if w < 0:
+        _check(lib, int(w))
+    return first, n_out
 
 
 def analyze_windows(lengths, n_samples, hop, min_tail=0):
@@ -380,6 +417,44 @@ class HipClassifier:
         _check(self._lib, self._lib.bnhip_analyze_pcm(self._h, x.ctypes.data, bit_depth, ln.ctypes.data, ln.size, int(hop), int(min_tail),
                                                       activation, sensitivity, k, float(threshold), rows.ctypes.data if cap else None,
                                                       int(cap), C.byref(n)))
+        return rows[:min(int(cap), n.value)], n.value
+
+    def _analyze_mixed_args(self, raw, recs):
+        self._alive()
+        _analyze_mixed_protos(self._lib)
+        recs = np.ascontiguousarray(recs, RECORDING).reshape(-1)
+        x = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
+        bad = ~np.isin(recs["bits_per_sample"], (0, 16, 24, 32))
+        if bad.any():
+            raise HipError(E_INVALID, f"unsupported bit depth: {int(recs['bits_per_sample'][bad][0])} (supported: 0 = float32, 16, 24, 32)")
+        want = int((recs["length"] * np.where(recs["bits_per_sample"] == 0, 4, recs["bits_per_sample"] // 8)).sum())
+        if x.size != want:
+            raise HipError(E_INVALID, f"input size mismatch: the recordings hold {want} bytes, got {x.size} bytes")
+        return x, recs
+
+    def analyze_mixed_pcm_topk(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0):
+        """bnhip_analyze_mixed_pcm_topk: recordings at their own rates and depths (a RECORDING table; their bytes packed back to
+        back as they are in their files) in, the top-k of every overlapping window at model_rate out - resampled, converted and
+        framed on the device.  hop and min_tail count samples at model_rate.  -> (conf [W, k], idx [W, k], first_window)."""
+        x, recs = self._analyze_mixed_args(raw, recs)
+        first, _ = analyze_mixed_windows(recs, model_rate, self.n_samples, hop, min_tail)
+        kk, w = min(k, self._n_classes), int(first[-1])
+        conf = np.empty((w, kk), np.float32)
+        idx = np.empty((w, kk), np.int32)
+        _check(self._lib, self._lib.bnhip_analyze_mixed_pcm_topk(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
+                                                                 int(min_tail), activation, sensitivity, k, conf.ctypes.data, idx.ctypes.data))
+        return conf, idx, first
+
+    def analyze_mixed_pcm(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
+        """bnhip_analyze_mixed_pcm: the same call, answered as detection rows, as analyze_pcm answers.  -> (rows, total)."""
+        x, recs = self._analyze_mixed_args(raw, recs)
+        if cap is None:
+            cap = int(analyze_mixed_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]) * min(k, self._n_classes)
+        rows = np.zeros(int(cap), DETECTION)
+        n = C.c_size_t(0)
+        _check(self._lib, self._lib.bnhip_analyze_mixed_pcm(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
+                                                            int(min_tail), activation, sensitivity, k, float(threshold),
+                                                            rows.ctypes.data if cap else None, int(cap), C.byref(n)))
         return rows[:min(int(cap), n.value)], n.value
 
     # ---- plumbing

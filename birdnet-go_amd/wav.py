@@ -108,7 +108,7 @@ def frame_clips(samples, sample_rate, clip_seconds=3.0, overlap_seconds=0.0, min
 
 
 def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0,
-                 model_rate=48000, device=0, device_framing=False):
+                 model_rate=48000, device=0, device_framing=False, device_resample=False):
     """File analysis = read -> (resample to the model's rate) -> frame -> batched predict_topk.
     Returns rows (start_s, end_s, label|index, confidence).
 
@@ -118,9 +118,11 @@ def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds
     `analysis/buffer_consumer.go:118,192`); window times are in seconds of audio, whatever the file's rate.
 
     device_framing=True: the same rows from one `bnhip_analyze_pcm` call - the file's PCM bytes go to the device as they are
-    and the windows are framed there (a resampled file goes as float32)."""
+    and the windows are framed there (a resampled file goes as float32; with device_resample=True it too goes as it is and is
+    resampled on the device, see analyze_files)."""
     if device_framing:
-        return analyze_files([path], classifier, labels, sensitivity, overlap_seconds, top_k, threshold, model_rate, device)[0]
+        return analyze_files([path], classifier, labels, sensitivity, overlap_seconds, top_k, threshold, model_rate, device,
+                             device_resample=device_resample)[0]
     s, rate, _ = read_wav(path)
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
@@ -141,16 +143,25 @@ def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds
 
 
 def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
-                  device=0):
+                  device=0, device_resample=False):
     """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
     path, each what analyze_file returns for that file.  The files' PCM bytes are sent as they are when all of them are at the
     model's rate and share one bit depth; otherwise every file goes as float32 (converted, and resampled where its rate differs,
-    exactly as analyze_file does)."""
+    exactly as analyze_file does).
+
+    device_resample=True: every file's bytes go as they are, whatever its rate and depth, in one `bnhip_analyze_mixed_pcm` call
+    that resamples and converts them on the device - the same rows."""
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
     pcm = [read_wav_pcm(p) for p in paths]
     depths = {bits for _, _, bits in pcm}
-    if len(depths) == 1 and all(rate == model_rate for _, rate, _ in pcm):
+    recs = None
+    if device_resample:
+        from . import host
+        bufs = [raw for raw, _, _ in pcm]
+        lengths = [len(raw) // (bits // 8) for raw, _, bits in pcm]
+        recs = host.recordings(lengths, [rate for _, rate, _ in pcm], [bits for _, _, bits in pcm])
+    elif len(depths) == 1 and all(rate == model_rate for _, rate, _ in pcm):
         bits, bufs = depths.pop(), [raw for raw, _, _ in pcm]
         lengths = [len(raw) // (bits // 8) for raw in bufs]
     else:
@@ -173,7 +184,10 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     t32 = np.float32(threshold)
     if float(t32) < threshold:
         t32 = np.nextafter(t32, np.float32(np.inf))
-    det, _ = classifier.analyze_pcm(b"".join(bufs), bits, lengths, hop, min_tail, k=top_k, sensitivity=sensitivity, threshold=float(t32))
+    if recs is not None:
+        det, _ = classifier.analyze_mixed_pcm(b"".join(bufs), recs, model_rate, hop, min_tail, k=top_k, sensitivity=sensitivity, threshold=float(t32))
+    else:
+        det, _ = classifier.analyze_pcm(b"".join(bufs), bits, lengths, hop, min_tail, k=top_k, sensitivity=sensitivity, threshold=float(t32))
     out = [[] for _ in paths]
     for r, w, j, c in zip(det["recording"], det["window"], det["class_index"], det["confidence"]):
         start = np.float64(int(w) * hop) / model_rate

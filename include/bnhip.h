@@ -245,6 +245,39 @@ int bnhip_analyze_pcm(bnhip_model* m, const void* pcm, int bits_per_sample, cons
                       int64_t min_tail, int activation, double sensitivity, int k, float threshold, bnhip_detection* out,
                       size_t cap, size_t* n_out);
 
+/* File analysis of recordings at their own sample rates and bit depths: a directory of field recordings (32, 44.1, 96, 192, 250,
+ * 384 kHz; 16- and 24-bit files side by side) in one call.  The reference resamples file input to the model's rate before analysis
+ * (internal/audiocore/resample/resample.go:57-172; call sites analysis/buffer_consumer.go:118,192) and converts the PCM depths as
+ * audiocore/convert/pcm.go:206-268; here both happen on the device, between the upload and the framing, and the resampled audio
+ * never exists on the host.
+ *   recs     One bnhip_recording per recording: length in samples at its own `rate`, bits_per_sample 0 = float32, or 16 / 24 / 32 as
+ *            in bnhip_analyze_pcm.  pcm holds recording r in length * bytes-per-sample bytes, directly after recording r - 1.
+ *            Recording r becomes n_out[r] = ceil(length * L / M) samples at model_rate (L / M = model_rate / rate in lowest terms:
+ *            bnhip_resample_length in 64 bits; equal rates give n_out = length), each the value bnhip_resample_f32 computes from
+ *            the recording converted to float32, bit for bit.  hop, min_tail, the model's clip and every `window` of a detection
+ *            row count samples at model_rate, and the window table is bnhip_analyze_windows' over n_out.
+ *   windows  Host only, needs no device: that table.  n_samples is the window; resampled_length (may be NULL): [n_recordings], the
+ *            n_out.  returns the total W (>= 1) or a negative BNHIP_E_*.
+ *   pcm_topk / pcm  What bnhip_analyze_pcm_topk / bnhip_analyze_pcm answer for the float32 recordings at model_rate, bit for bit.
+ *            One H2D copy per recording, one resample-and-convert launch for the burst, then the same chunks.  A burst whose
+ *            recordings are all at model_rate and share one depth IS the bnhip_analyze_pcm call: no second block, no extra launch.
+ * BNHIP_E_INVALID (nothing written, the handle stays usable): everything bnhip_analyze_pcm refuses (the 2^36-sample limit holds for
+ * the recordings as they come and as they are at model_rate), a rate <= 0, model_rate <= 0, an unknown depth in any recording, a
+ * length or an n_out of 2^31 or more.  BNHIP_E_UNSUPPORTED, before any allocation: a rate whose phase table does not fit LDS
+ * (as bnhip_resample_f32 answers it); the error text names the recording and both rates. */
+typedef struct bnhip_recording {
+    int64_t length;
+    int32_t rate, bits_per_sample;
+} bnhip_recording;
+long long bnhip_analyze_mixed_windows(const bnhip_recording* recs, int n_recordings, int model_rate, int n_samples, int hop,
+                                      int64_t min_tail, int64_t* first_window, int64_t* resampled_length);
+int bnhip_analyze_mixed_pcm_topk(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate,
+                                 int hop, int64_t min_tail, int activation, double sensitivity, int k, float* out_conf,
+                                 int32_t* out_idx);
+int bnhip_analyze_mixed_pcm(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate, int hop,
+                            int64_t min_tail, int activation, double sensitivity, int k, float threshold, bnhip_detection* out,
+                            size_t cap, size_t* n_out);
+
 /* Ultrasonic frame-CV filter (internal/audiocore/ultrasonic/filter.go:20-66), float64 throughout.
  * samples: host float64 [n_clips * n] (int16/32768 as float64, convert/pcm.go:108-113).
  * cv/ok: [n_clips]. device: HIP device ordinal. */
