@@ -1,20 +1,27 @@
 // C ABI of file analysis: whole recordings in, the top-k of every overlapping window (or the detection rows above a threshold) out,
-// in one call - the windows are framed on the device (analyze.h).
+// in one call - the windows are framed on the device (analyze.h).  Recordings at their own rates and depths are resampled and
+// converted there too (resample.h, the slot launch), and multichannel recordings go up interleaved: a channel is picked or the
+// channels are mixed in that launch, where asked after a measurement of the channels' energies on the device (channels.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <vector>
 
 #include "analyze.h"
 #include "api_model.h"
 #include "api_oneshot.h"
+#include "channels.h"
 #include "resample.h"
 
 using namespace bnhip;
 
 static_assert(sizeof(bnhip_detection) == 16 && sizeof(DetRow) == 16, "a detection row is 16 bytes");
 static_assert(sizeof(bnhip_recording) == 16, "a recording's description is 16 bytes");
+static_assert(sizeof(bnhip_channels_recording) == 24, "a multichannel recording's description is 24 bytes");
+static_assert(sizeof(bnhip_channel_energy) == 24, "a channel's energy record is 24 bytes");
+static_assert(BNHIP_CHANNEL_MIX == CHANNEL_MIX && BNHIP_CHANNEL_AUTO == CHANNEL_AUTO, "the selection constants of channels.h");
 
 namespace bnhip {
 
@@ -70,6 +77,11 @@ struct Mixed {
     std::vector<int> plan_of;                     // [n_rec] index into plans, -1: at the model's rate
     long long n_tiles = 0;
     bool plain = false;                           // every recording at the model's rate, one depth: the existing body as it is
+    // the channels entries, where a recording has two channels or more (else empty: the call is the mixed one): [n_rec] each; a
+    // recording's `length` then counts frames.  select: a channel, CHANNEL_MIX or CHANNEL_AUTO (channels.h)
+    std::vector<int> channels, select;
+    std::vector<int32_t> chosen;                  // [n_rec], filled by analyze(): what was read
+    int ch(int r) const { return channels.empty() ? 1 : channels[r]; }
 };
 
 // The phase tables of one set of rates, concatenated in one device buffer and kept (api_oneshot.h): a second call with the same
@@ -162,7 +174,50 @@ const float* mixed_tables(const Mixed& mx, int device, const TableLock& lock) {
     return t ? t->d : nullptr;
 }
 
-#define AN_HIP(call, what)                                                                          \
+// ---- multichannel recordings (the bnhip_analyze_channels_* entries, bnhip_channel_energy_pcm)
+// The recordings of a channels call as the mixed call sees them (base: length in frames, rate, depth), and what the channels add.
+struct Channels {
+    std::vector<bnhip_recording> base;
+    std::vector<int> channels, select;
+    bool multi = false;                           // a recording has two channels or more
+};
+
+// every refusal of the channel fields, and of the burst's size in samples; fills ch.  (What the mixed call refuses of base - the
+// depths, rates and lengths - is mixed_check's to answer; measure: the measurement entry, where a float32 recording is refused
+// whatever its select)
+int channels_check(const bnhip_channels_recording* recs, int n_recordings, bool measure, Channels* ch) {
+    if (!recs) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (n_recordings < 1 || n_recordings > 65535) return set_err(BNHIP_E_INVALID, "n_recordings must be in [1, 65535]");
+    ch->base.resize(n_recordings); ch->channels.resize(n_recordings); ch->select.resize(n_recordings);
+    long long total = 0;
+    for (int r = 0; r < n_recordings; r++) {
+        const bnhip_channels_recording& q = recs[r];
+        const std::string who = "recording " + std::to_string(r) + ": ";
+        if (q.channels < 1 || q.channels > CHANNELS_MAX) return set_err(BNHIP_E_INVALID, who + "channels must be in [1, 16]");
+        if (q.select < CHANNEL_AUTO || q.select >= q.channels)
+            return set_err(BNHIP_E_INVALID, who + "select must be a channel index, BNHIP_CHANNEL_MIX or BNHIP_CHANNEL_AUTO");
+        if ((measure || q.select == CHANNEL_AUTO) && q.bits_per_sample == 0)
+            return set_err(BNHIP_E_INVALID, who + "the channel energies are measured on integer depths; a float32 recording takes a channel or the mix");
+        if (q.length >= 1 && q.length <= MIXED_MAX_LEN) {      // (else mixed_check refuses the length)
+            if (q.length * q.channels > ANALYZE_MAX_SAMPLES - total) return set_err(BNHIP_E_INVALID, "burst of 2^36 samples or more");
+            total += q.length * q.channels;
+        }
+        ch->base[r] = bnhip_recording{q.length, q.rate, q.bits_per_sample};
+        ch->channels[r] = q.channels; ch->select[r] = q.select;
+        ch->multi = ch->multi || q.channels > 1;
+    }
+    return BNHIP_OK;
+}
+
+// computeRmsDbfs (ffmpeg/analyze.go) from a channel's exact sum of squares, in 16-bit units: rms16 = sqrt(E / length) / 2^(bits - 16);
+// below 1 the reference answers -96
+double channel_rms_dbfs(unsigned long long lo, unsigned long long hi, int bits, long long length) {
+    const double e = (double)hi * 18446744073709551616.0 + (double)lo;
+    const double rms16 = std::sqrt(e / (double)length) / (double)(1ll << (bits - 16));
+    return rms16 < 1.0 ? -96.0 : 20.0 * std::log10(rms16 / 32768.0);
+}
+
+#define AN_HIP(call, what)                                                                         \
     do {                                                                                            \
         hipError_t e_ = (call);                                                                     \
         if (ok && e_ != hipSuccess) { ok = false; err = std::string(what) + ": " + hipGetErrorString(e_); } \
@@ -198,8 +253,13 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
         block_bytes += analyze_slot_bytes(lengths[r], bits);
     }
     // mixed: the raw block (every recording as it is in its file, from a 16-byte line on), a descriptor per recording and the tile prefix
+    // channels: the raw block holds interleaved frames; beside the descriptors lie the channel counts and the selection table
+    // [n_rec] each, and the recordings that ask for a measurement have a descriptor and a tile prefix of their own (channels.h)
     std::vector<ResampleSlotDesc> desc;
-    std::vector<long long> tile0;
+    std::vector<long long> tile0, etile0;
+    std::vector<EnergyDesc> edesc;
+    std::vector<int> chsel;
+    const bool mc = mx && !mx->channels.empty();
     size_t raw_bytes = 0, rs_lds = 0;
     if (mx) {
         desc.resize(n_recordings); tile0.assign((size_t)n_recordings + 1, 0);
@@ -214,10 +274,21 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
                 ds.L = rp.p.L; ds.M = rp.p.M; ds.T = rp.p.T; ds.half = rp.p.half; ds.tab_off = (int)rp.tab_off;
                 rs_lds = std::max(rs_lds, resample_lds(rp.p.L, rp.p.M, rp.p.T));
             }
-            raw_bytes += ((size_t)q.length * analyze_sample_bytes(q.bits_per_sample) + 15) / 16 * 16;
+            raw_bytes += ((size_t)q.length * mx->ch(r) * analyze_sample_bytes(q.bits_per_sample) + 15) / 16 * 16;
             tile0[r + 1] = tile0[r] + resample_slot_tiles(lengths[r]);
         }
     }
+    if (mc) {
+        chsel.assign(mx->channels.begin(), mx->channels.end());
+        chsel.insert(chsel.end(), mx->select.begin(), mx->select.end());
+        etile0.push_back(0);
+        for (int r = 0; r < n_recordings; r++) {
+            if (mx->select[r] != CHANNEL_AUTO) continue;
+            edesc.push_back(EnergyDesc{desc[r].in_off, desc[r].n_in, desc[r].bits, mx->channels[r], r});
+            etile0.push_back(etile0.back() + energy_tiles(desc[r].n_in));
+        }
+    }
+    const long long n_etiles = edesc.empty() ? 0 : etile0.back();
     if (hipSetDevice(e.device) != hipSuccess) return set_err(BNHIP_E_RUNTIME, "hipSetDevice failed");
     // whatever an earlier asynchronous call still has queued on the engine's streams finishes first (as host_run does)
     e.sync_contexts();
@@ -230,7 +301,11 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     const size_t o_table = up(block_bytes), o_conf = o_table + up(table_bytes), o_idx = o_conf + up(tk_bytes), o_scr = o_idx + up(tk_bytes);
     const size_t o_total = o_scr + (det ? up(detections_scratch_bytes(W)) : 0), o_rows = o_total + (det ? 256 : 0);
     const size_t o_raw = o_rows + up(rows_cap * sizeof(DetRow)), o_desc = o_raw + up(raw_bytes);
-    const size_t desc_bytes = desc.size() * sizeof(ResampleSlotDesc), all_bytes = o_desc + (mx ? up(desc_bytes) + up(tile0.size() * 8) : 0);
+    const size_t desc_bytes = desc.size() * sizeof(ResampleSlotDesc), o_chsel = o_desc + (mx ? up(desc_bytes) + up(tile0.size() * 8) : 0);
+    // (channels: | channel counts, selections | measurement descriptors | their tile prefix | tile partials | sums)
+    const size_t o_edesc = o_chsel + up(chsel.size() * 4), o_etile0 = o_edesc + up(edesc.size() * sizeof(EnergyDesc));
+    const size_t o_part = o_etile0 + (edesc.empty() ? 0 : up(etile0.size() * 8)), o_energy = o_part + up((size_t)n_etiles * ENERGY_ROW_BYTES);
+    const size_t all_bytes = o_energy + up(edesc.size() * ENERGY_ROW_BYTES);
     char* d = nullptr;
     if (hipMalloc((void**)&d, all_bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -243,7 +318,8 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     if (!mx) AN_HIP(hipMemsetAsync(d, 0, o_table, e.stream), "memset");
     const char* src = static_cast<const char*>(pcm);
     for (int r = 0; ok && r < n_recordings; r++) {
-        const size_t bytes = mx ? (size_t)mx->recs[r].length * analyze_sample_bytes(mx->recs[r].bits_per_sample) : (size_t)lengths[r] * analyze_sample_bytes(bits);
+        const size_t bytes = mx ? (size_t)mx->recs[r].length * mx->ch(r) * analyze_sample_bytes(mx->recs[r].bits_per_sample)
+                                : (size_t)lengths[r] * analyze_sample_bytes(bits);
         AN_HIP(hipMemcpyAsync(mx ? d + o_raw + desc[r].in_off : d + slot[2 * r], src, bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
         src += bytes;
     }
@@ -256,8 +332,25 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
         char* d_tile0 = d + o_desc + up(desc_bytes);
         AN_HIP(hipMemcpyAsync(d + o_desc, desc.data(), desc_bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
         AN_HIP(hipMemcpyAsync(d_tile0, tile0.data(), tile0.size() * 8, hipMemcpyHostToDevice, e.stream), "H2D copy");
-        if (ok) launch_resample_slots(d + o_raw, d, d_tables, reinterpret_cast<const ResampleSlotDesc*>(d + o_desc),
-                                      reinterpret_cast<const long long*>(d_tile0), n_recordings, tile0[n_recordings], rs_lds, e.stream);
+        if (mc) {
+            // the selections go up as asked for; the measurement, if any recording asks for one, overwrites its entries on the
+            // device, and the slot launch behind it reads them there
+            int* d_ch = reinterpret_cast<int*>(d + o_chsel);
+            AN_HIP(hipMemcpyAsync(d_ch, chsel.data(), chsel.size() * 4, hipMemcpyHostToDevice, e.stream), "H2D copy");
+            if (!edesc.empty()) {
+                AN_HIP(hipMemcpyAsync(d + o_edesc, edesc.data(), edesc.size() * sizeof(EnergyDesc), hipMemcpyHostToDevice, e.stream), "H2D copy");
+                AN_HIP(hipMemcpyAsync(d + o_etile0, etile0.data(), etile0.size() * 8, hipMemcpyHostToDevice, e.stream), "H2D copy");
+                if (ok) launch_channel_energy(d + o_raw, reinterpret_cast<const EnergyDesc*>(d + o_edesc), reinterpret_cast<const long long*>(d + o_etile0),
+                                              (int)edesc.size(), n_etiles, reinterpret_cast<unsigned long long*>(d + o_part),
+                                              reinterpret_cast<unsigned long long*>(d + o_energy), d_ch + n_recordings, e.stream);
+            }
+            if (ok) launch_resample_slots_mc(d + o_raw, d, d_tables, reinterpret_cast<const ResampleSlotDesc*>(d + o_desc),
+                                             reinterpret_cast<const long long*>(d_tile0), n_recordings, tile0[n_recordings], rs_lds, d_ch,
+                                             d_ch + n_recordings, e.stream);
+        } else if (ok) {
+            launch_resample_slots(d + o_raw, d, d_tables, reinterpret_cast<const ResampleSlotDesc*>(d + o_desc),
+                                  reinterpret_cast<const long long*>(d_tile0), n_recordings, tile0[n_recordings], rs_lds, e.stream);
+        }
     }
     WinView view;
     view.first = reinterpret_cast<const long long*>(d + o_table);
@@ -289,6 +382,11 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     } else if (ok) {
         AN_HIP(hipMemcpyAsync(out_conf, d_conf, tk_bytes, hipMemcpyDeviceToHost, e.stream), "D2H copy");
         AN_HIP(hipMemcpyAsync(out_idx, d_idx, tk_bytes, hipMemcpyDeviceToHost, e.stream), "D2H copy");
+    }
+    if (ok && mc) {
+        mx->chosen.resize(n_recordings);
+        AN_HIP(hipMemcpyAsync(mx->chosen.data(), d + o_chsel + (size_t)n_recordings * 4, (size_t)n_recordings * 4, hipMemcpyDeviceToHost, e.stream),
+               "D2H copy");
     }
     {
         const hipError_t he = hipStreamSynchronize(e.stream);
@@ -372,6 +470,120 @@ int bnhip_analyze_mixed_pcm(bnhip_model* m, const void* pcm, const bnhip_recordi
     BN_GUARD_BEGIN
     return analyze_mixed(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, threshold, out, cap,
                          n_out);
+    BN_GUARD_END((void)0)
+}
+
+// ---- multichannel recordings
+long long bnhip_analyze_channels_windows(const bnhip_channels_recording* recs, int n_recordings, int model_rate, int n_samples, int hop,
+                                         int64_t min_tail, int64_t* first_window, int64_t* resampled_length) {
+    BN_GUARD_BEGIN
+    if (!first_window) return set_err(BNHIP_E_INVALID, "NULL argument");
+    Channels ch;
+    if (int rc = channels_check(recs, n_recordings, false, &ch)) return rc;
+    return bnhip_analyze_mixed_windows(ch.base.data(), n_recordings, model_rate, n_samples, hop, min_tail, first_window, resampled_length);
+    BN_GUARD_END((void)0)
+}
+
+// the two device entries: a burst of mono recordings is the mixed call, with that call's own fast path
+static int analyze_channels(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate, int hop,
+                            int64_t min_tail, int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold,
+                            bnhip_detection* out_rows, size_t cap, size_t* n_out, int32_t* chosen) {
+    Channels ch;
+    if (int rc = channels_check(recs, n_recordings, false, &ch)) return rc;
+    Mixed mx;
+    if (int rc = mixed_check(ch.base.data(), n_recordings, model_rate, &mx)) return rc;
+    if (ch.multi) {
+        mx.plain = false;
+        mx.channels = ch.channels; mx.select = ch.select;
+    }
+    const int rc = analyze(m, pcm, mx.plain ? ch.base[0].bits_per_sample : 0, mx.n_out.data(), n_recordings, hop, min_tail, activation, sensitivity, k,
+                           out_conf, out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx);
+    if (rc == BNHIP_OK && chosen) {
+        // (one channel: channel 0 is what auto picks, and a mix of one channel is asked for and answered as a mix)
+        for (int r = 0; r < n_recordings; r++) chosen[r] = ch.multi ? mx.chosen[r] : ch.select[r] == CHANNEL_AUTO ? 0 : ch.select[r];
+    }
+    return rc;
+}
+
+int bnhip_analyze_channels_pcm_topk(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                                    int hop, int64_t min_tail, int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx,
+                                    int32_t* chosen) {
+    BN_GUARD_BEGIN
+    return analyze_channels(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, out_conf, out_idx, false, 0.f, nullptr,
+                            0, nullptr, chosen);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_analyze_channels_pcm(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate, int hop,
+                               int64_t min_tail, int activation, double sensitivity, int k, float threshold, bnhip_detection* out, size_t cap,
+                               size_t* n_out, int32_t* chosen) {
+    BN_GUARD_BEGIN
+    return analyze_channels(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, threshold, out,
+                            cap, n_out, chosen);
+    BN_GUARD_END((void)0)
+}
+
+// the measurement alone: one DevCarve (the raw block, the descriptors and tile prefix, the partials, the sums, the decisions), one
+// H2D copy per recording, the two launches, the sums and decisions down
+int bnhip_channel_energy_pcm(int device, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, bnhip_channel_energy* out,
+                             int32_t* chosen) {
+    BN_GUARD_BEGIN
+    const char* what = "channel_energy_pcm";
+    if (!pcm || !out) return set_err(BNHIP_E_INVALID, "NULL argument");
+    Channels ch;
+    if (int rc = channels_check(recs, n_recordings, true, &ch)) return rc;
+    std::vector<EnergyDesc> edesc(n_recordings);
+    std::vector<long long> etile0((size_t)n_recordings + 1, 0);
+    size_t raw_bytes = 0, n_rows = 0;
+    for (int r = 0; r < n_recordings; r++) {
+        const bnhip_recording& q = ch.base[r];
+        const std::string who = "recording " + std::to_string(r) + ": ";
+        if (q.bits_per_sample != 16 && q.bits_per_sample != 24 && q.bits_per_sample != 32)
+            return set_err(BNHIP_E_INVALID, who + "unsupported bit depth: " + std::to_string(q.bits_per_sample) + " (supported: 16, 24, 32)");
+        if (q.rate <= 0) return set_err(BNHIP_E_INVALID, who + "the sample rate must be positive");
+        if (q.length < 1) return set_err(BNHIP_E_INVALID, "every recording needs at least one sample");
+        if (q.length > MIXED_MAX_LEN) return set_err(BNHIP_E_INVALID, who + "2^31 samples or more");
+        edesc[r] = EnergyDesc{(long long)raw_bytes, (int)q.length, q.bits_per_sample, ch.channels[r], r};
+        etile0[r + 1] = etile0[r] + energy_tiles(q.length);
+        raw_bytes += ((size_t)q.length * ch.channels[r] * analyze_sample_bytes(q.bits_per_sample) + 15) / 16 * 16;
+        n_rows += ch.channels[r];
+    }
+    if (int rc = use_device(device)) return rc;
+    const long long n_tiles = etile0[n_recordings];
+    DevCarve cv;
+    const size_t o_raw = cv.add(raw_bytes), o_desc = cv.add(edesc.size() * sizeof(EnergyDesc)), o_tile0 = cv.add(etile0.size() * 8);
+    const size_t o_part = cv.add((size_t)n_tiles * ENERGY_ROW_BYTES), o_sums = cv.add((size_t)n_recordings * ENERGY_ROW_BYTES);
+    const size_t o_sel = cv.add((size_t)n_recordings * 4);
+    DevBlocks b;
+    cv.alloc(b);
+    const char* src = static_cast<const char*>(pcm);
+    for (int r = 0; b.he == hipSuccess && r < n_recordings; r++) {
+        const size_t bytes = (size_t)ch.base[r].length * ch.channels[r] * analyze_sample_bytes(ch.base[r].bits_per_sample);
+        b.he = hipMemcpy(cv.at<char>(o_raw) + edesc[r].in_off, src, bytes, hipMemcpyHostToDevice);
+        src += bytes;
+    }
+    if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_desc), edesc.data(), edesc.size() * sizeof(EnergyDesc), hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_tile0), etile0.data(), etile0.size() * 8, hipMemcpyHostToDevice);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    launch_channel_energy(cv.at<void>(o_raw), cv.at<EnergyDesc>(o_desc), cv.at<long long>(o_tile0), n_recordings, n_tiles,
+                          cv.at<unsigned long long>(o_part), cv.at<unsigned long long>(o_sums), cv.at<int>(o_sel), nullptr);
+    if (int rc = launch_status(what)) { hipDeviceSynchronize(); return rc; }
+    // (the null stream orders the copies after the kernels; the first one is the call's synchronise)
+    std::vector<unsigned long long> sums((size_t)n_recordings * 2 * CHANNELS_MAX);
+    std::vector<int32_t> sel(n_recordings);
+    b.he = hipMemcpy(sums.data(), cv.at<void>(o_sums), sums.size() * 8, hipMemcpyDeviceToHost);
+    if (b.he == hipSuccess) b.he = hipMemcpy(sel.data(), cv.at<void>(o_sel), sel.size() * 4, hipMemcpyDeviceToHost);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    bnhip_channel_energy* o = out;
+    for (int r = 0; r < n_recordings; r++) {
+        for (int c = 0; c < ch.channels[r]; c++, o++) {
+            o->sum_lo = sums[((size_t)r * CHANNELS_MAX + c) * 2];
+            o->sum_hi = sums[((size_t)r * CHANNELS_MAX + c) * 2 + 1];
+            o->rms_dbfs = channel_rms_dbfs(o->sum_lo, o->sum_hi, ch.base[r].bits_per_sample, ch.base[r].length);
+        }
+        if (chosen) chosen[r] = sel[r];
+    }
+    return BNHIP_OK;
     BN_GUARD_END((void)0)
 }
 

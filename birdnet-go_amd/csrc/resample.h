@@ -94,6 +94,11 @@ inline long long resample_slot_tiles(long long n_out) { return (n_out + RESAMPLE
 // each <= RESAMPLE_LDS_MAX.
 void launch_resample_slots(const void* d_raw, void* d_slots, const float* d_tables, const ResampleSlotDesc* d_desc, const long long* d_tile0,
                            int n_rec, long long n_tiles, size_t lds, hipStream_t s);
+// The multichannel form (bnhip_analyze_channels_*): recording r is n_in FRAMES of d_channels[r] interleaved samples, and d_sel[r] (a
+// channel index or CHANNEL_MIX, channels.h) says which value of a frame is staged.  The descriptor is the one above; the two
+// tables [n_rec] lie beside it.  d_sel is read on the device when the launch runs: a measurement enqueued in front may write it.
+void launch_resample_slots_mc(const void* d_raw, void* d_slots, const float* d_tables, const ResampleSlotDesc* d_desc, const long long* d_tile0,
+                              int n_rec, long long n_tiles, size_t lds, const int* d_channels, const int* d_sel, hipStream_t s);
 
 // One stream of one call.  Stream indices (n_base, i_next, keep_from) are positions since the stream started.
 struct ResampleBankDesc {

@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "channels.h"
 #include "kernels.h"
 #include "pcm_sample.h"
 #include "ragged.h"
@@ -181,13 +182,22 @@ int launch_resample_ragged(const int16_t* d_in, float* d_out, const float* d_tab
 // other; a sub-tile stages its input span - converted in the load, zeros outside the recording - and computes as resample_tile does:
 // the same p, the same newest input and the fmaf chain over the same taps in the same order, so the bits are k_resample<false, false>'s
 // on the converted recording.  The slot's tail up to a whole quad is written as zeros here (the framed min/max launch loads quads).
-template <int BITS>
+//
+// MC (k_resample_slots_mc): the recording is frames of C interleaved channels and a staged value is channel_sample's (channels.h) -
+// channel `sel` or the mean of the channels - where frame_sample stands; everything after the staged float32 is the same code.
+template <int BITS, bool MC>
+__device__ __forceinline__ float slot_sample(const char* __restrict__ in, long long n, int C, int sel) {
+    if constexpr (MC) return channel_sample<BITS>(in, n, C, sel);
+    else return frame_sample<BITS>(in, n);
+}
+
+template <int BITS, bool MC>
 __device__ __forceinline__ void resample_slot_tile(const char* __restrict__ in, float* __restrict__ out, const float* __restrict__ table,
-                                                   const ResampleSlotDesc& d, long long i0) {
+                                                   const ResampleSlotDesc& d, long long i0, int C, int sel) {
     const long long n_pad = ((long long)d.n_out + 3) & ~3ll;
     const long long i_end = min(n_pad, i0 + RESAMPLE_SLOT_TILE);
     if (d.L == 0) {                               // at the model's rate: converted only
-        for (long long i = i0 + threadIdx.x; i < i_end; i += 256) out[i] = i < d.n_out ? frame_sample<BITS>(in, i) : 0.0f;
+        for (long long i = i0 + threadIdx.x; i < i_end; i += 256) out[i] = i < d.n_out ? slot_sample<BITS, MC>(in, i, C, sel) : 0.0f;
         return;
     }
     extern __shared__ float sm[];
@@ -206,7 +216,7 @@ __device__ __forceinline__ void resample_slot_tile(const char* __restrict__ in, 
         __syncthreads();                          // the sub-tile in front has read its span
         for (int k = threadIdx.x; k < span; k += 256) {
             const long long n = lo + k;
-            xs[k] = n >= 0 && n < d.n_in ? frame_sample<BITS>(in, n) : 0.0f;
+            xs[k] = n >= 0 && n < d.n_in ? slot_sample<BITS, MC>(in, n, C, sel) : 0.0f;
         }
         __syncthreads();
         const long long i = s0 + threadIdx.x;
@@ -224,19 +234,35 @@ __device__ __forceinline__ void resample_slot_tile(const char* __restrict__ in, 
     }
 }
 
-__global__ __launch_bounds__(256) void k_resample_slots(const char* __restrict__ raw, char* __restrict__ slots, const float* __restrict__ tables,
-                                                        const ResampleSlotDesc* __restrict__ desc, const long long* __restrict__ tile0,
-                                                        int n_rec) {
+template <bool MC>
+__device__ __forceinline__ void resample_slots_block(const char* __restrict__ raw, char* __restrict__ slots, const float* __restrict__ tables,
+                                                     const ResampleSlotDesc* __restrict__ desc, const long long* __restrict__ tile0,
+                                                     int n_rec, const int* __restrict__ channels, const int* __restrict__ sel) {
     const int r = ragged_clip(tile0, n_rec, (long long)blockIdx.x);
     const ResampleSlotDesc d = desc[r];
     const long long i0 = ((long long)blockIdx.x - tile0[r]) * RESAMPLE_SLOT_TILE;
     const char* in = raw + d.in_off;
     float* out = reinterpret_cast<float*>(slots + d.out_off);
     const float* table = tables + d.tab_off;
-    if (d.bits == 16) resample_slot_tile<16>(in, out, table, d, i0);
-    else if (d.bits == 24) resample_slot_tile<24>(in, out, table, d, i0);
-    else if (d.bits == 32) resample_slot_tile<32>(in, out, table, d, i0);
-    else resample_slot_tile<0>(in, out, table, d, i0);
+    const int C = MC ? channels[r] : 1, sl = MC ? sel[r] : 0;
+    if (d.bits == 16) resample_slot_tile<16, MC>(in, out, table, d, i0, C, sl);
+    else if (d.bits == 24) resample_slot_tile<24, MC>(in, out, table, d, i0, C, sl);
+    else if (d.bits == 32) resample_slot_tile<32, MC>(in, out, table, d, i0, C, sl);
+    else resample_slot_tile<0, MC>(in, out, table, d, i0, C, sl);
+}
+
+__global__ __launch_bounds__(256) void k_resample_slots(const char* __restrict__ raw, char* __restrict__ slots, const float* __restrict__ tables,
+                                                        const ResampleSlotDesc* __restrict__ desc, const long long* __restrict__ tile0,
+                                                        int n_rec) {
+    resample_slots_block<false>(raw, slots, tables, desc, tile0, n_rec, nullptr, nullptr);
+}
+
+// the multichannel form: recording r has channels[r] interleaved channels (n_in counts frames) and sel[r] - a channel or
+// CHANNEL_MIX, device memory that the measurement in front of this launch may have written (channels.hip) - says what is fetched
+__global__ __launch_bounds__(256) void k_resample_slots_mc(const char* __restrict__ raw, char* __restrict__ slots, const float* __restrict__ tables,
+                                                           const ResampleSlotDesc* __restrict__ desc, const long long* __restrict__ tile0,
+                                                           int n_rec, const int* __restrict__ channels, const int* __restrict__ sel) {
+    resample_slots_block<true>(raw, slots, tables, desc, tile0, n_rec, channels, sel);
 }
 
 void launch_resample_slots(const void* d_raw, void* d_slots, const float* d_tables, const ResampleSlotDesc* d_desc, const long long* d_tile0,
@@ -245,6 +271,14 @@ void launch_resample_slots(const void* d_raw, void* d_slots, const float* d_tabl
     lds_limit_once<&k_resample_slots>(160 * 1024);
     hipLaunchKernelGGL(k_resample_slots, dim3((unsigned)n_tiles), dim3(256), lds, s, static_cast<const char*>(d_raw), static_cast<char*>(d_slots),
                        d_tables, d_desc, d_tile0, n_rec);
+}
+
+void launch_resample_slots_mc(const void* d_raw, void* d_slots, const float* d_tables, const ResampleSlotDesc* d_desc, const long long* d_tile0,
+                              int n_rec, long long n_tiles, size_t lds, const int* d_channels, const int* d_sel, hipStream_t s) {
+    if (n_rec <= 0 || n_tiles <= 0) return;
+    lds_limit_once<&k_resample_slots_mc>(160 * 1024);
+    hipLaunchKernelGGL(k_resample_slots_mc, dim3((unsigned)n_tiles), dim3(256), lds, s, static_cast<const char*>(d_raw), static_cast<char*>(d_slots),
+                       d_tables, d_desc, d_tile0, n_rec, d_channels, d_sel);
 }
 
 // ------------------------------------------------------------------------------------------------ bank form

@@ -59,7 +59,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_process_pcm16", "bnhip_denoise_ragged_workspace_size", "bnhip_denoise_ragged_device", "bnhip_denoise_ragged_pcm16",
            "bnhip_process_ragged_pcm16", "bnhip_process_spectrogram_png_ragged_pcm16", "bnhip_analyze_windows",
            "bnhip_analyze_pcm_topk", "bnhip_analyze_pcm", "bnhip_analyze_mixed_windows", "bnhip_analyze_mixed_pcm_topk",
-           "bnhip_analyze_mixed_pcm"]
+           "bnhip_analyze_mixed_pcm", "bnhip_analyze_channels_windows", "bnhip_analyze_channels_pcm_topk",
+           "bnhip_analyze_channels_pcm", "bnhip_channel_energy_pcm"]
 
 
 class HipError(RuntimeError):
@@ -156,6 +157,77 @@ def recordings(lengths, rates, depths):
     recs = np.zeros(ln.size, RECORDING)
     recs["length"], recs["rate"], recs["bits_per_sample"] = ln, rates, depths
     return recs
+
+
+def _analyze_channels_protos(lib):
+    """... and of the entries for multichannel recordings (apart again, for the same reason)."""
+    _analyze_mixed_protos(lib)
+    lib.bnhip_analyze_channels_windows.restype = C.c_longlong
+    lib.bnhip_analyze_channels_windows.argtypes = lib.bnhip_analyze_mixed_windows.argtypes
+    lib.bnhip_analyze_channels_pcm_topk.argtypes = lib.bnhip_analyze_mixed_pcm_topk.argtypes + [C.c_void_p]
+    lib.bnhip_analyze_channels_pcm.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes + [C.c_void_p]
+    lib.bnhip_channel_energy_pcm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    return lib
+
+
+# one recording of the channels entries (bnhip_channels_recording): frames at its own rate, the rate, the depth, the channels of a
+# frame and which of them is read (a channel index, CHANNEL_MIX or CHANNEL_AUTO)
+CHANNELS_RECORDING = np.dtype([("length", "<i8"), ("rate", "<i4"), ("bits_per_sample", "<i4"), ("channels", "<i4"), ("select", "<i4")])
+# one channel of bnhip_channel_energy_pcm (bnhip_channel_energy): the exact sum of squares in 128 bits, and its level
+CHANNEL_ENERGY = np.dtype([("sum_lo", "<u8"), ("sum_hi", "<u8"), ("rms_dbfs", "<f8")])
+CHANNEL_MIX, CHANNEL_AUTO = -1, -2
+
+
+def channel_select(choice):
+    """A channel index, "mix" or "auto" -> the `select` of a CHANNELS_RECORDING."""
+    return {"mix": CHANNEL_MIX, "auto": CHANNEL_AUTO}[choice] if isinstance(choice, str) else int(choice)
+
+
+def channel_recordings(lengths, rates, depths, channels, select=0):
+    """-> the CHANNELS_RECORDING table of recordings of `lengths` frames of `channels` interleaved samples at `rates` Hz and `depths`
+    bits; select: per recording (or one for all) a channel index, "mix" / CHANNEL_MIX or "auto" / CHANNEL_AUTO."""
+    ln = np.asarray(lengths, np.int64).reshape(-1)
+    recs = np.zeros(ln.size, CHANNELS_RECORDING)
+    recs["length"], recs["rate"], recs["bits_per_sample"], recs["channels"] = ln, rates, depths, channels
+    recs["select"] = [channel_select(s) for s in select] if isinstance(select, (list, tuple)) else channel_select(select)
+    return recs
+
+
+def _channels_bytes(raw, recs):
+    """The interleaved bytes of a channels call as a uint8 array, checked against the table."""
+    recs = np.ascontiguousarray(recs, CHANNELS_RECORDING).reshape(-1)
+    x = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
+    bad = ~np.isin(recs["bits_per_sample"], (0, 16, 24, 32))
+    if bad.any():
+        raise HipError(E_INVALID, f"unsupported bit depth: {int(recs['bits_per_sample'][bad][0])} (supported: 0 = float32, 16, 24, 32)")
+    want = int((recs["length"] * recs["channels"].astype(np.int64) * np.where(recs["bits_per_sample"] == 0, 4, recs["bits_per_sample"] // 8)).sum())
+    if x.size != want:
+        raise HipError(E_INVALID, f"input size mismatch: the recordings hold {want} bytes, got {x.size} bytes")
+    return x, recs
+
+
+def analyze_channels_windows(recs, model_rate, n_samples, hop, min_tail=0):
+    """bnhip_analyze_channels_windows (host only): analyze_mixed_windows over the (length, rate) of a CHANNELS_RECORDING table."""
+    lib = _analyze_channels_protos(load_library())
+    recs = np.ascontiguousarray(recs, CHANNELS_RECORDING).reshape(-1)
+    first, n_out = np.zeros(recs.size + 1, np.int64), np.zeros(recs.size, np.int64)
+    w = lib.bnhip_analyze_channels_windows(recs.ctypes.data if recs.size else None, recs.size, int(model_rate), int(n_samples), int(hop),
+                                           int(min_tail), first.ctypes.data, n_out.ctypes.data)
+    if w < 0:
+        _check(lib, int(w))
+    return first, n_out
+
+
+def channel_energy(raw, recs, device=0):
+    """bnhip_channel_energy_pcm: the per-channel measurement behind "auto", alone.  raw: the recordings' interleaved bytes packed back
+    to back; recs: a CHANNELS_RECORDING table of integer depths.  -> (CHANNEL_ENERGY [sum of channels], recording-major; chosen int32
+    [n]: what "auto" picks).  The exact sum of squares of row i is (int(sum_hi[i]) << 64) | int(sum_lo[i])."""
+    lib = _analyze_channels_protos(load_library())
+    x, recs = _channels_bytes(raw, recs)
+    out = np.zeros(int(recs["channels"].clip(0, None).sum()), CHANNEL_ENERGY)
+    chosen = np.zeros(recs.size, np.int32)
+    _check(lib, lib.bnhip_channel_energy_pcm(int(device), x.ctypes.data, recs.ctypes.data, recs.size, out.ctypes.data, chosen.ctypes.data))
+    return out, chosen
 
 
 def analyze_mixed_windows(recs, model_rate, n_samples, hop, min_tail=0):
@@ -456,6 +528,39 @@ class HipClassifier:
                                                             int(min_tail), activation, sensitivity, k, float(threshold),
                                                             rows.ctypes.data if cap else None, int(cap), C.byref(n)))
         return rows[:min(int(cap), n.value)], n.value
+
+    def analyze_channels_pcm_topk(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0):
+        """bnhip_analyze_channels_pcm_topk: multichannel recordings (a CHANNELS_RECORDING table; their interleaved frames packed
+        back to back as they are in their files) in; each recording's chosen channel, or the mean of its channels, is what
+        analyze_mixed_pcm_topk then analyses - fetched, and where asked decided, on the device.
+        -> (conf [W, k], idx [W, k], first_window, chosen int32 [n]: the channel read or CHANNEL_MIX)."""
+        self._alive()
+        _analyze_channels_protos(self._lib)
+        x, recs = _channels_bytes(raw, recs)
+        first, _ = analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)
+        kk, w = min(k, self._n_classes), int(first[-1])
+        conf = np.empty((w, kk), np.float32)
+        idx = np.empty((w, kk), np.int32)
+        chosen = np.zeros(recs.size, np.int32)
+        _check(self._lib, self._lib.bnhip_analyze_channels_pcm_topk(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate),
+                                                                    int(hop), int(min_tail), activation, sensitivity, k, conf.ctypes.data,
+                                                                    idx.ctypes.data, chosen.ctypes.data))
+        return conf, idx, first, chosen
+
+    def analyze_channels_pcm(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
+        """bnhip_analyze_channels_pcm: the same call, answered as detection rows, as analyze_pcm answers.  -> (rows, total, chosen)."""
+        self._alive()
+        _analyze_channels_protos(self._lib)
+        x, recs = _channels_bytes(raw, recs)
+        if cap is None:
+            cap = int(analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]) * min(k, self._n_classes)
+        rows = np.zeros(int(cap), DETECTION)
+        n = C.c_size_t(0)
+        chosen = np.zeros(recs.size, np.int32)
+        _check(self._lib, self._lib.bnhip_analyze_channels_pcm(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
+                                                               int(min_tail), activation, sensitivity, k, float(threshold),
+                                                               rows.ctypes.data if cap else None, int(cap), C.byref(n), chosen.ctypes.data))
+        return rows[:min(int(cap), n.value)], n.value, chosen
 
     # ---- plumbing
     def set_stream(self, hip_stream_ptr):

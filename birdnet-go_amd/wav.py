@@ -19,6 +19,23 @@ class WavError(ValueError):
 
 def _first_channel(path_or_bytes):
     """-> (first channel's sample bytes uint8 [n, bits / 8], sample_rate, bit_depth)."""
+    data, rate, bits, channels = _data_chunk(path_or_bytes)
+    bps = bits // 8
+    n = len(data) // (bps * channels)
+    return np.frombuffer(data, np.uint8, n * bps * channels).reshape(n, channels, bps)[:, 0, :], rate, bits
+
+
+def read_wav_frames(path_or_bytes):
+    """-> (the whole frames of the data chunk as they are in the file - the channels interleaved, little-endian, bit_depth / 8 bytes a
+    sample -, sample_rate, bit_depth, channels): what the multichannel analysis sends (`HipClassifier.analyze_channels_pcm`), which
+    picks or mixes the channels on the device.  No pass over the samples is made here."""
+    data, rate, bits, channels = _data_chunk(path_or_bytes)
+    frame = (bits // 8) * channels
+    return data[:len(data) // frame * frame], rate, bits, channels
+
+
+def _data_chunk(path_or_bytes):
+    """-> (the data chunk's bytes, sample_rate, bit_depth, channels) of an integer-PCM WAV file."""
     raw = path_or_bytes if isinstance(path_or_bytes, (bytes, bytearray)) else open(path_or_bytes, "rb").read()
     if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
         raise WavError("not a RIFF/WAVE file")
@@ -43,9 +60,7 @@ def _first_channel(path_or_bytes):
         raise WavError(f"unsupported WAV format tag {tag} (integer PCM only)")
     if bits not in (16, 24, 32) or channels < 1:
         raise WavError(f"unsupported audio bit depth: {bits}")
-    bps = bits // 8
-    n = len(data) // (bps * channels)
-    return np.frombuffer(data, np.uint8, n * bps * channels).reshape(n, channels, bps)[:, 0, :], int(rate), int(bits)
+    return data, int(rate), int(bits), int(channels)
 
 
 def read_wav_pcm(path_or_bytes):
@@ -108,7 +123,7 @@ def frame_clips(samples, sample_rate, clip_seconds=3.0, overlap_seconds=0.0, min
 
 
 def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0,
-                 model_rate=48000, device=0, device_framing=False, device_resample=False):
+                 model_rate=48000, device=0, device_framing=False, device_resample=False, channels=None, return_chosen=False):
     """File analysis = read -> (resample to the model's rate) -> frame -> batched predict_topk.
     Returns rows (start_s, end_s, label|index, confidence).
 
@@ -119,7 +134,14 @@ def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds
 
     device_framing=True: the same rows from one `bnhip_analyze_pcm` call - the file's PCM bytes go to the device as they are
     and the windows are framed there (a resampled file goes as float32; with device_resample=True it too goes as it is and is
-    resampled on the device, see analyze_files)."""
+    resampled on the device, see analyze_files).
+
+    channels (a channel index, "mix" or "auto"; analyze_files): the file's frames go interleaved and the channel is picked or mixed
+    on the device, in the device-framed call; return_chosen=True then answers (rows, the channel read or "mix")."""
+    if channels is not None:
+        rows, chosen = analyze_files([path], classifier, labels, sensitivity, overlap_seconds, top_k, threshold, model_rate, device,
+                                     channels=channels, return_chosen=True)
+        return (rows[0], chosen[0]) if return_chosen else rows[0]
     if device_framing:
         return analyze_files([path], classifier, labels, sensitivity, overlap_seconds, top_k, threshold, model_rate, device,
                              device_resample=device_resample)[0]
@@ -143,20 +165,35 @@ def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds
 
 
 def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
-                  device=0, device_resample=False):
+                  device=0, device_resample=False, channels=None, return_chosen=False):
     """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
     path, each what analyze_file returns for that file.  The files' PCM bytes are sent as they are when all of them are at the
     model's rate and share one bit depth; otherwise every file goes as float32 (converted, and resampled where its rate differs,
     exactly as analyze_file does).
 
     device_resample=True: every file's bytes go as they are, whatever its rate and depth, in one `bnhip_analyze_mixed_pcm` call
-    that resamples and converts them on the device - the same rows."""
+    that resamples and converts them on the device - the same rows.
+
+    channels: None analyses every file's first channel, de-interleaved here on the host (the paths above).  A channel index, "mix"
+    or "auto" sends every file's frames interleaved as they are, whatever its rate, depth and channel count, in one
+    `bnhip_analyze_channels_pcm` call: that channel, the mean of the channels, or - decided per file on the device from the
+    channels' energies, by the reference's rule - one of the two.  return_chosen=True (with channels set): -> (rows, chosen), chosen
+    the channel read of every file, or "mix"."""
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
-    pcm = [read_wav_pcm(p) for p in paths]
-    depths = {bits for _, _, bits in pcm}
-    recs = None
-    if device_resample:
+    if return_chosen and channels is None:
+        raise ValueError("return_chosen needs channels")
+    recs = crecs = None
+    if channels is None:
+        pcm = [read_wav_pcm(p) for p in paths]
+        depths = {bits for _, _, bits in pcm}
+    if channels is not None:
+        from . import host
+        frames = [read_wav_frames(p) for p in paths]
+        bufs = [raw for raw, _, _, _ in frames]
+        lengths = [len(raw) // ((bits // 8) * ch) for raw, _, bits, ch in frames]
+        crecs = host.channel_recordings(lengths, [f[1] for f in frames], [f[2] for f in frames], [f[3] for f in frames], channels)
+    elif device_resample:
         from . import host
         bufs = [raw for raw, _, _ in pcm]
         lengths = [len(raw) // (bits // 8) for raw, _, bits in pcm]
@@ -184,7 +221,12 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     t32 = np.float32(threshold)
     if float(t32) < threshold:
         t32 = np.nextafter(t32, np.float32(np.inf))
-    if recs is not None:
+    chosen = None
+    if crecs is not None:
+        det, _, sel = classifier.analyze_channels_pcm(b"".join(bufs), crecs, model_rate, hop, min_tail, k=top_k, sensitivity=sensitivity,
+                                                      threshold=float(t32))
+        chosen = ["mix" if s < 0 else int(s) for s in sel]
+    elif recs is not None:
         det, _ = classifier.analyze_mixed_pcm(b"".join(bufs), recs, model_rate, hop, min_tail, k=top_k, sensitivity=sensitivity, threshold=float(t32))
     else:
         det, _ = classifier.analyze_pcm(b"".join(bufs), bits, lengths, hop, min_tail, k=top_k, sensitivity=sensitivity, threshold=float(t32))
@@ -192,4 +234,4 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     for r, w, j, c in zip(det["recording"], det["window"], det["class_index"], det["confidence"]):
         start = np.float64(int(w) * hop) / model_rate
         out[int(r)].append((float(start), float(start + clip_seconds), labels[j] if labels else int(j), float(c)))
-    return out
+    return (out, chosen) if return_chosen else out

@@ -278,6 +278,57 @@ int bnhip_analyze_mixed_pcm(bnhip_model* m, const void* pcm, const bnhip_recordi
                             int64_t min_tail, int activation, double sensitivity, int k, float threshold, bnhip_detection* out,
                             size_t cap, size_t* n_out);
 
+/* File analysis of multichannel recordings: stereo and 4- to 8-channel files as field recorders and microphone arrays write them go
+ * to the device interleaved, exactly as they are in a WAV data chunk, and the launch that converts and resamples fetches one channel
+ * or the mean of the channels - no de-interleaving pass on the host.  Which one may be left to a measurement made on the device in
+ * the same call: the reference's channel policy (internal/audiocore/ffmpeg/analyze.go:157-202: per-channel RMS dBFS; a channel that
+ * leads by more than 6 dB is picked, both below -60 dBFS or anything else gives the downmix), restated on exact integer sums.
+ *   recs     One bnhip_channels_recording per recording: length in FRAMES (samples per channel) at its own rate, the depth as in
+ *            bnhip_recording, channels 1..16, and select: a channel index, BNHIP_CHANNEL_MIX or BNHIP_CHANNEL_AUTO.  pcm holds recording
+ *            r as length * channels interleaved samples, directly after recording r - 1.
+ *   sample   Channel c: sample n is element n * channels + c, converted as bnhip_analyze_mixed_pcm converts it.  Mix, integer depths:
+ *            (float)((double)S / (double)(channels * 2^(bits - 1))), S the exact integer sum of the frame.  Mix, float32: the channels
+ *            added in channel order in fp64, divided by (double)channels, rounded to float32.  The result is the recording that the
+ *            mixed call then resamples and frames, bit for bit.
+ *   auto     Integer depths only.  E[c] = the exact sum of squares of channel c (128 bits), Ed[c] = (double)sum_hi * 2^64 +
+ *            (double)sum_lo.  A channel is quiet when Ed[c] < (1073.741824 * 4^(bits - 16)) * (double)length (-60 dBFS).  One channel
+ *            gives channel 0; every channel quiet gives the mix; else the channel with the largest Ed (ties: the lower index) is
+ *            picked when Ed[top] > 3.9810717055349722 * Ed[second] (6 dB in power), and the mix otherwise.
+ *   windows  Host only: the table of bnhip_analyze_mixed_windows over (length, rate); the channels do not enter it.
+ *   pcm_topk / pcm  As bnhip_analyze_mixed_pcm_topk / bnhip_analyze_mixed_pcm; chosen (may be NULL): [n_recordings], the channel read
+ *            or BNHIP_CHANNEL_MIX.  One H2D copy per recording, the measurement (two launches, only over the recordings that ask for
+ *            auto, none when no recording does), one slot launch, then the same chunks.  A burst whose recordings all have one
+ *            channel IS the bnhip_analyze_mixed_* call, with that call's own fast path.
+ *   bnhip_channel_energy_pcm  The measurement alone, for every recording whatever its select: out [sum of channels], recording-major:
+ *            the 128-bit sum of squares of the channel's integer samples and rms_dbfs = 20 log10(rms16 / 32768) with rms16 =
+ *            sqrt(E / length) / 2^(bits - 16), -96 when rms16 < 1 (computed on the host); chosen (may be NULL): what
+ *            BNHIP_CHANNEL_AUTO picks.
+ * BNHIP_E_INVALID (nothing written, the handle stays usable): everything bnhip_analyze_mixed_pcm refuses, channels outside 1..16,
+ * select outside its range, auto (or the measurement entry) on a float32 recording, length * channels summed over the burst at 2^36
+ * or more, a multi-device or plan-only handle. */
+#define BNHIP_CHANNEL_MIX  (-1)
+#define BNHIP_CHANNEL_AUTO (-2)
+typedef struct bnhip_channels_recording {
+    int64_t length;
+    int32_t rate, bits_per_sample;
+    int32_t channels;
+    int32_t select;
+} bnhip_channels_recording;
+typedef struct bnhip_channel_energy {
+    uint64_t sum_lo, sum_hi;
+    double rms_dbfs;
+} bnhip_channel_energy;
+long long bnhip_analyze_channels_windows(const bnhip_channels_recording* recs, int n_recordings, int model_rate, int n_samples, int hop,
+                                         int64_t min_tail, int64_t* first_window, int64_t* resampled_length);
+int bnhip_analyze_channels_pcm_topk(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                    int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                    float* out_conf, int32_t* out_idx, int32_t* chosen);
+int bnhip_analyze_channels_pcm(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                               int hop, int64_t min_tail, int activation, double sensitivity, int k, float threshold,
+                               bnhip_detection* out, size_t cap, size_t* n_out, int32_t* chosen);
+int bnhip_channel_energy_pcm(int device, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                             bnhip_channel_energy* out, int32_t* chosen);
+
 /* Ultrasonic frame-CV filter (internal/audiocore/ultrasonic/filter.go:20-66), float64 throughout.
  * samples: host float64 [n_clips * n] (int16/32768 as float64, convert/pcm.go:108-113).
  * cv/ok: [n_clips]. device: HIP device ordinal. */
