@@ -2,6 +2,8 @@
 // in one call - the windows are framed on the device (analyze.h).  Recordings at their own rates and depths are resampled and
 // converted there too (resample.h, the slot launch), and multichannel recordings go up interleaved: a channel is picked or the
 // channels are mixed in that launch, where asked after a measurement of the channels' energies on the device (channels.h).
+// Any of the calls can end in detection events instead of rows: the rows stay on the device and the reference's result post-filters run
+// there as the call's tail (events.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,11 +15,14 @@
 #include "api_model.h"
 #include "api_oneshot.h"
 #include "channels.h"
+#include "events.h"
 #include "resample.h"
 
 using namespace bnhip;
 
 static_assert(sizeof(bnhip_detection) == 16 && sizeof(DetRow) == 16, "a detection row is 16 bytes");
+static_assert(sizeof(bnhip_event) == 32 && sizeof(Event) == 32, "an event is 32 bytes");
+static_assert(BNHIP_EVENTS_KEEP_DROPPED == EVENTS_KEEP_DROPPED, "the flag of events.h");
 static_assert(sizeof(bnhip_recording) == 16, "a recording's description is 16 bytes");
 static_assert(sizeof(bnhip_channels_recording) == 24, "a multichannel recording's description is 24 bytes");
 static_assert(sizeof(bnhip_channel_energy) == 24, "a channel's energy record is 24 bytes");
@@ -217,6 +222,25 @@ double channel_rms_dbfs(unsigned long long lo, unsigned long long hi, int bits, 
     return rms16 < 1.0 ? -96.0 : 20.0 * std::log10(rms16 / 32768.0);
 }
 
+// ---- detection events (the bnhip_*_events entries, bnhip_detection_events)
+constexpr int EVENT_MAX_CLASSES = (int)(TOPK_LDS_MAX / 4);     // 38 400: with recording < 65 535 a (recording, class) key is below 2^32
+constexpr unsigned long long EVENT_MAX_ROWS = 1ull << 31;
+
+// what an events entry adds to its sibling's arguments: the filter and where the events go
+struct EventsOut { const bnhip_event_filter* f; bnhip_event* out; };
+
+// every refusal of the filter itself
+int event_filter_check(const bnhip_event_filter* f) {
+    if (!f || !f->class_threshold) return set_err(BNHIP_E_INVALID, "NULL event filter / class_threshold");
+    if (f->hold_windows < 1) return set_err(BNHIP_E_INVALID, "hold_windows must be at least 1");
+    if (f->min_count < 1) return set_err(BNHIP_E_INVALID, "min_count must be at least 1");
+    if (f->flags & ~BNHIP_EVENTS_KEEP_DROPPED) return set_err(BNHIP_E_INVALID, "unknown event filter flags");
+    return BNHIP_OK;
+}
+
+// bytes of the filter's tables on the device: class_threshold [n_classes], then class_veto [n_classes] where there is one
+size_t event_tables_bytes(int n_classes) { return (size_t)n_classes * 4 + (size_t)n_classes; }
+
 #define AN_HIP(call, what)                                                                         \
     do {                                                                                            \
         hipError_t e_ = (call);                                                                     \
@@ -227,15 +251,22 @@ double channel_rms_dbfs(unsigned long long lo, unsigned long long hi, int bits, 
 // describes them, and bits / lengths state the float32 slots they are resampled into - what the chunk loop frames.
 int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, int n_recordings, int hop, int64_t min_tail, int activation,
             double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold, bnhip_detection* out_rows, size_t cap,
-            size_t* n_out, Mixed* mx = nullptr) {
+            size_t* n_out, Mixed* mx = nullptr, const EventsOut* ev = nullptr) {
     if (!m || !pcm || !lengths) return set_err(BNHIP_E_INVALID, "NULL argument");
-    if (det ? (!n_out || (cap && !out_rows)) : (!out_conf || !out_idx)) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (det ? (!n_out || (cap && !(ev ? (const void*)ev->out : (const void*)out_rows))) : (!out_conf || !out_idx))
+        return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (ev) if (int rc = event_filter_check(ev->f)) return rc;
     if (bits != 0 && bits != 16 && bits != 24 && bits != 32)
         return set_err(BNHIP_E_INVALID, "unsupported bit depth: " + std::to_string(bits) + " (supported: 0 = float32, 16, 24, 32)");
     if (k <= 0) return set_err(BNHIP_E_INVALID, "k must be positive");
     if (activation < 0 || activation > 2) return set_err(BNHIP_E_INVALID, "unknown activation");
     Engine& e = m->eng();
     if (int rc = check_table(lengths, n_recordings, e.n_samples, hop, min_tail)) return rc;
+    if (ev) {                                     // (an argument error like the others: answered before the handle is looked at)
+        std::vector<long long> len64(lengths, lengths + n_recordings), first((size_t)n_recordings + 1);
+        const long long rows_max = analyze_windows(len64.data(), n_recordings, e.n_samples, hop, min_tail, first.data()) * std::min(k, e.n_classes);
+        if ((unsigned long long)rows_max >= EVENT_MAX_ROWS) return set_err(BNHIP_E_INVALID, "2^31 detection rows or more");
+    }
     if (m->engs.size() > 1) return set_err(BNHIP_E_INVALID, "file analysis runs on one device; use a single-device handle");
     if (e.device < 0) return set_err(BNHIP_E_INVALID, "plan-only model cannot run");
     if ((size_t)e.n_classes * 4 > TOPK_LDS_MAX) return set_err(BNHIP_E_UNSUPPORTED, "too many classes for the LDS top-k");
@@ -295,9 +326,12 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     if (e.stream) hipStreamSynchronize(e.stream);
     // one allocation: recordings | tables | top-k confidences | top-k indices | detection scratch | row count | rows
     // (mixed: | raw block | descriptors, tile prefix)
+    // events: every row stays on the device (the caller's cap counts events), and behind everything else lie the filter's tables,
+    // the event scratch (events.h) and the events
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t table_bytes = table.size() * 8, tk_bytes = (size_t)W * kk * 4;
-    const size_t rows_cap = det ? std::min(cap, (size_t)W * kk) : 0;
+    const size_t n_rows_max = (size_t)W * kk, ev_cap = ev ? std::min(cap, n_rows_max) : 0;
+    const size_t rows_cap = ev ? n_rows_max : det ? std::min(cap, n_rows_max) : 0;
     const size_t o_table = up(block_bytes), o_conf = o_table + up(table_bytes), o_idx = o_conf + up(tk_bytes), o_scr = o_idx + up(tk_bytes);
     const size_t o_total = o_scr + (det ? up(detections_scratch_bytes(W)) : 0), o_rows = o_total + (det ? 256 : 0);
     const size_t o_raw = o_rows + up(rows_cap * sizeof(DetRow)), o_desc = o_raw + up(raw_bytes);
@@ -305,7 +339,9 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     // (channels: | channel counts, selections | measurement descriptors | their tile prefix | tile partials | sums)
     const size_t o_edesc = o_chsel + up(chsel.size() * 4), o_etile0 = o_edesc + up(edesc.size() * sizeof(EnergyDesc));
     const size_t o_part = o_etile0 + (edesc.empty() ? 0 : up(etile0.size() * 8)), o_energy = o_part + up((size_t)n_etiles * ENERGY_ROW_BYTES);
-    const size_t all_bytes = o_energy + up(edesc.size() * ENERGY_ROW_BYTES);
+    const size_t o_evtab = o_energy + up(edesc.size() * ENERGY_ROW_BYTES), o_evscr = o_evtab + (ev ? up(event_tables_bytes(e.n_classes)) : 0);
+    const size_t o_evout = o_evscr + (ev ? up(events_scratch_bytes(n_rows_max)) : 0);
+    const size_t all_bytes = o_evout + up(ev_cap * sizeof(Event));
     char* d = nullptr;
     if (hipMalloc((void**)&d, all_bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -324,6 +360,12 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
         src += bytes;
     }
     AN_HIP(hipMemcpyAsync(d + o_table, table.data(), table_bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
+    if (ev) {
+        AN_HIP(hipMemcpyAsync(d + o_evtab, ev->f->class_threshold, (size_t)e.n_classes * 4, hipMemcpyHostToDevice, e.stream), "H2D copy");
+        if (ev->f->class_veto)
+            AN_HIP(hipMemcpyAsync(d + o_evtab + (size_t)e.n_classes * 4, ev->f->class_veto, (size_t)e.n_classes, hipMemcpyHostToDevice, e.stream),
+                   "H2D copy");
+    }
     if (mx) {
         // (the lock is held from the tables' lookup until the launch that reads them is enqueued, api_oneshot.h)
         TableLock lock(g_rate_tables.mu);
@@ -372,9 +414,23 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     if (ok && det) {
         launch_detections(d_conf, d_idx, W, kk, threshold, view, d + o_scr, reinterpret_cast<DetRow*>(d + o_rows), rows_cap,
                           reinterpret_cast<unsigned long long*>(d + o_total), e.stream);
+        // the event tail reads the rows where they lie, and their count where launch_detections left it
+        if (ev) {
+            const uint8_t* d_veto = ev->f->class_veto ? reinterpret_cast<const uint8_t*>(d + o_evtab + (size_t)e.n_classes * 4) : nullptr;
+            const EventFilterDev fd{reinterpret_cast<const float*>(d + o_evtab), d_veto, ev->f->veto_threshold, ev->f->hold_windows, ev->f->min_count,
+                                    ev->f->flags, e.n_classes};
+            launch_events(reinterpret_cast<const DetRow*>(d + o_rows), reinterpret_cast<const unsigned long long*>(d + o_total), n_rows_max, fd,
+                          events_passes((unsigned long long)n_recordings * e.n_classes - 1), d + o_evscr, reinterpret_cast<Event*>(d + o_evout), ev_cap,
+                          e.stream);
+        }
     }
     if (ok) AN_HIP(hipGetLastError(), "kernel launch");
-    if (ok && det) {
+    if (ok && ev) {
+        AN_HIP(hipMemcpyAsync(&total, events_total(d + o_evscr), 8, hipMemcpyDeviceToHost, e.stream), "D2H copy");
+        AN_HIP(hipStreamSynchronize(e.stream), "file analysis");
+        const size_t n_ev = (size_t)std::min<unsigned long long>(total, ev_cap);
+        if (ok && n_ev) AN_HIP(hipMemcpyAsync(ev->out, d + o_evout, n_ev * sizeof(Event), hipMemcpyDeviceToHost, e.stream), "D2H copy");
+    } else if (ok && det) {
         AN_HIP(hipMemcpyAsync(&total, d + o_total, 8, hipMemcpyDeviceToHost, e.stream), "D2H copy");
         AN_HIP(hipStreamSynchronize(e.stream), "file analysis");
         const size_t n_rows = (size_t)std::min<unsigned long long>(total, rows_cap);
@@ -430,6 +486,17 @@ int bnhip_analyze_pcm(bnhip_model* m, const void* pcm, int bits_per_sample, cons
     BN_GUARD_END((void)0)
 }
 
+// the events entries: the rows entry with every non-NaN row kept on the device (threshold -inf) and the event tail behind it
+int bnhip_analyze_pcm_events(bnhip_model* m, const void* pcm, int bits_per_sample, const int64_t* lengths, int n_recordings, int hop,
+                             int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter, bnhip_event* out,
+                             size_t cap, size_t* n_out) {
+    BN_GUARD_BEGIN
+    const EventsOut ev{filter, out};
+    return analyze(m, pcm, bits_per_sample, lengths, n_recordings, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, -INFINITY,
+                   nullptr, cap, n_out, nullptr, &ev);
+    BN_GUARD_END((void)0)
+}
+
 // ---- recordings at their own rates and depths
 long long bnhip_analyze_mixed_windows(const bnhip_recording* recs, int n_recordings, int model_rate, int n_samples, int hop, int64_t min_tail,
                                       int64_t* first_window, int64_t* resampled_length) {
@@ -449,11 +516,11 @@ long long bnhip_analyze_mixed_windows(const bnhip_recording* recs, int n_recordi
 // the two device entries: a burst that the existing entries take as it is goes to them
 static int analyze_mixed(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate, int hop, int64_t min_tail,
                          int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold,
-                         bnhip_detection* out_rows, size_t cap, size_t* n_out) {
+                         bnhip_detection* out_rows, size_t cap, size_t* n_out, const EventsOut* ev = nullptr) {
     Mixed mx;
     if (int rc = mixed_check(recs, n_recordings, model_rate, &mx)) return rc;
     return analyze(m, pcm, mx.plain ? recs[0].bits_per_sample : 0, mx.n_out.data(), n_recordings, hop, min_tail, activation, sensitivity, k, out_conf,
-                   out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx);
+                   out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx, ev);
 }
 
 int bnhip_analyze_mixed_pcm_topk(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate, int hop,
@@ -473,6 +540,16 @@ int bnhip_analyze_mixed_pcm(bnhip_model* m, const void* pcm, const bnhip_recordi
     BN_GUARD_END((void)0)
 }
 
+int bnhip_analyze_mixed_pcm_events(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate, int hop,
+                                   int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter,
+                                   bnhip_event* out, size_t cap, size_t* n_out) {
+    BN_GUARD_BEGIN
+    const EventsOut ev{filter, out};
+    return analyze_mixed(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, -INFINITY, nullptr,
+                         cap, n_out, &ev);
+    BN_GUARD_END((void)0)
+}
+
 // ---- multichannel recordings
 long long bnhip_analyze_channels_windows(const bnhip_channels_recording* recs, int n_recordings, int model_rate, int n_samples, int hop,
                                          int64_t min_tail, int64_t* first_window, int64_t* resampled_length) {
@@ -487,7 +564,7 @@ long long bnhip_analyze_channels_windows(const bnhip_channels_recording* recs, i
 // the two device entries: a burst of mono recordings is the mixed call, with that call's own fast path
 static int analyze_channels(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate, int hop,
                             int64_t min_tail, int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold,
-                            bnhip_detection* out_rows, size_t cap, size_t* n_out, int32_t* chosen) {
+                            bnhip_detection* out_rows, size_t cap, size_t* n_out, int32_t* chosen, const EventsOut* ev = nullptr) {
     Channels ch;
     if (int rc = channels_check(recs, n_recordings, false, &ch)) return rc;
     Mixed mx;
@@ -497,7 +574,7 @@ static int analyze_channels(bnhip_model* m, const void* pcm, const bnhip_channel
         mx.channels = ch.channels; mx.select = ch.select;
     }
     const int rc = analyze(m, pcm, mx.plain ? ch.base[0].bits_per_sample : 0, mx.n_out.data(), n_recordings, hop, min_tail, activation, sensitivity, k,
-                           out_conf, out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx);
+                           out_conf, out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx, ev);
     if (rc == BNHIP_OK && chosen) {
         // (one channel: channel 0 is what auto picks, and a mix of one channel is asked for and answered as a mix)
         for (int r = 0; r < n_recordings; r++) chosen[r] = ch.multi ? mx.chosen[r] : ch.select[r] == CHANNEL_AUTO ? 0 : ch.select[r];
@@ -521,6 +598,79 @@ int bnhip_analyze_channels_pcm(bnhip_model* m, const void* pcm, const bnhip_chan
     return analyze_channels(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, threshold, out,
                             cap, n_out, chosen);
     BN_GUARD_END((void)0)
+}
+
+int bnhip_analyze_channels_pcm_events(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                                      int hop, int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter,
+                                      bnhip_event* out, size_t cap, size_t* n_out, int32_t* chosen) {
+    BN_GUARD_BEGIN
+    const EventsOut ev{filter, out};
+    return analyze_channels(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, -INFINITY,
+                            nullptr, cap, n_out, chosen, &ev);
+    BN_GUARD_END((void)0)
+}
+
+// ---- detection events
+// the tail alone over rows the host holds: one pass over the rows for every refusal, one block (rows | tables | scratch | events),
+// the rows and tables up, the tail's launches, the count and the events down
+int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                           bnhip_event* out, size_t cap, size_t* n_out) {
+    BN_GUARD_BEGIN
+    const char* what = "detection_events";
+    if (!n_out || (cap && !out) || (n_rows && !rows)) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (int rc = event_filter_check(filter)) return rc;
+    if (n_classes < 1 || n_classes > EVENT_MAX_CLASSES) return set_err(BNHIP_E_INVALID, "n_classes must be in [1, 38400]");
+    if (n_rows >= EVENT_MAX_ROWS) return set_err(BNHIP_E_INVALID, "2^31 detection rows or more");
+    int max_rec = 0;
+    for (size_t i = 0; i < n_rows; i++) {
+        const bnhip_detection& q = rows[i];
+        const std::string who = "row " + std::to_string(i) + ": ";
+        if (q.recording < 0 || q.recording > 65534) return set_err(BNHIP_E_INVALID, who + "recording must be in [0, 65534]");
+        if (q.window < 0) return set_err(BNHIP_E_INVALID, who + "negative window");
+        if (q.class_index < 0 || q.class_index >= n_classes) return set_err(BNHIP_E_INVALID, who + "class_index outside the table");
+        if (i && (q.recording < rows[i - 1].recording || (q.recording == rows[i - 1].recording && q.window < rows[i - 1].window)))
+            return set_err(BNHIP_E_INVALID, who + "rows must be nondecreasing in (recording, window)");
+        max_rec = std::max(max_rec, (int)q.recording);
+    }
+    if (n_rows == 0) { *n_out = 0; return BNHIP_OK; }
+    if (int rc = use_device(device)) return rc;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t ev_cap = std::min(cap, n_rows);
+    const size_t o_count = up(n_rows * sizeof(DetRow)), o_tab = o_count + 256, o_scr = o_tab + up(event_tables_bytes(n_classes));
+    const size_t o_out = o_scr + up(events_scratch_bytes(n_rows)), all_bytes = o_out + up(ev_cap * sizeof(Event));
+    DevBlocks b;
+    char* d = static_cast<char*>(b.get(all_bytes));
+    const unsigned long long n64 = n_rows;
+    if (b.he == hipSuccess) b.he = hipMemcpy(d, rows, n_rows * sizeof(DetRow), hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) b.he = hipMemcpy(d + o_count, &n64, 8, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) b.he = hipMemcpy(d + o_tab, filter->class_threshold, (size_t)n_classes * 4, hipMemcpyHostToDevice);
+    if (b.he == hipSuccess && filter->class_veto)
+        b.he = hipMemcpy(d + o_tab + (size_t)n_classes * 4, filter->class_veto, (size_t)n_classes, hipMemcpyHostToDevice);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    const uint8_t* d_veto = filter->class_veto ? reinterpret_cast<const uint8_t*>(d + o_tab + (size_t)n_classes * 4) : nullptr;
+    const EventFilterDev fd{reinterpret_cast<const float*>(d + o_tab), d_veto, filter->veto_threshold, filter->hold_windows, filter->min_count,
+                            filter->flags, n_classes};
+    launch_events(reinterpret_cast<const DetRow*>(d), reinterpret_cast<const unsigned long long*>(d + o_count), n_rows, fd,
+                  events_passes((unsigned long long)(max_rec + 1) * n_classes - 1), d + o_scr, reinterpret_cast<Event*>(d + o_out), ev_cap, nullptr);
+    if (int rc = launch_status(what)) { hipDeviceSynchronize(); return rc; }
+    // (the null stream orders the copies after the kernels; the first one is the call's synchronise)
+    unsigned long long total = 0;
+    b.he = hipMemcpy(&total, events_total(d + o_scr), 8, hipMemcpyDeviceToHost);
+    const size_t n_ev = (size_t)std::min<unsigned long long>(total, ev_cap);
+    if (b.he == hipSuccess && n_ev) b.he = hipMemcpy(out, d + o_out, n_ev * sizeof(Event), hipMemcpyDeviceToHost);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    *n_out = (size_t)total;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+// calculateMinDetectionsFromSettings (processor.go:1669-1729), host only
+int bnhip_event_min_count(int level, double overlap_seconds) {
+    if (level == 0) return 1;
+    static const double share[6] = {0.0, 0.20, 0.30, 0.50, 0.60, 0.70};
+    const double segment = std::max(0.1, 3.0 - overlap_seconds);
+    const double required = 6.0 / segment * (level >= 1 && level <= 5 ? share[level] : 0.30) - 1e-9;
+    return (int)std::max(1.0, std::ceil(required));
 }
 
 // the measurement alone: one DevCarve (the raw block, the descriptors and tile prefix, the partials, the sums, the decisions), one

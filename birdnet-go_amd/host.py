@@ -60,7 +60,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_process_ragged_pcm16", "bnhip_process_spectrogram_png_ragged_pcm16", "bnhip_analyze_windows",
            "bnhip_analyze_pcm_topk", "bnhip_analyze_pcm", "bnhip_analyze_mixed_windows", "bnhip_analyze_mixed_pcm_topk",
            "bnhip_analyze_mixed_pcm", "bnhip_analyze_channels_windows", "bnhip_analyze_channels_pcm_topk",
-           "bnhip_analyze_channels_pcm", "bnhip_channel_energy_pcm"]
+           "bnhip_analyze_channels_pcm", "bnhip_channel_energy_pcm", "bnhip_analyze_pcm_events", "bnhip_analyze_mixed_pcm_events",
+           "bnhip_analyze_channels_pcm_events", "bnhip_detection_events", "bnhip_event_min_count"]
 
 
 class HipError(RuntimeError):
@@ -204,6 +205,68 @@ def _channels_bytes(raw, recs):
     if x.size != want:
         raise HipError(E_INVALID, f"input size mismatch: the recordings hold {want} bytes, got {x.size} bytes")
     return x, recs
+
+
+def _analyze_events_protos(lib):
+    """... and of the detection-event entries (apart again, for the same reason)."""
+    _analyze_channels_protos(lib)
+    tail = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]                # filter, out, cap, n_out
+    lib.bnhip_analyze_pcm_events.argtypes = lib.bnhip_analyze_pcm.argtypes[:10] + tail
+    lib.bnhip_analyze_mixed_pcm_events.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + tail
+    lib.bnhip_analyze_channels_pcm_events.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + tail + [C.c_void_p]
+    lib.bnhip_detection_events.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int] + tail
+    lib.bnhip_event_min_count.argtypes = [C.c_int, C.c_double]
+    return lib
+
+
+# one event of the *_events entries (bnhip_event)
+EVENT = np.dtype([("recording", "<i4"), ("class_index", "<i4"), ("first_window", "<i4"), ("last_window", "<i4"), ("best_window", "<i4"),
+                  ("count", "<i4"), ("confidence", "<f4"), ("status", "<i4")])
+EVENTS_KEEP_DROPPED = 1
+EVENT_KEPT, EVENT_FEW, EVENT_VETOED = 0, 1, 2
+
+
+class _EventFilterStruct(C.Structure):
+    _fields_ = [("class_threshold", C.c_void_p), ("class_veto", C.c_void_p), ("veto_threshold", C.c_float), ("hold_windows", C.c_int32),
+                ("min_count", C.c_int32), ("flags", C.c_int32)]
+
+
+class EventTables:
+    """The filter of the *_events entries (bnhip_event_filter) as its tables: class_threshold float32 [n_classes] (a hit is
+    confidence > class_threshold[class]: +inf or NaN excludes the class), class_veto uint8 [n_classes] or None, veto_threshold,
+    hold_windows, min_count, flags (EVENTS_KEEP_DROPPED).  wav.EventFilter builds one from lists and seconds."""
+
+    def __init__(self, class_threshold, class_veto=None, veto_threshold=0.0, hold_windows=1, min_count=1, flags=0):
+        self.class_threshold = np.ascontiguousarray(class_threshold, np.float32).reshape(-1)
+        self.class_veto = None if class_veto is None else np.ascontiguousarray(class_veto, np.uint8).reshape(-1)
+        self.veto_threshold, self.hold_windows, self.min_count, self.flags = float(veto_threshold), int(hold_windows), int(min_count), int(flags)
+
+    def _struct(self, n_classes):
+        """-> the C struct; the tables must hold n_classes entries each (the arrays stay alive with self)."""
+        if self.class_threshold.size != n_classes or (self.class_veto is not None and self.class_veto.size != n_classes):
+            raise HipError(E_INVALID, f"the event filter's tables must hold n_classes = {n_classes} entries")
+        return _EventFilterStruct(self.class_threshold.ctypes.data, None if self.class_veto is None else self.class_veto.ctypes.data,
+                                  self.veto_threshold, self.hold_windows, self.min_count, self.flags)
+
+
+def event_min_count(level, overlap_seconds):
+    """bnhip_event_min_count (host only): the reference's minimum hit count of a detection for a false-positive filter level
+    (0-5) at an analysis overlap in seconds."""
+    return int(_analyze_events_protos(load_library()).bnhip_event_min_count(int(level), float(overlap_seconds)))
+
+
+def detection_events(rows, n_classes, filter, device=0, cap=None):
+    """bnhip_detection_events: the event tail alone over DETECTION rows the host holds (nondecreasing in (recording, window)).
+    -> the events (EVENT), ascending by (recording, class_index, first_window); with cap -> (events[:cap], total)."""
+    lib = _analyze_events_protos(load_library())
+    rows = np.ascontiguousarray(rows, DETECTION).reshape(-1)
+    room = rows.size if cap is None else int(cap)
+    out = np.zeros(room, EVENT)
+    n = C.c_size_t(0)
+    fs = filter._struct(int(n_classes))
+    _check(lib, lib.bnhip_detection_events(int(device), rows.ctypes.data if rows.size else None, rows.size, int(n_classes), C.addressof(fs),
+                                           out.ctypes.data if room else None, room, C.byref(n)))
+    return out[:n.value] if cap is None else (out[:min(room, n.value)], n.value)
 
 
 def analyze_channels_windows(recs, model_rate, n_samples, hop, min_tail=0):
@@ -561,6 +624,45 @@ class HipClassifier:
                                                                int(min_tail), activation, sensitivity, k, float(threshold),
                                                                rows.ctypes.data if cap else None, int(cap), C.byref(n), chosen.ctypes.data))
         return rows[:min(int(cap), n.value)], n.value, chosen
+
+    def _events_call(self, entry, head, n_windows, k, filter, cap, extra=()):
+        """The tail of the three *_events calls: room for every event (there are at most as many as rows) unless cap says less."""
+        _analyze_events_protos(self._lib)
+        room = int(n_windows) * min(k, self._n_classes) if cap is None else int(cap)
+        out = np.zeros(room, EVENT)
+        n = C.c_size_t(0)
+        fs = filter._struct(self._n_classes)
+        _check(self._lib, entry(*head, C.addressof(fs), out.ctypes.data if room else None, room, C.byref(n), *extra))
+        return out[:n.value] if cap is None else (out[:min(room, n.value)], n.value)
+
+    def analyze_pcm_events(self, raw, bit_depth, lengths, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
+        """bnhip_analyze_pcm_events: the analyze_pcm call answered as detection events (EVENT) - the rows merged on the device under
+        `filter` (an EventTables).  -> the events, ascending by (recording, class_index, first_window); with cap -> (events[:cap], total)."""
+        x, ln = self._analyze_args(raw, bit_depth, lengths)
+        w = analyze_windows(ln, self.n_samples, hop, min_tail)[-1]
+        _analyze_events_protos(self._lib)
+        head = (self._h, x.ctypes.data, bit_depth, ln.ctypes.data, ln.size, int(hop), int(min_tail), activation, sensitivity, k)
+        return self._events_call(self._lib.bnhip_analyze_pcm_events, head, w, k, filter, cap)
+
+    def analyze_mixed_pcm_events(self, raw, recs, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
+        """bnhip_analyze_mixed_pcm_events: analyze_mixed_pcm answered as detection events, as analyze_pcm_events answers."""
+        x, recs = self._analyze_mixed_args(raw, recs)
+        w = analyze_mixed_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]
+        _analyze_events_protos(self._lib)
+        head = (self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop), int(min_tail), activation, sensitivity, k)
+        return self._events_call(self._lib.bnhip_analyze_mixed_pcm_events, head, w, k, filter, cap)
+
+    def analyze_channels_pcm_events(self, raw, recs, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
+        """bnhip_analyze_channels_pcm_events: analyze_channels_pcm answered as detection events.  -> (events, chosen); with cap ->
+        (events[:cap], total, chosen)."""
+        self._alive()
+        _analyze_events_protos(self._lib)
+        x, recs = _channels_bytes(raw, recs)
+        w = analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]
+        chosen = np.zeros(recs.size, np.int32)
+        head = (self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop), int(min_tail), activation, sensitivity, k)
+        got = self._events_call(self._lib.bnhip_analyze_channels_pcm_events, head, w, k, filter, cap, extra=(chosen.ctypes.data,))
+        return (got, chosen) if cap is None else (got[0], got[1], chosen)
 
     # ---- plumbing
     def set_stream(self, hip_stream_ptr):

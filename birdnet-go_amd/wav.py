@@ -8,6 +8,7 @@ PCM sub-format is what `tawnyowl.wav` uses).  Framing follows the documented fil
 least `min_tail` seconds of audio).  Host-side numpy; the conversion arithmetic is restated here
 independently of the oracle (product code must not import oracle/).
 """
+import math
 import struct
 
 import numpy as np
@@ -164,8 +165,64 @@ def analyze_file(path, classifier, labels=None, sensitivity=1.0, overlap_seconds
     return rows
 
 
+def _round_down_f32(v):
+    """The float32 t with `x > t` true for exactly the float32 x with `x > v` in float64: v rounded DOWN (toward -inf).  No float32
+    lies between t and v, so the strict test keeps the same rows; rounding to nearest could land above v and drop a confidence
+    that lies between.  (The mirror of the >= threshold of the rows, which is rounded up.)"""
+    v = float(v)
+    t = np.float32(v)
+    if not np.isfinite(t):
+        return t if not np.isfinite(v) or v < 0 else np.float32(np.finfo(np.float32).max)      # (a finite v beyond float32's range)
+    return np.nextafter(t, np.float32(-np.inf)) if float(t) > v else t
+
+
+class EventFilter:
+    """The reference's result post-filters for analyze_files(events=...): which hits count and how they merge into detection events
+    (include/bnhip.h, "Detection events").
+
+    default_threshold, thresholds {class index: value}: a hit is confidence > its class's threshold.  include (indices; every other
+    class is excluded) and exclude (indices).  veto (indices): classes whose hits above veto_threshold drop the events that began
+    in the hold before them (the privacy filter's human voice) and that form no events themselves.  hold_seconds: how long an
+    event stays open after its first hit.  min_count: the hits an event needs; or level (0-5): the reference's false-positive filter
+    level, from which the count follows at the call's overlap.  keep_dropped: answer the dropped events too, with their status."""
+
+    def __init__(self, default_threshold=0.8, thresholds=None, include=None, exclude=(), veto=(), veto_threshold=0.0, hold_seconds=15.0,
+                 min_count=None, level=None, keep_dropped=False):
+        if min_count is not None and level is not None:
+            raise ValueError("min_count or level, not both")
+        self.default_threshold, self.thresholds = float(default_threshold), dict(thresholds or {})
+        self.include, self.exclude, self.veto = (None if include is None else list(include)), list(exclude), list(veto)
+        self.veto_threshold, self.hold_seconds = float(veto_threshold), float(hold_seconds)
+        self.min_count, self.level, self.keep_dropped = min_count, level, bool(keep_dropped)
+
+    def hold_windows(self, model_rate, hop):
+        return max(1, int(math.ceil(self.hold_seconds * model_rate / hop)))
+
+    def tables(self, n_classes, model_rate, hop, overlap_seconds=0.0):
+        """-> the host.EventTables of this filter for a model of n_classes classes analysed at `hop` samples of model_rate."""
+        from . import host
+        thr = np.full(n_classes, _round_down_f32(self.default_threshold), np.float32)
+        for j, v in self.thresholds.items():
+            thr[j] = _round_down_f32(v)
+        if self.include is not None:
+            out = np.ones(n_classes, bool)
+            out[self.include] = False
+            thr[out] = np.inf
+        thr[self.exclude] = np.inf
+        veto = None
+        if self.veto:
+            veto = np.zeros(n_classes, np.uint8)
+            veto[self.veto] = 1
+        if self.level is not None:
+            min_count = host.event_min_count(self.level, overlap_seconds)
+        else:
+            min_count = 1 if self.min_count is None else int(self.min_count)
+        return host.EventTables(thr, veto, _round_down_f32(self.veto_threshold), self.hold_windows(model_rate, hop), min_count,
+                                host.EVENTS_KEEP_DROPPED if self.keep_dropped else 0)
+
+
 def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
-                  device=0, device_resample=False, channels=None, return_chosen=False):
+                  device=0, device_resample=False, channels=None, return_chosen=False, events=None):
     """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
     path, each what analyze_file returns for that file.  The files' PCM bytes are sent as they are when all of them are at the
     model's rate and share one bit depth; otherwise every file goes as float32 (converted, and resampled where its rate differs,
@@ -178,7 +235,12 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     or "auto" sends every file's frames interleaved as they are, whatever its rate, depth and channel count, in one
     `bnhip_analyze_channels_pcm` call: that channel, the mean of the channels, or - decided per file on the device from the
     channels' energies, by the reference's rule - one of the two.  return_chosen=True (with channels set): -> (rows, chosen), chosen
-    the channel read of every file, or "mix"."""
+    the channel read of every file, or "mix".
+
+    events (an EventFilter): every route above answers detection events instead of rows, merged on the device in the same call
+    (`bnhip_analyze_*_pcm_events`; `threshold` gives way to the filter's own): per path a list of (start_s, end_s, label | index,
+    confidence, count), and with keep_dropped also the status; start = first_window * hop / rate, end = last_window * hop / rate +
+    the clip."""
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
     if return_chosen and channels is None:
@@ -221,6 +283,24 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     t32 = np.float32(threshold)
     if float(t32) < threshold:
         t32 = np.nextafter(t32, np.float32(np.inf))
+    if events is not None:
+        flt = events.tables(classifier.num_species(),model_rate, hop, overlap_seconds)
+        chosen = None
+        if crecs is not None:
+            ev, sel = classifier.analyze_channels_pcm_events(b"".join(bufs), crecs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)
+            chosen = ["mix" if s < 0 else int(s) for s in sel]
+        elif recs is not None:
+            ev = classifier.analyze_mixed_pcm_events(b"".join(bufs), recs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)
+        else:
+            ev = classifier.analyze_pcm_events(b"".join(bufs), bits, lengths, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)
+        out = [[] for _ in paths]
+        for e in ev:
+            start = np.float64(int(e["first_window"]) * hop) / model_rate
+            end = np.float64(int(e["last_window"]) * hop) / model_rate + clip_seconds
+            j = int(e["class_index"])
+            row = (float(start), float(end), labels[j] if labels else j, float(e["confidence"]), int(e["count"]))
+            out[int(e["recording"])].append(row + (int(e["status"]),) if events.keep_dropped else row)
+        return (out, chosen) if return_chosen else out
     chosen = None
     if crecs is not None:
         det, _, sel = classifier.analyze_channels_pcm(b"".join(bufs), crecs, model_rate, hop, min_tail, k=top_k, sensitivity=sensitivity,

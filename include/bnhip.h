@@ -329,6 +329,66 @@ int bnhip_analyze_channels_pcm(bnhip_model* m, const void* pcm, const bnhip_chan
 int bnhip_channel_energy_pcm(int device, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
                              bnhip_channel_energy* out, int32_t* chosen);
 
+/* Detection events: the rows of a file-analysis call merged on the device into what a user of the reference sees.  Its processor
+ * (internal/analysis/processor/processor.go) tests every result against a per-species threshold (getBaseConfidenceThreshold; the
+ * strict test `result.Confidence <= confidenceThreshold` at line 1046; the include / exclude lists), merges repeated hits of one
+ * species from one source into a pending detection held for a fixed time (lines 713-786: the best hit is kept, on > only, and the
+ * rest are counted), and at the flush discards a detection that matched fewer than minDetections times (shouldDiscardDetection,
+ * lines 1485-1495; calculateMinDetectionsFromSettings, lines 1669-1729; false_positive_filter.go:42-59) or began at or before a
+ * human voice was heard (lines 1497-1516; handleHumanDetection, lines 1319-1334).  Here the clock is audio time, in windows.
+ *   rows     The call's top-k rows (recording r, window w, class c, confidence x), by recording, then window, then rank.
+ *   hit      class_veto[c] == 0 and x > class_threshold[c]: float32, strict, false for a NaN on either side - a threshold of +inf or
+ *            NaN excludes its class, which is how include / exclude lists and custom thresholds are stated.
+ *   veto hit class_veto[c] != 0 and x > veto_threshold: marks window w of recording r (LastHumanDetection).  A veto class forms no
+ *            event.  class_veto may be NULL: no veto class.
+ *   events   The hits of one (r, c), by window (equal windows in row order; a row given twice is two hits).  The first opens an event
+ *            at b = w; every following hit with w < b + hold_windows joins it; the first with w >= b + hold_windows opens the next
+ *            event at its own window (FlushDeadline = created + detectionWindow: the hold is fixed from the first hit and does not
+ *            slide).  first_window = b, last_window = the last hit that joined, count = the hits, confidence = the largest, best_window
+ *            = the window of the largest (ties: the earliest).
+ *   status   1 when count < min_count; else 2 when recording r has a veto hit at a window v with b <= v < b + hold_windows; else 0.
+ *            Without BNHIP_EVENTS_KEEP_DROPPED in flags only status-0 events are answered; with it all are, each with its status.
+ *   order    Ascending by (recording, class_index, first_window).  *n_out = the events answered; min(cap, *n_out) are written in that
+ *            order (out may be NULL when cap is 0).  The same rows give the same bytes on every run.
+ *   bnhip_analyze_pcm_events / _mixed_pcm_events / _channels_pcm_events  The arguments of bnhip_analyze_pcm / _mixed_pcm / _channels_pcm
+ *            with the threshold replaced by the filter (its tables hold n_classes entries of the model) and the rows by the events:
+ *            every non-NaN row of the call stays on the device and the tail runs behind the last chunk - no row crosses PCIe.  The
+ *            fast paths of the mixed and channels calls hold as before.
+ *   bnhip_detection_events  The tail alone over rows the host holds (kept from an earlier call, or of several calls joined):
+ *            nondecreasing in (recording, window), checked on the host in one pass.  n_rows == 0 answers zero events.
+ *   bnhip_event_min_count  Host only: calculateMinDetectionsFromSettings - 3.0 s chunk, 6.0 s reference window, segment = max(0.1, 3 -
+ *            overlap), shares 0 / 0.20 / 0.30 / 0.50 / 0.60 / 0.70 for levels 0-5 (any other level: 0.30), max(1, ceil(6 / segment *
+ *            share - 1e-9)); level 0 gives 1.
+ * BNHIP_E_INVALID (nothing written, the handle stays usable, before any device call): everything the sibling entry refuses, a NULL
+ * filter or class_threshold, hold_windows < 1, min_count < 1, unknown flag bits, windows * min(k, n_classes) of 2^31 or more; for
+ * bnhip_detection_events: n_classes outside 1..38400, a recording outside 0..65534, a negative window, a class outside the table,
+ * rows out of order, n_rows of 2^31 or more. */
+#define BNHIP_EVENTS_KEEP_DROPPED 1
+typedef struct bnhip_event_filter {
+    const float* class_threshold;      /* [n_classes] */
+    const uint8_t* class_veto;         /* [n_classes] or NULL */
+    float veto_threshold;
+    int32_t hold_windows, min_count, flags;
+} bnhip_event_filter;
+typedef struct bnhip_event {           /* 32 bytes */
+    int32_t recording, class_index, first_window, last_window, best_window, count;
+    float confidence;
+    int32_t status;
+} bnhip_event;
+int bnhip_analyze_pcm_events(bnhip_model* m, const void* pcm, int bits_per_sample, const int64_t* lengths, int n_recordings, int hop,
+                             int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter,
+                             bnhip_event* out, size_t cap, size_t* n_out);
+int bnhip_analyze_mixed_pcm_events(bnhip_model* m, const void* pcm, const bnhip_recording* recs, int n_recordings, int model_rate,
+                                   int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                   const bnhip_event_filter* filter, bnhip_event* out, size_t cap, size_t* n_out);
+int bnhip_analyze_channels_pcm_events(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                      int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                      const bnhip_event_filter* filter, bnhip_event* out, size_t cap, size_t* n_out,
+                                      int32_t* chosen);
+int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                           bnhip_event* out, size_t cap, size_t* n_out);
+int bnhip_event_min_count(int level, double overlap_seconds);
+
 /* Ultrasonic frame-CV filter (internal/audiocore/ultrasonic/filter.go:20-66), float64 throughout.
  * samples: host float64 [n_clips * n] (int16/32768 as float64, convert/pcm.go:108-113).
  * cv/ok: [n_clips]. device: HIP device ordinal. */
