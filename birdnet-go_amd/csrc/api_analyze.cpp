@@ -15,6 +15,7 @@
 #include "api_model.h"
 #include "api_oneshot.h"
 #include "channels.h"
+#include "clips.h"
 #include "events.h"
 #include "resample.h"
 
@@ -247,11 +248,118 @@ size_t event_tables_bytes(int n_classes) { return (size_t)n_classes * 4 + (size_
         if (ok && e_ != hipSuccess) { ok = false; err = std::string(what) + ": " + hipGetErrorString(e_); } \
     } while (0)
 
+// ---- the recordings on the device (every device entry of this file)
+// What a call's recordings need there, worked out on the host.  The slot block: recording r at slot[2 r] (analyze.h).
+// mixed: the raw block (every recording as it is in its file, from a 16-byte line on), a descriptor per recording and the tile prefix
+// channels: the raw block holds interleaved frames; beside the descriptors lie the channel counts and the selection table
+// [n_rec] each, and the recordings that ask for a measurement have a descriptor and a tile prefix of their own (channels.h)
+struct SlotPlan {
+    size_t block_bytes = 0, raw_bytes = 0, rs_lds = 0;
+    std::vector<ResampleSlotDesc> desc;
+    std::vector<long long> tile0, etile0;
+    std::vector<EnergyDesc> edesc;
+    std::vector<int> chsel;
+    bool mc = false;
+    long long n_etiles = 0;
+};
+// bits / lengths state the slots (mixed: float32, the n_out); fills slot [n_rec][2]
+SlotPlan slot_plan(const int64_t* lengths, int n_recordings, int bits, const Mixed* mx, long long* slot) {
+    SlotPlan sp;
+    for (int r = 0; r < n_recordings; r++) {
+        slot[2 * r] = (long long)sp.block_bytes; slot[2 * r + 1] = lengths[r];
+        sp.block_bytes += analyze_slot_bytes(lengths[r], bits);
+    }
+    sp.mc = mx && !mx->channels.empty();
+    if (mx) {
+        sp.desc.resize(n_recordings); sp.tile0.assign((size_t)n_recordings + 1, 0);
+        for (int r = 0; r < n_recordings; r++) {
+            const bnhip_recording& q = mx->recs[r];
+            ResampleSlotDesc& ds = sp.desc[r];
+            ds.in_off = (long long)sp.raw_bytes; ds.out_off = slot[2 * r];
+            ds.n_in = (int)q.length; ds.n_out = (int)lengths[r]; ds.bits = q.bits_per_sample;
+            ds.L = ds.M = ds.T = ds.half = ds.tab_off = 0;
+            if (mx->plan_of[r] >= 0) {
+                const RatePlan& rp = mx->plans[mx->plan_of[r]];
+                ds.L = rp.p.L; ds.M = rp.p.M; ds.T = rp.p.T; ds.half = rp.p.half; ds.tab_off = (int)rp.tab_off;
+                sp.rs_lds = std::max(sp.rs_lds, resample_lds(rp.p.L, rp.p.M, rp.p.T));
+            }
+            sp.raw_bytes += ((size_t)q.length * mx->ch(r) * analyze_sample_bytes(q.bits_per_sample) + 15) / 16 * 16;
+            sp.tile0[r + 1] = sp.tile0[r] + resample_slot_tiles(lengths[r]);
+        }
+    }
+    if (sp.mc) {
+        sp.chsel.assign(mx->channels.begin(), mx->channels.end());
+        sp.chsel.insert(sp.chsel.end(), mx->select.begin(), mx->select.end());
+        sp.etile0.push_back(0);
+        for (int r = 0; r < n_recordings; r++) {
+            if (mx->select[r] != CHANNEL_AUTO) continue;
+            sp.edesc.push_back(EnergyDesc{sp.desc[r].in_off, sp.desc[r].n_in, sp.desc[r].bits, mx->channels[r], r});
+            sp.etile0.push_back(sp.etile0.back() + energy_tiles(sp.desc[r].n_in));
+        }
+    }
+    sp.n_etiles = sp.edesc.empty() ? 0 : sp.etile0.back();
+    return sp;
+}
+
+// where a call has carved the plan's parts: the slot block and its bytes up to the next part (zero-filled on the fast path), then
+// (mixed) the raw block, the descriptors, the tile prefix, (channels) the counts and selections, the measurement's descriptors, tile
+// prefix, partials and sums
+struct SlotDev {
+    char* block;
+    size_t block_room;
+    char *raw, *desc, *tile0, *chsel, *edesc, *etile0, *part, *energy;
+};
+
+// The recordings go up and the slot block is filled, on s: the slots' zero fill and one copy per recording into its slot, or
+// (mixed) one copy per recording into the raw block, the tables, the measurement where a recording asks for one, and the slot
+// launch (k_resample_slots writes every slot whole, its zeros included).  The first failure is left in ok / err.
+void slot_upload(const SlotPlan& sp, const void* pcm, int bits, const int64_t* lengths, int n_recordings, const long long* slot, const Mixed* mx,
+                 int device, const SlotDev& dv, hipStream_t s, bool& ok, std::string& err) {
+    if (!mx) AN_HIP(hipMemsetAsync(dv.block, 0, dv.block_room, s), "memset");
+    const char* src = static_cast<const char*>(pcm);
+    for (int r = 0; ok && r < n_recordings; r++) {
+        const size_t bytes = mx ? (size_t)mx->recs[r].length * mx->ch(r) * analyze_sample_bytes(mx->recs[r].bits_per_sample)
+                                : (size_t)lengths[r] * analyze_sample_bytes(bits);
+        AN_HIP(hipMemcpyAsync(mx ? dv.raw + sp.desc[r].in_off : dv.block + slot[2 * r], src, bytes, hipMemcpyHostToDevice, s), "H2D copy");
+        src += bytes;
+    }
+    if (!mx) return;
+    // (the lock is held from the tables' lookup until the launch that reads them is enqueued, api_oneshot.h)
+    TableLock lock(g_rate_tables.mu);
+    const float* d_tables = mx->plans.empty() ? nullptr : mixed_tables(*mx, device, lock);
+    if (ok && !mx->plans.empty() && !d_tables) { ok = false; err = "phase table upload failed"; }
+    AN_HIP(hipMemcpyAsync(dv.desc, sp.desc.data(), sp.desc.size() * sizeof(ResampleSlotDesc), hipMemcpyHostToDevice, s), "H2D copy");
+    AN_HIP(hipMemcpyAsync(dv.tile0, sp.tile0.data(), sp.tile0.size() * 8, hipMemcpyHostToDevice, s), "H2D copy");
+    const ResampleSlotDesc* d_desc = reinterpret_cast<const ResampleSlotDesc*>(dv.desc);
+    const long long* d_tile0 = reinterpret_cast<const long long*>(dv.tile0);
+    if (sp.mc) {
+        // the selections go up as asked for; the measurement, if any recording asks for one, overwrites its entries on the
+        // device, and the slot launch behind it reads them there
+        int* d_ch = reinterpret_cast<int*>(dv.chsel);
+        AN_HIP(hipMemcpyAsync(d_ch, sp.chsel.data(), sp.chsel.size() * 4, hipMemcpyHostToDevice, s), "H2D copy");
+        if (!sp.edesc.empty()) {
+            AN_HIP(hipMemcpyAsync(dv.edesc, sp.edesc.data(), sp.edesc.size() * sizeof(EnergyDesc), hipMemcpyHostToDevice, s), "H2D copy");
+            AN_HIP(hipMemcpyAsync(dv.etile0, sp.etile0.data(), sp.etile0.size() * 8, hipMemcpyHostToDevice, s), "H2D copy");
+            if (ok) launch_channel_energy(dv.raw, reinterpret_cast<const EnergyDesc*>(dv.edesc), reinterpret_cast<const long long*>(dv.etile0),
+                                          (int)sp.edesc.size(), sp.n_etiles, reinterpret_cast<unsigned long long*>(dv.part),
+                                          reinterpret_cast<unsigned long long*>(dv.energy), d_ch + n_recordings, s);
+        }
+        if (ok) launch_resample_slots_mc(dv.raw, dv.block, d_tables, d_desc, d_tile0, n_recordings, sp.tile0[n_recordings], sp.rs_lds, d_ch,
+                                         d_ch + n_recordings, s);
+    } else if (ok) {
+        launch_resample_slots(dv.raw, dv.block, d_tables, d_desc, d_tile0, n_recordings, sp.tile0[n_recordings], sp.rs_lds, s);
+    }
+}
+
+// what bnhip_analyze_channels_pcm_clips adds to its events call: the export settings and where everything goes (clips.h)
+struct ClipsTail { const bnhip_clip_export* x; bnhip_clips_out* o; int model_rate; };
+
 // bnhip_analyze_pcm_topk, and with `det` the detection rows behind it.  mx (the mixed entries): pcm holds the recordings as mx
-// describes them, and bits / lengths state the float32 slots they are resampled into - what the chunk loop frames.
+// describes them, and bits / lengths state the float32 slots they are resampled into - what the chunk loop frames.  ct: with the
+// events down and the recordings still in their slots, the clip export runs as the call's continuation.
 int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, int n_recordings, int hop, int64_t min_tail, int activation,
             double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold, bnhip_detection* out_rows, size_t cap,
-            size_t* n_out, Mixed* mx = nullptr, const EventsOut* ev = nullptr) {
+            size_t* n_out, Mixed* mx = nullptr, const EventsOut* ev = nullptr, const ClipsTail* ct = nullptr) {
     if (!m || !pcm || !lengths) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (det ? (!n_out || (cap && !(ev ? (const void*)ev->out : (const void*)out_rows))) : (!out_conf || !out_idx))
         return set_err(BNHIP_E_INVALID, "NULL argument");
@@ -278,48 +386,14 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     const long long W64 = analyze_windows(len64.data(), n_recordings, e.n_samples, hop, min_tail, first);
     if (W64 > INT_MAX) return set_err(BNHIP_E_INVALID, "more than INT_MAX windows");
     const int W = (int)W64, kk = std::min(k, e.n_classes);
-    size_t block_bytes = 0;
-    for (int r = 0; r < n_recordings; r++) {
-        slot[2 * r] = (long long)block_bytes; slot[2 * r + 1] = lengths[r];
-        block_bytes += analyze_slot_bytes(lengths[r], bits);
-    }
-    // mixed: the raw block (every recording as it is in its file, from a 16-byte line on), a descriptor per recording and the tile prefix
-    // channels: the raw block holds interleaved frames; beside the descriptors lie the channel counts and the selection table
-    // [n_rec] each, and the recordings that ask for a measurement have a descriptor and a tile prefix of their own (channels.h)
-    std::vector<ResampleSlotDesc> desc;
-    std::vector<long long> tile0, etile0;
-    std::vector<EnergyDesc> edesc;
-    std::vector<int> chsel;
-    const bool mc = mx && !mx->channels.empty();
-    size_t raw_bytes = 0, rs_lds = 0;
-    if (mx) {
-        desc.resize(n_recordings); tile0.assign((size_t)n_recordings + 1, 0);
-        for (int r = 0; r < n_recordings; r++) {
-            const bnhip_recording& q = mx->recs[r];
-            ResampleSlotDesc& ds = desc[r];
-            ds.in_off = (long long)raw_bytes; ds.out_off = slot[2 * r];
-            ds.n_in = (int)q.length; ds.n_out = (int)lengths[r]; ds.bits = q.bits_per_sample;
-            ds.L = ds.M = ds.T = ds.half = ds.tab_off = 0;
-            if (mx->plan_of[r] >= 0) {
-                const RatePlan& rp = mx->plans[mx->plan_of[r]];
-                ds.L = rp.p.L; ds.M = rp.p.M; ds.T = rp.p.T; ds.half = rp.p.half; ds.tab_off = (int)rp.tab_off;
-                rs_lds = std::max(rs_lds, resample_lds(rp.p.L, rp.p.M, rp.p.T));
-            }
-            raw_bytes += ((size_t)q.length * mx->ch(r) * analyze_sample_bytes(q.bits_per_sample) + 15) / 16 * 16;
-            tile0[r + 1] = tile0[r] + resample_slot_tiles(lengths[r]);
-        }
-    }
-    if (mc) {
-        chsel.assign(mx->channels.begin(), mx->channels.end());
-        chsel.insert(chsel.end(), mx->select.begin(), mx->select.end());
-        etile0.push_back(0);
-        for (int r = 0; r < n_recordings; r++) {
-            if (mx->select[r] != CHANNEL_AUTO) continue;
-            edesc.push_back(EnergyDesc{desc[r].in_off, desc[r].n_in, desc[r].bits, mx->channels[r], r});
-            etile0.push_back(etile0.back() + energy_tiles(desc[r].n_in));
-        }
-    }
-    const long long n_etiles = edesc.empty() ? 0 : etile0.back();
+    const SlotPlan sp = slot_plan(lengths, n_recordings, bits, mx, slot);
+    const size_t block_bytes = sp.block_bytes, raw_bytes = sp.raw_bytes;
+    const std::vector<ResampleSlotDesc>& desc = sp.desc;
+    const std::vector<long long>&tile0 = sp.tile0, &etile0 = sp.etile0;
+    const std::vector<EnergyDesc>& edesc = sp.edesc;
+    const std::vector<int>& chsel = sp.chsel;
+    const bool mc = sp.mc;
+    const long long n_etiles = sp.n_etiles;
     if (hipSetDevice(e.device) != hipSuccess) return set_err(BNHIP_E_RUNTIME, "hipSetDevice failed");
     // whatever an earlier asynchronous call still has queued on the engine's streams finishes first (as host_run does)
     e.sync_contexts();
@@ -349,50 +423,14 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
     }
     bool ok = true;
     std::string err;
-    // the slots' zero fill, then one copy per recording into its slot (mixed: into the raw block; k_resample_slots writes every
-    // slot whole, its zeros included)
-    if (!mx) AN_HIP(hipMemsetAsync(d, 0, o_table, e.stream), "memset");
-    const char* src = static_cast<const char*>(pcm);
-    for (int r = 0; ok && r < n_recordings; r++) {
-        const size_t bytes = mx ? (size_t)mx->recs[r].length * mx->ch(r) * analyze_sample_bytes(mx->recs[r].bits_per_sample)
-                                : (size_t)lengths[r] * analyze_sample_bytes(bits);
-        AN_HIP(hipMemcpyAsync(mx ? d + o_raw + desc[r].in_off : d + slot[2 * r], src, bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
-        src += bytes;
-    }
+    const SlotDev dv{d, o_table, d + o_raw, d + o_desc, d + o_desc + up(desc_bytes), d + o_chsel, d + o_edesc, d + o_etile0, d + o_part, d + o_energy};
+    slot_upload(sp, pcm, bits, lengths, n_recordings, slot, mx, e.device, dv, e.stream, ok, err);
     AN_HIP(hipMemcpyAsync(d + o_table, table.data(), table_bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
     if (ev) {
         AN_HIP(hipMemcpyAsync(d + o_evtab, ev->f->class_threshold, (size_t)e.n_classes * 4, hipMemcpyHostToDevice, e.stream), "H2D copy");
         if (ev->f->class_veto)
             AN_HIP(hipMemcpyAsync(d + o_evtab + (size_t)e.n_classes * 4, ev->f->class_veto, (size_t)e.n_classes, hipMemcpyHostToDevice, e.stream),
                    "H2D copy");
-    }
-    if (mx) {
-        // (the lock is held from the tables' lookup until the launch that reads them is enqueued, api_oneshot.h)
-        TableLock lock(g_rate_tables.mu);
-        const float* d_tables = mx->plans.empty() ? nullptr : mixed_tables(*mx, e.device, lock);
-        if (ok && !mx->plans.empty() && !d_tables) { ok = false; err = "phase table upload failed"; }
-        char* d_tile0 = d + o_desc + up(desc_bytes);
-        AN_HIP(hipMemcpyAsync(d + o_desc, desc.data(), desc_bytes, hipMemcpyHostToDevice, e.stream), "H2D copy");
-        AN_HIP(hipMemcpyAsync(d_tile0, tile0.data(), tile0.size() * 8, hipMemcpyHostToDevice, e.stream), "H2D copy");
-        if (mc) {
-            // the selections go up as asked for; the measurement, if any recording asks for one, overwrites its entries on the
-            // device, and the slot launch behind it reads them there
-            int* d_ch = reinterpret_cast<int*>(d + o_chsel);
-            AN_HIP(hipMemcpyAsync(d_ch, chsel.data(), chsel.size() * 4, hipMemcpyHostToDevice, e.stream), "H2D copy");
-            if (!edesc.empty()) {
-                AN_HIP(hipMemcpyAsync(d + o_edesc, edesc.data(), edesc.size() * sizeof(EnergyDesc), hipMemcpyHostToDevice, e.stream), "H2D copy");
-                AN_HIP(hipMemcpyAsync(d + o_etile0, etile0.data(), etile0.size() * 8, hipMemcpyHostToDevice, e.stream), "H2D copy");
-                if (ok) launch_channel_energy(d + o_raw, reinterpret_cast<const EnergyDesc*>(d + o_edesc), reinterpret_cast<const long long*>(d + o_etile0),
-                                              (int)edesc.size(), n_etiles, reinterpret_cast<unsigned long long*>(d + o_part),
-                                              reinterpret_cast<unsigned long long*>(d + o_energy), d_ch + n_recordings, e.stream);
-            }
-            if (ok) launch_resample_slots_mc(d + o_raw, d, d_tables, reinterpret_cast<const ResampleSlotDesc*>(d + o_desc),
-                                             reinterpret_cast<const long long*>(d_tile0), n_recordings, tile0[n_recordings], rs_lds, d_ch,
-                                             d_ch + n_recordings, e.stream);
-        } else if (ok) {
-            launch_resample_slots(d + o_raw, d, d_tables, reinterpret_cast<const ResampleSlotDesc*>(d + o_desc),
-                                  reinterpret_cast<const long long*>(d_tile0), n_recordings, tile0[n_recordings], rs_lds, e.stream);
-        }
     }
     WinView view;
     view.first = reinterpret_cast<const long long*>(d + o_table);
@@ -448,10 +486,16 @@ int analyze(bnhip_model* m, const void* pcm, int bits, const int64_t* lengths, i
         const hipError_t he = hipStreamSynchronize(e.stream);
         if (ok && he != hipSuccess) { ok = false; err = std::string("file analysis: ") + hipGetErrorString(he); }
     }
+    // the continuation: nothing of the call is in flight any more, and the recordings are where the windows were framed from
+    int rc_tail = BNHIP_OK;
+    if (ok && ct) {
+        ct->o->n_events = (size_t)total;
+        rc_tail = clip_export_run(e.device, d, bits, view.slot, lengths, n_recordings, hop, ct->model_rate, ct->x, ct->o);
+    }
     hipFree(d);
     if (!ok) { (void)hipGetLastError(); e.mm_dirty = true; return set_err(BNHIP_E_RUNTIME, err); }
     if (det) *n_out = (size_t)total;
-    return BNHIP_OK;
+    return rc_tail;
 }
 
 }  // namespace
@@ -564,7 +608,8 @@ long long bnhip_analyze_channels_windows(const bnhip_channels_recording* recs, i
 // the two device entries: a burst of mono recordings is the mixed call, with that call's own fast path
 static int analyze_channels(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate, int hop,
                             int64_t min_tail, int activation, double sensitivity, int k, float* out_conf, int32_t* out_idx, bool det, float threshold,
-                            bnhip_detection* out_rows, size_t cap, size_t* n_out, int32_t* chosen, const EventsOut* ev = nullptr) {
+                            bnhip_detection* out_rows, size_t cap, size_t* n_out, int32_t* chosen, const EventsOut* ev = nullptr,
+                            const ClipsTail* ct = nullptr) {
     Channels ch;
     if (int rc = channels_check(recs, n_recordings, false, &ch)) return rc;
     Mixed mx;
@@ -574,7 +619,7 @@ static int analyze_channels(bnhip_model* m, const void* pcm, const bnhip_channel
         mx.channels = ch.channels; mx.select = ch.select;
     }
     const int rc = analyze(m, pcm, mx.plain ? ch.base[0].bits_per_sample : 0, mx.n_out.data(), n_recordings, hop, min_tail, activation, sensitivity, k,
-                           out_conf, out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx, ev);
+                           out_conf, out_idx, det, threshold, out_rows, cap, n_out, mx.plain ? nullptr : &mx, ev, ct);
     if (rc == BNHIP_OK && chosen) {
         // (one channel: channel 0 is what auto picks, and a mix of one channel is asked for and answered as a mix)
         for (int r = 0; r < n_recordings; r++) chosen[r] = ch.multi ? mx.chosen[r] : ch.select[r] == CHANNEL_AUTO ? 0 : ch.select[r];
@@ -607,6 +652,81 @@ int bnhip_analyze_channels_pcm_events(bnhip_model* m, const void* pcm, const bnh
     const EventsOut ev{filter, out};
     return analyze_channels(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, -INFINITY,
                             nullptr, cap, n_out, chosen, &ev);
+    BN_GUARD_END((void)0)
+}
+
+// ---- detection clips (clips.h; the span rule and the export's second phase: api_clips.cpp)
+// the events call with the clip export as its continuation
+int bnhip_analyze_channels_pcm_clips(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                                     int hop, int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter,
+                                     int32_t* chosen, const bnhip_clip_export* x, bnhip_clips_out* out) {
+    BN_GUARD_BEGIN
+    if (int rc = clip_export_check(x, out, model_rate)) return rc;
+    if (int rc = event_filter_check(filter)) return rc;
+    if (filter->flags & BNHIP_EVENTS_KEEP_DROPPED) return set_err(BNHIP_E_INVALID, "the clip export takes kept events only: BNHIP_EVENTS_KEEP_DROPPED is refused");
+    const EventsOut ev{filter, out->events};
+    const ClipsTail ct{x, out, model_rate};
+    size_t n_events = 0;
+    return analyze_channels(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, nullptr, nullptr, true, -INFINITY,
+                            nullptr, out->event_cap, &n_events, chosen, &ev, &ct);
+    BN_GUARD_END((void)0)
+}
+
+// the cut alone: one DevCarve (the slot block, the slot table, with a burst off the fast path the parts of slot_upload, the cut's
+// tables, the clips), the upload, the cut, one D2H copy
+int bnhip_recording_clips_pcm16(int device, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                                const bnhip_clip_span* spans, int n_spans, int16_t* out_pcm) {
+    BN_GUARD_BEGIN
+    const char* what = "recording_clips_pcm16";
+    if (!pcm || !spans || !out_pcm) return set_err(BNHIP_E_INVALID, "NULL argument");
+    Channels ch;
+    if (int rc = channels_check(recs, n_recordings, false, &ch)) return rc;
+    Mixed mx;
+    if (int rc = mixed_check(ch.base.data(), n_recordings, model_rate, &mx)) return rc;
+    if (ch.multi) {
+        mx.plain = false;
+        mx.channels = ch.channels; mx.select = ch.select;
+    }
+    if (n_spans < 1 || n_spans > 65535) return set_err(BNHIP_E_INVALID, "n_spans must be in [1, 65535]");
+    long long total = 0;
+    for (int i = 0; i < n_spans; i++) {
+        const bnhip_clip_span& q = spans[i];
+        const std::string who = "span " + std::to_string(i) + ": ";
+        if (q.recording < 0 || q.recording >= n_recordings) return set_err(BNHIP_E_INVALID, who + "recording outside the table");
+        if (q.length < 0) return set_err(BNHIP_E_INVALID, who + "negative length");
+        if (q.start < 0 || q.start > mx.n_out[q.recording] - q.length) return set_err(BNHIP_E_INVALID, who + "outside its recording");
+        total += q.length;
+    }
+    if (total > RAGGED_MAX_SAMPLES) return set_err(BNHIP_E_INVALID, "the clips' total length must be below 2^36 samples");
+    Mixed* pm = mx.plain ? nullptr : &mx;
+    if (pm) if (int rc = mixed_plans(pm)) return rc;
+    const CutPlan plan = cut_plan(spans, (size_t)n_spans, n_spans);
+    if (plan.n_clips() == 0) return BNHIP_OK;
+    const int bits = pm ? 0 : ch.base[0].bits_per_sample;
+    std::vector<long long> slot((size_t)n_recordings * 2);
+    const SlotPlan sp = slot_plan(mx.n_out.data(), n_recordings, bits, pm, slot.data());
+    if (int rc = use_device(device)) return rc;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    DevCarve cv;
+    const size_t o_block = cv.add(up(sp.block_bytes)), o_slot = cv.add(slot.size() * 8), o_tab = cv.add(plan.table_bytes());
+    const size_t o_out = cv.add((size_t)total * 2);
+    const size_t o_raw = cv.add(sp.raw_bytes), o_desc = cv.add(sp.desc.size() * sizeof(ResampleSlotDesc)), o_tile0 = cv.add(sp.tile0.size() * 8);
+    const size_t o_chsel = cv.add(sp.chsel.size() * 4), o_edesc = cv.add(sp.edesc.size() * sizeof(EnergyDesc)), o_etile0 = cv.add(sp.etile0.size() * 8);
+    const size_t o_part = cv.add((size_t)sp.n_etiles * ENERGY_ROW_BYTES), o_energy = cv.add(sp.edesc.size() * ENERGY_ROW_BYTES);
+    DevBlocks b;
+    cv.alloc(b);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    bool ok = true;
+    std::string err;
+    const SlotDev dv{cv.at<char>(o_block), up(sp.block_bytes), cv.at<char>(o_raw), cv.at<char>(o_desc), cv.at<char>(o_tile0), cv.at<char>(o_chsel),
+                     cv.at<char>(o_edesc), cv.at<char>(o_etile0), cv.at<char>(o_part), cv.at<char>(o_energy)};
+    slot_upload(sp, pcm, bits, mx.n_out.data(), n_recordings, slot.data(), pm, device, dv, nullptr, ok, err);
+    AN_HIP(hipMemcpyAsync(cv.at<void>(o_slot), slot.data(), slot.size() * 8, hipMemcpyHostToDevice, nullptr), "H2D copy");
+    if (ok) AN_HIP(cut_enqueue(plan, dv.block, bits, cv.at<long long>(o_slot), cv.at<void>(o_tab), cv.at<int16_t>(o_out), nullptr), "clip cut");
+    // (the null stream orders the copy after the kernels; it is the call's synchronise)
+    if (ok) AN_HIP(hipMemcpy(out_pcm, cv.at<void>(o_out), (size_t)total * 2, hipMemcpyDeviceToHost), "D2H copy");
+    if (!ok) { hipDeviceSynchronize(); (void)hipGetLastError(); return set_err(BNHIP_E_RUNTIME, std::string(what) + ": " + err); }
+    return BNHIP_OK;
     BN_GUARD_END((void)0)
 }
 

@@ -13,6 +13,7 @@
 #include <numeric>
 
 #include "api_oneshot.h"
+#include "clip_source.h"
 #include "flac_decode.h"
 #include "kernels.h"
 #include "png.h"
@@ -144,15 +145,7 @@ void render_enqueue(const RenderTables& t, const DevCarve& cv, const RenderParts
                        cv.at<uint8_t>(p.o_img), cv.at<void>(p.o_rows), nullptr);
 }
 
-// Where the int16 clips of a render come from: the host's PCM, a decode on the device, or the processed-audio chain.  reserve() adds the source's
-// own parts to the call's DevCarve, fill() enqueues on the null stream what puts the clips at d_pcm, finish() runs after the
-// call's synchronise.
-struct ClipSource {
-    virtual void reserve(DevCarve&) {}
-    virtual hipError_t fill(const DevCarve& cv, int16_t* d_pcm, size_t pcm_bytes) = 0;
-    virtual hipError_t finish(const DevCarve&) { return hipSuccess; }
-    virtual ~ClipSource() {}
-};
+// The sources of this file's entries (ClipSource, clip_source.h): the host's PCM, a decode on the device, the processed-audio chain.
 struct PcmSource : ClipSource {
     const int16_t* pcm;
     explicit PcmSource(const int16_t* p) : pcm(p) {}
@@ -308,6 +301,19 @@ int device_run(const char* what, const char* size_entry, int device, const void*
 }
 
 }  // namespace
+
+namespace bnhip {
+
+int spectrogram_image_check(int width, int height, const double* window, double top_db, double range_db) {
+    return spec_image_check(width, height, window, top_db, range_db);
+}
+int spectrogram_png_run(const char* what, int device, ClipSource& src, const Clips& c, int rate_in, int rate_out, int width, int height,
+                        const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out, size_t out_cap,
+                        uint64_t* offsets) {
+    return png_run(what, device, src, c, rate_in, rate_out, width, height, window, top_db, range_db, palette, out, out_cap, offsets);
+}
+
+}  // namespace bnhip
 
 extern "C" {
 

@@ -19,4 +19,13 @@ template <> __device__ __forceinline__ float frame_sample<24>(const char* p, lon
 }
 template <> __device__ __forceinline__ float frame_sample<32>(const char* p, long long i) { return (float)reinterpret_cast<const int32_t*>(p)[i] / 2147483648.0f; }
 
+// The way back, for a clip cut out of a recording (k_cut_clips, clips.hip): x is what frame_sample answers, q = clamp(rint(x * 2^15),
+// -32768, 32767) with ties to even, and a NaN gives 0.  x * 2^15 is exact (or an infinity), so the one rounding is rint's; a 16-bit
+// sample comes back as itself.
+__host__ __device__ __forceinline__ int16_t sample_pcm16(float x) {
+    const float y = rintf(x * 32768.0f);
+    if (!(y == y)) return 0;
+    return (int16_t)(y < -32768.0f ? -32768.0f : y > 32767.0f ? 32767.0f : y);
+}
+
 }  // namespace bnhip

@@ -61,7 +61,8 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_analyze_pcm_topk", "bnhip_analyze_pcm", "bnhip_analyze_mixed_windows", "bnhip_analyze_mixed_pcm_topk",
            "bnhip_analyze_mixed_pcm", "bnhip_analyze_channels_windows", "bnhip_analyze_channels_pcm_topk",
            "bnhip_analyze_channels_pcm", "bnhip_channel_energy_pcm", "bnhip_analyze_pcm_events", "bnhip_analyze_mixed_pcm_events",
-           "bnhip_analyze_channels_pcm_events", "bnhip_detection_events", "bnhip_event_min_count"]
+           "bnhip_analyze_channels_pcm_events", "bnhip_detection_events", "bnhip_event_min_count",
+           "bnhip_event_clip_spans", "bnhip_recording_clips_pcm16", "bnhip_analyze_channels_pcm_clips"]
 
 
 class HipError(RuntimeError):
@@ -267,6 +268,98 @@ def detection_events(rows, n_classes, filter, device=0, cap=None):
     _check(lib, lib.bnhip_detection_events(int(device), rows.ctypes.data if rows.size else None, rows.size, int(n_classes), C.addressof(fs),
                                            out.ctypes.data if room else None, room, C.byref(n)))
     return out[:n.value] if cap is None else (out[:min(room, n.value)], n.value)
+
+
+def _analyze_clips_protos(lib):
+    """... and of the detection-clip entries (apart again, for the same reason)."""
+    _analyze_events_protos(lib)
+    lib.bnhip_event_clip_spans.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.bnhip_recording_clips_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.bnhip_analyze_channels_pcm_clips.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return lib
+
+
+# one span of the detection-clip entries (bnhip_clip_span): samples at the model's rate
+CLIP_SPAN = np.dtype([("start", "<i8"), ("length", "<i4"), ("recording", "<i4")])
+
+
+class _ClipExportStruct(C.Structure):
+    _fields_ = [("pre_samples", C.c_int32), ("post_samples", C.c_int32), ("max_samples", C.c_int32), ("extended", C.c_int32),
+                ("normalize", C.c_int32), ("gate_fallback", C.c_int32), ("target_lufs", C.c_double), ("true_peak_dbtp", C.c_double),
+                ("max_gain_db", C.c_double), ("seek_interval", C.c_int32), ("lpc_order", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("rate_out", C.c_int32), ("reserved", C.c_int32), ("window", C.c_void_p), ("top_db", C.c_double),
+                ("range_db", C.c_double), ("palette", C.c_void_p)]
+
+
+class _ClipsOutStruct(C.Structure):
+    _fields_ = [("events", C.c_void_p), ("event_cap", C.c_size_t), ("n_events", C.c_size_t), ("spans", C.c_void_p), ("loudness", C.c_void_p),
+                ("flac", C.c_void_p), ("flac_cap", C.c_size_t), ("flac_offsets", C.c_void_p), ("png", C.c_void_p), ("png_cap", C.c_size_t),
+                ("png_offsets", C.c_void_p), ("n_clips", C.c_size_t)]
+
+
+class ClipSettings:
+    """The export settings of the detection-clip entries (bnhip_clip_export), in samples at the model's rate: the span rule
+    (pre_samples, post_samples, max_samples, extended), the normalise (normalize, target_lufs, true_peak_dbtp, max_gain_db,
+    gate_fallback), the FLAC encoder (seek_interval, lpc_order) and - with width > 0 and a palette - the spectrogram PNG (width, height
+    (default: the one spectrogram_size gives the width), rate_out, window, top_db, range_db).  wav.ClipExport builds one from seconds."""
+
+    def __init__(self, pre_samples, post_samples, max_samples, extended=False, normalize=True, target_lufs=-23.0, true_peak_dbtp=-1.0,
+                 max_gain_db=30.0, gate_fallback=False, seek_interval=0, lpc_order=0, width=0, rate_out=0, window=None, top_db=0.0,
+                 range_db=100.0, palette=None, height=None):
+        self.pre_samples, self.post_samples, self.max_samples, self.extended = int(pre_samples), int(post_samples), int(max_samples), bool(extended)
+        self.normalize, self.target_lufs, self.true_peak_dbtp = bool(normalize), float(target_lufs), float(true_peak_dbtp)
+        self.max_gain_db, self.gate_fallback = float(max_gain_db), bool(gate_fallback)
+        self.seek_interval, self.lpc_order = int(seek_interval), int(lpc_order)
+        self.width, self.rate_out, self.top_db, self.range_db = int(width), int(rate_out), float(top_db), float(range_db)
+        self.height = (spectrogram_size(self.width)[0] if height is None else int(height)) if self.width > 0 else 0
+        self._window = _spectrogram_window(window, 2 * (self.height - 1))[0] if self.width > 0 else None
+        self._palette = _png_palette(palette) if self.width > 0 else None
+
+    def _struct(self):
+        """-> the C struct (the tables stay alive with self)."""
+        return _ClipExportStruct(self.pre_samples, self.post_samples, self.max_samples, int(self.extended), int(self.normalize),
+                                 int(self.gate_fallback), self.target_lufs, self.true_peak_dbtp, self.max_gain_db, self.seek_interval,
+                                 self.lpc_order, self.width, self.height, self.rate_out, 0,
+                                 None if self._window is None else self._window.ctypes.data, self.top_db, self.range_db,
+                                 None if self._palette is None else self._palette.ctypes.data)
+
+
+def event_clip_spans(events, resampled_length, hop, settings):
+    """bnhip_event_clip_spans (host only): the clip of every event (EVENT) of recordings of `resampled_length` samples at the model's
+    rate, analysed at `hop` -> CLIP_SPAN [n_events]; an event with a non-zero status gets length 0."""
+    lib = _analyze_clips_protos(load_library())
+    ev = np.ascontiguousarray(events, EVENT).reshape(-1)
+    ln = np.ascontiguousarray(resampled_length, np.int64).reshape(-1)
+    spans = np.zeros(ev.size, CLIP_SPAN)
+    xs = settings._struct()
+    _check(lib, lib.bnhip_event_clip_spans(ev.ctypes.data if ev.size else None, ev.size, ln.ctypes.data, ln.size, int(hop), C.addressof(xs),
+                                           spans.ctypes.data if ev.size else None))
+    return spans
+
+
+def recording_clips(raw, recs, model_rate, spans, device=0):
+    """bnhip_recording_clips_pcm16: the spans (CLIP_SPAN) cut out of recordings (a CHANNELS_RECORDING table; their bytes as the
+    channels entries take them) as they are at the model's rate - resampled, and their channel fetched, on the device.
+    -> the list of int16 clips of the spans of non-zero length, in span order."""
+    lib = _analyze_clips_protos(load_library())
+    x, recs = _channels_bytes(raw, recs)
+    spans = np.ascontiguousarray(spans, CLIP_SPAN).reshape(-1)
+    lens = spans["length"][spans["length"] > 0].astype(np.int64)
+    out = np.zeros(max(int(lens.sum()), 1), np.int16)
+    _check(lib, lib.bnhip_recording_clips_pcm16(int(device), x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), spans.ctypes.data,
+                                                spans.size, out.ctypes.data))
+    ends = np.cumsum(lens)
+    return [out[int(e - n):int(e)].copy() for e, n in zip(ends, lens)]
+
+
+class ClipsResult:
+    """What analyze_channels_pcm_clips answers: events (EVENT, the first event_cap), n_events (the total), spans (CLIP_SPAN, one per
+    event written), n_clips, and per clip - the j-th span of non-zero length - loudness[j] (Loudness; None without normalize),
+    flac[j] (bytes) and png[j] (bytes; png is None without images); chosen as the channels entries answer it."""
+
+    def __init__(self, events, n_events, spans, loudness, flac, png, chosen):
+        self.events, self.n_events, self.spans, self.loudness, self.flac, self.png, self.chosen = events, n_events, spans, loudness, flac, png, chosen
+        self.n_clips = len(flac)
 
 
 def analyze_channels_windows(recs, model_rate, n_samples, hop, min_tail=0):
@@ -663,6 +756,45 @@ class HipClassifier:
         head = (self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop), int(min_tail), activation, sensitivity, k)
         got = self._events_call(self._lib.bnhip_analyze_channels_pcm_events, head, w, k, filter, cap, extra=(chosen.ctypes.data,))
         return (got, chosen) if cap is None else (got[0], got[1], chosen)
+
+    def analyze_channels_pcm_clips(self, raw, recs, model_rate, hop, filter, settings, min_tail=0, k=10, activation=0, sensitivity=1.0,
+                                   event_cap=None, max_clips=None, flac_cap=None, png_cap=None):
+        """bnhip_analyze_channels_pcm_clips: analyze_channels_pcm_events, and in the same call the clip of every event written - cut
+        out of the recordings on the device, normalised, FLAC-encoded and (with settings.width) rendered to a PNG - under `settings`
+        (a ClipSettings).  Room: event_cap events (default: every row), and for the streams flac_cap / png_cap bytes (default: the
+        bounds of max_clips clips of the longest span the settings allow; max_clips defaults to min(event_cap, 65535)).  Clips are
+        made in event order for as long as their bounds fit.  -> a ClipsResult; its flac_offsets / png_offsets are the raw uint64
+        tables [event_cap + 1], untouched (all ones) from n_clips + 1 on."""
+        self._alive()
+        _analyze_clips_protos(self._lib)
+        x, recs = _channels_bytes(raw, recs)
+        first, n_out = analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)
+        room = int(first[-1]) * min(k, self._n_classes) if event_cap is None else int(event_cap)
+        n_max = min(room, 65535) if max_clips is None else int(max_clips)
+        longest = max(1, min(settings.max_samples, int(n_out.max())))
+        if not settings.extended:
+            longest = max(1, min(longest, settings.pre_samples + settings.post_samples))
+        if flac_cap is None:
+            flac_cap = flac_ragged_max_bytes([longest] * n_max, settings.seek_interval) if n_max else 0
+        if png_cap is None:
+            png_cap = png_max_bytes(n_max, settings.width, settings.height) if n_max and settings.width > 0 else 0
+        events, spans = np.zeros(room, EVENT), np.zeros(room, CLIP_SPAN)
+        loud = (Loudness * max(room, 1))()
+        flac, png = np.empty(max(int(flac_cap), 1), np.uint8), np.empty(max(int(png_cap), 1), np.uint8)
+        flac_off, png_off = np.full(room + 1, 2 ** 64 - 1, np.uint64), np.full(room + 1, 2 ** 64 - 1, np.uint64)
+        chosen = np.zeros(recs.size, np.int32)
+        fs, xs = filter._struct(self._n_classes), settings._struct()
+        o = _ClipsOutStruct(events.ctypes.data, room, 0, spans.ctypes.data, C.addressof(loud), flac.ctypes.data, int(flac_cap), flac_off.ctypes.data,
+                            png.ctypes.data, int(png_cap), png_off.ctypes.data, 0)
+        _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
+                                                                     int(min_tail), activation, sensitivity, k, C.addressof(fs), chosen.ctypes.data,
+                                                                     C.addressof(xs), C.addressof(o)))
+        n_ev, n = min(room, o.n_events), int(o.n_clips)
+        res = ClipsResult(events[:n_ev], int(o.n_events), spans[:n_ev], list(loud[:n]) if settings.normalize else None,
+                          _flac_streams(flac, flac_off[:n + 1]) if n else [],
+                          (_flac_streams(png, png_off[:n + 1]) if n else []) if settings.width > 0 else None, chosen)
+        res.flac_offsets, res.png_offsets = flac_off, png_off
+        return res
 
     # ---- plumbing
     def set_stream(self, hip_stream_ptr):

@@ -221,8 +221,50 @@ class EventFilter:
                                 host.EVENTS_KEEP_DROPPED if self.keep_dropped else 0)
 
 
+class ClipExport:
+    """What analyze_files(events=..., export=...) saves of every detection event, as the reference does for an approved detection
+    (include/bnhip.h, "Detection clips"): the clip from pre_capture_seconds before the event's first window to length_seconds -
+    pre_capture_seconds behind it - with extended=True behind the event's LAST window, the clip then cut at max_seconds (required) -
+    loudness-normalised (normalize, target_lufs, true_peak_dbtp, max_gain_db, gate_fallback), FLAC-encoded (lpc_order,
+    seek_seconds: a seek point every so many seconds, 0 = none) and, with image=(width, height) and a palette, rendered to a
+    spectrogram PNG at rate_out (window, top_db, range_db as host.spectrogram_png_ragged takes them).  max_clips: the clips one
+    call has room for; the events behind them come back without a clip."""
+
+    def __init__(self, length_seconds=15.0, pre_capture_seconds=3.0, extended=False, max_seconds=None, normalize=True, target_lufs=-23.0,
+                 true_peak_dbtp=-1.0, max_gain_db=30.0, gate_fallback=False, lpc_order=8, seek_seconds=0.0, image=None, palette=None,
+                 rate_out=0, window=None, top_db=0.0, range_db=100.0, max_clips=256):
+        if extended and max_seconds is None:
+            raise ValueError("extended capture needs max_seconds")
+        if image is not None and palette is None:
+            raise ValueError("an image needs a palette")
+        self.length_seconds, self.pre_capture_seconds, self.extended = float(length_seconds), float(pre_capture_seconds), bool(extended)
+        self.max_seconds = None if max_seconds is None else float(max_seconds)
+        self.normalize, self.target_lufs, self.true_peak_dbtp = bool(normalize), float(target_lufs), float(true_peak_dbtp)
+        self.max_gain_db, self.gate_fallback, self.lpc_order, self.seek_seconds = float(max_gain_db), bool(gate_fallback), int(lpc_order), float(seek_seconds)
+        self.image, self.palette, self.rate_out, self.window = image, palette, int(rate_out), window
+        self.top_db, self.range_db, self.max_clips = float(top_db), float(range_db), int(max_clips)
+
+    def settings(self, model_rate):
+        """-> the host.ClipSettings of this export at model_rate: seconds become samples, rounded to nearest."""
+        from . import host
+        pre = int(round(self.pre_capture_seconds * model_rate))
+        post = int(round(self.length_seconds * model_rate)) - pre
+        most = 2 ** 31 - 1 if self.max_seconds is None else int(round(self.max_seconds * model_rate))
+        width, height = self.image if self.image is not None else (0, None)
+        return host.ClipSettings(pre, post, most, self.extended, self.normalize, self.target_lufs, self.true_peak_dbtp, self.max_gain_db,
+                                 self.gate_fallback, int(round(self.seek_seconds * model_rate)), self.lpc_order, width, self.rate_out, self.window,
+                                 self.top_db, self.range_db, self.palette, height)
+
+
+def clip_spans(events, resampled_length, hop, export, model_rate=48000):
+    """The span rule of ClipExport alone (bnhip_event_clip_spans, host only): events (host.EVENT) of recordings of `resampled_length`
+    samples at model_rate, analysed at `hop` -> host.CLIP_SPAN [n_events] (start, length in samples; length 0 for a dropped event)."""
+    from . import host
+    return host.event_clip_spans(events, resampled_length, hop, export.settings(model_rate))
+
+
 def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
-                  device=0, device_resample=False, channels=None, return_chosen=False, events=None):
+                  device=0, device_resample=False, channels=None, return_chosen=False, events=None, export=None):
     """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
     path, each what analyze_file returns for that file.  The files' PCM bytes are sent as they are when all of them are at the
     model's rate and share one bit depth; otherwise every file goes as float32 (converted, and resampled where its rate differs,
@@ -240,21 +282,29 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     events (an EventFilter): every route above answers detection events instead of rows, merged on the device in the same call
     (`bnhip_analyze_*_pcm_events`; `threshold` gives way to the filter's own): per path a list of (start_s, end_s, label | index,
     confidence, count), and with keep_dropped also the status; start = first_window * hop / rate, end = last_window * hop / rate +
-    the clip."""
+    the clip.
+
+    export (a ClipExport, with events; keep_dropped is refused): the same call also makes every event's clip on the device
+    (`bnhip_analyze_channels_pcm_clips`: every file's frames go up interleaved as they are - channels=None reads channel 0 there).
+    Each tuple is followed by the clip's start and length in samples at model_rate, its FLAC bytes, its loudness record
+    (host.Loudness, None without normalize) and its PNG bytes or None; an event behind the export's max_clips has None for all three."""
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
     if return_chosen and channels is None:
         raise ValueError("return_chosen needs channels")
+    if export is not None and (events is None or events.keep_dropped):
+        raise ValueError("export needs events, without keep_dropped")
     recs = crecs = None
-    if channels is None:
+    select = 0 if channels is None and export is not None else channels      # (the export takes the files' frames: channel 0 is read there)
+    if select is None:
         pcm = [read_wav_pcm(p) for p in paths]
         depths = {bits for _, _, bits in pcm}
-    if channels is not None:
+    if select is not None:
         from . import host
         frames = [read_wav_frames(p) for p in paths]
         bufs = [raw for raw, _, _, _ in frames]
         lengths = [len(raw) // ((bits // 8) * ch) for raw, _, bits, ch in frames]
-        crecs = host.channel_recordings(lengths, [f[1] for f in frames], [f[2] for f in frames], [f[3] for f in frames], channels)
+        crecs = host.channel_recordings(lengths, [f[1] for f in frames], [f[2] for f in frames], [f[3] for f in frames], select)
     elif device_resample:
         from . import host
         bufs = [raw for raw, _, _ in pcm]
@@ -285,8 +335,12 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
         t32 = np.nextafter(t32, np.float32(np.inf))
     if events is not None:
         flt = events.tables(classifier.num_species(),model_rate, hop, overlap_seconds)
-        chosen = None
-        if crecs is not None:
+        chosen = clips = None
+        if export is not None:
+            clips = classifier.analyze_channels_pcm_clips(b"".join(bufs), crecs, model_rate, hop, flt, export.settings(model_rate), min_tail,
+                                                          k=top_k, sensitivity=sensitivity, max_clips=export.max_clips)
+            ev, chosen = clips.events, ["mix" if s < 0 else int(s) for s in clips.chosen]
+        elif crecs is not None:
             ev, sel = classifier.analyze_channels_pcm_events(b"".join(bufs), crecs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)
             chosen = ["mix" if s < 0 else int(s) for s in sel]
         elif recs is not None:
@@ -294,11 +348,18 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
         else:
             ev = classifier.analyze_pcm_events(b"".join(bufs), bits, lengths, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)
         out = [[] for _ in paths]
-        for e in ev:
+        nc = 0                                        # the clip of the next event with a span (clips are made in event order)
+        for i, e in enumerate(ev):
             start = np.float64(int(e["first_window"]) * hop) / model_rate
             end = np.float64(int(e["last_window"]) * hop) / model_rate + clip_seconds
             j = int(e["class_index"])
             row = (float(start), float(end), labels[j] if labels else j, float(e["confidence"]), int(e["count"]))
+            if clips is not None:
+                sp = clips.spans[i]
+                has = int(sp["length"]) > 0 and nc < clips.n_clips
+                row += (int(sp["start"]), int(sp["length"]), clips.flac[nc] if has else None,
+                        clips.loudness[nc] if has and clips.loudness is not None else None, clips.png[nc] if has and clips.png is not None else None)
+                nc += 1 if int(sp["length"]) > 0 else 0
             out[int(e["recording"])].append(row + (int(e["status"]),) if events.keep_dropped else row)
         return (out, chosen) if return_chosen else out
     chosen = None

@@ -389,6 +389,75 @@ int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_row
                            bnhip_event* out, size_t cap, size_t* n_out);
 int bnhip_event_min_count(int level, double overlap_seconds);
 
+/* Detection clips: what the reference saves for every approved detection, made from the recordings of a file-analysis call while
+ * they are still on the device.  Its processor takes the audio from BeginTime back by the pre-capture to the end of the capture
+ * window, or under extended capture to as long as the bird kept calling (internal/analysis/processor/extended_capture.go:232-280,
+ * processor.go:1105-1110, 2234-2300), loudness-normalises the clip, encodes it and renders its spectrogram.  Here the clock is
+ * audio time, in samples at the model's rate.
+ *   span     Of event e of recording r, N = resampled_length[r]: begin = first_window * hop - pre_samples, end = (extended ?
+ *            last_window : first_window) * hop + post_samples (post_samples: captureLength - preCaptureLength), both clamped to
+ *            [0, N], then end = min(end, begin + max_samples).  start = begin, length = end - begin >= 1; an event with status != 0
+ *            gets length 0: no clip.
+ *   bnhip_event_clip_spans  Host only: the rule over events the caller holds; spans [n_events].
+ *   clip     Sample i of a span is q = clamp(rint(x * 32768), -32768, 32767), x the float32 that the windows of the call are framed
+ *            from (the sample of a 16 / 24 / 32-bit recording at the model's rate, else what the device resampler and the channel
+ *            fetch wrote); ties to even, a NaN gives 0.  A 16-bit recording's clip is its own samples.  Mono int16, packed back to
+ *            back in span order: the layout of "Ragged bursts".
+ *   bnhip_recording_clips_pcm16  The cut alone: the upload, channel fetch / measurement and slot launch of bnhip_analyze_channels_pcm
+ *            (mono recordings of one depth at the model's rate are cut as they are), then one launch.  Spans of length 0 are skipped;
+ *            out_pcm holds the others, the sum of their lengths in samples.
+ *   bnhip_analyze_channels_pcm_clips  bnhip_analyze_channels_pcm_events, and behind it, in the same call: the spans of the events
+ *            written, the cut, and on the clips where they lie bnhip_loudness_ragged_normalize_device (with normalize != 0),
+ *            bnhip_flac_ragged_encode_device at lpc_order over the gained clips, and with width > 0 the render of
+ *            bnhip_spectrogram_png_ragged_pcm16 (rate_in = model_rate) over them.  The recordings go up once and no PCM comes back.
+ *            With normalize == 0 the streams are those of bnhip_flac_ragged_encode_pcm16 without factors and loudness is not written.
+ *   out      events [event_cap]: as bnhip_analyze_channels_pcm_events writes them, n_events the total.  spans, loudness: [event_cap];
+ *            flac_offsets, png_offsets: [event_cap + 1] (png, png_offsets, palette: only with width > 0).  spans[i] belongs to
+ *            events[i]; clip j is the j-th span of non-zero length, its streams flac[flac_offsets[j] .. flac_offsets[j + 1]) and
+ *            png[png_offsets[j] ..), its record loudness[j].
+ *   n_clips  The largest n with n <= the events written, n <= 65535, bnhip_flac_ragged_max_bytes(n, lens, seek_interval) <= flac_cap
+ *            and, with width > 0, bnhip_png_max_bytes(n, width, height) <= png_cap.  With n_clips == 0 nothing but events, spans,
+ *            n_events and n_clips is written, and the second phase touches no device.
+ * BNHIP_E_INVALID (nothing written, before any device call): everything the events entry refuses, NULL arguments, pre_samples < 0,
+ * post_samples < 1, max_samples < 1, BNHIP_EVENTS_KEEP_DROPPED, what the normalise, FLAC and render entries refuse of their own
+ * settings; for bnhip_event_clip_spans an event's recording outside the table; for bnhip_recording_clips_pcm16 n_spans outside
+ * 1..65535, a span outside its recording, a negative length, a total of 2^36 samples or more. */
+typedef struct bnhip_clip_span {       /* 16 bytes */
+    int64_t start;
+    int32_t length, recording;
+} bnhip_clip_span;
+typedef struct bnhip_clip_export {
+    int32_t pre_samples, post_samples, max_samples, extended;
+    int32_t normalize, gate_fallback;
+    double target_lufs, true_peak_dbtp, max_gain_db;
+    int32_t seek_interval, lpc_order;
+    int32_t width, height, rate_out, reserved;     /* width 0: no images */
+    const double* window;                          /* [2 (height - 1)] or NULL: periodic Hann */
+    double top_db, range_db;
+    const uint8_t* palette;                        /* [768] */
+} bnhip_clip_export;
+typedef struct bnhip_clips_out {
+    bnhip_event* events;
+    size_t event_cap, n_events;
+    bnhip_clip_span* spans;
+    struct bnhip_loudness* loudness;               /* (declared under "Clip loudness" below) */
+    uint8_t* flac;
+    size_t flac_cap;
+    uint64_t* flac_offsets;
+    uint8_t* png;
+    size_t png_cap;
+    uint64_t* png_offsets;
+    size_t n_clips;
+} bnhip_clips_out;
+int bnhip_event_clip_spans(const bnhip_event* events, size_t n_events, const int64_t* resampled_length, int n_recordings, int hop,
+                           const bnhip_clip_export* x, bnhip_clip_span* spans);
+int bnhip_recording_clips_pcm16(int device, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                                const bnhip_clip_span* spans, int n_spans, int16_t* out_pcm);
+int bnhip_analyze_channels_pcm_clips(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                     int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                     const bnhip_event_filter* filter, int32_t* chosen, const bnhip_clip_export* x,
+                                     bnhip_clips_out* out);
+
 /* Ultrasonic frame-CV filter (internal/audiocore/ultrasonic/filter.go:20-66), float64 throughout.
  * samples: host float64 [n_clips * n] (int16/32768 as float64, convert/pcm.go:108-113).
  * cv/ok: [n_clips]. device: HIP device ordinal. */
