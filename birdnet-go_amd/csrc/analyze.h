@@ -1,4 +1,4 @@
-// File analysis (api_analyze.cpp, analyze.hip): the overlapping windows of a burst of recordings are framed on the device.
+// File analysis (api_analyze.cpp, analyze_recordings.cpp, analyze.hip): the overlapping windows of a burst of recordings are framed on the device.
 //
 // The recordings sit in ONE device block, recording r in a slot of its own: the slot starts 16-byte aligned and holds the
 // recording's samples followed by zeros up to a whole quad (4 samples).  Window j of recording r starts at sample j * hop of the

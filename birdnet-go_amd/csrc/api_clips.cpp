@@ -1,11 +1,11 @@
-// Detection clips from analysed recordings (clips.h): the span rule (bnhip_event_clip_spans), and the second phase of
-// bnhip_analyze_channels_pcm_clips - the cut, the normalise, the FLAC encode, the render and the PNG encode over the clips where
-// they lie.  The entries that hold the recordings (bnhip_recording_clips_pcm16, bnhip_analyze_channels_pcm_clips) are in
-// api_analyze.cpp beside the upload they share with the analysis calls.
+// Detection clips from analysed recordings (clips.h): the span rule (bnhip_event_clip_spans), the cut alone
+// (bnhip_recording_clips_pcm16), and the second phase of bnhip_analyze_channels_pcm_clips - the cut, the normalise, the FLAC encode,
+// the render and the PNG encode over the clips where they lie.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "analyze_recordings.h"
 #include "clip_source.h"
 #include "clips.h"
 #include "flac.h"
@@ -174,6 +174,47 @@ int bnhip_event_clip_spans(const bnhip_event* events, size_t n_events, const int
     if (hop < 1) return set_err(BNHIP_E_INVALID, "hop must be at least 1");
     if (int rc = span_rule_check(x)) return rc;
     return event_spans(events, n_events, resampled_length, n_recordings, hop, x, spans);
+    BN_GUARD_END((void)0)
+}
+
+// the cut alone: one DevCarve (the recordings' parts, the slot table, the cut's tables, the clips), the upload, the cut, one D2H copy
+int bnhip_recording_clips_pcm16(int device, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                                const bnhip_clip_span* spans, int n_spans, int16_t* out_pcm) {
+    BN_GUARD_BEGIN
+    const char* what = "recording_clips_pcm16";
+    if (!pcm || !spans || !out_pcm) return set_err(BNHIP_E_INVALID, "NULL argument");
+    Recordings rec;
+    if (int rc = describe(recs, n_recordings, model_rate, &rec)) return rc;
+    if (n_spans < 1 || n_spans > 65535) return set_err(BNHIP_E_INVALID, "n_spans must be in [1, 65535]");
+    long long total = 0;
+    for (int i = 0; i < n_spans; i++) {
+        const bnhip_clip_span& q = spans[i];
+        const std::string who = "span " + std::to_string(i) + ": ";
+        if (q.recording < 0 || q.recording >= n_recordings) return set_err(BNHIP_E_INVALID, who + "recording outside the table");
+        if (q.length < 0) return set_err(BNHIP_E_INVALID, who + "negative length");
+        if (q.start < 0 || q.start > rec.n_out[q.recording] - q.length) return set_err(BNHIP_E_INVALID, who + "outside its recording");
+        total += q.length;
+    }
+    if (total > RAGGED_MAX_SAMPLES) return set_err(BNHIP_E_INVALID, "the clips' total length must be below 2^36 samples");
+    if (int rc = rate_plans(&rec)) return rc;
+    const CutPlan plan = cut_plan(spans, (size_t)n_spans, n_spans);
+    if (plan.n_clips() == 0) return BNHIP_OK;
+    std::vector<long long> slot((size_t)n_recordings * 2);
+    const SlotPlan sp = slot_plan(rec, slot.data());
+    if (int rc = use_device(device)) return rc;
+    DevCarve cv;
+    const SlotDev dv = slot_reserve(sp, cv);
+    const size_t o_slot = cv.add(slot.size() * 8), o_tab = cv.add(plan.table_bytes()), o_out = cv.add((size_t)total * 2);
+    DevBlocks b;
+    cv.alloc(b);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    slot_upload(sp, pcm, rec, slot.data(), device, dv, nullptr, b);
+    AN_HIP(b, hipMemcpyAsync(cv.at<void>(o_slot), slot.data(), slot.size() * 8, hipMemcpyHostToDevice, nullptr));
+    AN_HIP(b, cut_enqueue(plan, dv.at(dv.block), rec.bits, cv.at<long long>(o_slot), cv.at<void>(o_tab), cv.at<int16_t>(o_out), nullptr));
+    // (the null stream orders the copy after the kernels; it is the call's synchronise)
+    AN_HIP(b, hipMemcpy(out_pcm, cv.at<void>(o_out), (size_t)total * 2, hipMemcpyDeviceToHost));
+    if (b.he != hipSuccess) { hipDeviceSynchronize(); return hip_fail(what, b); }
+    return BNHIP_OK;
     BN_GUARD_END((void)0)
 }
 

@@ -1,0 +1,103 @@
+// C ABI of detection events (events.h): the event tail alone over rows the host holds, the reference's minimum hit count, and what
+// the tail of an analysis call shares with them (api_events.h).
+#include "api_events.h"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+using namespace bnhip;
+
+static_assert(sizeof(bnhip_detection) == 16 && sizeof(DetRow) == 16, "a detection row is 16 bytes");
+static_assert(sizeof(bnhip_event) == 32 && sizeof(Event) == 32, "an event is 32 bytes");
+static_assert(BNHIP_EVENTS_KEEP_DROPPED == EVENTS_KEEP_DROPPED, "the flag of events.h");
+
+namespace bnhip {
+
+int event_filter_check(const bnhip_event_filter* f) {
+    if (!f || !f->class_threshold) return set_err(BNHIP_E_INVALID, "NULL event filter / class_threshold");
+    if (f->hold_windows < 1) return set_err(BNHIP_E_INVALID, "hold_windows must be at least 1");
+    if (f->min_count < 1) return set_err(BNHIP_E_INVALID, "min_count must be at least 1");
+    if (f->flags & ~BNHIP_EVENTS_KEEP_DROPPED) return set_err(BNHIP_E_INVALID, "unknown event filter flags");
+    return BNHIP_OK;
+}
+
+EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, char* d_tables, hipStream_t s, DevBlocks& b) {
+    char* d_veto = f->class_veto ? d_tables + (size_t)n_classes * 4 : nullptr;
+    if (b.he == hipSuccess) b.he = hipMemcpyAsync(d_tables, f->class_threshold, (size_t)n_classes * 4, hipMemcpyHostToDevice, s);
+    if (b.he == hipSuccess && d_veto) b.he = hipMemcpyAsync(d_veto, f->class_veto, (size_t)n_classes, hipMemcpyHostToDevice, s);
+    return EventFilterDev{reinterpret_cast<const float*>(d_tables), reinterpret_cast<const uint8_t*>(d_veto), f->veto_threshold, f->hold_windows,
+                          f->min_count, f->flags, n_classes};
+}
+
+void fetch_counted(const void* d_total, const void* d_records, size_t record_bytes, size_t cap, void* out, unsigned long long* total, hipStream_t s,
+                   DevBlocks& b) {
+    if (b.he == hipSuccess) b.he = hipMemcpyAsync(total, d_total, 8, hipMemcpyDeviceToHost, s);
+    if (b.he == hipSuccess) b.he = hipStreamSynchronize(s);
+    const size_t n = (size_t)std::min<unsigned long long>(*total, cap);
+    if (b.he == hipSuccess && n) b.he = hipMemcpyAsync(out, d_records, n * record_bytes, hipMemcpyDeviceToHost, s);
+}
+
+}  // namespace bnhip
+
+// what the LDS top-k holds (api_predict.cpp): with recording < 65 535 a (recording, class) key is below 2^32
+static constexpr int EVENT_MAX_CLASSES = 150 * 1024 / 4;
+
+extern "C" {
+
+// the tail alone over rows the host holds: one pass over the rows for every refusal, one DevCarve (rows, their count, the filter's
+// tables, the scratch, the events), the rows and tables up, the tail's launches, the count and the events down
+int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                           bnhip_event* out, size_t cap, size_t* n_out) {
+    BN_GUARD_BEGIN
+    const char* what = "detection_events";
+    if (!n_out || (cap && !out) || (n_rows && !rows)) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (int rc = event_filter_check(filter)) return rc;
+    if (n_classes < 1 || n_classes > EVENT_MAX_CLASSES) return set_err(BNHIP_E_INVALID, "n_classes must be in [1, 38400]");
+    if (n_rows >= EVENT_MAX_ROWS) return set_err(BNHIP_E_INVALID, "2^31 detection rows or more");
+    int max_rec = 0;
+    for (size_t i = 0; i < n_rows; i++) {
+        const bnhip_detection& q = rows[i];
+        const std::string who = "row " + std::to_string(i) + ": ";
+        if (q.recording < 0 || q.recording > 65534) return set_err(BNHIP_E_INVALID, who + "recording must be in [0, 65534]");
+        if (q.window < 0) return set_err(BNHIP_E_INVALID, who + "negative window");
+        if (q.class_index < 0 || q.class_index >= n_classes) return set_err(BNHIP_E_INVALID, who + "class_index outside the table");
+        if (i && (q.recording < rows[i - 1].recording || (q.recording == rows[i - 1].recording && q.window < rows[i - 1].window)))
+            return set_err(BNHIP_E_INVALID, who + "rows must be nondecreasing in (recording, window)");
+        max_rec = std::max(max_rec, (int)q.recording);
+    }
+    if (n_rows == 0) { *n_out = 0; return BNHIP_OK; }
+    if (int rc = use_device(device)) return rc;
+    const size_t ev_cap = std::min(cap, n_rows);
+    DevCarve cv;
+    const size_t o_rows = cv.add(n_rows * sizeof(DetRow)), o_count = cv.add(8), o_tab = cv.add(event_tables_bytes(n_classes));
+    const size_t o_scr = cv.add(events_scratch_bytes(n_rows)), o_out = cv.add(ev_cap * sizeof(Event));
+    DevBlocks b;
+    cv.alloc(b);
+    const unsigned long long n64 = n_rows;
+    if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_rows), rows, n_rows * sizeof(DetRow), hipMemcpyHostToDevice);
+    if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_count), &n64, 8, hipMemcpyHostToDevice);
+    const EventFilterDev fd = event_filter_upload(filter, n_classes, cv.at<char>(o_tab), nullptr, b);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    launch_events(cv.at<DetRow>(o_rows), cv.at<unsigned long long>(o_count), n_rows, fd, events_passes((unsigned long long)(max_rec + 1) * n_classes - 1),
+                  cv.at<void>(o_scr), cv.at<Event>(o_out), ev_cap, nullptr);
+    if (int rc = launch_status(what)) { hipDeviceSynchronize(); return rc; }
+    unsigned long long total = 0;
+    fetch_counted(events_total(cv.at<void>(o_scr)), cv.at<void>(o_out), sizeof(Event), ev_cap, out, &total, nullptr, b);
+    if (b.he == hipSuccess) b.he = hipStreamSynchronize(nullptr);
+    if (b.he != hipSuccess) return hip_fail(what, b);
+    *n_out = (size_t)total;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+// calculateMinDetectionsFromSettings (processor.go:1669-1729), host only
+int bnhip_event_min_count(int level, double overlap_seconds) {
+    if (level == 0) return 1;
+    static const double share[6] = {0.0, 0.20, 0.30, 0.50, 0.60, 0.70};
+    const double segment = std::max(0.1, 3.0 - overlap_seconds);
+    const double required = 6.0 / segment * (level >= 1 && level <= 5 ? share[level] : 0.30) - 1e-9;
+    return (int)std::max(1.0, std::ceil(required));
+}
+
+}  // extern "C"

@@ -1,0 +1,25 @@
+// What the event tail's two callers share (api_events.cpp: the tail alone; api_analyze.cpp: the tail of an analysis call): the
+// filter's refusals, its tables on the device, and the copy that brings a counted list of records down.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "api_oneshot.h"
+#include "events.h"
+
+namespace bnhip {
+
+constexpr unsigned long long EVENT_MAX_ROWS = 1ull << 31;
+
+// every refusal of the filter itself; -> 0 or a negative BNHIP_E_*
+int event_filter_check(const bnhip_event_filter* f);
+// bytes of the filter's tables on the device: class_threshold [n_classes], then class_veto [n_classes] where there is one
+inline size_t event_tables_bytes(int n_classes) { return (size_t)n_classes * 4 + (size_t)n_classes; }
+// the tables go up to d_tables (event_tables_bytes) on s, a failure into b; -> the filter as the kernels read it
+EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, char* d_tables, hipStream_t s, DevBlocks& b);
+
+// A list the device has counted (detection rows, events): the count comes down and s is synchronised, then min(*total, cap)
+// records are copied to out - that copy is left in flight on s.  A failure goes into b.
+void fetch_counted(const void* d_total, const void* d_records, size_t record_bytes, size_t cap, void* out, unsigned long long* total, hipStream_t s,
+                   DevBlocks& b);
+
+}  // namespace bnhip

@@ -60,7 +60,7 @@ struct DevBlocks {
 };
 
 // The device parts of a host-pointer call: add() every part first (-> its handle), alloc() once, then at() each handle.  The parts
-// of DEV_OWN_BLOCK bytes and more are carved from one block at 256-byte alignment (what the device entries ask of a workspace), so a
+// of own_below (DEV_OWN_BLOCK) bytes and more are carved from one block at 256-byte alignment (what the device entries ask of a workspace), so a
 // call makes one driver allocation however many large parts it has.  A smaller part is an allocation of its own: those the HIP
 // runtime serves from blocks it keeps, with no driver call (1.4 us against 130 us and more from 2 MiB on, and a call on one 15 s
 // clip is 0.26 ms slower with its 1.4 MB parts in one 3 MB block than with each on its own: DESIGN.md section 9, "One body per
@@ -69,14 +69,15 @@ constexpr size_t DEV_OWN_BLOCK = (size_t)2 << 20;
 struct DevCarve {
     std::vector<size_t> sizes;
     std::vector<char*> parts;
+    size_t own_below = DEV_OWN_BLOCK;        // a part smaller than this is an allocation of its own (0: every part from the one block)
     size_t add(size_t bytes) { sizes.push_back(bytes ? bytes : 1); return sizes.size() - 1; }
     void alloc(DevBlocks& b) {
         auto al = [](size_t s) { return (s + 255) & ~(size_t)255; };
         size_t shared = 0;
-        for (size_t s : sizes) if (s >= DEV_OWN_BLOCK) shared += al(s);
+        for (size_t s : sizes) if (s >= own_below) shared += al(s);
         char* next = shared ? (char*)b.get(shared) : nullptr;
         for (size_t s : sizes) {
-            if (s < DEV_OWN_BLOCK) { parts.push_back((char*)b.get(s)); continue; }
+            if (s < own_below) { parts.push_back((char*)b.get(s)); continue; }
             parts.push_back(next);
             if (next) next += al(s);
         }

@@ -1,4 +1,4 @@
-// Multichannel recordings (api_analyze.cpp bnhip_analyze_channels_*, bnhip_channel_energy_pcm): the frames stay interleaved as they
+// Multichannel recordings (bnhip_analyze_channels_*, analyze_recordings.cpp; bnhip_channel_energy_pcm, api_channels.cpp): the frames stay interleaved as they
 // are in the file, and the launch that converts and resamples fetches "channel c" or "the mean of the channels" (channel_sample,
 // used by k_resample_slots_mc, resample.hip).  Which one is, where asked, decided from a measurement made on the device
 // (channels.hip): the exact sum of squares of every channel as a 128-bit integer, the reference's left / right / downmix rule

@@ -1,4 +1,4 @@
-// Detection events (api_analyze.cpp, events.hip): the detection rows of a file-analysis call merged on the device into what the
+// Detection events (api_events.cpp, api_analyze.cpp, events.hip): the detection rows of a file-analysis call merged on the device into what the
 // reference's processor reports - a per-class threshold, repeated hits of one class in one recording merged into an event held
 // for a fixed number of windows, the minimum hit count and the privacy veto (include/bnhip.h, "Detection events").
 //

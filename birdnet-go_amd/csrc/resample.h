@@ -1,6 +1,6 @@
 // Polyphase resampler (resample.hip): the filter design, the one-shot / streaming launch and the bank launch (api_resample.cpp
 // bnhip_resampler_bank_*), which resamples one call's frames of every stream of a bank that shares (rate_in, rate_out).  The
-// bank's descriptor table travels in front of the packed PCM16 in one staging buffer.  The slot launch (api_analyze.cpp) resamples
+// bank's descriptor table travels in front of the packed PCM16 in one staging buffer.  The slot launch (analyze_recordings.cpp) resamples
 // a burst of recordings at their own rates and depths into the float32 slots that file analysis frames.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,7 +70,7 @@ size_t resample_ragged_table_bytes(int n_clips);
 int launch_resample_ragged(const int16_t* d_in, float* d_out, const float* d_table, int n_clips, const int* lens_in, const int* lens_out,
                            int L, int M, int T, int half, void* d_tables, hipStream_t s);
 
-// The slot form (file analysis of recordings at their own rates and depths, api_analyze.cpp): recording r lies as it is in its file
+// The slot form (file analysis of recordings at their own rates and depths, analyze_recordings.cpp): recording r lies as it is in its file
 // - n_in samples of `bits` (0 = float32, 16, 24 packed, 32) from byte in_off of the raw block - and becomes n_out float32 samples at
 // byte out_off of the slot block, followed by zeros up to a whole quad (what analyze_slot_bytes(n_out, 0) reserves).  L == 0: the
 // recording is at the model's rate and is only converted; else out[i] is resample_tile's fmaf chain over the [L][T] phase table at

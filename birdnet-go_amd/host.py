@@ -12,6 +12,7 @@ Error behaviour follows the reference: size mismatch is an error (tflite/classif
 This file is plumbing for tests/bench in this repo (Go is not installed here); the production
 binding is the cgo file under go/ (see INTEGRATION.md).
 """
+import collections
 import ctypes as C
 import json
 import math
@@ -195,17 +196,24 @@ def channel_recordings(lengths, rates, depths, channels, select=0):
     return recs
 
 
+def _checked_bytes(raw, depths, samples, expected):
+    """The bytes of a file-analysis call as a uint8 array, checked against the depth(s) and sample count(s) of its recordings."""
+    x = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
+    depths, samples = np.atleast_1d(depths), np.atleast_1d(samples)
+    bad = ~np.isin(depths, (0, 16, 24, 32))
+    if bad.any():
+        raise HipError(E_INVALID, f"unsupported bit depth: {int(depths[bad][0])} (supported: 0 = float32, 16, 24, 32)")
+    bps = np.where(depths == 0, 4, depths // 8)
+    want = int((samples * bps).sum())
+    if x.size != want:
+        raise HipError(E_INVALID, "input size mismatch: " + expected.format(want=want, samples=int(samples.sum()), bps=int(bps[0]) if bps.size else 0) + f", got {x.size} bytes")
+    return x
+
+
 def _channels_bytes(raw, recs):
     """The interleaved bytes of a channels call as a uint8 array, checked against the table."""
     recs = np.ascontiguousarray(recs, CHANNELS_RECORDING).reshape(-1)
-    x = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
-    bad = ~np.isin(recs["bits_per_sample"], (0, 16, 24, 32))
-    if bad.any():
-        raise HipError(E_INVALID, f"unsupported bit depth: {int(recs['bits_per_sample'][bad][0])} (supported: 0 = float32, 16, 24, 32)")
-    want = int((recs["length"] * recs["channels"].astype(np.int64) * np.where(recs["bits_per_sample"] == 0, 4, recs["bits_per_sample"] // 8)).sum())
-    if x.size != want:
-        raise HipError(E_INVALID, f"input size mismatch: the recordings hold {want} bytes, got {x.size} bytes")
-    return x, recs
+    return _checked_bytes(raw, recs["bits_per_sample"], recs["length"] * recs["channels"].astype(np.int64), "the recordings hold {want} bytes"), recs
 
 
 def _analyze_events_protos(lib):
@@ -362,16 +370,21 @@ class ClipsResult:
         self.n_clips = len(flac)
 
 
-def analyze_channels_windows(recs, model_rate, n_samples, hop, min_tail=0):
-    """bnhip_analyze_channels_windows (host only): analyze_mixed_windows over the (length, rate) of a CHANNELS_RECORDING table."""
-    lib = _analyze_channels_protos(load_library())
-    recs = np.ascontiguousarray(recs, CHANNELS_RECORDING).reshape(-1)
-    first, n_out = np.zeros(recs.size + 1, np.int64), np.zeros(recs.size, np.int64)
-    w = lib.bnhip_analyze_channels_windows(recs.ctypes.data if recs.size else None, recs.size, int(model_rate), int(n_samples), int(hop),
-                                           int(min_tail), first.ctypes.data, n_out.ctypes.data)
+def _windows(protos, entry, table, args, resampled=True):
+    """The three *_windows entries (host only) over `table` [n] -> (first_window int64 [n + 1], resampled_length int64 [n] or None)."""
+    lib = protos(load_library())
+    first, n_out = np.zeros(table.size + 1, np.int64), np.zeros(table.size, np.int64) if resampled else None
+    w = getattr(lib, entry)(table.ctypes.data if table.size else None, table.size, *[int(v) for v in args], first.ctypes.data,
+                            *([n_out.ctypes.data] if resampled else []))
     if w < 0:
         _check(lib, int(w))
     return first, n_out
+
+
+def analyze_channels_windows(recs, model_rate, n_samples, hop, min_tail=0):
+    """bnhip_analyze_channels_windows (host only): analyze_mixed_windows over the (length, rate) of a CHANNELS_RECORDING table."""
+    recs = np.ascontiguousarray(recs, CHANNELS_RECORDING).reshape(-1)
+    return _windows(_analyze_channels_protos, "bnhip_analyze_channels_windows", recs, (model_rate, n_samples, hop, min_tail))
 
 
 def channel_energy(raw, recs, device=0):
@@ -389,26 +402,67 @@ def channel_energy(raw, recs, device=0):
 def analyze_mixed_windows(recs, model_rate, n_samples, hop, min_tail=0):
     """bnhip_analyze_mixed_windows (host only): recordings (a RECORDING table) at their own rates, framed at model_rate.
     -> (first_window int64 [n + 1], resampled_length int64 [n]: each recording's samples at model_rate)."""
-    lib = _analyze_mixed_protos(load_library())
     recs = np.ascontiguousarray(recs, RECORDING).reshape(-1)
-    first, n_out = np.zeros(recs.size + 1, np.int64), np.zeros(recs.size, np.int64)
-    w = lib.bnhip_analyze_mixed_windows(recs.ctypes.data if recs.size else None, recs.size, int(model_rate), int(n_samples), int(hop),
-                                        int(min_tail), first.ctypes.data, n_out.ctypes.data)
-    if w < 0:
-        _check(lib, int(w))
-    return first, n_out
+    return _windows(_analyze_mixed_protos, "bnhip_analyze_mixed_windows", recs, (model_rate, n_samples, hop, min_tail))
 
 
 def analyze_windows(lengths, n_samples, hop, min_tail=0):
     """bnhip_analyze_windows (host only): the window prefix table [n_recordings + 1] of recordings of `lengths` samples framed into
     windows of n_samples advanced by hop; the last entry is the number of windows."""
-    lib = _analyze_protos(load_library())
     ln = np.ascontiguousarray(lengths, np.int64).reshape(-1)
-    first = np.zeros(ln.size + 1, np.int64)
-    w = lib.bnhip_analyze_windows(ln.ctypes.data if ln.size else None, ln.size, int(n_samples), int(hop), int(min_tail), first.ctypes.data)
-    if w < 0:
-        _check(lib, int(w))
-    return first
+    return _windows(_analyze_protos, "bnhip_analyze_windows", ln, (n_samples, hop, min_tail), resampled=False)[0]
+
+
+# How a file-analysis call states its recordings: protos / entry - the ctypes prototypes and the entries' common name; x - the checked
+# bytes; table - lengths or a recordings table, and args - what the C entries take of it between pcm and hop; windows(n_samples, hop,
+# min_tail) -> (first_window, resampled_length); chosen - whether the entries answer a channel per recording
+_Form = collections.namedtuple("_Form", "protos entry x table args windows chosen")
+
+
+def _plain_form(raw, bit_depth, lengths):
+    ln = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+    x = _checked_bytes(raw, bit_depth, ln, "expected {samples} samples of {bps} bytes")
+    return _Form(_analyze_protos, "bnhip_analyze_pcm", x, ln, (bit_depth, ln.ctypes.data, ln.size), lambda *a: (analyze_windows(ln, *a), ln), False)
+
+
+def _mixed_form(raw, recs, model_rate):
+    recs = np.ascontiguousarray(recs, RECORDING).reshape(-1)
+    x = _checked_bytes(raw, recs["bits_per_sample"], recs["length"], "the recordings hold {want} bytes")
+    return _Form(_analyze_mixed_protos, "bnhip_analyze_mixed_pcm", x, recs, (recs.ctypes.data, recs.size, int(model_rate)),
+                 lambda *a: analyze_mixed_windows(recs, model_rate, *a), False)
+
+
+def _channels_form(raw, recs, model_rate):
+    x, recs = _channels_bytes(raw, recs)
+    return _Form(_analyze_channels_protos, "bnhip_analyze_channels_pcm", x, recs, (recs.ctypes.data, recs.size, int(model_rate)),
+                 lambda *a: analyze_channels_windows(recs, model_rate, *a), True)
+
+
+# How such a call is answered: (lib, kk = min(k, n_classes), first() -> first_window, room(cap) -> records to make room for) -> (the
+# entry's suffix, the C arguments behind k, result() -> what the call returns, as a tuple)
+def _topk_answer():
+    def answer(lib, kk, first, room):
+        f = first()
+        conf, idx = np.empty((int(f[-1]), kk), np.float32), np.empty((int(f[-1]), kk), np.int32)
+        return "_topk", (conf.ctypes.data, idx.ctypes.data), lambda: (conf, idx, f)
+    return answer
+
+
+def _rows_answer(threshold, cap):
+    def answer(lib, kk, first, room):
+        rows, n = np.zeros(room(cap), DETECTION), C.c_size_t(0)
+        return "", (float(threshold), rows.ctypes.data if rows.size else None, rows.size, C.byref(n)), lambda: (rows[:min(rows.size, n.value)], n.value)
+    return answer
+
+
+def _events_answer(filter, cap, n_classes):
+    def answer(lib, kk, first, room):
+        _analyze_events_protos(lib)
+        first()                                         # (a bad table is answered as the windows entry answers it, before the filter)
+        out, n, fs = np.zeros(room(cap), EVENT), C.c_size_t(0), filter._struct(n_classes)
+        return "_events", (C.byref(fs), out.ctypes.data if out.size else None, out.size, C.byref(n)), \
+            lambda: (out[:n.value],) if cap is None else (out[:min(out.size, n.value)], n.value)
+    return answer
 
 
 def init():
@@ -609,153 +663,72 @@ class HipClassifier:
                                                            conf.ctypes.data, idx.ctypes.data))
         return conf, idx
 
-    def _analyze_args(self, raw, bit_depth, lengths):
+    def _room(self, cap, first, k):
+        """Records a file-analysis call makes room for: every row (an event is made of at least one) unless cap says less."""
+        return int(first()[-1]) * min(k, self._n_classes) if cap is None else int(cap)
+
+    def _analyze(self, form, answer, hop, min_tail, k, activation, sensitivity):
+        """The body of the nine analyze_* calls: the recordings as `form` states them (a _Form), answered as `answer` says."""
         self._alive()
-        _analyze_protos(self._lib)
-        if bit_depth not in (0, 16, 24, 32):
-            raise HipError(E_INVALID, f"unsupported bit depth: {bit_depth} (supported: 0 = float32, 16, 24, 32)")
-        x = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
-        ln = np.ascontiguousarray(lengths, np.int64).reshape(-1)
-        bps = bit_depth // 8 if bit_depth else 4
-        if x.size != int(ln.sum()) * bps:
-            raise HipError(E_INVALID, f"input size mismatch: expected {int(ln.sum())} samples of {bps} bytes, got {x.size} bytes")
-        return x, ln
+        lib = form.protos(self._lib)
+        table = []                                      # the window table, made when the answer first asks for it
+
+        def first():
+            if not table:
+                table.append(form.windows(self.n_samples, hop, min_tail)[0])
+            return table[0]
+        suffix, tail, result = answer(lib, min(k, self._n_classes), first, lambda cap: self._room(cap, first, k))
+        chosen = [np.zeros(form.table.size, np.int32)] if form.chosen else []
+        _check(lib, getattr(lib, form.entry + suffix)(self._h, form.x.ctypes.data, *form.args, int(hop), int(min_tail), activation, sensitivity, k,
+                                                      *tail, *[c.ctypes.data for c in chosen]))
+        got = result() + tuple(chosen)
+        return got[0] if len(got) == 1 else got
 
     def analyze_pcm_topk(self, raw, bit_depth, lengths, hop, min_tail=0, k=10, activation=0, sensitivity=1.0):
         """bnhip_analyze_pcm_topk: recordings (packed back to back, `lengths` samples each; bit_depth 0 = float32) in, the top-k of
         every overlapping window out - the windows are framed on the device.  -> (conf [W, k], idx [W, k], first_window)."""
-        x, ln = self._analyze_args(raw, bit_depth, lengths)
-        first = analyze_windows(ln, self.n_samples, hop, min_tail)
-        kk, w = min(k, self._n_classes), int(first[-1])
-        conf = np.empty((w, kk), np.float32)
-        idx = np.empty((w, kk), np.int32)
-        _check(self._lib, self._lib.bnhip_analyze_pcm_topk(self._h, x.ctypes.data, bit_depth, ln.ctypes.data, ln.size, int(hop), int(min_tail),
-                                                           activation, sensitivity, k, conf.ctypes.data, idx.ctypes.data))
-        return conf, idx, first
+        return self._analyze(_plain_form(raw, bit_depth, lengths), _topk_answer(), hop, min_tail, k, activation, sensitivity)
 
     def analyze_pcm(self, raw, bit_depth, lengths, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
         """bnhip_analyze_pcm: the same call, answered as detection rows (DETECTION: recording, window inside the recording,
         class_index, confidence) with confidence >= threshold, ordered by window, then rank.  -> (rows, total); cap limits the rows
         written (default: room for every row), total is their number whatever the cap."""
-        x, ln = self._analyze_args(raw, bit_depth, lengths)
-        if cap is None:
-            cap = int(analyze_windows(ln, self.n_samples, hop, min_tail)[-1]) * min(k, self._n_classes)
-        rows = np.zeros(int(cap), DETECTION)
-        n = C.c_size_t(0)
-        _check(self._lib, self._lib.bnhip_analyze_pcm(self._h, x.ctypes.data, bit_depth, ln.ctypes.data, ln.size, int(hop), int(min_tail),
-                                                      activation, sensitivity, k, float(threshold), rows.ctypes.data if cap else None,
-                                                      int(cap), C.byref(n)))
-        return rows[:min(int(cap), n.value)], n.value
-
-    def _analyze_mixed_args(self, raw, recs):
-        self._alive()
-        _analyze_mixed_protos(self._lib)
-        recs = np.ascontiguousarray(recs, RECORDING).reshape(-1)
-        x = np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
-        bad = ~np.isin(recs["bits_per_sample"], (0, 16, 24, 32))
-        if bad.any():
-            raise HipError(E_INVALID, f"unsupported bit depth: {int(recs['bits_per_sample'][bad][0])} (supported: 0 = float32, 16, 24, 32)")
-        want = int((recs["length"] * np.where(recs["bits_per_sample"] == 0, 4, recs["bits_per_sample"] // 8)).sum())
-        if x.size != want:
-            raise HipError(E_INVALID, f"input size mismatch: the recordings hold {want} bytes, got {x.size} bytes")
-        return x, recs
+        return self._analyze(_plain_form(raw, bit_depth, lengths), _rows_answer(threshold, cap), hop, min_tail, k, activation, sensitivity)
 
     def analyze_mixed_pcm_topk(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0):
         """bnhip_analyze_mixed_pcm_topk: recordings at their own rates and depths (a RECORDING table; their bytes packed back to
         back as they are in their files) in, the top-k of every overlapping window at model_rate out - resampled, converted and
         framed on the device.  hop and min_tail count samples at model_rate.  -> (conf [W, k], idx [W, k], first_window)."""
-        x, recs = self._analyze_mixed_args(raw, recs)
-        first, _ = analyze_mixed_windows(recs, model_rate, self.n_samples, hop, min_tail)
-        kk, w = min(k, self._n_classes), int(first[-1])
-        conf = np.empty((w, kk), np.float32)
-        idx = np.empty((w, kk), np.int32)
-        _check(self._lib, self._lib.bnhip_analyze_mixed_pcm_topk(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
-                                                                 int(min_tail), activation, sensitivity, k, conf.ctypes.data, idx.ctypes.data))
-        return conf, idx, first
+        return self._analyze(_mixed_form(raw, recs, model_rate), _topk_answer(), hop, min_tail, k, activation, sensitivity)
 
     def analyze_mixed_pcm(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
         """bnhip_analyze_mixed_pcm: the same call, answered as detection rows, as analyze_pcm answers.  -> (rows, total)."""
-        x, recs = self._analyze_mixed_args(raw, recs)
-        if cap is None:
-            cap = int(analyze_mixed_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]) * min(k, self._n_classes)
-        rows = np.zeros(int(cap), DETECTION)
-        n = C.c_size_t(0)
-        _check(self._lib, self._lib.bnhip_analyze_mixed_pcm(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
-                                                            int(min_tail), activation, sensitivity, k, float(threshold),
-                                                            rows.ctypes.data if cap else None, int(cap), C.byref(n)))
-        return rows[:min(int(cap), n.value)], n.value
+        return self._analyze(_mixed_form(raw, recs, model_rate), _rows_answer(threshold, cap), hop, min_tail, k, activation, sensitivity)
 
     def analyze_channels_pcm_topk(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0):
         """bnhip_analyze_channels_pcm_topk: multichannel recordings (a CHANNELS_RECORDING table; their interleaved frames packed
         back to back as they are in their files) in; each recording's chosen channel, or the mean of its channels, is what
         analyze_mixed_pcm_topk then analyses - fetched, and where asked decided, on the device.
         -> (conf [W, k], idx [W, k], first_window, chosen int32 [n]: the channel read or CHANNEL_MIX)."""
-        self._alive()
-        _analyze_channels_protos(self._lib)
-        x, recs = _channels_bytes(raw, recs)
-        first, _ = analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)
-        kk, w = min(k, self._n_classes), int(first[-1])
-        conf = np.empty((w, kk), np.float32)
-        idx = np.empty((w, kk), np.int32)
-        chosen = np.zeros(recs.size, np.int32)
-        _check(self._lib, self._lib.bnhip_analyze_channels_pcm_topk(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate),
-                                                                    int(hop), int(min_tail), activation, sensitivity, k, conf.ctypes.data,
-                                                                    idx.ctypes.data, chosen.ctypes.data))
-        return conf, idx, first, chosen
+        return self._analyze(_channels_form(raw, recs, model_rate), _topk_answer(), hop, min_tail, k, activation, sensitivity)
 
     def analyze_channels_pcm(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
         """bnhip_analyze_channels_pcm: the same call, answered as detection rows, as analyze_pcm answers.  -> (rows, total, chosen)."""
-        self._alive()
-        _analyze_channels_protos(self._lib)
-        x, recs = _channels_bytes(raw, recs)
-        if cap is None:
-            cap = int(analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]) * min(k, self._n_classes)
-        rows = np.zeros(int(cap), DETECTION)
-        n = C.c_size_t(0)
-        chosen = np.zeros(recs.size, np.int32)
-        _check(self._lib, self._lib.bnhip_analyze_channels_pcm(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
-                                                               int(min_tail), activation, sensitivity, k, float(threshold),
-                                                               rows.ctypes.data if cap else None, int(cap), C.byref(n), chosen.ctypes.data))
-        return rows[:min(int(cap), n.value)], n.value, chosen
-
-    def _events_call(self, entry, head, n_windows, k, filter, cap, extra=()):
-        """The tail of the three *_events calls: room for every event (there are at most as many as rows) unless cap says less."""
-        _analyze_events_protos(self._lib)
-        room = int(n_windows) * min(k, self._n_classes) if cap is None else int(cap)
-        out = np.zeros(room, EVENT)
-        n = C.c_size_t(0)
-        fs = filter._struct(self._n_classes)
-        _check(self._lib, entry(*head, C.addressof(fs), out.ctypes.data if room else None, room, C.byref(n), *extra))
-        return out[:n.value] if cap is None else (out[:min(room, n.value)], n.value)
+        return self._analyze(_channels_form(raw, recs, model_rate), _rows_answer(threshold, cap), hop, min_tail, k, activation, sensitivity)
 
     def analyze_pcm_events(self, raw, bit_depth, lengths, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
         """bnhip_analyze_pcm_events: the analyze_pcm call answered as detection events (EVENT) - the rows merged on the device under
         `filter` (an EventTables).  -> the events, ascending by (recording, class_index, first_window); with cap -> (events[:cap], total)."""
-        x, ln = self._analyze_args(raw, bit_depth, lengths)
-        w = analyze_windows(ln, self.n_samples, hop, min_tail)[-1]
-        _analyze_events_protos(self._lib)
-        head = (self._h, x.ctypes.data, bit_depth, ln.ctypes.data, ln.size, int(hop), int(min_tail), activation, sensitivity, k)
-        return self._events_call(self._lib.bnhip_analyze_pcm_events, head, w, k, filter, cap)
+        return self._analyze(_plain_form(raw, bit_depth, lengths), _events_answer(filter, cap, self._n_classes), hop, min_tail, k, activation, sensitivity)
 
     def analyze_mixed_pcm_events(self, raw, recs, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
         """bnhip_analyze_mixed_pcm_events: analyze_mixed_pcm answered as detection events, as analyze_pcm_events answers."""
-        x, recs = self._analyze_mixed_args(raw, recs)
-        w = analyze_mixed_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]
-        _analyze_events_protos(self._lib)
-        head = (self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop), int(min_tail), activation, sensitivity, k)
-        return self._events_call(self._lib.bnhip_analyze_mixed_pcm_events, head, w, k, filter, cap)
+        return self._analyze(_mixed_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes), hop, min_tail, k, activation, sensitivity)
 
     def analyze_channels_pcm_events(self, raw, recs, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
         """bnhip_analyze_channels_pcm_events: analyze_channels_pcm answered as detection events.  -> (events, chosen); with cap ->
         (events[:cap], total, chosen)."""
-        self._alive()
-        _analyze_events_protos(self._lib)
-        x, recs = _channels_bytes(raw, recs)
-        w = analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)[0][-1]
-        chosen = np.zeros(recs.size, np.int32)
-        head = (self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop), int(min_tail), activation, sensitivity, k)
-        got = self._events_call(self._lib.bnhip_analyze_channels_pcm_events, head, w, k, filter, cap, extra=(chosen.ctypes.data,))
-        return (got, chosen) if cap is None else (got[0], got[1], chosen)
+        return self._analyze(_channels_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes), hop, min_tail, k, activation, sensitivity)
 
     def analyze_channels_pcm_clips(self, raw, recs, model_rate, hop, filter, settings, min_tail=0, k=10, activation=0, sensitivity=1.0,
                                    event_cap=None, max_clips=None, flac_cap=None, png_cap=None):
@@ -767,9 +740,9 @@ class HipClassifier:
         tables [event_cap + 1], untouched (all ones) from n_clips + 1 on."""
         self._alive()
         _analyze_clips_protos(self._lib)
-        x, recs = _channels_bytes(raw, recs)
-        first, n_out = analyze_channels_windows(recs, model_rate, self.n_samples, hop, min_tail)
-        room = int(first[-1]) * min(k, self._n_classes) if event_cap is None else int(event_cap)
+        form = _channels_form(raw, recs, model_rate)
+        first, n_out = form.windows(self.n_samples, hop, min_tail)
+        room = self._room(event_cap, lambda: first, k)
         n_max = min(room, 65535) if max_clips is None else int(max_clips)
         longest = max(1, min(settings.max_samples, int(n_out.max())))
         if not settings.extended:
@@ -782,13 +755,13 @@ class HipClassifier:
         loud = (Loudness * max(room, 1))()
         flac, png = np.empty(max(int(flac_cap), 1), np.uint8), np.empty(max(int(png_cap), 1), np.uint8)
         flac_off, png_off = np.full(room + 1, 2 ** 64 - 1, np.uint64), np.full(room + 1, 2 ** 64 - 1, np.uint64)
-        chosen = np.zeros(recs.size, np.int32)
+        chosen = np.zeros(form.table.size, np.int32)
         fs, xs = filter._struct(self._n_classes), settings._struct()
         o = _ClipsOutStruct(events.ctypes.data, room, 0, spans.ctypes.data, C.addressof(loud), flac.ctypes.data, int(flac_cap), flac_off.ctypes.data,
                             png.ctypes.data, int(png_cap), png_off.ctypes.data, 0)
-        _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips(self._h, x.ctypes.data, recs.ctypes.data, recs.size, int(model_rate), int(hop),
-                                                                     int(min_tail), activation, sensitivity, k, C.addressof(fs), chosen.ctypes.data,
-                                                                     C.addressof(xs), C.addressof(o)))
+        _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips(self._h, form.x.ctypes.data, *form.args, int(hop), int(min_tail), activation,
+                                                                     sensitivity, k, C.addressof(fs), chosen.ctypes.data, C.addressof(xs),
+                                                                     C.addressof(o)))
         n_ev, n = min(room, o.n_events), int(o.n_clips)
         res = ClipsResult(events[:n_ev], int(o.n_events), spans[:n_ev], list(loud[:n]) if settings.normalize else None,
                           _flac_streams(flac, flac_off[:n + 1]) if n else [],

@@ -212,25 +212,29 @@ def clf(gpu):
 
 
 def test_fused_burst(clf):
-    """The five-recording burst (67 windows: three chunks at max_batch 32).  The existing entries answer the same bytes before and
-    after the events calls on the same handle."""
-    recs = _recordings(LENGTHS)
+    """The five-recording burst with its last recording lengthened to just over 2^20 samples (190 windows: six chunks at max_batch
+    32), so that the slot block alone is past the 2 MiB from which a call's device parts share one block (DEV_OWN_BLOCK,
+    csrc/api_oneshot.h) while every table beside it is far below.  The existing entries answer the same bytes before and after the
+    events calls on the same handle."""
+    lengths = LENGTHS[:-1] + [175 * HOP + 2]                                # (as the burst's own last recording: a tail that is dropped)
+    assert lengths[-1] > 1 << 20 and host.analyze_windows(lengths, CLIP, HOP, MIN_TAIL)[-1] == 190
+    recs = _recordings(lengths)
     raw, n_classes = _bytes(np.concatenate(recs), 16), clf.num_species()
-    rows, total = clf.analyze_pcm(raw, 16, LENGTHS, HOP, MIN_TAIL, k=K, threshold=0.0)
-    topk = clf.analyze_pcm_topk(raw, 16, LENGTHS, HOP, MIN_TAIL, k=K)
-    assert total == rows.size == 67 * K
+    rows, total = clf.analyze_pcm(raw, 16, lengths, HOP, MIN_TAIL, k=K, threshold=0.0)
+    topk = clf.analyze_pcm_topk(raw, 16, lengths, HOP, MIN_TAIL, k=K)
+    assert total == rows.size == 190 * K
     f = _pick_filter(rows, n_classes)
     want = evref.events(rows, f)
     assert set(want["status"]) == {0, 1, 2}                              # the comparison cannot pass empty
-    got = clf.analyze_pcm_events(raw, 16, LENGTHS, HOP, f, MIN_TAIL, k=K)
+    got = clf.analyze_pcm_events(raw, 16, lengths, HOP, f, MIN_TAIL, k=K)
     assert np.array_equal(got, want)
-    kept = clf.analyze_pcm_events(raw, 16, LENGTHS, HOP, _without_dropped(f), MIN_TAIL, k=K)
+    kept = clf.analyze_pcm_events(raw, 16, lengths, HOP, _without_dropped(f), MIN_TAIL, k=K)
     assert kept.size and np.array_equal(kept, want[want["status"] == 0])
-    few, n = clf.analyze_pcm_events(raw, 16, LENGTHS, HOP, f, MIN_TAIL, k=K, cap=2)
+    few, n = clf.analyze_pcm_events(raw, 16, lengths, HOP, f, MIN_TAIL, k=K, cap=2)
     assert n == want.size and np.array_equal(few, want[:2])
     assert np.array_equal(host.detection_events(rows, n_classes, f), want)       # the tail alone, over the rows brought down
-    again, total2 = clf.analyze_pcm(raw, 16, LENGTHS, HOP, MIN_TAIL, k=K, threshold=0.0)
-    topk2 = clf.analyze_pcm_topk(raw, 16, LENGTHS, HOP, MIN_TAIL, k=K)
+    again, total2 = clf.analyze_pcm(raw, 16, lengths, HOP, MIN_TAIL, k=K, threshold=0.0)
+    topk2 = clf.analyze_pcm_topk(raw, 16, lengths, HOP, MIN_TAIL, k=K)
     assert total2 == total and again.tobytes() == rows.tobytes()
     assert all(a.tobytes() == b.tobytes() for a, b in zip(topk, topk2))
 
