@@ -91,7 +91,7 @@ bool Engine::bind_device(const WeightPlan& wp, std::string* err, int* code) {
     HIPCHK(hipMalloc((void**)&d_post_conf, (size_t)max_batch * n_classes * 4));
     if (emb_dim) HIPCHK(hipMalloc((void**)&d_stage_emb, (size_t)max_batch * emb_dim * 4));
     if (!defer_weights) mark_bf16_storage();
-    if (autotune && !defer_weights) tune_or_load();
+    if (autotune && !defer_weights) { tune_or_load(); time_fold_proj(); }
     *code = BNHIP_OK;
     return true;
 }
@@ -172,7 +172,7 @@ void Engine::finish_deferred() {
     if (device < 0) return;
     hipSetDevice(device);
     mark_bf16_storage();
-    if (autotune) tune_or_load();
+    if (autotune) { tune_or_load(); time_fold_proj(); }
     defer_weights = false;
 }
 
@@ -235,6 +235,42 @@ bool Engine::norm_resident_taken(int n, const void* x, int bits, const float* xn
     if (norm_pair < 0 || n <= 16) return false;
     const uintptr_t in_align = bits == 16 ? 8 : bits == 24 ? 4 : 16;
     return !(reinterpret_cast<uintptr_t>(x) & (in_align - 1)) && !(reinterpret_cast<uintptr_t>(xn) & 15);
+}
+
+// ---- a narrow projection inside its reader's launch
+// Eligible (plan time): an fp32 engine's pointwise projection on the f32-MFMA kernel with at most 16 output channels from at most 32
+// inputs, no activation, no residual, whose output is read by nothing but the next step - a fused expand+depthwise layer in the
+// chunk-loop small-K form with one K slab and a 3 x 3 stride-2 filter (the instantiated shapes).  In the v2.4 stack that is
+// b1/project -> b2/expand+dw; the other single-reader projections feed layers of 144+ channels and would move more bytes than they save.
+// A call takes the one launch when both steps lie in the part of the plan it runs (a two-phase host call cut between them runs the
+// pair), the projection's tuning is an f32-MFMA tile, and the call is large enough that the chunk loop is not cut into parts
+// (expdw_proj_ok).  BNHIP_FOLD_PROJ=0, read once in build(), keeps the pair everywhere.
+void Engine::find_fold_pair() {
+    fold_pair = -1;
+    if (!fold_proj || precision != 0) return;
+    const int ns = (int)steps.size();
+    for (int si = 0; si + 1 < ns; si++) {
+        const Step& a = steps[si]; const Step& b = steps[si + 1];
+        if (a.kind != S_PW || b.kind != S_EXPAND_DW || b.mode == 1 || b.in0 != a.out || a.out < 0) continue;
+        if (a.in2 >= 0 || a.act != ACT_NONE || a.tail || (a.bx && bf16x3) || a.Co > 16 || a.C > 32 || (a.C & 3) || (a.Co & 3)) continue;
+        if (a.H != b.H || a.W != b.W || a.Co != b.C || b.kh != 3 || b.sh != 2 || expdw_skw(b.C, b.act, false) != 16) continue;
+        if (a.out == v_logits || a.out == v_emb || a.out == v_input || vals[a.out].external) continue;
+        int readers = 0;
+        for (const Step& t : steps)
+            for (int v : {t.in0, t.in1, t.in2}) readers += v == a.out;
+        if (readers != 1) continue;
+        fold_pair = si;
+        break;
+    }
+}
+bool Engine::fold_taken(int si, int n, bool lane_tuning) const {
+    if (fold_pair < 0 || si != fold_pair || !fold_faster) return false;
+    const int s_end = part_s1 < 0 ? (int)steps.size() : part_s1;
+    if (si < part_s0 || si + 1 >= s_end) return false;
+    const Step& a = steps[si]; const Step& b = steps[si + 1];
+    if (a.wbx && (lane_tuning ? a.wm : a.wm_full) >= 5) return false;             // (tuned onto the split-bf16 family: other arithmetic)
+    if (vals[a.in0].half || vals[a.out].half || vals[b.out].half || expdw_pipe16(b)) return false;
+    return expdw_proj_ok(b.shape, expdw_geo(b), n, b.Co);
 }
 
 // ================================================================================================ run
@@ -512,6 +548,7 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
         if (s.kind == S_MEAN_PARTIAL && si > 0 && steps[si - 1].tail == 1 && tail_taken(si - 1, n, nl > 1)) continue;
         if (s.kind == S_MEAN_FINISH && si > 1 && steps[si - 2].tail == 1 && tail_taken(si - 2, n, nl > 1)) continue;
         if (s.kind == S_NORMALIZE && si == norm_pair + 1 && res_x[li]) continue;      // ran inside the clip_minmax step's launch
+        if (s.kind == S_PW && fold_taken(si, n, nl > 1)) continue;                    // runs inside the next step's launch (folded projection)
         ProfEntry pe{};
         // diagnostics (tools/debug): a host-side synchronize before / after every launch of one kernel class
         static const char* dbg_sync_before = getenv("BNHIP_DEBUG_SYNC_BEFORE");
@@ -629,9 +666,19 @@ bool Engine::run_eager(const float* d_in_all, int n_all, float* d_logits_all, fl
             case S_EXPAND_DW:
                 {
                     StemGeom sg{s.H2, s.W2, s.pt2, s.pl2};
-                    launch_expand_dw(in0, s.w0, s.w1, s.w2, s.w3, out, out2, n, s.H, s.W, s.C, s.Co,
-                                     s.Ho, s.Wo, s.kh, s.sh, s.pt, s.pl, s.act, s.act2, s.shape, s.mode == 1 ? &sg : nullptr, stream,
-                                     s.bx ? s.wbx : nullptr, precision, vals[s.out].half ? 1 : 0, vals[s.in0].half ? 1 : 0);
+                    ExpDwProj pj{};
+                    const bool fold = si > 0 && fold_taken(si - 1, n, nl > 1);
+                    if (fold) {
+                        const Step& a = steps[si - 1];
+                        pj = ExpDwProj{vptr(a.in0, d_in, d_logits, d_emb, clip0), a.w0, a.w1, vptr(a.in1, d_in, d_logits, d_emb, clip0), a.C, a.Co};
+                        // (profile: the launch reads the projection's input and gate instead of the projection's output)
+                        pe.more_bytes = 4.0 * s.H * s.W * (a.C - a.Co) + (a.in1 >= 0 ? 4.0 * a.C : 0.0);
+                    }
+                    if (!launch_expand_dw(in0, s.w0, s.w1, s.w2, s.w3, out, out2, n, s.H, s.W, s.C, s.Co,
+                                          s.Ho, s.Wo, s.kh, s.sh, s.pt, s.pl, s.act, s.act2, s.shape, s.mode == 1 ? &sg : nullptr, stream,
+                                          s.bx ? s.wbx : nullptr, precision, vals[s.out].half ? 1 : 0, vals[s.in0].half ? 1 : 0, fold ? &pj : nullptr)) {
+                        *err = "k_expand_dw_sk refused a folded projection its predicate accepted"; mm_dirty = true; return false;
+                    }
                 }
                 break;
             case S_MEAN_PARTIAL:

@@ -146,6 +146,16 @@ class Engine {
     bool pcm_direct = false;            // nothing but that pair reads the input: a PCM call needs no float copy of the batch
     void find_norm_pair();              // plan time
     bool norm_resident_taken(int n, const void* x, int bits, const float* xn) const;   // a lane of n clips runs the pair as the one launch, reading x (float32: bits 0, or PCM)
+    // A narrow projection folded into the fused expand+depthwise launch that is its only reader (k_expand_dw_sk_proj, expdw.hip: the
+    // projection's accumulator is the expand's resident operand).  The plan keeps both steps (find_fold_pair marks the pair), a call
+    // runs them as the one launch where fold_taken holds and as the pair everywhere else - same bits.
+    bool fold_proj = true;              // BNHIP_FOLD_PROJ=0: always the pair; the environment read ONCE in build()
+    int fold_pair = -1;                 // index of the S_PW step whose successor is the S_EXPAND_DW step that absorbs it; else -1
+    bool fold_faster = true;            // create time (time_fold_proj): the one launch beat the pair on this engine's batch
+    float fold_us[2] = {0.f, 0.f};      // ... and the two times it compared: pair, fold (0: not timed)
+    void find_fold_pair();              // plan time
+    bool fold_taken(int si, int n, bool lane_tuning) const;   // a call of n clips runs steps si, si + 1 as the one launch
+    void time_fold_proj();              // create time, after the tuners: pair against fold, back to back, at max_batch
     hipEvent_t ev_ctx_fork = nullptr, ev_ctx_done[kMaxDepth] = {nullptr, nullptr, nullptr};
     unsigned call_idx = 0;
     bool run_pipelined(const float* d_in, int n, float* d_logits, float* d_emb, std::string* err);

@@ -40,6 +40,11 @@ struct ExpDwParams {
     FDiv d_bpc{}, d_cch{}, d_tw{};      // blocks per clip, channel chunks, tiles per row (set by the launcher)
     int cpp = 0;                        // chunk-loop form: channel chunks per block (0 = all: one block per (clip, tile)); small calls cut the loop into parts
     FDiv d_part{};                      // ... and the divisor by the parts per tile
+    // PROJ form of k_expand_dw_sk (the producer's narrow projection folded into the block prologue): x is the PROJECTION's input
+    // [B, H, W, pj_K], pj_w its weights [pj_N][pj_K], pj_b its bias [pj_N] (or null), pj_gate its per-(clip, k) scale [B][pj_K] (or
+    // null); Cin above stays the projection's output width pj_N, the K of the expand
+    const float* pj_w = nullptr; const float* pj_b = nullptr; const float* pj_gate = nullptr;
+    int pj_K = 0, pj_N = 0;
 };
 #define ED_ES 36     // E row stride (floats)
 // Phase 1 feeds the MFMA straight from global memory: every footprint pixel row belongs to exactly one wave
@@ -512,9 +517,22 @@ __global__ __launch_bounds__(256, BX ? expdw_min_waves(K, S, TOW, TRH) : 1) void
 // NS (PH = 1 only): 32-wide slabs of K the block keeps resident - a bf16 fragment is 4 registers per tile and slab, so layers
 // with 48 ... 256 input channels fit the chunk-loop form that the f32 operands (8 registers per 32 channels) reserve for K <= 32
 // (instantiated: 2, 3, 5, 8 slabs = 64, 96, 160, 256 padded channels).
-template <int K, int S, int TOH, int TOW, int TRH, bool STEM, int KW, bool LOOP = !STEM, int NW = 4, int PH = 0, int NS = 1>
-__global__ __launch_bounds__(64 * NW, expdw_sk_waves(K, S, TOH, TOW, TRH, PH == 1 ? 16 * NS : KW, !LOOP, NW)) void k_expand_dw_sk(ExpDwParams p, unsigned nblk) {
+// PROJ (chunk-loop form, KW = 16, f32 pipe): the layer in front is a narrow pointwise projection (N <= 16 output channels from
+// K <= 32, squeeze-excite gate on its input, no activation, no residual) that nothing else reads.  Its output tile IS this kernel's
+// resident operand: a v_mfma_f32_16x16x4_f32 with the projection weights on the A side and the gated input pixel on the B side
+// leaves, in lane (li, kq), D[4 kq .. + 3][li] - channels 4 kq .. + 3 of pixel li, exactly the fragment xA the expand MFMAs read.  So
+// the block prologue loads the projection's input over the footprint (two float4 per owned tile instead of one), multiplies by the
+// gate and runs the projection's 8 MFMAs per tile once - no LDS, no barrier - and the projection's launch, its output tensor and
+// this kernel's read of it are gone.  Every operation is k_pw_gemm's in its order (gate multiply in fp32 at operand-load time,
+// zero accumulator, the permuted K order of both 16-wide slabs, operands beyond K / N exact zeros, bias added afterwards), so the
+// fragment holds the bits the projection would have stored.
+// (the body is shared by two kernel templates - k_expand_dw_sk, whose template list is what recorded profiles and the ISA audit name,
+// and k_expand_dw_sk_proj - and inlined into each; the parameter block by value, as a kernel receives it: by reference the register
+// allocation of every instantiation moved by a register or two)
+template <int K, int S, int TOH, int TOW, int TRH, bool STEM, int KW, bool LOOP, int NW, int PH, int NS, bool PROJ>
+__device__ __forceinline__ void expand_dw_sk_body(ExpDwParams p, unsigned nblk) {
     static_assert(PH == 0 || PH == 1, "phase 1 on the f32 or on the bf16 pipe");
+    static_assert(!PROJ || (LOOP && !STEM && PH == 0 && KW == 16), "folded projection: chunk-loop form on the f32 pipe, one K slab");
     constexpr bool B16 = PH == 1;                             // operands are bf16 fragments of 32-wide slabs
     static_assert(!B16 || (LOOP && !STEM), "bf16 phase 1: chunk-loop form");
     static_assert(NS == 1 || B16, "several resident slabs: bf16 operands only");
@@ -579,8 +597,60 @@ __global__ __launch_bounds__(64 * NW, expdw_sk_waves(K, S, TOH, TOW, TRH, PH == 
     f32x4 xB[(KW == 32 && !B16) ? JTW : 1];              // k = 16 + 4 kq .. (slab 1)
     f32x2 xH[(KW == 24 && !B16) ? JTW : 1];              // k = 16 + 2 kq, + 1 (half slab)
     bf16x8 xb[B16 ? JTW : 1][NS];                        // B16: k = 32 ns + 8 kq .. + 7 of each slab, as bf16
+    // PROJ: the projection's own operands, once per block - weight rows li of both slabs (zero beyond N / K), the lane's bias quad,
+    // the clip's gate over the lane's k quads
+    f32x4 pjw0 = {0.f, 0.f, 0.f, 0.f}, pjw1 = pjw0, pjb = pjw0, pjg0 = {1.f, 1.f, 1.f, 1.f}, pjg1 = pjg0;
+    const bool pjk0 = PROJ && 4 * kq < p.pj_K, pjk1 = PROJ && 16 + 4 * kq < p.pj_K;
+    if constexpr (PROJ) {
+        auto ld4 = [](const float* q) { const float4 t = *reinterpret_cast<const float4*>(q); return (f32x4){t.x, t.y, t.z, t.w}; };
+        if (li < p.pj_N && pjk0) pjw0 = ld4(p.pj_w + li * p.pj_K + 4 * kq);
+        if (li < p.pj_N && pjk1) pjw1 = ld4(p.pj_w + li * p.pj_K + 16 + 4 * kq);
+        if (p.pj_b && 4 * kq < p.pj_N) pjb = ld4(p.pj_b + 4 * kq);
+        if (p.pj_gate) {
+            const float* gq = p.pj_gate + (size_t)b * p.pj_K;
+            pjg0 = ld4(gq + (pjk0 ? 4 * kq : 0));
+            pjg1 = ld4(gq + (pjk1 ? 16 + 4 * kq : 0));
+        }
+    }
     auto load_x = [&]() {
         const float* xbase = STEM ? p.x + (size_t)b * p.Hin * p.Win * 2 : p.x;
+        if constexpr (PROJ) {
+            // all the footprint's loads first, then the MFMAs (tile-outer: tile a's 8 MFMAs run under the loads of the later tiles)
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            f32x4 y0[JTW], y1[JTW];
+#pragma unroll
+            for (int a = 0; a < JTW; a++) {
+                const int j = 16 * (wave + NW * a) + li;
+                const int r = j / TIW, c = j - r * TIW;
+                const int iw = iw0 + c;
+                xin[a] = j < nvalid && iw >= 0 && iw < p.W;
+                const int ihc = min(ih0 + vr0 + r, p.H - 1), iwc = min(max(iw, 0), p.W - 1);
+                const float* xp = xbase + (size_t)((b * p.H * p.W + ihc * p.xsh + iwc * p.xsw) * p.pj_K);
+                // lanes whose k quads lie beyond K read any in-bounds address and feed exact zeros, as k_pw_gemm's operand load does
+                const float4 t = *reinterpret_cast<const float4*>(xp + (pjk0 ? 4 * kq : 0));
+                const float4 t2 = *reinterpret_cast<const float4*>(xp + (pjk1 ? 16 + 4 * kq : 0));
+                y0[a] = (f32x4){t.x, t.y, t.z, t.w}; y1[a] = (f32x4){t2.x, t2.y, t2.z, t2.w};
+            }
+#pragma unroll
+            for (int a = 0; a < JTW; a++) {
+                f32x4 s0 = y0[a], s1 = y1[a];
+                if (p.pj_gate) {
+                    s0[0] *= pjg0[0]; s0[1] *= pjg0[1]; s0[2] *= pjg0[2]; s0[3] *= pjg0[3];
+                    s1[0] *= pjg1[0]; s1[1] *= pjg1[1]; s1[2] *= pjg1[2]; s1[3] *= pjg1[3];
+                }
+                s0 = pjk0 ? s0 : z; s1 = pjk1 ? s1 : z;
+                f32x4 d = z;
+                if (wave + NW * a < jtv) {                 // (wave-uniform: the tiles the chunk loop will use)
+#pragma unroll
+                    for (int sidx = 0; sidx < 4; sidx++) d = __builtin_amdgcn_mfma_f32_16x16x4f32(pjw0[sidx], s0[sidx], d, 0, 0, 0);
+#pragma unroll
+                    for (int sidx = 0; sidx < 4; sidx++) d = __builtin_amdgcn_mfma_f32_16x16x4f32(pjw1[sidx], s1[sidx], d, 0, 0, 0);
+                    if (p.pj_b) d += pjb;
+                }
+                xA[a] = d;
+            }
+            return;
+        }
 #pragma unroll
         for (int a = 0; a < JTW; a++) {
             const int j = 16 * (wave + NW * a) + li;
@@ -815,6 +885,16 @@ __global__ __launch_bounds__(64 * NW, expdw_sk_waves(K, S, TOH, TOW, TRH, PH == 
     }
 }
 
+template <int K, int S, int TOH, int TOW, int TRH, bool STEM, int KW, bool LOOP = !STEM, int NW = 4, int PH = 0, int NS = 1>
+__global__ __launch_bounds__(64 * NW, expdw_sk_waves(K, S, TOH, TOW, TRH, PH == 1 ? 16 * NS : KW, !LOOP, NW)) void k_expand_dw_sk(ExpDwParams p, unsigned nblk) {
+    expand_dw_sk_body<K, S, TOH, TOW, TRH, STEM, KW, LOOP, NW, PH, NS, false>(p, nblk);
+}
+// the chunk-loop form with the producer's projection in its prologue (PROJ above): one K slab, f32 pipe
+template <int K, int S, int TOH, int TOW, int TRH, int NW>
+__global__ __launch_bounds__(64 * NW, expdw_sk_waves(K, S, TOH, TOW, TRH, 16, false, NW)) void k_expand_dw_sk_proj(ExpDwParams p, unsigned nblk) {
+    expand_dw_sk_body<K, S, TOH, TOW, TRH, false, 16, true, NW, 0, 1, true>(p, nblk);
+}
+
 // K of the expand GEMM as the kernel walks it: 16-wide slabs plus, when Cin <= 8 mod 16, one 8-wide half slab (two MFMA
 // steps instead of four: Cin = 24 / 40 would otherwise spend 25 % / 17 % of their MFMAs on zero columns)
 int expdw_kw(int Cin) { return (Cin & 1) ? (Cin + 15) / 16 * 16 : (Cin + 7) / 8 * 8; }
@@ -957,6 +1037,28 @@ bool expdw_supported(int k, int s, int Cin, int Cmid, int act_e, int prec) {
     // (k_expand_dw_sk<PH = 1, NS = 5 | 8>: 160 / 256 padded input channels, 2 NS MFMAs of 16 cycles per tile and chunk)
     return prec == 1 && expdw_sk_pipe16(Cin, act_e, false, prec, true);
 }
+// Small calls of the chunk-loop form: chunks per block when a (clip, tile)'s loop is cut into parts (ExpDwParams::cpp), 0 when one
+// block walks them all
+static int expdw_cut_cpp(int B, int tiles, int cchunks) {
+    const int cus = device_cus();
+    if (cchunks <= 1 || (long)B * tiles >= cus / 2) return 0;
+    const int want = (int)std::min<long>(cchunks, (cus + (long)B * tiles - 1) / ((long)B * tiles));
+    const int cpp = (cchunks + want - 1) / want, nparts = (cchunks + cpp - 1) / cpp;
+    return nparts > 1 ? cpp : 0;
+}
+// The folded-projection form (k_expand_dw_sk_proj) exists for the 3 x 3 stride-2 shapes of the chunk-loop form with one K slab.
+// A call of B clips takes it when the layer is in that form on the f32 pipe (g.skw == 16), the shape is one of those, and the call
+// is large enough that one block walks all the chunks of its tile (a cut loop would project once per part).
+bool expdw_proj_ok(int shape, const ExpDwGeo& g0, int B, int Cmid) {
+    if (g0.stem || g0.skw != 16) return false;
+    if (!expdw_shape_fits(shape, g0, false)) shape = expdw_default_shape(g0);
+    if (shape < 0) return false;
+    const ExpDwShape& sh = kExpDwShapes[shape % kNumExpDwShapes];
+    if (sh.k != 3 || sh.s != 2) return false;
+    const ExpDwGeo g = expdw_oriented(shape, g0);
+    const int tiles = ((g.Ho + sh.toh - 1) / sh.toh) * ((g.Wo + sh.tow - 1) / sh.tow);
+    return expdw_cut_cpp(B, tiles, (Cmid + 31) / 32) == 0;
+}
 // k_expand_dw of one tile shape: the full-width form where the shape has one and the launch qualifies
 template <int K, int S, int TH, int TW, int TR, bool H8, bool BX>
 static void ed_launch(const ExpDwParams& p, unsigned nblk, hipStream_t st, bool fullw) {
@@ -969,20 +1071,22 @@ static void ed_launch(const ExpDwParams& p, unsigned nblk, hipStream_t st, bool 
     }
     hipLaunchKernelGGL((k_expand_dw<K, S, TH, TW, TR, H8, BX>), dim3(nblk), dim3(256), 0, st, p, nblk);
 }
-void launch_expand_dw(const float* x, const float* we, const float* be, const float* wd, const float* bd, float* y,
+bool launch_expand_dw(const float* x, const float* we, const float* be, const float* wd, const float* bd, float* y,
                       float* partial, int B, int H, int W, int Cin, int Cmid, int Ho, int Wo, int k, int s, int pt,
                       int pl, int act_e, int act_d, int shape, const StemGeom* stem, hipStream_t st, const uint16_t* wep, int prec, int out_bf16,
-                      int in_bf16) {
+                      int in_bf16, const ExpDwProj* proj) {
     // (a layer whose phase 1 runs on the bf16 pipe never takes an eight-wave shape - those exist in the f32 form only - so that
     // the arithmetic of a layer does not depend on which tile the tuner preferred: skw = 0 withholds them)
     const bool pipe16 = expdw_sk_pipe16(Cin, act_e, stem != nullptr, prec, wep != nullptr);
     const ExpDwGeo g0{k, s, H, W, Ho, Wo, pt, pl, stem != nullptr, pipe16 ? 0 : expdw_skw(Cin, act_e, stem != nullptr)};
+    // (a folded projection is launched where expdw_proj_ok holds and nowhere else: a refusal is the caller's bug, not a fallback)
+    if (proj && (pipe16 || out_bf16 || in_bf16 || proj->N != Cin || proj->K > 32 || (proj->K & 3) || (proj->N & 3) || !expdw_proj_ok(shape, g0, B, Cmid))) return false;
     if (!expdw_shape_fits(shape, g0, false)) shape = expdw_default_shape(g0);
-    if (shape < 0) return;                             // the planner only fuses layers some shape accepts
+    if (shape < 0) return true;                        // the planner only fuses layers some shape accepts
     const ExpDwShape* sh = &kExpDwShapes[shape % kNumExpDwShapes];
     const bool tr = shape >= kNumExpDwShapes;
     const ExpDwGeo g = expdw_oriented(shape, g0);
-    ExpDwParams p{x, we, be, wd, bd, y, partial, B, g.H, g.W, Cin, Cmid, g.Ho, g.Wo, g.pt, g.pl, act_e, act_d,
+    ExpDwParams p{proj ? proj->x : x, we, be, wd, bd, y, partial, B, g.H, g.W, Cin, Cmid, g.Ho, g.Wo, g.pt, g.pl, act_e, act_d,
                   (g.Ho + sh->toh - 1) / sh->toh, (g.Wo + sh->tow - 1) / sh->tow, (Cmid + 31) / 32, expdw_kw(Cin), expdw_cp(Cmid)};
     // the kernel's rows are image columns when tr: one kernel row step = one pixel, one kernel column step = an image row
     p.xsh = tr ? 1 : W; p.xsw = tr ? W : 1; p.ysh = tr ? 1 : Wo; p.ysw = tr ? Wo : 1; p.tr = tr ? 1 : 0;
@@ -1010,16 +1114,12 @@ void launch_expand_dw(const float* x, const float* we, const float* be, const fl
         p.d_bpc = make_fdiv((unsigned)tiles);
         // ... unless the call is so small that the chip would idle behind a few serial chunk loops (one clip: 12-24 blocks walking
         // five chunks each, 19-24 us): then the loop is cut into parts until the grid has about one block per CU
-        const int cus = device_cus();
-        if (p.cchunks > 1 && (long)B * tiles < cus / 2) {
-            const int want = (int)std::min<long>(p.cchunks, (cus + (long)B * tiles - 1) / ((long)B * tiles));
-            const int cpp = (p.cchunks + want - 1) / want, nparts = (p.cchunks + cpp - 1) / cpp;
-            if (nparts > 1) {
-                p.cpp = cpp;
-                p.d_part = make_fdiv((unsigned)nparts);
-                nblk = (unsigned)B * tiles * nparts;
-                p.d_bpc = make_fdiv((unsigned)(tiles * nparts));
-            }
+        if (const int cpp = expdw_cut_cpp(B, tiles, p.cchunks)) {
+            const int nparts = (p.cchunks + cpp - 1) / cpp;
+            p.cpp = cpp;
+            p.d_part = make_fdiv((unsigned)nparts);
+            nblk = (unsigned)B * tiles * nparts;
+            p.d_bpc = make_fdiv((unsigned)(tiles * nparts));
         }
     }
     if (stem) {
@@ -1027,24 +1127,37 @@ void launch_expand_dw(const float* x, const float* we, const float* be, const fl
 #define ED_STEM(TH_, TW_, TR_)                                                                                \
     if (sh->k == 3 && sh->s == 1 && sh->toh == TH_ && sh->tow == TW_ && sh->trh == TR_) {                     \
         hipLaunchKernelGGL((k_expand_dw_sk<3, 1, TH_, TW_, TR_, true, 24>), dim3(nblk), dim3(256), 0, st, p, nblk);  \
-        return;                                                                                               \
+        return true;                                                                                          \
     }
         ED_STEM(8, 16, 10) ED_STEM(4, 16, 6) ED_STEM(8, 32, 6) ED_STEM(8, 32, 10)
 #undef ED_STEM
-        return;
+        return true;
     }
-#define ED_CASE8(K_, S_, TH_, TW_, TR_)                                                                       \
+    if (proj) {
+        // (expdw_proj_ok above: chunk-loop form on the f32 pipe, Kw = 16, a 3 x 3 stride-2 shape, the loop uncut)
+        if (!sk || p.Kw != 16 || p.cpp != 0) return false;
+        p.pj_w = proj->w; p.pj_b = proj->bias; p.pj_gate = proj->gate; p.pj_K = proj->K; p.pj_N = proj->N;
+#define ED_PROJ(TH_, TW_, TR_, NW_)                                                                           \
+    if (sh->nw == NW_ && sh->toh == TH_ && sh->tow == TW_ && sh->trh == TR_) {                                \
+        hipLaunchKernelGGL((k_expand_dw_sk_proj<3, 2, TH_, TW_, TR_, NW_>), dim3(nblk), dim3(64 * NW_), 0, st, p, nblk); \
+        return true;                                                                                          \
+    }
+        ED_PROJ(4, 8, 9, 4) ED_PROJ(8, 8, 12, 4) ED_PROJ(8, 8, 17, 4) ED_PROJ(8, 8, 12, 8) ED_PROJ(8, 8, 17, 8)
+#undef ED_PROJ
+        return false;
+    }
+#define ED_CASE8(K_, S_, TH_, TW_, TR_)                                                                     \
     if (sh->nw == 8 && sh->k == K_ && sh->s == S_ && sh->toh == TH_ && sh->tow == TW_ && sh->trh == TR_) {    \
         if (p.Kw == 16) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 16, true, 8>), dim3(nblk), dim3(512), 0, st, p, nblk); \
         else if (p.Kw == 24) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 24, true, 8>), dim3(nblk), dim3(512), 0, st, p, nblk); \
         else hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 32, true, 8>), dim3(nblk), dim3(512), 0, st, p, nblk); \
-        return;                                                                                               \
+        return true;                                                                                          \
     }
     if (sh->nw == 8) {
-        if (!sk || stem) return;                       // (expdw_shape_fits never offers these to other layers)
+        if (!sk || stem) return true;                     // (expdw_shape_fits never offers these to other layers)
         ED_CASE8(3, 1, 8, 16, 10) ED_CASE8(3, 1, 8, 32, 6) ED_CASE8(3, 1, 8, 32, 10) ED_CASE8(5, 1, 8, 16, 12) ED_CASE8(5, 1, 8, 32, 6)
         ED_CASE8(3, 2, 8, 8, 12) ED_CASE8(3, 2, 8, 8, 17) ED_CASE8(5, 2, 8, 8, 19)
-        return;
+        return true;
     }
 #undef ED_CASE8
 #define ED_CASE(K_, S_, TH_, TW_, TR_)                                                                        \
@@ -1060,13 +1173,14 @@ void launch_expand_dw(const float* x, const float* we, const float* be, const fl
         else if (sk && p.Kw == 32) hipLaunchKernelGGL((k_expand_dw_sk<K_, S_, TH_, TW_, TR_, false, 32>), dim3(nblk), dim3(256), 0, st, p, nblk); \
         else if (p.Kw & 8) ed_launch<K_, S_, TH_, TW_, TR_, true, false>(p, nblk, st, fullw);                     \
         else ed_launch<K_, S_, TH_, TW_, TR_, false, false>(p, nblk, st, fullw);                                  \
-        return;                                                                                               \
+        return true;                                                                                          \
     }
     ED_CASE(3, 1, 8, 16, 10) ED_CASE(3, 1, 4, 16, 6) ED_CASE(3, 1, 8, 32, 6) ED_CASE(3, 1, 8, 32, 10)
     ED_CASE(5, 1, 8, 16, 12) ED_CASE(5, 1, 4, 16, 8) ED_CASE(5, 1, 8, 32, 6) ED_CASE(5, 1, 12, 16, 12)
     ED_CASE(3, 2, 4, 8, 9) ED_CASE(3, 2, 8, 8, 12) ED_CASE(3, 2, 8, 8, 17)
     ED_CASE(5, 2, 4, 8, 11) ED_CASE(5, 2, 4, 16, 6) ED_CASE(5, 2, 8, 8, 19)
 #undef ED_CASE
+    return true;
 }
 
 // plain depthwise conv staged through LDS: the fused kernel in COPY mode (its phase 2 alone), same shape indices as above

@@ -264,14 +264,21 @@ struct StemGeom { int Hin, Win, pt, pl; };   // raw image size and the stem conv
 // parameters are the planner's padded copies: we [expdw_cp(Cmid)][expdw_kw(Cin)], be/bd [Cp], wd [k*k][Cp] (zeros beyond)
 int expdw_kw(int Cin);
 int expdw_cp(int Cmid);
-void launch_expand_dw(const float* x, const float* we, const float* be, const float* wd, const float* bd, float* y,
+// The narrow projection in front of a chunk-loop layer, folded into that layer's launch (k_expand_dw_sk_proj, expdw.hip): x is the
+// projection's input [B, H, W, K], w its weights [N][K], bias [N] or null, gate its per-(clip, k) input scale [B][K] or null; no
+// activation, no residual; N is the fused layer's Cin.  expdw_proj_ok: a call of B clips with tile shape `shape` can take the form.
+struct ExpDwProj { const float* x; const float* w; const float* bias; const float* gate; int K, N; };
+bool expdw_proj_ok(int shape, const ExpDwGeo& g, int B, int Cmid);
+// returns false (nothing launched) only for a folded projection the form does not cover
+bool launch_expand_dw(const float* x, const float* we, const float* be, const float* wd, const float* bd, float* y,
                       float* partial, int B, int H, int W, int Cin, int Cmid, int Ho, int Wo, int k, int s, int pt,
                       int pl, int act_e, int act_d, int shape /* index into the shape table; -1 = cost model */,
                       const StemGeom* stem /* non-null: x is the raw image and the expand is the 3x3/2 stem (see expdw.hip) */,
                       hipStream_t st, const uint16_t* wep = nullptr /* non-null: phase 1 on the split-bf16 MFMA (expdw_bx_image) */,
                       int prec = 0 /* with wep: 1 = plain bf16 operands (one product) */,
                       int out_bf16 = 0 /* y is written as bf16 (bf16 activation storage; Cmid % 4 == 0) */,
-                      int in_bf16 = 0 /* x holds bf16 values (bf16 residual stream): only where expdw_sk_pipe16 holds */);
+                      int in_bf16 = 0 /* x holds bf16 values (bf16 residual stream): only where expdw_sk_pipe16 holds */,
+                      const ExpDwProj* proj = nullptr /* non-null: x is ignored, the layer's input is projected in the block prologue */);
 // plain depthwise convolution through the same kernel (COPY mode: LDS-staged taps); shape as for launch_expand_dw, partial
 // (nullable) [B, expdw_shape_slabs(shape, geo), C]
 bool dwconv_lds_supported(const DwParams& p);

@@ -1599,6 +1599,7 @@ bool Engine::build(TflModel m, int dev, int maxb, bool plan_only, std::string* e
     max_batch = maxb;
     pw_sw = pw_switches_from_env();      // (tests flip these between engines of one process; nothing reads them after this line)
     if (const char* e = getenv("BNHIP_NORM_RESIDENT")) norm_resident = atoi(e) != 0;
+    if (const char* e = getenv("BNHIP_FOLD_PROJ")) fold_proj = atoi(e) != 0;
     const PlanSwitches sw;
     *code = BNHIP_E_UNSUPPORTED;
     // graph rewrites first (float16 constants behind DEQUANTIZE, unfolded batch norm, PAD + VALID convolutions): the
@@ -1617,6 +1618,7 @@ bool Engine::build(TflModel m, int dev, int maxb, bool plan_only, std::string* e
     tensor_value = L.tv;
     mark_tails();
     find_norm_pair();
+    find_fold_pair();
 
     mark_liveness(vals, steps);
     if (v_emb >= 0) vals[v_emb].last = (int)steps.size();      // keep until copy-out
@@ -1635,9 +1637,17 @@ bool Engine::build(TflModel m, int dev, int maxb, bool plan_only, std::string* e
     // gets its own copy of the (smaller) lane layout instead.
     n_lanes = std::max(1, std::min(n_lanes, kMaxLanes));
     lane_cap = (max_batch + n_lanes - 1) / n_lanes;
+    // (a folded projection's operands - its input and gate - are read by the launch of the NEXT step: for the layout they live one
+    // step longer, so that step's outputs never land on them; the plan's own liveness, which pick_split reads, is unchanged)
+    const int fv0 = fold_pair >= 0 ? steps[fold_pair].in0 : -1, fv1 = fold_pair >= 0 ? steps[fold_pair].in1 : -1;
+    const int fl0 = fv0 >= 0 ? vals[fv0].last : 0, fl1 = fv1 >= 0 ? vals[fv1].last : 0;
+    if (fv0 >= 0) vals[fv0].last = std::max(fl0, fold_pair + 1);
+    if (fv1 >= 0) vals[fv1].last = std::max(fl1, fold_pair + 1);
     act_bytes = plan_arena(vals, steps, (size_t)max_batch, false, no_reuse);
     lane_bytes = n_lanes > 1 ? align_up(plan_arena(vals, steps, (size_t)lane_cap, true, no_reuse), 256) : 0;
     act_bytes = std::max(act_bytes, lane_bytes * (size_t)n_lanes);
+    if (fv0 >= 0) vals[fv0].last = fl0;
+    if (fv1 >= 0) vals[fv1].last = fl1;
     pick_split();
 
     w_bytes = L.w.img.size() * sizeof(float);

@@ -466,6 +466,34 @@ void Engine::autotune_pw() {
     });
 }
 
+// The folded projection (find_fold_pair) against the pair of launches it replaces, both back to back at max_batch with the tunings
+// the calls will run (the projection's tile, the fused layer's shape): the form is kept only where the one launch is faster than the
+// two together.  Not part of the tuning text - the verdict is one bit about two kernels that compute the same bits, timed in
+// well under a millisecond, so every engine takes its own whatever its tiles came from.
+void Engine::time_fold_proj() {
+    fold_faster = true; fold_us[0] = fold_us[1] = 0.f;
+    if (fold_pair < 0 || device < 0) return;
+    const int n = max_batch;
+    if (!fold_taken(fold_pair, n, false)) return;                   // (this batch would run the pair anyway: nothing to time)
+    const Step& a = steps[fold_pair]; const Step& b = steps[fold_pair + 1];
+    PwParams p = pw_params(a, n, false);
+    p.A = vptr(a.in0, d_stage_in, d_stage_logits, nullptr); p.ascale = vptr(a.in1, d_stage_in, d_stage_logits, nullptr);
+    p.out = vptr(a.out, d_stage_in, d_stage_logits, nullptr);
+    float* out = vptr(b.out, d_stage_in, d_stage_logits, nullptr);
+    float* out2 = vptr(b.out2, d_stage_in, d_stage_logits, nullptr);
+    const ExpDwProj pj{p.A, a.w0, a.w1, p.ascale, a.C, a.Co};
+    auto expdw = [&](const ExpDwProj* proj) {
+        launch_expand_dw(p.out, b.w0, b.w1, b.w2, b.w3, out, out2, n, b.H, b.W, b.C, b.Co, b.Ho, b.Wo, b.kh, b.sh, b.pt, b.pl, b.act, b.act2,
+                         b.shape, nullptr, stream, nullptr, precision, 0, 0, proj);
+    };
+    LaunchTimer timer(stream);
+    const float pair = timer.back_to_back([&]() { launch_pw_gemm(p, stream); expdw(nullptr); });
+    const float fold = timer.back_to_back([&]() { expdw(&pj); });
+    fold_us[0] = pair * 1e3f; fold_us[1] = fold * 1e3f;
+    fold_faster = fold < pair;
+    if (getenv("BNHIP_DEBUG")) fprintf(stderr, "[bnhip] tune %s + %s: pair %.1f us, one launch %.1f us -> %s\n", a.name.c_str(), b.name.c_str(), pair * 1e3, fold * 1e3, fold_faster ? "folded" : "pair");
+}
+
 // Per marked layer and per tuning (a lane's batch, max_batch): every fused candidate - row tiles of 48 / 96 / 192 rows, column
 // tiles of 64 / 96 / 128 - against the SUM of the GEMM's tuned tile and the depthwise (or the two mean) launches it would replace.
 void Engine::autotune_tail() {
