@@ -1,0 +1,371 @@
+// C ABI of the real-time detection-event bank (events_bank.h; include/bnhip.h, "Detection events: the real-time bank").
+//
+// Every call is one transaction in the discipline of stream_bank.h: one H2D copy of the call's header (the sources of the call,
+// ascending, with their clocks and parities; the row map; for the host form the rows), the launches, one copy back (the count and the
+// first events; a second copy only for an answer beyond EVB_FIRST_FETCH events), one synchronise, and a commit that runs only once
+// everything succeeded - the host flips the parities and advances the clocks there, so a failed call changes no source.  The
+// bank's frames are rows, not PCM, and a call's answer is counted on the device, so bank_call itself does not fit; its buffers
+// (bank_grow) and its teardown (bank_free) do.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "api_events.h"
+#include "events_bank.h"
+#include "stream_bank.h"
+
+using namespace bnhip;
+
+static_assert(BNHIP_EVENT_PENDING == EVENT_PENDING, "the status of events_bank.h");
+static_assert(sizeof(EvbGroup) == 32, "a group header is 32 bytes");
+
+struct bnhip_event_bank {
+    struct Source {
+        int64_t clock = 0;              // windows given since creation or reset
+        int parity = 0;                 // slab read by the next call
+        bool live = false;              // the slab holds state (false: every slot free, no veto window)
+    };
+    std::mutex mu;                      // calls on one bank are serialised
+    std::mutex tick_mu;                 // ... and so are the ticks that feed it: d_rows is theirs from the first chunk to the bank's call
+    int device = 0, max_sources = 0, n_classes = 0, k = 0, hold = 0, slots = 0;
+    float veto_thr = 0.0f;
+    int min_count = 1, flags = 0;
+    bool tables_dirty = true;           // h_tab is newer than d_tab: the next call's header copy takes it along
+    std::vector<Source> src;
+    hipStream_t stream = nullptr;       // the bank's own, made at the first call that needs it: a bank fed by the tick alone runs on
+                                        // the model's stream and adds none to the few hardware queues a process has (hostpipe.cpp)
+    int32_t* d_state = nullptr;         // [max_sources][2][evb_slab_ints(slots)]
+    char* h_tab = nullptr; char* d_tab = nullptr;                                 // class_threshold [n_classes] | class_veto [n_classes]
+    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // groups | row map | rows
+    uint8_t* h_out = nullptr; void* d_out = nullptr; size_t out_cap = 0;         // count, overflow flag | events
+    void* d_work = nullptr; size_t work_cap = 0;                                 // staged events | counts and bases
+    void* d_rows = nullptr; size_t rows_cap = 0;                                 // the fused tick's rows: conf [n][k] | idx [n][k]
+    ~bnhip_event_bank() {               // (bank_free has drained the stream)
+        if (stream) hipStreamDestroy(stream);
+        for (void* p : {(void*)d_state, (void*)d_tab, d_stage, d_out, d_work, d_rows}) if (p) hipFree(p);
+        for (void* p : {(void*)h_tab, (void*)h_stage, (void*)h_out}) if (p) hipHostFree(p);
+    }
+};
+
+namespace {
+
+constexpr const char* WHAT = "event bank";
+constexpr int EVB_MAX_CLASSES = 150 * 1024 / 4;   // what the LDS top-k holds (api_events.cpp)
+constexpr size_t EVB_FIRST_FETCH = 127;           // events that come down with the count: 16 + 127 * 32 = 4080 bytes
+constexpr size_t EVB_HEAD = 16;
+
+int evb_fail(hipError_t he) {
+    (void)hipGetLastError();
+    return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(WHAT) + ": " + hipGetErrorString(he));
+}
+
+void evb_take_filter(bnhip_event_bank* b, const bnhip_event_filter* f) {
+    memcpy(b->h_tab, f->class_threshold, (size_t)b->n_classes * 4);
+    uint8_t* veto = reinterpret_cast<uint8_t*>(b->h_tab) + (size_t)b->n_classes * 4;
+    if (f->class_veto) memcpy(veto, f->class_veto, (size_t)b->n_classes);
+    else memset(veto, 0, (size_t)b->n_classes);
+    b->veto_thr = f->veto_threshold; b->min_count = f->min_count; b->flags = f->flags;
+    b->tables_dirty = true;
+}
+
+// the bank's own stream (the bank is locked); NULL with the error set
+hipStream_t evb_stream(bnhip_event_bank* b) {
+    if (b->stream) return b->stream;
+    hipSetDevice(b->device);
+    const hipError_t he = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (he != hipSuccess) { b->stream = nullptr; evb_fail(he); }
+    return b->stream;
+}
+
+// One call (the bank is locked).  EVB_PROCESS: rows r = 0..n_rows-1 of sources[r]; conf / idx are host rows, or with on_device rows
+// on the bank's device.  EVB_FLUSH / EVB_PENDING: the live slots of `one` (or of every source: -1).  The call runs on s, or with
+// own_stream on the bank's own.
+int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, const float* conf, const int32_t* idx, bool on_device, int one,
+             bnhip_event* out, size_t cap, size_t* n_out, bool own_stream, hipStream_t s) {
+    const int k = b->k;
+    std::vector<EvbGroup> groups;
+    std::vector<int32_t> rowmap;
+    size_t stage_total = 0;
+    auto add_group = [&](int source, int n_windows, uint32_t row_off) {
+        const bnhip_event_bank::Source& S = b->src[(size_t)source];
+        const size_t room = (S.live ? (size_t)b->slots : 0) + (size_t)n_windows * (size_t)k;      // the live events and those the call opens
+        EvbGroup g{};
+        g.source = source; g.clock = (int32_t)S.clock; g.n_windows = n_windows; g.row_off = row_off;
+        g.stage_off = (uint32_t)stage_total; g.stage_cap = (uint32_t)room;
+        g.rd_parity = S.live ? S.parity : -1; g.wr_parity = S.parity ^ 1;
+        groups.push_back(g);
+        stage_total += room;
+    };
+    if (mode == EVB_PROCESS) {
+        if (n_rows < 0) return set_err(BNHIP_E_INVALID, "n_rows is negative");
+        if ((unsigned long long)n_rows * (unsigned long long)k >= EVENT_MAX_ROWS) return set_err(BNHIP_E_INVALID, "n_rows * k of 2^31 or more");
+        if (n_rows > 0 && (!sources || !conf || !idx)) return set_err(BNHIP_E_INVALID, "NULL argument");
+        std::vector<std::pair<int32_t, int32_t>> order;                   // (source, row) of the rows that count
+        order.reserve((size_t)n_rows);
+        for (int r = 0; r < n_rows; r++) {
+            if (sources[r] < 0) continue;                                 // (a source that was reset under the tick)
+            if (sources[r] >= b->max_sources)
+                return set_err(BNHIP_E_INVALID, "row " + std::to_string(r) + ": no such event bank source: " + std::to_string(sources[r]));
+            if (!on_device)
+                for (int i = 0; i < k; i++)
+                    if (idx[(size_t)r * k + i] >= b->n_classes)
+                        return set_err(BNHIP_E_INVALID, "row " + std::to_string(r) + ": class_index outside the table");
+            order.emplace_back(sources[r], r);
+        }
+        std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& c) { return a.first < c.first; });
+        rowmap.resize(order.size());
+        for (size_t i = 0; i < order.size();) {
+            size_t j = i;
+            while (j < order.size() && order[j].first == order[i].first) { rowmap[j] = order[j].second; j++; }
+            if (b->src[(size_t)order[i].first].clock + (int64_t)(j - i) > (int64_t)INT32_MAX)
+                return set_err(BNHIP_E_INVALID, "source " + std::to_string(order[i].first) + ": the clock would pass 2^31 - 1 windows (reset the source)");
+            add_group(order[i].first, (int)(j - i), (uint32_t)i);
+            i = j;
+        }
+    } else {
+        if (one < -1 || one >= b->max_sources) return set_err(BNHIP_E_INVALID, "no such event bank source: " + std::to_string(one));
+        for (int sn = one < 0 ? 0 : one; sn < (one < 0 ? b->max_sources : one + 1); sn++)
+            if (b->src[(size_t)sn].live) add_group(sn, 0, 0);
+    }
+    if (groups.empty()) { *n_out = 0; return BNHIP_OK; }
+
+    // ---- stage
+    hipSetDevice(b->device);
+    if (own_stream && !(s = evb_stream(b))) return BNHIP_E_RUNTIME;
+    const size_t G = groups.size(), row_vals = on_device || mode != EVB_PROCESS ? 0 : (size_t)n_rows * (size_t)k;
+    const size_t o_map = G * sizeof(EvbGroup), o_conf = o_map + rowmap.size() * 4, o_idx = o_conf + row_vals * 4;
+    const size_t stage_bytes = o_idx + row_vals * 4;
+    const size_t out_room = std::min(cap, stage_total);
+    const size_t o_counts = stage_total * sizeof(Event);
+    if (!bank_grow((void**)&b->h_stage, &b->d_stage, &b->stage_cap, stage_bytes) ||
+        !bank_grow((void**)&b->h_out, &b->d_out, &b->out_cap, EVB_HEAD + std::max<size_t>(out_room, 1) * sizeof(Event)))
+        return set_err(BNHIP_E_NOMEM, std::string("allocation failed (") + WHAT + " staging)");
+    if (b->work_cap < o_counts + 2 * G * 4) {
+        const size_t want = o_counts + 2 * G * 4, c = std::max<size_t>(want + want / 2, 1 << 16);
+        void* nd = nullptr;
+        if (hipMalloc(&nd, c) != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_NOMEM, std::string("allocation failed (") + WHAT + " work area)"); }
+        if (b->d_work) hipFree(b->d_work);
+        b->d_work = nd; b->work_cap = c;
+    }
+    memcpy(b->h_stage, groups.data(), o_map);
+    if (!rowmap.empty()) memcpy(b->h_stage + o_map, rowmap.data(), rowmap.size() * 4);
+    if (row_vals) {
+        memcpy(b->h_stage + o_conf, conf, row_vals * 4);
+        memcpy(b->h_stage + o_idx, idx, row_vals * 4);
+    }
+    const size_t tab_bytes = (size_t)b->n_classes * 5;
+    hipError_t he = hipSuccess;
+    if (b->tables_dirty) he = hipMemcpyAsync(b->d_tab, b->h_tab, tab_bytes, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(b->d_stage, b->h_stage, stage_bytes, hipMemcpyHostToDevice, s);
+    if (he != hipSuccess) { hipStreamSynchronize(s); return evb_fail(he); }
+
+    // ---- run
+    const char* ds = static_cast<const char*>(b->d_stage);
+    char* dw = static_cast<char*>(b->d_work);
+    char* dout = static_cast<char*>(b->d_out);
+    EvbCall c{};
+    c.groups = reinterpret_cast<const EvbGroup*>(ds); c.n_groups = (int)G;
+    c.rowmap = reinterpret_cast<const int32_t*>(ds + o_map);
+    c.conf = row_vals ? reinterpret_cast<const float*>(ds + o_conf) : conf;
+    c.idx = row_vals ? reinterpret_cast<const int32_t*>(ds + o_idx) : idx;
+    c.k = k; c.slots = b->slots; c.mode = mode;
+    c.state = b->d_state;
+    c.stage = reinterpret_cast<Event*>(dw);
+    c.counts = reinterpret_cast<uint32_t*>(dw + o_counts);
+    c.head = reinterpret_cast<unsigned long long*>(dout);
+    c.out = reinterpret_cast<Event*>(dout + EVB_HEAD);
+    c.out_cap = out_room;
+    const EventFilterDev fd{reinterpret_cast<const float*>(b->d_tab), reinterpret_cast<const uint8_t*>(b->d_tab) + (size_t)b->n_classes * 4,
+                            b->veto_thr, b->hold, b->min_count, b->flags, b->n_classes};
+    launch_event_bank(c, fd, s);
+    he = hipGetLastError();
+    const size_t first_n = std::min(out_room, EVB_FIRST_FETCH);
+    if (he == hipSuccess) he = hipMemcpyAsync(b->h_out, b->d_out, EVB_HEAD + first_n * sizeof(Event), hipMemcpyDeviceToHost, s);
+    const hipError_t hs = hipStreamSynchronize(s);
+    if (he == hipSuccess) he = hs;
+    if (he != hipSuccess) return evb_fail(he);
+    unsigned long long head[2];
+    memcpy(head, b->h_out, sizeof head);
+    if (head[1]) return set_err(BNHIP_E_RUNTIME, std::string(WHAT) + ": a source ran out of slots");
+    const size_t total = (size_t)head[0];
+    if (total > cap) {
+        *n_out = total;
+        return set_err(BNHIP_E_INVALID, "event buffer too small: the call answers " + std::to_string(total) + " events");
+    }
+    if (total > first_n) {
+        he = hipMemcpyAsync(b->h_out + EVB_HEAD + first_n * sizeof(Event), dout + EVB_HEAD + first_n * sizeof(Event), (total - first_n) * sizeof(Event),
+                            hipMemcpyDeviceToHost, s);
+        const hipError_t hs2 = hipStreamSynchronize(s);
+        if (he == hipSuccess) he = hs2;
+        if (he != hipSuccess) return evb_fail(he);
+    }
+    if (total) memcpy(out, b->h_out + EVB_HEAD, total * sizeof(Event));
+    *n_out = total;
+
+    // ---- commit: everything above succeeded
+    b->tables_dirty = false;
+    if (mode == EVB_PENDING) return BNHIP_OK;
+    for (const EvbGroup& g : groups) {
+        bnhip_event_bank::Source& S = b->src[(size_t)g.source];
+        if (mode == EVB_FLUSH) { S.live = false; continue; }             // (no slot is live any more, and the veto windows lie behind the clock)
+        S.parity ^= 1;
+        S.live = true;
+        S.clock += g.n_windows;
+    }
+    return BNHIP_OK;
+}
+
+// what create and set_filter refuse of the filter and the bank's shape together
+int evb_shape_check(const bnhip_event_filter* f, int k) {
+    if (int rc = event_filter_check(f)) return rc;
+    if (k < 1) return set_err(BNHIP_E_INVALID, "k must be at least 1");
+    if ((long long)k * f->hold_windows > EVB_MAX_SLOTS) return set_err(BNHIP_E_INVALID, "k * hold_windows must be at most 4096");
+    return BNHIP_OK;
+}
+
+int evb_answer_check(const bnhip_event_bank* b, const bnhip_event* out, size_t cap, const size_t* n_out) {
+    if (!b || !n_out || (cap && !out)) return set_err(BNHIP_E_INVALID, "NULL argument");
+    return BNHIP_OK;
+}
+
+}  // namespace
+
+namespace bnhip {
+int event_bank_device(const bnhip_event_bank* b) { return b->device; }
+int event_bank_k(const bnhip_event_bank* b) { return b->k; }
+std::mutex& event_bank_tick_mutex(bnhip_event_bank* b) { return b->tick_mu; }
+int event_bank_rows(bnhip_event_bank* b, size_t n_rows, float** d_conf, int32_t** d_idx) {
+    std::lock_guard<std::mutex> lk(b->mu);
+    const size_t half = (n_rows * (size_t)b->k * 4 + 255) / 256 * 256;
+    if (b->rows_cap < 2 * half) {
+        hipSetDevice(b->device);
+        void* nd = nullptr;
+        if (hipMalloc(&nd, 2 * half) != hipSuccess) { (void)hipGetLastError(); return set_err(BNHIP_E_NOMEM, "allocation failed (event bank rows)"); }
+        if (b->d_rows) hipFree(b->d_rows);
+        b->d_rows = nd; b->rows_cap = 2 * half;
+    }
+    *d_conf = static_cast<float*>(b->d_rows);
+    *d_idx = reinterpret_cast<int32_t*>(static_cast<char*>(b->d_rows) + half);
+    return BNHIP_OK;
+}
+}  // namespace bnhip
+
+extern "C" {
+
+int bnhip_event_bank_create(int device, int max_sources, int n_classes, int k, const bnhip_event_filter* filter, bnhip_event_bank** out) {
+    if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (int rc = evb_shape_check(filter, k)) return rc;
+    if (max_sources < 1 || max_sources > 65535) return set_err(BNHIP_E_INVALID, "max_sources must be in [1, 65535]");
+    if (n_classes < 1 || n_classes > EVB_MAX_CLASSES) return set_err(BNHIP_E_INVALID, "n_classes must be in [1, 38400]");
+    bnhip_event_bank* b = nullptr;
+    BN_GUARD_BEGIN
+    if (int rc = use_device(device)) return rc;
+    b = new bnhip_event_bank();
+    b->device = device; b->max_sources = max_sources; b->n_classes = n_classes; b->k = k; b->hold = filter->hold_windows;
+    b->slots = std::min(k * filter->hold_windows, n_classes);
+    b->src.resize((size_t)max_sources);
+    hipError_t he = hipMalloc((void**)&b->d_state, (size_t)max_sources * 2 * evb_slab_ints(b->slots) * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&b->d_tab, (size_t)n_classes * 5);
+    if (he == hipSuccess) he = hipHostMalloc((void**)&b->h_tab, (size_t)n_classes * 5, hipHostMallocPortable);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        bank_free(b); b = nullptr;
+        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(WHAT) + " create: " + hipGetErrorString(he));
+    }
+    evb_take_filter(b, filter);
+    *out = b;
+    return BNHIP_OK;
+    BN_GUARD_END(bank_free(b))
+}
+
+int bnhip_event_bank_info(const bnhip_event_bank* b, int* max_sources, int* n_classes, int* k, int* hold_windows, int* slots_per_source) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (max_sources) *max_sources = b->max_sources;
+    if (n_classes) *n_classes = b->n_classes;
+    if (k) *k = b->k;
+    if (hold_windows) *hold_windows = b->hold;
+    if (slots_per_source) *slots_per_source = b->slots;
+    return BNHIP_OK;
+}
+
+int bnhip_event_bank_set_filter(bnhip_event_bank* b, const bnhip_event_filter* filter) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (int rc = event_filter_check(filter)) return rc;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (filter->hold_windows != b->hold)
+        return set_err(BNHIP_E_INVALID, "hold_windows is fixed for the bank's life: " + std::to_string(b->hold) + ", not " + std::to_string(filter->hold_windows));
+    evb_take_filter(b, filter);
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_event_bank_process(bnhip_event_bank* b, const int32_t* sources, int n_rows, const float* conf, const int32_t* idx, bnhip_event* out,
+                             size_t cap, size_t* n_out) {
+    if (int rc = evb_answer_check(b, out, cap, n_out)) return rc;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    return evb_call(b, EVB_PROCESS, sources, n_rows, conf, idx, false, -1, out, cap, n_out, true, nullptr);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_event_bank_process_device(bnhip_event_bank* b, const int32_t* sources, int n_rows, const float* d_conf, const int32_t* d_idx,
+                                    bnhip_event* out, size_t cap, size_t* n_out, void* stream) {
+    if (int rc = evb_answer_check(b, out, cap, n_out)) return rc;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    return evb_call(b, EVB_PROCESS, sources, n_rows, d_conf, d_idx, true, -1, out, cap, n_out, false, static_cast<hipStream_t>(stream));
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_event_bank_flush(bnhip_event_bank* b, int source, bnhip_event* out, size_t cap, size_t* n_out) {
+    if (int rc = evb_answer_check(b, out, cap, n_out)) return rc;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    return evb_call(b, EVB_FLUSH, nullptr, 0, nullptr, nullptr, false, source, out, cap, n_out, true, nullptr);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_event_bank_pending(bnhip_event_bank* b, bnhip_event* out, size_t cap, size_t* n_out) {
+    if (int rc = evb_answer_check(b, out, cap, n_out)) return rc;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    return evb_call(b, EVB_PENDING, nullptr, 0, nullptr, nullptr, false, -1, out, cap, n_out, true, nullptr);
+    BN_GUARD_END((void)0)
+}
+
+// host only: a source without state reads as "every slot free, no veto window"
+int bnhip_event_bank_reset(bnhip_event_bank* b, int source) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (source < -1 || source >= b->max_sources) return set_err(BNHIP_E_INVALID, "no such event bank source: " + std::to_string(source));
+    for (int sn = source < 0 ? 0 : source; sn < (source < 0 ? b->max_sources : source + 1); sn++) {
+        b->src[(size_t)sn].live = false;
+        b->src[(size_t)sn].clock = 0;
+    }
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_event_bank_clock(bnhip_event_bank* b, int source, int64_t* windows) {
+    if (!b || !windows) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (source < 0 || source >= b->max_sources) return set_err(BNHIP_E_INVALID, "no such event bank source: " + std::to_string(source));
+    *windows = b->src[(size_t)source].clock;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+void bnhip_event_bank_destroy(bnhip_event_bank* b) {
+    try { bank_free(b); } catch (...) {}
+}
+
+}  // extern "C"

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <mutex>
+
 #include "api_oneshot.h"
 #include "events.h"
 
@@ -21,5 +23,13 @@ EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, c
 // records are copied to out - that copy is left in flight on s.  A failure goes into b.
 void fetch_counted(const void* d_total, const void* d_records, size_t record_bytes, size_t cap, void* out, unsigned long long* total, hipStream_t s,
                    DevBlocks& b);
+
+// the real-time bank (api_event_bank.cpp), as the tick entry (api_predict.cpp) needs it
+int event_bank_device(const bnhip_event_bank* b);
+int event_bank_k(const bnhip_event_bank* b);
+// one tick at a time feeds a bank: held from before the first chunk until the bank's call has returned
+std::mutex& event_bank_tick_mutex(bnhip_event_bank* b);
+// room on the bank's device for the rows of a tick, kept and grown by the bank: conf [n_rows][k], idx [n_rows][k]
+int event_bank_rows(bnhip_event_bank* b, size_t n_rows, float** d_conf, int32_t** d_idx);
 
 }  // namespace bnhip

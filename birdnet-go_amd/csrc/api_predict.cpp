@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "api_events.h"
 #include "api_model.h"
 #include "heatmap.h"
 #include "hostpipe.h"
@@ -239,16 +240,12 @@ int bnhip_range_heatmap(bnhip_model* m, const float* coords, int n_cells, int sp
     BN_GUARD_END((void)0)
 }
 
-// One tick: who is ready -> rows filled chunk by chunk under the device's work on the previous chunks -> top-k.
-int bnhip_windows_predict_topk(bnhip_windows* w, bnhip_model* m, int bits_per_sample, int activation, double sensitivity, int k,
-                               int* sources, int* n_windows, float* out_conf, int32_t* out_idx, const void** batch) {
-    if (!w || !m || !sources || !n_windows || !out_conf || !out_idx) return set_err(BNHIP_E_INVALID, "NULL argument");
-    *n_windows = 0;
-    if (batch) *batch = w->batch;
-    if (!pcm_depth_known(bits_per_sample))
-        return set_err(BNHIP_E_INVALID, "unsupported bit depth: " + std::to_string(bits_per_sample) + " (supported: 16, 24, 32)");
-    if (k <= 0) return set_err(BNHIP_E_INVALID, "n_clips and k must be positive");
-    if (activation < 0 || activation > 2) return set_err(BNHIP_E_INVALID, "unknown activation");
+// One tick: who is ready -> rows filled chunk by chunk under the device's work on the previous chunks -> top-k.  With a bank
+// (bnhip_windows_predict_events) the top-k rows of every chunk also stay on the device, and the bank's call runs behind the last
+// chunk on the model's stream: every refusal of the bank stage that can be known before the windows are taken is answered first.
+static int windows_tick(bnhip_windows* w, bnhip_model* m, bnhip_event_bank* bank, int bits_per_sample, int activation, double sensitivity, int k,
+                        int* sources, int* n_windows, float* out_conf, int32_t* out_idx, const void** batch, bnhip_event* events, size_t cap,
+                        size_t* n_events) {
     bool begun = false;
     BN_GUARD_BEGIN
     Engine& e = m->eng();
@@ -259,6 +256,18 @@ int bnhip_windows_predict_topk(bnhip_windows* w, bnhip_model* m, int bits_per_sa
         return set_err(BNHIP_E_INVALID, "window size mismatch: assembler " + std::to_string(w->a->window_bytes()) + " bytes, model clip " +
                                         std::to_string(clip_bytes) + " bytes");
     bnhip::WindowAssembler& a = *w->a;
+    const int kk = std::min(k, e.n_classes);
+    float* d_keep_conf = nullptr;                           // the tick's rows on the device, for the bank
+    int32_t* d_keep_idx = nullptr;
+    std::unique_lock<std::mutex> feeding;
+    if (bank) {
+        if (m->engs.size() > 1) return set_err(BNHIP_E_INVALID, "bnhip_windows_predict_events: the bank lives on one device; use a single-device handle");
+        if (event_bank_device(bank) != e.device) return set_err(BNHIP_E_INVALID, "model and event bank are on different devices");
+        if (event_bank_k(bank) != kk)
+            return set_err(BNHIP_E_INVALID, "the tick's rows hold " + std::to_string(kk) + " results, the event bank's " + std::to_string(event_bank_k(bank)));
+        feeding = std::unique_lock<std::mutex>(event_bank_tick_mutex(bank));
+        if (int rc = event_bank_rows(bank, (size_t)a.max_batch(), &d_keep_conf, &d_keep_idx)) return rc;
+    }
     const int n = a.collect_begin(a.max_batch(), sources);
     begun = true;
     if (n == 0) { a.collect_end(); return BNHIP_OK; }       // "try again later"
@@ -273,6 +282,7 @@ int bnhip_windows_predict_topk(bnhip_windows* w, bnhip_model* m, int bits_per_sa
     HostJob call;
     call.src = rows; call.pcm_bits = bits_per_sample; call.topk = k; call.activation = activation; call.sensitivity = sensitivity;
     call.out_conf = out_conf; call.out_idx = out_idx;
+    call.d_keep_conf = d_keep_conf; call.d_keep_idx = d_keep_idx;
     int rc = shard_run(m, n, [=](Engine& en, int off, int cnt, std::string& err) {
         HostJob j = shard_job(en, call, off, cnt);
         j.prepare = [=](int first, int c) { fill(off + first, c); };
@@ -288,8 +298,36 @@ int bnhip_windows_predict_topk(bnhip_windows* w, bnhip_model* m, int bits_per_sa
     a.collect_end();
     begun = false;
     *n_windows = n;
+    if (rc == BNHIP_OK && bank) rc = bnhip_event_bank_process_device(bank, sources, n, d_keep_conf, d_keep_idx, events, cap, n_events, e.stream);
     return rc;
     BN_GUARD_END(if (begun) w->a->collect_end())
+}
+
+int bnhip_windows_predict_topk(bnhip_windows* w, bnhip_model* m, int bits_per_sample, int activation, double sensitivity, int k,
+                               int* sources, int* n_windows, float* out_conf, int32_t* out_idx, const void** batch) {
+    if (!w || !m || !sources || !n_windows || !out_conf || !out_idx) return set_err(BNHIP_E_INVALID, "NULL argument");
+    *n_windows = 0;
+    if (batch) *batch = w->batch;
+    if (!pcm_depth_known(bits_per_sample))
+        return set_err(BNHIP_E_INVALID, "unsupported bit depth: " + std::to_string(bits_per_sample) + " (supported: 16, 24, 32)");
+    if (k <= 0) return set_err(BNHIP_E_INVALID, "n_clips and k must be positive");
+    if (activation < 0 || activation > 2) return set_err(BNHIP_E_INVALID, "unknown activation");
+    return windows_tick(w, m, nullptr, bits_per_sample, activation, sensitivity, k, sources, n_windows, out_conf, out_idx, batch, nullptr, 0, nullptr);
+}
+
+int bnhip_windows_predict_events(bnhip_windows* w, bnhip_model* m, bnhip_event_bank* bank, int bits_per_sample, int activation, double sensitivity,
+                                 int k, int* sources, int* n_windows, float* out_conf, int32_t* out_idx, const void** batch, bnhip_event* events,
+                                 size_t cap, size_t* n_events) {
+    if (!w || !m || !bank || !sources || !n_windows || !out_conf || !out_idx || !n_events || (cap && !events))
+        return set_err(BNHIP_E_INVALID, "NULL argument");
+    *n_windows = 0;
+    *n_events = 0;
+    if (batch) *batch = w->batch;
+    if (!pcm_depth_known(bits_per_sample))
+        return set_err(BNHIP_E_INVALID, "unsupported bit depth: " + std::to_string(bits_per_sample) + " (supported: 16, 24, 32)");
+    if (k <= 0) return set_err(BNHIP_E_INVALID, "n_clips and k must be positive");
+    if (activation < 0 || activation > 2) return set_err(BNHIP_E_INVALID, "unknown activation");
+    return windows_tick(w, m, bank, bits_per_sample, activation, sensitivity, k, sources, n_windows, out_conf, out_idx, batch, events, cap, n_events);
 }
 
 int bnhip_debug_fetch(bnhip_model* m, int tensor_index, int n_clips, float* out, size_t cap_floats) {

@@ -1,0 +1,195 @@
+// The streaming detection-event rule on the device (events_bank.h).
+//
+// k_evb_update  one wave per source of the call.  The source's slots come into LDS (lanes take slots 64 at a step), the wave walks the
+//               source's windows of this call in order - per result a ballot on class over the live slots, the matching lane joins or
+//               the lowest free slot opens; the veto window rises; the slots that are due are staged, their status final, and freed -
+//               and the slots go out to the slab of the other parity.  Flush ("every live slot is due") and pending ("stage without
+//               freeing") are modes of the same walk.
+// k_evb_scan    one block: the exclusive scan of the sources' answered counts, sources ascending, and their total.
+// k_evb_emit    one block per source: a staged event's rank is the number of the source's staged events with a smaller (class, first
+//               window), counted against keys in LDS; it lands at base + rank.
+// Integer work bound by latency: plain loads and stores, compares, ballots; nothing is accumulated in floating point.
+#include "events_bank.h"
+
+#include "block_scan.h"
+#include "kernels.h"
+
+namespace bnhip {
+
+namespace {
+
+using u32 = unsigned int;
+using u64 = unsigned long long;
+
+constexpr int EVB_KEY_TILE = 1024;
+
+__global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) {
+    extern __shared__ int evb_sm[];
+    const int S = c.slots, lane = threadIdx.x;
+    int* cls = evb_sm;
+    int* first = evb_sm + S;
+    int* last = evb_sm + 2 * S;
+    int* best = evb_sm + 3 * S;
+    int* count = evb_sm + 4 * S;
+    float* conf = reinterpret_cast<float*>(evb_sm + 5 * S);
+    const EvbGroup g = c.groups[blockIdx.x];
+    const size_t slab = (size_t)S * 6 + 4;
+    const int* rd = g.rd_parity >= 0 ? c.state + ((size_t)g.source * 2 + (size_t)g.rd_parity) * slab : nullptr;
+    int* wr = c.state + ((size_t)g.source * 2 + (size_t)g.wr_parity) * slab;
+    for (int s = lane; s < S; s += 64) {
+        cls[s] = rd ? rd[s] : -1;
+        first[s] = rd ? rd[S + s] : 0;
+        last[s] = rd ? rd[2 * S + s] : 0;
+        best[s] = rd ? rd[3 * S + s] : 0;
+        count[s] = rd ? rd[4 * S + s] : 0;
+        conf[s] = rd ? __int_as_float(rd[5 * S + s]) : 0.0f;
+    }
+    int veto_win = rd ? rd[6 * S] : -1;            // the source's largest veto-hit window so far
+    __syncthreads();
+    const u64 lt = (1ull << lane) - 1ull;
+    u32 staged = 0;
+    bool overflow = false;
+    Event* stage = c.stage + g.stage_off;
+
+    // the live slots that are due after window w (every live slot in the flush and pending modes): staged in slot order, freed
+    // unless the call only looks
+    auto stage_due = [&](long long w) {
+        for (int s0 = 0; s0 < S; s0 += 64) {
+            const int s = s0 + lane;
+            const bool live = s < S && cls[s] >= 0;
+            const bool due = live && (c.mode != EVB_PROCESS || (long long)first[s] + f.hold <= w + 1);
+            int status = EVENT_PENDING;
+            if (due && c.mode != EVB_PENDING)
+                status = count[s] < f.min_count ? EVENT_FEW : veto_win >= first[s] ? EVENT_VETOED : EVENT_KEPT;
+            const bool answered = due && (c.mode == EVB_PENDING || status == EVENT_KEPT || (f.flags & EVENTS_KEEP_DROPPED));
+            const u64 m = __ballot(answered);
+            const u32 pos = staged + (u32)__popcll(m & lt);
+            if (answered) {
+                if (pos < g.stage_cap) {
+                    Event e;
+                    e.recording = g.source; e.cls = cls[s]; e.first_window = first[s]; e.last_window = last[s];
+                    e.best_window = best[s]; e.count = count[s]; e.confidence = conf[s]; e.status = status;
+                    stage[pos] = e;
+                } else {
+                    overflow = true;
+                }
+            }
+            if (due && c.mode != EVB_PENDING) cls[s] = -1;
+            staged += (u32)__popcll(m);
+        }
+        __syncthreads();
+    };
+
+    if (c.mode != EVB_PROCESS) {
+        stage_due(0);
+    } else {
+        for (int j = 0; j < g.n_windows; j++) {
+            const size_t row = (size_t)c.rowmap[g.row_off + j] * (size_t)c.k;
+            const int w = g.clock + j;
+            for (int i = 0; i < c.k; i++) {
+                const float x = c.conf[row + i];
+                const int ci = c.idx[row + i];
+                if ((u32)ci >= (u32)f.n_classes) continue;             // no result
+                if (f.veto[ci] != 0) {
+                    if (x > f.veto_thr) veto_win = w;
+                    continue;
+                }
+                if (!(x > f.thr[ci])) continue;                        // float32, strict, false for a NaN on either side
+                bool placed = false;
+                for (int s0 = 0; s0 < S && !placed; s0 += 64) {        // at most one live slot holds the class
+                    const int s = s0 + lane;
+                    const bool mine = s < S && cls[s] == ci;
+                    if (__ballot(mine) == 0) continue;
+                    if (mine) {
+                        last[s] = w;
+                        count[s] += 1;
+                        if (x > conf[s]) { conf[s] = x; best[s] = w; }  // (ties: the earliest stays)
+                    }
+                    placed = true;
+                }
+                for (int s0 = 0; s0 < S && !placed; s0 += 64) {        // the lowest free slot opens the event
+                    const int s = s0 + lane;
+                    const u64 free_m = __ballot(s < S && cls[s] < 0);
+                    if (free_m == 0) continue;
+                    if (lane == __ffsll((long long)free_m) - 1) {
+                        cls[s] = ci; first[s] = w; last[s] = w; best[s] = w; count[s] = 1; conf[s] = x;
+                    }
+                    placed = true;
+                }
+                if (!placed) overflow = true;                          // (never: slots = min(k * hold, n_classes) is exact)
+                __syncthreads();
+            }
+            stage_due(w);
+        }
+        for (int s = lane; s < S; s += 64) {
+            wr[s] = cls[s];
+            wr[S + s] = first[s];
+            wr[2 * S + s] = last[s];
+            wr[3 * S + s] = best[s];
+            wr[4 * S + s] = count[s];
+            wr[5 * S + s] = __float_as_int(conf[s]);
+        }
+        if (lane == 0) wr[6 * S] = veto_win;
+    }
+    const bool any_overflow = __ballot(overflow) != 0;
+    if (lane == 0) c.counts[blockIdx.x] = any_overflow ? 0u : staged;
+    if (any_overflow && lane == 0) c.head[1] = 1ull;
+}
+
+// counts[0 .. n) -> their exclusive bases at counts[n .. 2n), 256 at a time with a running carry; the total to head[0]
+__global__ __launch_bounds__(256) void k_evb_scan(u32* __restrict__ counts, u32 n, u64* __restrict__ head) {
+    __shared__ u64 sh[256];
+    u64 carry = 0;
+    for (u32 b0 = 0; b0 < n; b0 += 256) {
+        const u32 b = b0 + threadIdx.x;
+        const u64 v = b < n ? (u64)counts[b] : 0ull;
+        const u64 incl = block_scan(v, sh, threadIdx.x);
+        if (b < n) counts[n + b] = (u32)(carry + incl - v);
+        const u64 sum = sh[255];
+        __syncthreads();                          // (sh is written again by the next round's scan)
+        carry += sum;
+    }
+    if (threadIdx.x == 0) head[0] = carry;
+}
+
+__device__ __forceinline__ u64 evb_key(const Event& e) { return ((u64)(u32)e.cls << 32) | (u32)e.first_window; }
+
+__global__ __launch_bounds__(256) void k_evb_emit(EvbCall c) {
+    __shared__ u64 keys[EVB_KEY_TILE];
+    const u32 tid = threadIdx.x, G = (u32)c.n_groups;
+    const EvbGroup g = c.groups[blockIdx.x];
+    const u32 n = min(c.counts[blockIdx.x], g.stage_cap);
+    const u64 base = c.counts[G + blockIdx.x];
+    const Event* stage = c.stage + g.stage_off;
+    for (u32 i0 = 0; i0 < n; i0 += 256) {
+        const u32 i = i0 + tid;
+        const bool mine = i < n;
+        Event e{};
+        if (mine) e = stage[i];
+        const u64 key = evb_key(e);
+        u32 rank = 0;
+        for (u32 t0 = 0; t0 < n; t0 += EVB_KEY_TILE) {
+            const u32 m = min((u32)EVB_KEY_TILE, n - t0);
+            __syncthreads();
+            for (u32 q = tid; q < m; q += 256) keys[q] = evb_key(stage[t0 + q]);
+            __syncthreads();
+            if (mine) for (u32 q = 0; q < m; q++) rank += keys[q] < key ? 1u : 0u;
+        }
+        const u64 o = base + rank;
+        if (mine && o < c.out_cap) c.out[o] = e;
+    }
+}
+
+}  // namespace
+
+void launch_event_bank(const EvbCall& c, const EventFilterDev& f, hipStream_t s) {
+    hipMemsetAsync(c.head, 0, 16, s);
+    if (c.n_groups <= 0) return;
+    const int lds = c.slots * 6 * 4;
+    lds_limit_once<k_evb_update>(EVB_MAX_SLOTS * 6 * 4);
+    hipLaunchKernelGGL(k_evb_update, dim3((u32)c.n_groups), dim3(64), lds, s, c, f);
+    hipLaunchKernelGGL(k_evb_scan, dim3(1), dim3(256), 0, s, c.counts, (u32)c.n_groups, c.head);
+    hipLaunchKernelGGL(k_evb_emit, dim3((u32)c.n_groups), dim3(256), 0, s, c);
+}
+
+}  // namespace bnhip

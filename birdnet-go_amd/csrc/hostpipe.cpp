@@ -357,6 +357,10 @@ int small_run(Engine& e, const HostJob& j, std::string& err) {
         if (kk) {
             launch_activation(e.d_stage_logits, e.d_post_conf, n, e.n_classes, j.activation, j.sensitivity, e.stream);
             launch_topk(e.d_post_conf, n, e.n_classes, kk, e.d_topk_conf, e.d_topk_idx, e.stream);
+            if (j.d_keep_conf) {
+                HP_TRY(hipMemcpyAsync(j.d_keep_conf + (size_t)off * kk, e.d_topk_conf, (size_t)n * kk * 4, hipMemcpyDeviceToDevice, e.stream), "D2D copy");
+                HP_TRY(hipMemcpyAsync(j.d_keep_idx + (size_t)off * kk, e.d_topk_idx, (size_t)n * kk * 4, hipMemcpyDeviceToDevice, e.stream), "D2D copy");
+            }
             HP_TRY(hipMemcpyAsync(j.out_conf + (size_t)off * kk, e.d_topk_conf, (size_t)n * kk * 4, hipMemcpyDeviceToHost, e.stream), "D2H copy");
             HP_TRY(hipMemcpyAsync(j.out_idx + (size_t)off * kk, e.d_topk_idx, (size_t)n * kk * 4, hipMemcpyDeviceToHost, e.stream), "D2H copy");
         }
@@ -548,6 +552,10 @@ int host_run_split(Engine& e, const HostJob& j, const std::vector<int>& csize, s
             if (kk) {
                 launch_activation(o.d_logits, o.d_conf, gn, e.n_classes, j.activation, j.sensitivity, st);
                 launch_topk(o.d_conf, gn, e.n_classes, kk, o.d_tkc, o.d_tki, st);
+                if (j.d_keep_conf) {
+                    HP_PIPE(hipMemcpyAsync(j.d_keep_conf + (size_t)first * kk, o.d_tkc, (size_t)gn * kk * 4, hipMemcpyDeviceToDevice, st), "D2D copy");
+                    HP_PIPE(hipMemcpyAsync(j.d_keep_idx + (size_t)first * kk, o.d_tki, (size_t)gn * kk * 4, hipMemcpyDeviceToDevice, st), "D2D copy");
+                }
             }
             HP_PIPE(hipEventRecord(o.ev_done, st), "event record");   // (back phase of group g done)
             if (trace) hipEventRecord(tev[2 + 3 * nch + 2 * g], st);
@@ -759,6 +767,10 @@ int host_run(Engine& e, const HostJob& j, std::string& err) {
         if (kk) {
             launch_activation(s.d_logits, s.d_conf, n, e.n_classes, j.activation, j.sensitivity, cs);
             launch_topk(s.d_conf, n, e.n_classes, kk, s.d_tkc, s.d_tki, cs);
+            if (j.d_keep_conf) {
+                HP_PIPE(hipMemcpyAsync(j.d_keep_conf + (size_t)cfirst[c] * kk, s.d_tkc, (size_t)n * kk * 4, hipMemcpyDeviceToDevice, cs), "D2D copy");
+                HP_PIPE(hipMemcpyAsync(j.d_keep_idx + (size_t)cfirst[c] * kk, s.d_tki, (size_t)n * kk * 4, hipMemcpyDeviceToDevice, cs), "D2D copy");
+            }
         }
         HP_PIPE(hipEventRecord(s.ev_comp, cs), "event record");
         if (trace) hipEventRecord(tev[3 + 3 * c], cs);

@@ -27,6 +27,10 @@ struct HostJob {
     double sensitivity = 1.0;
     float* out_conf = nullptr;
     int32_t* out_idx = nullptr;
+    // optional: the call's top-k rows also stay on the device, [n_clips][min(topk, n_classes)] each, copied device to device behind
+    // every chunk's top-k on that chunk's stream (bnhip_windows_predict_events: the event bank reads them there)
+    float* d_keep_conf = nullptr;
+    int32_t* d_keep_idx = nullptr;
     // Optional producer of the input: when set, clips [first, first + n) of `src` do not exist until prepare(first, n) has
     // returned.  The pipeline calls it once per chunk, in order, where it would otherwise start staging that chunk - i.e. while
     // the previous chunks are on the device (bnhip_windows_predict_topk: the window assembler fills the rows then).

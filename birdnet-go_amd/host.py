@@ -63,7 +63,10 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_analyze_mixed_pcm", "bnhip_analyze_channels_windows", "bnhip_analyze_channels_pcm_topk",
            "bnhip_analyze_channels_pcm", "bnhip_channel_energy_pcm", "bnhip_analyze_pcm_events", "bnhip_analyze_mixed_pcm_events",
            "bnhip_analyze_channels_pcm_events", "bnhip_detection_events", "bnhip_event_min_count",
-           "bnhip_event_clip_spans", "bnhip_recording_clips_pcm16", "bnhip_analyze_channels_pcm_clips"]
+           "bnhip_event_clip_spans", "bnhip_recording_clips_pcm16", "bnhip_analyze_channels_pcm_clips", "bnhip_event_bank_create",
+           "bnhip_event_bank_info", "bnhip_event_bank_set_filter", "bnhip_event_bank_process", "bnhip_event_bank_process_device",
+           "bnhip_event_bank_flush", "bnhip_event_bank_reset", "bnhip_event_bank_pending", "bnhip_event_bank_clock",
+           "bnhip_event_bank_destroy", "bnhip_windows_predict_events"]
 
 
 class HipError(RuntimeError):
@@ -276,6 +279,121 @@ def detection_events(rows, n_classes, filter, device=0, cap=None):
     _check(lib, lib.bnhip_detection_events(int(device), rows.ctypes.data if rows.size else None, rows.size, int(n_classes), C.addressof(fs),
                                            out.ctypes.data if room else None, room, C.byref(n)))
     return out[:n.value] if cap is None else (out[:min(room, n.value)], n.value)
+
+
+def _event_bank_protos(lib):
+    """... and of the real-time event bank and its tick (apart again, for the same reason)."""
+    _analyze_events_protos(lib)
+    vp, ci, sz = C.c_void_p, C.c_int, C.c_size_t
+    answer = [vp, sz, C.POINTER(sz)]                                                  # out, cap, n_out
+    lib.bnhip_event_bank_create.argtypes = [ci, ci, ci, ci, vp, C.POINTER(vp)]
+    lib.bnhip_event_bank_info.argtypes = [vp] + [C.POINTER(ci)] * 5
+    lib.bnhip_event_bank_set_filter.argtypes = [vp, vp]
+    lib.bnhip_event_bank_process.argtypes = [vp, vp, ci, vp, vp] + answer
+    lib.bnhip_event_bank_process_device.argtypes = [vp, vp, ci, vp, vp] + answer + [vp]
+    lib.bnhip_event_bank_flush.argtypes = [vp, ci] + answer
+    lib.bnhip_event_bank_reset.argtypes = [vp, ci]
+    lib.bnhip_event_bank_pending.argtypes = [vp] + answer
+    lib.bnhip_event_bank_clock.argtypes = [vp, ci, C.POINTER(C.c_int64)]
+    lib.bnhip_event_bank_destroy.argtypes = [vp]
+    lib.bnhip_event_bank_destroy.restype = None
+    lib.bnhip_windows_predict_events.argtypes = [vp, vp, vp, ci, ci, C.c_double, ci, C.POINTER(ci), C.POINTER(ci), vp, vp, C.POINTER(vp)] + answer
+    return lib
+
+
+EVENT_PENDING = -1
+
+
+class EventBank:
+    """`bnhip_event_bank` (include/bnhip.h, "Detection events: the real-time bank"): the detection-event rule in streaming form.
+    The bank keeps every source's pending detections on the device across calls; `process(sources, conf, idx)` feeds it top-k rows
+    (row r is the next window of sources[r]; a source < 0 skips the row) and returns the events (EVENT) that became due, ascending by
+    (source, class_index, first_window).  `flush(source=-1)` answers the live events as if the streams had ended, `reset(source=-1)`
+    drops them and zeroes the clock, `pending()` lists them with status EVENT_PENDING.  filter: an EventTables; k and its
+    hold_windows are fixed for the bank's life.  A call that fails changes no source.  cap: None = whatever the call answers (a
+    call refused for room is repeated with the room it named); a number = that room, and HipError with `.needed` beyond it."""
+
+    ROOM = 256
+
+    def __init__(self, n_classes, k, filter, max_sources=256, device=0):
+        lib = self._lib = _event_bank_protos(load_library())
+        self._h = None
+        self.n_classes, self.k, self.max_sources, self.device = int(n_classes), int(k), int(max_sources), int(device)
+        fs = filter._struct(self.n_classes)
+        h = C.c_void_p()
+        _check(lib, lib.bnhip_event_bank_create(self.device, self.max_sources, self.n_classes, self.k, C.addressof(fs), C.byref(h)))
+        self._h = h
+        v = [C.c_int() for _ in range(5)]
+        _check(lib, lib.bnhip_event_bank_info(h, *[C.byref(x) for x in v]))
+        self.hold_windows, self.slots_per_source = v[3].value, v[4].value
+
+    def _alive(self):
+        if self._h is None:
+            raise HipError(E_INVALID, "event bank is closed")
+        return self._h
+
+    def _answer(self, call, cap):
+        """call(out pointer, room, byref n) -> rc, with the room handled as the class docstring says."""
+        room = self.ROOM if cap is None else int(cap)
+        while True:
+            out, n = np.zeros(room, EVENT), C.c_size_t(0)
+            rc = call(out.ctypes.data if room else None, room, C.byref(n))
+            if rc == E_INVALID and n.value > room:
+                if cap is None:
+                    room = n.value
+                    continue
+                msg = (self._lib.bnhip_last_error() or b"").decode("utf-8", "replace")
+                e = HipError(rc, msg)
+                e.needed = n.value
+                raise e
+            _check(self._lib, rc)
+            return out[:n.value]
+
+    @staticmethod
+    def _rows(sources, conf, idx, k):
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        conf = np.ascontiguousarray(conf, np.float32).reshape(-1)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        if conf.size != src.size * k or idx.size != src.size * k:
+            raise HipError(E_INVALID, f"the event bank's rows hold k = {k} results")
+        return src, conf, idx
+
+    def process(self, sources, conf, idx, cap=None):
+        src, conf, idx = self._rows(sources, conf, idx, self.k)
+        h, L = self._alive(), self._lib
+        P = lambda a: a.ctypes.data if a.size else None
+        return self._answer(lambda o, room, n: L.bnhip_event_bank_process(h, P(src), src.size, P(conf), P(idx), o, room, n), cap)
+
+    def flush(self, source=-1, cap=None):
+        h, L = self._alive(), self._lib
+        return self._answer(lambda o, room, n: L.bnhip_event_bank_flush(h, int(source), o, room, n), cap)
+
+    def pending(self, cap=None):
+        h, L = self._alive(), self._lib
+        return self._answer(lambda o, room, n: L.bnhip_event_bank_pending(h, o, room, n), cap)
+
+    def reset(self, source=-1):
+        _check(self._lib, self._lib.bnhip_event_bank_reset(self._alive(), int(source)))
+
+    def set_filter(self, filter):
+        fs = filter._struct(self.n_classes)
+        _check(self._lib, self._lib.bnhip_event_bank_set_filter(self._alive(), C.addressof(fs)))
+
+    def clock(self, source):
+        w = C.c_int64(0)
+        _check(self._lib, self._lib.bnhip_event_bank_clock(self._alive(), int(source), C.byref(w)))
+        return w.value
+
+    def close(self):
+        if self._h is not None:
+            self._lib.bnhip_event_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _analyze_clips_protos(lib):
@@ -662,6 +780,13 @@ class HipClassifier:
         _check(self._lib, self._lib.bnhip_predict_pcm_topk(self._h, x.ctypes.data, bit_depth, batch_size, activation, sensitivity, k,
                                                            conf.ctypes.data, idx.ctypes.data))
         return conf, idx
+
+    def predict_windows_events(self, win, bank, bit_depth=16, k=10, activation=0, sensitivity=1.0):
+        """One tick answered as rows and as detection events (bnhip_windows_predict_events): every ready window of the assembler
+        `win` (stream.NativeWindows) through the model, the top-k rows back as bnhip_windows_predict_topk writes them, and in the same
+        call fed to `bank` (an EventBank on this device; its source numbers are the assembler's).
+        -> (source indices, rows view, conf [n, kk], idx [n, kk], events)."""
+        return win.predict_events(self, bank, bit_depth, k, activation, sensitivity)
 
     def _room(self, cap, first, k):
         """Records a file-analysis call makes room for: every row (an event is made of at least one) unless cap says less."""
@@ -2150,6 +2275,12 @@ class BirdNET:
         -> (source indices, uint8 rows view, per-window top-10 lists); a source index of -1 marks a row to skip."""
         idxs, rows, conf, idx = win.predict_topk(self.classifier, bit_depth, self.TOP_K, 0, self.sensitivity)
         return idxs, rows, [[(self.labels[i], float(c)) for c, i in zip(cr, ir)] for cr, ir in zip(conf, idx)]
+
+    def predict_windows_events(self, win, bank, bit_depth=16):
+        """predict_windows with the tick's rows also fed to `bank` (an EventBank on the model's device) in the same call
+        (bnhip_windows_predict_events).  -> (source indices, rows view, per-window top-10 lists, the events that became due)."""
+        idxs, rows, conf, idx, events = self.classifier.predict_windows_events(win, bank, bit_depth, self.TOP_K, 0, self.sensitivity)
+        return idxs, rows, [[(self.labels[i], float(c)) for c, i in zip(cr, ir)] for cr, ir in zip(conf, idx)], events
 
     def predict_pcm_batch(self, raw, bit_depth, batch_size):
         """The windows' little-endian PCM bytes as captured (a1 runs in the kernel, process.go:479-497) -> per-window top-10."""

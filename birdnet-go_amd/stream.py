@@ -319,6 +319,36 @@ class NativeWindows:
                 raise
         return srcs, self._view(p)[:n.value], conf[:n.value].copy(), idx[:n.value].copy()
 
+    def predict_events(self, clf, bank, bit_depth=16, k=10, activation=0, sensitivity=1.0):
+        """predict_topk with the tick's rows also fed to `bank` (host.EventBank) behind the last chunk, in the same call
+        (bnhip_windows_predict_events).  -> (source indices, rows view, conf, idx, the events that became due).  A tick whose
+        events do not fit the room feeds the bank the returned rows instead: the refused call has changed no source."""
+        clf._alive()
+        lib = _host._event_bank_protos(self._lib)
+        kk = min(k, clf.num_species())
+        if getattr(self, "_tk", None) is None or self._tk[0].shape[1] != kk:
+            self._tk = (np.empty((self.max_batch, kk), np.float32), np.empty((self.max_batch, kk), np.int32))
+        conf, idx = self._tk
+        if getattr(self, "_ev", None) is None:
+            self._ev = np.zeros(4096, _host.EVENT)
+        n, p, ne = C.c_int(0), C.c_void_p(), C.c_size_t(0)
+        rc = lib.bnhip_windows_predict_events(self._alive(), clf._h, bank._alive(), bit_depth, activation, sensitivity, k, self._sources,
+                                              C.byref(n), conf.ctypes.data, idx.ctypes.data, C.byref(p), self._ev.ctypes.data, self._ev.size,
+                                              C.byref(ne))
+        srcs = list(self._sources[:n.value])
+        events = None
+        if rc == _host.E_INVALID and ne.value > self._ev.size:
+            events, rc = bank.process(srcs, conf[:n.value], idx[:n.value]), _host.BNHIP_OK
+        if rc != _host.BNHIP_OK:
+            try:
+                self._check(rc)
+            except Exception as e:
+                e.sources = srcs
+                raise
+        if events is None:
+            events = self._ev[:ne.value].copy()
+        return srcs, self._view(p)[:n.value], conf[:n.value].copy(), idx[:n.value].copy(), events
+
     def ready(self):
         n = C.c_int(0)
         self._check(self._lib.bnhip_windows_ready(self._alive(), C.byref(n)))
@@ -616,9 +646,11 @@ class WindowBatcher:
     resampler drain.  A failed call costs its own frames only (on_error), as the consumer logs the error and goes on."""
 
     BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
+    EVENT_SOURCES = 1024                     # native: sources of a model's event bank (assembler slots are reused)
 
     def __init__(self, orch: Orchestrator, queue: _results.ResultsQueue = None, overruns: OverrunTrackers = None,
-                 max_batch=256, pre_capture_s=0.0, bit_depth=16, clock=time.time, on_error=None, native=True):
+                 max_batch=256, pre_capture_s=0.0, bit_depth=16, clock=time.time, on_error=None, native=True, events=None,
+                 on_events=None):
         self.orch = orch
         self.queue = queue if queue is not None else _results.ResultsQueue()
         self.overruns = overruns if overruns is not None else OverrunTrackers()
@@ -640,6 +672,10 @@ class WindowBatcher:
         self.sl_streams = {}                 # source -> (source rate, stream of that rate's bank, name)
         self.sl_pending = {}                 # native: source rate -> [(source, stream, pcm bytes)] until the next tick
         self.sl_reports = []                 # finished reports until take_sound_levels()
+        self.events = events                 # native: a host.EventTables -> detection events beside the Results (None: none)
+        self.on_events = on_events
+        self.event_banks = {}                # native: model_id -> host.EventBank over that model's assembler sources
+        self.event_reports = []              # the ticks' events until take_events()
 
     def allocate(self, source, model_id, capacity=None, source_rate=None):
         """The buffer of (source, model_id).  source_rate: the rate the source captures at; None or the model's effective rate
@@ -679,10 +715,14 @@ class WindowBatcher:
                         if key is not None:
                             self._release_rate(k[0], key)
                     win.close()
+                    bank = self.event_banks.pop(model_id, None)
+                    if bank is not None:
+                        bank.close()
                 win = self.assemblers[model_id] = NativeWindows(overlap, read, self.max_batch)
             old = self.buffers.pop((source, model_id), None)
             if old is not None:
                 win.remove_source(old.index)
+                self._reset_events(model_id, old.index)
             ab = self.buffers[(source, model_id)] = _NativeSource(win, win.add_source(source, capacity), source)
         return ab
 
@@ -692,10 +732,35 @@ class WindowBatcher:
                 ab = self.buffers.pop(k)
                 if isinstance(ab, _NativeSource):
                     ab.win.remove_source(ab.index)
+                    self._reset_events(k[1], ab.index)
                 key = self.rates.pop(k, None)
                 if key is not None:
                     self._release_rate(source, key)
         self.overruns.remove_source(source)
+
+    def _reset_events(self, model_id, index):
+        """(under self.mu) an assembler slot is reused by the next source: its pending detections go with the source."""
+        bank = self.event_banks.get(model_id)
+        if bank is not None and index < bank.max_sources:
+            bank.reset(index)
+
+    def _event_bank(self, model_id, inst):
+        """(under the model's inference lock) the bank of the model's assembler, created at the first tick with `events`."""
+        bank = self.event_banks.get(model_id)
+        if bank is None:
+            n_classes = len(inst.labels)
+            bank = _host.EventBank(n_classes, min(getattr(inst, "TOP_K", 10), n_classes), self.events, self.EVENT_SOURCES)
+            with self.mu:
+                self.event_banks[model_id] = bank
+        return bank
+
+    def take_events(self):
+        """-> the detection events since the last call, oldest first: {"timestamp" (the batcher's clock at the tick), "source",
+        "model_id", "class_index", "label", "first_window", "last_window", "best_window", "count", "confidence", "status"}; windows
+        count the source's windows since it was allocated."""
+        with self.mu:
+            out, self.event_reports = self.event_reports, []
+        return out
 
     # (under self.mu) one resampler stream per (source, rate pair) while a buffer of the source uses the pair
     def _acquire_rate(self, source, key):
@@ -950,9 +1015,26 @@ class WindowBatcher:
         def name(win, i):
             return None if i < 0 else names.get((id(win), i), f"source#{i}")
 
-        def one_tick(inst, win):
+        tick_events = []
+
+        def one_tick(inst, win, model_id=None):
             # an instance that can run the whole tick in the library does (rows assembled under the device's work on the
             # previous chunk); anything else gets the collected rows
+            if self.events is not None and hasattr(inst, "predict_windows"):
+                bank = self._event_bank(model_id, inst)
+                if hasattr(inst, "predict_windows_events"):       # rows and events in one call
+                    idxs, rows, lists, ev = inst.predict_windows_events(win, bank, self.bit_depth)
+                else:                                             # the bank is fed the rows the tick returned
+                    idxs, rows, lists = inst.predict_windows(win, self.bit_depth)
+                    number = {label: i for i, label in enumerate(inst.labels)}
+                    conf = np.full((len(idxs), bank.k), np.nan, np.float32)
+                    idx = np.full((len(idxs), bank.k), -1, np.int32)
+                    for r, lst in enumerate(lists):
+                        for j, (label, c) in enumerate(lst[:bank.k]):
+                            conf[r, j], idx[r, j] = c, number[label]
+                    ev = bank.process(idxs, conf, idx)
+                tick_events.append((inst, ev))
+                return idxs, rows, lists
             if hasattr(inst, "predict_windows"):
                 return inst.predict_windows(win, self.bit_depth)
             idxs, rows = win.collect(self.max_batch)
@@ -976,7 +1058,7 @@ class WindowBatcher:
                 start = now - (self.pre_capture_s + spec.clip_length_s)
                 t0 = time.perf_counter()
                 try:
-                    idxs, rows, lists = self.orch.predict_model(model_id, lambda inst: one_tick(inst, win))
+                    idxs, rows, lists = self.orch.predict_model(model_id, lambda inst: one_tick(inst, win, model_id))
                 except Exception as e:
                     lost = [name(win, i) for i in getattr(e, "sources", [])]
                     self.errors += max(1, len(lost))
@@ -985,6 +1067,17 @@ class WindowBatcher:
                     break
                 if not idxs:
                     break
+                for inst, ev in tick_events:
+                    reports = [{"timestamp": now, "source": name(win, int(e["recording"])), "model_id": model_id, "class_index": int(e["class_index"]),
+                                "label": inst.labels[int(e["class_index"])], "first_window": int(e["first_window"]),
+                                "last_window": int(e["last_window"]), "best_window": int(e["best_window"]), "count": int(e["count"]),
+                                "confidence": float(e["confidence"]), "status": int(e["status"])} for e in ev]
+                    if reports:
+                        with self.mu:
+                            self.event_reports.extend(reports)
+                        if self.on_events:
+                            self.on_events(model_id, reports)
+                del tick_events[:]
                 sources = [name(win, i) for i in idxs]
                 sent += _emit_results(self.orch, rows, lists, time.perf_counter() - t0, [start] * len(idxs), [now] * len(idxs), sources,
                                       model_id, self.queue, self.overruns)
@@ -1013,6 +1106,9 @@ class WindowBatcher:
             for bank in self.sl_banks.values():
                 bank.close()
             self.sl_banks.clear()
+            for bank in self.event_banks.values():
+                bank.close()
+            self.event_banks.clear()
             self.sl_streams.clear()
             self.sl_pending.clear()
 

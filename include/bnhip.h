@@ -389,6 +389,69 @@ int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_row
                            bnhip_event* out, size_t cap, size_t* n_out);
 int bnhip_event_min_count(int level, double overlap_seconds);
 
+/* Detection events: the real-time bank.  The same rule in streaming form, for the reference's product path (processDetections and
+ * flushPendingDetections, processor.go:671-804, 1485-1516, 1741-1795): a bank keeps every source's pending detections on the device
+ * across calls and is fed the top-k rows of each tick; a call answers the detections that became due in it.  The filter struct, the
+ * event struct, hits, veto hits, counts, ties and the statuses are those above.
+ *   sources  A bank holds max_sources sources, 0..max_sources-1.  A source's clock is the number of windows the bank has been given
+ *            for it since creation or reset; the j-th row of source s in a call, in row order, is window clock[s] + j.  That number is
+ *            `window` of the rule above, and the source number is `recording`.
+ *   rows     k results (conf, idx) as the top-k entries write them; idx < 0 is no result, and a row of k such entries only advances
+ *            the clock (a window that was consumed but not analysed).
+ *   events   The first hit of (s, c) with no live event opens one at b = w; a hit with w < b + hold_windows joins it.  After window w
+ *            of a source is applied, every live event of it with b + hold_windows <= w + 1 is due: answered in that call, its slot
+ *            freed - before window w + 1 is applied, so a hit at exactly b + hold_windows opens the next event.
+ *   status   1 when count < min_count; else 2 when the source's largest veto-hit window so far is >= b (an event is flushed right
+ *            after window b + hold_windows - 1, so this is b <= v < b + hold_windows of the rule above); else 0.
+ *            BNHIP_EVENTS_KEEP_DROPPED as above.
+ *   slots    A source has at most one live event per class and opens at most k per window, and an event opened at b is gone after
+ *            window b + hold_windows - 1: while window w is applied the live events began in [w - hold_windows + 1, w].  So
+ *            slots_per_source = min(k * hold_windows, n_classes) is exact.
+ *   order    A call's answer ascends by (source, class_index, first_window): unique within a call, so the same calls give the same
+ *            bytes on every run.
+ *   bnhip_event_bank_create  Copies the filter's tables; hold_windows and k are fixed for the bank's life.
+ *   bnhip_event_bank_set_filter  New thresholds, veto table, veto threshold, min_count and flags from the next call on (settings
+ *            reloads, the host's own dynamic thresholds); a different hold_windows is refused.
+ *   bnhip_event_bank_process  Rows from host memory.  sources[r] < 0 skips row r; a source may appear several times or not at all.
+ *   bnhip_event_bank_process_device  The same with the rows already on the bank's device: enqueued on `stream`, synchronised before
+ *            it returns.  A class index outside the table is no result here; the host form refuses it in its one checking pass.
+ *   bnhip_event_bank_flush  Answers every live event of `source` (-1: of all) as if the stream had ended, statuses by the same rule;
+ *            the clocks stay.  The rows of a recording fed and then flushed answer exactly bnhip_detection_events of those rows.
+ *   bnhip_event_bank_reset  Drops the live events of `source` (-1: of all) unanswered, clock 0, veto memory cleared.
+ *   bnhip_event_bank_pending  The live events of all sources with status BNHIP_EVENT_PENDING and the fields as they stand, ascending
+ *            by (source, class_index); changes nothing (SnapshotVisiblePending, the "currently hearing" list).
+ *   bnhip_windows_predict_events  bnhip_windows_predict_topk - the same tick, out_conf / out_idx filled exactly as there - with the
+ *            rows also kept on the device and bnhip_event_bank_process_device run behind the last chunk on the model's stream; the
+ *            bank's source numbers are the assembler's.  *n_windows == 0 runs nothing and answers no events.  An error before the
+ *            bank stage leaves the bank unchanged.  The bank's k is the tick's row width min(k, n_classes); single-device handles.
+ *   calls    Every bank call is one transaction: a header copy, the launches, one copy back, and a commit once everything succeeded
+ *            (each source's state is a pair of slabs; a launch reads one and writes the other).  A call that fails changes no source.
+ *            More events than cap is such a failure: BNHIP_E_INVALID with *n_out = the number needed, nothing written; the same call
+ *            with room then succeeds.
+ * BNHIP_E_INVALID (before any device call, the handle stays usable): NULL where a pointer is required, max_sources outside 1..65535,
+ * n_classes outside 1..38400, k < 1, hold_windows < 1, min_count < 1, k * hold_windows > 4096, unknown flag bits, a source number
+ * >= max_sources, n_rows < 0 or n_rows * k of 2^31 or more, a clock that the call would take past 2^31 - 1 (reset the source), a tick
+ * whose row width differs from the bank's k, model and bank on different devices, the host form's class index >= n_classes.  In
+ * the tick a source number >= max_sources can only be seen once the windows are taken: out_conf / out_idx are filled, the bank is
+ * unchanged.  Allocation failure: BNHIP_E_NOMEM. */
+#define BNHIP_EVENT_PENDING (-1)
+typedef struct bnhip_event_bank bnhip_event_bank;
+int bnhip_event_bank_create(int device, int max_sources, int n_classes, int k, const bnhip_event_filter* filter, bnhip_event_bank** out);
+int bnhip_event_bank_info(const bnhip_event_bank* b, int* max_sources, int* n_classes, int* k, int* hold_windows, int* slots_per_source);
+int bnhip_event_bank_set_filter(bnhip_event_bank* b, const bnhip_event_filter* filter);
+int bnhip_event_bank_process(bnhip_event_bank* b, const int32_t* sources, int n_rows, const float* conf, const int32_t* idx,
+                             bnhip_event* out, size_t cap, size_t* n_out);
+int bnhip_event_bank_process_device(bnhip_event_bank* b, const int32_t* sources, int n_rows, const float* d_conf, const int32_t* d_idx,
+                                    bnhip_event* out, size_t cap, size_t* n_out, void* stream);
+int bnhip_event_bank_flush(bnhip_event_bank* b, int source, bnhip_event* out, size_t cap, size_t* n_out);
+int bnhip_event_bank_reset(bnhip_event_bank* b, int source);
+int bnhip_event_bank_pending(bnhip_event_bank* b, bnhip_event* out, size_t cap, size_t* n_out);
+int bnhip_event_bank_clock(bnhip_event_bank* b, int source, int64_t* windows);
+void bnhip_event_bank_destroy(bnhip_event_bank* b);
+int bnhip_windows_predict_events(bnhip_windows* w, bnhip_model* m, bnhip_event_bank* bank, int bits_per_sample, int activation,
+                                 double sensitivity, int k, int* sources, int* n_windows, float* out_conf, int32_t* out_idx,
+                                 const void** batch, bnhip_event* events, size_t cap, size_t* n_events);
+
 /* Detection clips: what the reference saves for every approved detection, made from the recordings of a file-analysis call while
  * they are still on the device.  Its processor takes the audio from BeginTime back by the pre-capture to the end of the capture
  * window, or under extended capture to as long as the bird kept calling (internal/analysis/processor/extended_capture.go:232-280,
