@@ -16,7 +16,7 @@ using namespace bnhip;
 
 static_assert(sizeof(bnhip_clip_span) == 16, "a clip span is 16 bytes");
 
-namespace {
+namespace bnhip {
 
 int span_rule_check(const bnhip_clip_export* x) {
     if (x->pre_samples < 0) return set_err(BNHIP_E_INVALID, "pre_samples must not be negative");
@@ -24,6 +24,10 @@ int span_rule_check(const bnhip_clip_export* x) {
     if (x->max_samples < 1) return set_err(BNHIP_E_INVALID, "max_samples must be at least 1");
     return 0;
 }
+
+}  // namespace bnhip
+
+namespace {
 
 // the rule of bnhip.h "Detection clips" for one event of a recording of N samples at the model's rate
 bnhip_clip_span event_span(const bnhip_event& e, long long N, int hop, const bnhip_clip_export* x) {
@@ -43,13 +47,12 @@ int event_spans(const bnhip_event* events, size_t n_events, const int64_t* n_out
     return BNHIP_OK;
 }
 
-// The clips of an export as a ClipSource (clip_source.h): cut out of the slot block, normalised into d_pcm (or cut straight into it),
+// The clips of an export as a ClipSource (clip_source.h): cut by the call's Cutter, normalised into d_pcm (or cut straight into it),
 // and encoded from there; the records and the FLAC streams come down in finish().
 struct ExportSource : ClipSource {
     const char* what;
-    int device, bits, rate;
-    const void* d_block;
-    const long long* d_slot;
+    int device, rate;
+    const Cutter& cut;
     const CutPlan& plan;
     Clips clips;
     const bnhip_clip_export* x;
@@ -58,12 +61,11 @@ struct ExportSource : ClipSource {
     size_t o_tab = 0, o_cut = 0, o_res = 0, o_lws = 0, o_bytes = 0, o_off = 0, o_fws = 0;
     int rc = 0;                              // the normalise's own refusal, with its text: what the entry answers instead of a HIP error
     std::string err;
-    ExportSource(const char* w, int dev, const void* block, int b, const long long* slot, const CutPlan& p, int r, const bnhip_clip_export* xx,
-                 bnhip_clips_out* oo)
-        : what(w), device(dev), bits(b), rate(r), d_block(block), d_slot(slot), plan(p), clips(Clips::ragged(p.n_clips(), p.lens.data())), x(xx),
+    ExportSource(const char* w, int dev, const Cutter& ct, const CutPlan& p, int r, const bnhip_clip_export* xx, bnhip_clips_out* oo)
+        : what(w), device(dev), rate(r), cut(ct), plan(p), clips(Clips::ragged(p.n_clips(), p.lens.data())), x(xx),
           o(oo), cap(flac_max_bytes(clips, xx->seek_interval)), res_bytes((size_t)p.n_clips() * sizeof(bnhip_loudness)) {}
     void reserve(DevCarve& cv) override {
-        o_tab = cv.add(plan.table_bytes());
+        o_tab = cv.add(cut.table_bytes(plan));
         if (x->normalize) {
             o_cut = cv.add((size_t)plan.total() * 2);
             o_res = cv.add(res_bytes);
@@ -75,7 +77,7 @@ struct ExportSource : ClipSource {
     }
     hipError_t fill(const DevCarve& cv, int16_t* d_pcm, size_t) override {
         int16_t* d_cut = x->normalize ? cv.at<int16_t>(o_cut) : d_pcm;
-        const hipError_t he = cut_enqueue(plan, d_block, bits, d_slot, cv.at<void>(o_tab), d_cut, nullptr);
+        const hipError_t he = cut.enqueue(plan, cv.at<void>(o_tab), d_cut);
         if (he != hipSuccess) return he;
         if (x->normalize) {
             rc = loudness_enqueue(what, device, d_cut, clips, rate, x->target_lufs, x->true_peak_dbtp, x->max_gain_db, x->gate_fallback,
@@ -134,16 +136,12 @@ int clip_export_check(const bnhip_clip_export* x, const bnhip_clips_out* o, int 
     return BNHIP_OK;
 }
 
-int clip_export_run(int device, const void* d_block, int bits, const long long* d_slot, const int64_t* n_out, int n_recordings, int hop,
-                    int model_rate, const bnhip_clip_export* x, bnhip_clips_out* o) {
-    const char* what = "analyze_channels_pcm_clips";
-    const size_t n_written = std::min(o->event_cap, o->n_events);
+int clip_export_spans(const char* what, int device, const Cutter& cut, size_t n_spans, int rate, const bnhip_clip_export* x, bnhip_clips_out* o) {
     o->n_clips = 0;
-    if (int rc = event_spans(o->events, n_written, n_out, n_recordings, hop, x, o->spans)) return rc;
-    // the capacity rule: clips in event order for as long as their streams' bounds fit what the caller has room for
+    // the capacity rule: clips in span order for as long as their streams' bounds fit what the caller has room for
     int n = 0;
     size_t flac_need = 0;
-    for (size_t i = 0; i < n_written && n < 65535; i++) {
+    for (size_t i = 0; i < n_spans && n < 65535; i++) {
         if (o->spans[i].length < 1) continue;
         flac_need += flac_max_bytes(1, o->spans[i].length, x->seek_interval);
         if (flac_need > o->flac_cap) break;
@@ -151,15 +149,23 @@ int clip_export_run(int device, const void* d_block, int bits, const long long* 
         n++;
     }
     if (n == 0) return BNHIP_OK;
-    const CutPlan plan = cut_plan(o->spans, n_written, n);
-    ExportSource src(what, device, d_block, bits, d_slot, plan, model_rate, x, o);
+    const CutPlan plan = cut_plan(o->spans, n_spans, n);
+    ExportSource src(what, device, cut, plan, rate, x, o);
     if (int rc = clips_check(src.clips)) return rc;
-    const int rc = x->width > 0 ? spectrogram_png_run(what, device, src, src.clips, model_rate, x->rate_out, x->width, x->height, x->window, x->top_db,
+    const int rc = x->width > 0 ? spectrogram_png_run(what, device, src, src.clips, rate, x->rate_out, x->width, x->height, x->window, x->top_db,
                                                       x->range_db, x->palette, o->png, o->png_cap, o->png_offsets)
                                 : audio_run(what, device, src);
     if (src.rc) return set_err(src.rc, src.err);
     if (rc == BNHIP_OK) o->n_clips = (size_t)n;
     return rc;
+}
+
+int clip_export_run(int device, const void* d_block, int bits, const long long* d_slot, const int64_t* n_out, int n_recordings, int hop,
+                    int model_rate, const bnhip_clip_export* x, bnhip_clips_out* o) {
+    const size_t n_written = std::min(o->event_cap, o->n_events);
+    o->n_clips = 0;
+    if (int rc = event_spans(o->events, n_written, n_out, n_recordings, hop, x, o->spans)) return rc;
+    return clip_export_spans("analyze_channels_pcm_clips", device, SlotCutter(d_block, bits, d_slot), n_written, model_rate, x, o);
 }
 
 }  // namespace bnhip

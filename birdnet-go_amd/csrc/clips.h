@@ -40,12 +40,32 @@ CutPlan cut_plan(const bnhip_clip_span* spans, size_t n_spans, int limit);
 // the plan's tables go to d_tables (table_bytes(), 8-byte aligned) and the cut is enqueued behind them on s
 hipError_t cut_enqueue(const CutPlan& p, const void* d_block, int bits, const long long* d_slot, void* d_tables, int16_t* d_out, hipStream_t s);
 
+// Where an export's clips are cut from: the slot block of a file-analysis call, or the rings of a capture bank (capture_bank.h).
+// enqueue() puts the plan's tables at d_tables (table_bytes(), 8-byte aligned) and the cut into d_out behind them, on the null stream.
+struct Cutter {
+    virtual size_t table_bytes(const CutPlan& p) const = 0;
+    virtual hipError_t enqueue(const CutPlan& p, void* d_tables, int16_t* d_out) const = 0;
+    virtual ~Cutter() {}
+};
+struct SlotCutter : Cutter {
+    const void* d_block;
+    int bits;
+    const long long* d_slot;
+    SlotCutter(const void* block, int b, const long long* slot) : d_block(block), bits(b), d_slot(slot) {}
+    size_t table_bytes(const CutPlan& p) const override { return p.table_bytes(); }
+    hipError_t enqueue(const CutPlan& p, void* d_tables, int16_t* d_out) const override { return cut_enqueue(p, d_block, bits, d_slot, d_tables, d_out, nullptr); }
+};
+
+// what the span rule refuses of its settings (pre_samples, post_samples, max_samples); -> 0 or BNHIP_E_INVALID
+int span_rule_check(const bnhip_clip_export* x);
 // What bnhip_analyze_channels_pcm_clips checks of its export settings before any device is touched; -> 0 or a negative BNHIP_E_*
 int clip_export_check(const bnhip_clip_export* x, const bnhip_clips_out* o, int model_rate);
-// The second phase of that call, behind the events: the spans of the events written, the capacity rule, and - for n_clips > 0 - one
-// DevCarve, the cut, the normalise, the FLAC encode, the render and the PNG encode on the null stream, and the copies that bring the
-// records and the streams down.  d_block / d_slot: the call's slot block and slot table, still on the device; n_out: the
-// recordings' lengths at the model's rate.
+// The export behind the spans, whatever they are cut from: o->spans[0 .. n_spans) are known and checked; the capacity rule, and - for
+// n_clips > 0 - one DevCarve, the cut, the normalise, the FLAC encode, the render and the PNG encode on the null stream, and the
+// copies that bring the records and the streams down.
+int clip_export_spans(const char* what, int device, const Cutter& cut, size_t n_spans, int rate, const bnhip_clip_export* x, bnhip_clips_out* o);
+// The second phase of that call, behind the events: the spans of the events written, then clip_export_spans over the slot block.
+// d_block / d_slot: the call's slot block and slot table, still on the device; n_out: the recordings' lengths at the model's rate.
 int clip_export_run(int device, const void* d_block, int bits, const long long* d_slot, const int64_t* n_out, int n_recordings, int hop,
                     int model_rate, const bnhip_clip_export* x, bnhip_clips_out* o);
 

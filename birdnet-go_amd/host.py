@@ -66,7 +66,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_event_clip_spans", "bnhip_recording_clips_pcm16", "bnhip_analyze_channels_pcm_clips", "bnhip_event_bank_create",
            "bnhip_event_bank_info", "bnhip_event_bank_set_filter", "bnhip_event_bank_process", "bnhip_event_bank_process_device",
            "bnhip_event_bank_flush", "bnhip_event_bank_reset", "bnhip_event_bank_pending", "bnhip_event_bank_clock",
-           "bnhip_event_bank_destroy", "bnhip_windows_predict_events"]
+           "bnhip_event_bank_destroy", "bnhip_windows_predict_events", "bnhip_capture_bank_create", "bnhip_capture_bank_info",
+           "bnhip_capture_bank_positions", "bnhip_capture_bank_reset", "bnhip_capture_bank_write", "bnhip_capture_bank_read_pcm16",
+           "bnhip_capture_bank_clips", "bnhip_capture_bank_destroy", "bnhip_capture_spans"]
 
 
 class HipError(RuntimeError):
@@ -486,6 +488,150 @@ class ClipsResult:
     def __init__(self, events, n_events, spans, loudness, flac, png, chosen):
         self.events, self.n_events, self.spans, self.loudness, self.flac, self.png, self.chosen = events, n_events, spans, loudness, flac, png, chosen
         self.n_clips = len(flac)
+
+
+def _capture_bank_protos(lib):
+    """... and of the capture bank (apart again, for the same reason)."""
+    _analyze_clips_protos(lib)
+    vp, ci, i64 = C.c_void_p, C.c_int, C.c_int64
+    lib.bnhip_capture_bank_create.argtypes = [ci, ci, i64, ci, C.POINTER(vp)]
+    lib.bnhip_capture_bank_info.argtypes = [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(ci)]
+    lib.bnhip_capture_bank_positions.argtypes = [vp, vp, vp]
+    lib.bnhip_capture_bank_reset.argtypes = [vp, ci]
+    lib.bnhip_capture_bank_write.argtypes = [vp, ci, vp, vp, vp, ci]
+    lib.bnhip_capture_bank_read_pcm16.argtypes = [vp, vp, ci, vp]
+    lib.bnhip_capture_bank_clips.argtypes = [vp, vp, ci, vp, vp]
+    lib.bnhip_capture_bank_destroy.argtypes = [vp]
+    lib.bnhip_capture_bank_destroy.restype = None
+    lib.bnhip_capture_spans.argtypes = [vp, C.c_size_t, ci, vp, vp, vp, ci, vp, vp, vp]
+    return lib
+
+
+CAPTURE_OK, CAPTURE_CLAMPED, CAPTURE_NOT_YET, CAPTURE_GONE, CAPTURE_DROPPED = 0, 1, 2, 3, 4
+
+
+def capture_spans(events, written, oldest, hop, settings, origins=None):
+    """bnhip_capture_spans (host only): the clip of every event (EVENT; `recording` is the source) on the sources' running clocks -
+    written / oldest as CaptureBank.positions answers them, origins[s] the position of window 0's first sample (None: 0), hop in
+    capture samples -> (CLIP_SPAN [n_events], status int32 [n_events]: CAPTURE_OK, _CLAMPED, _NOT_YET, _GONE or _DROPPED; only the
+    first two have a length)."""
+    lib = _capture_bank_protos(load_library())
+    ev = np.ascontiguousarray(events, EVENT).reshape(-1)
+    wr, old = np.ascontiguousarray(written, np.int64).reshape(-1), np.ascontiguousarray(oldest, np.int64).reshape(-1)
+    org = None if origins is None else np.ascontiguousarray(origins, np.int64).reshape(-1)
+    if old.size != wr.size or (org is not None and org.size != wr.size):
+        raise HipError(E_INVALID, "written, oldest and origins hold one entry per source")
+    spans, status = np.zeros(ev.size, CLIP_SPAN), np.zeros(ev.size, np.int32)
+    xs = settings._struct()
+    P = lambda a: a.ctypes.data if ev.size else None
+    _check(lib, lib.bnhip_capture_spans(P(ev), ev.size, wr.size, wr.ctypes.data, old.ctypes.data, None if org is None else org.ctypes.data,
+                                        int(hop), C.addressof(xs), P(spans), P(status)))
+    return spans, status
+
+
+class CaptureBank:
+    """`bnhip_capture_bank` (include/bnhip.h, "Capture bank"): per-source rings of mono int16 on the device - max_sources * capacity * 2
+    bytes - written once per tick and cut into detection clips where they lie.  seconds: the least each ring holds (rounded up to
+    1024 samples; `capacity` is the result).  Positions are samples on each source's own clock: `written` counts everything given
+    since creation or reset, and [oldest, written) is readable."""
+
+    def __init__(self, max_sources, seconds, rate=48000, device=0, capacity_samples=None):
+        lib = self._lib = _capture_bank_protos(load_library())
+        self._h = None
+        self.max_sources, self.rate, self.device = int(max_sources), int(rate), int(device)
+        want = int(capacity_samples) if capacity_samples is not None else int(math.ceil(seconds * self.rate))
+        h = C.c_void_p()
+        _check(lib, lib.bnhip_capture_bank_create(self.device, self.max_sources, want, self.rate, C.byref(h)))
+        self._h = h
+        cap = C.c_int64()
+        _check(lib, lib.bnhip_capture_bank_info(h, None, C.byref(cap), None))
+        self.capacity = cap.value
+
+    def _alive(self):
+        if self._h is None:
+            raise HipError(E_INVALID, "capture bank is closed")
+        return self._h
+
+    def write(self, frames, bit_depth=16):
+        """frames: [(source, PCM bytes or array), ...] - one call per tick for every source; a source may appear several times, its
+        frames are appended in call order.  bit_depth 16, 24 or 32: what the bytes hold; the rings keep int16."""
+        size = bit_depth // 8 if bit_depth in (16, 24, 32) else 1
+        keep = [np.ascontiguousarray(f).reshape(-1).view(np.uint8) if isinstance(f, np.ndarray) else np.frombuffer(f, np.uint8) for _, f in frames]
+        for a in keep:
+            if a.size % size:
+                raise HipError(E_INVALID, f"frame of {a.size} bytes is not whole {bit_depth}-bit samples")
+        src = np.array([s for s, _ in frames], np.int32)
+        n = np.array([a.size // size for a in keep], np.int64)
+        ptr = (C.c_void_p * max(len(keep), 1))(*[a.ctypes.data if a.size else None for a in keep])
+        _check(self._lib, self._lib.bnhip_capture_bank_write(self._alive(), len(keep), src.ctypes.data, n.ctypes.data, ptr, int(bit_depth)))
+
+    def positions(self):
+        """-> (written int64 [max_sources], oldest int64 [max_sources])."""
+        wr, old = np.zeros(self.max_sources, np.int64), np.zeros(self.max_sources, np.int64)
+        _check(self._lib, self._lib.bnhip_capture_bank_positions(self._alive(), wr.ctypes.data, old.ctypes.data))
+        return wr, old
+
+    def spans(self, events, hop, settings, origins=None):
+        """capture_spans over the bank's positions as they stand."""
+        wr, old = self.positions()
+        return capture_spans(events, wr, old, hop, settings, origins)
+
+    def read(self, spans):
+        """bnhip_capture_bank_read_pcm16: spans (CLIP_SPAN: `recording` the source, `start` a position) -> the list of int16 clips of
+        the spans of non-zero length, in span order."""
+        spans = np.ascontiguousarray(spans, CLIP_SPAN).reshape(-1)
+        lens = spans["length"][spans["length"] > 0].astype(np.int64)
+        out = np.zeros(max(int(lens.sum()), 1), np.int16)
+        _check(self._lib, self._lib.bnhip_capture_bank_read_pcm16(self._alive(), spans.ctypes.data, spans.size, out.ctypes.data))
+        ends = np.cumsum(lens)
+        return [out[int(e - n):int(e)].copy() for e, n in zip(ends, lens)]
+
+    def export_raw(self, spans, settings, flac_cap=None, png_cap=None):
+        """bnhip_capture_bank_clips -> a ClipsResult without events: the spans as given, and per clip - the j-th span of non-zero
+        length - loudness[j], flac[j], png[j].  Room defaults to the bounds of every span."""
+        spans = np.ascontiguousarray(spans, CLIP_SPAN).reshape(-1).copy()
+        room = spans.size
+        lens = [int(n) for n in spans["length"] if n > 0]
+        if flac_cap is None:
+            flac_cap = flac_ragged_max_bytes(lens, settings.seek_interval) if lens else 0
+        if png_cap is None:
+            png_cap = png_max_bytes(len(lens), settings.width, settings.height) if lens and settings.width > 0 else 0
+        given = np.zeros(max(room, 1), CLIP_SPAN)
+        loud = (Loudness * max(room, 1))()
+        flac, png = np.empty(max(int(flac_cap), 1), np.uint8), np.empty(max(int(png_cap), 1), np.uint8)
+        flac_off, png_off = np.full(room + 1, 2 ** 64 - 1, np.uint64), np.full(room + 1, 2 ** 64 - 1, np.uint64)
+        xs = settings._struct()
+        o = _ClipsOutStruct(None, 0, 0, given.ctypes.data, C.addressof(loud), flac.ctypes.data, int(flac_cap), flac_off.ctypes.data, png.ctypes.data,
+                            int(png_cap), png_off.ctypes.data, 0)
+        _check(self._lib, self._lib.bnhip_capture_bank_clips(self._alive(), spans.ctypes.data, spans.size, C.addressof(xs), C.addressof(o)))
+        n = int(o.n_clips)
+        res = ClipsResult(np.zeros(0, EVENT), 0, given[:room], list(loud[:n]) if settings.normalize else None,
+                          _flac_streams(flac, flac_off[:n + 1]) if n else [],
+                          (_flac_streams(png, png_off[:n + 1]) if n else []) if settings.width > 0 else None, None)
+        res.flac_offsets, res.png_offsets = flac_off, png_off
+        return res
+
+    def export(self, spans, settings, flac_cap=None, png_cap=None):
+        """The clips of the spans of non-zero length, cut, normalised, encoded and rendered on the device in one call -> one dict per
+        clip made: {"flac": bytes, "png": bytes or None, "loudness": Loudness or None, "span": the CLIP_SPAN record}."""
+        res = self.export_raw(spans, settings, flac_cap, png_cap)
+        made = [q for q in res.spans if q["length"] > 0][:res.n_clips]
+        return [{"flac": res.flac[j], "png": res.png[j] if res.png is not None else None,
+                 "loudness": res.loudness[j] if res.loudness is not None else None, "span": q} for j, q in enumerate(made)]
+
+    def reset(self, source=-1):
+        _check(self._lib, self._lib.bnhip_capture_bank_reset(self._alive(), int(source)))
+
+    def close(self):
+        if self._h is not None:
+            self._lib.bnhip_capture_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _windows(protos, entry, table, args, resampled=True):

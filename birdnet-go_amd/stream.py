@@ -378,8 +378,8 @@ class NativeWindows:
 class _NativeSource:
     """One source of a NativeWindows with the AnalysisBuffer's surface (write / ready / overwrite_count / reset)."""
 
-    def __init__(self, win: NativeWindows, index, source_id):
-        self.win, self.index, self.source_id = win, index, source_id
+    def __init__(self, win: NativeWindows, index, source_id, model_id=None):
+        self.win, self.index, self.source_id, self.model_id = win, index, source_id, model_id
         self.read_size, self.overlap_size, self.window_size = win.read_size, win.overlap_size, win.window_bytes
 
     def write(self, data):
@@ -614,6 +614,16 @@ def process_data(orch, data, start_time, captured_at, source, model_id, queue, o
                            overruns, bit_depth)
 
 
+@dataclass(frozen=True)
+class CaptureSettings:
+    """WindowBatcher(capture=...): every source's last `seconds` of audio stay on the device (one host.CaptureBank per model, at
+    the model's rate, max_sources rings: max_sources * seconds * rate * 2 bytes) and every approved detection event is answered with
+    its clip, cut, normalised, FLAC-encoded and rendered there under `export` (a wav.ClipExport)."""
+    seconds: float
+    export: object
+    max_sources: int = 256
+
+
 class WindowBatcher:
     """All (source, model) monitors of buffer_manager.go:388-496 in one object.  `tick()` is one poll: every buffer with a
     window ready is read, windows of the same model form one batch (at most `max_batch` per device call), inactive models
@@ -643,14 +653,22 @@ class WindowBatcher:
     source rate and after set_processing's EQ and gain, is one ProcessSamples call, and `take_sound_levels()` returns the
     finished SoundLevelData-shaped reports.  One host.SoundLevelBank per source rate.  Python rings: one bank call per write.
     Native rings: the frames are queued and the next `tick()` runs one bank call per rate, after the EQ drain and before the
-    resampler drain.  A failed call costs its own frames only (on_error), as the consumer logs the error and goes on."""
+    resampler drain.  A failed call costs its own frames only (on_error), as the consumer logs the error and goes on.
+
+    `events=` (a host.EventTables) adds the detection events of every tick (take_events, on_events).  With `capture=` (a
+    CaptureSettings; native rings, with events) the bytes that reach a source's ring are also staged for the model's
+    host.CaptureBank: a tick uploads them in one write call before the model call, and the events that became due are answered
+    with their clips in one export call (take_clips, on_clips).  An event whose clip ends behind what has been written is kept and
+    tried again on later ticks, never cut short; one whose audio has left the ring is reported without a clip."""
 
     BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
     EVENT_SOURCES = 1024                     # native: sources of a model's event bank (assembler slots are reused)
 
     def __init__(self, orch: Orchestrator, queue: _results.ResultsQueue = None, overruns: OverrunTrackers = None,
                  max_batch=256, pre_capture_s=0.0, bit_depth=16, clock=time.time, on_error=None, native=True, events=None,
-                 on_events=None):
+                 on_events=None, capture=None, on_clips=None):
+        if capture is not None and (events is None or not native):
+            raise StreamError("capture needs events and the native rings")
         self.orch = orch
         self.queue = queue if queue is not None else _results.ResultsQueue()
         self.overruns = overruns if overruns is not None else OverrunTrackers()
@@ -676,6 +694,14 @@ class WindowBatcher:
         self.on_events = on_events
         self.event_banks = {}                # native: model_id -> host.EventBank over that model's assembler sources
         self.event_reports = []              # the ticks' events until take_events()
+        self.capture = capture               # native: a CaptureSettings -> the events' clips from per-source rings on the device
+        self.on_clips = on_clips
+        self.capture_banks = {}              # model_id -> host.CaptureBank over that model's assembler sources
+        self.capture_staged = {}             # model_id -> [(assembler source, bytes)] until the next tick
+        self.capture_fed = {}                # (model_id, assembler source) -> samples staged since the source was allocated
+        self.capture_base = {}               # ... of them, those before the bank source's last reset: position 0 of its clock
+        self.capture_waiting = {}            # model_id -> [(event, source name, label)] whose clips end behind what is written
+        self.clip_reports = []               # the ticks' clips until take_clips()
 
     def allocate(self, source, model_id, capacity=None, source_rate=None):
         """The buffer of (source, model_id).  source_rate: the rate the source captures at; None or the model's effective rate
@@ -715,15 +741,17 @@ class WindowBatcher:
                         if key is not None:
                             self._release_rate(k[0], key)
                     win.close()
-                    bank = self.event_banks.pop(model_id, None)
-                    if bank is not None:
-                        bank.close()
+                    for bank in (self.event_banks.pop(model_id, None), self.capture_banks.pop(model_id, None)):
+                        if bank is not None:
+                            bank.close()
+                    for k in [k for k in self.capture_fed if k[0] == model_id]:
+                        self._reset_capture(model_id, k[1], forget=True)
                 win = self.assemblers[model_id] = NativeWindows(overlap, read, self.max_batch)
             old = self.buffers.pop((source, model_id), None)
             if old is not None:
                 win.remove_source(old.index)
                 self._reset_events(model_id, old.index)
-            ab = self.buffers[(source, model_id)] = _NativeSource(win, win.add_source(source, capacity), source)
+            ab = self.buffers[(source, model_id)] = _NativeSource(win, win.add_source(source, capacity), source, model_id)
         return ab
 
     def remove(self, source, model_id=None):
@@ -743,6 +771,118 @@ class WindowBatcher:
         bank = self.event_banks.get(model_id)
         if bank is not None and index < bank.max_sources:
             bank.reset(index)
+        self._reset_capture(model_id, index, forget=True)
+
+    def _reset_capture(self, model_id, index, forget=False):
+        """(under self.mu) the capture ring of an assembler slot starts again; forget: so does the slot's stream."""
+        if self.capture is None:
+            return
+        bank = self.capture_banks.get(model_id)
+        if bank is not None and index < bank.max_sources:
+            bank.reset(index)
+        key = (model_id, index)
+        if forget:
+            self.capture_fed.pop(key, None)
+            self.capture_base.pop(key, None)
+            self.capture_staged[model_id] = [it for it in self.capture_staged.get(model_id, []) if it[0] != index]
+        else:
+            self.capture_base[key] = self.capture_fed.get(key, 0)
+        self.capture_waiting[model_id] = [it for it in self.capture_waiting.get(model_id, []) if int(it[0]["recording"]) != index]
+
+    def _ring_write(self, ab, data):
+        """One ring write; with capture the same bytes are staged for the model's capture bank."""
+        ab.write(data)
+        if self.capture is not None:
+            with self.mu:
+                self._stage_capture(ab, data)
+
+    def _stage_capture(self, ab, data):
+        """(under self.mu)"""
+        if self.capture is None or not isinstance(ab, _NativeSource):
+            return
+        raw = _as_bytes(data).tobytes()
+        self.capture_staged.setdefault(ab.model_id, []).append((ab.index, raw))
+        key = (ab.model_id, ab.index)
+        self.capture_fed[key] = self.capture_fed.get(key, 0) + len(raw) // (self.bit_depth // 8)
+
+    def _capture_upload(self, model_id, spec):
+        """The bytes staged since the last tick go up in one write call (the bank is made at the first)."""
+        with self.mu:
+            staged = self.capture_staged.pop(model_id, [])
+            bank = self.capture_banks.get(model_id)
+        staged = [it for it in staged if it[0] < self.capture.max_sources]
+        if not staged:
+            return
+        try:
+            if bank is None:
+                bank = _host.CaptureBank(self.capture.max_sources, self.capture.seconds, spec.effective_sample_rate())
+                with self.mu:
+                    self.capture_banks[model_id] = bank
+            bank.write(staged, self.bit_depth)
+        except Exception as e:                                    # the frames are lost to the rings: their sources' clocks start again
+            self.errors += len(staged)
+            with self.mu:
+                for index in {i for i, _ in staged}:
+                    self._reset_capture(model_id, index)
+            if self.on_error:
+                self.on_error(model_id, sorted({f"source#{i}" for i, _ in staged}), e)
+
+    def _capture_export(self, model_id, win, now):
+        """The waiting events against the rings as they stand: those whose clips are complete are exported in one call."""
+        with self.mu:
+            waiting = self.capture_waiting.pop(model_id, [])
+            bank = self.capture_banks.get(model_id)
+            base = dict(self.capture_base)
+        if not waiting or bank is None:
+            return
+        bps = self.bit_depth // 8
+        hop, overlap = win.read_size // bps, win.overlap_size // bps
+        settings = self.capture.export.settings(bank.rate)
+        origins = np.full(bank.max_sources, -overlap, np.int64)   # the first window begins with `overlap` zeros
+        for (m, index), n in base.items():
+            if m == model_id and index < bank.max_sources:
+                origins[index] -= n
+        inside = [it for it in waiting if int(it[0]["recording"]) < bank.max_sources]
+        ev = np.array([it[0] for it in inside], _host.EVENT) if inside else np.zeros(0, _host.EVENT)
+        spans, status = bank.spans(ev, hop, settings, origins)
+        room = max(1, min(self.capture.export.max_clips, 65535))
+        ready = [i for i in range(len(inside)) if status[i] in (_host.CAPTURE_OK, _host.CAPTURE_CLAMPED)]
+        later = [inside[i] for i in range(len(inside)) if status[i] == _host.CAPTURE_NOT_YET] + [inside[i] for i in ready[room:]]
+        ready = ready[:room]
+        clips = []
+        if ready:
+            try:
+                clips = bank.export(spans[ready], settings)
+            except Exception as e:
+                self.errors += len(ready)
+                if self.on_error:
+                    self.on_error(model_id, sorted({inside[i][1] for i in ready}), e)
+                ready = []
+        reports = []
+        made = {i: clips[j] for j, i in enumerate(ready[:len(clips)])}
+        for i, (e, source, label) in enumerate(inside):
+            if i not in made and status[i] != _host.CAPTURE_GONE:
+                continue
+            c = made.get(i)
+            reports.append({"timestamp": now, "source": source, "model_id": model_id, "class_index": int(e["class_index"]), "label": label,
+                            "first_window": int(e["first_window"]), "last_window": int(e["last_window"]), "status": int(status[i]),
+                            "start": int(spans[i]["start"]), "length": int(spans[i]["length"]) if c is not None else 0,
+                            "flac": c["flac"] if c is not None else None, "png": c["png"] if c is not None else None,
+                            "loudness": c["loudness"] if c is not None else None})
+        with self.mu:
+            if later:
+                self.capture_waiting[model_id] = later + self.capture_waiting.get(model_id, [])
+            self.clip_reports.extend(reports)
+        if reports and self.on_clips:
+            self.on_clips(model_id, reports)
+
+    def take_clips(self):
+        """-> the detection clips since the last call, oldest first: {"timestamp", "source", "model_id", "class_index", "label",
+        "first_window", "last_window", "status" (host.CAPTURE_OK, _CLAMPED: begun later than asked, or _GONE: no clip), "start" (the
+        position of the clip's first sample on the source's capture clock), "length", "flac", "png", "loudness"}."""
+        with self.mu:
+            out, self.clip_reports = self.clip_reports, []
+        return out
 
     def _event_bank(self, model_id, inst):
         """(under the model's inference lock) the bank of the model's assembler, created at the first tick with `events`."""
@@ -934,11 +1074,11 @@ class WindowBatcher:
                     else:
                         resampled.append((self.resamplers[(source,) + key], targets))
         for ab in abs_:
-            ab.write(data)
+            self._ring_write(ab, data)
         for r, targets in resampled:
             out = r.resample_into(raw)
             for ab in targets:
-                ab.write(out)
+                self._ring_write(ab, out)
         if sl is not None:                                        # python: one monitor call per write
             with self.mu:
                 try:
@@ -959,7 +1099,7 @@ class WindowBatcher:
         applyProcessing or resample and goes on): they count in self.errors, (sources, error) goes to `failed` -> None."""
         try:
             wins = {id(ab.win) for *_, bufs in items for ab in bufs}
-            if len(wins) == 1 and all(len(bufs) == 1 for *_, bufs in items):
+            if self.capture is None and len(wins) == 1 and all(len(bufs) == 1 for *_, bufs in items):   # (capture stages what the rings get)
                 bank.write_windows(items[0][3][0].win, [(st, bufs[0].index, raw) for _, st, raw, bufs in items])
                 return None
             return bank.process([(st, raw) for _, st, raw, _ in items])
@@ -1003,6 +1143,7 @@ class WindowBatcher:
                 for (*_, targets), out in zip(items, outs or []):
                     for ab in targets:
                         ab.write(out)
+                        self._stage_capture(ab, out)
         for sources, e in failed:
             if self.on_error:
                 self.on_error(None, sources, e)
@@ -1045,6 +1186,8 @@ class WindowBatcher:
                 raise
 
         for model_id, win in wins:
+            if self.capture is not None and self.orch.model_spec_for(model_id) is not None:
+                self._capture_upload(model_id, self.orch.model_spec_for(model_id))
             while True:
                 spec = self.orch.model_spec_for(model_id)
                 if spec is None or not self.orch.is_model_active(model_id):   # consumed, not analysed (buffer_manager.go:478-481)
@@ -1075,6 +1218,9 @@ class WindowBatcher:
                     if reports:
                         with self.mu:
                             self.event_reports.extend(reports)
+                            if self.capture is not None:
+                                self.capture_waiting.setdefault(model_id, []).extend(
+                                    (e.copy(), r["source"], r["label"]) for e, r in zip(ev, reports) if int(e["status"]) == 0)
                         if self.on_events:
                             self.on_events(model_id, reports)
                 del tick_events[:]
@@ -1083,6 +1229,8 @@ class WindowBatcher:
                                       model_id, self.queue, self.overruns)
                 if len(idxs) < min(self.max_batch, win.max_batch):
                     break
+            if self.capture is not None:
+                self._capture_export(model_id, win, self.clock())
         return sent
 
     def close(self):
@@ -1106,9 +1254,12 @@ class WindowBatcher:
             for bank in self.sl_banks.values():
                 bank.close()
             self.sl_banks.clear()
-            for bank in self.event_banks.values():
+            for bank in list(self.event_banks.values()) + list(self.capture_banks.values()):
                 bank.close()
             self.event_banks.clear()
+            self.capture_banks.clear()
+            for d in (self.capture_staged, self.capture_fed, self.capture_base, self.capture_waiting):
+                d.clear()
             self.sl_streams.clear()
             self.sl_pending.clear()
 

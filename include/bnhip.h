@@ -521,6 +521,71 @@ int bnhip_analyze_channels_pcm_clips(bnhip_model* m, const void* pcm, const bnhi
                                      const bnhip_event_filter* filter, int32_t* chosen, const bnhip_clip_export* x,
                                      bnhip_clips_out* out);
 
+/* Capture bank: the real-time path's detection clips.  The reference keeps a CaptureBuffer per source - a circular PCM buffer with a
+ * monotonic byte counter, from which ReadSegment cuts a detection's audio (internal/audiocore/buffer/capture.go:60-112, 132-179,
+ * 198-330).  A bank keeps every source's ring on the device: a source's audio goes up once per tick, and a due detection is answered
+ * as finished FLAC and PNG bytes, as on the file path.  No PCM comes back.
+ *   rings    max_sources rings of mono int16 at one sample rate, all allocated at create: max_sources * capacity * 2 bytes of device
+ *            memory (2.95 GB for 256 sources of 120 s at 48 kHz).  capacity_samples is rounded up to a multiple of 1024 samples (the
+ *            reference aligns to 2048 bytes: the same); bnhip_capture_bank_info answers the rounded value.
+ *   clock    Audio time: written[s] is the number of samples ever given for source s since create or reset, and the sample at
+ *            position P of that clock lies in the ring for as long as oldest[s] <= P < written[s], oldest[s] = max(0, written[s] -
+ *            capacity, floor[s]) (floor: "a failed write" below).  A write longer than the ring counts in full although only its
+ *            last `capacity` samples are stored - unlike the reference, whose counter advances by the stored tail only
+ *            (capture.go:148-152, 162), so that positions behind such a write no longer are audio time there.
+ *   bnhip_capture_bank_positions  written [max_sources], oldest [max_sources].
+ *   bnhip_capture_bank_reset  Source `source` (-1: all) starts again: written 0, floor 0.  Host work only.
+ *   bnhip_capture_bank_write  One call per tick for every source: frame f is n_samples[f] samples of bits_per_sample (16, 24 or 32,
+ *            little endian, packed) for source sources[f].  A source may appear several times; its frames are appended in call order.
+ *            A sample is stored as q = clamp(rint(x * 32768), -32768, 32767), x the float32 of "Detection clips" above: a 16-bit
+ *            sample as itself.  If a source's frames of one call total more than the ring, its last `capacity` samples are stored.
+ *            One staging copy, one launch, one synchronise, then the commit: written[s] += the source's total.
+ *   a failed write  The rings are too large to keep twice, so a write that fails on the device leaves written as it was and
+ *            raises floor[s] of every source of the call to written[s] + total[s] - capacity where that is positive: no later read
+ *            returns a cell the failed launch may have touched.
+ *   bnhip_capture_bank_read_pcm16  The cut alone.  spans: bnhip_clip_span with `recording` the source and `start` a position on its
+ *            clock; every span of non-zero length must lie in [oldest, written) of its source.  Spans of length 0 are skipped;
+ *            out_pcm holds the others packed back to back, as bnhip_recording_clips_pcm16 does.
+ *   bnhip_capture_bank_clips  The cut, then exactly the second phase of bnhip_analyze_channels_pcm_clips over the clips where they
+ *            lie: the normalise (with normalize != 0), the FLAC encode at lpc_order, and with width > 0 the render and PNG encode;
+ *            rate_in is the bank's rate.  The same n_clips rule over the spans, the same records and offsets.  out->events is not
+ *            used (event_cap 0 is allowed); out->spans [n_spans] receives the spans as given; loudness [n_spans], flac_offsets /
+ *            png_offsets [n_spans + 1].
+ *   bnhip_capture_spans  Host only, no bank: bnhip_event_clip_spans on a running clock.  hop: capture samples per window step;
+ *            origins[s] (NULL: 0): the position of window 0's first sample, which may be negative - the window assembler's first
+ *            window begins with its overlap of zeros, so a host that feeds both from one stream passes -overlap_samples.  For
+ *            event e of source s = e.recording: P0 = origins[s] + first_window * hop - pre_samples, P1 = origins[s] + (extended ?
+ *            last_window : first_window) * hop + post_samples, start = max(P0, oldest[s]), and in this order: e.status != 0 ->
+ *            BNHIP_CAPTURE_DROPPED; P1 > written[s] -> BNHIP_CAPTURE_NOT_YET (the end is never cut short - capture.go:265-293:
+ *            insufficient data is an error, not a shorter clip - the host asks again after a later write); start >= P1 ->
+ *            BNHIP_CAPTURE_GONE; each of these with length 0.  Else length = min(P1, start + max_samples) - start, and the status
+ *            is BNHIP_CAPTURE_CLAMPED when start > P0 (capture.go:222-228), else BNHIP_CAPTURE_OK.  spans, status: [n_events].
+ *   calls    Every bank call holds the bank's lock and has synchronised before it returns.  The same calls give the same bytes on
+ *            every run.  Single-device handles.
+ * BNHIP_E_INVALID (before any device call, the handle stays usable): NULL where a pointer is required, max_sources outside 1..65535,
+ * capacity_samples outside 1..2^31 - 1024, rate outside 1..1048575, bits_per_sample not 16, 24 or 32, a source outside the bank, a
+ * negative frame or span length, n_spans outside 1..65535, a span outside [oldest, written), a total of 2^36 samples or more, what
+ * bnhip_analyze_channels_pcm_clips refuses of its export settings; for bnhip_capture_spans what bnhip_event_clip_spans refuses and
+ * an event's source outside n_sources.  Allocation failure: BNHIP_E_NOMEM. */
+#define BNHIP_CAPTURE_OK 0
+#define BNHIP_CAPTURE_CLAMPED 1
+#define BNHIP_CAPTURE_NOT_YET 2
+#define BNHIP_CAPTURE_GONE 3
+#define BNHIP_CAPTURE_DROPPED 4
+typedef struct bnhip_capture_bank bnhip_capture_bank;
+int bnhip_capture_bank_create(int device, int max_sources, int64_t capacity_samples, int rate, bnhip_capture_bank** out);
+int bnhip_capture_bank_info(const bnhip_capture_bank* b, int* max_sources, int64_t* capacity_samples, int* rate);
+int bnhip_capture_bank_positions(bnhip_capture_bank* b, int64_t* written, int64_t* oldest);
+int bnhip_capture_bank_reset(bnhip_capture_bank* b, int source);
+int bnhip_capture_bank_write(bnhip_capture_bank* b, int n_frames, const int32_t* sources, const int64_t* n_samples,
+                             const void* const* frames, int bits_per_sample);
+int bnhip_capture_bank_read_pcm16(bnhip_capture_bank* b, const bnhip_clip_span* spans, int n_spans, int16_t* out_pcm);
+int bnhip_capture_bank_clips(bnhip_capture_bank* b, const bnhip_clip_span* spans, int n_spans, const bnhip_clip_export* x,
+                             bnhip_clips_out* out);
+void bnhip_capture_bank_destroy(bnhip_capture_bank* b);
+int bnhip_capture_spans(const bnhip_event* events, size_t n_events, int n_sources, const int64_t* written, const int64_t* oldest,
+                        const int64_t* origins, int hop, const bnhip_clip_export* x, bnhip_clip_span* spans, int32_t* status);
+
 /* Ultrasonic frame-CV filter (internal/audiocore/ultrasonic/filter.go:20-66), float64 throughout.
  * samples: host float64 [n_clips * n] (int16/32768 as float64, convert/pcm.go:108-113).
  * cv/ok: [n_clips]. device: HIP device ordinal. */
