@@ -86,7 +86,11 @@ struct Request { bnhip_model* m; const void* pcm; int hop; int64_t min_tail; int
 // cap counts events) and the reference's result post-filters run there as the call's tail (events.h)
 struct TopK { float* conf; int32_t* idx; bool complete() const { return conf && idx; } };
 struct Rows { float threshold; bnhip_detection* out; size_t cap; size_t* n_out; bool complete() const { return n_out && (!cap || out); } };
-struct Events { const bnhip_event_filter* filter; bnhip_event* out; size_t cap; size_t* n_out; bool complete() const { return n_out && (!cap || out); } };
+struct Events {
+    const bnhip_event_filter* filter; bnhip_event* out; size_t cap; size_t* n_out;
+    bool extended = false; const bnhip_event_extend* extend = nullptr;      // the _extended entries: under this extend, then required
+    bool complete() const { return n_out && (!cap || out); }
+};
 // what bnhip_analyze_channels_pcm_clips adds to its events call: the export settings and where everything goes (clips.h)
 struct ClipsTail { const bnhip_clip_export* x; bnhip_clips_out* o; int model_rate; };
 struct Answer {
@@ -106,6 +110,7 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
     if (!q.m || !q.pcm || !lengths) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (!std::visit([](const auto& w) { return w.complete(); }, a.what)) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (ev) if (int rc = event_filter_check(ev->filter)) return rc;
+    if (ev && ev->extended) if (int rc = event_extend_check(ev->filter->hold_windows, ev->extend)) return rc;
     if (rec.bits != 0 && rec.bits != 16 && rec.bits != 24 && rec.bits != 32)
         return set_err(BNHIP_E_INVALID, "unsupported bit depth: " + std::to_string(rec.bits) + " (supported: 0 = float32, 16, 24, 32)");
     if (q.k <= 0) return set_err(BNHIP_E_INVALID, "k must be positive");
@@ -142,7 +147,7 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
     size_t o_scr = 0, o_total = 0, o_rows = 0, o_evtab = 0, o_evscr = 0, o_evout = 0;
     if (!tk) { o_scr = cv.add(detections_scratch_bytes(W)); o_total = cv.add(8); o_rows = cv.add(rows_cap * sizeof(DetRow)); }
     if (ev) {
-        o_evtab = cv.add(event_tables_bytes(e.n_classes)); o_evscr = cv.add(events_scratch_bytes(n_rows_max));
+        o_evtab = cv.add(event_tables_bytes(e.n_classes, ev->extended)); o_evscr = cv.add(events_scratch_bytes(n_rows_max));
         o_evout = cv.add(out_cap * sizeof(Event));
     }
     DevBlocks b;
@@ -151,7 +156,7 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
     slot_upload(sp, q.pcm, rec, slot, e.device, dv, e.stream, b);
     AN_HIP(b, hipMemcpyAsync(cv.at<void>(o_table), table.data(), table.size() * 8, hipMemcpyHostToDevice, e.stream));
     EventFilterDev fd{};
-    if (ev) fd = event_filter_upload(ev->filter, e.n_classes, cv.at<char>(o_evtab), e.stream, b);
+    if (ev) fd = event_filter_upload(ev->filter, e.n_classes, cv.at<char>(o_evtab), e.stream, b, ev->extended ? ev->extend : nullptr);
     WinView view;
     view.first = cv.at<long long>(o_table);
     view.slot = view.first + rec.n + 1;
@@ -327,19 +332,50 @@ int bnhip_analyze_channels_pcm_events(bnhip_model* m, const void* pcm, const bnh
     BN_GUARD_END((void)0)
 }
 
-// the events call with the clip export as its continuation (clips.h; the span rule and the export itself: api_clips.cpp)
-int bnhip_analyze_channels_pcm_clips(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
-                                     int hop, int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter,
-                                     int32_t* chosen, const bnhip_clip_export* x, bnhip_clips_out* out) {
+int bnhip_analyze_channels_pcm_events_extended(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                               int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                               const bnhip_event_filter* filter, const bnhip_event_extend* extend, bnhip_event* out, size_t cap,
+                                               size_t* n_out, int32_t* chosen) {
     BN_GUARD_BEGIN
+    return analyze_entry(AN_REQUEST, {.what = Events{.filter = filter, .out = out, .cap = cap, .n_out = n_out, .extended = true, .extend = extend},
+                                      .chosen = chosen},
+                        recs, n_recordings, model_rate);
+    BN_GUARD_END((void)0)
+}
+
+}  // extern "C"
+
+// the events call with the clip export as its continuation (clips.h; the span rule and the export itself: api_clips.cpp)
+static int analyze_clips(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate, int hop,
+                         int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter, bool extended,
+                         const bnhip_event_extend* extend, int32_t* chosen, const bnhip_clip_export* x, bnhip_clips_out* out) {
     if (int rc = clip_export_check(x, out, model_rate)) return rc;
     if (int rc = event_filter_check(filter)) return rc;
     if (filter->flags & BNHIP_EVENTS_KEEP_DROPPED) return set_err(BNHIP_E_INVALID, "the clip export takes kept events only: BNHIP_EVENTS_KEEP_DROPPED is refused");
     const ClipsTail tail{x, out, model_rate};
     size_t n_events = 0;
-    return analyze_entry(AN_REQUEST, {.what = Events{.filter = filter, .out = out->events, .cap = out->event_cap, .n_out = &n_events}, .chosen = chosen,
-                                      .clips = &tail},
+    return analyze_entry(AN_REQUEST, {.what = Events{.filter = filter, .out = out->events, .cap = out->event_cap, .n_out = &n_events,
+                                                     .extended = extended, .extend = extend},
+                                      .chosen = chosen, .clips = &tail},
                         recs, n_recordings, model_rate);
+}
+
+extern "C" {
+
+int bnhip_analyze_channels_pcm_clips(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate,
+                                     int hop, int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter,
+                                     int32_t* chosen, const bnhip_clip_export* x, bnhip_clips_out* out) {
+    BN_GUARD_BEGIN
+    return analyze_clips(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, filter, false, nullptr, chosen, x, out);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_analyze_channels_pcm_clips_extended(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                              int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                              const bnhip_event_filter* filter, const bnhip_event_extend* extend, int32_t* chosen,
+                                              const bnhip_clip_export* x, bnhip_clips_out* out) {
+    BN_GUARD_BEGIN
+    return analyze_clips(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, filter, true, extend, chosen, x, out);
     BN_GUARD_END((void)0)
 }
 

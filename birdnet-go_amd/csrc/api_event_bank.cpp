@@ -35,12 +35,17 @@ struct bnhip_event_bank {
     int device = 0, max_sources = 0, n_classes = 0, k = 0, hold = 0, slots = 0;
     float veto_thr = 0.0f;
     int min_count = 1, flags = 0;
+    bool extended = false;              // created extended: the slots carry their deadlines, the tables a third part
+    int longest_wait = 0;               // ... and W of the extend it was created with: what the slots were sized for
+    EventExtend x{};                    // the extend's numbers in force (max_windows 0: sliding is off)
     bool tables_dirty = true;           // h_tab is newer than d_tab: the next call's header copy takes it along
     std::vector<Source> src;
     hipStream_t stream = nullptr;       // the bank's own, made at the first call that needs it: a bank fed by the tick alone runs on
                                         // the model's stream and adds none to the few hardware queues a process has (hostpipe.cpp)
-    int32_t* d_state = nullptr;         // [max_sources][2][evb_slab_ints(slots)]
+    int32_t* d_state = nullptr;         // [max_sources][2][evb_slab_ints(slots, extended)]
     char* h_tab = nullptr; char* d_tab = nullptr;                                 // class_threshold [n_classes] | class_veto [n_classes]
+                                                                                  // | extended: class_extended [n_classes]
+    size_t tab_bytes() const { return (size_t)n_classes * (extended ? 6 : 5); }
     uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // groups | row map | rows
     uint8_t* h_out = nullptr; void* d_out = nullptr; size_t out_cap = 0;         // count, overflow flag | events
     void* d_work = nullptr; size_t work_cap = 0;                                 // staged events | counts and bases
@@ -70,6 +75,15 @@ void evb_take_filter(bnhip_event_bank* b, const bnhip_event_filter* f) {
     if (f->class_veto) memcpy(veto, f->class_veto, (size_t)b->n_classes);
     else memset(veto, 0, (size_t)b->n_classes);
     b->veto_thr = f->veto_threshold; b->min_count = f->min_count; b->flags = f->flags;
+    b->tables_dirty = true;
+}
+
+// (an extended bank) x NULL: sliding off
+void evb_take_extend(bnhip_event_bank* b, const bnhip_event_extend* x) {
+    uint8_t* slide = reinterpret_cast<uint8_t*>(b->h_tab) + (size_t)b->n_classes * 5;
+    if (x && x->class_extended) memcpy(slide, x->class_extended, (size_t)b->n_classes);
+    else memset(slide, 1, (size_t)b->n_classes);
+    b->x = x ? event_extend_numbers(x) : EventExtend{};
     b->tables_dirty = true;
 }
 
@@ -158,9 +172,8 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
         memcpy(b->h_stage + o_conf, conf, row_vals * 4);
         memcpy(b->h_stage + o_idx, idx, row_vals * 4);
     }
-    const size_t tab_bytes = (size_t)b->n_classes * 5;
     hipError_t he = hipSuccess;
-    if (b->tables_dirty) he = hipMemcpyAsync(b->d_tab, b->h_tab, tab_bytes, hipMemcpyHostToDevice, s);
+    if (b->tables_dirty) he = hipMemcpyAsync(b->d_tab, b->h_tab, b->tab_bytes(), hipMemcpyHostToDevice, s);
     if (he == hipSuccess) he = hipMemcpyAsync(b->d_stage, b->h_stage, stage_bytes, hipMemcpyHostToDevice, s);
     if (he != hipSuccess) { hipStreamSynchronize(s); return evb_fail(he); }
 
@@ -173,15 +186,16 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
     c.rowmap = reinterpret_cast<const int32_t*>(ds + o_map);
     c.conf = row_vals ? reinterpret_cast<const float*>(ds + o_conf) : conf;
     c.idx = row_vals ? reinterpret_cast<const int32_t*>(ds + o_idx) : idx;
-    c.k = k; c.slots = b->slots; c.mode = mode;
+    c.k = k; c.slots = b->slots; c.mode = mode; c.extended = b->extended;
     c.state = b->d_state;
     c.stage = reinterpret_cast<Event*>(dw);
     c.counts = reinterpret_cast<uint32_t*>(dw + o_counts);
     c.head = reinterpret_cast<unsigned long long*>(dout);
     c.out = reinterpret_cast<Event*>(dout + EVB_HEAD);
     c.out_cap = out_room;
-    const EventFilterDev fd{reinterpret_cast<const float*>(b->d_tab), reinterpret_cast<const uint8_t*>(b->d_tab) + (size_t)b->n_classes * 4,
-                            b->veto_thr, b->hold, b->min_count, b->flags, b->n_classes};
+    EventFilterDev fd{reinterpret_cast<const float*>(b->d_tab), reinterpret_cast<const uint8_t*>(b->d_tab) + (size_t)b->n_classes * 4,
+                      b->veto_thr, b->hold, b->min_count, b->flags, b->n_classes};
+    if (b->extended) { fd.slide = reinterpret_cast<const uint8_t*>(b->d_tab) + (size_t)b->n_classes * 5; fd.x = b->x; }
     launch_event_bank(c, fd, s);
     he = hipGetLastError();
     const size_t first_n = std::min(out_room, EVB_FIRST_FETCH);
@@ -228,6 +242,39 @@ int evb_shape_check(const bnhip_event_filter* f, int k) {
     return BNHIP_OK;
 }
 
+// create, with or without an extend
+int evb_create(int device, int max_sources, int n_classes, int k, const bnhip_event_filter* filter, bool extended, const bnhip_event_extend* extend,
+               bnhip_event_bank** out) {
+    if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (int rc = evb_shape_check(filter, k)) return rc;
+    if (extended) if (int rc = event_extend_check(filter->hold_windows, extend, k)) return rc;
+    if (max_sources < 1 || max_sources > 65535) return set_err(BNHIP_E_INVALID, "max_sources must be in [1, 65535]");
+    if (n_classes < 1 || n_classes > EVB_MAX_CLASSES) return set_err(BNHIP_E_INVALID, "n_classes must be in [1, 38400]");
+    bnhip_event_bank* b = nullptr;
+    BN_GUARD_BEGIN
+    if (int rc = use_device(device)) return rc;
+    b = new bnhip_event_bank();
+    b->device = device; b->max_sources = max_sources; b->n_classes = n_classes; b->k = k; b->hold = filter->hold_windows;
+    b->extended = extended;
+    b->longest_wait = extended ? ev_longest_wait(b->hold, event_extend_numbers(extend)) : b->hold;
+    b->slots = std::min(k * b->longest_wait, n_classes);
+    b->src.resize((size_t)max_sources);
+    hipError_t he = hipMalloc((void**)&b->d_state, (size_t)max_sources * 2 * evb_slab_ints(b->slots, extended) * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&b->d_tab, b->tab_bytes());
+    if (he == hipSuccess) he = hipHostMalloc((void**)&b->h_tab, b->tab_bytes(), hipHostMallocPortable);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        bank_free(b); b = nullptr;
+        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(WHAT) + " create: " + hipGetErrorString(he));
+    }
+    evb_take_filter(b, filter);
+    if (extended) evb_take_extend(b, extend);
+    *out = b;
+    return BNHIP_OK;
+    BN_GUARD_END(bank_free(b))
+}
+
 int evb_answer_check(const bnhip_event_bank* b, const bnhip_event* out, size_t cap, const size_t* n_out) {
     if (!b || !n_out || (cap && !out)) return set_err(BNHIP_E_INVALID, "NULL argument");
     return BNHIP_OK;
@@ -258,30 +305,12 @@ int event_bank_rows(bnhip_event_bank* b, size_t n_rows, float** d_conf, int32_t*
 extern "C" {
 
 int bnhip_event_bank_create(int device, int max_sources, int n_classes, int k, const bnhip_event_filter* filter, bnhip_event_bank** out) {
-    if (!out) return set_err(BNHIP_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (int rc = evb_shape_check(filter, k)) return rc;
-    if (max_sources < 1 || max_sources > 65535) return set_err(BNHIP_E_INVALID, "max_sources must be in [1, 65535]");
-    if (n_classes < 1 || n_classes > EVB_MAX_CLASSES) return set_err(BNHIP_E_INVALID, "n_classes must be in [1, 38400]");
-    bnhip_event_bank* b = nullptr;
-    BN_GUARD_BEGIN
-    if (int rc = use_device(device)) return rc;
-    b = new bnhip_event_bank();
-    b->device = device; b->max_sources = max_sources; b->n_classes = n_classes; b->k = k; b->hold = filter->hold_windows;
-    b->slots = std::min(k * filter->hold_windows, n_classes);
-    b->src.resize((size_t)max_sources);
-    hipError_t he = hipMalloc((void**)&b->d_state, (size_t)max_sources * 2 * evb_slab_ints(b->slots) * 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&b->d_tab, (size_t)n_classes * 5);
-    if (he == hipSuccess) he = hipHostMalloc((void**)&b->h_tab, (size_t)n_classes * 5, hipHostMallocPortable);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        bank_free(b); b = nullptr;
-        return set_err(he == hipErrorOutOfMemory ? BNHIP_E_NOMEM : BNHIP_E_RUNTIME, std::string(WHAT) + " create: " + hipGetErrorString(he));
-    }
-    evb_take_filter(b, filter);
-    *out = b;
-    return BNHIP_OK;
-    BN_GUARD_END(bank_free(b))
+    return evb_create(device, max_sources, n_classes, k, filter, false, nullptr, out);
+}
+
+int bnhip_event_bank_create_extended(int device, int max_sources, int n_classes, int k, const bnhip_event_filter* filter,
+                                     const bnhip_event_extend* extend, bnhip_event_bank** out) {
+    return evb_create(device, max_sources, n_classes, k, filter, true, extend, out);
 }
 
 int bnhip_event_bank_info(const bnhip_event_bank* b, int* max_sources, int* n_classes, int* k, int* hold_windows, int* slots_per_source) {
@@ -302,6 +331,22 @@ int bnhip_event_bank_set_filter(bnhip_event_bank* b, const bnhip_event_filter* f
     if (filter->hold_windows != b->hold)
         return set_err(BNHIP_E_INVALID, "hold_windows is fixed for the bank's life: " + std::to_string(b->hold) + ", not " + std::to_string(filter->hold_windows));
     evb_take_filter(b, filter);
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_event_bank_set_extend(bnhip_event_bank* b, const bnhip_event_extend* extend) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (!b->extended) return set_err(BNHIP_E_INVALID, "the event bank was created without an extend");
+    if (extend) {
+        if (int rc = event_extend_check(b->hold, extend)) return rc;
+        const int W = ev_longest_wait(b->hold, event_extend_numbers(extend));
+        if (W > b->longest_wait)
+            return set_err(BNHIP_E_INVALID, "the longest wait is fixed for the bank's life: at most " + std::to_string(b->longest_wait) + ", not " + std::to_string(W));
+    }
+    evb_take_extend(b, extend);
     return BNHIP_OK;
     BN_GUARD_END((void)0)
 }

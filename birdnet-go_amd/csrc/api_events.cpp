@@ -22,12 +22,37 @@ int event_filter_check(const bnhip_event_filter* f) {
     return BNHIP_OK;
 }
 
-EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, char* d_tables, hipStream_t s, DevBlocks& b) {
+int event_extend_check(int hold_windows, const bnhip_event_extend* x, int k) {
+    if (!x) return set_err(BNHIP_E_INVALID, "NULL event extend");
+    if (x->max_windows < hold_windows) return set_err(BNHIP_E_INVALID, "max_windows must be at least hold_windows");
+    if (x->short_wait < 1) return set_err(BNHIP_E_INVALID, "short_wait must be at least 1");
+    if (x->medium_wait < 1) return set_err(BNHIP_E_INVALID, "medium_wait must be at least 1");
+    if (x->long_wait < 1) return set_err(BNHIP_E_INVALID, "long_wait must be at least 1");
+    if (x->medium_from < 1) return set_err(BNHIP_E_INVALID, "medium_from must be at least 1");
+    if (x->long_from < x->medium_from) return set_err(BNHIP_E_INVALID, "long_from must be at least medium_from");
+    if (k > 0 && (long long)k * ev_longest_wait(hold_windows, event_extend_numbers(x)) > 4096)
+        return set_err(BNHIP_E_INVALID, "k * W must be at most 4096 (W: the longest of hold_windows, short_wait, medium_wait, long_wait)");
+    return BNHIP_OK;
+}
+
+EventExtend event_extend_numbers(const bnhip_event_extend* x) {
+    EventExtend n;
+    n.max_windows = x->max_windows; n.short_wait = x->short_wait; n.medium_from = x->medium_from; n.medium_wait = x->medium_wait;
+    n.long_from = x->long_from; n.long_wait = x->long_wait;
+    return n;
+}
+
+EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, char* d_tables, hipStream_t s, DevBlocks& b,
+                                   const bnhip_event_extend* x) {
     char* d_veto = f->class_veto ? d_tables + (size_t)n_classes * 4 : nullptr;
+    char* d_slide = x && x->class_extended ? d_tables + (size_t)n_classes * 5 : nullptr;
     if (b.he == hipSuccess) b.he = hipMemcpyAsync(d_tables, f->class_threshold, (size_t)n_classes * 4, hipMemcpyHostToDevice, s);
     if (b.he == hipSuccess && d_veto) b.he = hipMemcpyAsync(d_veto, f->class_veto, (size_t)n_classes, hipMemcpyHostToDevice, s);
-    return EventFilterDev{reinterpret_cast<const float*>(d_tables), reinterpret_cast<const uint8_t*>(d_veto), f->veto_threshold, f->hold_windows,
-                          f->min_count, f->flags, n_classes};
+    if (b.he == hipSuccess && d_slide) b.he = hipMemcpyAsync(d_slide, x->class_extended, (size_t)n_classes, hipMemcpyHostToDevice, s);
+    EventFilterDev fd{reinterpret_cast<const float*>(d_tables), reinterpret_cast<const uint8_t*>(d_veto), f->veto_threshold, f->hold_windows,
+                      f->min_count, f->flags, n_classes};
+    if (x) { fd.slide = reinterpret_cast<const uint8_t*>(d_slide); fd.x = event_extend_numbers(x); }
+    return fd;
 }
 
 void fetch_counted(const void* d_total, const void* d_records, size_t record_bytes, size_t cap, void* out, unsigned long long* total, hipStream_t s,
@@ -43,16 +68,17 @@ void fetch_counted(const void* d_total, const void* d_records, size_t record_byt
 // what the LDS top-k holds (api_predict.cpp): with recording < 65 535 a (recording, class) key is below 2^32
 static constexpr int EVENT_MAX_CLASSES = 150 * 1024 / 4;
 
-extern "C" {
+namespace {
 
 // the tail alone over rows the host holds: one pass over the rows for every refusal, one DevCarve (rows, their count, the filter's
-// tables, the scratch, the events), the rows and tables up, the tail's launches, the count and the events down
-int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
-                           bnhip_event* out, size_t cap, size_t* n_out) {
-    BN_GUARD_BEGIN
+// tables, the scratch, the events), the rows and tables up, the tail's launches, the count and the events down.  extended: under
+// `extend`, which is then required
+int detection_events(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter, bool extended,
+                     const bnhip_event_extend* extend, bnhip_event* out, size_t cap, size_t* n_out) {
     const char* what = "detection_events";
     if (!n_out || (cap && !out) || (n_rows && !rows)) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (int rc = event_filter_check(filter)) return rc;
+    if (extended) if (int rc = event_extend_check(filter->hold_windows, extend)) return rc;
     if (n_classes < 1 || n_classes > EVENT_MAX_CLASSES) return set_err(BNHIP_E_INVALID, "n_classes must be in [1, 38400]");
     if (n_rows >= EVENT_MAX_ROWS) return set_err(BNHIP_E_INVALID, "2^31 detection rows or more");
     int max_rec = 0;
@@ -70,14 +96,14 @@ int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_row
     if (int rc = use_device(device)) return rc;
     const size_t ev_cap = std::min(cap, n_rows);
     DevCarve cv;
-    const size_t o_rows = cv.add(n_rows * sizeof(DetRow)), o_count = cv.add(8), o_tab = cv.add(event_tables_bytes(n_classes));
+    const size_t o_rows = cv.add(n_rows * sizeof(DetRow)), o_count = cv.add(8), o_tab = cv.add(event_tables_bytes(n_classes, extended));
     const size_t o_scr = cv.add(events_scratch_bytes(n_rows)), o_out = cv.add(ev_cap * sizeof(Event));
     DevBlocks b;
     cv.alloc(b);
     const unsigned long long n64 = n_rows;
     if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_rows), rows, n_rows * sizeof(DetRow), hipMemcpyHostToDevice);
     if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_count), &n64, 8, hipMemcpyHostToDevice);
-    const EventFilterDev fd = event_filter_upload(filter, n_classes, cv.at<char>(o_tab), nullptr, b);
+    const EventFilterDev fd = event_filter_upload(filter, n_classes, cv.at<char>(o_tab), nullptr, b, extended ? extend : nullptr);
     if (b.he != hipSuccess) return hip_fail(what, b);
     launch_events(cv.at<DetRow>(o_rows), cv.at<unsigned long long>(o_count), n_rows, fd, events_passes((unsigned long long)(max_rec + 1) * n_classes - 1),
                   cv.at<void>(o_scr), cv.at<Event>(o_out), ev_cap, nullptr);
@@ -88,7 +114,32 @@ int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_row
     if (b.he != hipSuccess) return hip_fail(what, b);
     *n_out = (size_t)total;
     return BNHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bnhip_detection_events(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                           bnhip_event* out, size_t cap, size_t* n_out) {
+    BN_GUARD_BEGIN
+    return detection_events(device, rows, n_rows, n_classes, filter, false, nullptr, out, cap, n_out);
     BN_GUARD_END((void)0)
+}
+
+int bnhip_detection_events_extended(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                                    const bnhip_event_extend* extend, bnhip_event* out, size_t cap, size_t* n_out) {
+    BN_GUARD_BEGIN
+    return detection_events(device, rows, n_rows, n_classes, filter, true, extend, out, cap, n_out);
+    BN_GUARD_END((void)0)
+}
+
+// ev_deadline for the host (events.h), host only
+int64_t bnhip_event_deadline(int32_t hold_windows, const bnhip_event_extend* extend, int64_t first_window, int64_t window) {
+    if (hold_windows < 1) return set_err(BNHIP_E_INVALID, "hold_windows must be at least 1");
+    if (int rc = event_extend_check(hold_windows, extend)) return rc;
+    if (first_window < 0 || window < first_window) return set_err(BNHIP_E_INVALID, "window must be at least first_window, and neither negative");
+    return ev_deadline(first_window, window, hold_windows, event_extend_numbers(extend));
 }
 
 // calculateMinDetectionsFromSettings (processor.go:1669-1729), host only

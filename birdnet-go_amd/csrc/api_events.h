@@ -14,10 +14,17 @@ constexpr unsigned long long EVENT_MAX_ROWS = 1ull << 31;
 
 // every refusal of the filter itself; -> 0 or a negative BNHIP_E_*
 int event_filter_check(const bnhip_event_filter* f);
-// bytes of the filter's tables on the device: class_threshold [n_classes], then class_veto [n_classes] where there is one
-inline size_t event_tables_bytes(int n_classes) { return (size_t)n_classes * 4 + (size_t)n_classes; }
-// the tables go up to d_tables (event_tables_bytes) on s, a failure into b; -> the filter as the kernels read it
-EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, char* d_tables, hipStream_t s, DevBlocks& b);
+// every refusal of an extend beside a filter that event_filter_check has passed (x NULL: refused); k > 0: also k * W
+int event_extend_check(int hold_windows, const bnhip_event_extend* x, int k = 0);
+// the extend's numbers as the kernels read them
+EventExtend event_extend_numbers(const bnhip_event_extend* x);
+// bytes of the filter's tables on the device: class_threshold [n_classes], then class_veto [n_classes] where there is one, then
+// an extend's class_extended [n_classes] where there is one
+inline size_t event_tables_bytes(int n_classes, bool extended = false) { return (size_t)n_classes * 4 + (size_t)n_classes * (extended ? 2 : 1); }
+// the tables go up to d_tables (event_tables_bytes) on s, a failure into b; -> the filter as the kernels read it.  x: the extend
+// that event_extend_check has passed, or NULL for none
+EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, char* d_tables, hipStream_t s, DevBlocks& b,
+                                   const bnhip_event_extend* x = nullptr);
 
 // A list the device has counted (detection rows, events): the count comes down and s is synchronised, then min(*total, cap)
 // records are copied to out - that copy is left in flight on s.  A failure goes into b.

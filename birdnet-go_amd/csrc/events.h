@@ -23,12 +23,38 @@ struct Event {
 constexpr int EVENTS_KEEP_DROPPED = 1;
 constexpr int EVENT_KEPT = 0, EVENT_FEW = 1, EVENT_VETOED = 2;
 
-// The filter as the kernels read it: thr [n_classes] and veto [n_classes] (or NULL) are device pointers.
+// Extended capture's numbers (bnhip_event_extend without its table), in windows.  max_windows == 0: no extend, every deadline is
+// b + hold.
+struct EventExtend {
+    int max_windows = 0, short_wait = 0, medium_from = 0, medium_wait = 0, long_from = 0, long_wait = 0;
+};
+// The sliding deadline (include/bnhip.h, "Detection events: extended capture"; calculateExtendedFlushDeadline,
+// extended_capture.go:311-329), stated once for both kernels and the host: an event of a sliding class opened at window b, hit at
+// window w >= b, is due at min(w + wait(w - b), b + max_windows).  b < the deadline the hit joined under <= b + max_windows, so the
+// answer is at least w + 1.
+__host__ __device__ inline long long ev_deadline(long long b, long long w, int hold, const EventExtend& x) {
+    const long long t = w - b;
+    const long long wait = t < x.medium_from ? (hold > x.short_wait ? hold : x.short_wait) : t < x.long_from ? x.medium_wait : x.long_wait;
+    const long long d = w + wait, most = b + x.max_windows;
+    return d < most ? d : most;
+}
+// W: no live event's deadline lies further behind its last hit
+inline int ev_longest_wait(int hold, const EventExtend& x) {
+    int W = hold > x.short_wait ? hold : x.short_wait;
+    W = x.medium_wait > W ? x.medium_wait : W;
+    return x.long_wait > W ? x.long_wait : W;
+}
+
+// The filter as the kernels read it: thr [n_classes] and veto [n_classes] (or NULL) are device pointers; with x.max_windows > 0 the
+// classes with slide[c] != 0 (slide NULL: all of them) take the sliding deadline.
 struct EventFilterDev {
     const float* thr;
     const uint8_t* veto;
     float veto_thr;
     int hold, min_count, flags, n_classes;
+    const uint8_t* slide = nullptr;
+    EventExtend x{};
+    __host__ __device__ bool slides(int cls) const { return x.max_windows > 0 && (!slide || slide[cls] != 0); }
 };
 
 // radix passes (8-bit digits) that keys up to max_key need: 1..4

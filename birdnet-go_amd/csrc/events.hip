@@ -239,6 +239,59 @@ __global__ __launch_bounds__(256) void k_ev_walk(const u32* __restrict__ key, co
     }
 }
 
+// The same walk under extended capture (events.h, ev_deadline).  A hit joins while its window lies before the deadline that its
+// predecessor's window gave the open event, so with b known lane j compares against ev_deadline(b, window of lane j - 1); lane 0's
+// predecessor is the last window of the step before, carried in prev.  The first lane at or beyond its deadline starts the next
+// event; the lanes behind it are judged again with the new b.  A deadline may move either way, so the lanes beyond it are no
+// suffix any more: todo masks the lanes that have their event.  A group of a class that does not slide keeps b + hold.
+__global__ __launch_bounds__(256) void k_ev_walk_slide(const u32* __restrict__ key, const int* __restrict__ win, const u64* __restrict__ counts,
+                                                       u32 N, EventFilterDev f, uint8_t* __restrict__ start) {
+    const u32 n = ev_rows(counts, N), lane = threadIdx.x & 63;
+    const u32 c0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+    if (c0 >= n) return;
+    const u32 me = c0 + lane;
+    const bool head = me < n && (me == 0 || key[me] != key[me - 1]);
+    u64 heads = __ballot(head);
+    while (heads) {
+        const u32 h = (u32)__ffsll((long long)heads) - 1u;
+        heads &= heads - 1ull;
+        u32 pos = c0 + h;
+        const u32 k = key[pos];
+        const bool slides = f.slides((int)(k % (u32)f.n_classes));
+        long long b = 0;
+        int prev = 0;
+        bool open = false;
+        for (;;) {
+            const u32 j = pos + lane;
+            const bool in = j < n && key[j] == k;
+            const int w = in ? win[j] : 0;
+            const u64 m_in = __ballot(in);
+            u64 todo = ~0ull;
+            if (!open) {                          // the group's first hit opens its first event
+                b = __shfl(w, 0);
+                if (lane == 0) start[pos] = 1;
+                open = true;
+                todo = ~1ull;
+            }
+            const int up = __shfl_up(w, 1);
+            const long long p = lane == 0 ? prev : up;
+            for (;;) {
+                const long long d = slides ? ev_deadline(b, p, f.hold, f.x) : b + f.hold;
+                const u64 m = __ballot(in && (long long)w >= d) & todo;
+                if (!m) break;
+                const int s = __ffsll((long long)m) - 1;
+                b = __shfl(w, s);
+                if ((int)lane == s) start[j] = 1;
+                todo = (~1ull) << s;              // (s == 63: none)
+            }
+            if (m_in != ~0ull) break;             // the group ends inside this step
+            prev = __shfl(w, 63);
+            pos += 64;
+            if (pos >= n) break;
+        }
+    }
+}
+
 // the event that begins at sorted hit i; -> whether it is answered
 __device__ __forceinline__ bool ev_reduce(u32 i, u32 n, const u32* __restrict__ key, const int* __restrict__ win, const float* __restrict__ conf,
                                           const uint8_t* __restrict__ start, const u64* __restrict__ veto, u32 n_veto, const EventFilterDev& f,
@@ -265,14 +318,18 @@ __device__ __forceinline__ bool ev_reduce(u32 i, u32 n, const u32* __restrict__ 
     if (count < f.min_count) {
         e.status = EVENT_FEW;
     } else {
-        // the recording's first veto window at or behind b: vetoed when it lies inside the hold
+        // the recording's first veto window at or behind b: vetoed when it lies inside the hold - before the event's final deadline,
+        // which under extended capture is the one its last hit gave it
         const u64 from = ((u64)(u32)e.recording << 32) | (u32)e.first_window;
+        u64 end = from + (u64)(u32)f.hold;
+        if (f.slides(e.cls))
+            end = ((u64)(u32)e.recording << 32) + (u64)min(ev_deadline(e.first_window, last, f.hold, f.x), 0xffffffffll);
         u32 lo = 0, hi = n_veto;
         while (lo < hi) {
             const u32 mid = lo + (hi - lo) / 2;
             if (veto[mid] < from) lo = mid + 1; else hi = mid;
         }
-        if (lo < n_veto && veto[lo] < from + (u64)(u32)f.hold) e.status = EVENT_VETOED;
+        if (lo < n_veto && veto[lo] < end) e.status = EVENT_VETOED;
     }
     return e.status == EVENT_KEPT || (f.flags & EVENTS_KEEP_DROPPED);
 }
@@ -330,7 +387,8 @@ void launch_events(const DetRow* rows, const unsigned long long* d_n, size_t N, 
     int* win = reinterpret_cast<int*>(sc.key[a ^ 1]);
     float* conf = reinterpret_cast<float*>(sc.idx[a ^ 1]);
     hipLaunchKernelGGL(k_ev_gather, rows_grid, block, 0, s, rows, sc.idx[a], sc.counts, n32, win, conf, sc.start);
-    hipLaunchKernelGGL(k_ev_walk, rows_grid, block, 0, s, sc.key[a], win, sc.counts, n32, f.hold, sc.start);
+    if (f.x.max_windows > 0) hipLaunchKernelGGL(k_ev_walk_slide, rows_grid, block, 0, s, sc.key[a], win, sc.counts, n32, f, sc.start);
+    else hipLaunchKernelGGL(k_ev_walk, rows_grid, block, 0, s, sc.key[a], win, sc.counts, n32, f.hold, sc.start);
     hipLaunchKernelGGL(k_ev_events<false>, rows_grid, block, 0, s, sc.key[a], win, conf, sc.start, sc.veto, sc.counts, n32, f, sc.base, out, cap);
     hipLaunchKernelGGL(k_ev_bases, dim3(1), block, 0, s, sc.base, nb, sc.counts + 2, (u64*)nullptr);
     hipLaunchKernelGGL(k_ev_events<true>, rows_grid, block, 0, s, sc.key[a], win, conf, sc.start, sc.veto, sc.counts, n32, f, sc.base, out, cap);

@@ -2,10 +2,11 @@
 // source's pending detections stay on the device across calls, and a call feeds them the top-k rows of the windows it brings.
 //
 // A source's state is one slab: its slots as a struct of arrays (class or -1 for a free slot, first / last / best window, count,
-// confidence) and behind them the source's latest veto-hit window.  A launch reads the slab of the source's parity and writes the
-// other; the host flips the parity only once the whole call has succeeded (stream_bank.h).  Three launches make a call: the update
-// (one wave per source of the call), a one-block scan of the sources' answered counts, and the emit that ranks each source's staged
-// events by (class, first window).  Compares and integer counts only; no rank comes from the return value of an atomic.
+// confidence; in a bank created extended also the deadline, events.h) and behind them the source's latest veto-hit window.  A
+// launch reads the slab of the source's parity and writes the other; the host flips the parity only once the whole call has
+// succeeded (stream_bank.h).  Three launches make a call: the update (one wave per source of the call), a one-block scan of the
+// sources' answered counts, and the emit that ranks each source's staged events by (class, first window).  Compares and integer
+// counts only; no rank comes from the return value of an atomic.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,11 +18,14 @@
 namespace bnhip {
 
 constexpr int EVENT_PENDING = -1;
-constexpr int EVB_MAX_SLOTS = 4096;              // k * hold_windows at the most: a source's slots fit one wave's LDS (96 KiB)
+constexpr int EVB_MAX_SLOTS = 4096;              // k * hold_windows (extended: k * W) at the most: a source's slots fit one wave's LDS
 enum EvbMode { EVB_PROCESS = 0, EVB_FLUSH = 1, EVB_PENDING = 2 };
 
-// ints of one slab: six arrays of `slots`, then the veto window (padded to 16 bytes)
-inline size_t evb_slab_ints(int slots) { return (size_t)slots * 6 + 4; }
+// arrays of a slab and of the update's LDS: six, and in a bank created extended the slots' deadlines as the seventh (96 / 112 KiB at
+// EVB_MAX_SLOTS, inside the CU's 160 KiB)
+__host__ __device__ inline int evb_arrays(bool extended) { return extended ? 7 : 6; }
+// ints of one slab: the arrays of `slots`, then the veto window (padded to 16 bytes)
+__host__ __device__ inline size_t evb_slab_ints(int slots, bool extended = false) { return (size_t)slots * evb_arrays(extended) + 4; }
 
 // One source of a call, sources ascending.  Its rows are rowmap[row_off .. row_off + n_windows) (row numbers of the call, in
 // call order); row j is window clock + j.  Its staged events go to stage[stage_off ..).
@@ -42,7 +46,8 @@ struct EvbCall {
     const float* conf;                           // [rows][k]
     const int32_t* idx;
     int k, slots, mode;
-    int32_t* state;                              // [max_sources][2][evb_slab_ints(slots)]
+    bool extended;                               // the bank was created extended: a slot carries its deadline
+    int32_t* state;                              // [max_sources][2][evb_slab_ints(slots, extended)]
     Event* stage;                                // the call's staging area
     uint32_t* counts;                            // [n_groups] answered events of each source, then [n_groups] their exclusive bases
     unsigned long long* head;                    // [0] the call's answered events, [1] non-zero: a source ran out of slots or staging

@@ -11,6 +11,8 @@
 // Integer work bound by latency: plain loads and stores, compares, ballots; nothing is accumulated in floating point.
 #include "events_bank.h"
 
+#include <climits>
+
 #include "block_scan.h"
 #include "kernels.h"
 
@@ -23,17 +25,26 @@ using u64 = unsigned long long;
 
 constexpr int EVB_KEY_TILE = 1024;
 
+// a deadline as a slot stores it: no clock passes 2^31 - 1 windows, so a later one is never reached either way
+__device__ __forceinline__ int evb_due(long long d) { return (int)min(d, (long long)INT_MAX); }
+
+// EXT: the bank was created extended - a slot carries its deadline (the seventh array, behind the other six in LDS and in the slab),
+// set when the slot opens and rewritten by every hit of a sliding class (ev_deadline).  Without it the deadline is first + hold
+// and nothing is stored.
+template <bool EXT>
 __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) {
     extern __shared__ int evb_sm[];
     const int S = c.slots, lane = threadIdx.x;
+    constexpr int A = EXT ? 7 : 6;
     int* cls = evb_sm;
     int* first = evb_sm + S;
     int* last = evb_sm + 2 * S;
     int* best = evb_sm + 3 * S;
     int* count = evb_sm + 4 * S;
     float* conf = reinterpret_cast<float*>(evb_sm + 5 * S);
+    int* deadline = evb_sm + 6 * S;                // (EXT only)
     const EvbGroup g = c.groups[blockIdx.x];
-    const size_t slab = (size_t)S * 6 + 4;
+    const size_t slab = (size_t)S * A + 4;
     const int* rd = g.rd_parity >= 0 ? c.state + ((size_t)g.source * 2 + (size_t)g.rd_parity) * slab : nullptr;
     int* wr = c.state + ((size_t)g.source * 2 + (size_t)g.wr_parity) * slab;
     for (int s = lane; s < S; s += 64) {
@@ -43,8 +54,9 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
         best[s] = rd ? rd[3 * S + s] : 0;
         count[s] = rd ? rd[4 * S + s] : 0;
         conf[s] = rd ? __int_as_float(rd[5 * S + s]) : 0.0f;
+        if (EXT) deadline[s] = rd ? rd[6 * S + s] : 0;
     }
-    int veto_win = rd ? rd[6 * S] : -1;            // the source's largest veto-hit window so far
+    int veto_win = rd ? rd[A * S] : -1;            // the source's largest veto-hit window so far
     __syncthreads();
     const u64 lt = (1ull << lane) - 1ull;
     u32 staged = 0;
@@ -57,7 +69,7 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
         for (int s0 = 0; s0 < S; s0 += 64) {
             const int s = s0 + lane;
             const bool live = s < S && cls[s] >= 0;
-            const bool due = live && (c.mode != EVB_PROCESS || (long long)first[s] + f.hold <= w + 1);
+            const bool due = live && (c.mode != EVB_PROCESS || (EXT ? (long long)deadline[s] : (long long)first[s] + f.hold) <= w + 1);
             int status = EVENT_PENDING;
             if (due && c.mode != EVB_PENDING)
                 status = count[s] < f.min_count ? EVENT_FEW : veto_win >= first[s] ? EVENT_VETOED : EVENT_KEPT;
@@ -95,6 +107,7 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
                     continue;
                 }
                 if (!(x > f.thr[ci])) continue;                        // float32, strict, false for a NaN on either side
+                const bool slides = EXT && f.slides(ci);
                 bool placed = false;
                 for (int s0 = 0; s0 < S && !placed; s0 += 64) {        // at most one live slot holds the class
                     const int s = s0 + lane;
@@ -104,6 +117,7 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
                         last[s] = w;
                         count[s] += 1;
                         if (x > conf[s]) { conf[s] = x; best[s] = w; }  // (ties: the earliest stays)
+                        if (slides) deadline[s] = evb_due(ev_deadline(first[s], w, f.hold, f.x));
                     }
                     placed = true;
                 }
@@ -113,10 +127,11 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
                     if (free_m == 0) continue;
                     if (lane == __ffsll((long long)free_m) - 1) {
                         cls[s] = ci; first[s] = w; last[s] = w; best[s] = w; count[s] = 1; conf[s] = x;
+                        if (EXT) deadline[s] = evb_due(slides ? ev_deadline(w, w, f.hold, f.x) : (long long)w + f.hold);
                     }
                     placed = true;
                 }
-                if (!placed) overflow = true;                          // (never: slots = min(k * hold, n_classes) is exact)
+                if (!placed) overflow = true;                          // (never: slots = min(k * hold or k * W, n_classes) is exact)
                 __syncthreads();
             }
             stage_due(w);
@@ -128,8 +143,9 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
             wr[3 * S + s] = best[s];
             wr[4 * S + s] = count[s];
             wr[5 * S + s] = __float_as_int(conf[s]);
+            if (EXT) wr[6 * S + s] = deadline[s];
         }
-        if (lane == 0) wr[6 * S] = veto_win;
+        if (lane == 0) wr[A * S] = veto_win;
     }
     const bool any_overflow = __ballot(overflow) != 0;
     if (lane == 0) c.counts[blockIdx.x] = any_overflow ? 0u : staged;
@@ -185,9 +201,14 @@ __global__ __launch_bounds__(256) void k_evb_emit(EvbCall c) {
 void launch_event_bank(const EvbCall& c, const EventFilterDev& f, hipStream_t s) {
     hipMemsetAsync(c.head, 0, 16, s);
     if (c.n_groups <= 0) return;
-    const int lds = c.slots * 6 * 4;
-    lds_limit_once<k_evb_update>(EVB_MAX_SLOTS * 6 * 4);
-    hipLaunchKernelGGL(k_evb_update, dim3((u32)c.n_groups), dim3(64), lds, s, c, f);
+    const int lds = c.slots * evb_arrays(c.extended) * 4;
+    if (c.extended) {
+        lds_limit_once<k_evb_update<true>>(EVB_MAX_SLOTS * 7 * 4);
+        hipLaunchKernelGGL(k_evb_update<true>, dim3((u32)c.n_groups), dim3(64), lds, s, c, f);
+    } else {
+        lds_limit_once<k_evb_update<false>>(EVB_MAX_SLOTS * 6 * 4);
+        hipLaunchKernelGGL(k_evb_update<false>, dim3((u32)c.n_groups), dim3(64), lds, s, c, f);
+    }
     hipLaunchKernelGGL(k_evb_scan, dim3(1), dim3(256), 0, s, c.counts, (u32)c.n_groups, c.head);
     hipLaunchKernelGGL(k_evb_emit, dim3((u32)c.n_groups), dim3(256), 0, s, c);
 }

@@ -68,7 +68,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_event_bank_flush", "bnhip_event_bank_reset", "bnhip_event_bank_pending", "bnhip_event_bank_clock",
            "bnhip_event_bank_destroy", "bnhip_windows_predict_events", "bnhip_capture_bank_create", "bnhip_capture_bank_info",
            "bnhip_capture_bank_positions", "bnhip_capture_bank_reset", "bnhip_capture_bank_write", "bnhip_capture_bank_read_pcm16",
-           "bnhip_capture_bank_clips", "bnhip_capture_bank_destroy", "bnhip_capture_spans"]
+           "bnhip_capture_bank_clips", "bnhip_capture_bank_destroy", "bnhip_capture_spans", "bnhip_detection_events_extended",
+           "bnhip_analyze_channels_pcm_events_extended", "bnhip_analyze_channels_pcm_clips_extended",
+           "bnhip_event_bank_create_extended", "bnhip_event_bank_set_extend", "bnhip_event_deadline"]
 
 
 class HipError(RuntimeError):
@@ -230,6 +232,11 @@ def _analyze_events_protos(lib):
     lib.bnhip_analyze_channels_pcm_events.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + tail + [C.c_void_p]
     lib.bnhip_detection_events.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int] + tail
     lib.bnhip_event_min_count.argtypes = [C.c_int, C.c_double]
+    xtail = [C.c_void_p] + tail                                                       # filter, extend, out, cap, n_out
+    lib.bnhip_analyze_channels_pcm_events_extended.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + xtail + [C.c_void_p]
+    lib.bnhip_detection_events_extended.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int] + xtail
+    lib.bnhip_event_deadline.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int64]
+    lib.bnhip_event_deadline.restype = C.c_int64
     return lib
 
 
@@ -263,14 +270,53 @@ class EventTables:
                                   self.veto_threshold, self.hold_windows, self.min_count, self.flags)
 
 
+class _EventExtendStruct(C.Structure):
+    _fields_ = [("class_extended", C.c_void_p), ("max_windows", C.c_int32), ("short_wait", C.c_int32), ("medium_from", C.c_int32),
+                ("medium_wait", C.c_int32), ("long_from", C.c_int32), ("long_wait", C.c_int32)]
+
+
+class EventExtend:
+    """Extended capture beside an EventTables (bnhip_event_extend; include/bnhip.h, "Detection events: extended capture"), in
+    windows: class_extended uint8 [n_classes] (non-zero: every hit of the class moves its event's deadline) or None for every
+    class, max_windows (an event opened at b is due at b + max_windows at the latest), short_wait, medium_from, medium_wait,
+    long_from, long_wait.  wav.ExtendedCapture builds one from species and seconds."""
+
+    def __init__(self, class_extended, max_windows, short_wait, medium_from, medium_wait, long_from, long_wait):
+        self.class_extended = None if class_extended is None else np.ascontiguousarray(class_extended, np.uint8).reshape(-1)
+        self.max_windows, self.short_wait, self.medium_from = int(max_windows), int(short_wait), int(medium_from)
+        self.medium_wait, self.long_from, self.long_wait = int(medium_wait), int(long_from), int(long_wait)
+
+    def longest_wait(self, hold_windows):
+        """W: no deadline lies further behind the hit that set it."""
+        return max(int(hold_windows), self.short_wait, self.medium_wait, self.long_wait)
+
+    def _struct(self, n_classes):
+        """-> the C struct; the table must hold n_classes entries (the array stays alive with self)."""
+        if self.class_extended is not None and self.class_extended.size != n_classes:
+            raise HipError(E_INVALID, f"the event extend's table must hold n_classes = {n_classes} entries")
+        return _EventExtendStruct(None if self.class_extended is None else self.class_extended.ctypes.data, self.max_windows, self.short_wait,
+                                  self.medium_from, self.medium_wait, self.long_from, self.long_wait)
+
+
+def event_deadline(hold_windows, extend, first_window, window):
+    """bnhip_event_deadline (host only): the deadline of an event of a sliding class opened at first_window, last hit at window."""
+    lib = _analyze_events_protos(load_library())
+    xs = extend._struct(extend.class_extended.size if extend.class_extended is not None else 0)
+    d = lib.bnhip_event_deadline(int(hold_windows), C.addressof(xs), int(first_window), int(window))
+    if d < 0:
+        _check(lib, int(d))
+    return int(d)
+
+
 def event_min_count(level, overlap_seconds):
     """bnhip_event_min_count (host only): the reference's minimum hit count of a detection for a false-positive filter level
     (0-5) at an analysis overlap in seconds."""
     return int(_analyze_events_protos(load_library()).bnhip_event_min_count(int(level), float(overlap_seconds)))
 
 
-def detection_events(rows, n_classes, filter, device=0, cap=None):
-    """bnhip_detection_events: the event tail alone over DETECTION rows the host holds (nondecreasing in (recording, window)).
+def detection_events(rows, n_classes, filter, device=0, cap=None, extend=None):
+    """bnhip_detection_events: the event tail alone over DETECTION rows the host holds (nondecreasing in (recording, window));
+    with extend (an EventExtend) bnhip_detection_events_extended.
     -> the events (EVENT), ascending by (recording, class_index, first_window); with cap -> (events[:cap], total)."""
     lib = _analyze_events_protos(load_library())
     rows = np.ascontiguousarray(rows, DETECTION).reshape(-1)
@@ -278,8 +324,13 @@ def detection_events(rows, n_classes, filter, device=0, cap=None):
     out = np.zeros(room, EVENT)
     n = C.c_size_t(0)
     fs = filter._struct(int(n_classes))
-    _check(lib, lib.bnhip_detection_events(int(device), rows.ctypes.data if rows.size else None, rows.size, int(n_classes), C.addressof(fs),
-                                           out.ctypes.data if room else None, room, C.byref(n)))
+    head = (int(device), rows.ctypes.data if rows.size else None, rows.size, int(n_classes), C.addressof(fs))
+    answer = (out.ctypes.data if room else None, room, C.byref(n))
+    if extend is None:
+        _check(lib, lib.bnhip_detection_events(*head, *answer))
+    else:
+        xs = extend._struct(int(n_classes))
+        _check(lib, lib.bnhip_detection_events_extended(*head, C.addressof(xs), *answer))
     return out[:n.value] if cap is None else (out[:min(room, n.value)], n.value)
 
 
@@ -291,6 +342,8 @@ def _event_bank_protos(lib):
     lib.bnhip_event_bank_create.argtypes = [ci, ci, ci, ci, vp, C.POINTER(vp)]
     lib.bnhip_event_bank_info.argtypes = [vp] + [C.POINTER(ci)] * 5
     lib.bnhip_event_bank_set_filter.argtypes = [vp, vp]
+    lib.bnhip_event_bank_create_extended.argtypes = [ci, ci, ci, ci, vp, vp, C.POINTER(vp)]
+    lib.bnhip_event_bank_set_extend.argtypes = [vp, vp]
     lib.bnhip_event_bank_process.argtypes = [vp, vp, ci, vp, vp] + answer
     lib.bnhip_event_bank_process_device.argtypes = [vp, vp, ci, vp, vp] + answer + [vp]
     lib.bnhip_event_bank_flush.argtypes = [vp, ci] + answer
@@ -312,18 +365,27 @@ class EventBank:
     (row r is the next window of sources[r]; a source < 0 skips the row) and returns the events (EVENT) that became due, ascending by
     (source, class_index, first_window).  `flush(source=-1)` answers the live events as if the streams had ended, `reset(source=-1)`
     drops them and zeroes the clock, `pending()` lists them with status EVENT_PENDING.  filter: an EventTables; k and its
-    hold_windows are fixed for the bank's life.  A call that fails changes no source.  cap: None = whatever the call answers (a
-    call refused for room is repeated with the room it named); a number = that room, and HipError with `.needed` beyond it."""
+    hold_windows are fixed for the bank's life.  extend (an EventExtend): the bank is created extended
+    (bnhip_event_bank_create_extended) - the hits of its sliding classes move their events' deadlines; `set_extend(extend | None)`
+    then changes the table and the numbers, within the longest wait the bank was created with.  A call that fails changes no
+    source.  cap: None = whatever the call answers (a call refused for room is repeated with the room it named); a number = that
+    room, and HipError with `.needed` beyond it."""
 
     ROOM = 256
 
-    def __init__(self, n_classes, k, filter, max_sources=256, device=0):
+    def __init__(self, n_classes, k, filter, max_sources=256, device=0, extend=None):
         lib = self._lib = _event_bank_protos(load_library())
         self._h = None
         self.n_classes, self.k, self.max_sources, self.device = int(n_classes), int(k), int(max_sources), int(device)
+        self.extended = extend is not None
         fs = filter._struct(self.n_classes)
         h = C.c_void_p()
-        _check(lib, lib.bnhip_event_bank_create(self.device, self.max_sources, self.n_classes, self.k, C.addressof(fs), C.byref(h)))
+        if extend is None:
+            _check(lib, lib.bnhip_event_bank_create(self.device, self.max_sources, self.n_classes, self.k, C.addressof(fs), C.byref(h)))
+        else:
+            xs = extend._struct(self.n_classes)
+            _check(lib, lib.bnhip_event_bank_create_extended(self.device, self.max_sources, self.n_classes, self.k, C.addressof(fs), C.addressof(xs),
+                                                             C.byref(h)))
         self._h = h
         v = [C.c_int() for _ in range(5)]
         _check(lib, lib.bnhip_event_bank_info(h, *[C.byref(x) for x in v]))
@@ -381,6 +443,11 @@ class EventBank:
         fs = filter._struct(self.n_classes)
         _check(self._lib, self._lib.bnhip_event_bank_set_filter(self._alive(), C.addressof(fs)))
 
+    def set_extend(self, extend):
+        """bnhip_event_bank_set_extend: a new EventExtend from the next call on; None turns sliding off."""
+        xs = None if extend is None else extend._struct(self.n_classes)
+        _check(self._lib, self._lib.bnhip_event_bank_set_extend(self._alive(), None if xs is None else C.addressof(xs)))
+
     def clock(self, source):
         w = C.c_int64(0)
         _check(self._lib, self._lib.bnhip_event_bank_clock(self._alive(), int(source), C.byref(w)))
@@ -404,6 +471,7 @@ def _analyze_clips_protos(lib):
     lib.bnhip_event_clip_spans.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.bnhip_recording_clips_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.bnhip_analyze_channels_pcm_clips.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bnhip_analyze_channels_pcm_clips_extended.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + [C.c_void_p] * 5
     return lib
 
 
@@ -719,12 +787,15 @@ def _rows_answer(threshold, cap):
     return answer
 
 
-def _events_answer(filter, cap, n_classes):
+def _events_answer(filter, cap, n_classes, extend=None):
+    """extend (an EventExtend): the _events_extended entry, which only the channels form has."""
     def answer(lib, kk, first, room):
         _analyze_events_protos(lib)
         first()                                         # (a bad table is answered as the windows entry answers it, before the filter)
         out, n, fs = np.zeros(room(cap), EVENT), C.c_size_t(0), filter._struct(n_classes)
-        return "_events", (C.byref(fs), out.ctypes.data if out.size else None, out.size, C.byref(n)), \
+        xs = None if extend is None else extend._struct(n_classes)
+        return "_events" if xs is None else "_events_extended", \
+            (C.byref(fs),) + (() if xs is None else (C.byref(xs),)) + (out.ctypes.data if out.size else None, out.size, C.byref(n)), \
             lambda: (out[:n.value],) if cap is None else (out[:min(out.size, n.value)], n.value)
     return answer
 
@@ -996,14 +1067,17 @@ class HipClassifier:
         """bnhip_analyze_mixed_pcm_events: analyze_mixed_pcm answered as detection events, as analyze_pcm_events answers."""
         return self._analyze(_mixed_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes), hop, min_tail, k, activation, sensitivity)
 
-    def analyze_channels_pcm_events(self, raw, recs, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
-        """bnhip_analyze_channels_pcm_events: analyze_channels_pcm answered as detection events.  -> (events, chosen); with cap ->
-        (events[:cap], total, chosen)."""
-        return self._analyze(_channels_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes), hop, min_tail, k, activation, sensitivity)
+    def analyze_channels_pcm_events(self, raw, recs, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None,
+                                    extend=None):
+        """bnhip_analyze_channels_pcm_events: analyze_channels_pcm answered as detection events; with extend (an EventExtend)
+        bnhip_analyze_channels_pcm_events_extended.  -> (events, chosen); with cap -> (events[:cap], total, chosen)."""
+        return self._analyze(_channels_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes, extend), hop, min_tail, k,
+                             activation, sensitivity)
 
     def analyze_channels_pcm_clips(self, raw, recs, model_rate, hop, filter, settings, min_tail=0, k=10, activation=0, sensitivity=1.0,
-                                   event_cap=None, max_clips=None, flac_cap=None, png_cap=None):
-        """bnhip_analyze_channels_pcm_clips: analyze_channels_pcm_events, and in the same call the clip of every event written - cut
+                                   event_cap=None, max_clips=None, flac_cap=None, png_cap=None, extend=None):
+        """bnhip_analyze_channels_pcm_clips (with extend, an EventExtend: bnhip_analyze_channels_pcm_clips_extended):
+        analyze_channels_pcm_events, and in the same call the clip of every event written - cut
         out of the recordings on the device, normalised, FLAC-encoded and (with settings.width) rendered to a PNG - under `settings`
         (a ClipSettings).  Room: event_cap events (default: every row), and for the streams flac_cap / png_cap bytes (default: the
         bounds of max_clips clips of the longest span the settings allow; max_clips defaults to min(event_cap, 65535)).  Clips are
@@ -1030,9 +1104,13 @@ class HipClassifier:
         fs, xs = filter._struct(self._n_classes), settings._struct()
         o = _ClipsOutStruct(events.ctypes.data, room, 0, spans.ctypes.data, C.addressof(loud), flac.ctypes.data, int(flac_cap), flac_off.ctypes.data,
                             png.ctypes.data, int(png_cap), png_off.ctypes.data, 0)
-        _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips(self._h, form.x.ctypes.data, *form.args, int(hop), int(min_tail), activation,
-                                                                     sensitivity, k, C.addressof(fs), chosen.ctypes.data, C.addressof(xs),
-                                                                     C.addressof(o)))
+        head = (self._h, form.x.ctypes.data, *form.args, int(hop), int(min_tail), activation, sensitivity, k, C.addressof(fs))
+        if extend is None:
+            _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips(*head, chosen.ctypes.data, C.addressof(xs), C.addressof(o)))
+        else:
+            es = extend._struct(self._n_classes)
+            _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips_extended(*head, C.addressof(es), chosen.ctypes.data, C.addressof(xs),
+                                                                                  C.addressof(o)))
         n_ev, n = min(room, o.n_events), int(o.n_clips)
         res = ClipsResult(events[:n_ev], int(o.n_events), spans[:n_ev], list(loud[:n]) if settings.normalize else None,
                           _flac_streams(flac, flac_off[:n + 1]) if n else [],

@@ -618,7 +618,10 @@ def process_data(orch, data, start_time, captured_at, source, model_id, queue, o
 class CaptureSettings:
     """WindowBatcher(capture=...): every source's last `seconds` of audio stay on the device (one host.CaptureBank per model, at
     the model's rate, max_sources rings: max_sources * seconds * rate * 2 bytes) and every approved detection event is answered with
-    its clip, cut, normalised, FLAC-encoded and rendered there under `export` (a wav.ClipExport)."""
+    its clip, cut, normalised, FLAC-encoded and rendered there under `export` (a wav.ClipExport).  Under extended capture
+    (WindowBatcher(extend=...), export.extended) an event is answered only once its deadline has passed, up to the extend's
+    max_seconds behind its first hit: `seconds` must then hold max_seconds plus the pre-capture (and the ticks until the export),
+    or the head of a long event has left the ring by the time it is due and the event is reported without a clip."""
     seconds: float
     export: object
     max_sources: int = 256
@@ -659,16 +662,23 @@ class WindowBatcher:
     CaptureSettings; native rings, with events) the bytes that reach a source's ring are also staged for the model's
     host.CaptureBank: a tick uploads them in one write call before the model call, and the events that became due are answered
     with their clips in one export call (take_clips, on_clips).  An event whose clip ends behind what has been written is kept and
-    tried again on later ticks, never cut short; one whose audio has left the ring is reported without a clip."""
+    tried again on later ticks, never cut short; one whose audio has left the ring is reported without a clip.
+
+    `extend=` (a host.EventExtend; native rings, with events) creates every model's event bank extended: the hits of the chosen classes move their
+    events' deadlines (include/bnhip.h, "Detection events: extended capture"), so a bird that keeps calling is one long event.  With
+    `capture=` and an export with extended=True such an event's clip runs from its first hit to its last; the retry above waits for
+    the audio behind the last hit."""
 
     BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
     EVENT_SOURCES = 1024                     # native: sources of a model's event bank (assembler slots are reused)
 
     def __init__(self, orch: Orchestrator, queue: _results.ResultsQueue = None, overruns: OverrunTrackers = None,
                  max_batch=256, pre_capture_s=0.0, bit_depth=16, clock=time.time, on_error=None, native=True, events=None,
-                 on_events=None, capture=None, on_clips=None):
+                 on_events=None, capture=None, on_clips=None, extend=None):
         if capture is not None and (events is None or not native):
             raise StreamError("capture needs events and the native rings")
+        if extend is not None and (events is None or not native):
+            raise StreamError("extend needs events and the native rings")
         self.orch = orch
         self.queue = queue if queue is not None else _results.ResultsQueue()
         self.overruns = overruns if overruns is not None else OverrunTrackers()
@@ -691,6 +701,7 @@ class WindowBatcher:
         self.sl_pending = {}                 # native: source rate -> [(source, stream, pcm bytes)] until the next tick
         self.sl_reports = []                 # finished reports until take_sound_levels()
         self.events = events                 # native: a host.EventTables -> detection events beside the Results (None: none)
+        self.extend = extend                 # native: a host.EventExtend -> the models' event banks are created extended (None: not)
         self.on_events = on_events
         self.event_banks = {}                # native: model_id -> host.EventBank over that model's assembler sources
         self.event_reports = []              # the ticks' events until take_events()
@@ -889,7 +900,7 @@ class WindowBatcher:
         bank = self.event_banks.get(model_id)
         if bank is None:
             n_classes = len(inst.labels)
-            bank = _host.EventBank(n_classes, min(getattr(inst, "TOP_K", 10), n_classes), self.events, self.EVENT_SOURCES)
+            bank = _host.EventBank(n_classes, min(getattr(inst, "TOP_K", 10), n_classes), self.events, self.EVENT_SOURCES, extend=self.extend)
             with self.mu:
                 self.event_banks[model_id] = bank
         return bank

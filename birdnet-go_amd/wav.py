@@ -221,6 +221,35 @@ class EventFilter:
                                 host.EVENTS_KEEP_DROPPED if self.keep_dropped else 0)
 
 
+class ExtendedCapture:
+    """The reference's extended capture for analyze_files(events=..., extend=...) and stream.WindowBatcher(events=..., extend=...)
+    (include/bnhip.h, "Detection events: extended capture"): every new hit of an event of the chosen species moves the event's
+    deadline - short_wait_seconds (or the filter's hold, if longer) behind the hit while the event is younger than
+    medium_after_seconds, medium_wait_seconds while it is younger than long_after_seconds, long_wait_seconds after that - and
+    max_seconds behind the event's first hit is the latest.  species: None for every class, or class indices."""
+
+    def __init__(self, species=None, max_seconds=None, short_wait_seconds=15.0, medium_after_seconds=30.0, medium_wait_seconds=30.0,
+                 long_after_seconds=120.0, long_wait_seconds=60.0):
+        if max_seconds is None:
+            raise ValueError("extended capture needs max_seconds")
+        self.species = None if species is None else list(species)
+        self.max_seconds, self.short_wait_seconds = float(max_seconds), float(short_wait_seconds)
+        self.medium_after_seconds, self.medium_wait_seconds = float(medium_after_seconds), float(medium_wait_seconds)
+        self.long_after_seconds, self.long_wait_seconds = float(long_after_seconds), float(long_wait_seconds)
+
+    def tables(self, n_classes, model_rate, hop):
+        """-> the host.EventExtend for a model of n_classes classes analysed at `hop` samples of model_rate: seconds become windows
+        as EventFilter.hold_windows makes them, with a ceiling."""
+        from . import host
+        table = None
+        if self.species is not None:
+            table = np.zeros(n_classes, np.uint8)
+            table[self.species] = 1
+        w = lambda seconds: max(1, int(math.ceil(seconds * model_rate / hop)))
+        return host.EventExtend(table, w(self.max_seconds), w(self.short_wait_seconds), w(self.medium_after_seconds), w(self.medium_wait_seconds),
+                                w(self.long_after_seconds), w(self.long_wait_seconds))
+
+
 class ClipExport:
     """What analyze_files(events=..., export=...) saves of every detection event, as the reference does for an approved detection
     (include/bnhip.h, "Detection clips"): the clip from pre_capture_seconds before the event's first window to length_seconds -
@@ -264,7 +293,7 @@ def clip_spans(events, resampled_length, hop, export, model_rate=48000):
 
 
 def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
-                  device=0, device_resample=False, channels=None, return_chosen=False, events=None, export=None):
+                  device=0, device_resample=False, channels=None, return_chosen=False, events=None, export=None, extend=None):
     """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
     path, each what analyze_file returns for that file.  The files' PCM bytes are sent as they are when all of them are at the
     model's rate and share one bit depth; otherwise every file goes as float32 (converted, and resampled where its rate differs,
@@ -287,15 +316,22 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     export (a ClipExport, with events; keep_dropped is refused): the same call also makes every event's clip on the device
     (`bnhip_analyze_channels_pcm_clips`: every file's frames go up interleaved as they are - channels=None reads channel 0 there).
     Each tuple is followed by the clip's start and length in samples at model_rate, its FLAC bytes, its loudness record
-    (host.Loudness, None without normalize) and its PNG bytes or None; an event behind the export's max_clips has None for all three."""
+    (host.Loudness, None without normalize) and its PNG bytes or None; an event behind the export's max_clips has None for all three.
+
+    extend (an ExtendedCapture, with events): the events of its species last as long as the bird kept calling
+    (`bnhip_analyze_channels_pcm_events_extended`, `bnhip_analyze_channels_pcm_clips_extended`); the call takes the channels route, as
+    with export, and an export with extended=True then cuts every clip to its event's last hit."""
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
     if return_chosen and channels is None:
         raise ValueError("return_chosen needs channels")
     if export is not None and (events is None or events.keep_dropped):
         raise ValueError("export needs events, without keep_dropped")
+    if extend is not None and events is None:
+        raise ValueError("extend needs events")
     recs = crecs = None
-    select = 0 if channels is None and export is not None else channels      # (the export takes the files' frames: channel 0 is read there)
+    # (the export and the extend take the files' frames: channel 0 is read there)
+    select = 0 if channels is None and (export is not None or extend is not None) else channels
     if select is None:
         pcm = [read_wav_pcm(p) for p in paths]
         depths = {bits for _, _, bits in pcm}
@@ -335,13 +371,15 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
         t32 = np.nextafter(t32, np.float32(np.inf))
     if events is not None:
         flt = events.tables(classifier.num_species(),model_rate, hop, overlap_seconds)
+        ext = None if extend is None else extend.tables(classifier.num_species(), model_rate, hop)
         chosen = clips = None
         if export is not None:
             clips = classifier.analyze_channels_pcm_clips(b"".join(bufs), crecs, model_rate, hop, flt, export.settings(model_rate), min_tail,
-                                                          k=top_k, sensitivity=sensitivity, max_clips=export.max_clips)
+                                                          k=top_k, sensitivity=sensitivity, max_clips=export.max_clips, extend=ext)
             ev, chosen = clips.events, ["mix" if s < 0 else int(s) for s in clips.chosen]
         elif crecs is not None:
-            ev, sel = classifier.analyze_channels_pcm_events(b"".join(bufs), crecs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)
+            ev, sel = classifier.analyze_channels_pcm_events(b"".join(bufs), crecs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity,
+                                                             extend=ext)
             chosen = ["mix" if s < 0 else int(s) for s in sel]
         elif recs is not None:
             ev = classifier.analyze_mixed_pcm_events(b"".join(bufs), recs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)

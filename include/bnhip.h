@@ -344,7 +344,7 @@ int bnhip_channel_energy_pcm(int device, const void* pcm, const bnhip_channels_r
  *   events   The hits of one (r, c), by window (equal windows in row order; a row given twice is two hits).  The first opens an event
  *            at b = w; every following hit with w < b + hold_windows joins it; the first with w >= b + hold_windows opens the next
  *            event at its own window (FlushDeadline = created + detectionWindow: the hold is fixed from the first hit and does not
- *            slide).  first_window = b, last_window = the last hit that joined, count = the hits, confidence = the largest, best_window
+ *            slide; extended capture, where it does: "Detection events: extended capture" below).  first_window = b, last_window = the last hit that joined, count = the hits, confidence = the largest, best_window
  *            = the window of the largest (ties: the earliest).
  *   status   1 when count < min_count; else 2 when recording r has a veto hit at a window v with b <= v < b + hold_windows; else 0.
  *            Without BNHIP_EVENTS_KEEP_DROPPED in flags only status-0 events are answered; with it all are, each with its status.
@@ -452,6 +452,57 @@ int bnhip_windows_predict_events(bnhip_windows* w, bnhip_model* m, bnhip_event_b
                                  double sensitivity, int k, int* sources, int* n_windows, float* out_conf, int32_t* out_idx,
                                  const void** batch, bnhip_event* events, size_t cap, size_t* n_events);
 
+/* Detection events: extended capture.  For the species chosen for it the reference lets every new hit of a pending detection move
+ * its flush deadline (applyExtendedCapture and calculateExtendedFlushDeadline, internal/analysis/processor/extended_capture.go:282-329,
+ * applied at processor.go:788-790): now + max(normal window, 15 s) while the session is under 30 s, now + 30 s while it is under
+ * 2 min, now + 60 s after that, capped at FirstDetected + MaxDuration - a detection is then as long as the bird kept calling.  Both
+ * rules above take it as one more struct; the clock stays audio time in windows, and the host turns the reference's seconds into
+ * windows as it does for hold_windows, with a ceiling.
+ *   deadline An event opened at window b carries a deadline d.  class_extended[c] == 0: d = b + hold_windows, set once - the rule
+ *            above.  Otherwise (class_extended NULL: every class) every hit of the event at window w, the one that opens it too, sets
+ *            d = min(w + wait(w - b), b + max_windows), with wait(t) = max(hold_windows, short_wait) for t < medium_from,
+ *            medium_wait for medium_from <= t < long_from, long_wait for t >= long_from.  The last hit's deadline stands (the
+ *            reference overwrites FlushDeadline the same way), so a deadline may also move earlier; it is never before w + 1.
+ *   events   A hit at window w joins the live event of its (recording or source, class) while w < d; a hit at w >= d opens the next
+ *            event at its own window; equal windows join in row order.  In the bank an event is due after window w' once d <= w' + 1:
+ *            answered, its slot freed, before window w' + 1 is applied.
+ *   status   1 when count < min_count; else 2 for a veto hit at a window v with b <= v < d, d the event's final deadline (in the
+ *            bank still "the largest veto-hit window so far is >= b" at the flush); else 0.
+ *   slots    While window w is applied every live event has d >= w + 1 and d <= its last hit + W, W = max(hold_windows, short_wait,
+ *            medium_wait, long_wait): its last hit lies in [w - W + 1, w], and a window brings at most k hits.  So slots_per_source =
+ *            min(k * W, n_classes) is exact, by the argument of "slots" above; bnhip_event_bank_info reports it.
+ *   bnhip_detection_events_extended, bnhip_analyze_channels_pcm_events_extended, bnhip_analyze_channels_pcm_clips_extended (below)
+ *            Their namesakes with the extend behind the filter.  class_extended all zero answers the namesake's bytes.  With
+ *            bnhip_clip_export.extended a clip then runs to the last hit of an event that may be max_windows long.
+ *   bnhip_event_bank_create_extended  bnhip_event_bank_create with the extend: the bank's slots carry their deadlines, and W is
+ *            fixed for the bank's life.  process, process_device, flush, pending, reset, clock, set_filter and
+ *            bnhip_windows_predict_events take such a bank unchanged.  The rows of a recording fed and then flushed answer exactly
+ *            bnhip_detection_events_extended of those rows.
+ *   bnhip_event_bank_set_extend  A new table and new numbers from the next call on; a live event keeps its deadline until its next
+ *            hit.  NULL turns sliding off (every event opened from then on is held hold_windows).  Refused: a W above the bank's
+ *            own, and a bank created without an extend.
+ *   bnhip_event_deadline  Host only: d of an event of a sliding class opened at first_window and last hit at window.
+ * BNHIP_E_INVALID (before any device call): what the namesake refuses, a NULL extend (but for set_extend), max_windows <
+ * hold_windows, a wait below 1, medium_from < 1, long_from < medium_from, k * W > 4096; for bnhip_event_deadline hold_windows < 1,
+ * a negative first_window and window < first_window (it answers the negative code). */
+typedef struct bnhip_event_extend {
+    const uint8_t* class_extended;     /* [n_classes], non-zero: the class slides; NULL: every class does */
+    int32_t max_windows;               /* MaxDuration: an event opened at b is due at b + max_windows at the latest */
+    int32_t short_wait;                /* 15 s */
+    int32_t medium_from, medium_wait;  /* 30 s, 30 s */
+    int32_t long_from, long_wait;      /* 2 min, 60 s */
+} bnhip_event_extend;
+int bnhip_detection_events_extended(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                                    const bnhip_event_extend* extend, bnhip_event* out, size_t cap, size_t* n_out);
+int bnhip_analyze_channels_pcm_events_extended(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                               int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                               const bnhip_event_filter* filter, const bnhip_event_extend* extend, bnhip_event* out,
+                                               size_t cap, size_t* n_out, int32_t* chosen);
+int bnhip_event_bank_create_extended(int device, int max_sources, int n_classes, int k, const bnhip_event_filter* filter,
+                                     const bnhip_event_extend* extend, bnhip_event_bank** out);
+int bnhip_event_bank_set_extend(bnhip_event_bank* b, const bnhip_event_extend* extend);
+int64_t bnhip_event_deadline(int32_t hold_windows, const bnhip_event_extend* extend, int64_t first_window, int64_t window);
+
 /* Detection clips: what the reference saves for every approved detection, made from the recordings of a file-analysis call while
  * they are still on the device.  Its processor takes the audio from BeginTime back by the pre-capture to the end of the capture
  * window, or under extended capture to as long as the bird kept calling (internal/analysis/processor/extended_capture.go:232-280,
@@ -520,6 +571,11 @@ int bnhip_analyze_channels_pcm_clips(bnhip_model* m, const void* pcm, const bnhi
                                      int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
                                      const bnhip_event_filter* filter, int32_t* chosen, const bnhip_clip_export* x,
                                      bnhip_clips_out* out);
+/* ... under extended capture ("Detection events: extended capture") */
+int bnhip_analyze_channels_pcm_clips_extended(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                              int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                              const bnhip_event_filter* filter, const bnhip_event_extend* extend, int32_t* chosen,
+                                              const bnhip_clip_export* x, bnhip_clips_out* out);
 
 /* Capture bank: the real-time path's detection clips.  The reference keeps a CaptureBuffer per source - a circular PCM buffer with a
  * monotonic byte counter, from which ReadSegment cuts a detection's audio (internal/audiocore/buffer/capture.go:60-112, 132-179,
