@@ -196,10 +196,114 @@ __global__ __launch_bounds__(256) void k_evb_emit(EvbCall c) {
     }
 }
 
-}  // namespace
+// ---- dynamic thresholds (events_bank.h): the per-class passes around the launches above
 
-void launch_event_bank(const EvbCall& c, const EventFilterDev& f, hipStream_t s) {
-    hipMemsetAsync(c.head, 0, 16, s);
+// the change flags of a class: bits 0-1 the level an expiry took away (0: none), bit 2 a learning changed the level, bits 3-4 from,
+// bits 5-6 to
+__device__ __forceinline__ u32 evd_records_of(u32 flags) { return ((flags & 3u) ? 1u : 0u) + ((flags >> 2) & 1u); }
+
+__global__ __launch_bounds__(256) void k_evd_prepare(EvdCall d) {
+    const int c = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (c >= d.n_classes) return;
+    const EvdSlab rd = evd_slab(d.area, d.n_classes, d.rd_parity), wr = evd_slab(d.area, d.n_classes, d.rd_parity ^ 1);
+    int L = rd.level[c], n = rd.count[c];
+    long long A = rd.learned_at[c];
+    const long long E = rd.expires[c];
+    const bool dyn = d.dynamic[c] != 0;
+    u32 flags = 0;
+    if (dyn && n > 0 && d.now > E) {               // (strict: now.After(Timer))
+        flags = (u32)L;
+        L = 0; n = 0; A = -1;
+    }
+    wr.level[c] = L; wr.count[c] = n; wr.expires[c] = E; wr.learned_at[c] = A;
+    d.thr_eff()[c] = dyn ? ev_threshold(d.base[c], L, d.min_threshold) : d.base[c];
+    d.touch()[c] = 0u; d.best()[c] = 0u; d.flags()[c] = flags;
+}
+
+// blocks [0, n_groups): the source's staged events that were approved; the blocks behind them: the results of the call's rows
+__global__ __launch_bounds__(256) void k_evd_mark(EvbCall c, EventFilterDev f, EvdCall d) {
+    const u32 tid = threadIdx.x, G = (u32)c.n_groups;
+    if (blockIdx.x < G) {
+        const EvbGroup g = c.groups[blockIdx.x];
+        const u32 n = min(c.counts[blockIdx.x], g.stage_cap);
+        const Event* stage = c.stage + g.stage_off;
+        for (u32 i = tid; i < n; i += 256) {
+            const Event e = stage[i];
+            if (e.status != EVENT_KEPT || (u32)e.cls >= (u32)d.n_classes || d.dynamic[e.cls] == 0) continue;
+            // above the trigger the confidence is positive, so its bits order as it does
+            if (e.confidence > d.trigger && e.confidence >= d.base[e.cls]) atomicMax(&d.best()[e.cls], __float_as_uint(e.confidence));
+        }
+        return;
+    }
+    const u64 i = (u64)(blockIdx.x - G) * 256u + tid;
+    if (i >= (u64)d.n_rows * (u64)c.k) return;
+    const size_t at = (size_t)c.rowmap[i / (u32)c.k] * (size_t)c.k + (size_t)(i % (u32)c.k);
+    const float x = c.conf[at];
+    const int ci = c.idx[at];
+    if ((u32)ci >= (u32)d.n_classes || f.veto[ci] != 0 || d.dynamic[ci] == 0) return;
+    if (evd_slab(d.area, d.n_classes, d.rd_parity ^ 1).count[ci] > 0 && x > f.thr[ci] && x > d.base[ci]) d.touch()[ci] = 1u;
+}
+
+__global__ __launch_bounds__(256) void k_evd_apply(EvdCall d, u64* __restrict__ head) {
+    const int c = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (c >= d.n_classes || d.dynamic[c] == 0) return;
+    const EvdSlab wr = evd_slab(d.area, d.n_classes, d.rd_parity ^ 1);
+    u32 flags = d.flags()[c];
+    const u32 best = d.best()[c];
+    if (d.touch()[c] != 0u || best != 0u) wr.expires[c] = d.now + d.valid;
+    if (best != 0u) {
+        const long long A = wr.learned_at[c];
+        if (A < 0 || d.now - A >= d.cooldown) {
+            const int L = wr.level[c], n0 = wr.count[c], n = n0 == INT_MAX ? n0 : n0 + 1, L2 = min(n, 3);
+            wr.count[c] = n; wr.level[c] = L2; wr.learned_at[c] = d.now;
+            if (L2 != L) flags |= 4u | ((u32)L << 3) | ((u32)L2 << 5);
+        }
+    }
+    d.flags()[c] = flags;
+    const u32 nrec = evd_records_of(flags);
+    if (nrec) atomicAdd(reinterpret_cast<u32*>(head) + 3, nrec);           // (the upper half of head[1]; the sum needs no order)
+}
+
+// The records, classes ascending and an expiry before a learning, 256 classes at a time with a running carry (k_evb_scan's walk).
+// Changes are rare: the block leaves at once when k_evd_apply counted none.
+__global__ __launch_bounds__(256) void k_evd_changes(EvdCall d, const u64* __restrict__ head) {
+    __shared__ u32 sh[256];
+    if ((head[1] >> 32) == 0ull) return;
+    u32 carry = 0;
+    for (int c0 = 0; c0 < d.n_classes; c0 += 256) {
+        const int c = c0 + (int)threadIdx.x;
+        const u32 flags = c < d.n_classes ? d.flags()[c] : 0u;
+        const u32 v = evd_records_of(flags);
+        const u32 incl = block_scan(v, sh, (int)threadIdx.x);
+        u32 pos = carry + incl - v;
+        if (v) {
+            const float base = d.base[c];
+            ThresholdChange r{};
+            r.cls = c;
+            if (flags & 3u) {
+                r.previous_level = (int)(flags & 3u); r.new_level = 0; r.reason = EVD_EXPIRY;
+                r.previous_value = ev_threshold(base, r.previous_level, d.min_threshold); r.new_value = base; r.confidence = 0.0f;
+                d.records()[pos] = r;
+                if (pos < (u32)EVD_FIRST_CHANGES) d.first[pos] = r;
+                pos++;
+            }
+            if (flags & 4u) {
+                r.previous_level = (int)((flags >> 3) & 3u); r.new_level = (int)((flags >> 5) & 3u); r.reason = EVD_HIGH_CONFIDENCE;
+                r.previous_value = ev_threshold(base, r.previous_level, d.min_threshold);
+                r.new_value = ev_threshold(base, r.new_level, d.min_threshold);
+                r.confidence = __uint_as_float(d.best()[c]);
+                d.records()[pos] = r;
+                if (pos < (u32)EVD_FIRST_CHANGES) d.first[pos] = r;
+            }
+        }
+        const u32 sum = sh[255];
+        __syncthreads();                          // (sh is written again by the next round's scan)
+        carry += sum;
+    }
+}
+
+// update, scan, emit: the launches of every call that has a source in it
+void evb_launch_core(const EvbCall& c, const EventFilterDev& f, hipStream_t s) {
     if (c.n_groups <= 0) return;
     const int lds = c.slots * evb_arrays(c.extended) * 4;
     if (c.extended) {
@@ -211,6 +315,24 @@ void launch_event_bank(const EvbCall& c, const EventFilterDev& f, hipStream_t s)
     }
     hipLaunchKernelGGL(k_evb_scan, dim3(1), dim3(256), 0, s, c.counts, (u32)c.n_groups, c.head);
     hipLaunchKernelGGL(k_evb_emit, dim3((u32)c.n_groups), dim3(256), 0, s, c);
+}
+
+}  // namespace
+
+void launch_event_bank(const EvbCall& c, const EventFilterDev& f, hipStream_t s, const EvdCall* d) {
+    hipMemsetAsync(c.head, 0, 16, s);
+    if (d) {
+        const u32 cb = ((u32)d->n_classes + 255u) / 256u;
+        hipLaunchKernelGGL(k_evd_prepare, dim3(cb), dim3(256), 0, s, *d);
+        evb_launch_core(c, f, s);
+        const u64 results = (u64)d->n_rows * (u64)c.k;
+        const u32 mb = (u32)max(c.n_groups, 0) + (u32)((results + 255u) / 256u);
+        if (mb) hipLaunchKernelGGL(k_evd_mark, dim3(mb), dim3(256), 0, s, c, f, *d);
+        hipLaunchKernelGGL(k_evd_apply, dim3(cb), dim3(256), 0, s, *d, c.head);
+        hipLaunchKernelGGL(k_evd_changes, dim3(1), dim3(256), 0, s, *d, (const u64*)c.head);
+        return;
+    }
+    evb_launch_core(c, f, s);
 }
 
 }  // namespace bnhip

@@ -70,7 +70,10 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_capture_bank_positions", "bnhip_capture_bank_reset", "bnhip_capture_bank_write", "bnhip_capture_bank_read_pcm16",
            "bnhip_capture_bank_clips", "bnhip_capture_bank_destroy", "bnhip_capture_spans", "bnhip_detection_events_extended",
            "bnhip_analyze_channels_pcm_events_extended", "bnhip_analyze_channels_pcm_clips_extended",
-           "bnhip_event_bank_create_extended", "bnhip_event_bank_set_extend", "bnhip_event_deadline"]
+           "bnhip_event_bank_create_extended", "bnhip_event_bank_set_extend", "bnhip_event_deadline",
+           "bnhip_event_bank_create_dynamic", "bnhip_event_bank_set_dynamic", "bnhip_event_bank_set_now",
+           "bnhip_event_bank_threshold_changes", "bnhip_event_bank_thresholds", "bnhip_event_bank_set_thresholds",
+           "bnhip_event_bank_reset_thresholds", "bnhip_event_threshold"]
 
 
 class HipError(RuntimeError):
@@ -298,6 +301,40 @@ class EventExtend:
                                   self.medium_from, self.medium_wait, self.long_from, self.long_wait)
 
 
+class _EventDynamicStruct(C.Structure):
+    _fields_ = [("class_dynamic", C.c_void_p), ("trigger", C.c_float), ("min_threshold", C.c_float), ("valid", C.c_int64),
+                ("cooldown", C.c_int64)]
+
+
+# one record of EventBank.threshold_changes (bnhip_threshold_change)
+THRESHOLD_CHANGE = np.dtype([("class_index", "<i4"), ("previous_level", "<i4"), ("new_level", "<i4"), ("reason", "<i4"),
+                             ("previous_value", "<f4"), ("new_value", "<f4"), ("confidence", "<f4"), ("pad", "<i4")])
+THRESHOLD_EXPIRY, THRESHOLD_HIGH_CONFIDENCE = 0, 1
+
+
+class EventDynamic:
+    """Dynamic thresholds beside an EventTables (bnhip_event_dynamic; include/bnhip.h, "Detection events: dynamic thresholds"):
+    class_dynamic uint8 [n_classes] (non-zero: the class learns; zero: a species with a custom threshold) or None for every class,
+    trigger, min_threshold, and valid and cooldown in bank time (the unit of EventBank.set_now)."""
+
+    def __init__(self, class_dynamic, trigger, min_threshold, valid, cooldown):
+        self.class_dynamic = None if class_dynamic is None else np.ascontiguousarray(class_dynamic, np.uint8).reshape(-1)
+        self.trigger, self.min_threshold, self.valid, self.cooldown = float(trigger), float(min_threshold), int(valid), int(cooldown)
+
+    def _struct(self, n_classes):
+        """-> the C struct; the table must hold n_classes entries (the array stays alive with self)."""
+        if self.class_dynamic is not None and self.class_dynamic.size != n_classes:
+            raise HipError(E_INVALID, f"the event dynamic's table must hold n_classes = {n_classes} entries")
+        return _EventDynamicStruct(None if self.class_dynamic is None else self.class_dynamic.ctypes.data, self.trigger, self.min_threshold,
+                                   self.valid, self.cooldown)
+
+
+def event_threshold(base, level, min_threshold):
+    """bnhip_event_threshold (host only): the effective threshold of a base at a level (float32)."""
+    lib = _event_bank_protos(load_library())
+    return np.float32(lib.bnhip_event_threshold(float(np.float32(base)), int(level), float(np.float32(min_threshold))))
+
+
 def event_deadline(hold_windows, extend, first_window, window):
     """bnhip_event_deadline (host only): the deadline of an event of a sliding class opened at first_window, last hit at window."""
     lib = _analyze_events_protos(load_library())
@@ -353,6 +390,15 @@ def _event_bank_protos(lib):
     lib.bnhip_event_bank_destroy.argtypes = [vp]
     lib.bnhip_event_bank_destroy.restype = None
     lib.bnhip_windows_predict_events.argtypes = [vp, vp, vp, ci, ci, C.c_double, ci, C.POINTER(ci), C.POINTER(ci), vp, vp, C.POINTER(vp)] + answer
+    lib.bnhip_event_bank_create_dynamic.argtypes = [ci, ci, ci, ci, vp, vp, vp, C.POINTER(vp)]
+    lib.bnhip_event_bank_set_dynamic.argtypes = [vp, vp]
+    lib.bnhip_event_bank_set_now.argtypes = [vp, C.c_int64]
+    lib.bnhip_event_bank_threshold_changes.argtypes = [vp] + answer
+    lib.bnhip_event_bank_thresholds.argtypes = [vp] * 6
+    lib.bnhip_event_bank_set_thresholds.argtypes = [vp] * 5
+    lib.bnhip_event_bank_reset_thresholds.argtypes = [vp, ci]
+    lib.bnhip_event_threshold.argtypes = [C.c_float, ci, C.c_float]
+    lib.bnhip_event_threshold.restype = C.c_float
     return lib
 
 
@@ -369,18 +415,29 @@ class EventBank:
     (bnhip_event_bank_create_extended) - the hits of its sliding classes move their events' deadlines; `set_extend(extend | None)`
     then changes the table and the numbers, within the longest wait the bank was created with.  A call that fails changes no
     source.  cap: None = whatever the call answers (a call refused for room is repeated with the room it named); a number = that
-    room, and HipError with `.needed` beyond it."""
+    room, and HipError with `.needed` beyond it.  dynamic (an EventDynamic): the bank is created dynamic
+    (bnhip_event_bank_create_dynamic) - it learns per-class thresholds on the device, at the bank time `set_now(now)` gives;
+    `set_dynamic(dynamic | None)` changes the settings or freezes the learning, `thresholds()` / `restore_thresholds(...)` /
+    `reset_thresholds(class_index=-1)` are the state's snapshot, restore and reset, and `threshold_changes()` takes the change
+    records (THRESHOLD_CHANGE) of the calls since it was last asked."""
 
     ROOM = 256
 
-    def __init__(self, n_classes, k, filter, max_sources=256, device=0, extend=None):
+    def __init__(self, n_classes, k, filter, max_sources=256, device=0, extend=None, dynamic=None):
         lib = self._lib = _event_bank_protos(load_library())
         self._h = None
         self.n_classes, self.k, self.max_sources, self.device = int(n_classes), int(k), int(max_sources), int(device)
         self.extended = extend is not None
         fs = filter._struct(self.n_classes)
         h = C.c_void_p()
-        if extend is None:
+        self.dynamic = dynamic is not None
+        self._changes = []
+        if dynamic is not None:
+            xs = None if extend is None else extend._struct(self.n_classes)
+            ds = dynamic._struct(self.n_classes)
+            _check(lib, lib.bnhip_event_bank_create_dynamic(self.device, self.max_sources, self.n_classes, self.k, C.addressof(fs),
+                                                            None if xs is None else C.addressof(xs), C.addressof(ds), C.byref(h)))
+        elif extend is None:
             _check(lib, lib.bnhip_event_bank_create(self.device, self.max_sources, self.n_classes, self.k, C.addressof(fs), C.byref(h)))
         else:
             xs = extend._struct(self.n_classes)
@@ -396,8 +453,9 @@ class EventBank:
             raise HipError(E_INVALID, "event bank is closed")
         return self._h
 
-    def _answer(self, call, cap):
-        """call(out pointer, room, byref n) -> rc, with the room handled as the class docstring says."""
+    def _answer(self, call, cap, changes=True):
+        """call(out pointer, room, byref n) -> rc, with the room handled as the class docstring says.  changes: the call replaces the
+        bank's change records (process, flush; not pending, after which the previous call's still stand and were collected then)."""
         room = self.ROOM if cap is None else int(cap)
         while True:
             out, n = np.zeros(room, EVENT), C.c_size_t(0)
@@ -411,7 +469,55 @@ class EventBank:
                 e.needed = n.value
                 raise e
             _check(self._lib, rc)
+            if self.dynamic and changes:
+                self._collect_changes()
             return out[:n.value]
+
+    def _collect_changes(self):
+        """(a dynamic bank, after a successful call) the call's change records join those not yet taken."""
+        room = 16
+        while True:
+            out, n = np.zeros(room, THRESHOLD_CHANGE), C.c_size_t(0)
+            rc = self._lib.bnhip_event_bank_threshold_changes(self._alive(), out.ctypes.data, room, C.byref(n))
+            if rc == E_INVALID and n.value > room:
+                room = n.value
+                continue
+            _check(self._lib, rc)
+            if n.value:
+                self._changes.append(out[:n.value])
+            return
+
+    def threshold_changes(self):
+        """-> the change records (THRESHOLD_CHANGE) of the process / flush / tick calls since the last take, in call order."""
+        got, self._changes = self._changes, []
+        return np.concatenate(got) if got else np.zeros(0, THRESHOLD_CHANGE)
+
+    def set_now(self, now):
+        """bnhip_event_bank_set_now: bank time of the calls that follow; it never decreases."""
+        _check(self._lib, self._lib.bnhip_event_bank_set_now(self._alive(), int(now)))
+
+    def set_dynamic(self, dynamic):
+        """bnhip_event_bank_set_dynamic: a new EventDynamic from the next call on; None freezes the learning (thr_eff = base)."""
+        ds = None if dynamic is None else dynamic._struct(self.n_classes)
+        _check(self._lib, self._lib.bnhip_event_bank_set_dynamic(self._alive(), None if ds is None else C.addressof(ds)))
+
+    def thresholds(self):
+        """bnhip_event_bank_thresholds -> level, high_count (int32), expires, learned_at (int64), current (float32), [n_classes] each."""
+        n = self.n_classes
+        a = [np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.float32)]
+        _check(self._lib, self._lib.bnhip_event_bank_thresholds(self._alive(), *[x.ctypes.data for x in a]))
+        return tuple(a)
+
+    def restore_thresholds(self, level, high_count, expires, learned_at):
+        """bnhip_event_bank_set_thresholds: persisted state back into the bank."""
+        a = [np.ascontiguousarray(level, np.int32).reshape(-1), np.ascontiguousarray(high_count, np.int32).reshape(-1),
+             np.ascontiguousarray(expires, np.int64).reshape(-1), np.ascontiguousarray(learned_at, np.int64).reshape(-1)]
+        if any(x.size != self.n_classes for x in a):
+            raise HipError(E_INVALID, f"the threshold state holds n_classes = {self.n_classes} entries per array")
+        _check(self._lib, self._lib.bnhip_event_bank_set_thresholds(self._alive(), *[x.ctypes.data for x in a]))
+
+    def reset_thresholds(self, class_index=-1):
+        _check(self._lib, self._lib.bnhip_event_bank_reset_thresholds(self._alive(), int(class_index)))
 
     @staticmethod
     def _rows(sources, conf, idx, k):
@@ -434,7 +540,7 @@ class EventBank:
 
     def pending(self, cap=None):
         h, L = self._alive(), self._lib
-        return self._answer(lambda o, room, n: L.bnhip_event_bank_pending(h, o, room, n), cap)
+        return self._answer(lambda o, room, n: L.bnhip_event_bank_pending(h, o, room, n), cap, changes=False)
 
     def reset(self, source=-1):
         _check(self._lib, self._lib.bnhip_event_bank_reset(self._alive(), int(source)))

@@ -347,6 +347,8 @@ class NativeWindows:
                 raise
         if events is None:
             events = self._ev[:ne.value].copy()
+            if bank.dynamic and n.value:                            # (the bank's call ran: its change records join the bank's list)
+                bank._collect_changes()
         return srcs, self._view(p)[:n.value], conf[:n.value].copy(), idx[:n.value].copy(), events
 
     def ready(self):
@@ -667,18 +669,26 @@ class WindowBatcher:
     `extend=` (a host.EventExtend; native rings, with events) creates every model's event bank extended: the hits of the chosen classes move their
     events' deadlines (include/bnhip.h, "Detection events: extended capture"), so a bird that keeps calling is one long event.  With
     `capture=` and an export with extended=True such an event's clip runs from its first hit to its last; the retry above waits for
-    the audio behind the last hit."""
+    the audio behind the last hit.
+
+    `dynamic=` (a host.EventDynamic; native rings, with events) creates every model's event bank dynamic: the bank learns per-class
+    thresholds on the device (include/bnhip.h, "Detection events: dynamic thresholds"; one bank per model is the reference's
+    modelID:species scoping).  Bank time is the batcher's `clock` in milliseconds since its creation, set before every tick; the
+    EventDynamic's valid and cooldown are in that unit.  The ticks' threshold changes go to take_threshold_changes() and
+    on_threshold_changes(model_id, changes)."""
 
     BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
     EVENT_SOURCES = 1024                     # native: sources of a model's event bank (assembler slots are reused)
 
     def __init__(self, orch: Orchestrator, queue: _results.ResultsQueue = None, overruns: OverrunTrackers = None,
                  max_batch=256, pre_capture_s=0.0, bit_depth=16, clock=time.time, on_error=None, native=True, events=None,
-                 on_events=None, capture=None, on_clips=None, extend=None):
+                 on_events=None, capture=None, on_clips=None, extend=None, dynamic=None, on_threshold_changes=None):
         if capture is not None and (events is None or not native):
             raise StreamError("capture needs events and the native rings")
         if extend is not None and (events is None or not native):
             raise StreamError("extend needs events and the native rings")
+        if dynamic is not None and (events is None or not native):
+            raise StreamError("dynamic needs events and the native rings")
         self.orch = orch
         self.queue = queue if queue is not None else _results.ResultsQueue()
         self.overruns = overruns if overruns is not None else OverrunTrackers()
@@ -702,6 +712,10 @@ class WindowBatcher:
         self.sl_reports = []                 # finished reports until take_sound_levels()
         self.events = events                 # native: a host.EventTables -> detection events beside the Results (None: none)
         self.extend = extend                 # native: a host.EventExtend -> the models' event banks are created extended (None: not)
+        self.dynamic = dynamic               # native: a host.EventDynamic -> the models' event banks learn their thresholds (None: not)
+        self.on_threshold_changes = on_threshold_changes
+        self.threshold_reports = []          # the ticks' threshold changes until take_threshold_changes()
+        self.created, self.bank_now = clock() if dynamic is not None else None, 0   # bank time: milliseconds of `clock` since here, never decreasing
         self.on_events = on_events
         self.event_banks = {}                # native: model_id -> host.EventBank over that model's assembler sources
         self.event_reports = []              # the ticks' events until take_events()
@@ -900,7 +914,8 @@ class WindowBatcher:
         bank = self.event_banks.get(model_id)
         if bank is None:
             n_classes = len(inst.labels)
-            bank = _host.EventBank(n_classes, min(getattr(inst, "TOP_K", 10), n_classes), self.events, self.EVENT_SOURCES, extend=self.extend)
+            bank = _host.EventBank(n_classes, min(getattr(inst, "TOP_K", 10), n_classes), self.events, self.EVENT_SOURCES, extend=self.extend,
+                                   dynamic=self.dynamic)
             with self.mu:
                 self.event_banks[model_id] = bank
         return bank
@@ -911,6 +926,14 @@ class WindowBatcher:
         count the source's windows since it was allocated."""
         with self.mu:
             out, self.event_reports = self.event_reports, []
+        return out
+
+    def take_threshold_changes(self):
+        """-> the threshold changes since the last call, oldest first: {"timestamp", "model_id", "class_index", "label",
+        "previous_level", "new_level", "reason" (host.THRESHOLD_EXPIRY / THRESHOLD_HIGH_CONFIDENCE), "previous_value", "new_value",
+        "confidence"}."""
+        with self.mu:
+            out, self.threshold_reports = self.threshold_reports, []
         return out
 
     # (under self.mu) one resampler stream per (source, rate pair) while a buffer of the source uses the pair
@@ -1174,6 +1197,9 @@ class WindowBatcher:
             # previous chunk); anything else gets the collected rows
             if self.events is not None and hasattr(inst, "predict_windows"):
                 bank = self._event_bank(model_id, inst)
+                if self.dynamic is not None:
+                    self.bank_now = max(self.bank_now, int(round((self.clock() - self.created) * 1000.0)))
+                    bank.set_now(self.bank_now)
                 if hasattr(inst, "predict_windows_events"):       # rows and events in one call
                     idxs, rows, lists, ev = inst.predict_windows_events(win, bank, self.bit_depth)
                 else:                                             # the bank is fed the rows the tick returned
@@ -1234,6 +1260,17 @@ class WindowBatcher:
                                     (e.copy(), r["source"], r["label"]) for e, r in zip(ev, reports) if int(e["status"]) == 0)
                         if self.on_events:
                             self.on_events(model_id, reports)
+                    if self.dynamic is not None:
+                        changes = [{"timestamp": now, "model_id": model_id, "class_index": int(c["class_index"]),
+                                    "label": inst.labels[int(c["class_index"])], "previous_level": int(c["previous_level"]),
+                                    "new_level": int(c["new_level"]), "reason": int(c["reason"]), "previous_value": float(c["previous_value"]),
+                                    "new_value": float(c["new_value"]), "confidence": float(c["confidence"])}
+                                   for c in self.event_banks[model_id].threshold_changes()]
+                        if changes:
+                            with self.mu:
+                                self.threshold_reports.extend(changes)
+                            if self.on_threshold_changes:
+                                self.on_threshold_changes(model_id, changes)
                 del tick_events[:]
                 sources = [name(win, i) for i in idxs]
                 sent += _emit_results(self.orch, rows, lists, time.perf_counter() - t0, [start] * len(idxs), [now] * len(idxs), sources,

@@ -411,7 +411,8 @@ int bnhip_event_min_count(int level, double overlap_seconds);
  *            bytes on every run.
  *   bnhip_event_bank_create  Copies the filter's tables; hold_windows and k are fixed for the bank's life.
  *   bnhip_event_bank_set_filter  New thresholds, veto table, veto threshold, min_count and flags from the next call on (settings
- *            reloads, the host's own dynamic thresholds); a different hold_windows is refused.
+ *            reloads; in a dynamic bank - "Detection events: dynamic thresholds" below - the thresholds are the classes' bases); a
+ *            different hold_windows is refused.
  *   bnhip_event_bank_process  Rows from host memory.  sources[r] < 0 skips row r; a source may appear several times or not at all.
  *   bnhip_event_bank_process_device  The same with the rows already on the bank's device: enqueued on `stream`, synchronised before
  *            it returns.  A class index outside the table is no result here; the host form refuses it in its one checking pass.
@@ -502,6 +503,90 @@ int bnhip_event_bank_create_extended(int device, int max_sources, int n_classes,
                                      const bnhip_event_extend* extend, bnhip_event_bank** out);
 int bnhip_event_bank_set_extend(bnhip_event_bank* b, const bnhip_event_extend* extend);
 int64_t bnhip_event_deadline(int32_t hold_windows, const bnhip_event_extend* extend, int64_t first_window, int64_t window);
+
+/* Detection events: dynamic thresholds.  An approved detection above DynamicThreshold.Trigger lowers that species' threshold to 75 %,
+ * 50 % and then 25 % of its base, every later hit above the base keeps the lowered threshold alive, and ValidHours without one
+ * resets it (internal/analysis/processor/dynamic_threshold.go; processor.go:794, 1034-1046, 1582-1591).  The reference keys this
+ * state modelID:species, so here it is per class and shared by all sources of a bank: it lives on the device beside the sources'
+ * slabs, the effective thresholds are derived there at the start of every call, the learning runs behind the emit in the same
+ * transaction, and the host is handed the list of threshold changes (the reference's ThresholdEvents).
+ *   time     Bank time is an int64 in a unit the host chooses (milliseconds, windows), given by bnhip_event_bank_set_now: host
+ *            only, it stands for the calls that follow.  0 <= now < 2^62, never decreasing.  The sources' clocks stay audio time.
+ *   settings class_dynamic [n_classes] (non-zero: the class learns; NULL: every class; zero is a species with a custom threshold,
+ *            which the reference never adjusts), trigger, min_threshold, valid (ValidHours in bank time, 1..2^61), cooldown
+ *            (max(capture length - pre-capture, 5 s) in bank time, 0..2^61).  The base of class c is the filter's
+ *            class_threshold[c]: a set_filter with new bases recalculates every effective threshold at the next call
+ *            (RecalculateDynamicThresholds).
+ *   state    Per class: level L in 0..3, count n >= 0, expires E, learned_at A (-1: never); initially L = n = E = 0, A = -1.  The
+ *            state of a class that is not dynamic is kept and ignored.
+ *   a call   process, process_device, flush or the tick at time `now`, in this order (pending changes nothing):
+ *            1 expiry: a dynamic class with now > E (strict) and n > 0: a record (L -> 0, EXPIRY, confidence 0) when L != 0, then
+ *              L = 0, n = 0, A = -1.
+ *            2 thr_eff[c] = (float) max((double) base[c] * mult(L), (double) min_threshold) for a dynamic class with L > 0, mult =
+ *              0.75 / 0.50 / 0.25; otherwise base[c] bit for bit, NaN and +inf included (they still exclude the class).
+ *            3 the bank's rule with thr_eff where class_threshold stood, fixed for the whole call.
+ *            4 touch (updateDynamicThreshold): every result (x, c) of the call's counted rows with class_veto[c] == 0, c dynamic,
+ *              n > 0 after step 1, x > thr_eff[c] and x > base[c] sets E = now + valid.
+ *            5 learn (LearnFromApprovedDetection): of the events that became due in this call with status 0 - whatever cap and
+ *              BNHIP_EVENTS_KEEP_DROPPED are - class c is approved high when it is dynamic, x > trigger (strict) and x >= base[c];
+ *              X is the largest such x.  Then E = now + valid, and if A < 0 or now - A >= cooldown: n = min(n + 1, INT32_MAX),
+ *              A = now, L' = min(n, 3), with a record (L -> L', HIGH_CONFIDENCE, confidence X) when L' != L.  Any number of
+ *              sources approving a class in one call is one learning, whatever order they are walked in.
+ *            What steps 4 and 5 write is seen by the next call.  A dynamic bank runs steps 1, 2 and 4-5 also in a call that
+ *            has no source in it (no counted row, no live source to flush); *n_windows == 0 of the tick stays no call at all.
+ *   differs  from the reference: expiry is applied at the start of every call, not lazily at the species' next hit (the thresholds
+ *            are the same, the EXPIRY record is earlier); an entry exists exactly when n > 0 (the reference keeps a level-0 entry,
+ *            its base clamped to min_threshold, until its periodic clean-up); the clock is what set_now gives; one call is one
+ *            instant.
+ *   bnhip_event_bank_create_dynamic  bnhip_event_bank_create (extend NULL) or bnhip_event_bank_create_extended with the dynamic.
+ *            process, process_device, flush, pending, reset (which leaves the class state alone), clock, set_filter, set_extend and
+ *            bnhip_windows_predict_events take such a bank unchanged.  A bank created without one launches what it did before.
+ *   bnhip_event_bank_set_dynamic  New settings from the next call on.  NULL turns learning off: thr_eff = base and the state is
+ *            frozen, not cleared.
+ *   bnhip_event_bank_threshold_changes  The records of the last successful process / flush / tick call, ascending by (class_index,
+ *            EXPIRY before HIGH_CONFIDENCE); none after a call that changed nothing.  *n_out = their number; more than cap is
+ *            BNHIP_E_INVALID with nothing written.  previous_value / new_value are bnhip_event_threshold at the two levels.
+ *   bnhip_event_bank_thresholds  GetDynamicThresholdData: the state as the last successful call left it, dense [n_classes] arrays,
+ *            any of them NULL; current = thr_eff of step 2 from that state and the filter in force (the host derives IsActive
+ *            from expires and its own now).
+ *   bnhip_event_bank_set_thresholds  Restores persisted state (threshold_persistence.go).  Refused unless 0 <= level <= 3, level ==
+ *            min(high_count, 3), learned_at >= -1 and expires >= 0 for every class.
+ *   bnhip_event_bank_reset_thresholds  ResetDynamicThreshold / ResetAll: class_index (-1: every class) back to the initial state.
+ *            bnhip_event_bank_thresholds, _set_thresholds and _reset_thresholds are synchronous: each is a blocking copy of one
+ *            slab of the class state (24 bytes per class; _reset_thresholds of one class a copy each way) on the default stream,
+ *            which also waits for the process's blocking streams - calls for an API view or a settings change, not for every tick.
+ *   bnhip_event_threshold  Host only: thr_eff of a base at a level.
+ *   calls    The class state is a pair of slabs with a parity of its own, flipped in the call's commit: a call that fails - more
+ *            events than cap too - changes no class, and the same call repeated with room gives the same events, state and changes.
+ * BNHIP_E_INVALID (before any device call): what the namesakes refuse, a NULL dynamic at create, a NaN or negative trigger or
+ * min_threshold, valid or cooldown out of range, a decreasing or out-of-range now, a level outside 0..3 for bnhip_event_threshold
+ * (it answers NaN), and the entries of this section on a bank created without a dynamic. */
+#define BNHIP_THRESHOLD_EXPIRY 0
+#define BNHIP_THRESHOLD_HIGH_CONFIDENCE 1
+typedef struct bnhip_event_dynamic {
+    const uint8_t* class_dynamic;      /* [n_classes], non-zero: the class learns; NULL: every class does */
+    float trigger;                     /* DynamicThreshold.Trigger */
+    float min_threshold;               /* DynamicThreshold.Min */
+    int64_t valid;                     /* ValidHours, in bank time */
+    int64_t cooldown;                  /* max(capture length - pre-capture, 5 s), in bank time */
+} bnhip_event_dynamic;
+typedef struct bnhip_threshold_change {
+    int32_t class_index, previous_level, new_level, reason;
+    float previous_value, new_value, confidence;
+    int32_t pad;
+} bnhip_threshold_change;
+int bnhip_event_bank_create_dynamic(int device, int max_sources, int n_classes, int k, const bnhip_event_filter* filter,
+                                    const bnhip_event_extend* extend /* may be NULL */, const bnhip_event_dynamic* dynamic,
+                                    bnhip_event_bank** out);
+int bnhip_event_bank_set_dynamic(bnhip_event_bank* b, const bnhip_event_dynamic* dynamic);
+int bnhip_event_bank_set_now(bnhip_event_bank* b, int64_t now);
+int bnhip_event_bank_threshold_changes(bnhip_event_bank* b, bnhip_threshold_change* out, size_t cap, size_t* n_out);
+int bnhip_event_bank_thresholds(bnhip_event_bank* b, int32_t* level, int32_t* high_count, int64_t* expires, int64_t* learned_at,
+                                float* current);
+int bnhip_event_bank_set_thresholds(bnhip_event_bank* b, const int32_t* level, const int32_t* high_count, const int64_t* expires,
+                                    const int64_t* learned_at);
+int bnhip_event_bank_reset_thresholds(bnhip_event_bank* b, int class_index);
+float bnhip_event_threshold(float base, int level, float min_threshold);
 
 /* Detection clips: what the reference saves for every approved detection, made from the recordings of a file-analysis call while
  * they are still on the device.  Its processor takes the audio from BeginTime back by the pre-capture to the end of the capture
