@@ -365,27 +365,20 @@ __global__ __launch_bounds__(1024) void k_se(SeParams p) {
         const int C4 = p.C / 4;
         int G = 1;
         while (G * 2 * C4 <= NTHR && G * 2 <= p.Cr) G *= 2;
-        float4* part4 = reinterpret_cast<float4*>(part);           // [G][C4] (G * C <= 4096 floats <= scratch? see launch)
-        // (C4 <= NTHR is guaranteed by launch_se: a block is never smaller than the channel-quad count)
-        const int c4 = tid % C4, g = tid / C4;
-        if (g < G) {
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4* w4 = reinterpret_cast<const float4*>(p.w2) + c4;
-#pragma unroll 8
-            for (int j = g; j < p.Cr; j += G) {
-                float4 w = w4[(size_t)j * C4];
-                float rj = r[j];
-                acc.x = fmaf(w.x, rj, acc.x); acc.y = fmaf(w.y, rj, acc.y); acc.z = fmaf(w.z, rj, acc.z); acc.w = fmaf(w.w, rj, acc.w);
-            }
-            if (G > 1) part4[g * C4 + c4] = acc;
-            else {
-                float4 bb = p.b2 ? reinterpret_cast<const float4*>(p.b2)[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-                float4 o = make_float4(apply_act(acc.x + bb.x, p.act2), apply_act(acc.y + bb.y, p.act2),
-                                       apply_act(acc.z + bb.z, p.act2), apply_act(acc.w + bb.w, p.act2));
-                reinterpret_cast<float4*>(p.scale + (size_t)b * p.C)[c4] = o;
-            }
-        }
         if (G > 1) {
+            float4* part4 = reinterpret_cast<float4*>(part);       // [G][C4]: G * C4 <= NTHR float4, the scratch launch_se sizes
+            const int c4 = tid % C4, g = tid / C4;
+            if (g < G) {
+                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4* w4 = reinterpret_cast<const float4*>(p.w2) + c4;
+#pragma unroll 8
+                for (int j = g; j < p.Cr; j += G) {
+                    float4 w = w4[(size_t)j * C4];
+                    float rj = r[j];
+                    acc.x = fmaf(w.x, rj, acc.x); acc.y = fmaf(w.y, rj, acc.y); acc.z = fmaf(w.z, rj, acc.z); acc.w = fmaf(w.w, rj, acc.w);
+                }
+                part4[g * C4 + c4] = acc;
+            }
             __syncthreads();
             for (int c = tid; c < C4; c += NTHR) {
                 float4 acc = part4[c];
@@ -394,6 +387,23 @@ __global__ __launch_bounds__(1024) void k_se(SeParams p) {
                 float4 o = make_float4(apply_act(acc.x + bb.x, p.act2), apply_act(acc.y + bb.y, p.act2),
                                        apply_act(acc.z + bb.z, p.act2), apply_act(acc.w + bb.w, p.act2));
                 reinterpret_cast<float4*>(p.scale + (size_t)b * p.C)[c] = o;
+            }
+        } else {
+            // G == 1: a thread walks the quads tid, tid + NTHR, ...  launch_se doubles the block only up to 1024 threads, so a layer of
+            // more than 4096 channels has more quads than the block has threads (one trip of this loop everywhere else)
+            for (int c4 = tid; c4 < C4; c4 += NTHR) {
+                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4* w4 = reinterpret_cast<const float4*>(p.w2) + c4;
+#pragma unroll 8
+                for (int j = 0; j < p.Cr; j++) {
+                    float4 w = w4[(size_t)j * C4];
+                    float rj = r[j];
+                    acc.x = fmaf(w.x, rj, acc.x); acc.y = fmaf(w.y, rj, acc.y); acc.z = fmaf(w.z, rj, acc.z); acc.w = fmaf(w.w, rj, acc.w);
+                }
+                float4 bb = p.b2 ? reinterpret_cast<const float4*>(p.b2)[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+                float4 o = make_float4(apply_act(acc.x + bb.x, p.act2), apply_act(acc.y + bb.y, p.act2),
+                                       apply_act(acc.z + bb.z, p.act2), apply_act(acc.w + bb.w, p.act2));
+                reinterpret_cast<float4*>(p.scale + (size_t)b * p.C)[c4] = o;
             }
         }
     } else {
@@ -405,6 +415,11 @@ __global__ __launch_bounds__(1024) void k_se(SeParams p) {
         }
     }
 }
+// Dynamic LDS of k_se for a block of thr threads: mean [C], r [Cr], and the fold scratch - [P][C] floats with P C <= threads, or
+// [G][C / 4] float4 with G C / 4 <= threads, i.e. at most one float4 per thread.  k_se raises no limit of its own, so a launch may
+// ask for 64 KB; se_supported: the largest block's request stays within that (the planner refuses the block otherwise).
+size_t se_lds_bytes(int C, int Cr, int thr) { return (size_t)(C + Cr + 4 * thr + 16) * sizeof(float); }
+bool se_supported(int C, int Cr) { return C > 0 && Cr > 0 && se_lds_bytes(C, Cr, 1024) <= 64 * 1024; }
 void launch_se(const SeParams& p, hipStream_t s) {
     // Block size: 1024 threads finish a clip fastest when the kernel owns the GPU, but a 16-wave workgroup needs a whole
     // CU's worth of free wave slots and, beside another context's kernels, waited for one 5-30x its own run time
@@ -413,11 +428,10 @@ void launch_se(const SeParams& p, hipStream_t s) {
     static const int env = getenv("BNHIP_SE_THREADS") ? atoi(getenv("BNHIP_SE_THREADS")) : 0;
     int thr = env ? env : (p.threads ? p.threads : 1024);
     thr = std::max(64, std::min(1024, thr / 64 * 64));
-    while (thr < 1024 && (p.C + 3) / 4 > thr) thr *= 2;              // FC2 maps one thread to a channel quad
-    // mean, r, fold scratch: [P][C] floats with P C <= threads, or [G][C / 4] float4 with G C / 4 <= threads - i.e. at most one
-    // float4 per thread.  (Sized for 1024 threads whatever the block, a 4-wave block asked for 16 KB more LDS than it can use and,
+    while (thr < 1024 && (p.C + 3) / 4 > thr) thr *= 2;              // FC2 maps one thread to a channel quad (beyond 4096 channels: k_se loops)
+    // (Sized for 1024 threads whatever the block, a 4-wave block asked for 16 KB more LDS than it can use and,
     // beside another context's LDS-heavy kernels, waited for it: rocprofv3, Perch bf16 pipelined: avg 62 us, max 777 us.)
-    const size_t lds = (size_t)(p.C + p.Cr + 4 * thr + 16) * sizeof(float);
+    const size_t lds = se_lds_bytes(p.C, p.Cr, thr);
     hipLaunchKernelGGL(k_se, dim3(p.B), dim3(thr), lds, s, p);
 }
 

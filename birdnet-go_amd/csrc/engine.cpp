@@ -828,7 +828,7 @@ std::string Engine::describe() const {
         os << "\",\"H\":" << s.H << ",\"W\":" << s.W << ",\"C\":" << s.C << ",\"Co\":" << s.Co << ",\"k\":" << s.kh
            << ",\"stride\":" << s.sh << ",\"act\":" << s.act << ",\"fused_scale\":" << (s.kind == S_PW && s.in1 >= 0 ? 1 : 0)
            << ",\"shape\":" << s.shape << ",\"dw_lds\":" << s.dwl << ",\"bx\":" << s.bx << ",\"nt\":" << s.nt << ",\"wm\":" << s.wm << ",\"nt_full\":" << s.nt_full << ",\"wm_full\":" << s.wm_full << ",\"fused_res\":" << (s.kind == S_PW && s.in2 >= 0 ? 1 : 0) << ",\"fused_sum\":" << (s.out2 >= 0 ? 1 : 0) << ",\"flops\":" << sv.flops << ",\"bytes\":" << sv.bytes << ",\"wbytes\":" << s.wbytes
-           << ",\"tail\":" << s.tail << ",\"absorbed\":" << (absorbed ? 1 : 0) << ",\"out_v\":" << s.out << ",\"out2_v\":" << s.out2
+           << ",\"tail\":" << s.tail << ",\"absorbed\":" << (absorbed ? 1 : 0) << ",\"out_v\":" << s.out << ",\"out2_v\":" << s.out2 << ",\"S\":" << s.S
            << ",\"in_bf16\":" << ((s.in0 >= 0 && vals[s.in0].half) ? 1 : 0) << ",\"out_bf16\":" << ((s.out >= 0 && vals[s.out].half) ? 1 : 0) << "}";
     }
     os << "]}";

@@ -303,6 +303,8 @@ struct SeParams {         // squeeze-excite FCs on pooled sums
     int threads = 0;                             // workgroup size (0 = 1024); see launch_se
 };
 void launch_se(const SeParams& p, hipStream_t s);
+size_t se_lds_bytes(int C, int Cr, int threads);   // dynamic LDS of a k_se block
+bool se_supported(int C, int Cr);                  // the 1024-thread block's LDS stays within what a launch may ask for (plan time)
 
 // ---- generic fallbacks (unfused graphs)
 void launch_unary(const float* in, float* out, size_t n, int act, hipStream_t s);

@@ -1080,6 +1080,7 @@ struct Lowering {
         int c1 = P.only_consumer(P.skip_down(mt));
         int Cr = 0, Cb = 0;
         if (!fc_like(c1, C, &Cr)) return no();
+        if (!se_supported(C, Cr)) return no();       // k_se's LDS request would exceed a launch's limit: the generic steps run the block
         int act1 = ACT_NONE, act2 = ACT_NONE;
         int r = fc_act(c1, &act1);
         if (r < 0) return no();
