@@ -174,7 +174,8 @@ struct PwParams {         // pointwise conv / fully-connected as GEMM: out[M,N] 
     int wm = 0;           // row tile: 1 = 64 rows per block, otherwise 128; 3 / 4 = the same tiles on k_pw_pipe
     int prec = 0;         // k_pw_bx3 only: 0 = six bf16 products per fp32 product (fp32-equivalent), 1 = one (plain bf16 operands,
                           // fp32 accumulate: the "precision":"bf16" engines)
-    int a_bf16 = 0;       // k_pw_bx3 / k_pw_bx3p only: A holds bf16 values (bf16 activation storage, K % 4 == 0)
+    int a_bf16 = 0;       // A holds bf16 values (bf16 activation storage, K % 8 == 0): k_pw_bx3 / k_pw_bx3p in either precision, and the
+                          // one-product forms of k_pw_b16, k_pw_b16s and k_pw_ws; never k_pw_lat or a six-product k_pw_b16 / k_pw_ws
     int out_bf16 = 0;     // any pw kernel: out is written as bf16 (N % 4 == 0)
     int res_bf16 = 0;     // any pw kernel: res holds bf16 values (N % 4 == 0) - the residual stream of a "precision":"bf16" engine
     int sw = 0;           // PW_SW_* bits: experiment / test switches of the split-bf16 kernel family, read from the environment ONCE per
@@ -197,7 +198,8 @@ void launch_pw_bx3(const PwParams& p, const uint16_t* Wimg, hipStream_t s);
 // The same GEMM with A streamed straight from global memory two slabs ahead (pw_b16.hip; PwParams::wm = 9 / 10: 128- / 64-row
 // tiles; one product per operand pair for "precision":"bf16" engines - 128-row tiles only - or the six-product fp32-equivalent
 // form): called by launch_pw_bx3, which has resolved the tile (nt = 16-column units) and the grid.
-bool pw_b16_ok(int prec, int K, int sw);
+// bf16 A (PwParams::a_bf16) only on the one-product form: a six-product call with bf16 A is refused and runs on k_pw_bx3.
+bool pw_b16_ok(int prec, int K, int sw, int a_bf16 = 0);
 // k_pw_b16 with a row tile that is a whole number of clips (PwParams::wm = 13 / 14 / 15: 48, 96, 192 rows; six-product form, fp32
 // activations, no scale, no residual) and the consumer of its output folded into the epilogue: the k x k stride-1 SAME depthwise
 // convolution of the next step with its squeeze-excite sums (what k_dwconv_t computes, in its operation order), or the spatial mean

@@ -551,7 +551,10 @@ void launch_pw_b16s(const PwParams& p, const uint16_t* Wimg, int Npad, hipStream
 }
 
 // the switches (BNHIP_PW_B16 / BNHIP_PW_B16S: 0 = candidate taken away, 2 = forced) are read once per engine and travel in PwParams::sw
-bool pw_b16_ok(int prec, int K, int sw) { return (prec == 0 || prec == 1) && (K & 3) == 0 && K >= 16 && !(sw & PW_SW_B16_OFF); }
+// (the six-product form has no bf16-A instantiation - launch_pw_b16 would read bf16 storage as fp32: such a call stays on k_pw_bx3)
+bool pw_b16_ok(int prec, int K, int sw, int a_bf16) {
+    return (prec == 0 || prec == 1) && (K & 3) == 0 && K >= 16 && !(sw & PW_SW_B16_OFF) && !(a_bf16 && prec == 0);
+}
 
 // prec 1 (one product): 128-row tiles; prec 0 (six products): 64- or 128-row tiles (wm = 1 | 2)
 void launch_pw_b16(const PwParams& p, const uint16_t* Wimg, int nt, int wm, int Npad, int nblk_n, unsigned nblk, hipStream_t s) {

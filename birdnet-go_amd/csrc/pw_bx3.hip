@@ -414,7 +414,7 @@ void launch_pw_bx3(const PwParams& p, const uint16_t* Wimg, hipStream_t s) {
     const int Npad = pw_bx3_npad(p.N);
     // "precision":"bf16" engines: 128-row tiles run on the kernel built for one product per operand fragment (pw_b16.hip) -
     // the same arithmetic, A straight from global memory into fragments
-    if ((p.wm == 9 || p.wm == 10 || (p.sw & PW_SW_B16_FORCE)) && (wm == 2 || p.prec == 0) && pw_b16_ok(p.prec, p.K, p.sw)) {
+    if ((p.wm == 9 || p.wm == 10 || (p.sw & PW_SW_B16_FORCE)) && (wm == 2 || p.prec == 0) && pw_b16_ok(p.prec, p.K, p.sw, p.a_bf16)) {
         launch_pw_b16(p, Wimg, nt, wm, Npad, g.nblk_n, g.nblk, s);
         return;
     }

@@ -68,7 +68,7 @@ int main(int argc, char** argv) {
     std::mt19937 rng(1234);
     std::normal_distribution<float> nd(0.f, 1.f);
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    size_t fz_cmp = 0, fz_bad = 0, fz_ws = 0, fz_lat = 0;
+    size_t fz_cmp = 0, fz_bad = 0, fz_ws = 0, fz_lat = 0, fz_tiled = 0, fz_kept = 0;
     auto run = [&](const Shape& sh, bool fuzz) {
         const int M = sh.M, N = sh.N, K = sh.K, B = (M + sh.HW - 1) / sh.HW;
         std::vector<float> A((size_t)M * K), W((size_t)N * K), bias(N), sc((size_t)B * K), res((size_t)M * N);
@@ -130,6 +130,11 @@ int main(int argc, char** argv) {
                 if (memcmp(&hout[i], &href[i], 4)) { if (!bad) first = i; bad++; }
             if (fuzz) {
                 fz_cmp++; fz_ws += c.wm == 12; fz_lat += c.wm == 14;
+                if (c.wm != 12 && c.wm != 14) {              // a tiled candidate: did pw_fill_grid leave it the tile it asked for?
+                    int nt = c.nt, wm = (c.wm == 5 || c.wm == 7 || c.wm == 10) ? 1 : 2;
+                    PwGrid g = pw_grid(M, N, nt, wm);
+                    fz_tiled++; fz_kept += !pw_fill_grid(M, N, &nt, &wm, &g);
+                }
                 if (bad) { fz_bad++; printf("   MISMATCH M=%d N=%d K=%d HW=%d scale=%d res=%d act=%d wm=%d nt=%d: %zu of %zu, first at row %zu col %zu: %g vs %g\n", M, N, K, sh.HW,
                                             (int)sh.scale, (int)sh.res, sh.act, c.wm, c.nt, bad, hout.size(), first / N, first % N, hout[first], href[first]); }
                 continue;
@@ -155,7 +160,8 @@ int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "--fuzz")) {
         // pw_lab --fuzz <seed> <count>: random shapes (K tails, ragged N, N % 4 != 0, one row, scale / residual / swish on and off) through
         // every kernel form of the split-bf16 family - k_pw_ws and k_pw_lat wherever they accept the layer, whatever its size - bitwise
-        // against the tiled k_pw_bx3.  Prints mismatches and one summary line (tests/test_pw_lab.py asserts on it).
+        // against the tiled k_pw_bx3.  Prints mismatches and one summary line (tests/test_pw_lab.py asserts on it), which also counts the tiled
+        // candidates and how many of them pw_fill_grid left at the tile they asked for (all of them under BNHIP_PW_FILL=0).
         std::mt19937 fr((unsigned)(argc > 2 ? atoi(argv[2]) : 1));
         const int count = argc > 3 ? atoi(argv[3]) : 24;
         for (int i = 0; i < count; i++) {
@@ -175,7 +181,8 @@ int main(int argc, char** argv) {
             }
             run(sh, true);
         }
-        printf("fuzz: %d shapes, %zu comparisons (%zu on k_pw_ws, %zu on k_pw_lat), %zu mismatches\n", count, fz_cmp, fz_ws, fz_lat, fz_bad);
+        printf("fuzz: %d shapes, %zu comparisons (%zu on k_pw_ws, %zu on k_pw_lat; %zu tiled, %zu of them at the requested tile), %zu mismatches\n", count, fz_cmp, fz_ws,
+               fz_lat, fz_tiled, fz_kept, fz_bad);
         return fz_bad ? 1 : 0;
     }
     for (const Shape& sh : shapes) {
