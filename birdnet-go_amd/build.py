@@ -9,9 +9,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.environ.get("BNHIP_LIBDIR") or os.path.join(HERE, "lib")      # (BNHIP_LIBDIR + BNHIP_EXTRA_FLAGS: an A/B build beside the shipped one)
 LIB = os.path.join(LIBDIR, "libbnhip.so")
-SOURCES = ["frontend.hip", "conv.hip", "pw_gemm.hip", "pw_bx3.hip", "dwconv.hip", "post.hip", "expdw.hip", "pw_b16.hip", "pw_ws.hip", "generic.hip", "resample.hip", "eq.hip", "soundlevel.hip", "heatmap.hip", "stft.hip", "spectrogram.hip", "loudness.hip", "flac.hip", "flac_decode.hip", "png.hip", "denoise.hip", "analyze.hip", "channels.hip", "engine.cpp", "tune.cpp", "planner.cpp", "graph_passes.cpp", "tflite_model.cpp", "model_onnx.cpp", "hostpipe.cpp", "numa.cpp", "windows.cpp", "api.cpp", "api_windows.cpp", "api_model.cpp", "api_predict.cpp", "api_ultrasonic.cpp", "api_resample.cpp", "api_eq.cpp", "api_soundlevel.cpp", "api_spectrogram.cpp", "api_loudness.cpp", "api_flac.cpp", "api_flac_decode.cpp", "api_png.cpp", "api_denoise.cpp", "api_analyze.cpp", "events.hip", "clips.hip", "api_clips.cpp", "analyze_recordings.cpp", "api_events.cpp", "api_channels.cpp", "events_bank.hip", "api_event_bank.cpp", "capture_bank.hip", "api_capture_bank.cpp"]
-# (a new unit goes last, as events.hip, then events_bank.hip / api_event_bank.cpp and then capture_bank.hip / api_capture_bank.cpp did: units linked behind a new one move, and the headline benchmark was 0.2 % slower with events.hip mid-list - DESIGN section 9)
-HEADERS = ["kernels.h", "pw_common.h", "engine.h", "tflite_model.h", "model_onnx.h", "hostpipe.h", "numa.h", "windows.h", "resample.h", "eq_bank.h", "soundlevel_bank.h", "heatmap.h", "spectrogram.h", "loudness.h", "pcmgain.h", "flac.h", "flac_decode.h", "flac_parse.h", "png.h", "block_scan.h", "ragged.h", "pcm_sample.h", "fft_r8.h", "fft_passes.h", "denoise.h", "process_chain.h", "analyze.h", "channels.h", "events.h", "clips.h", "clip_source.h", "analyze_recordings.h", "api_events.h", "events_bank.h", "capture_bank.h", "api_common.h", "api_oneshot.h", "api_model.h", "stream_bank.h", os.path.join("..", "..", "include", "bnhip.h")]
+SOURCES = ["frontend.hip", "conv.hip", "pw_gemm.hip", "pw_bx3.hip", "dwconv.hip", "post.hip", "expdw.hip", "pw_b16.hip", "pw_ws.hip", "generic.hip", "resample.hip", "eq.hip", "soundlevel.hip", "heatmap.hip", "stft.hip", "spectrogram.hip", "loudness.hip", "flac.hip", "flac_decode.hip", "png.hip", "denoise.hip", "analyze.hip", "channels.hip", "engine.cpp", "tune.cpp", "planner.cpp", "graph_passes.cpp", "tflite_model.cpp", "model_onnx.cpp", "hostpipe.cpp", "numa.cpp", "windows.cpp", "api.cpp", "api_windows.cpp", "api_model.cpp", "api_predict.cpp", "api_ultrasonic.cpp", "api_resample.cpp", "api_eq.cpp", "api_soundlevel.cpp", "api_spectrogram.cpp", "api_loudness.cpp", "api_flac.cpp", "api_flac_decode.cpp", "api_png.cpp", "api_denoise.cpp", "api_analyze.cpp", "events.hip", "clips.hip", "api_clips.cpp", "analyze_recordings.cpp", "api_events.cpp", "api_channels.cpp", "events_bank.hip", "api_event_bank.cpp", "capture_bank.hip", "api_capture_bank.cpp", "levels.hip", "api_level.cpp"]
+# (a new unit goes last, as events.hip, then events_bank.hip / api_event_bank.cpp then capture_bank.hip / api_capture_bank.cpp and then levels.hip / api_level.cpp did: units linked behind a new one move, and the headline benchmark was 0.2 % slower with events.hip mid-list - DESIGN section 9)
+HEADERS = ["kernels.h", "pw_common.h", "engine.h", "tflite_model.h", "model_onnx.h", "hostpipe.h", "numa.h", "windows.h", "resample.h", "eq_bank.h", "soundlevel_bank.h", "heatmap.h", "spectrogram.h", "loudness.h", "pcmgain.h", "flac.h", "flac_decode.h", "flac_parse.h", "png.h", "block_scan.h", "ragged.h", "pcm_sample.h", "fft_r8.h", "fft_passes.h", "denoise.h", "process_chain.h", "analyze.h", "channels.h", "events.h", "clips.h", "clip_source.h", "analyze_recordings.h", "api_events.h", "events_bank.h", "capture_bank.h", "levels.h", "api_common.h", "api_oneshot.h", "api_model.h", "stream_bank.h", os.path.join("..", "..", "include", "bnhip.h")]
 # -fno-slp-vectorize: gfx950 hazard, reproduced standalone (tools/ubench/pkf32_vs_bf16mfma.hip, profiles/r04_pk_hazard.txt): a
 # packed-fp32 VALU instruction whose op_sel bit for src1 is set (v_pk_fma_f32 / v_pk_mul_f32 ... op_sel:[0,1,..]: the LOW result
 # computed from src1's HIGH half) returns a wrong low half in lanes 48-63 while another wave on the same CU executes

@@ -21,26 +21,6 @@
 
 using namespace bnhip;
 
-struct bnhip_capture_bank {
-    struct Source {
-        int64_t written = 0;            // samples given since creation or reset
-        int64_t floor = 0;              // no position below this one is readable
-    };
-    std::mutex mu;                      // calls on one bank are serialised
-    int device = 0, max_sources = 0, rate = 0;
-    int64_t capacity = 0;               // samples of one ring, a multiple of CAPTURE_ALIGN
-    std::vector<Source> src;
-    hipStream_t stream = nullptr;       // the writes' own
-    int16_t* d_rings = nullptr;         // [max_sources][capacity]
-    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // pieces | tile prefix | packed frames
-    int64_t oldest(int s) const { return std::max<int64_t>({0, src[(size_t)s].written - capacity, src[(size_t)s].floor}); }
-    ~bnhip_capture_bank() {             // (bank_free has drained the stream)
-        if (stream) hipStreamDestroy(stream);
-        for (void* p : {(void*)d_rings, d_stage}) if (p) hipFree(p);
-        if (h_stage) hipHostFree(h_stage);
-    }
-};
-
 namespace {
 
 constexpr const char* WHAT = "capture bank";
@@ -83,6 +63,60 @@ void capture_span(const bnhip_event& e, int64_t written, int64_t oldest, int64_t
 }
 
 }  // namespace
+
+namespace bnhip {
+
+int capture_plan(const bnhip_capture_bank* b, int n_frames, const int32_t* sources, const int64_t* n_samples, const void* const* frames,
+                 const int64_t* frame_at, CapturePlan* p) {
+    const int64_t cap = b->capacity;
+    // ---- check, and each source's total
+    p->total.assign((size_t)b->max_sources, 0);
+    int64_t given = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const std::string who = "frame " + std::to_string(f) + ": ";
+        if (sources[f] < 0 || sources[f] >= b->max_sources) return set_err(BNHIP_E_INVALID, who + "no such capture bank source: " + std::to_string(sources[f]));
+        if (n_samples[f] < 0) return set_err(BNHIP_E_INVALID, who + "negative frame length");
+        if (n_samples[f] > 0 && !frames[f]) return set_err(BNHIP_E_INVALID, who + "frame pointer is NULL");
+        if (n_samples[f] > RAGGED_MAX_SAMPLES - given) return set_err(BNHIP_E_INVALID, "the frames' total length must be below 2^36 samples");
+        given += n_samples[f];
+        if (p->total[(size_t)sources[f]] == 0 && n_samples[f] > 0) p->listed.push_back(sources[f]);
+        p->total[(size_t)sources[f]] += n_samples[f];
+    }
+    // ---- per frame what is stored of it, cut where the ring wraps
+    p->tile0.assign(1, 0);
+    std::vector<int64_t> seen((size_t)b->max_sources, 0);                 // samples of the source in the frames before
+    for (int f = 0; f < n_frames; f++) {
+        const int s = sources[f];
+        const int64_t q0 = seen[(size_t)s], skip = std::max<int64_t>(p->total[(size_t)s] - cap, 0);
+        seen[(size_t)s] += n_samples[f];
+        const int64_t from = std::max(q0, skip) - q0, n = n_samples[f] - from;
+        if (n <= 0) continue;
+        p->parts.push_back(CapturePlan::Part{f, from, n});
+        int64_t pos = b->src[(size_t)s].written + q0 + from, src = frame_at ? frame_at[f] + from : p->packed, left = n;
+        while (left > 0) {
+            const int64_t cell = pos % cap, run = std::min(left, cap - cell);
+            p->pieces.push_back(CapPiece{src, (long long)s * cap + cell, run});
+            p->tile0.push_back(p->tile0.back() + cut_tiles((long long)s * cap + cell, run));
+            pos += run; src += run; left -= run;
+        }
+        p->packed += n;
+    }
+    if (p->tile0.back() > INT_MAX) return set_err(BNHIP_E_INVALID, "the frames' stored samples must fit 2^31 - 1 tiles of 2048");
+    return BNHIP_OK;
+}
+
+void capture_write_failed(bnhip_capture_bank* b, const CapturePlan& p) {
+    for (int32_t s : p.listed) {
+        bnhip_capture_bank::Source& S = b->src[(size_t)s];
+        S.floor = std::max(S.floor, S.written + p.total[(size_t)s] - b->capacity);
+    }
+}
+
+void capture_write_commit(bnhip_capture_bank* b, const CapturePlan& p) {
+    for (int32_t s : p.listed) b->src[(size_t)s].written += p.total[(size_t)s];
+}
+
+}  // namespace bnhip
 
 extern "C" {
 
@@ -154,47 +188,12 @@ int bnhip_capture_bank_write(bnhip_capture_bank* b, int n_frames, const int32_t*
     std::lock_guard<std::mutex> lk(b->mu);
     const int64_t cap = b->capacity;
     const size_t bytes = (size_t)bits_per_sample / 8;
-    // ---- check, and each source's total
-    std::vector<int64_t> total((size_t)b->max_sources, 0);
-    std::vector<int32_t> listed;                                          // the call's sources, in the order they first appear
-    int64_t given = 0;
-    for (int f = 0; f < n_frames; f++) {
-        const std::string who = "frame " + std::to_string(f) + ": ";
-        if (sources[f] < 0 || sources[f] >= b->max_sources) return set_err(BNHIP_E_INVALID, who + "no such capture bank source: " + std::to_string(sources[f]));
-        if (n_samples[f] < 0) return set_err(BNHIP_E_INVALID, who + "negative frame length");
-        if (n_samples[f] > 0 && !frames[f]) return set_err(BNHIP_E_INVALID, who + "frame pointer is NULL");
-        if (n_samples[f] > RAGGED_MAX_SAMPLES - given) return set_err(BNHIP_E_INVALID, "the frames' total length must be below 2^36 samples");
-        given += n_samples[f];
-        if (total[(size_t)sources[f]] == 0 && n_samples[f] > 0) listed.push_back(sources[f]);
-        total[(size_t)sources[f]] += n_samples[f];
-    }
-    if (listed.empty()) return BNHIP_OK;
-    // ---- plan: per frame what is stored of it (a source's samples of this call but the last `capacity` are not), cut where the ring
-    // wraps.  Sample q of a source's call lies at position written + q, in cell (written + q) mod capacity: the stored ones are at
-    // most `capacity` consecutive positions, so no two of them share a cell.
-    struct Part { int frame; int64_t from, n; };                          // samples from .. from + n of the frame, packed in this order
-    std::vector<Part> parts;
-    std::vector<CapPiece> pieces;
-    std::vector<long long> tile0(1, 0);
-    std::vector<int64_t> seen((size_t)b->max_sources, 0);                 // samples of the source in the frames before
-    int64_t packed = 0;
-    for (int f = 0; f < n_frames; f++) {
-        const int s = sources[f];
-        const int64_t q0 = seen[(size_t)s], skip = std::max<int64_t>(total[(size_t)s] - cap, 0);
-        seen[(size_t)s] += n_samples[f];
-        const int64_t from = std::max(q0, skip) - q0, n = n_samples[f] - from;
-        if (n <= 0) continue;
-        parts.push_back(Part{f, from, n});
-        int64_t pos = b->src[(size_t)s].written + q0 + from, src = packed, left = n;
-        while (left > 0) {
-            const int64_t cell = pos % cap, run = std::min(left, cap - cell);
-            pieces.push_back(CapPiece{src, (long long)s * cap + cell, run});
-            tile0.push_back(tile0.back() + cut_tiles((long long)s * cap + cell, run));
-            pos += run; src += run; left -= run;
-        }
-        packed += n;
-    }
-    if (tile0.back() > INT_MAX) return set_err(BNHIP_E_INVALID, "the frames' stored samples must fit 2^31 - 1 tiles of 2048");
+    CapturePlan plan;
+    if (int rc = capture_plan(b, n_frames, sources, n_samples, frames, nullptr, &plan)) return rc;
+    if (plan.listed.empty()) return BNHIP_OK;
+    const std::vector<CapPiece>& pieces = plan.pieces;
+    const std::vector<long long>& tile0 = plan.tile0;
+    const int64_t packed = plan.packed;
     // ---- stage
     hipSetDevice(b->device);
     const size_t o_tile = pieces.size() * sizeof(CapPiece), o_pcm = (o_tile + tile0.size() * 8 + 15) / 16 * 16;
@@ -204,7 +203,7 @@ int bnhip_capture_bank_write(bnhip_capture_bank* b, int n_frames, const int32_t*
     memcpy(b->h_stage, pieces.data(), o_tile);
     memcpy(b->h_stage + o_tile, tile0.data(), tile0.size() * 8);
     uint8_t* pk = b->h_stage + o_pcm;
-    for (const Part& p : parts) {
+    for (const CapturePlan::Part& p : plan.parts) {
         memcpy(pk, static_cast<const uint8_t*>(frames[p.frame]) + (size_t)p.from * bytes, (size_t)p.n * bytes);
         pk += (size_t)p.n * bytes;
     }
@@ -222,15 +221,11 @@ int bnhip_capture_bank_write(bnhip_capture_bank* b, int n_frames, const int32_t*
     if (he == hipSuccess) he = hs;
     if (he != hipSuccess) {
         // the launch may have stored any part of what it was given: nothing it could have touched is readable again
-        if (launched)
-            for (int32_t s : listed) {
-                bnhip_capture_bank::Source& S = b->src[(size_t)s];
-                S.floor = std::max(S.floor, S.written + total[(size_t)s] - cap);
-            }
+        if (launched) capture_write_failed(b, plan);
         return cap_fail(WHAT, he);
     }
     // ---- commit: everything above succeeded
-    for (int32_t s : listed) b->src[(size_t)s].written += total[(size_t)s];
+    capture_write_commit(b, plan);
     return BNHIP_OK;
     BN_GUARD_END((void)0)
 }

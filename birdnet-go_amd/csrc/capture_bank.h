@@ -8,8 +8,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <mutex>
 #include <vector>
 
 #include "clips.h"
@@ -52,5 +54,51 @@ struct RingCutter : Cutter {
 // which form of k_ring_cut the library launches ("Capture bank": the measurement that chose it); the
 // environment variable BNHIP_RING_CUT=aligned|element overrides it for that measurement
 bool ring_cut_aligned();
+
+}  // namespace bnhip
+
+// The bank itself (api_capture_bank.cpp; api_level.cpp's fused write reaches it too).  The clocks are the host's.
+struct bnhip_capture_bank {
+    struct Source {
+        int64_t written = 0;            // samples given since creation or reset
+        int64_t floor = 0;              // no position below this one is readable
+    };
+    std::mutex mu;                      // calls on one bank are serialised
+    int device = 0, max_sources = 0, rate = 0;
+    int64_t capacity = 0;               // samples of one ring, a multiple of CAPTURE_ALIGN
+    std::vector<Source> src;
+    hipStream_t stream = nullptr;       // the writes' own
+    int16_t* d_rings = nullptr;         // [max_sources][capacity]
+    uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // pieces | tile prefix | packed frames
+    int64_t oldest(int s) const { return std::max<int64_t>({0, src[(size_t)s].written - capacity, src[(size_t)s].floor}); }
+    ~bnhip_capture_bank() {             // (bank_free has drained the stream)
+        if (stream) hipStreamDestroy(stream);
+        for (void* p : {(void*)d_rings, d_stage}) if (p) hipFree(p);
+        if (h_stage) hipHostFree(h_stage);
+    }
+};
+
+namespace bnhip {
+
+// What a write stores, worked out before any device call (under the bank's lock): the checks of bnhip_capture_bank_write, each
+// source's total, and per frame what is stored of it (a source's samples of this call but the last `capacity` are not), cut where
+// the ring wraps.  Sample q of a source's call lies at position written + q, in cell (written + q) mod capacity: the stored ones are
+// at most `capacity` consecutive positions, so no two of them share a cell.
+struct CapturePlan {
+    struct Part { int frame; int64_t from, n; };          // samples from .. from + n of the frame are stored
+    std::vector<int64_t> total;                           // [max_sources]: the call's samples of each source
+    std::vector<int32_t> listed;                          // the call's sources, in the order they first appear
+    std::vector<Part> parts;
+    std::vector<CapPiece> pieces;
+    std::vector<long long> tile0;                         // [pieces + 1]
+    int64_t packed = 0;                                   // stored samples, all parts
+};
+// frame_at NULL: the parts are staged packed back to back in parts order (a piece's src counts from there); else frame f's sample 0
+// is staged at sample frame_at[f] of the PCM and the frames are staged whole.  -> BNHIP_OK or BNHIP_E_INVALID
+int capture_plan(const bnhip_capture_bank* b, int n_frames, const int32_t* sources, const int64_t* n_samples, const void* const* frames,
+                 const int64_t* frame_at, CapturePlan* p);
+// "a failed write" of bnhip.h: nothing the launch could have touched is readable again
+void capture_write_failed(bnhip_capture_bank* b, const CapturePlan& p);
+void capture_write_commit(bnhip_capture_bank* b, const CapturePlan& p);
 
 }  // namespace bnhip

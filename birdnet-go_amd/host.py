@@ -73,7 +73,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_event_bank_create_extended", "bnhip_event_bank_set_extend", "bnhip_event_deadline",
            "bnhip_event_bank_create_dynamic", "bnhip_event_bank_set_dynamic", "bnhip_event_bank_set_now",
            "bnhip_event_bank_threshold_changes", "bnhip_event_bank_thresholds", "bnhip_event_bank_set_thresholds",
-           "bnhip_event_bank_reset_thresholds", "bnhip_event_threshold"]
+           "bnhip_event_bank_reset_thresholds", "bnhip_event_threshold", "bnhip_audio_level", "bnhip_level_bank_create",
+           "bnhip_level_bank_add_stream", "bnhip_level_bank_remove_stream", "bnhip_level_bank_process_pcm", "bnhip_level_bank_latest",
+           "bnhip_level_bank_stats", "bnhip_level_bank_reset", "bnhip_level_bank_destroy", "bnhip_capture_bank_write_levels"]
 
 
 class HipError(RuntimeError):
@@ -673,6 +675,7 @@ def _capture_bank_protos(lib):
     lib.bnhip_capture_bank_positions.argtypes = [vp, vp, vp]
     lib.bnhip_capture_bank_reset.argtypes = [vp, ci]
     lib.bnhip_capture_bank_write.argtypes = [vp, ci, vp, vp, vp, ci]
+    lib.bnhip_capture_bank_write_levels.argtypes = [vp, vp, ci, vp, vp, vp, vp, ci, vp]
     lib.bnhip_capture_bank_read_pcm16.argtypes = [vp, vp, ci, vp]
     lib.bnhip_capture_bank_clips.argtypes = [vp, vp, ci, vp, vp]
     lib.bnhip_capture_bank_destroy.argtypes = [vp]
@@ -682,6 +685,28 @@ def _capture_bank_protos(lib):
 
 
 CAPTURE_OK, CAPTURE_CLAMPED, CAPTURE_NOT_YET, CAPTURE_GONE, CAPTURE_DROPPED = 0, 1, 2, 3, 4
+
+# bnhip_audio_level_data / bnhip_audio_level_stats (include/bnhip.h, "Audio level bank")
+AUDIO_LEVEL = np.dtype([("stream", "<i4"), ("frame", "<i4"), ("level", "<i4"), ("clipping", "<i4"), ("n_samples", "<i8"),
+                        ("clipped_samples", "<i8"), ("sum_squares", "<u8")])
+AUDIO_LEVEL_STATS = np.dtype([("sum", "<i8"), ("count", "<i8"), ("zero_count", "<i8"), ("clip_count", "<i8"), ("min", "<i4"), ("max", "<i4"),
+                              ("avg_level", "<i4"), ("zero_pct", "<i4"), ("clipping_pct", "<i4"), ("_pad", "<i4")])
+
+
+def _pcm_frames(frames, bit_depth, whole):
+    """PCM frames (bytes or arrays) of bit_depth -> (uint8 arrays kept alive, int64 sample counts, C array of their addresses) for
+    the capture and level bank entries.  A frame that is not whole samples is refused; with whole=False a 16-bit frame of an odd
+    byte count loses its last byte instead, as calculateAudioLevel truncates it (buffer_consumer.go:279-287)."""
+    size = bit_depth // 8 if bit_depth in (16, 24, 32) else 1
+    keep = [np.ascontiguousarray(f).reshape(-1).view(np.uint8) if isinstance(f, np.ndarray) else np.frombuffer(f, np.uint8) for f in frames]
+    if not whole and bit_depth == 16:
+        keep = [a[:a.size & ~1] for a in keep]
+    for a in keep:
+        if a.size % size:
+            raise HipError(E_INVALID, f"frame of {a.size} bytes is not whole {bit_depth}-bit samples")
+    n = np.array([a.size // size for a in keep], np.int64)
+    ptr = (C.c_void_p * max(len(keep), 1))(*[a.ctypes.data if a.size else None for a in keep])
+    return keep, n, ptr
 
 
 def capture_spans(events, written, oldest, hop, settings, origins=None):
@@ -726,18 +751,24 @@ class CaptureBank:
             raise HipError(E_INVALID, "capture bank is closed")
         return self._h
 
-    def write(self, frames, bit_depth=16):
+    def write(self, frames, bit_depth=16, levels=None):
         """frames: [(source, PCM bytes or array), ...] - one call per tick for every source; a source may appear several times, its
-        frames are appended in call order.  bit_depth 16, 24 or 32: what the bytes hold; the rings keep int16."""
-        size = bit_depth // 8 if bit_depth in (16, 24, 32) else 1
-        keep = [np.ascontiguousarray(f).reshape(-1).view(np.uint8) if isinstance(f, np.ndarray) else np.frombuffer(f, np.uint8) for _, f in frames]
-        for a in keep:
-            if a.size % size:
-                raise HipError(E_INVALID, f"frame of {a.size} bytes is not whole {bit_depth}-bit samples")
+        frames are appended in call order.  bit_depth 16, 24 or 32: what the bytes hold; the rings keep int16.  levels: (a
+        LevelBank, its stream per frame, -1: not measured) - the frames are also measured where the upload has put them
+        (bnhip_capture_bank_write_levels) -> the AUDIO_LEVEL records, one per frame."""
+        keep, n, ptr = _pcm_frames([f for _, f in frames], bit_depth, whole=True)
         src = np.array([s for s, _ in frames], np.int32)
-        n = np.array([a.size // size for a in keep], np.int64)
-        ptr = (C.c_void_p * max(len(keep), 1))(*[a.ctypes.data if a.size else None for a in keep])
-        _check(self._lib, self._lib.bnhip_capture_bank_write(self._alive(), len(keep), src.ctypes.data, n.ctypes.data, ptr, int(bit_depth)))
+        if levels is None:
+            _check(self._lib, self._lib.bnhip_capture_bank_write(self._alive(), len(keep), src.ctypes.data, n.ctypes.data, ptr, int(bit_depth)))
+            return None
+        bank, streams = levels
+        st = np.array([int(s) for s in streams], np.int32)
+        if st.size != len(keep):
+            raise HipError(E_INVALID, "levels names one level bank stream per frame")
+        out = np.zeros(max(len(keep), 1), AUDIO_LEVEL)
+        _check(self._lib, self._lib.bnhip_capture_bank_write_levels(self._alive(), bank._alive(), len(keep), src.ctypes.data, st.ctypes.data,
+                                                                    n.ctypes.data, ptr, int(bit_depth), out.ctypes.data))
+        return out[:len(keep)]
 
     def positions(self):
         """-> (written int64 [max_sources], oldest int64 [max_sources])."""
@@ -2552,6 +2583,58 @@ class SoundLevelBank(_StreamBank):
                     "sample_count": r.sample_count[j]}
             out.append({"stream": r.stream, "frame": r.frame, "duration_seconds": r.duration_s, "octave_bands": bands})
         return out
+
+
+def audio_level(sum_squares, n, clipping):
+    """bnhip_audio_level (host only): calculateAudioLevel's level 0..100 (buffer_consumer.go:310-331) from a frame's integers -
+    the sum of the squares of its n int16 samples and whether any of them is full scale."""
+    lib = load_library()
+    lib.bnhip_audio_level.argtypes = [C.c_uint64, C.c_int64, C.c_int, C.POINTER(C.c_int)]
+    level = C.c_int(0)
+    _check(lib, lib.bnhip_audio_level(int(sum_squares), int(n), 1 if clipping else 0, C.byref(level)))
+    return level.value
+
+
+class LevelBank(_StreamBank):
+    """`bnhip_level_bank` (include/bnhip.h, "Audio level bank"): the input level meter (calculateAudioLevel behind an
+    AudioLevelConsumer route) for many sources of any rate, every call one device call.  `process([(stream, PCM), ...])` measures
+    each frame (a stream may appear several times; an empty frame is a measurement) and returns the AUDIO_LEVEL records, one per
+    frame: level 0..100, clipping, and the integers they came from.  `latest()` -> AUDIO_LEVEL [max_streams], stream -1 where dead or
+    never measured; `stats(stream, reset)` -> the accumulators of AudioLevelStats and logAndReset's derived fields as a dict.
+    Errors leave every stream untouched."""
+
+    _prefix, _what = "level_bank", "level bank"
+
+    def __init__(self, max_streams=256, device=0):
+        vp, ci = C.c_void_p, C.c_int
+        L = self._bind(create=[ci, ci, C.POINTER(vp)], process_pcm=[vp, ci, vp, vp, vp, ci, vp], latest=[vp, vp], stats=[vp, ci, ci, vp],
+                       reset=[vp, ci])
+        self.max_streams = int(max_streams)
+        _check(L, L.bnhip_level_bank_create(device, self.max_streams, C.byref(self._h)))
+
+    def process(self, frames, bit_depth=16):
+        """A 16-bit frame of an odd byte count loses its last byte, as the reference truncates it; for 24 and 32 bit, bytes that are
+        not whole samples are refused, as CaptureBank.write refuses them."""
+        keep, n, ptr = _pcm_frames([f for _, f in frames], bit_depth, whole=False)
+        st = np.array([int(s) for s, _ in frames], np.int32)
+        out = np.zeros(max(len(keep), 1), AUDIO_LEVEL)
+        _check(self._lib, self._lib.bnhip_level_bank_process_pcm(self._alive(), len(keep), st.ctypes.data, n.ctypes.data, ptr, int(bit_depth),
+                                                                 out.ctypes.data))
+        return out[:len(keep)]
+
+    def latest(self):
+        out = np.zeros(self.max_streams, AUDIO_LEVEL)
+        _check(self._lib, self._lib.bnhip_level_bank_latest(self._alive(), out.ctypes.data))
+        return out
+
+    def stats(self, stream, reset=False):
+        """reset: snapshot and start again, as logAndReset."""
+        out = np.zeros(1, AUDIO_LEVEL_STATS)
+        _check(self._lib, self._lib.bnhip_level_bank_stats(self._alive(), int(stream), 1 if reset else 0, out.ctypes.data))
+        return {k: int(out[0][k]) for k in AUDIO_LEVEL_STATS.names if k != "_pad"}
+
+    def reset(self, stream=-1):
+        _check(self._lib, self._lib.bnhip_level_bank_reset(self._alive(), int(stream)))
 
 
 class Perch:

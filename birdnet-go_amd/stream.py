@@ -660,6 +660,14 @@ class WindowBatcher:
     Native rings: the frames are queued and the next `tick()` runs one bank call per rate, after the EQ drain and before the
     resampler drain.  A failed call costs its own frames only (on_error), as the consumer logs the error and goes on.
 
+    `set_audio_level(source)` gives a source the input level meter (calculateAudioLevel behind an AudioLevelConsumer route,
+    internal/analysis/audio_level_consumer.go:65-93): every frame given to write(source, data) is one measurement, of the frame as
+    given - at the source's rate and BEFORE set_processing's EQ and gain, as the reference's level consumer is a route of its own
+    beside the analysis route - and `take_audio_levels()` returns the AudioLevelData-shaped results.  One host.LevelBank for all
+    sources.  Python rings: one bank call per write.  Native rings: the frames are queued and the next `tick()` measures every
+    source's queued frames in one bank call, ahead of the EQ drain.  A failed call costs its own frames only (on_error).
+    `audio_level_stats(source, reset)` answers the source's five-minute-summary accumulators.
+
     `events=` (a host.EventTables) adds the detection events of every tick (take_events, on_events).  With `capture=` (a
     CaptureSettings; native rings, with events) the bytes that reach a source's ring are also staged for the model's
     host.CaptureBank: a tick uploads them in one write call before the model call, and the events that became due are answered
@@ -710,6 +718,10 @@ class WindowBatcher:
         self.sl_streams = {}                 # source -> (source rate, stream of that rate's bank, name)
         self.sl_pending = {}                 # native: source rate -> [(source, stream, pcm bytes)] until the next tick
         self.sl_reports = []                 # finished reports until take_sound_levels()
+        self.al_bank = None                  # host.LevelBank of the metered sources (created on first use)
+        self.al_streams = {}                 # source -> (its stream of al_bank, name)
+        self.al_pending = []                 # native: [(source, stream, pcm bytes)] of metered sources until the next tick
+        self.al_reports = []                 # measurements until take_audio_levels()
         self.events = events                 # native: a host.EventTables -> detection events beside the Results (None: none)
         self.extend = extend                 # native: a host.EventExtend -> the models' event banks are created extended (None: not)
         self.dynamic = dynamic               # native: a host.EventDynamic -> the models' event banks learn their thresholds (None: not)
@@ -1020,6 +1032,76 @@ class WindowBatcher:
             if old is not None:
                 self.sl_banks[old[0]].remove_stream(old[1])
 
+    def set_audio_level(self, source, name=None):
+        """The source's input level meter; name defaults to the source.  Calling it again starts a fresh stream (empty
+        accumulators); frames queued before keep the old one."""
+        if self.al_pending:
+            self._drain_audio_levels()
+        with self.mu:
+            if self.al_bank is None:
+                self.al_bank = _host.LevelBank(self.BANK_STREAMS)
+            old = self.al_streams.pop(source, None)
+            if old is not None:
+                self.al_bank.remove_stream(old[0])
+            self.al_streams[source] = (self.al_bank.add_stream(), source if name is None else name)
+
+    def clear_audio_level(self, source):
+        """The source's meter stops; frames queued before still count."""
+        if self.al_pending:
+            self._drain_audio_levels()
+        with self.mu:
+            old = self.al_streams.pop(source, None)
+            if old is not None:
+                self.al_bank.remove_stream(old[0])
+
+    def take_audio_levels(self):
+        """-> the measurements since the last call, oldest first: {"timestamp" (the batcher's clock when the measurement came
+        back), "source", "name", "level" (0..100), "clipping" (bool)}, one per frame written to a metered source."""
+        with self.mu:
+            out, self.al_reports = self.al_reports, []
+        return out
+
+    def audio_level_stats(self, source, reset=False):
+        """host.LevelBank.stats of the source's stream: what the reference's five-minute summary logs (reset: and starts again)."""
+        if self.al_pending:
+            self._drain_audio_levels()
+        with self.mu:
+            if source not in self.al_streams:
+                raise StreamError(f"source {source!r} has no audio level meter")
+            return self.al_bank.stats(self.al_streams[source][0], reset)
+
+    def _audio_level_call(self, items):
+        """(under self.mu) One bank call over items [(source, stream, pcm bytes), ...] -> self.al_reports, or the error."""
+        try:
+            recs = self.al_bank.process([(st, raw) for _, st, raw in items])
+        except Exception as e:
+            self.errors += len(items)
+            return e
+        for (src, _, _), r in zip(items, recs):
+            name = self.al_streams.get(src, (None, src))[1]
+            self.al_reports.append({"timestamp": self.clock(), "source": src, "name": name, "level": int(r["level"]),
+                                    "clipping": bool(r["clipping"])})
+        return None
+
+    def _measure_level(self, source, stream, data):
+        """write()'s frame of a metered source: queued (native) or measured at once (python)."""
+        raw = _as_bytes(data).tobytes()
+        with self.mu:
+            if self.native:
+                self.al_pending.append((source, stream, raw))
+                return
+            err = self._audio_level_call([(source, stream, raw)])
+        if err is not None and self.on_error:
+            self.on_error(None, [source], err)
+
+    def _drain_audio_levels(self):
+        """Native: every metered source's queued frames through one device call (host.LevelBank)."""
+        with self.mu:
+            items, self.al_pending = self.al_pending, []
+            err = self._audio_level_call(items) if items else None
+        if err is not None and self.on_error:
+            self.on_error(None, sorted({src for src, *_ in items}), err)
+
     def take_sound_levels(self):
         """-> the finished reports since the last call, oldest first: {"timestamp" (the batcher's clock when the report was
         made), "source", "name", "duration_seconds", "octave_bands": {key: {"center_frequency_hz", "min_db", "max_db", "mean_db",
@@ -1064,6 +1146,9 @@ class WindowBatcher:
         (once per rate pair: buffer_consumer.go:184-210).  A processed source's bytes are processed first (set_processing)."""
         with self.mu:
             st = self.eq_streams.get(source)
+            al = self.al_streams.get(source)
+        if al is not None:                                        # the level route: the frame as given, before the EQ
+            self._measure_level(source, al[0], data)
         if st is not None:
             raw = _as_bytes(data).tobytes()
             try:
@@ -1302,6 +1387,11 @@ class WindowBatcher:
             for bank in self.sl_banks.values():
                 bank.close()
             self.sl_banks.clear()
+            if self.al_bank is not None:
+                self.al_bank.close()
+            self.al_bank = None
+            self.al_streams.clear()
+            self.al_pending.clear()
             for bank in list(self.event_banks.values()) + list(self.capture_banks.values()):
                 bank.close()
             self.event_banks.clear()
@@ -1313,6 +1403,8 @@ class WindowBatcher:
 
     def tick(self):
         if self.native:
+            if self.al_pending:
+                self._drain_audio_levels()
             if self.eq_pending:
                 self._drain_equalized()
             if self.sl_pending:

@@ -1243,6 +1243,79 @@ int bnhip_soundlevel_bank_process_pcm16(bnhip_soundlevel_bank* b, int n_frames, 
                                         const int* n_in, bnhip_sound_level* reports, int max_reports, int* n_reports);
 void bnhip_soundlevel_bank_destroy(bnhip_soundlevel_bank* b);
 
+/* Audio level bank: the per-source input level meter.  The reference gives every source an AudioLevelConsumer route
+ * (internal/analysis/audio_level_consumer.go:65-93) whose every frame goes through calculateAudioLevel
+ * (internal/analysis/buffer_consumer.go:252-332): an RMS level mapped to 0..100 and a clipping flag, which feed the level bars
+ * (internal/api/v2/audio/audio_level.go), the audio_level health check (internal/health/checks/audio.go:230-298) and the
+ * five-minute per-source summary (internal/analysis/audio_level_stats.go).  A bank measures every frame of a call in one device
+ * call; one bank serves sources of any rate, because the level does not depend on the rate.
+ *   the rule       For a frame of n int16 samples q[i]: sum = the exact integer sum of q[i]^2, clipping = any q[i] is 32767 or
+ *                  -32768.  Then in float64, in this order: rms = sqrt(double(sum) / double(n)); db = 20 * log10(rms / 32768.0);
+ *                  scaled = (db - (-60.0)) * (100.0 / 50.0); if clipping, scaled = max(scaled, 95.0); scaled clamped to [0, 100];
+ *                  level = (int)scaled, truncating.  n == 0 gives level 0 and no clipping, and is still a measurement (the
+ *                  reference publishes it); silence gives log10(0) = -Inf, which the clamp turns into 0.  The device computes the
+ *                  two integers, the host the rest.  A frame holds at most 2^23 samples: up to there sum <= 2^53, so the
+ *                  reference's running float64 sum is exact and equals the integer sum.
+ *   24 and 32 bit  The reference meters 16-bit PCM only.  This project's own rule for 24- and 32-bit input: the meter measures
+ *                  q = clamp(rint(x * 32768), -32768, 32767), x the float32 of "Detection clips" above - the sample the capture
+ *                  ring stores.
+ *   bnhip_audio_level  The rule from the integers on, host only, no device: *level from sum_squares, n_samples (0..2^23) and
+ *                  clipping != 0.  Uses the C library's sqrt and log10; a Go host may ignore it and use its own math.
+ *   create         max_streams fixes the slot table; one HIP stream per bank.  destroy: NULL-safe.
+ *   add_stream     a fresh stream: never measured, empty accumulators; slots of removed streams are reused fresh.
+ *   process_pcm    frames f = 0..n_frames-1: n_samples[f] samples of bits_per_sample (16, 24 or 32, little endian, packed) at
+ *                  frames[f], of stream streams[f]; a stream may appear several times, and an empty frame is a measurement.
+ *                  levels[f] receives frame f's record.  One transaction: every check, then the tables and the frames staged
+ *                  (each frame at a 16-byte line), one H2D copy, one launch, one D2H copy of the n_frames integer records, one
+ *                  synchronise, then the commit on the host: each frame's level by the rule and, per stream in call order,
+ *                  `latest` and the accumulators exactly as AudioLevelStats.Record (audio_level_stats.go:42-73): sum, count,
+ *                  min, max, count of level 0, count of clipping frames.  The accumulators live on the host: a failed call
+ *                  changes nothing.
+ *   latest         out [max_streams]: each live stream's last record; stream = -1 (the rest zero) where the slot is dead or was
+ *                  never measured.
+ *   stats          The accumulators of one stream and logAndReset's derived fields (audio_level_stats.go:107-134), all integer
+ *                  divisions: avg_level = sum / count, zero_pct = zero_count * 100 / count, clipping_pct = clip_count * 100 /
+ *                  count; count 0: all zero.  reset != 0: snapshot and start again, as logAndReset; `latest` stays.
+ *   reset          Stream `stream` (-1: all live streams): latest and the accumulators cleared.  Host work only.
+ *   bnhip_capture_bank_write_levels  bnhip_capture_bank_write ("Capture bank" above) with the frames also measured where the
+ *                  upload has put them.  level_streams[f] names the level bank's stream for frame f; -1: the frame is stored
+ *                  but not measured - levels[f].stream is -1 and the level bank does not see it.  Both banks must be on one
+ *                  device; the capture bank's lock is taken first.  Both banks' checks, then one staging copy - whole frames,
+ *                  each at a 16-byte line - the ring write and the level launch on the capture bank's stream, one D2H copy of
+ *                  the records, one synchronise, then both commits.  A source whose frames exceed its ring is stored trimmed, as
+ *                  bnhip_capture_bank_write does, but measured in full: that is why this form stages whole frames.  On a device
+ *                  failure the capture bank applies "a failed write" and the level bank is unchanged.  The 2^23-sample limit
+ *                  applies to measured frames only.  The rings and clocks end as after bnhip_capture_bank_write of the frames.
+ * BNHIP_E_INVALID (before any device call, the handle stays usable): NULL where a pointer is required, max_streams outside
+ * 1..65535, bits_per_sample not 16, 24 or 32, an unknown or removed stream, a negative length, a measured frame above 2^23 samples,
+ * a NULL frame of non-zero length, a total of 2^36 samples or more, banks on different devices, and what bnhip_capture_bank_write
+ * refuses.  Allocation failure: BNHIP_E_NOMEM.  Calls on one bank are serialised internally; the same call gives the same bytes
+ * on every run.  Single-device handles. */
+typedef struct bnhip_level_bank bnhip_level_bank;
+typedef struct bnhip_audio_level_data {    /* one AudioLevelData (buffer_consumer.go:243-248) + the integers it came from */
+    int32_t stream, frame;                 /* frame: index in the call */
+    int32_t level, clipping;
+    int64_t n_samples, clipped_samples;
+    uint64_t sum_squares;
+} bnhip_audio_level_data;
+typedef struct bnhip_audio_level_stats {   /* audioLevelAccum + logAndReset's derived fields */
+    int64_t sum, count, zero_count, clip_count;
+    int32_t min, max, avg_level, zero_pct, clipping_pct;   /* count 0: all zero */
+} bnhip_audio_level_stats;
+int bnhip_audio_level(uint64_t sum_squares, int64_t n_samples, int clipping, int* level);
+int bnhip_level_bank_create(int device, int max_streams, bnhip_level_bank** out);
+int bnhip_level_bank_add_stream(bnhip_level_bank* b, int* out_stream);
+int bnhip_level_bank_remove_stream(bnhip_level_bank* b, int stream);
+int bnhip_level_bank_process_pcm(bnhip_level_bank* b, int n_frames, const int32_t* streams, const int64_t* n_samples,
+                                 const void* const* frames, int bits_per_sample, bnhip_audio_level_data* levels);
+int bnhip_level_bank_latest(bnhip_level_bank* b, bnhip_audio_level_data* out);
+int bnhip_level_bank_stats(bnhip_level_bank* b, int stream, int reset, bnhip_audio_level_stats* out);
+int bnhip_level_bank_reset(bnhip_level_bank* b, int stream);
+void bnhip_level_bank_destroy(bnhip_level_bank* b);
+int bnhip_capture_bank_write_levels(bnhip_capture_bank* capture_bank, bnhip_level_bank* level_bank, int n_frames, const int32_t* sources,
+                                    const int32_t* level_streams, const int64_t* n_samples, const void* const* frames,
+                                    int bits_per_sample, bnhip_audio_level_data* levels);
+
 /* Stream plumbing for hosts that own a HIP stream (bench harness: torch's current stream). */
 int bnhip_set_stream(bnhip_model* m, void* hip_stream);
 int bnhip_synchronize(bnhip_model* m);
