@@ -89,6 +89,7 @@ struct Rows { float threshold; bnhip_detection* out; size_t cap; size_t* n_out; 
 struct Events {
     const bnhip_event_filter* filter; bnhip_event* out; size_t cap; size_t* n_out;
     bool extended = false; const bnhip_event_extend* extend = nullptr;      // the _extended entries: under this extend, then required
+    bool guarded = false; const bnhip_event_guards* guards = nullptr;       // the _guarded entries: under these guards, then required
     bool complete() const { return n_out && (!cap || out); }
 };
 // what bnhip_analyze_channels_pcm_clips adds to its events call: the export settings and where everything goes (clips.h)
@@ -111,6 +112,8 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
     if (!std::visit([](const auto& w) { return w.complete(); }, a.what)) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (ev) if (int rc = event_filter_check(ev->filter)) return rc;
     if (ev && ev->extended) if (int rc = event_extend_check(ev->filter->hold_windows, ev->extend)) return rc;
+    if (ev && ev->guarded) if (int rc = event_guards_check(ev->guards)) return rc;
+    if (ev && ev->guarded) if (int rc = event_guards_spans_check(ev->guards, rec.n - 1)) return rc;
     if (rec.bits != 0 && rec.bits != 16 && rec.bits != 24 && rec.bits != 32)
         return set_err(BNHIP_E_INVALID, "unsupported bit depth: " + std::to_string(rec.bits) + " (supported: 0 = float32, 16, 24, 32)");
     if (q.k <= 0) return set_err(BNHIP_E_INVALID, "k must be positive");
@@ -144,11 +147,12 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
     cv.own_below = 0;
     const SlotDev dv = slot_reserve(sp, cv);
     const size_t o_table = cv.add(table.size() * 8), o_conf = cv.add(tk_bytes), o_idx = cv.add(tk_bytes);
-    size_t o_scr = 0, o_total = 0, o_rows = 0, o_evtab = 0, o_evscr = 0, o_evout = 0;
+    size_t o_scr = 0, o_total = 0, o_rows = 0, o_evtab = 0, o_evscr = 0, o_evout = 0, o_evguards = 0;
     if (!tk) { o_scr = cv.add(detections_scratch_bytes(W)); o_total = cv.add(8); o_rows = cv.add(rows_cap * sizeof(DetRow)); }
     if (ev) {
-        o_evtab = cv.add(event_tables_bytes(e.n_classes, ev->extended)); o_evscr = cv.add(events_scratch_bytes(n_rows_max));
+        o_evtab = cv.add(event_tables_bytes(e.n_classes, ev->extended)); o_evscr = cv.add(events_scratch_bytes(n_rows_max, ev->guarded && ev->guards->class_dog));
         o_evout = cv.add(out_cap * sizeof(Event));
+        if (ev->guarded) o_evguards = cv.add(event_guards_bytes(e.n_classes, ev->guards));
     }
     DevBlocks b;
     cv.alloc(b);
@@ -157,6 +161,7 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
     AN_HIP(b, hipMemcpyAsync(cv.at<void>(o_table), table.data(), table.size() * 8, hipMemcpyHostToDevice, e.stream));
     EventFilterDev fd{};
     if (ev) fd = event_filter_upload(ev->filter, e.n_classes, cv.at<char>(o_evtab), e.stream, b, ev->extended ? ev->extend : nullptr);
+    if (ev && ev->guarded) event_guards_upload(ev->guards, e.n_classes, cv.at<char>(o_evguards), e.stream, b, fd);
     WinView view;
     view.first = cv.at<long long>(o_table);
     view.slot = view.first + rec.n + 1;
@@ -343,19 +348,32 @@ int bnhip_analyze_channels_pcm_events_extended(bnhip_model* m, const void* pcm, 
     BN_GUARD_END((void)0)
 }
 
+int bnhip_analyze_channels_pcm_events_guarded(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                              int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                              const bnhip_event_filter* filter, const bnhip_event_extend* extend,
+                                              const bnhip_event_guards* guards, bnhip_event* out, size_t cap, size_t* n_out, int32_t* chosen) {
+    BN_GUARD_BEGIN
+    return analyze_entry(AN_REQUEST, {.what = Events{.filter = filter, .out = out, .cap = cap, .n_out = n_out, .extended = extend != nullptr,
+                                                     .extend = extend, .guarded = true, .guards = guards},
+                                      .chosen = chosen},
+                        recs, n_recordings, model_rate);
+    BN_GUARD_END((void)0)
+}
+
 }  // extern "C"
 
 // the events call with the clip export as its continuation (clips.h; the span rule and the export itself: api_clips.cpp)
 static int analyze_clips(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings, int model_rate, int hop,
                          int64_t min_tail, int activation, double sensitivity, int k, const bnhip_event_filter* filter, bool extended,
-                         const bnhip_event_extend* extend, int32_t* chosen, const bnhip_clip_export* x, bnhip_clips_out* out) {
+                         const bnhip_event_extend* extend, int32_t* chosen, const bnhip_clip_export* x, bnhip_clips_out* out,
+                         bool guarded = false, const bnhip_event_guards* guards = nullptr) {
     if (int rc = clip_export_check(x, out, model_rate)) return rc;
     if (int rc = event_filter_check(filter)) return rc;
     if (filter->flags & BNHIP_EVENTS_KEEP_DROPPED) return set_err(BNHIP_E_INVALID, "the clip export takes kept events only: BNHIP_EVENTS_KEEP_DROPPED is refused");
     const ClipsTail tail{x, out, model_rate};
     size_t n_events = 0;
     return analyze_entry(AN_REQUEST, {.what = Events{.filter = filter, .out = out->events, .cap = out->event_cap, .n_out = &n_events,
-                                                     .extended = extended, .extend = extend},
+                                                     .extended = extended, .extend = extend, .guarded = guarded, .guards = guards},
                                       .chosen = chosen, .clips = &tail},
                         recs, n_recordings, model_rate);
 }
@@ -376,6 +394,17 @@ int bnhip_analyze_channels_pcm_clips_extended(bnhip_model* m, const void* pcm, c
                                               const bnhip_clip_export* x, bnhip_clips_out* out) {
     BN_GUARD_BEGIN
     return analyze_clips(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, filter, true, extend, chosen, x, out);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_analyze_channels_pcm_clips_guarded(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                             int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                             const bnhip_event_filter* filter, const bnhip_event_extend* extend,
+                                             const bnhip_event_guards* guards, int32_t* chosen, const bnhip_clip_export* x,
+                                             bnhip_clips_out* out) {
+    BN_GUARD_BEGIN
+    return analyze_clips(m, pcm, recs, n_recordings, model_rate, hop, min_tail, activation, sensitivity, k, filter, extend != nullptr, extend,
+                         chosen, x, out, true, guards);
     BN_GUARD_END((void)0)
 }
 

@@ -11,6 +11,12 @@
 // pair of slabs with a parity of its own that the same commit flips; its call passes an EvdCall to the launches, and the first 16
 // change records come down beside the head in the same copy, in the room of as many first events.  A bank created without one
 // takes exactly the path it took before.
+//
+// Guards (include/bnhip.h, "Detection events: dog-bark and daylight filters") are a setting like the filter: their three class
+// tables are a part of the bank's tables that exists from the first set_guards on, and the daylight spans of the call's sources
+// ride behind the row map in the header copy - no launch and no copy is added, and a bank that never had guards set builds the
+// header it built before.  A source's dog window lives in its slab, so the commit covers it; a source that may hold one stays
+// live across a flush (its freed slab is written to the other parity), since a bark counts for events that open after it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,7 +42,8 @@ struct bnhip_event_bank {
     struct Source {
         int64_t clock = 0;              // windows given since creation or reset
         int parity = 0;                 // slab read by the next call
-        bool live = false;              // the slab holds state (false: every slot free, no veto window)
+        bool live = false;              // the slab holds state (false: every slot free, no veto window, no dog window)
+        bool dog = false;               // a call under guards with a dog table has written the slab: it may hold a dog window
     };
     std::mutex mu;                      // calls on one bank are serialised
     std::mutex tick_mu;                 // ... and so are the ticks that feed it: d_rows is theirs from the first chunk to the bank's call
@@ -54,6 +61,12 @@ struct bnhip_event_bank {
     int cls_parity = 0;                 // slab of the class state read by the next call
     char* d_dyn = nullptr;              // evd_area_bytes(n_classes)
     std::vector<bnhip_threshold_change> changes;   // the records of the last successful process / flush call
+    bool guarded = false;               // guards are in force (set_guards)
+    bool has_guards = false;            // ... or were once: the tables carry their three parts behind the others
+    bool g_dog = false, g_dog_filtered = false, g_daylight = false;      // which of the three tables the guards in force have
+    float dog_thr = 0.0f;
+    int dog_remember = 0;
+    std::vector<int32_t> day;           // [max_sources][8][2] daylight spans from the first set_daylight on; an unused span is 0, 0
     bool tables_dirty = true;           // h_tab is newer than d_tab: the next call's header copy takes it along
     std::vector<Source> src;
     hipStream_t stream = nullptr;       // the bank's own, made at the first call that needs it: a bank fed by the tick alone runs on
@@ -62,7 +75,9 @@ struct bnhip_event_bank {
     char* h_tab = nullptr; char* d_tab = nullptr;                                 // class_threshold [n_classes] | class_veto [n_classes]
                                                                                   // | extended: class_extended [n_classes]
                                                                                   // | dynamic: class_dynamic [n_classes]
-    size_t tab_bytes() const { return (size_t)n_classes * (5 + (extended ? 1 : 0) + (dynamic ? 1 : 0)); }
+                                                                                  // | guards: class_dog, class_dog_filtered, class_daylight
+    size_t guards_tab_off() const { return (size_t)n_classes * (5 + (extended ? 1 : 0) + (dynamic ? 1 : 0)); }
+    size_t tab_bytes() const { return guards_tab_off() + (has_guards ? (size_t)n_classes * 3 : 0); }
     size_t dyn_tab_off() const { return (size_t)n_classes * (extended ? 6 : 5); }
     uint8_t* h_stage = nullptr; void* d_stage = nullptr; size_t stage_cap = 0;   // groups | row map | rows
     uint8_t* h_out = nullptr; void* d_out = nullptr; size_t out_cap = 0;         // count, overflow flag | events
@@ -175,7 +190,8 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
         EvbGroup g{};
         g.source = source; g.clock = (int32_t)S.clock; g.n_windows = n_windows; g.row_off = row_off;
         g.stage_off = (uint32_t)stage_total; g.stage_cap = (uint32_t)room;
-        g.rd_parity = S.live ? S.parity : -1; g.wr_parity = S.parity ^ 1;
+        g.rd_parity = S.live ? S.parity : -1;
+        g.wr_parity = mode == EVB_PROCESS || (mode == EVB_FLUSH && S.dog) ? (S.parity ^ 1) : -1;
         groups.push_back(g);
         stage_total += room;
     };
@@ -222,8 +238,10 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
     hipSetDevice(b->device);
     if (own_stream && !(s = evb_stream(b))) return BNHIP_E_RUNTIME;
     const size_t G = groups.size(), row_vals = on_device || mode != EVB_PROCESS ? 0 : (size_t)n_rows * (size_t)k;
+    const bool marks_dog = b->guarded && b->g_dog, daylight = b->guarded && b->g_daylight && !b->day.empty() && mode != EVB_PENDING;
     const size_t o_map = G * sizeof(EvbGroup), o_conf = o_map + rowmap.size() * 4, o_idx = o_conf + row_vals * 4;
-    const size_t stage_bytes = o_idx + row_vals * 4;
+    const size_t o_day = o_idx + row_vals * 4, day_bytes = daylight ? G * EVB_DAYLIGHT_SPANS * 8 : 0;     // the sources' spans, by group
+    const size_t stage_bytes = o_day + day_bytes;
     const size_t out_room = std::min(cap, stage_total);
     const size_t o_ev = EVB_HEAD + (dyn ? (size_t)EVD_FIRST_CHANGES * sizeof(ThresholdChange) : 0);   // head | dyn: the first change records | events
     const size_t o_counts = stage_total * sizeof(Event);
@@ -243,6 +261,9 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
         memcpy(b->h_stage + o_conf, conf, row_vals * 4);
         memcpy(b->h_stage + o_idx, idx, row_vals * 4);
     }
+    for (size_t gi = 0; day_bytes && gi < G; gi++)
+        memcpy(b->h_stage + o_day + gi * EVB_DAYLIGHT_SPANS * 8, b->day.data() + (size_t)groups[gi].source * EVB_DAYLIGHT_SPANS * 2,
+               EVB_DAYLIGHT_SPANS * 8);
     hipError_t he = hipSuccess;
     if (b->tables_dirty) he = hipMemcpyAsync(b->d_tab, b->h_tab, b->tab_bytes(), hipMemcpyHostToDevice, s);
     if (he == hipSuccess && stage_bytes) he = hipMemcpyAsync(b->d_stage, b->h_stage, stage_bytes, hipMemcpyHostToDevice, s);
@@ -258,6 +279,7 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
     c.conf = row_vals ? reinterpret_cast<const float*>(ds + o_conf) : conf;
     c.idx = row_vals ? reinterpret_cast<const int32_t*>(ds + o_idx) : idx;
     c.k = k; c.slots = b->slots; c.mode = mode; c.extended = b->extended;
+    c.day = day_bytes ? reinterpret_cast<const int32_t*>(ds + o_day) : nullptr;
     c.state = b->d_state;
     c.stage = reinterpret_cast<Event*>(dw);
     c.counts = reinterpret_cast<uint32_t*>(dw + o_counts);
@@ -267,6 +289,13 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
     EventFilterDev fd{reinterpret_cast<const float*>(b->d_tab), reinterpret_cast<const uint8_t*>(b->d_tab) + (size_t)b->n_classes * 4,
                       b->veto_thr, b->hold, b->min_count, b->flags, b->n_classes};
     if (b->extended) { fd.slide = reinterpret_cast<const uint8_t*>(b->d_tab) + (size_t)b->n_classes * 5; fd.x = b->x; }
+    if (b->guarded) {
+        const uint8_t* gt = reinterpret_cast<const uint8_t*>(b->d_tab) + b->guards_tab_off();
+        const size_t n = (size_t)b->n_classes;
+        fd.g.dog = b->g_dog ? gt : nullptr; fd.g.dog_filtered = b->g_dog_filtered ? gt + n : nullptr;
+        fd.g.daylight = b->g_daylight ? gt + 2 * n : nullptr;
+        fd.g.dog_thr = b->dog_thr; fd.g.dog_remember = b->dog_remember;
+    }
     if (dyn) {
         EvdCall d{};
         d.area = b->d_dyn; d.rd_parity = b->cls_parity; d.base = fd.thr;
@@ -322,9 +351,14 @@ int evb_call(bnhip_event_bank* b, int mode, const int32_t* sources, int n_rows, 
     if (dyn) b->cls_parity ^= 1;
     for (const EvbGroup& g : groups) {
         bnhip_event_bank::Source& S = b->src[(size_t)g.source];
-        if (mode == EVB_FLUSH) { S.live = false; continue; }             // (no slot is live any more, and the veto windows lie behind the clock)
+        if (mode == EVB_FLUSH) {
+            if (g.wr_parity >= 0) S.parity ^= 1;                         // (the freed slab keeps the dog window)
+            else S.live = false;                                         // (no slot is live any more, and the veto windows lie behind the clock)
+            continue;
+        }
         S.parity ^= 1;
         S.live = true;
+        S.dog = S.dog || marks_dog;
         S.clock += g.n_windows;
     }
     return BNHIP_OK;
@@ -530,6 +564,70 @@ int bnhip_event_bank_set_filter(bnhip_event_bank* b, const bnhip_event_filter* f
     BN_GUARD_END((void)0)
 }
 
+int bnhip_event_bank_set_guards(bnhip_event_bank* b, const bnhip_event_guards* guards) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (guards) if (int rc = event_guards_check(guards)) return rc;
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (!guards) { b->guarded = false; return BNHIP_OK; }
+    const size_t n = (size_t)b->n_classes;
+    if (!b->has_guards) {               // the tables grow by the guards' three parts, once (the bank is idle: every call ends synchronised)
+        hipSetDevice(b->device);
+        const size_t bytes = b->guards_tab_off() + n * 3;
+        char* nh = nullptr; char* nd = nullptr;
+        hipError_t he = hipHostMalloc((void**)&nh, bytes, hipHostMallocPortable);
+        if (he == hipSuccess) he = hipMalloc((void**)&nd, bytes);
+        if (he != hipSuccess) {
+            if (nh) hipHostFree(nh);
+            (void)hipGetLastError();
+            return set_err(BNHIP_E_NOMEM, std::string("allocation failed (") + WHAT + " guards)");
+        }
+        memcpy(nh, b->h_tab, b->guards_tab_off());
+        hipHostFree(b->h_tab); hipFree(b->d_tab);
+        b->h_tab = nh; b->d_tab = nd;
+        b->has_guards = true;
+    }
+    uint8_t* gt = reinterpret_cast<uint8_t*>(b->h_tab) + b->guards_tab_off();
+    const uint8_t* tables[3] = {guards->class_dog, guards->class_dog_filtered, guards->class_daylight};
+    for (int t = 0; t < 3; t++) {
+        if (tables[t]) memcpy(gt + n * t, tables[t], n);
+        else memset(gt + n * t, 0, n);
+    }
+    b->g_dog = guards->class_dog != nullptr; b->g_dog_filtered = guards->class_dog_filtered != nullptr;
+    b->g_daylight = guards->class_daylight != nullptr;
+    b->dog_thr = guards->dog_threshold; b->dog_remember = guards->dog_remember_windows;
+    b->guarded = true;
+    b->tables_dirty = true;
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_event_bank_set_daylight(bnhip_event_bank* b, int source, const int32_t* spans, int n) {
+    if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (n < 0 || n > EVB_DAYLIGHT_SPANS) return set_err(BNHIP_E_INVALID, "a source takes 0 to 8 daylight spans");
+    if (n > 0 && !spans) return set_err(BNHIP_E_INVALID, "NULL argument");
+    for (int i = 0; i < n; i++) {
+        if (spans[2 * i] < 0 || spans[2 * i + 1] <= spans[2 * i])
+            return set_err(BNHIP_E_INVALID, "daylight span " + std::to_string(i) + ": needs 0 <= from < to");
+        if (i && spans[2 * i] < spans[2 * i - 1])
+            return set_err(BNHIP_E_INVALID, "daylight span " + std::to_string(i) + ": spans must ascend and not overlap");
+    }
+    BN_GUARD_BEGIN
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (source < -1 || source >= b->max_sources) return set_err(BNHIP_E_INVALID, "no such event bank source: " + std::to_string(source));
+    if (source < 0 && n != 0) return set_err(BNHIP_E_INVALID, "source -1 only clears: n must be 0");
+    if (source < 0) { std::fill(b->day.begin(), b->day.end(), 0); return BNHIP_OK; }
+    if (b->day.empty()) {
+        if (n == 0) return BNHIP_OK;
+        b->day.assign((size_t)b->max_sources * EVB_DAYLIGHT_SPANS * 2, 0);
+    }
+    int32_t* at = b->day.data() + (size_t)source * EVB_DAYLIGHT_SPANS * 2;
+    std::fill_n(at, EVB_DAYLIGHT_SPANS * 2, 0);
+    if (n) memcpy(at, spans, (size_t)n * 8);
+    return BNHIP_OK;
+    BN_GUARD_END((void)0)
+}
+
 int bnhip_event_bank_set_extend(bnhip_event_bank* b, const bnhip_event_extend* extend) {
     if (!b) return set_err(BNHIP_E_INVALID, "NULL argument");
     BN_GUARD_BEGIN
@@ -588,7 +686,9 @@ int bnhip_event_bank_reset(bnhip_event_bank* b, int source) {
     if (source < -1 || source >= b->max_sources) return set_err(BNHIP_E_INVALID, "no such event bank source: " + std::to_string(source));
     for (int sn = source < 0 ? 0 : source; sn < (source < 0 ? b->max_sources : source + 1); sn++) {
         b->src[(size_t)sn].live = false;
+        b->src[(size_t)sn].dog = false;
         b->src[(size_t)sn].clock = 0;
+        if (!b->day.empty()) std::fill_n(b->day.begin() + (size_t)sn * EVB_DAYLIGHT_SPANS * 2, EVB_DAYLIGHT_SPANS * 2, 0);
     }
     return BNHIP_OK;
     BN_GUARD_END((void)0)

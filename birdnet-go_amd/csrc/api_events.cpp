@@ -55,6 +55,44 @@ EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, c
     return fd;
 }
 
+int event_guards_check(const bnhip_event_guards* g) {
+    if (!g) return set_err(BNHIP_E_INVALID, "NULL event guards");
+    if (g->dog_remember_windows < 0) return set_err(BNHIP_E_INVALID, "dog_remember_windows must not be negative");
+    return BNHIP_OK;
+}
+
+int event_guards_spans_check(const bnhip_event_guards* g, int max_recording) {
+    if (g->n_spans < 0 || g->n_spans > (1 << 20)) return set_err(BNHIP_E_INVALID, "n_spans must be in [0, 2^20]");
+    if (g->n_spans > 0 && !g->daylight_spans) return set_err(BNHIP_E_INVALID, "NULL daylight_spans");
+    for (int i = 0; i < g->n_spans; i++) {
+        const int32_t* sp = g->daylight_spans + (size_t)i * 3;
+        const std::string who = "daylight span " + std::to_string(i) + ": ";
+        if (sp[0] < 0 || sp[0] > max_recording) return set_err(BNHIP_E_INVALID, who + "recording outside the call");
+        if (sp[1] < 0 || sp[2] <= sp[1]) return set_err(BNHIP_E_INVALID, who + "needs 0 <= from < to");
+        if (i && (sp[0] < sp[-3] || (sp[0] == sp[-3] && sp[1] < sp[-1])))
+            return set_err(BNHIP_E_INVALID, who + "spans must ascend by (recording, from) and not overlap");
+    }
+    return BNHIP_OK;
+}
+
+void event_guards_upload(const bnhip_event_guards* g, int n_classes, char* d_guards, hipStream_t s, DevBlocks& b, EventFilterDev& fd) {
+    const size_t n = (size_t)n_classes;
+    const uint8_t* tables[3] = {g->class_dog, g->class_dog_filtered, g->class_daylight};
+    const uint8_t* dev[3] = {nullptr, nullptr, nullptr};
+    for (int t = 0; t < 3; t++) {
+        if (!tables[t]) continue;
+        dev[t] = reinterpret_cast<const uint8_t*>(d_guards) + n * t;
+        if (b.he == hipSuccess) b.he = hipMemcpyAsync(d_guards + n * t, tables[t], n, hipMemcpyHostToDevice, s);
+    }
+    char* d_spans = d_guards + (n * 3 + 3) / 4 * 4;
+    if (g->n_spans > 0 && b.he == hipSuccess)
+        b.he = hipMemcpyAsync(d_spans, g->daylight_spans, (size_t)g->n_spans * 12, hipMemcpyHostToDevice, s);
+    fd.g.dog = dev[0]; fd.g.dog_filtered = dev[1]; fd.g.daylight = dev[2];
+    fd.g.dog_thr = g->dog_threshold; fd.g.dog_remember = g->dog_remember_windows;
+    fd.g.spans = g->n_spans > 0 ? reinterpret_cast<const int32_t*>(d_spans) : nullptr;
+    fd.g.n_spans = g->n_spans;
+}
+
 void fetch_counted(const void* d_total, const void* d_records, size_t record_bytes, size_t cap, void* out, unsigned long long* total, hipStream_t s,
                    DevBlocks& b) {
     if (b.he == hipSuccess) b.he = hipMemcpyAsync(total, d_total, 8, hipMemcpyDeviceToHost, s);
@@ -72,13 +110,16 @@ namespace {
 
 // the tail alone over rows the host holds: one pass over the rows for every refusal, one DevCarve (rows, their count, the filter's
 // tables, the scratch, the events), the rows and tables up, the tail's launches, the count and the events down.  extended: under
-// `extend`, which is then required
+// `extend`, which is then required; guarded: under `guards`, which are then required
 int detection_events(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter, bool extended,
-                     const bnhip_event_extend* extend, bnhip_event* out, size_t cap, size_t* n_out) {
+                     const bnhip_event_extend* extend, bnhip_event* out, size_t cap, size_t* n_out, bool guarded = false,
+                     const bnhip_event_guards* guards = nullptr) {
     const char* what = "detection_events";
     if (!n_out || (cap && !out) || (n_rows && !rows)) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (int rc = event_filter_check(filter)) return rc;
     if (extended) if (int rc = event_extend_check(filter->hold_windows, extend)) return rc;
+    if (guarded) if (int rc = event_guards_check(guards)) return rc;
+    if (guarded) if (int rc = event_guards_spans_check(guards, 65534)) return rc;
     if (n_classes < 1 || n_classes > EVENT_MAX_CLASSES) return set_err(BNHIP_E_INVALID, "n_classes must be in [1, 38400]");
     if (n_rows >= EVENT_MAX_ROWS) return set_err(BNHIP_E_INVALID, "2^31 detection rows or more");
     int max_rec = 0;
@@ -97,13 +138,15 @@ int detection_events(int device, const bnhip_detection* rows, size_t n_rows, int
     const size_t ev_cap = std::min(cap, n_rows);
     DevCarve cv;
     const size_t o_rows = cv.add(n_rows * sizeof(DetRow)), o_count = cv.add(8), o_tab = cv.add(event_tables_bytes(n_classes, extended));
-    const size_t o_scr = cv.add(events_scratch_bytes(n_rows)), o_out = cv.add(ev_cap * sizeof(Event));
+    const size_t o_scr = cv.add(events_scratch_bytes(n_rows, guarded && guards->class_dog)), o_out = cv.add(ev_cap * sizeof(Event));
+    const size_t o_guards = guarded ? cv.add(event_guards_bytes(n_classes, guards)) : 0;
     DevBlocks b;
     cv.alloc(b);
     const unsigned long long n64 = n_rows;
     if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_rows), rows, n_rows * sizeof(DetRow), hipMemcpyHostToDevice);
     if (b.he == hipSuccess) b.he = hipMemcpy(cv.at<void>(o_count), &n64, 8, hipMemcpyHostToDevice);
-    const EventFilterDev fd = event_filter_upload(filter, n_classes, cv.at<char>(o_tab), nullptr, b, extended ? extend : nullptr);
+    EventFilterDev fd = event_filter_upload(filter, n_classes, cv.at<char>(o_tab), nullptr, b, extended ? extend : nullptr);
+    if (guarded) event_guards_upload(guards, n_classes, cv.at<char>(o_guards), nullptr, b, fd);
     if (b.he != hipSuccess) return hip_fail(what, b);
     launch_events(cv.at<DetRow>(o_rows), cv.at<unsigned long long>(o_count), n_rows, fd, events_passes((unsigned long long)(max_rec + 1) * n_classes - 1),
                   cv.at<void>(o_scr), cv.at<Event>(o_out), ev_cap, nullptr);
@@ -131,6 +174,14 @@ int bnhip_detection_events_extended(int device, const bnhip_detection* rows, siz
                                     const bnhip_event_extend* extend, bnhip_event* out, size_t cap, size_t* n_out) {
     BN_GUARD_BEGIN
     return detection_events(device, rows, n_rows, n_classes, filter, true, extend, out, cap, n_out);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_detection_events_guarded(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                                   const bnhip_event_extend* extend, const bnhip_event_guards* guards, bnhip_event* out, size_t cap,
+                                   size_t* n_out) {
+    BN_GUARD_BEGIN
+    return detection_events(device, rows, n_rows, n_classes, filter, extend != nullptr, extend, out, cap, n_out, true, guards);
     BN_GUARD_END((void)0)
 }
 

@@ -26,6 +26,18 @@ inline size_t event_tables_bytes(int n_classes, bool extended = false) { return 
 EventFilterDev event_filter_upload(const bnhip_event_filter* f, int n_classes, char* d_tables, hipStream_t s, DevBlocks& b,
                                    const bnhip_event_extend* x = nullptr);
 
+// Guards (include/bnhip.h, "Detection events: dog-bark and daylight filters").  Every refusal of the struct itself but its spans
+// (g NULL: refused): the bank's set_guards needs no more
+int event_guards_check(const bnhip_event_guards* g);
+// ... and of its spans; max_recording: the largest recording of the call
+int event_guards_spans_check(const bnhip_event_guards* g, int max_recording);
+// bytes of the guards' part on the device: class_dog, class_dog_filtered, class_daylight [n_classes] each, then the spans
+inline size_t event_guards_bytes(int n_classes, const bnhip_event_guards* g) {
+    return ((size_t)n_classes * 3 + 3) / 4 * 4 + (size_t)(g ? g->n_spans : 0) * 12;
+}
+// the guards' tables and spans go up to d_guards (event_guards_bytes, 4-byte aligned) on s and into fd.g, a failure into b
+void event_guards_upload(const bnhip_event_guards* g, int n_classes, char* d_guards, hipStream_t s, DevBlocks& b, EventFilterDev& fd);
+
 // A list the device has counted (detection rows, events): the count comes down and s is synchronised, then min(*total, cap)
 // records are copied to out - that copy is left in flight on s.  A failure goes into b.
 void fetch_counted(const void* d_total, const void* d_records, size_t record_bytes, size_t cap, void* out, unsigned long long* total, hipStream_t s,

@@ -21,7 +21,7 @@ struct Event {
     int32_t status;
 };
 constexpr int EVENTS_KEEP_DROPPED = 1;
-constexpr int EVENT_KEPT = 0, EVENT_FEW = 1, EVENT_VETOED = 2;
+constexpr int EVENT_KEPT = 0, EVENT_FEW = 1, EVENT_VETOED = 2, EVENT_DOG = 3, EVENT_DAYLIGHT = 4;
 
 // Extended capture's numbers (bnhip_event_extend without its table), in windows.  max_windows == 0: no extend, every deadline is
 // b + hold.
@@ -45,6 +45,25 @@ inline int ev_longest_wait(int hold, const EventExtend& x) {
     return x.long_wait > W ? x.long_wait : W;
 }
 
+// The dog-bark and daylight guards as the kernels read them (include/bnhip.h, "Detection events: dog-bark and daylight filters"):
+// three class tables on the device, each NULL for none.  The file tail reads the daylight spans as rows (recording, from, to),
+// ascending and disjoint; the bank brings its sources' spans with the call (events_bank.h) and leaves spans NULL.
+struct EventGuardsDev {
+    const uint8_t* dog = nullptr;
+    const uint8_t* dog_filtered = nullptr;
+    const uint8_t* daylight = nullptr;
+    float dog_thr = 0.0f;
+    int dog_remember = 0;
+    const int32_t* spans = nullptr;
+    int n_spans = 0;
+    // a result that marks its window as a dog hit: float32, strict, false for a NaN on either side
+    __host__ __device__ bool dog_hit(int cls, float x) const { return dog && dog[cls] != 0 && x > dog_thr; }
+    // an event due at d, the largest dog-hit window before d being v (-1: none): dropped as a recent dog bark
+    __host__ __device__ bool dog_drops(int cls, long long d, long long v) const {
+        return dog_filtered && dog_filtered[cls] != 0 && v >= 0 && v < d && d - v <= dog_remember;
+    }
+};
+
 // The filter as the kernels read it: thr [n_classes] and veto [n_classes] (or NULL) are device pointers; with x.max_windows > 0 the
 // classes with slide[c] != 0 (slide NULL: all of them) take the sliding deadline.
 struct EventFilterDev {
@@ -54,16 +73,18 @@ struct EventFilterDev {
     int hold, min_count, flags, n_classes;
     const uint8_t* slide = nullptr;
     EventExtend x{};
+    EventGuardsDev g{};
     __host__ __device__ bool slides(int cls) const { return x.max_windows > 0 && (!slide || slide[cls] != 0); }
 };
 
 // radix passes (8-bit digits) that keys up to max_key need: 1..4
 int events_passes(unsigned long long max_key);
-// bytes of scratch for up to N rows; the scratch starts 256-byte aligned
-size_t events_scratch_bytes(size_t N);
+// bytes of scratch for up to N rows; the scratch starts 256-byte aligned.  guarded: with room for the dog hits of a filter whose
+// g.dog is set
+size_t events_scratch_bytes(size_t N, bool guarded = false);
 // where launch_events leaves the number of events (all that the filter answers, whatever the cap): 8 bytes inside the scratch
 unsigned long long* events_total(void* scratch);
-// rows [min(*d_n, N)], nondecreasing in (recording, window): the events in (recording, class, first_window) order land in
+// rows [min(*d_n, N)], nondecreasing in (recording, window); with f.g.dog the scratch is a guarded one: the events in (recording, class, first_window) order land in
 // out[0 .. min(cap, total)).  N is the host's bound on the row count and sizes every grid; blocks behind *d_n leave at once.
 void launch_events(const DetRow* rows, const unsigned long long* d_n, size_t N, const EventFilterDev& f, int passes, void* scratch,
                    Event* out, unsigned long long cap, hipStream_t s);

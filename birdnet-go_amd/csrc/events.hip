@@ -1,5 +1,6 @@
-// Detection events on the device (events.h): mark the hits and the veto windows, stable-sort the hits by (recording, class), find
-// the events under the greedy hold rule, reduce each, apply the minimum count and the veto, compact into output order.
+// Detection events on the device (events.h): mark the hits, the veto windows and under guards the dog windows, stable-sort the hits by
+// (recording, class), find the events under the greedy hold rule, reduce each, apply the minimum count, the veto and the guards,
+// compact into output order.
 //
 // Every count that lives on the device stays there: the grids are sized from the host's bound N on the row count, and a block
 // behind the real count leaves at once.  No step accumulates floating point, and no rank comes from the return value of an atomic:
@@ -18,7 +19,7 @@ using u32 = unsigned int;
 using u64 = unsigned long long;
 
 constexpr int EV_TILE = 2048;                     // keys of one radix block: 8 rounds of 256
-constexpr int EV_COUNTS_BYTES = 256;              // counts[0] = hits, [1] = veto hits, [2] = events
+constexpr int EV_COUNTS_BYTES = 256;              // counts[0] = hits, [1] = veto hits, [2] = events, [3] = dog hits (guarded)
 
 size_t ev_up(size_t b) { return (b + 255) / 256 * 256; }
 size_t ev_nb(size_t N) { return (N + 255) / 256; }
@@ -27,8 +28,9 @@ size_t ev_nt(size_t N) { return (N + EV_TILE - 1) / EV_TILE; }
 // the parts of the scratch, in order
 struct EvScratch {
     u64* counts; u64* base; u32* key[2]; u32* idx[2]; u64* veto; u32* hist; u32* digits; uint8_t* start;
+    u64* dog = nullptr; u64* dbase = nullptr;      // (guarded only, behind everything else: the other parts lie where they lay)
     size_t bytes;
-    EvScratch(void* scratch, size_t N) {
+    EvScratch(void* scratch, size_t N, bool guarded) {
         char* p = static_cast<char*>(scratch);
         size_t o = 0;
         auto take = [&](size_t b) { char* q = p ? p + o : nullptr; o += ev_up(b); return q; };
@@ -42,6 +44,10 @@ struct EvScratch {
         hist = reinterpret_cast<u32*>(take(ev_nt(N) * 256 * 4));
         digits = reinterpret_cast<u32*>(take(256 * 4));
         start = reinterpret_cast<uint8_t*>(take(N));
+        if (guarded) {
+            dog = reinterpret_cast<u64*>(take(N * 8));
+            dbase = reinterpret_cast<u64*>(take(ev_nb(N) * 8));
+        }
         bytes = o;
     }
 };
@@ -58,14 +64,27 @@ __device__ __forceinline__ u64 ev_mark(const DetRow& q, const EventFilterDev& f)
     const bool vh = v && q.confidence > f.veto_thr;
     return (hit ? 1ull : 0ull) | (vh ? 1ull << 32 : 0ull);
 }
-// thread = row: the block's packed totals
+// a row's third flag, scanned on its own: a dog hit, whatever else the row is
+__device__ __forceinline__ u64 ev_mark_dog(const DetRow& q, const EventFilterDev& f) {
+    return (u32)q.cls < (u32)f.n_classes && f.g.dog_hit(q.cls, q.confidence) ? 1ull : 0ull;
+}
+// thread = row: the block's packed totals; DOG: also its dog hits
+template <bool DOG>
 __global__ __launch_bounds__(256) void k_ev_mark_count(const DetRow* __restrict__ rows, const u64* __restrict__ d_n, u32 N, EventFilterDev f,
-                                                       u64* __restrict__ base) {
+                                                       u64* __restrict__ base, u64* __restrict__ dbase) {
     __shared__ u64 sh[256];
     const u32 n = ev_rows(d_n, N), i = blockIdx.x * 256 + threadIdx.x;
-    const u64 c = i < n ? ev_mark(rows[i], f) : 0ull;
+    DetRow q{0, 0, 0, 0.0f};
+    if (i < n) q = rows[i];
+    const u64 c = i < n ? ev_mark(q, f) : 0ull;
     const u64 incl = block_scan(c, sh, threadIdx.x);
     if (threadIdx.x == 255) base[blockIdx.x] = incl;
+    if (DOG) {
+        __shared__ u64 shd[256];
+        const u64 dg = i < n ? ev_mark_dog(q, f) : 0ull;
+        const u64 dincl = block_scan(dg, shd, threadIdx.x);
+        if (threadIdx.x == 255) dbase[blockIdx.x] = dincl;
+    }
 }
 // one block: the block totals in place -> exclusive bases, 256 at a time with a running carry.  The grand total goes to *lo, or
 // with hi its two packed halves to *lo and *hi.
@@ -86,10 +105,11 @@ __global__ __launch_bounds__(256) void k_ev_bases(u64* __restrict__ base, u32 nb
         else *lo = carry;
     }
 }
-// thread = row: a hit's key and row number, a veto hit's (recording, window), each in row order
+// thread = row: a hit's key and row number, a veto hit's (recording, window), DOG: a dog hit's (recording, window), each in row order
+template <bool DOG>
 __global__ __launch_bounds__(256) void k_ev_mark_scatter(const DetRow* __restrict__ rows, const u64* __restrict__ d_n, u32 N, EventFilterDev f,
                                                          const u64* __restrict__ base, u32* __restrict__ key, u32* __restrict__ idx,
-                                                         u64* __restrict__ veto) {
+                                                         u64* __restrict__ veto, const u64* __restrict__ dbase, u64* __restrict__ dog) {
     __shared__ u64 sh[256];
     const u32 n = ev_rows(d_n, N), i = blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x * 256 >= n) return;
@@ -103,6 +123,12 @@ __global__ __launch_bounds__(256) void k_ev_mark_scatter(const DetRow* __restric
         idx[j] = i;
     }
     if (c >> 32) veto[excl >> 32] = ((u64)(u32)q.recording << 32) | (u32)q.window;
+    if (DOG) {
+        __shared__ u64 shd[256];
+        const u64 dg = i < n ? ev_mark_dog(q, f) : 0ull;
+        const u64 dexcl = dbase[blockIdx.x] + block_scan(dg, shd, threadIdx.x) - dg;
+        if (dg) dog[dexcl] = ((u64)(u32)q.recording << 32) | (u32)q.window;
+    }
 }
 
 // ------------------------------------------------------------------------------------------ the stable sort
@@ -294,8 +320,8 @@ __global__ __launch_bounds__(256) void k_ev_walk_slide(const u32* __restrict__ k
 
 // the event that begins at sorted hit i; -> whether it is answered
 __device__ __forceinline__ bool ev_reduce(u32 i, u32 n, const u32* __restrict__ key, const int* __restrict__ win, const float* __restrict__ conf,
-                                          const uint8_t* __restrict__ start, const u64* __restrict__ veto, u32 n_veto, const EventFilterDev& f,
-                                          Event& e) {
+                                          const uint8_t* __restrict__ start, const u64* __restrict__ veto, u32 n_veto,
+                                          const u64* __restrict__ dog, u32 n_dog, const EventFilterDev& f, Event& e) {
     const u32 k = key[i];
     float best = conf[i];
     int bw = win[i], last = bw, count = 0;
@@ -330,22 +356,49 @@ __device__ __forceinline__ bool ev_reduce(u32 i, u32 n, const u32* __restrict__ 
             if (veto[mid] < from) lo = mid + 1; else hi = mid;
         }
         if (lo < n_veto && veto[lo] < end) e.status = EVENT_VETOED;
+        if (e.status == EVENT_KEPT && n_dog && f.g.dog_filtered && f.g.dog_filtered[e.cls] != 0) {
+            // the recording's last dog window before the final deadline d (end = (recording, d)): the entry in front of the first at
+            // or behind end
+            lo = 0, hi = n_dog;
+            while (lo < hi) {
+                const u32 mid = lo + (hi - lo) / 2;
+                if (dog[mid] < end) lo = mid + 1; else hi = mid;
+            }
+            if (lo > 0 && (dog[lo - 1] >> 32) == (u64)(u32)e.recording &&
+                f.g.dog_drops(e.cls, (long long)(end & 0xffffffffull), (long long)(dog[lo - 1] & 0xffffffffull)))
+                e.status = EVENT_DOG;
+        }
+        if (e.status == EVENT_KEPT && f.g.n_spans > 0 && f.g.daylight && f.g.daylight[e.cls] != 0) {
+            // the last span that begins at or before (recording, b): rows (recording, from, to), ascending and disjoint
+            int slo = 0, shi = f.g.n_spans;
+            while (slo < shi) {
+                const int mid = slo + (shi - slo) / 2;
+                const int32_t* sp = f.g.spans + (size_t)mid * 3;
+                if (sp[0] < e.recording || (sp[0] == e.recording && sp[1] <= e.first_window)) slo = mid + 1; else shi = mid;
+            }
+            if (slo > 0) {
+                const int32_t* sp = f.g.spans + (size_t)(slo - 1) * 3;
+                if (sp[0] == e.recording && e.first_window < sp[2]) e.status = EVENT_DAYLIGHT;
+            }
+        }
     }
     return e.status == EVENT_KEPT || (f.flags & EVENTS_KEEP_DROPPED);
 }
 // thread = sorted hit: 1 where an answered event begins, scanned over the block; EMIT writes the events at their ranks
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_ev_events(const u32* __restrict__ key, const int* __restrict__ win, const float* __restrict__ conf,
-                                                   const uint8_t* __restrict__ start, const u64* __restrict__ veto, const u64* __restrict__ counts,
-                                                   u32 N, EventFilterDev f, u64* __restrict__ base, Event* __restrict__ out, u64 cap) {
+                                                   const uint8_t* __restrict__ start, const u64* __restrict__ veto, const u64* __restrict__ dog,
+                                                   const u64* __restrict__ counts, u32 N, EventFilterDev f, u64* __restrict__ base,
+                                                   Event* __restrict__ out, u64 cap) {
     __shared__ u32 sh[256];
     const u32 n = ev_rows(counts, N), n_veto = (u32)min(counts[1], (u64)N), i = blockIdx.x * 256 + threadIdx.x;
+    const u32 n_dog = dog ? (u32)min(counts[3], (u64)N) : 0u;
     if (blockIdx.x * 256 >= n) {
         if (!EMIT && threadIdx.x == 0) base[blockIdx.x] = 0;
         return;
     }
     Event e;
-    const u32 c = i < n && start[i] && ev_reduce(i, n, key, win, conf, start, veto, n_veto, f, e) ? 1u : 0u;
+    const u32 c = i < n && start[i] && ev_reduce(i, n, key, win, conf, start, veto, n_veto, dog, n_dog, f, e) ? 1u : 0u;
     const u32 incl = block_scan(c, sh, threadIdx.x);
     if (!EMIT) {
         if (threadIdx.x == 255) base[blockIdx.x] = incl;
@@ -362,19 +415,29 @@ int events_passes(unsigned long long max_key) {
     while (p < 4 && (max_key >> (8 * p)) != 0) p++;
     return p;
 }
-size_t events_scratch_bytes(size_t N) { return EvScratch(nullptr, N).bytes; }
+size_t events_scratch_bytes(size_t N, bool guarded) { return EvScratch(nullptr, N, guarded).bytes; }
 unsigned long long* events_total(void* scratch) { return static_cast<u64*>(scratch) + 2; }
 
 void launch_events(const DetRow* rows, const unsigned long long* d_n, size_t N, const EventFilterDev& f, int passes, void* scratch, Event* out,
                    unsigned long long cap, hipStream_t s) {
-    const EvScratch sc(scratch, N);
+    const bool dogs = f.g.dog != nullptr;
+    const EvScratch sc(scratch, N, dogs);
     hipMemsetAsync(sc.counts, 0, EV_COUNTS_BYTES, s);
     if (N == 0) return;
     const u32 n32 = (u32)N, nb = (u32)ev_nb(N), nt = (u32)ev_nt(N);
     const dim3 rows_grid(nb), tiles_grid(nt), block(256);
-    hipLaunchKernelGGL(k_ev_mark_count, rows_grid, block, 0, s, rows, d_n, n32, f, sc.base);
-    hipLaunchKernelGGL(k_ev_bases, dim3(1), block, 0, s, sc.base, nb, sc.counts, sc.counts + 1);
-    hipLaunchKernelGGL(k_ev_mark_scatter, rows_grid, block, 0, s, rows, d_n, n32, f, sc.base, sc.key[0], sc.idx[0], sc.veto);
+    if (dogs) {
+        hipLaunchKernelGGL(k_ev_mark_count<true>, rows_grid, block, 0, s, rows, d_n, n32, f, sc.base, sc.dbase);
+        hipLaunchKernelGGL(k_ev_bases, dim3(1), block, 0, s, sc.base, nb, sc.counts, sc.counts + 1);
+        hipLaunchKernelGGL(k_ev_bases, dim3(1), block, 0, s, sc.dbase, nb, sc.counts + 3, (u64*)nullptr);
+        hipLaunchKernelGGL(k_ev_mark_scatter<true>, rows_grid, block, 0, s, rows, d_n, n32, f, sc.base, sc.key[0], sc.idx[0], sc.veto, sc.dbase,
+                           sc.dog);
+    } else {
+        hipLaunchKernelGGL(k_ev_mark_count<false>, rows_grid, block, 0, s, rows, d_n, n32, f, sc.base, (u64*)nullptr);
+        hipLaunchKernelGGL(k_ev_bases, dim3(1), block, 0, s, sc.base, nb, sc.counts, sc.counts + 1);
+        hipLaunchKernelGGL(k_ev_mark_scatter<false>, rows_grid, block, 0, s, rows, d_n, n32, f, sc.base, sc.key[0], sc.idx[0], sc.veto,
+                           (const u64*)nullptr, (u64*)nullptr);
+    }
     int a = 0;
     for (int p = 0; p < passes; p++, a ^= 1) {
         hipLaunchKernelGGL(k_ev_radix<false>, tiles_grid, block, 0, s, sc.key[a], sc.idx[a], sc.key[a ^ 1], sc.idx[a ^ 1], sc.counts, n32, 8 * p,
@@ -389,9 +452,9 @@ void launch_events(const DetRow* rows, const unsigned long long* d_n, size_t N, 
     hipLaunchKernelGGL(k_ev_gather, rows_grid, block, 0, s, rows, sc.idx[a], sc.counts, n32, win, conf, sc.start);
     if (f.x.max_windows > 0) hipLaunchKernelGGL(k_ev_walk_slide, rows_grid, block, 0, s, sc.key[a], win, sc.counts, n32, f, sc.start);
     else hipLaunchKernelGGL(k_ev_walk, rows_grid, block, 0, s, sc.key[a], win, sc.counts, n32, f.hold, sc.start);
-    hipLaunchKernelGGL(k_ev_events<false>, rows_grid, block, 0, s, sc.key[a], win, conf, sc.start, sc.veto, sc.counts, n32, f, sc.base, out, cap);
+    hipLaunchKernelGGL(k_ev_events<false>, rows_grid, block, 0, s, sc.key[a], win, conf, sc.start, sc.veto, sc.dog, sc.counts, n32, f, sc.base, out, cap);
     hipLaunchKernelGGL(k_ev_bases, dim3(1), block, 0, s, sc.base, nb, sc.counts + 2, (u64*)nullptr);
-    hipLaunchKernelGGL(k_ev_events<true>, rows_grid, block, 0, s, sc.key[a], win, conf, sc.start, sc.veto, sc.counts, n32, f, sc.base, out, cap);
+    hipLaunchKernelGGL(k_ev_events<true>, rows_grid, block, 0, s, sc.key[a], win, conf, sc.start, sc.veto, sc.dog, sc.counts, n32, f, sc.base, out, cap);
 }
 
 }  // namespace bnhip

@@ -2,7 +2,8 @@
 // source's pending detections stay on the device across calls, and a call feeds them the top-k rows of the windows it brings.
 //
 // A source's state is one slab: its slots as a struct of arrays (class or -1 for a free slot, first / last / best window, count,
-// confidence; in a bank created extended also the deadline, events.h) and behind them the source's latest veto-hit window.  A
+// confidence; in a bank created extended also the deadline, events.h) and behind them the source's latest veto-hit window and, in
+// its padding, the latest dog-hit window (-1: none; include/bnhip.h, "Detection events: dog-bark and daylight filters").  A
 // launch reads the slab of the source's parity and writes the other; the host flips the parity only once the whole call has
 // succeeded (stream_bank.h).  Three launches make a call: the update (one wave per source of the call), a one-block scan of the
 // sources' answered counts, and the emit that ranks each source's staged events by (class, first window).  Compares and integer
@@ -18,13 +19,14 @@
 namespace bnhip {
 
 constexpr int EVENT_PENDING = -1;
+constexpr int EVB_DAYLIGHT_SPANS = 8;            // daylight spans of a source (BNHIP_EVENT_DAYLIGHT_SPANS)
 constexpr int EVB_MAX_SLOTS = 4096;              // k * hold_windows (extended: k * W) at the most: a source's slots fit one wave's LDS
 enum EvbMode { EVB_PROCESS = 0, EVB_FLUSH = 1, EVB_PENDING = 2 };
 
 // arrays of a slab and of the update's LDS: six, and in a bank created extended the slots' deadlines as the seventh (96 / 112 KiB at
 // EVB_MAX_SLOTS, inside the CU's 160 KiB)
 __host__ __device__ inline int evb_arrays(bool extended) { return extended ? 7 : 6; }
-// ints of one slab: the arrays of `slots`, then the veto window (padded to 16 bytes)
+// ints of one slab: the arrays of `slots`, then the veto window and the dog window (padded to 16 bytes)
 __host__ __device__ inline size_t evb_slab_ints(int slots, bool extended = false) { return (size_t)slots * evb_arrays(extended) + 4; }
 
 // One source of a call, sources ascending.  Its rows are rowmap[row_off .. row_off + n_windows) (row numbers of the call, in
@@ -36,7 +38,8 @@ struct EvbGroup {
     uint32_t row_off;
     uint32_t stage_off, stage_cap;
     int32_t rd_parity;                           // slab to read; -1: the source has no state yet (every slot free, no veto window)
-    int32_t wr_parity;                           // slab to write (process mode only)
+    int32_t wr_parity;                           // slab to write; in the flush mode -1: none, else the source keeps a dog window and its
+                                                 // freed slab goes there
 };
 
 struct EvbCall {
@@ -47,6 +50,8 @@ struct EvbCall {
     const int32_t* idx;
     int k, slots, mode;
     bool extended;                               // the bank was created extended: a slot carries its deadline
+    const int32_t* day;                          // [n_groups][EVB_DAYLIGHT_SPANS][2] the sources' daylight spans [from, to), an unused one
+                                                 // 0, 0; NULL: none (always without f.g.daylight)
     int32_t* state;                              // [max_sources][2][evb_slab_ints(slots, extended)]
     Event* stage;                                // the call's staging area
     uint32_t* counts;                            // [n_groups] answered events of each source, then [n_groups] their exclusive bases

@@ -2,7 +2,8 @@
 //
 // k_evb_update  one wave per source of the call.  The source's slots come into LDS (lanes take slots 64 at a step), the wave walks the
 //               source's windows of this call in order - per result a ballot on class over the live slots, the matching lane joins or
-//               the lowest free slot opens; the veto window rises; the slots that are due are staged, their status final, and freed -
+//               the lowest free slot opens; the veto window and under guards the dog window rise; the slots that are due are staged,
+//               their status final (minimum count, veto, and under guards recent dog bark and daylight), and freed -
 //               and the slots go out to the slab of the other parity.  Flush ("every live slot is due") and pending ("stage without
 //               freeing") are modes of the same walk.
 // k_evb_scan    one block: the exclusive scan of the sources' answered counts, sources ascending, and their total.
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
     const EvbGroup g = c.groups[blockIdx.x];
     const size_t slab = (size_t)S * A + 4;
     const int* rd = g.rd_parity >= 0 ? c.state + ((size_t)g.source * 2 + (size_t)g.rd_parity) * slab : nullptr;
-    int* wr = c.state + ((size_t)g.source * 2 + (size_t)g.wr_parity) * slab;
+    int* wr = g.wr_parity >= 0 ? c.state + ((size_t)g.source * 2 + (size_t)g.wr_parity) * slab : nullptr;
     for (int s = lane; s < S; s += 64) {
         cls[s] = rd ? rd[s] : -1;
         first[s] = rd ? rd[S + s] : 0;
@@ -57,6 +58,8 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
         if (EXT) deadline[s] = rd ? rd[6 * S + s] : 0;
     }
     int veto_win = rd ? rd[A * S] : -1;            // the source's largest veto-hit window so far
+    int dog_win = rd ? rd[A * S + 1] : -1;         // ... and its largest dog-hit window
+    const int32_t* day = c.day ? c.day + (size_t)blockIdx.x * (EVB_DAYLIGHT_SPANS * 2) : nullptr;
     __syncthreads();
     const u64 lt = (1ull << lane) - 1ull;
     u32 staged = 0;
@@ -71,8 +74,15 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
             const bool live = s < S && cls[s] >= 0;
             const bool due = live && (c.mode != EVB_PROCESS || (EXT ? (long long)deadline[s] : (long long)first[s] + f.hold) <= w + 1);
             int status = EVENT_PENDING;
-            if (due && c.mode != EVB_PENDING)
+            if (due && c.mode != EVB_PENDING) {
                 status = count[s] < f.min_count ? EVENT_FEW : veto_win >= first[s] ? EVENT_VETOED : EVENT_KEPT;
+                // the guards measure from the event's final deadline, which an early flush has not reached yet
+                if (status == EVENT_KEPT && f.g.dog_drops(cls[s], EXT ? (long long)deadline[s] : (long long)first[s] + f.hold, dog_win))
+                    status = EVENT_DOG;
+                if (status == EVENT_KEPT && day && f.g.daylight[cls[s]] != 0)
+                    for (int q = 0; q < EVB_DAYLIGHT_SPANS; q++)
+                        if (day[2 * q] <= first[s] && first[s] < day[2 * q + 1]) status = EVENT_DAYLIGHT;
+            }
             const bool answered = due && (c.mode == EVB_PENDING || status == EVENT_KEPT || (f.flags & EVENTS_KEEP_DROPPED));
             const u64 m = __ballot(answered);
             const u32 pos = staged + (u32)__popcll(m & lt);
@@ -102,6 +112,7 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
                 const float x = c.conf[row + i];
                 const int ci = c.idx[row + i];
                 if ((u32)ci >= (u32)f.n_classes) continue;             // no result
+                if (f.g.dog_hit(ci, x)) dog_win = w;                   // (whatever else the result is)
                 if (f.veto[ci] != 0) {
                     if (x > f.veto_thr) veto_win = w;
                     continue;
@@ -145,7 +156,12 @@ __global__ __launch_bounds__(64) void k_evb_update(EvbCall c, EventFilterDev f) 
             wr[5 * S + s] = __float_as_int(conf[s]);
             if (EXT) wr[6 * S + s] = deadline[s];
         }
-        if (lane == 0) wr[A * S] = veto_win;
+        if (lane == 0) { wr[A * S] = veto_win; wr[A * S + 1] = dog_win; }
+    }
+    if (c.mode == EVB_FLUSH && wr) {
+        // a source that keeps a dog window stays live across its flush: every slot free, the two windows as they stand
+        for (int s = lane; s < S; s += 64) wr[s] = -1;
+        if (lane == 0) { wr[A * S] = veto_win; wr[A * S + 1] = dog_win; }
     }
     const bool any_overflow = __ballot(overflow) != 0;
     if (lane == 0) c.counts[blockIdx.x] = any_overflow ? 0u : staged;

@@ -75,7 +75,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_event_bank_threshold_changes", "bnhip_event_bank_thresholds", "bnhip_event_bank_set_thresholds",
            "bnhip_event_bank_reset_thresholds", "bnhip_event_threshold", "bnhip_audio_level", "bnhip_level_bank_create",
            "bnhip_level_bank_add_stream", "bnhip_level_bank_remove_stream", "bnhip_level_bank_process_pcm", "bnhip_level_bank_latest",
-           "bnhip_level_bank_stats", "bnhip_level_bank_reset", "bnhip_level_bank_destroy", "bnhip_capture_bank_write_levels"]
+           "bnhip_level_bank_stats", "bnhip_level_bank_reset", "bnhip_level_bank_destroy", "bnhip_capture_bank_write_levels",
+           "bnhip_detection_events_guarded", "bnhip_analyze_channels_pcm_events_guarded", "bnhip_analyze_channels_pcm_clips_guarded",
+           "bnhip_event_bank_set_guards", "bnhip_event_bank_set_daylight"]
 
 
 class HipError(RuntimeError):
@@ -240,6 +242,9 @@ def _analyze_events_protos(lib):
     xtail = [C.c_void_p] + tail                                                       # filter, extend, out, cap, n_out
     lib.bnhip_analyze_channels_pcm_events_extended.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + xtail + [C.c_void_p]
     lib.bnhip_detection_events_extended.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int] + xtail
+    gtail = [C.c_void_p] + xtail                                                      # filter, extend, guards, out, cap, n_out
+    lib.bnhip_analyze_channels_pcm_events_guarded.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + gtail + [C.c_void_p]
+    lib.bnhip_detection_events_guarded.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int] + gtail
     lib.bnhip_event_deadline.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_int64]
     lib.bnhip_event_deadline.restype = C.c_int64
     return lib
@@ -249,7 +254,8 @@ def _analyze_events_protos(lib):
 EVENT = np.dtype([("recording", "<i4"), ("class_index", "<i4"), ("first_window", "<i4"), ("last_window", "<i4"), ("best_window", "<i4"),
                   ("count", "<i4"), ("confidence", "<f4"), ("status", "<i4")])
 EVENTS_KEEP_DROPPED = 1
-EVENT_KEPT, EVENT_FEW, EVENT_VETOED = 0, 1, 2
+EVENT_KEPT, EVENT_FEW, EVENT_VETOED, EVENT_DOG, EVENT_DAYLIGHT = 0, 1, 2, 3, 4
+EVENT_DAYLIGHT_SPANS = 8
 
 
 class _EventFilterStruct(C.Structure):
@@ -303,6 +309,38 @@ class EventExtend:
                                   self.medium_from, self.medium_wait, self.long_from, self.long_wait)
 
 
+class _EventGuardsStruct(C.Structure):
+    _fields_ = [("class_dog", C.c_void_p), ("class_dog_filtered", C.c_void_p), ("class_daylight", C.c_void_p), ("daylight_spans", C.c_void_p),
+                ("dog_threshold", C.c_float), ("dog_remember_windows", C.c_int32), ("n_spans", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EventGuards:
+    """The dog-bark and daylight filters beside an EventTables (bnhip_event_guards; include/bnhip.h, "Detection events: dog-bark
+    and daylight filters"), in windows: class_dog uint8 [n_classes] (non-zero: a result of the class above dog_threshold marks its
+    window as a dog hit) or None, class_dog_filtered uint8 [n_classes] (non-zero: an event of the class is dropped with status
+    EVENT_DOG when the last dog hit lies at most dog_remember_windows before its deadline) or None, class_daylight uint8 [n_classes]
+    (non-zero: an event of the class that begins inside a daylight span is dropped with status EVENT_DAYLIGHT) or None, and for the
+    file tail daylight_spans int32 [n_spans, 3] = (recording, from, to), ascending and disjoint, or None; a bank takes its sources'
+    spans through EventBank.set_daylight and does not read these.  wav.EventGuards builds one from labels, minutes and seconds."""
+
+    def __init__(self, class_dog=None, dog_threshold=0.0, class_dog_filtered=None, dog_remember_windows=0, class_daylight=None,
+                 daylight_spans=None):
+        tab = lambda t: None if t is None else np.ascontiguousarray(t, np.uint8).reshape(-1)
+        self.class_dog, self.class_dog_filtered, self.class_daylight = tab(class_dog), tab(class_dog_filtered), tab(class_daylight)
+        self.dog_threshold, self.dog_remember_windows = float(dog_threshold), int(dog_remember_windows)
+        self.daylight_spans = None if daylight_spans is None else np.ascontiguousarray(daylight_spans, np.int32).reshape(-1, 3)
+
+    def _struct(self, n_classes):
+        """-> the C struct; the tables must hold n_classes entries each (the arrays stay alive with self)."""
+        for t in (self.class_dog, self.class_dog_filtered, self.class_daylight):
+            if t is not None and t.size != n_classes:
+                raise HipError(E_INVALID, f"the event guards' tables must hold n_classes = {n_classes} entries")
+        p = lambda t: None if t is None or t.size == 0 else t.ctypes.data
+        n_spans = 0 if self.daylight_spans is None else self.daylight_spans.shape[0]
+        return _EventGuardsStruct(p(self.class_dog), p(self.class_dog_filtered), p(self.class_daylight), p(self.daylight_spans),
+                                  self.dog_threshold, self.dog_remember_windows, n_spans, 0)
+
+
 class _EventDynamicStruct(C.Structure):
     _fields_ = [("class_dynamic", C.c_void_p), ("trigger", C.c_float), ("min_threshold", C.c_float), ("valid", C.c_int64),
                 ("cooldown", C.c_int64)]
@@ -353,9 +391,10 @@ def event_min_count(level, overlap_seconds):
     return int(_analyze_events_protos(load_library()).bnhip_event_min_count(int(level), float(overlap_seconds)))
 
 
-def detection_events(rows, n_classes, filter, device=0, cap=None, extend=None):
+def detection_events(rows, n_classes, filter, device=0, cap=None, extend=None, guards=None):
     """bnhip_detection_events: the event tail alone over DETECTION rows the host holds (nondecreasing in (recording, window));
-    with extend (an EventExtend) bnhip_detection_events_extended.
+    with extend (an EventExtend) bnhip_detection_events_extended; with guards (an EventGuards) bnhip_detection_events_guarded,
+    under the extend or none.
     -> the events (EVENT), ascending by (recording, class_index, first_window); with cap -> (events[:cap], total)."""
     lib = _analyze_events_protos(load_library())
     rows = np.ascontiguousarray(rows, DETECTION).reshape(-1)
@@ -365,7 +404,11 @@ def detection_events(rows, n_classes, filter, device=0, cap=None, extend=None):
     fs = filter._struct(int(n_classes))
     head = (int(device), rows.ctypes.data if rows.size else None, rows.size, int(n_classes), C.addressof(fs))
     answer = (out.ctypes.data if room else None, room, C.byref(n))
-    if extend is None:
+    if guards is not None:
+        xs = None if extend is None else extend._struct(int(n_classes))
+        gs = guards._struct(int(n_classes))
+        _check(lib, lib.bnhip_detection_events_guarded(*head, None if xs is None else C.addressof(xs), C.addressof(gs), *answer))
+    elif extend is None:
         _check(lib, lib.bnhip_detection_events(*head, *answer))
     else:
         xs = extend._struct(int(n_classes))
@@ -399,6 +442,8 @@ def _event_bank_protos(lib):
     lib.bnhip_event_bank_thresholds.argtypes = [vp] * 6
     lib.bnhip_event_bank_set_thresholds.argtypes = [vp] * 5
     lib.bnhip_event_bank_reset_thresholds.argtypes = [vp, ci]
+    lib.bnhip_event_bank_set_guards.argtypes = [vp, vp]
+    lib.bnhip_event_bank_set_daylight.argtypes = [vp, ci, vp, ci]
     lib.bnhip_event_threshold.argtypes = [C.c_float, ci, C.c_float]
     lib.bnhip_event_threshold.restype = C.c_float
     return lib
@@ -421,11 +466,13 @@ class EventBank:
     (bnhip_event_bank_create_dynamic) - it learns per-class thresholds on the device, at the bank time `set_now(now)` gives;
     `set_dynamic(dynamic | None)` changes the settings or freezes the learning, `thresholds()` / `restore_thresholds(...)` /
     `reset_thresholds(class_index=-1)` are the state's snapshot, restore and reset, and `threshold_changes()` takes the change
-    records (THRESHOLD_CHANGE) of the calls since it was last asked."""
+    records (THRESHOLD_CHANGE) of the calls since it was last asked.  guards (an EventGuards): `set_guards(guards)` right after
+    the create - any bank takes the dog-bark and daylight filters; `set_guards(guards | None)` changes them or turns them off from
+    the next call on, and `set_daylight(source, spans)` gives a source its daylight spans [(from, to), ...] in its own clock."""
 
     ROOM = 256
 
-    def __init__(self, n_classes, k, filter, max_sources=256, device=0, extend=None, dynamic=None):
+    def __init__(self, n_classes, k, filter, max_sources=256, device=0, extend=None, dynamic=None, guards=None):
         lib = self._lib = _event_bank_protos(load_library())
         self._h = None
         self.n_classes, self.k, self.max_sources, self.device = int(n_classes), int(k), int(max_sources), int(device)
@@ -449,6 +496,19 @@ class EventBank:
         v = [C.c_int() for _ in range(5)]
         _check(lib, lib.bnhip_event_bank_info(h, *[C.byref(x) for x in v]))
         self.hold_windows, self.slots_per_source = v[3].value, v[4].value
+        if guards is not None:
+            self.set_guards(guards)
+
+    def set_guards(self, guards):
+        """bnhip_event_bank_set_guards: an EventGuards from the next call on (its daylight_spans are not read); None turns them off."""
+        gs = None if guards is None else guards._struct(self.n_classes)
+        _check(self._lib, self._lib.bnhip_event_bank_set_guards(self._alive(), None if gs is None else C.addressof(gs)))
+
+    def set_daylight(self, source, spans=()):
+        """bnhip_event_bank_set_daylight: the daylight spans [(from, to), ...] of a source, in windows of its clock, ascending and
+        disjoint, at most EVENT_DAYLIGHT_SPANS; source -1 with no spans clears every source."""
+        sp = np.ascontiguousarray(spans, np.int32).reshape(-1, 2)
+        _check(self._lib, self._lib.bnhip_event_bank_set_daylight(self._alive(), int(source), sp.ctypes.data if sp.size else None, sp.shape[0]))
 
     def _alive(self):
         if self._h is None:
@@ -580,6 +640,7 @@ def _analyze_clips_protos(lib):
     lib.bnhip_recording_clips_pcm16.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.bnhip_analyze_channels_pcm_clips.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bnhip_analyze_channels_pcm_clips_extended.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + [C.c_void_p] * 5
+    lib.bnhip_analyze_channels_pcm_clips_guarded.argtypes = lib.bnhip_analyze_mixed_pcm.argtypes[:10] + [C.c_void_p] * 6
     return lib
 
 
@@ -924,15 +985,18 @@ def _rows_answer(threshold, cap):
     return answer
 
 
-def _events_answer(filter, cap, n_classes, extend=None):
-    """extend (an EventExtend): the _events_extended entry, which only the channels form has."""
+def _events_answer(filter, cap, n_classes, extend=None, guards=None):
+    """extend (an EventExtend): the _events_extended entry, which only the channels form has; guards (an EventGuards): its
+    _events_guarded entry, under the extend or none."""
     def answer(lib, kk, first, room):
         _analyze_events_protos(lib)
         first()                                         # (a bad table is answered as the windows entry answers it, before the filter)
         out, n, fs = np.zeros(room(cap), EVENT), C.c_size_t(0), filter._struct(n_classes)
         xs = None if extend is None else extend._struct(n_classes)
-        return "_events" if xs is None else "_events_extended", \
-            (C.byref(fs),) + (() if xs is None else (C.byref(xs),)) + (out.ctypes.data if out.size else None, out.size, C.byref(n)), \
+        gs = None if guards is None else guards._struct(n_classes)
+        middle = (() if xs is None else (C.byref(xs),)) if gs is None else (None if xs is None else C.byref(xs), C.byref(gs))
+        return "_events_guarded" if gs is not None else "_events" if xs is None else "_events_extended", \
+            (C.byref(fs),) + middle + (out.ctypes.data if out.size else None, out.size, C.byref(n)), \
             lambda: (out[:n.value],) if cap is None else (out[:min(out.size, n.value)], n.value)
     return answer
 
@@ -1205,15 +1269,17 @@ class HipClassifier:
         return self._analyze(_mixed_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes), hop, min_tail, k, activation, sensitivity)
 
     def analyze_channels_pcm_events(self, raw, recs, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None,
-                                    extend=None):
+                                    extend=None, guards=None):
         """bnhip_analyze_channels_pcm_events: analyze_channels_pcm answered as detection events; with extend (an EventExtend)
-        bnhip_analyze_channels_pcm_events_extended.  -> (events, chosen); with cap -> (events[:cap], total, chosen)."""
-        return self._analyze(_channels_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes, extend), hop, min_tail, k,
+        bnhip_analyze_channels_pcm_events_extended; with guards (an EventGuards) bnhip_analyze_channels_pcm_events_guarded, under
+        the extend or none.  -> (events, chosen); with cap -> (events[:cap], total, chosen)."""
+        return self._analyze(_channels_form(raw, recs, model_rate), _events_answer(filter, cap, self._n_classes, extend, guards), hop, min_tail, k,
                              activation, sensitivity)
 
     def analyze_channels_pcm_clips(self, raw, recs, model_rate, hop, filter, settings, min_tail=0, k=10, activation=0, sensitivity=1.0,
-                                   event_cap=None, max_clips=None, flac_cap=None, png_cap=None, extend=None):
-        """bnhip_analyze_channels_pcm_clips (with extend, an EventExtend: bnhip_analyze_channels_pcm_clips_extended):
+                                   event_cap=None, max_clips=None, flac_cap=None, png_cap=None, extend=None, guards=None):
+        """bnhip_analyze_channels_pcm_clips (with extend, an EventExtend: bnhip_analyze_channels_pcm_clips_extended; with guards, an
+        EventGuards: bnhip_analyze_channels_pcm_clips_guarded, under the extend or none):
         analyze_channels_pcm_events, and in the same call the clip of every event written - cut
         out of the recordings on the device, normalised, FLAC-encoded and (with settings.width) rendered to a PNG - under `settings`
         (a ClipSettings).  Room: event_cap events (default: every row), and for the streams flac_cap / png_cap bytes (default: the
@@ -1242,7 +1308,12 @@ class HipClassifier:
         o = _ClipsOutStruct(events.ctypes.data, room, 0, spans.ctypes.data, C.addressof(loud), flac.ctypes.data, int(flac_cap), flac_off.ctypes.data,
                             png.ctypes.data, int(png_cap), png_off.ctypes.data, 0)
         head = (self._h, form.x.ctypes.data, *form.args, int(hop), int(min_tail), activation, sensitivity, k, C.addressof(fs))
-        if extend is None:
+        if guards is not None:
+            es = None if extend is None else extend._struct(self._n_classes)
+            gs = guards._struct(self._n_classes)
+            _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips_guarded(*head, None if es is None else C.addressof(es), C.addressof(gs),
+                                                                                 chosen.ctypes.data, C.addressof(xs), C.addressof(o)))
+        elif extend is None:
             _check(self._lib, self._lib.bnhip_analyze_channels_pcm_clips(*head, chosen.ctypes.data, C.addressof(xs), C.addressof(o)))
         else:
             es = extend._struct(self._n_classes)

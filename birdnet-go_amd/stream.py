@@ -22,6 +22,7 @@ Byte work here is exact by construction (numpy slices); tests/test_stream.py rep
 (analysis_test.go:23-243) and compares against the line-by-line restatement in oracle/gostream.py.
 """
 import ctypes as C
+import math
 import threading
 import time
 from dataclasses import dataclass
@@ -683,20 +684,28 @@ class WindowBatcher:
     thresholds on the device (include/bnhip.h, "Detection events: dynamic thresholds"; one bank per model is the reference's
     modelID:species scoping).  Bank time is the batcher's `clock` in milliseconds since its creation, set before every tick; the
     EventDynamic's valid and cooldown are in that unit.  The ticks' threshold changes go to take_threshold_changes() and
-    on_threshold_changes(model_id, changes)."""
+    on_threshold_changes(model_id, changes).
+
+    `guards=` (a host.EventGuards; native rings, with events) sets the dog-bark and daylight filters on every model's event bank
+    (include/bnhip.h, "Detection events: dog-bark and daylight filters"): an event that the reference's flush would discard for a
+    recent dog bark or for beginning in daylight carries status host.EVENT_DOG or host.EVENT_DAYLIGHT and, without
+    EVENTS_KEEP_DROPPED, is not answered - nor learnt from, nor cut.  `set_guards(guards | None)` changes them from the next tick
+    on, `set_daylight(source, intervals)` gives a source its daylight intervals."""
 
     BANK_STREAMS = 1024                      # native: streams per rate pair's resampler bank
     EVENT_SOURCES = 1024                     # native: sources of a model's event bank (assembler slots are reused)
 
     def __init__(self, orch: Orchestrator, queue: _results.ResultsQueue = None, overruns: OverrunTrackers = None,
                  max_batch=256, pre_capture_s=0.0, bit_depth=16, clock=time.time, on_error=None, native=True, events=None,
-                 on_events=None, capture=None, on_clips=None, extend=None, dynamic=None, on_threshold_changes=None):
+                 on_events=None, capture=None, on_clips=None, extend=None, dynamic=None, on_threshold_changes=None, guards=None):
         if capture is not None and (events is None or not native):
             raise StreamError("capture needs events and the native rings")
         if extend is not None and (events is None or not native):
             raise StreamError("extend needs events and the native rings")
         if dynamic is not None and (events is None or not native):
             raise StreamError("dynamic needs events and the native rings")
+        if guards is not None and (events is None or not native):
+            raise StreamError("guards need events and the native rings")
         self.orch = orch
         self.queue = queue if queue is not None else _results.ResultsQueue()
         self.overruns = overruns if overruns is not None else OverrunTrackers()
@@ -725,6 +734,8 @@ class WindowBatcher:
         self.events = events                 # native: a host.EventTables -> detection events beside the Results (None: none)
         self.extend = extend                 # native: a host.EventExtend -> the models' event banks are created extended (None: not)
         self.dynamic = dynamic               # native: a host.EventDynamic -> the models' event banks learn their thresholds (None: not)
+        self.guards = guards                 # native: a host.EventGuards -> set on the models' event banks (None: none)
+        self.daylight = {}                   # (model_id, assembler source) -> [(from, to)] in windows, for the bank of that model
         self.on_threshold_changes = on_threshold_changes
         self.threshold_reports = []          # the ticks' threshold changes until take_threshold_changes()
         self.created, self.bank_now = clock() if dynamic is not None else None, 0   # bank time: milliseconds of `clock` since here, never decreasing
@@ -808,6 +819,7 @@ class WindowBatcher:
         bank = self.event_banks.get(model_id)
         if bank is not None and index < bank.max_sources:
             bank.reset(index)
+        self.daylight.pop((model_id, index), None)
         self._reset_capture(model_id, index, forget=True)
 
     def _reset_capture(self, model_id, index, forget=False):
@@ -927,10 +939,48 @@ class WindowBatcher:
         if bank is None:
             n_classes = len(inst.labels)
             bank = _host.EventBank(n_classes, min(getattr(inst, "TOP_K", 10), n_classes), self.events, self.EVENT_SOURCES, extend=self.extend,
-                                   dynamic=self.dynamic)
+                                   dynamic=self.dynamic, guards=self.guards)
             with self.mu:
                 self.event_banks[model_id] = bank
+                for (mid, index), spans in self.daylight.items():
+                    if mid == model_id and spans:
+                        bank.set_daylight(index, spans)
         return bank
+
+    def set_guards(self, guards):
+        """New guards (a host.EventGuards) on every model's event bank from the next tick on; None turns them off."""
+        if self.events is None or not self.native:
+            raise StreamError("guards need events and the native rings")
+        with self.mu:
+            self.guards = guards
+            for bank in self.event_banks.values():
+                bank.set_guards(guards)
+
+    def set_daylight(self, source, intervals, model_id=None):
+        """The daylight intervals [(from_seconds, to_seconds), ...] of `source` (of its buffer for model_id, or for every model), in
+        seconds of the source's audio clock - the audio written since it was allocated: at most host.EVENT_DAYLIGHT_SPANS, ascending
+        and disjoint; [] for none.  Window w of the source begins at w * hop seconds (hop: the model's read size) and is in daylight
+        when that instant lies in [from, to): both edges are rounded up to the next window start, from_window = ceil(from / hop) and
+        to_window = ceil(to / hop).  The intervals are read when an event is flushed, so they have to cover the first windows of the
+        events that are still pending - give the day's dawn and dusk ahead of time and replace them after the last event of the
+        day has been answered.  Re-allocating or removing the source clears them."""
+        if self.events is None or not self.native:
+            raise StreamError("guards need events and the native rings")
+        with self.mu:
+            keys = [k for k, ab in self.buffers.items() if k[0] == source and (model_id is None or k[1] == model_id) and isinstance(ab, _NativeSource)]
+            if not keys:
+                raise StreamError(f"no native buffer of source {source!r}")
+            for k in keys:
+                spec = self.orch.model_spec_for(k[1])
+                _, _, read = spec.buffer_dimensions()
+                hop = read / (self.bit_depth // 8) / spec.effective_sample_rate()
+                spans = [(max(0, int(math.ceil(lo / hop))), max(0, int(math.ceil(hi / hop)))) for lo, hi in intervals]
+                spans = [sp for sp in spans if sp[1] > sp[0]]                     # (an interval that holds no window start)
+                index = self.buffers[k].index
+                self.daylight[(k[1], index)] = spans
+                bank = self.event_banks.get(k[1])
+                if bank is not None:
+                    bank.set_daylight(index, spans)
 
     def take_events(self):
         """-> the detection events since the last call, oldest first: {"timestamp" (the batcher's clock at the tick), "source",

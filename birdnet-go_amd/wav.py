@@ -250,6 +250,75 @@ class ExtendedCapture:
                                 w(self.long_after_seconds), w(self.long_wait_seconds))
 
 
+# the reference's dog classes (vocalization_labels.go): BirdNET's "Dog_<localised name>" by its prefix, Perch v2's by their names
+DOG_LABEL_PREFIX = "dog_"
+DOG_LABELS = ("dog", "bark", "growling", "canis familiaris")
+
+
+def is_dog_label(label):
+    """isDogDetection: whether a raw classifier label is a dog class for the dog-bark filter (case-insensitive)."""
+    low = str(label).lower()
+    return low in DOG_LABELS or low.startswith(DOG_LABEL_PREFIX)
+
+
+class EventGuards:
+    """The reference's dog-bark and daylight filters for analyze_files(events=..., guards=...) (include/bnhip.h, "Detection events:
+    dog-bark and daylight filters").
+
+    Dog bark: a result of a dog class above `confidence` marks its window; an event of one of `species` whose deadline lies at most
+    remember_minutes behind the last such window before it is dropped (status host.EVENT_DOG).  dog_labels: the dog classes as
+    indices, or None to find them among the labels passed to tables() by the reference's rule (is_dog_label).  Daylight: an event of
+    one of daylight_species whose first window begins inside a daylight interval of its file is dropped (host.EVENT_DAYLIGHT).
+    daylight: {path: [(from_seconds, to_seconds), ...]} in seconds from the recording's start, ascending and disjoint (the host's
+    civil dawn + offset and civil dusk - offset; a path without an entry has no daylight: the filter fails open).  species and
+    daylight_species hold class indices, or labels when tables() is given labels.
+
+    Windows: remember_minutes becomes ceil(minutes * 60 * rate / hop) windows, as the hold does.  Window w begins at w * hop / rate
+    seconds and is in daylight when that instant lies in [from, to): both edges are rounded up to the next window start,
+    ceil(seconds * rate / hop)."""
+
+    def __init__(self, confidence, species=(), remember_minutes=5.0, dog_labels=None, daylight_species=(), daylight=None):
+        self.confidence, self.species, self.remember_minutes = float(confidence), list(species), float(remember_minutes)
+        self.dog_labels = None if dog_labels is None else list(dog_labels)
+        self.daylight_species, self.daylight = list(daylight_species), dict(daylight or {})
+        if self.remember_minutes < 0:
+            raise ValueError("remember_minutes must not be negative")
+
+    def tables(self, n_classes, model_rate, hop, labels=None, paths=()):
+        """-> the host.EventGuards for a model of n_classes classes analysed at `hop` samples of model_rate; paths: the call's
+        files in order, whose daylight intervals become the spans of recordings 0, 1, ..."""
+        from . import host
+
+        def table(items):
+            t = np.zeros(n_classes, np.uint8)
+            for it in items:
+                if isinstance(it, str):
+                    if labels is None or it not in labels:
+                        raise ValueError(f"unknown species label: {it!r}")
+                    it = list(labels).index(it)
+                t[int(it)] = 1
+            return t if t.any() else None
+
+        if self.dog_labels is not None:
+            dog = table(self.dog_labels)
+        else:
+            dog = table([j for j, name in enumerate(labels or ()) if j < n_classes and is_dog_label(name)])
+        edge = lambda seconds: max(0, int(math.ceil(seconds * model_rate / hop)))
+        spans = []
+        for r, path in enumerate(paths):
+            last = 0
+            for lo, hi in self.daylight.get(path, ()):
+                lo, hi = edge(lo), edge(hi)
+                if lo < last:
+                    raise ValueError(f"{path}: daylight intervals must ascend and not overlap")
+                if hi > lo:                                               # (an interval that holds no window start drops nothing)
+                    spans.append((r, lo, hi))
+                    last = hi
+        remember = int(math.ceil(self.remember_minutes * 60.0 * model_rate / hop))
+        return host.EventGuards(dog, _round_down_f32(self.confidence), table(self.species), remember, table(self.daylight_species),
+                                np.array(spans, np.int32).reshape(-1, 3) if spans else None)
+
+
 class ClipExport:
     """What analyze_files(events=..., export=...) saves of every detection event, as the reference does for an approved detection
     (include/bnhip.h, "Detection clips"): the clip from pre_capture_seconds before the event's first window to length_seconds -
@@ -293,7 +362,7 @@ def clip_spans(events, resampled_length, hop, export, model_rate=48000):
 
 
 def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
-                  device=0, device_resample=False, channels=None, return_chosen=False, events=None, export=None, extend=None):
+                  device=0, device_resample=False, channels=None, return_chosen=False, events=None, export=None, extend=None, guards=None):
     """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
     path, each what analyze_file returns for that file.  The files' PCM bytes are sent as they are when all of them are at the
     model's rate and share one bit depth; otherwise every file goes as float32 (converted, and resampled where its rate differs,
@@ -320,7 +389,12 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
 
     extend (an ExtendedCapture, with events): the events of its species last as long as the bird kept calling
     (`bnhip_analyze_channels_pcm_events_extended`, `bnhip_analyze_channels_pcm_clips_extended`); the call takes the channels route, as
-    with export, and an export with extended=True then cuts every clip to its event's last hit."""
+    with export, and an export with extended=True then cuts every clip to its event's last hit.
+
+    guards (an EventGuards, with events): the reference's dog-bark and daylight filters run on the device behind the other two
+    (`bnhip_analyze_channels_pcm_events_guarded`, `bnhip_analyze_channels_pcm_clips_guarded`), with or without an extend; the call
+    takes the channels route.  A dropped event is left out - with keep_dropped it comes with status host.EVENT_DOG or
+    host.EVENT_DAYLIGHT - and gets no clip.  `labels` is where the dog classes are looked for."""
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
     if return_chosen and channels is None:
@@ -329,9 +403,11 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
         raise ValueError("export needs events, without keep_dropped")
     if extend is not None and events is None:
         raise ValueError("extend needs events")
+    if guards is not None and events is None:
+        raise ValueError("guards need events")
     recs = crecs = None
     # (the export and the extend take the files' frames: channel 0 is read there)
-    select = 0 if channels is None and (export is not None or extend is not None) else channels
+    select = 0 if channels is None and (export is not None or extend is not None or guards is not None) else channels
     if select is None:
         pcm = [read_wav_pcm(p) for p in paths]
         depths = {bits for _, _, bits in pcm}
@@ -372,14 +448,16 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     if events is not None:
         flt = events.tables(classifier.num_species(),model_rate, hop, overlap_seconds)
         ext = None if extend is None else extend.tables(classifier.num_species(), model_rate, hop)
+        gds = None if guards is None else guards.tables(classifier.num_species(), model_rate, hop, labels, list(paths))
         chosen = clips = None
         if export is not None:
             clips = classifier.analyze_channels_pcm_clips(b"".join(bufs), crecs, model_rate, hop, flt, export.settings(model_rate), min_tail,
-                                                          k=top_k, sensitivity=sensitivity, max_clips=export.max_clips, extend=ext)
+                                                          k=top_k, sensitivity=sensitivity, max_clips=export.max_clips, extend=ext,
+                                                          guards=gds)
             ev, chosen = clips.events, ["mix" if s < 0 else int(s) for s in clips.chosen]
         elif crecs is not None:
             ev, sel = classifier.analyze_channels_pcm_events(b"".join(bufs), crecs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity,
-                                                             extend=ext)
+                                                             extend=ext, guards=gds)
             chosen = ["mix" if s < 0 else int(s) for s in sel]
         elif recs is not None:
             ev = classifier.analyze_mixed_pcm_events(b"".join(bufs), recs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)

@@ -588,6 +588,72 @@ int bnhip_event_bank_set_thresholds(bnhip_event_bank* b, const int32_t* level, c
 int bnhip_event_bank_reset_thresholds(bnhip_event_bank* b, int class_index);
 float bnhip_event_threshold(float base, int level, float min_threshold);
 
+/* Detection events: dog-bark and daylight filters.  The reference's shouldDiscardDetection (processor.go:1485-1566) runs four tests
+ * at the flush, in this order: the minimum count, the privacy filter, the dog-bark filter (dogbarkfilter.go:15-27, marked at
+ * processor.go:1302-1314) and the daylight filter (daylight_filter.go:104-160).  The first two are the rules above; the guards are
+ * the other two, taken by both rules as one more struct, so that status 0 means approved by every test of the flush.  The clock
+ * stays audio time in windows; the host turns DogBarkFilter.Remember (minutes) into windows as it does for hold_windows, with a
+ * ceiling, and the sun times (its own suncalc: the device gets intervals, not a location) into spans of windows.
+ *   dog hit  A result (x, c) with class_dog[c] != 0 and x > dog_threshold: float32, strict, false for a NaN on either side.  It marks
+ *            window w of its recording or source (LastDogDetection).  Marking does not look at class_threshold and does not stop the
+ *            result from being an ordinary hit - the dog class is a class like any other and may form events of its own; a class
+ *            that is also a veto class still forms none.  class_dog NULL: no dog class.
+ *   status 3 BNHIP_EVENT_DOG ("recent dog bark"): class_dog_filtered[c] != 0 and the recording or source has a dog hit at a window
+ *            v < d with d - v <= dog_remember_windows, d the event's final deadline (b + hold_windows, or the sliding one of extended
+ *            capture).  Only the largest such v matters, and it may lie before b.  A recording or source without a dog hit drops
+ *            nothing.  The reference flushes at the deadline, so its time.Since(lastDogBark) is the distance from the bark to d;
+ *            measuring from d - this project's choice - is also what makes an early bnhip_event_bank_flush and the file tail agree.
+ *   status 4 BNHIP_EVENT_DAYLIGHT: class_daylight[c] != 0 and first_window lies in a daylight span [from, to) of its recording or
+ *            source (FirstDetected in [CivilDawn + offset, CivilDusk - offset)).  No span - an inverted or unknown window of the
+ *            reference - is no daylight: the filter fails open.
+ *   order    1 (count), then 2 (veto), then 3, then 4: the first that applies is the status.  BNHIP_EVENTS_KEEP_DROPPED answers 3
+ *            and 4 like 1 and 2; without it only status 0 is answered.
+ *   spans    File tail: daylight_spans [n_spans][3] = (recording, from, to), ascending by (recording, from), disjoint within a
+ *            recording, 0 <= from < to, n_spans <= 2^20.  Bank: bnhip_event_bank_set_daylight(bank, source, spans [n][2] = (from, to),
+ *            n) with at most BNHIP_EVENT_DAYLIGHT_SPANS per source, in that source's clock; the struct's daylight_spans / n_spans are
+ *            not read by a bank.  It is a setting, valid from the next call on and read at the flush: the spans have to cover the
+ *            first windows of the events that are still live.  source -1 is allowed with n == 0 only and clears every source.
+ *   bnhip_detection_events_guarded, bnhip_analyze_channels_pcm_events_guarded, bnhip_analyze_channels_pcm_clips_guarded  Their
+ *            _extended namesakes with the guards behind the extend, which may be NULL here (no class slides).  Guards whose three
+ *            tables are NULL or all zero, and no spans, answer the namesake's bytes.  The clip export cuts status-0 events only, as
+ *            before.
+ *   bnhip_event_bank_set_guards  On any bank - plain, extended or dynamic - from the next call on; NULL turns the guards off.
+ *            process, process_device, flush, pending (still status -1) and bnhip_windows_predict_events carry the rule unchanged.
+ *            The dog window of a source is recorded only while guards with a class_dog table are set (the reference marks only
+ *            while the filter is enabled); it lives in the source's slab, so a failed call leaves it as it was, and it survives a
+ *            flush and set_guards(NULL).  bnhip_event_bank_reset of a source clears its dog window and its daylight spans: its
+ *            clock returns to 0.  The rows of a recording fed and then flushed answer exactly bnhip_detection_events_guarded of
+ *            those rows when the source's spans are the recording's.  In a dynamic bank an event with status 3 or 4 does not learn
+ *            (processApprovedDetection is never reached); the touch of rows is not affected.  A bank that never had guards set
+ *            runs exactly the launches and copies it ran before.
+ * BNHIP_E_INVALID (before any device call, nothing written, the handle stays usable): what the namesake refuses, NULL guards on the
+ * _guarded entries, dog_remember_windows < 0, n_spans < 0 or above 2^20, NULL daylight_spans with n_spans > 0, spans out of order,
+ * overlapping, empty or negative, a span's recording outside the call (outside 0..65534 for bnhip_detection_events_guarded), more
+ * than BNHIP_EVENT_DAYLIGHT_SPANS spans in a bank call, a source outside the bank, source -1 with n != 0. */
+#define BNHIP_EVENT_DOG 3
+#define BNHIP_EVENT_DAYLIGHT 4
+#define BNHIP_EVENT_DAYLIGHT_SPANS 8
+typedef struct bnhip_event_guards {
+    const uint8_t* class_dog;          /* [n_classes], non-zero: a dog class; NULL: none */
+    const uint8_t* class_dog_filtered; /* [n_classes], non-zero: a species the bark suppresses (DogBarkFilter.Species); NULL: none */
+    const uint8_t* class_daylight;     /* [n_classes], non-zero: a species dropped in daylight (DaylightFilter.Species); NULL: none */
+    const int32_t* daylight_spans;     /* [n_spans][3] (recording, from, to): the file tail's; NULL with n_spans == 0 */
+    float dog_threshold;               /* DogBarkFilter.Confidence: a dog result must exceed it */
+    int32_t dog_remember_windows;      /* DogBarkFilter.Remember, >= 0 */
+    int32_t n_spans;
+    int32_t reserved;
+} bnhip_event_guards;
+int bnhip_detection_events_guarded(int device, const bnhip_detection* rows, size_t n_rows, int n_classes, const bnhip_event_filter* filter,
+                                   const bnhip_event_extend* extend /* may be NULL */, const bnhip_event_guards* guards, bnhip_event* out,
+                                   size_t cap, size_t* n_out);
+int bnhip_analyze_channels_pcm_events_guarded(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                              int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                              const bnhip_event_filter* filter, const bnhip_event_extend* extend /* may be NULL */,
+                                              const bnhip_event_guards* guards, bnhip_event* out, size_t cap, size_t* n_out,
+                                              int32_t* chosen);
+int bnhip_event_bank_set_guards(bnhip_event_bank* b, const bnhip_event_guards* guards /* NULL: off */);
+int bnhip_event_bank_set_daylight(bnhip_event_bank* b, int source, const int32_t* spans /* [n][2] */, int n);
+
 /* Detection clips: what the reference saves for every approved detection, made from the recordings of a file-analysis call while
  * they are still on the device.  Its processor takes the audio from BeginTime back by the pre-capture to the end of the capture
  * window, or under extended capture to as long as the bird kept calling (internal/analysis/processor/extended_capture.go:232-280,
@@ -661,6 +727,12 @@ int bnhip_analyze_channels_pcm_clips_extended(bnhip_model* m, const void* pcm, c
                                               int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
                                               const bnhip_event_filter* filter, const bnhip_event_extend* extend, int32_t* chosen,
                                               const bnhip_clip_export* x, bnhip_clips_out* out);
+/* ... under the guards ("Detection events: dog-bark and daylight filters"); extend may be NULL */
+int bnhip_analyze_channels_pcm_clips_guarded(bnhip_model* m, const void* pcm, const bnhip_channels_recording* recs, int n_recordings,
+                                             int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                                             const bnhip_event_filter* filter, const bnhip_event_extend* extend,
+                                             const bnhip_event_guards* guards, int32_t* chosen, const bnhip_clip_export* x,
+                                             bnhip_clips_out* out);
 
 /* Capture bank: the real-time path's detection clips.  The reference keeps a CaptureBuffer per source - a circular PCM buffer with a
  * monotonic byte counter, from which ReadSegment cuts a detection's audio (internal/audiocore/buffer/capture.go:60-112, 132-179,
