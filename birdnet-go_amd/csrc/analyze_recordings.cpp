@@ -6,6 +6,8 @@
 #include <climits>
 #include <string>
 
+#include "flac_parse.h"
+
 using namespace bnhip;
 
 static_assert(sizeof(bnhip_recording) == 16, "a recording's description is 16 bytes");
@@ -122,6 +124,28 @@ int describe(const bnhip_channels_recording* recs, int n_recordings, int model_r
     return mixed_describe(model_rate, rec);
 }
 
+int describe(const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings, int model_rate, Recordings* rec) {
+    if (int rc = count_check(streams, n_recordings)) return rc;
+    if (!offsets || !select) return set_err(BNHIP_E_INVALID, "NULL argument");
+    std::vector<bnhip_channels_recording> recs((size_t)n_recordings);
+    rec->flac_infos.resize((size_t)n_recordings);
+    rec->flac_offsets = offsets;
+    for (int r = 0; r < n_recordings; r++) {
+        const std::string who = "recording " + std::to_string(r) + ": ";
+        if (offsets[r + 1] < offsets[r]) return set_err(BNHIP_E_INVALID, "offsets must ascend");
+        bnhip_flac_info& in = rec->flac_infos[(size_t)r];
+        flac_stream_info(streams + offsets[r], (size_t)(offsets[r + 1] - offsets[r]), &in, true);
+        if (in.status == BNHIP_FLAC_BAD_METADATA) return set_err(BNHIP_E_INVALID, who + "not a FLAC stream, or its metadata blocks are damaged");
+        if (in.status != BNHIP_FLAC_OK)
+            return set_err(BNHIP_E_INVALID, who + "a FLAC stream of " + std::to_string(in.channels) + " channels, " + std::to_string(in.bits) +
+                                                " bits, block size " + std::to_string(in.max_block) +
+                                                " is not decoded (1 or 2 channels, 16 or 24 bits, a fixed block size up to 8192, or 16384 for mono 16-bit)");
+        recs[(size_t)r] = bnhip_channels_recording{(int64_t)in.total_samples, (int32_t)in.rate, (int32_t)in.bits, (int32_t)in.channels, select[r]};
+    }
+    if (int rc = flacdec_burst_check(n_recordings, rec->flac_infos.data(), offsets, nullptr, true)) return rc;
+    return describe(recs.data(), n_recordings, model_rate, rec);
+}
+
 // (what the mixed call refuses of the recordings - the depths, rates and lengths - is recording_check's to answer)
 int channels_check(const bnhip_channels_recording* recs, int n_recordings, bool measure, Recordings* rec) {
     if (int rc = count_check(recs, n_recordings)) return rc;
@@ -182,6 +206,11 @@ SlotPlan slot_plan(const Recordings& rec, long long* slot) {
         slot[2 * r] = (long long)sp.block_bytes; slot[2 * r + 1] = lengths[r];
         sp.block_bytes += analyze_slot_bytes(lengths[r], rec.bits);
     }
+    if (rec.flac()) {
+        sp.flac_bytes = (size_t)rec.flac_offsets[rec.n];
+        sp.flac_ws = flacdec_workspace_bytes(rec.n, rec.flac_infos.data(), rec.flac_offsets, true);
+        sp.flac_res = (size_t)rec.n * sizeof(bnhip_flac_decode_result);
+    }
     if (rec.plain) return sp;
     sp.desc.resize(rec.n); sp.tile0.assign((size_t)rec.n + 1, 0);
     for (int r = 0; r < rec.n; r++) {
@@ -219,6 +248,9 @@ SlotDev slot_reserve(const SlotPlan& sp, DevCarve& cv) {
     dv.etile0 = cv.add(sp.en.tile0.size() * 8);
     dv.part = cv.add((size_t)sp.en.n_tiles() * ENERGY_ROW_BYTES);
     dv.energy = cv.add(sp.en.desc.size() * ENERGY_ROW_BYTES);
+    dv.flac_in = cv.add(sp.flac_bytes);
+    dv.flac_ws = cv.add(sp.flac_ws);
+    dv.flac_res = cv.add(sp.flac_res);
     return dv;
 }
 
@@ -227,8 +259,22 @@ void slot_upload(const SlotPlan& sp, const void* pcm, const Recordings& rec, con
     char *block = dv.at(dv.block), *raw = dv.at(dv.raw);
     if (rec.plain) AN_HIP(b, hipMemsetAsync(block, 0, dv.block_room, s));
     const char* src = static_cast<const char*>(pcm);
-    for (int r = 0; r < rec.n; src += rec.raw_bytes(r), r++)
-        AN_HIP(b, hipMemcpyAsync(rec.plain ? block + slot[2 * r] : raw + sp.desc[r].in_off, src, rec.raw_bytes(r), hipMemcpyHostToDevice, s));
+    if (rec.flac()) {
+        // the compressed bytes go up once, and the decoder writes what the copies would have brought: recording r's interleaved
+        // PCM at its own depth, on its 16-byte line of the raw block or in its slot; a frame it does not restore stays zero
+        const size_t first = (size_t)rec.flac_offsets[0];
+        if (sp.flac_bytes > first) AN_HIP(b, hipMemcpyAsync(dv.at(dv.flac_in) + first, src + first, sp.flac_bytes - first, hipMemcpyHostToDevice, s));
+        if (!rec.plain) AN_HIP(b, hipMemsetAsync(raw, 0, sp.raw_bytes, s));
+        if (b.he == hipSuccess) {
+            FlacDecWork w = flacdec_work(rec.n, rec.flac_infos.data(), rec.flac_offsets, dv.at<void>(dv.flac_ws), true);
+            for (int r = 0; r < rec.n; r++) flacdec_place(w, r, (unsigned long long)(rec.plain ? slot[2 * r] : sp.desc[r].in_off));
+            launch_flacdec(dv.at<uint8_t>(dv.flac_in), w, rec.plain ? block : raw, rec.plain ? sp.block_bytes : sp.raw_bytes,
+                           dv.at<bnhip_flac_decode_result>(dv.flac_res), s);
+        }
+    } else {
+        for (int r = 0; r < rec.n; src += rec.raw_bytes(r), r++)
+            AN_HIP(b, hipMemcpyAsync(rec.plain ? block + slot[2 * r] : raw + sp.desc[r].in_off, src, rec.raw_bytes(r), hipMemcpyHostToDevice, s));
+    }
     if (rec.plain) return;
     // (the lock is held from the tables' lookup until the launch that reads them is enqueued, api_oneshot.h)
     TableLock lock(g_rate_tables.mu);

@@ -1,7 +1,9 @@
 // The recordings of a file-analysis call (api_analyze.cpp, api_clips.cpp, api_channels.cpp): the three forms the C ABI states them
 // in taken to one description, every refusal that needs neither a handle nor a device, and the recordings on the device - the slot
 // block of analyze.h that the windows are framed from, filled by one copy per recording or, for recordings at their own rates,
-// depths and channel counts, by the slot launch of resample.h behind the measurement of channels.h.
+// depths and channel counts, by the slot launch of resample.h behind the measurement of channels.h.  A fourth form states the
+// recordings as FLAC streams: it is the channels form with every field read from STREAMINFO, and the device decoder of
+// flac_decode.h writes the bytes that the copies would have brought.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +14,7 @@
 #include "analyze.h"
 #include "api_oneshot.h"
 #include "channels.h"
+#include "flac_decode.h"
 #include "resample.h"
 
 namespace bnhip {
@@ -41,6 +44,10 @@ struct Recordings {
     std::vector<int> channels, select;
     bool multi = false;
     std::vector<int32_t> chosen;                  // [n] of a multi burst, filled by the call: what was read
+    // the FLAC form: the recordings' bytes are compressed streams (the call's pcm argument) at flac_offsets [n + 1]; every info OK
+    std::vector<bnhip_flac_info> flac_infos;
+    const uint64_t* flac_offsets = nullptr;
+    bool flac() const { return !flac_infos.empty(); }
 
     // the samples of the slots: what the windows are framed over
     const int64_t* lengths() const { return recs.empty() ? given : n_out.data(); }
@@ -64,6 +71,9 @@ struct Recordings {
 int describe(int bits, const int64_t* lengths, int n_recordings, Recordings* rec);
 int describe(const bnhip_recording* recs, int n_recordings, int model_rate, Recordings* rec);
 int describe(const bnhip_channels_recording* recs, int n_recordings, int model_rate, Recordings* rec);
+// FLAC streams back to back in host memory: the channels form of what each STREAMINFO says, with select [n]; a stream that
+// bnhip_flac_recording_info does not accept is refused here, by name
+int describe(const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings, int model_rate, Recordings* rec);
 // the channels form's own part of that: every refusal of the channel fields and of the burst's size in samples; fills recs,
 // channels, select, multi.  measure: the measurement entry, where a float32 recording is refused whatever its select
 int channels_check(const bnhip_channels_recording* recs, int n_recordings, bool measure, Recordings* rec);
@@ -85,6 +95,7 @@ EnergyPlan energy_plan(const Recordings& rec, bool all);
 // selection table [n] each, and the measurement of the recordings that ask for one
 struct SlotPlan {
     size_t block_bytes = 0, raw_bytes = 0, rs_lds = 0;
+    size_t flac_bytes = 0, flac_ws = 0, flac_res = 0;      // the FLAC form: the compressed burst, the decoder's workspace, its results
     std::vector<ResampleSlotDesc> desc;
     std::vector<long long> tile0;
     std::vector<int> chsel;
@@ -95,18 +106,20 @@ SlotPlan slot_plan(const Recordings& rec, long long* slot);
 
 // Where a call has reserved the plan's parts, as handles of cv: the slot block (block_room bytes of it are zero-filled on the fast
 // path), the raw block, the descriptors, the tile prefix, the counts and selections, the measurement's descriptors, tile prefix,
-// partials and sums
+// partials and sums, and for the FLAC form the compressed burst, the decoder's workspace and its results
 struct SlotDev {
     const DevCarve* cv;
     size_t block_room;
-    size_t block, raw, desc, tile0, chsel, edesc, etile0, part, energy;
+    size_t block, raw, desc, tile0, chsel, edesc, etile0, part, energy, flac_in, flac_ws, flac_res;
     template <class T = char> T* at(size_t part) const { return cv->at<T>(part); }
 };
 SlotDev slot_reserve(const SlotPlan& sp, DevCarve& cv);
 
 // The recordings go up and the slot block is filled, on s: the slots' zero fill and one copy per recording into its slot, or
 // one copy per recording into the raw block, the tables, the measurement where a recording asks for one, and the slot launch
-// (k_resample_slots writes every slot whole, its zeros included).  The first failure is left in b.
+// (k_resample_slots writes every slot whole, its zeros included).  The FLAC form: one copy of the compressed burst, the raw block
+// (or on the fast path the slots) cleared, and the decoder's launches in place of the copies; the rest is the same.  The first
+// failure is left in b.
 void slot_upload(const SlotPlan& sp, const void* pcm, const Recordings& rec, const long long* slot, int device, const SlotDev& dv, hipStream_t s,
                  DevBlocks& b);
 

@@ -97,6 +97,7 @@ struct ClipsTail { const bnhip_clip_export* x; bnhip_clips_out* o; int model_rat
 struct Answer {
     std::variant<TopK, Rows, Events> what;
     int32_t* chosen = nullptr;                    // the channels entries: [n] what was read of each recording, or NULL
+    bnhip_flac_decode_result* flac_result = nullptr;      // the FLAC entries: [n] what the decoder found of each stream
     const ClipsTail* clips = nullptr;             // with the events down and the recordings still in their slots, the clip export runs
 };
 
@@ -108,7 +109,7 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
     const Rows* rw = std::get_if<Rows>(&a.what);
     const Events* ev = std::get_if<Events>(&a.what);
     const int64_t* lengths = rec.lengths();
-    if (!q.m || !q.pcm || !lengths) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (!q.m || !q.pcm || !lengths || (rec.flac() && !a.flac_result)) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (!std::visit([](const auto& w) { return w.complete(); }, a.what)) return set_err(BNHIP_E_INVALID, "NULL argument");
     if (ev) if (int rc = event_filter_check(ev->filter)) return rc;
     if (ev && ev->extended) if (int rc = event_extend_check(ev->filter->hold_windows, ev->extend)) return rc;
@@ -202,6 +203,9 @@ int analyze(const Request& q, Recordings& rec, const Answer& a) {
         rec.chosen.resize(rec.n);
         AN_HIP(b, hipMemcpyAsync(rec.chosen.data(), dv.at<int>(dv.chsel) + rec.n, (size_t)rec.n * 4, hipMemcpyDeviceToHost, e.stream));
     }
+    if (ok() && rec.flac())
+        AN_HIP(b, hipMemcpyAsync(a.flac_result, dv.at<void>(dv.flac_res), (size_t)rec.n * sizeof(bnhip_flac_decode_result), hipMemcpyDeviceToHost,
+                                 e.stream));
     {
         const hipError_t he = hipStreamSynchronize(e.stream);
         if (b.he == hipSuccess) b.he = he;
@@ -300,6 +304,54 @@ int bnhip_analyze_mixed_pcm_events(bnhip_model* m, const void* pcm, const bnhip_
                                    bnhip_event* out, size_t cap, size_t* n_out) {
     BN_GUARD_BEGIN
     return analyze_entry(AN_REQUEST, {.what = Events{.filter = filter, .out = out, .cap = cap, .n_out = n_out}}, recs, n_recordings, model_rate);
+    BN_GUARD_END((void)0)
+}
+
+// ---- recordings as FLAC streams: the channels calls over what each STREAMINFO says, decoded on the device
+long long bnhip_analyze_flac_windows(const uint8_t* streams, const uint64_t* offsets, int n_recordings, int model_rate, int n_samples, int hop,
+                                     int64_t min_tail, int64_t* first_window, int64_t* resampled_length) {
+    BN_GUARD_BEGIN
+    if (!first_window) return set_err(BNHIP_E_INVALID, "NULL argument");
+    if (n_recordings < 1 || n_recordings > 65535) return set_err(BNHIP_E_INVALID, "n_recordings must be in [1, 65535]");
+    const std::vector<int32_t> select((size_t)n_recordings, BNHIP_CHANNEL_MIX);
+    Recordings rec;
+    if (int rc = describe(streams, offsets, select.data(), n_recordings, model_rate, &rec)) return rc;
+    if (int rc = check_table(rec.lengths(), n_recordings, n_samples, hop, min_tail)) return rc;
+    const long long W = window_table(rec.lengths(), n_recordings, n_samples, hop, min_tail, first_window);
+    if (resampled_length) std::copy(rec.n_out.begin(), rec.n_out.end(), resampled_length);
+    return W;
+    BN_GUARD_END((void)0)
+}
+
+#define AN_FLAC_REQUEST {.m = m, .pcm = streams, .hop = hop, .min_tail = min_tail, .activation = activation, .sensitivity = sensitivity, .k = k}
+
+int bnhip_analyze_flac_topk(bnhip_model* m, const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings,
+                            int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k, float* out_conf,
+                            int32_t* out_idx, int32_t* chosen, bnhip_flac_decode_result* result) {
+    BN_GUARD_BEGIN
+    return analyze_entry(AN_FLAC_REQUEST, {.what = TopK{.conf = out_conf, .idx = out_idx}, .chosen = chosen, .flac_result = result},
+                        streams, offsets, select, n_recordings, model_rate);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_analyze_flac(bnhip_model* m, const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings, int model_rate,
+                       int hop, int64_t min_tail, int activation, double sensitivity, int k, float threshold, bnhip_detection* out, size_t cap,
+                       size_t* n_out, int32_t* chosen, bnhip_flac_decode_result* result) {
+    BN_GUARD_BEGIN
+    return analyze_entry(AN_FLAC_REQUEST,
+                        {.what = Rows{.threshold = threshold, .out = out, .cap = cap, .n_out = n_out}, .chosen = chosen, .flac_result = result},
+                        streams, offsets, select, n_recordings, model_rate);
+    BN_GUARD_END((void)0)
+}
+
+int bnhip_analyze_flac_events(bnhip_model* m, const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings,
+                              int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                              const bnhip_event_filter* filter, bnhip_event* out, size_t cap, size_t* n_out, int32_t* chosen,
+                              bnhip_flac_decode_result* result) {
+    BN_GUARD_BEGIN
+    return analyze_entry(AN_FLAC_REQUEST,
+                        {.what = Events{.filter = filter, .out = out, .cap = cap, .n_out = n_out}, .chosen = chosen, .flac_result = result},
+                        streams, offsets, select, n_recordings, model_rate);
     BN_GUARD_END((void)0)
 }
 

@@ -172,7 +172,7 @@ struct FlacSource : ClipSource {
             const hipError_t he = hipMemcpy(d_in + offsets[0], streams + offsets[0], in_bytes, hipMemcpyHostToDevice);
             if (he != hipSuccess) return he;
         }
-        launch_flacdec(d_in, flacdec_work(n_streams, infos.data(), offsets, cv.at<void>(o_ws)), d_pcm, pcm_bytes / 2,
+        launch_flacdec(d_in, flacdec_work(n_streams, infos.data(), offsets, cv.at<void>(o_ws)), d_pcm, pcm_bytes,
                        cv.at<bnhip_flac_decode_result>(o_res), nullptr);
         return hipGetLastError();
     }

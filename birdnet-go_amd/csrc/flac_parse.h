@@ -1,8 +1,10 @@
 // The FLAC frame reader of the device decoder (flac_decode.hip) stated once, as host and device inline code: the frame header test,
-// the bit reader over a bounded byte span, the subframe and residual readers and the predictor, written from RFC 9639 for mono
-// 16-bit streams of fixed block size.  The kernels and a plain g++ build (tests/native/flac_parse_main.cpp, under ASan + UBSan)
-// compile this one statement.  Nothing here reads outside the span it is given, loops longer than the block size or the span's bits
-// allow, or relies on signed overflow or a negative shift: prediction sums are int64, the wasted-bit shift is a multiply.
+// the bit reader over a bounded byte span, the subframe and residual readers and the predictor, written from RFC 9639 for streams
+// of fixed block size: mono 16-bit clips (flac_parse_frame, int16 samples and int32 products) and recordings of 1 or 2 channels
+// at 16 or 24 bits (flac_parse_frame_wide, int32 samples and 64-bit products, the stereo decorrelation beside it).  The kernels
+// and plain g++ builds (tests/native/flac_parse_main.cpp and flac_parse_wide_main.cpp, under ASan + UBSan) compile this one
+// statement.  Nothing here reads outside the span it is given, loops longer than the block size or the span's bits allow, or
+// relies on signed overflow or a negative shift: prediction sums are int64, the wasted-bit shift is a multiply.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -19,21 +21,33 @@
 namespace bnhip {
 
 constexpr uint32_t FLACDEC_MIN_BLOCK = 16, FLACDEC_MAX_BLOCK = 16384;     // STREAMINFO block sizes that are decoded
+// ... of a wide stream (anything but mono 16-bit): its frame's bytes and its int32 samples lie side by side in LDS (flac_decode.h)
+constexpr uint32_t FLACDEC_MAX_BLOCK_WIDE = 8192;
 constexpr uint32_t FLACDEC_HEAD_MAX = 16;          // sync and codes 4, coded number 7, explicit block size 2, explicit rate 2, CRC-8 1
 constexpr uint32_t FLACDEC_MAX_ORDER = 32;
 // The bytes a frame of bs samples is read within: the VERBATIM bound.  A frame that needs more is not a frame.
 FLACP_HD size_t flacdec_frame_cap(uint32_t bs) { return 2 * (size_t)bs + 32; }
+// ... of a stream of `channels` at `bits`: bs x channels x bytes, a stereo frame's side channel taking one bit more per sample
+FLACP_HD size_t flacdec_frame_cap(uint32_t bs, uint32_t channels, uint32_t bits) {
+    return (size_t)bs * channels * (bits / 8) + (channels == 2 ? (size_t)bs / 8 + 1 : 0) + 32;
+}
 
 // No frame is shorter: a 6-byte header, a CONSTANT subframe's 3 bytes, CRC-16.  A stream whose STREAMINFO promises more frames than its
 // audio bytes can hold is CORRUPT at its audio offset without a look at the bytes, so a sample count in a damaged file sizes nothing.
 constexpr uint32_t FLACDEC_MIN_FRAME = 11;
 FLACP_HD bool flacdec_too_short(uint64_t frames, uint64_t audio_bytes) { return frames > audio_bytes / FLACDEC_MIN_FRAME; }
+// ... of a stream of `channels` at `bits`: a CONSTANT subframe per channel (independent channels: the shortest); 11 for mono 16
+FLACP_HD uint32_t flacdec_min_frame(uint32_t channels, uint32_t bits) { return 6u + channels * (1u + bits / 8u) + 2u; }
+FLACP_HD bool flacdec_too_short(uint64_t frames, uint64_t audio_bytes, uint32_t channels, uint32_t bits) {
+    return frames > audio_bytes / flacdec_min_frame(channels, bits);
+}
 
-enum { FLACP_OK = 0, FLACP_INVALID = 1, FLACP_RANGE = 2 };     // a frame's parse: fine, not a frame, a sample outside int16
+enum { FLACP_OK = 0, FLACP_INVALID = 1, FLACP_RANGE = 2 };     // a frame's parse: fine, not a frame, a sample outside the depth
 
 // What a stream's STREAMINFO holds every frame header to.
 struct FlacStreamShape {
     uint32_t rate, bs, total, frames;               // frames = ceil(total / bs)
+    uint32_t channels = 1, bits = 16;               // 1 or 2; 16 or 24
 };
 struct FlacFrameHead {
     uint32_t number, bs, bytes;                     // bytes: the header's, CRC-8 included
@@ -65,14 +79,16 @@ FLACP_HD uint32_t flac_crc16(const uint8_t* p, size_t n) {
 }
 
 // Is p[0 .. avail) the start of a frame header of this stream?  Sync with the blocking-strategy and reserved bits clear, no reserved
-// code, mono, 16 bits (or "as STREAMINFO"), the stream's rate, a well-formed coded number below the frame count, the block size that
+// code, the stream's channel count (mono: code 0; stereo: independent 1, left/side 8, side/right 9, mid/side 10) and depth (its
+// size code or "as STREAMINFO"), the stream's rate, a well-formed coded number below the frame count, the block size that
 // frame must have (bs, or the remainder in the last frame), CRC-8.  avail is what is left of the stream.
 FLACP_HD bool flac_frame_head(const uint8_t* p, size_t avail, const FlacStreamShape& s, FlacFrameHead* h) {
     if (avail < 6) return false;
     if (p[0] != 0xFFu || p[1] != 0xF8u) return false;
     const uint32_t bs_code = p[2] >> 4, rate_code = p[2] & 15u, channels = p[3] >> 4, size_code = (p[3] >> 1) & 7u;
-    if ((p[3] & 1u) || bs_code == 0 || rate_code == 15 || channels != 0) return false;
-    if (size_code != 0 && size_code != 4) return false;
+    if ((p[3] & 1u) || bs_code == 0 || rate_code == 15) return false;
+    if (s.channels == 1 ? channels != 0 : (channels != 1 && channels != 8 && channels != 9 && channels != 10)) return false;
+    if (size_code != 0 && size_code != (s.bits == 16 ? 4u : 6u)) return false;
     const uint32_t b0 = p[4];
     uint32_t nb = 1;
     uint64_t number = b0;
@@ -185,14 +201,15 @@ struct FlacBits {
 // Where a frame's samples go.  The count-only sink parses a frame to its end without predicting; the store sink keeps the samples
 // (before the wasted-bit shift, which the reader applies at the end) where the predictor reads them back.
 struct FlacCountSink {
-    static constexpr bool kStore = false;
+    static constexpr bool kStore = false, kWide = false;
+    FLACP_HD void channel(uint32_t) {}
     FLACP_HD void put(uint32_t, int32_t) {}
     FLACP_HD int32_t get(uint32_t) const { return 0; }
     FLACP_HD void set_coef(uint32_t, int32_t) {}
     FLACP_HD int32_t coef(uint32_t) const { return 0; }
 };
 struct FlacStoreSink {
-    static constexpr bool kStore = true;
+    static constexpr bool kStore = true, kWide = false;     // kWide: a coefficient times a sample needs 64 bits
     int16_t* x;                                     // [the block size]
     int32_t* c;                                     // [FLACDEC_MAX_ORDER] the predictor's coefficients (beside x: LDS on the device)
     FLACP_HD void put(uint32_t i, int32_t v) { x[i] = (int16_t)v; }
@@ -200,7 +217,133 @@ struct FlacStoreSink {
     FLACP_HD void set_coef(uint32_t j, int32_t v) { c[j] = v; }
     FLACP_HD int32_t coef(uint32_t j) const { return c[j]; }
 };
+// ... of a recording's frame: int32 samples (up to 25 bits: a 24-bit stream's side channel), channel ch at x + ch * stride
+struct FlacWideSink {
+    static constexpr bool kStore = true, kWide = true;
+    int32_t* x;                                     // [channels][stride]
+    int32_t* c;                                     // [FLACDEC_MAX_ORDER]
+    uint32_t stride, base;
+    FLACP_HD void channel(uint32_t ch) { base = ch * stride; }
+    FLACP_HD void put(uint32_t i, int32_t v) { x[base + i] = v; }
+    FLACP_HD int32_t get(uint32_t i) const { return x[base + i]; }
+    FLACP_HD void set_coef(uint32_t j, int32_t v) { c[j] = v; }
+    FLACP_HD int32_t coef(uint32_t j) const { return c[j]; }
+};
 
+// One subframe of bs samples at `depth` bits (the stream's, or one more for a side channel) into the sink's current channel, the
+// wasted-bit shift applied.  -> FLACP_OK, FLACP_INVALID for anything that is not a subframe, or FLACP_RANGE (store sinks only) when
+// a predicted sample does not fit the depth.  Sink::kWide chooses the product's width at compile time: the residual loop holds no
+// run-time branch on it.
+template <class Sink>
+FLACP_HD int flac_parse_subframe(FlacBits& b, uint32_t bs, int depth, Sink& sink) {
+    if (b.take(1)) return FLACP_INVALID;
+    const uint32_t kind = b.take(6);
+    uint32_t wasted = 0;
+    if (b.take(1)) wasted = b.unary() + 1u;
+    if (b.fail || wasted >= (uint32_t)depth) return FLACP_INVALID;
+    const int bps = depth - (int)wasted;
+    const int64_t lim = (int64_t)1 << (bps - 1);
+    if (kind == 0) {
+        const int64_t v = b.stake(bps);
+        if (Sink::kStore) for (uint32_t i = 0; i < bs; i++) sink.put(i, (int32_t)v);
+    } else if (kind == 1) {
+        for (uint32_t i = 0; i < bs && !b.fail; i++) sink.put(i, (int32_t)b.stake(bps));
+    } else if ((kind >= 8 && kind <= 12) || kind >= 32) {
+        const bool lpc = kind >= 32;
+        const uint32_t order = lpc ? kind - 31 : kind - 8;
+        if (order > bs) return FLACP_INVALID;
+        for (uint32_t i = 0; i < order; i++) sink.put(i, (int32_t)b.stake(bps));
+        int shift = 0;
+        if (lpc) {
+            const int precision = (int)b.take(4) + 1;
+            if (precision == 16) return FLACP_INVALID;
+            shift = (int)b.stake(5);
+            if (shift < 0) return FLACP_INVALID;
+            for (uint32_t j = 0; j < order; j++) sink.set_coef(j, (int32_t)b.stake(precision));
+        } else {
+            const int32_t fixed[5][4] = {{0, 0, 0, 0}, {1, 0, 0, 0}, {2, -1, 0, 0}, {3, -3, 1, 0}, {4, -6, 4, -1}};
+            for (uint32_t j = 0; j < order; j++) sink.set_coef(j, fixed[order][j]);
+        }
+        const uint32_t method = b.take(2);
+        if (method > 1) return FLACP_INVALID;
+        const int pbits = method ? 5 : 4;
+        const uint32_t esc = method ? 31 : 15;
+        const uint32_t porder = b.take(4);
+        if (b.fail || (bs & ((1u << porder) - 1u)) != 0 || (bs >> porder) < order) return FLACP_INVALID;
+        // Orders up to 8 (every FIXED predictor, and the LPC orders of this project's encoder) keep the coefficients and the last 8
+        // samples in registers; longer predictors read both back from the sink.
+        constexpr uint32_t kWin = 8;
+        const bool window = Sink::kStore && order <= kWin;
+        int32_t cw[kWin], hw[kWin];
+#if defined(__clang__)
+#pragma unroll
+#endif
+        for (uint32_t j = 0; j < kWin; j++) {
+            cw[j] = window && j < order ? sink.coef(j) : 0;
+            hw[j] = window && j < order ? sink.get(order - 1 - j) : 0;
+        }
+        uint32_t i = order;
+        for (uint32_t part = 0; part < (1u << porder); part++) {
+            const uint32_t count = (bs >> porder) - (part == 0 ? order : 0u);
+            const uint32_t k = b.take(pbits);
+            const uint32_t width = k == esc ? b.take(5) : 0u;
+            if (b.fail) return FLACP_INVALID;
+            for (uint32_t c = 0; c < count; c++, i++) {
+                int64_t r;
+                if (k == esc) {
+                    r = width ? b.stake((int)width) : 0;
+                } else {
+                    const uint64_t u = ((uint64_t)b.unary() << k) | b.take((int)k);
+                    r = (int64_t)(u >> 1) ^ -(int64_t)(u & 1u);
+                }
+                if (b.fail) return FLACP_INVALID;
+                if (Sink::kStore) {
+                    int64_t pred = 0;
+                    // (a coefficient has at most 15 bits and a kept sample 16: the product fits 32; a wide sink's samples have up
+                    // to 25 bits, its products 40, a sum of 32 of them 45)
+                    if (window) {
+#if defined(__clang__)
+#pragma unroll
+#endif
+                        for (uint32_t j = 0; j < kWin; j++) pred += Sink::kWide ? (int64_t)cw[j] * hw[j] : (int64_t)(cw[j] * hw[j]);
+                    } else {
+                        for (uint32_t j = 0; j < order; j++)
+                            pred += Sink::kWide ? (int64_t)sink.coef(j) * sink.get(i - 1 - j) : (int64_t)(sink.coef(j) * sink.get(i - 1 - j));
+                    }
+                    const int64_t v = r + (pred >> shift);
+                    if (v < -lim || v >= lim) return FLACP_RANGE;
+                    sink.put(i, (int32_t)v);
+#if defined(__clang__)
+#pragma unroll
+#endif
+                    for (uint32_t j = kWin - 1; j > 0; j--) hw[j] = hw[j - 1];
+                    hw[0] = (int32_t)v;
+                }
+            }
+        }
+    } else {
+        return FLACP_INVALID;                       // a reserved subframe type
+    }
+    if (b.fail) return FLACP_INVALID;
+    if (Sink::kStore && wasted)
+        for (uint32_t i = 0; i < bs; i++) sink.put(i, sink.get(i) * (int32_t)(1u << wasted));
+    return FLACP_OK;
+}
+
+// the zero padding to the byte behind a frame's last subframe and the room for its CRC-16 -> FLACP_OK with *frame_bytes set
+FLACP_HD int flac_frame_end(FlacBits& b, size_t n, size_t* frame_bytes) {
+    const int pad = (int)((8 - (b.bits_read() & 7)) & 7);
+    if (b.take(pad) != 0 || b.fail) return FLACP_INVALID;
+    const size_t body = b.bits_read() / 8;
+    if (body + 2 > n) return FLACP_INVALID;
+    *frame_bytes = body + 2;
+    return FLACP_OK;
+}
+
+// The clips' reader: the mono 16-bit frame as one function of its own, beside the recordings' reader (flac_parse_subframe above,
+// flac_parse_frame_wide below) and not on top of it.  Stated through the shared subframe reader the same arithmetic compiled to more scalar registers in both
+// clip kernels (the restore at the register file's limit, with spills) and the clip decoder lost 13 % ("FLAC
+// recordings"); a change to one reader is made to the other.
 // The frame whose header (head_bytes long, already tested) starts p[0 .. n): one subframe of bs samples, zero padding to the byte.
 // -> FLACP_OK with *frame_bytes = the frame's length, CRC-16 included (which the caller checks: it lies inside the span), FLACP_INVALID
 // for anything that is not a frame, or FLACP_RANGE (store sink only) when a sample does not fit 16 bits.
@@ -305,9 +448,49 @@ FLACP_HD int flac_parse_frame(const uint8_t* p, size_t n, uint32_t head_bytes, u
     return FLACP_OK;
 }
 
+// A recording's frame: one subframe per channel of the stream (s.channels, which the header test held the frame to), the side
+// channel of a stereo assignment read at one bit more than s.bits.  The channels are left as coded; *assign (the header's channel
+// code) says how flac_decorrelate takes them to left and right.
+template <class Sink>
+FLACP_HD int flac_parse_frame_wide(const uint8_t* p, size_t n, uint32_t head_bytes, uint32_t bs, const FlacStreamShape& s, Sink& sink,
+                                   size_t* frame_bytes, uint32_t* assign) {
+    if (n < 4) return FLACP_INVALID;
+    const uint32_t code = p[3] >> 4;
+    if (s.channels == 1 ? code != 0 : (code != 1 && code != 8 && code != 9 && code != 10)) return FLACP_INVALID;
+    *assign = code;
+    FlacBits b;
+    b.init(p, n, head_bytes);
+    for (uint32_t ch = 0; ch < s.channels; ch++) {
+        const bool side = (ch == 1 && (code == 8 || code == 10)) || (ch == 0 && code == 9);
+        sink.channel(ch);
+        if (const int rc = flac_parse_subframe(b, bs, (int)s.bits + (side ? 1 : 0), sink)) return rc;
+    }
+    return flac_frame_end(b, n, frame_bytes);
+}
+
+// One sample pair of a stereo frame as coded (a: the first subframe's, c: the second's) -> left and right, in exact integers;
+// false when either falls outside the stream's depth.
+FLACP_HD bool flac_decorrelate(uint32_t assign, int32_t a, int32_t c, uint32_t bits, int32_t* left, int32_t* right) {
+    int64_t l = a, r = c;
+    if (assign == 8) {
+        r = (int64_t)a - c;                                            // left, side
+    } else if (assign == 9) {
+        l = (int64_t)a + c;                                            // side, right
+    } else if (assign == 10) {
+        const int64_t m = (int64_t)a * 2 + (c & 1);                    // mid, side: (M << 1) | (S & 1)
+        l = (m + c) >> 1;
+        r = (m - c) >> 1;
+    }
+    const int64_t lim = (int64_t)1 << (bits - 1);
+    *left = (int32_t)l;
+    *right = (int32_t)r;
+    return l >= -lim && l < lim && r >= -lim && r < lim;
+}
+
 // The marker and the metadata blocks of stream[0 .. n_bytes), every read bounded by n_bytes: bnhip_flac_stream_info (bnhip.h) without
-// its argument check.  Host only.
-inline void flac_stream_info(const uint8_t* stream, size_t n_bytes, bnhip_flac_info* out) {
+// its argument check, or with `recordings` bnhip_flac_recording_info, which accepts 1 or 2 channels at 16 or 24 bits (anything but
+// mono 16-bit up to FLACDEC_MAX_BLOCK_WIDE).  Host only.
+inline void flac_stream_info(const uint8_t* stream, size_t n_bytes, bnhip_flac_info* out, bool recordings = false) {
     *out = bnhip_flac_info{};
     out->status = BNHIP_FLAC_BAD_METADATA;
     if (n_bytes < 4 || stream[0] != 'f' || stream[1] != 'L' || stream[2] != 'a' || stream[3] != 'C') return;
@@ -344,9 +527,10 @@ inline void flac_stream_info(const uint8_t* stream, size_t n_bytes, bnhip_flac_i
     if (!have_info) return;
     out->audio_offset = pos;
     out->status = BNHIP_FLAC_UNSUPPORTED;
-    if (out->channels != 1 || out->bits != 16 || out->rate == 0) return;
+    const bool clip = out->channels == 1 && out->bits == 16;
+    if (out->rate == 0 || !(clip || (recordings && out->channels <= 2 && (out->bits == 16 || out->bits == 24)))) return;
     if (out->total_samples == 0 || out->total_samples > 0x7FFFFFFFull) return;
-    if (out->max_block > FLACDEC_MAX_BLOCK) return;
+    if (out->max_block > (clip ? FLACDEC_MAX_BLOCK : FLACDEC_MAX_BLOCK_WIDE)) return;
     if (out->min_block != out->max_block && out->total_samples > out->max_block) return;       // more than one frame
     if (n_bytes - pos >= 2 && stream[pos] == 0xFFu && stream[pos + 1] == 0xF9u) return;         // the first frame says variable block size
     out->status = BNHIP_FLAC_OK;

@@ -67,6 +67,37 @@ def stream_info(stream):
     return _host.flac_stream_info(stream)
 
 
+def recording_info(stream):
+    """stream_info with the acceptance of the recording decoder: 1 or 2 channels, 16 or 24 bits, a fixed block size up to 8192 (mono
+    16-bit: 16384) -> host.FlacInfo."""
+    return _host.flac_recording_info(stream)
+
+
+def decode_recordings(streams, device=0, as_bytes=False):
+    """Recordings read back: a list of FLAC streams of 1 or 2 channels at 16 or 24 bits -> (recordings, results) in the input's
+    order, in one device call.  recordings[i] is an int16 (16-bit streams) or int32 (24-bit) array shaped [frames, channels] - or,
+    with as_bytes, the interleaved little-endian PCM at the stream's own depth, exactly a WAV data chunk of the same audio -, and
+    None where the stream's metadata is not accepted.  A stream whose results[i].status is host.FLAC_CORRUPT keeps the frames in
+    front of the damage; every sample that was not restored is zero."""
+    infos = [_host.flac_recording_info(s) for s in streams]
+    pcm, offsets, results = _host.flac_decode_recordings(streams, device=device)
+    out = []
+    for i, info in enumerate(infos):
+        if info.status != _host.FLAC_OK:
+            out.append(None)
+            continue
+        b = pcm[int(offsets[i]):int(offsets[i + 1])]
+        if as_bytes:
+            out.append(b.tobytes())
+        elif info.bits == 16:
+            out.append(b.copy().view("<i2").reshape(-1, int(info.channels)))
+        else:
+            t = b.reshape(-1, 3).astype(np.int32)
+            v = t[:, 0] | (t[:, 1] << 8) | (t[:, 2] << 16)
+            out.append((v - ((v & 0x800000) << 1)).astype(np.int32).reshape(-1, int(info.channels)))
+    return out, results
+
+
 def decode_clips(streams, device=0):
     """Saved clips read back: a list of FLAC streams (mono, 16 bits, fixed block size; what encode_clips writes and what a general
     encoder may write for mono int16) -> (clips, results) in the input's order, in one device call.  clips[i] is an int16 array, or

@@ -77,7 +77,9 @@ SYMBOLS = ["bnhip_init", "bnhip_shutdown", "bnhip_model_create", "bnhip_model_in
            "bnhip_level_bank_add_stream", "bnhip_level_bank_remove_stream", "bnhip_level_bank_process_pcm", "bnhip_level_bank_latest",
            "bnhip_level_bank_stats", "bnhip_level_bank_reset", "bnhip_level_bank_destroy", "bnhip_capture_bank_write_levels",
            "bnhip_detection_events_guarded", "bnhip_analyze_channels_pcm_events_guarded", "bnhip_analyze_channels_pcm_clips_guarded",
-           "bnhip_event_bank_set_guards", "bnhip_event_bank_set_daylight"]
+           "bnhip_event_bank_set_guards", "bnhip_event_bank_set_daylight", "bnhip_flac_recording_info",
+           "bnhip_flac_decode_recordings_workspace_size", "bnhip_flac_decode_recordings_device", "bnhip_flac_decode_recordings",
+           "bnhip_analyze_flac_windows", "bnhip_analyze_flac_topk", "bnhip_analyze_flac", "bnhip_analyze_flac_events"]
 
 
 class HipError(RuntimeError):
@@ -946,7 +948,8 @@ def analyze_windows(lengths, n_samples, hop, min_tail=0):
 # How a file-analysis call states its recordings: protos / entry - the ctypes prototypes and the entries' common name; x - the checked
 # bytes; table - lengths or a recordings table, and args - what the C entries take of it between pcm and hop; windows(n_samples, hop,
 # min_tail) -> (first_window, resampled_length); chosen - whether the entries answer a channel per recording
-_Form = collections.namedtuple("_Form", "protos entry x table args windows chosen")
+# extra - further arrays the entries fill behind `chosen`, answered behind it
+_Form = collections.namedtuple("_Form", "protos entry x table args windows chosen extra", defaults=((),))
 
 
 def _plain_form(raw, bit_depth, lengths):
@@ -966,6 +969,48 @@ def _channels_form(raw, recs, model_rate):
     x, recs = _channels_bytes(raw, recs)
     return _Form(_analyze_channels_protos, "bnhip_analyze_channels_pcm", x, recs, (recs.ctypes.data, recs.size, int(model_rate)),
                  lambda *a: analyze_channels_windows(recs, model_rate, *a), True)
+
+
+def _analyze_flac_protos(lib):
+    """... and of the entries for recordings given as FLAC streams (apart again, for the same reason)."""
+    _analyze_events_protos(lib)
+    head = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_int]
+    lib.bnhip_analyze_flac_windows.restype = C.c_longlong
+    lib.bnhip_analyze_flac_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.bnhip_analyze_flac_topk.argtypes = head + [C.c_void_p] * 4
+    lib.bnhip_analyze_flac.argtypes = head + [C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]
+    lib.bnhip_analyze_flac_events.argtypes = head + [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]
+    return lib
+
+
+# one stream's verdict of the FLAC entries (bnhip_flac_decode_result)
+FLAC_RESULT = np.dtype([("status", "<i4"), ("frames", "<i4"), ("fail_offset", "<u8")])
+
+
+def analyze_flac_windows(streams, model_rate, n_samples, hop, min_tail=0):
+    """bnhip_analyze_flac_windows (host only): analyze_channels_windows over the (length, rate) of FLAC streams' STREAMINFO.
+    -> (first_window int64 [n + 1], resampled_length int64 [n])."""
+    lib = _analyze_flac_protos(load_library())
+    buf, offsets = _flac_burst(streams)
+    n = len(streams)
+    first, n_out = np.zeros(n + 1, np.int64), np.zeros(n, np.int64)
+    w = lib.bnhip_analyze_flac_windows(buf.ctypes.data, offsets.ctypes.data, n, int(model_rate), int(n_samples), int(hop), int(min_tail),
+                                       first.ctypes.data, n_out.ctypes.data)
+    if w < 0:
+        _check(lib, int(w))
+    return first, n_out
+
+
+def _flac_form(streams, select, model_rate):
+    """Recordings as a list of FLAC streams; select: one choice for all (a channel index, "mix" or "auto") or one per recording."""
+    buf, offsets = _flac_burst(streams)
+    n = len(streams)
+    sel = np.array([channel_select(s) for s in (select if isinstance(select, (list, tuple, np.ndarray)) else [select] * n)], np.int32)
+    if sel.size != n:
+        raise HipError(E_INVALID, "select holds one choice per recording")
+    form = _Form(_analyze_flac_protos, "bnhip_analyze_flac", buf, sel, (offsets.ctypes.data, sel.ctypes.data, n, int(model_rate)),
+                 lambda *a: analyze_flac_windows(streams, model_rate, *a), True, (np.zeros(n, FLAC_RESULT),))
+    return form, offsets                                # (offsets: kept alive by the caller for the call)
 
 
 # How such a call is answered: (lib, kk = min(k, n_classes), first() -> first_window, room(cap) -> records to make room for) -> (the
@@ -1221,7 +1266,7 @@ class HipClassifier:
                 table.append(form.windows(self.n_samples, hop, min_tail)[0])
             return table[0]
         suffix, tail, result = answer(lib, min(k, self._n_classes), first, lambda cap: self._room(cap, first, k))
-        chosen = [np.zeros(form.table.size, np.int32)] if form.chosen else []
+        chosen = ([np.zeros(form.table.size, np.int32)] if form.chosen else []) + list(form.extra)
         _check(lib, getattr(lib, form.entry + suffix)(self._h, form.x.ctypes.data, *form.args, int(hop), int(min_tail), activation, sensitivity, k,
                                                       *tail, *[c.ctypes.data for c in chosen]))
         got = result() + tuple(chosen)
@@ -1258,6 +1303,25 @@ class HipClassifier:
     def analyze_channels_pcm(self, raw, recs, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
         """bnhip_analyze_channels_pcm: the same call, answered as detection rows, as analyze_pcm answers.  -> (rows, total, chosen)."""
         return self._analyze(_channels_form(raw, recs, model_rate), _rows_answer(threshold, cap), hop, min_tail, k, activation, sensitivity)
+
+    def analyze_flac_topk(self, streams, select, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0):
+        """bnhip_analyze_flac_topk: analyze_channels_pcm_topk with the recordings given as FLAC streams (a list of bytes; 1 or 2
+        channels, 16 or 24 bits) - rate, depth, channels and length are STREAMINFO's, the compressed bytes go up once and are decoded
+        on the device.  select: a channel index, "mix" or "auto", for all or per recording.
+        -> (conf, idx, first_window, chosen, results: a FLAC_RESULT per recording - a damaged stream does not fail the call)."""
+        form, keep = _flac_form(streams, select, model_rate)
+        return self._analyze(form, _topk_answer(), hop, min_tail, k, activation, sensitivity)
+
+    def analyze_flac(self, streams, select, model_rate, hop, min_tail=0, k=10, activation=0, sensitivity=1.0, threshold=0.0, cap=None):
+        """bnhip_analyze_flac: the same call, answered as detection rows.  -> (rows, total, chosen, results)."""
+        form, keep = _flac_form(streams, select, model_rate)
+        return self._analyze(form, _rows_answer(threshold, cap), hop, min_tail, k, activation, sensitivity)
+
+    def analyze_flac_events(self, streams, select, model_rate, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
+        """bnhip_analyze_flac_events: the same call, answered as detection events.  -> (events, chosen, results); with cap ->
+        (events[:cap], total, chosen, results)."""
+        form, keep = _flac_form(streams, select, model_rate)
+        return self._analyze(form, _events_answer(filter, cap, self._n_classes), hop, min_tail, k, activation, sensitivity)
 
     def analyze_pcm_events(self, raw, bit_depth, lengths, hop, filter, min_tail=0, k=10, activation=0, sensitivity=1.0, cap=None):
         """bnhip_analyze_pcm_events: the analyze_pcm call answered as detection events (EVENT) - the rows merged on the device under
@@ -2048,6 +2112,61 @@ def flac_stream_info(stream):
     lib.bnhip_flac_stream_info.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
     _check(lib, lib.bnhip_flac_stream_info(buf.ctypes.data, buf.size - 1, C.addressof(info)))
     return info
+
+
+def flac_recording_info(stream):
+    """bnhip_flac_recording_info: flac_stream_info with the acceptance of the recording entries (1 or 2 channels, 16 or 24 bits)."""
+    lib = load_library()
+    buf = np.frombuffer(bytes(stream) + b"\0", np.uint8)
+    info = FlacInfo()
+    lib.bnhip_flac_recording_info.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_flac_recording_info(buf.ctypes.data, buf.size - 1, C.addressof(info)))
+    return info
+
+
+def flac_decode_recordings(streams, device=0, guard=0):
+    """bnhip_flac_decode_recordings: a burst of FLAC recordings (1 or 2 channels, 16 or 24 bits) decoded in one device call
+    -> (pcm uint8: the recordings' interleaved PCM at their own depths, back to back; pcm_offsets uint64 [n + 1]; list of
+    FlacDecodeResult).  guard: that many bytes of 0xA5 are kept in front of and behind the output and checked after the call."""
+    lib = load_library()
+    buf, offsets = _flac_burst(streams)
+    n = len(streams)
+    infos = [flac_recording_info(s) for s in streams]
+    total = sum(int(i.total_samples) * int(i.channels) * (int(i.bits) // 8) for i in infos if i.status == FLAC_OK)
+    room = np.full(total + 2 * guard + 1, 0xA5, np.uint8)
+    out = room[guard:guard + total]
+    pcm_offsets = np.zeros(n + 1, np.uint64)
+    res = (FlacDecodeResult * n)()
+    lib.bnhip_flac_decode_recordings.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    _check(lib, lib.bnhip_flac_decode_recordings(device, buf.ctypes.data, n, offsets.ctypes.data, room.ctypes.data + guard, total,
+                                                 pcm_offsets.ctypes.data, C.addressof(res)))
+    if guard and not (np.all(room[:guard] == 0xA5) and np.all(room[guard + total:] == 0xA5)):
+        raise HipError(E_RUNTIME, "bnhip_flac_decode_recordings wrote outside its output")
+    return out, pcm_offsets, list(res)
+
+
+def flac_decode_recordings_workspace_size(infos, offsets):
+    """Bytes of device scratch flac_decode_recordings_device needs (infos: flac_recording_info's)."""
+    lib = load_library()
+    arr = (FlacInfo * len(infos))(*infos)
+    off = np.ascontiguousarray(offsets, np.uint64)
+    out = C.c_size_t(0)
+    lib.bnhip_flac_decode_recordings_workspace_size.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    _check(lib, lib.bnhip_flac_decode_recordings_workspace_size(len(infos), C.addressof(arr), off.ctypes.data, C.byref(out)))
+    return int(out.value)
+
+
+def flac_decode_recordings_device(d_streams_ptr, offsets, infos, d_pcm_ptr, pcm_cap_bytes, d_result_ptr, d_workspace_ptr, workspace_bytes,
+                                  device=0, hip_stream_ptr=None):
+    """Device-resident form of flac_decode_recordings: the streams, the PCM bytes (cleared on the stream first), the FlacDecodeResult
+    [n] records and the workspace are device pointers; enqueued on the stream, not synchronised."""
+    lib = load_library()
+    arr = (FlacInfo * len(infos))(*infos)
+    off = np.ascontiguousarray(offsets, np.uint64)
+    lib.bnhip_flac_decode_recordings_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                        C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(lib, lib.bnhip_flac_decode_recordings_device(device, d_streams_ptr, len(infos), off.ctypes.data, C.addressof(arr), d_pcm_ptr,
+                                                        int(pcm_cap_bytes), d_result_ptr, d_workspace_ptr, int(workspace_bytes), hip_stream_ptr))
 
 
 def flac_decode_workspace_size(infos, offsets):

@@ -361,6 +361,21 @@ def clip_spans(events, resampled_length, hop, export, model_rate=48000):
     return host.event_clip_spans(events, resampled_length, hop, export.settings(model_rate))
 
 
+def _is_flac(p):
+    return p[:4] == b"fLaC" if isinstance(p, (bytes, bytearray)) else str(p).lower().endswith(".flac")
+
+
+def _name(p):
+    return f"<{len(p)} bytes>" if isinstance(p, (bytes, bytearray)) else str(p)
+
+
+def _flac_results(paths, results):
+    """A recording the device decoder did not find whole is an error of the call, by name."""
+    for p, r in zip(paths, results):
+        if int(r["status"]) != 0:
+            raise WavError(f"{_name(p)}: damaged FLAC stream: frame {int(r['frames'])} at byte {int(r['fail_offset'])} does not decode")
+
+
 def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_seconds=0.0, top_k=10, threshold=0.0, model_rate=48000,
                   device=0, device_resample=False, channels=None, return_chosen=False, events=None, export=None, extend=None, guards=None):
     """analyze_file(device_framing=True) for a burst of recordings in ONE device call (`bnhip_analyze_pcm`): -> one list of rows per
@@ -394,7 +409,12 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
     guards (an EventGuards, with events): the reference's dog-bark and daylight filters run on the device behind the other two
     (`bnhip_analyze_channels_pcm_events_guarded`, `bnhip_analyze_channels_pcm_clips_guarded`), with or without an extend; the call
     takes the channels route.  A dropped event is left out - with keep_dropped it comes with status host.EVENT_DOG or
-    host.EVENT_DAYLIGHT - and gets no clip.  `labels` is where the dog classes are looked for."""
+    host.EVENT_DAYLIGHT - and gets no clip.  `labels` is where the dog classes are looked for.
+
+    FLAC recordings (paths ending in .flac, or bytes that start with fLaC; 1 or 2 channels, 16 or 24 bits), with channels set: the
+    compressed files go to the device as they are and are decoded there, in one `bnhip_analyze_flac` / `bnhip_analyze_flac_events`
+    call - the same rows as the same audio in WAV files.  A burst that holds a FLAC file takes FLAC files only; a file the decoder
+    finds damaged raises WavError naming it and the offset; export, extend and guards are not offered for FLAC files."""
     if model_rate <= 0:
         raise WavError(f"invalid model sample rate {model_rate}")
     if return_chosen and channels is None:
@@ -405,13 +425,24 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
         raise ValueError("extend needs events")
     if guards is not None and events is None:
         raise ValueError("guards need events")
-    recs = crecs = None
+    recs = crecs = flac = None
+    if any(_is_flac(p) for p in paths):
+        if export is not None or extend is not None or guards is not None:
+            raise ValueError("export=, extend= and guards= are not offered for FLAC recordings: decode them (flac.decode_recordings) or use WAV files")
+        if channels is None:
+            raise ValueError("FLAC recordings are analysed with channels set (a channel index, \"mix\" or \"auto\")")
+        for p in paths:
+            if not _is_flac(p):
+                raise WavError(f"a burst that holds FLAC recordings takes FLAC recordings only: {_name(p)} is not one")
+        flac = [bytes(p) if isinstance(p, (bytes, bytearray)) else open(p, "rb").read() for p in paths]
     # (the export and the extend take the files' frames: channel 0 is read there)
     select = 0 if channels is None and (export is not None or extend is not None or guards is not None) else channels
     if select is None:
         pcm = [read_wav_pcm(p) for p in paths]
         depths = {bits for _, _, bits in pcm}
-    if select is not None:
+    if flac is not None:
+        bufs, lengths = flac, None                        # (the lengths in samples are STREAMINFO's, read by the call)
+    elif select is not None:
         from . import host
         frames = [read_wav_frames(p) for p in paths]
         bufs = [raw for raw, _, _, _ in frames]
@@ -434,7 +465,7 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
                 s = host.Resampler(rate, model_rate, device=device).resample_f32(s)
             bufs.append(np.ascontiguousarray(s, np.float32).tobytes())
         lengths = [len(raw) // 4 for raw in bufs]
-    if not bufs or min(lengths) < 1:
+    if not bufs or (lengths is not None and min(lengths) < 1):
         raise WavError("a recording without samples")
     clip_seconds = classifier.n_samples / float(model_rate)
     clip_len, hop, min_tail = _framing(model_rate, clip_seconds, overlap_seconds, 1.0)
@@ -455,6 +486,10 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
                                                           k=top_k, sensitivity=sensitivity, max_clips=export.max_clips, extend=ext,
                                                           guards=gds)
             ev, chosen = clips.events, ["mix" if s < 0 else int(s) for s in clips.chosen]
+        elif flac is not None:
+            ev, sel, res = classifier.analyze_flac_events(flac, select, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity)
+            _flac_results(paths, res)
+            chosen = ["mix" if s < 0 else int(s) for s in sel]
         elif crecs is not None:
             ev, sel = classifier.analyze_channels_pcm_events(b"".join(bufs), crecs, model_rate, hop, flt, min_tail, k=top_k, sensitivity=sensitivity,
                                                              extend=ext, guards=gds)
@@ -479,7 +514,11 @@ def analyze_files(paths, classifier, labels=None, sensitivity=1.0, overlap_secon
             out[int(e["recording"])].append(row + (int(e["status"]),) if events.keep_dropped else row)
         return (out, chosen) if return_chosen else out
     chosen = None
-    if crecs is not None:
+    if flac is not None:
+        det, _, sel, res = classifier.analyze_flac(flac, select, model_rate, hop, min_tail, k=top_k, sensitivity=sensitivity, threshold=float(t32))
+        _flac_results(paths, res)
+        chosen = ["mix" if s < 0 else int(s) for s in sel]
+    elif crecs is not None:
         det, _, sel = classifier.analyze_channels_pcm(b"".join(bufs), crecs, model_rate, hop, min_tail, k=top_k, sensitivity=sensitivity,
                                                       threshold=float(t32))
         chosen = ["mix" if s < 0 else int(s) for s in sel]

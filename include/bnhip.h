@@ -1083,6 +1083,62 @@ int bnhip_flac_spectrogram_png(int device, const uint8_t* streams, int n_streams
                                int height, const double* window, double top_db, double range_db, const uint8_t* palette, uint8_t* out,
                                size_t out_cap, uint64_t* png_offsets, bnhip_flac_decode_result* result);
 
+/* FLAC recordings: what field recorders and archives write - 1 or 2 channels, 16 or 24 bits - decoded on the device by the same
+ * five launches, to interleaved PCM at each stream's own depth: int16, or packed little-endian 3-byte samples; exactly the bytes of
+ * a WAV data chunk of the same audio.  Stereo frames take the four channel assignments of RFC 9639 (independent, left/side,
+ * side/right, mid/side), the side channel read at one bit more than the depth and decorrelated in exact integers; wasted bits are
+ * per subframe; the predictor of a stream that is not mono 16-bit multiplies in 64 bits.
+ *   bnhip_flac_recording_info: bnhip_flac_stream_info with the wider acceptance (host only, every read bounded by n_bytes).  OK: 1
+ *                 or 2 channels, 16 or 24 bits, 1 .. 2^31 - 1 sample frames, a fixed block size of 16 .. 16384 (mono 16-bit) or
+ *                 16 .. 8192 (every other shape: a frame's bytes and its int32 samples share LDS).  Anything else that parses is
+ *                 BNHIP_FLAC_UNSUPPORTED - more channels, 8 / 12 / 20 / 32 bits, variable block size, a block size above the cap.
+ *   bnhip_flac_decode_recordings: host memory in and out, one call for the burst.  Recording c's bytes are pcm[pcm_offsets[c] ..
+ *                 pcm_offsets[c + 1]), total_samples x channels x bits / 8 of them for a stream whose metadata is accepted and none
+ *                 otherwise, back to back (a later recording may start at an odd byte); pcm_offsets [n_streams + 1] is filled by
+ *                 the call.  The output is cleared first: the samples of a frame that was not restored are zero.  A stream whose
+ *                 chain of frames breaks is CORRUPT at that frame and keeps the frames in front of the break; a frame whose
+ *                 decoded samples leave the depth's range makes the stream CORRUPT at that frame and leaves its own samples zero.
+ *                 Where both happen the result names the earlier frame.
+ *   ..._workspace_size / ..._device: the device-resident form, as bnhip_flac_decode_workspace_size / bnhip_flac_decode_device
+ *                 are for clips; infos are bnhip_flac_recording_info's, d_pcm is cleared on hip_stream ahead of the kernels,
+ *                 pcm_cap_bytes counts bytes.
+ * BNHIP_E_INVALID as for the clip entries.  bnhip_flac_stream_info and the clip entries answer stereo and 24-bit streams as before:
+ * BNHIP_FLAC_UNSUPPORTED.  The STREAMINFO MD5 is not verified. */
+int bnhip_flac_recording_info(const uint8_t* stream, size_t n_bytes, bnhip_flac_info* out);
+int bnhip_flac_decode_recordings_workspace_size(int n_streams, const bnhip_flac_info* infos, const uint64_t* offsets, size_t* bytes);
+int bnhip_flac_decode_recordings_device(int device, const uint8_t* d_streams, int n_streams, const uint64_t* offsets,
+                                        const bnhip_flac_info* infos, void* d_pcm, size_t pcm_cap_bytes, bnhip_flac_decode_result* d_result,
+                                        void* d_workspace, size_t workspace_bytes, void* hip_stream);
+int bnhip_flac_decode_recordings(int device, const uint8_t* streams, int n_streams, const uint64_t* offsets, void* pcm,
+                                 size_t pcm_cap_bytes, uint64_t* pcm_offsets, bnhip_flac_decode_result* result);
+
+/* File analysis of FLAC recordings: the bnhip_analyze_channels_* calls with the recordings given as FLAC streams.  The compressed
+ * bytes go to the device once; the decoder above writes each recording's interleaved PCM, at its own depth, where the channels
+ * call's copies would have put it (its 16-byte line of the raw block, or its slot on the fast path), and from there the call IS the
+ * channels call: the measurement, the slot launch, the framing, the model, the tail.
+ *   streams  Recording r is streams[offsets[r] .. offsets[r + 1]), a whole FLAC stream; offsets [n_recordings + 1] ascend.  Rate,
+ *            depth, channels and length (in frames) are what its STREAMINFO says.
+ *   select   [n_recordings]: a channel index, BNHIP_CHANNEL_MIX or BNHIP_CHANNEL_AUTO, as bnhip_channels_recording.select.
+ *   chosen   (may be NULL) [n_recordings], as the channels calls answer it.
+ *   result   [n_recordings]: what the decoder found of each stream.  A stream found damaged on the device does not fail the call:
+ *            its result is BNHIP_FLAC_CORRUPT with the frame and the offset, and its answers are those of the channels call on the
+ *            PCM that bnhip_flac_decode_recordings returns for it, zeros included.  The host decides what to do with it.
+ *   windows  Host only: bnhip_analyze_channels_windows over the (length, rate) of the streams.
+ * BNHIP_E_INVALID (nothing written, no device work, the handle stays usable), naming the recording: a stream whose
+ * bnhip_flac_recording_info status is not BNHIP_FLAC_OK, and everything the channels call refuses of the same recordings. */
+long long bnhip_analyze_flac_windows(const uint8_t* streams, const uint64_t* offsets, int n_recordings, int model_rate, int n_samples,
+                                     int hop, int64_t min_tail, int64_t* first_window, int64_t* resampled_length);
+int bnhip_analyze_flac_topk(bnhip_model* m, const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings,
+                            int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k, float* out_conf,
+                            int32_t* out_idx, int32_t* chosen, bnhip_flac_decode_result* result);
+int bnhip_analyze_flac(bnhip_model* m, const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings,
+                       int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k, float threshold,
+                       bnhip_detection* out, size_t cap, size_t* n_out, int32_t* chosen, bnhip_flac_decode_result* result);
+int bnhip_analyze_flac_events(bnhip_model* m, const uint8_t* streams, const uint64_t* offsets, const int32_t* select, int n_recordings,
+                              int model_rate, int hop, int64_t min_tail, int activation, double sensitivity, int k,
+                              const bnhip_event_filter* filter, bnhip_event* out, size_t cap, size_t* n_out, int32_t* chosen,
+                              bnhip_flac_decode_result* result);
+
 /* Processed audio: the review UI's "re-listen with noise reduction / normalisation / gain" (ProcessAudioByID and
  * ProcessedSpectrogramByID, internal/api/v2/media/media.go:1200-1447), whose filter chain
  * internal/audiocore/ffmpeg/process.go:164-251 builds for an FFmpeg child process per clip in the fixed order
